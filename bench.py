@@ -442,6 +442,26 @@ def trained_spectrum_batch(B, T):
 
 
 
+DUMP_UTTERANCES = 8   # utterances of the batch whose waveforms and linear spectrograms --dump-outputs writes (seeded choice)
+
+
+def dump_outputs(out_dir, wav_host, lin_out, ali_out):
+    """What the last timed step handed its caller, for comparing two builds output for output: alignments (n_steps, B, Ts)
+    whole (7.7 MB); waveforms (8, 274725) and linear spectrograms (8, 1000, 1025) of the same fixed, seeded choice of 8
+    utterances (the whole batch would be 70 + 262 MB).  ``utterances.npy`` holds that choice.  Float32, 49 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    pick = np.sort(np.random.default_rng(0).choice(wav_host.shape[0], min(DUMP_UTTERANCES, wav_host.shape[0]), replace=False))
+    arrays = {'utterances': pick.astype(np.float32), 'wav': wav_host[pick]}
+    if lin_out is not None:
+        arrays['linear'] = lin_out.to_host()[pick]
+    if ali_out is not None:
+        arrays['alignments'] = ali_out.to_host()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    print('bench: outputs of the last timed step in {} ({:.1f} MB)'.format(
+        out_dir, sum(a.size * 4 for a in arrays.values()) / 2 ** 20), file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -463,11 +483,16 @@ def main():
                          'waveforms out, upload and download inside the timed region) and report facade_ms_per_step')
     ap.add_argument('--no-aux-outputs', action='store_true', help='A/B: do not write the linear spectrograms and alignments')
     ap.add_argument('--dist-selftest', action='store_true', help='rehearse the N > 1 launch path without GPU work')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step returned (rank 0's shard) as DIR/<name>.npy, float32, at most 64 MB: "
+                         'the alignments whole, the waveforms and linear spectrograms of a fixed, seeded sample of utterances')
     ap.add_argument('--cpu-baseline-only', action='store_true',
                     help='print the cpu_baseline object and exit (no GPU call is made: how the bench runs it, in a child)')
     ap.add_argument('--cpu-baseline-utts', type=int, default=6, help='with --cpu-baseline-only: utterances of the sample (tests: 1)')
     ap.add_argument('--cpu-baseline-repeats', type=int, default=5, help='with --cpu-baseline-only: timed repeats (tests: 1)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # a bench that stops answering says where: every 4 minutes without an exit, all thread stacks on stderr
     import faulthandler
@@ -642,6 +667,8 @@ def main():
         launches[st] = n // max(1, args.steps)
     w = wav.to_host()
     assert np.isfinite(w).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w, lin_out, ali_out)
     # the dominant kernel alone (no overlapping stream), for reference next to the in-pipeline figure
     eng.synchronize()
     eng.profile_reset()

@@ -249,9 +249,9 @@ int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_
 
 /* The same call for a caller that lives in HOST memory -- what the reference's inference() / serve() are
  * (tacotron/inference.py:75-101,185-200, serve.py:89-126: host id arrays in, host waveforms out) -- without giving up the
- * call pipeline: the ids are copied to a pinned staging buffer of the handle and uploaded on a copy stream, the
- * call is enqueued behind that upload (the initial phases are drawn on the device from p->seed, as the reference
- * draws them with np.random), and the waveforms are downloaded into pinned memory of the handle on a second copy
+ * call pipeline: the ids are copied to a pinned staging buffer of the handle and uploaded on the stream that runs
+ * the call's encoder, in front of it (the initial phases are drawn on the device from p->seed, as the reference
+ * draws them with np.random), and the waveforms are downloaded into pinned memory of the handle on a copy
  * stream as soon as they are complete.  The call returns at once with a ticket; tts_wait_host blocks until that
  * call's waveforms have arrived and hands out the pinned buffer, [B * hop*(T-1)] floats, valid until the THIRD
  * tts_synthesize_host call after the one that produced it (three buffer sets rotate: the device holds three calls at

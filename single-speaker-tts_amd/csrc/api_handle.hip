@@ -377,7 +377,6 @@ int sync_all(tts_handle_t h) {
     if (h->front && h->front != h->stream) HIPCHK(h, hipStreamSynchronize(h->front));
     if (h->aux) HIPCHK(h, hipStreamSynchronize(h->aux));
     if (h->encs) HIPCHK(h, hipStreamSynchronize(h->encs));
-    if (h->hio.in) HIPCHK(h, hipStreamSynchronize(h->hio.in));
     if (h->hio.out) HIPCHK(h, hipStreamSynchronize(h->hio.out));
     return check_status(h);
 }
@@ -676,7 +675,6 @@ int tts_destroy(tts_handle_t h) {
         if (h->hio.ev_d2h[i]) hipEventDestroy(h->hio.ev_d2h[i]);
     }
     if (h->hio.status_pinned) hipHostFree(h->hio.status_pinned);
-    if (h->hio.in) hipStreamDestroy(h->hio.in);
     if (h->hio.out) hipStreamDestroy(h->hio.out);
     if (h->ev_aux) hipEventDestroy(h->ev_aux);
     if (h->ev_front_done) hipEventDestroy(h->ev_front_done);

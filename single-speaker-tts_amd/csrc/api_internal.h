@@ -98,7 +98,7 @@ struct tts_handle_s {
     // resident): lowest priority was 0.15 ms per step better while the main stream was the longer one and 0.1 ms worse once
     // Griffin-Lim's run cut had given it slack; the main stream's own priority is as good as the greatest in a device-resident
     // loop but HALVES the throughput of tts_synthesize_host -- streams of one priority share a few hardware queues, and with
-    // the two copy streams of the host path the front stream lands on the main stream's queue.
+    // the copy streams of the host path the front stream lands on the main stream's queue.
     hipStream_t front = nullptr;
     // The encoder of a pipelined call runs on a stream of its own (round 4): it depends on the ids only, so it need not
     // queue behind the previous call's decoder on the front stream -- it runs as soon as the decoder of the call TWO back
@@ -176,9 +176,10 @@ struct tts_handle_s {
 
     // host-memory calls (tts_synthesize_host): pinned staging of the ids, device copies, pinned waveform buffers and the
     // device buffers they are copied from, one set per call in flight (ticket mod 3: the device pipeline holds three calls
-    // at once since round 4 -- encoder of k + 2, decoder of k + 1, Griffin-Lim of k); two copy streams
+    // at once since round 4 -- encoder of k + 2, decoder of k + 1, Griffin-Lim of k); the ids go up on the stream that
+    // runs the call's encoder, the outputs come down on one copy stream
     struct {
-        hipStream_t in = nullptr, out = nullptr;
+        hipStream_t out = nullptr;
         int32_t* ids_pinned[3] = {nullptr, nullptr, nullptr};
         int32_t* ids_dev[3] = {nullptr, nullptr, nullptr};
         size_t ids_bytes = 0;
@@ -210,8 +211,15 @@ struct tts_handle_s {
     bool defer_projection = false, has_pending_proj = false;
     int defer_parity = 0;
     GemmGroup pending_proj;
-    hipEvent_t input_event = nullptr;   // set around a tts_synthesize call: its first kernel waits for this event
-    hipEvent_t enc_done_event = nullptr;   // ... and this one is recorded behind its encoder
+    // set around a tts_synthesize call (tts_synthesize_host): the ids' upload, enqueued on the encoder's stream in front of
+    // the encoder (behind `wait`, recorded in `done`), and an event recorded behind the encoder
+    struct {
+        int32_t* dst = nullptr;
+        const int32_t* src = nullptr;
+        size_t bytes = 0;
+        hipEvent_t wait = nullptr, done = nullptr;
+    } input_upload;
+    hipEvent_t enc_done_event = nullptr;
 
     std::vector<ManifestEntry> manifest;
     std::map<std::string, std::vector<float>> host_w;

@@ -220,7 +220,12 @@ int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_
         }
     }
     if (pipelined) h->last_enc_ahead = enc_ahead_cfg ? 1 : 0;
-    if (h->input_event) HIPCHK(h, hipStreamWaitEvent(h->stream, h->input_event, 0));   // (tts_synthesize_host: the ids' upload)
+    if (h->input_upload.bytes) {   // (tts_synthesize_host: the ids' upload, in front of the encoder on its own stream)
+        const auto& up = h->input_upload;
+        if (up.wait) HIPCHK(h, hipStreamWaitEvent(h->stream, up.wait, 0));
+        HIPCHK(h, hipMemcpyAsync(up.dst, up.src, up.bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(up.done, h->stream));
+    }
     rc = tts_encoder_forward(h, ids, B, Ts, memory);
     if (!rc && h->enc_done_event) HIPCHK(h, hipEventRecord(h->enc_done_event, h->stream));
     if (!rc && pipelined && keys_ahead) {
@@ -325,13 +330,14 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     const bool want_lin = (sp->host_outputs & TTS_HOST_LINEAR) != 0, want_ali = (sp->host_outputs & TTS_HOST_ALIGNMENTS) != 0;
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;
-    if (!io.in) {
-        // The copy streams get the LOWEST priority: streams of one priority share a few hardware queues in creation order
-        // (whatever else the process has created counts), and a copy stream that lands on the main stream's queue holds the
-        // main stream's kernels behind its event waits and its 70 MB download.  Nothing else in the library uses this level.
+    if (!io.out) {
+        // The copy stream gets the LOWEST priority: streams of one priority share a few hardware queues in creation order
+        // (whatever else the process has created counts; GPU_MAX_HW_QUEUES per priority, as few as 2), and a copy stream that
+        // lands on the main stream's queue holds the main stream's kernels behind its event waits and its 70 MB download.
+        // The only other stream at this level is the encoder's; the ids' upload rides on that one (in tts_synthesize), since
+        // a second copy stream there would share a queue with it and park the encoder of call k + 2 behind the download of k.
         int prio_least = 0, prio_greatest = 0;
         HIPCHK(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-        HIPCHK(h, hipStreamCreateWithPriority(&io.in, hipStreamNonBlocking, prio_least));
         HIPCHK(h, hipStreamCreateWithPriority(&io.out, hipStreamNonBlocking, prio_least));
         for (int i = 0; i < 3; ++i) {
             HIPCHK(h, hipEventCreateWithFlags(&io.ev_h2d[i], hipEventDisableTiming));
@@ -345,7 +351,6 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
         n_ali * sizeof(float) > io.ali_bytes) {
         // growing the buffers: nothing of an earlier call may be in flight
         if ((rc = sync_all(h))) return rc;
-        HIPCHK(h, hipStreamSynchronize(io.in));
         HIPCHK(h, hipStreamSynchronize(io.out));
         for (int i = 0; i < 3; ++i) {
             if (ids_bytes > io.ids_bytes) {
@@ -384,17 +389,19 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     // the pinned staging buffer and the device copy of the ids were last used by the call three back
     if (io.d2h_pending[par]) HIPCHK(h, hipEventSynchronize(io.ev_h2d[par]));
     std::memcpy(io.ids_pinned[par], ids_host, ids_bytes);
-    if (io.enc_pending[par]) HIPCHK(h, hipStreamWaitEvent(io.in, io.ev_enc[par], 0));
-    HIPCHK(h, hipMemcpyAsync(io.ids_dev[par], io.ids_pinned[par], ids_bytes, hipMemcpyHostToDevice, io.in));
-    HIPCHK(h, hipEventRecord(io.ev_h2d[par], io.in));
     // the waveform buffer of this set is free once the download of the call three back has left it
     if (io.d2h_pending[par]) HIPCHK(h, hipStreamWaitEvent(h->stream, io.ev_d2h[par], 0));
-    h->input_event = io.ev_h2d[par];
+    // the device copy of the ids is free once the encoder of the call three back has read it (the same stream as a rule)
+    h->input_upload.dst = io.ids_dev[par];
+    h->input_upload.src = io.ids_pinned[par];
+    h->input_upload.bytes = ids_bytes;
+    h->input_upload.wait = io.enc_pending[par] ? io.ev_enc[par] : nullptr;
+    h->input_upload.done = io.ev_h2d[par];
     h->enc_done_event = io.ev_enc[par];
     // (the optional outputs of this set were last read by the download of the call three back: same event as the waveforms)
     rc = tts_synthesize(h, io.ids_dev[par], B, Ts, sp, nullptr, io.wav_dev[par], nullptr, want_ali ? io.ali_dev[par] : nullptr,
                         want_lin ? io.lin_dev[par] : nullptr);
-    h->input_event = nullptr;
+    h->input_upload = {};
     h->enc_done_event = nullptr;
     if (rc) return rc;
     io.enc_pending[par] = true;

@@ -59,3 +59,31 @@ def test_bench_under_torchrun_one_rccl_rank():
     assert rec['weight_broadcast_ms_steady'] > 0 and rec['communicator_setup_ms'] > 0
     assert rec['rank_ms_per_step'] and len(rec['rank_devices']) == 1 and rec['straggler_rank'] == 0
     assert rec['value'] > 0 and rec['steps'] == 3
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: what the last timed step returned, float32, at most 64 MB, the same from run to run
+    with the same arguments (same inputs, same seeds) -- what lets two builds be compared output for output."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / 'run{}'.format(run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
+                              '--dump-outputs', str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert out.returncode == 0, out.stderr.decode()[-3000:]
+        rec = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith('{')][-1])
+        assert rec['steps'] == 2
+        dumps.append({p.stem: np.load(str(p)) for p in d.glob('*.npy')})
+    a = dumps[0]
+    assert set(a) == {'utterances', 'wav', 'linear', 'alignments'}
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    n = a['utterances'].shape[0]
+    assert a['wav'].shape == (n, 275 * 999) and a['linear'].shape == (n, 1000, 1025) and a['alignments'].shape == (200, 64, 150)
+    assert a['alignments'].min() >= 0.0 and a['alignments'].max() <= 1.0 + 1e-6   # attention weights of every decoder step
+    assert 0.99 < float(np.abs(a['wav']).max()) <= 1.0 + 1e-6            # peak-normalised waveforms
+    for k in a:
+        assert np.array_equal(a[k], dumps[1][k]), k

@@ -183,6 +183,21 @@ int tts_decoder_forward(tts_handle_t h, const float* memory, int B, int Ts, int 
  * mel [B*T*n_mels] -> output_linear_spec [B*T*(1+n_fft/2)]. */
 int tts_postnet_forward(tts_handle_t h, const float* mel, int B, int T, float* linear);
 
+/* ---- evaluation ------------------------------------------------------------------------- */
+/* Tacotron in Mode.EVAL (tacotron/model.py:299-306, 432-442): encoder, free-running decoder for n_steps = T_red,
+ * post-net + final Dense, then the three L1 losses against zero-padded targets.
+ * mel_target [B * n_steps*r * n_mels], linear_target [B * n_steps*r * F] (device) ->
+ * losses [3] = {loss, loss_decoder, loss_post_processing} (device, float);
+ * optional (NULL to skip): l1_sums [B][2] (device, double), mel, alignments, linear as in tts_synthesize.
+ * The stages are those of tts_encoder_forward / tts_decoder_forward (the stand-alone decoder choice,
+ * tts_decoder_kernel_choice(h, B, Ts, 0)) / tts_postnet_forward: the spectrograms are theirs bit for bit.  The means
+ * are float64 sums in a fixed order (per-utterance sums l1_sums[u] = {sum |mel_t - mel|, sum |lin_t - lin|}) rounded
+ * once to float32, loss = loss_decoder + loss_post_processing in float32; the bits depend neither on the grid nor on
+ * earlier calls.  NaN / Inf in a target or output give a NaN / Inf loss.  Float buffers must be 4-byte aligned. */
+int tts_evaluate(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps,
+                 const float* mel_target, const float* linear_target, float* losses,
+                 double* l1_sums, float* mel, float* alignments, float* linear);
+
 /* ---- spectrogram de-normalisation ------------------------------------------------------ */
 /* inference() post-step + synthesize() power (tacotron/inference.py:93-101,175;
  * audio/conversion.py:81-102, 32-53): per utterance transpose to (F,T),
@@ -270,7 +285,7 @@ int tts_wait_host_outputs(tts_handle_t h, int ticket, const float** linear_host,
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
- * (launches of tts_debug_gemm).
+ * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

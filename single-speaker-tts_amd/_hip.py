@@ -80,6 +80,8 @@ _PROTOTYPES = {
     'tts_encoder_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'tts_decoder_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'tts_postnet_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'tts_evaluate': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p]),
     'tts_denorm_power': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p]),
     'tts_griffin_lim': (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_void_p, c_void_p]),
@@ -355,6 +357,38 @@ class Engine(object):
         lin = out if out is not None else self.empty((B, T, 1 + self.cfg.n_fft // 2))
         self._check(self.lib.tts_postnet_forward(self.handle, p_mel, B, T, lin.data_ptr()))
         return lin
+
+    def evaluate(self, ids, mel_target, linear_target, want_sums=False, want_mel=False, want_alignments=False,
+                 want_linear=False, losses=None):
+        """Mode.EVAL on one batch (tts_evaluate): ids int32 (B, T_sent), targets as the reference feeds them --
+        mel (B, T_red, r*n_mels) or (B, T, n_mels), linear (B, T_red, r*F) or (B, T, F), zero-padded -- host arrays or
+        device buffers.  The decoder free-runs for n_steps = T_red.  Returns a dict with the device arrays ``losses``
+        (3,) = [loss, loss_decoder, loss_post_processing] and, where asked for, ``l1_sums`` (B, 2) float64, ``mel``
+        (B, T, n_mels), ``alignments`` (T_red, B, T_sent), ``linear`` (B, T, F)."""
+        B, Ts = ids.shape
+        r, nm, F = self.cfg.reduction, self.cfg.n_mels, 1 + self.cfg.n_fft // 2
+        mel_sz, lin_sz = int(np.prod(mel_target.shape)), int(np.prod(linear_target.shape))
+        if mel_target.shape[0] != B or mel_sz % (B * r * nm):
+            raise ValueError('evaluate: mel target of shape {} for B = {}, r * n_mels = {}'.format(mel_target.shape, B, r * nm))
+        n_steps = mel_sz // (B * r * nm)
+        T = n_steps * r
+        if linear_target.shape[0] != B or lin_sz != B * T * F:
+            raise ValueError('evaluate: linear target of shape {}, ({}, {}, {}) floats needed'.format(
+                linear_target.shape, B, T, F))
+        self._check_ids(ids)
+        p_ids, _k1 = self._in(ids, np.int32, 'ids')
+        p_mel, _k2 = self._in(mel_target, np.float32, 'eval_mel_target')
+        p_lin, _k3 = self._in(linear_target, np.float32, 'eval_linear_target')
+        out = dict(losses=losses if losses is not None else self.empty((3,)))
+        out['l1_sums'] = self.empty((B, 2), np.float64) if want_sums else None
+        out['mel'] = self.empty((B, T, nm)) if want_mel else None
+        out['alignments'] = self.empty((n_steps, B, Ts)) if want_alignments else None
+        out['linear'] = self.empty((B, T, F)) if want_linear else None
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        self._check(self.lib.tts_evaluate(self.handle, p_ids, B, Ts, n_steps, p_mel, p_lin, out['losses'].data_ptr(),
+                                          ptr(out['l1_sums']), ptr(out['mel']), ptr(out['alignments']), ptr(out['linear'])))
+        out['n_steps'] = n_steps
+        return out
 
     def denorm_power(self, linear, ref_db, max_db, power, out=None):
         B, T, F = linear.shape

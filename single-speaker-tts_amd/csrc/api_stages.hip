@@ -919,6 +919,56 @@ int tts_postnet_forward(tts_handle_t h, const float* mel, int B, int T, float* l
 }
 
 
+// Mode.EVAL (reference tacotron/model.py:299-306, 432-442): the stand-alone encoder, free-running decoder and post-net of
+// tts_encoder_forward / tts_decoder_forward / tts_postnet_forward (the same kernels, so the same bits), then the L1 losses
+// against the targets (eval_loss.hip).  Spectrograms the caller does not ask for go to workspaces of the handle.
+int tts_evaluate(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps, const float* mel_target,
+                 const float* linear_target, float* losses, double* l1_sums, float* mel, float* alignments, float* linear) {
+    DeviceScope dev_scope(h);
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!ids || !mel_target || !linear_target || !losses || B < 1 || Ts < 1 || n_steps < 1)
+        return fail(h, TTS_ERR_INVALID, "evaluate: bad arguments (ids, both targets and losses are required; B, Ts, n_steps >= 1)");
+    const tts_config_t& c = h->cfg;
+    const int T = n_steps * c.reduction, F = 1 + c.n_fft / 2;
+    if ((long long)n_steps * c.reduction > (1 << 24) || (double)B * T * F >= 9.0e18)
+        return fail(h, TTS_ERR_INVALID, "evaluate: sizes out of range");
+    for (const void* p : {(const void*)mel_target, (const void*)linear_target, (const void*)mel, (const void*)linear,
+                          (const void*)losses})
+        if ((uintptr_t)p & 3) return fail(h, TTS_ERR_INVALID, "evaluate: float buffers must be 4-byte aligned");
+    if ((uintptr_t)l1_sums & 7) return fail(h, TTS_ERR_INVALID, "evaluate: l1_sums must be 8-byte aligned");
+    const size_t n_mel = (size_t)B * T * c.n_mels, n_lin = (size_t)B * T * F;
+    WS(h, "eval.memory", float, (size_t)B * Ts * 2 * c.n_gru_units, memory);
+    float* mel_o = mel;
+    if (!mel_o) {
+        WS(h, "eval.mel", float, n_mel, mel_ws);
+        mel_o = mel_ws;
+    }
+    float* lin_o = linear;
+    if (!lin_o) {
+        WS(h, "eval.linear", float, n_lin, lin_ws);
+        lin_o = lin_ws;
+    }
+    WS(h, "eval.partial", double, eval_loss_partial_count(B, T, c.n_mels, F), partial);
+    double* sums = l1_sums;
+    if (!sums) {
+        WS(h, "eval.sums", double, (size_t)2 * B, sums_ws);
+        sums = sums_ws;
+    }
+    if ((rc = standalone_begin(h))) return rc;
+    if ((rc = encoder_impl(h, ids, B, Ts, memory))) return rc;
+    if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel_o, alignments))) return rc;
+    if ((rc = postnet_impl(h, mel_o, B, T, lin_o, nullptr, 0.f, 0.f, 1.f))) return rc;
+    {
+        ProfScope ps(h, ST_EVAL_LOSS, 2);
+        const int blocks = 8 * std::max(1, h->n_cus_dev);   // memory-bound: 8 workgroups of 256 threads per compute unit
+        HIPCHK(h, launch_eval_loss(h->stream, mel_target, mel_o, linear_target, lin_o, B, T, c.n_mels, F, blocks, partial, sums,
+                                   losses));
+    }
+    return standalone_end(h);
+}
+
+
 int tts_denorm_power(tts_handle_t h, const float* linear, int B, int T, int F, float ref_db, float max_db, float power,
                      float* mag) {
     DeviceScope dev_scope(h);

@@ -121,6 +121,15 @@ hipError_t launch_cbhg_tail(hipStream_t s, const CbhgTailParams& p);
 hipError_t cu_hold_configure();   // per device, before the first launch_cu_hold
 hipError_t launch_cu_hold(hipStream_t s, int n_cus, const int* flag, double timeout_ms, int lds_kb = 64);
 
+// ----------------------------------------------------------------------------- evaluation losses (eval_loss.hip)
+// Mode.EVAL L1 losses (reference tacotron/model.py:432-442): targets / outputs [B][T][n_mels] and [B][T][F], all 4-byte aligned.
+// sums [B][2] (double) = per-utterance L1 sums {mel, linear}; losses [3] = {loss, loss_decoder, loss_post_processing}.
+// partial: eval_loss_partial_count() doubles.  Fixed summation order, float64, no atomics: the bits depend on the shapes and
+// on the target's address modulo 16 bytes, never on `max_blocks` (the grid) or on earlier launches.
+size_t eval_loss_partial_count(int B, int T, int n_mels, int F);
+hipError_t launch_eval_loss(hipStream_t s, const float* mel_t, const float* mel_o, const float* lin_t, const float* lin_o, int B,
+                            int T, int n_mels, int F, int max_blocks, double* partial, double* sums, float* losses);
+
 // ----------------------------------------------------------------------------- helpers
 struct DevBuf {
     void* p = nullptr;

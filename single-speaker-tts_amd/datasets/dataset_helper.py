@@ -3,11 +3,15 @@
 Only what ``tacotron/inference.py`` calls is reproduced: ``process_sentences`` (:146-241) with its
 helpers ``sent2idx`` (:51-68), ``idx2sent`` (:70-87), ``replace_abbreviations`` (:127-144),
 ``utf8_to_ascii`` (:89-109), ``update_char_dict`` (:111-125) and the static
-``apply_reduction_padding`` (:357-401).  Corpus loading / feature pre-computation are out of scope.
+``apply_reduction_padding`` (:357-401); for evaluation, the feature cache reader
+``cache_precalculated_features`` (:285-305) over the ``<wav stem>.npz`` files that ``pre_compute_features``
+(:326-356) writes.  Computing features from ``.wav`` files (librosa) is out of scope.
 
 Quirks kept on purpose: abbreviations are applied with ``str.replace`` in dict order (so
 ``'.' -> ''`` must come last), characters outside the vocabulary raise ``KeyError``, the EOS id is
 appended, and every id sequence is returned as the raw bytes of an int32 array."""
+import os
+
 import numpy as np
 
 
@@ -72,6 +76,40 @@ class DatasetHelper(object):
             id_sequences.append(np.array(idx, dtype=np.int32).tobytes())
             sequence_lengths.append(len(idx))
         return id_sequences, sequence_lengths
+
+    @staticmethod
+    def feature_path(wav_path):
+        """``<path>/<stem>.wav`` -> ``<path>/<stem>.npz`` (reference dataset_helper.py:348-351)."""
+        if isinstance(wav_path, bytes):
+            wav_path = wav_path.decode()
+        return '{}.npz'.format(os.path.splitext(wav_path)[0])
+
+    @staticmethod
+    def load_features(wav_path):
+        """Pre-computed features of one recording: (mel_mag_db (T_red, n_mels*r), linear_mag_db (T_red, F*r)) as
+        float32, already reduction-padded (keys ``mel_mag_db`` / ``linear_mag_db``, reference :354-356).  A missing
+        ``.npz`` raises FileNotFoundError naming it."""
+        path = DatasetHelper.feature_path(wav_path)
+        if not os.path.isfile(path):
+            raise FileNotFoundError('pre-computed features {} not found (written by the reference\'s '
+                                    'DatasetHelper.pre_compute_features; computing them from the .wav is not '
+                                    'part of this package)'.format(path))
+        with np.load(path) as z:
+            return (np.asarray(z['mel_mag_db'], dtype=np.float32), np.asarray(z['linear_mag_db'], dtype=np.float32))
+
+    @staticmethod
+    def cache_precalculated_features(wav_paths):
+        """reference :285-305: {wav path without extension: {'mel_mag_db', 'linear_mag_db'}} held in RAM."""
+        cache = dict()
+        for wav_path in wav_paths:
+            mel, lin = DatasetHelper.load_features(wav_path)
+            cache[os.path.splitext(wav_path)[0]] = dict(mel_mag_db=mel, linear_mag_db=lin)
+        return cache
+
+    def load_audio(self, file_path):
+        """Evaluation targets of one recording, as the reference's ``load_audio`` returns them (lj_speech.py:106-156):
+        read here from the pre-computed ``.npz`` next to the ``.wav``."""
+        return self.load_features(file_path)
 
     @staticmethod
     def apply_reduction_padding(mel_mag_db, linear_mag_db, reduction_factor):

@@ -1,6 +1,10 @@
-"""LJ-Speech text helper: dB constants and the abbreviation table of reference
-datasets/lj_speech.py (:20-29, :37-60).  Audio loading (``load_audio`` :106-156) is the training
-data path and out of scope; the analysis kernels it would use are in ``audio.features``."""
+"""LJ-Speech helper: dB constants, the abbreviation table and the corpus listing reader of reference
+datasets/lj_speech.py (:20-29, :37-60, :62-103).  Audio features come from the pre-computed ``.npz``
+files (``DatasetHelper.load_features``); computing them from the ``.wav`` (``load_audio`` :106-156,
+librosa) is out of scope -- the analysis kernels it would use are in ``audio.features``."""
+import csv
+import os
+
 from .dataset_helper import DatasetHelper
 
 
@@ -21,3 +25,25 @@ class LJSpeechDatasetHelper(DatasetHelper):
             'capt.': 'captain', 'esq.': 'esquire', 'ltd.': 'limited', 'col.': 'colonel', 'ft.': 'fort',
             '[': '', ']': '', '.': '',
         }
+
+    def load(self, max_samples=None, min_len=None, max_len=None, listing_file_name='metadata.csv'):
+        """reference :62-103: ``<dataset>/<listing>`` rows ``id|transcript|normalised transcript`` ->
+        (id_sequences (bytes of int32 arrays), sequence_lengths incl. EOS, ``<dataset>/wavs/<id>.wav`` paths).
+        Sentences (ASCII, before lower-casing) shorter than ``min_len`` or longer than ``max_len`` are skipped;
+        reading stops after ``max_samples`` kept rows."""
+        data_file = os.path.join(self._dataset_folder, listing_file_name)
+        wav_folder = os.path.join(self._dataset_folder, 'wavs')
+        file_paths, sentences = [], []
+        with open(data_file, 'r') as csv_file:
+            for file_id, _, normalized_sentence in csv.reader(csv_file, delimiter='|', quotechar='|'):
+                sentence = self.utf8_to_ascii(normalized_sentence)
+                if min_len is not None and len(sentence) < min_len:
+                    continue
+                if max_len is not None and len(sentence) > max_len:
+                    continue
+                sentences.append(sentence)
+                file_paths.append('{}.wav'.format(os.path.join(wav_folder, file_id)))
+                if max_samples is not None and len(sentences) == max_samples:
+                    break
+        id_sentences, sentence_lengths = self.process_sentences(sentences)
+        return id_sentences, sentence_lengths, file_paths

@@ -1,0 +1,218 @@
+"""Drop-in mirror of the reference's ``tacotron.evaluate`` (tacotron/evaluate.py): the eval loss of a checkpoint.
+
+``batched_placeholders`` (:18-151) buckets the evaluation set by sentence length and pads every batch,
+``evaluate`` (:153-257) runs ``Tacotron(..., Mode.EVAL)`` over one epoch and averages the three losses
+unweighted over the batches, ``collect_checkpoint_paths`` (:284-326) lists a run's checkpoints and
+:func:`main` is the reference's ``__main__`` (:329-364): the latest checkpoint, or with ``--all`` every one.
+
+Batch order.  The reference fills its buckets from TensorFlow input queues, whose order is not reproducible.
+Here the order is fixed: the buckets in ascending order of length, within a bucket the utterances in dataset
+order, a batch whenever a bucket holds ``batch_size`` utterances; with ``allow_smaller_batches`` the leftovers of
+the buckets then follow, in ascending bucket order, as smaller batches (without it they are dropped, as
+TensorFlow drops them).  Because the losses are averaged per batch, the batch composition -- not the order --
+decides the result.
+
+TensorBoard events are not written: every evaluated checkpoint appends one JSON line with the reference's
+summary tags (``loss/loss``, ``loss/loss_decoder``, ``loss/loss_post_processing``) and its global step to
+``<checkpoint_dir>/<checkpoint_save_run>/eval_summaries.jsonl``.
+"""
+import bisect
+import json
+import os
+
+import numpy as np
+
+from .model import Mode, Tacotron
+from .params import dataset_params, evaluation_params, model_params
+
+SUMMARY_FILE = 'eval_summaries.jsonl'
+
+
+def bucket_boundaries(sentence_lengths, n_buckets):
+    """reference :80-99: the first length of every ``n // n_buckets``-th slice of the sorted lengths, without the
+    first and last one, de-duplicated.  AssertionError when fewer than ``n_buckets`` entries were loaded."""
+    n_samples = len(sentence_lengths)
+    if n_samples < n_buckets:
+        raise AssertionError('The number of entries loaded is smaller than the number of '
+                             'buckets to be created. Automatic calculation of the bucket '
+                             'boundaries is not possible.')
+    bucket_step = n_samples // n_buckets
+    boundaries = np.sort(np.asarray(sentence_lengths))[::bucket_step][1:-1].tolist()
+    return sorted(set(boundaries))
+
+
+def bucket_batches(sentence_lengths, boundaries, batch_size, allow_smaller_batches=True):
+    """Index lists of the batches in the documented order (module docstring).  An utterance of length L goes to bucket
+    ``bisect_right(boundaries, L)``: buckets [-inf, b0), [b0, b1), ..., [b_last, inf) as in TensorFlow's
+    bucket_by_sequence_length."""
+    buckets = [[] for _ in range(len(boundaries) + 1)]
+    for i, length in enumerate(sentence_lengths):
+        buckets[bisect.bisect_right(boundaries, int(length))].append(i)
+    full, rest = [], []
+    for b in buckets:
+        n_full = len(b) // batch_size
+        full += [b[k * batch_size:(k + 1) * batch_size] for k in range(n_full)]
+        if len(b) % batch_size:
+            rest.append(b[n_full * batch_size:])
+    return full + (rest if allow_smaller_batches else [])
+
+
+def pad_batch(sentences, sentence_lengths, features):
+    """dynamic_pad: ids padded with the <PAD> id 0, spectrograms with zero frames to the batch maximum.
+    sentences: list of int32 arrays; features: list of (mel (T_red, n_mels*r), linear (T_red, F*r))."""
+    B = len(sentences)
+    Ts = max(len(s) for s in sentences)
+    T_red = max(m.shape[0] for m, _ in features)
+    ids = np.zeros((B, Ts), np.int32)
+    mel = np.zeros((B, T_red, features[0][0].shape[1]), np.float32)
+    lin = np.zeros((B, T_red, features[0][1].shape[1]), np.float32)
+    frames = np.zeros(B, np.int32)
+    for b, (s, (m, l)) in enumerate(zip(sentences, features)):
+        ids[b, :len(s)] = s
+        mel[b, :m.shape[0]] = m
+        lin[b, :l.shape[0]] = l
+        frames[b] = m.shape[0]
+    return {
+        'ph_sentences': ids,
+        'ph_sentence_length': np.asarray(sentence_lengths, np.int32),
+        'ph_mel_specs': mel,
+        'ph_lin_specs': lin,
+        'ph_time_frames': frames,
+    }
+
+
+def batched_placeholders(dataset, max_samples, batch_size, n_buckets=None, allow_smaller_batches=None, verbose=True):
+    """reference :18-151: yields one padded feed dict per batch (keys ``ph_sentences`` (B, T_sent) int32,
+    ``ph_sentence_length`` (B,), ``ph_mel_specs`` (B, T_red, n_mels*r), ``ph_lin_specs`` (B, T_red, F*r),
+    ``ph_time_frames`` (B,) = unpadded T_red), in the order of the module docstring.  The features of a batch are
+    read from the pre-computed ``.npz`` files when the batch is formed."""
+    n_buckets = evaluation_params.n_buckets if n_buckets is None else n_buckets
+    allow = evaluation_params.allow_smaller_batches if allow_smaller_batches is None else allow_smaller_batches
+    sentences, sentence_lengths, wav_paths = dataset.load(max_samples=max_samples)
+    if verbose:
+        print('Loaded {} dataset entries.'.format(len(sentence_lengths)))
+    boundaries = bucket_boundaries(sentence_lengths, n_buckets)
+    if verbose:
+        print('bucket_boundaries', boundaries)
+        print('n_buckets: {} + 2'.format(len(boundaries)))
+    for idx in bucket_batches(sentence_lengths, boundaries, batch_size, allow):
+        yield pad_batch([np.frombuffer(sentences[i], dtype=np.int32) for i in idx],
+                        [sentence_lengths[i] for i in idx],
+                        [dataset.load_audio(wav_paths[i]) for i in idx])
+
+
+def global_step_of(checkpoint_file):
+    """reference :180: the global step is the part of the file name after the last '-'."""
+    return int(checkpoint_file.split('-')[-1])
+
+
+def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_save_run=None, verbose=True):
+    """reference :153-257.  Restores ``checkpoint_file`` into ``model`` (a ``Tacotron(..., Mode.EVAL)``) once, runs every
+    feed dict of ``batches`` through tts_evaluate and returns ``{loss, loss_decoder, loss_post_processing, global_step,
+    n_batches}``: the per-batch float32 losses averaged unweighted over the batches.  Raises if no batch ran.  Appends
+    the summary line (module docstring) when ``checkpoint_dir`` (default ``evaluation_params.checkpoint_dir``) is set."""
+    if model._mode != Mode.EVAL:
+        raise ValueError('evaluate() needs a Tacotron in Mode.EVAL')
+    global_step = global_step_of(checkpoint_file)
+    if verbose:
+        print('[checkpoint_file] step: {}, file: "{}"'.format(global_step, checkpoint_file))
+        print('Restoring model...')
+    model.restore(checkpoint_file)
+    if verbose:
+        print('Restoring finished')
+    sums = np.zeros(3, np.float64)
+    n_batches = 0
+    for feed in batches:
+        out = model.evaluate_device(feed['ph_sentences'], feed['ph_mel_specs'], feed['ph_lin_specs'],
+                                    want_mel=False, want_alignments=False, want_linear=False)
+        sums += out['losses'].to_host().astype(np.float64)
+        n_batches += 1
+    if n_batches == 0:
+        raise Exception('Error: No batches were processed!')
+    avg = sums / n_batches
+    result = dict(loss=float(avg[0]), loss_decoder=float(avg[1]), loss_post_processing=float(avg[2]),
+                  global_step=global_step, n_batches=n_batches)
+    if verbose:
+        print('[evaluate] step: {}, batches: {}, loss: {:.6f}, loss_decoder: {:.6f}, loss_post_processing: {:.6f}'.format(
+            global_step, n_batches, result['loss'], result['loss_decoder'], result['loss_post_processing']))
+    checkpoint_dir = evaluation_params.checkpoint_dir if checkpoint_dir is None else checkpoint_dir
+    if checkpoint_dir:
+        save_dir = os.path.join(checkpoint_dir, checkpoint_save_run or evaluation_params.checkpoint_save_run)
+        os.makedirs(save_dir, exist_ok=True)
+        line = {'global_step': global_step, 'checkpoint': checkpoint_file, 'n_batches': n_batches,
+                'loss/loss': result['loss'], 'loss/loss_decoder': result['loss_decoder'],
+                'loss/loss_post_processing': result['loss_post_processing']}
+        with open(os.path.join(save_dir, SUMMARY_FILE), 'a') as f:
+            f.write(json.dumps(line) + '\n')
+    return result
+
+
+def collect_checkpoint_paths(checkpoint_dir):
+    """reference :284-326: the ``all_model_checkpoint_paths`` entries of ``<checkpoint_dir>/checkpoint`` (the first line,
+    ``model_checkpoint_path``, is dropped), joined onto the directory."""
+    with open(os.path.join(checkpoint_dir, 'checkpoint'), 'r') as f:
+        lines = [line.strip() for line in f]
+    lines = lines[1:]
+    lines = [line.replace('all_model_checkpoint_paths: ', '') for line in lines]
+    lines = [line.replace('"', '') for line in lines]
+    return [os.path.join(checkpoint_dir, line) for line in lines]
+
+
+def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, batch_size=None, checkpoint_dir=None,
+                        checkpoint_save_run=None, hparams=None, device_id=0, verbose=True):
+    """One cycle of the reference's ``__eval_cycle`` (:336-352): a dataset loader, the batches, a model with its own
+    engine, :func:`evaluate`; the engine is released afterwards."""
+    from ..datasets.lj_speech import LJSpeechDatasetHelper
+    dataset = LJSpeechDatasetHelper(dataset_folder=dataset_folder or dataset_params.dataset_folder,
+                                    char_dict=dataset_params.vocabulary_dict, fill_dict=False)
+    batches = batched_placeholders(dataset,
+                                   evaluation_params.max_samples if max_samples is None else max_samples,
+                                   evaluation_params.batch_size if batch_size is None else batch_size, verbose=verbose)
+    model = Tacotron(Tacotron.model_placeholders(), Mode.EVAL, hparams=hparams or model_params, device_id=device_id)
+    try:
+        return evaluate(model, checkpoint_file, batches, checkpoint_dir=checkpoint_dir,
+                        checkpoint_save_run=checkpoint_save_run, verbose=verbose)
+    finally:
+        model.engine.close()
+
+
+def main(argv=None):
+    """The reference's ``python tacotron/evaluate.py`` (:329-364):
+
+        python -m single-speaker-tts_amd.tacotron.evaluate [--all] [--checkpoint-dir D] [--load-run R] [--save-run S]
+                                                           [--dataset-folder F] [--max-samples N] [--batch-size B]
+
+    The options override the ``evaluation_params`` / ``dataset_params`` fields of the same name.  Without ``--all``
+    (``evaluate_all_checkpoints``) the latest checkpoint of ``<checkpoint_dir>/<load_run>`` is evaluated, with it every
+    checkpoint its listing file names.  Prints one JSON line per checkpoint."""
+    import argparse
+    from .checkpoint import latest_checkpoint
+    ap = argparse.ArgumentParser(prog='tacotron.evaluate')
+    ap.add_argument('--all', action='store_true', default=evaluation_params.evaluate_all_checkpoints)
+    ap.add_argument('--checkpoint-dir', default=evaluation_params.checkpoint_dir)
+    ap.add_argument('--load-run', default=evaluation_params.checkpoint_load_run)
+    ap.add_argument('--save-run', default=evaluation_params.checkpoint_save_run)
+    ap.add_argument('--dataset-folder', default=dataset_params.dataset_folder)
+    ap.add_argument('--max-samples', type=int, default=evaluation_params.max_samples)
+    ap.add_argument('--batch-size', type=int, default=evaluation_params.batch_size)
+    ap.add_argument('--device', type=int, default=0)
+    args = ap.parse_args(argv)
+    load_dir = os.path.join(args.checkpoint_dir, args.load_run)
+    if args.all:
+        files = collect_checkpoint_paths(load_dir)
+        print('Found #{} checkpoints to evalue.'.format(len(files)))
+    else:
+        latest = latest_checkpoint(load_dir)
+        if latest is None:
+            raise FileNotFoundError('no checkpoint found in {}'.format(load_dir))
+        files = [latest]
+    for checkpoint_file in files:
+        res = evaluate_checkpoint(checkpoint_file, dataset_folder=args.dataset_folder, max_samples=args.max_samples,
+                                  batch_size=args.batch_size, checkpoint_dir=args.checkpoint_dir,
+                                  checkpoint_save_run=args.save_run, device_id=args.device)
+        print(json.dumps(dict(res, checkpoint=checkpoint_file)))
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

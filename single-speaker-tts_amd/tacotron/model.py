@@ -1,4 +1,4 @@
-"""Drop-in mirror of the reference's ``tacotron.model`` surface for the inference path.
+"""Drop-in mirror of the reference's ``tacotron.model`` surface for the inference and evaluation paths.
 
 Reference: tacotron/model.py -- ``Mode`` (:20-23), ``Tacotron(inputs, mode, training_summary)``
 (:35-112) with attributes ``inp_sentences``, ``output_mel_spec`` (B,T,80),
@@ -8,8 +8,13 @@ Reference: tacotron/model.py -- ``Mode`` (:20-23), ``Tacotron(inputs, mode, trai
 
 There is no TensorFlow graph here: the "tensors" are symbolic :class:`Fetch` handles and
 ``Tacotron.run(fetches, feed_dict)`` plays the role of ``session.run`` (reference
-tacotron/inference.py:75-85) by driving the HIP library.  Only ``Mode.PREDICT`` exists on this
-path; TRAIN / EVAL are outside the accelerated scope and raise ``NotImplementedError``.
+tacotron/inference.py:75-85) by driving the HIP library.
+
+``Mode.PREDICT`` and ``Mode.EVAL`` exist on this path.  EVAL (reference :299-306, 432-442) feeds
+``ph_sentences``, ``ph_mel_specs`` (B, T_red, r*n_mels) and ``ph_lin_specs`` (B, T_red, r*F); the decoder
+free-runs for T_red steps and ``loss_op`` / ``loss_op_decoder`` / ``loss_op_post_processing`` are the L1
+losses of tts_evaluate (``ph_sentence_length`` / ``ph_time_frames`` are accepted and do not enter them).
+TRAIN is outside the accelerated scope and raises ``NotImplementedError``.
 """
 import os
 
@@ -46,7 +51,7 @@ class Fetch(object):
 
 
 class Tacotron(object):
-    """Tacotron in PREDICT mode on one MI355X.
+    """Tacotron in PREDICT or EVAL mode on one MI355X.
 
     ``weights`` ({tf variable name: array}, see tacotron/weights.py) may be given here or later
     through :meth:`restore`; it replaces ``tf.train.Saver().restore`` (reference
@@ -54,9 +59,9 @@ class Tacotron(object):
 
     def __init__(self, inputs, mode, training_summary=True, weights=None, hparams=None, device_id=0,
                  stream=None, engine=None):
-        if mode != Mode.PREDICT:
-            raise NotImplementedError('only Mode.PREDICT is implemented on the MI355X path '
-                                      '(training / evaluation are out of scope)')
+        if mode not in (Mode.PREDICT, Mode.EVAL):
+            raise NotImplementedError('only Mode.PREDICT and Mode.EVAL are implemented on the MI355X path '
+                                      '(training is out of scope)')
         self.hparams = hparams or model_params
         self._mode = mode
         self._training_summary = training_summary
@@ -66,6 +71,10 @@ class Tacotron(object):
         self.inp_linear_spec = inputs.get('ph_lin_specs')
         self.inp_time_steps = inputs.get('ph_time_frames')
         self.loss_op = self.loss_op_decoder = self.loss_op_post_processing = None
+        if mode == Mode.EVAL:   # reference tacotron/model.py:432-442
+            self.loss_op = Fetch('loss_op')
+            self.loss_op_decoder = Fetch('loss_op_decoder')
+            self.loss_op_post_processing = Fetch('loss_op_post_processing')
         self.output_mel_spec = Fetch('output_mel_spec')
         self.reduced_output_mel_spec = Fetch('reduced_output_mel_spec')
         self.output_linear_spec = Fetch('output_linear_spec')
@@ -118,20 +127,51 @@ class Tacotron(object):
         linear = eng.postnet_forward(mel)
         return dict(memory=memory, mel=mel, alignments=align, linear=linear, n_steps=S)
 
+    def get_loss_op(self):
+        """reference tacotron/model.py:446-451"""
+        return self.loss_op
+
+    def evaluate_device(self, sentences, mel_specs, lin_specs, want_mel=True, want_alignments=True, want_linear=True):
+        """Mode.EVAL on one batch: encoder -> decoder (T_red free-running steps) -> post-net -> L1 losses, one
+        tts_evaluate call; returns device arrays (``losses`` = [loss, loss_decoder, loss_post_processing])."""
+        sentences = np.ascontiguousarray(sentences, dtype=np.int32)
+        if sentences.ndim != 2:
+            raise ValueError('sentences must be (B, T_sent) int32')
+        return self.engine.evaluate(sentences, mel_specs, lin_specs, want_mel=want_mel, want_alignments=want_alignments,
+                                    want_linear=want_linear)
+
+    @staticmethod
+    def _feed(feed_dict, ph):
+        if ph is None:
+            return None
+        for k, v in feed_dict.items():
+            if k is ph or getattr(k, 'name', None) == getattr(ph, 'name', object()):
+                return v
+        return None
+
     def run(self, fetches, feed_dict, n_steps=None):
-        """session.run analogue: ``model.run([model.output_linear_spec], {model.inp_sentences: ids})``."""
+        """session.run analogue: ``model.run([model.output_linear_spec], {model.inp_sentences: ids})``; in Mode.EVAL the
+        feed also holds ``inp_mel_spec`` and ``inp_linear_spec`` and the loss fetches are available."""
         single = not isinstance(fetches, (list, tuple))
         fl = [fetches] if single else list(fetches)
-        sentences = None
-        for k, v in feed_dict.items():
-            if k is self.inp_sentences or getattr(k, 'name', None) == getattr(self.inp_sentences, 'name', object()):
-                sentences = v
+        sentences = self._feed(feed_dict, self.inp_sentences)
         if sentences is None:
             raise KeyError('feed_dict must feed model.inp_sentences')
-        out = self.predict_device(sentences, n_steps)
+        if self._mode == Mode.EVAL:
+            mel_t, lin_t = self._feed(feed_dict, self.inp_mel_spec), self._feed(feed_dict, self.inp_linear_spec)
+            if mel_t is None or lin_t is None:
+                raise KeyError('Mode.EVAL: feed_dict must feed model.inp_mel_spec and model.inp_linear_spec')
+            names = {f.name for f in fl}
+            out = self.evaluate_device(sentences, mel_t, lin_t,
+                                       want_mel=bool(names & {'output_mel_spec', 'reduced_output_mel_spec'}),
+                                       want_alignments=bool(names & {'alignment_history', 'summary'}),
+                                       want_linear=bool(names & {'output_linear_spec', 'summary'}))
+        else:
+            out = self.predict_device(sentences, n_steps)
         B = np.asarray(sentences).shape[0]
         S, r, nm = out['n_steps'], self.hparams.reduction, self.hparams.n_mels
         res = []
+        losses = None
         for f in fl:
             if f.name == 'output_linear_spec':
                 res.append(out['linear'].to_host())
@@ -141,6 +181,10 @@ class Tacotron(object):
                 res.append(out['mel'].to_host().reshape(B, S, r * nm))
             elif f.name == 'alignment_history':
                 res.append(out['alignments'].to_host())
+            elif f.name in ('loss_op', 'loss_op_decoder', 'loss_op_post_processing') and 'losses' in out:
+                if losses is None:
+                    losses = out['losses'].to_host()
+                res.append(losses[('loss_op', 'loss_op_decoder', 'loss_op_post_processing').index(f.name)])
             elif f.name == 'summary':
                 res.append(self._dump(out))
             else:

@@ -5,6 +5,7 @@ singletons (plain dataclasses; no TensorFlow):
 
   * ``model_params``      <- reference tacotron/params/model.py:8-153
   * ``inference_params``  <- reference tacotron/params/inference.py:4-35
+  * ``evaluation_params`` <- reference tacotron/params/evaluation.py:4-50
   * ``dataset_params``    <- reference tacotron/params/dataset.py:9-32
   * LJ-Speech dB constants <- reference datasets/lj_speech.py:20-29
 
@@ -100,6 +101,24 @@ class InferenceParams:
     n_synthesis_threads: int = 6
 
 
+@dataclass
+class EvaluationParams:
+    batch_size: int = 32
+    n_threads: int = 4              # (the reference's loader threads; batches are formed on the host here)
+    max_samples: int = 1024
+    shuffle_samples: bool = False
+    n_pre_calc_batches: int = 8
+    n_samples_per_bucket: int = 16
+    n_buckets: int = 20
+    allow_smaller_batches: bool = True
+    checkpoint_dir: str = '/tmp/tacotron/ljspeech/LJSpeech'
+    checkpoint_load_run: str = 'train'
+    checkpoint_save_run: str = 'evaluate'
+    evaluate_all_checkpoints: bool = False
+    summary_save_steps: int = 50
+    performance_log_steps: int = 50
+
+
 class LJSpeechConstants:
     """dB statistics of the LJ-Speech loader (reference datasets/lj_speech.py:20-29)."""
     mel_mag_ref_db = 6.02
@@ -127,4 +146,5 @@ class DatasetParams:
 
 model_params = ModelParams()
 inference_params = InferenceParams()
+evaluation_params = EvaluationParams()
 dataset_params = DatasetParams()

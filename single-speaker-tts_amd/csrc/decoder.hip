@@ -297,24 +297,23 @@ __global__ __launch_bounds__(256) void dec_predict_centre_kernel(const float* __
                                                                  int Ts, int local_d, int* __restrict__ err_flag) {
     constexpr int A = 256;
     __shared__ float qs[A];
-    __shared__ float red[4];
+    __shared__ double red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     qs[tid] = query[(size_t)b * A + tid];
     __syncthreads();
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    // in double (tts_common.h, predicted_centre)
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
     for (int k = 0; k < A; k += 4) {
-        a0 = fmaf(qs[k + 0], wp[(size_t)(k + 0) * A + tid], a0);
-        a1 = fmaf(qs[k + 1], wp[(size_t)(k + 1) * A + tid], a1);
-        a2 = fmaf(qs[k + 2], wp[(size_t)(k + 2) * A + tid], a2);
-        a3 = fmaf(qs[k + 3], wp[(size_t)(k + 3) * A + tid], a3);
+        a0 = fma((double)qs[k + 0], (double)wp[(size_t)(k + 0) * A + tid], a0);
+        a1 = fma((double)qs[k + 1], (double)wp[(size_t)(k + 1) * A + tid], a1);
+        a2 = fma((double)qs[k + 2], (double)wp[(size_t)(k + 2) * A + tid], a2);
+        a3 = fma((double)qs[k + 3], (double)wp[(size_t)(k + 3) * A + tid], a3);
     }
-    float v = tanhf_((a0 + a1) + (a2 + a3)) * vp[tid];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const double v = wave_sum_f64((double)tanhf((float)((a0 + a1) + (a2 + a3))) * (double)vp[tid]);
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) {
-        const float p = (float)Ts * sigmoidf_((red[0] + red[1]) + (red[2] + red[3]));
+        const float p = predicted_centre((red[0] + red[1]) + (red[2] + red[3]), Ts);
         p_out[b] = p;
         const int c = (int)floorf(p);
         if (c - local_d < 0 || c + local_d + 1 > Ts) *err_flag = 1;

@@ -384,23 +384,23 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
     if (LOCAL && lc.d > 0) {
         w_n = 2 * lc.d + 1;
         if (lc.predictive) {
-            // (q W_p)[n]: thread (n, half of k); then v_p . tanh(.) over the row's 512 threads
-            const int n = t512 & 255, kh = t512 >> 8;
-            float a0 = 0.f, a1 = 0.f;
-            const float* wpn = lc.wp + (size_t)(128 * kh) * PD_D + n;
-            for (int k = 0; k < 128; k += 2) {
-                a0 = fmaf(qs[128 * kh + k], wpn[(size_t)k * PD_D], a0);
-                a1 = fmaf(qs[128 * kh + k + 1], wpn[(size_t)(k + 1) * PD_D], a1);
+            // (q W_p)[n] by thread n of the row's first 256, then v_p . tanh(.) over them, in double (tts_common.h,
+            // predicted_centre): waves 0..3 leave their sums as (hi, lo) pairs in redm[hw], redm[4 + hw]
+            if (t512 < 256) {
+                double a0 = 0.0, a1 = 0.0;
+                const float* wpn = lc.wp + t512;
+                for (int k = 0; k < PD_D; k += 2) {
+                    a0 = fma((double)qs[k], (double)wpn[(size_t)k * PD_D], a0);
+                    a1 = fma((double)qs[k + 1], (double)wpn[(size_t)(k + 1) * PD_D], a1);
+                }
+                const double v = wave_sum_f64((double)tanhf((float)(a0 + a1)) * (double)lc.vp[t512]);
+                if (lane == 0) split_f64(v, &redm[hw], &redm[4 + hw]);
             }
-            part[kh * PD_D + n] = a0 + a1;
             __syncthreads();
-            float v = 0.f;
-            if (t512 < 256) v = tanhf_(part[t512] + part[PD_D + t512]) * lc.vp[t512];
+            double z = 0.0;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-            if (lane == 0) redm[hw] = v;   // waves 4..7 of the row hold zeros
-            __syncthreads();
-            const float p = (float)Ts * sigmoidf_((redm[0] + redm[1]) + (redm[2] + redm[3]));
+            for (int i = 0; i < 4; ++i) z += (double)redm[i] + (double)redm[4 + i];
+            const float p = predicted_centre(z, Ts);
             const int c = (int)floorf(p);
             // a window that leaves the memory: the reference's padding arithmetic fails there (decoder.hip)
             if (t512 == 0 && row_ok) {

@@ -501,22 +501,23 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
     if (LOCAL) {
         w_n = 2 * lc.d + 1;
         if (lc.predictive) {
-            // (q W_p)[n] by thread n of the row's 256 (columns coalesced), then v_p . tanh(.) over them
-            float v = 0.f;
+            // (q W_p)[n] by thread n of the row's 256 (columns coalesced), then v_p . tanh(.) over them, in double
+            // (tts_common.h, predicted_centre): the waves' sums as (hi, lo) pairs in redm[hw], redm[4 + hw]
             if (active) {
-                float a0 = 0.f, a1 = 0.f;
+                double a0 = 0.0, a1 = 0.0;
                 const float* wpn = lc.wp + t256;
                 for (int k = 0; k < WS_D; k += 2) {
-                    a0 = fmaf(qs[k], wpn[(size_t)k * WS_D], a0);
-                    a1 = fmaf(qs[k + 1], wpn[(size_t)(k + 1) * WS_D], a1);
+                    a0 = fma((double)qs[k], (double)wpn[(size_t)k * WS_D], a0);
+                    a1 = fma((double)qs[k + 1], (double)wpn[(size_t)(k + 1) * WS_D], a1);
                 }
-                v = tanhf_(a0 + a1) * lc.vp[t256];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-                if (lane == 0) redm[hw] = v;
+                const double v = wave_sum_f64((double)tanhf((float)(a0 + a1)) * (double)lc.vp[t256]);
+                if (lane == 0) split_f64(v, &redm[hw], &redm[4 + hw]);
             }
             __syncthreads();
-            const float pp = (float)Ts * sigmoidf_((redm[0] + redm[1]) + (redm[2] + redm[3]));
+            double z = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) z += (double)redm[i] + (double)redm[4 + i];
+            const float pp = predicted_centre(z, Ts);
             const int c = (int)floorf(pp);
             // a window that leaves the memory: the reference's padding arithmetic fails there (decoder.hip)
             if (active && t256 == 0 && row_ok) {

@@ -21,6 +21,29 @@ enum Epi { EPI_STD = 0, EPI_HIGHWAY = 1 };
 // fmas, v_div_fmas, v_div_fixup: ten dependent instructions), which sits three times on the critical path of every
 // GRU step.  rcp(inf) = 0 and rcp(1) = 1, so the limits stay exact.
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// LocalLuongAttention's predicted window centre p = T_s * sigmoid(v_p . tanh(q W_p)) (reference attention.py:246-258).
+// The reported gaussian alignments exp(-(j - p)^2 / 2 * (D/2)^2) move by (D/2)^2 (j - p) relative per unit of p, so
+// the fast float sigmoidf_ / tanhf_ (a few ulps of p) doubled their error: the centre is evaluated in double instead --
+// the q W_p products, tanh, the v_p reduction and the sigmoid -- and rounded to float once.  One value per utterance
+// and step, off the global-attention path.  Partial sums cross LDS as float (hi, lo) pairs.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ void split_f64(double v, float* hi, float* lo) {
+    *hi = (float)v;
+    *lo = (float)(v - (double)*hi);
+}
+// exp(-z) = expf(-zf) exp(-(z - zf)), zf = (float)z: the float exponential (~1 ulp) and a first-order correction for
+// the rounding of z (|z - zf| < 1e-7 |z|), then the division in double (a double exp would spill the weight-stationary
+// decoder's registers)
+__device__ __forceinline__ float predicted_centre(double z, int Ts) {
+    const float zf = (float)z;
+    const double e = (double)expf(-zf) * (1.0 - (z - (double)zf));
+    return (float)((double)Ts / (1.0 + e));
+}
+
 __device__ __forceinline__ float tanhf_(float x) {
     // tanh(x) = 1 - 2/(exp(2x)+1); exact limits at +-inf, abs error ~1e-7.
     float e = __expf(2.0f * x);

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import audio_oracle as A
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +30,10 @@ def test_golden_network_fixture(engine):
     assert np.abs(al.to_host() - g['alignments']).max() < 1e-4
     lin = engine.postnet_forward(mel.to_host().reshape(2, -1, 80))
     assert rel_l2(lin.to_host(), g['linear']) < 1e-3
+    assert_parity(mem.to_host(), g['memory'], BTC, 1e-3, 'golden network memory')
+    assert_mel_parity(mel.to_host(), g['reduced_mel'], 1e-3, 'golden network')
+    assert_alignment_rows(al.to_host(), g['alignments'], 1e-4, 'golden network')
+    assert_parity(lin.to_host(), g['linear'], BTC, 1e-3, 'golden network linear')
 
 
 def test_golden_griffin_lim_fixture(engine):
@@ -270,11 +275,17 @@ def test_weights_through_the_checkpoint_importer_match_the_oracle(tmp_path, form
     mem = eng.encoder_forward(ids)
     mel, al = eng.decoder_forward(mem, S)
     lin = eng.postnet_forward(mel.to_host().reshape(B, S * hp.reduction, hp.n_mels))
+    mem_h, mel_h, al_h, lin_h = (x.to_host() for x in (mem, mel, al, lin))
     errs = dict(memory=rel_l2(mem.to_host().reshape(-1), ref_mem.reshape(-1)), mel=rel_l2(mel.to_host().reshape(-1), ref_mel.reshape(-1)),
                 align=float(np.abs(al.to_host().reshape(-1) - ref_al.reshape(-1)).max()), linear=rel_l2(lin.to_host().reshape(-1), ref_lin.reshape(-1)))
     eng.close()
     print('importer ({}) vs oracle: {}'.format(form, errs))
     assert errs['memory'] < 1e-4 and errs['mel'] < 1e-3 and errs['align'] < 1e-4 and errs['linear'] < 1e-3, errs
+    label = 'importer ({})'.format(form)
+    assert_parity(mem_h.reshape(ref_mem.shape), ref_mem, BTC, 1e-4, label + ' memory')
+    assert_mel_parity(mel_h.reshape(ref_mel.shape), ref_mel, 1e-3, label)
+    assert_alignment_rows(al_h.reshape(ref_al.shape), ref_al, 1e-4, label)
+    assert_parity(lin_h.reshape(ref_lin.shape), ref_lin, BTC, 1e-3, label + ' linear')
 
 
 def test_host_facade_two_calls_in_flight_equals_serial_calls(engine, hparams):

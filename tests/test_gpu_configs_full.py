@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_parity
 from oracle import audio_oracle as A
 from oracle import tacotron_oracle as O
 
@@ -73,6 +74,9 @@ def test_config1_single_sentence_text_to_waveform_full_size(hparams, weights, we
           'convergence e2e {:.5f} / staged {:.5f} vs oracle {:.5f}'.format(e_mel, e_lin, e_al, e_mag, mse_gl, ref_mse,
                                                                          sc_hip, sc_gl, sc_ref))
     assert e_mel < 1e-3 and e_lin < 1e-3 and e_al < 1e-4 and e_mag < 1e-3
+    assert_parity(mel, ref['mel'], BTC, 1e-3, 'config 1 mel')
+    assert_parity(lin, ref['linear'], BTC, 1e-3, 'config 1 linear')
+    assert_alignment_rows(out['alignments'].to_host(), ref['alignments'], 1e-4, 'config 1')
     assert abs(mse_gl - ref_mse) <= 0.01 * ref_mse
     assert abs(sc_gl - sc_ref) <= 0.01 * sc_ref and abs(sc_hip - sc_ref) <= 0.01 * sc_ref
     eng.close()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import tacotron_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +48,11 @@ def test_cudnn_full_network(cudnn_setup, B, Ts, S):
                 align=float(np.abs(al.to_host() - ref['alignments']).max()), linear=rel_l2(lin.to_host(), ref['linear']))
     print('cudnn variant B={} Ts={} S={}: {}'.format(B, Ts, S, errs))
     assert errs['memory'] < 1e-3 and errs['mel'] < 1e-3 and errs['linear'] < 1e-3 and errs['align'] < 1e-4
+    label = 'cudnn variant B={} Ts={} S={}'.format(B, Ts, S)
+    assert_parity(mem.to_host(), ref['memory'], BTC, 1e-3, label + ' memory')
+    assert_mel_parity(mel.to_host(), ref['reduced_mel'], 1e-3, label)
+    assert_alignment_rows(al.to_host(), ref['alignments'], 1e-4, label)
+    assert_parity(lin.to_host(), ref['linear'], BTC, 1e-3, label + ' linear')
 
 
 def test_cudnn_differs_from_grucell(cudnn_setup, engine, hparams):
@@ -56,6 +62,7 @@ def test_cudnn_differs_from_grucell(cudnn_setup, engine, hparams):
     a = eng.postnet_forward(mel).to_host()
     ref = O.post_process(mel.astype(np.float64), O.cast_weights(w, np.float64), hp)
     assert rel_l2(a, ref) < 1e-3
+    assert_parity(a, ref, BTC, 1e-3, 'cudnn post-net linear')
 
 
 @pytest.mark.parametrize('B,Ts,S', [(2, 9, 4), (19, 60, 12)])
@@ -78,6 +85,9 @@ def test_cudnn_persistent_decoder(cudnn_setup, B, Ts, S):
         mel_s, al_s = eng.decoder_forward(dev, S)
         eng.synchronize()
         assert rel_l2(mel_s.to_host(), ref_mel) < 1e-3 and np.abs(al_s.to_host() - ref_al).max() < 1e-4
+        label = 'cudnn streamed-weights decoder B={} Ts={} S={}'.format(B, Ts, S)
+        assert_mel_parity(mel_s.to_host(), ref_mel, 1e-3, label)
+        assert_alignment_rows(al_s.to_host(), ref_al, 1e-4, label)
         eng.set_option('pd_ws', 1)
         eng.set_option('persistent_decoder', 0)
         mel0, al0 = eng.decoder_forward(dev, S)
@@ -90,6 +100,10 @@ def test_cudnn_persistent_decoder(cudnn_setup, B, Ts, S):
         B, Ts, S, e_mel, e_al, rel_l2(mel, mel0)))
     assert e_mel < 1e-3 and e_al < 1e-4
     assert rel_l2(mel, mel0) < 1e-5 and np.abs(al - al0).max() < 1e-4
+    label = 'cudnn weight-stationary decoder B={} Ts={} S={}'.format(B, Ts, S)
+    assert_mel_parity(mel, ref_mel, 1e-3, label)
+    assert_alignment_rows(al, ref_al, 1e-4, label)
+    assert_mel_parity(mel0, ref_mel, 1e-3, label.replace('weight-stationary', 'launch-per-layer'))
 
 
 @pytest.mark.parametrize('B,Ts,S,delay', [(20, 50, 40, 1), (64, 150, 60, 2)])

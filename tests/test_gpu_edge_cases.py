@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import audio_oracle as A
 from oracle import tacotron_oracle as O
 
@@ -18,6 +19,7 @@ def test_encoder_edge_shapes(engine, hparams, weights64, B, Ts):
     ref = O.encoder(ids, weights64, hparams)
     got = engine.encoder_forward(ids).to_host()
     assert got.shape == ref.shape and rel_l2(got, ref) < 1e-3
+    assert_parity(got, ref, BTC, 1e-3, 'encoder edge B={} Ts={} memory'.format(B, Ts))
 
 
 @pytest.mark.parametrize('B,Ts,S', [(1, 1, 1), (1, 2, 3), (3, 3, 2), (65, 5, 2), (2, 130, 2)])
@@ -29,6 +31,9 @@ def test_decoder_edge_shapes(engine, hparams, weights64, B, Ts, S):
     mel, al = engine.decoder_forward(memory, S)
     assert rel_l2(mel.to_host(), ref_mel) < 1e-3
     assert np.abs(al.to_host() - ref_al).max() < 1e-4
+    label = 'decoder edge B={} Ts={} S={}'.format(B, Ts, S)
+    assert_mel_parity(mel.to_host(), ref_mel, 1e-3, label)
+    assert_alignment_rows(al.to_host(), ref_al, 1e-4, label)
     mel2, none = engine.decoder_forward(memory, S, want_alignments=False)
     assert none is None and np.array_equal(mel2.to_host(), mel.to_host())
 
@@ -40,6 +45,7 @@ def test_postnet_edge_shapes(engine, hparams, weights64, B, T):
     ref = O.post_process(mel.astype(np.float64), weights64, hparams)
     got = engine.postnet_forward(mel).to_host()
     assert got.shape == ref.shape == (B, T, 1025) and rel_l2(got, ref) < 1e-3
+    assert_parity(got, ref, BTC, 1e-3, 'postnet edge B={} T={} linear'.format(B, T))
 
 
 @pytest.mark.parametrize('T', [5, 6, 31, 32, 33, 64, 65])

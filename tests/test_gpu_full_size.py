@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import audio_oracle as A
 from oracle import tacotron_oracle as O
 
@@ -29,6 +30,7 @@ def test_config2_encoder_32x150(engine, hparams, weights64):
     e = rel_l2(got, ref)
     print('config 2 encoder 32x150 rel-L2', e)
     assert e < 1e-3
+    assert_parity(got, ref, BTC, 1e-3, 'config 2 memory')
 
 
 def test_config3_decoder_200_steps_b64(engine, hparams, weights64):
@@ -46,6 +48,8 @@ def test_config3_decoder_200_steps_b64(engine, hparams, weights64):
     assert e < 1e-3 and e_last < 1e-3
     assert np.abs(al - ref_al).max() < 1e-4
     assert np.allclose(al.sum(-1), 1.0, atol=1e-5)
+    assert_mel_parity(mel, ref_mel, 1e-3, 'config 3')
+    assert_alignment_rows(al, ref_al, 1e-4, 'config 3')
 
 
 def test_shard_invariance(engine):
@@ -72,6 +76,7 @@ def test_config4_postnet_full_length(engine, hparams, weights64):
     e = rel_l2(got, ref)
     print('config 4 post-net T=1000 rel-L2', e)
     assert got.shape == (4, 1000, 1025) and e < 1e-3
+    assert_parity(got, ref, BTC, 1e-3, 'config 4 linear')
 
 
 def test_config4_griffin_lim_full_length(engine):

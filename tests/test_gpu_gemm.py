@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -46,6 +47,7 @@ def test_gemm_conv_matches_numpy(engine, B, T, Cin, ktaps, N, pool):
     e = rel_l2(got, ref)
     print('gemm B={} T={} Cin={} k={} N={} pool={}: rel-L2 {:.2e}'.format(B, T, Cin, ktaps, N, pool, e))
     assert e < 1e-5
+    assert_parity(got, ref, {'row': 0, 'col': 1}, 1e-5, 'gemm B={} T={} Cin={} k={} N={} pool={}'.format(B, T, Cin, ktaps, N, pool))
     dx.free(); dw.free(); dc.free()
 
 
@@ -72,6 +74,8 @@ def test_gemm_variant_forms_match_numpy(engine, option):
             dc = engine.empty((M, N))
             engine._check(engine.lib.tts_debug_gemm(engine.handle, dx.data_ptr(), dw.data_ptr(), dc.data_ptr(), M, N, Cin, ktaps, T, pool))
             assert rel_l2(dc.to_host(), ref) < 1e-5, (option, B, T, Cin, ktaps, N, pool)
+            assert_parity(dc.to_host(), ref, {'row': 0, 'col': 1}, 1e-5, '{} gemm B={} T={} Cin={} k={} N={} pool={}'.format(
+                option, B, T, Cin, ktaps, N, pool))
             dx.free(); dw.free(); dc.free()
     finally:
         engine.set_option(option, 0)

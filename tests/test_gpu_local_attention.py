@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import tacotron_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +59,9 @@ def test_local_attention_decoder(hparams, weights, weights64, B, Ts, S, D, gauss
         print('local attention B={} Ts={} S={} D={} gaussian={}: mel {:.2e} align {:.2e}'.format(
             B, Ts, S, D, gaussian, e_mel, e_al))
         assert e_mel < 1e-3 and e_al < 1e-4
+        label = 'local attention {} B={} Ts={} S={} D={}'.format(pd, B, Ts, S, D)
+        assert_mel_parity(mel.to_host(), ref_mel, 1e-3, label)
+        assert_alignment_rows(al, ref_al, 1e-4, label)
         # structure: nothing outside the window, window follows the step index
         for t in range(S):
             p = min(max(t, D), Ts - (D + 1))
@@ -134,6 +138,9 @@ def test_local_end_to_end_synthesize(hparams, weights, weights64):
         assert rel_l2(out['mel'].to_host(), ref['mel']) < 1e-3
         assert rel_l2(out['linear'].to_host(), ref['linear']) < 1e-3
         assert float(np.abs(out['alignments'].to_host() - ref['alignments']).max()) < 1e-4
+        assert_parity(out['mel'].to_host(), ref['mel'], BTC, 1e-3, 'local attention synthesize mel')
+        assert_parity(out['linear'].to_host(), ref['linear'], BTC, 1e-3, 'local attention synthesize linear')
+        assert_alignment_rows(out['alignments'].to_host(), ref['alignments'], 1e-4, 'local attention synthesize')
     finally:
         eng.close()
 
@@ -174,6 +181,14 @@ def test_predictive_local_attention_decoder(hparams, B, Ts, S, D, gaussian, vp_s
         print('predictive local attention B={} Ts={} S={} D={}: mel {:.2e} align {:.2e}; window centres {:.1f}..{:.1f}'.format(
             B, Ts, S, D, e_mel, e_al, centres.min(), centres.max()))
         assert e_mel < 1e-3 and e_al < 1e-4
+        label = 'predictive local attention {} B={} Ts={} S={} D={}'.format(pd, B, Ts, S, D)
+        assert_mel_parity(mel.to_host(), ref_mel, 1e-3, label)
+        # gaussian rows move by (D/2)^2 (j - p) per unit of the predicted centre p: the kernels evaluate p in double
+        # (tests/test_parity_helper.py::test_predictive_gaussian_rows_need_an_accurate_centre).  At v_p x 8 and Ts 150,
+        # p = 150 sigmoid(v_p . tanh(q W_p)) also amplifies the float32 decoder state q by the eightfold v_p: the float32
+        # restatement leaves 7.1e-5 with an exact centre, the decoder forms measured 1.3e-4 ... 2.2e-4 on an MI355X (fast
+        # float GRU intrinsics in the state).  That one case is held to 3e-4, every other row to 1e-4.
+        assert_alignment_rows(al, ref_al, 3e-4 if (gaussian and vp_scale == 8.0) else 1e-4, label)
         assert np.all((al != 0).sum(-1) <= 2 * D + 1)
         if not gaussian:
             np.testing.assert_allclose(al.sum(-1), 1.0, atol=1e-5)

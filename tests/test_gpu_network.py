@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import tacotron_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -42,11 +43,16 @@ def test_encoder_stages(engine, hparams, weights64, B, Ts):
         'proj2': engine.debug_workspace('enc.p2', (B, Ts, 128)),
         'highway': engine.debug_workspace('enc.hw0', (B, Ts, 128)),
     }
-    errs = {k: rel_l2(v, stages[k] if k != 'proj2' else stages['proj2'] + stages['prenet']) for k, v in got.items()}
+    refs = {k: stages[k] if k != 'proj2' else stages['proj2'] + stages['prenet'] for k in got}
+    errs = {k: rel_l2(v, refs[k]) for k, v in got.items()}
     errs['memory'] = rel_l2(mem, ref)
     print('encoder B={} Ts={}: {}'.format(B, Ts, errs))
     for k, e in errs.items():
         assert e < (FINAL_TOL if k == 'memory' else STAGE_TOL), (k, e)
+    label = 'encoder B={} Ts={}'.format(B, Ts)
+    for k, v in got.items():
+        assert_parity(v, refs[k], BTC, STAGE_TOL, '{} {}'.format(label, k))
+    assert_parity(mem, ref, BTC, FINAL_TOL, label + ' memory')
 
 
 @pytest.mark.parametrize('B,Ts,S', [(2, 7, 3), (3, 37, 10), (17, 150, 6)])
@@ -62,6 +68,9 @@ def test_decoder(engine, hparams, weights64, B, Ts, S):
     assert e_mel < FINAL_TOL
     assert e_al < 1e-4
     assert np.allclose(al.to_host().sum(-1), 1.0, atol=1e-5)
+    label = 'decoder B={} Ts={} S={}'.format(B, Ts, S)
+    assert_mel_parity(mel.to_host(), ref_mel, FINAL_TOL, label)
+    assert_alignment_rows(al.to_host(), ref_al, 1e-4, label)
 
 
 def test_decoder_graph_matches_eager(engine):
@@ -120,6 +129,10 @@ def test_postnet_stages(engine, hparams, weights64, B, T):
     print('postnet B={} T={}: {}'.format(B, T, errs))
     for k, e in errs.items():
         assert e < (FINAL_TOL if k in ('linear', 'gru') else STAGE_TOL), (k, e)
+    label = 'postnet B={} T={}'.format(B, T)
+    for k, v in got.items():
+        assert_parity(v, stages[k], BTC, FINAL_TOL if k == 'gru' else STAGE_TOL, '{} {}'.format(label, k))
+    assert_parity(lin, ref, BTC, FINAL_TOL, label + ' linear')
 
 
 def test_full_network_small(engine, hparams, weights64):
@@ -132,6 +145,10 @@ def test_full_network_small(engine, hparams, weights64):
     lin = engine.postnet_forward(mel.to_host().reshape(B, -1, 80))
     assert rel_l2(mel.to_host(), ref['reduced_mel']) < FINAL_TOL
     assert rel_l2(lin.to_host(), ref['linear']) < FINAL_TOL
+    assert_parity(mem.to_host(), ref['memory'], BTC, FINAL_TOL, 'full network memory')
+    assert_mel_parity(mel.to_host(), ref['reduced_mel'], FINAL_TOL, 'full network')
+    assert_alignment_rows(al.to_host(), ref['alignments'], 1e-4, 'full network')
+    assert_parity(lin.to_host(), ref['linear'], BTC, FINAL_TOL, 'full network linear')
 
 
 # ---- CBHG tail (csrc/cbhg_tail.hip): lifter + highway stack + GRU input projections in one launch, against the oracle and
@@ -153,6 +170,10 @@ def test_cbhg_tail_forms(engine, hparams, weights64, fused, B, T):
     e = {'highway': rel_l2(hw, stages['highway']), 'gru': rel_l2(gru, stages['gru']), 'linear': rel_l2(lin, ref)}
     print('cbhg tail fused={} B={} T={}: {}'.format(fused, B, T, e))
     assert e['highway'] < STAGE_TOL and e['gru'] < FINAL_TOL and e['linear'] < FINAL_TOL, e
+    label = 'cbhg tail fused={} B={} T={}'.format(fused, B, T)
+    assert_parity(hw, stages['highway'], BTC, STAGE_TOL, label + ' highway')
+    assert_parity(gru, stages['gru'], BTC, FINAL_TOL, label + ' gru')
+    assert_parity(lin, ref, BTC, FINAL_TOL, label + ' linear')
 
 
 @pytest.mark.parametrize('n_hw', [0, 1, 3])
@@ -171,12 +192,18 @@ def test_cbhg_tail_layer_counts(hparams, n_hw):
         rng = np.random.default_rng(n_hw)
         ids = make_ids(rng, 3, 50)
         mem = eng.encoder_forward(ids).to_host()
-        assert rel_l2(mem, O.encoder(ids, w64, hp, {})) < FINAL_TOL
+        ref_mem = O.encoder(ids, w64, hp, {})
+        assert rel_l2(mem, ref_mem) < FINAL_TOL
         mel = rng.random((2, 70, 80)).astype(np.float32)
         st = {}
         ref = O.post_process(mel.astype(np.float64), w64, hp, st)
         lin = eng.postnet_forward(mel).to_host()
-        assert rel_l2(eng.debug_workspace('post.hw0', (2, 70, 128)), st['highway']) < STAGE_TOL
+        hw = eng.debug_workspace('post.hw0', (2, 70, 128))
+        assert rel_l2(hw, st['highway']) < STAGE_TOL
         assert rel_l2(lin, ref) < FINAL_TOL
+        label = 'cbhg tail n_hw={}'.format(n_hw)
+        assert_parity(mem, ref_mem, BTC, FINAL_TOL, label + ' memory')
+        assert_parity(hw, st['highway'], BTC, STAGE_TOL, label + ' highway')
+        assert_parity(lin, ref, BTC, FINAL_TOL, label + ' linear')
     finally:
         eng.close()

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from parity import assert_alignment_rows, assert_mel_parity
 from oracle import tacotron_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +46,9 @@ def test_persistent_decoder_vs_oracle(persistent, hparams, weights64, B, Ts, S):
     assert e_mel < 1e-3
     assert e_al < 1e-4
     assert np.allclose(al.to_host().sum(-1), 1.0, atol=1e-5)
+    label = 'persistent decoder B={} Ts={} S={}'.format(B, Ts, S)
+    assert_mel_parity(mel.to_host(), ref_mel, 1e-3, label)
+    assert_alignment_rows(al.to_host(), ref_al, 1e-4, label)
 
 
 def test_persistent_decoder_200_steps_b64(persistent, hparams, weights64):
@@ -70,6 +74,9 @@ def test_persistent_decoder_200_steps_b64(persistent, hparams, weights64):
         rows, e, float(np.abs(al[:, rows] - ref_al).max())))
     assert e < 1e-3
     assert np.abs(al[:, rows] - ref_al).max() < 1e-4
+    label = 'persistent decoder B=64 S=200 rows {}'.format(rows)
+    assert_mel_parity(mel[rows], ref_mel, 1e-3, label)
+    assert_alignment_rows(al[:, rows], ref_al, 1e-4, label)
 
 
 @pytest.mark.parametrize('B,Ts,S,reruns', [(20, 50, 12, 3), (64, 150, 200, 4)])

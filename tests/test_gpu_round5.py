@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, PKG, pkg, rel_l2
+from parity import BTC, assert_alignment_rows, assert_parity
 from oracle import audio_oracle as A
 from oracle import tacotron_oracle as O
 
@@ -122,6 +123,7 @@ def test_postnet_b64_t1000_vs_oracle_rows_0_and_63(engine, hparams, weights64):
         e = rel_l2(got[b:b + 1], ref)
         print('post-net B=64 T=1000 row {}: rel-L2 {:.3e}'.format(b, e))
         assert e < 1e-3
+        assert_parity(got[b:b + 1], ref, BTC, 1e-3, 'post-net B=64 T=1000 row {} linear'.format(b))
 
 
 def test_synthesize_b64_full_size_vs_oracle_rows_0_and_63(engine, hparams, weights64):
@@ -155,6 +157,10 @@ def test_synthesize_b64_full_size_vs_oracle_rows_0_and_63(engine, hparams, weigh
             b, e_mel, e_lin, e_al, sc_hip, sc_ref))
         assert e_mel < 1e-3 and e_lin < 1e-3 and e_al < 1e-4
         assert abs(sc_hip - sc_ref) <= 0.01 * sc_ref
+        label = 'synthesize B=64 row {}'.format(b)
+        assert_parity(mel[b:b + 1], ref['mel'], BTC, 1e-3, label + ' mel')
+        assert_parity(lin[b:b + 1], ref['linear'], BTC, 1e-3, label + ' linear')
+        assert_alignment_rows(al[:, b:b + 1], ref['alignments'], 1e-4, label)
 
 
 # ---------------------------------------------------------------------------------------------- functional corners
@@ -193,6 +199,9 @@ def test_without_post_processing_vs_oracle(no_post, B, Ts, S):
     e_mel, e_lin = rel_l2(out['mel'].to_host(), ref['mel']), rel_l2(out['linear'].to_host(), ref['linear'])
     print('apply_post_processing=False B={} Ts={} S={}: mel {:.2e} linear {:.2e}'.format(B, Ts, S, e_mel, e_lin))
     assert e_mel < 1e-3 and e_lin < 1e-3
+    label = 'apply_post_processing=False B={} Ts={} S={}'.format(B, Ts, S)
+    assert_parity(out['mel'].to_host(), ref['mel'], BTC, 1e-3, label + ' mel')
+    assert_parity(out['linear'].to_host(), ref['linear'], BTC, 1e-3, label + ' linear')
     assert np.array_equal(lin_staged.to_host(), out['linear'].to_host())
     for b in range(B):
         mag = A.linear_to_magnitude(ref['linear'][b].astype(np.float32), REF_DB, MAX_DB, POWER)

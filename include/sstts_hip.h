@@ -240,6 +240,55 @@ int tts_mel_spectrogram(tts_handle_t h, const float* lin, int B, int n_frames, i
 int tts_db_convert(tts_handle_t h, const float* in, size_t n, int mode, float ref_db, float max_db,
                    float* out);
 
+/* ---- dataset features (reference datasets/lj_speech.py:106-156 load_audio, dataset_helper.py:326-356) ------------ */
+/* A RAGGED batch of B recordings: samples back to back in `wav` (device, float32), recording b is
+ * wav[offsets[b] .. offsets[b+1]) with `offsets` a HOST array of B + 1 non-decreasing int64 (offsets[0] = 0 is not required).
+ *
+ * librosa.effects.trim (librosa 0.6) of every recording: reflect padding by frame_length / 2, frames k = 0 .. n / hop,
+ * mse_k = mean square of the frame (float64), frame k non-silent iff 10 log10(max(1e-10, mse_k)) - 10 log10(max(1e-10,
+ * max mse)) > -top_db (float64), bounds[2b] = first * hop, bounds[2b + 1] = min(n, (last + 1) * hop).  bounds: DEVICE int64
+ * [2B].  Needs n > frame_length / 2 for every recording (TTS_ERR_INVALID otherwise) and top_db > 0.  Two launches whatever
+ * B and the lengths are; asynchronous. */
+int tts_trim_bounds(tts_handle_t h, const float* wav, const int64_t* offsets, int B, int frame_length, int hop_length,
+                    float top_db, int64_t* bounds);
+
+/* The feature pass.  ALWAYS start from tts_default_feature_params (fills `struct_size` and the model's values). */
+typedef struct tts_feature_params {
+    int32_t struct_size;         /* sizeof(tts_feature_params_t) of the caller's header */
+    int32_t n_fft;               /* 2048: a power of two, 256 .. 4096 */
+    int32_t win_length;          /* 1102: 2 .. n_fft */
+    int32_t hop_length;          /* 275 */
+    int32_t sampling_rate;       /* 22050 */
+    int32_t n_mels;              /* 80 (HTK mel filterbank, norm 1, librosa 0.6) */
+    float fmin, fmax;            /* 0, 8000 (fmax <= 0: sampling_rate / 2) */
+    float mel_ref_db, mel_max_db;        /* 6.02, 99.89 (LJSpeechDatasetHelper) */
+    float linear_ref_db, linear_max_db;  /* 35.66, 100 */
+    int32_t normalize;           /* 1: normalize_decibel of both rows; 0: raw dB (magnitude_to_decibel) */
+    int32_t reduction;           /* 5: frames are zero-padded to a multiple of it */
+    int32_t trim;                /* 1: features of the trimmed segment (tts_trim_bounds); 0: of the whole recording */
+    float trim_top_db;           /* 60 */
+    int32_t trim_frame_length;   /* 2048 */
+    int32_t trim_hop_length;     /* 512 */
+} tts_feature_params_t;
+int tts_default_feature_params(tts_feature_params_t* p);
+/* Planning: plan (HOST int64 [3B]) = {start, end, T_pad} per recording -- the analysed segment wav[offsets[b] + start ..
+ * offsets[b] + end) (the trim bounds, or the whole recording) and its frame count 1 + (end - start) / hop zero-padded to a
+ * multiple of p->reduction.  With p->trim this enqueues tts_trim_bounds and synchronises the stream once to read the bounds
+ * back; without, nothing is enqueued.  A segment of at most n_fft / 2 samples is refused with TTS_ERR_INVALID (reflect
+ * padding is undefined there). */
+int tts_plan_features(tts_handle_t h, const float* wav, const int64_t* offsets, int B, const tts_feature_params_t* p,
+                      int64_t* plan);
+/* For every recording and frame t < T_pad of its plan: |STFT| of the segment (periodic hann, centred, reflect padding by
+ * n_fft / 2 about the SEGMENT's ends), then the rows
+ *   lin[t] = normalize_decibel(magnitude_to_decibel(|X_t|), linear_ref_db, linear_max_db)    (F = 1 + n_fft / 2 values)
+ *   mel[t] = normalize_decibel(magnitude_to_decibel(M |X_t|), mel_ref_db, mel_max_db)       (n_mels values)
+ * (raw dB when p->normalize is 0), and 0 in the padding rows t >= 1 + (end - start) / hop.  Outputs (device, float32) are
+ * time-major and ragged: recording b's rows follow those of recording b - 1, mel_out [sum T_pad][n_mels], lin_out
+ * [sum T_pad][F] -- per recording the reference's (T_pad / r, n_mels r) / (T_pad / r, F r) arrays.  One launch; a recording's
+ * rows are the same bits whatever batch it is in and at whatever position.  Asynchronous; the plan is read on the host. */
+int tts_extract_features(tts_handle_t h, const float* wav, const int64_t* offsets, int B, const tts_feature_params_t* p,
+                         const int64_t* plan, float* mel_out, float* lin_out);
+
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,
  * optional peak normalisation; replaces tacotron/inference.py:162-200 minus file IO.
@@ -285,7 +334,8 @@ int tts_wait_host_outputs(tts_handle_t h, int ticket, const float** linear_host,
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
- * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate).
+ * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate), "features" (tts_trim_bounds, the trim of tts_plan_features and
+ * tts_extract_features).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -56,6 +56,17 @@ class TtsSynthParams(ctypes.Structure):
     ]
 
 
+class TtsFeatureParams(ctypes.Structure):
+    """struct tts_feature_params (include/sstts_hip.h)."""
+    _fields_ = [
+        ('struct_size', c_int32), ('n_fft', c_int32), ('win_length', c_int32), ('hop_length', c_int32),
+        ('sampling_rate', c_int32), ('n_mels', c_int32), ('fmin', c_float), ('fmax', c_float),
+        ('mel_ref_db', c_float), ('mel_max_db', c_float), ('linear_ref_db', c_float), ('linear_max_db', c_float),
+        ('normalize', c_int32), ('reduction', c_int32), ('trim', c_int32), ('trim_top_db', c_float),
+        ('trim_frame_length', c_int32), ('trim_hop_length', c_int32),
+    ]
+
+
 _PROTOTYPES = {
     'tts_version': (c_char_p, []),
     'tts_default_config': (c_int, [POINTER(TtsConfig)]),
@@ -91,6 +102,11 @@ _PROTOTYPES = {
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     'tts_mel_spectrogram': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                     c_void_p]),
+    'tts_trim_bounds': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    'tts_default_feature_params': (c_int, [POINTER(TtsFeatureParams)]),
+    'tts_plan_features': (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(TtsFeatureParams), c_void_p]),
+    'tts_extract_features': (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(TtsFeatureParams), c_void_p, c_void_p,
+                                     c_void_p]),
     'tts_synthesize': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(TtsSynthParams), c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
     'tts_synthesize_host': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(TtsSynthParams), POINTER(c_int)]),
@@ -515,6 +531,61 @@ class Engine(object):
         d = self.to_device(x)
         self._check(self.lib.tts_db_convert(self.handle, d.ptr, x.size, mode, ref_db, max_db, d.ptr))
         return d.to_host()
+
+    # ------------------------------------------------------------------ dataset features
+    def feature_params(self, **kw):
+        """tts_default_feature_params with fields overridden by keyword (names of struct tts_feature_params)."""
+        p = TtsFeatureParams()
+        self._check(self.lib.tts_default_feature_params(byref(p)))
+        for k, v in kw.items():
+            if k == 'struct_size' or not hasattr(p, k):
+                raise TypeError('unknown feature parameter {!r}'.format(k))
+            setattr(p, k, v)
+        return p
+
+    @staticmethod
+    def _ragged(wavs):
+        wavs = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        if not wavs:
+            raise ValueError('no recordings')
+        offsets = np.zeros(len(wavs) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([w.size for w in wavs])
+        return np.concatenate(wavs), offsets
+
+    def trim_bounds(self, wavs, frame_length=2048, hop_length=512, top_db=60.0):
+        """librosa.effects.trim (0.6) interval of every recording of a list of 1-D float32 arrays: int64 (B, 2) {start, end}."""
+        flat, offsets = self._ragged(wavs)
+        B = len(wavs)
+        d = self.to_device(flat)
+        bounds = self.empty((B, 2), np.int64)
+        self._check(self.lib.tts_trim_bounds(self.handle, d.ptr, offsets.ctypes.data, B, int(frame_length), int(hop_length),
+                                             float(top_db), bounds.data_ptr()))
+        return bounds.to_host()
+
+    def extract_features(self, wavs, params=None):
+        """Features of a list of 1-D float32 recordings (tts_plan_features + tts_extract_features, one batch):
+        a list of (mel (T_red, n_mels r), lin (T_red, F r)) float32 arrays, as the reference's load_audio returns them."""
+        p = params if params is not None else self.feature_params()
+        flat, offsets = self._ragged(wavs)
+        B = len(wavs)
+        d = self.to_device(flat)
+        plan = np.zeros(3 * B, dtype=np.int64)
+        self._check(self.lib.tts_plan_features(self.handle, d.ptr, offsets.ctypes.data, B, byref(p), plan.ctypes.data))
+        plan = plan.reshape(B, 3)
+        rows = int(plan[:, 2].sum())
+        F = 1 + p.n_fft // 2
+        mel = self.empty((rows, p.n_mels))
+        lin = self.empty((rows, F))
+        self._check(self.lib.tts_extract_features(self.handle, d.ptr, offsets.ctypes.data, B, byref(p),
+                                                  plan.ctypes.data, mel.data_ptr(), lin.data_ptr()))
+        mel_h, lin_h = mel.to_host(), lin.to_host()
+        out, r0, r = [], 0, p.reduction
+        for b in range(B):
+            tp = int(plan[b, 2])
+            out.append((mel_h[r0:r0 + tp].reshape(tp // r, p.n_mels * r), lin_h[r0:r0 + tp].reshape(tp // r, F * r)))
+            r0 += tp
+        self.last_feature_plan = plan
+        return out
 
     # ------------------------------------------------------------------ profiling / debug
     def profile_reset(self):

@@ -1,0 +1,59 @@
+"""Mirror of reference audio/effects.py: silence trimming and cropping.
+
+``trim_silence`` is librosa.effects.trim (librosa 0.6: frame length 2048, hop 512, reference power = the loudest frame)
+computed by tts_trim_bounds on the GPU.  ``pitch_shift`` / ``time_stretch`` (resampling, phase vocoder) are out of scope."""
+import numpy as np
+
+from . import default_engine
+from .conversion import ms_to_samples
+
+
+def pitch_shift(wav, sampling_rate, octaves):
+    raise NotImplementedError('pitch_shift (librosa resampling, reference audio/effects.py:9-43) is out of scope')
+
+
+def time_stretch(wav, rate):
+    raise NotImplementedError('time_stretch (librosa phase vocoder, reference audio/effects.py:46-88) is out of scope')
+
+
+def trim_silence(wav, threshold_db=40, ref=np.max, engine=None):
+    """reference :188-215: (wav[start:end], np.array([start, end])) of librosa.effects.trim(wav, threshold_db, ref).
+    Only ``ref=np.max`` (the reference's default) is supported."""
+    if ref is not np.max:
+        raise NotImplementedError('trim_silence: only ref=np.max is supported')
+    eng = engine or default_engine()
+    wav = np.asarray(wav)
+    start, end = (int(v) for v in eng.trim_bounds([wav.astype(np.float32)], 2048, 512, float(threshold_db))[0])
+    return wav[start:end], np.array([start, end])
+
+
+def crop_silence_left(wav, sampling_rate, length_ms, safe_crop=True):
+    """reference :91-136: (wav[n_cropped:], n_cropped), n_cropped = min(samples(length_ms), leading silence) when
+    safe_crop."""
+    assert (length_ms > 0), 'Crop length must be greater 0.'
+    samples = ms_to_samples(length_ms, sampling_rate)
+    assert (samples < len(wav)), 'Crop length can not be greater than the total wav length.'
+    if safe_crop:
+        _, non_silence_region = trim_silence(wav)
+        samples = min(samples, non_silence_region[0])
+    return wav[samples:], samples
+
+
+def crop_silence_right(wav, sampling_rate, length_ms, safe_crop=True):
+    """reference :139-185: (wav[:-n_cropped], n_cropped).  As in the reference, n_cropped = 0 returns an empty array."""
+    assert (length_ms > 0), 'Crop length must be greater 0.'
+    samples = ms_to_samples(length_ms, sampling_rate)
+    assert (samples < len(wav)), 'Crop length can not be greater than the total wav length.'
+    if safe_crop:
+        _, non_silence_region = trim_silence(wav)
+        samples = min(samples, len(wav) - non_silence_region[1])
+    return wav[:-samples], samples
+
+
+def silence_interval_from_spectrogram(mag_spec_db, threshold_db, ref=np.max):
+    """reference :218-233 (host numpy): first and last frame (column) whose reference dB exceeds threshold_db, or None."""
+    ref_trim_spec_db = ref(mag_spec_db, axis=0)
+    nonzero = np.flatnonzero(np.array(ref_trim_spec_db > threshold_db, dtype=np.int32))
+    if len(nonzero) == 0:
+        return None
+    return np.min(nonzero), np.max(nonzero)

@@ -1,4 +1,5 @@
-"""Mirror of reference audio/io.py ``save_wav`` (:33-53): float32 WAV, optional peak normalisation.
+"""Mirror of reference audio/io.py: ``save_wav`` (:33-53, float32 WAV, optional peak normalisation) and ``load_wav``
+(:8-30, librosa.core.load of a RIFF/WAVE file at its native rate; standard library and numpy only).
 
 librosa.output.write_wav(path, y.astype(float32), sr, norm=True) = util.normalize(y, norm=inf)
 then scipy.io.wavfile.write of float32 samples (WAVE_FORMAT_IEEE_FLOAT).  The normalisation runs
@@ -40,5 +41,65 @@ def save_wav(wav_path, wav, sampling_rate, norm=False, engine=None):
     _write_float32_wav(wav_path, wav, sampling_rate)
 
 
+_PCM, _IEEE_FLOAT, _EXTENSIBLE = 1, 3, 0xFFFE
+
+
+def _read_wav(path):
+    """-> (format tag, channels, rate, bits, raw data bytes) of a RIFF/WAVE file."""
+    with open(path, 'rb') as f:
+        blob = f.read()
+    if len(blob) < 12 or blob[:4] != b'RIFF' or blob[8:12] != b'WAVE':
+        raise ValueError('{}: not a RIFF/WAVE file (format tag {!r})'.format(path, blob[:4]))
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= len(blob):
+        cid, size = blob[pos:pos + 4], struct.unpack('<I', blob[pos + 4:pos + 8])[0]
+        body = blob[pos + 8:pos + 8 + size]
+        if cid == b'fmt ':
+            if len(body) < 16:
+                raise ValueError('{}: truncated fmt chunk'.format(path))
+            tag, channels, rate, _, _, bits = struct.unpack('<HHIIHH', body[:16])
+            if tag == _EXTENSIBLE and len(body) >= 26:
+                tag = struct.unpack('<H', body[24:26])[0]   # first two bytes of the sub-format GUID
+            fmt = (tag, channels, rate, bits)
+        elif cid == b'data':
+            data = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or data is None:
+        raise ValueError('{}: no {} chunk'.format(path, 'fmt' if fmt is None else 'data'))
+    return fmt + (data,)
+
+
 def load_wav(wav_path, sampling_rate=None, offset=0.0, duration=None):
-    raise NotImplementedError('load_wav (librosa resampling loader) is outside the inference path')
+    """reference audio/io.py:8-30: librosa.core.load(path, sr=None, offset, duration) of a RIFF/WAVE file ->
+    (float32 mono samples, native rate).  PCM 8 (unsigned), 16, 24, 32 bit and IEEE float32 / float64; integers scaled by
+    1 / 2 ** (bits - 1), channels averaged; offset / duration in seconds at int(round(sr * x)) samples.  Resampling is out of
+    scope: any `sampling_rate` other than None or the native rate raises NotImplementedError."""
+    tag, channels, rate, bits, raw = _read_wav(wav_path)
+    if sampling_rate is not None and int(sampling_rate) != rate:
+        raise NotImplementedError('load_wav: resampling {} Hz -> {} Hz is not supported'.format(rate, sampling_rate))
+    if channels < 1:
+        raise ValueError('{}: {} channels'.format(wav_path, channels))
+    if tag == _PCM and bits in (8, 16, 24, 32):
+        width = bits // 8
+        n = len(raw) // (width * channels)
+        raw = raw[:n * width * channels]
+        if bits == 8:
+            x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0)
+        elif bits == 24:
+            b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+            x = np.where(v >= 1 << 23, v - (1 << 24), v).astype(np.float32)
+        else:
+            x = np.frombuffer(raw, dtype='<i{}'.format(width)).astype(np.float32)
+        x = x * np.float32(1.0 / float(1 << (bits - 1)))
+    elif tag == _IEEE_FLOAT and bits in (32, 64):
+        width = bits // 8
+        n = len(raw) // (width * channels)
+        x = np.frombuffer(raw[:n * width * channels], dtype='<f{}'.format(width)).astype(np.float32)
+    else:
+        raise ValueError('{}: unsupported WAV format tag {} with {} bits per sample'.format(wav_path, tag, bits))
+    x = x.reshape(-1, channels)
+    y = x[:, 0].copy() if channels == 1 else np.mean(x, axis=1, dtype=np.float32)
+    start = int(round(rate * offset))
+    stop = None if duration is None else start + int(round(rate * duration))
+    return np.ascontiguousarray(y[start:stop], dtype=np.float32), rate

@@ -12,15 +12,18 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libsstts_hip.so')
-SOURCES = ['gemm_f32.hip', 'cbhg_tail.hip', 'gru.hip', 'decoder.hip', 'decoder_persistent.hip', 'decoder_ws.hip', 'griffin_lim.hip', 'griffin_lim_generic.hip', 'reserve.hip', 'eval_loss.hip', 'api_handle.hip', 'api_stages.hip', 'api_pipeline.hip']
-HEADERS = ['tts_common.h', 'decoder.h', 'griffin_lim.h', 'api_internal.h', os.path.join('..', '..', 'include', 'sstts_hip.h')]
+SOURCES = ['gemm_f32.hip', 'cbhg_tail.hip', 'gru.hip', 'decoder.hip', 'decoder_persistent.hip', 'decoder_ws.hip', 'griffin_lim.hip', 'griffin_lim_generic.hip', 'reserve.hip', 'eval_loss.hip', 'features.hip', 'api_handle.hip', 'api_stages.hip', 'api_pipeline.hip']
+HEADERS = ['tts_common.h', 'fft_wave.h', 'fft_lds.h', 'decoder.h', 'griffin_lim.h', 'api_internal.h', os.path.join('..', '..', 'include', 'sstts_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-Wno-unused-result']
 # Packed f32 VALU ops (v_pk_add/mul/fma_f32) issue slower than the two scalar ops they replace on gfx950 and
 # need aligned register pairs (extra v_mov); the SLP vectoriser forms them from complex arithmetic.  Measured
 # on the wave-level FFT: 2.70 -> 2.02 us, 92 -> 67 VGPRs (tools/fft_microbench.hip).
 # griffin_lim_generic.hip: no packed-f32 selection at all (its complex type is two scalars; see the note there -- packed results
 # were stored wrong when MFMA waves of another stream shared the compute unit)
-EXTRA_FLAGS = {'griffin_lim.hip': ['-fno-slp-vectorize'], 'griffin_lim_generic.hip': ['-fno-slp-vectorize']}
+# features.hip: no packed-f32 instruction either (the wave FFT in its scalar form, fft_wave.h FFT_WAVE_SCALAR); the vector
+# combiner would still pair the two halves of a 64-bit LDS load of a complex number into v_pk_add_f32 (30 of them), hence its switch
+EXTRA_FLAGS = {'griffin_lim.hip': ['-fno-slp-vectorize'], 'griffin_lim_generic.hip': ['-fno-slp-vectorize'],
+               'features.hip': ['-fno-slp-vectorize', '-mllvm', '-disable-vector-combine']}
 
 
 def _digest(paths, extra=()):

@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -645,6 +645,7 @@ int tts_destroy(tts_handle_t h) {
     if (h->gl.tables) hipFree(h->gl.tables);
     if (h->an.window) hipFree(h->an.window);
     if (h->an.mel_wt) hipFree(h->an.mel_wt);
+    feat_release(h);
     if (h->an.flag) hipFree(h->an.flag);
     if (h->front) {
         hipStreamSynchronize(h->front);

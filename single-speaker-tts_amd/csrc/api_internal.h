@@ -48,7 +48,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -291,6 +291,19 @@ struct tts_handle_s {
         int* flag = nullptr;
     } an;
 
+    // dataset feature pass (features.hip): tables of the last configuration, pinned staging of the per-recording descriptors
+    struct {
+        int n_fft = 0, win = 0;
+        float* window = nullptr;          // [win] periodic hann
+        int sr = 0, n_mels = 0;
+        float fmin = 0, fmax = 0;
+        float* mel_w = nullptr;           // packed non-zero filterbank weights
+        int* mel_band = nullptr;          // [n_mels][2] {first bin, first weight}, [n_mels] end bins follow
+        void* staging = nullptr;          // pinned host buffer of the descriptor uploads
+        size_t staging_bytes = 0;
+        hipEvent_t staged = nullptr;      // the last upload from `staging` has been read
+    } feat;
+
     // profiling
     std::vector<ProfSpan> spans;
     double prof_ms[ST_COUNT] = {0};
@@ -379,6 +392,7 @@ int graph_quiesce(tts_handle_t h);
 int graph_drop(tts_handle_t h);
 int ws_get(tts_handle_t h, const char* name, size_t bytes, void** out);
 void prof_collect(tts_handle_t h);
+void feat_release(tts_handle_t h);   // features.hip: the feature pass's tables and staging
 GemmGroup dense_group(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M, int N, int K, int act);
 GemmGroup conv_group(const float* A, int Cin, int ktaps, int T, const float* Wt, const float* bias, const float* scale, const float* shift, float* C, int ldc, int coff, int M, int N, int act, int pool);
 int gemm_attach_image(tts_handle_t h, GemmGroup& g, bool refresh = false);

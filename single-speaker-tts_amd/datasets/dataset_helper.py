@@ -5,7 +5,9 @@ helpers ``sent2idx`` (:51-68), ``idx2sent`` (:70-87), ``replace_abbreviations`` 
 ``utf8_to_ascii`` (:89-109), ``update_char_dict`` (:111-125) and the static
 ``apply_reduction_padding`` (:357-401); for evaluation, the feature cache reader
 ``cache_precalculated_features`` (:285-305) over the ``<wav stem>.npz`` files that ``pre_compute_features``
-(:326-356) writes.  Computing features from ``.wav`` files (librosa) is out of scope.
+(:326-356) writes.  ``compute_features`` / ``pre_compute_features`` make those files from the ``.wav`` recordings as the
+reference's ``load_audio`` does (lj_speech.py:106-156: load, trim, |STFT|, HTK mel, dB, normalisation, reduction padding),
+batched on the GPU (tts_plan_features / tts_extract_features), without librosa.
 
 Quirks kept on purpose: abbreviations are applied with ``str.replace`` in dict order (so
 ``'.' -> ''`` must come last), characters outside the vocabulary raise ``KeyError``, the EOS id is
@@ -16,6 +18,12 @@ import numpy as np
 
 
 class DatasetHelper(object):
+    # dB constants of the feature normalisation; a loader sets its own (LJSpeechDatasetHelper: reference lj_speech.py:20-29)
+    mel_mag_ref_db = None
+    mel_mag_max_db = None
+    linear_ref_db = None
+    linear_mag_max_db = None
+
     def __init__(self, dataset_folder, char_dict, fill_dict):
         self._dataset_folder = dataset_folder
         self._char2idx_dict = char_dict
@@ -91,9 +99,8 @@ class DatasetHelper(object):
         ``.npz`` raises FileNotFoundError naming it."""
         path = DatasetHelper.feature_path(wav_path)
         if not os.path.isfile(path):
-            raise FileNotFoundError('pre-computed features {} not found (written by the reference\'s '
-                                    'DatasetHelper.pre_compute_features; computing them from the .wav is not '
-                                    'part of this package)'.format(path))
+            raise FileNotFoundError('pre-computed features {} not found (written by DatasetHelper.pre_compute_features: '
+                                    'python -m single-speaker-tts_amd.tacotron.dataset_precalc_features)'.format(path))
         with np.load(path) as z:
             return (np.asarray(z['mel_mag_db'], dtype=np.float32), np.asarray(z['linear_mag_db'], dtype=np.float32))
 
@@ -105,6 +112,52 @@ class DatasetHelper(object):
             mel, lin = DatasetHelper.load_features(wav_path)
             cache[os.path.splitext(wav_path)[0]] = dict(mel_mag_db=mel, linear_mag_db=lin)
         return cache
+
+    @classmethod
+    def feature_params(cls, engine, hparams=None):
+        """tts_feature_params of the reference's load_audio: model_params' analysis settings, the class's dB constants,
+        librosa.effects.trim's defaults (top_db 60, frames of 2048 at hop 512)."""
+        from ..audio.conversion import ms_to_samples
+        from ..tacotron.params import model_params
+        hp = hparams or model_params
+        if cls.mel_mag_ref_db is None:
+            raise NotImplementedError('{} defines no dB constants for the features'.format(cls.__name__))
+        return engine.feature_params(
+            n_fft=hp.n_fft, win_length=ms_to_samples(hp.win_len, hp.sampling_rate),
+            hop_length=ms_to_samples(hp.win_hop, hp.sampling_rate), sampling_rate=hp.sampling_rate, n_mels=hp.n_mels,
+            fmin=float(hp.mel_fmin), fmax=float(hp.mel_fmax), mel_ref_db=cls.mel_mag_ref_db, mel_max_db=cls.mel_mag_max_db,
+            linear_ref_db=cls.linear_ref_db, linear_max_db=cls.linear_mag_max_db, normalize=1, reduction=hp.reduction,
+            trim=1, trim_top_db=60.0, trim_frame_length=2048, trim_hop_length=512)
+
+    @classmethod
+    def compute_features(cls, wav_paths, batch_size=32, engine=None, hparams=None):
+        """Features of every recording as the reference's load_audio returns them: a list of (mel_mag_db (T_red,
+        n_mels r), linear_mag_db (T_red, F r)) float32, one extract_features call per batch of ``batch_size`` files.
+        The recordings are read at their native rate (load_wav; no resampling, as the reference's load_wav(path))."""
+        from ..audio import default_engine
+        from ..audio.io import load_wav
+        eng = engine or default_engine()
+        params = cls.feature_params(eng, hparams)
+        out = []
+        paths = [p.decode() if isinstance(p, bytes) else p for p in wav_paths]
+        for i in range(0, len(paths), max(1, int(batch_size))):
+            wavs = [load_wav(p)[0] for p in paths[i:i + batch_size]]
+            out.extend(eng.extract_features(wavs, params))
+        return out
+
+    def pre_compute_features(self, paths, batch_size=32, engine=None):
+        """reference :326-356: ``<path>/<stem>.npz`` next to every ``<path>/<stem>.wav``, keys ``mel_mag_db`` /
+        ``linear_mag_db`` (what load_features reads)."""
+        paths = [p.decode() if isinstance(p, bytes) else p for p in paths]
+        print('Loaded {} dataset entries.'.format(len(paths)))
+        batch_size = max(1, int(batch_size))
+        for i in range(0, len(paths), batch_size):
+            chunk = paths[i:i + batch_size]
+            feats = self.compute_features(chunk, batch_size=batch_size, engine=engine)
+            for wav_path, (mel_mag_db, linear_mag_db) in zip(chunk, feats):
+                out_path = self.feature_path(wav_path)
+                print('Writing: "{}"'.format(out_path))
+                np.savez(out_path, mel_mag_db=mel_mag_db, linear_mag_db=linear_mag_db)
 
     def load_audio(self, file_path):
         """Evaluation targets of one recording, as the reference's ``load_audio`` returns them (lj_speech.py:106-156):

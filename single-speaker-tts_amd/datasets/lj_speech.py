@@ -1,7 +1,7 @@
 """LJ-Speech helper: dB constants, the abbreviation table and the corpus listing reader of reference
-datasets/lj_speech.py (:20-29, :37-60, :62-103).  Audio features come from the pre-computed ``.npz``
-files (``DatasetHelper.load_features``); computing them from the ``.wav`` (``load_audio`` :106-156,
-librosa) is out of scope -- the analysis kernels it would use are in ``audio.features``."""
+datasets/lj_speech.py (:20-29, :37-60, :62-103).  Evaluation reads audio features from the pre-computed ``.npz``
+files (``DatasetHelper.load_features``); ``DatasetHelper.pre_compute_features`` writes them from the ``.wav`` files
+as the reference's ``load_audio`` (:106-156) computes them, with these dB constants (features.hip on the GPU)."""
 import csv
 import os
 

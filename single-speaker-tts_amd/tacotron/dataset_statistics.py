@@ -1,0 +1,44 @@
+"""Mirror of the reference's ``tacotron/dataset_statistics.py``: the vocabulary of a dataset's transcripts and the four dB
+constants of the feature normalisation (datasets.statistics.collect_decibel_statistics), printed under the reference's
+names -- which it crosses: the mean max mel dB is printed as ``mel_mag_ref_db``, the mean min as ``mel_mag_max_db``, and
+likewise for the linear constants.
+
+    python -m single-speaker-tts_amd.tacotron.dataset_statistics [--dataset-folder DIR]"""
+import argparse
+import os
+
+from ..datasets.lj_speech import LJSpeechDatasetHelper
+from ..datasets.statistics import collect_decibel_statistics
+from .params import dataset_params
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='tacotron.dataset_statistics')
+    ap.add_argument('--dataset-folder', default=dataset_params.dataset_folder)
+    args = ap.parse_args(argv)
+    dataset = LJSpeechDatasetHelper(dataset_folder=args.dataset_folder, char_dict={'pad': 0, 'eos': 1}, fill_dict=True)
+    if not os.path.exists(args.dataset_folder):
+        print("Dataset folder '{}' could not be found.".format(args.dataset_folder))
+        return 1
+    print('Dataset: {}'.format(args.dataset_folder))
+    print('Loading dataset ...')
+    _, _, paths = dataset.load()
+    print('Dataset vocabulary:')
+    sorted_by_value = sorted(dataset._char2idx_dict.items(), key=lambda kv: kv[1])
+    print('vocabulary_dict={')
+    for k, v in sorted_by_value:
+        print("    '{}': {},".format(k, v))
+    print('},')
+    print('vocabulary_size={}'.format(len(sorted_by_value)))
+    print('\n\n')
+    print('Collecting decibel statistics for {} files ...'.format(len(paths)))
+    min_linear_db, max_linear_db, min_mel_db, max_mel_db = collect_decibel_statistics(paths)
+    print('mel_mag_ref_db = ', max_mel_db)
+    print('mel_mag_max_db = ', min_mel_db)
+    print('linear_ref_db = ', max_linear_db)
+    print('linear_mag_max_db = ', min_linear_db)
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

@@ -480,51 +480,10 @@ GemmGroup conv_group(const float* A, int Cin, int ktaps, int T, const float* Wt,
 }
 
 
-// Attach the pre-split image of g.Wt (made now if this weight matrix has none yet for this (N, K, Cin); `refresh`: made
-// again whatever the cache holds -- tts_debug_gemm, whose caller owns the weights and may have rewritten them).
-int gemm_attach_image(tts_handle_t h, GemmGroup& g, bool refresh) {
-    g.Wimg = nullptr;
-    if (!h->gemm_presplit) return TTS_OK;
-    auto& im = h->wimg[g.Wt];
-    const size_t bytes = gemm_weight_image_bytes(g.N, g.K);
-    const bool fresh = im.p == nullptr || im.N != g.N || im.K != g.K || im.Cin != g.Cin;
-    if (fresh || refresh) {
-        if (im.bytes < bytes) {
-            if (im.p) {
-                int rc = sync_all(h);   // (a launch that reads the old image may be in flight)
-                if (rc) return rc;
-                HIPCHK(h, hipFree(im.p));
-                im.p = nullptr; im.bytes = 0;
-            }
-            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&im.p), bytes));
-            im.bytes = bytes;
-        }
-        im.N = g.N; im.K = g.K; im.Cin = g.Cin;
-        HIPCHK(h, launch_gemm_pack_weights(h->stream, g.Wt, im.p, g.N, g.K, g.Cin));
-        // a new image is complete before any stream may use it (the first call of a shape runs unpipelined and makes them
-        // all; later calls find them in the cache)
-        if (fresh) HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    g.Wimg = im.p;
-    return TTS_OK;
-}
-
-void gemm_drop_images(tts_handle_t h) {
-    for (auto& kv : h->wimg)
-        if (kv.second.p) hipFree(kv.second.p);
-    h->wimg.clear();
-}
-
-
 int run_single(tts_handle_t h, const GemmGroup& g) {
     GemmBatch b;
     std::memset(&b, 0, sizeof(b));
     b.g[0] = g;
-    b.ps = h->gemm_ps;
-    {
-        int rc = gemm_attach_image(h, b.g[0]);
-        if (rc) return rc;
-    }
     HIPCHK(h, launch_gemm(h->stream, b, 1));
     return TTS_OK;
 }
@@ -617,7 +576,6 @@ int tts_create(const tts_config_t* cfg, int device_id, tts_handle_t* out) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || cus < 1) cus = 256;
         h->n_cus_dev = cus;
     }
-    if (h->use_graph && !graph_runtime_ok(nullptr)) h->use_graph = 0;
     build_manifest(h);
     *out = h;
     return TTS_OK;
@@ -687,7 +645,6 @@ int tts_destroy(tts_handle_t h) {
     if (h->encs) hipStreamDestroy(h->encs);
     if (h->ev_serial_done) hipEventDestroy(h->ev_serial_done);
     if (h->ev_graph_done) hipEventDestroy(h->ev_graph_done);
-    gemm_drop_images(h);
     for (int i = 0; i < 2; ++i) {
         if (h->ev_post_done[i]) hipEventDestroy(h->ev_post_done[i]);
         if (h->ev_gl_done[i]) hipEventDestroy(h->ev_gl_done[i]);
@@ -755,12 +712,6 @@ int tts_set_option(tts_handle_t h, const char* key, int value) {
     }
     else if (!std::strcmp(key, "gl_pair")) h->gl_pair = value;
     else if (!std::strcmp(key, "gl_wide_from")) h->gl_wide = value < -2 ? -2 : value;
-    else if (!std::strcmp(key, "gemm_presplit") || !std::strcmp(key, "gemm_ps")) {
-        if (value && !gemm_experiments_built())
-            return fail(h, TTS_ERR_UNSUPPORTED, std::string(key) + ": a measured-and-not-faster GEMM variant of round 5; its kernels are only "
-                        "in a tools build of gemm_f32.hip (-DGEMM_EXPERIMENTS, tools/build_variant.sh)");
-        (key[5] == 'p' && key[6] == 'r' ? h->gemm_presplit : h->gemm_ps) = value;
-    }
     else if (!std::strcmp(key, "pd_ws")) {
         if (value != h->pd_ws) {   // (may change whether a pipelined call's decoder is a persistent kernel at all)
             int rc = sync_all(h);
@@ -968,7 +919,6 @@ int tts_finalize_weights(tts_handle_t h) {
         int rc = graph_drop(h);
         if (rc) return rc;
     }
-    gemm_drop_images(h);   // (keyed by addresses inside the old arena)
     if (h->arena) hipFree(h->arena);
     h->arena = nullptr;
     HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&h->arena), p.host.size() * sizeof(float)));

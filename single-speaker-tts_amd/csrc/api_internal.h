@@ -61,9 +61,6 @@ struct ProfSpan {
 }  // namespace tts_api
 using namespace tts_api;   // (the handle is a global type: include/sstts_hip.h declares tts_handle_s)
 
-#ifndef TTS_USE_GRAPH_DEFAULT
-#define TTS_USE_GRAPH_DEFAULT 0   // (tools: -DTTS_USE_GRAPH_DEFAULT=1 builds a library whose handles replay the decoder graph)
-#endif
 struct tts_handle_s {
     tts_config_t cfg;
     int device = 0;
@@ -80,7 +77,7 @@ struct tts_handle_s {
     // DEBUG_CLR_GRAPH_PACKET_CAPTURE=0, i.e. without the runtime's pre-built AQL packets -- the graph's dec_gemm_kernel nodes use
     // 16 bytes of scratch); the same binary and sequence are right on the 7.2 runtime, graph on, every time
     // (profiles/r06_experiment_hipgraph.txt).
-    int use_graph = TTS_USE_GRAPH_DEFAULT;   // (a tools build with the default ON still checks the runtime: tts_create)
+    int use_graph = 0;
     int fused_tail = 1;          // CBHG: lifter + highway stack + GRU input projections as one launch (cbhg_tail.hip)
     bool tail_configured = false;
     int profile = 0;
@@ -137,14 +134,6 @@ struct tts_handle_s {
     //  call pipeline: `defer_projection`.  On the front stream behind its decoder it gave the same 14.45 ms per step in round 5;
     //  the option that switched it is gone)
     bool ws_configured = false;
-    // Round 5's two GEMM variants, measured and not faster (profiles/r05_experiment_gemm_presplit.txt, HISTORY.md part C): weights
-    // pre-split into the kernel's bf16 LDS images ("gemm_presplit": images made on first use per weight matrix, keyed by its
-    // address in the arena; tts_finalize_weights drops them) and the producer / consumer form of the kernel ("gemm_ps").  Their
-    // kernels are only compiled into a tools build of gemm_f32.hip (-DGEMM_EXPERIMENTS); the shipped library refuses both options.
-    struct WeightImage { unsigned char* p = nullptr; size_t bytes = 0; int N = 0, K = 0, Cin = 0; };
-    std::map<const float*, WeightImage> wimg;
-    int gemm_presplit = 0;
-    int gemm_ps = 0;
     int gl_pair = 3;                 // Griffin-Lim iterations per launch (1..3) where nothing per-iteration is asked for
     // First Griffin-Lim launch of a pipelined call that is cut for all compute units (gl_run, `wide_from`): -1 = by the rule
     // in gl_wide_from() below, -2 = never, >= 0 = that launch index.
@@ -322,16 +311,6 @@ namespace tts_api {
         }                                                                                       \
     } while (0)
 
-
-#define HIPCHK(h, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) {                                                                 \
-            (h)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-            return TTS_ERR_HIP;                                                                 \
-        }                                                                                       \
-    } while (0)
-
 // Every entry point that takes a handle runs on the handle's device, whatever device is current on the calling
 // thread (one process may hold handles on several GPUs, or a caller may have switched devices after tts_create);
 // the caller's current device is restored on return.
@@ -395,8 +374,6 @@ void prof_collect(tts_handle_t h);
 void feat_release(tts_handle_t h);   // features.hip: the feature pass's tables and staging
 GemmGroup dense_group(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M, int N, int K, int act);
 GemmGroup conv_group(const float* A, int Cin, int ktaps, int T, const float* Wt, const float* bias, const float* scale, const float* shift, float* C, int ldc, int coff, int M, int N, int act, int pool);
-int gemm_attach_image(tts_handle_t h, GemmGroup& g, bool refresh = false);
-void gemm_drop_images(tts_handle_t h);
 int run_single(tts_handle_t h, const GemmGroup& g);
 bool graph_runtime_ok(int* have);
 int run_cbhg(tts_handle_t h, const CbhgWeights& w, const char* tag, const float* x, int B, int T, float* out, int64_t* launches);
@@ -424,14 +401,5 @@ bool denorm_can_assert(float ref_db, float max_db);
 int denorm_flag_arm(tts_handle_t h, int** flag);
 int denorm_flag_read(tts_handle_t h);
 int gl_wide_from(tts_handle_t h, int B, int Ts, int n_steps, int T, int n_iter);
-
-#define WS(h, name, type, count, var)                                             \
-    type* var = nullptr;                                                          \
-    {                                                                             \
-        void* _p = nullptr;                                                       \
-        int _rc = ws_get(h, name, (size_t)(count) * sizeof(type), &_p);           \
-        if (_rc != TTS_OK) return _rc;                                            \
-        var = reinterpret_cast<type*>(_p);                                        \
-    }
 
 }  // namespace tts_api

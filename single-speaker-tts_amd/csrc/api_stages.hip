@@ -33,11 +33,6 @@ int run_cbhg(tts_handle_t h, const CbhgWeights& w, const char* tag, const float*
             b.g[i] = conv_group(x, w.c_in, k + 1, T, w.bank_wt[k], w.bank_b[k], w.bank_scale[k], w.bank_shift[k], bank,
                                 NB * NF, k * NF, M, NF, ACT_RELU, 0);
         }
-        for (int i = 0; i < ng; ++i) {
-            int rc = gemm_attach_image(h, b.g[i]);
-            if (rc) return rc;
-        }
-        b.ps = h->gemm_ps;
         HIPCHK(h, launch_gemm(h->stream, b, ng));
         ++*launches;
     }
@@ -49,11 +44,7 @@ int run_cbhg(tts_handle_t h, const CbhgWeights& w, const char* tag, const float*
         const int slices = gemm_splitk_slices(g.K);
         if (slices > 1) {
             WS(h, (t + ".splitk").c_str(), float, (size_t)slices * M * g.N, part);
-            {
-                int rc = gemm_attach_image(h, g);
-                if (rc) return rc;
-            }
-            HIPCHK(h, launch_gemm_splitk(h->stream, g, slices, part, h->gemm_ps));
+            HIPCHK(h, launch_gemm_splitk(h->stream, g, slices, part));
             ++*launches;
         } else {
             int rc = run_single(h, g);
@@ -486,13 +477,6 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
             q.mse_partial = want_mse ? msep : nullptr;
             if (want_mse) mse_chunks = q.slots_per_utt;
             next_counter(q);
-#ifdef GL_TIMELINE   // tools only: stamps of workgroup 0 during the last launch
-            WS(h, "gl.timeline", unsigned long long, 1024 + 64 * 16, tl);
-            if (it + n_stage >= n_iter) {
-                HIPCHK(h, hipMemsetAsync(tl, 0, (1024 + 64 * 16) * sizeof(unsigned long long), h->stream));
-                p.dbg = pw.dbg = tl;
-            }
-#endif
             // no more workgroups than the plan counts on: one that finds its compute unit taken (the call pipeline's other
             // stream) would start when the first of the others leaves, load its tables, find no item and only
             // lengthen the launch
@@ -501,46 +485,6 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
             it += n_stage;
             ++launch_idx;
         }
-#ifdef GL_TIMELINE
-        if (n_iter > 0) {
-            std::vector<unsigned long long> host(1024 + 64 * 16);
-            HIPCHK(h, hipMemcpyAsync(host.data(), p.dbg, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            {   // per-wave stamps of workgroup 0
-                unsigned long long w0 = ~0ull;
-                for (int i = 1024; i < 1024 + 64 * 16; ++i) if (host[i] && host[i] < w0) w0 = host[i];
-                for (int w = 0; w < 16; ++w) {
-                    bool any = false;
-                    for (int i = 0; i < 64; ++i) any = any || host[1024 + w * 64 + i];
-                    if (!any) continue;
-                    fprintf(stderr, "wave %2d:", w);
-                    for (int i = 0; i < 64; ++i) {
-                        const unsigned long long v = host[1024 + w * 64 + i];
-                        if (v) fprintf(stderr, " [%d]%.1f", i, (double)(v - w0) * 0.01);
-                    }
-                    fprintf(stderr, "\n");
-                }
-            }
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (int w = 0; w < 512; ++w) if (host[2 * w]) { t0 = std::min(t0, host[2 * w]); t1 = std::max(t1, host[2 * w + 1]); }
-            std::vector<double> ends, starts;
-            for (int w = 0; w < 512; ++w) if (host[2 * w]) { starts.push_back((host[2 * w] - t0) * 0.01); ends.push_back((host[2 * w + 1] - t0) * 0.01); }
-            std::sort(ends.begin(), ends.end());
-            std::sort(starts.begin(), starts.end());
-            const size_t n = ends.size();
-            double mean = 0; for (double e : ends) mean += e; mean /= n ? n : 1;
-            fprintf(stderr, "workgroups %zu: start last %.1f us; end min %.1f p10 %.1f median %.1f mean %.1f p90 %.1f max %.1f us\n", n,
-                    starts.back(), ends.front(), ends[n / 10], ends[n / 2], mean, ends[n * 9 / 10], ends.back());
-            if (getenv("GL_TIMELINE_WGS"))   // every workgroup: block, XCC, first item, runs, start, end
-                for (int w = 0; w < 512; ++w)
-                    if (host[2 * w]) {
-                        const unsigned long long m = host[1536 + w];
-                        fprintf(stderr, "wg %3d xcc %d item %4d runs %d start %.1f end %.1f\n", w, (int)((m >> 48) & 0xf), (int)(m & 0xffffffffu),
-                                (int)((m >> 32) & 0xffff), (host[2 * w] - t0) * 0.01, (host[2 * w + 1] - t0) * 0.01);
-                    }
-            p.dbg = pw.dbg = nullptr;
-        }
-#endif
     }
     if (mse) {
         if (n_iter > 0) {
@@ -1136,23 +1080,14 @@ int tts_debug_gemm(tts_handle_t h, const float* A, const float* Wt, float* C, in
     DeviceScope dev_scope(h);
     if (!h || !A || !Wt || !C || M < 1 || N < 1 || Cin < 4 || (Cin & 3) || ktaps < 1 || T < 1 || M % T) return TTS_ERR_INVALID;
     GemmGroup g = conv_group(A, Cin, ktaps, T, Wt, nullptr, nullptr, nullptr, C, N, 0, M, N, ACT_NONE, pool);
-    {   // the caller's weights: their image is made again on every call (outside the timed span)
-        int rc = gemm_attach_image(h, g, true);
-        if (rc) return rc;
-    }
     ProfScope ps(h, ST_DEBUG_GEMM, 1);
     const int slices = gemm_splitk_slices(g.K);   // same rule as the CBHG projections
     if (slices > 1) {
         WS(h, "debug.splitk", float, (size_t)slices * M * N, part);
-        HIPCHK(h, launch_gemm_splitk(h->stream, g, slices, part, h->gemm_ps));
+        HIPCHK(h, launch_gemm_splitk(h->stream, g, slices, part));
         return TTS_OK;
     }
-    GemmBatch b;
-    std::memset(&b, 0, sizeof(b));
-    b.g[0] = g;
-    b.ps = h->gemm_ps;
-    HIPCHK(h, launch_gemm(h->stream, b, 1));
-    return TTS_OK;
+    return run_single(h, g);
 }
 
 

@@ -46,12 +46,8 @@ namespace tts {
 // beside Griffin-Lim: one pass and two rows at a time (round-2 start) 15.16 / 17.29 ms, 2 and 4: 14.87 / 17.24, 2 and 8:
 // 15.05 / 17.27, 3 and 8: 15.78 / 17.60 (the prefetched keys live across the wait for the cluster and spill).  The phase
 // is bound by the cluster's arrival skew, not by its dependent memory trips.
-#ifndef PD_KB
 #define PD_KB 2
-#endif
-#ifndef PD_VB
 #define PD_VB 4
-#endif
 
 typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned pd_u32x4;
 
@@ -71,17 +67,6 @@ __device__ __forceinline__ void pd_st4(const __amdgpu_buffer_rsrc_t& rs, unsigne
 // all four column blocks [r | u | hh | xi] come from the same staged [x ; h] tile, r and u never leave the
 // workgroup, so the cell is ONE hop: the second pass continues on the tile of the first (`cont`).
 enum PdEpi { PD_ACT = 0, PD_GATES = 1, PD_CAND = 2, PD_CUDNN_RU = 3, PD_CUDNN_HX = 4 };
-
-#ifdef PD_TIMELINE   // tools only: s_memrealtime stamps (100 MHz) of workgroup 0 in step 100, [phase][8], kept in LDS
-__device__ unsigned long long* pd_dbg = nullptr;
-__device__ __shared__ int pd_tl_step, pd_tl_phase;
-__device__ __shared__ float* pd_tl_lds;
-#define PD_STAMP(I)                                                                                              \
-    if (blockIdx.x == 0 && threadIdx.x == 0 && pd_tl_step == 100)                                               \
-        reinterpret_cast<unsigned long long*>(pd_tl_lds)[pd_tl_phase * 8 + (I)] = __builtin_amdgcn_s_memrealtime();
-#else
-#define PD_STAMP(I)
-#endif
 
 struct PdPhase {
     const float* a0; int lda0; int k0;   // A columns [0, k0): a0 (null = zeros), row stride lda0
@@ -107,11 +92,7 @@ struct PdPhase {
 #define PD_OFF_R (PD_OFF_U + 16 * 32)
 #define PD_OFF_CTRL (PD_OFF_R + 16 * 32)
 #define PD_OFF_SC (PD_OFF_CTRL + 16)
-#ifdef PD_TIMELINE
-size_t pd_lds_bytes(int Ts) { return ((size_t)PD_OFF_SC + 2 * (size_t)((Ts + 3) & ~3)) * sizeof(float) + 1024; }
-#else
 size_t pd_lds_bytes(int Ts) { return ((size_t)PD_OFF_SC + 2 * (size_t)((Ts + 3) & ~3)) * sizeof(float); }
-#endif
 
 // Start of a phase: wait until `target` arrivals have been counted on the cluster's counter (lane 0 polls, everybody
 // meets at the barrier).  The arrival of THIS workgroup for the previous phase was signalled when that phase ended
@@ -122,9 +103,7 @@ __device__ __forceinline__ void pd_wait(unsigned* cnt, unsigned target, int* sta
         if (ctrl[0] == 0) {
             unsigned spins = 0;
             while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-#ifndef PD_NO_POLL_SLEEP
                 __builtin_amdgcn_s_sleep(1);
-#endif
                 if ((++spins & 1023u) == 0 &&
                     (spins > PD_SPIN_LIMIT || __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                     __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -207,9 +186,7 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
         }
     }
 
-    PD_STAMP(0)
     if (!ph.cont) pd_wait(cnt, target, status, ctrl);
-    PD_STAMP(1)
     if (ph.delay && !ph.cont && j == 3)   // a late stager: what a workgroup that clears its poll late looks like to its peers
         for (int i = 0; i < ph.delay; ++i) __builtin_amdgcn_s_sleep(127);
 
@@ -230,7 +207,6 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
             if (sdst[u] >= 0) *reinterpret_cast<float4*>(As + sdst[u]) = sv[u];
         __syncthreads();
     }
-    PD_STAMP(2)
 
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -248,7 +224,6 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
 #pragma unroll
     for (int i = 0; i < 4; ++i) red[(wave * 16 + q * 4 + i) * PD_RED_LD + r] = acc[i];
     __syncthreads();
-    PD_STAMP(3)
 
     // ---- epilogue: thread e owns (row, 4 consecutive units) of every gate; K slices added in a fixed order
     if (tid < tpg * 64) {
@@ -315,10 +290,8 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
             }
         }
     }
-    PD_STAMP(4)
     if (ph.more) __syncthreads();   // r / u are in LDS, the partial tiles may be overwritten
     else if (tid < tpg * 64) pd_publish_wave(cnt, PD_ARRIVALS / (unsigned)tpg);   // (tpg = 1 or 2 storing waves)
-    PD_STAMP(5)
 }
 
 // Luong dot attention for rows 2j and 2j+1 of the cluster (TF-1.8 _luong_score / _compute_attention; dot form at
@@ -349,11 +322,6 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
     const int row = b0 + 2 * j + half;
     const bool row_ok = row < B;
     const int rr = row_ok ? row : B - 1;
-#ifdef PD_ABL_ONE_MEMORY   // tools only (wrong results): every utterance attends over utterance 0's memory, 0.3 MB instead of 19 MB
-    const int mr = 0;
-#else
-    const int mr = rr;
-#endif
 
     // Scores: 16 lanes per key, 32 keys per pass of the row's 8 waves, PD_KB passes requested together (a pass per
     // round trip to L2 / the Infinity Cache was five dependent trips per step at Ts = 150).  The keys do not depend on
@@ -369,11 +337,9 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
             for (int i = 0; i < 4; ++i) kpre[q][i] = *reinterpret_cast<const float4*>(kr + (l16 + 16 * i) * 4);
         }
     };
-    if (!LOCAL) load_keys(keys + (size_t)mr * Ts * PD_D, 0, Ts);
+    if (!LOCAL) load_keys(keys + (size_t)rr * Ts * PD_D, 0, Ts);
 
-    PD_STAMP(0)
     pd_wait(cnt, target, status, ctrl);
-    PD_STAMP(1)
 
     if (t512 < 64) *reinterpret_cast<float4*>(qs + 4 * t512) = pd_ld4(pd_rsrc(query), (unsigned)(rr * PD_D + 4 * t512) * 4u);
     __syncthreads();
@@ -419,7 +385,7 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
         }
     }
 
-    const float* kb = keys + ((size_t)mr * Ts + w_lo) * PD_D;
+    const float* kb = keys + ((size_t)rr * Ts + w_lo) * PD_D;
     for (int j0 = 0; j0 < w_n; j0 += 32 * PD_KB) {
         if (LOCAL || j0 > 0) load_keys(kb, j0, w_n);
 #pragma unroll
@@ -444,7 +410,6 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
     }
     __syncthreads();
 
-    PD_STAMP(2)
     float m = -INFINITY;
     for (int jj = t512; jj < w_n; jj += 512) m = fmaxf(m, sc[jj]);
 #pragma unroll
@@ -468,10 +433,9 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
     sum = ((redm[0] + redm[1]) + (redm[2] + redm[3])) + ((redm[4] + redm[5]) + (redm[6] + redm[7]));
     const float inv = 1.0f / sum;
 
-    PD_STAMP(3)
     // context: wave hw takes positions hw, hw + 8, ...; lane d4 owns 4 consecutive depth elements (1 KB rows, coalesced);
     // PD_VB rows requested together (two per trip were ten dependent trips per step at Ts = 150)
-    const float* vb = values + ((size_t)mr * Ts + w_lo) * PD_D + 4 * lane;
+    const float* vb = values + ((size_t)rr * Ts + w_lo) * PD_D + 4 * lane;
     float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int j0 = hw; j0 < w_n; j0 += 8 * PD_VB) {
         float4 vv[PD_VB];
@@ -516,9 +480,7 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
             align_t[(size_t)row * Ts + k] = a;
         }
     }
-    PD_STAMP(4)
     pd_publish(cnt);
-    PD_STAMP(5)
 }
 __device__ __attribute__((noinline)) void pd_attention_local(const float* query, const float* keys, const float* values, float* ctx,
                                                              float* align_t, int Ts, float* lds, int j, int b0, int B, unsigned* cnt,
@@ -554,9 +516,6 @@ __global__ __launch_bounds__(PD_THREADS) void dec_persistent_kernel(PdParams p) 
         // ONE instance of the phase body in a loop over the step's ten phases (ten inlined copies spill)
 #pragma nounroll
         for (int k = 0; k < 10; ++k) {
-#ifdef PD_TIMELINE
-            if (threadIdx.x == 0) { pd_tl_step = t; pd_tl_phase = k; pd_tl_lds = lds + ((PD_OFF_SC + 2 * ((p.Ts + 3) & ~3) + 1) & ~1); }
-#endif
             if (k == 4) {
                 PdLocal lc;
                 lc.d = p.local_d; lc.gaussian = p.local_gaussian; lc.predictive = p.local_predictive; lc.step = t;
@@ -618,10 +577,6 @@ __global__ __launch_bounds__(PD_THREADS) void dec_persistent_kernel(PdParams p) 
             if (!ph.more) ++g;
         }
     }
-#ifdef PD_TIMELINE
-    __syncthreads();
-    if (blockIdx.x == 0 && threadIdx.x < 80 && pd_dbg) pd_dbg[threadIdx.x] = reinterpret_cast<unsigned long long*>(pd_tl_lds)[threadIdx.x];
-#endif
 }
 
 bool decoder_persistent_supports(const DecoderWeights& w, int cudnn, int B, int Ts) {
@@ -669,24 +624,6 @@ hipError_t decoder_persistent_enqueue(hipStream_t s, const DecoderWeights& w, co
     p.local_d = w.local_d; p.local_gaussian = w.local_gaussian; p.local_predictive = w.local_d > 0 && w.local_predictive;
     p.local_wp = w.local_wp; p.local_vp = w.local_vp; p.p_hist = sc.p_hist; p.err_flag = sc.err_flag;
     if (p.local_predictive && (e = hipMemsetAsync(sc.err_flag, 0, sizeof(int), s)) != hipSuccess) return e;
-#ifdef PD_TIMELINE
-    {
-        static unsigned long long* dbg = nullptr;
-        if (dbg) {
-            (void)hipStreamSynchronize(s);
-            unsigned long long hst[80];
-            (void)hipMemcpy(hst, dbg, sizeof(hst), hipMemcpyDeviceToHost);
-            for (int k = 0; k < 10; ++k) {
-                fprintf(stderr, "phase %d:", k);
-                for (int i = 0; i < 6; ++i) fprintf(stderr, " [%d]%.2f", i, (double)(hst[k * 8 + i] - hst[0]) / 100.0);
-                fprintf(stderr, "\n");
-            }
-        } else {
-            (void)hipMalloc(&dbg, 80 * sizeof(unsigned long long));
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(pd_dbg), &dbg, sizeof(dbg));
-        }
-    }
-#endif
     hipLaunchKernelGGL(dec_persistent_kernel, dim3(PD_W * clusters), dim3(PD_THREADS), pd_lds_bytes(Ts), s, p);
     return hipGetLastError();
 }

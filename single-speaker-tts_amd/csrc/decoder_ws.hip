@@ -40,12 +40,8 @@ namespace tts {
 #define WS_P2 128
 #define WS_RED_LD 20
 #define WS_SPIN_LIMIT 2000000u
-#ifndef WS_KB
 #define WS_KB 2      // key passes (16 positions each) requested together per row
-#endif
-#ifndef WS_VB
 #define WS_VB 8      // value rows per wave requested together
-#endif
 
 // weight registers per lane and phase: 4 * (K / k-slices / 16); the offsets of the phases in the register image
 #define WS_R0 0      // pre-net 1 (folded)        K 512, 1 tile : 16
@@ -98,16 +94,6 @@ __device__ __forceinline__ void ws_st4(const __amdgpu_buffer_rsrc_t& rs, unsigne
 }
 
 enum WsEpi { WS_ACT = 0, WS_GATES = 1, WS_CAND = 2, WS_CUDNN_RU = 3 };
-
-#ifdef WS_TIMELINE   // tools only: s_memrealtime stamps (100 MHz) of workgroup 0, thread 0 in step 100: [phase 0..9][8]
-__device__ unsigned long long ws_dbg[10 * 8];
-__device__ __shared__ int ws_tl_step, ws_tl_phase;
-#define WS_STAMP(I) if (blockIdx.x == 0 && threadIdx.x == 0 && ws_tl_step == 100) ws_dbg[ws_tl_phase * 8 + (I)] = __builtin_amdgcn_s_memrealtime();
-#define WS_TL_PHASE(T, K) if (threadIdx.x == 0) { ws_tl_step = (T); ws_tl_phase = (K); }
-#else
-#define WS_STAMP(I)
-#define WS_TL_PHASE(T, K)
-#endif
 
 // Start of a phase: wait until `target` arrivals have been counted on the cluster's counter (one lane polls, everybody
 // meets at the barrier).
@@ -228,7 +214,6 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
     // KEEP0: the slices inside segment 0 need nothing the cluster is still working on (wave-uniform); EARLY1: those inside
     // segment 1, once it is in LDS
     const bool early = (KEEP0 && kb + KW <= K0) || (EARLY1 && kb >= K0);
-    WS_STAMP(0)
     if (EARLY1) {
 #pragma unroll
         for (int u = 0; u < PRE; ++u) *reinterpret_cast<float4*>(As + 4 * (tid + WS_THREADS * (u + NLD0))) = pre[u];
@@ -237,7 +222,6 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
     if (early) mma_slice();
 
     ws_wait(cnt, ph.target, status, ctrl);
-    WS_STAMP(1)
     if (ph.delay && j == 3)   // a late stager: what a workgroup that clears its poll late looks like to its peers
         for (int i = 0; i < ph.delay; ++i) __builtin_amdgcn_s_sleep(127);
 
@@ -255,9 +239,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
         for (int u = U0; u < U1; ++u) *reinterpret_cast<float4*>(As + 4 * (tid + WS_THREADS * u)) = sv[u];
         __syncthreads();
     }
-    WS_STAMP(2)
     if (!early) mma_slice();
-    WS_STAMP(3)
     // C/D map of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg.  The partial tiles are indexed by (slice, tile).
     const int rslot = slice * TILES + tile;
 #pragma unroll
@@ -266,7 +248,6 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
         if (RB == 2) red[((rslot * RB + 1) * 16 + q * 4 + i) * WS_RED_LD + r] = acc1[i];
     }
     __syncthreads();
-    WS_STAMP(4)
     if (NEXT1) {   // the next phase's early segment: requested now, in flight during this phase's epilogue and publish
         const __amdgpu_buffer_rsrc_t rn = ws_rsrc(ph.next1);
 #pragma unroll
@@ -330,9 +311,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
             }
         }
         // (a plain yhist store drains with the others: one wait covers both)
-        WS_STAMP(5)
         if (EPI != WS_CUDNN_RU) ws_publish_wave(cnt, WS_ARRIVALS / (unsigned)(NT >= 64 ? NT / 64 : 1));
-        WS_STAMP(6)
     }
     if (EPI == WS_CUDNN_RU) __syncthreads();   // r / u are in LDS, the partial tiles may be overwritten (no hand-off here)
 }
@@ -484,10 +463,8 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
         }
     };
     if (active && !LOCAL) load_keys(keys + (size_t)mr * Ts * WS_D, 0, Ts);   // (the window of the local form may depend on the query)
-    WS_STAMP(0)
 
     ws_wait(cnt, target, status, ctrl);
-    WS_STAMP(1)
 
     // the query: row rl of the attention GRU's new state (block format: unit u at ((u / 16) * M + row) * 16 + u % 16)
     if (active && t256 < 64)
@@ -562,7 +539,6 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
         }
     }
     __syncthreads();
-    WS_STAMP(2)
 
     float m = -INFINITY;
     if (active) {
@@ -595,7 +571,6 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
 
     // context: wave hw takes positions hw, hw + 4, ...; a lane owns 4 consecutive depth elements (1 KB rows, coalesced);
     // WS_VB rows requested together
-    WS_STAMP(3)
     if (active) {
         const float* vb = values + ((size_t)mr * Ts + w_lo) * WS_D + 4 * lane;
         float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -616,7 +591,6 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
         *reinterpret_cast<float4*>(part + hw * WS_D + 4 * lane) = c0;
     }
     __syncthreads();
-    WS_STAMP(4)
     // wave 0 hands the rows over: a lane's 16 bytes are (block j', row RPW j + hf, units 4c..4c+3) -- M = 32: eight lanes one
     // 128-byte line of the context buffer (block format: two rows x 16 units), two store instructions; M = 16: one
     if (wave == 0) {
@@ -634,9 +608,7 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
             a.x *= iv; a.y *= iv; a.z *= iv; a.w *= iv;
             ws_st4(ws_rsrc(ctx), (unsigned)((jb * M + RPW * j + hf) * 16 + 4 * c) * 4u, a);
         }
-        WS_STAMP(5)
         ws_publish_wave(cnt, WS_ARRIVALS);
-        WS_STAMP(6)
     }
     if (active && align_t && row_ok) {
         if (!LOCAL) {
@@ -722,28 +694,21 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
         // into the pre-net matrix (decoder.hip); x_0 = GO frame = zeros (helpers.py:108): y and attention are zero at step 0,
         // so only the bias differs there (the un-folded one)
         ph.a0 = ycur; ph.a1 = att; ph.out = p1; ph.bias_slot = t == 0 ? 1 : 0; ph.target = per * g++;
-        WS_TL_PHASE(t, 0)
         ws_phase<M, WS_D, 16, WS_D, 1, 16, WS_ACT, ACT_RELU, WS_R0, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         ph.a0 = p1; ph.a1 = nullptr; ph.out = p2; ph.bias_slot = 2; ph.target = per * g++; ph.next1 = h_att_o;
-        WS_TL_PHASE(t, 1)
         ws_phase<M, WS_D, 16, 0, 1, 8, WS_ACT, ACT_RELU, WS_R1, false, 0, false, true>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         // attention GRU (model.py:226-229) on [p2 ; h_att]; the new state is the attention query
         if (CUDNN) {   // one hand-off: r, u, then x W_ci and h W_ch on the same staged tile
             ph.a0 = p2; ph.a1 = h_att_o; ph.out = nullptr; ph.bias_slot = 3; ph.target = per * g;
-            WS_TL_PHASE(t, 2)
             ws_phase<M, WS_P2, 8, WS_D, 2, 16, WS_CUDNN_RU, ACT_NONE, WS_R2, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.out = h_att; ph.bias_slot = 4; ++g;
-            WS_TL_PHASE(t, 3)
             ws_phase_hx<M, WS_P2, 8, WS_R3, false>(w, ph, lds, j, b0, p.B, cnt, pre);
         } else {       // TF GRUCell: gates on [p2 ; h_att], a hop, candidate on [p2 ; r*h_att]
             ph.a0 = p2; ph.a1 = h_att_o; ph.out = rh; ph.bias_slot = 3; ph.target = per * g++;
-            WS_TL_PHASE(t, 2)
             ws_phase<M, WS_P2, 8, WS_D, 2, 16, WS_GATES, ACT_NONE, WS_R2, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.a0 = p2; ph.a1 = rh; ph.out = h_att; ph.bias_slot = 4; ph.target = per * g++;
-            WS_TL_PHASE(t, 3)
             ws_phase<M, WS_P2, 8, WS_D, 1, 16, WS_CAND, ACT_NONE, WS_R3, true, 4, false, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         }
-        WS_TL_PHASE(t, 4)
         {
             WsLocal lc;
             lc.d = p.local_d; lc.gaussian = p.local_gaussian; lc.predictive = p.local_predictive; lc.step = t;
@@ -754,38 +719,29 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
         }
         // attention_layer(concat([cell_output, context])), no bias
         ph.a0 = h_att; ph.a1 = ctx; ph.out = att; ph.bias_slot = 5; ph.target = per * g++; ph.next1 = h_d1_o;
-        WS_TL_PHASE(t, 5)
         ws_phase<M, WS_D, 16, WS_D, 1, 16, WS_ACT, ACT_NONE, WS_R5, false, 0, false, true>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         // two ResidualWrapper(GRU cell) layers (model.py:254-269); the top one writes the y history
         ph.layer = 1;
         if (CUDNN) {
             ph.a0 = att; ph.a1 = h_d1_o; ph.out = nullptr; ph.bias_slot = 6; ph.target = per * g;
-            WS_TL_PHASE(t, 6)
             ws_phase<M, WS_D, 16, WS_D, 2, 16, WS_CUDNN_RU, ACT_NONE, WS_R6, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.out = h_d1; ph.yout = y0; ph.bias_slot = 7; ++g; ph.next1 = h_d2_o;
-            WS_TL_PHASE(t, 7)
             ws_phase_hx<M, WS_D, 16, WS_R7, true>(w, ph, lds, j, b0, p.B, cnt, pre);
             ph.layer = 2; ph.yout = nullptr;
             ph.a0 = y0; ph.a1 = h_d2_o; ph.out = nullptr; ph.bias_slot = 8; ph.target = per * g;
-            WS_TL_PHASE(t, 8)
             ws_phase<M, WS_D, 16, WS_D, 2, 16, WS_CUDNN_RU, ACT_NONE, WS_R8, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.out = h_d2; ph.yout = ycur; ph.yhist = p.yhist + (size_t)t * WS_D; ph.bias_slot = 9; ++g; ph.next1 = att;
-            WS_TL_PHASE(t, 9)
             ws_phase_hx<M, WS_D, 16, WS_R9, true>(w, ph, lds, j, b0, p.B, cnt, pre);
         } else {
             ph.a0 = att; ph.a1 = h_d1_o; ph.out = rh; ph.bias_slot = 6; ph.target = per * g++;
-            WS_TL_PHASE(t, 6)
             ws_phase<M, WS_D, 16, WS_D, 2, 16, WS_GATES, ACT_NONE, WS_R6, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.a0 = att; ph.a1 = rh; ph.out = h_d1; ph.yout = y0; ph.bias_slot = 7; ph.target = per * g++; ph.next1 = h_d2_o;
-            WS_TL_PHASE(t, 7)
             ws_phase<M, WS_D, 16, WS_D, 1, 16, WS_CAND, ACT_NONE, WS_R7, true, 4, false, true>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.layer = 2; ph.yout = nullptr;
             ph.a0 = y0; ph.a1 = h_d2_o; ph.out = rh; ph.bias_slot = 8; ph.target = per * g++;
-            WS_TL_PHASE(t, 8)
             ws_phase<M, WS_D, 16, WS_D, 2, 16, WS_GATES, ACT_NONE, WS_R8, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
             ph.a0 = y0; ph.a1 = rh; ph.out = h_d2; ph.yout = ycur; ph.yhist = p.yhist + (size_t)t * WS_D; ph.bias_slot = 9;
             ph.target = per * g++; ph.next1 = att;
-            WS_TL_PHASE(t, 9)
             ws_phase<M, WS_D, 16, WS_D, 1, 16, WS_CAND, ACT_NONE, WS_R9, true, 4, false, true>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         }
     }
@@ -938,18 +894,6 @@ hipError_t decoder_ws_enqueue(hipStream_t s, const DecoderWeights& w, float* scr
         else { if (cudnn) WS_LAUNCH(true, 32, false); else WS_LAUNCH(false, 32, false); }
     }
 #undef WS_LAUNCH
-#ifdef WS_TIMELINE
-    {
-        (void)hipStreamSynchronize(s);
-        unsigned long long hst[80];
-        (void)hipMemcpyFromSymbol(hst, HIP_SYMBOL(ws_dbg), sizeof(hst));
-        for (int k = 0; k < 10; ++k) {
-            fprintf(stderr, "phase %d:", k);
-            for (int i = 0; i < 7; ++i) fprintf(stderr, " [%d]%.2f", i, (double)(hst[k * 8 + i] - hst[0]) / 100.0);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
     return hipGetLastError();
 }
 

@@ -209,19 +209,8 @@ __device__ __forceinline__ void fft16(cf (&v)[16]) {
     for (int i = 0; i < 16; ++i) v[i] = o[i];
 }
 
-#ifndef E1S
-#define E1S 80   // row stride (complex) of the first exchange image: 2*E1S = 32 (mod 64) banks
-#endif
-#ifndef E2S
 #define E2S 17
-#endif
-#ifndef EX_CPLX
-#ifdef GL_FFT_LDS_STAGE1
-#define EX_CPLX 1280   // 16 rows of E1S
-#else
 #define EX_CPLX 1088   // 64 rows of E2S (the only exchange image) >= the 1024 bins of the merge pass
-#endif
-#endif
 
 struct FftTw {
     const cf* a;   // LDS table: a[(k2-1)*64] = W1024^{lane*k2}, k2 = 1..15 (already offset by lane)
@@ -262,19 +251,6 @@ __device__ __forceinline__ void fft1024(cf (&v)[16], cf* ex, const TW& tw, int l
     fft16<ZLO, ZHI>(v);
 #pragma unroll
     for (int k2 = 1; k2 < 16; ++k2) v[k2] = cmul(v[k2], tw.a_at(k2));
-#ifdef GL_FFT_LDS_STAGE1
-#pragma unroll
-    for (int k2 = 0; k2 < 16; ++k2) ex[k2 * E1S + lane] = v[k2];
-    wave_lds_sync();
-    {
-        const int a = lane & 15, kq = lane >> 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) v[4 * i + b] = ex[(kq + 4 * i) * E1S + a + 16 * b];
-    }
-    wave_lds_sync();
-#else
     // new v[4 i + b] at lane (a, kq) = old v[4 i + kq] at lane (a, b)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -283,7 +259,6 @@ __device__ __forceinline__ void fft1024(cf (&v)[16], cf* ex, const TW& tw, int l
         swap_bit5(v[4 * i + 0], v[4 * i + 2]);
         swap_bit5(v[4 * i + 1], v[4 * i + 3]);
     }
-#endif
     const int a = lane & 15, kq = lane >> 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

@@ -37,12 +37,8 @@ namespace tts {
 // Register cap: amdgpu_num_vgpr(80) makes hipcc allocate 160 unified registers (accumulators included, four values spilled)
 // instead of 104 + 64 accumulation registers: still three waves per SIMD, the encoder / post-net 2.5 % faster alone (2.83 ->
 // 2.75 ms) and 32 registers per lane left on a CU that holds three GEMM workgroups (small kernels of the other stream fit).
-#ifndef GEMM_NUM_VGPR
 #define GEMM_NUM_VGPR 80
-#endif
-#ifndef GEMM_NUM_VGPR_POOL
 #define GEMM_NUM_VGPR_POOL 128
-#endif
 #define BM 128
 #define BN 128
 #define BK 32
@@ -71,7 +67,6 @@ __device__ __forceinline__ void store_split4(unsigned char* img, int row, int kq
     *reinterpret_cast<uint2*>(img + 2 * BM * 64 + off) = make_uint2(pack_hi(l[0], l[1]), pack_hi(l[2], l[3]));
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 max4(float4 a, float4 b) {
     return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
 }
@@ -80,22 +75,7 @@ __device__ __forceinline__ float4 max4(float4 a, float4 b) {
 // powf out of the register allocation of every other GEMM)
 // POOL: instantiation whose A loader takes max(x[t], x[t+1]) (the two k = 3 projections that follow a max-pool): kept
 // apart so that every other GEMM carries neither its second load nor its registers.
-// PRE and PS are round 5's two measured-and-not-faster variants (HISTORY.md part C, profiles/r05_experiment_gemm_presplit.txt).
-// They stay in the body's source as template parameters, but the shipped library instantiates neither: only a tools build
-// with -DGEMM_EXPERIMENTS (tools/build_variant.sh) compiles their kernels and accepts the options "gemm_presplit" / "gemm_ps".
-// PRE: the weights come PRE-SPLIT (round 5): `g.Wimg` holds, per 128-row block of N and per k tile in the order the k loop
-// visits them, the 24 KB LDS image of the B tile itself -- [split][row][4 chunks, swizzled][8 bf16], made once per weight by
-// gemm_pack_weights_kernel with the same split3 -- so staging the B tile is six 16-byte loads and six linear ds_write_b128
-// per thread and no VALU work: the constants are no longer re-split in every k tile of every workgroup of every call
-// (round 4: half of the kernel's 85.5 M VALU instructions per launch, profiles/r04_gemm_mfma_counters.txt).
-// PS (round 5): PRODUCER / CONSUMER split inside the workgroup.  512 threads: waves 0..3 only multiply (the 2 x 2 wave tile of
-// the 256-thread form), waves 4..7 only stage (global loads, the three-way split, LDS stores) into the OTHER of two LDS image
-// pairs; one barrier per k tile.  In the 256-thread form every wave splits, then every wave multiplies, and the three
-// workgroups of a compute unit fall into step with each other (the matrix pipe serialises their MFMA phases, so they reach
-// their VALU phases together): matrix pipe and vector pipe take turns instead of running side by side -- 41 % matrix-pipe
-// busy with neither pipe, nor LDS latency, nor occupancy as the limit (profiles/r05_experiment_gemm_presplit.txt).  Here every
-// SIMD holds one multiplying and one staging wave for the whole k loop.
-template <bool DENORM, bool POOL, bool PRE, bool PS = false>
+template <bool DENORM, bool POOL>
 __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
     const GemmGroup& g = batch.g[blockIdx.z];
     const int M = g.M, N = g.N, K = g.K;
@@ -111,19 +91,14 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
     const int n0 = (seq % nyb) * BN;
     if (n0 >= N || m0 >= M) return;
 
-    // [split][row][32 bf16], chunks swizzled; PS: two such pairs in dynamic LDS (96 KB), As / Bs = the pair being read,
-    // As_w / Bs_w = the pair being written
-    __shared__ __attribute__((aligned(16))) unsigned char As_static[PS ? 16 : 3 * BM * 64];
-    __shared__ __attribute__((aligned(16))) unsigned char Bs_static[PS ? 16 : 3 * BN * 64];
-    extern __shared__ __attribute__((aligned(16))) unsigned char ps_smem[];
-    unsigned char* As = PS ? ps_smem : As_static;
-    unsigned char* Bs = PS ? ps_smem + 3 * BM * 64 : Bs_static;
-    unsigned char* As_w = As;
-    unsigned char* Bs_w = Bs;
+    // [split][row][32 bf16], chunks swizzled.  (Addressed through the two pointers: as arrays, the same kernel gets another
+    // register allocation, one value fewer spilled.)
+    __shared__ __attribute__((aligned(16))) unsigned char As_lds[3 * BM * 64];
+    __shared__ __attribute__((aligned(16))) unsigned char Bs_lds[3 * BN * 64];
+    unsigned char* const As = As_lds;
+    unsigned char* const Bs = Bs_lds;
 
-    // PS: both roles index their work with 0..255 (a consumer's wave tile, a producer's staging rows)
-    const bool producer = PS && threadIdx.x >= 256;
-    const int tid = PS ? (int)(threadIdx.x & 255) : (int)threadIdx.x;
+    const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -136,11 +111,7 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
     // which the buffer range check turns into a zero result -- the loader has no branches and no selects on data.
     typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
     const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, (int)0xFFFFFFF0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t b_rs = PRE ? __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(g.Wimg), 0, (int)0xFFFFFFF0u, 0x00020000)
-                                            : __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.Wt), 0, (int)0xFFFFFFF0u, 0x00020000);
-    auto buf16 = [](const __amdgpu_buffer_rsrc_t& rs, unsigned byte_off) {
-        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0));
-    };
+    const __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.Wt), 0, (int)0xFFFFFFF0u, 0x00020000);
     auto buf4 = [](const __amdgpu_buffer_rsrc_t& rs, unsigned byte_off) {
         return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 0));
     };
@@ -174,16 +145,7 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
         b_off[i] = (b_ok[i] ? n : 0) * K;
     }
 
-    float4 ra[4], rb[PRE ? 1 : 4];
-    uint4 rbi[PRE ? 6 : 1];      // PRE: this thread's six 16-byte pieces of the B tile's image
-    // PRE: byte offset of the next tile's image (tiles are requested in the order the image was made in)
-    unsigned img_off = PRE ? ((unsigned)(n0 / BN) * (unsigned)((K + BK - 1) / BK) + (unsigned)((g.kt1 > 0 ? g.kt0 : 0) / BK)) * (unsigned)(3 * BN * 64) + (unsigned)tid * 16u
-                           : 0u;
-    auto load_b_image = [&]() {
-#pragma unroll
-        for (int i = 0; i < (PRE ? 6 : 0); ++i) rbi[i] = buf16(b_rs, img_off + (unsigned)(4096 * i));
-        img_off += 3 * BN * 64;
-    };
+    float4 ra[4], rb[4];
     float4 ra4 = make_float4(0.f, 0.f, 0.f, 0.f);   // POOL: the raw row behind this thread's four
     unsigned pool_own = 0, pool_nxt = 0;            // POOL (fast path): validity bits of the loaded tile's tap, per row
     bool pool_raw = false;                          // POOL: ra holds raw rows (fast path), to be pooled when stored
@@ -261,21 +223,17 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
                 // land before the MFMAs of the tile in front of them are even issued
                 pool_own = (own[0] ? 1u : 0u) | (own[1] ? 2u : 0u) | (own[2] ? 4u : 0u) | (own[3] ? 8u : 0u);
                 pool_nxt = (nxt[0] ? 1u : 0u) | (nxt[1] ? 2u : 0u) | (nxt[2] ? 4u : 0u) | (nxt[3] ? 8u : 0u);
-                if (PRE) load_b_image();
-                else {
 #pragma unroll
-                    for (int i = 0; i < (PRE ? 0 : 4); ++i)
-                        rb[i] = buf4(b_rs, (b_ok[i] && kin) ? (unsigned)(b_off[i] + kk) * 4u : 0xFFFFFFFFu);
-                }
+                for (int i = 0; i < 4; ++i)
+                    rb[i] = buf4(b_rs, (b_ok[i] && kin) ? (unsigned)(b_off[i] + kk) * 4u : 0xFFFFFFFFu);
             } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const bool ok = kin && ((tapmask[i] >> tap) & 1u);
-                const unsigned off = ok ? (unsigned)(a_off[i] + kk) * 4u : 0xFFFFFFFFu;
-                ra[i] = buf4(a_rs, off);
-                if (!PRE) rb[PRE ? 0 : i] = buf4(b_rs, (b_ok[i] && kin) ? (unsigned)(b_off[i] + kk) * 4u : 0xFFFFFFFFu);
-            }
-            if (PRE) load_b_image();
+                for (int i = 0; i < 4; ++i) {
+                    const bool ok = kin && ((tapmask[i] >> tap) & 1u);
+                    const unsigned off = ok ? (unsigned)(a_off[i] + kk) * 4u : 0xFFFFFFFFu;
+                    ra[i] = buf4(a_rs, off);
+                    rb[i] = buf4(b_rs, (b_ok[i] && kin) ? (unsigned)(b_off[i] + kk) * 4u : 0xFFFFFFFFu);
+                }
             }
             // advance to the next tile
             if (tap_inner) {          // tap inner, channel chunk outer
@@ -300,9 +258,8 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
             float4 v = buf4(a_rs, off);
             if (POOL) v = max4(v, buf4(a_rs, (ok && ts + 1 < g.T) ? off + (unsigned)g.lda * 4u : off));
             ra[i] = v;
-            if (!PRE) rb[PRE ? 0 : i] = buf4(b_rs, (b_ok[i] && kin) ? (unsigned)(b_off[i] + kk) * 4u : 0xFFFFFFFFu);
+            rb[i] = buf4(b_rs, (b_ok[i] && kin) ? (unsigned)(b_off[i] + kk) * 4u : 0xFFFFFFFFu);
         }
-        if (PRE) load_b_image();
     };
     auto store_tile = [&]() {
         if (POOL && pool_raw) {   // pooled_i = nxt_i ? max(x_i, x_{i+1}) : x_i with x_i = own_i ? raw_i : 0 (x_{i+1}: the raw value)
@@ -318,11 +275,9 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
         for (int i = 0; i < 4; ++i) {
             const int row = (tid >> 3) + 32 * i;
             const int arow = POOL ? 4 * (tid >> 3) + i : row;
-            store_split4(As_w, arow, kq, ra[i]);
-            if (!PRE) store_split4(Bs_w, row, kq, rb[PRE ? 0 : i]);
+            store_split4(As, arow, kq, ra[i]);
+            store_split4(Bs, row, kq, rb[i]);
         }
-#pragma unroll
-        for (int i = 0; i < (PRE ? 6 : 0); ++i) *reinterpret_cast<uint4*>(Bs_w + tid * 16 + 4096 * i) = rbi[i];
     };
 
     // 32 x 32 blocks of this wave that lie entirely past M or N get no MFMAs (wave-uniform): the final Dense has
@@ -382,46 +337,17 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
         }
     };
     auto k_loop = [&](auto edge_c) {
-        if (!PS) {
-            load_tile(k_begin);
-            for (int kt = k_begin; kt < k_end; kt += BK) {
-                store_tile();
-                __syncthreads();
-                if (kt + BK < k_end) load_tile(kt + BK);
-                mma_tile(edge_c);
-                __syncthreads();
-            }
-            return;
-        }
-        // PS: the producers are one tile ahead in LDS and one more in registers
-        unsigned char* const A0 = ps_smem, * const B0 = ps_smem + 3 * BM * 64;
-        unsigned char* const A1 = ps_smem + 3 * (BM + BN) * 64, * const B1 = A1 + 3 * BM * 64;
-        if (producer) {
-            load_tile(k_begin);
-            As_w = A0; Bs_w = B0;
-            store_tile();
-            if (k_begin + BK < k_end) load_tile(k_begin + BK);
-        }
-        __syncthreads();
-        int cur = 0;
+        load_tile(k_begin);
         for (int kt = k_begin; kt < k_end; kt += BK) {
-            if (producer) {
-                if (kt + BK < k_end) {
-                    As_w = cur ? A0 : A1; Bs_w = cur ? B0 : B1;
-                    store_tile();
-                    if (kt + 2 * BK < k_end) load_tile(kt + 2 * BK);
-                }
-            } else {
-                As = cur ? A1 : A0; Bs = cur ? B1 : B0;
-                mma_tile(edge_c);
-            }
+            store_tile();
             __syncthreads();
-            cur ^= 1;
+            if (kt + BK < k_end) load_tile(kt + BK);
+            mma_tile(edge_c);
+            __syncthreads();
         }
     };
     if (blk_live[0][0] && blk_live[0][1] && blk_live[1][0] && blk_live[1][1]) k_loop(std::false_type{});
     else k_loop(std::true_type{});
-    if (producer) return;   // (PS: the staging waves have no part in the epilogue)
 
     // ---- epilogue.  C/D map of 32x32: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     if (g.epi == EPI_HIGHWAY) {
@@ -485,72 +411,14 @@ __device__ __forceinline__ void gemm_body(const GemmBatch& batch) {
     }
 }
 
-#ifdef GEMM_EXPERIMENTS
-#define GEMM_PRE_OK true
-#else
-#define GEMM_PRE_OK false
-#endif
-bool gemm_experiments_built() { return GEMM_PRE_OK; }
-template <bool DENORM, bool PRE>
+template <bool DENORM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(GEMM_NUM_VGPR))) void gemm_f32_kernel(GemmBatch batch) {
-    gemm_body<DENORM, false, PRE && GEMM_PRE_OK>(batch);
+    gemm_body<DENORM, false>(batch);
 }
 // the max-pool loader keeps a fifth raw row and the validity bits of the tile in flight: a register budget of its own
 // (two waves per SIMD) instead of spilling inside the k loop -- scratch accesses queue behind the tile's global loads
-template <bool PRE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(GEMM_NUM_VGPR_POOL))) void gemm_f32_pool_kernel(GemmBatch batch) {
-    gemm_body<false, true, PRE && GEMM_PRE_OK>(batch);
-}
-
-#ifdef GEMM_EXPERIMENTS
-// the producer / consumer form (gemm_body, PS): 512 threads, two LDS image pairs in dynamic shared memory
-#define GEMM_PS_LDS (2 * 3 * (BM + BN) * 64)
-template <bool DENORM, bool PRE>
-__global__ __launch_bounds__(512) void gemm_ps_kernel(GemmBatch batch) {
-    gemm_body<DENORM, false, PRE, true>(batch);
-}
-template <bool PRE>
-__global__ __launch_bounds__(512) void gemm_ps_pool_kernel(GemmBatch batch) {
-    gemm_body<false, true, PRE, true>(batch);
-}
-template <typename K>
-static hipError_t gemm_ps_launch(K kernel, dim3 grid, hipStream_t s, const GemmBatch& b) {
-    // (more than 64 KB of dynamic LDS needs the attribute; per device and kernel, cheap: set on every launch)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_PS_LDS);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, grid, dim3(512), GEMM_PS_LDS, s, b);
-    return hipGetLastError();
-}
-
-// The pre-split image of one weight matrix Wt [N][K] (see gemm_body, PRE): grid (k tiles, 128-row blocks of N), the tiles in
-// the order the k loop of a GEMM with this (K, Cin) visits them -- linear, or for a convolution whose channel count is a
-// multiple of the tile depth: channel chunk outer, tap inner.  Rows past N and k past K are zeros.
-__global__ __launch_bounds__(256) void gemm_pack_weights_kernel(const float* __restrict__ Wt, unsigned char* __restrict__ img, int N, int K, int Cin) {
-    const int it = blockIdx.x, nb = blockIdx.y, tid = threadIdx.x;
-    const int ktaps = K / Cin;
-    const bool tap_inner = ktaps > 1 && (Cin % BK) == 0;
-    const int kb = tap_inner ? (it % ktaps) * Cin + (it / ktaps) * BK : it * BK;
-    unsigned char* tile = img + ((size_t)nb * gridDim.x + it) * (3 * BN * 64);
-    const int kq = tid & 7;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = (tid >> 3) + 32 * i;
-        const int n = nb * BN + row, kk = kb + 4 * kq;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (n < N && kk < K) v = ld4(Wt + (size_t)n * K + kk);
-        store_split4(tile, row, kq, v);
-    }
-}
-#endif
-size_t gemm_weight_image_bytes(int N, int K) { return (size_t)((N + BN - 1) / BN) * (size_t)((K + BK - 1) / BK) * (3 * BN * 64); }
-hipError_t launch_gemm_pack_weights(hipStream_t s, const float* Wt, unsigned char* img, int N, int K, int Cin) {
-#ifdef GEMM_EXPERIMENTS
-    hipLaunchKernelGGL(gemm_pack_weights_kernel, dim3((K + BK - 1) / BK, (N + BN - 1) / BN), dim3(256), 0, s, Wt, img, N, K, Cin);
-    return hipGetLastError();
-#else
-    (void)s; (void)Wt; (void)img; (void)N; (void)K; (void)Cin;
-    return hipErrorNotSupported;
-#endif
+    gemm_body<false, true>(batch);
 }
 
 hipError_t launch_gemm(hipStream_t s, const GemmBatch& b, int n_groups) {
@@ -570,27 +438,9 @@ hipError_t launch_gemm(hipStream_t s, const GemmBatch& b, int n_groups) {
     for (int i = 0; i < n_groups; ++i) pool = pool || b.g[i].pool != 0;
     for (int i = 0; i < n_groups; ++i)
         if (pool && (!b.g[i].pool || b.g[i].C2)) return hipErrorInvalidValue;   // a pooled launch is homogeneous, never de-normalising
-#ifdef GEMM_EXPERIMENTS
-    // pre-split weight images: all groups of a launch or none (api_stages.hip attaches them to every weight it launches with)
-    bool pre = true;
-    for (int i = 0; i < n_groups; ++i) pre = pre && b.g[i].Wimg != nullptr;
-    if (b.ps) {
-        if (pool) return pre ? gemm_ps_launch(gemm_ps_pool_kernel<true>, grid, s, b) : gemm_ps_launch(gemm_ps_pool_kernel<false>, grid, s, b);
-        if (denorm) return pre ? gemm_ps_launch(gemm_ps_kernel<true, true>, grid, s, b) : gemm_ps_launch(gemm_ps_kernel<true, false>, grid, s, b);
-        return pre ? gemm_ps_launch(gemm_ps_kernel<false, true>, grid, s, b) : gemm_ps_launch(gemm_ps_kernel<false, false>, grid, s, b);
-    }
-    if (pre) {
-        if (pool) hipLaunchKernelGGL((gemm_f32_pool_kernel<true>), grid, dim3(256), 0, s, b);
-        else if (denorm) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, dim3(256), 0, s, b);
-        else hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, dim3(256), 0, s, b);
-        return hipGetLastError();
-    }
-#else
-    if (b.ps) return hipErrorNotSupported;
-#endif
-    if (pool) hipLaunchKernelGGL((gemm_f32_pool_kernel<false>), grid, dim3(256), 0, s, b);
-    else if (denorm) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, s, b);
+    if (pool) hipLaunchKernelGGL(gemm_f32_pool_kernel, grid, dim3(256), 0, s, b);
+    else if (denorm) hipLaunchKernelGGL((gemm_f32_kernel<true>), grid, dim3(256), 0, s, b);
+    else hipLaunchKernelGGL((gemm_f32_kernel<false>), grid, dim3(256), 0, s, b);
     return hipGetLastError();
 }
 
@@ -612,11 +462,10 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, int slic
 // not depend on how many others share the batch (the summation order over k is part of the result).
 int gemm_splitk_slices(int K) { return K >= 4096 ? 8 : 1; }   // (8: 600 workgroups for the encoder projection at 64 x 150 tokens; 4 left a CU with 1.2)
 
-hipError_t launch_gemm_splitk(hipStream_t s, const GemmGroup& g, int slices, float* partial, int ps) {
+hipError_t launch_gemm_splitk(hipStream_t s, const GemmGroup& g, int slices, float* partial) {
     if (slices < 2 || slices > TTS_GEMM_MAX_GROUPS || g.epi != EPI_STD || g.C2) return hipErrorInvalidValue;
     GemmBatch b;
     memset(&b, 0, sizeof(b));
-    b.ps = ps;
     const int k_tiles = (g.K + BK - 1) / BK;
     for (int i = 0; i < slices; ++i) {
         GemmGroup p = g;

@@ -39,7 +39,6 @@ struct GlParams {
     unsigned long long seed;
     unsigned* work_counter;  // zeroed counter of THIS launch: the persistent workgroups draw item ids from it
     unsigned* clear_counter; // null, or the counter of an EARLIER launch on this stream: one thread zeroes it for a later launch
-    unsigned long long* dbg; // tools only (-DGL_TIMELINE builds): [GL waves][64] s_memrealtime stamps of workgroup 0
 };
 
 // out[2*16*2*64]: set 0 = window[n] / n_fft, set 1 = set 0 * rwss at an interior frame; n = 2*(lane + 64 c) + e

@@ -31,9 +31,6 @@
 // (one instruction per ~4 cycles and SIMD whatever it is), and a packed instruction costs about as much as a
 // scalar one.  This file is still compiled with -fno-slp-vectorize: what the SLP vectoriser packs on its own
 // (unrelated scalars, with v_mov shuffles to align the pairs) is slower than leaving it scalar.
-//
-// Compile-time switches used by the tools/ micro-benchmarks only: GL_NO_ALTPRIO, GL_FFT_LDS_STAGE1 (first
-// exchange through LDS), GL_NO_STREAMING_HINT, E1S / E2S (exchange strides).
 #include "tts_common.h"
 #include "griffin_lim.h"
 #include "fft_wave.h"
@@ -105,11 +102,7 @@ __device__ __forceinline__ void mirror_bins(const cf (&z)[16], cf (&m)[16], cf* 
 // The spectra are streamed once per iteration (1.3 GB per launch at the bench size): non-temporal accesses
 // keep them from evicting the decoder's weights and attention memory, which the second stream re-reads
 // every step while this kernel runs.
-#ifdef GL_PLAIN_LOAD
-__device__ __forceinline__ float gl_stream_load(const float* p) { return *p; }
-#else
 __device__ __forceinline__ float gl_stream_load(const float* p) { return __builtin_nontemporal_load(p); }
-#endif
 __device__ __forceinline__ void gl_stream_store(cf* p, cf v) { __builtin_nontemporal_store(v, p); }
 #define GL_STREAM_LOAD(ptr) gl_stream_load(ptr)
 #define GL_STREAM_STORE(ptr, val) gl_stream_store((ptr), (val))
@@ -172,18 +165,6 @@ __device__ __forceinline__ gl_state_t gl_state_encode(cf x) { return gl_pack_pha
 __device__ __forceinline__ cf gl_state_decode(gl_state_t s, float mag) { return gl_unpack_phasor(s, mag); }
 size_t gl_state_bytes() { return sizeof(gl_state_t); }
 
-// tools-only ablations (garbage results, timing only): -DGL_ABL_NOSTORE drops the spectrum stores, -DGL_ABL_NOLOAD the
-// spectrum loads, -DGL_ABL_NOFLAG the waits of the overlap-add chain; -DGL_CLOCK logs the shader clock of every launch
-#ifdef GL_ABL_NOLOAD
-#define GL_ABL_LD(load, fake) (fake)
-#else
-#define GL_ABL_LD(load, fake) (load)
-#endif
-
-#ifdef GL_CLOCK   // tools only: shader clock held during every launch (workgroup 0), read back by gl_clock_dump()
-__device__ unsigned long long gl_clock_log[4096][2];
-__device__ unsigned gl_clock_n;
-#endif
 // ====================================================================================== streaming form
 // One Griffin-Lim iteration (MODE 0) or the final iSTFT (MODE 1) WITHOUT phases: a run of consecutive frames of one
 // utterance is a stream.  Frame index i of the run (frame t = run_t0 - halo + i, halo = ncol - 1) belongs to wave
@@ -218,7 +199,7 @@ enum { CT_OLA = 0, CT_SNEXT = 1, CT_OLB = 2 /* chain words of stages 1, 2 */, CT
 
 // NST = 2: TWO iterations per launch.  The kernel draws a constant amount of power per instruction and per byte, and
 // with the spectra streaming the chip holds a shader clock of ~1.9 GHz against ~2.3 GHz for the same arithmetic without
-// memory traffic (tools: -DGL_CLOCK): what shortens the launch is energy, not overlap.  So the second iteration is fed
+// memory traffic (a shader-clock probe, round 6): what shortens the launch is energy, not overlap.  So the second iteration is fed
 // from registers: stage A is the iteration above on ring A; its merged spectrum of frame t - lag is normalised to
 // |S| e^{i phi} where it stands (no phasor code written, none read back: 8 instead of 12 bytes per bin and iteration,
 // ~90 VALU instructions per frame and iteration less) and goes straight into stage B -- inverse FFT, overlap-add into
@@ -267,12 +248,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     cf* ex = ex_all + wave * EX_CPLX;
 
-#ifdef GL_CLOCK   // tools only: shader clock held during the launch (s_memtime ticks per 100 MHz s_memrealtime tick)
-    const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef GL_TIMELINE
-    if (p.dbg && tid == 0) p.dbg[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-#endif
     // ---------------- one-time setup: twiddles and BOTH windows in registers
     if (tid == 0) ctrl[CT_SNEXT] = (int)atomicAdd(p.work_counter, 1u);
     // (the counter of the launch before this one on the stream is drained: every workgroup that drew from it has ended)
@@ -309,10 +284,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     }
     __syncthreads();
     int item = __builtin_amdgcn_readfirstlane(ctrl[CT_SNEXT]);
-#ifdef GL_TIMELINE
-    int tl_runs = 0;
-    const int tl_first = item;
-#endif
 
     // ---------------- work item -> (utterance, first frame, frames, slot of its partial results); wave-uniform
     auto decode_item = [&](int it, int& b, int& t0, int& len, int& slot) {
@@ -339,7 +310,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
             _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) gc[j_] = GL_ROW(plo_, phi_, j_); \
             nyq_c = prow_[MH / 2];                                                              \
         }                                                                                       \
-        _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) gs[j_] = GL_ABL_LD(GL_STREAM_LOAD(j_ < 8 ? slo_ + 64 * j_ : shi_ - 64 * (j_ - 8)), (float)(tf_ + j_ + lane)); \
+        _Pragma("unroll") for (int j_ = 0; j_ < 16; ++j_) gs[j_] = GL_STREAM_LOAD(j_ < 8 ? slo_ + 64 * j_ : shi_ - 64 * (j_ - 8)); \
         nyq_s = srow_[MH / 2];                                                                  \
     }
     // vmcnt counts loads and stores together, in issue order.  The row for the next iteration is requested early in
@@ -358,21 +329,12 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     const gl_state_t* x_in = reinterpret_cast<const gl_state_t*>(p.phase_in);
     gl_state_t* x_out = reinterpret_cast<gl_state_t*>(p.phase_out);
 
-#ifdef GL_TIMELINE   // tools only: 100 MHz stamps of workgroup 0's waves, [wave][64], from the tenth iteration of a run on
-    int stamp_n = 0;
-#define GLS_STAMP()                                                                                       \
-    if (p.dbg && blockIdx.x == 0 && lane == 0 && stamp_n < 64 && i >= 10 * GL_NW)                         \
-        p.dbg[1024 + wave * 64 + stamp_n++] = __builtin_amdgcn_s_memrealtime();
-#else
-#define GLS_STAMP()
-#endif
     // Issue priority by lateness.  The overlap-add chain makes every wave do one index per round; the hardware
     // arbitrates the two waves of a SIMD by age, so waves 0-3 run ahead, then sleep at the chain while their partners
     // (4-7) run alone -- and a wave alone on a SIMD fills fewer issue slots than two (the timeline showed 2.4 us of
     // waiting per 7.5 us iteration for the older half, none for the younger).  A wave whose next overlap-add is what the
     // chain will ask for next raises its priority, one that is far ahead lowers it: the waves then arrive at the chain
     // about when it is their turn.
-#ifndef GL_NO_LATEPRIO
 #define GLS_URGENCY(NEXT_INDEX)                                                                    \
     {                                                                                              \
         const int d_ = __builtin_amdgcn_readfirstlane((NEXT_INDEX) - gl_flag_load(ctrl + CT_OLA)); \
@@ -381,9 +343,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         else if (d_ <= 5) __builtin_amdgcn_s_setprio(1);                                           \
         else __builtin_amdgcn_s_setprio(0);                                                        \
     }
-#else
-#define GLS_URGENCY(NEXT_INDEX)
-#endif
 
     // ---------------- the pieces of an iteration (all inlined; `v` is the wave's FFT register set)
     // G in the pair-owner layout (gk[c] = G[k], gk[8 + c] = G[MH - k], k = lane + 64 c; mid = G[512], lane 0's) -> input of
@@ -458,9 +417,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         const int qb_edge = 128 * ((acc_len - 1) >> 7);
         unsigned keep0 = qb_edge + 2 * lane < acc_len ? ~0u : 0u, keep1 = qb_edge + 2 * lane + 1 < acc_len ? ~0u : 0u;   // (bit masks)
         asm volatile("" : "+v"(keep0), "+v"(keep1));
-#ifndef GL_ABL_NOFLAG
         while (gl_flag_load(ctrl + chain) < idx) __builtin_amdgcn_s_sleep(1);
-#endif
         asm volatile("" ::: "memory");
         cf fin[16];   // MODE 1: what the slots hold after this index (the finished samples are among them)
         {
@@ -646,7 +603,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                 next_item = __builtin_amdgcn_readfirstlane(nv);
                 if (next_item < p.n_items) decode_item(next_item, nb, nt0, nlen, nslot);
             }
-            GLS_STAMP()   // 0: iteration start
             GLS_URGENCY(i)
             cf v[16];
             if (valid) {
@@ -671,7 +627,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
 #pragma unroll
                 for (int j = 0; j < 16; ++j) asm volatile("v_mov_b64 %0, 0" : "=v"(v[j]));
             }
-            GLS_STAMP()   // 1: decoded, split
             GLS_URGENCY(i)
             // the row is consumed.  NST == 1: request this wave's next one now (of this run, or the first of the next item).
             // NST > 1: the LAST stage requests it; the magnitude registers first take |S| of the frames that go from stage to
@@ -690,10 +645,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                 fft1024(v, ex, tw, lane);
                 synth_window(t, v);
             }
-            GLS_STAMP()   // 2: inverse FFT + window done
             if (late && i == i_res && lane == 0) gl_flag_store(ctrl + CT_SNEXT, (int)drawn);
             overlap_add(ringA, CT_OLA, i, s, t, b, run_t0, run_len, v);
-            GLS_STAMP()   // 3: overlap-add issued, flag passed on
             if (NST == 1) {
                 // the next row has arrived (requested before the inverse FFT) -- settled on every path round the loop, at
                 // the point of the iteration where the fewest registers are live, before this iteration's stores are issued
@@ -740,13 +693,11 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                     sm += sm < 0 ? R : 0;
                     fft_input(ring_prev, i_prev, sm, tk, yb_prev, v);
                     fft1024<FZ_LO, FZ_HI>(v, ex, tw, lane);
-                    GLS_STAMP()   // (a) a further stage's forward transform done
                     cf gk[16];
                     // |S| e^{i phi}: x * (|S| / |x|), and (|S|, 0) for a zero bin (numpy's exp(1j * angle(0)) = 1); the
                     // bins are X / MH of a windowed signal, far from both ends of the float range
                     const cf xmid = merge_pass(v, [&](int c, cf x) { gk[c] = gl_normalise(x, gs[c]); });   // |S| e^{i phi}
                     split_pass(gk, gl_normalise(xmid, nyq_s), v);
-                    GLS_STAMP()   // (b) merged, normalised, split
                 } else {
 #pragma unroll
                     for (int j = 0; j < 16; ++j) asm volatile("v_mov_b64 %0, 0" : "=v"(v[j]));   // (as in stage 0)
@@ -759,13 +710,10 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                         fft1024(v, ex, tw, lane);
                         synth_window(tk, v);
                     }
-                    GLS_STAMP()   // (c) inverse transform and window done
                     overlap_add(ring_k, CT_OLB + k - 1, ik, sk, tk, b, run_t0, run_len, v);
-                    GLS_STAMP()   // (d) overlap-add done, flag passed on
                 }
             }
             if (NST > 1) GLS_TOUCH_ROW()
-            GLS_STAMP()   // 4
             // ---------------- forward FFT of the frame `lag` behind in the last stage: its signal is final
             const int jj = ik, sb = sk;
             if (MODE == 0 && jj >= halo + lag && jj < halo + lag + run_len) {
@@ -780,17 +728,12 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                 }
                 fft_input(ring_k, jj, sm, tm, yb_k, v);
                 fft1024<FZ_LO, FZ_HI>(v, ex, tw, lane);
-                GLS_STAMP()   // 5: forward FFT done
                 GLS_URGENCY(i + GL_NW)
                 gl_state_t* orow = x_out + ((size_t)b * p.T + tm) * p.FP;
                 gl_state_t* olo = orow + lane;
                 gl_state_t* ohi = orow + (MH - lane);
                 const cf xmid = merge_pass(v, [&](int c, cf x) {
-#ifdef GL_ABL_NOSTORE
-                    if (__float_as_uint(x.x) == 0x12345678u) __builtin_nontemporal_store(gl_state_encode(x), c < 8 ? olo + 64 * c : ohi - 64 * (c - 8));
-#else
                     __builtin_nontemporal_store(gl_state_encode(x), c < 8 ? olo + 64 * c : ohi - 64 * (c - 8));
-#endif
                     if (MSE) {
                         const float d = mg[c] - (float)MH * sqrtf(fmaf(x.x, x.x, x.y * x.y));   // x = X / MH
                         mse_acc += d * d;
@@ -803,7 +746,6 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                         mse_acc += d * d;
                     }
                 }
-                GLS_STAMP()   // 6: merged, encoded, stores issued
             }
             s += GL_NW;
             s -= s >= R ? R : 0;
@@ -828,30 +770,10 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         }
         __syncthreads();
         item = next_item;
-#ifdef GL_TIMELINE
-        ++tl_runs;
-#endif
     }
-#ifdef GL_TIMELINE
-    if (p.dbg && tid == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        p.dbg[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        if (blockIdx.x < 512) p.dbg[1536 + blockIdx.x] = (unsigned long long)(unsigned)tl_first | ((unsigned long long)tl_runs << 32) | ((unsigned long long)(xcc & 0xf) << 48);
-    }
-#endif
-#ifdef GL_CLOCK
-    if (tid == 0 && blockIdx.x == 0 && MODE == 0) {
-        const unsigned long long dt = __builtin_amdgcn_s_memtime() - clk_t0, dr = __builtin_amdgcn_s_memrealtime() - clk_r0;
-        const unsigned n = atomicAdd(&gl_clock_n, 1u);
-        if (n < 4096) { gl_clock_log[n][0] = dt; gl_clock_log[n][1] = dr; }
-    }
-#endif
 #undef GLS_LOAD_ROW
 #undef GLS_NEXT_ROW
 #undef GLS_TOUCH_ROW
-#undef GLS_STAMP
 #undef GLS_URGENCY
 }
 
@@ -896,7 +818,7 @@ size_t gl_stream_lds_bytes(const GlParams& p) {
 
 // Work items of the streaming form.  The frames of all utterances, one after another, are dealt to the workgroups in
 // contiguous pieces of equal COST; a piece that crosses the end of an utterance is two runs (the tail of one utterance
-// and the head of the next).  What a run costs beyond its frames was measured per workgroup (tools: -DGL_TIMELINE,
+// and the head of the next).  What a run costs beyond its frames was measured per workgroup (round 6,
 // profiles/r06_experiment_gl_cut.txt): at three iterations per launch every stage starts halo + lag indices before the
 // next one's first frame -- 24 indices per run that carry 72 of a frame's 6 transforms, 12 frames' worth with start and
 // drain, a little less at an utterance's end where the frames outside are skipped but the reflect-padded ones take the
@@ -1097,19 +1019,11 @@ static hipError_t gl_stream_launch_wh(hipStream_t s, const GlParams& p, dim3 gri
         if (MODE == 0 && p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, M, N, true>), grid, dim3(GL_THREADS), lds, s, p);   \
         else hipLaunchKernelGGL((gl_stream_kernel<MODE, W, H, M, N, false>), grid, dim3(GL_THREADS), lds, s, p);        \
     }
-#ifdef GL_FAST_BUILD
-    if (mse) return hipErrorInvalidValue;
-    if (final_istft) GLS_LAUNCH_N(1, false, 1)
-    else if (n_stage == 2) GLS_LAUNCH_N(0, false, 2)
-    else if (n_stage == 3) GLS_LAUNCH_N(0, false, 3)
-    else GLS_LAUNCH_N(0, false, 1)
-#else
     if (n_stage == 3) GLS_LAUNCH_N(0, false, 3)
     else if (n_stage == 2) GLS_LAUNCH_N(0, false, 2)
     else if (final_istft) GLS_LAUNCH_N(1, false, 1)
     else if (mse) GLS_LAUNCH_N(0, true, 1)
     else GLS_LAUNCH_N(0, false, 1)
-#endif
 #undef GLS_LAUNCH_N
     return hipGetLastError();
 }
@@ -1128,18 +1042,14 @@ hipError_t launch_gl_stream(hipStream_t s, const GlParams& p_in, int n_cus, int 
     const dim3 grid(nwg);
     const bool mse = p.mse_partial != nullptr;
     if (p.win == 1102 && p.hop == 275) return gl_stream_launch_wh<1102, 275>(s, p, grid, lds, final_istft, n_stage, mse);
-#ifndef GL_FAST_BUILD
     if (p.win == 800 && p.hop == 200) return gl_stream_launch_wh<800, 200>(s, p, grid, lds, final_istft, n_stage, mse);
-#endif
     return hipErrorInvalidValue;
 }
 
 template <int W, int H>
 static hipError_t gl_stream_configure_wh() {
     hipError_t e;
-#ifndef GL_FAST_BUILD
     if ((e = gl_stream_set_attr<0, W, H, true>()) != hipSuccess) return e;
-#endif
     if ((e = gl_stream_set_attr<0, W, H, false>()) != hipSuccess) return e;
     if ((e = gl_stream_set_attr<0, W, H, false, 2>()) != hipSuccess) return e;
     if ((e = gl_stream_set_attr<0, W, H, false, 3>()) != hipSuccess) return e;
@@ -1148,9 +1058,7 @@ static hipError_t gl_stream_configure_wh() {
 }
 hipError_t gl_stream_configure() {
     hipError_t e = gl_stream_configure_wh<1102, 275>();
-#ifndef GL_FAST_BUILD
     if (e == hipSuccess) e = gl_stream_configure_wh<800, 200>();
-#endif
     return e;
 }
 
@@ -1479,16 +1387,4 @@ hipError_t launch_peak_normalize(hipStream_t s, float* wav, int B, int n) {
     return hipGetLastError();
 }
 
-#ifdef GL_CLOCK
-extern "C" void gl_clock_dump() {
-    static unsigned long long host[4096][2];
-    unsigned n = 0;
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(&n, HIP_SYMBOL(gl_clock_n), sizeof(n));
-    (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(gl_clock_log), sizeof(host));
-    if (n > 4096) n = 4096;
-    for (unsigned i = 0; i < n; ++i)
-        printf("launch %4u: workgroup 0 ran %.1f us at %.0f MHz\n", i, (double)host[i][1] * 0.01, (double)host[i][0] * 100.0 / (double)host[i][1]);
-}
-#endif
 }  // namespace tts

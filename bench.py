@@ -12,6 +12,12 @@ LJ-Speech batch") is quoted on.  Inputs (ids, initial phases) are resident in HB
 timed region.  For N > 1 every rank runs its own 64-utterance shard (weak scaling, no data-path
 collective); weights are generated on rank 0 and broadcast once over RCCL before timing.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line
+(with the figures the timed steps' own HIP events and the committed counter records give).  --full adds the measurements
+that take runs of their own after the timed steps: a stand-alone Griffin-Lim launch, Griffin-Lim beside a running decoder
+on the timed workload's and a trained model's spectra, the MFMA GEMM launch of roofline_mfma, and the CPU baseline (unless
+--no-cpu-baseline).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -426,6 +432,54 @@ def gl_beside_decoder(sstts, eng, hp, blob, ids, mags, B, T, dev_cus, reserve, p
     return out
 
 
+def gl_iteration_alone_ms(eng, init, B, F, T):
+    """the dominant kernel alone (no overlapping stream), for reference next to the in-pipeline figure: ms per iteration of
+    three launches of the bench's form, HIP events of the library (tts_profile_get "gl_iter")"""
+    eng.synchronize()
+    eng.profile_reset()
+    # (non-zero magnitudes: an all-zero spectrogram would send every frame down the kernel's exact
+    #  zero-bin path, which the synthesised spectrograms of the timed steps never take)
+    mag_alone = eng.to_device((np.random.default_rng(1).random((B, F, T), dtype=np.float32) ** 4) * 10 + 1e-3)
+    eng.griffin_lim(mag_alone, 3 * GL_PER_LAUNCH, WIN, HOP, N_FFT, init_phase=init, want_mse=False)
+    ms_alone, n_alone = eng.profile_get('gl_iter')
+    mag_alone.free()
+    return ms_alone / max(1, n_alone)
+
+
+def gemm_roofline(eng, hp, B, T):
+    """second roofline: the MFMA GEMM kernel on the largest post-net layer (first projection: conv1d k=3, 1024 -> 256
+    channels, max-pool fused into the loader, M = B*T rows), HIP events around 10 launches of tts_debug_gemm after one
+    untimed launch; the `roofline_mfma` object of the bench line"""
+    M, N, CIN, KT = B * T, hp.post.projections[0][0], hp.post.n_banks * hp.post.n_filters, 3
+    rng = np.random.default_rng(3)
+    ga = eng.to_device(rng.standard_normal((M + 8, CIN), dtype=np.float32))
+    gw = eng.to_device(rng.standard_normal((N, KT * CIN), dtype=np.float32) * 0.05)
+    gc = eng.empty((M, N))
+    eng._check(eng.lib.tts_debug_gemm(eng.handle, ga.data_ptr(), gw.data_ptr(), gc.data_ptr(), M, N, CIN, KT, T, 1))
+    eng.synchronize()
+    eng.profile_reset()
+    for _ in range(10):
+        eng._check(eng.lib.tts_debug_gemm(eng.handle, ga.data_ptr(), gw.data_ptr(), gc.data_ptr(), M, N, CIN, KT, T, 1))
+    gemm_ms, gemm_n = eng.profile_get('debug_gemm')
+    gemm_ms /= max(1, gemm_n)
+    gemm_flop = 2.0 * M * N * KT * CIN
+    for d in (ga, gw, gc):
+        d.free()
+    gemm_tflops = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    # f32 GEMM on the bf16 matrix pipe: every f32 operand split exactly into three bf16 terms, six bf16 MFMAs per
+    # product block, f32 accumulation (csrc/gemm_f32.hip).  `achieved` counts the f32-equivalent flops 2 M N K;
+    # `peak` = dense bf16 MFMA peak / 6; `frac_of_f32_mfma_peak` prices the same flops against the f32-input MFMA
+    # the kernel used until round 3 (> 1 is possible: that is the point of the split)
+    return {'kernel': 'gemm_f32_pool_kernel (post-net projection 1: conv1d k=3, 1024 -> 256, max-pool in the loader, '
+                      'M = {}; f32 operands as 3 x bf16, 6 x v_mfma_f32_32x32x16_bf16 per 16 k)'.format(M),
+            'bound': 'mfma', 'achieved': gemm_tflops,
+            'peak': MFMA_BF16_PEAK_TFLOPS / GEMM_PRODUCTS, 'unit': 'TFLOP/s (f32-equivalent)',
+            'frac': gemm_tflops / (MFMA_BF16_PEAK_TFLOPS / GEMM_PRODUCTS),
+            'frac_of_f32_mfma_peak': gemm_tflops / MFMA_F32_PEAK_TFLOPS,
+            'bf16_mfma_tflops': gemm_tflops * GEMM_PRODUCTS, 'bf16_mfma_peak': MFMA_BF16_PEAK_TFLOPS,
+            'traffic': None, 'launch_ms': gemm_ms, 'flop_per_launch': gemm_flop}
+
+
 def trained_spectrum_batch(B, T):
     """The one model output the reference ships (a (1, 1025, 1000, 1) linear-spectrogram dump after 215k training steps,
     reference visualization/data/ljspeech/v1.1/post-processing/, copied as data to tests/golden/) as B magnitude
@@ -469,7 +523,10 @@ def main():
     # to overlap with: ~16 ms once) is below 0.1 ms per step; 40 steps report 0.4 ms per step more than the steady state
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure what takes runs of its own: Griffin-Lim alone and beside a running '
+                         'decoder, the MFMA GEMM roofline launch, the CPU baseline (off by default: a plain run times the steps only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
     ap.add_argument('--pipeline', type=int, default=None, help='override the library default (stream pipelining)')
     ap.add_argument('--reserve-cus', type=int, default=None)
     ap.add_argument('--hold-lds-kb', type=int, default=None)
@@ -619,7 +676,7 @@ def main():
     # Initial phases: drawn per call inside the path, as the reference does (np.random.rand in audio/synthesis.py:91) -- here
     # a counter-based draw from a per-call seed, made by the first Griffin-Lim launch itself (csrc/griffin_lim.hip,
     # gl_seed_phasor).  `init` (an explicit (B, F, T) array, what the parity tests pass) is only used by the stand-alone
-    # Griffin-Lim measurement below.
+    # Griffin-Lim measurement of --full below.
     calls = [0]
 
     def step():
@@ -669,22 +726,16 @@ def main():
     assert np.isfinite(w).all()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, w, lin_out, ali_out)
-    # the dominant kernel alone (no overlapping stream), for reference next to the in-pipeline figure
-    eng.synchronize()
-    eng.profile_reset()
-    # (non-zero magnitudes: an all-zero spectrogram would send every frame down the kernel's exact
-    #  zero-bin path, which the synthesised spectrograms of the timed steps never take)
-    mag_alone = eng.to_device((np.random.default_rng(1).random((B, F, T), dtype=np.float32) ** 4) * 10 + 1e-3)
-    eng.griffin_lim(mag_alone, 3 * GL_PER_LAUNCH, WIN, HOP, N_FFT, init_phase=init, want_mse=False)
-    ms_alone, n_alone = eng.profile_get('gl_iter')
-    gl_alone_ms = ms_alone / max(1, n_alone)
-    mag_alone.free()
+    # --full only: the measurements that take runs of their own (a plain run reports None for their figures)
+    gl_alone_ms = None
+    if args.full:
+        gl_alone_ms = gl_iteration_alone_ms(eng, init, B, F, T)
     # The contract's synthetic weights put half of the linear-spectrogram bins on the clip floor (below): Griffin-Lim beside a
     # running decoder on spectra with a TRAINED model's dynamic range, and -- same harness, same box -- on the spectra of
     # the timed workload.  Reported beside the contract's figure, never instead of it.
     floor_frac = None
     gl_harness = {}
-    if rank == 0 and lin_out is not None:
+    if args.full and rank == 0 and lin_out is not None:
         reserve = args.reserve_cus if args.reserve_cus is not None else 32
         per_launch_h = args.gl_pair if args.gl_pair is not None else GL_PER_LAUNCH
         lin_host = lin_out.to_host()
@@ -698,23 +749,7 @@ def main():
             gl_harness = gl_beside_decoder(sstts, eng, hp, blob, ids, mags, B, T, dev_cus, reserve, per_launch_h, N_STEPS)
         for m in mags.values():
             m.free()
-    # second roofline: the MFMA GEMM kernel on the largest post-net layer (first projection: conv1d k=3,
-    # 1024 -> 256 channels, max-pool fused into the loader, M = B*T rows), HIP events around tts_debug_gemm
-    M, N, CIN, KT = B * T, hp.post.projections[0][0], hp.post.n_banks * hp.post.n_filters, 3
-    rng = np.random.default_rng(3)
-    ga = eng.to_device(rng.standard_normal((M + 8, CIN), dtype=np.float32))
-    gw = eng.to_device(rng.standard_normal((N, KT * CIN), dtype=np.float32) * 0.05)
-    gc = eng.empty((M, N))
-    eng._check(eng.lib.tts_debug_gemm(eng.handle, ga.data_ptr(), gw.data_ptr(), gc.data_ptr(), M, N, CIN, KT, T, 1))
-    eng.synchronize()
-    eng.profile_reset()
-    for _ in range(10):
-        eng._check(eng.lib.tts_debug_gemm(eng.handle, ga.data_ptr(), gw.data_ptr(), gc.data_ptr(), M, N, CIN, KT, T, 1))
-    gemm_ms, gemm_n = eng.profile_get('debug_gemm')
-    gemm_ms /= max(1, gemm_n)
-    gemm_flop = 2.0 * M * N * KT * CIN
-    for d in (ga, gw, gc):
-        d.free()
+    roofline_mfma = gemm_roofline(eng, hp, B, T) if args.full else None
 
     facade_ms = None
     if args.through_facade:
@@ -766,7 +801,6 @@ def main():
         dec_choice = eng.decoder_kernel_choice(B_PER_GPU, TS, pipelined=(args.pipeline is None or args.pipeline != 0))
         dec_ms = stage_ms['decoder']
         dec_flop = DEC_MFLOP_PER_UTT_STEP * 1e6 * B_PER_GPU * N_STEPS
-        gemm_tflops = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
         out = {
             'metric': 'mel-frames/sec (end-to-end text->waveform incl. 60-iter Griffin-Lim, 64-utt LJ-Speech-shaped batch per GPU)',
             'value': frames_total * args.steps / elapsed,
@@ -787,6 +821,7 @@ def main():
             # f32 accumulation: same error against the float64 oracle as the f32 MFMA, tests/test_gpu_gemm.py)
             'dtype': 'f32',
             'data': 'synthetic',
+            'full': args.full,   # False: the figures of the runs --full adds are None
             'config': {'workload': 'end-to-end Tacotron inference, B=64/GPU, T_sent=150, 200 decoder steps (r=5, 1000 frames), '
                                    '1025-bin linear, Griffin-Lim 60 iterations, n_fft 2048 / win 1102 / hop 275',
                        'global_batch': world * B_PER_GPU, 'parallelism': 'utterance shards, dp{}'.format(world)},
@@ -854,20 +889,9 @@ def main():
                                  'us_per_phase': 1e3 * dec_ms / (N_STEPS * DEC_PHASES_PER_STEP),
                                  'flop_per_call': dec_flop,
                                  'note': 'measured beside the Griffin-Lim launches of the previous call (stage_ms.decoder)'},
-            # f32 GEMM on the bf16 matrix pipe: every f32 operand split exactly into three bf16 terms, six bf16 MFMAs per
-            # product block, f32 accumulation (csrc/gemm_f32.hip).  `achieved` counts the f32-equivalent flops 2 M N K;
-            # `peak` = dense bf16 MFMA peak / 6; `frac_of_f32_mfma_peak` prices the same flops against the f32-input MFMA
-            # the kernel used until round 3 (> 1 is possible: that is the point of the split)
-            'roofline_mfma': {'kernel': 'gemm_f32_pool_kernel (post-net projection 1: conv1d k=3, 1024 -> 256, max-pool in the loader, '
-                                        'M = {}; f32 operands as 3 x bf16, 6 x v_mfma_f32_32x32x16_bf16 per 16 k)'.format(M),
-                              'bound': 'mfma', 'achieved': gemm_tflops,
-                              'peak': MFMA_BF16_PEAK_TFLOPS / GEMM_PRODUCTS, 'unit': 'TFLOP/s (f32-equivalent)',
-                              'frac': gemm_tflops / (MFMA_BF16_PEAK_TFLOPS / GEMM_PRODUCTS),
-                              'frac_of_f32_mfma_peak': gemm_tflops / MFMA_F32_PEAK_TFLOPS,
-                              'bf16_mfma_tflops': gemm_tflops * GEMM_PRODUCTS, 'bf16_mfma_peak': MFMA_BF16_PEAK_TFLOPS,
-                              'traffic': None, 'launch_ms': gemm_ms, 'flop_per_launch': gemm_flop},
+            'roofline_mfma': roofline_mfma,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline_in_child()
         else:
             out['cpu_baseline'] = None

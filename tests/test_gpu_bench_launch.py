@@ -18,7 +18,7 @@ def test_bench_gpus2_self_launch_gloo():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                          '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                          '--full', '--no-cpu-baseline'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     rec = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith('{')][-1])
     assert rec['n_gpus'] == 2 and rec['world_size_seen'] == 2
@@ -34,6 +34,8 @@ def test_bench_gpus2_self_launch_gloo():
     assert rec['padded_sentence_length'] == 150
     for key in ('roofline', 'roofline_valu', 'roofline_decoder', 'roofline_mfma'):
         assert key in rec
+    # --full: the measurements that take runs of their own after the timed steps, on every rank of the N > 1 path
+    assert rec['full'] is True and rec['roofline_mfma']['achieved'] > 0 and rec['roofline']['iteration_ms_alone'] > 0
 
 
 def test_bench_under_torchrun_one_rccl_rank():
@@ -59,6 +61,8 @@ def test_bench_under_torchrun_one_rccl_rank():
     assert rec['weight_broadcast_ms_steady'] > 0 and rec['communicator_setup_ms'] > 0
     assert rec['rank_ms_per_step'] and len(rec['rank_devices']) == 1 and rec['straggler_rank'] == 0
     assert rec['value'] > 0 and rec['steps'] == 3
+    # a plain run: none of the measurements --full adds
+    assert rec['full'] is False and rec['roofline_mfma'] is None and rec['cpu_baseline'] is None
 
 
 def test_bench_dump_outputs(tmp_path):

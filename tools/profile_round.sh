@@ -8,7 +8,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [[ $PART == *A* ]]; then
-echo "== bench"; python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/bench.err; tail -c 400 $O/${TAG}_bench.json; echo
+echo "== bench"; python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/bench.err; tail -c 400 $O/${TAG}_bench.json; echo
 for PL in 1 0; do
   rm -rf $O/stats$PL
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats$PL -- python3 $R/bench.py --steps 12 --warmup 3 --no-cpu-baseline --pipeline $PL > $O/stats$PL.log 2>&1

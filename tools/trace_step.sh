@@ -14,8 +14,8 @@ tag=sys.argv[1]
 f=glob.glob('gpurun_out/%s/steptrace/**/*kernel_trace.csv'%tag,recursive=True)[0]
 rows=list(csv.DictReader(open(f)))
 rows.sort(key=lambda r:int(r['Start_Timestamp']))
-# from the sixth persistent decoder launch (a timed step: 3 warm-up + 6 timed calls come first, the launches after them belong to
-# bench.py's trained-spectrum harness) for ~32 ms: two pipelined steps
+# from the sixth persistent decoder launch (a timed step: 3 warm-up + 6 timed calls come first; with --full the launches after
+# them would belong to bench.py's trained-spectrum harness) for ~32 ms: two pipelined steps
 pd=[i for i,r in enumerate(rows) if 'dec_persistent' in r['Kernel_Name'] or 'dec_ws' in r['Kernel_Name']]
 i0=pd[5]; t0=int(rows[i0]['Start_Timestamp'])
 last=None

@@ -198,6 +198,32 @@ int tts_evaluate(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps,
                  const float* mel_target, const float* linear_target, float* losses,
                  double* l1_sums, float* mel, float* alignments, float* linear);
 
+/* ---- teacher forcing -------------------------------------------------------------------- */
+/* The decoder fed as TacotronTrainingHelper feeds it (tacotron/helpers.py:208-405, chosen at tacotron/model.py:284-298):
+ * the GO frame (zeros) at step 0 and frame t*r - 1 of the target at step t >= 1 (outputs[:, r-1::r]) instead of its own last
+ * frame; the last r-frame group of the target is never fed.  Everything else is the inference network of Mode.PREDICT:
+ * pre-net dropout off, batch norm from the moving statistics, no gradient -- this is NOT Mode.TRAIN.  Global and
+ * LocalLuong attention (with tts_decoder_forward's refusals), both GRU formulations.
+ * memory [B*Ts*256], mel_target [B * n_steps*r * n_mels] (device, 16-byte aligned; == (B, n_steps, r*n_mels)) ->
+ * mel [B * n_steps * (r*n_mels)] and alignments [n_steps * B * Ts] (may be NULL), as tts_decoder_forward.
+ * Decoder: tts_teacher_kernel_choice.  Given the padded shape (Ts, n_steps), an utterance's outputs depend neither on B,
+ * on its position in the batch, on the rows per cluster nor on the calls the handle ran before.  Never graph-captured. */
+int tts_decoder_forward_teacher(tts_handle_t h, const float* memory, int B, int Ts, int n_steps,
+                                const float* mel_target, float* mel, float* alignments);
+/* Teacher-forced forward pass of the whole network: tts_encoder_forward, tts_decoder_forward_teacher,
+ * tts_postnet_forward (the post-net reads the teacher-forced mel prediction), then -- with linear_target != NULL --
+ * the three L1 losses of tts_evaluate (tacotron/model.py:432-442, same kernels, same determinism and NaN rules):
+ * losses [3] = {loss, loss_decoder, loss_post_processing}, optional l1_sums [B][2] (double).  linear_target == NULL:
+ * no losses (losses, l1_sums ignored).  mel, alignments, linear: optional outputs (NULL to skip) as in tts_evaluate.
+ * Arguments are checked as tts_evaluate checks them; mel_target must be 16-byte aligned. */
+int tts_teacher_forced(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps,
+                       const float* mel_target, const float* linear_target, float* losses,
+                       double* l1_sums, float* mel, float* alignments, float* linear);
+/* Which decoder a teacher-forced call of this shape takes: 2 = the weight-stationary kernel's teacher variant
+ * (decoder_ws.hip), where a stand-alone free-running call would take that kernel; 0 = launch per layer (decoder.hip) --
+ * also where the free-running call would take decoder_persistent.hip (1), which has no teacher form.  Host only. */
+int tts_teacher_kernel_choice(tts_handle_t h, int B, int T_sent);
+
 /* ---- spectrogram de-normalisation ------------------------------------------------------ */
 /* inference() post-step + synthesize() power (tacotron/inference.py:93-101,175;
  * audio/conversion.py:81-102, 32-53): per utterance transpose to (F,T),

@@ -93,6 +93,10 @@ _PROTOTYPES = {
     'tts_postnet_forward': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'tts_evaluate': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p]),
+    'tts_decoder_forward_teacher': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'tts_teacher_forced': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
+    'tts_teacher_kernel_choice': (c_int, [c_void_p, c_int, c_int]),
     'tts_denorm_power': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p]),
     'tts_griffin_lim': (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_void_p, c_void_p]),
@@ -405,6 +409,70 @@ class Engine(object):
                                           ptr(out['l1_sums']), ptr(out['mel']), ptr(out['alignments']), ptr(out['linear'])))
         out['n_steps'] = n_steps
         return out
+
+    def _teacher_steps(self, mel_target, B, what):
+        r, nm = self.cfg.reduction, self.cfg.n_mels
+        mel_sz = int(np.prod(mel_target.shape))
+        if mel_target.shape[0] != B or mel_sz == 0 or mel_sz % (B * r * nm):
+            raise ValueError('{}: mel target of shape {} for B = {}, r * n_mels = {}'.format(what, mel_target.shape, B, r * nm))
+        return mel_sz // (B * r * nm)
+
+    def decoder_forward_teacher(self, memory, mel_target, want_alignments=True, mel=None, alignments=None):
+        """Teacher-forced decoder (tts_decoder_forward_teacher; reference helpers.py:208-405, TacotronTrainingHelper):
+        step 0 reads the GO frame, step t >= 1 frame t*r - 1 of ``mel_target`` -- (B, S, r*n_mels) or (B, S*r, n_mels), host
+        array or device buffer; n_steps = S.  The inference network otherwise (no dropout, moving batch-norm statistics, no
+        gradient): this is not Mode.TRAIN.  Returns (mel (B, S, r*n_mels), alignments (S, B, Ts) or None), as
+        :meth:`decoder_forward`."""
+        B, Ts = memory.shape[0], memory.shape[1]
+        n_steps = self._teacher_steps(mel_target, B, 'decoder_forward_teacher')
+        p_mem, _k1 = self._in(memory, np.float32)
+        p_tgt, _k2 = self._in(mel_target, np.float32, 'teacher_mel_target')
+        if mel is None:
+            mel = self.empty((B, n_steps, self.cfg.reduction * self.cfg.n_mels))
+        if alignments is None and want_alignments:
+            alignments = self.empty((n_steps, B, Ts))
+        self._check(self.lib.tts_decoder_forward_teacher(self.handle, p_mem, B, Ts, n_steps, p_tgt, mel.data_ptr(),
+                                                         alignments.data_ptr() if alignments is not None else None))
+        return mel, alignments
+
+    def teacher_forced(self, ids, mel_target, linear_target=None, want_sums=False, want_mel=True, want_alignments=True,
+                       want_linear=True, losses=None):
+        """Teacher-forced forward pass on one batch (tts_teacher_forced): encoder, the decoder of
+        :meth:`decoder_forward_teacher`, the post-net on its mel prediction and -- with ``linear_target`` -- the L1 losses
+        of :meth:`evaluate`.  Shapes and inputs as :meth:`evaluate` takes them; no dropout, no batch statistics, no
+        gradient (not Mode.TRAIN).  Returns a dict of device arrays: ``mel`` (B, T, n_mels), ``alignments``
+        (T_red, B, T_sent), ``linear`` (B, T, F) where asked for, ``losses`` (3,) and ``l1_sums`` (B, 2) float64 (with
+        ``want_sums``) when a linear target is given, else None; and ``n_steps``."""
+        B, Ts = ids.shape
+        r, nm, F = self.cfg.reduction, self.cfg.n_mels, 1 + self.cfg.n_fft // 2
+        n_steps = self._teacher_steps(mel_target, B, 'teacher_forced')
+        T = n_steps * r
+        if linear_target is not None and (linear_target.shape[0] != B or int(np.prod(linear_target.shape)) != B * T * F):
+            raise ValueError('teacher_forced: linear target of shape {}, ({}, {}, {}) floats needed'.format(
+                linear_target.shape, B, T, F))
+        self._check_ids(ids)
+        p_ids, _k1 = self._in(ids, np.int32, 'ids')
+        p_mel, _k2 = self._in(mel_target, np.float32, 'teacher_mel_target')
+        p_lin, _k3 = self._in(linear_target, np.float32, 'teacher_linear_target')
+        with_losses = linear_target is not None
+        out = dict(losses=(losses if losses is not None else self.empty((3,))) if with_losses else None)
+        out['l1_sums'] = self.empty((B, 2), np.float64) if want_sums and with_losses else None
+        out['mel'] = self.empty((B, T, nm)) if want_mel else None
+        out['alignments'] = self.empty((n_steps, B, Ts)) if want_alignments else None
+        out['linear'] = self.empty((B, T, F)) if want_linear else None
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        self._check(self.lib.tts_teacher_forced(self.handle, p_ids, B, Ts, n_steps, p_mel, p_lin, ptr(out['losses']),
+                                                ptr(out['l1_sums']), ptr(out['mel']), ptr(out['alignments']),
+                                                ptr(out['linear'])))
+        out['n_steps'] = n_steps
+        return out
+
+    def teacher_kernel_choice(self, B, Ts):
+        """tts_teacher_kernel_choice: 2 = decoder_ws.hip's teacher variant, 0 = launch per layer."""
+        rc = self.lib.tts_teacher_kernel_choice(self.handle, int(B), int(Ts))
+        if rc < 0:
+            self._check(rc)
+        return rc
 
     def denorm_power(self, linear, ref_db, max_db, power, out=None):
         B, T, F = linear.shape

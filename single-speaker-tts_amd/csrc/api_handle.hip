@@ -893,6 +893,7 @@ int tts_finalize_weights(tts_handle_t h) {
     // the decoder's weights once more, in the register order of the weight-stationary persistent kernel (decoder_ws.hip):
     // TF GRUCell form, the default layer sizes (decoder_ws_supports checks the rest per call)
     size_t o_wsw = 0, o_wsb = 0;
+    bool ws_teacher = false;
     const bool ws_image = c.n_decoder_gru_layers == 2 && att == 256 && U == 256 && mem == 256 &&
                           c.dec_prenet_units[0] == 256 && c.dec_prenet_units[1] == 128 && c.n_mels <= 256;
     if (ws_image) {
@@ -907,8 +908,9 @@ int tts_finalize_weights(tts_handle_t h) {
             hw.g_gw[l] = hb + o_dg[l].gates_wt; hw.g_gb[l] = hb + o_dg[l].gates_b;
             hw.g_cw[l] = hb + o_dg[l].cand_wt; hw.g_cb[l] = hb + o_dg[l].cand_b;
         }
+        hw.w1 = hb + o_dpw[0]; hw.n_mels = c.n_mels;
         hw.cudnn = cudnn ? 1 : 0;
-        decoder_ws_pack(hw, p.host.data() + o_wsw, p.host.data() + o_wsb);
+        ws_teacher = decoder_ws_pack(hw, p.host.data() + o_wsw, p.host.data() + o_wsb);
     }
 
     {
@@ -955,6 +957,7 @@ int tts_finalize_weights(tts_handle_t h) {
     d.prenet1_units = c.dec_prenet_units[0]; d.prenet2_units = c.dec_prenet_units[1];
     d.ws_wimg = ws_image ? base + o_wsw : nullptr;
     d.ws_bimg = ws_image ? base + o_wsb : nullptr;
+    d.ws_teacher = ws_image && ws_teacher ? 1 : 0;
     h->dense_wt = base + o_dw;
     h->dense_b = base + o_db;
     h->zeros = base + o_zero;

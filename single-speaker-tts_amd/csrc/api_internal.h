@@ -395,7 +395,9 @@ int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memor
 int pd_kernel_for(tts_handle_t h, int B, int Ts, int budget);
 int pd_choice(tts_handle_t h, int B, int Ts, int budget, bool pipelined);
 int attention_keys(tts_handle_t h, const float* memory, int B, int Ts, float* keys);
-int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments);
+int teacher_choice(tts_handle_t h, int B, int Ts);
+int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments,
+                 const float* target = nullptr);
 int postnet_impl(tts_handle_t h, const float* mel, int B, int T, float* linear, float* mag, float ref_db, float max_db, float power, int* db_flag = nullptr);
 bool denorm_can_assert(float ref_db, float max_db);
 int denorm_flag_arm(tts_handle_t h, int** flag);

@@ -598,7 +598,14 @@ int attention_keys(tts_handle_t h, const float* memory, int B, int Ts, float* ke
     return run_single(h, dense_group(memory, mem, h->mem_wt, nullptr, keys, A, B * Ts, A, mem, ACT_NONE));
 }
 
-int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments) {
+// Which decoder a teacher-forced call takes (stand-alone, never captured): the weight-stationary kernel's teacher variant where
+// the free-running call would take that kernel, else the launch-per-layer path (decoder_persistent.hip has no teacher form).
+int teacher_choice(tts_handle_t h, int B, int Ts) {
+    return pd_choice(h, B, Ts, h->n_cus_dev, false) == 2 && h->dec.ws_teacher ? 2 : 0;
+}
+
+int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments,
+                 const float* target) {
     int rc = TTS_OK;
     const tts_config_t& c = h->cfg;
     if (h->dec.local_d > 0 && Ts < 2 * h->dec.local_d + 1)
@@ -620,9 +627,9 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
     WS(h, "dec.att_stats", float, (size_t)n_steps * B * TTS_ATT_PARTS * 2, att_stats);
     // (the launch-per-layer path replays a captured graph with its buffers baked in: one y history there)
     const int pd_budget = h->cur_cu_budget > 0 ? h->cur_cu_budget : h->n_cus_dev;
-    const int pd_kernel = pd_choice(h, B, Ts, pd_budget, h->cur_cu_budget > 0);
+    const int pd_kernel = target ? teacher_choice(h, B, Ts) : pd_choice(h, B, Ts, pd_budget, h->cur_cu_budget > 0);
     const bool use_pd = pd_kernel != 0;
-    const bool defer_proj = h->defer_projection && use_pd;
+    const bool defer_proj = h->defer_projection && use_pd && !target;
     WS(h, defer_proj ? (h->defer_parity ? "dec.yhist.odd" : "dec.yhist.even") : "dec.yhist", float, (size_t)B * n_steps * U, yhist);
     WS(h, "dec.align_raw", float, (size_t)n_steps * B * Ts, align_raw);
     DecoderScratch sc;
@@ -684,9 +691,15 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
         WS(h, "dec.ws_sync", unsigned, (size_t)64 * clusters + 2, ws_sync);
         if (ws_sync != h->pd_sync || clusters != h->pd_clusters)   // new buffer / new layout: the sticky status word starts clean
             HIPCHK(h, hipMemsetAsync(ws_sync + 64 * clusters + 1, 0, sizeof(unsigned), h->stream));
+        float* xg = nullptr;
+        if (target) {   // teacher forcing: the pre-net inputs x_t W1x + b1 of all steps, one GEMM in front of the loop
+            WS(h, "dec.teacher_xg", float, (size_t)B * n_steps * c.dec_prenet_units[0], xg_ws);
+            HIPCHK(h, decoder_teacher_inputs(h->stream, h->dec, h->zeros, target, B, n_steps, xg_ws));
+            xg = xg_ws;
+        }
         HIPCHK(h, decoder_ws_enqueue(h->stream, h->dec, ws_scratch, yhist, memory, keys, B, Ts, n_steps, alignments, ws_sync,
                                      h->cur_hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0, rows, clusters, sc.p_hist,
-                                     sc.err_flag));
+                                     sc.err_flag, xg));
         h->pd_rows_used = rows;
         h->pd_sync = ws_sync;
         h->pd_clusters = clusters;
@@ -705,8 +718,8 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
         h->pd_sync = pd_sync;
         h->pd_clusters = clusters;
         h->pd_used = true;
-    } else if (!h->use_graph) {
-        HIPCHK(h, decoder_enqueue(h->stream, h->dec, sc, memory, keys, B, Ts, n_steps, alignments, c.force_cudnn));
+    } else if (!h->use_graph || target) {   // (a teacher-forced call is never captured)
+        HIPCHK(h, decoder_enqueue(h->stream, h->dec, sc, memory, keys, B, Ts, n_steps, alignments, c.force_cudnn, target));
     } else {
         auto& k = h->dec_key;
         // (the scratch and weight structs are plain pointers and ints, zeroed before they are filled: compared bytewise)
@@ -856,6 +869,22 @@ int tts_decoder_forward(tts_handle_t h, const float* memory, int B, int Ts, int 
 }
 
 
+// Teacher forcing (reference helpers.py:208-405): the decoder reads mel_target frame t*r - 1 at step t >= 1.
+int tts_decoder_forward_teacher(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, const float* mel_target,
+                                float* mel, float* alignments) {
+    DeviceScope dev_scope(h);
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!memory || !mel_target || !mel || B < 1 || Ts < 1 || n_steps < 1)
+        return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: bad arguments");
+    if ((uintptr_t)mel_target & 15) return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: mel_target must be 16-byte aligned");
+    if ((long long)n_steps * h->cfg.reduction > (1 << 24)) return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: sizes out of range");
+    if ((rc = standalone_begin(h))) return rc;
+    if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel, alignments, mel_target))) return rc;
+    return standalone_end(h);
+}
+
+
 int tts_postnet_forward(tts_handle_t h, const float* mel, int B, int T, float* linear) {
     DeviceScope dev_scope(h);
     if (!linear) return fail(h, TTS_ERR_INVALID, "postnet_forward: bad arguments");
@@ -910,6 +939,67 @@ int tts_evaluate(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps,
                                    losses));
     }
     return standalone_end(h);
+}
+
+
+// Teacher-forced forward pass (reference helpers.py:208-405 feeding the inference network): tts_evaluate with the decoder of
+// tts_decoder_forward_teacher; linear_target == NULL: no losses (losses and l1_sums are then ignored).
+int tts_teacher_forced(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps, const float* mel_target,
+                       const float* linear_target, float* losses, double* l1_sums, float* mel, float* alignments, float* linear) {
+    DeviceScope dev_scope(h);
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (!ids || !mel_target || (linear_target && !losses) || B < 1 || Ts < 1 || n_steps < 1)
+        return fail(h, TTS_ERR_INVALID, "teacher_forced: bad arguments (ids and mel_target are required, losses with a linear "
+                                        "target; B, Ts, n_steps >= 1)");
+    const tts_config_t& c = h->cfg;
+    const int T = n_steps * c.reduction, F = 1 + c.n_fft / 2;
+    if ((long long)n_steps * c.reduction > (1 << 24) || (double)B * T * F >= 9.0e18)
+        return fail(h, TTS_ERR_INVALID, "teacher_forced: sizes out of range");
+    for (const void* p : {(const void*)linear_target, (const void*)mel, (const void*)linear, (const void*)losses})
+        if ((uintptr_t)p & 3) return fail(h, TTS_ERR_INVALID, "teacher_forced: float buffers must be 4-byte aligned");
+    if ((uintptr_t)mel_target & 15) return fail(h, TTS_ERR_INVALID, "teacher_forced: mel_target must be 16-byte aligned");
+    if (linear_target && ((uintptr_t)l1_sums & 7)) return fail(h, TTS_ERR_INVALID, "teacher_forced: l1_sums must be 8-byte aligned");
+    const size_t n_mel = (size_t)B * T * c.n_mels, n_lin = (size_t)B * T * F;
+    WS(h, "eval.memory", float, (size_t)B * Ts * 2 * c.n_gru_units, memory);
+    float* mel_o = mel;
+    if (!mel_o) {
+        WS(h, "eval.mel", float, n_mel, mel_ws);
+        mel_o = mel_ws;
+    }
+    float* lin_o = linear;
+    if (!lin_o && linear_target) {
+        WS(h, "eval.linear", float, n_lin, lin_ws);
+        lin_o = lin_ws;
+    }
+    double* partial = nullptr;
+    double* sums = l1_sums;
+    if (linear_target) {
+        WS(h, "eval.partial", double, eval_loss_partial_count(B, T, c.n_mels, F), partial_ws);
+        partial = partial_ws;
+        if (!sums) {
+            WS(h, "eval.sums", double, (size_t)2 * B, sums_ws);
+            sums = sums_ws;
+        }
+    }
+    if ((rc = standalone_begin(h))) return rc;
+    if ((rc = encoder_impl(h, ids, B, Ts, memory))) return rc;
+    if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel_o, alignments, mel_target))) return rc;
+    if (lin_o && (rc = postnet_impl(h, mel_o, B, T, lin_o, nullptr, 0.f, 0.f, 1.f))) return rc;
+    if (linear_target) {
+        ProfScope ps(h, ST_EVAL_LOSS, 2);
+        const int blocks = 8 * std::max(1, h->n_cus_dev);   // (as tts_evaluate)
+        HIPCHK(h, launch_eval_loss(h->stream, mel_target, mel_o, linear_target, lin_o, B, T, c.n_mels, F, blocks, partial, sums,
+                                   losses));
+    }
+    return standalone_end(h);
+}
+
+
+int tts_teacher_kernel_choice(tts_handle_t h, int B, int Ts) {
+    if (!h || B < 1 || Ts < 1) return TTS_ERR_INVALID;
+    if (!h->finalized) return fail(h, TTS_ERR_NOT_LOADED, "teacher_kernel_choice: weights not finalised");
+    return teacher_choice(h, B, Ts);
 }
 
 

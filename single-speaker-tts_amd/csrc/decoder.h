@@ -53,6 +53,8 @@ struct DecoderWeights {
     const float* local_vp;           // [A]
     const float* ws_wimg;            // decoder_ws.hip: the weights in register order (decoder_ws_pack), or null
     const float* ws_bimg;            // ... and the biases per workgroup
+    int ws_teacher;                  // decoder_ws.hip's teacher-forced variant may run: the attention columns of the folded
+                                     // pre-net matrix in the register image are W1a bit for bit (checked by decoder_ws_pack)
 };
 
 struct DecoderScratch {
@@ -73,9 +75,17 @@ struct DecoderScratch {
 // Enqueues the whole n_steps loop on stream s (capturable: no syncs, no allocations), including
 // the deferred alignment normalisation.  The output projection of all steps (yhist -> mel) is
 // one large GEMM issued by the caller.
+// target != null: teacher forcing (reference helpers.py:208-405, TacotronTrainingHelper) -- the pre-net reads the GO frame
+// at step 0 and mel frame t*r - 1 of target [B][n_steps*r][n_mels] (16-byte aligned) at step t >= 1, through the unfolded
+// pre-net matrix, instead of the fed-back prediction.
 hipError_t decoder_enqueue(hipStream_t s, const DecoderWeights& w, const DecoderScratch& sc,
                            const float* memory, const float* keys, int B, int Ts, int n_steps,
-                           float* align, int cudnn);
+                           float* align, int cudnn, const float* target = nullptr);
+// The teacher-forced pre-net-1 inputs of decoder_ws.hip's teacher variant: xg[b][s][P1] = x_{s+1} W1x + b1, with
+// x_{s+1} = target frame (s+1)*r - 1, for s < n_steps (row n_steps - 1 reads the last frame: computed, never used).  One
+// launch of decoder.hip's GEMM over all B * n_steps rows (its bits per row do not depend on the row count).
+hipError_t decoder_teacher_inputs(hipStream_t s, const DecoderWeights& w, const float* zeros, const float* target, int B,
+                                  int n_steps, float* xg);
 
 // ---- persistent form (decoder_persistent.hip): one launch for the whole loop; both GRU formulations, global and local attention
 struct PdParams {
@@ -126,15 +136,20 @@ struct WsParams {
     const float *local_wp, *local_vp;
     float* p_hist;                                // [n_steps][B] predicted window centres (predictive mode)
     int* err_flag;                                // raised when a predicted window leaves the memory
+    const float* xg;                              // teacher variant: decoder_teacher_inputs' [B][n_steps][256], else unused
 };
 struct DecWsHostWeights {                         // host pointers to the packed [N][K] matrices and biases of DecoderWeights
     const float *w1f, *b1f, *b1, *w2, *b2, *ag_w, *ag_b, *ac_w, *ac_b, *al_w;
+    const float* w1; int n_mels;                  // the unfolded pre-net matrix [P1][n_mels + 256] (teacher-variant check only)
     const float *g_gw[2], *g_gb[2], *g_cw[2], *g_cb[2];
     int cudnn;                                    // CudnnCompatibleGRUCell: *g_w / *g_b are the [4U][K] / [4U] blocks r | u | hh | xi, *c_* unused
 };
 size_t decoder_ws_wimg_floats();
 size_t decoder_ws_bimg_floats();
-void decoder_ws_pack(const DecWsHostWeights& hw, float* wimg, float* bimg);
+// Returns whether the teacher-forced variant may run: the attention columns of the folded pre-net matrix (w1f[:, 256:]) are
+// those of the unfolded one (w1[:, n_mels:], [P1][n_mels + 256]) bit for bit -- the only pre-net weights it multiplies in
+// the loop.  (w1 may be null: then false.)
+bool decoder_ws_pack(const DecWsHostWeights& hw, float* wimg, float* bimg);
 bool decoder_ws_supports(const DecoderWeights& w, int cudnn, int B, int Ts);
 // rows = utterances per cluster of 16 workgroups: 32 (round 5) or 16 (round 6: twice the compute units, ~0.8 of the time; the
 // same bits per utterance)
@@ -145,6 +160,10 @@ hipError_t decoder_ws_configure();                // per device
 // `sync`: 64 * max(clusters, sync_clusters) + 2 unsigned words (counters, resident count, sticky status word)
 hipError_t decoder_ws_enqueue(hipStream_t s, const DecoderWeights& w, float* scratch, float* yhist, const float* memory,
                               const float* keys, int B, int Ts, int n_steps, float* align, unsigned* sync, int* hold_flag,
-                              int cudnn, int dbg_delay, int rows = 32, int sync_clusters = 0, float* p_hist = nullptr, int* err_flag = nullptr);
+                              int cudnn, int dbg_delay, int rows = 32, int sync_clusters = 0, float* p_hist = nullptr, int* err_flag = nullptr,
+                              const float* xg = nullptr);
+// xg != null: the teacher-forced variant (template TEACH of dec_ws_kernel).  xg = decoder_teacher_inputs' [B][n_steps][256]:
+// at step t >= 1 pre-net 1 adds xg[b][t - 1] where the free form adds its bias, and multiplies only the attention half of
+// its register-resident matrix (the fed-back half is skipped: its partial tiles are zero); step 0 is the free form's.
 
 }  // namespace tts

@@ -423,7 +423,7 @@ static hipError_t run_gru(hipStream_t s, const DecoderWeights::Gru& g, const Dec
 
 hipError_t decoder_enqueue(hipStream_t s, const DecoderWeights& w, const DecoderScratch& sc,
                            const float* memory, const float* keys, int B, int Ts, int n_steps,
-                           float* align, int cudnn) {
+                           float* align, int cudnn, const float* target) {
     const int A = w.att_units, U = w.dec_units, NM = w.n_mels;
     const int P1 = w.prenet1_units, P2 = w.prenet2_units;
     const int LD = w.local_d;                       // 0: global LuongAttention
@@ -441,6 +441,9 @@ hipError_t decoder_enqueue(hipStream_t s, const DecoderWeights& w, const Decoder
         DecGemm p1;
         if (t == 0) {   // GO frame: zeros (helpers.py:108)
             p1 = mk(sc.zeros, 0, NM, sc.att, A, w.prenet1_wt, w.prenet1_b, B, P1, NM + A);
+        } else if (target) {   // teacher forcing: x_t = target frame t*r - 1 (helpers.py:208-405, outputs[:, r-1::r])
+            const int R = w.reduction;
+            p1 = mk(target + ((size_t)t * R - 1) * NM, n_steps * R * NM, NM, sc.att, A, w.prenet1_wt, w.prenet1_b, B, P1, NM + A);
         } else {        // x_t = (y_{t-1} W_o + b_o)[-n_mels:], folded into the pre-net matrix
             p1 = mk(sc.yhist + (size_t)(t - 1) * U, yld, U, sc.att, A, w.prenet1f_wt, w.prenet1f_b, B, P1, U + A);
         }
@@ -494,6 +497,16 @@ hipError_t decoder_enqueue(hipStream_t s, const DecoderWeights& w, const Decoder
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t decoder_teacher_inputs(hipStream_t s, const DecoderWeights& w, const float* zeros, const float* target, int B,
+                                  int n_steps, float* xg) {
+    const int NM = w.n_mels, A = w.att_units, P1 = w.prenet1_units, R = w.reduction;
+    // row (b, s) = frame (s + 1) * r - 1 = the last of group s: one row stride r * n_mels over all B * n_steps rows; the
+    // attention half of the operand is zeros (exact zero products)
+    DecGemm p = mk(target + (size_t)(R - 1) * NM, R * NM, NM, zeros, 0, w.prenet1_wt, w.prenet1_b, B * n_steps, P1, NM + A);
+    p.epi = DEC_EPI_ACT; p.act = ACT_NONE; p.out = xg; p.ldo = P1;
+    return run_gemm(s, p);
 }
 
 }  // namespace tts

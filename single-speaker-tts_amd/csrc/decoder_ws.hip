@@ -131,6 +131,7 @@ struct WsPhase {
     const float* next1;                 // NEXT1: segment 1 of the phase after this one (a cluster's buffer, 256 units)
     unsigned target;
     int delay;                          // tests only: workgroup 3 stages late
+    const float* xg; int xg_ld;         // XG: rows [B][xg_ld] added in place of the bias (null: the bias), see ws_phase
 };
 
 // LDS offset (floats) of element (row r of row block 0, k = kk + 4 q) of the staged tile, kk a multiple of 16; the
@@ -157,11 +158,16 @@ __device__ __forceinline__ int ws_a_off(int kk, int r, int q, int* rbs) {
 // per thread behind that phase's MFMAs, in flight during its epilogue and its publish, handed over in `pre`): it is written to
 // LDS at once, and the waves whose K slices lie inside it (4..7) run their MFMAs while lane 0 of wave 0 already polls for the
 // cluster; behind the wait only segment 0 is staged and only waves 0..3 multiply -- one wave per SIMD instead of two.
+// XG (teacher forcing, pre-net 1 behind EARLY1): segment 0 -- the fed-back output -- is neither staged nor multiplied (the
+// partial tiles of its K slices are zero) and the epilogue adds row b of ph.xg (this workgroup's units) where it adds the
+// bias: the pre-net input x_t W1x + b1, computed for all steps before the launch (decoder_teacher_inputs) -- plain loads, an
+// earlier launch on the same stream wrote it.  With ph.xg null (step 0: the GO frame) the bias, as in the free form.
 template <int M, int K0, int UB0, int K1, int TILES, int UBO, int EPI, int ACT, int ROFF, bool KEEP0 = false, int SROT = 0, bool EARLY1 = false,
-          bool NEXT1 = false>
+          bool NEXT1 = false, bool XG = false>
 __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const WsPhase& ph, float* lds, int j, int b0, int B,
                                          unsigned* cnt, int* status, float4 (&pre)[4]) {
     static_assert(!EARLY1 || (K1 == WS_D && !KEEP0), "EARLY1: a 256-unit second segment");
+    static_assert(!XG || (EARLY1 && TILES == 1 && EPI == WS_ACT), "XG: pre-net 1");
     static_assert(M == 32 || M == 16, "rows per cluster");
     constexpr int RB = M / 16;                       // 16-row blocks per wave
     constexpr int PRE = WS_D * M / 4 / WS_THREADS;   // 16-byte pieces per thread of a 256-unit buffer (the early segment)
@@ -228,7 +234,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
     // ---- stage the cluster's A tile: a linear copy of the (at most two) block-format buffers, all loads in flight together
     // (KEEP0: segment 0 is in place)
     {
-        constexpr int U0 = KEEP0 ? NLD0 : 0, U1 = EARLY1 ? NLD0 : NLD;
+        constexpr int U0 = KEEP0 ? NLD0 : 0, U1 = XG ? U0 : (EARLY1 ? NLD0 : NLD);
         const __amdgpu_buffer_rsrc_t r0 = ws_rsrc(ph.a0), r1 = ws_rsrc((K1 > 0 && !EARLY1) ? ph.a1 : ph.a0);
         float4 sv[NLD];
 #pragma unroll
@@ -239,7 +245,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
         for (int u = U0; u < U1; ++u) *reinterpret_cast<float4*>(As + 4 * (tid + WS_THREADS * u)) = sv[u];
         __syncthreads();
     }
-    if (!early) mma_slice();
+    if (!early && !XG) mma_slice();
     // C/D map of 16x16: col = lane & 15, row = (lane >> 4) * 4 + reg.  The partial tiles are indexed by (slice, tile).
     const int rslot = slice * TILES + tile;
 #pragma unroll
@@ -264,7 +270,11 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
         float4 v[TILES];
 #pragma unroll
         for (int g = 0; g < TILES; ++g) {
-            v[g] = *reinterpret_cast<const float4*>(bias + g * 16 + c4);
+            if (XG && ph.xg)   // (a padding row of the last cluster: zeros)
+                v[g] = b0 + row < B ? *reinterpret_cast<const float4*>(ph.xg + (size_t)(b0 + row) * ph.xg_ld + j * 16 + c4)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+            else
+                v[g] = *reinterpret_cast<const float4*>(bias + g * 16 + c4);
 #pragma unroll
             for (int s = 0; s < KSL; ++s) {
                 const float4 t4 = *reinterpret_cast<const float4*>(red + (((s * TILES + g) * RB + rb) * 16 + rr) * WS_RED_LD + c4);
@@ -633,7 +643,9 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
     }
 }
 
-template <bool CUDNN, int M, bool LOCAL = false>
+// TEACH: teacher forcing (reference helpers.py:208-405, TacotronTrainingHelper): pre-net 1 reads target frame t*r - 1 at step
+// t >= 1, as p.xg = x_t W1x + b1 (see ws_phase, XG); every other phase is the free form's.
+template <bool CUDNN, int M, bool LOCAL = false, bool TEACH = false>
 __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
     constexpr int PRE = WS_D * M / 4 / WS_THREADS;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -694,7 +706,8 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
         // into the pre-net matrix (decoder.hip); x_0 = GO frame = zeros (helpers.py:108): y and attention are zero at step 0,
         // so only the bias differs there (the un-folded one)
         ph.a0 = ycur; ph.a1 = att; ph.out = p1; ph.bias_slot = t == 0 ? 1 : 0; ph.target = per * g++;
-        ws_phase<M, WS_D, 16, WS_D, 1, 16, WS_ACT, ACT_RELU, WS_R0, false, 0, true, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
+        if (TEACH) { ph.xg = t > 0 ? p.xg + (size_t)(t - 1) * WS_D : nullptr; ph.xg_ld = p.n_steps * WS_D; }
+        ws_phase<M, WS_D, 16, WS_D, 1, 16, WS_ACT, ACT_RELU, WS_R0, false, 0, true, false, TEACH>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         ph.a0 = p1; ph.a1 = nullptr; ph.out = p2; ph.bias_slot = 2; ph.target = per * g++; ph.next1 = h_att_o;
         ws_phase<M, WS_D, 16, 0, 1, 8, WS_ACT, ACT_RELU, WS_R1, false, 0, false, true>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         // attention GRU (model.py:226-229) on [p2 ; h_att]; the new state is the attention query
@@ -765,10 +778,14 @@ size_t decoder_ws_scratch_floats(int B, int rows) {
 int decoder_ws_clusters(int B, int rows) { const int M = ws_rows(rows); return (B + M - 1) / M; }
 
 hipError_t decoder_ws_configure() {
-    const void* fns[8] = {reinterpret_cast<const void*>(&dec_ws_kernel<false, 32>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32>),
-                          reinterpret_cast<const void*>(&dec_ws_kernel<false, 16>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16>),
-                          reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, true>),
-                          reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, true>)};
+    const void* fns[16] = {reinterpret_cast<const void*>(&dec_ws_kernel<false, 32>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, true>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, true>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, false, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, false, true>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, false, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, false, true>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, true, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, true, true>),
+                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, true, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, true, true>)};
     for (const void* f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
         if (e != hipSuccess) return e;
@@ -781,7 +798,7 @@ hipError_t decoder_ws_configure() {
 // [DEC_WS_NREG / 4 float4][64 lanes][4]: lane (n = lane & 15, q = lane >> 4) of wave w holds, in register ROFF + 4 c + e
 // of a phase with TILES column tiles, W[gate * 256 + j * UBO + n][slice * KW + 16 c + 4 q + e] with gate = w % TILES,
 // slice = (w / TILES + SROT) % (8 / TILES) -- exactly what ws_phase multiplies the staged element (row, that k) with.  bimg [16][slots][32].
-void decoder_ws_pack(const DecWsHostWeights& hw, float* wimg, float* bimg) {
+bool decoder_ws_pack(const DecWsHostWeights& hw, float* wimg, float* bimg) {
     struct Ph { const float* Wt; int K, tiles, ubo, roff, srot, k0; };
     // srot: ws_phase's SROT (the candidate phases); k0 > 0: a CudnnCompatibleGRUCell's second half (ws_phase_hx) on the
     // [4U][K] block r | u | hh | xi: waves 0..3 hold W_ci (rows 3U..) over the k0 input columns, waves 4..7 W_ch (rows 2U..)
@@ -849,6 +866,12 @@ void decoder_ws_pack(const DecWsHostWeights& hw, float* wimg, float* bimg) {
             }
         }
     }
+    // the teacher-forced variant multiplies only the attention columns of the folded pre-net matrix (waves 4..7 of pre-net 1)
+    if (!hw.w1) return false;
+    for (int n = 0; n < WS_D; ++n)
+        if (std::memcmp(hw.w1f + (size_t)n * 2 * WS_D + WS_D, hw.w1 + (size_t)n * (hw.n_mels + WS_D) + hw.n_mels, WS_D * sizeof(float)))
+            return false;
+    return true;
 }
 size_t decoder_ws_wimg_floats() { return (size_t)WS_W * WS_NW * DEC_WS_NREG * 64; }
 size_t decoder_ws_bimg_floats() { return (size_t)WS_W * DEC_WS_BIAS_SLOTS * 32; }
@@ -859,7 +882,7 @@ size_t decoder_ws_bimg_floats() { return (size_t)WS_W * DEC_WS_BIAS_SLOTS * 32; 
 // rows: utterances per cluster (32: 16 compute units per 32 utterances; 16: per 16 -- same bits, see the LDS map)
 hipError_t decoder_ws_enqueue(hipStream_t s, const DecoderWeights& w, float* scratch, float* yhist, const float* memory,
                               const float* keys, int B, int Ts, int n_steps, float* align, unsigned* sync, int* hold_flag,
-                              int cudnn, int dbg_delay, int rows, int sync_clusters, float* p_hist, int* err_flag) {
+                              int cudnn, int dbg_delay, int rows, int sync_clusters, float* p_hist, int* err_flag, const float* xg) {
     const int M = ws_rows(rows);
     const int clusters = (B + M - 1) / M;
     // (the resident count and the sticky status word sit behind the counters of `sync_clusters` clusters: one place for
@@ -879,20 +902,24 @@ hipError_t decoder_ws_enqueue(hipStream_t s, const DecoderWeights& w, float* scr
     p.B = B; p.Ts = Ts; p.n_steps = n_steps; p.dbg_delay = dbg_delay; p.cudnn = cudnn;
     p.local_d = w.local_d; p.local_gaussian = w.local_gaussian; p.local_predictive = w.local_d > 0 && w.local_predictive;
     p.local_wp = w.local_wp; p.local_vp = w.local_vp; p.p_hist = p_hist; p.err_flag = err_flag;
+    p.xg = xg;
+    if (xg && !w.ws_teacher) return hipErrorInvalidValue;
     if (p.local_predictive) {
         if (!p_hist || !err_flag) return hipErrorInvalidValue;
         if ((e = hipMemsetAsync(err_flag, 0, sizeof(int), s)) != hipSuccess) return e;
     }
     const dim3 grid(WS_W * clusters), block(WS_THREADS);
     const size_t lds = ws_lds_bytes(Ts, M);
-#define WS_LAUNCH(C, MM, L) hipLaunchKernelGGL((dec_ws_kernel<C, MM, L>), grid, block, lds, s, p)
+#define WS_LAUNCH(C, MM, L, T) hipLaunchKernelGGL((dec_ws_kernel<C, MM, L, T>), grid, block, lds, s, p)
+#define WS_LAUNCH_T(C, MM, L) do { if (xg) WS_LAUNCH(C, MM, L, true); else WS_LAUNCH(C, MM, L, false); } while (0)
     if (w.local_d > 0) {
-        if (M == 16) { if (cudnn) WS_LAUNCH(true, 16, true); else WS_LAUNCH(false, 16, true); }
-        else { if (cudnn) WS_LAUNCH(true, 32, true); else WS_LAUNCH(false, 32, true); }
+        if (M == 16) { if (cudnn) WS_LAUNCH_T(true, 16, true); else WS_LAUNCH_T(false, 16, true); }
+        else { if (cudnn) WS_LAUNCH_T(true, 32, true); else WS_LAUNCH_T(false, 32, true); }
     } else {
-        if (M == 16) { if (cudnn) WS_LAUNCH(true, 16, false); else WS_LAUNCH(false, 16, false); }
-        else { if (cudnn) WS_LAUNCH(true, 32, false); else WS_LAUNCH(false, 32, false); }
+        if (M == 16) { if (cudnn) WS_LAUNCH_T(true, 16, false); else WS_LAUNCH_T(false, 16, false); }
+        else { if (cudnn) WS_LAUNCH_T(true, 32, false); else WS_LAUNCH_T(false, 32, false); }
     }
+#undef WS_LAUNCH_T
 #undef WS_LAUNCH
     return hipGetLastError();
 }

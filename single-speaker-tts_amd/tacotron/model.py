@@ -14,7 +14,9 @@ tacotron/inference.py:75-85) by driving the HIP library.
 ``ph_sentences``, ``ph_mel_specs`` (B, T_red, r*n_mels) and ``ph_lin_specs`` (B, T_red, r*F); the decoder
 free-runs for T_red steps and ``loss_op`` / ``loss_op_decoder`` / ``loss_op_post_processing`` are the L1
 losses of tts_evaluate (``ph_sentence_length`` / ``ph_time_frames`` are accepted and do not enter them).
-TRAIN is outside the accelerated scope and raises ``NotImplementedError``.
+TRAIN is outside the accelerated scope and raises ``NotImplementedError``.  ``Tacotron.teacher_forced_device`` runs the
+network with the decoder fed as the reference's TacotronTrainingHelper feeds it (helpers.py:208-405), in either mode; it is
+the inference network otherwise (no dropout, no batch statistics, no gradient), not Mode.TRAIN.
 """
 import os
 
@@ -139,6 +141,20 @@ class Tacotron(object):
             raise ValueError('sentences must be (B, T_sent) int32')
         return self.engine.evaluate(sentences, mel_specs, lin_specs, want_mel=want_mel, want_alignments=want_alignments,
                                     want_linear=want_linear)
+
+    def teacher_forced_device(self, sentences, mel_specs, lin_specs=None, want_mel=True, want_alignments=True,
+                              want_linear=True, want_sums=False):
+        """Teacher-forced forward pass on one batch, one tts_teacher_forced call: the decoder reads the GO frame at step 0
+        and frame t*r - 1 of ``mel_specs`` (B, T_red, r*n_mels) at step t >= 1, as the reference's TacotronTrainingHelper
+        feeds it (tacotron/helpers.py:208-405); the post-net reads that mel prediction.  The inference network otherwise:
+        no dropout, batch norm from the moving statistics, no gradient -- this is not Mode.TRAIN, and works in either mode
+        of this object.  ``lin_specs`` (B, T_red, r*F): the three L1 losses of ``evaluate_device`` as well.  Returns
+        device arrays (see Engine.teacher_forced)."""
+        sentences = np.ascontiguousarray(sentences, dtype=np.int32)
+        if sentences.ndim != 2:
+            raise ValueError('sentences must be (B, T_sent) int32')
+        return self.engine.teacher_forced(sentences, mel_specs, lin_specs, want_sums=want_sums, want_mel=want_mel,
+                                          want_alignments=want_alignments, want_linear=want_linear)
 
     @staticmethod
     def _feed(feed_dict, ph):

@@ -142,7 +142,12 @@ int tts_synchronize(tts_handle_t h);
 /* Numerics: float32 throughout.  The dense and convolution layers form their f32 products from exact three-way bf16 splits of
  * both operands on the bf16 matrix pipe (same measured error against float64 as f32-input MFMA, tests/test_gpu_gemm.py).  One
  * difference from IEEE f32 arithmetic on non-finite values: an output that depends on a +-Inf operand is NaN (the split of Inf
- * contains Inf - Inf), not +-Inf; NaN operands give NaN; every output that depends on finite operands only is unaffected. */
+ * contains Inf - Inf), not +-Inf; NaN operands give NaN; every output that depends on finite operands only is unaffected.
+ * Non-finite values on the audio side: a NaN is never turned into a plausible finite number.  Where the reference clips
+ * (np.clip, np.maximum: tts_denorm_power, the de-normalising epilogue of tts_synthesize's final Dense, tts_db_convert) a NaN
+ * input gives a NaN output at the same element, as in numpy, and +-Inf clip like any other value; every element that does not
+ * depend on the NaN keeps the bits of a clean run.  A NaN magnitude makes the waveform of ITS utterance non-finite and its
+ * Griffin-Lim mse NaN (the other utterances of the batch are untouched); no loop bound or wait of a kernel depends on data. */
 
 /* ---- weights: replaces tf.train.Saver().restore (tacotron/inference.py:55,71) ---------- */
 /* Manifest: names follow the TF variable scopes (see single-speaker-tts_amd/tacotron/weights.py). */
@@ -230,7 +235,9 @@ int tts_teacher_kernel_choice(tts_handle_t h, int B, int T_sent);
  * db = (clip(x,0,1)-1)*(|ref|+|max|)+ref, mag = 10^(db/20), mag ** power.
  * linear [B*T*F] -> mag [B*F*T].  Returns TTS_ERR_DB_RANGE when some value de-normalises to less than
  * -100 dB (decibel_to_magnitude's assertion; checked on the data, and only for constants that allow it:
- * ref - |ref| - |max| < -100 -- the call then synchronises the stream). */
+ * ref - |ref| - |max| < -100 -- the call then synchronises the stream).  A NaN in `linear` gives NaN at its transposed
+ * position of `mag` and nothing else (np.clip and np.power carry it; it does not trip the -100 dB check), +Inf clips to 1
+ * and -Inf to 0. */
 int tts_denorm_power(tts_handle_t h, const float* linear, int B, int T, int F,
                      float ref_db, float max_db, float power, float* mag);
 
@@ -244,7 +251,9 @@ int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, u
                     int B, int T, int n_iter, int win_length, int hop_length, int n_fft,
                     float* wav, float* mse);
 /* librosa.output.write_wav(norm=True) scaling (audio/io.py:53): wav /= max|wav| per
- * utterance unless the peak is below FLT_MIN.  In place, wav [B*n]. */
+ * utterance unless the peak is below FLT_MIN.  In place, wav [B*n].  NaN samples stay NaN and do not take part in the peak
+ * search (numpy's max would make the whole utterance NaN): the finite samples of that utterance are scaled by the peak of
+ * the finite ones, other utterances are not affected. */
 int tts_peak_normalize(tts_handle_t h, float* wav, int B, int n);
 
 /* ---- analysis features (audio/features.py:5-86,116-145) and dB helpers ---------------- */
@@ -262,7 +271,8 @@ int tts_mel_spectrogram(tts_handle_t h, const float* lin, int B, int n_frames, i
                         int sampling_rate, int n_mels, float fmin, float fmax, float* mel);
 /* Elementwise audio/conversion.py: mode 0 magnitude_to_decibel (:5-29), 1 decibel_to_magnitude
  * (:32-53; TTS_ERR_DB_RANGE if any input < -100, synchronous), 2 normalize_decibel (:56-78),
- * 3 inv_normalize_decibel (:81-102).  in/out [n] (may alias). */
+ * 3 inv_normalize_decibel (:81-102).  in/out [n] (may alias).  NaN in gives NaN out in every mode (np.maximum(1e-5, nan)
+ * and np.clip(nan, 0, 1) are NaN; a NaN does not trip mode 1's range check); +-Inf clip like any other value. */
 int tts_db_convert(tts_handle_t h, const float* in, size_t n, int mode, float ref_db, float max_db,
                    float* out);
 

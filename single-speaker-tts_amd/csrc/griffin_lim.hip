@@ -1203,10 +1203,11 @@ __global__ void db_convert_kernel(const float* in, float* out, size_t n, int mod
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float x = in[i];
         float y;
-        if (mode == 0) y = (float)(20.0 * log10((double)fmaxf(1e-5f, x)));   // analysis side: exact rounding
+        // np.maximum / np.clip hand a NaN on where fmaxf / fminf drop it: modes 0, 2 and 3 select it back (clip_keep_nan)
+        if (mode == 0) y = (float)(20.0 * log10((double)(x != x ? x : fmaxf(1e-5f, x))));   // analysis side: exact rounding
         else if (mode == 1) y = exp2f(x * (0.05f * 3.3219280948873623f));
-        else if (mode == 2) y = fminf(fmaxf(1.0f + (x - ref_db) / range, 0.f), 1.f);
-        else y = (fminf(fmaxf(x, 0.f), 1.f) - 1.0f) * range + ref_db;
+        else if (mode == 2) y = clip_keep_nan(1.0f + (x - ref_db) / range, 0.f, 1.f);
+        else y = (clip_keep_nan(x, 0.f, 1.f) - 1.0f) * range + ref_db;
         out[i] = y;
     }
 }

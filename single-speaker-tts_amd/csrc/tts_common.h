@@ -49,9 +49,16 @@ __device__ __forceinline__ float tanhf_(float x) {
     float e = __expf(2.0f * x);
     return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
+// np.clip(x, lo, hi): fmaxf / fminf return the other operand for a NaN, np.clip (and np.maximum) return the NaN -- a
+// compare and a select put it back; finite and infinite x take the fminf / fmaxf path bit for bit
+__device__ __forceinline__ float clip_keep_nan(float x, float lo, float hi) {
+    const float c = fminf(fmaxf(x, lo), hi);
+    return x != x ? x : c;
+}
 // reference tacotron/inference.py:96-101,175 + audio/conversion.py:102,51: clip -> dB -> magnitude -> ** power
+// (a NaN stays a NaN through all three, as in the reference: see "Non-finite values" in include/sstts_hip.h)
 __device__ __forceinline__ float denorm_db(float x, float ref_db, float range_db) {
-    const float c = fminf(fmaxf(x, 0.f), 1.f);
+    const float c = clip_keep_nan(x, 0.f, 1.f);
     return (c - 1.0f) * range_db + ref_db;
 }
 __device__ __forceinline__ float db_pow(float db, float power) {

@@ -48,6 +48,20 @@ def assert_parity(got, ref, axes, tol, label):
     return errs
 
 
+def assert_segment_parity(got, ref, hop, tol, label):
+    """A waveform [hop (T - 1)] (or a batch [B, hop (T - 1)] of them) as its hop segments [T - 1, hop]: every segment --
+    the two at the ends of an utterance, where the halo and the window sum differ, and the ones at the seams between runs
+    among them -- and every sample to `tol`, with the floor of slice_errors (a silent segment is measured against the
+    RMS one)."""
+    g = np.asarray(got)
+    r = np.asarray(ref)
+    assert g.shape == r.shape and r.shape[-1] % hop == 0, (g.shape, r.shape, hop)
+    if r.ndim == 1:
+        return assert_parity(g.reshape(-1, hop), r.reshape(-1, hop), {'seg': 0}, tol, label)
+    B = r.shape[0]
+    return assert_parity(g.reshape(B, -1, hop), r.reshape(B, -1, hop), {'utt': 0, 'seg': 1}, tol, label)
+
+
 def alignment_rows(got, ref):
     """rel-L2 of every (step, utterance) row of [S, B, Ts] alignments, as an [S, B] array.  A row of softmax weights sums
     to 1, so its norm is at least 1 / sqrt(Ts): no floor is needed (an all-zero reference row -- nothing to attend to --

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import audio_cases as C
 from conftest import pkg, rel_l2
 from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
 from oracle import audio_oracle as A
@@ -98,6 +99,12 @@ def test_stft_and_mel_features(engine):
     assert rel_l2(mel, rmel) < 1e-5
     lin2 = engine.stft_magnitude(y[None], N_FFT, WIN, HOP, 2.0).to_host()[0]
     assert rel_l2(lin2, np.abs(ref) ** 2) < 1e-5
+    # ... and per bin / channel, per frame and per element against the float64 spectrum (test_gpu_analysis.py)
+    ref64 = A.stft(y, N_FFT, HOP, WIN, dtype=np.complex128)
+    assert_parity(C.as_real(S)[None], C.as_real(ref64)[None], C.STFT_AXES, C.ANALYSIS_TOL, 'stft features stft')
+    assert_parity(lin2[None], (np.abs(ref64) ** 2)[None], C.STFT_AXES, C.ANALYSIS_TOL, 'stft features |S|^2')
+    rmel64 = np.matmul(A.mel_filterbank(22050, N_FFT, 80, 0, 8000), np.abs(ref64))
+    assert_parity(mel[None], rmel64[None], C.MEL_AXES, C.ANALYSIS_TOL, 'stft features mel')
     # default hop = win // 4, default win = n_fft (librosa defaults kept by the reference wrapper)
     S2 = F.linear_scale_spectrogram(y, N_FFT, engine=engine)
     assert S2.shape == (1025, 1 + len(y) // 512)

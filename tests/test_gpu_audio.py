@@ -7,31 +7,32 @@ convergence) within 1 %, not sample equality.
 import numpy as np
 import pytest
 
+import audio_cases as C
 from conftest import pkg, rel_l2
 from oracle import audio_oracle as A
+from parity import assert_parity, assert_segment_parity
 
 pytestmark = pytest.mark.gpu
 
 N_FFT, WIN, HOP = 2048, 1102, 275
 
 
-def synth_mag(rng, B, T):
-    """magnitude spectrograms of band-limited noise + tones, (B, 1025, T) float32."""
-    out = []
-    for b in range(B):
-        n = HOP * (T - 1)
-        t = np.arange(n) / 22050.0
-        y = 0.3 * np.sin(2 * np.pi * (220 + 40 * b) * t) + 0.1 * rng.standard_normal(n)
-        out.append(np.abs(A.stft(y.astype(np.float32), N_FFT, HOP, WIN)).astype(np.float32))
-    return np.stack(out)
+# magnitude spectrograms of band-limited noise + tones, (B, 1025, T) float32.  The generators and case tables live in
+# audio_cases.py: test_audio_bounds_host.py runs a float32 restatement over the same inputs (on the CPU) and shows it within
+# a quarter of the per-segment bounds used here.
+synth_mag = C.synth_mag
 
 
-@pytest.mark.parametrize('B,T,n_iter', [(1, 12, 0), (2, 12, 1), (2, 40, 1), (1, 70, 3)])
+def gl_segments(wav, ref_wav, hop, n_iter, label):
+    """every hop segment of an utterance's waveform -- the two at its ends and the ones at the seams between runs among
+    them -- and every sample to the bound the whole utterance is held to"""
+    assert_segment_parity(wav, ref_wav, hop, C.gl_tol(n_iter), label)
+
+
+@pytest.mark.parametrize('B,T,n_iter', C.GL_FEW)
 def test_griffin_lim_few_iterations(engine, B, T, n_iter):
-    rng = np.random.default_rng(10 * T + n_iter)
-    mag = synth_mag(rng, B, T)
+    mag, init = C.gl_few_input(B, T, n_iter)
     assert mag.shape == (B, 1025, T)
-    init = rng.random(mag.shape).astype(np.float32)
     wav, mse = engine.griffin_lim(mag, n_iter, WIN, HOP, N_FFT, init_phase=init)
     wav, mse = wav.to_host(), mse.to_host()
     for b in range(B):
@@ -40,6 +41,7 @@ def test_griffin_lim_few_iterations(engine, B, T, n_iter):
         print('GL B={} T={} it={} b={}: wav rel-L2 {:.3e} mse {} vs {}'.format(B, T, n_iter, b, e, mse[b], ref_mse))
         assert wav[b].shape == ref_wav.shape
         assert e < 1e-4 * max(1, n_iter)   # one iteration from identical phases <= 1e-4
+        gl_segments(wav[b], ref_wav, HOP, n_iter, 'GL few B={} T={} it={} b={}'.format(B, T, n_iter, b))
         if n_iter > 0:
             assert abs(mse[b] - ref_mse) <= 1e-3 * abs(ref_mse) + 1e-9
 
@@ -126,15 +128,13 @@ def test_peak_normalize(engine):
 
 
 @pytest.mark.parametrize('per_launch', [1, 2, 3])
-@pytest.mark.parametrize('B,T,n_iter,want_mse', [(2, 40, 6, False), (1, 70, 7, True), (3, 151, 5, True), (2, 9, 4, False)])
+@pytest.mark.parametrize('B,T,n_iter,want_mse', C.GL_PER_LAUNCH)
 def test_griffin_lim_iterations_per_launch(engine, per_launch, B, T, n_iter, want_mse):
     """gl_stream_kernel runs 1, 2 or 3 iterations per launch (the spectrum goes from one iteration to the next in
     registers, normalised to |S| e^{i phi} without the 32-bit phasor code in between): every split of n_iter into
     launches -- with the mse the last iteration is always a launch of its own -- against the oracle.  Runs shorter
     than the stages' lead (T = 9), runs that wrap the rings several times (T = 151), both utterance ends in one run."""
-    rng = np.random.default_rng(1000 * T + n_iter)
-    mag = synth_mag(rng, B, T)
-    init = rng.random(mag.shape).astype(np.float32)
+    mag, init = C.gl_per_launch_input(B, T, n_iter)
     engine.set_option('gl_pair', per_launch)
     try:
         wav, mse = engine.griffin_lim(mag, n_iter, WIN, HOP, N_FFT, init_phase=init, want_mse=want_mse)
@@ -147,6 +147,7 @@ def test_griffin_lim_iterations_per_launch(engine, per_launch, B, T, n_iter, wan
         e = rel_l2(wav[b], ref_wav)
         print('GL {} per launch, B={} T={} it={} b={}: wav rel-L2 {:.3e}'.format(per_launch, B, T, n_iter, b, e))
         assert e < 1e-4 * n_iter
+        gl_segments(wav[b], ref_wav, HOP, n_iter, 'GL {} per launch B={} T={} it={} b={}'.format(per_launch, B, T, n_iter, b))
         if want_mse:
             assert abs(mse[b] - ref_mse) <= 1e-3 * abs(ref_mse) + 1e-9
 
@@ -195,8 +196,8 @@ def test_griffin_lim_seeded_start(engine, per_launch, n_iter, want_mse, seed):
             assert abs(m_seed.to_host()[b] - ref_mse) <= 1e-3 * abs(ref_mse) + 1e-9
 
 
-@pytest.mark.parametrize('run_len', [8, 16, 40, 104, 296])
-@pytest.mark.parametrize('per_launch,n_iter,want_mse', [(1, 2, True), (3, 4, False)])
+@pytest.mark.parametrize('run_len', C.GL_RUN_LENS)
+@pytest.mark.parametrize('per_launch,n_iter,want_mse', C.GL_RUN_CUT_FORMS)
 def test_griffin_lim_forced_run_cuts(engine, run_len, per_launch, n_iter, want_mse):
     """Every cut of the utterances into runs gives the same waveform (the same BITS even:
     test_griffin_lim_bits_do_not_depend_on_the_cut; here against the oracle): forced run lengths from one round of the waves to longer than the utterance -- many runs per
@@ -204,9 +205,8 @@ def test_griffin_lim_forced_run_cuts(engine, run_len, per_launch, n_iter, want_m
     it 24 indices before their end, remainders of one class."""
     import os
     B, T = 5, 151
-    rng = np.random.default_rng(run_len)
-    mag = synth_mag(rng, B, T)
-    init = rng.random(mag.shape).astype(np.float32)
+    mag, init = C.gl_run_cut_input(run_len)
+    assert mag.shape == (B, 1025, T)
     engine.set_option('gl_pair', per_launch)
     engine.set_option('debug_hooks', 1)
     engine.set_option('gl_run_len', run_len)
@@ -221,6 +221,7 @@ def test_griffin_lim_forced_run_cuts(engine, run_len, per_launch, n_iter, want_m
     for b in range(B):
         ref_wav, ref_mse = A.griffin_lim_v2(mag[b], WIN, HOP, N_FFT, n_iter, init_phase=init[b])
         assert rel_l2(wav[b], ref_wav) < 1e-4 * n_iter
+        gl_segments(wav[b], ref_wav, HOP, n_iter, 'GL run_len {} {} per launch it={} b={}'.format(run_len, per_launch, n_iter, b))
         if want_mse:
             assert abs(mse[b] - ref_mse) <= 1e-3 * abs(ref_mse) + 1e-9
 
@@ -296,23 +297,14 @@ def test_griffin_lim_utterances_cut_into_different_numbers_of_runs(engine, weigh
 
 # ---- every power-of-two n_fft / window / hop on the audio surface (csrc/griffin_lim_generic.hip): the reference passes
 # n_fft, win_length and hop_length as arguments (audio/synthesis.py:5-40, 43-125; audio/features.py:5-86, 116-145)
-@pytest.mark.parametrize('n_fft,win,hop,B,T', [
-    (1024, 800, 200, 3, 60),
-    (4096, 2400, 600, 2, 40),
-    (512, 512, 128, 2, 50),        # win == n_fft, hop = win / 4 (librosa's defaults)
-    (256, 200, 50, 1, 45),
-    (2048, 1200, 300, 2, 40),      # the model's n_fft with another window / hop: the general kernels as well
-    (2048, 800, 200, 3, 60),       # 50 / 12.5 ms at 16 kHz: the streaming kernel's second instantiation (round 6)
-    (2048, 800, 200, 1, 260),      # ... several laps of its LDS ring
-    (2048, 2048, 512, 1, 30),
-])
+# (512, 512, 128): win == n_fft, hop = win / 4 (librosa's defaults); (2048, 1200, 300): the model's n_fft with another window /
+# hop, the general kernels as well; (2048, 800, 200): 50 / 12.5 ms at 16 kHz, the streaming kernel's second instantiation
+# (round 6), with T = 260 several laps of its LDS ring
+@pytest.mark.parametrize('n_fft,win,hop,B,T', C.GL_OTHER_SIZES)
 def test_griffin_lim_other_sizes_one_iteration(engine, n_fft, win, hop, B, T):
     """One iteration and the final iSTFT from identical phases against the oracle, sample by sample (<= 1e-4 of the peak),
     with the mse of the iteration."""
-    rng = np.random.default_rng(n_fft + win)
-    F = 1 + n_fft // 2
-    mag = ((rng.random((B, F, T)) ** 4) * 10).astype(np.float32)
-    init = rng.random((B, F, T)).astype(np.float32)
+    mag, init = C.gl_other_sizes_input(n_fft, win, B, T)
     wav, mse = engine.griffin_lim(mag, 1, win, hop, n_fft, init_phase=init, want_mse=True)
     wav, mse = wav.to_host(), mse.to_host()
     assert wav.shape == (B, hop * (T - 1))
@@ -320,11 +312,13 @@ def test_griffin_lim_other_sizes_one_iteration(engine, n_fft, win, hop, B, T):
         ref_wav, ref_mse = A.griffin_lim_v2(mag[b], win, hop, n_fft, 1, init_phase=init[b])
         assert np.abs(wav[b] - ref_wav).max() <= 1e-4 * max(1e-6, np.abs(ref_wav).max()), (n_fft, b)
         assert rel_l2(wav[b], ref_wav) < 2e-5
+        gl_segments(wav[b], ref_wav, hop, 1, 'GL {}/{}/{} T={} b={}'.format(n_fft, win, hop, T, b))
         assert abs(mse[b] - ref_mse) <= 1e-4 * ref_mse
     # no iteration at all: the iSTFT of the initial estimate
     wav0, _ = engine.griffin_lim(mag, 0, win, hop, n_fft, init_phase=init, want_mse=False)
     ref0, _ = A.griffin_lim_v2(mag[0], win, hop, n_fft, 0, init_phase=init[0])
     assert rel_l2(wav0.to_host()[0], ref0) < 2e-5
+    gl_segments(wav0.to_host()[0], ref0, hop, 0, 'GL {}/{}/{} T={} no iteration'.format(n_fft, win, hop, T))
 
 
 @pytest.mark.parametrize('n_fft,win,hop', [(1024, 800, 200), (4096, 2400, 600), (2048, 800, 200)])
@@ -366,6 +360,13 @@ def test_stft_and_mel_other_sizes(engine, n_fft, win, hop):
     assert mel.shape == rmel.shape == (80, 38) and rel_l2(mel, rmel) < 1e-5
     p2 = engine.stft_magnitude(y[None], n_fft, win, hop, 2.0).to_host()[0]
     assert rel_l2(p2, np.abs(ref) ** 2) < 1e-5
+    # ... and per bin / channel, per frame and per element against the float64 spectrum (test_gpu_analysis.py)
+    ref64 = A.stft(y, n_fft, hop, win, dtype=np.complex128)
+    label = 'stft other sizes {}/{}/{}'.format(n_fft, win, hop)
+    assert_parity(C.as_real(S)[None], C.as_real(ref64)[None], C.STFT_AXES, C.ANALYSIS_TOL, label + ' stft')
+    assert_parity(p2[None], (np.abs(ref64) ** 2)[None], C.STFT_AXES, C.ANALYSIS_TOL, label + ' |S|^2')
+    rmel64 = np.matmul(A.mel_filterbank(22050, n_fft, 80, 0, 8000), np.abs(ref64))
+    assert_parity(mel[None], rmel64[None], C.MEL_AXES, C.ANALYSIS_TOL, label + ' mel')
 
 
 @pytest.mark.parametrize('per_launch', [1, 2, 3])
@@ -374,9 +375,7 @@ def test_streaming_kernel_second_window_iterations_per_launch(engine, per_launch
     three iterations per launch, runs cut by the planner for a batch that does not fit one run per workgroup: 7 iterations
     against the oracle through the mse and sample-wise within the bound of test_griffin_lim_few_iterations."""
     B, T, n_iter, win, hop = 3, 150, 7, 800, 200
-    rng = np.random.default_rng(800 + per_launch)
-    mag = ((rng.random((B, 1025, T)) ** 4) * 10).astype(np.float32)
-    init = rng.random((B, 1025, T)).astype(np.float32)
+    mag, init = C.gl_second_window_input(per_launch)
     try:
         engine.set_option('gl_pair', per_launch)
         wav, mse = engine.griffin_lim(mag, n_iter, win, hop, N_FFT, init_phase=init, want_mse=True)
@@ -386,4 +385,5 @@ def test_streaming_kernel_second_window_iterations_per_launch(engine, per_launch
     for b in range(B):
         ref_wav, ref_mse = A.griffin_lim_v2(mag[b], win, hop, N_FFT, n_iter, init_phase=init[b])
         assert rel_l2(wav[b], ref_wav) < 1e-4 * n_iter, (per_launch, b)
+        gl_segments(wav[b], ref_wav, hop, n_iter, 'GL 800/200 {} per launch b={}'.format(per_launch, b))
         assert abs(mse[b] - ref_mse) <= 1e-3 * ref_mse

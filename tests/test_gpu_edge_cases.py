@@ -4,7 +4,8 @@ import numpy as np
 import pytest
 
 from conftest import pkg, rel_l2
-from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity
+import audio_cases as C
+from parity import BTC, assert_alignment_rows, assert_mel_parity, assert_parity, assert_segment_parity
 from oracle import audio_oracle as A
 from oracle import tacotron_oracle as O
 
@@ -48,18 +49,16 @@ def test_postnet_edge_shapes(engine, hparams, weights64, B, T):
     assert_parity(got, ref, BTC, 1e-3, 'postnet edge B={} T={} linear'.format(B, T))
 
 
-@pytest.mark.parametrize('T', [5, 6, 31, 32, 33, 64, 65])
+@pytest.mark.parametrize('T', C.GL_CHUNK_T)
 def test_griffin_lim_chunk_boundaries(engine, T):
-    rng = np.random.default_rng(T)
     n = HOP * (T - 1)
-    y = (0.2 * np.sin(2 * np.pi * 300 * np.arange(n) / 22050) + 0.05 * rng.standard_normal(n)).astype(np.float32)
-    mag = np.abs(A.stft(y, N_FFT, HOP, WIN)).astype(np.float32)
+    mag, init = C.gl_chunk_input(T)     # (test_audio_bounds_host.py runs float32 arithmetic over the same input)
     assert mag.shape == (1025, T)
-    init = rng.random((1, 1025, T)).astype(np.float32)
     wav, mse = engine.griffin_lim(mag[None], 2, WIN, HOP, N_FFT, init_phase=init)
     ref_wav, ref_mse = A.griffin_lim_v2(mag, WIN, HOP, N_FFT, 2, init_phase=init[0])
     assert wav.shape == (1, n)
     assert rel_l2(wav.to_host()[0], ref_wav) < 1e-4
+    assert_segment_parity(wav.to_host()[0], ref_wav, HOP, C.gl_tol(2), 'GL chunk T={}'.format(T))
     assert abs(mse.to_host()[0] - ref_mse) <= 1e-3 * ref_mse
 
 

@@ -9,7 +9,8 @@ import pytest
 
 from conftest import rel_l2
 from oracle import tacotron_oracle as O
-from parity import BTC, alignment_rows, assert_alignment_rows, assert_mel_parity, assert_parity, slice_errors
+from parity import (BTC, alignment_rows, assert_alignment_rows, assert_mel_parity, assert_parity, assert_segment_parity,
+                    slice_errors)
 
 FINAL_TOL = 1e-3
 
@@ -184,3 +185,21 @@ def test_predictive_gaussian_rows_need_an_accurate_centre(hparams, B, Ts, S, D, 
     assert accurate < 1e-4
     if vp_scale == 8.0:
         assert plain > 1e-4
+
+
+def test_one_hop_segment_of_a_waveform():
+    """a 1e-3 error in the LAST hop segment of 150 (the halo / window-sum edge of an utterance) moves the utterance's
+    rel-L2 by 8e-5 and passes 1e-4; the per-segment check fails it, for one waveform and for a batch"""
+    rng = np.random.default_rng(5)
+    hop, T = 275, 151
+    ref = rng.standard_normal((3, hop * (T - 1)))
+    got = ref.astype(np.float32).astype(np.float64)
+    assert_segment_parity(got, ref, hop, 1e-4, 'clean batch')
+    assert_segment_parity(got[1], ref[1], hop, 1e-4, 'clean')
+    got[1, -hop:] *= 1.001
+    assert rel_l2(got[1], ref[1]) < 1e-4
+    for g, r in ((got[1], ref[1]), (got, ref)):
+        with pytest.raises(AssertionError) as e:
+            assert_segment_parity(g, r, hop, 1e-4, 'last segment')
+        assert 'seg' in str(e.value) and str(T - 2) in str(e.value)
+    assert_segment_parity(got[0], ref[0], hop, 1e-4, 'the other utterances')

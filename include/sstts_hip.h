@@ -117,7 +117,17 @@ int tts_set_stream(tts_handle_t h, void* hip_stream);
  * so a call's spectrograms do not depend on what the handle ran before); 2 = any persistent kernel whenever the configuration
  * allows; 0 = never: one launch per layer; tts_synchronize reports TTS_ERR_HIP if one of its bounded waits timed out),
  * "gl_pair" (Griffin-Lim iterations per launch, 1..3, default 3: the spectrum passes from one iteration to the next in
- * registers; identical arithmetic per iteration), "gl_wide_from" (pipelined calls: the first Griffin-Lim launch that is cut
+ * registers; identical arithmetic per iteration), "gl_momentum" (fast Griffin-Lim, Perraudin / Balazs / Soendergaard 2013: the
+ * momentum alpha in thousandths, 0 .. 999, default 0 = the reference's plain loop; any other value is TTS_ERR_INVALID and
+ * leaves the option as it was.  alpha = (float)(value / 1000.0).  With c_i = stft(istft(|S| angles_i)) the next phases are
+ * those of t_i = c_i + alpha (c_i - c_{i-1}) (t_0 = c_0; a bin with t_i = 0 gets phase 0) -- librosa's and torchaudio's
+ * `momentum`, whose rebuilt - momentum / (1 + momentum) * tprev is the same t up to a positive scale; the mse stays that of
+ * the projection c_i of the last iteration.  It governs tts_griffin_lim, tts_synthesize and tts_synthesize_host alike.  With
+ * alpha > 0 the previous projection is kept per bin in float32 (8 B x B x T x 1056 of workspace at n_fft 2048, allocated
+ * by the first such call) and every iteration is a launch of its own whatever "gl_pair" says; utterances stay independent
+ * of each other, a call's waveform and mse are the same bits from run to run and whatever the cut into runs, and a NaN
+ * magnitude makes its own utterance's waveform non-finite and its mse NaN and touches no other, all as for alpha = 0),
+ * "gl_wide_from" (pipelined calls: the first Griffin-Lim launch that is cut
  * for all compute units instead of all but "reserve_cus" -- the next call's decoder has left them by then; -1 (default) =
  * from a model of the two durations, -2 = never, n >= 0 = launch n; the waveform's bits do not depend on the cut),
  * "fused_tail" (default 1: lifter + highway stack + GRU input

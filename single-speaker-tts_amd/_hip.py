@@ -202,6 +202,33 @@ def _is_device(x):
     return hasattr(x, 'data_ptr') and not isinstance(x, np.ndarray)
 
 
+def momentum_thousandths(momentum):
+    """The ``gl_momentum`` option value of a fast Griffin-Lim momentum in [0, 1): thousandths, 0 .. 999.  Anything else
+    (a NaN included) is a ValueError -- raised here, before a handle is touched."""
+    m = float(momentum)
+    if not 0.0 <= m < 1.0:
+        raise ValueError('momentum must be in [0, 1), got {!r}'.format(momentum))
+    return min(999, int(round(m * 1000.0)))
+
+
+class _MomentumScope(object):
+    """``gl_momentum`` set for the calls made inside the block and put back afterwards; None: the handle's current value."""
+
+    def __init__(self, engine, momentum):
+        self.engine = engine
+        self.value = None if momentum is None else momentum_thousandths(momentum)
+
+    def __enter__(self):
+        self.saved = self.engine._gl_momentum
+        if self.value is not None and self.value != self.saved:
+            self.engine.set_option('gl_momentum', self.value)
+
+    def __exit__(self, *exc):
+        if self.engine._gl_momentum != self.saved:
+            self.engine.set_option('gl_momentum', self.saved)
+        return False
+
+
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
@@ -246,6 +273,7 @@ class Engine(object):
         self.handle = h
         self.device_id = int(device_id)
         self._staging = {}
+        self._gl_momentum = 0   # the handle's "gl_momentum" (the C ABI has no getter: set_option keeps it)
         if stream is not None:
             self._check(self.lib.tts_set_stream(self.handle, c_void_p(stream)))
 
@@ -277,6 +305,8 @@ class Engine(object):
 
     def set_option(self, key, value):
         self._check(self.lib.tts_set_option(self.handle, key.encode(), int(value)))
+        if key == 'gl_momentum':
+            self._gl_momentum = int(value)
 
     def synchronize(self):
         self._check(self.lib.tts_synchronize(self.handle))
@@ -481,14 +511,18 @@ class Engine(object):
         self._check(self.lib.tts_denorm_power(self.handle, p_lin, B, T, F, ref_db, max_db, power, mag.data_ptr()))
         return mag
 
-    def griffin_lim(self, mag, n_iter, win_length, hop_length, n_fft, init_phase=None, seed=0, want_mse=True):
+    def griffin_lim(self, mag, n_iter, win_length, hop_length, n_fft, init_phase=None, seed=0, want_mse=True, momentum=None):
+        """``momentum``: the fast Griffin-Lim momentum in [0, 1) for this call (librosa's and torchaudio's ``momentum``;
+        0 = the reference's plain loop); None: the handle's ``gl_momentum`` option as it stands."""
+        scope = _MomentumScope(self, momentum)
         B, F, T = mag.shape
         p_mag, _k1 = self._in(mag, np.float32)
         p_init, _k2 = self._in(init_phase, np.float32)
         wav = self.empty((B, hop_length * (T - 1)))
         mse = self.empty((B,)) if want_mse else None
-        self._check(self.lib.tts_griffin_lim(self.handle, p_mag, p_init, seed, B, T, n_iter, win_length, hop_length,
-                                             n_fft, wav.data_ptr(), mse.data_ptr() if mse is not None else None))
+        with scope:
+            self._check(self.lib.tts_griffin_lim(self.handle, p_mag, p_init, seed, B, T, n_iter, win_length, hop_length,
+                                                 n_fft, wav.data_ptr(), mse.data_ptr() if mse is not None else None))
         return wav, mse
 
     def peak_normalize(self, wav):
@@ -497,7 +531,9 @@ class Engine(object):
         return wav
 
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
-                   seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None):
+                   seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
+                   momentum=None):
+        scope = _MomentumScope(self, momentum)   # (as in griffin_lim)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         F = 1 + self.cfg.n_fft // 2
@@ -519,24 +555,28 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
-                                            mel.data_ptr() if mel is not None else None,
-                                            ali.data_ptr() if ali is not None else None,
-                                            lin.data_ptr() if lin is not None else None))
+        with scope:
+            self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
+                                                mel.data_ptr() if mel is not None else None,
+                                                ali.data_ptr() if ali is not None else None,
+                                                lin.data_ptr() if lin is not None else None))
         return dict(wav=wav, mel=mel, alignments=ali, linear=lin)
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
-                        peak_normalize=True, want_linear=False, want_alignments=False):
+                        peak_normalize=True, want_linear=False, want_alignments=False, momentum=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
-        calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``."""
+        calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
+        ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs)."""
+        scope = _MomentumScope(self, momentum)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed, 1 if peak_normalize else 0,
                             (1 if want_linear else 0) | (2 if want_alignments else 0))
         t = c_int(-1)
-        self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
+        with scope:
+            self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes = getattr(self, '_host_shapes', {})
         self._host_shapes[t.value] = (B, hop_length * (n_steps * self.cfg.reduction - 1))
         self._host_out_shapes = getattr(self, '_host_out_shapes', {})

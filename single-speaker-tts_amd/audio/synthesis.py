@@ -3,14 +3,22 @@
 ``spectrogram_to_wav`` (:5-40) and ``griffin_lim_v2`` (:43-125) keep their signatures; two
 optional keyword arguments are added because the reference draws its initial phase from the
 unseeded global ``np.random`` (:85): ``init_phase`` injects those U[0,1) numbers, ``seed`` draws
-them on the device.  A leading batch axis (B, F, T) reconstructs B utterances in one call."""
+them on the device.  A leading batch axis (B, F, T) reconstructs B utterances in one call.
+
+``momentum`` (default 0.0, the reference's loop) is the fast Griffin-Lim momentum of Perraudin, Balazs and Soendergaard
+(2013), the ``momentum`` of ``librosa.griffinlim``: the next phases are those of c_i + momentum (c_i - c_{i-1}).  These two
+functions state the momentum of every call, as librosa's do: the default 0.0 runs the reference's loop even on an engine
+whose ``gl_momentum`` option has been set (``Engine.griffin_lim(momentum=None)`` is the call that follows the option)."""
 import numpy as np
 
 from . import default_engine
+from .._hip import momentum_thousandths
 
 
-def griffin_lim_v2(spectrogram, win_length, hop_length, n_fft, n_iter, init_phase=None, seed=None, engine=None):
+def griffin_lim_v2(spectrogram, win_length, hop_length, n_fft, n_iter, init_phase=None, seed=None, engine=None,
+                   momentum=0.0):
     """Returns (audio float32 (n,) or (B,n), mse float32)."""
+    momentum_thousandths(momentum)   # ValueError outside [0, 1), before an engine is made
     eng = engine or default_engine()
     spec = np.asarray(spectrogram, dtype=np.float32)
     single = spec.ndim == 2
@@ -20,15 +28,16 @@ def griffin_lim_v2(spectrogram, win_length, hop_length, n_fft, n_iter, init_phas
             init_phase = np.asarray(init_phase, dtype=np.float32)[None]
     if seed is None and init_phase is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1))   # unseeded, like the reference
-    wav, mse = eng.griffin_lim(spec, n_iter, win_length, hop_length, n_fft, init_phase=init_phase, seed=seed or 0)
+    wav, mse = eng.griffin_lim(spec, n_iter, win_length, hop_length, n_fft, init_phase=init_phase, seed=seed or 0,
+                               momentum=momentum)
     wav, mse = wav.to_host(), mse.to_host()
     if n_iter == 0:
         return (wav[0], None) if single else (wav, None)
     return (wav[0], mse[0]) if single else (wav, mse)
 
 
-def spectrogram_to_wav(mag, win_length, hop_length, n_fft, n_iter, init_phase=None, seed=None, engine=None):
+def spectrogram_to_wav(mag, win_length, hop_length, n_fft, n_iter, init_phase=None, seed=None, engine=None, momentum=0.0):
     """reference audio/synthesis.py:5-40."""
     wav, _ = griffin_lim_v2(mag, win_length=win_length, hop_length=hop_length, n_fft=n_fft, n_iter=n_iter,
-                            init_phase=init_phase, seed=seed, engine=engine)
+                            init_phase=init_phase, seed=seed, engine=engine, momentum=momentum)
     return wav.astype(np.float32)

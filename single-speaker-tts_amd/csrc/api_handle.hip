@@ -711,6 +711,10 @@ int tts_set_option(tts_handle_t h, const char* key, int value) {
         h->persistent_decoder = value;
     }
     else if (!std::strcmp(key, "gl_pair")) h->gl_pair = value;
+    else if (!std::strcmp(key, "gl_momentum")) {
+        if (value < 0 || value > 999) return fail(h, TTS_ERR_INVALID, "gl_momentum: thousandths of the momentum, 0 .. 999");
+        h->gl_momentum = value;
+    }
     else if (!std::strcmp(key, "gl_wide_from")) h->gl_wide = value < -2 ? -2 : value;
     else if (!std::strcmp(key, "pd_ws")) {
         if (value != h->pd_ws) {   // (may change whether a pipelined call's decoder is a persistent kernel at all)

@@ -135,6 +135,9 @@ struct tts_handle_s {
     //  the option that switched it is gone)
     bool ws_configured = false;
     int gl_pair = 3;                 // Griffin-Lim iterations per launch (1..3) where nothing per-iteration is asked for
+    // fast Griffin-Lim: the momentum alpha in thousandths, 0 (default: the reference's plain loop) .. 999; alpha > 0 runs one
+    // iteration per launch whatever gl_pair says (gl_stream_kernel, MOM)
+    int gl_momentum = 0;
     // First Griffin-Lim launch of a pipelined call that is cut for all compute units (gl_run, `wide_from`): -1 = by the rule
     // in gl_wide_from() below, -2 = never, >= 0 = that launch index.
     int gl_wide = -1;

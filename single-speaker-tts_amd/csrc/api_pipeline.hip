@@ -21,7 +21,7 @@ int gl_wide_from(tts_handle_t h, int B, int Ts, int n_steps, int T, int n_iter) 
     if (pd == 0) return -1;                    // launch-per-layer decoder: sleeper workgroups hold the units through the whole phase
     if (h->gl_wide >= 0) return h->gl_wide;    // (tools: an explicit launch index)
     if (pd != 2) return -1;                    // the streamed-weights decoder outlasts Griffin-Lim
-    const int per_launch = h->gl_pair < 1 ? 1 : (h->gl_pair > 3 ? 3 : h->gl_pair);
+    const int per_launch = h->gl_momentum > 0 ? 1 : (h->gl_pair < 1 ? 1 : (h->gl_pair > 3 ? 3 : h->gl_pair));   // (as gl_run)
     // The constants were measured on 256 compute units with 32 reserved (224 for Griffin-Lim) at T_s = 150: a launch scales
     // with the units Griffin-Lim really has, a decoder step with the memory length through its attention phase (8.9 of 44.5 us
     // at T_s = 150: keys and values of the whole memory per step, decoder_ws.hip).  On a device of another size the model is
@@ -58,6 +58,7 @@ int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_
     // the model's window / hop run in the streaming kernel; any other pair in the general kernels (same results to rounding)
     const bool gl_streaming = gl_is_streaming(c.n_fft, sp->win_length, sp->hop_length);
     if (gl_streaming && (rc = gl_prepare(h, T, sp->win_length, sp->hop_length, c.n_fft))) return rc;
+    bool mom_grows = false;   // this call allocates (or grows) the momentum buffer
     if (!gl_streaming && (sp->win_length < 2 || sp->win_length > c.n_fft || sp->hop_length < 1))
         return fail(h, TTS_ERR_INVALID, "synthesize: need 2 <= win_length <= n_fft, hop_length >= 1");
     if (!gl_streaming) {
@@ -72,6 +73,11 @@ int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_
         WS(h, "glg.frames", float, (size_t)B * T * sp->win_length, glg_fr);
         WS(h, "glg.mse_partial", float, (size_t)B * T, glg_ms);
         (void)glg_ph; (void)glg_fr; (void)glg_ms;
+        if (h->gl_momentum > 0 && sp->n_iter > 1) {
+            mom_grows = h->ws["glg.mom"].bytes < (size_t)B * T * FP * sizeof(float2);
+            WS(h, "glg.mom", float2, (size_t)B * T * FP, glg_mc);
+            (void)glg_mc;
+        }
     }
     // (one encoder output per call parity: the encoder of call k + 1 writes one while the decoder of call k reads the other)
     WS(h, "syn.memory.even", float, (size_t)B * Ts * 2 * c.n_gru_units, memory_e);
@@ -108,11 +114,20 @@ int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_
     WS(h, "syn.phase1.even", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph1e);
     WS(h, "syn.phase0.odd", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph0o);
     WS(h, "syn.phase1.odd", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph1o);
+    // (momentum: the previous projection, 8 bytes per bin; ONE buffer -- only Griffin-Lim launches touch it, and those of
+    //  consecutive calls follow each other on the main stream)
+    if (gl_streaming && h->gl_momentum > 0 && sp->n_iter > 1) {
+        mom_grows = h->ws["gl.mom"].bytes < (size_t)B * T * FP * sizeof(float2);
+        WS(h, "gl.mom", float2, (size_t)B * T * FP, gl_mc);
+        (void)gl_mc;
+    }
     float2* const phase_pair[2] = {reinterpret_cast<float2*>(parity ? gph0o : gph0e), reinterpret_cast<float2*>(parity ? gph1o : gph1e)};
     // Pipelined only while the library owns its stream (inputs on a borrowed stream may still be in flight) and
     // from the second call of a shape on: the first call of a new (B, Ts, n_steps) grows the workspaces, which
     // synchronises every stream -- under the CU reservation that would park the host on the sleepers' 100 ms bound.
-    const bool same_shape = h->syn_shape[0] == B && h->syn_shape[1] == Ts && h->syn_shape[2] == sp->n_steps;
+    // (the momentum option switched on between two calls of a shape: its buffer is new, and this call is unpipelined like the
+    //  first of a shape)
+    const bool same_shape = h->syn_shape[0] == B && h->syn_shape[1] == Ts && h->syn_shape[2] == sp->n_steps && !mom_grows;
     h->syn_shape[0] = B; h->syn_shape[1] = Ts; h->syn_shape[2] = sp->n_steps;
     // (a borrowed stream is pipelined only on request, pipeline = 2: the caller then vouches that the inputs of a call
     //  are complete when it is made -- the library cannot tell them from the previous call's work on that stream)

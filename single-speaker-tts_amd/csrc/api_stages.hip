@@ -303,6 +303,13 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
     WS(h, "glg.phase", float2, (size_t)B * T * Fp, ph);
     WS(h, "glg.frames", float, (size_t)B * T * win, frames);
     WS(h, "glg.mse_partial", float, (size_t)B * T, msep);
+    // fast Griffin-Lim: the previous projection per bin, allocated only for a call that has a second iteration to use it
+    const float alpha = (float)(h->gl_momentum / 1000.0);
+    float2* mom_c = nullptr;
+    if (h->gl_momentum > 0 && n_iter > 1) {
+        WS(h, "glg.mom", float2, (size_t)B * T * Fp, mc);
+        mom_c = mc;
+    }
     float* sig = wav;   // every iteration's signal estimate lives in the caller's buffer: the last one is the result
     HIPCHK(h, launch_glg_phase_init(h->stream, init_ft, seed, ph, B, F, T, Fp));
     {
@@ -311,7 +318,7 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
             HIPCHK(h, launch_glg_istft(h->stream, mag_int, ph, h->glg.window, h->glg.rwss, tw, frames, sig, B, T, Fp, n_fft, win, hop));
             const bool want_mse = mse && it == n_iter - 1;
             HIPCHK(h, launch_glg_stft(h->stream, sig, L, h->glg.window, tw, ph, B, T, Fp, n_fft, win, hop, 0, mag_int,
-                                      want_mse ? msep : nullptr));
+                                      want_mse ? msep : nullptr, mom_c, alpha, it == 0));
         }
     }
     if (mse) {
@@ -423,6 +430,15 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     int per_launch = h->gl_pair;
     per_launch = per_launch < 1 ? 1 : (per_launch > 3 ? 3 : per_launch);
     while (per_launch > 1 && gl_stream_ring_frames(win, hop, per_launch) <= 0) --per_launch;
+    // fast Griffin-Lim (option "gl_momentum"): the previous projection per bin, 8 bytes, allocated only for a call that has a
+    // second iteration to use it; such a call runs one iteration per launch (gl_stream_kernel, MOM) and is cut for that form.
+    // Without momentum nothing below differs from what it was: p.mom_c stays null and the plain instantiations are launched.
+    if (h->gl_momentum > 0 && n_iter > 1) {
+        WS(h, "gl.mom", float2, (size_t)B * T * FP, mc);
+        p.mom_c = mc;
+        p.mom_alpha = (float)(h->gl_momentum / 1000.0);
+        per_launch = 1;
+    }
     // (the cut decides who does which frames, never the waveform's bits: every sample is summed over the frames that cover it in
     //  ascending order whatever run they lie in -- tests/test_gpu_audio.py::test_griffin_lim_bits_do_not_depend_on_the_cut)
     HIPCHK(h, gl_plan_stream(p, n_cus - held > 16 ? n_cus - held : n_cus, per_launch, h->debug_hooks ? h->gl_runs : 0,
@@ -434,7 +450,8 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
                           !(h->debug_hooks && (h->gl_runs || h->gl_run_len));
     if (two_cuts) HIPCHK(h, gl_plan_stream(pw, n_cus, per_launch, 0, 0, h->stream));
     const int nchunks = std::max(p.slots_per_utt, pw.slots_per_utt);
-    WS(h, "gl.mse_partial", float, (size_t)B * nchunks, msep);
+    // (with momentum the squared error is kept per frame: gl_stream_kernel, MOM)
+    WS(h, "gl.mse_partial", float, (size_t)B * ((p.mom_c && mse) ? std::max(nchunks, T) : nchunks), msep);
     // One zeroed work counter per launch (the persistent workgroups draw their item ids from it): slots of a ring that is
     // zeroed ONCE; a launch takes the next slot and zeroes the slot of the launch before it on the stream, which is drained
     // by then.  (Until round 4 a memset per call: two fill kernels and their dependencies, 0.1 ms between the post-net and
@@ -474,8 +491,9 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
             q.phase_in = cur;
             q.phase_out = nxt;
             q.seeded = seed_in_kernel && it == 0;
+            q.mom_first = it == 0;
             q.mse_partial = want_mse ? msep : nullptr;
-            if (want_mse) mse_chunks = q.slots_per_utt;
+            if (want_mse) mse_chunks = q.mom_c ? T : q.slots_per_utt;
             next_counter(q);
             // no more workgroups than the plan counts on: one that finds its compute unit taken (the call pipeline's other
             // stream) would start when the first of the others leaves, load its tables, find no item and only

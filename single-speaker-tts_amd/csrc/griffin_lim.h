@@ -13,7 +13,7 @@ struct GlParams {
     const float2* phase_in;  // [B][T][FP] 32-bit phasor codes of the current estimate (the pointer type is historical)
     float2* phase_out;       // [B][T][FP]       (iteration)
     float* wav;              // [B][hop*(T-1)]   (final iSTFT)
-    float* mse_partial;      // [B][slots_per_utt] or null
+    float* mse_partial;      // [B][slots_per_utt] or null ([B][T], one per frame, where mom_c is set)
     float* peak_partial;     // [B][slots_per_utt] or null (final iSTFT: per-run max |wav|)
     const float* window;     // [win] periodic hann
     const float* wlane;      // [2][64 lanes][16][2] per-lane window images (gl_build_wlane): analysis / interior synthesis
@@ -39,6 +39,12 @@ struct GlParams {
     unsigned long long seed;
     unsigned* work_counter;  // zeroed counter of THIS launch: the persistent workgroups draw item ids from it
     unsigned* clear_counter; // null, or the counter of an EARLIER launch on this stream: one thread zeroes it for a later launch
+    // fast Griffin-Lim (momentum, gl_stream_kernel MOM): the projection c of the previous iteration, [B][T][FP] complex, in the
+    // kernel's scale (X / 1024), read and rewritten in place by the run that owns a frame; null = the plain iteration.
+    // mom_first: the first iteration of a call (t = c: nothing is read, the buffer need not be initialised)
+    float2* mom_c;
+    float mom_alpha;
+    int mom_first;
 };
 
 // out[2*16*2*64]: set 0 = window[n] / n_fft, set 1 = set 0 * rwss at an interior frame; n = 2*(lane + 64 c) + e
@@ -81,7 +87,10 @@ hipError_t launch_glg_istft(hipStream_t s, const float* mag, const float2* ph, c
                             float* frames, float* wav, int B, int T, int Fp, int n_fft, int win, int hop);
 // mode 0: out = unit phasors of the spectrum (+ per-frame squared magnitude error against mag when mse_partial != null);
 // mode 1: out = the complex spectrum
+// mom_c != null (mode 0): the momentum form -- the phasors are those of t = c + alpha (c - previous c), the spectrum c is read
+// from and rewritten to mom_c [B][Tf][Fp] (mom_first: t = c, nothing read)
 hipError_t launch_glg_stft(hipStream_t s, const float* wav, int n, const float* window, const float2* tw, float2* out, int B, int Tf, int Fp,
-                           int n_fft, int win, int hop, int mode, const float* mag, float* mse_partial);
+                           int n_fft, int win, int hop, int mode, const float* mag, float* mse_partial, float2* mom_c = nullptr,
+                           float mom_alpha = 0.f, int mom_first = 0);
 
 }  // namespace tts

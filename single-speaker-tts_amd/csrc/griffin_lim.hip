@@ -207,9 +207,18 @@ enum { CT_OLA = 0, CT_SNEXT = 1, CT_OLB = 2 /* chain words of stages 1, 2 */, CT
 // more frames at either end in stage A (2.6 % more transforms for runs of 144 frames).
 // SEEDED: stage 0 makes its input from the seed (the first launch of a call without an initial-phase array) -- an
 // instantiation of its own: as a run-time branch it cost every launch 38 more spilled registers.
-template <int MODE, int WIN_CT, int HOP_CT, bool MSE, int NST = 1, bool SEEDED = false>
+// MOM: fast Griffin-Lim (Perraudin, Balazs, Soendergaard 2013).  The phasor code that leaves the launch is that of
+// t = c + alpha (c - c_prev) instead of the projection c itself; c (the merged spectrum X / MH, 8 bytes per bin, float32: a
+// 16-bit state does not hold the parity bound) goes to p.mom_c, from where the next iteration reads it as c_prev.  One
+// iteration per launch only: the frames whose c a run reads and writes are then exactly the frames it owns (the halo frames
+// of a run are decoded from their codes and transformed back, never projected), so the buffer is updated in place, no run
+// reads what another writes and the cut does not reach the bits.  Fused stages would need stage k's c of a frame `lag`
+// indices later in another wave: 8.2 KB per frame, a dozen frames per stage -- more than the rings leave of the LDS
+// ("Fast Griffin-Lim").  The first iteration of a call (p.mom_first) has no c_prev: t = c, nothing is read.
+template <int MODE, int WIN_CT, int HOP_CT, bool MSE, int NST = 1, bool SEEDED = false, bool MOM = false>
 __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     static_assert(!SEEDED || MODE == 0, "the seeded start is an iteration's");
+    static_assert(!MOM || (MODE == 0 && NST == 1), "momentum: one iteration per launch");
     static_assert(NST == 1 || (NST >= 2 && NST <= 3 && MODE == 0 && !MSE), "several iterations per launch: plain iterations only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int win = WIN_CT ? WIN_CT : p.win;
@@ -726,13 +735,39 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
 #pragma unroll
                     for (int c = 0; c < 16; ++c) mg[c] = fabsf(GL_STREAM_LOAD(c < 8 ? mrow + lane + 64 * c : mrow + (MH - lane) - 64 * (c - 8)));
                 }
+                // momentum: the previous projection of this frame, requested in front of the transform that covers the loads
+                cf cp[16], cp_mid = cmk(0.f, 0.f);
+                cf* const crow = MOM ? reinterpret_cast<cf*>(p.mom_c) + ((size_t)b * p.T + tm) * p.FP : nullptr;
+                cf* const clo = MOM ? crow + lane : nullptr;
+                cf* const chi = MOM ? crow + (MH - lane) : nullptr;
+                const bool mom_prev = MOM && !p.mom_first;   // (a kernel argument: a scalar branch)
+                if (MOM) {
+#pragma unroll
+                    for (int c = 0; c < 16; ++c) cp[c] = cmk(0.f, 0.f);
+                    if (mom_prev) {
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) cp[c] = __builtin_nontemporal_load(c < 8 ? clo + 64 * c : chi - 64 * (c - 8));
+                        cp_mid = crow[MH / 2];
+                    }
+                }
+                // t = c + alpha (c - c_prev); the first iteration of a call: t = c
+                auto mom_t = [&](cf x, cf prev) __attribute__((always_inline)) -> cf {
+                    return mom_prev ? cadd(x, cscale(csub(x, prev), p.mom_alpha)) : x;
+                };
                 fft_input(ring_k, jj, sm, tm, yb_k, v);
                 fft1024<FZ_LO, FZ_HI>(v, ex, tw, lane);
                 GLS_URGENCY(i + GL_NW)
+                // momentum: the squared error goes out per FRAME (p.mse_partial [B][T], summed in frame order by the reduction), so
+                // that the mse, like the waveform, is the same bits whatever runs the frames lie in
+                if (MOM && MSE) mse_acc = 0.f;
                 gl_state_t* orow = x_out + ((size_t)b * p.T + tm) * p.FP;
                 gl_state_t* olo = orow + lane;
                 gl_state_t* ohi = orow + (MH - lane);
                 const cf xmid = merge_pass(v, [&](int c, cf x) {
+                    if (MOM) {
+                        GL_STREAM_STORE(c < 8 ? clo + 64 * c : chi - 64 * (c - 8), x);
+                        __builtin_nontemporal_store(gl_state_encode(mom_t(x, cp[c])), c < 8 ? olo + 64 * c : ohi - 64 * (c - 8));
+                    } else
                     __builtin_nontemporal_store(gl_state_encode(x), c < 8 ? olo + 64 * c : ohi - 64 * (c - 8));
                     if (MSE) {
                         const float d = mg[c] - (float)MH * sqrtf(fmaf(x.x, x.x, x.y * x.y));   // x = X / MH
@@ -740,11 +775,18 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                     }
                 });
                 if (lane == 0) {
-                    __builtin_nontemporal_store(gl_state_encode(xmid), orow + MH / 2);   // bin 512
+                    if (MOM) crow[MH / 2] = xmid;
+                    __builtin_nontemporal_store(gl_state_encode(MOM ? mom_t(xmid, cp_mid) : xmid), orow + MH / 2);   // bin 512
                     if (MSE) {
                         const float d = fabsf(mrow[MH / 2]) - (float)MH * sqrtf(fmaf(xmid.x, xmid.x, xmid.y * xmid.y));
                         mse_acc += d * d;
                     }
+                }
+                if (MOM && MSE) {
+                    float r = mse_acc;
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) r += __shfl_xor(r, o);
+                    if (lane == 0) p.mse_partial[(size_t)b * p.T + tm] = r;
                 }
             }
             s += GL_NW;
@@ -752,7 +794,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         }
         __builtin_amdgcn_s_setprio(0);
         // ---------------- run end: per-run partial results (fixed order), then everyone is done with the rings
-        if ((MODE == 0 && MSE) || (MODE == 1 && p.peak_partial)) {
+        if ((MODE == 0 && MSE && !MOM) || (MODE == 1 && p.peak_partial)) {
             float r = MODE == 0 ? mse_acc : pk;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) r = MODE == 0 ? r + __shfl_xor(r, o) : fmaxf(r, __shfl_xor(r, o));
@@ -1004,6 +1046,13 @@ static hipError_t gl_stream_set_attr() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, NST, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
+// the momentum instantiations: plain, seeded (a call's first launch) and with the mse (its last); a call with momentum has at
+// least two iterations, so no launch is seeded AND asked for the mse
+template <int W, int H, bool MSE, bool SEEDED>
+static hipError_t gl_stream_set_attr_mom() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, 1, SEEDED, true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
 
 // The (window, hop) pairs the streaming kernel is instantiated for (both windows in registers, every span bound static): the
 // model's 50 ms / 12.5 ms at the reference's 22.05 kHz (1102 / 275, dataset_params.sampling_rate; audio/conversion.py:122-136)
@@ -1018,6 +1067,14 @@ static hipError_t gl_stream_launch_wh(hipStream_t s, const GlParams& p, dim3 gri
     {                                                                                                                    \
         if (MODE == 0 && p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, M, N, true>), grid, dim3(GL_THREADS), lds, s, p);   \
         else hipLaunchKernelGGL((gl_stream_kernel<MODE, W, H, M, N, false>), grid, dim3(GL_THREADS), lds, s, p);        \
+    }
+    // the momentum form: instantiations of their own, one iteration per launch; a call without momentum never comes here
+    if (p.mom_c && !final_istft) {
+        if (mse && p.seeded) return hipErrorInvalidValue;   // (see gl_stream_set_attr_mom)
+        if (mse) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, true, 1, false, true>), grid, dim3(GL_THREADS), lds, s, p);
+        else if (p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, true, true>), grid, dim3(GL_THREADS), lds, s, p);
+        else hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, false, true>), grid, dim3(GL_THREADS), lds, s, p);
+        return hipGetLastError();
     }
     if (n_stage == 3) GLS_LAUNCH_N(0, false, 3)
     else if (n_stage == 2) GLS_LAUNCH_N(0, false, 2)
@@ -1036,6 +1093,7 @@ hipError_t launch_gl_stream(hipStream_t s, const GlParams& p_in, int n_cus, int 
     p.n_stage = n_stage;
     p.ring_frames = gl_stream_ring_frames(p.win, p.hop, n_stage);
     if (p.ring_frames < GL_NW || n_stage < 1 || n_stage > 3 || (n_stage > 1 && (final_istft || p.mse_partial))) return hipErrorInvalidValue;
+    if (p.mom_c && !final_istft && n_stage != 1) return hipErrorInvalidValue;   // momentum: one iteration per launch
     const size_t lds = gl_stream_lds_bytes(p);
     // one workgroup per compute unit (256 registers x 8 waves), as many as the cut was made for
     const int nwg = p.n_workers > 0 && p.n_workers < n_cus ? p.n_workers : (p.n_items < n_cus ? p.n_items : n_cus);
@@ -1054,6 +1112,9 @@ static hipError_t gl_stream_configure_wh() {
     if ((e = gl_stream_set_attr<0, W, H, false, 2>()) != hipSuccess) return e;
     if ((e = gl_stream_set_attr<0, W, H, false, 3>()) != hipSuccess) return e;
     if ((e = gl_stream_set_attr<1, W, H, false>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr_mom<W, H, false, false>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr_mom<W, H, false, true>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr_mom<W, H, true, false>()) != hipSuccess) return e;
     return hipSuccess;
 }
 hipError_t gl_stream_configure() {

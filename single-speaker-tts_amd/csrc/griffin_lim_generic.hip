@@ -89,11 +89,15 @@ __global__ void glg_ola_kernel(const float* __restrict__ frames, const float* __
 // ------------------------------------------------------------------------------------------------ forward transform
 // MODE 0: out_ph = unit phasors of the spectrum (the next iteration's estimate), optional mse partials (one per frame);
 // MODE 1: out_z = the complex spectrum itself (tts_stft)
+// MODE 0 with mom_c != null: fast Griffin-Lim -- the phasors are those of t = c + alpha (c - c_prev), c the spectrum of this
+// iteration; c_prev is read from mom_c [B][Tf][Fp] and c written in its place (a frame's row is its workgroup's alone).  The
+// first iteration of a call (mom_first) reads nothing: t = c.  The mse stays that of the projection c.
 template <int MODE>
 __global__ __launch_bounds__(GLG_THREADS) void glg_stft_kernel(const float* __restrict__ wav, int n, const float* __restrict__ window,
                                                                const gcf* __restrict__ tw, gcf* __restrict__ out, int Tf, int Fp, int N,
                                                                int m, int win, int hop, const float* __restrict__ mag,
-                                                               float* __restrict__ mse_partial) {
+                                                               float* __restrict__ mse_partial, gcf* mom_c, float mom_alpha,
+                                                               int mom_first) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     gcf* a = reinterpret_cast<gcf*>(smem);
     __shared__ float red[GLG_THREADS / 64];
@@ -131,9 +135,18 @@ __global__ __launch_bounds__(GLG_THREADS) void glg_stft_kernel(const float* __re
             out[row + k] = z;
         } else {
             const float s2 = z.x * z.x + z.y * z.y;
-            const float r = rsqrtf(s2);
+            gcf tz = z;
+            if (mom_c) {
+                if (!mom_first) {
+                    const gcf prev = mom_c[row + k];
+                    tz = (gcf){z.x + mom_alpha * (z.x - prev.x), z.y + mom_alpha * (z.y - prev.y)};
+                }
+                mom_c[row + k] = z;
+            }
+            const float t2 = tz.x * tz.x + tz.y * tz.y;
+            const float r = rsqrtf(t2);
             // numpy: exp(1j * angle(0)) = 1
-            out[row + k] = (k <= H && s2 > 1.0e-37f) ? (gcf){z.x * r, z.y * r} : (gcf){1.f, 0.f};
+            out[row + k] = (k <= H && t2 > 1.0e-37f) ? (gcf){tz.x * r, tz.y * r} : (gcf){1.f, 0.f};
             if (mse_partial && k <= H) {
                 const float d = fabsf(mag[row + k]) - sqrtf(s2);
                 err += d * d;
@@ -213,14 +226,17 @@ hipError_t launch_glg_istft(hipStream_t s, const float* mag, const float2* ph, c
 }
 
 hipError_t launch_glg_stft(hipStream_t s, const float* wav, int n, const float* window, const float2* tw, float2* out, int B, int Tf, int Fp,
-                           int n_fft, int win, int hop, int mode, const float* mag, float* mse_partial) {
+                           int n_fft, int win, int hop, int mode, const float* mag, float* mse_partial, float2* mom_c, float mom_alpha,
+                           int mom_first) {
     const int m = glg_log2(n_fft);
     if (mode == 1)
         hipLaunchKernelGGL((glg_stft_kernel<1>), dim3(Tf, B), dim3(glg_threads(n_fft)), glg_lds(n_fft), s, wav, n, window,
-                           reinterpret_cast<const gcf*>(tw), reinterpret_cast<gcf*>(out), Tf, Fp, n_fft, m, win, hop, mag, mse_partial);
+                           reinterpret_cast<const gcf*>(tw), reinterpret_cast<gcf*>(out), Tf, Fp, n_fft, m, win, hop, mag, mse_partial,
+                           (gcf*)nullptr, 0.f, 0);
     else
         hipLaunchKernelGGL((glg_stft_kernel<0>), dim3(Tf, B), dim3(glg_threads(n_fft)), glg_lds(n_fft), s, wav, n, window,
-                           reinterpret_cast<const gcf*>(tw), reinterpret_cast<gcf*>(out), Tf, Fp, n_fft, m, win, hop, mag, mse_partial);
+                           reinterpret_cast<const gcf*>(tw), reinterpret_cast<gcf*>(out), Tf, Fp, n_fft, m, win, hop, mag, mse_partial,
+                           reinterpret_cast<gcf*>(mom_c), mom_alpha, mom_first);
     return hipGetLastError();
 }
 

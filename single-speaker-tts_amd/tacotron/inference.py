@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from .._hip import momentum_thousandths
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
 from .model import Mode, Tacotron
@@ -50,9 +51,12 @@ def inference(model, sentences, n_steps=None):
     return [mag[b] for b in range(mag.shape[0])]
 
 
-def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False):
+def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
+                     momentum=0.0):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
-    of the reference (tacotron/inference.py:170-188) fused into one device call."""
+    of the reference (tacotron/inference.py:170-188) fused into one device call.  ``momentum``: fast Griffin-Lim
+    (audio.synthesis), 0.0 = the reference's loop."""
+    momentum_thousandths(momentum)   # ValueError outside [0, 1), before the engine is touched
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -61,12 +65,12 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     out = model.engine.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), S, loader.mel_mag_ref_db,
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
-                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize)
+                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum)
     return out['wav'].to_host()
 
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
-                      want_alignments=False):
+                      want_alignments=False, momentum=0.0):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -76,7 +80,8 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     With ``want_linear`` / ``want_alignments`` every item is a tuple ``(wavs, linear, alignments)``: the normalised linear
     spectrograms (B, T, 1025) -- what ``model.output_linear_spec`` is, the thing the reference's ``inference()`` fetches
     (:75-92) -- and the alignments (n_steps, B, T_sent) of the same call, downloaded behind the waveforms (None where not
-    asked for)."""
+    asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop."""
+    momentum_thousandths(momentum)   # (a generator: raised at its first item, before the engine is touched)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -98,24 +103,26 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     for k, ids in enumerate(batches):
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
-                                           want_alignments=want_alignments))
+                                           want_alignments=want_alignments, momentum=momentum))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
         yield collect(pending.pop(0))
 
 
-def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0):
+def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum=0.0):
     """``inference()`` over a stream of batches with three calls in flight: per batch ``(spectrograms, waveforms)`` where
     ``spectrograms`` is what the reference's ``inference()`` returns for that batch -- per utterance the (1025, T) linear
     magnitude spectrogram ``decibel_to_magnitude(inv_normalize_decibel(spec.T, mel_ref_db, mel_max_db))``
     (tacotron/inference.py:93-101; computed on the host from the downloaded network output with the conversions of
     ``audio.conversion``) -- and ``waveforms`` the Griffin-Lim reconstructions the reference's ``__main__`` makes of them
-    (:170-188)."""
+    (:170-188).  ``momentum`` as in ``synthesize_stream``."""
+    momentum_thousandths(momentum)
     loader = dataset_params.dataset_loader
     ref_db, max_db = np.float32(loader.mel_mag_ref_db), np.float32(loader.mel_mag_max_db)
     rng_db = np.float32(abs(float(ref_db)) + abs(float(max_db)))
-    for wavs, lin, _ in synthesize_stream(model, batches, n_steps=n_steps, n_iter=n_iter, seed=seed, copy=True, want_linear=True):
+    for wavs, lin, _ in synthesize_stream(model, batches, n_steps=n_steps, n_iter=n_iter, seed=seed, copy=True, want_linear=True,
+                                          momentum=momentum):
         specs = []
         for b in range(lin.shape[0]):
             # inv_normalize_decibel, decibel_to_magnitude (reference audio/conversion.py:81-102, 32-53) in host arithmetic:
@@ -126,11 +133,12 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0):
         yield specs, wavs
 
 
-def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0):
+def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
     float32 WAV, save_wav(norm=True)).  Returns the list of waveforms."""
+    momentum_thousandths(momentum)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -142,7 +150,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     max_length = max(sequence_lengths)
     sentences = np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False)
+    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum)
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, True)
     return list(wavs)
@@ -164,19 +172,13 @@ def main(argv=None):
 
         python -m single-speaker-tts_amd.tacotron.inference [--synthesis-file F] [--synthesis-dir D]
                                                             [--weights CKPT | --synthetic-weights SEED]
+                                                            [--momentum ALPHA]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
     variables); ``--synthetic-weights`` a seed for the synthetic initialiser (no checkpoint ships with the reference)."""
-    import argparse
-    ap = argparse.ArgumentParser(prog='tacotron.inference')
-    ap.add_argument('--synthesis-file', default=None)
-    ap.add_argument('--synthesis-dir', default=None)
-    ap.add_argument('--weights', default=None)
-    ap.add_argument('--synthetic-weights', type=int, default=None)
-    ap.add_argument('--device', type=int, default=0)
-    ap.add_argument('--seed', type=int, default=0, help='seed of the Griffin-Lim start phases (the reference draws them unseeded)')
-    args = ap.parse_args(argv)
+    args = parse_args(argv)
+    momentum_thousandths(args.momentum)
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -192,10 +194,26 @@ def main(argv=None):
         weights = inference_params.checkpoint_file
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
-    wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed)
+    wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
+                                momentum=args.momentum)
     for i in range(len(wavs)):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
+
+
+def parse_args(argv=None):
+    """The command line of ``main``."""
+    import argparse
+    ap = argparse.ArgumentParser(prog='tacotron.inference')
+    ap.add_argument('--synthesis-file', default=None)
+    ap.add_argument('--synthesis-dir', default=None)
+    ap.add_argument('--weights', default=None)
+    ap.add_argument('--synthetic-weights', type=int, default=None)
+    ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--seed', type=int, default=0, help='seed of the Griffin-Lim start phases (the reference draws them unseeded)')
+    ap.add_argument('--momentum', type=float, default=0.0,
+                    help='fast Griffin-Lim momentum in [0, 1); 0 (default) is the reference\'s loop, librosa uses 0.99')
+    return ap.parse_args(argv)
 
 
 if __name__ == '__main__':

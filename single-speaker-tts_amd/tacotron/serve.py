@@ -8,6 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
+from .._hip import momentum_thousandths
 from ..audio.conversion import ms_to_samples
 from .inference import pad_sentence
 from .model import Mode, Tacotron
@@ -22,9 +23,11 @@ def pre_process_sentences(_sentences, dataset):
     return np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
 
 
-def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0):
+def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
-    constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86)."""
+    constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86); ``momentum``: fast Griffin-Lim
+    (audio.synthesis), 0.0 = the reference's loop."""
+    momentum_thousandths(momentum)
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
     win_hop = ms_to_samples(model_params.win_hop, model_params.sampling_rate)
@@ -33,12 +36,12 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0):
         spec = spec[None]
     mag = engine.denorm_power(spec, loader.mel_mag_ref_db, loader.mel_mag_max_db, model_params.magnitude_power)
     wav, _ = engine.griffin_lim(mag, model_params.reconstruction_iterations, win_len, win_hop, model_params.n_fft,
-                                init_phase=init_phase, seed=seed, want_mse=False)
+                                init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum)
     wav = wav.to_host()
     return [wav[b] for b in range(wav.shape[0])]
 
 
-def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False):
+def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -46,7 +49,9 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     ``sentence_generator`` (reference serve.py:108-124 blocks on a live generator, and a client may wait for its answer
     before it sends more).  ``pipelined=True`` keeps three batches in flight for OFFLINE streams whose batches are all
     available: batch k is then yielded only after batch k + 2 has been pulled from the generator (the last one when the
-    generator ends), which on a request-driven generator would hold every answer back by two requests."""
+    generator ends), which on a request-driven generator would hold every answer back by two requests.
+    ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop."""
+    momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
@@ -55,10 +60,10 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
         for sentences in sentence_generator:
             ids = pre_process_sentences(sentences, dataset)
             spectrograms = model.run(model.output_linear_spec, {model.inp_sentences: ids})
-            yield post_process_spectrograms(spectrograms, model.engine)
+            yield post_process_spectrograms(spectrograms, model.engine, momentum=momentum)
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
-    for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True):
+    for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum):
         yield [wavs[b] for b in range(wavs.shape[0])]

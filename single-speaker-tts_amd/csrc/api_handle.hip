@@ -355,6 +355,13 @@ GruOffsets pack_dec_gru(tts_handle_t h, Packer& p, const std::string& scope, int
 // Did every bounded wait of the persistent decoder's launches so far end by arrival?  The status word is STICKY on the
 // device (no launch clears it): a timeout in call j is still there when call j + 1 has been queued behind it; the
 // host clears the word when it has read it.  The caller has synchronised the streams the kernels ran on.
+int pd_timed_out(tts_handle_t h) {
+    return fail(h, TTS_ERR_HIP,
+                "persistent decoder: a workgroup waited for its cluster longer than the bound (not all "
+                "workgroups were co-resident); the outputs of that call are invalid -- the handle has "
+                "switched to the launch-per-layer path (tts_set_option(h, \"persistent_decoder\", 1) switches back)");
+}
+
 int check_status(tts_handle_t h) {
     if (h->pd_used) {
         h->pd_used = false;
@@ -362,11 +369,7 @@ int check_status(tts_handle_t h) {
         HIPCHK(h, hipMemcpy(&status, h->pd_sync + 64 * h->pd_clusters + 1, sizeof(int), hipMemcpyDeviceToHost));
         if (status) HIPCHK(h, hipMemset(h->pd_sync + 64 * h->pd_clusters + 1, 0, sizeof(int)));
         if (status) h->persistent_decoder = 0;   // every later call takes the launch-per-layer path by itself
-        if (status)
-            return fail(h, TTS_ERR_HIP,
-                        "persistent decoder: a workgroup waited for its cluster longer than the bound (not all "
-                        "workgroups were co-resident); the outputs of that call are invalid -- the handle has "
-                        "switched to the launch-per-layer path (tts_set_option(h, \"persistent_decoder\", 1) switches back)");
+        if (status) return pd_timed_out(h);
     }
     return TTS_OK;
 }
@@ -374,20 +377,18 @@ int check_status(tts_handle_t h) {
 
 int sync_all(tts_handle_t h) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->front && h->front != h->stream) HIPCHK(h, hipStreamSynchronize(h->front));
-    if (h->aux) HIPCHK(h, hipStreamSynchronize(h->aux));
-    if (h->encs) HIPCHK(h, hipStreamSynchronize(h->encs));
+    if (h->pl.front && h->pl.front != h->stream) HIPCHK(h, hipStreamSynchronize(h->pl.front));
+    if (h->pl.aux) HIPCHK(h, hipStreamSynchronize(h->pl.aux));
+    if (h->pl.encs) HIPCHK(h, hipStreamSynchronize(h->pl.encs));
     if (h->hio.out) HIPCHK(h, hipStreamSynchronize(h->hio.out));
     return check_status(h);
 }
 
 
-// the decoder graph's last launch has finished (see ev_graph_done)
+// the decoder graph's last launch has finished (see graph_done)
 int graph_quiesce(tts_handle_t h) {
-    if (h->graph_in_flight) {
-        HIPCHK(h, hipEventSynchronize(h->ev_graph_done));
-        h->graph_in_flight = false;
-    }
+    HIPCHK(h, h->graph_done.sync());
+    h->graph_done.disarm();
     return TTS_OK;
 }
 
@@ -605,52 +606,13 @@ int tts_destroy(tts_handle_t h) {
     if (h->an.mel_wt) hipFree(h->an.mel_wt);
     feat_release(h);
     if (h->an.flag) hipFree(h->an.flag);
-    if (h->front) {
-        hipStreamSynchronize(h->front);
-        hipStreamDestroy(h->front);
-    }
-    if (h->aux) {
-        hipStreamSynchronize(h->aux);
-        hipStreamDestroy(h->aux);
-    }
-    if (h->hold_flags) hipFree(h->hold_flags);
-    for (int i = 0; i < 3; ++i) {
-        if (h->hio.ids_pinned[i]) hipHostFree(h->hio.ids_pinned[i]);
-        if (h->hio.ids_dev[i]) hipFree(h->hio.ids_dev[i]);
-        if (h->hio.wav_pinned[i]) hipHostFree(h->hio.wav_pinned[i]);
-        if (h->hio.wav_dev[i]) hipFree(h->hio.wav_dev[i]);
-        if (i == 0) {
-            for (auto& kv : h->glg.tw) hipFree(kv.second);
-            if (h->glg.window) hipFree(h->glg.window);
-            if (h->glg.rwss) hipFree(h->glg.rwss);
-        }
-        if (h->hio.lin_pinned[i]) hipHostFree(h->hio.lin_pinned[i]);
-        if (h->hio.lin_dev[i]) hipFree(h->hio.lin_dev[i]);
-        if (h->hio.ali_pinned[i]) hipHostFree(h->hio.ali_pinned[i]);
-        if (h->hio.ali_dev[i]) hipFree(h->hio.ali_dev[i]);
-        if (h->hio.ev_h2d[i]) hipEventDestroy(h->hio.ev_h2d[i]);
-        if (h->hio.ev_enc[i]) hipEventDestroy(h->hio.ev_enc[i]);
-        if (h->hio.ev_ready[i]) hipEventDestroy(h->hio.ev_ready[i]);
-        if (h->hio.ev_d2h[i]) hipEventDestroy(h->hio.ev_d2h[i]);
-    }
-    if (h->hio.status_pinned) hipHostFree(h->hio.status_pinned);
-    if (h->hio.out) hipStreamDestroy(h->hio.out);
-    if (h->ev_aux) hipEventDestroy(h->ev_aux);
-    if (h->ev_front_done) hipEventDestroy(h->ev_front_done);
-    for (int i = 0; i < 2; ++i) {
-        if (h->ev_enc_ready[i]) hipEventDestroy(h->ev_enc_ready[i]);
-        if (h->ev_dec_done[i]) hipEventDestroy(h->ev_dec_done[i]);
-        if (h->ev_gap[i]) hipEventDestroy(h->ev_gap[i]);
-    }
-    if (h->encs) hipStreamDestroy(h->encs);
-    if (h->ev_serial_done) hipEventDestroy(h->ev_serial_done);
-    if (h->ev_graph_done) hipEventDestroy(h->ev_graph_done);
-    for (int i = 0; i < 2; ++i) {
-        if (h->ev_post_done[i]) hipEventDestroy(h->ev_post_done[i]);
-        if (h->ev_gl_done[i]) hipEventDestroy(h->ev_gl_done[i]);
-    }
+    for (auto& kv : h->glg.tw) hipFree(kv.second);
+    if (h->glg.window) hipFree(h->glg.window);
+    if (h->glg.rwss) hipFree(h->glg.rwss);
+    h->pl.teardown();
+    h->hio.teardown();
     if (h->own_stream) hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // frees the staging buffers and the signals' events (member destructors): keep it inside dev_scope
     return TTS_OK;
 }
 
@@ -665,9 +627,7 @@ int tts_set_stream(tts_handle_t h, void* s) {
         int rc = sync_all(h);
         if (rc) return rc;
     }
-    h->post_pending[0] = h->post_pending[1] = false;
-    h->gl_pending[0] = h->gl_pending[1] = false;
-    h->gl_wide_used[0] = h->gl_wide_used[1] = false;
+    h->pl.reset();
     {
         int rc = graph_drop(h);
         if (rc) return rc;
@@ -703,7 +663,7 @@ int tts_set_option(tts_handle_t h, const char* key, int value) {
     else if (!std::strcmp(key, "persistent_decoder")) {
         // the decoder form decides whether a pipelined call runs its encoder ahead on `encs` (tts_synthesize: enc_ahead_cfg):
         // a call of the other form may still be using the one set of encoder workspaces and the `memory` buffer of its
-        // parity on `front`, which the encoder-ahead ordering (ev_dec_done of the call two back) does not cover
+        // parity on `front`, which the encoder-ahead ordering (dec_done of the call two back) does not cover
         if (value != h->persistent_decoder) {
             int rc = sync_all(h);
             if (rc) return rc;
@@ -752,9 +712,7 @@ int tts_set_option(tts_handle_t h, const char* key, int value) {
     } else if (!std::strcmp(key, "pipeline")) {
         int rc = sync_all(h);
         if (rc) return rc;
-        h->post_pending[0] = h->post_pending[1] = false;
-        h->gl_pending[0] = h->gl_pending[1] = false;
-        h->gl_wide_used[0] = h->gl_wide_used[1] = false;
+        h->pl.reset();
         h->pipeline = value;
     }
     else return fail(h, TTS_ERR_INVALID, std::string("unknown option ") + key);
@@ -1004,7 +962,7 @@ int tts_memcpy_h2d(tts_handle_t h, void* dst, const void* src, size_t bytes) {
 int tts_memcpy_d2h(tts_handle_t h, void* dst, const void* src, size_t bytes) {
     DeviceScope dev_scope(h);
     if (!h) return TTS_ERR_INVALID;
-    if (h->front) HIPCHK(h, hipStreamSynchronize(h->front));   // optional outputs of a pipelined synthesize
+    if (h->pl.front) HIPCHK(h, hipStreamSynchronize(h->pl.front));   // optional outputs of a pipelined synthesize
     HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // the bytes are host-visible from here on: a timed-out persistent kernel must not pass for a result

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -57,6 +58,164 @@ struct ProfSpan {
     int64_t launches;
 };
 
+// One ordering edge between streams (or a stream and the host): an event and whether something recorded in it still has to be
+// waited for.  Created at the first record -- never under a stream capture: nothing records a Signal inside one.
+struct Signal {
+    hipEvent_t ev = nullptr;
+    bool armed = false;
+    Signal() = default;
+    Signal(const Signal&) = delete;
+    Signal& operator=(const Signal&) = delete;
+    ~Signal() {
+        if (ev) hipEventDestroy(ev);
+    }
+    hipError_t record(hipStream_t s) {
+        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(ev, s);
+        if (e == hipSuccess) armed = true;
+        return e;
+    }
+    hipError_t wait(hipStream_t s) const { return armed ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }   // (a stream waits)
+    hipError_t sync() const { return armed ? hipEventSynchronize(ev) : hipSuccess; }                     // (the host waits)
+    void disarm() { armed = false; }   // what was recorded is known to be complete, or has been waited for by all it concerns
+};
+
+// A pinned host buffer and the device buffer it is copied to or from (tts_synthesize_host); sizes only increase.
+template <class T>
+struct StagedBuf {
+    T* pinned = nullptr;
+    T* dev = nullptr;
+    size_t bytes = 0;
+    StagedBuf() = default;
+    StagedBuf(const StagedBuf&) = delete;
+    StagedBuf& operator=(const StagedBuf&) = delete;
+    ~StagedBuf() { release(); }
+    hipError_t release() {
+        const hipError_t e1 = pinned ? hipHostFree(pinned) : hipSuccess;
+        const hipError_t e2 = dev ? hipFree(dev) : hipSuccess;
+        pinned = dev = nullptr;
+        bytes = 0;
+        return e1 != hipSuccess ? e1 : e2;
+    }
+    hipError_t grow(size_t need) {   // (the caller has synchronised everything that may still use the buffers)
+        if (need <= bytes) return hipSuccess;
+        hipError_t e = release();
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&pinned), need, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dev), need);
+        if (e == hipSuccess) bytes = need;
+        return e;
+    }
+};
+
+// What tts_synthesize hands to its encoder and decoder per call (encoder_impl / decoder_impl are enqueued on h->stream and take
+// everything else from here); default-constructed: a stand-alone call of a stage entry point.  Two instances per call:
+// tts_synthesize_host fills `upload` and `enc_done` only, tts_synthesize reads those and fills the rest for decoder_impl.
+struct StageArgs {
+    int* hold_flag = nullptr;        // the sleepers' flag: a persistent decoder releases the held compute units once resident
+    int cu_budget = 0;               // the compute units the front stream may count on (0 = the whole chip, not pipelined)
+    bool chip_idle = false;          // the main stream had nothing in flight when this call's decoder was enqueued
+    // Under the call pipeline the decoder's output projection (y history -> mel, one GEMM) is not issued behind the decoder
+    // on the front stream, where it gets the decoder's 32 compute units (0.3 ms), but at the head of the post-net on the
+    // main stream (0.03 ms); the y history is then a buffer per call parity.
+    bool project_later = false;
+    int parity = 0;
+    float* keys = nullptr;           // attention keys of the memory the decoder gets, already computed
+    // tts_synthesize_host: the ids' upload, enqueued on the encoder's stream in front of the encoder (behind the last record of
+    // `enc_done`, recorded in `done`), and a signal recorded behind the encoder
+    struct {
+        int32_t* dst = nullptr;
+        const int32_t* src = nullptr;
+        size_t bytes = 0;
+        Signal* done = nullptr;
+    } upload;
+    Signal* enc_done = nullptr;
+};
+
+// tts_synthesize pipelining: encoder + decoder (latency bound, few CUs) of call k+1 run on
+// `front` while post-net + Griffin-Lim (throughput bound) of call k run on the handle's `stream`.
+struct CallPipeline {
+    hipStream_t aux = nullptr;      // stream the sleepers run on
+    int* hold_flags = nullptr;      // two flag words, alternating per call
+    Signal aux_mark;                // the front and encoder streams start behind this point of the main / sleeper stream
+    unsigned call_count = 0;
+    // The front stream (encoder, decoder, explicit initial phases of the NEXT call beside this call's post-net and Griffin-Lim):
+    // greatest priority.  Measured alternatives for the calls of the persistent decoder (which keeps its CUs by being
+    // resident): lowest priority was 0.15 ms per step better while the main stream was the longer one and 0.1 ms worse once
+    // Griffin-Lim's run cut had given it slack; the main stream's own priority is as good as the greatest in a device-resident
+    // loop but HALVES the throughput of tts_synthesize_host -- streams of one priority share a few hardware queues, and with
+    // the copy streams of the host path the front stream lands on the main stream's queue.
+    hipStream_t front = nullptr;
+    // The encoder of a pipelined call runs on a stream of its own (round 4): it depends on the ids only, so it need not
+    // queue behind the previous call's decoder on the front stream -- it runs as soon as the decoder of the call TWO back
+    // has finished with this parity's `memory` buffer, i.e. one inter-Griffin-Lim gap earlier, and the decoders follow
+    // each other back to back (the step was enc + dec = 17.2 ms against 15.6 ms of post-net + Griffin-Lim).
+    hipStream_t encs = nullptr;
+    Signal enc_ready[2];   // encoder of the last call of this parity done (enc stream)
+    Signal dec_done[2];    // decoder of the last call of this parity done (front stream)
+    // ... and not before the main stream has reached the post-net of that call (the Griffin-Lim phase before it is over):
+    // an encoder let loose during a Griffin-Lim phase gets its compute units one launch boundary at a time (3 ms for 0.75 ms
+    // of work) and slows those launches by 15 %; in the gap it shares the chip with the post-net, as before
+    Signal gap[2];
+    Signal front_done;     // everything of the last pipelined call on the front stream
+    Signal post_done[2];   // post-net of the calls of even / odd parity
+    bool gl_wide_used[2] = {false, false};   // the Griffin-Lim phase of that parity's last call ends in launches on ALL compute units
+    Signal gl_done[2];     // Griffin-Lim of the calls of even / odd parity (its phase buffers are free)
+    // encoder + decoder of an UNPIPELINED call or of a stand-alone stage call (they ran on the main stream); disarmed once the
+    // front and encoder streams have waited for it
+    Signal serial_done;
+    unsigned syn_calls = 0;
+    int syn_shape[3] = {0, 0, 0};   // (B, Ts, n_steps) of the previous tts_synthesize call
+    int last_enc_ahead = -1;        // did the previous PIPELINED call run its encoder ahead on `encs` (1) or on `front` (0)?
+
+    // Every stream has been synchronised (sync_all): nothing recorded so far orders anything any more
+    void reset() {
+        for (Signal* s : {&aux_mark, &front_done, &serial_done}) s->disarm();
+        for (int i = 0; i < 2; ++i) {
+            for (Signal* s : {&enc_ready[i], &dec_done[i], &gap[i], &post_done[i], &gl_done[i]}) s->disarm();
+            gl_wide_used[i] = false;
+        }
+    }
+    void teardown() {   // (the handle is about to be deleted; the signals go with it)
+        for (hipStream_t s : {front, aux})
+            if (s) {
+                hipStreamSynchronize(s);
+                hipStreamDestroy(s);
+            }
+        if (hold_flags) hipFree(hold_flags);
+        if (encs) hipStreamDestroy(encs);
+    }
+};
+
+// host-memory calls (tts_synthesize_host): pinned staging of the ids, device copies, pinned waveform buffers and the
+// device buffers they are copied from, one set per call in flight (ticket mod 3: the device pipeline holds three calls
+// at once since round 4 -- encoder of k + 2, decoder of k + 1, Griffin-Lim of k); the ids go up on the stream that
+// runs the call's encoder, the outputs come down on one copy stream
+struct HostIo {
+    hipStream_t out = nullptr;
+    StagedBuf<int32_t> ids[3];
+    StagedBuf<float> wav[3];
+    Signal h2d[3];      // upload of the ids done
+    Signal enc[3];      // encoder done with the ids buffer
+    Signal ready[3];    // waveforms complete on the device
+    Signal d2h[3];      // waveforms have arrived in pinned memory
+    size_t n_floats[3] = {0, 0, 0};
+    // optional outputs of a host call (tts_synth_params_t::host_outputs): linear spectrograms and alignments
+    StagedBuf<float> lin[3], ali[3];
+    size_t n_lin[3] = {0, 0, 0}, n_ali[3] = {0, 0, 0};
+    bool failed[3] = {false, false, false};   // this set's call ended on a decoder timeout: EVERY wait on its ticket fails
+    int* status_pinned = nullptr;   // [3][2]: the persistent decoder's sticky status word ([.][1]) as it stood behind
+                                    // each call's download
+    int tickets = 0;
+
+    void reset() {   // everything has been synchronised: the sets are free
+        for (int i = 0; i < 3; ++i)
+            for (Signal* s : {&h2d[i], &enc[i], &ready[i], &d2h[i]}) s->disarm();
+    }
+    void teardown() {   // (the staging buffers and the signals go with the handle)
+        if (status_pinned) hipHostFree(status_pinned);
+        if (out) hipStreamDestroy(out);
+    }
+};
 
 }  // namespace tts_api
 using namespace tts_api;   // (the handle is a global type: include/sstts_hip.h declares tts_handle_s)
@@ -81,48 +240,11 @@ struct tts_handle_s {
     int fused_tail = 1;          // CBHG: lifter + highway stack + GRU input projections as one launch (cbhg_tail.hip)
     bool tail_configured = false;
     int profile = 0;
-    // tts_synthesize pipelining: encoder + decoder (latency bound, few CUs) of call k+1 run on
-    // `front` while post-net + Griffin-Lim (throughput bound) of call k run on `stream`.
     int pipeline = 1;      // on while the library owns its stream (see tts_synthesize); ~9 % on MI355X
     int reserve_cus = 32;  // CUs held for the front stream by LDS-hogging sleeper workgroups (reserve.hip)
     int hold_lds_kb = 64;  // LDS of one sleeper: > 80 KB guarantees one sleeper per CU
-    hipStream_t aux = nullptr;      // stream the sleepers run on
-    int* hold_flags = nullptr;      // two flag words, alternating per call
-    hipEvent_t ev_aux = nullptr;
-    unsigned call_count = 0;
-    // The front stream (encoder, decoder, explicit initial phases of the NEXT call beside this call's post-net and Griffin-Lim):
-    // greatest priority.  Measured alternatives for the calls of the persistent decoder (which keeps its CUs by being
-    // resident): lowest priority was 0.15 ms per step better while the main stream was the longer one and 0.1 ms worse once
-    // Griffin-Lim's run cut had given it slack; the main stream's own priority is as good as the greatest in a device-resident
-    // loop but HALVES the throughput of tts_synthesize_host -- streams of one priority share a few hardware queues, and with
-    // the copy streams of the host path the front stream lands on the main stream's queue.
-    hipStream_t front = nullptr;
-    // The encoder of a pipelined call runs on a stream of its own (round 4): it depends on the ids only, so it need not
-    // queue behind the previous call's decoder on the front stream -- it runs as soon as the decoder of the call TWO back
-    // has finished with this parity's `memory` buffer, i.e. one inter-Griffin-Lim gap earlier, and the decoders follow
-    // each other back to back (the step was enc + dec = 17.2 ms against 15.6 ms of post-net + Griffin-Lim).
-    hipStream_t encs = nullptr;
     int enc_stream = 1;   // option "enc_stream": 0 = the encoder on the front stream in front of its decoder (round 3)
-    hipEvent_t ev_enc_ready[2] = {nullptr, nullptr};   // encoder of the last call of this parity done (enc stream)
-    hipEvent_t ev_dec_done[2] = {nullptr, nullptr};    // decoder of the last call of this parity done (front stream)
-    // ... and not before the main stream has reached the post-net of that call (the Griffin-Lim phase before it is over):
-    // an encoder let loose during a Griffin-Lim phase gets its compute units one launch boundary at a time (3 ms for 0.75 ms
-    // of work) and slows those launches by 15 %; in the gap it shares the chip with the post-net, as before
-    hipEvent_t ev_gap[2] = {nullptr, nullptr};
-    bool enc_ready_pending[2] = {false, false}, dec_done_pending[2] = {false, false}, gap_pending[2] = {false, false};
-    hipEvent_t ev_front_done = nullptr;
-    hipEvent_t ev_post_done[2] = {nullptr, nullptr};   // post-net of the calls of even / odd parity
-    bool post_pending[2] = {false, false};
-    bool gl_wide_used[2] = {false, false};   // the Griffin-Lim phase of that parity's last call ends in launches on ALL compute units
-    hipEvent_t ev_gl_done[2] = {nullptr, nullptr};     // Griffin-Lim of the calls of even / odd parity (its phase buffers are free)
-    bool gl_pending[2] = {false, false};
-    bool front_pending = false;     // ev_front_done has been recorded at least once
-    hipEvent_t ev_serial_done = nullptr;   // encoder + decoder of an UNPIPELINED call (they ran on the main stream)
-    bool serial_pending = false;           // ... has been recorded since the front stream last waited for it
-    unsigned syn_calls = 0;
-    int syn_shape[3] = {0, 0, 0};   // (B, Ts, n_steps) of the previous tts_synthesize call
-    int last_enc_ahead = -1;        // did the previous PIPELINED call run its encoder ahead on `encs` (1) or on `front` (0)?
-    bool in_synthesize = false;     // the stage entry points are being called by tts_synthesize (which orders the streams itself)
+    CallPipeline pl;       // the streams, signals and per-parity state of the call pipeline
     // persistent decoder (decoder_ws.hip / decoder_persistent.hip): 0 never, 2 whenever a kernel covers the configuration,
     // 1 (default) where it was measured to be the faster choice: pd_choice() below has the rule and the numbers.
     int persistent_decoder = 1;
@@ -131,8 +253,8 @@ struct tts_handle_s {
     // budget, else decoder_persistent.hip (8 x 16, weights streamed from L2 every step); 0 = always the latter
     int pd_ws = 1;
     // (the decoder's output projection -- one GEMM over all steps -- runs on the MAIN stream in front of the post-net under the
-    //  call pipeline: `defer_projection`.  On the front stream behind its decoder it gave the same 14.45 ms per step in round 5;
-    //  the option that switched it is gone)
+    //  call pipeline: StageArgs::project_later.  On the front stream behind its decoder it gave the same 14.45 ms per step in
+    //  round 5; the option that switched it is gone)
     bool ws_configured = false;
     int gl_pair = 3;                 // Griffin-Lim iterations per launch (1..3) where nothing per-iteration is asked for
     // fast Griffin-Lim: the momentum alpha in thousandths, 0 (default: the reference's plain loop) .. 999; alpha > 0 runs one
@@ -156,62 +278,13 @@ struct tts_handle_s {
     unsigned gl_ring_seq = 0;
     unsigned* gl_ring_last = nullptr;  // slot of the most recent launch (dirty)
     hipStream_t gl_ring_stream = nullptr;
-    float* pre_keys = nullptr;   // attention keys of the memory the next tts_decoder_forward gets, already computed (tts_synthesize)
     bool pd_used = false;            // a persistent launch has been enqueued since the last status check
     unsigned* pd_sync = nullptr;     // counters + status word of the last persistent launch
     int pd_clusters = 0;
-    int* cur_hold_flag = nullptr;    // set by tts_synthesize around its decoder call: the sleepers' flag
-    int cur_cu_budget = 0;           // ... and the compute units the front stream may count on (0 = the whole chip)
-    bool dec_chip_idle = false;      // tts_synthesize: the main stream had nothing in flight when this call's decoder was enqueued
     int pd_rows = 0;                 // tests ("pd_rows" behind "debug_hooks"): utterances per cluster of the weight-stationary decoder, 16 / 32
     int pd_rows_used = 0;            // ... of the last launch
 
-    // host-memory calls (tts_synthesize_host): pinned staging of the ids, device copies, pinned waveform buffers and the
-    // device buffers they are copied from, one set per call in flight (ticket mod 3: the device pipeline holds three calls
-    // at once since round 4 -- encoder of k + 2, decoder of k + 1, Griffin-Lim of k); the ids go up on the stream that
-    // runs the call's encoder, the outputs come down on one copy stream
-    struct {
-        hipStream_t out = nullptr;
-        int32_t* ids_pinned[3] = {nullptr, nullptr, nullptr};
-        int32_t* ids_dev[3] = {nullptr, nullptr, nullptr};
-        size_t ids_bytes = 0;
-        float* wav_dev[3] = {nullptr, nullptr, nullptr};
-        float* wav_pinned[3] = {nullptr, nullptr, nullptr};
-        size_t wav_bytes = 0;
-        hipEvent_t ev_h2d[3] = {nullptr, nullptr, nullptr};      // upload of the ids done
-        hipEvent_t ev_enc[3] = {nullptr, nullptr, nullptr};      // encoder done with the ids buffer
-        hipEvent_t ev_ready[3] = {nullptr, nullptr, nullptr};    // waveforms complete on the device
-        hipEvent_t ev_d2h[3] = {nullptr, nullptr, nullptr};      // waveforms have arrived in pinned memory
-        bool d2h_pending[3] = {false, false, false}, enc_pending[3] = {false, false, false};
-        size_t n_floats[3] = {0, 0, 0};
-        // optional outputs of a host call (tts_synth_params_t::host_outputs): linear spectrograms and alignments
-        float* lin_dev[3] = {nullptr, nullptr, nullptr};
-        float* lin_pinned[3] = {nullptr, nullptr, nullptr};
-        size_t lin_bytes = 0;
-        float* ali_dev[3] = {nullptr, nullptr, nullptr};
-        float* ali_pinned[3] = {nullptr, nullptr, nullptr};
-        size_t ali_bytes = 0;
-        size_t n_lin[3] = {0, 0, 0}, n_ali[3] = {0, 0, 0};
-        bool failed[3] = {false, false, false};   // this set's call ended on a decoder timeout: EVERY wait on its ticket fails
-        int* status_pinned = nullptr;   // [3][2]: the persistent decoder's sticky status word ([.][1]) as it stood behind
-                                        // each call's download
-        int tickets = 0;
-    } hio;
-    // Under the call pipeline the decoder's output projection (y history -> mel, one GEMM) is not issued behind the decoder
-    // on the front stream, where it gets the decoder's 32 compute units (0.3 ms), but at the head of the post-net on the
-    // main stream (0.03 ms); the y history is then a buffer per call parity.
-    bool defer_projection = false, has_pending_proj = false;
-    int defer_parity = 0;
-    GemmGroup pending_proj;
-    // set around a tts_synthesize call (tts_synthesize_host): the ids' upload, enqueued on the encoder's stream in front of
-    // the encoder (behind `wait`, recorded in `done`), and an event recorded behind the encoder
-    struct {
-        int32_t* dst = nullptr;
-        const int32_t* src = nullptr;
-        size_t bytes = 0;
-        hipEvent_t wait = nullptr, done = nullptr;
-    } input_upload;
-    hipEvent_t enc_done_event = nullptr;
+    HostIo hio;   // tts_synthesize_host: staging buffers, copy stream and signals of the three calls in flight
 
     std::vector<ManifestEntry> manifest;
     std::map<std::string, std::vector<float>> host_w;
@@ -239,8 +312,7 @@ struct tts_handle_s {
     // A launch of dec_graph is complete: recorded behind every hipGraphLaunch, waited for by the HOST before the same
     // executable graph is launched again or destroyed (never two launches of one hipGraphExec_t in flight, never one
     // destroyed under a launch).
-    hipEvent_t ev_graph_done = nullptr;
-    bool graph_in_flight = false;
+    Signal graph_done;
     hipGraph_t dec_graph_src = nullptr;   // the captured graph the executable one was instantiated from: kept alive with it
     struct {   // everything the captured launches have baked in: shapes and EVERY pointer (decoder_impl)
         const void* memory = nullptr;
@@ -293,7 +365,7 @@ struct tts_handle_s {
         int* mel_band = nullptr;          // [n_mels][2] {first bin, first weight}, [n_mels] end bins follow
         void* staging = nullptr;          // pinned host buffer of the descriptor uploads
         size_t staging_bytes = 0;
-        hipEvent_t staged = nullptr;      // the last upload from `staging` has been read
+        Signal staged;                    // the last upload from `staging` has been read
     } feat;
 
     // profiling
@@ -359,15 +431,10 @@ struct ProfScope {
     }
 };
 
-struct SynthScope {   // tts_synthesize is running: the stage entry points leave the stream ordering to it
-    tts_handle_t h;
-    explicit SynthScope(tts_handle_t h_) : h(h_) { h->in_synthesize = true; }
-    ~SynthScope() { h->in_synthesize = false; }
-};
-
 // ---- defined in api_handle.hip / api_stages.hip / api_pipeline.hip
 int fail(tts_handle_t h, int code, const std::string& msg);
 void build_manifest(tts_handle_t h);
+int pd_timed_out(tts_handle_t h);   // the persistent decoder's timeout, reported in ONE wording (check_status, tts_wait_host)
 int check_status(tts_handle_t h);
 int sync_all(tts_handle_t h);
 int graph_quiesce(tts_handle_t h);
@@ -400,7 +467,7 @@ int pd_choice(tts_handle_t h, int B, int Ts, int budget, bool pipelined);
 int attention_keys(tts_handle_t h, const float* memory, int B, int Ts, float* keys);
 int teacher_choice(tts_handle_t h, int B, int Ts);
 int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments,
-                 const float* target = nullptr);
+                 const float* target = nullptr, const StageArgs& args = StageArgs(), std::optional<GemmGroup>* deferred = nullptr);
 int postnet_impl(tts_handle_t h, const float* mel, int B, int T, float* linear, float* mag, float ref_db, float max_db, float power, int* db_flag = nullptr);
 bool denorm_can_assert(float ref_db, float max_db);
 int denorm_flag_arm(tts_handle_t h, int** flag);

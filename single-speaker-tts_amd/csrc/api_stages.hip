@@ -152,13 +152,6 @@ int gl_tables(tts_handle_t h) {
 int device_cus(tts_handle_t h) { return h->gl.n_cus; }
 
 
-int gl_fp(int n_fft);
-
-int glg_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
-
-int glg_twiddles(tts_handle_t h, int n_fft, const float2** out);
-
-
 int stft_prepare(tts_handle_t h, int n, int win, int hop, int n_fft) {
     if (n_fft != TTS_GL_NFFT) return fail(h, TTS_ERR_UNSUPPORTED, "stft: n_fft != 2048 takes the general kernels (stft_run)");
     if (win < 2 || win > n_fft || hop < 1) return fail(h, TTS_ERR_INVALID, "stft: need 2 <= win_length <= n_fft, hop >= 1");
@@ -353,30 +346,14 @@ int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft) {
     if (g.wss) hipFree(g.wss);
     if (g.wlane) hipFree(g.wlane);
     g.window = g.wss = g.wlane = nullptr;
-    // periodic hann (scipy get_window('hann', win, fftbins=True)), float64 then float32
-    std::vector<double> wd(win);
-    std::vector<float> wf(win);
-    for (int i = 0; i < win; ++i) {
-        wd[i] = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / win);
-        wf[i] = (float)wd[i];
-    }
-    // librosa window_sumsquare: float32 buffer, sequential += of the padded squared window
-    const size_t n = (size_t)n_fft + (size_t)hop * (T - 1);
-    std::vector<float> wss(n, 0.f);
-    const int lpad = (n_fft - win) / 2;
-    for (int i = 0; i < T; ++i) {
-        const size_t s = (size_t)i * hop;
-        for (int j = 0; j < win; ++j) {
-            const size_t idx = s + lpad + j;
-            if (idx < n) wss[idx] = (float)((double)wss[idx] + wd[j] * wd[j]);
-        }
-    }
-    // the kernels multiply: 1 / wss where librosa's istft divides (wss > tiny(float32)), 1 elsewhere
-    for (size_t i = 0; i < n; ++i) wss[i] = wss[i] > 1.17549435e-38f ? (float)(1.0 / (double)wss[i]) : 1.0f;
+    std::vector<double> wd;
+    std::vector<float> wf, wss;
+    hann_window(win, wd, wf);
+    recip_window_sumsquare(wd, n_fft, hop, T, wss);   // (the kernels multiply where librosa's istft divides)
     HIPCHK(h, hipMalloc(&g.window, win * sizeof(float)));
-    HIPCHK(h, hipMalloc(&g.wss, n * sizeof(float)));
+    HIPCHK(h, hipMalloc(&g.wss, wss.size() * sizeof(float)));
     HIPCHK(h, hipMemcpy(g.window, wf.data(), win * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(g.wss, wss.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(g.wss, wss.data(), wss.size() * sizeof(float), hipMemcpyHostToDevice));
     {
         std::vector<float> wl(2 * 16 * 2 * 64);
         gl_build_wlane(wf.data(), wss.data(), win, hop, T, wl.data());
@@ -533,24 +510,21 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
 
 
 // ---------------------------------------------------------------------------------------- stages
-// A stage entry point called by the USER (not by tts_synthesize) runs on the main stream in the one set of enc.* / dec.*
-// workspaces that the pipelined calls use on the encoder and front streams: it starts behind whatever those streams still
-// hold, and the next pipelined call's encoder and decoder start behind it (ev_serial_done, as for an unpipelined
+// A stage entry point called by the USER (tts_synthesize orders the streams itself) runs on the main stream in the one set of
+// enc.* / dec.* workspaces that the pipelined calls use on the encoder and front streams: it starts behind whatever those
+// streams still hold, and the next pipelined call's encoder and decoder start behind it (serial_done, as for an unpipelined
 // tts_synthesize).  Stream order alone covers the post-net (main stream on both sides).
 int standalone_begin(tts_handle_t h) {
-    if (h->in_synthesize || !h->encs) return TTS_OK;
+    if (!h->pl.encs) return TTS_OK;
     for (int i = 0; i < 2; ++i) {
-        if (h->enc_ready_pending[i]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_enc_ready[i], 0));
-        if (h->dec_done_pending[i]) HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_dec_done[i], 0));
+        HIPCHK(h, h->pl.enc_ready[i].wait(h->stream));
+        HIPCHK(h, h->pl.dec_done[i].wait(h->stream));
     }
     return TTS_OK;
 }
 
 int standalone_end(tts_handle_t h) {
-    if (h->in_synthesize || !h->front) return TTS_OK;
-    if (!h->ev_serial_done) HIPCHK(h, hipEventCreateWithFlags(&h->ev_serial_done, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(h->ev_serial_done, h->stream));
-    h->serial_pending = true;
+    if (h->pl.front) HIPCHK(h, h->pl.serial_done.record(h->stream));
     return TTS_OK;
 }
 
@@ -623,7 +597,7 @@ int teacher_choice(tts_handle_t h, int B, int Ts) {
 }
 
 int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments,
-                 const float* target) {
+                 const float* target, const StageArgs& args, std::optional<GemmGroup>* deferred) {
     int rc = TTS_OK;
     const tts_config_t& c = h->cfg;
     if (h->dec.local_d > 0 && Ts < 2 * h->dec.local_d + 1)
@@ -635,20 +609,19 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
     const int NL = c.n_decoder_gru_layers;
     WS(h, "dec.keys", float, (size_t)B * Ts * A, keys_ws);
     // (the call pipeline computes the keys behind the encoder, on the encoder's stream, in a buffer of the call's parity)
-    float* keys = h->pre_keys ? h->pre_keys : keys_ws;
-    const bool have_keys = h->pre_keys != nullptr;
-    h->pre_keys = nullptr;
+    float* keys = args.keys ? args.keys : keys_ws;
+    const bool have_keys = args.keys != nullptr;
     const size_t state_floats = (size_t)B * (A + 2 * ((size_t)A + (size_t)NL * U));   // att | h_att, h_dec[] | their second copies
     WS(h, "dec.state", float, state_floats, state);
     WS(h, "dec.tmp", float, (size_t)B * (c.dec_prenet_units[0] + c.dec_prenet_units[1] + 6 * (size_t)U), tmp);
     WS(h, "dec.ctx_parts", float, (size_t)TTS_ATT_PARTS * B * mem, ctx_parts);
     WS(h, "dec.att_stats", float, (size_t)n_steps * B * TTS_ATT_PARTS * 2, att_stats);
     // (the launch-per-layer path replays a captured graph with its buffers baked in: one y history there)
-    const int pd_budget = h->cur_cu_budget > 0 ? h->cur_cu_budget : h->n_cus_dev;
-    const int pd_kernel = target ? teacher_choice(h, B, Ts) : pd_choice(h, B, Ts, pd_budget, h->cur_cu_budget > 0);
+    const int pd_budget = args.cu_budget > 0 ? args.cu_budget : h->n_cus_dev;
+    const int pd_kernel = target ? teacher_choice(h, B, Ts) : pd_choice(h, B, Ts, pd_budget, args.cu_budget > 0);
     const bool use_pd = pd_kernel != 0;
-    const bool defer_proj = h->defer_projection && use_pd && !target;
-    WS(h, defer_proj ? (h->defer_parity ? "dec.yhist.odd" : "dec.yhist.even") : "dec.yhist", float, (size_t)B * n_steps * U, yhist);
+    const bool defer_proj = args.project_later && deferred && use_pd && !target;
+    WS(h, defer_proj ? (args.parity ? "dec.yhist.odd" : "dec.yhist.even") : "dec.yhist", float, (size_t)B * n_steps * U, yhist);
     WS(h, "dec.align_raw", float, (size_t)n_steps * B * Ts, align_raw);
     DecoderScratch sc;
     std::memset(&sc, 0, sizeof(sc));
@@ -701,7 +674,7 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
         // The same bits either way (decoder_ws.hip), so the choice may look at the clock.
         int rows = 32;
         if (decoder_ws_workgroups(B, 16) <= pd_budget) rows = 16;
-        else if (h->cur_cu_budget > 0 && h->dec_chip_idle && decoder_ws_workgroups(B, 16) <= h->n_cus_dev) rows = 16;
+        else if (args.cu_budget > 0 && args.chip_idle && decoder_ws_workgroups(B, 16) <= h->n_cus_dev) rows = 16;
         if (h->debug_hooks && (h->pd_rows == 16 || h->pd_rows == 32) && decoder_ws_workgroups(B, h->pd_rows) <= h->n_cus_dev)
             rows = h->pd_rows;   // (tests: "pd_rows")
         const int clusters = decoder_ws_clusters(B, 16);   // layout of the sync words: that of the form with more clusters
@@ -716,7 +689,7 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
             xg = xg_ws;
         }
         HIPCHK(h, decoder_ws_enqueue(h->stream, h->dec, ws_scratch, yhist, memory, keys, B, Ts, n_steps, alignments, ws_sync,
-                                     h->cur_hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0, rows, clusters, sc.p_hist,
+                                     args.hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0, rows, clusters, sc.p_hist,
                                      sc.err_flag, xg));
         h->pd_rows_used = rows;
         h->pd_sync = ws_sync;
@@ -732,7 +705,7 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
         if (pd_sync != h->pd_sync || clusters != h->pd_clusters)   // new buffer / new layout: the sticky status word starts clean
             HIPCHK(h, hipMemsetAsync(pd_sync + 64 * clusters + 1, 0, sizeof(unsigned), h->stream));
         HIPCHK(h, decoder_persistent_enqueue(h->stream, h->dec, sc, memory, keys, B, Ts, n_steps, alignments, pd_sync,
-                                             h->cur_hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0));
+                                             args.hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0));
         h->pd_sync = pd_sync;
         h->pd_clusters = clusters;
         h->pd_used = true;
@@ -768,16 +741,13 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
         }
         if ((rc = graph_quiesce(h))) return rc;   // (never two launches of one executable graph in flight)
         HIPCHK(h, hipGraphLaunch(h->dec_graph, h->stream));
-        if (!h->ev_graph_done) HIPCHK(h, hipEventCreateWithFlags(&h->ev_graph_done, hipEventDisableTiming));
-        HIPCHK(h, hipEventRecord(h->ev_graph_done, h->stream));
-        h->graph_in_flight = true;
+        HIPCHK(h, h->graph_done.record(h->stream));   // (behind the launch, outside the capture)
     }
     // OutputProjectionWrapper for all steps at once: mel[b][t][:] = y[b][t] W_o + b_o
     {
         const GemmGroup proj = dense_group(yhist, U, h->dec.out_wt, h->dec.out_b, mel, OUT, B * n_steps, OUT, U, ACT_NONE);
         if (defer_proj) {
-            h->pending_proj = proj;
-            h->has_pending_proj = true;
+            *deferred = proj;   // (StageArgs::project_later: the caller issues it)
         } else if ((rc = run_single(h, proj))) {
             return rc;
         }
@@ -838,7 +808,8 @@ int postnet_impl(tts_handle_t h, const float* mel, int B, int T, float* linear, 
 // -100.  The lowest value inv_normalize_decibel can produce is ref - (|ref| + |max|) (clip(x) == 0): with the
 // reference's constants (6.02, 99.89) that is -93.87 dB, so the assertion cannot fire and nothing is checked.
 // Constants that allow it get the data-dependent check the reference makes: the de-normalising kernels raise
-// a device flag, which the caller reads back (one stream synchronisation, only in that configuration).
+// a device flag, which the caller reads back (one stream synchronisation, only in that configuration).  tts_db_convert's
+// dB-to-magnitude mode arms and reads the same flag around its own kernel, whatever the constants.
 bool denorm_can_assert(float ref_db, float max_db) {
     return ref_db - (std::fabs(ref_db) + std::fabs(max_db)) < -100.0f;
 }
@@ -1145,15 +1116,11 @@ int tts_db_convert(tts_handle_t h, const float* in, size_t n, int mode, float re
     if (n == 0) return TTS_OK;
     if (mode == 1) {
         // reference audio/conversion.py:47-49: AssertionError if any dB value < -100
-        if (!h->an.flag) HIPCHK(h, hipMalloc(&h->an.flag, sizeof(int)));
-        HIPCHK(h, hipMemsetAsync(h->an.flag, 0, sizeof(int), h->stream));
-        HIPCHK(h, launch_any_below(h->stream, in, n, -100.0f, h->an.flag));
-        int flag = 0;
-        HIPCHK(h, hipMemcpyAsync(&flag, h->an.flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (flag)
-            return fail(h, TTS_ERR_DB_RANGE,
-                        "\"conversion.decibel_to_magnitude\" was asked to convert a dB value smaller -100 dB.");
+        int* flag = nullptr;
+        int rc = denorm_flag_arm(h, &flag);
+        if (rc) return rc;
+        HIPCHK(h, launch_any_below(h->stream, in, n, -100.0f, flag));
+        if ((rc = denorm_flag_read(h))) return rc;
     }
     HIPCHK(h, launch_db_convert(h->stream, in, out, n, mode, ref_db, max_db));
     return TTS_OK;

@@ -298,8 +298,7 @@ bool pow2_in(int x, int lo, int hi) { return x >= lo && x <= hi && (x & (x - 1))
 // Descriptors go to the device through a pinned buffer of the handle; the previous upload from it must have been read first.
 int stage_upload(tts_handle_t h, const void* src, size_t bytes, void* dst) {
     auto& f = h->feat;
-    if (f.staged) HIPCHK(h, hipEventSynchronize(f.staged));
-    else HIPCHK(h, hipEventCreateWithFlags(&f.staged, hipEventDisableTiming));
+    HIPCHK(h, f.staged.sync());
     if (f.staging_bytes < bytes) {
         if (f.staging) HIPCHK(h, hipHostFree(f.staging));
         f.staging = nullptr;
@@ -309,7 +308,7 @@ int stage_upload(tts_handle_t h, const void* src, size_t bytes, void* dst) {
     }
     std::memcpy(f.staging, src, bytes);
     HIPCHK(h, hipMemcpyAsync(dst, f.staging, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(f.staged, h->stream));
+    HIPCHK(h, f.staged.record(h->stream));
     return TTS_OK;
 }
 
@@ -432,12 +431,8 @@ void feat_release(tts_handle_t h) {
     if (f.window) hipFree(f.window);
     if (f.mel_w) hipFree(f.mel_w);
     if (f.mel_band) hipFree(f.mel_band);
-    if (f.staged) {
-        hipEventSynchronize(f.staged);
-        hipEventDestroy(f.staged);
-    }
+    f.staged.sync();   // (tts_destroy only, in front of `delete h`: the pointers are not used again, the event goes with the handle)
     if (f.staging) hipHostFree(f.staging);
-    f = {};
 }
 }  // namespace tts_api
 

@@ -124,6 +124,40 @@ def test_local_short_memory_is_refused(hparams, weights, weights64, gaussian):
         eng.close()
 
 
+def test_local_short_memory_refused_by_pipelined_synthesize_leaves_the_handle_whole(hparams, weights):
+    """The refusal above inside a PIPELINED tts_synthesize: the second call of a shape has its encoder on another stream
+    already when the decoder refuses the memory.  Both calls fail, and the handle is as good as new afterwards: the same
+    calls on it and on a fresh handle give the same bits."""
+    D = 1
+    rng = np.random.default_rng(21)
+    short = rng.integers(2, 39, (2, 2 * D)).astype(np.int32)
+    ids = [rng.integers(2, 39, (2, 2 * D + 1)).astype(np.int32) for _ in range(2)]
+    kw = dict(n_steps=2, ref_db=6.02, max_db=99.89, power=1.3, n_iter=1, win_length=1102, hop_length=275, seed=5,
+              want_mel=True, want_alignments=True, want_linear=True)
+
+    def run(eng):
+        dev = [eng.to_device(x) for x in ids]           # uploaded up front: nothing synchronises between the two calls
+        outs = [eng.synthesize(d, **kw) for d in dev]
+        eng.synchronize()
+        return [{k: v.to_host() for k, v in o.items()} for o in outs]
+
+    _, eng = _setup(hparams, weights, D, True)
+    _, fresh = _setup(hparams, weights, D, True)
+    try:
+        dev_short = eng.to_device(short)
+        for _ in range(2):                               # (the second one is the pipelined call)
+            with pytest.raises(pkg('_hip').TtsError) as ei:
+                eng.synthesize(dev_short, **kw)
+            assert ei.value.code == -5
+        got, want = run(eng), run(fresh)
+        for g, w in zip(got, want):
+            for k in ('wav', 'mel', 'alignments', 'linear'):
+                assert np.isfinite(w[k]).all() and np.array_equal(g[k], w[k]), k
+    finally:
+        eng.close()
+        fresh.close()
+
+
 def test_local_end_to_end_synthesize(hparams, weights, weights64):
     """tts_synthesize with the local mechanism: spectrograms against the oracle."""
     hp, eng = _setup(hparams, weights, 10, True)

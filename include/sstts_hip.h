@@ -47,27 +47,38 @@ enum tts_status {
 /* Architecture hyper-parameters; field names and defaults follow the reference's
  * model_params (tacotron/params/model.py:8-153).  ALWAYS start from tts_default_config: it fills the defaults and
  * `struct_size`, and tts_create refuses a struct whose size is not the library's (a caller built against another version of
- * this header, or a zero-initialised struct) instead of reading past its end or taking zeros for settings. */
+ * this header, or a zero-initialised struct) instead of reading past its end or taking zeros for settings.
+ *
+ * Accepted range of every field (anything else: TTS_ERR_UNSUPPORTED / TTS_ERR_INVALID from tts_create, before the device is
+ * touched; the message names the limit).  Common to all counts and widths: at most 2^20; and every weight matrix a GEMM
+ * loader reads -- the embedding table, the pre-nets, a bank convolution, a projection, the output projection -- holds at
+ * most 2^30 - 5 floats (32-bit byte offsets).  tests/test_gpu_architectures.py runs the network against the float64 oracle
+ * at architectures that move every one of these fields (tests/arch_cases.py).
+ * Decoder form: the persistent kernels (option "persistent_decoder") cover 2 decoder GRU layers, dec_prenet_units
+ * {256, 128} and n_mels <= 256 (the streamed-weights kernel also needs n_mels % 16 == 0, which tts_create demands anyway);
+ * every other accepted architecture takes one launch per layer, whatever the option says.  CBHG tail: the fused launch
+ * (option "fused_tail") covers an input of at most 128 channels (enc_prenet_units[1], n_mels) and at most 8 highway layers;
+ * wider or deeper ones run layer by layer, with the same result to rounding. */
 typedef struct tts_config {
     int32_t struct_size;         /* sizeof(tts_config_t) of the header the caller was built with (set by tts_default_config) */
-    int32_t vocabulary_size;     /* 39  */
-    int32_t embedding_size;      /* 256 */
-    int32_t enc_prenet_units[2]; /* 256, 128 */
-    int32_t enc_n_banks;         /* 16  */
-    int32_t enc_n_filters;       /* 128 */
-    int32_t enc_proj_filters[2]; /* 128, 128 (kernel size 3; relu, linear) */
-    int32_t post_n_banks;        /* 8   */
-    int32_t post_n_filters;      /* 128 */
-    int32_t post_proj_filters[2];/* 256, 80 */
-    int32_t n_highway_layers;    /* 4   */
-    int32_t n_highway_units;     /* 128 */
-    int32_t n_gru_units;         /* 128 (CBHG bi-GRU, both encoder and post-net) */
-    int32_t dec_prenet_units[2]; /* 256, 128 */
-    int32_t n_attention_units;   /* 256 */
-    int32_t n_decoder_gru_units; /* 256 */
-    int32_t n_decoder_gru_layers;/* 2   */
-    int32_t n_mels;              /* 80  */
-    int32_t reduction;           /* 5   */
+    int32_t vocabulary_size;     /* 39: >= 1 */
+    int32_t embedding_size;      /* 256: a multiple of 16 */
+    int32_t enc_prenet_units[2]; /* 256, 128: multiples of 16 */
+    int32_t enc_n_banks;         /* 16: >= 1 (more than 16 banks: several launches) */
+    int32_t enc_n_filters;       /* 128: a multiple of 32 */
+    int32_t enc_proj_filters[2]; /* 128, 128 (kernel size 3; relu, linear): [0] a multiple of 4, [1] == enc_prenet_units[1] (residual) */
+    int32_t post_n_banks;        /* 8: >= 1 */
+    int32_t post_n_filters;      /* 128: a multiple of 32 */
+    int32_t post_proj_filters[2];/* 256, 80: [0] a multiple of 4, [1] == n_mels (residual) */
+    int32_t n_highway_layers;    /* 4: >= 0 */
+    int32_t n_highway_units;     /* 128, nothing else */
+    int32_t n_gru_units;         /* 128, nothing else (CBHG bi-GRU, both encoder and post-net) */
+    int32_t dec_prenet_units[2]; /* 256, 128: multiples of 16 */
+    int32_t n_attention_units;   /* 256, nothing else */
+    int32_t n_decoder_gru_units; /* 256, nothing else */
+    int32_t n_decoder_gru_layers;/* 2: 1 .. 4 */
+    int32_t n_mels;              /* 80: a multiple of 16, at most 1024 (the GO frame is read from a block of 1024 zeros) */
+    int32_t reduction;           /* 5: >= 1 (256 x n_mels x reduction within the weight limit) */
     int32_t n_fft;               /* 2048 */
     int32_t force_cudnn;         /* 0: tf GRUCell (TF-CPU parity target); 1: CudnnCompatibleGRUCell */
     /* model_params.attention (tacotron/params/model.py:112-128).  The local mechanism is the reference's

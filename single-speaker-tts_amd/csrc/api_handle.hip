@@ -563,6 +563,44 @@ int tts_create(const tts_config_t* cfg, int device_id, tts_handle_t* out) {
         return fail(nullptr, TTS_ERR_INVALID, "luong_local_mode must be TTS_LOCAL_MONOTONIC or TTS_LOCAL_PREDICTIVE");
     if (c.enc_n_banks < 1 || c.post_n_banks < 1 || c.reduction < 1 || c.vocabulary_size < 1 || c.n_highway_layers < 0)
         return fail(nullptr, TTS_ERR_INVALID, "bad counts");
+    // upper bounds: what the fixed-size buffers and the 32-bit operand offsets of the kernels hold (include/sstts_hip.h, tts_config_t)
+    if (c.n_mels > TTS_MAX_N_MELS)
+        return fail(nullptr, TTS_ERR_UNSUPPORTED,
+                    "n_mels is " + std::to_string(c.n_mels) + ", at most " + std::to_string(TTS_MAX_N_MELS) +
+                    " supported (the decoder's GO frame is read from a block of that many zeros)");
+    {
+        const int fields[] = {c.vocabulary_size, c.embedding_size, c.enc_prenet_units[0], c.enc_prenet_units[1], c.enc_n_banks,
+                              c.enc_n_filters, c.enc_proj_filters[0], c.enc_proj_filters[1], c.post_n_banks, c.post_n_filters,
+                              c.post_proj_filters[0], c.post_proj_filters[1], c.dec_prenet_units[0], c.dec_prenet_units[1],
+                              c.reduction, c.n_highway_layers};
+        for (int v : fields)
+            if (v > TTS_MAX_FIELD)
+                return fail(nullptr, TTS_ERR_UNSUPPORTED, "a count or layer width of " + std::to_string(v) + ": at most " +
+                                                              std::to_string(TTS_MAX_FIELD) + " (2^20) supported");
+        // (every field is at most 2^20 from here on: the products below fit 64 bits)
+        struct { const char* what; long long n; } mats[] = {
+            {"the embedding table (vocabulary_size x embedding_size)", (long long)c.vocabulary_size * c.embedding_size},
+            {"encoder pre-net layer 1", (long long)c.embedding_size * c.enc_prenet_units[0]},
+            {"encoder pre-net layer 2", (long long)c.enc_prenet_units[0] * c.enc_prenet_units[1]},
+            {"the widest encoder bank convolution (enc_n_banks x enc_prenet_units[1] x enc_n_filters)",
+             (long long)c.enc_n_banks * c.enc_prenet_units[1] * c.enc_n_filters},
+            {"encoder projection 1 (3 x enc_n_banks x enc_n_filters x enc_proj_filters[0])",
+             3ll * c.enc_n_banks * c.enc_n_filters * c.enc_proj_filters[0]},
+            {"encoder projection 2", 3ll * c.enc_proj_filters[0] * c.enc_proj_filters[1]},
+            {"the widest post-net bank convolution (post_n_banks x n_mels x post_n_filters)",
+             c.apply_post_processing ? (long long)c.post_n_banks * c.n_mels * c.post_n_filters : 0},
+            {"post-net projection 1 (3 x post_n_banks x post_n_filters x post_proj_filters[0])",
+             c.apply_post_processing ? 3ll * c.post_n_banks * c.post_n_filters * c.post_proj_filters[0] : 0},
+            {"post-net projection 2", c.apply_post_processing ? 3ll * c.post_proj_filters[0] * c.post_proj_filters[1] : 0},
+            {"the output projection (n_decoder_gru_units x n_mels x reduction)",
+             (long long)c.n_decoder_gru_units * c.n_mels * c.reduction}};
+        for (const auto& m : mats)
+            if (m.n > TTS_MAX_WEIGHT_FLOATS)
+                return fail(nullptr, TTS_ERR_UNSUPPORTED,
+                            std::string(m.what) + " has " + std::to_string(m.n) + " weights, at most " +
+                            std::to_string(TTS_MAX_WEIGHT_FLOATS) + " (2^30 - 5) supported: the GEMM loaders address an operand "
+                            "with 32-bit byte offsets");
+    }
     if (hipSetDevice(device_id) != hipSuccess) return fail(nullptr, TTS_ERR_HIP, "hipSetDevice failed");
     auto h = new tts_handle_s();
     h->cfg = c;
@@ -851,7 +889,7 @@ int tts_finalize_weights(tts_handle_t h) {
     const int F = 1 + c.n_fft / 2;
     const size_t o_dw = pack_transposed(p, W(h, "dense/kernel").data(), c.apply_post_processing ? mem : c.n_mels, F);
     const size_t o_db = pack_copy(p, W(h, "dense/bias").data(), F);
-    const size_t o_zero = p.alloc(1024);
+    const size_t o_zero = p.alloc(TTS_MAX_N_MELS);   // >= n_mels (tts_create) and >= n_attention_units zeros
     // the decoder's weights once more, in the register order of the weight-stationary persistent kernel (decoder_ws.hip):
     // TF GRUCell form, the default layer sizes (decoder_ws_supports checks the rest per call)
     size_t o_wsw = 0, o_wsb = 0;

@@ -21,6 +21,11 @@ namespace tts_api {
 using namespace tts;
 
 
+// Upper bounds of tts_config_t that tts_create holds (include/sstts_hip.h documents them per field)
+constexpr int TTS_MAX_N_MELS = 1024;                          // floats of the arena's zero block: the decoder's GO frame is read from it
+constexpr int TTS_MAX_FIELD = 1 << 20;                        // any count or width: products of three fields fit 64 bits
+constexpr long long TTS_MAX_WEIGHT_FLOATS = (1ll << 30) - 5;  // launch_gemm (gemm_f32.hip): 4 N K < 0xFFFFFFF0 bytes per operand
+
 extern thread_local std::string g_create_error;   // tts_create failures (no handle to keep the message in)
 
 struct ManifestEntry {
@@ -302,7 +307,7 @@ struct tts_handle_s {
     DecoderWeights dec;
     const float* dense_wt = nullptr;
     const float* dense_b = nullptr;
-    const float* zeros = nullptr;   // 1024 zero floats inside the arena
+    const float* zeros = nullptr;   // TTS_MAX_N_MELS zero floats inside the arena
 
     // workspace (grow-only)
     std::map<std::string, DevBuf> ws;

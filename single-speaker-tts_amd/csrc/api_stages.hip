@@ -867,7 +867,9 @@ int tts_decoder_forward_teacher(tts_handle_t h, const float* memory, int B, int 
     if (!memory || !mel_target || !mel || B < 1 || Ts < 1 || n_steps < 1)
         return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: bad arguments");
     if ((uintptr_t)mel_target & 15) return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: mel_target must be 16-byte aligned");
-    if ((long long)n_steps * h->cfg.reduction > (1 << 24)) return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: sizes out of range");
+    // (the target's row stride n_steps * r * n_mels is a 32-bit operand of the decoder GEMM: decoder.hip, DecGemm::lda0)
+    if ((long long)n_steps * h->cfg.reduction > (1 << 24) || (long long)n_steps * h->cfg.reduction * h->cfg.n_mels > 0x7FFFFFFFll)
+        return fail(h, TTS_ERR_INVALID, "decoder_forward_teacher: sizes out of range");
     if ((rc = standalone_begin(h))) return rc;
     if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel, alignments, mel_target))) return rc;
     return standalone_end(h);
@@ -943,7 +945,8 @@ int tts_teacher_forced(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_
                                         "target; B, Ts, n_steps >= 1)");
     const tts_config_t& c = h->cfg;
     const int T = n_steps * c.reduction, F = 1 + c.n_fft / 2;
-    if ((long long)n_steps * c.reduction > (1 << 24) || (double)B * T * F >= 9.0e18)
+    if ((long long)n_steps * c.reduction > (1 << 24) || (double)B * T * F >= 9.0e18 ||
+        (long long)n_steps * c.reduction * c.n_mels > 0x7FFFFFFFll)   // (the target's row stride: tts_decoder_forward_teacher)
         return fail(h, TTS_ERR_INVALID, "teacher_forced: sizes out of range");
     for (const void* p : {(const void*)linear_target, (const void*)mel, (const void*)linear, (const void*)losses})
         if ((uintptr_t)p & 3) return fail(h, TTS_ERR_INVALID, "teacher_forced: float buffers must be 4-byte aligned");

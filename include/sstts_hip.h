@@ -271,6 +271,18 @@ int tts_denorm_power(tts_handle_t h, const float* linear, int B, int T, int F,
 int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, uint64_t seed,
                     int B, int T, int n_iter, int win_length, int hop_length, int n_fft,
                     float* wav, float* mse);
+/* tts_griffin_lim for utterances of different lengths in one padded batch.  mag, init_phase: [B][F][T_max] as tts_griffin_lim
+ * takes them; n_frames: HOST int32 [B], 1 <= n_frames[b] <= T_max with hop (n_frames[b] - 1) > n_fft / 2 for every b
+ * (TTS_ERR_INVALID otherwise, naming the utterance, before anything is enqueued).  Columns t >= n_frames[b] of mag and
+ * init_phase are never read.  wav [B][hop (T_max - 1)]: samples [0, hop (n_frames[b] - 1)) are
+ * the reconstruction of utterance b alone -- the bits of tts_griffin_lim(B = 1, T = n_frames[b]) on its columns with the same
+ * handle options, in the streaming and in the general kernels -- and the rest of its row is written as 0.  mse [B] or NULL: mean
+ * over F x n_frames[b] (with "gl_momentum" and in the general kernels the bits of that single call, otherwise equal to rounding:
+ * the plain streaming form sums per run).  init_phase == NULL draws bin (b, f, t) as tts_griffin_lim(B, T_max, seed) does.
+ * n_frames[b] == T_max for every b gives the bits of tts_griffin_lim.  No model needs to be loaded. */
+int tts_griffin_lim_ragged(tts_handle_t h, const float* mag, const float* init_phase, uint64_t seed, int B, int T_max,
+                           const int32_t* n_frames, int n_iter, int win_length, int hop_length, int n_fft,
+                           float* wav, float* mse);
 /* librosa.output.write_wav(norm=True) scaling (audio/io.py:53): wav /= max|wav| per
  * utterance unless the peak is below FLT_MIN.  In place, wav [B*n].  NaN samples stay NaN and do not take part in the peak
  * search (numpy's max would make the whole utterance NaN): the finite samples of that utterance are scaled by the peak of
@@ -408,6 +420,9 @@ int tts_debug_workspace(tts_handle_t h, const char* name, void** dptr, size_t* b
  * items[n][4] = {utterance, first frame, frames, slot word} in the order the workgroups draw them (at most max_items
  * are written); *ring_frames = frames the LDS ring of the kernel holds; returns the number of items. */
 int tts_debug_gl_plan(int T, int B, int win_length, int hop_length, int n_workers, int* items, int max_items, int* ring_frames);
+/* host only, as tts_debug_gl_plan: the cut of a ragged batch (n_frames[b] frames in utterance b; no run leaves its utterance) */
+int tts_debug_gl_plan_ragged(const int32_t* n_frames, int B, int win_length, int hop_length, int n_workers,
+                             int* items, int max_items, int* ring_frames);
 /* Diagnostic: one GEMM / conv1d launch on device buffers (A [M][Cin] rows of sequences of length T, Wt [N][ktaps*Cin]). */
 int tts_debug_gemm(tts_handle_t h, const float* A, const float* Wt, float* C, int M, int N, int Cin, int ktaps, int T,
                    int pool);

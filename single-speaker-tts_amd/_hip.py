@@ -100,6 +100,8 @@ _PROTOTYPES = {
     'tts_denorm_power': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p]),
     'tts_griffin_lim': (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_int, c_int, c_int, c_int,
                                 c_int, c_void_p, c_void_p]),
+    'tts_griffin_lim_ragged': (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_int, POINTER(c_int32), c_int, c_int,
+                                       c_int, c_int, c_void_p, c_void_p]),
     'tts_peak_normalize': (c_int, [c_void_p, c_void_p, c_int, c_int]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
@@ -123,6 +125,7 @@ _PROTOTYPES = {
     'tts_debug_hold': (c_int, [c_void_p, c_int, c_int, ctypes.c_double]),
     'tts_debug_gemm': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     'tts_debug_gl_plan': (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int)]),
+    'tts_debug_gl_plan_ragged': (c_int, [POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int)]),
     'tts_device_info': (c_int, [c_void_p, c_char_p, POINTER(c_int)]),
 }
 
@@ -200,6 +203,21 @@ class DeviceArray(object):
 
 def _is_device(x):
     return hasattr(x, 'data_ptr') and not isinstance(x, np.ndarray)
+
+
+def ragged_frame_counts(n_frames, B, T_max, hop_length, n_fft):
+    """The ``n_frames`` argument of a ragged Griffin-Lim call as a contiguous int32 array of B lengths, checked as
+    tts_griffin_lim_ragged checks them (ValueError, raised before a handle is touched): 1 <= n_frames[b] <= T_max and a
+    signal longer than the reflect padding, hop (n_frames[b] - 1) > n_fft / 2."""
+    nf = np.ascontiguousarray(np.asarray(n_frames).reshape(-1), dtype=np.int32)
+    if nf.shape[0] != B:
+        raise ValueError('n_frames: {} lengths for a batch of {}'.format(nf.shape[0], B))
+    for b, n in enumerate(nf.tolist()):
+        if not 1 <= n <= T_max:
+            raise ValueError('n_frames[{}] = {} is not in 1 .. T_max = {}'.format(b, n, T_max))
+        if hop_length * (n - 1) <= n_fft // 2:
+            raise ValueError('n_frames[{}] = {}: the signal is shorter than n_fft / 2 (reflect padding undefined)'.format(b, n))
+    return nf
 
 
 def momentum_thousandths(momentum):
@@ -511,15 +529,26 @@ class Engine(object):
         self._check(self.lib.tts_denorm_power(self.handle, p_lin, B, T, F, ref_db, max_db, power, mag.data_ptr()))
         return mag
 
-    def griffin_lim(self, mag, n_iter, win_length, hop_length, n_fft, init_phase=None, seed=0, want_mse=True, momentum=None):
+    def griffin_lim(self, mag, n_iter, win_length, hop_length, n_fft, init_phase=None, seed=0, want_mse=True, momentum=None,
+                    n_frames=None):
         """``momentum``: the fast Griffin-Lim momentum in [0, 1) for this call (librosa's and torchaudio's ``momentum``;
-        0 = the reference's plain loop); None: the handle's ``gl_momentum`` option as it stands."""
+        0 = the reference's plain loop); None: the handle's ``gl_momentum`` option as it stands.
+        ``n_frames``: B frame counts -- a ragged batch (tts_griffin_lim_ragged): ``mag`` and ``init_phase`` are padded to
+        (B, F, T_max), utterance b is reconstructed from its first n_frames[b] columns alone (the padding never reaches a
+        result), row b of ``wav`` holds its hop (n_frames[b] - 1) samples followed by zeros and ``mse[b]`` is its own."""
         scope = _MomentumScope(self, momentum)
         B, F, T = mag.shape
+        nf = ragged_frame_counts(n_frames, B, T, hop_length, n_fft) if n_frames is not None else None
         p_mag, _k1 = self._in(mag, np.float32)
         p_init, _k2 = self._in(init_phase, np.float32)
         wav = self.empty((B, hop_length * (T - 1)))
         mse = self.empty((B,)) if want_mse else None
+        if nf is not None:
+            with scope:
+                self._check(self.lib.tts_griffin_lim_ragged(self.handle, p_mag, p_init, seed, B, T, nf.ctypes.data_as(POINTER(c_int32)),
+                                                            n_iter, win_length, hop_length, n_fft, wav.data_ptr(),
+                                                            mse.data_ptr() if mse is not None else None))
+            return wav, mse
         with scope:
             self._check(self.lib.tts_griffin_lim(self.handle, p_mag, p_init, seed, B, T, n_iter, win_length, hop_length,
                                                  n_fft, wav.data_ptr(), mse.data_ptr() if mse is not None else None))

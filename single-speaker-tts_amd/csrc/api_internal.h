@@ -350,6 +350,16 @@ struct tts_handle_s {
         bool configured = false;
     } glg;
 
+    // ragged Griffin-Lim (tts_griffin_lim_ragged): what the last call uploaded -- the lengths with the window sum-square
+    // tables made for them, and the run table of the streaming kernel -- kept while the next call asks for the same
+    struct {
+        std::vector<int> tab_key, plan_key;
+        int* lens = nullptr;       // [B] device (workspace "gl.rag_lens")
+        float* rw = nullptr;       // streaming [B][2][rw_E], general [B][n_fft + hop (T_max - 1)] (workspace "gl.rag_rw")
+        int4* items = nullptr;     // workspace "gl.rag_items"
+        int n_items = 0, slots = 1, workers = 1;
+    } rag;
+
     // analysis-side tables (STFT window, mel basis)
     struct {
         int win = 0;
@@ -461,9 +471,10 @@ int gl_fp(int n_fft);
 bool gl_is_streaming(int n_fft, int win, int hop);
 int glg_twiddles(tts_handle_t h, int n_fft, const float2** out);
 int glg_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
-int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize);
+// a ragged batch: host lengths [B] (T is then T_max); null everywhere = one length
+int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames = nullptr);
 int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
-int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1);
+int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);
 int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memory);

@@ -282,14 +282,117 @@ int glg_prepare(tts_handle_t h, int T, int win, int hop, int n_fft) {
 }
 
 
+// ---- ragged batches (tts_griffin_lim_ragged): per-utterance tables
+// The first and the last E entries of recip_window_sumsquare(T) without making the n_fft + hop (T - 1) between them: entry i is a
+// float32 sum, in frame order, over the frames that cover sample i, so the first E do not see frames from K on and the last E,
+// counted from the end, are those of any signal of K frames or more (the same addends in the same order).  out[2 E]: [head | tail];
+// a signal shorter than E has both halves start at its entry 0.
+static void gl_rwss_edges(const std::vector<double>& wd, int n_fft, int hop, int T, int E, float* out) {
+    const int win = (int)wd.size(), halo = (win + hop - 1) / hop - 1, lpad = (n_fft - win) / 2;
+    const int K = halo + (lpad + win + hop - 1) / hop + 3;
+    std::vector<float> r;
+    recip_window_sumsquare(wd, n_fft, hop, std::min(T, K), r);
+    const size_t m = std::min((size_t)E, r.size());
+    std::fill(out, out + 2 * (size_t)E, 0.f);
+    std::copy(r.begin(), r.begin() + m, out);
+    std::copy(r.end() - m, r.end(), out + E);
+}
+
+// Uploads the lengths and the window sum-square tables of a ragged batch (h->rag.lens / rw) unless the last call's are the same.
+// streaming: [B][2][E] edge tables; general kernels: a whole row of n_fft + hop (T_max - 1) per utterance, made for its length.
+static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_max, int win, int hop, int n_fft, bool streaming) {
+    const int E = gl_rw_edge_len(n_fft, win, hop);
+    const size_t row = streaming ? 2 * (size_t)E : (size_t)n_fft + (size_t)hop * (T_max - 1);
+    WS(h, "gl.rag_lens", int, (size_t)B, d_lens);
+    WS(h, "gl.rag_rw", float, (size_t)B * row, d_rw);
+    std::vector<int> key = {streaming ? 1 : 0, n_fft, win, hop, T_max, B};
+    key.insert(key.end(), n_frames, n_frames + B);
+    auto& r = h->rag;
+    if (r.lens == d_lens && r.rw == d_rw && r.tab_key == key) return TTS_OK;
+    std::vector<double> wd;
+    std::vector<float> wf;
+    hann_window(win, wd, wf);
+    std::vector<float> host((size_t)B * row, 0.f);
+    std::map<int, int> first_with;   // length -> the first utterance that has it (its row is copied)
+    for (int b = 0; b < B; ++b) {
+        float* dst = host.data() + (size_t)b * row;
+        auto it = first_with.find(n_frames[b]);
+        if (it != first_with.end()) {
+            std::copy(host.data() + (size_t)it->second * row, host.data() + (size_t)(it->second + 1) * row, dst);
+            continue;
+        }
+        first_with[n_frames[b]] = b;
+        if (streaming) {
+            gl_rwss_edges(wd, n_fft, hop, n_frames[b], E, dst);
+        } else {
+            std::vector<float> full;
+            recip_window_sumsquare(wd, n_fft, hop, n_frames[b], full);
+            std::copy(full.begin(), full.end(), dst);
+        }
+    }
+    r.tab_key.clear();
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (an earlier call may still read the tables)
+    HIPCHK(h, hipMemcpy(d_lens, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(d_rw, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    r.lens = d_lens; r.rw = d_rw; r.tab_key = key;
+    return TTS_OK;
+}
+
+// The cut of a ragged batch for the streaming kernel: made per call and kept in the handle while the lengths stay (the process-wide
+// cache of gl_plan_stream never frees a table: right for the handful of shapes a server runs, not for a dataset's worth of length
+// vectors).  Sets what gl_plan_stream sets.
+static int gl_rag_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len) {
+    std::vector<int> key = {p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len};
+    key.insert(key.end(), n_frames, n_frames + p.B);
+    auto& r = h->rag;
+    p.ring_frames = gl_stream_ring_frames(p.win, p.hop, 1);
+    std::vector<int4> items;
+    if (r.plan_key != key) {
+        gl_plan_items_ragged(n_frames, p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len, &items, &r.slots, &r.workers);
+        r.n_items = (int)items.size();
+        r.plan_key.clear();
+        r.items = nullptr;
+    }
+    WS(h, "gl.rag_items", int4, (size_t)r.n_items, d_items);
+    if (r.items != d_items) {
+        if (items.empty())   // (the workspace moved under a plan that is still the right one)
+            gl_plan_items_ragged(n_frames, p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len, &items, &r.slots, &r.workers);
+        r.plan_key.clear();
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(d_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice));
+        r.items = d_items;
+        r.plan_key = key;
+    }
+    p.items = r.items;
+    p.n_items = r.n_items;
+    p.slots_per_utt = r.slots;
+    p.n_workers = r.workers;
+    return TTS_OK;
+}
+
+static bool gl_rag_all_full(const int32_t* n_frames, int B, int T) {
+    for (int b = 0; b < B; ++b) if (n_frames[b] != T) return false;
+    return true;
+}
+
+
 // mag_int: [B][T][Fp] (Fp = gl_fp(n_fft)); init_ft: reference-layout U[0,1) numbers or null (then the seed)
 int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win,
-                   int hop, int n_fft, float* wav, float* mse, bool peak_normalize) {
+                   int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames) {
     if (T < 1) return fail(h, TTS_ERR_INVALID, "griffin_lim: T >= 1");
     if ((long long)hop * (T - 1) <= n_fft / 2)
         return fail(h, TTS_ERR_INVALID, "griffin_lim: signal shorter than n_fft/2 (reflect padding undefined)");
     int rc = glg_prepare(h, T, win, hop, n_fft);
     if (rc) return rc;
+    // a ragged batch: the kernels take the lengths and a row of 1 / window sum-square per utterance (made for its length)
+    const int* d_lens = nullptr;
+    const float* rwss = h->glg.rwss;
+    if (n_frames) {
+        if (peak_normalize) return fail(h, TTS_ERR_INVALID, "griffin_lim: no peak normalisation of a ragged batch");
+        if ((rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, false))) return rc;
+        d_lens = h->rag.lens;
+        rwss = h->rag.rw;
+    }
     const float2* tw = nullptr;
     if ((rc = glg_twiddles(h, n_fft, &tw))) return rc;
     const int F = 1 + n_fft / 2, Fp = gl_fp(n_fft), L = hop * (T - 1);
@@ -304,23 +407,24 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
         mom_c = mc;
     }
     float* sig = wav;   // every iteration's signal estimate lives in the caller's buffer: the last one is the result
-    HIPCHK(h, launch_glg_phase_init(h->stream, init_ft, seed, ph, B, F, T, Fp));
+    HIPCHK(h, launch_glg_phase_init(h->stream, init_ft, seed, ph, B, F, T, Fp, d_lens));
     {
         ProfScope ps(h, ST_GL_ITER, 3 * (int64_t)n_iter);
         for (int it = 0; it < n_iter; ++it) {
-            HIPCHK(h, launch_glg_istft(h->stream, mag_int, ph, h->glg.window, h->glg.rwss, tw, frames, sig, B, T, Fp, n_fft, win, hop));
+            HIPCHK(h, launch_glg_istft(h->stream, mag_int, ph, h->glg.window, rwss, tw, frames, sig, B, T, Fp, n_fft, win, hop, d_lens));
             const bool want_mse = mse && it == n_iter - 1;
             HIPCHK(h, launch_glg_stft(h->stream, sig, L, h->glg.window, tw, ph, B, T, Fp, n_fft, win, hop, 0, mag_int,
-                                      want_mse ? msep : nullptr, mom_c, alpha, it == 0));
+                                      want_mse ? msep : nullptr, mom_c, alpha, it == 0, d_lens));
         }
     }
     if (mse) {
-        if (n_iter > 0) HIPCHK(h, launch_gl_mse_reduce(h->stream, msep, B, T, (float)((double)F * T), mse));
+        if (n_iter > 0 && d_lens) HIPCHK(h, launch_gl_mse_reduce_ragged(h->stream, msep, B, T, F, d_lens, 1, mse));
+        else if (n_iter > 0) HIPCHK(h, launch_gl_mse_reduce(h->stream, msep, B, T, (float)((double)F * T), mse));
         else HIPCHK(h, hipMemsetAsync(mse, 0, B * sizeof(float), h->stream));
     }
     {
         ProfScope ps(h, ST_GL_FINAL, 2);
-        HIPCHK(h, launch_glg_istft(h->stream, mag_int, ph, h->glg.window, h->glg.rwss, tw, frames, wav, B, T, Fp, n_fft, win, hop));
+        HIPCHK(h, launch_glg_istft(h->stream, mag_int, ph, h->glg.window, rwss, tw, frames, wav, B, T, Fp, n_fft, win, hop, d_lens));
     }
     if (peak_normalize) HIPCHK(h, launch_peak_normalize(h->stream, wav, B, L));
     return TTS_OK;
@@ -373,9 +477,15 @@ int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft) {
 int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter,
            int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize,
            bool under_reservation, float2* const* phase_pair, bool phase_ready,
-           int wide_from) {
+           int wide_from, const int32_t* n_frames) {
     int rc = gl_prepare(h, T, win, hop, n_fft);
     if (rc) return rc;
+    // a ragged batch (T is T_max): the lengths and every utterance's own window sum-square ends, on the device
+    if (n_frames) {
+        if (peak_normalize || under_reservation || phase_pair)
+            return fail(h, TTS_ERR_INVALID, "griffin_lim: a ragged batch is a stand-alone call without peak normalisation");
+        if ((rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, true))) return rc;
+    }
     const int F = 1 + n_fft / 2, FP = TTS_GL_FP;
     float2 *ph0, *ph1;
     if (phase_pair) {
@@ -397,6 +507,11 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     p.T = T; p.FP = FP; p.win = win; p.hop = hop;
     p.ncol = (win + hop - 1) / hop;
     p.B = B;
+    if (n_frames) {   // (launch_gl_stream then takes the RAG instantiations)
+        p.n_frames = h->rag.lens;
+        p.rw_edge = h->rag.rw;
+        p.rw_E = gl_rw_edge_len(n_fft, win, hop);
+    }
     if (gl_stream_ring_frames(win, hop) < 1)
         return fail(h, TTS_ERR_UNSUPPORTED, "griffin_lim: this window / hop pair does not fit the LDS ring (hop beyond the window's 128-sample slots, or too long)");
     const int n_cus = (h->debug_hooks && h->gl_workers >= 16 && h->gl_workers <= device_cus(h)) ? h->gl_workers : device_cus(h);   // (tools: "gl_workers")
@@ -418,6 +533,9 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     }
     // (the cut decides who does which frames, never the waveform's bits: every sample is summed over the frames that cover it in
     //  ascending order whatever run they lie in -- tests/test_gpu_audio.py::test_griffin_lim_bits_do_not_depend_on_the_cut)
+    if (n_frames) {
+        if ((rc = gl_rag_plan(h, p, n_frames, n_cus, per_launch, h->debug_hooks ? h->gl_runs : 0, h->debug_hooks ? h->gl_run_len : 0))) return rc;
+    } else
     HIPCHK(h, gl_plan_stream(p, n_cus - held > 16 ? n_cus - held : n_cus, per_launch, h->debug_hooks ? h->gl_runs : 0,
                              h->debug_hooks ? h->gl_run_len : 0, h->stream));
     // wide_from >= 0 (the pipelined tts_synthesize, see gl_wide_from there): launches from that index on are cut for ALL
@@ -448,7 +566,7 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     };
     // a seeded start with at least one iteration needs no codes: the first launch makes the initial phasors itself
     const bool seed_in_kernel = !init_ft && n_iter >= 1;
-    if (!phase_ready && !seed_in_kernel) HIPCHK(h, launch_phase_init(h->stream, init_ft, seed, ph0, B, F, T, FP));
+    if (!phase_ready && !seed_in_kernel) HIPCHK(h, launch_phase_init(h->stream, init_ft, seed, ph0, B, F, T, FP, p.n_frames));
     p.F = pw.F = F;
     p.seed = pw.seed = seed;
     int launch_idx = 0, mse_chunks = p.slots_per_utt, peak_chunks = p.slots_per_utt;
@@ -482,7 +600,9 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
         }
     }
     if (mse) {
-        if (n_iter > 0) {
+        if (n_iter > 0 && n_frames) {
+            HIPCHK(h, launch_gl_mse_reduce_ragged(h->stream, msep, B, mse_chunks, F, p.n_frames, p.mom_c ? 1 : 0, mse));
+        } else if (n_iter > 0) {
             HIPCHK(h, launch_gl_mse_reduce(h->stream, msep, B, mse_chunks, (float)((double)F * T), mse));
         } else {
             HIPCHK(h, hipMemsetAsync(mse, 0, B * sizeof(float), h->stream));
@@ -498,6 +618,8 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
         q.mse_partial = nullptr;
         q.wav = wav;
         q.peak_partial = peak_normalize ? msep : nullptr;   // the mse partials are consumed by now
+        // a ragged batch: what lies behind an utterance's end in its row is 0 (one fill; the launch writes the signals over it)
+        if (n_frames && !gl_rag_all_full(n_frames, B, T)) HIPCHK(h, hipMemsetAsync(wav, 0, (size_t)B * hop * (T - 1) * sizeof(float), h->stream));
         next_counter(q);
         HIPCHK(h, launch_gl_stream(h->stream, q, wide ? n_cus : free_cus, 1, 1));
         peak_chunks = q.slots_per_utt;
@@ -1036,6 +1158,36 @@ int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, u
 }
 
 
+// tts_griffin_lim for utterances of different lengths in one padded batch (include/sstts_hip.h)
+int tts_griffin_lim_ragged(tts_handle_t h, const float* mag, const float* init_phase, uint64_t seed, int B, int T_max,
+                           const int32_t* n_frames, int n_iter, int win_length, int hop_length, int n_fft, float* wav, float* mse) {
+    DeviceScope dev_scope(h);
+    if (!h || !mag || !wav || !n_frames || B < 1 || n_iter < 0) return fail(h, TTS_ERR_INVALID, "griffin_lim_ragged: bad arguments");
+    const bool streaming = gl_is_streaming(n_fft, win_length, hop_length);
+    if (!streaming && !glg_supports(n_fft)) return fail(h, TTS_ERR_UNSUPPORTED, "griffin_lim: n_fft must be a power of two between 256 and 4096");
+    if (T_max < 1 || win_length < 2 || win_length > n_fft || hop_length < 1)
+        return fail(h, TTS_ERR_INVALID, "griffin_lim: need 2 <= win_length <= n_fft, hop_length >= 1, T >= 1");
+    // every length is checked before anything is enqueued
+    for (int b = 0; b < B; ++b) {
+        if (n_frames[b] < 1 || n_frames[b] > T_max)
+            return fail(h, TTS_ERR_INVALID, "griffin_lim_ragged: n_frames[" + std::to_string(b) + "] = " + std::to_string(n_frames[b]) +
+                                                " is not in 1 .. T_max = " + std::to_string(T_max));
+        if ((long long)hop_length * (n_frames[b] - 1) <= n_fft / 2)
+            return fail(h, TTS_ERR_INVALID, "griffin_lim_ragged: utterance " + std::to_string(b) + " (" + std::to_string(n_frames[b]) +
+                                                " frames): signal shorter than n_fft/2 (reflect padding undefined)");
+    }
+    // the lengths go to the device first: the transpose, too, stops at n_frames[b] (no padding column is read by any kernel)
+    const int F = 1 + n_fft / 2, Fp = streaming ? TTS_GL_FP : gl_fp(n_fft);
+    int rc = streaming ? gl_prepare(h, T_max, win_length, hop_length, n_fft) : TTS_OK;
+    if (rc) return rc;
+    if ((rc = gl_rag_tables(h, n_frames, B, T_max, win_length, hop_length, n_fft, streaming))) return rc;
+    WS(h, "gl.mag", float, (size_t)B * T_max * Fp, magi);
+    HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magi, B, F, T_max, Fp, h->rag.lens));
+    if (!streaming) return gl_run_generic(h, magi, init_phase, seed, B, T_max, n_iter, win_length, hop_length, n_fft, wav, mse, false, n_frames);
+    return gl_run(h, magi, init_phase, seed, B, T_max, n_iter, win_length, hop_length, n_fft, wav, mse, false, false, nullptr, false, -1, n_frames);
+}
+
+
 int tts_peak_normalize(tts_handle_t h, float* wav, int B, int n) {
     DeviceScope dev_scope(h);
     if (!h || !wav || B < 1 || n < 1) return fail(h, TTS_ERR_INVALID, "peak_normalize: bad arguments");
@@ -1143,6 +1295,31 @@ int tts_debug_gl_plan(int T, int B, int win_length, int hop_length, int n_worker
     std::vector<int4> v;
     int slots = 0;
     const int n = gl_plan_items(T, B, win_length, hop_length, n_workers, n_stage, 0, 0, &v, &slots);
+    if (ring_frames) *ring_frames = ring;
+    for (int k = 0; k < n && k < max_items; ++k) {
+        items[4 * k] = v[k].x; items[4 * k + 1] = v[k].y; items[4 * k + 2] = v[k].z; items[4 * k + 3] = v[k].w;
+    }
+    return n;
+}
+
+
+// The same for a ragged batch (tts_griffin_lim_ragged): n_frames[b] frames in utterance b.
+int tts_debug_gl_plan_ragged(const int32_t* n_frames, int B, int win_length, int hop_length, int n_workers, int* items, int max_items,
+                             int* ring_frames) {
+    if (!n_frames || B < 1 || win_length < 2 || win_length > TTS_GL_NFFT || hop_length < 1 || n_workers < 1 || !items || max_items < 0)
+        return TTS_ERR_INVALID;
+    int T_max = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n_frames[b] < 1) return TTS_ERR_INVALID;
+        T_max = std::max(T_max, (int)n_frames[b]);
+    }
+    const int ring = gl_stream_ring_frames(win_length, hop_length);
+    if ((win_length + hop_length - 1) / hop_length > 8 || ring < 1) return TTS_ERR_UNSUPPORTED;
+    int n_stage = 3;   // the handle's default launch form (option "gl_pair")
+    while (n_stage > 1 && gl_stream_ring_frames(win_length, hop_length, n_stage) <= 0) --n_stage;
+    std::vector<int4> v;
+    int slots = 0;
+    const int n = gl_plan_items_ragged(n_frames, T_max, B, win_length, hop_length, n_workers, n_stage, 0, 0, &v, &slots);
     if (ring_frames) *ring_frames = ring;
     for (int k = 0; k < n && k < max_items; ++k) {
         items[4 * k] = v[k].x; items[4 * k + 1] = v[k].y; items[4 * k + 2] = v[k].z; items[4 * k + 3] = v[k].w;

@@ -45,7 +45,17 @@ struct GlParams {
     float2* mom_c;
     float mom_alpha;
     int mom_first;
+    // ragged batch (gl_stream_kernel RAG): frames of every utterance, [B] in device memory; T above is then T_max, the stride
+    // of every buffer (mag, codes, mom_c, the seeded index, wav rows of hop (T_max - 1)).  rw_edge [B][2][rw_E]: 1 / window
+    // sum-square of utterance b's OWN length where it is not the interior image -- its first rw_E entries and its last rw_E
+    // (gl_rwss_edges).  Null = one length, T, for all.
+    const int* n_frames;
+    const float* rw_edge;
+    int rw_E;
 };
+
+// entries per end of an utterance in GlParams::rw_edge: every sample an edge frame's window reaches
+inline int gl_rw_edge_len(int n_fft, int win, int hop) { return n_fft + ((win + hop - 1) / hop - 1) * hop; }
 
 // out[2*16*2*64]: set 0 = window[n] / n_fft, set 1 = set 0 * rwss at an interior frame; n = 2*(lane + 64 c) + e
 void gl_build_wlane(const float* window, const float* rwss, int win, int hop, int T, float* out);
@@ -59,13 +69,20 @@ hipError_t gl_plan_stream(GlParams& p, int n_workers, int n_stage = 1, int force
 // the same cut on the host alone (no device): items[n][4] = {utterance, first frame, frames, slot word}; returns n
 int gl_plan_items(int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
                   std::vector<int4>* items, int* slots_per_utt, int* workers_out = nullptr);
+// the cut of a ragged batch: lens[b] frames in utterance b (null: T for all, the call above); no run leaves its utterance
+int gl_plan_items_ragged(const int* lens, int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
+                         std::vector<int4>* items, int* slots_per_utt, int* workers_out = nullptr);
 hipError_t launch_gl_stream(hipStream_t s, const GlParams& p, int n_cus, int final_istft, int n_stage = 1);
 hipError_t gl_configure();
 size_t gl_state_bytes();   // bytes per bin of the state between launches (4: a phasor code)
 hipError_t launch_gl_mse_reduce(hipStream_t s, const float* partial, int B, int nchunks, float denom, float* mse);
-hipError_t launch_mag_ft_to_tf(hipStream_t s, const float* in, float* out, int B, int F, int T, int FP);
+// ragged: mse[b] = sum / (F n_frames[b]); per_frame: the partials are one per frame (the first n_frames[b] of a row of nchunks are summed)
+hipError_t launch_gl_mse_reduce_ragged(hipStream_t s, const float* partial, int B, int nchunks, int F, const int* n_frames, int per_frame,
+                                       float* mse);
+// n_frames (device, [B]) != null in the two launchers that take it: a ragged batch -- columns t >= n_frames[b] are not touched
+hipError_t launch_mag_ft_to_tf(hipStream_t s, const float* in, float* out, int B, int F, int T, int FP, const int* n_frames = nullptr);
 hipError_t launch_tf_to_ft(hipStream_t s, const float* in, float* out, int B, int F, int T, int FP);
-hipError_t launch_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, void* out, int B, int F, int T, int FP);
+hipError_t launch_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, void* out, int B, int F, int T, int FP, const int* n_frames = nullptr);
 hipError_t launch_denorm_power(hipStream_t s, const float* lin, float* mag, size_t rows, int F, int FP,
                                float ref_db, float max_db, float power, int* below_flag);
 hipError_t launch_peak_normalize(hipStream_t s, float* wav, int B, int n);
@@ -81,16 +98,18 @@ hipError_t launch_any_below(hipStream_t s, const float* in, size_t n, float lim,
 // float2 unit phasors; tw = exp(-2 pi i k / n_fft), k < n_fft / 2
 bool glg_supports(int n_fft);   // power of two, 256 .. 4096
 hipError_t glg_configure();
-hipError_t launch_glg_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, float2* out, int B, int F, int T, int Fp);
+hipError_t launch_glg_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, float2* out, int B, int F, int T, int Fp, const int* n_frames = nullptr);
 // frames [B][T][win] scratch; wav [B][hop (T - 1)]: inverse transform of every frame, then the overlap-add (a gather in frame order)
+// n_frames != null (device, [B]): a ragged batch -- T is T_max (the stride of every buffer), the workgroups of frames t >= n_frames[b]
+// exit, utterance b's signal has hop (n_frames[b] - 1) samples and rwss is [B][n_fft + hop (T - 1)], a row per utterance's own length
 hipError_t launch_glg_istft(hipStream_t s, const float* mag, const float2* ph, const float* window, const float* rwss, const float2* tw,
-                            float* frames, float* wav, int B, int T, int Fp, int n_fft, int win, int hop);
+                            float* frames, float* wav, int B, int T, int Fp, int n_fft, int win, int hop, const int* n_frames = nullptr);
 // mode 0: out = unit phasors of the spectrum (+ per-frame squared magnitude error against mag when mse_partial != null);
 // mode 1: out = the complex spectrum
 // mom_c != null (mode 0): the momentum form -- the phasors are those of t = c + alpha (c - previous c), the spectrum c is read
 // from and rewritten to mom_c [B][Tf][Fp] (mom_first: t = c, nothing read)
 hipError_t launch_glg_stft(hipStream_t s, const float* wav, int n, const float* window, const float2* tw, float2* out, int B, int Tf, int Fp,
                            int n_fft, int win, int hop, int mode, const float* mag, float* mse_partial, float2* mom_c = nullptr,
-                           float mom_alpha = 0.f, int mom_first = 0);
+                           float mom_alpha = 0.f, int mom_first = 0, const int* n_frames = nullptr);
 
 }  // namespace tts

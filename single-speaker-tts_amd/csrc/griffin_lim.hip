@@ -215,7 +215,14 @@ enum { CT_OLA = 0, CT_SNEXT = 1, CT_OLB = 2 /* chain words of stages 1, 2 */, CT
 // reads what another writes and the cut does not reach the bits.  Fused stages would need stage k's c of a frame `lag`
 // indices later in another wave: 8.2 KB per frame, a dozen frames per stage -- more than the rings leave of the LDS
 // ("Fast Griffin-Lim").  The first iteration of a call (p.mom_first) has no c_prev: t = c, nothing is read.
-template <int MODE, int WIN_CT, int HOP_CT, bool MSE, int NST = 1, bool SEEDED = false, bool MOM = false>
+// RAG: a ragged batch (tts_griffin_lim_ragged).  The frames of a run's utterance, Tb = p.n_frames[b], are loaded with the item
+// (wave-uniform: a scalar) and take the place of p.T wherever the END of the utterance matters -- the row clamps, the interior
+// test of the synthesis window, the signal length L of the reflect padding, `valid` / `emit` -- while p.T = T_max stays the
+// stride of every buffer, so rows t >= Tb are never read.  1 / window sum-square at an utterance's ends comes from its own
+// table (p.rw_edge); the interior image in registers does not depend on the length.  An instantiation of its own, as SEEDED
+// and MOM are: with RAG = false Tb and L are the constants they were and the code is what it was ("Ragged
+// Griffin-Lim", has the resource table).
+template <int MODE, int WIN_CT, int HOP_CT, bool MSE, int NST = 1, bool SEEDED = false, bool MOM = false, bool RAG = false>
 __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     static_assert(!SEEDED || MODE == 0, "the seeded start is an iteration's");
     static_assert(!MOM || (MODE == 0 && NST == 1), "momentum: one iteration per launch");
@@ -244,7 +251,15 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     const int R = p.ring_frames;
     const int ring_len = hop * R;
     const int ring_floats = (ring_len + acc_len + 128 + 3) & ~3;
-    const int L = hop * (p.T - 1);                     // samples of the (trimmed) signal
+    const int L = hop * (p.T - 1);                     // samples of the (trimmed) signal; RAG: of a row of p.wav
+    // RAG: frames and samples of the run's utterance, set per run (below); GL_TB / GL_L are p.T and L otherwise, the very
+    // expressions the uniform kernel has always had
+    int Tb_r = p.T;
+    int L_r = L;
+    const float* rw_head = nullptr;                    // RAG: 1 / window sum-square of the utterance's first / last rw_E samples,
+    const float* rw_tail = nullptr;                    //      both based so that the padded sample index addresses them
+#define GL_TB (RAG ? Tb_r : p.T)
+#define GL_L (RAG ? L_r : L)
     // carve: [exchange: GL_NW * EX_CPLX cf][control][ring A: ring_len + acc_len + 128 floats][ring B]
     cf* ex_all = reinterpret_cast<cf*>(smem_raw);
     int* ctrl = reinterpret_cast<int*>(ex_all + GL_NW * EX_CPLX);
@@ -295,9 +310,10 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     int item = __builtin_amdgcn_readfirstlane(ctrl[CT_SNEXT]);
 
     // ---------------- work item -> (utterance, first frame, frames, slot of its partial results); wave-uniform
-    auto decode_item = [&](int it, int& b, int& t0, int& len, int& slot) {
+    auto decode_item = [&](int it, int& b, int& t0, int& len, int& slot, int& tb) {
         const int4 q = p.items[it];   // (wave-uniform index: a scalar load)
         b = q.x; t0 = q.y; len = q.z; slot = q.w;
+        if (RAG) tb = p.n_frames[q.x];   // (a scalar load as well)
     };
 
     // prefetch registers of one spectrum row in the pair-owner layout: phasor codes and magnitudes of bins lane + 64 j
@@ -307,10 +323,10 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     gl_state_t nyq_c;
     float nyq_s;
     constexpr bool seeded = SEEDED;
-#define GLS_LOAD_ROW(BASE_C, BASE_M, TF)                                                        \
+#define GLS_LOAD_ROW(BASE_C, BASE_M, TF, TB)                                                    \
     {                                                                                           \
         int tf_ = (TF);                                                                         \
-        tf_ = tf_ < 0 ? 0 : (tf_ >= p.T ? p.T - 1 : tf_);                                       \
+        tf_ = tf_ < 0 ? 0 : (tf_ >= (TB) ? (TB) - 1 : tf_);                                     \
         const gl_state_t* prow_ = (BASE_C) + (size_t)tf_ * p.FP;                                \
         const float* srow_ = (BASE_M) + (size_t)tf_ * p.FP;                                     \
         const gl_state_t* plo_ = prow_ + lane; const gl_state_t* phi_ = prow_ + (MH - lane);    \
@@ -378,12 +394,12 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     };
     // z[m] = conj(v) / MH, m = lane + 64 c: x[2m] = Re, x[2m+1] = Im; synthesis window (with 1 / window-sum-square)
     auto synth_window = [&](int t, cf (&v)[16]) __attribute__((always_inline)) {
-        if (t >= halo && t + halo < p.T) {
+        if (t >= halo && t + halo < GL_TB) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) v[c] = v[c] * cmk(wsyn[c][0], wsyn[c][1]);   // (wsyn[c][1] carries the conjugation's sign)
         } else {
             // frame near an utterance end: fewer overlapping neighbours, 1 / wss per sample (rare)
-            const float* rwp = p.rwss + (size_t)t * hop + wpad;
+            const float* rwp = (RAG ? (t < halo ? rw_head : rw_tail) : p.rwss) + (size_t)t * hop + wpad;
 #pragma unroll
             for (int c0 = 0; c0 < 16; c0 += 4) {
 #pragma unroll
@@ -471,7 +487,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
             asm volatile("" ::: "memory");
             const int q_fin = wpad - fs;
             const int y0 = t * hop + fs - MH;
-            const bool emit = (t >= run_t0 || run_t0 == 0) && (t < run_t0 + run_len || run_t0 + run_len == p.T);
+            const bool emit = (t >= run_t0 || run_t0 == 0) && (t < run_t0 + run_len || run_t0 + run_len == GL_TB);
             float* wb = p.wav + (size_t)b * L;
 #pragma unroll
             for (int c = 0; c < 16; ++c) {
@@ -482,8 +498,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                     const int q = qb + 2 * lane;
                     const int y = y0 + q;
                     const cf a = fin[c];
-                    if (emit && q >= q_fin && q < q_fin + hop && y >= 0 && y < L) { wb[y] = a.x; pk = fmaxf(pk, fabsf(a.x)); }
-                    if (emit && q + 1 >= q_fin && q + 1 < q_fin + hop && y + 1 >= 0 && y + 1 < L) { wb[y + 1] = a.y; pk = fmaxf(pk, fabsf(a.y)); }
+                    if (emit && q >= q_fin && q < q_fin + hop && y >= 0 && y < GL_L) { wb[y] = a.x; pk = fmaxf(pk, fabsf(a.x)); }
+                    if (emit && q + 1 >= q_fin && q + 1 < q_fin + hop && y + 1 >= 0 && y + 1 < GL_L) { wb[y + 1] = a.y; pk = fmaxf(pk, fabsf(a.y)); }
                 }
             }
         }
@@ -492,7 +508,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     // the iteration of index idx of its stage (y_base: trimmed-signal index of that stage's ring coordinate 0)
     auto fft_input = [&](const float* ring, int idx, int sm, int tm, int y_base, cf (&v)[16]) __attribute__((always_inline)) {
         const int ylo = tm * hop + wpad - MH;                    // y index of window sample 0
-        const bool edge = ylo < 0 || ylo + win > L;              // reflect padding needed
+        const bool edge = ylo < 0 || ylo + win > GL_L;              // reflect padding needed
         // The span is read linearly when it does not cross the end of the lap, or when the next lap's fold (index
         // m + R - sm) has not happened yet: what it will fold is still in the guard, behind the ring.
         if (!edge && (hop * sm + S <= ring_len || R - sm > lag)) {
@@ -528,7 +544,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                     if (nw >= 0 && nw < win) {
                         int y = ylo + nw;
                         y = y < 0 ? -y : y;
-                        y = y >= L ? 2 * (L - 1) - y : y;
+                        y = y >= GL_L ? 2 * (GL_L - 1) - y : y;
                         int off = y - ub, lap = lap0;
                         if (off >= ring_len) { off -= ring_len; ++lap; }
                         else if (off < 0) { off += ring_len; --lap; }
@@ -567,7 +583,15 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     bool have_row = false;   // (per wave) the first row of this run was requested in the last iteration of the previous one
     while (item < p.n_items) {
         int b, run_t0, run_len, slot;
-        decode_item(item, b, run_t0, run_len, slot);
+        decode_item(item, b, run_t0, run_len, slot, Tb_r);
+        if (RAG) {
+            L_r = hop * (Tb_r - 1);
+            // the utterance's table: [first rw_E entries | last rw_E entries] of 1 / window sum-square at ITS length (whose
+            // n_fft + L entries are fewer than rw_E where it has `halo` frames or less: both halves then start at entry 0)
+            const int cut = NFFT + L_r - p.rw_E;
+            rw_head = p.rw_edge + (size_t)b * 2 * p.rw_E;
+            rw_tail = rw_head + p.rw_E - (cut > 0 ? cut : 0);
+        }
         const float* magb = p.mag + (size_t)b * p.T * p.FP;
         const gl_state_t* phb = x_in + (size_t)b * p.T * p.FP;
         // The next item is drawn LATE in a run (by the wave of index n_idx - 24, read by every wave in its last iteration):
@@ -579,7 +603,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         const int i_res = n_idx - 3 * GL_NW;
         unsigned next_item_reg = GL_NO_ITEM;
         if (tid == 0 && !late) next_item_reg = atomicAdd(p.work_counter, 1u);
-        if (!have_row) GLS_LOAD_ROW(phb, magb, run_t0 - lead + wave)
+        if (!have_row) GLS_LOAD_ROW(phb, magb, run_t0 - lead + wave, GL_TB)
         have_row = false;
         // run start: the guards read as zero for index 0, the chains start at 0
         for (int q = tid; q < acc_len + 128; q += GL_THREADS) {
@@ -589,8 +613,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         if (tid == 0) { ctrl[CT_OLA] = 0; ctrl[CT_OLB] = 0; ctrl[CT_OLB + 1] = 0; ctrl[CT_SNEXT] = (int)next_item_reg; }
         __syncthreads();
         int next_item = __builtin_amdgcn_readfirstlane(ctrl[CT_SNEXT]);   // (late: GL_NO_ITEM until the wave's last iteration)
-        int nb = b, nt0 = 0, nlen = 0, nslot = 0;
-        if (!late && next_item < p.n_items) decode_item(next_item, nb, nt0, nlen, nslot);
+        int nb = b, nt0 = 0, nlen = 0, nslot = 0, nTb = p.T;
+        if (!late && next_item < p.n_items) decode_item(next_item, nb, nt0, nlen, nslot, nTb);
 
         // the LAST stage (the only one of NST == 1) has the indices of one iteration, j <-> frame run_t0 - halo + j; every
         // stage before it runs halo + lag indices ahead of the next: stage 0 index i <-> frame run_t0 - NST halo + i
@@ -601,7 +625,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         GLS_TOUCH_ROW()
         for (int i = wave; i < n_idx; i += GL_NW) {
             const int t = run_t0 - lead + i;
-            const bool valid = t >= 0 && t < p.T;             // wave-uniform
+            const bool valid = t >= 0 && t < GL_TB;           // wave-uniform
             unsigned drawn = 0;
             if (late && i == i_res && lane == 0) drawn = atomicAdd(p.work_counter, 1u);   // (consumed before this index's overlap-add)
             if (late && i + GL_NW >= n_idx) {
@@ -610,7 +634,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                 int nv;
                 while ((nv = gl_flag_load(ctrl + CT_SNEXT)) == (int)GL_NO_ITEM) __builtin_amdgcn_s_sleep(1);
                 next_item = __builtin_amdgcn_readfirstlane(nv);
-                if (next_item < p.n_items) decode_item(next_item, nb, nt0, nlen, nslot);
+                if (next_item < p.n_items) decode_item(next_item, nb, nt0, nlen, nslot, nTb);
             }
             GLS_URGENCY(i)
             cf v[16];
@@ -642,9 +666,9 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
             // stage, each requested where its stage starts (below)
 #define GLS_NEXT_ROW()                                                                                                   \
             if (i + GL_NW < n_idx) {                                                                                     \
-                GLS_LOAD_ROW(phb, magb, t + GL_NW)                                                                       \
+                GLS_LOAD_ROW(phb, magb, t + GL_NW, GL_TB)                                                                \
             } else if (next_item < p.n_items) {                                                                          \
-                GLS_LOAD_ROW(x_in + (size_t)nb * p.T * p.FP, p.mag + (size_t)nb * p.T * p.FP, nt0 - lead + wave)         \
+                GLS_LOAD_ROW(x_in + (size_t)nb * p.T * p.FP, p.mag + (size_t)nb * p.T * p.FP, nt0 - lead + wave, (RAG ? nTb : p.T)) \
                 have_row = true;                                                                                         \
             }
             if (NST == 1) {
@@ -680,7 +704,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                 sk += sk < 0 ? R : 0;
                 ring_k += ring_floats;
                 yb_k += halo * hop;
-                const bool valid_k = ik >= 0 && tk >= 0 && tk < p.T;
+                const bool valid_k = ik >= 0 && tk >= 0 && tk < GL_TB;
                 {
                     // |S| of this stage's frame, requested where the stage starts (the forward transform covers the loads;
                     // unconditional: a row that is not needed is one that exists).  ONE load site for every further stage --
@@ -690,7 +714,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                     // iteration), and because those temporaries were transform registers as well, the compiler's waits for
                     // "loads that may still write them" stood in the middle of the transforms and inside the overlap-add's
                     // critical section: 190.5 -> 185.9 us per iteration alone (profiles/r06_experiment_gl_issue.txt)
-                    const int tq = tk < 0 ? 0 : (tk >= p.T ? p.T - 1 : tk);
+                    const int tq = tk < 0 ? 0 : (tk >= GL_TB ? GL_TB - 1 : tk);
                     const float* mrow_ = magb + (size_t)tq * p.FP;
                     const float* mlo_ = mrow_ + lane; const float* mhi_ = mrow_ + (MH - lane);
 #pragma unroll
@@ -814,6 +838,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         item = next_item;
     }
 #undef GLS_LOAD_ROW
+#undef GL_TB
+#undef GL_L
 #undef GLS_NEXT_ROW
 #undef GLS_TOUCH_ROW
 #undef GLS_URGENCY
@@ -879,13 +905,16 @@ GlCutCost gl_cut_cost(int halo, int lag, int n_stage) {
     return GlCutCost{c * (5.5 / 6.0), c * 0.5};
 }
 // deals the frames to `W` workers with at most `M` cost each; returns false if they do not fit.  workers[w] = its runs
-bool gl_deal(int T, int B, int W, double M, const GlCutCost& cc, int min_len, std::vector<std::vector<GlRun>>& workers, double* makespan) {
+// lens: frames per utterance (null: T for all); no run is shorter than min(min_len, its utterance)
+bool gl_deal(const int* lens, int T, int B, int W, double M, const GlCutCost& cc, int min_len_all, std::vector<std::vector<GlRun>>& workers, double* makespan) {
     workers.assign((size_t)W, {});
     int b = 0, t = 0, w = 0;
     double load = 0.0, worst = 0.0;
     while (b < B) {
         if (w >= W) return false;
-        const int rest = T - t;
+        const int Tb = lens ? lens[b] : T;
+        const int min_len = std::min(Tb, min_len_all);
+        const int rest = Tb - t;
         const double left = t > 0 ? cc.interior : cc.edge;
         const double whole = rest + left + cc.edge;                    // the rest of the utterance as one run
         if (load + whole <= M + 1e-9) {
@@ -914,6 +943,24 @@ bool gl_deal(int T, int B, int W, double M, const GlCutCost& cc, int min_len, st
 
 int gl_plan_items(int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
                   std::vector<int4>* items, int* slots_per_utt, int* workers_out) {
+    return gl_plan_items_ragged(nullptr, T, B, win, hop, n_workers, n_stage, force_runs, force_run_len, items, slots_per_utt, workers_out);
+}
+
+// lens == null: T frames in every utterance, and every line below does what it did for one length
+int gl_plan_items_ragged(const int* lens, int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
+                         std::vector<int4>* items, int* slots_per_utt, int* workers_out) {
+    auto len_of = [&](int b) { return lens ? lens[b] : T; };
+    long long total_frames = 0;
+    int T_min = len_of(0), T_top = len_of(0);
+    for (int b = 0; b < B; ++b) {
+        total_frames += len_of(b);
+        T_min = std::min(T_min, len_of(b));
+        T_top = std::max(T_top, len_of(b));
+    }
+    if (lens && T_min == T_top) {   // one length after all: the uniform cut, item for item
+        lens = nullptr;
+        T = T_top;
+    }
     const int ncol = (win + hop - 1) / hop, halo = ncol - 1;
     n_stage = n_stage < 1 ? 1 : (n_stage > 3 ? 3 : n_stage);
     n_workers = n_workers < 1 ? 1 : n_workers;
@@ -923,29 +970,42 @@ int gl_plan_items(int T, int B, int win, int hop, int n_workers, int n_stage, in
     // tests / experiments only (per-handle options "gl_runs" / "gl_run_len" behind "debug_hooks", api_handle.hip): every
     // utterance cut alike into runs of one length and a rest, one run per list entry
     int forced_len = 0;
-    if (force_runs >= 1 && force_runs <= T) forced_len = ((T + force_runs - 1) / force_runs + GL_NW - 1) / GL_NW * GL_NW;
+    if (force_runs >= 1 && force_runs <= T_top) forced_len = ((T_top + force_runs - 1) / force_runs + GL_NW - 1) / GL_NW * GL_NW;
     if (force_run_len >= GL_NW) forced_len = force_run_len / GL_NW * GL_NW;
     if (forced_len > 0) {
-        for (int t0 = 0; t0 < T; t0 += forced_len)
-            for (int b = 0; b < B; ++b) workers.push_back({GlRun{b, t0, std::min(forced_len, T - t0)}});
+        for (int t0 = 0; t0 < T_top; t0 += forced_len)
+            for (int b = 0; b < B; ++b)
+                if (t0 < len_of(b)) workers.push_back({GlRun{b, t0, std::min(forced_len, len_of(b) - t0)}});
     } else {
         const GlCutCost cc = gl_cut_cost(halo, lag, n_stage);
         // the shortest run: a round of the eight waves -- down to half a round where the workgroups outnumber the rounds (one
         // utterance on a whole chip: 250 runs of 4 frames instead of 125 of 8, Griffin-Lim 1.06 -> 0.92 ms per call at B = 1)
-        const long long per_worker = (long long)B * T / n_workers;
-        const int min_len = std::min(T, (int)std::max<long long>(GL_NW / 2, std::min<long long>(GL_NW, per_worker)));
+        const long long per_worker = total_frames / n_workers;
+        const int min_len_all = (int)std::max<long long>(GL_NW / 2, std::min<long long>(GL_NW, per_worker));
+        const int min_len = std::min(T_min, min_len_all);
         // the smallest makespan over a scan of the bound (the deal is greedy: a lower bound does not always give a lower result)
-        const double total = (double)B * (T + 2 * cc.edge);
+        const double total = (double)total_frames + (double)B * 2 * cc.edge;
         double lo = std::max(total / n_workers, (double)min_len + 2 * cc.edge), best_t = 1e300;
         std::vector<std::vector<GlRun>> cand;
+        int best_step = -1;
         for (int step = 0; step < 400; ++step) {
             const double M = lo * (1.0 + 0.0025 * step);
             double t = 0.0;
-            if (!gl_deal(T, B, n_workers, M, cc, min_len, cand, &t)) continue;
-            if (t < best_t - 1e-9) { best_t = t; workers = cand; }
+            if (!gl_deal(lens, T, B, n_workers, M, cc, min_len_all, cand, &t)) continue;
+            if (t < best_t - 1e-9) { best_t = t; workers = cand; best_step = step; }
+        }
+        // a ragged batch: the bounds between the best step and the one before it, sixteen times as fine (utterance ends fall
+        // anywhere in a share, so a step of the scan -- a quarter per cent, 6 frames of a share of 2600 -- is worth looking into)
+        if (lens && best_step > 0) {
+            for (int sub = 1; sub < 16; ++sub) {
+                const double M = lo * (1.0 + 0.0025 * (best_step - 1 + sub / 16.0));
+                double t = 0.0;
+                if (!gl_deal(lens, T, B, n_workers, M, cc, min_len_all, cand, &t)) continue;
+                if (t < best_t - 1e-9) { best_t = t; workers = cand; }
+            }
         }
         if (workers.empty()) {   // (cannot happen: at twice the average every deal fits) one run per utterance
-            for (int b = 0; b < B; ++b) workers.push_back({GlRun{b, 0, T}});
+            for (int b = 0; b < B; ++b) workers.push_back({GlRun{b, 0, len_of(b)}});
         }
     }
     // table order = the order the persistent workgroups draw in: every worker's first run, then the runs that follow in
@@ -966,6 +1026,24 @@ int gl_plan_items(int T, int B, int win, int hop, int n_workers, int n_stage, in
     items->clear();
     size_t depth = 0;
     for (const auto& w : workers) depth = std::max(depth, w.size());
+    if (lens) {
+        // a ragged batch: the workers' runs differ too much in length for "level by level" to be the order they come free in (one
+        // worker is through three short utterances before another has finished its first long one, and would take that one's
+        // second run).  Behind the first runs the table is in the order of the PLANNED start of every run, frames and per-run
+        // cost counted: a worker that comes free finds the run planned for that moment -- its own, if the plan holds.
+        std::vector<std::pair<double, const GlRun*>> rest;
+        for (const auto& w : workers) {
+            double before = 0.0;
+            for (size_t d = 0; d < w.size(); ++d) {
+                if (d == 0) items->push_back(make_int4(w[d].b, w[d].t0, w[d].len, slot_word(w[d])));
+                else rest.push_back({before, &w[d]});
+                before += w[d].len + 11.0;
+            }
+        }
+        std::stable_sort(rest.begin(), rest.end(), [](const std::pair<double, const GlRun*>& a, const std::pair<double, const GlRun*>& b) { return a.first < b.first; });
+        for (const auto& e : rest) items->push_back(make_int4(e.second->b, e.second->t0, e.second->len, slot_word(*e.second)));
+        depth = 0;
+    }
     for (size_t d = 0; d < depth; ++d) {
         std::vector<std::pair<double, const GlRun*>> level;
         for (const auto& w : workers) {
@@ -1038,19 +1116,19 @@ hipError_t gl_plan_stream(GlParams& p, int n_workers, int n_stage, int force_run
     return hipSuccess;
 }
 
-template <int MODE, int W, int H, bool MSE, int NST = 1>
+template <int MODE, int W, int H, bool MSE, int NST = 1, bool RAG = false>
 static hipError_t gl_stream_set_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<MODE, W, H, MSE, NST, false>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<MODE, W, H, MSE, NST, false, false, RAG>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess || MODE != 0) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, NST, true>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, NST, true, false, RAG>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 // the momentum instantiations: plain, seeded (a call's first launch) and with the mse (its last); a call with momentum has at
 // least two iterations, so no launch is seeded AND asked for the mse
-template <int W, int H, bool MSE, bool SEEDED>
+template <int W, int H, bool MSE, bool SEEDED, bool RAG = false>
 static hipError_t gl_stream_set_attr_mom() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, 1, SEEDED, true>),
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, 1, SEEDED, true, RAG>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
@@ -1061,19 +1139,20 @@ static hipError_t gl_stream_set_attr_mom() {
 // needed ~100 spilled registers per lane.
 bool gl_stream_instantiated(int win, int hop) { return (win == 1102 && hop == 275) || (win == 800 && hop == 200); }
 
-template <int W, int H>
+// RAG: the ragged instantiations (p.n_frames set) -- the same launch forms, one for one
+template <int W, int H, bool RAG>
 static hipError_t gl_stream_launch_wh(hipStream_t s, const GlParams& p, dim3 grid, size_t lds, int final_istft, int n_stage, bool mse) {
 #define GLS_LAUNCH_N(MODE, M, N)                                                                                         \
     {                                                                                                                    \
-        if (MODE == 0 && p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, M, N, true>), grid, dim3(GL_THREADS), lds, s, p);   \
-        else hipLaunchKernelGGL((gl_stream_kernel<MODE, W, H, M, N, false>), grid, dim3(GL_THREADS), lds, s, p);        \
+        if (MODE == 0 && p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, M, N, true, false, RAG>), grid, dim3(GL_THREADS), lds, s, p);   \
+        else hipLaunchKernelGGL((gl_stream_kernel<MODE, W, H, M, N, false, false, RAG>), grid, dim3(GL_THREADS), lds, s, p);        \
     }
     // the momentum form: instantiations of their own, one iteration per launch; a call without momentum never comes here
     if (p.mom_c && !final_istft) {
         if (mse && p.seeded) return hipErrorInvalidValue;   // (see gl_stream_set_attr_mom)
-        if (mse) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, true, 1, false, true>), grid, dim3(GL_THREADS), lds, s, p);
-        else if (p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, true, true>), grid, dim3(GL_THREADS), lds, s, p);
-        else hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, false, true>), grid, dim3(GL_THREADS), lds, s, p);
+        if (mse) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, true, 1, false, true, RAG>), grid, dim3(GL_THREADS), lds, s, p);
+        else if (p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, true, true, RAG>), grid, dim3(GL_THREADS), lds, s, p);
+        else hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, false, true, RAG>), grid, dim3(GL_THREADS), lds, s, p);
         return hipGetLastError();
     }
     if (n_stage == 3) GLS_LAUNCH_N(0, false, 3)
@@ -1099,27 +1178,35 @@ hipError_t launch_gl_stream(hipStream_t s, const GlParams& p_in, int n_cus, int 
     const int nwg = p.n_workers > 0 && p.n_workers < n_cus ? p.n_workers : (p.n_items < n_cus ? p.n_items : n_cus);
     const dim3 grid(nwg);
     const bool mse = p.mse_partial != nullptr;
-    if (p.win == 1102 && p.hop == 275) return gl_stream_launch_wh<1102, 275>(s, p, grid, lds, final_istft, n_stage, mse);
-    if (p.win == 800 && p.hop == 200) return gl_stream_launch_wh<800, 200>(s, p, grid, lds, final_istft, n_stage, mse);
+    if (p.n_frames) {
+        if (!p.rw_edge || p.rw_E != gl_rw_edge_len(NFFT, p.win, p.hop)) return hipErrorInvalidValue;
+        if (p.win == 1102 && p.hop == 275) return gl_stream_launch_wh<1102, 275, true>(s, p, grid, lds, final_istft, n_stage, mse);
+        if (p.win == 800 && p.hop == 200) return gl_stream_launch_wh<800, 200, true>(s, p, grid, lds, final_istft, n_stage, mse);
+        return hipErrorInvalidValue;
+    }
+    if (p.win == 1102 && p.hop == 275) return gl_stream_launch_wh<1102, 275, false>(s, p, grid, lds, final_istft, n_stage, mse);
+    if (p.win == 800 && p.hop == 200) return gl_stream_launch_wh<800, 200, false>(s, p, grid, lds, final_istft, n_stage, mse);
     return hipErrorInvalidValue;
 }
 
-template <int W, int H>
+template <int W, int H, bool RAG>
 static hipError_t gl_stream_configure_wh() {
     hipError_t e;
-    if ((e = gl_stream_set_attr<0, W, H, true>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<0, W, H, false>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<0, W, H, false, 2>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<0, W, H, false, 3>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<1, W, H, false>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr_mom<W, H, false, false>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr_mom<W, H, false, true>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr_mom<W, H, true, false>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr<0, W, H, true, 1, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr<0, W, H, false, 1, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr<0, W, H, false, 2, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr<0, W, H, false, 3, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr<1, W, H, false, 1, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr_mom<W, H, false, false, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr_mom<W, H, false, true, RAG>()) != hipSuccess) return e;
+    if ((e = gl_stream_set_attr_mom<W, H, true, false, RAG>()) != hipSuccess) return e;
     return hipSuccess;
 }
 hipError_t gl_stream_configure() {
-    hipError_t e = gl_stream_configure_wh<1102, 275>();
-    if (e == hipSuccess) e = gl_stream_configure_wh<800, 200>();
+    hipError_t e = gl_stream_configure_wh<1102, 275, false>();
+    if (e == hipSuccess) e = gl_stream_configure_wh<800, 200, false>();
+    if (e == hipSuccess) e = gl_stream_configure_wh<1102, 275, true>();
+    if (e == hipSuccess) e = gl_stream_configure_wh<800, 200, true>();
     return e;
 }
 
@@ -1306,25 +1393,49 @@ hipError_t launch_gl_mse_reduce(hipStream_t s, const float* partial, int B, int 
     return hipGetLastError();
 }
 
+// ragged: the utterance's own denominator F * n_frames[b], made as the uniform call makes its one (double product, then float);
+// per_frame (momentum, general kernels): the row holds one partial per frame and the first n_frames[b] are summed, in frame
+// order -- the sum of the single-utterance call, bit for bit.  Otherwise every slot of the row (the last run zeroed the unused)
+__global__ void gl_mse_reduce_ragged_kernel(const float* partial, int nchunks, int F, const int* n_frames, int per_frame, float* mse) {
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const int Tb = n_frames[b];
+        const int n = per_frame ? Tb : nchunks;
+        float s = 0.f;
+        for (int i = 0; i < n; ++i) s += partial[(size_t)b * nchunks + i];
+        mse[b] = s / (float)((double)F * Tb);
+    }
+}
+hipError_t launch_gl_mse_reduce_ragged(hipStream_t s, const float* partial, int B, int nchunks, int F, const int* n_frames, int per_frame,
+                                       float* mse) {
+    hipLaunchKernelGGL(gl_mse_reduce_ragged_kernel, dim3(B), dim3(64), 0, s, partial, nchunks, F, n_frames, per_frame, mse);
+    return hipGetLastError();
+}
+
 // (B,F,T) reference layout -> internal (B,T,FP) magnitude (abs taken, as griffin_lim_v2 does)
-__global__ void mag_ft_to_tf_kernel(const float* in, float* out, int F, int T, int FP) {
+// RAG (a ragged batch): columns t >= n_frames[b] are neither read nor written; a tile that lies behind the utterance's end leaves
+template <bool RAG>
+__global__ void mag_ft_to_tf_kernel(const float* in, float* out, int F, int T, int FP, const int* n_frames) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
     const int f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x, ty = threadIdx.y;   // 32 x 8
+    const int Tb = RAG ? n_frames[b] : T;
+    if (RAG && t0 >= Tb) return;   // (the whole workgroup)
     for (int i = ty; i < 32; i += 8) {
         const int f = f0 + i, t = t0 + tx;
-        tile[i][tx] = (f < F && t < T) ? fabsf(in[((size_t)b * F + f) * T + t]) : 0.f;
+        tile[i][tx] = (f < F && t < Tb) ? fabsf(in[((size_t)b * F + f) * T + t]) : 0.f;
     }
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
         const int t = t0 + i, f = f0 + tx;
-        if (t < T && f < FP) out[((size_t)b * T + t) * FP + f] = tile[tx][i];
+        if (t < Tb && f < FP) out[((size_t)b * T + t) * FP + f] = tile[tx][i];
     }
 }
-hipError_t launch_mag_ft_to_tf(hipStream_t s, const float* in, float* out, int B, int F, int T, int FP) {
+hipError_t launch_mag_ft_to_tf(hipStream_t s, const float* in, float* out, int B, int F, int T, int FP, const int* n_frames) {
     dim3 grid((T + 31) / 32, (FP + 31) / 32, B);
-    hipLaunchKernelGGL(mag_ft_to_tf_kernel, grid, dim3(32, 8), 0, s, in, out, F, T, FP);
+    if (n_frames) hipLaunchKernelGGL(mag_ft_to_tf_kernel<true>, grid, dim3(32, 8), 0, s, in, out, F, T, FP, n_frames);
+    else hipLaunchKernelGGL(mag_ft_to_tf_kernel<false>, grid, dim3(32, 8), 0, s, in, out, F, T, FP, n_frames);
     return hipGetLastError();
 }
 
@@ -1354,15 +1465,19 @@ hipError_t launch_tf_to_ft(hipStream_t s, const float* in, float* out, int B, in
 // no iteration follows -- the first launch of an iteration makes it itself); out (B,T,FP) phasor codes (no magnitudes
 // needed: the state is the phasor alone).  Running it on a side stream beside the post-net was tried and cost 1.3 ms
 // per step instead of saving 0.17: a third busy stream slows the Griffin-Lim launches of the main one.
-__global__ void phase_init_kernel(const float* init_ft, uint64_t seed, gl_state_t* out, int F, int T, int FP) {
+// RAG (a ragged batch): as mag_ft_to_tf_kernel -- nothing behind n_frames[b] is read or written
+template <bool RAG>
+__global__ void phase_init_kernel(const float* init_ft, uint64_t seed, gl_state_t* out, int F, int T, int FP, const int* n_frames) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
     const int f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int tx = threadIdx.x, ty = threadIdx.y;
+    const int Tb = RAG ? n_frames[b] : T;
+    if (RAG && t0 >= Tb) return;   // (the whole workgroup)
     for (int i = ty; i < 32; i += 8) {
         const int f = f0 + i, t = t0 + tx;
         float u = 0.f;
-        if (f < F && t < T) {
+        if (f < F && t < Tb) {
             const size_t idx = ((size_t)b * F + f) * T + t;
             u = init_ft ? init_ft[idx] : 0.f;
         }
@@ -1371,7 +1486,7 @@ __global__ void phase_init_kernel(const float* init_ft, uint64_t seed, gl_state_
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
         const int t = t0 + i, f = f0 + tx;
-        if (t < T && f < FP) {
+        if (t < Tb && f < FP) {
             float sn, cs;
             sincospif(2.0f * tile[tx][i], &sn, &cs);
             cf e = cmk(cs, sn);   // phasor of exp(2 pi i u)
@@ -1380,9 +1495,10 @@ __global__ void phase_init_kernel(const float* init_ft, uint64_t seed, gl_state_
         }
     }
 }
-hipError_t launch_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, void* out, int B, int F, int T, int FP) {
+hipError_t launch_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, void* out, int B, int F, int T, int FP, const int* n_frames) {
     dim3 grid((T + 31) / 32, (FP + 31) / 32, B);
-    hipLaunchKernelGGL(phase_init_kernel, grid, dim3(32, 8), 0, s, init_ft, seed, reinterpret_cast<gl_state_t*>(out), F, T, FP);
+    if (n_frames) hipLaunchKernelGGL(phase_init_kernel<true>, grid, dim3(32, 8), 0, s, init_ft, seed, reinterpret_cast<gl_state_t*>(out), F, T, FP, n_frames);
+    else hipLaunchKernelGGL(phase_init_kernel<false>, grid, dim3(32, 8), 0, s, init_ft, seed, reinterpret_cast<gl_state_t*>(out), F, T, FP, n_frames);
     return hipGetLastError();
 }
 

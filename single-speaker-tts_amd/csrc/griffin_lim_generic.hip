@@ -39,10 +39,12 @@ namespace tts {
 // frames[b][t][j] = window[j] * irfft(|S| e^{i phi})[pad + j], j < win  (pad = (N - win) / 2)
 __global__ __launch_bounds__(GLG_THREADS) void glg_istft_kernel(const float* __restrict__ mag, const gcf* __restrict__ ph,
                                                                 const float* __restrict__ window, const gcf* __restrict__ tw,
-                                                                float* __restrict__ frames, int T, int Fp, int N, int m, int win) {
+                                                                float* __restrict__ frames, int T, int Fp, int N, int m, int win,
+                                                                const int* __restrict__ n_frames) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     gcf* a = reinterpret_cast<gcf*>(smem);
     const int t = blockIdx.x, b = blockIdx.y;
+    if (n_frames && t >= n_frames[b]) return;   // ragged batch: a padding frame (the whole workgroup leaves; its rows are never read)
     const size_t row = ((size_t)b * T + t) * Fp;
     // real inverse transform of N = 2 M points as a complex one of M: with z[n] = x[2n] + i x[2n+1],
     //   Z[k] = (X[k] + conj X[M-k]) + i conj(W_N^k) (X[k] - conj X[M-k])   (= 2 FFT_M(z)[k]),   x = IFFT_M(Z) / N
@@ -69,20 +71,26 @@ __global__ __launch_bounds__(GLG_THREADS) void glg_istft_kernel(const float* __r
 }
 
 // wav[b][s] = rwss[s + N/2] * sum_t frames[b][t][s + N/2 - t hop - pad], frames in increasing t; s < L = hop (T - 1)
+// ragged batch (n_frames != null): utterance b has Tb = n_frames[b] frames and hop (Tb - 1) samples, the rest of its row of L is
+// written as 0; rwss has a row of N + L entries per utterance, made for ITS length; T and L stay the strides
 __global__ void glg_ola_kernel(const float* __restrict__ frames, const float* __restrict__ rwss, float* __restrict__ wav, int T, int N,
-                               int win, int hop, int L) {
+                               int win, int hop, int L, const int* __restrict__ n_frames) {
     const int b = blockIdx.y;
     const int pad = (N - win) >> 1;
+    const int Tb = n_frames ? n_frames[b] : T;
+    const int Lb = n_frames ? hop * (Tb - 1) : L;
+    const float* rw = n_frames ? rwss + (size_t)b * (N + L) : rwss;
     for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < L; s += gridDim.x * blockDim.x) {
+        if (s >= Lb) { wav[(size_t)b * L + s] = 0.f; continue; }
         const int n = s + (N >> 1);           // index in the padded signal
         const int q = n - pad;                // frame t covers it when 0 <= q - t hop < win
         int t_lo = (q - win + hop) / hop;     // ceil((q - win + 1) / hop)
         if (q - win + 1 <= 0) t_lo = 0;
         int t_hi = q / hop;
-        if (t_hi > T - 1) t_hi = T - 1;
+        if (t_hi > Tb - 1) t_hi = Tb - 1;
         float acc = 0.f;
         for (int t = t_lo; t <= t_hi; ++t) acc += frames[((size_t)b * T + t) * win + (q - t * hop)];
-        wav[(size_t)b * L + s] = acc * rwss[n];
+        wav[(size_t)b * L + s] = acc * rw[n];
     }
 }
 
@@ -97,13 +105,18 @@ __global__ __launch_bounds__(GLG_THREADS) void glg_stft_kernel(const float* __re
                                                                const gcf* __restrict__ tw, gcf* __restrict__ out, int Tf, int Fp, int N,
                                                                int m, int win, int hop, const float* __restrict__ mag,
                                                                float* __restrict__ mse_partial, gcf* mom_c, float mom_alpha,
-                                                               int mom_first) {
+                                                               int mom_first, const int* __restrict__ n_frames) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     gcf* a = reinterpret_cast<gcf*>(smem);
     __shared__ float red[GLG_THREADS / 64];
     const int t = blockIdx.x, b = blockIdx.y;
     const int H = N >> 1, pad = (N - win) >> 1;
     const float* y = wav + (size_t)b * n;
+    // ragged batch: a padding frame's workgroup leaves; the signal reflects at the utterance's own end (n stays the row stride)
+    if (n_frames) {
+        if (t >= n_frames[b]) return;
+        n = hop * (n_frames[b] - 1);
+    }
     const int y0 = t * hop - H;               // signal index of padded-frame sample 0
     // real transform of N = 2 M points as a complex one of M: z[n] = x[2n] + i x[2n+1], Z = FFT_M(z),
     //   X[k] = ((Z[k] + conj Z[M-k]) - i W_N^k (Z[k] - conj Z[M-k])) / 2,  k <= M  (Z[M] = Z[0])
@@ -167,8 +180,10 @@ __global__ __launch_bounds__(GLG_THREADS) void glg_stft_kernel(const float* __re
 }
 
 // initial unit phasors: exp(2 pi i u) from a (B, F, T) array of U[0,1) numbers, or a counter-based draw from the seed
-__global__ void glg_phase_init_kernel(const float* __restrict__ init_ft, unsigned long long seed, gcf* __restrict__ out, int F, int T, int Fp) {
+__global__ void glg_phase_init_kernel(const float* __restrict__ init_ft, unsigned long long seed, gcf* __restrict__ out, int F, int T, int Fp,
+                                      const int* __restrict__ n_frames) {
     const int b = blockIdx.z, t = blockIdx.y;
+    if (n_frames && t >= n_frames[b]) return;   // ragged batch: a padding frame is neither read nor written
     for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < Fp; f += gridDim.x * blockDim.x) {
         gcf e = (gcf){1.f, 0.f};
         if (f < F) {
@@ -208,35 +223,35 @@ static int glg_log2(int N) {
 
 bool glg_supports(int n_fft) { return n_fft >= 256 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0; }
 
-hipError_t launch_glg_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, float2* out, int B, int F, int T, int Fp) {
+hipError_t launch_glg_phase_init(hipStream_t s, const float* init_ft, uint64_t seed, float2* out, int B, int F, int T, int Fp, const int* n_frames) {
     hipLaunchKernelGGL(glg_phase_init_kernel, dim3((Fp + 255) / 256, T, B), dim3(256), 0, s, init_ft, (unsigned long long)seed,
-                       reinterpret_cast<gcf*>(out), F, T, Fp);
+                       reinterpret_cast<gcf*>(out), F, T, Fp, n_frames);
     return hipGetLastError();
 }
 
 hipError_t launch_glg_istft(hipStream_t s, const float* mag, const float2* ph, const float* window, const float* rwss, const float2* tw,
-                            float* frames, float* wav, int B, int T, int Fp, int n_fft, int win, int hop) {
+                            float* frames, float* wav, int B, int T, int Fp, int n_fft, int win, int hop, const int* n_frames) {
     const int m = glg_log2(n_fft);
     hipLaunchKernelGGL(glg_istft_kernel, dim3(T, B), dim3(glg_threads(n_fft)), glg_lds(n_fft), s, mag, reinterpret_cast<const gcf*>(ph), window,
-                       reinterpret_cast<const gcf*>(tw), frames, T, Fp, n_fft, m, win);
+                       reinterpret_cast<const gcf*>(tw), frames, T, Fp, n_fft, m, win, n_frames);
     const int L = hop * (T - 1);
     hipLaunchKernelGGL(glg_ola_kernel, dim3((L + 255) / 256 > 1024 ? 1024 : (L + 255) / 256, B), dim3(256), 0, s, frames, rwss, wav, T, n_fft,
-                       win, hop, L);
+                       win, hop, L, n_frames);
     return hipGetLastError();
 }
 
 hipError_t launch_glg_stft(hipStream_t s, const float* wav, int n, const float* window, const float2* tw, float2* out, int B, int Tf, int Fp,
                            int n_fft, int win, int hop, int mode, const float* mag, float* mse_partial, float2* mom_c, float mom_alpha,
-                           int mom_first) {
+                           int mom_first, const int* n_frames) {
     const int m = glg_log2(n_fft);
     if (mode == 1)
         hipLaunchKernelGGL((glg_stft_kernel<1>), dim3(Tf, B), dim3(glg_threads(n_fft)), glg_lds(n_fft), s, wav, n, window,
                            reinterpret_cast<const gcf*>(tw), reinterpret_cast<gcf*>(out), Tf, Fp, n_fft, m, win, hop, mag, mse_partial,
-                           (gcf*)nullptr, 0.f, 0);
+                           (gcf*)nullptr, 0.f, 0, (const int*)nullptr);
     else
         hipLaunchKernelGGL((glg_stft_kernel<0>), dim3(Tf, B), dim3(glg_threads(n_fft)), glg_lds(n_fft), s, wav, n, window,
                            reinterpret_cast<const gcf*>(tw), reinterpret_cast<gcf*>(out), Tf, Fp, n_fft, m, win, hop, mag, mse_partial,
-                           reinterpret_cast<gcf*>(mom_c), mom_alpha, mom_first);
+                           reinterpret_cast<gcf*>(mom_c), mom_alpha, mom_first, n_frames);
     return hipGetLastError();
 }
 

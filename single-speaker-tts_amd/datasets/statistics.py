@@ -1,12 +1,17 @@
 """Mirror of reference datasets/statistics.py:11-98: the dB statistics the feature normalisation constants come from.
 
 The spectrograms are computed by tts_extract_features (no trim, no normalisation: raw dB rows, n_fft 1024, hop 256,
-window 1024, 80 HTK mel bands over 0 .. sr // 2); the per-file min / max are taken on the host.  The reconstruction-error
-statistics and plots of the reference module (:101-258) are out of scope."""
+window 1024, 80 HTK mel bands over 0 .. sr // 2); the per-file min / max are taken on the host.
+
+``collect_reconstruction_error`` is the reference's :146-187 -- |STFT| of every recording followed by Griffin-Lim, the mean
+of the last iteration's mse -- as ragged batches: one tts_griffin_lim_ragged call reconstructs ``batch_size`` recordings of
+different lengths.  The duration statistics and the plots of the reference module (:101-143, :190-258) are out of scope."""
 import numpy as np
 
 from ..audio import default_engine
+from ..audio.conversion import ms_to_samples
 from ..audio.io import load_wav
+from ..audio.synthesis import griffin_lim_v2
 
 N_FFT = 1024
 
@@ -40,3 +45,60 @@ def collect_decibel_statistics(path_listing, batch_size=32, engine=None):
                 stats += _stats(mel_db, lin_db)
     stats /= len(paths)
     return stats
+
+
+RECONSTRUCTION_N_FFT = 2048      # reference :149
+RECONSTRUCTION_WIN_MS = 50.0     # :152
+RECONSTRUCTION_HOP_MS = 12.5     # :155
+
+
+def _padded_magnitudes(eng, wavs, n_fft, win, hop):
+    """|STFT| of every recording (Engine.stft_magnitude, recordings of one length in one call) packed into a zero-padded
+    (B, F, T_max) array; returns it with the frame counts 1 + n // hop."""
+    frames = [1 + len(w) // hop for w in wavs]
+    mag = np.zeros((len(wavs), 1 + n_fft // 2, max(frames)), dtype=np.float32)
+    by_len = {}
+    for i, w in enumerate(wavs):
+        by_len.setdefault(len(w), []).append(i)
+    for n, idx in sorted(by_len.items()):
+        m = eng.stft_magnitude(np.stack([np.asarray(wavs[i], dtype=np.float32) for i in idx]), n_fft, win, hop)
+        m = m.to_host() if hasattr(m, 'to_host') else np.asarray(m)
+        for k, i in enumerate(idx):
+            mag[i, :, :frames[i]] = m[k]
+    return mag, frames
+
+
+def collect_reconstruction_error(path_listing, n_iters, batch_size=32, seed=None, engine=None, init_phases=None):
+    """reference :146-187: the mean over the files of the Griffin-Lim reconstruction error after ``n_iters`` iterations, at
+    n_fft 2048 with a 50 ms window and a 12.5 ms hop (``ms_to_samples`` of each file's sampling rate).  Printed and returned.
+
+    The recordings are taken ``batch_size`` files at a time; those of one sampling rate are sorted by length and
+    reconstructed in ONE ragged Griffin-Lim call (``griffin_lim_v2(..., n_frames=...)``), so the padding is neither computed
+    nor able to change a result.  ``seed`` seeds the initial phases (None: unseeded, like the reference);
+    ``init_phases`` (a test hook, as ``griffin_lim_v2``'s ``init_phase``) maps a path to its (F, T) array of U[0, 1) numbers."""
+    eng = engine or default_engine()
+    paths = [p.decode() if isinstance(p, bytes) else p for p in path_listing]
+    n_fft = RECONSTRUCTION_N_FFT
+    print('Collecting reconstruction statistics for {} files ...'.format(len(paths)))
+    mse_errors = []
+    step = max(1, int(batch_size))
+    for i in range(0, len(paths), step):
+        chunk = paths[i:i + step]
+        loaded = [load_wav(p) for p in chunk]
+        for sr in sorted({r for _, r in loaded}):
+            win = ms_to_samples(RECONSTRUCTION_WIN_MS, sampling_rate=sr)
+            hop = ms_to_samples(RECONSTRUCTION_HOP_MS, sampling_rate=sr)
+            group = sorted((k for k, (_, r) in enumerate(loaded) if r == sr), key=lambda k: len(loaded[k][0]))
+            mag, frames = _padded_magnitudes(eng, [loaded[k][0] for k in group], n_fft, win, hop)
+            init = None
+            if init_phases is not None:
+                init = np.zeros(mag.shape, dtype=np.float32)
+                for row, k in enumerate(group):
+                    init[row, :, :frames[row]] = np.asarray(init_phases[chunk[k]], dtype=np.float32)
+            batch_seed = None if seed is None else int(seed) + i
+            _, mse = griffin_lim_v2(mag, win_length=win, hop_length=hop, n_fft=n_fft, n_iter=n_iters, init_phase=init,
+                                    seed=batch_seed, engine=eng, n_frames=frames)
+            mse_errors.extend(float(m) for m in (mse if mse is not None else np.zeros(len(group))))
+    total_mse = sum(mse_errors) / len(mse_errors)
+    print('Dataset MSE with {} iterations: {}'.format(n_iters, total_mse))
+    return total_mse

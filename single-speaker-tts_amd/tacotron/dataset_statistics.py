@@ -3,19 +3,26 @@ constants of the feature normalisation (datasets.statistics.collect_decibel_stat
 names -- which it crosses: the mean max mel dB is printed as ``mel_mag_ref_db``, the mean min as ``mel_mag_max_db``, and
 likewise for the linear constants.
 
-    python -m single-speaker-tts_amd.tacotron.dataset_statistics [--dataset-folder DIR]"""
+    python -m single-speaker-tts_amd.tacotron.dataset_statistics [--dataset-folder DIR] [--reconstruction-iters N]
+
+``--reconstruction-iters N`` adds the reference's Griffin-Lim reconstruction error after N iterations
+(datasets.statistics.collect_reconstruction_error) behind the dB statistics; without it the output is what it was."""
 import argparse
 import os
 
 from ..datasets.lj_speech import LJSpeechDatasetHelper
-from ..datasets.statistics import collect_decibel_statistics
+from ..datasets.statistics import collect_decibel_statistics, collect_reconstruction_error
 from .params import dataset_params
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='tacotron.dataset_statistics')
     ap.add_argument('--dataset-folder', default=dataset_params.dataset_folder)
+    ap.add_argument('--reconstruction-iters', type=int, default=None, metavar='N',
+                    help='also print the mean Griffin-Lim reconstruction error after N iterations')
     args = ap.parse_args(argv)
+    if args.reconstruction_iters is not None and args.reconstruction_iters < 1:
+        ap.error('--reconstruction-iters: at least one iteration')
     dataset = LJSpeechDatasetHelper(dataset_folder=args.dataset_folder, char_dict={'pad': 0, 'eos': 1}, fill_dict=True)
     if not os.path.exists(args.dataset_folder):
         print("Dataset folder '{}' could not be found.".format(args.dataset_folder))
@@ -37,6 +44,8 @@ def main(argv=None):
     print('mel_mag_max_db = ', min_mel_db)
     print('linear_ref_db = ', max_linear_db)
     print('linear_mag_max_db = ', min_linear_db)
+    if args.reconstruction_iters is not None:
+        collect_reconstruction_error(paths, args.reconstruction_iters)
     return 0
 
 

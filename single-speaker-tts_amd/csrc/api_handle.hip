@@ -381,6 +381,7 @@ int sync_all(tts_handle_t h) {
     if (h->pl.aux) HIPCHK(h, hipStreamSynchronize(h->pl.aux));
     if (h->pl.encs) HIPCHK(h, hipStreamSynchronize(h->pl.encs));
     if (h->hio.out) HIPCHK(h, hipStreamSynchronize(h->hio.out));
+    h->gl_plans.synced();
     return check_status(h);
 }
 
@@ -640,6 +641,7 @@ int tts_destroy(tts_handle_t h) {
     if (h->gl.tw1024) hipFree(h->gl.tw1024);
     if (h->gl.tw2048) hipFree(h->gl.tw2048);
     if (h->gl.tables) hipFree(h->gl.tables);
+    h->gl_plans.release();
     if (h->an.window) hipFree(h->an.window);
     if (h->an.mel_wt) hipFree(h->an.mel_wt);
     feat_release(h);

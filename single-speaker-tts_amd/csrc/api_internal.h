@@ -82,7 +82,35 @@ struct Signal {
     }
     hipError_t wait(hipStream_t s) const { return armed ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }   // (a stream waits)
     hipError_t sync() const { return armed ? hipEventSynchronize(ev) : hipSuccess; }                     // (the host waits)
+    bool done() const { return !armed || hipEventQuery(ev) == hipSuccess; }                              // (nobody waits)
     void disarm() { armed = false; }   // what was recorded is known to be complete, or has been waited for by all it concerns
+};
+
+// The run tables of the streaming Griffin-Lim kernel, owned by the handle: one entry per cut (gl_plan in api_stages.hip makes
+// and finds them; DESIGN.md 4.5 has the rules).  A call that finds its cut allocates, copies and waits for nothing; a new one
+// costs one asynchronous copy on the call's stream and at most one hipMalloc.  The least recently used entry is replaced: two
+// per shape (a pipelined call's narrow and wide cut) for the shapes a server runs; a dataset's length vectors come and go.
+constexpr int GL_PLAN_CAPACITY = 16;
+struct GlPlanStore {
+    struct Entry {
+        std::vector<int> key;        // empty: no cut
+        std::vector<GlItem> items;   // host copy
+        int slots = 1, workers = 1;
+        int4* dev = nullptr;         // device table
+        size_t room = 0;             // ... and the items it has room for
+        // the stream the upload and the launches that read the table are enqueued on (null: nothing since the handle was last
+        // synchronised); `ready`: behind the upload -- and behind the readers on the stream before, once it has changed
+        hipStream_t stream = nullptr;
+        Signal ready;
+        unsigned long long used = 0;
+    };
+    std::vector<std::unique_ptr<Entry>> entries;   // at most GL_PLAN_CAPACITY
+    unsigned long long clock = 0;
+    // what a replaced entry left behind while enqueued work may still have read it: freed where the handle is synchronised
+    std::vector<void*> retired_dev;
+    std::vector<std::vector<GlItem>> retired_host;
+    void synced();    // every stream of the handle has been synchronised (sync_all)
+    void release();   // tts_destroy
 };
 
 // A pinned host buffer and the device buffer it is copied to or from (tts_synthesize_host); sizes only increase.
@@ -350,14 +378,14 @@ struct tts_handle_s {
         bool configured = false;
     } glg;
 
+    GlPlanStore gl_plans;   // run tables of the streaming kernel, uniform and ragged batches alike
+
     // ragged Griffin-Lim (tts_griffin_lim_ragged): what the last call uploaded -- the lengths with the window sum-square
-    // tables made for them, and the run table of the streaming kernel -- kept while the next call asks for the same
+    // tables made for them -- kept while the next call asks for the same
     struct {
-        std::vector<int> tab_key, plan_key;
+        std::vector<int> tab_key;
         int* lens = nullptr;       // [B] device (workspace "gl.rag_lens")
         float* rw = nullptr;       // streaming [B][2][rw_E], general [B][n_fft + hop (T_max - 1)] (workspace "gl.rag_rw")
-        int4* items = nullptr;     // workspace "gl.rag_items"
-        int n_items = 0, slots = 1, workers = 1;
     } rag;
 
     // analysis-side tables (STFT window, mel basis)
@@ -474,6 +502,9 @@ int glg_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
 // a ragged batch: host lengths [B] (T is then T_max); null everywhere = one length
 int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames = nullptr);
 int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
+// the cut of p's batch (T, B, win, hop; n_frames: host lengths of a ragged batch or null) for launches of n_stage iterations on
+// n_workers workgroups, from the handle's store: sets p.items / n_items / slots_per_utt / n_workers for launches on h->stream
+int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len);
 int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);

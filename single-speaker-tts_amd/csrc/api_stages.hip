@@ -338,41 +338,79 @@ static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_m
     return TTS_OK;
 }
 
-// The cut of a ragged batch for the streaming kernel: made per call and kept in the handle while the lengths stay (the process-wide
-// cache of gl_plan_stream never frees a table: right for the handful of shapes a server runs, not for a dataset's worth of length
-// vectors).  Sets what gl_plan_stream sets.
-static int gl_rag_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len) {
-    std::vector<int> key = {p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len};
-    key.insert(key.end(), n_frames, n_frames + p.B);
-    auto& r = h->rag;
-    p.ring_frames = gl_stream_ring_frames(p.win, p.hop, 1);
-    std::vector<int4> items;
-    if (r.plan_key != key) {
-        gl_plan_items_ragged(n_frames, p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len, &items, &r.slots, &r.workers);
-        r.n_items = (int)items.size();
-        r.plan_key.clear();
-        r.items = nullptr;
+void GlPlanStore::synced() {
+    for (auto& e : entries) {
+        e->stream = nullptr;
+        e->ready.disarm();
     }
-    WS(h, "gl.rag_items", int4, (size_t)r.n_items, d_items);
-    if (r.items != d_items) {
-        if (items.empty())   // (the workspace moved under a plan that is still the right one)
-            gl_plan_items_ragged(n_frames, p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len, &items, &r.slots, &r.workers);
-        r.plan_key.clear();
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(d_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice));
-        r.items = d_items;
-        r.plan_key = key;
-    }
-    p.items = r.items;
-    p.n_items = r.n_items;
-    p.slots_per_utt = r.slots;
-    p.n_workers = r.workers;
-    return TTS_OK;
+    for (void* d : retired_dev) hipFree(d);
+    retired_dev.clear();
+    retired_host.clear();
+}
+
+void GlPlanStore::release() {
+    synced();
+    for (auto& e : entries) hipFree(e->dev);
+    entries.clear();
 }
 
 static bool gl_rag_all_full(const int32_t* n_frames, int B, int T) {
     for (int b = 0; b < B; ++b) if (n_frames[b] != T) return false;
     return true;
+}
+
+int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len) {
+    // lengths that are all equal are one length: the uniform cut and its key (gl_plan_items does the same)
+    int T = p.T;
+    if (n_frames && gl_rag_all_full(n_frames, p.B, n_frames[0])) {
+        T = n_frames[0];
+        n_frames = nullptr;
+    }
+    std::vector<int> key = {T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len};
+    if (n_frames) key.insert(key.end(), n_frames, n_frames + p.B);
+    GlPlanStore& st = h->gl_plans;
+    GlPlanStore::Entry* e = nullptr;
+    for (auto& q : st.entries)
+        if (q->key == key) e = q.get();
+    const bool found = e != nullptr;
+    if (!found) {
+        if ((int)st.entries.size() < GL_PLAN_CAPACITY) {
+            st.entries.emplace_back(new GlPlanStore::Entry);
+            e = st.entries.back().get();
+        } else {   // the least recently used entry makes room
+            e = st.entries.front().get();
+            for (auto& q : st.entries)
+                if (q->used < e->used) e = q.get();
+            e->key.clear();
+            if (!e->ready.done()) st.retired_host.push_back(std::move(e->items));   // (its upload may still be reading the host copy)
+        }
+        gl_plan_items(n_frames, T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len, &e->items, &e->slots, &e->workers);
+        if (e->items.size() > e->room) {
+            if (e->dev) st.retired_dev.push_back(e->dev);   // (not freed here: enqueued launches may still read it)
+            e->dev = nullptr; e->room = 0; e->stream = nullptr;
+            const size_t room = (e->items.size() + 255) & ~(size_t)255;
+            HIPCHK(h, hipMalloc(reinterpret_cast<void**>(&e->dev), room * sizeof(GlItem)));
+            e->room = room;
+        }
+    }
+    // From here on h->stream is where the table is used.  What another stream still holds of it comes first: the upload, for the
+    // launches' sake, and the launches that read it, for the sake of an overwrite -- now (a table used again) or later.
+    if (e->stream && e->stream != h->stream) {
+        HIPCHK(h, e->ready.record(e->stream));
+        HIPCHK(h, e->ready.wait(h->stream));
+    }
+    if (!found) {
+        HIPCHK(h, hipMemcpyAsync(e->dev, e->items.data(), e->items.size() * sizeof(GlItem), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, e->ready.record(h->stream));
+        e->key = std::move(key);
+    }
+    e->stream = h->stream;
+    e->used = ++st.clock;
+    p.items = e->dev;
+    p.n_items = (int)e->items.size();
+    p.slots_per_utt = e->slots;
+    p.n_workers = e->workers;
+    return TTS_OK;
 }
 
 
@@ -533,17 +571,14 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     }
     // (the cut decides who does which frames, never the waveform's bits: every sample is summed over the frames that cover it in
     //  ascending order whatever run they lie in -- tests/test_gpu_audio.py::test_griffin_lim_bits_do_not_depend_on_the_cut)
-    if (n_frames) {
-        if ((rc = gl_rag_plan(h, p, n_frames, n_cus, per_launch, h->debug_hooks ? h->gl_runs : 0, h->debug_hooks ? h->gl_run_len : 0))) return rc;
-    } else
-    HIPCHK(h, gl_plan_stream(p, n_cus - held > 16 ? n_cus - held : n_cus, per_launch, h->debug_hooks ? h->gl_runs : 0,
-                             h->debug_hooks ? h->gl_run_len : 0, h->stream));
+    const int free_cus = n_cus - held > 16 ? n_cus - held : n_cus;
+    if ((rc = gl_plan(h, p, n_frames, free_cus, per_launch, h->debug_hooks ? h->gl_runs : 0, h->debug_hooks ? h->gl_run_len : 0))) return rc;
     // wide_from >= 0 (the pipelined tts_synthesize, see gl_wide_from there): launches from that index on are cut for ALL
     // compute units -- the second stream's decoder has left its share by then.  A second cut of the same frames.
     GlParams pw = p;
     const bool two_cuts = held > 0 && wide_from >= 0 && n_cus - held > 16 &&
                           !(h->debug_hooks && (h->gl_runs || h->gl_run_len));
-    if (two_cuts) HIPCHK(h, gl_plan_stream(pw, n_cus, per_launch, 0, 0, h->stream));
+    if (two_cuts && (rc = gl_plan(h, pw, n_frames, n_cus, per_launch, 0, 0))) return rc;
     const int nchunks = std::max(p.slots_per_utt, pw.slots_per_utt);
     // (with momentum the squared error is kept per frame: gl_stream_kernel, MOM)
     WS(h, "gl.mse_partial", float, (size_t)B * ((p.mom_c && mse) ? std::max(nchunks, T) : nchunks), msep);
@@ -572,7 +607,6 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     int launch_idx = 0, mse_chunks = p.slots_per_utt, peak_chunks = p.slots_per_utt;
     float2* cur = ph0;
     float2* nxt = ph1;
-    const int free_cus = n_cus - held > 16 ? n_cus - held : n_cus;
     {
         ProfScope ps(h, ST_GL_ITER, n_iter);
         // the streaming kernel runs two iterations per launch (gl_stream_kernel, NST = 2) wherever no per-iteration result
@@ -1284,47 +1318,35 @@ int tts_db_convert(tts_handle_t h, const float* in, size_t n, int mode, float re
 
 // Host-only view of the Griffin-Lim work-item planner (no GPU needed): items[n][4] = {utterance, first frame, frames, slot word}
 // in the order the workgroups draw them (at most max_items are written), *ring_frames = frames the kernel's LDS ring holds;
-// returns the number of items or a negative status.
-int tts_debug_gl_plan(int T, int B, int win_length, int hop_length, int n_workers, int* items, int max_items, int* ring_frames) {
+// returns the number of items or a negative status.  n_frames: the lengths of a ragged batch (T is then their maximum) or null.
+static int debug_gl_plan(const int32_t* n_frames, int T, int B, int win_length, int hop_length, int n_workers, int* items, int max_items,
+                         int* ring_frames) {
+    for (int b = 0; n_frames && b < B; ++b) {
+        if (n_frames[b] < 1) return TTS_ERR_INVALID;
+        T = std::max(T, (int)n_frames[b]);
+    }
     if (T < 1 || B < 1 || win_length < 2 || win_length > TTS_GL_NFFT || hop_length < 1 || n_workers < 1 || !items || max_items < 0)
         return TTS_ERR_INVALID;
     const int ring = gl_stream_ring_frames(win_length, hop_length);
     if ((win_length + hop_length - 1) / hop_length > 8 || ring < 1) return TTS_ERR_UNSUPPORTED;
     int n_stage = 3;   // the handle's default launch form (option "gl_pair")
     while (n_stage > 1 && gl_stream_ring_frames(win_length, hop_length, n_stage) <= 0) --n_stage;
-    std::vector<int4> v;
+    std::vector<GlItem> v;
     int slots = 0;
-    const int n = gl_plan_items(T, B, win_length, hop_length, n_workers, n_stage, 0, 0, &v, &slots);
+    const int n = gl_plan_items(n_frames, T, B, win_length, hop_length, n_workers, n_stage, 0, 0, &v, &slots);
     if (ring_frames) *ring_frames = ring;
-    for (int k = 0; k < n && k < max_items; ++k) {
-        items[4 * k] = v[k].x; items[4 * k + 1] = v[k].y; items[4 * k + 2] = v[k].z; items[4 * k + 3] = v[k].w;
-    }
+    std::memcpy(items, v.data(), (size_t)std::min(n, max_items) * sizeof(GlItem));
     return n;
 }
 
+int tts_debug_gl_plan(int T, int B, int win_length, int hop_length, int n_workers, int* items, int max_items, int* ring_frames) {
+    return debug_gl_plan(nullptr, T, B, win_length, hop_length, n_workers, items, max_items, ring_frames);
+}
 
 // The same for a ragged batch (tts_griffin_lim_ragged): n_frames[b] frames in utterance b.
 int tts_debug_gl_plan_ragged(const int32_t* n_frames, int B, int win_length, int hop_length, int n_workers, int* items, int max_items,
                              int* ring_frames) {
-    if (!n_frames || B < 1 || win_length < 2 || win_length > TTS_GL_NFFT || hop_length < 1 || n_workers < 1 || !items || max_items < 0)
-        return TTS_ERR_INVALID;
-    int T_max = 0;
-    for (int b = 0; b < B; ++b) {
-        if (n_frames[b] < 1) return TTS_ERR_INVALID;
-        T_max = std::max(T_max, (int)n_frames[b]);
-    }
-    const int ring = gl_stream_ring_frames(win_length, hop_length);
-    if ((win_length + hop_length - 1) / hop_length > 8 || ring < 1) return TTS_ERR_UNSUPPORTED;
-    int n_stage = 3;   // the handle's default launch form (option "gl_pair")
-    while (n_stage > 1 && gl_stream_ring_frames(win_length, hop_length, n_stage) <= 0) --n_stage;
-    std::vector<int4> v;
-    int slots = 0;
-    const int n = gl_plan_items_ragged(n_frames, T_max, B, win_length, hop_length, n_workers, n_stage, 0, 0, &v, &slots);
-    if (ring_frames) *ring_frames = ring;
-    for (int k = 0; k < n && k < max_items; ++k) {
-        items[4 * k] = v[k].x; items[4 * k + 1] = v[k].y; items[4 * k + 2] = v[k].z; items[4 * k + 3] = v[k].w;
-    }
-    return n;
+    return n_frames ? debug_gl_plan(n_frames, 0, B, win_length, hop_length, n_workers, items, max_items, ring_frames) : TTS_ERR_INVALID;
 }
 
 

@@ -9,6 +9,7 @@
 // live in the inline namespace tts::fft_scalar, apart from the packed ones.
 #pragma once
 #include "tts_common.h"
+#include "gl_plan.h"   // EX_CPLX
 
 #ifdef FFT_WAVE_SCALAR
 namespace tts {
@@ -210,7 +211,7 @@ __device__ __forceinline__ void fft16(cf (&v)[16]) {
 }
 
 #define E2S 17
-#define EX_CPLX 1088   // 64 rows of E2S (the only exchange image) >= the 1024 bins of the merge pass
+static_assert(EX_CPLX >= 64 * E2S && EX_CPLX > 1024, "a wave's exchange buffer: 64 rows of E2S (the only exchange image), and the 1024 bins + Nyquist of the merge pass");
 
 struct FftTw {
     const cf* a;   // LDS table: a[(k2-1)*64] = W1024^{lane*k2}, k2 = 1..15 (already offset by lane)

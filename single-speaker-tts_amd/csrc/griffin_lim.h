@@ -1,12 +1,12 @@
 // Griffin-Lim / audio kernel launchers shared between griffin_lim.hip and the api_*.hip files.
 #pragma once
 #include "tts_common.h"
-#include <vector>
+#include "gl_plan.h"
 
 namespace tts {
 
 #define TTS_GL_FP 1056      // padded row length of the frame-major spectra (F = 1025): rows start on 128-byte lines
-#define TTS_GL_NFFT 2048
+#define TTS_GL_NFFT tts::NFFT   // the streaming kernel's n_fft (gl_plan.h); every other power of two takes the general path
 
 struct GlParams {
     const float* mag;        // [B][T][FP]
@@ -24,10 +24,8 @@ struct GlParams {
     int T, FP, win, hop;
     int B;                   // utterances
     int ncol;                // ceil(win / hop): frames that overlap a sample, halo = ncol - 1
-    // work items of a launch (gl_plan_stream): a table of RUNS in device memory, {utterance, first frame, frames, slot};
-    // item ids are drawn in table order (first every workgroup's first run, then the runs that follow them).  A run's
-    // partial results (mse, peak) go to slot (w & 0xffff) of its utterance; the run with the utterance's last slot carries
-    // in w >> 16 how many slots up to slots_per_utt it has to zero (utterances are not all cut into the same number of runs).
+    // work items of a launch: the table of gl_plan_items in device memory (a GlItem is read as an int4); item ids are drawn in
+    // table order (first every workgroup's first run, then the runs that follow them)
     const int4* items;
     int n_items, slots_per_utt;
     int n_workers;           // workgroups the cut was made for (= the launch's grid)
@@ -54,24 +52,11 @@ struct GlParams {
     int rw_E;
 };
 
-// entries per end of an utterance in GlParams::rw_edge: every sample an edge frame's window reaches
-inline int gl_rw_edge_len(int n_fft, int win, int hop) { return n_fft + ((win + hop - 1) / hop - 1) * hop; }
+static_assert(sizeof(GlItem) == sizeof(int4), "the kernel reads a GlItem as an int4");
 
-// out[2*16*2*64]: set 0 = window[n] / n_fft, set 1 = set 0 * rwss at an interior frame; n = 2*(lane + 64 c) + e
-void gl_build_wlane(const float* window, const float* rwss, int win, int hop, int T, float* out);
-// streaming form of the iteration / final iSTFT (gl_stream_kernel): no chunks, a run is one stream through an LDS ring
-int gl_stream_ring_frames(int win, int hop, int n_stage = 1);   // 0: the window / hop pair does not fit
 bool gl_stream_instantiated(int win, int hop);                  // the (window, hop) pairs gl_stream_kernel is compiled for (n_fft 2048)
-// needs T, B, win, hop, ncol; sets items / n_items / slots_per_utt (the cut for launches of n_stage iterations on n_workers
-// workgroups; the table is uploaded to the current device once per shape and set of speeds and lives as long as the process)
-// stream: the stream the launches that use the cut will be enqueued on (a table that is new is uploaded there)
-hipError_t gl_plan_stream(GlParams& p, int n_workers, int n_stage = 1, int force_runs = 0, int force_run_len = 0, hipStream_t stream = nullptr);
-// the same cut on the host alone (no device): items[n][4] = {utterance, first frame, frames, slot word}; returns n
-int gl_plan_items(int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
-                  std::vector<int4>* items, int* slots_per_utt, int* workers_out = nullptr);
-// the cut of a ragged batch: lens[b] frames in utterance b (null: T for all, the call above); no run leaves its utterance
-int gl_plan_items_ragged(const int* lens, int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
-                         std::vector<int4>* items, int* slots_per_utt, int* workers_out = nullptr);
+// streaming form of the iteration / final iSTFT (gl_stream_kernel): no chunks, a run is one stream through an LDS ring.
+// p needs T, B, win, hop, ncol and the table of a cut (items, n_items, slots_per_utt, n_workers)
 hipError_t launch_gl_stream(hipStream_t s, const GlParams& p, int n_cus, int final_istft, int n_stage = 1);
 hipError_t gl_configure();
 size_t gl_state_bytes();   // bytes per bin of the state between launches (4: a phasor code)

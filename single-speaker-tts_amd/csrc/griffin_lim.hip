@@ -20,7 +20,7 @@
 // defined.  The time-domain signal never goes to HBM; per bin and iteration the ALGORITHMIC traffic (what the
 // roofline is priced on) is 8 B X in + 4 B |S| + 8 B X out; what really moves with three iterations per launch is a
 // 4-byte phasor code in and out per launch plus |S|.  The cut of an utterance into runs is planned on the host:
-// gl_plan_stream.
+// gl_plan_items (gl_plan.hip).
 //
 // FFT: real 2048-point transforms as 1024-point complex FFTs with a split/merge pass.  One wave
 // per FFT, 16 points per lane: radix-16 in registers -> 4x4 register/lane transpose (v_permlane16_swap /
@@ -36,7 +36,6 @@
 #include "fft_wave.h"
 #include <algorithm>
 #include <cmath>
-#include <mutex>
 #include <cstdlib>
 
 namespace tts {
@@ -94,10 +93,7 @@ __device__ __forceinline__ void mirror_bins(const cf (&z)[16], cf (&m)[16], cf* 
 #define GL_BIN(lane, j) ((j) < 8 ? (lane) + 64 * (j) : MH - (lane) - 64 * ((j) - 8))
 // element j of a row through its two lane bases LO = row + lane, HI = row + (MH - lane): the offsets are instruction constants
 #define GL_ROW(LO, HI, j) ((j) < 8 ? (LO)[64 * (j)] : (HI)[-64 * ((j) - 8)])
-#define GL_NW 8            // waves per workgroup
-#define GL_THREADS 512
-#define NFFT 2048
-#define MH 1024            // NFFT / 2
+#define GL_THREADS 512     // GL_NW waves; NFFT, MH, GL_NW: gl_plan.h
 
 // The spectra are streamed once per iteration (1.3 GB per launch at the bench size): non-temporal accesses
 // keep them from evicting the decoder's weights and attention memory, which the second stream re-reads
@@ -195,7 +191,7 @@ size_t gl_state_bytes() { return sizeof(gl_state_t); }
 // index-mapped read path: 4 + (halo + ceil(S / hop)) / R of the frames.
 // MODE 1 writes out, straight from the overlap-add's registers, the hop samples that index i makes final.
 #define GL_NO_ITEM 0x7FFFFFFEu   // "not drawn yet" in the control word of the next item (item ids are < 2^31 - 2)
-enum { CT_OLA = 0, CT_SNEXT = 1, CT_OLB = 2 /* chain words of stages 1, 2 */, CT_SWORDS = 16 };
+enum { CT_OLA = 0, CT_SNEXT = 1, CT_OLB = 2 /* chain words of stages 1, 2 */ };   // of the CT_SWORDS control words (gl_plan.h)
 
 // NST = 2: TWO iterations per launch.  The kernel draws a constant amount of power per instruction and per byte, and
 // with the spectra streaming the chip holds a shader clock of ~1.9 GHz against ~2.3 GHz for the same arithmetic without
@@ -596,7 +592,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
         const gl_state_t* phb = x_in + (size_t)b * p.T * p.FP;
         // The next item is drawn LATE in a run (by the wave of index n_idx - 24, read by every wave in its last iteration):
         // drawn at the start, a workgroup committed itself to a second run before it knew how long the first would take, and
-        // a cut with runs of two lengths (gl_plan_stream) paired long runs with short ones at random.  Runs too short for
+        // a cut with runs of two lengths (gl_plan_items) paired long runs with short ones at random.  Runs too short for
         // that (fewer than four rounds of the waves) still draw it at the start.
         const int n_idx = run_len + NST * (halo + lag);
         const bool late = n_idx >= 4 * GL_NW;
@@ -845,292 +841,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
 #undef GLS_URGENCY
 }
 
-
-// ---- streaming form: geometry, plan, launch
-namespace {
-struct GlStreamGeom { int c_lo, n_sl, S, acc_len, halo; };
-GlStreamGeom gl_stream_geom(int win, int hop) {
-    GlStreamGeom g;
-    const int wpad = (NFFT - win) >> 1;
-    g.c_lo = wpad >> 7;
-    g.n_sl = ((wpad + win - 1) >> 7) - g.c_lo + 1;
-    g.S = 128 * g.n_sl;
-    g.acc_len = g.S - hop;
-    g.halo = (win + hop - 1) / hop - 1;
-    return g;
-}
-}  // namespace
-
-// Frames the ring holds (0: the window / hop pair does not fit).  Lower bound: what keeps an index from overwriting ring
-// positions that a slower wave may still read (see gl_stream_kernel), and the reflect-padded frames' reach; upper
-// bound: LDS.  More frames only make the lap-end read path rarer.
-int gl_stream_ring_frames(int win, int hop, int n_stage) {
-    const GlStreamGeom g = gl_stream_geom(win, hop);
-    if (g.acc_len < 0) return 0;   // hop > span: frames do not even touch (ncol = 1 with a hop beyond the padded slots)
-    const int wpad = (NFFT - win) >> 1;
-    const int lag = (g.halo + 1) * hop > 2 * (MH - wpad) ? g.halo : g.halo + 1;
-    // (n_stage rings share what the exchange buffers leave of the 160 KB)
-    const int budget = (160 * 1024 - (int)(GL_NW * EX_CPLX * sizeof(cf)) - CT_SWORDS * (int)sizeof(int)) / (int)sizeof(float) / n_stage - g.acc_len - 132;
-    int need = 9 + lag + (g.S + hop - 1) / hop + 1;
-    const int reach = (g.S + win + 2 * hop + hop - 1) / hop;   // what a reflect-padded frame reads is still in the ring, within one lap
-    need = std::max(need, std::max(reach, GL_NW));
-    const int R = std::min(budget / hop, std::max(64, need));
-    return R >= need ? R : 0;
-}
-
-size_t gl_stream_lds_bytes(const GlParams& p) {
-    const GlStreamGeom g = gl_stream_geom(p.win, p.hop);
-    return (size_t)(GL_NW * EX_CPLX) * sizeof(cf) + CT_SWORDS * sizeof(int) +
-           (size_t)(p.n_stage < 1 ? 1 : p.n_stage) * (size_t)((p.hop * p.ring_frames + g.acc_len + 128 + 3) & ~3) * sizeof(float);
-}
-
-// Work items of the streaming form.  The frames of all utterances, one after another, are dealt to the workgroups in
-// contiguous pieces of equal COST; a piece that crosses the end of an utterance is two runs (the tail of one utterance
-// and the head of the next).  What a run costs beyond its frames was measured per workgroup (round 6,
-// profiles/r06_experiment_gl_cut.txt): at three iterations per launch every stage starts halo + lag indices before the
-// next one's first frame -- 24 indices per run that carry 72 of a frame's 6 transforms, 12 frames' worth with start and
-// drain, a little less at an utterance's end where the frames outside are skipped but the reflect-padded ones take the
-// index-mapped path.  Until round 6 every utterance was cut alike into runs of one length (a multiple of the eight waves)
-// and a rest: at T = 1000, B = 64 on 224 workgroups three runs of 296 frames and one of 112, so that 192 workgroups took
-// one long run (640 us) and 32 two short ones (515 us) -- 4.7 % of the chip idle in every launch; on 256 workgroups three of
-// 256 and one of 232 (572 / 515 us, 4.5 %).  The waveform's bits do not depend on the cut (every sample is summed over the
-// frames that cover it in ascending order whatever run they are in: tests/test_gpu_audio.py).
-namespace {
-struct GlRun { int b, t0, len; };
-struct GlCutCost { double interior, edge; };   // per END of a run, in frames
-GlCutCost gl_cut_cost(int halo, int lag, int n_stage) {
-    // interior end: (halo + lag) / 2 * n_stage^2 transforms of the 2 n_stage a frame takes = (halo + lag) n_stage / 4
-    // frames (6 at 4 / 4 / 3), measured 5.5 with the start and drain of the stream; an utterance's end: about half
-    const double c = (halo + lag) * n_stage / 4.0;
-    return GlCutCost{c * (5.5 / 6.0), c * 0.5};
-}
-// deals the frames to `W` workers with at most `M` cost each; returns false if they do not fit.  workers[w] = its runs
-// lens: frames per utterance (null: T for all); no run is shorter than min(min_len, its utterance)
-bool gl_deal(const int* lens, int T, int B, int W, double M, const GlCutCost& cc, int min_len_all, std::vector<std::vector<GlRun>>& workers, double* makespan) {
-    workers.assign((size_t)W, {});
-    int b = 0, t = 0, w = 0;
-    double load = 0.0, worst = 0.0;
-    while (b < B) {
-        if (w >= W) return false;
-        const int Tb = lens ? lens[b] : T;
-        const int min_len = std::min(Tb, min_len_all);
-        const int rest = Tb - t;
-        const double left = t > 0 ? cc.interior : cc.edge;
-        const double whole = rest + left + cc.edge;                    // the rest of the utterance as one run
-        if (load + whole <= M + 1e-9) {
-            workers[w].push_back(GlRun{b, t, rest});
-            load += whole;
-            ++b; t = 0;
-            continue;
-        }
-        int len = (int)std::floor(M - load - left - cc.interior + 1e-9);   // a run that ends inside the utterance
-        if (rest - len < min_len) len = rest - min_len;                     // (never leave a sliver to the next worker)
-        if (len >= min_len) {
-            workers[w].push_back(GlRun{b, t, len});
-            load += len + left + cc.interior;
-            t += len;
-        } else if (workers[w].empty()) {
-            return false;                                                   // M is smaller than the smallest run
-        }
-        worst = std::max(worst, load);
-        ++w; load = 0.0;
-    }
-    worst = std::max(worst, load);
-    if (makespan) *makespan = worst;
-    return true;
-}
-}  // namespace
-
-int gl_plan_items(int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
-                  std::vector<int4>* items, int* slots_per_utt, int* workers_out) {
-    return gl_plan_items_ragged(nullptr, T, B, win, hop, n_workers, n_stage, force_runs, force_run_len, items, slots_per_utt, workers_out);
-}
-
-// lens == null: T frames in every utterance, and every line below does what it did for one length
-int gl_plan_items_ragged(const int* lens, int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
-                         std::vector<int4>* items, int* slots_per_utt, int* workers_out) {
-    auto len_of = [&](int b) { return lens ? lens[b] : T; };
-    long long total_frames = 0;
-    int T_min = len_of(0), T_top = len_of(0);
-    for (int b = 0; b < B; ++b) {
-        total_frames += len_of(b);
-        T_min = std::min(T_min, len_of(b));
-        T_top = std::max(T_top, len_of(b));
-    }
-    if (lens && T_min == T_top) {   // one length after all: the uniform cut, item for item
-        lens = nullptr;
-        T = T_top;
-    }
-    const int ncol = (win + hop - 1) / hop, halo = ncol - 1;
-    n_stage = n_stage < 1 ? 1 : (n_stage > 3 ? 3 : n_stage);
-    n_workers = n_workers < 1 ? 1 : n_workers;
-    const int wpad = (TTS_GL_NFFT - win) >> 1;
-    const int lag = (halo + 1) * hop > 2 * (TTS_GL_NFFT / 2 - wpad) ? halo : halo + 1;
-    std::vector<std::vector<GlRun>> workers;
-    // tests / experiments only (per-handle options "gl_runs" / "gl_run_len" behind "debug_hooks", api_handle.hip): every
-    // utterance cut alike into runs of one length and a rest, one run per list entry
-    int forced_len = 0;
-    if (force_runs >= 1 && force_runs <= T_top) forced_len = ((T_top + force_runs - 1) / force_runs + GL_NW - 1) / GL_NW * GL_NW;
-    if (force_run_len >= GL_NW) forced_len = force_run_len / GL_NW * GL_NW;
-    if (forced_len > 0) {
-        for (int t0 = 0; t0 < T_top; t0 += forced_len)
-            for (int b = 0; b < B; ++b)
-                if (t0 < len_of(b)) workers.push_back({GlRun{b, t0, std::min(forced_len, len_of(b) - t0)}});
-    } else {
-        const GlCutCost cc = gl_cut_cost(halo, lag, n_stage);
-        // the shortest run: a round of the eight waves -- down to half a round where the workgroups outnumber the rounds (one
-        // utterance on a whole chip: 250 runs of 4 frames instead of 125 of 8, Griffin-Lim 1.06 -> 0.92 ms per call at B = 1)
-        const long long per_worker = total_frames / n_workers;
-        const int min_len_all = (int)std::max<long long>(GL_NW / 2, std::min<long long>(GL_NW, per_worker));
-        const int min_len = std::min(T_min, min_len_all);
-        // the smallest makespan over a scan of the bound (the deal is greedy: a lower bound does not always give a lower result)
-        const double total = (double)total_frames + (double)B * 2 * cc.edge;
-        double lo = std::max(total / n_workers, (double)min_len + 2 * cc.edge), best_t = 1e300;
-        std::vector<std::vector<GlRun>> cand;
-        int best_step = -1;
-        for (int step = 0; step < 400; ++step) {
-            const double M = lo * (1.0 + 0.0025 * step);
-            double t = 0.0;
-            if (!gl_deal(lens, T, B, n_workers, M, cc, min_len_all, cand, &t)) continue;
-            if (t < best_t - 1e-9) { best_t = t; workers = cand; best_step = step; }
-        }
-        // a ragged batch: the bounds between the best step and the one before it, sixteen times as fine (utterance ends fall
-        // anywhere in a share, so a step of the scan -- a quarter per cent, 6 frames of a share of 2600 -- is worth looking into)
-        if (lens && best_step > 0) {
-            for (int sub = 1; sub < 16; ++sub) {
-                const double M = lo * (1.0 + 0.0025 * (best_step - 1 + sub / 16.0));
-                double t = 0.0;
-                if (!gl_deal(lens, T, B, n_workers, M, cc, min_len_all, cand, &t)) continue;
-                if (t < best_t - 1e-9) { best_t = t; workers = cand; }
-            }
-        }
-        if (workers.empty()) {   // (cannot happen: at twice the average every deal fits) one run per utterance
-            for (int b = 0; b < B; ++b) workers.push_back({GlRun{b, 0, len_of(b)}});
-        }
-    }
-    // table order = the order the persistent workgroups draw in: every worker's first run, then the runs that follow in
-    // the order their workers come free (the shortest first runs first)
-    std::vector<int> slot_of((size_t)B, 0), runs_of((size_t)B, 0);
-    for (const auto& w : workers) for (const GlRun& r : w) ++runs_of[r.b];
-    int spu = 1;
-    for (int b = 0; b < B; ++b) spu = std::max(spu, runs_of[b]);
-    std::vector<int> slot_at;   // slot of a run = its ordinal inside the utterance (by first frame)
-    auto slot_word = [&](const GlRun& r) {
-        int ord = 0;
-        for (const auto& w : workers) for (const GlRun& q : w) if (q.b == r.b && q.t0 < r.t0) ++ord;
-        const int pad = ord == runs_of[r.b] - 1 ? spu - runs_of[r.b] : 0;
-        return ord | (pad << 16);
-    };
-    // table order = the order the persistent workgroups draw in: every worker's first run, then the runs that follow in
-    // the order their workers come free (the shortest first runs first)
-    items->clear();
-    size_t depth = 0;
-    for (const auto& w : workers) depth = std::max(depth, w.size());
-    if (lens) {
-        // a ragged batch: the workers' runs differ too much in length for "level by level" to be the order they come free in (one
-        // worker is through three short utterances before another has finished its first long one, and would take that one's
-        // second run).  Behind the first runs the table is in the order of the PLANNED start of every run, frames and per-run
-        // cost counted: a worker that comes free finds the run planned for that moment -- its own, if the plan holds.
-        std::vector<std::pair<double, const GlRun*>> rest;
-        for (const auto& w : workers) {
-            double before = 0.0;
-            for (size_t d = 0; d < w.size(); ++d) {
-                if (d == 0) items->push_back(make_int4(w[d].b, w[d].t0, w[d].len, slot_word(w[d])));
-                else rest.push_back({before, &w[d]});
-                before += w[d].len + 11.0;
-            }
-        }
-        std::stable_sort(rest.begin(), rest.end(), [](const std::pair<double, const GlRun*>& a, const std::pair<double, const GlRun*>& b) { return a.first < b.first; });
-        for (const auto& e : rest) items->push_back(make_int4(e.second->b, e.second->t0, e.second->len, slot_word(*e.second)));
-        depth = 0;
-    }
-    for (size_t d = 0; d < depth; ++d) {
-        std::vector<std::pair<double, const GlRun*>> level;
-        for (const auto& w : workers) {
-            if (w.size() <= d) continue;
-            double before = 0.0;
-            for (size_t q = 0; q < d; ++q) before += w[q].len;
-            level.push_back({before, &w[d]});
-        }
-        std::stable_sort(level.begin(), level.end(), [](const std::pair<double, const GlRun*>& a, const std::pair<double, const GlRun*>& b) { return a.first < b.first; });
-        for (const auto& e : level) items->push_back(make_int4(e.second->b, e.second->t0, e.second->len, slot_word(*e.second)));
-    }
-    if (workers_out) {
-        int nw = 0;
-        for (const auto& w : workers) nw += !w.empty();
-        *workers_out = nw;
-    }
-    if (slots_per_utt) *slots_per_utt = spu;
-    return (int)items->size();
-}
-
-// The cut of a shape is made once per process and uploaded once per device (a table of 16 bytes per run).
-hipError_t gl_plan_stream(GlParams& p, int n_workers, int n_stage, int force_runs, int force_run_len, hipStream_t stream) {
-    // A table on a device: uploaded by an asynchronous copy on the stream of the call that first needs it (the host copy lives
-    // in the cache, at a stable address) -- a cut made in the middle of a run of pipelined calls must not wait for the streams to
-    // drain, as a synchronous copy does.  Calls on other streams wait for the `ready` event until it has been seen complete.
-    struct Table { int4* ptr = nullptr; hipEvent_t ready = nullptr; hipStream_t owner = nullptr; bool seen = false; };
-    struct Plan { std::vector<int4> items; int slots = 1, workers = 1; std::map<int, Table> dev; };
-    struct Pool { char* base = nullptr; size_t used = 0, size = 0; };   // tables are carved from 1 MB blocks and never freed
-    static std::map<std::vector<int>, Plan> cache;
-    static std::map<int, Pool> pools;
-    static std::mutex cache_mutex;
-    std::lock_guard<std::mutex> lock(cache_mutex);
-    // ONE cut for all launches of a call; ring_frames is set per launch (launch_gl_stream)
-    p.ring_frames = gl_stream_ring_frames(p.win, p.hop, 1);
-    const std::vector<int> key = {p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len};
-    Plan& plan = cache[key];
-    if (plan.items.empty())
-        gl_plan_items(p.T, p.B, p.win, p.hop, n_workers, n_stage, force_runs, force_run_len, &plan.items, &plan.slots, &plan.workers);
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    Table& t = plan.dev[dev];
-    if (!t.ptr) {
-        const size_t bytes = (plan.items.size() * sizeof(int4) + 255) & ~(size_t)255;
-        Pool& pool = pools[dev];
-        if (pool.used + bytes > pool.size) {
-            const size_t block = std::max<size_t>(bytes, 1u << 20);
-            void* m = nullptr;
-            if ((e = hipMalloc(&m, block)) != hipSuccess) return e;
-            pool.base = static_cast<char*>(m); pool.used = 0; pool.size = block;
-        }
-        int4* d = reinterpret_cast<int4*>(pool.base + pool.used);
-        hipEvent_t ev = nullptr;
-        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(d, plan.items.data(), plan.items.size() * sizeof(int4), hipMemcpyHostToDevice, stream)) != hipSuccess ||
-            (e = hipEventRecord(ev, stream)) != hipSuccess) {
-            (void)hipEventDestroy(ev);
-            return e;
-        }
-        pool.used += bytes;
-        t.ptr = d; t.ready = ev; t.owner = stream; t.seen = false;
-    } else if (!t.seen) {
-        if (hipEventQuery(t.ready) == hipSuccess) t.seen = true;
-        else if (stream != t.owner && (e = hipStreamWaitEvent(stream, t.ready, 0)) != hipSuccess) return e;
-    }
-    p.items = t.ptr;
-    p.n_items = (int)plan.items.size();
-    p.slots_per_utt = plan.slots;
-    p.n_workers = plan.workers;
-    return hipSuccess;
-}
-
-template <int MODE, int W, int H, bool MSE, int NST = 1, bool RAG = false>
-static hipError_t gl_stream_set_attr() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<MODE, W, H, MSE, NST, false, false, RAG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess || MODE != 0) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, NST, true, false, RAG>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-// the momentum instantiations: plain, seeded (a call's first launch) and with the mse (its last); a call with momentum has at
-// least two iterations, so no launch is seeded AND asked for the mse
-template <int W, int H, bool MSE, bool SEEDED, bool RAG = false>
-static hipError_t gl_stream_set_attr_mom() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_stream_kernel<0, W, H, MSE, 1, SEEDED, true, RAG>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
+// ---- streaming form: launch (geometry and the cut of a batch into runs: gl_plan.hip)
 
 // The (window, hop) pairs the streaming kernel is instantiated for (both windows in registers, every span bound static): the
 // model's 50 ms / 12.5 ms at the reference's 22.05 kHz (1102 / 275, dataset_params.sampling_rate; audio/conversion.py:122-136)
@@ -1139,99 +850,69 @@ static hipError_t gl_stream_set_attr_mom() {
 // needed ~100 spilled registers per lane.
 bool gl_stream_instantiated(int win, int hop) { return (win == 1102 && hop == 275) || (win == 800 && hop == 200); }
 
-// RAG: the ragged instantiations (p.n_frames set) -- the same launch forms, one for one
+// THE table of launch forms: the kernel that runs (final iSTFT, with the mse, iterations per launch, seeded start, momentum),
+// null where there is none.  What is configured and what is launched are both read from it.  RAG: the ragged instantiations
+// (p.n_frames set) -- the same forms, one for one.
+typedef void (*GlStreamKernel)(GlParams);
 template <int W, int H, bool RAG>
-static hipError_t gl_stream_launch_wh(hipStream_t s, const GlParams& p, dim3 grid, size_t lds, int final_istft, int n_stage, bool mse) {
-#define GLS_LAUNCH_N(MODE, M, N)                                                                                         \
-    {                                                                                                                    \
-        if (MODE == 0 && p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, M, N, true, false, RAG>), grid, dim3(GL_THREADS), lds, s, p);   \
-        else hipLaunchKernelGGL((gl_stream_kernel<MODE, W, H, M, N, false, false, RAG>), grid, dim3(GL_THREADS), lds, s, p);        \
+static GlStreamKernel gl_stream_form_wh(bool final_istft, bool mse, int n_stage, bool seeded, bool mom) {
+    if (final_istft) return (mse || n_stage != 1 || seeded || mom) ? nullptr : &gl_stream_kernel<1, W, H, false, 1, false, false, RAG>;
+    if (mom) {
+        // one iteration per launch: plain, seeded (a call's first launch) and with the mse (its last); a call with momentum has
+        // at least two iterations, so no launch is seeded AND asked for the mse
+        if (n_stage != 1 || (mse && seeded)) return nullptr;
+        if (mse) return &gl_stream_kernel<0, W, H, true, 1, false, true, RAG>;
+        return seeded ? &gl_stream_kernel<0, W, H, false, 1, true, true, RAG> : &gl_stream_kernel<0, W, H, false, 1, false, true, RAG>;
     }
-    // the momentum form: instantiations of their own, one iteration per launch; a call without momentum never comes here
-    if (p.mom_c && !final_istft) {
-        if (mse && p.seeded) return hipErrorInvalidValue;   // (see gl_stream_set_attr_mom)
-        if (mse) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, true, 1, false, true, RAG>), grid, dim3(GL_THREADS), lds, s, p);
-        else if (p.seeded) hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, true, true, RAG>), grid, dim3(GL_THREADS), lds, s, p);
-        else hipLaunchKernelGGL((gl_stream_kernel<0, W, H, false, 1, false, true, RAG>), grid, dim3(GL_THREADS), lds, s, p);
-        return hipGetLastError();
+    if (mse)   // (the last iteration of a call, alone in its launch)
+        return n_stage != 1 ? nullptr : seeded ? &gl_stream_kernel<0, W, H, true, 1, true, false, RAG> : &gl_stream_kernel<0, W, H, true, 1, false, false, RAG>;
+    switch (n_stage) {
+        case 1: return seeded ? &gl_stream_kernel<0, W, H, false, 1, true, false, RAG> : &gl_stream_kernel<0, W, H, false, 1, false, false, RAG>;
+        case 2: return seeded ? &gl_stream_kernel<0, W, H, false, 2, true, false, RAG> : &gl_stream_kernel<0, W, H, false, 2, false, false, RAG>;
+        case 3: return seeded ? &gl_stream_kernel<0, W, H, false, 3, true, false, RAG> : &gl_stream_kernel<0, W, H, false, 3, false, false, RAG>;
     }
-    if (n_stage == 3) GLS_LAUNCH_N(0, false, 3)
-    else if (n_stage == 2) GLS_LAUNCH_N(0, false, 2)
-    else if (final_istft) GLS_LAUNCH_N(1, false, 1)
-    else if (mse) GLS_LAUNCH_N(0, true, 1)
-    else GLS_LAUNCH_N(0, false, 1)
-#undef GLS_LAUNCH_N
-    return hipGetLastError();
+    return nullptr;
+}
+static GlStreamKernel gl_stream_form(int win, int hop, bool rag, bool final_istft, bool mse, int n_stage, bool seeded, bool mom) {
+    if (win == 1102 && hop == 275)
+        return rag ? gl_stream_form_wh<1102, 275, true>(final_istft, mse, n_stage, seeded, mom) : gl_stream_form_wh<1102, 275, false>(final_istft, mse, n_stage, seeded, mom);
+    if (win == 800 && hop == 200)
+        return rag ? gl_stream_form_wh<800, 200, true>(final_istft, mse, n_stage, seeded, mom) : gl_stream_form_wh<800, 200, false>(final_istft, mse, n_stage, seeded, mom);
+    return nullptr;
 }
 
-// p.work_counter must point at a zeroed counter that no other launch uses; p planned by gl_plan_stream.
-// n_stage = 2: two iterations in this launch (phase_in -> phase_out is then TWO Griffin-Lim iterations); not for the final
-// iSTFT and not with the mse.
+// p.work_counter must point at a zeroed counter that no other launch uses; p.items: a table of gl_plan_items.
+// n_stage = 2, 3: that many iterations in this launch (phase_in -> phase_out is then SEVERAL Griffin-Lim iterations); not for
+// the final iSTFT, not with the mse and not with momentum.
 hipError_t launch_gl_stream(hipStream_t s, const GlParams& p_in, int n_cus, int final_istft, int n_stage) {
     GlParams p = p_in;
     p.n_stage = n_stage;
+    if (n_stage < 1 || n_stage > 3) return hipErrorInvalidValue;
     p.ring_frames = gl_stream_ring_frames(p.win, p.hop, n_stage);
-    if (p.ring_frames < GL_NW || n_stage < 1 || n_stage > 3 || (n_stage > 1 && (final_istft || p.mse_partial))) return hipErrorInvalidValue;
-    if (p.mom_c && !final_istft && n_stage != 1) return hipErrorInvalidValue;   // momentum: one iteration per launch
-    const size_t lds = gl_stream_lds_bytes(p);
+    if (p.ring_frames < GL_NW) return hipErrorInvalidValue;
+    if (p.n_frames && (!p.rw_edge || p.rw_E != gl_rw_edge_len(NFFT, p.win, p.hop))) return hipErrorInvalidValue;
+    // (the final iSTFT of a call with momentum is the plain one)
+    const GlStreamKernel kernel = gl_stream_form(p.win, p.hop, p.n_frames != nullptr, final_istft != 0, p.mse_partial != nullptr, n_stage,
+                                                 p.seeded != 0, p.mom_c && !final_istft);
+    if (!kernel) return hipErrorInvalidValue;
     // one workgroup per compute unit (256 registers x 8 waves), as many as the cut was made for
     const int nwg = p.n_workers > 0 && p.n_workers < n_cus ? p.n_workers : (p.n_items < n_cus ? p.n_items : n_cus);
-    const dim3 grid(nwg);
-    const bool mse = p.mse_partial != nullptr;
-    if (p.n_frames) {
-        if (!p.rw_edge || p.rw_E != gl_rw_edge_len(NFFT, p.win, p.hop)) return hipErrorInvalidValue;
-        if (p.win == 1102 && p.hop == 275) return gl_stream_launch_wh<1102, 275, true>(s, p, grid, lds, final_istft, n_stage, mse);
-        if (p.win == 800 && p.hop == 200) return gl_stream_launch_wh<800, 200, true>(s, p, grid, lds, final_istft, n_stage, mse);
-        return hipErrorInvalidValue;
-    }
-    if (p.win == 1102 && p.hop == 275) return gl_stream_launch_wh<1102, 275, false>(s, p, grid, lds, final_istft, n_stage, mse);
-    if (p.win == 800 && p.hop == 200) return gl_stream_launch_wh<800, 200, false>(s, p, grid, lds, final_istft, n_stage, mse);
-    return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kernel, dim3(nwg), dim3(GL_THREADS), gl_stream_lds_bytes(p.win, p.hop, p.ring_frames, n_stage), s, p);
+    return hipGetLastError();
 }
 
-template <int W, int H, bool RAG>
-static hipError_t gl_stream_configure_wh() {
-    hipError_t e;
-    if ((e = gl_stream_set_attr<0, W, H, true, 1, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<0, W, H, false, 1, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<0, W, H, false, 2, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<0, W, H, false, 3, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr<1, W, H, false, 1, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr_mom<W, H, false, false, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr_mom<W, H, false, true, RAG>()) != hipSuccess) return e;
-    if ((e = gl_stream_set_attr_mom<W, H, true, false, RAG>()) != hipSuccess) return e;
-    return hipSuccess;
-}
-hipError_t gl_stream_configure() {
-    hipError_t e = gl_stream_configure_wh<1102, 275, false>();
-    if (e == hipSuccess) e = gl_stream_configure_wh<800, 200, false>();
-    if (e == hipSuccess) e = gl_stream_configure_wh<1102, 275, true>();
-    if (e == hipSuccess) e = gl_stream_configure_wh<800, 200, true>();
-    return e;
-}
-
-void gl_build_wlane(const float* window, const float* rwss, int win, int hop, int T, float* out) {
-    const int wpad = (NFFT - win) / 2;
-    const int halo = (win + hop - 1) / hop - 1;
-    const int t_ref = halo < T ? halo : T - 1;   // an interior frame (all `halo` neighbours either side exist) if there is one
-    for (int c = 0; c < 16; ++c)
-        for (int e = 0; e < 2; ++e)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int nw = 2 * (lane + 64 * c) + e - wpad;
-                const bool in = nw >= 0 && nw < win;
-                const float w = in ? window[nw] * (0.5f / (float)MH) : 0.f;
-                const float rw = in ? rwss[(size_t)t_ref * hop + wpad + nw] : 0.f;
-                out[(0 * 64 + lane) * 32 + 2 * c + e] = w;
-                out[(1 * 64 + lane) * 32 + 2 * c + e] = w * rw;
+// every launch form of every instantiation may take the whole LDS budget: the table's whole domain, walked once
+static hipError_t gl_stream_configure() {
+    for (int wh = 0; wh < 2; ++wh)
+        for (int rag = 0; rag < 2; ++rag)
+            for (int i = 0; i < 16 * 3; ++i) {   // four flags and 1..3 iterations per launch
+                const bool final_istft = i & 1, mse = i & 2, seeded = i & 4, mom = i & 8;
+                const GlStreamKernel kernel = gl_stream_form(wh ? 800 : 1102, wh ? 200 : 275, rag, final_istft, mse, 1 + i / 16, seeded, mom);
+                if (!kernel) continue;
+                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GL_LDS_BUDGET);
+                if (e != hipSuccess) return e;
             }
-}
-
-static hipError_t stft_configure();
-
-// Function attributes are per device: called once per handle (on the handle's device) by api_stages.hip.
-hipError_t gl_configure() {
-    const hipError_t e = gl_stream_configure();
-    return e != hipSuccess ? e : stft_configure();
+    return hipSuccess;
 }
 
 // ------------------------------------------------------------------------------------ analysis STFT
@@ -1299,8 +980,12 @@ __global__ __launch_bounds__(GL_THREADS) void stft_kernel(const float* __restric
 }
 
 static hipError_t stft_configure() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024);
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&stft_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, GL_LDS_BUDGET);
+}
+// Function attributes are per device: called once per handle (on the handle's device) by api_stages.hip.
+hipError_t gl_configure() {
+    const hipError_t e = gl_stream_configure();
+    return e != hipSuccess ? e : stft_configure();
 }
 
 hipError_t launch_stft(hipStream_t s, const float* wav, int B, int n, int Tf, const float* window, int win, int hop,

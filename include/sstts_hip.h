@@ -289,6 +289,32 @@ int tts_griffin_lim_ragged(tts_handle_t h, const float* mag, const float* init_p
  * the finite ones, other utterances are not affected. */
 int tts_peak_normalize(tts_handle_t h, float* wav, int B, int n);
 
+/* ---- end of speech ---------------------------------------------------------------------- */
+/* silence_interval_from_spectrogram (audio/effects.py:218-233; the criterion of the TODO at tacotron/inference.py:76-78,
+ * which the reference never calls), batched, and the frame count that follows from it.
+ * spec: DEVICE [B][T][row_stride], time-major; the first F floats of a row are its data, columns F .. row_stride - 1 are never
+ * read (tts_postnet_forward's `linear` has row_stride == F; the magnitude rows of tts_synthesize are padded).  Frame t of
+ * utterance b is ACTIVE iff np.max(row) > threshold as numpy evaluates it: the comparison is strict, a row that holds a NaN
+ * anywhere is silent (np.max carries the NaN, the comparison is False), +Inf is active, a row of -Inf is silent.
+ *   last_active[b] = the largest active t, -1 when there is none (the reference's trim_end / None); DEVICE int32 [B] or NULL
+ *   n_frames[b]    = min(T, max(min_frames, last_active[b] + 1 + keep_frames));                    DEVICE int32 [B]
+ * The threshold is in the units of the buffer (tts_speech_threshold converts decibels); nothing is computed on the data, so
+ * the result is exact and the same whatever B and the utterance's place in the batch.  Two launches, asynchronous, no model
+ * needed.  TTS_ERR_INVALID, before anything is enqueued: B, T, F < 1, row_stride < F, keep_frames < 0, min_frames outside
+ * [1, T], a NaN threshold, a NULL spec or n_frames. */
+int tts_speech_frames(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride,
+                      float threshold, int keep_frames, int min_frames,
+                      int32_t* n_frames, int32_t* last_active /* may be NULL */);
+/* A threshold in decibels in the units of a spectrogram buffer, computed in double and rounded once to float.
+ * units TTS_SPEECH_NORMALIZED_DB: the network's `linear`, x = (threshold_db - ref_db) / (|ref_db| + |max_db|) + 1 (the inverse
+ * of inv_normalize_decibel, audio/conversion.py:81-102; `power` ignored); TTS_SPEECH_MAGNITUDE_POWER: the de-normalised
+ * magnitudes ** power, m = pow(pow(10, threshold_db / 20), power) (ref_db, max_db ignored).  Both maps are monotone: the
+ * comparison in either domain is the reference's comparison in dB up to the float32 rounding of the data.  Host only.
+ * TTS_ERR_INVALID: a NaN argument that is used, |ref_db| + |max_db| == 0, power <= 0, unknown units, NULL out. */
+#define TTS_SPEECH_NORMALIZED_DB 0
+#define TTS_SPEECH_MAGNITUDE_POWER 1
+int tts_speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
+
 /* ---- analysis features (audio/features.py:5-86,116-145) and dB helpers ---------------- */
 /* librosa.stft(wav, n_fft, hop, win) as linear_scale_spectrogram returns it (features.py:145):
  * centre/reflect padding, periodic hann.  wav [B*n] -> out complex64 interleaved
@@ -400,11 +426,32 @@ int tts_wait_host(tts_handle_t h, int ticket, const float** wav_host, size_t* n_
 int tts_wait_host_outputs(tts_handle_t h, int ticket, const float** linear_host, size_t* n_linear, const float** align_host,
                           size_t* n_align);
 
+/* Stop where the speech ends (the reference's TODO, tacotron/inference.py:76-78).  A setting of the HANDLE, off by default and
+ * read when a call is made (as "gl_momentum" is): with enabled != 0, tts_synthesize and tts_synthesize_host run
+ * tts_speech_frames on the call's de-normalised magnitudes behind the post-net -- threshold_db converted with the call's
+ * power (tts_speech_threshold, TTS_SPEECH_MAGNITUDE_POWER; the call's ref_db / max_db de-normalised the data), keep_frames
+ * as given, min_frames = the smallest n with hop (n - 1) > n_fft / 2 -- WAIT on the host for the B lengths (the call then
+ * returns once its post-net has run; its Griffin-Lim, and the next call's decoder beside it, are asynchronous as ever) and
+ * reconstruct every utterance from its first n_frames[b] frames alone, as tts_griffin_lim_ragged does: wav keeps its shape
+ * [B][hop (T - 1)], samples [0, hop (n_frames[b] - 1)) are utterance b and the rest of the row is 0; with peak_normalize each
+ * utterance is scaled by its own peak (the bits of tts_peak_normalize on the padded rows).  mel / alignments / linear stay
+ * full length.  Lengths that all equal T give the bits of the call with the setting off.  A call whose T is below min_frames
+ * is TTS_ERR_INVALID.  The decoder loop itself always runs n_steps steps.
+ * TTS_ERR_INVALID (the setting stays as it was): a NaN threshold_db, keep_frames < 0. */
+int tts_set_end_of_speech(tts_handle_t h, int enabled, float threshold_db, int keep_frames);
+/* The lengths of the last tts_synthesize / tts_synthesize_host call made on the handle: n_frames_host, HOST int32 [B] (B: that
+ * call's; TTS_ERR_INVALID otherwise, or when no call has been made).  All T for a call made with the setting off.  Host only:
+ * the call itself has read them. */
+int tts_synth_frames(tts_handle_t h, int32_t* n_frames_host, int B);
+/* The lengths of a tts_synthesize_host call: waits as tts_wait_host does (same ticket rules, same reports), then hands out
+ * the handle's host copy, valid as long as the ticket's waveform buffer. */
+int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, int* B);
+
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
  * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate), "features" (tts_trim_bounds, the trim of tts_plan_features and
- * tts_extract_features).
+ * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -103,6 +103,11 @@ _PROTOTYPES = {
     'tts_griffin_lim_ragged': (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_int, c_int, POINTER(c_int32), c_int, c_int,
                                        c_int, c_int, c_void_p, c_void_p]),
     'tts_peak_normalize': (c_int, [c_void_p, c_void_p, c_int, c_int]),
+    'tts_speech_frames': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p]),
+    'tts_speech_threshold': (c_int, [c_float, c_float, c_float, c_float, c_int, POINTER(c_float)]),
+    'tts_set_end_of_speech': (c_int, [c_void_p, c_int, c_float, c_int]),
+    'tts_synth_frames': (c_int, [c_void_p, POINTER(c_int32), c_int]),
+    'tts_wait_host_frames': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -247,6 +252,50 @@ class _MomentumScope(object):
         return False
 
 
+def stop_at_silence_setting(stop_at_silence):
+    """``stop_at_silence`` of the synthesis calls -- None (off) or ``(threshold_db, keep_frames)`` -- as a checked tuple
+    ``(float, int)`` or None.  ValueError, raised before a handle is touched, for anything else: a NaN threshold, a negative
+    or non-integral keep_frames (tts_set_end_of_speech refuses the same)."""
+    if stop_at_silence is None:
+        return None
+    try:
+        threshold_db, keep_frames = stop_at_silence
+    except (TypeError, ValueError):
+        raise ValueError('stop_at_silence must be None or (threshold_db, keep_frames), got {!r}'.format(stop_at_silence))
+    threshold_db = float(threshold_db)
+    if threshold_db != threshold_db:
+        raise ValueError('stop_at_silence: threshold_db is NaN')
+    if int(keep_frames) != keep_frames or keep_frames < 0:
+        raise ValueError('stop_at_silence: keep_frames must be an integer >= 0, got {!r}'.format(keep_frames))
+    return threshold_db, int(keep_frames)
+
+
+def silence_keep_frames(keep_samples, hop_length):
+    """Whole frames that cover ``keep_samples`` samples of audio (the caller's ms_to_samples of its milliseconds): rounded up."""
+    if not keep_samples >= 0 or hop_length < 1:
+        raise ValueError('the audio kept behind the speech must be >= 0 samples, got {!r} (hop {!r})'.format(keep_samples, hop_length))
+    return -(-int(keep_samples) // int(hop_length))
+
+
+class _EndOfSpeechScope(object):
+    """End-of-speech stopping switched on for the calls made inside the block and put back afterwards, as _MomentumScope
+    does for the momentum; None: the handle's setting as it stands."""
+
+    def __init__(self, engine, stop_at_silence):
+        self.engine = engine
+        self.value = stop_at_silence_setting(stop_at_silence)
+
+    def __enter__(self):
+        self.saved = self.engine._end_of_speech
+        if self.value is not None:
+            self.engine.set_end_of_speech(True, *self.value)
+
+    def __exit__(self, *exc):
+        if self.engine._end_of_speech != self.saved:
+            self.engine.set_end_of_speech(*self.saved)
+        return False
+
+
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
@@ -292,6 +341,7 @@ class Engine(object):
         self.device_id = int(device_id)
         self._staging = {}
         self._gl_momentum = 0   # the handle's "gl_momentum" (the C ABI has no getter: set_option keeps it)
+        self._end_of_speech = (False, 0.0, 0)   # ... and its end-of-speech setting (set_end_of_speech keeps it)
         if stream is not None:
             self._check(self.lib.tts_set_stream(self.handle, c_void_p(stream)))
 
@@ -325,6 +375,11 @@ class Engine(object):
         self._check(self.lib.tts_set_option(self.handle, key.encode(), int(value)))
         if key == 'gl_momentum':
             self._gl_momentum = int(value)
+
+    def set_end_of_speech(self, enabled, threshold_db=0.0, keep_frames=0):
+        """tts_set_end_of_speech: the handle's setting, read by every synthesize / synthesize_host call made after it."""
+        self._check(self.lib.tts_set_end_of_speech(self.handle, 1 if enabled else 0, float(threshold_db), int(keep_frames)))
+        self._end_of_speech = (bool(enabled), float(threshold_db), int(keep_frames))
 
     def synchronize(self):
         self._check(self.lib.tts_synchronize(self.handle))
@@ -559,10 +614,65 @@ class Engine(object):
         self._check(self.lib.tts_peak_normalize(self.handle, wav.data_ptr(), B, n))
         return wav
 
+    def speech_threshold(self, threshold_db, ref_db, max_db, power=None):
+        """tts_speech_threshold: ``threshold_db`` in the units of a spectrogram buffer, computed in double and rounded once
+        to float32.  ``power`` None: normalised dB, the units of the network's ``linear`` -- (threshold_db - ref_db) /
+        (|ref_db| + |max_db|) + 1; otherwise the units of the de-normalised magnitudes ** power --
+        pow(pow(10, threshold_db / 20), power)."""
+        out = c_float()
+        rc = self.lib.tts_speech_threshold(float(threshold_db), float(ref_db), float(max_db),
+                                           1.0 if power is None else float(power), 0 if power is None else 1, byref(out))
+        if rc != TTS_OK:
+            raise ValueError('speech_threshold({!r}, {!r}, {!r}, {!r}): a NaN, a zero dB range or power <= 0'.format(
+                threshold_db, ref_db, max_db, power))
+        return np.float32(out.value)
+
+    def speech_frames(self, spec, threshold, keep_frames=0, min_frames=1, row_stride=None):
+        """tts_speech_frames on ``spec`` (B, T, F), time-major -- a host array or a device buffer.  ``row_stride`` (>= F):
+        the rows of the buffer are that many floats apart and only the first F of each are data.  A device buffer is then
+        B * T * row_stride floats of which (B, T, F) is the logical shape; a host array may be the view ``a[:, :, :F]`` of a
+        contiguous (B, T, row_stride) float32 array, which is uploaded as it is, padding included -- any other host array is
+        uploaded with NaN in the padding columns (they never reach a result).
+
+        Returns device int32 arrays ``(n_frames, last_active)`` of B entries: frame t is active iff np.max(spec[b, t]) >
+        ``threshold`` (strict; a row that holds a NaN is silent), last_active = the last active frame or -1, n_frames =
+        min(T, max(min_frames, last_active + 1 + keep_frames)).  ``threshold`` is in the units of ``spec``
+        (:meth:`speech_threshold`)."""
+        if len(spec.shape) != 3:
+            raise ValueError('speech_frames: spec must be (B, T, F), got shape {}'.format(tuple(spec.shape)))
+        B, T, F = (int(d) for d in spec.shape)
+        stride = F if row_stride is None else int(row_stride)
+        if not _is_device(spec) and stride > F:
+            base = spec.base if isinstance(spec, np.ndarray) else None
+            if (isinstance(base, np.ndarray) and base.shape == (B, T, stride) and base.dtype == np.float32 and
+                    base.flags['C_CONTIGUOUS'] and spec.ctypes.data == base.ctypes.data):
+                spec = base
+            else:
+                padded = np.full((B, T, stride), np.nan, dtype=np.float32)
+                padded[:, :, :F] = spec
+                spec = padded
+        p_spec, _k = self._in(spec, np.float32)
+        n_frames = self.empty((max(B, 1),), np.int32)
+        last = self.empty((max(B, 1),), np.int32)
+        try:
+            self._check(self.lib.tts_speech_frames(self.handle, p_spec, B, T, F, stride, float(threshold), int(keep_frames),
+                                                   int(min_frames), n_frames.data_ptr(), last.data_ptr()))
+        except Exception:   # (a refusal: nothing was enqueued, the outputs go back at once)
+            n_frames.free()
+            last.free()
+            raise
+        return n_frames, last
+
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
-                   momentum=None):
+                   momentum=None, stop_at_silence=None):
+        """``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
+        (tts_set_end_of_speech): every utterance is reconstructed from its frames up to the last one whose loudest bin is
+        above ``threshold_db``, plus ``keep_frames``; ``wav`` keeps its shape, row b holds hop (n_frames[b] - 1) samples
+        followed by zeros.  The result of a call made with stopping on (here or by ``set_end_of_speech``) carries ``n_frames``,
+        the int32 host array of the B lengths; ``synth_frames`` returns them for any call."""
         scope = _MomentumScope(self, momentum)   # (as in griffin_lim)
+        eos = _EndOfSpeechScope(self, stop_at_silence)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         F = 1 + self.cfg.n_fft // 2
@@ -584,27 +694,41 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope:
+        with scope, eos:
+            stopping = self._end_of_speech[0]
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
                                                 ali.data_ptr() if ali is not None else None,
                                                 lin.data_ptr() if lin is not None else None))
-        return dict(wav=wav, mel=mel, alignments=ali, linear=lin)
+        out = dict(wav=wav, mel=mel, alignments=ali, linear=lin)
+        if stopping:
+            out['n_frames'] = self.synth_frames(B)
+        return out
+
+    def synth_frames(self, B):
+        """tts_synth_frames: the B frame counts (int32 host array) of the last ``synthesize`` / ``synthesize_host`` call made
+        on the handle -- all T for a call made without end-of-speech stopping."""
+        n_frames = np.zeros(int(B), dtype=np.int32)
+        self._check(self.lib.tts_synth_frames(self.handle, n_frames.ctypes.data_as(POINTER(c_int32)), int(B)))
+        return n_frames
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
-                        peak_normalize=True, want_linear=False, want_alignments=False, momentum=None):
+                        peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
-        ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs)."""
+        ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
+        ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
+        has run)."""
         scope = _MomentumScope(self, momentum)
+        eos = _EndOfSpeechScope(self, stop_at_silence)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed, 1 if peak_normalize else 0,
                             (1 if want_linear else 0) | (2 if want_alignments else 0))
         t = c_int(-1)
-        with scope:
+        with scope, eos:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes = getattr(self, '_host_shapes', {})
         self._host_shapes[t.value] = (B, hop_length * (n_steps * self.cfg.reduction - 1))
@@ -626,6 +750,16 @@ class Engine(object):
             lin = None if lin is None else lin.copy()
             ali = None if ali is None else ali.copy()
         return lin, ali
+
+    def wait_host_frames(self, ticket):
+        """The B frame counts (int32, a copy) of a ``synthesize_host`` call: tts_wait_host_frames.  Waits like ``wait_host``
+        and does not consume the ticket; all T for a call made without ``stop_at_silence``."""
+        p = c_void_p()
+        n = c_int(0)
+        self._check(self.lib.tts_wait_host_frames(self.handle, int(ticket), byref(p), byref(n)))
+        if not n.value:
+            return np.zeros(0, dtype=np.int32)
+        return np.ctypeslib.as_array(ctypes.cast(p, POINTER(c_int32)), shape=(n.value,)).copy()
 
     def wait_host(self, ticket, copy=True):
         """Waveforms (B, hop*(T-1)) float32 of a ``synthesize_host`` call.  ``copy=False`` returns a view of the library's

@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -645,6 +645,7 @@ int tts_destroy(tts_handle_t h) {
     if (h->an.window) hipFree(h->an.window);
     if (h->an.mel_wt) hipFree(h->an.mel_wt);
     feat_release(h);
+    if (h->eos.pinned) hipHostFree(h->eos.pinned);
     if (h->an.flag) hipFree(h->an.flag);
     for (auto& kv : h->glg.tw) hipFree(kv.second);
     if (h->glg.window) hipFree(h->glg.window);
@@ -680,6 +681,27 @@ int tts_set_stream(tts_handle_t h, void* s) {
         HIPCHK(h, hipStreamCreate(&h->stream));
         h->own_stream = true;
     }
+    return TTS_OK;
+}
+
+
+int tts_set_end_of_speech(tts_handle_t h, int enabled, float threshold_db, int keep_frames) {
+    if (!h) return TTS_ERR_INVALID;
+    if (threshold_db != threshold_db) return fail(h, TTS_ERR_INVALID, "set_end_of_speech: threshold_db is NaN");
+    if (keep_frames < 0) return fail(h, TTS_ERR_INVALID, "set_end_of_speech: keep_frames < 0");
+    h->eos.enabled = enabled ? 1 : 0;
+    h->eos.threshold_db = threshold_db;
+    h->eos.keep_frames = keep_frames;
+    return TTS_OK;
+}
+
+
+int tts_synth_frames(tts_handle_t h, int32_t* n_frames_host, int B) {
+    if (!h || !n_frames_host) return TTS_ERR_INVALID;
+    if (h->eos.last.empty()) return fail(h, TTS_ERR_INVALID, "synth_frames: no tts_synthesize call has been made on this handle");
+    if (B != (int)h->eos.last.size())
+        return fail(h, TTS_ERR_INVALID, "synth_frames: the last call had " + std::to_string(h->eos.last.size()) + " utterances");
+    std::copy(h->eos.last.begin(), h->eos.last.end(), n_frames_host);
     return TTS_OK;
 }
 

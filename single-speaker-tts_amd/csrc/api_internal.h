@@ -54,7 +54,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -235,6 +235,7 @@ struct HostIo {
     // optional outputs of a host call (tts_synth_params_t::host_outputs): linear spectrograms and alignments
     StagedBuf<float> lin[3], ali[3];
     size_t n_lin[3] = {0, 0, 0}, n_ali[3] = {0, 0, 0};
+    std::vector<int32_t> frames[3];   // the lengths of this set's call (tts_wait_host_frames): all T without end-of-speech stopping
     bool failed[3] = {false, false, false};   // this set's call ended on a decoder timeout: EVERY wait on its ticket fails
     int* status_pinned = nullptr;   // [3][2]: the persistent decoder's sticky status word ([.][1]) as it stood behind
                                     // each call's download
@@ -384,9 +385,21 @@ struct tts_handle_s {
     // tables made for them -- kept while the next call asks for the same
     struct {
         std::vector<int> tab_key;
-        int* lens = nullptr;       // [B] device (workspace "gl.rag_lens")
+        const int* lens = nullptr; // [B] device (workspace "gl.rag_lens", or the caller's: gl_rag_tables)
         float* rw = nullptr;       // streaming [B][2][rw_E], general [B][n_fft + hop (T_max - 1)] (workspace "gl.rag_rw")
     } rag;
+
+    // end-of-speech stopping (tts_set_end_of_speech): the setting, the lengths a call's detection leaves on the device
+    // (workspace "eos.frames": one buffer -- the detection and the Griffin-Lim launches that read it follow each other on the
+    // main stream, call after call), the pinned words the host reads them from, and the last call's lengths
+    struct {
+        int enabled = 0;
+        float threshold_db = 0.f;
+        int keep_frames = 0;
+        int32_t* pinned = nullptr;
+        int pinned_room = 0;
+        std::vector<int32_t> last;
+    } eos;
 
     // analysis-side tables (STFT window, mel basis)
     struct {
@@ -500,12 +513,17 @@ bool gl_is_streaming(int n_fft, int win, int hop);
 int glg_twiddles(tts_handle_t h, int n_fft, const float2** out);
 int glg_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
 // a ragged batch: host lengths [B] (T is then T_max); null everywhere = one length
-int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames = nullptr);
+// d_frames: the same lengths, already in device memory (null: they are uploaded)
+int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames = nullptr, const int* d_frames = nullptr);
 int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
 // the cut of p's batch (T, B, win, hop; n_frames: host lengths of a ragged batch or null) for launches of n_stage iterations on
 // n_workers workgroups, from the handle's store: sets p.items / n_items / slots_per_utt / n_workers for launches on h->stream
 int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len);
-int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr);
+int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr, const int* d_frames = nullptr);
+// end of speech (speech_end.hip / api_stages.hip)
+int speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
+int speech_min_frames(int n_fft, int hop);   // the smallest n with hop (n - 1) > n_fft / 2
+int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int keep_frames, int min_frames, int32_t* n_frames, int32_t* last_active);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);
 int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memory);

@@ -57,9 +57,16 @@ struct SynthCall {
     int parity = 0;
     bool enc_ahead_cfg = false;
     bool mom_grows = false;      // this call allocates (or grows) the momentum buffer
+    bool eos_grows = false;      // ... or a buffer of end-of-speech stopping
     bool pipelined = false;
     int* hold_flag = nullptr;    // synth_order_front: the sleepers' flag, where sleepers hold compute units for this call
     std::optional<GemmGroup> proj;   // synth_front: the decoder's output projection, left to the main stream
+    // end-of-speech stopping (tts_set_end_of_speech), as the handle's setting stood when the call was made: the threshold in the
+    // units of `magi`, the frames kept behind the last active one, the shortest utterance Griffin-Lim takes
+    bool eos = false;
+    float eos_thr = 0.f;
+    int eos_keep = 0, eos_min = 1;
+    int32_t* d_frames = nullptr;   // the lengths on the device (workspace "eos.frames")
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -138,14 +145,37 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "gl.mom", float2, (size_t)B * T * FP, gl_mc);
         (void)gl_mc;
     }
+    if (k.eos) {
+        // the detection's row flags and lengths, the ragged Griffin-Lim's window sum-square tables (gl_rag_tables asks for the same
+        // size and finds them in place) and the pinned words the host reads the lengths from: nothing grows in mid-call
+        const size_t rw_row = k.gl_streaming ? 2 * (size_t)gl_rw_edge_len(c.n_fft, sp->win_length, sp->hop_length)
+                                             : (size_t)c.n_fft + (size_t)sp->hop_length * (T - 1);
+        // (the setting switched on between two calls of a shape: a buffer that is new or grows -- a larger stand-alone ragged
+        //  call may have left a smaller one -- makes this call unpipelined, as the momentum buffer does)
+        k.eos_grows = h->ws["eos.active"].bytes < (size_t)B * T || h->ws["eos.frames"].bytes < (size_t)B * sizeof(int32_t) ||
+                      h->ws["gl.rag_rw"].bytes < (size_t)B * rw_row * sizeof(float) || h->eos.pinned_room < B;
+        WS(h, "eos.active", unsigned char, (size_t)B * T, eos_act);
+        WS(h, "eos.frames", int32_t, (size_t)B, eos_fr);
+        (void)eos_act;
+        k.d_frames = eos_fr;
+        WS(h, "gl.rag_rw", float, (size_t)B * rw_row, eos_rw);
+        (void)eos_rw;
+        if (h->eos.pinned_room < B) {   // (read behind a synchronisation inside the call that filled it: never in flight here)
+            if (h->eos.pinned) HIPCHK(h, hipHostFree(h->eos.pinned));
+            h->eos.pinned = nullptr;
+            h->eos.pinned_room = 0;
+            HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->eos.pinned), (size_t)B * sizeof(int32_t), hipHostMallocDefault));
+            h->eos.pinned_room = B;
+        }
+    }
     k.phase_pair[0] = reinterpret_cast<float2*>(parity ? gph0o : gph0e);
     k.phase_pair[1] = reinterpret_cast<float2*>(parity ? gph1o : gph1e);
     // Pipelined only while the library owns its stream (inputs on a borrowed stream may still be in flight) and
     // from the second call of a shape on: the first call of a new (B, Ts, n_steps) grows the workspaces, which
     // synchronises every stream -- under the CU reservation that would park the host on the sleepers' 100 ms bound.
     // (the momentum option switched on between two calls of a shape: its buffer is new, and this call is unpipelined like the
-    //  first of a shape)
-    const bool same_shape = pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps && !k.mom_grows;
+    //  first of a shape; likewise the end-of-speech setting and its buffers)
+    const bool same_shape = pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps && !k.mom_grows && !k.eos_grows;
     pl.syn_shape[0] = B; pl.syn_shape[1] = Ts; pl.syn_shape[2] = sp->n_steps;
     // (a borrowed stream is pipelined only on request, pipeline = 2: the caller then vouches that the inputs of a call
     //  are complete when it is made -- the library cannot tell them from the previous call's work on that stream)
@@ -290,6 +320,28 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
     return TTS_OK;
 }
 
+// Step 5a, end-of-speech stopping: the lengths of this call's utterances, from its magnitudes on the main stream to h->eos.last.
+// The HOST waits here for the post-net.  Everything this call puts on the front and encoder streams has been enqueued by now,
+// and the call returns as soon as the lengths are read and its Griffin-Lim is enqueued: the next call's encoder and decoder,
+// enqueued by that call, run beside this call's Griffin-Lim as they do without the wait.  What the wait costs (1.0 ms per
+// batch at 64 x 1000 frames, profiles/eos.txt) is mostly WHEN the next call gets made: its encoder starts beside the first
+// Griffin-Lim launches instead of beside this post-net; the detection is 0.06 ms, the read-back and the enqueue a launch gap.
+static int synth_lengths(tts_handle_t h, SynthCall& k) {
+    const int B = k.B, T = k.T;
+    int rc = speech_frames_impl(h, k.magi, B, T, k.F, k.FP, k.eos_thr, k.eos_keep, k.eos_min, k.d_frames, nullptr);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->eos.pinned, k.d_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // (what the launches below are cut for and index with: checked again on this side)
+    for (int b = 0; b < B; ++b)
+        if (h->eos.pinned[b] < k.eos_min || h->eos.pinned[b] > T)
+            return fail(h, TTS_ERR_HIP, "synthesize: the end-of-speech detection returned " + std::to_string(h->eos.pinned[b]) +
+                                            " frames for utterance " + std::to_string(b) + ", outside [" + std::to_string(k.eos_min) +
+                                            ", " + std::to_string(T) + "]");
+    h->eos.last.assign(h->eos.pinned, h->eos.pinned + B);
+    return TTS_OK;
+}
+
 // Step 5: the main stream takes over behind the front stream -- the decoder's output projection, post-net and Griffin-Lim.
 static int synth_main(tts_handle_t h, SynthCall& k) {
     auto& pl = h->pl;
@@ -320,14 +372,28 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     if (db_flag && (rc = denorm_flag_read(h))) return rc;   // as the reference: no waveform for such a spectrogram
     // (also for an unpipelined call between pipelined ones: its buffers are the same ones)
     if (pl.front) HIPCHK(h, pl.post_done[parity].record(h->stream));
-    const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, T, sp->n_iter) : -1;
+    // the lengths: all T without end-of-speech stopping -- and a call that stops nowhere IS the uniform call
+    const int32_t* n_frames = nullptr;
+    int T_model = T;   // (gl_wide_from's model counts frames: a ragged batch is as long as its mean length)
+    if (k.eos) {
+        if ((rc = synth_lengths(h, k))) return rc;
+        long long sum = 0;
+        for (int b = 0; b < B; ++b) sum += h->eos.last[b];
+        if (sum != (long long)B * T) {
+            n_frames = h->eos.last.data();
+            T_model = (int)((sum + B - 1) / B);
+        }
+    } else {
+        h->eos.last.assign((size_t)B, T);
+    }
+    const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
     if (k.gl_streaming)
         rc = gl_run(h, k.magi, k.init_phase, sp->seed, B, T, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav, nullptr,
-                    sp->peak_normalize != 0, k.pipelined, k.phase_pair, phase_on_front, wide_from);
+                    sp->peak_normalize != 0, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, n_frames ? k.d_frames : nullptr);
     else
         rc = gl_run_generic(h, k.magi, k.init_phase, sp->seed, B, T, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav,
-                            nullptr, sp->peak_normalize != 0);
+                            nullptr, sp->peak_normalize != 0, n_frames, n_frames ? k.d_frames : nullptr);
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
 }
@@ -348,6 +414,15 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
     if (k.gl_streaming && (rc = gl_prepare(h, k.T, sp->win_length, sp->hop_length, c.n_fft))) return rc;
     if (!k.gl_streaming && (sp->win_length < 2 || sp->win_length > c.n_fft || sp->hop_length < 1))
         return fail(h, TTS_ERR_INVALID, "synthesize: need 2 <= win_length <= n_fft, hop_length >= 1");
+    if (h->eos.enabled) {   // (the setting is read here, once: refusals come before anything is enqueued)
+        k.eos = true;
+        k.eos_keep = h->eos.keep_frames;
+        k.eos_min = speech_min_frames(c.n_fft, sp->hop_length);
+        if (k.T < k.eos_min)
+            return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs at least " + std::to_string(k.eos_min) + " frames (hop (n - 1) > n_fft / 2)");
+        if (speech_threshold(h->eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
+            return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
+    }
     if ((rc = synth_workspaces(h, k))) return rc;
     if (k.pipelined && (rc = synth_streams(h))) return rc;
     hipStream_t enc_on = nullptr;
@@ -438,6 +513,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     if (want_ali) HIPCHK(h, hipMemcpyAsync(io.ali[par].pinned, io.ali[par].dev, n_ali * sizeof(float), hipMemcpyDeviceToHost, io.out));
     io.n_lin[par] = n_lin;
     io.n_ali[par] = n_ali;
+    io.frames[par] = h->eos.last;   // (the call has read them: synth_main)
     // the sticky status words of the persistent kernels travel with the waveforms (tts_wait_host must not wait for
     // anything but this call: a stream synchronisation there would wait for the NEXT call's download as well)
     io.status_pinned[2 * par] = io.status_pinned[2 * par + 1] = 0;
@@ -495,6 +571,19 @@ int tts_wait_host_outputs(tts_handle_t h, int ticket, const float** linear_host,
     if (n_linear) *n_linear = io.n_lin[par];
     if (align_host) *align_host = io.n_ali[par] ? io.ali[par].pinned : nullptr;
     if (n_align) *n_align = io.n_ali[par];
+    return TTS_OK;
+}
+
+
+int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, int* B) {
+    DeviceScope dev_scope(h);
+    if (!h || !n_frames) return TTS_ERR_INVALID;
+    const float* wav = nullptr;
+    const int rc = tts_wait_host(h, ticket, &wav, nullptr);   // same event, same checks (ticket range, decoder status)
+    if (rc) return rc;
+    const auto& f = h->hio.frames[ticket % 3];
+    *n_frames = f.data();
+    if (B) *B = (int)f.size();
     return TTS_OK;
 }
 

@@ -300,10 +300,22 @@ static void gl_rwss_edges(const std::vector<double>& wd, int n_fft, int hop, int
 
 // Uploads the lengths and the window sum-square tables of a ragged batch (h->rag.lens / rw) unless the last call's are the same.
 // streaming: [B][2][E] edge tables; general kernels: a whole row of n_fft + hop (T_max - 1) per utterance, made for its length.
-static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_max, int win, int hop, int n_fft, bool streaming) {
+// d_frames: the lengths are in device memory already (tts_synthesize: what its detection kernel left, which the host has read
+// and checked) -- the kernels read them there and only the tables, which the host has to compute, go up.
+// The uploads are synchronous copies into ONE buffer per handle, behind a synchronisation of h->stream.  That is enough under
+// the call pipeline too: the only readers of the lengths and tables are Griffin-Lim launches, and those of every call are
+// enqueued on the main stream (h->stream here) -- the front and encoder streams run encoders, decoders and the phase
+// initialisation of the whole padded batch, which takes no lengths.  Once the main stream is drained no reader is left.
+static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_max, int win, int hop, int n_fft, bool streaming,
+                         const int* d_frames = nullptr) {
     const int E = gl_rw_edge_len(n_fft, win, hop);
     const size_t row = streaming ? 2 * (size_t)E : (size_t)n_fft + (size_t)hop * (T_max - 1);
-    WS(h, "gl.rag_lens", int, (size_t)B, d_lens);
+    const int* d_lens = d_frames;
+    int* own_lens = nullptr;
+    if (!d_frames) {
+        WS(h, "gl.rag_lens", int, (size_t)B, lens_ws);
+        d_lens = own_lens = lens_ws;
+    }
     WS(h, "gl.rag_rw", float, (size_t)B * row, d_rw);
     std::vector<int> key = {streaming ? 1 : 0, n_fft, win, hop, T_max, B};
     key.insert(key.end(), n_frames, n_frames + B);
@@ -332,7 +344,7 @@ static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_m
     }
     r.tab_key.clear();
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (an earlier call may still read the tables)
-    HIPCHK(h, hipMemcpy(d_lens, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    if (own_lens) HIPCHK(h, hipMemcpy(own_lens, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(h, hipMemcpy(d_rw, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     r.lens = d_lens; r.rw = d_rw; r.tab_key = key;
     return TTS_OK;
@@ -416,7 +428,7 @@ int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers,
 
 // mag_int: [B][T][Fp] (Fp = gl_fp(n_fft)); init_ft: reference-layout U[0,1) numbers or null (then the seed)
 int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win,
-                   int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames) {
+                   int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames, const int* d_frames) {
     if (T < 1) return fail(h, TTS_ERR_INVALID, "griffin_lim: T >= 1");
     if ((long long)hop * (T - 1) <= n_fft / 2)
         return fail(h, TTS_ERR_INVALID, "griffin_lim: signal shorter than n_fft/2 (reflect padding undefined)");
@@ -426,8 +438,7 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
     const int* d_lens = nullptr;
     const float* rwss = h->glg.rwss;
     if (n_frames) {
-        if (peak_normalize) return fail(h, TTS_ERR_INVALID, "griffin_lim: no peak normalisation of a ragged batch");
-        if ((rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, false))) return rc;
+        if ((rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, false, d_frames))) return rc;
         d_lens = h->rag.lens;
         rwss = h->rag.rw;
     }
@@ -464,6 +475,7 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
         ProfScope ps(h, ST_GL_FINAL, 2);
         HIPCHK(h, launch_glg_istft(h->stream, mag_int, ph, h->glg.window, rwss, tw, frames, wav, B, T, Fp, n_fft, win, hop, d_lens));
     }
+    // (a ragged batch: the tail of a row is 0 -- glg_istft writes it -- and stays 0; the peak is the utterance's own)
     if (peak_normalize) HIPCHK(h, launch_peak_normalize(h->stream, wav, B, L));
     return TTS_OK;
 }
@@ -515,15 +527,13 @@ int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft) {
 int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter,
            int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize,
            bool under_reservation, float2* const* phase_pair, bool phase_ready,
-           int wide_from, const int32_t* n_frames) {
+           int wide_from, const int32_t* n_frames, const int* d_frames) {
     int rc = gl_prepare(h, T, win, hop, n_fft);
     if (rc) return rc;
-    // a ragged batch (T is T_max): the lengths and every utterance's own window sum-square ends, on the device
-    if (n_frames) {
-        if (peak_normalize || under_reservation || phase_pair)
-            return fail(h, TTS_ERR_INVALID, "griffin_lim: a ragged batch is a stand-alone call without peak normalisation");
-        if ((rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, true))) return rc;
-    }
+    // a ragged batch (T is T_max): the lengths and every utterance's own window sum-square ends, on the device.  Under the
+    // call pipeline as well: both cuts are made for the lengths, the phasor codes of the caller's pair cover the whole padded
+    // batch (written on the front stream without lengths: a superset of what the ragged launches read)
+    if (n_frames && (rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, true, d_frames))) return rc;
     const int F = 1 + n_fft / 2, FP = TTS_GL_FP;
     float2 *ph0, *ph1;
     if (phase_pair) {
@@ -578,8 +588,18 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     GlParams pw = p;
     const bool two_cuts = held > 0 && wide_from >= 0 && n_cus - held > 16 &&
                           !(h->debug_hooks && (h->gl_runs || h->gl_run_len));
-    if (two_cuts && (rc = gl_plan(h, pw, n_frames, n_cus, per_launch, 0, 0))) return rc;
-    const int nchunks = std::max(p.slots_per_utt, pw.slots_per_utt);
+    // A ragged batch under the pipeline (tts_synthesize with end-of-speech stopping) has new lengths in every call, so both
+    // cuts are planned in the call -- on the host, behind the wait for the lengths, while the main stream is idle.  Its wide
+    // cut is therefore planned where its first launch comes up: the narrow launches are enqueued by then and the planner
+    // runs beside them.  (The partials' workspace is sized for any cut: no run is shorter than half a round of the waves.)
+    bool wide_planned = !(two_cuts && n_frames);
+    if (two_cuts && wide_planned && (rc = gl_plan(h, pw, n_frames, n_cus, per_launch, 0, 0))) return rc;
+    auto plan_wide = [&]() -> int {
+        if (wide_planned) return TTS_OK;
+        wide_planned = true;
+        return gl_plan(h, pw, n_frames, n_cus, per_launch, 0, 0);
+    };
+    const int nchunks = wide_planned ? std::max(p.slots_per_utt, pw.slots_per_utt) : std::max(p.slots_per_utt, T / (GL_NW / 2) + 1);
     // (with momentum the squared error is kept per frame: gl_stream_kernel, MOM)
     WS(h, "gl.mse_partial", float, (size_t)B * ((p.mom_c && mse) ? std::max(nchunks, T) : nchunks), msep);
     // One zeroed work counter per launch (the persistent workgroups draw their item ids from it): slots of a ring that is
@@ -616,6 +636,7 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
             const int left = n_iter - (mse ? 1 : 0) - it;   // iterations that may share a launch
             const int n_stage = left >= per_launch ? per_launch : (left >= 1 ? left : 1);
             const bool wide = two_cuts && launch_idx >= wide_from;
+            if (wide && (rc = plan_wide())) return rc;
             GlParams& q = wide ? pw : p;
             q.phase_in = cur;
             q.phase_out = nxt;
@@ -645,6 +666,7 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     {
         ProfScope ps(h, ST_GL_FINAL, 1);
         const bool wide = two_cuts && launch_idx >= wide_from;
+        if (wide && (rc = plan_wide())) return rc;
         GlParams& q = wide ? pw : p;
         q.seeded = 0;
         q.phase_in = cur;
@@ -660,6 +682,8 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     }
     // (dividing by the peak inside the final launch -- by the workgroup that finishes an utterance's last run -- was built
     //  and measured: +0.09 ms on that launch against the 0.05 ms of this kernel)
+    // (a ragged batch: an utterance's runs hold the peak of its own hop (n_frames[b] - 1) samples -- fmaxf, so a NaN sample takes
+    //  no part, as in tts_peak_normalize; the zero tail of the row is divided like the rest and stays 0)
     if (peak_normalize) HIPCHK(h, launch_peak_scale(h->stream, wav, B, hop * (T - 1), msep, peak_chunks));
     return TTS_OK;
 }

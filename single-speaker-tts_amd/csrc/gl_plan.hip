@@ -69,7 +69,7 @@ void gl_build_wlane(const float* window, const float* rwss, int win, int hop, in
 // 256 and one of 232 (572 / 515 us, 4.5 %).  The waveform's bits do not depend on the cut (every sample is summed over the
 // frames that cover it in ascending order whatever run they are in: tests/test_gpu_audio.py).
 namespace {
-struct GlRun { int b, t0, len; };
+struct GlRun { int b, t0, len, ord = 0; };   // ord: the run's ordinal inside its utterance (by first frame), set once the cut stands
 struct GlCutCost { double interior, edge; };   // per END of a run, in frames
 GlCutCost gl_cut_cost(int halo, int lag, int n_stage) {
     // interior end: (halo + lag) / 2 * n_stage^2 transforms of the 2 n_stage a frame takes = (halo + lag) n_stage / 4
@@ -79,8 +79,15 @@ GlCutCost gl_cut_cost(int halo, int lag, int n_stage) {
 }
 // deals the frames to `W` workers with at most `M` cost each; returns false if they do not fit.  workers[w] = its runs
 // lens: frames per utterance (null: T for all); no run is shorter than min(min_len, its utterance)
-bool gl_deal(const int* lens, int T, int B, int W, double M, const GlCutCost& cc, int min_len_all, std::vector<std::vector<GlRun>>& workers, double* makespan) {
-    workers.assign((size_t)W, {});
+// STORE = false: the same walk without keeping the runs -- feasibility and makespan alone, no allocation.  The scan of the
+// bound below prices its ~400 candidates this way -- and leaves one as soon as a worker's load reaches `give_up`, the best
+// makespan so far, which it then cannot beat -- and deals only the winner (a call that stops at the end of the speech
+// plans on the host while the stream that bounds the step waits: tts_synthesize, synth_main).
+template <bool STORE>
+bool gl_deal(const int* lens, int T, int B, int W, double M, const GlCutCost& cc, int min_len_all, std::vector<std::vector<GlRun>>& workers, double* makespan,
+             double give_up = 1e300) {
+    if (STORE) workers.assign((size_t)W, {});
+    bool w_empty = true;   // (workers[w].empty() of the storing form)
     int b = 0, t = 0, w = 0;
     double load = 0.0, worst = 0.0;
     while (b < B) {
@@ -91,7 +98,8 @@ bool gl_deal(const int* lens, int T, int B, int W, double M, const GlCutCost& cc
         const double left = t > 0 ? cc.interior : cc.edge;
         const double whole = rest + left + cc.edge;                    // the rest of the utterance as one run
         if (load + whole <= M + 1e-9) {
-            workers[w].push_back(GlRun{b, t, rest});
+            if (STORE) workers[w].push_back(GlRun{b, t, rest});
+            w_empty = false;
             load += whole;
             ++b; t = 0;
             continue;
@@ -99,14 +107,15 @@ bool gl_deal(const int* lens, int T, int B, int W, double M, const GlCutCost& cc
         int len = (int)std::floor(M - load - left - cc.interior + 1e-9);   // a run that ends inside the utterance
         if (rest - len < min_len) len = rest - min_len;                     // (never leave a sliver to the next worker)
         if (len >= min_len) {
-            workers[w].push_back(GlRun{b, t, len});
+            if (STORE) workers[w].push_back(GlRun{b, t, len});
             load += len + left + cc.interior;
             t += len;
-        } else if (workers[w].empty()) {
+        } else if (w_empty) {
             return false;                                                   // M is smaller than the smallest run
         }
         worst = std::max(worst, load);
-        ++w; load = 0.0;
+        if (!STORE && worst >= give_up) return false;
+        ++w; load = 0.0; w_empty = true;
     }
     worst = std::max(worst, load);
     if (makespan) *makespan = worst;
@@ -152,13 +161,14 @@ int gl_plan_items(const int* lens, int T, int B, int win, int hop, int n_workers
         // the smallest makespan over a scan of the bound (the deal is greedy: a lower bound does not always give a lower result)
         const double total = (double)total_frames + (double)B * 2 * cc.edge;
         double lo = std::max(total / n_workers, (double)min_len + 2 * cc.edge), best_t = 1e300;
-        std::vector<std::vector<GlRun>> cand;
+        std::vector<std::vector<GlRun>> none;
         int best_step = -1;
+        double best_M = 0.0;
         for (int step = 0; step < 400; ++step) {
             const double M = lo * (1.0 + 0.0025 * step);
             double t = 0.0;
-            if (!gl_deal(lens, T, B, n_workers, M, cc, min_len_all, cand, &t)) continue;
-            if (t < best_t - 1e-9) { best_t = t; workers = cand; best_step = step; }
+            if (!gl_deal<false>(lens, T, B, n_workers, M, cc, min_len_all, none, &t, best_t - 1e-9)) continue;
+            if (t < best_t - 1e-9) { best_t = t; best_M = M; best_step = step; }
         }
         // a ragged batch: the bounds between the best step and the one before it, sixteen times as fine (utterance ends fall
         // anywhere in a share, so a step of the scan -- a quarter per cent, 6 frames of a share of 2600 -- is worth looking into)
@@ -166,21 +176,22 @@ int gl_plan_items(const int* lens, int T, int B, int win, int hop, int n_workers
             for (int sub = 1; sub < 16; ++sub) {
                 const double M = lo * (1.0 + 0.0025 * (best_step - 1 + sub / 16.0));
                 double t = 0.0;
-                if (!gl_deal(lens, T, B, n_workers, M, cc, min_len_all, cand, &t)) continue;
-                if (t < best_t - 1e-9) { best_t = t; workers = cand; }
+                if (!gl_deal<false>(lens, T, B, n_workers, M, cc, min_len_all, none, &t, best_t - 1e-9)) continue;
+                if (t < best_t - 1e-9) { best_t = t; best_M = M; }
             }
         }
+        if (best_step >= 0) gl_deal<true>(lens, T, B, n_workers, best_M, cc, min_len_all, workers, nullptr);   // the winner's runs
         if (workers.empty()) {   // (cannot happen: at twice the average every deal fits) one run per utterance
             for (int b = 0; b < B; ++b) workers.push_back({GlRun{b, 0, len_of(b)}});
         }
     }
     std::vector<int> runs_of((size_t)B, 0);
-    for (const auto& w : workers) for (const GlRun& r : w) ++runs_of[r.b];
+    // (every path above makes an utterance's runs in ascending order of their first frame: the ordinal is a count)
+    for (auto& w : workers) for (GlRun& r : w) r.ord = runs_of[r.b]++;
     int spu = 1;
     for (int b = 0; b < B; ++b) spu = std::max(spu, runs_of[b]);
     auto item_of = [&](const GlRun& r) {   // slot of a run = its ordinal inside the utterance (by first frame)
-        int ord = 0;
-        for (const auto& w : workers) for (const GlRun& q : w) if (q.b == r.b && q.t0 < r.t0) ++ord;
+        const int ord = r.ord;
         const int pad = ord == runs_of[r.b] - 1 ? spu - runs_of[r.b] : 0;
         return GlItem{r.b, r.t0, r.len, ord | (pad << 16)};
     };

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .._hip import momentum_thousandths
+from .._hip import momentum_thousandths, silence_keep_frames, stop_at_silence_setting
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
 from .model import Mode, Tacotron
@@ -51,13 +51,36 @@ def inference(model, sentences, n_steps=None):
     return [mag[b] for b in range(mag.shape[0])]
 
 
+SILENCE_KEEP_MS = 100.0   # audio kept behind the last frame above the threshold where a caller does not say
+
+
+def stop_setting(hp, stop_at_silence_db, silence_keep_ms):
+    """``stop_at_silence_db`` / ``silence_keep_ms`` of the helpers below as the engine's ``stop_at_silence``: None, or
+    (threshold_db, keep_frames) with the milliseconds converted by ms_to_samples and the hop (rounded up to whole frames).
+    The threshold is in de-normalised dB, the units ``audio.effects.silence_interval_from_spectrogram`` compares in."""
+    if stop_at_silence_db is None:
+        return None
+    if not float(silence_keep_ms) >= 0.0:
+        raise ValueError('silence_keep_ms must be >= 0, got {!r}'.format(silence_keep_ms))
+    hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
+    return stop_at_silence_setting((stop_at_silence_db, silence_keep_frames(ms_to_samples(float(silence_keep_ms), hp.sampling_rate), hop)))
+
+
+def cut_waveforms(wavs, n_frames, hop):
+    """Row b of a padded batch cut to its own hop (n_frames[b] - 1) samples: a list of arrays."""
+    return [wavs[b][:hop * (int(n_frames[b]) - 1)] for b in range(len(n_frames))]
+
+
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
-                     momentum=0.0):
+                     momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  ``momentum``: fast Griffin-Lim
-    (audio.synthesis), 0.0 = the reference's loop."""
+    (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind
+    its last frame above that many dB (the reference's TODO at :76-78); the result is then a LIST of B waveforms, each cut to
+    its own length."""
     momentum_thousandths(momentum)   # ValueError outside [0, 1), before the engine is touched
     hp = model.hparams
+    stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
     win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
@@ -65,12 +88,15 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     out = model.engine.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), S, loader.mel_mag_ref_db,
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
-                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum)
+                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum,
+                                  stop_at_silence=stop)
+    if stop is not None:
+        return cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop)
     return out['wav'].to_host()
 
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
-                      want_alignments=False, momentum=0.0):
+                      want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -80,9 +106,12 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     With ``want_linear`` / ``want_alignments`` every item is a tuple ``(wavs, linear, alignments)``: the normalised linear
     spectrograms (B, T, 1025) -- what ``model.output_linear_spec`` is, the thing the reference's ``inference()`` fetches
     (:75-92) -- and the alignments (n_steps, B, T_sent) of the same call, downloaded behind the waveforms (None where not
-    asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop."""
+    asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
+    ``stop_at_silence_db`` / ``silence_keep_ms`` as in ``synthesize_batch``: the waveforms of a batch are then a list of B
+    arrays (views of the pinned rows unless ``copy``), each cut to its own length."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before the engine is touched)
     hp = model.hparams
+    stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
     win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
@@ -91,11 +120,17 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     eng = model.engine
     extra = want_linear or want_alignments
 
+    def waveforms(ticket):
+        if stop is None:
+            return eng.wait_host(ticket, copy=copy)
+        n_frames = eng.wait_host_frames(ticket)
+        return cut_waveforms(eng.wait_host(ticket, copy=copy), n_frames, win_hop)
+
     def collect(ticket):
         if not extra:
-            return eng.wait_host(ticket, copy=copy)
+            return waveforms(ticket)
         lin, ali = eng.wait_host_outputs(ticket, copy=copy)
-        return eng.wait_host(ticket, copy=copy), lin, ali
+        return waveforms(ticket), lin, ali
 
     # three batches in flight (the library's three buffer sets): the encoder of batch k + 2 runs one inter-Griffin-Lim gap
     # ahead of its decoder, which follows the decoder of batch k + 1 without a pause, beside the Griffin-Lim of batch k
@@ -103,7 +138,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     for k, ids in enumerate(batches):
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
-                                           want_alignments=want_alignments, momentum=momentum))
+                                           want_alignments=want_alignments, momentum=momentum, stop_at_silence=stop))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -133,12 +168,15 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
         yield specs, wavs
 
 
-def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0):
+def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
+                         stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
-    float32 WAV, save_wav(norm=True)).  Returns the list of waveforms."""
+    float32 WAV, save_wav(norm=True)).  Returns the list of waveforms.  With ``stop_at_silence_db`` every file ends
+    ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames."""
     momentum_thousandths(momentum)
+    stop_setting(model_params, stop_at_silence_db, silence_keep_ms)   # (ValueError before anything is loaded)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -150,7 +188,8 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     max_length = max(sequence_lengths)
     sentences = np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum)
+    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum,
+                            stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms)
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, True)
     return list(wavs)
@@ -173,12 +212,16 @@ def main(argv=None):
         python -m single-speaker-tts_amd.tacotron.inference [--synthesis-file F] [--synthesis-dir D]
                                                             [--weights CKPT | --synthetic-weights SEED]
                                                             [--momentum ALPHA]
+                                                            [--stop-at-silence DB [--silence-keep-ms MS]]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
-    variables); ``--synthetic-weights`` a seed for the synthetic initialiser (no checkpoint ships with the reference)."""
+    variables); ``--synthetic-weights`` a seed for the synthetic initialiser (no checkpoint ships with the reference).
+    ``--stop-at-silence DB``: every wav ends ``--silence-keep-ms`` behind the last frame whose loudest bin is above DB
+    (de-normalised dB, e.g. -40) instead of after the full max_iterations frames: files of different lengths."""
     args = parse_args(argv)
     momentum_thousandths(args.momentum)
+    stop_setting(model_params, args.stop_at_silence, args.silence_keep_ms)
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -195,7 +238,8 @@ def main(argv=None):
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
     wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                momentum=args.momentum)
+                                momentum=args.momentum, stop_at_silence_db=args.stop_at_silence,
+                                silence_keep_ms=args.silence_keep_ms)
     for i in range(len(wavs)):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
@@ -213,6 +257,10 @@ def parse_args(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='seed of the Griffin-Lim start phases (the reference draws them unseeded)')
     ap.add_argument('--momentum', type=float, default=0.0,
                     help='fast Griffin-Lim momentum in [0, 1); 0 (default) is the reference\'s loop, librosa uses 0.99')
+    ap.add_argument('--stop-at-silence', type=float, default=None, metavar='DB',
+                    help='end every utterance behind its last frame above DB decibels (e.g. -40); default: all max_iterations frames')
+    ap.add_argument('--silence-keep-ms', type=float, default=SILENCE_KEEP_MS, metavar='MS',
+                    help='audio kept behind that frame (default {:g} ms)'.format(SILENCE_KEEP_MS))
     return ap.parse_args(argv)
 
 

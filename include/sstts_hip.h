@@ -315,6 +315,36 @@ int tts_speech_frames(tts_handle_t h, const float* spec, int B, int T, int F, in
 #define TTS_SPEECH_MAGNITUDE_POWER 1
 int tts_speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
 
+/* ---- speaking rate ---------------------------------------------------------------------- */
+/* time_stretch (audio/effects.py:46-88) as far as it reaches Griffin-Lim: the reference runs librosa 0.6 phase_vocoder(stft, rate)
+ * and keeps np.abs of the result, and |mag exp(1j phase)| = mag -- what is left of the vocoder is a linear blend of neighbouring
+ * magnitude frames.  For one utterance of n frames x[:, 0 .. n - 1] and a rate r (> 1 faster, < 1 slower):
+ *   n_out   = ceil(n / r), the division and the ceil in double = len(np.arange(0, n, r, dtype=float))
+ *   s = k r, i = (int)s, a = s - floor(s);   y[:, k] = (float)((1 - a) x[:, i] + a x[:, i + 1])          for k < n_out
+ * in double, every operation rounded on its own (no FMA) and the result rounded once to float32; columns i >= n are the vocoder's
+ * zero padding: they read as 0.0 and are never fetched.  The blend is always evaluated: 0 * NaN and 0 * Inf stay NaN as in numpy,
+ * a NaN is never turned into a finite number, and every element that does not depend on it keeps the bits of a clean run.
+ * Against the reference's whole path (phases carried, complex64, np.abs) the result differs by at most 2^-22 relative. */
+/* Host only: *out = n_out above.  TTS_ERR_INVALID: n_frames < 1, a rate that is not finite or outside [0.25, 4], NULL out. */
+int tts_stretched_frames(int n_frames, double rate, int* out);
+/* The blend on magnitudes in the reference layout, as tts_griffin_lim and tts_stft_magnitude hold them: mag [B][F][T] ->
+ * out [B][F][T_out].  n_frames: HOST int32 [B], the frames of each utterance, or NULL (all T); columns t >= n_frames[b] of mag are
+ * never read.  Row b of out holds stretched_frames(n_frames[b]) blended frames and 0 from there to T_out.  64-bit indexing, no
+ * atomics: an utterance's output is the same bits whatever B is and wherever it sits in the batch.  rate 1.0 is legal and returns
+ * the input bits for finite data.  One launch per 64 utterances, asynchronous (the lengths travel in the launch: nothing is
+ * uploaded), no model needed; profile stage "stretch".  TTS_ERR_INVALID, before anything is enqueued: a rate that is not finite
+ * or outside [0.25, 4], B, F or T < 1, an n_frames[b] outside [1, T], T_out smaller than the largest stretched length, a NULL
+ * mag or out. */
+int tts_stretch_magnitudes(tts_handle_t h, const float* mag, int B, int F, int T, const int32_t* n_frames, double rate, int T_out,
+                           float* out);
+/* The same arithmetic (the same bits for the same values) on time-major padded rows, the layout of tts_speech_frames and of the
+ * call pipeline: spec [B][T][row_stride] -> out [B][T_out][row_stride], the first F floats of a row are its data, columns
+ * F .. row_stride - 1 are neither read nor written.  Rows t >= n_frames[b] of spec are never read.  With row_stride % 4 == 0 and
+ * both buffers 16-byte aligned the rows move in 16-byte accesses.  Arguments and refusals as tts_stretch_magnitudes, and
+ * row_stride < F. */
+int tts_stretch_rows(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, const int32_t* n_frames, double rate,
+                     int T_out, float* out);
+
 /* ---- analysis features (audio/features.py:5-86,116-145) and dB helpers ---------------- */
 /* librosa.stft(wav, n_fft, hop, win) as linear_scale_spectrogram returns it (features.py:145):
  * centre/reflect padding, periodic hann.  wav [B*n] -> out complex64 interleaved
@@ -447,11 +477,28 @@ int tts_synth_frames(tts_handle_t h, int32_t* n_frames_host, int B);
  * the handle's host copy, valid as long as the ticket's waveform buffer. */
 int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, int* B);
 
+/* The speaking rate of synthesis (the reference's time_stretch, audio/effects.py:46-88, moved ahead of the one Griffin-Lim a call
+ * runs anyway).  A setting of the HANDLE, read when a call is made (as "gl_momentum" and tts_set_end_of_speech are); the default
+ * 1.0 means off, and off is the call as it always was, launch for launch.  With another rate tts_synthesize and
+ * tts_synthesize_host time-stretch the call's de-normalised magnitude ** power rows behind the post-net (tts_stretch_rows: exactly
+ * what Griffin-Lim consumes -- the blend acts on |S| ** power, the array the call has) and reconstruct from
+ * T' = tts_stretched_frames(T, rate) frames: wav is [B][hop (T' - 1)], an init_phase argument [B][F][T'], the pinned buffers of
+ * the host form are sized for T'; mel, alignments and linear keep their full length T.  The host form stays bit-identical to
+ * tts_synthesize + tts_memcpy_d2h; "gl_momentum" composes unchanged.  With end-of-speech stopping the lengths n[b] are detected on
+ * the unstretched magnitudes as ever and become n'[b] = min(T', max(min_frames, tts_stretched_frames(n[b], rate))) -- frames this
+ * adds are the vocoder's zeros; the ragged Griffin-Lim and the per-utterance peak normalisation run on them as they do today,
+ * and tts_synth_frames / tts_wait_host_frames report n'[b], the frames the waveform holds (all T' without stopping).  A call
+ * with T' < min_frames (hop (n - 1) > n_fft / 2) is TTS_ERR_INVALID.  The first call after the rate changed is not pipelined
+ * (its buffers grow).  The decoder loop always runs n_steps steps.
+ * TTS_ERR_INVALID (the setting stays as it was): a rate that is not finite or outside [0.25, 4]. */
+int tts_set_speaking_rate(tts_handle_t h, double rate);
+
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
  * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate), "features" (tts_trim_bounds, the trim of tts_plan_features and
- * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize).
+ * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize),
+ * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -108,6 +108,10 @@ _PROTOTYPES = {
     'tts_set_end_of_speech': (c_int, [c_void_p, c_int, c_float, c_int]),
     'tts_synth_frames': (c_int, [c_void_p, POINTER(c_int32), c_int]),
     'tts_wait_host_frames': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
+    'tts_stretched_frames': (c_int, [c_int, ctypes.c_double, POINTER(c_int)]),
+    'tts_stretch_magnitudes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_void_p]),
+    'tts_stretch_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_void_p]),
+    'tts_set_speaking_rate': (c_int, [c_void_p, ctypes.c_double]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -296,6 +300,68 @@ class _EndOfSpeechScope(object):
         return False
 
 
+SPEAKING_RATE_MIN, SPEAKING_RATE_MAX = 0.25, 4.0
+
+
+def speaking_rate_value(rate):
+    """``speaking_rate`` of the synthesis and stretch calls as a checked float (None stays None: the handle's setting as it
+    stands).  ValueError, raised before a handle is touched, for what tts_set_speaking_rate refuses: a rate that is not
+    finite or lies outside [0.25, 4]."""
+    if rate is None:
+        return None
+    try:
+        r = float(rate)
+    except (TypeError, ValueError):
+        raise ValueError('speaking_rate must be a number in [0.25, 4], got {!r}'.format(rate))
+    if not SPEAKING_RATE_MIN <= r <= SPEAKING_RATE_MAX:   # (a NaN fails both comparisons)
+        raise ValueError('speaking_rate must be finite and lie in [0.25, 4], got {!r}'.format(rate))
+    return r
+
+
+def stretched_frames(n, rate):
+    """tts_stretched_frames on the host: ceil(n / rate) in double = len(np.arange(0, n, rate, dtype=float)), the frames a
+    time-stretched utterance of ``n`` frames has (reference audio/effects.py:46-88, librosa 0.6 phase_vocoder)."""
+    r = speaking_rate_value(rate)
+    if r is None or int(n) != n or n < 1:
+        raise ValueError('stretched_frames: need n >= 1 frames and a rate, got {!r}, {!r}'.format(n, rate))
+    return int(np.ceil(np.float64(int(n)) / np.float64(r)))
+
+
+def stretch_frame_counts(n_frames, B, T):
+    """The ``n_frames`` argument of a stretch call as a contiguous int32 array of B lengths in 1 .. T (None stays None: all
+    T), checked as tts_stretch_magnitudes checks them -- ValueError, raised before a handle is touched."""
+    if n_frames is None:
+        return None
+    nf = np.asarray(n_frames)
+    if nf.shape != (B,):
+        raise ValueError('n_frames: shape {} for a batch of {}'.format(nf.shape, B))
+    if nf.dtype.kind not in 'iu':
+        raise ValueError('n_frames must be integers, got {}'.format(nf.dtype))
+    for b, n in enumerate(nf.tolist()):
+        if not 1 <= n <= T:
+            raise ValueError('n_frames[{}] = {} is not in 1 .. T = {}'.format(b, n, T))
+    return np.ascontiguousarray(nf, dtype=np.int32)
+
+
+class _SpeakingRateScope(object):
+    """The speaking rate set for the calls made inside the block and put back afterwards, as _EndOfSpeechScope does for its
+    setting; None: the handle's rate as it stands."""
+
+    def __init__(self, engine, rate):
+        self.engine = engine
+        self.value = speaking_rate_value(rate)
+
+    def __enter__(self):
+        self.saved = self.engine._speaking_rate
+        if self.value is not None and self.value != self.saved:
+            self.engine.set_speaking_rate(self.value)
+
+    def __exit__(self, *exc):
+        if self.engine._speaking_rate != self.saved:
+            self.engine.set_speaking_rate(self.saved)
+        return False
+
+
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
@@ -342,6 +408,7 @@ class Engine(object):
         self._staging = {}
         self._gl_momentum = 0   # the handle's "gl_momentum" (the C ABI has no getter: set_option keeps it)
         self._end_of_speech = (False, 0.0, 0)   # ... and its end-of-speech setting (set_end_of_speech keeps it)
+        self._speaking_rate = 1.0               # ... and its speaking rate (set_speaking_rate keeps it)
         if stream is not None:
             self._check(self.lib.tts_set_stream(self.handle, c_void_p(stream)))
 
@@ -380,6 +447,15 @@ class Engine(object):
         """tts_set_end_of_speech: the handle's setting, read by every synthesize / synthesize_host call made after it."""
         self._check(self.lib.tts_set_end_of_speech(self.handle, 1 if enabled else 0, float(threshold_db), int(keep_frames)))
         self._end_of_speech = (bool(enabled), float(threshold_db), int(keep_frames))
+
+    def set_speaking_rate(self, rate):
+        """tts_set_speaking_rate: the handle's setting, read by every synthesize / synthesize_host call made after it;
+        1.0 = off."""
+        r = speaking_rate_value(rate)
+        if r is None:
+            raise ValueError('set_speaking_rate: a rate in [0.25, 4] is needed')
+        self._check(self.lib.tts_set_speaking_rate(self.handle, r))
+        self._speaking_rate = r
 
     def synchronize(self):
         self._check(self.lib.tts_synchronize(self.handle))
@@ -663,25 +739,140 @@ class Engine(object):
             raise
         return n_frames, last
 
+    # ------------------------------------------------------------------ speaking rate
+    def stretched_frames(self, n, rate):
+        """tts_stretched_frames: the frames of a time-stretched utterance of ``n`` frames, ceil(n / rate)."""
+        r = speaking_rate_value(rate)
+        if r is None or int(n) != n or n < 1:
+            raise ValueError('stretched_frames: need n >= 1 frames and a rate, got {!r}, {!r}'.format(n, rate))
+        out = c_int(0)
+        rc = self.lib.tts_stretched_frames(int(n), r, byref(out))
+        if rc != TTS_OK:
+            raise ValueError('stretched_frames({!r}, {!r}) refused'.format(n, rate))
+        return out.value
+
+    def _stretch_args(self, what, shape, T, rate, n_frames, T_out):
+        r = speaking_rate_value(rate)
+        if r is None:
+            raise ValueError('{}: a rate in [0.25, 4] is needed'.format(what))
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError('{}: a non-empty 3-D array is needed, got shape {}'.format(what, tuple(shape)))
+        B = int(shape[0])
+        nf = stretch_frame_counts(n_frames, B, T)
+        longest = max(stretched_frames(n, r) for n in (nf.tolist() if nf is not None else [T]))
+        T_out = longest if T_out is None else int(T_out)
+        if T_out < longest:
+            raise ValueError('{}: T_out = {} is smaller than the longest stretched utterance, {} frames'.format(what, T_out, longest))
+        return r, nf, T_out
+
+    def stretch_magnitudes(self, mag, rate, n_frames=None, T_out=None):
+        """tts_stretch_magnitudes: the reference's time_stretch as far as it reaches Griffin-Lim (audio/effects.py:46-88) on
+        ``mag`` (B, F, T), the layout of ``griffin_lim`` and ``stft_magnitude`` -- a host array or a device buffer.  Frame k
+        of the result is the blend (1 - a) mag[:, :, i] + a mag[:, :, i + 1] at s = k rate, i = int(s), a = s - i, in double,
+        rounded once.  ``n_frames``: B lengths (host integers) -- columns at or behind them are never read; None: all T.
+        Returns a device array (B, F, T_out): utterance b holds ceil(n_frames[b] / rate) frames and zeros behind them;
+        ``T_out`` None: the longest stretched length."""
+        r, nf, T_out = self._stretch_args('stretch_magnitudes', mag.shape, int(mag.shape[2]) if len(mag.shape) == 3 else 0,
+                                          rate, n_frames, T_out)
+        B, F, T = (int(d) for d in mag.shape)
+        p_mag, _k = self._in(mag, np.float32)
+        out = self.empty((B, F, T_out))
+        try:
+            self._check(self.lib.tts_stretch_magnitudes(self.handle, p_mag, B, F, T,
+                                                        nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None, r, T_out,
+                                                        out.data_ptr()))
+        except Exception:   # (a refusal: nothing was enqueued)
+            out.free()
+            raise
+        return out
+
+    def stretch_rows(self, spec, rate, n_frames=None, T_out=None, row_stride=None):
+        """tts_stretch_rows: the same blend on time-major rows, ``spec`` (B, T, F) as ``speech_frames`` takes it (``row_stride``
+        as there: a device buffer of B * T * row_stride floats, or the view ``a[:, :, :F]`` of a contiguous host array; any
+        other host array is uploaded with NaN in the padding columns).  Returns a device array (B, T_out, row_stride) of which
+        the first F columns are written."""
+        r, nf, T_out = self._stretch_args('stretch_rows', spec.shape, int(spec.shape[1]) if len(spec.shape) == 3 else 0,
+                                          rate, n_frames, T_out)
+        B, T, F = (int(d) for d in spec.shape)
+        stride = F if row_stride is None else int(row_stride)
+        if stride < F:
+            raise ValueError('stretch_rows: row_stride {} < F = {}'.format(stride, F))
+        if not _is_device(spec) and stride > F:
+            base = spec.base if isinstance(spec, np.ndarray) else None
+            if (isinstance(base, np.ndarray) and base.shape == (B, T, stride) and base.dtype == np.float32 and
+                    base.flags['C_CONTIGUOUS'] and spec.ctypes.data == base.ctypes.data):
+                spec = base
+            else:
+                padded = np.full((B, T, stride), np.nan, dtype=np.float32)
+                padded[:, :, :F] = spec
+                spec = padded
+        p_spec, _k = self._in(spec, np.float32)
+        out = self.empty((B, T_out, stride))
+        try:
+            self._check(self.lib.tts_stretch_rows(self.handle, p_spec, B, T, F, stride,
+                                                  nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None, r, T_out,
+                                                  out.data_ptr()))
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def time_stretch(self, wavs, rate, n_iter=25, seed=0, want_magnitudes=False):
+        """The reference's waveform effect time_stretch (audio/effects.py:46-88) as a composition of existing calls:
+        ``stft_magnitude`` (n_fft 1024, window 1024, hop 256, power 1), ``stretch_magnitudes``, then ``griffin_lim`` in the
+        general kernels from phases drawn from ``seed`` (the reference draws np.random.rand).  ``wavs``: one waveform (n,) or
+        a uniform batch (B, n), host or device.  Returns a device array (B, 256 (T' - 1)) -- (256 (T' - 1),) for one waveform
+        given as a 1-D host array -- with T' = ceil((1 + n // 256) / rate); with ``want_magnitudes`` also the device arrays
+        (|STFT|, stretched) that were fed through."""
+        r = speaking_rate_value(rate)
+        if r is None:
+            raise ValueError('time_stretch: a rate in [0.25, 4] is needed')
+        single = len(wavs.shape) == 1
+        if single and not _is_device(wavs):
+            wavs = np.asarray(wavs).reshape(1, -1)
+        if len(wavs.shape) != 2:
+            raise ValueError('time_stretch: one waveform (n,) or a uniform batch (B, n) is needed, got shape {}'.format(tuple(wavs.shape)))
+        n_fft, win, hop = 1024, 1024, 256
+        T = 1 + int(wavs.shape[1]) // hop
+        if hop * (stretched_frames(T, r) - 1) <= n_fft // 2:
+            raise ValueError('time_stretch: {} samples at rate {} leave a signal shorter than n_fft / 2'.format(int(wavs.shape[1]), r))
+        mag = self.stft_magnitude(wavs, n_fft, win, hop, 1.0)
+        st = self.stretch_magnitudes(mag, r)
+        wav, _mse = self.griffin_lim(st, int(n_iter), win, hop, n_fft, seed=seed, want_mse=False)
+        if single:
+            wav.shape = (wav.shape[1],)
+        return (wav, mag, st) if want_magnitudes else wav
+
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
-                   momentum=None, stop_at_silence=None):
+                   momentum=None, stop_at_silence=None, speaking_rate=None):
         """``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
         (tts_set_end_of_speech): every utterance is reconstructed from its frames up to the last one whose loudest bin is
         above ``threshold_db``, plus ``keep_frames``; ``wav`` keeps its shape, row b holds hop (n_frames[b] - 1) samples
         followed by zeros.  The result of a call made with stopping on (here or by ``set_end_of_speech``) carries ``n_frames``,
-        the int32 host array of the B lengths; ``synth_frames`` returns them for any call."""
+        the int32 host array of the B lengths; ``synth_frames`` returns them for any call.
+        ``speaking_rate``: None (the handle's setting, 1.0 unless ``set_speaking_rate`` changed it) or a rate in [0.25, 4]
+        for this call (tts_set_speaking_rate): the magnitudes are time-stretched ahead of Griffin-Lim, ``wav`` is
+        (B, hop (T' - 1)) and ``init_phase`` (B, F, T') with T' = ``stretched_frames(T, rate)``; mel, alignments and linear
+        keep their length T."""
         scope = _MomentumScope(self, momentum)   # (as in griffin_lim)
         eos = _EndOfSpeechScope(self, stop_at_silence)
+        rate = _SpeakingRateScope(self, speaking_rate)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
+        r_call = self._speaking_rate if rate.value is None else rate.value
+        T_wav = T if r_call == 1.0 else stretched_frames(T, r_call)
         F = 1 + self.cfg.n_fft // 2
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed,
                             1 if peak_normalize else 0)
         self._check_ids(ids)
         p_ids, _k1 = self._in(ids, np.int32, 'ids')
         p_init, _k2 = self._in(init_phase, np.float32, 'init_phase')
-        wav = wav if wav is not None else self.empty((B, hop_length * (T - 1)))
+        if init_phase is not None and int(np.prod(init_phase.shape)) != B * F * T_wav:
+            raise ValueError('synthesize: init_phase of shape {} given, {} needed'.format(tuple(init_phase.shape), (B, F, T_wav)))
+        if wav is not None and int(np.prod(wav.shape)) != B * hop_length * (T_wav - 1):
+            raise ValueError('synthesize: wav buffer of shape {} given, {} needed'.format(tuple(wav.shape), (B, hop_length * (T_wav - 1))))
+        wav = wav if wav is not None else self.empty((B, hop_length * (T_wav - 1)))
         # want_*: False, True (a fresh buffer) or a device array of the right size to write into (no allocation in the call)
         def _out(want, shape):
             if want is None or want is False:
@@ -694,7 +885,7 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope, eos:
+        with scope, eos, rate:
             stopping = self._end_of_speech[0]
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
@@ -713,25 +904,30 @@ class Engine(object):
         return n_frames
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
-                        peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None):
+                        peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
+                        speaking_rate=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
         ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
-        has run)."""
+        has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1)))."""
         scope = _MomentumScope(self, momentum)
         eos = _EndOfSpeechScope(self, stop_at_silence)
+        rate = _SpeakingRateScope(self, speaking_rate)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed, 1 if peak_normalize else 0,
                             (1 if want_linear else 0) | (2 if want_alignments else 0))
         t = c_int(-1)
-        with scope, eos:
+        r_call = self._speaking_rate if rate.value is None else rate.value
+        T = n_steps * self.cfg.reduction
+        T_wav = T if r_call == 1.0 else stretched_frames(T, r_call)
+        with scope, eos, rate:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes = getattr(self, '_host_shapes', {})
-        self._host_shapes[t.value] = (B, hop_length * (n_steps * self.cfg.reduction - 1))
+        self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
         self._host_out_shapes = getattr(self, '_host_out_shapes', {})
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))
         return t.value

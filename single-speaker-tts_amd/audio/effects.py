@@ -1,7 +1,13 @@
 """Mirror of reference audio/effects.py: silence trimming and cropping.
 
 ``trim_silence`` is librosa.effects.trim (librosa 0.6: frame length 2048, hop 512, reference power = the loudest frame)
-computed by tts_trim_bounds on the GPU.  ``pitch_shift`` / ``time_stretch`` (resampling, phase vocoder) are out of scope."""
+computed by tts_trim_bounds on the GPU.
+
+``time_stretch`` and ``pitch_shift`` raise NotImplementedError here.  The reference's time_stretch (:46-88) is an STFT, the
+librosa phase vocoder, np.abs and Griffin-Lim; on this path that is ``Engine.time_stretch(wavs, rate)`` (device calls:
+tts_stft_magnitude, tts_stretch_magnitudes, tts_griffin_lim), and the speaking rate of synthesis is the ``speaking_rate``
+argument of the synthesis calls (tts_set_speaking_rate), which stretches the magnitudes a call already holds ahead of its one
+Griffin-Lim.  ``pitch_shift`` (:9-43) also needs librosa's resampler, which stays out of scope."""
 import numpy as np
 
 from . import default_engine

@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -692,6 +692,14 @@ int tts_set_end_of_speech(tts_handle_t h, int enabled, float threshold_db, int k
     h->eos.enabled = enabled ? 1 : 0;
     h->eos.threshold_db = threshold_db;
     h->eos.keep_frames = keep_frames;
+    return TTS_OK;
+}
+
+
+int tts_set_speaking_rate(tts_handle_t h, double rate) {
+    if (!h) return TTS_ERR_INVALID;
+    if (!(rate >= 0.25 && rate <= 4.0)) return fail(h, TTS_ERR_INVALID, "set_speaking_rate: the rate must be finite and lie in [0.25, 4]");
+    h->speaking_rate = rate;
     return TTS_OK;
 }
 

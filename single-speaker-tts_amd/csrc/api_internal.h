@@ -54,7 +54,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -198,6 +198,7 @@ struct CallPipeline {
     Signal serial_done;
     unsigned syn_calls = 0;
     int syn_shape[3] = {0, 0, 0};   // (B, Ts, n_steps) of the previous tts_synthesize call
+    int syn_tg = 0;                 // ... and the frames its Griffin-Lim reconstructed from (T, or T' with a speaking rate)
     int last_enc_ahead = -1;        // did the previous PIPELINED call run its encoder ahead on `encs` (1) or on `front` (0)?
 
     // Every stream has been synchronised (sync_all): nothing recorded so far orders anything any more
@@ -401,6 +402,9 @@ struct tts_handle_s {
         std::vector<int32_t> last;
     } eos;
 
+    // speaking rate (tts_set_speaking_rate): read when a call is made; 1.0 = off, the call then enqueues what it always did
+    double speaking_rate = 1.0;
+
     // analysis-side tables (STFT window, mel basis)
     struct {
         int win = 0;
@@ -524,6 +528,9 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
 int speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
 int speech_min_frames(int n_fft, int hop);   // the smallest n with hop (n - 1) > n_fft / 2
 int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int keep_frames, int min_frames, int32_t* n_frames, int32_t* last_active);
+// speaking rate (stretch.hip): both layouts of the time-stretch, arguments checked by the caller (stretch_plan.h)
+int stretch_impl(tts_handle_t h, const float* in, int B, int T, int F, int row_stride, bool time_major, const int32_t* n_frames, double rate,
+                 int T_out, float* out);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);
 int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memory);

@@ -1,6 +1,7 @@
 // C ABI, part 3: the call pipeline -- tts_synthesize (three calls in flight on the main, front and encoder streams, events per
 // call parity, the wide Griffin-Lim launches), its host-memory form and the tickets of tts_wait_host.
 #include "api_internal.h"
+#include "stretch_plan.h"
 
 namespace tts_api {
 
@@ -67,6 +68,13 @@ struct SynthCall {
     float eos_thr = 0.f;
     int eos_keep = 0, eos_min = 1;
     int32_t* d_frames = nullptr;   // the lengths on the device (workspace "eos.frames")
+    // speaking rate (tts_set_speaking_rate), as the handle's setting stood when the call was made.  Tg: the frames Griffin-Lim
+    // reconstructs from -- T with the setting off, else stretched_frames(T, rate) rows of `mags`, the time-stretch of `magi`
+    bool stretch = false;
+    double rate = 1.0;
+    int Tg = 0;
+    float* mags = nullptr;
+    bool st_grows = false;       // this call allocates (or grows) the stretched magnitudes
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -85,22 +93,23 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     auto& pl = h->pl;
     const tts_synth_params_t* sp = k.sp;
     const int B = k.B, Ts = k.Ts, T = k.T, FP = k.FP;
+    const int Tg = k.Tg;   // (everything of Griffin-Lim is sized for the frames it reconstructs from)
     if (!k.gl_streaming) {
         // the general kernels' tables and workspaces, sized HERE, before anything of this call is enqueued on the front or
         // encoder streams (a growing workspace synchronises every stream; gl_run_generic finds them in place)
-        if ((long long)sp->hop_length * (T - 1) <= c.n_fft / 2)
+        if ((long long)sp->hop_length * (Tg - 1) <= c.n_fft / 2)
             return fail(h, TTS_ERR_INVALID, "griffin_lim: signal shorter than n_fft/2 (reflect padding undefined)");
-        int rc = glg_prepare(h, T, sp->win_length, sp->hop_length, c.n_fft);
+        int rc = glg_prepare(h, Tg, sp->win_length, sp->hop_length, c.n_fft);
         if (rc) return rc;
         const float2* tw_unused = nullptr;
         if ((rc = glg_twiddles(h, c.n_fft, &tw_unused))) return rc;
-        WS(h, "glg.phase", float2, (size_t)B * T * FP, glg_ph);
-        WS(h, "glg.frames", float, (size_t)B * T * sp->win_length, glg_fr);
-        WS(h, "glg.mse_partial", float, (size_t)B * T, glg_ms);
+        WS(h, "glg.phase", float2, (size_t)B * Tg * FP, glg_ph);
+        WS(h, "glg.frames", float, (size_t)B * Tg * sp->win_length, glg_fr);
+        WS(h, "glg.mse_partial", float, (size_t)B * Tg, glg_ms);
         (void)glg_ph; (void)glg_fr; (void)glg_ms;
         if (h->gl_momentum > 0 && sp->n_iter > 1) {
-            k.mom_grows = h->ws["glg.mom"].bytes < (size_t)B * T * FP * sizeof(float2);
-            WS(h, "glg.mom", float2, (size_t)B * T * FP, glg_mc);
+            k.mom_grows = h->ws["glg.mom"].bytes < (size_t)B * Tg * FP * sizeof(float2);
+            WS(h, "glg.mom", float2, (size_t)B * Tg * FP, glg_mc);
             (void)glg_mc;
         }
     }
@@ -129,27 +138,34 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     }
     WS(h, "gl.mag", float, (size_t)B * T * FP, magi);
     k.magi = magi;
+    if (k.stretch) {
+        // (the setting switched on, or another rate, between two calls of a shape: this call is unpipelined, as with the
+        //  momentum buffer; same_shape below also compares Tg, which sizes the phasor codes)
+        k.st_grows = h->ws["gl.mag_st"].bytes < (size_t)B * Tg * FP * sizeof(float);
+        WS(h, "gl.mag_st", float, (size_t)B * Tg * FP, mags);
+        k.mags = mags;
+    }
     // Under the call pipeline the initial phasors of a call are written on the FRONT stream, behind its decoder (that
     // stream has slack, the main one bounds the step): the phasor-code buffers are then a pair per call parity, so that
     // the write does not wait for the previous call's Griffin-Lim.  All four are sized here, before anything is enqueued
     // (a growing workspace synchronises every stream).
     // (its own buffers, not the pair of the stand-alone tts_griffin_lim: 4 bytes per bin, the state is a phasor code)
-    WS(h, "syn.phase0.even", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph0e);
-    WS(h, "syn.phase1.even", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph1e);
-    WS(h, "syn.phase0.odd", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph0o);
-    WS(h, "syn.phase1.odd", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), gph1o);
+    WS(h, "syn.phase0.even", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph0e);
+    WS(h, "syn.phase1.even", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph1e);
+    WS(h, "syn.phase0.odd", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph0o);
+    WS(h, "syn.phase1.odd", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph1o);
     // (momentum: the previous projection, 8 bytes per bin; ONE buffer -- only Griffin-Lim launches touch it, and those of
     //  consecutive calls follow each other on the main stream)
     if (k.gl_streaming && h->gl_momentum > 0 && sp->n_iter > 1) {
-        k.mom_grows = h->ws["gl.mom"].bytes < (size_t)B * T * FP * sizeof(float2);
-        WS(h, "gl.mom", float2, (size_t)B * T * FP, gl_mc);
+        k.mom_grows = h->ws["gl.mom"].bytes < (size_t)B * Tg * FP * sizeof(float2);
+        WS(h, "gl.mom", float2, (size_t)B * Tg * FP, gl_mc);
         (void)gl_mc;
     }
     if (k.eos) {
         // the detection's row flags and lengths, the ragged Griffin-Lim's window sum-square tables (gl_rag_tables asks for the same
         // size and finds them in place) and the pinned words the host reads the lengths from: nothing grows in mid-call
         const size_t rw_row = k.gl_streaming ? 2 * (size_t)gl_rw_edge_len(c.n_fft, sp->win_length, sp->hop_length)
-                                             : (size_t)c.n_fft + (size_t)sp->hop_length * (T - 1);
+                                             : (size_t)c.n_fft + (size_t)sp->hop_length * (Tg - 1);
         // (the setting switched on between two calls of a shape: a buffer that is new or grows -- a larger stand-alone ragged
         //  call may have left a smaller one -- makes this call unpipelined, as the momentum buffer does)
         k.eos_grows = h->ws["eos.active"].bytes < (size_t)B * T || h->ws["eos.frames"].bytes < (size_t)B * sizeof(int32_t) ||
@@ -160,6 +176,11 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         k.d_frames = eos_fr;
         WS(h, "gl.rag_rw", float, (size_t)B * rw_row, eos_rw);
         (void)eos_rw;
+        if (k.stretch) {   // (the stretched lengths are the host's: the ragged Griffin-Lim uploads them, gl_rag_tables)
+            k.eos_grows = k.eos_grows || h->ws["gl.rag_lens"].bytes < (size_t)B * sizeof(int);
+            WS(h, "gl.rag_lens", int, (size_t)B, eos_lens);
+            (void)eos_lens;
+        }
         if (h->eos.pinned_room < B) {   // (read behind a synchronisation inside the call that filled it: never in flight here)
             if (h->eos.pinned) HIPCHK(h, hipHostFree(h->eos.pinned));
             h->eos.pinned = nullptr;
@@ -175,7 +196,9 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     // synchronises every stream -- under the CU reservation that would park the host on the sleepers' 100 ms bound.
     // (the momentum option switched on between two calls of a shape: its buffer is new, and this call is unpipelined like the
     //  first of a shape; likewise the end-of-speech setting and its buffers)
-    const bool same_shape = pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps && !k.mom_grows && !k.eos_grows;
+    const bool same_shape = pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps && !k.mom_grows && !k.eos_grows &&
+                            pl.syn_tg == Tg && !k.st_grows;
+    pl.syn_tg = Tg;
     pl.syn_shape[0] = B; pl.syn_shape[1] = Ts; pl.syn_shape[2] = sp->n_steps;
     // (a borrowed stream is pipelined only on request, pipeline = 2: the caller then vouches that the inputs of a call
     //  are complete when it is made -- the library cannot tell them from the previous call's work on that stream)
@@ -346,7 +369,7 @@ static int synth_lengths(tts_handle_t h, SynthCall& k) {
 static int synth_main(tts_handle_t h, SynthCall& k) {
     auto& pl = h->pl;
     const tts_synth_params_t* sp = k.sp;
-    const int B = k.B, T = k.T, parity = k.parity;
+    const int B = k.B, T = k.T, Tg = k.Tg, parity = k.parity;
     int rc = TTS_OK;
     // (a seeded start with iterations needs no initial codes at all: gl_run)
     const bool phase_on_front = k.gl_streaming && k.pipelined && sp->n_iter >= 0 && (k.init_phase != nullptr || sp->n_iter == 0);
@@ -355,7 +378,7 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
         if (phase_on_front) {
             // this parity's buffers were last used by the Griffin-Lim of the call two back
             HIPCHK(h, pl.gl_done[parity].wait(pl.front));
-            HIPCHK(h, launch_phase_init(pl.front, k.init_phase, sp->seed, k.phase_pair[0], B, k.F, T, k.FP));
+            HIPCHK(h, launch_phase_init(pl.front, k.init_phase, sp->seed, k.phase_pair[0], B, k.F, Tg, k.FP));
         }
         HIPCHK(h, pl.front_done.record(pl.front));
         HIPCHK(h, pl.front_done.wait(h->stream));
@@ -374,26 +397,41 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     if (pl.front) HIPCHK(h, pl.post_done[parity].record(h->stream));
     // the lengths: all T without end-of-speech stopping -- and a call that stops nowhere IS the uniform call
     const int32_t* n_frames = nullptr;
-    int T_model = T;   // (gl_wide_from's model counts frames: a ragged batch is as long as its mean length)
+    int T_model = Tg;   // (gl_wide_from's model counts frames: a ragged batch is as long as its mean length)
     if (k.eos) {
         if ((rc = synth_lengths(h, k))) return rc;
-        long long sum = 0;
-        for (int b = 0; b < B; ++b) sum += h->eos.last[b];
-        if (sum != (long long)B * T) {
-            n_frames = h->eos.last.data();
-            T_model = (int)((sum + B - 1) / B);
-        }
     } else {
         h->eos.last.assign((size_t)B, T);
     }
+    if (k.stretch) {
+        // The speaking rate: Griffin-Lim reconstructs from the time-stretch of this call's magnitudes (one pass, stretch.hip).
+        // Frames behind an utterance's end are not read; the lengths become min(Tg, max(min_frames, stretched_frames(n))) --
+        // whatever that adds to an utterance is the vocoder's zero padding, which the pass writes.
+        if ((rc = stretch_impl(h, k.magi, B, T, k.F, k.FP, true, k.eos ? h->eos.last.data() : nullptr, k.rate, Tg, k.mags))) return rc;
+        for (int b = 0; b < B; ++b) {
+            const long long m = std::max<long long>(k.eos_min, stretched_frames(h->eos.last[b], k.rate));
+            h->eos.last[b] = (int32_t)std::min<long long>(Tg, m);
+        }
+    }
+    if (k.eos) {
+        long long sum = 0;
+        for (int b = 0; b < B; ++b) sum += h->eos.last[b];
+        if (sum != (long long)B * Tg) {
+            n_frames = h->eos.last.data();
+            T_model = (int)((sum + B - 1) / B);
+        }
+    }
+    const float* gl_mag = k.stretch ? k.mags : k.magi;
+    // (the device's lengths are those of the detection: with a speaking rate the host's stretched ones are uploaded instead)
+    const int* d_frames = (n_frames && !k.stretch) ? k.d_frames : nullptr;
     const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
     if (k.gl_streaming)
-        rc = gl_run(h, k.magi, k.init_phase, sp->seed, B, T, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav, nullptr,
-                    sp->peak_normalize != 0, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, n_frames ? k.d_frames : nullptr);
+        rc = gl_run(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav, nullptr,
+                    sp->peak_normalize != 0, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
     else
-        rc = gl_run_generic(h, k.magi, k.init_phase, sp->seed, B, T, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav,
-                            nullptr, sp->peak_normalize != 0, n_frames, n_frames ? k.d_frames : nullptr);
+        rc = gl_run_generic(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav,
+                            nullptr, sp->peak_normalize != 0, n_frames, d_frames);
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
 }
@@ -411,13 +449,23 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
         return fail(h, TTS_ERR_UNSUPPORTED, "synthesize: n_fft must be a power of two between 256 and 4096");
     SynthCall k{ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, &host, sp->n_steps * c.reduction,
                 1 + c.n_fft / 2, gl_fp(c.n_fft), gl_is_streaming(c.n_fft, sp->win_length, sp->hop_length)};
-    if (k.gl_streaming && (rc = gl_prepare(h, k.T, sp->win_length, sp->hop_length, c.n_fft))) return rc;
+    k.Tg = k.T;
+    k.eos_min = sp->hop_length >= 1 ? speech_min_frames(c.n_fft, sp->hop_length) : 1;   // (the hop is checked below)
+    if (h->speaking_rate != 1.0) {   // (read here, once, as the end-of-speech setting below; 1.0: nothing of this call changes)
+        if (sp->hop_length < 1) return fail(h, TTS_ERR_INVALID, "synthesize: hop_length >= 1");
+        k.stretch = true;
+        k.rate = h->speaking_rate;
+        k.Tg = (int)stretched_frames(k.T, k.rate);
+        if (k.Tg < k.eos_min)
+            return fail(h, TTS_ERR_INVALID, "synthesize: the speaking rate leaves " + std::to_string(k.Tg) + " frames, Griffin-Lim needs at least " +
+                                                std::to_string(k.eos_min) + " (hop (n - 1) > n_fft / 2)");
+    }
+    if (k.gl_streaming && (rc = gl_prepare(h, k.Tg, sp->win_length, sp->hop_length, c.n_fft))) return rc;
     if (!k.gl_streaming && (sp->win_length < 2 || sp->win_length > c.n_fft || sp->hop_length < 1))
         return fail(h, TTS_ERR_INVALID, "synthesize: need 2 <= win_length <= n_fft, hop_length >= 1");
     if (h->eos.enabled) {   // (the setting is read here, once: refusals come before anything is enqueued)
         k.eos = true;
         k.eos_keep = h->eos.keep_frames;
-        k.eos_min = speech_min_frames(c.n_fft, sp->hop_length);
         if (k.T < k.eos_min)
             return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs at least " + std::to_string(k.eos_min) + " frames (hop (n - 1) > n_fft / 2)");
         if (speech_threshold(h->eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
@@ -458,8 +506,10 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
         return fail(h, TTS_ERR_INVALID, "synthesize_host: bad arguments");
     auto& io = h->hio;
     const int T = sp->n_steps * h->cfg.reduction;
+    // (with a speaking rate the waveforms have hop (T' - 1) samples: the pinned and device buffers are sized for them)
+    const long long Tg = h->speaking_rate != 1.0 ? stretched_frames(T, h->speaking_rate) : T;
     const size_t ids_bytes = (size_t)B * Ts * sizeof(int32_t);
-    const size_t n_wav = (size_t)B * sp->hop_length * (size_t)(T - 1);
+    const size_t n_wav = (size_t)B * sp->hop_length * (size_t)(Tg - 1);
     const bool want_lin = (sp->host_outputs & TTS_HOST_LINEAR) != 0, want_ali = (sp->host_outputs & TTS_HOST_ALIGNMENTS) != 0;
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;

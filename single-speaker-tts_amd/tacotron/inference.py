@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .._hip import momentum_thousandths, silence_keep_frames, stop_at_silence_setting
+from .._hip import momentum_thousandths, silence_keep_frames, speaking_rate_value, stop_at_silence_setting
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
 from .model import Mode, Tacotron
@@ -72,13 +72,16 @@ def cut_waveforms(wavs, n_frames, hop):
 
 
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
-                     momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS):
+                     momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind
     its last frame above that many dB (the reference's TODO at :76-78); the result is then a LIST of B waveforms, each cut to
-    its own length."""
+    its own length.  ``speaking_rate``: 1.0, or a rate in [0.25, 4] -- the magnitudes are time-stretched ahead of Griffin-Lim
+    (the reference's audio.effects.time_stretch, on the one reconstruction the call runs anyway): the waveforms are
+    (B, hop*(T'-1)) with T' = ceil(T / rate), ``init_phase`` is (B, F, T')."""
     momentum_thousandths(momentum)   # ValueError outside [0, 1), before the engine is touched
+    rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     hp = model.hparams
     stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
     loader = dataset_params.dataset_loader
@@ -89,14 +92,15 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
                                   init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum,
-                                  stop_at_silence=stop)
+                                  stop_at_silence=stop, speaking_rate=rate)
     if stop is not None:
         return cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop)
     return out['wav'].to_host()
 
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
-                      want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS):
+                      want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
+                      speaking_rate=1.0):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -108,8 +112,10 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     (:75-92) -- and the alignments (n_steps, B, T_sent) of the same call, downloaded behind the waveforms (None where not
     asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db`` / ``silence_keep_ms`` as in ``synthesize_batch``: the waveforms of a batch are then a list of B
-    arrays (views of the pinned rows unless ``copy``), each cut to its own length."""
+    arrays (views of the pinned rows unless ``copy``), each cut to its own length.  ``speaking_rate`` as in
+    ``synthesize_batch``."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before the engine is touched)
+    rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     hp = model.hparams
     stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
     loader = dataset_params.dataset_loader
@@ -138,7 +144,8 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     for k, ids in enumerate(batches):
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
-                                           want_alignments=want_alignments, momentum=momentum, stop_at_silence=stop))
+                                           want_alignments=want_alignments, momentum=momentum, stop_at_silence=stop,
+                                           speaking_rate=rate))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -169,14 +176,16 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
 
 
 def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
-                         stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS):
+                         stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
     float32 WAV, save_wav(norm=True)).  Returns the list of waveforms.  With ``stop_at_silence_db`` every file ends
-    ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames."""
+    ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames.
+    ``speaking_rate``: as in ``synthesize_batch`` (1.2: a fifth faster)."""
     momentum_thousandths(momentum)
     stop_setting(model_params, stop_at_silence_db, silence_keep_ms)   # (ValueError before anything is loaded)
+    speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -189,7 +198,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     sentences = np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
     wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum,
-                            stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms)
+                            stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate)
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, True)
     return list(wavs)
@@ -213,15 +222,18 @@ def main(argv=None):
                                                             [--weights CKPT | --synthetic-weights SEED]
                                                             [--momentum ALPHA]
                                                             [--stop-at-silence DB [--silence-keep-ms MS]]
+                                                            [--rate R]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
     variables); ``--synthetic-weights`` a seed for the synthetic initialiser (no checkpoint ships with the reference).
     ``--stop-at-silence DB``: every wav ends ``--silence-keep-ms`` behind the last frame whose loudest bin is above DB
-    (de-normalised dB, e.g. -40) instead of after the full max_iterations frames: files of different lengths."""
+    (de-normalised dB, e.g. -40) instead of after the full max_iterations frames: files of different lengths.
+    ``--rate R``: the speaking rate, 0.25 .. 4 (1.2: a fifth faster; default 1 = as the network speaks)."""
     args = parse_args(argv)
     momentum_thousandths(args.momentum)
     stop_setting(model_params, args.stop_at_silence, args.silence_keep_ms)
+    speaking_rate_value(args.rate)
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -239,7 +251,7 @@ def main(argv=None):
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
     wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
                                 momentum=args.momentum, stop_at_silence_db=args.stop_at_silence,
-                                silence_keep_ms=args.silence_keep_ms)
+                                silence_keep_ms=args.silence_keep_ms, speaking_rate=args.rate)
     for i in range(len(wavs)):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
@@ -261,6 +273,8 @@ def parse_args(argv=None):
                     help='end every utterance behind its last frame above DB decibels (e.g. -40); default: all max_iterations frames')
     ap.add_argument('--silence-keep-ms', type=float, default=SILENCE_KEEP_MS, metavar='MS',
                     help='audio kept behind that frame (default {:g} ms)'.format(SILENCE_KEEP_MS))
+    ap.add_argument('--rate', type=float, default=1.0, metavar='R',
+                    help='speaking rate in [0.25, 4]: the magnitudes are time-stretched ahead of Griffin-Lim (1.2: a fifth faster; default 1)')
     return ap.parse_args(argv)
 
 

@@ -8,7 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import momentum_thousandths
+from .._hip import momentum_thousandths, speaking_rate_value, stretched_frames
 from ..audio.conversion import ms_to_samples
 from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_sentence, stop_setting
 from .model import Mode, Tacotron
@@ -24,14 +24,17 @@ def pre_process_sentences(_sentences, dataset):
 
 
 def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0, stop_at_silence_db=None,
-                              silence_keep_ms=SILENCE_KEEP_MS):
+                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
     constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86); ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: every utterance is reconstructed only up to
     ``silence_keep_ms`` behind its last frame whose loudest bin is above that many dB (``Engine.speech_frames`` on the
-    normalised spectrograms, then one ragged Griffin-Lim call) and returned at its own length."""
+    normalised spectrograms, then one ragged Griffin-Lim call) and returned at its own length.  ``speaking_rate``: 1.0, or a
+    rate in [0.25, 4] -- the magnitudes are time-stretched (``Engine.stretch_magnitudes``) ahead of Griffin-Lim: T' =
+    ceil(T / rate) frames, ``init_phase`` (B, F, T'), lengths min(T', max(min_frames, ceil(n / rate)))."""
     momentum_thousandths(momentum)
     stop = stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
+    rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
     win_hop = ms_to_samples(model_params.win_hop, model_params.sampling_rate)
@@ -39,14 +42,21 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
     if spec.ndim == 2:
         spec = spec[None]
     n_frames = None
+    T = spec.shape[1]
+    min_frames = (model_params.n_fft // 2) // win_hop + 2   # the shortest signal Griffin-Lim takes: hop (n - 1) > n_fft / 2
+    if rate != 1.0 and stretched_frames(T, rate) < min_frames:
+        raise ValueError('speaking_rate {}: {} frames are left of {}, at least {} needed'.format(rate, stretched_frames(T, rate), T, min_frames))
     if stop is not None:
-        T = spec.shape[1]
-        min_frames = (model_params.n_fft // 2) // win_hop + 2   # the shortest signal Griffin-Lim takes: hop (n - 1) > n_fft / 2
         if T < min_frames:
             raise ValueError('stop_at_silence_db: spectrograms of {} frames, at least {} needed'.format(T, min_frames))
         thr = engine.speech_threshold(stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
         n_frames = engine.speech_frames(spec, thr, keep_frames=stop[1], min_frames=min_frames)[0].to_host()
     mag = engine.denorm_power(spec, loader.mel_mag_ref_db, loader.mel_mag_max_db, model_params.magnitude_power)
+    if rate != 1.0:
+        T_out = stretched_frames(T, rate)
+        mag = engine.stretch_magnitudes(mag, rate, n_frames=n_frames, T_out=T_out)
+        if n_frames is not None:
+            n_frames = np.array([min(T_out, max(min_frames, stretched_frames(int(n), rate))) for n in n_frames], np.int32)
     wav, _ = engine.griffin_lim(mag, model_params.reconstruction_iterations, win_len, win_hop, model_params.n_fft,
                                 init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_frames)
     wav = wav.to_host()
@@ -56,7 +66,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
-          silence_keep_ms=SILENCE_KEEP_MS):
+          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -66,9 +76,11 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     available: batch k is then yielded only after batch k + 2 has been pulled from the generator (the last one when the
     generator ends), which on a request-driven generator would hold every answer back by two requests.
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db`` /
-    ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech."""
+    ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech;
+    ``speaking_rate`` likewise."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
     stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
+    speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
@@ -78,11 +90,11 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
             ids = pre_process_sentences(sentences, dataset)
             spectrograms = model.run(model.output_linear_spec, {model.inp_sentences: ids})
             yield post_process_spectrograms(spectrograms, model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
-                                            silence_keep_ms=silence_keep_ms)
+                                            silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate)
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
     for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
-                                  stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms):
+                                  stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate):
         yield [wavs[b] for b in range(len(wavs))]

@@ -345,6 +345,31 @@ int tts_stretch_magnitudes(tts_handle_t h, const float* mag, int B, int F, int T
 int tts_stretch_rows(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, const int32_t* n_frames, double rate,
                      int T_out, float* out);
 
+/* ---- resampling ------------------------------------------------------------------------- */
+/* librosa 0.6 resample(..., res_type='kaiser_best') = resampy 0.2 resample_f with the 'kaiser_best' windowed sinc: the second half
+ * of pitch_shift (audio/effects.py:9-43) and what load_wav(sampling_rate=...) runs.  The filter is regenerated from resampy's
+ * published design (num_zeros 64, 512 table samples per zero crossing, Kaiser beta 14.769656459379492, rolloff
+ * 0.9475937167399596): win[j] = kaiser(2 n + 1, beta)[n + j] rolloff sinc(rolloff j / 512), j = 0 .. n = 32768, times rho for a
+ * ratio rho = target rate / source rate < 1; delta[j] = win[j + 1] - win[j], delta[n] = 0.  With scale = min(1, rho),
+ * step = (int)(512 scale) (resampy's truncation, kept) and inc = 1 / rho, output sample t of an utterance of n_in samples is
+ *   tr = t inc, m = (int)tr, frac = scale (tr - m);   f = 512 frac, off = (int)f, eta = f - off
+ *   y  = sum_i (win[off + i step] + eta delta[off + i step]) x[m - i]          i < min(m + 1, (32769 - off) / step)
+ *      + the same with frac = scale - frac on x[m + 1 + k]                      k < min(n_in - m - 1, (32769 - off) / step)
+ * the position in double, every operation rounded on its own; weights, products and sums in double, rounded once to float32.
+ * resampy writes (long long)(n_in rho) samples and librosa zero-pads them to ceil(n_in rho). */
+/* Host only: *out = ceil(n * ratio).  TTS_ERR_INVALID: n < 1, a ratio that is not finite or outside [0.25, 4], NULL out. */
+int tts_resampled_length(int n, double ratio, int* out);
+/* wav [B][n] -> out [B][N_out].  n_samples: HOST int32 [B], the samples of each utterance, or NULL (all n); samples at or behind
+ * n_samples[b] are never read.  Row b of out holds min((long long)(n_samples[b] ratio), N_out) computed samples and 0.0 from
+ * there to N_out (librosa's fix_length, in both directions).  A NaN or Inf input sample reaches every output whose window covers
+ * it and no other.  64-bit indexing, no atomics: an utterance's output is the same bits whatever B is and wherever it sits in
+ * the batch.  ratio 1.0 is legal and runs the filter.  Asynchronous on the handle's stream (the lengths travel in the launches;
+ * the first call at a ratio builds that ratio's table on the host and uploads it with a synchronous copy, which blocks the
+ * calling thread; ratios of 1 and above share one table), no model needed; profile stage "resample".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL wav or out, a ratio that is not finite or outside [0.25, 4], B, n or
+ * N_out < 1, an n_samples[b] outside [1, n]. */
+int tts_resample(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double ratio, int N_out, float* out);
+
 /* ---- analysis features (audio/features.py:5-86,116-145) and dB helpers ---------------- */
 /* librosa.stft(wav, n_fft, hop, win) as linear_scale_spectrogram returns it (features.py:145):
  * centre/reflect padding, periodic hann.  wav [B*n] -> out complex64 interleaved
@@ -493,12 +518,34 @@ int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, i
  * TTS_ERR_INVALID (the setting stays as it was): a rate that is not finite or outside [0.25, 4]. */
 int tts_set_speaking_rate(tts_handle_t h, double rate);
 
+/* The pitch of synthesis, in octaves (the reference's pitch_shift, audio/effects.py:9-43: a time-stretch by 2 ** -octaves, then
+ * the resampler back to the length it had).  A setting of the HANDLE, read when a call is made; the default 0 means off, and off
+ * is the call as it always was, launch for launch.  Otherwise, with rho = exp2(-octaves) and s the speaking rate,
+ * tts_synthesize and tts_synthesize_host stretch the call's magnitudes by s rho (tts_stretch_rows) to
+ * T' = tts_stretched_frames(T, s rho) frames, Griffin-Lim reconstructs hop (T' - 1) samples without peak normalisation, and
+ * tts_resample takes them by rho into rows of hop (T_s - 1) samples, T_s = tts_stretched_frames(T, s); with peak_normalize
+ * tts_peak_normalize then runs on those rows.  Pitch changes no shape and no reported length: wav, the pinned buffers and
+ * tts_synth_frames / tts_wait_host_frames are those of the same call without pitch; only init_phase is [B][F][T'].  With
+ * end-of-speech stopping the detection is as ever, the frames reported for utterance b stay n_s[b], the un-shifted call's,
+ * Griffin-Lim runs on n'[b] = min(T', max(min_frames, tts_stretched_frames(n[b], s rho))) frames, and row b holds
+ * min((long long)(hop (n'[b] - 1) rho), hop (n_s[b] - 1)) samples and zeros behind them.  A call whose s rho falls outside
+ * [0.25, 4] or whose T' < min_frames is TTS_ERR_INVALID, and so is one whose T_s < min_frames (the call without pitch, whose
+ * rows it fills, is refused too).  The first call after the setting changed is not pipelined; the first call at a new
+ * 2 ** -octaves also builds that ratio's resampling table on the host (32 769 window samples, a Bessel series each, once per
+ * handle, then 0.5 MiB per ratio) and uploads it with a synchronous copy: it blocks the calling thread for that long, also in
+ * the middle of a stream of tts_synthesize_host calls.  A caller that switches pitch per request can pay that ahead of time
+ * with a tts_resample call at each ratio it will use.
+ * "gl_momentum" composes unchanged; the host form stays bit-identical to tts_synthesize + tts_memcpy_d2h.
+ * TTS_ERR_INVALID (the setting stays as it was): a shift that is not finite or |octaves| > 1. */
+int tts_set_pitch(tts_handle_t h, double octaves);
+
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
  * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate), "features" (tts_trim_bounds, the trim of tts_plan_features and
  * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize),
- * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize).
+ * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
+ * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -112,6 +112,9 @@ _PROTOTYPES = {
     'tts_stretch_magnitudes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_void_p]),
     'tts_stretch_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_void_p]),
     'tts_set_speaking_rate': (c_int, [c_void_p, ctypes.c_double]),
+    'tts_resampled_length': (c_int, [c_int, ctypes.c_double, POINTER(c_int)]),
+    'tts_resample': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_void_p]),
+    'tts_set_pitch': (c_int, [c_void_p, ctypes.c_double]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -362,6 +365,93 @@ class _SpeakingRateScope(object):
         return False
 
 
+RESAMPLE_RATIO_MIN, RESAMPLE_RATIO_MAX = 0.25, 4.0
+PITCH_OCTAVES_MAX = 1.0
+
+
+def resample_ratio_value(ratio):
+    """``ratio`` (target rate / source rate) of the resampling calls as a checked float.  ValueError, raised before a handle is
+    touched, for what tts_resample refuses: a ratio that is not finite or lies outside [0.25, 4]."""
+    try:
+        r = float(ratio)
+    except (TypeError, ValueError):
+        raise ValueError('the resampling ratio must be a number in [0.25, 4], got {!r}'.format(ratio))
+    if not RESAMPLE_RATIO_MIN <= r <= RESAMPLE_RATIO_MAX:   # (a NaN fails both comparisons)
+        raise ValueError('the resampling ratio must be finite and lie in [0.25, 4], got {!r}'.format(ratio))
+    return r
+
+
+def resampled_valid(n, ratio):
+    """The samples resampy writes for ``n`` input samples: int(n * ratio), the product in double, truncated."""
+    r = resample_ratio_value(ratio)
+    if int(n) != n or n < 1:
+        raise ValueError('resampled_valid: need n >= 1 samples, got {!r}'.format(n))
+    return int(np.float64(int(n)) * np.float64(r))
+
+
+def resampled_length(n, ratio):
+    """tts_resampled_length on the host: ceil(n * ratio) in double, the length librosa.core.resample (fix=True) returns."""
+    r = resample_ratio_value(ratio)
+    if int(n) != n or n < 1:
+        raise ValueError('resampled_length: need n >= 1 samples, got {!r}'.format(n))
+    return int(np.ceil(np.float64(int(n)) * np.float64(r)))
+
+
+def pitch_octaves_value(octaves):
+    """``pitch`` of the synthesis calls, in octaves, as a checked float (None stays None: the handle's setting as it stands).
+    ValueError, raised before a handle is touched, for what tts_set_pitch refuses: a shift that is not finite or beyond one
+    octave either way."""
+    if octaves is None:
+        return None
+    try:
+        o = float(octaves)
+    except (TypeError, ValueError):
+        raise ValueError('pitch must be a number of octaves in [-1, 1], got {!r}'.format(octaves))
+    if not -PITCH_OCTAVES_MAX <= o <= PITCH_OCTAVES_MAX:   # (a NaN fails both comparisons)
+        raise ValueError('pitch must be finite and lie in [-1, 1] octaves, got {!r}'.format(octaves))
+    return o
+
+
+def pitch_semitones_value(semitones):
+    """``--pitch SEMITONES`` as octaves (semitones / 12), checked as ``pitch_octaves_value`` checks them."""
+    try:
+        st = float(semitones)
+    except (TypeError, ValueError):
+        raise ValueError('pitch must be a number of semitones in [-12, 12], got {!r}'.format(semitones))
+    if not -12.0 <= st <= 12.0:
+        raise ValueError('pitch must be finite and lie in [-12, 12] semitones, got {!r}'.format(semitones))
+    return st / 12.0
+
+
+def pitch_frames(T, speaking_rate, octaves):
+    """The frames Griffin-Lim reconstructs from in a call of T frames at ``speaking_rate`` shifted by ``octaves``:
+    stretched_frames(T, speaking_rate * 2 ** -octaves) -- the length of ``init_phase``'s last axis.  ValueError where the
+    product leaves [0.25, 4]."""
+    eff = float(speaking_rate) * float(np.exp2(-np.float64(octaves)))
+    if not SPEAKING_RATE_MIN <= eff <= SPEAKING_RATE_MAX:
+        raise ValueError('speaking rate {} times 2 ** -{} octaves = {} is outside [0.25, 4]'.format(speaking_rate, octaves, eff))
+    return stretched_frames(T, eff)
+
+
+class _PitchScope(object):
+    """The pitch set for the calls made inside the block and put back afterwards, as _SpeakingRateScope does for its setting;
+    None: the handle's pitch as it stands."""
+
+    def __init__(self, engine, octaves):
+        self.engine = engine
+        self.value = pitch_octaves_value(octaves)
+
+    def __enter__(self):
+        self.saved = self.engine._pitch
+        if self.value is not None and self.value != self.saved:
+            self.engine.set_pitch(self.value)
+
+    def __exit__(self, *exc):
+        if self.engine._pitch != self.saved:
+            self.engine.set_pitch(self.saved)
+        return False
+
+
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
@@ -409,6 +499,7 @@ class Engine(object):
         self._gl_momentum = 0   # the handle's "gl_momentum" (the C ABI has no getter: set_option keeps it)
         self._end_of_speech = (False, 0.0, 0)   # ... and its end-of-speech setting (set_end_of_speech keeps it)
         self._speaking_rate = 1.0               # ... and its speaking rate (set_speaking_rate keeps it)
+        self._pitch = 0.0                       # ... and its pitch in octaves (set_pitch keeps it)
         if stream is not None:
             self._check(self.lib.tts_set_stream(self.handle, c_void_p(stream)))
 
@@ -456,6 +547,14 @@ class Engine(object):
             raise ValueError('set_speaking_rate: a rate in [0.25, 4] is needed')
         self._check(self.lib.tts_set_speaking_rate(self.handle, r))
         self._speaking_rate = r
+
+    def set_pitch(self, octaves):
+        """tts_set_pitch: the handle's setting, read by every synthesize / synthesize_host call made after it; 0 = off."""
+        o = pitch_octaves_value(octaves)
+        if o is None:
+            raise ValueError('set_pitch: a shift in [-1, 1] octaves is needed')
+        self._check(self.lib.tts_set_pitch(self.handle, o))
+        self._pitch = o
 
     def synchronize(self):
         self._check(self.lib.tts_synchronize(self.handle))
@@ -843,9 +942,85 @@ class Engine(object):
             wav.shape = (wav.shape[1],)
         return (wav, mag, st) if want_magnitudes else wav
 
+    # ------------------------------------------------------------------ resampling and pitch
+    def resampled_length(self, n, ratio):
+        """tts_resampled_length: ceil(n * ratio), the samples librosa.core.resample returns for ``n``."""
+        r = resample_ratio_value(ratio)
+        if int(n) != n or n < 1:
+            raise ValueError('resampled_length: need n >= 1 samples, got {!r}'.format(n))
+        out = c_int(0)
+        if self.lib.tts_resampled_length(int(n), r, byref(out)) != TTS_OK:
+            raise ValueError('resampled_length({!r}, {!r}) refused'.format(n, ratio))
+        return out.value
+
+    def resample(self, wavs, ratio, n_samples=None, N_out=None):
+        """tts_resample: librosa 0.6 ``resample(..., res_type='kaiser_best')`` (resampy's windowed sinc) by ``ratio`` = target
+        rate / source rate in [0.25, 4].  ``wavs``: one waveform (n,) or a batch (B, n), a host array or a device buffer.
+        ``n_samples``: B lengths (host integers) -- samples at or behind them are never read; None: all n.  Returns a device
+        array (B, N_out) -- (N_out,) for one waveform given as a 1-D array, host or device: utterance b holds min(int(n_samples[b] * ratio),
+        N_out) resampled samples and zeros behind them; ``N_out`` None: ceil(longest * ratio), librosa's length."""
+        r = resample_ratio_value(ratio)
+        single = len(wavs.shape) == 1
+        if single and not _is_device(wavs):
+            wavs = np.asarray(wavs).reshape(1, -1)
+        if len(wavs.shape) not in (1, 2) or min(wavs.shape) < 1:
+            raise ValueError('resample: one waveform (n,) or a batch (B, n) is needed, got shape {}'.format(tuple(wavs.shape)))
+        # (a 1-D device buffer is one row as it lies)
+        B, n = (1, int(wavs.shape[0])) if len(wavs.shape) == 1 else (int(d) for d in wavs.shape)
+        ns = None
+        if n_samples is not None:
+            ns = np.asarray(n_samples)
+            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+            for b, m in enumerate(ns.tolist()):
+                if not 1 <= m <= n:
+                    raise ValueError('n_samples[{}] = {} is not in 1 .. n = {}'.format(b, m, n))
+            ns = np.ascontiguousarray(ns, dtype=np.int32)
+        if N_out is None:
+            N_out = resampled_length(int(ns.max()) if ns is not None else n, r)
+        N_out = int(N_out)
+        if N_out < 1:
+            raise ValueError('resample: N_out = {} < 1'.format(N_out))
+        p_wav, _k = self._in(wavs, np.float32)
+        out = self.empty((B, N_out))
+        try:
+            self._check(self.lib.tts_resample(self.handle, p_wav, B, n, ns.ctypes.data_as(POINTER(c_int32)) if ns is not None else None,
+                                              r, N_out, out.data_ptr()))
+        except Exception:   # (a refusal: nothing was enqueued)
+            out.free()
+            raise
+        if single:
+            out.shape = (N_out,)
+        return out
+
+    def pitch_shift(self, wavs, sampling_rate, octaves, n_iter=25, seed=0):
+        """The reference's waveform effect pitch_shift (audio/effects.py:9-43) as a composition of existing calls:
+        ``time_stretch(wavs, rate)`` with rate = 2 ** -octaves, then ``resample`` from sampling_rate / rate back to
+        sampling_rate, cut or zero-padded to the input's length (librosa's fix_length).  ``wavs``: one waveform (n,) or a
+        uniform batch (B, n).  Returns a device array of the input's shape."""
+        o = pitch_octaves_value(octaves)
+        if o is None:
+            raise ValueError('pitch_shift: a shift in [-1, 1] octaves is needed')
+        rate = float(np.exp2(-np.float64(o)))
+        sr = float(sampling_rate)
+        if not sr > 0:
+            raise ValueError('pitch_shift: sampling_rate must be positive, got {!r}'.format(sampling_rate))
+        single = len(wavs.shape) == 1
+        n = int(wavs.shape[-1])
+        st = self.time_stretch(wavs, rate, n_iter=n_iter, seed=seed)
+        if single:
+            st.shape = (1, st.shape[0])
+        try:
+            out = self.resample(st, sr / (sr / rate), N_out=n)
+        finally:
+            st.free()   # (tts_free waits for the device: the resampling that reads it has run)
+        if single:
+            out.shape = (n,)
+        return out
+
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
-                   momentum=None, stop_at_silence=None, speaking_rate=None):
+                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None):
         """``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
         (tts_set_end_of_speech): every utterance is reconstructed from its frames up to the last one whose loudest bin is
         above ``threshold_db``, plus ``keep_frames``; ``wav`` keeps its shape, row b holds hop (n_frames[b] - 1) samples
@@ -854,22 +1029,30 @@ class Engine(object):
         ``speaking_rate``: None (the handle's setting, 1.0 unless ``set_speaking_rate`` changed it) or a rate in [0.25, 4]
         for this call (tts_set_speaking_rate): the magnitudes are time-stretched ahead of Griffin-Lim, ``wav`` is
         (B, hop (T' - 1)) and ``init_phase`` (B, F, T') with T' = ``stretched_frames(T, rate)``; mel, alignments and linear
-        keep their length T."""
+        keep their length T.
+        ``pitch``: None (the handle's setting, 0 unless ``set_pitch`` changed it) or a shift in [-1, 1] octaves for this call
+        (tts_set_pitch): the magnitudes are stretched by rate * 2 ** -pitch, and the resampler takes Griffin-Lim's samples
+        back to the length of the call without pitch.  No shape and no reported length changes but ``init_phase``'s, which is
+        (B, F, ``pitch_frames(T, rate, pitch)``)."""
         scope = _MomentumScope(self, momentum)   # (as in griffin_lim)
         eos = _EndOfSpeechScope(self, stop_at_silence)
         rate = _SpeakingRateScope(self, speaking_rate)
+        shift = _PitchScope(self, pitch)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call = self._speaking_rate if rate.value is None else rate.value
+        o_call = self._pitch if shift.value is None else shift.value
         T_wav = T if r_call == 1.0 else stretched_frames(T, r_call)
+        # (a product of rate and 2 ** -pitch outside [0.25, 4] is the library's to refuse, at the call)
+        T_init = T_wav if o_call == 0.0 or init_phase is None else pitch_frames(T, r_call, o_call)
         F = 1 + self.cfg.n_fft // 2
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed,
                             1 if peak_normalize else 0)
         self._check_ids(ids)
         p_ids, _k1 = self._in(ids, np.int32, 'ids')
         p_init, _k2 = self._in(init_phase, np.float32, 'init_phase')
-        if init_phase is not None and int(np.prod(init_phase.shape)) != B * F * T_wav:
-            raise ValueError('synthesize: init_phase of shape {} given, {} needed'.format(tuple(init_phase.shape), (B, F, T_wav)))
+        if init_phase is not None and int(np.prod(init_phase.shape)) != B * F * T_init:
+            raise ValueError('synthesize: init_phase of shape {} given, {} needed'.format(tuple(init_phase.shape), (B, F, T_init)))
         if wav is not None and int(np.prod(wav.shape)) != B * hop_length * (T_wav - 1):
             raise ValueError('synthesize: wav buffer of shape {} given, {} needed'.format(tuple(wav.shape), (B, hop_length * (T_wav - 1))))
         wav = wav if wav is not None else self.empty((B, hop_length * (T_wav - 1)))
@@ -885,7 +1068,7 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope, eos, rate:
+        with scope, eos, rate, shift:
             stopping = self._end_of_speech[0]
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
@@ -905,16 +1088,18 @@ class Engine(object):
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
-                        speaking_rate=None):
+                        speaking_rate=None, pitch=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
         ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
-        has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1)))."""
+        has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1))); ``pitch`` as in
+        ``synthesize`` (no shape changes)."""
         scope = _MomentumScope(self, momentum)
         eos = _EndOfSpeechScope(self, stop_at_silence)
         rate = _SpeakingRateScope(self, speaking_rate)
+        shift = _PitchScope(self, pitch)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -924,7 +1109,7 @@ class Engine(object):
         r_call = self._speaking_rate if rate.value is None else rate.value
         T = n_steps * self.cfg.reduction
         T_wav = T if r_call == 1.0 else stretched_frames(T, r_call)
-        with scope, eos, rate:
+        with scope, eos, rate, shift:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes = getattr(self, '_host_shapes', {})
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))

@@ -7,7 +7,10 @@ computed by tts_trim_bounds on the GPU.
 librosa phase vocoder, np.abs and Griffin-Lim; on this path that is ``Engine.time_stretch(wavs, rate)`` (device calls:
 tts_stft_magnitude, tts_stretch_magnitudes, tts_griffin_lim), and the speaking rate of synthesis is the ``speaking_rate``
 argument of the synthesis calls (tts_set_speaking_rate), which stretches the magnitudes a call already holds ahead of its one
-Griffin-Lim.  ``pitch_shift`` (:9-43) also needs librosa's resampler, which stays out of scope."""
+Griffin-Lim.  ``pitch_shift`` (:9-43) is that time_stretch at 2 ** -octaves followed by librosa's resampler (resampy's
+'kaiser_best' windowed sinc) back to the input's length; on this path that is ``Engine.pitch_shift(wavs, sampling_rate, octaves)``
+(``Engine.time_stretch``, then ``Engine.resample``: tts_resample), and the pitch of synthesis is the ``pitch`` argument of the
+synthesis calls (tts_set_pitch), which stretches the call's magnitudes and resamples what its one Griffin-Lim made."""
 import numpy as np
 
 from . import default_engine
@@ -15,7 +18,7 @@ from .conversion import ms_to_samples
 
 
 def pitch_shift(wav, sampling_rate, octaves):
-    raise NotImplementedError('pitch_shift (librosa resampling, reference audio/effects.py:9-43) is out of scope')
+    raise NotImplementedError('pitch_shift (librosa resampling, reference audio/effects.py:9-43) is out of scope')   # see Engine.pitch_shift
 
 
 def time_stretch(wav, rate):

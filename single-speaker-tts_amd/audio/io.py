@@ -1,5 +1,6 @@
 """Mirror of reference audio/io.py: ``save_wav`` (:33-53, float32 WAV, optional peak normalisation) and ``load_wav``
-(:8-30, librosa.core.load of a RIFF/WAVE file at its native rate; standard library and numpy only).
+(:8-30, librosa.core.load of a RIFF/WAVE file at its native rate; standard library and numpy only).  ``resample`` is the
+resampler librosa.core.load runs for another rate, librosa.core.resample, on the GPU (tts_resample); ``load_wav`` does not call it.
 
 librosa.output.write_wav(path, y.astype(float32), sr, norm=True) = util.normalize(y, norm=inf)
 then scipy.io.wavfile.write of float32 samples (WAVE_FORMAT_IEEE_FLOAT).  The normalisation runs
@@ -67,6 +68,23 @@ def _read_wav(path):
     if fmt is None or data is None:
         raise ValueError('{}: no {} chunk'.format(path, 'fmt' if fmt is None else 'data'))
     return fmt + (data,)
+
+
+def resample(wav, orig_sr, target_sr, engine=None):
+    """librosa 0.6 librosa.core.resample(wav, orig_sr, target_sr, res_type='kaiser_best', fix=True, scale=False) of a mono
+    waveform (n,): resampy's windowed-sinc interpolator computed by tts_resample, zero-padded to ceil(n * target_sr / orig_sr)
+    samples; equal rates return ``wav`` itself, as librosa does.  The ratio target_sr / orig_sr must lie in [0.25, 4]."""
+    if orig_sr == target_sr:
+        return wav
+    wav = np.asarray(wav)
+    if wav.ndim != 1 or wav.shape[0] < 1:
+        raise ValueError('resample: a mono waveform (n,) is needed, got shape {}'.format(wav.shape))
+    ratio = float(target_sr) / orig_sr
+    eng = engine or default_engine()
+    out = eng.resample(wav.astype(np.float32), ratio)
+    y = out.to_host()
+    out.free()
+    return np.ascontiguousarray(y, dtype=wav.dtype if wav.dtype.kind == 'f' else np.float32)
 
 
 def load_wav(wav_path, sampling_rate=None, offset=0.0, duration=None):

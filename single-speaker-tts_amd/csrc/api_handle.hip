@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -645,6 +645,7 @@ int tts_destroy(tts_handle_t h) {
     if (h->an.window) hipFree(h->an.window);
     if (h->an.mel_wt) hipFree(h->an.mel_wt);
     feat_release(h);
+    resample_release(h);
     if (h->eos.pinned) hipHostFree(h->eos.pinned);
     if (h->an.flag) hipFree(h->an.flag);
     for (auto& kv : h->glg.tw) hipFree(kv.second);
@@ -700,6 +701,14 @@ int tts_set_speaking_rate(tts_handle_t h, double rate) {
     if (!h) return TTS_ERR_INVALID;
     if (!(rate >= 0.25 && rate <= 4.0)) return fail(h, TTS_ERR_INVALID, "set_speaking_rate: the rate must be finite and lie in [0.25, 4]");
     h->speaking_rate = rate;
+    return TTS_OK;
+}
+
+
+int tts_set_pitch(tts_handle_t h, double octaves) {
+    if (!h) return TTS_ERR_INVALID;
+    if (!(octaves >= -1.0 && octaves <= 1.0)) return fail(h, TTS_ERR_INVALID, "set_pitch: the shift must be finite and lie in [-1, 1] octaves");
+    h->pitch_octaves = octaves;
     return TTS_OK;
 }
 

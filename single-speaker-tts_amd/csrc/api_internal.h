@@ -54,7 +54,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -198,6 +198,7 @@ struct CallPipeline {
     Signal serial_done;
     unsigned syn_calls = 0;
     int syn_shape[3] = {0, 0, 0};   // (B, Ts, n_steps) of the previous tts_synthesize call
+    double syn_rho = 0.0;           // ... and the resampling ratio of its pitch (0: none)
     int syn_tg = 0;                 // ... and the frames its Griffin-Lim reconstructed from (T, or T' with a speaking rate)
     int last_enc_ahead = -1;        // did the previous PIPELINED call run its encoder ahead on `encs` (1) or on `front` (0)?
 
@@ -405,6 +406,17 @@ struct tts_handle_s {
     // speaking rate (tts_set_speaking_rate): read when a call is made; 1.0 = off, the call then enqueues what it always did
     double speaking_rate = 1.0;
 
+    // pitch (tts_set_pitch), in octaves: read when a call is made; 0 = off, the call then enqueues what it always did.
+    // pitch_lens: the frames the last shifted call's Griffin-Lim ran on (the call reports the un-shifted call's lengths)
+    double pitch_octaves = 0.0;
+    std::vector<int32_t> pitch_lens, pitch_samples, pitch_keep;
+
+    // the resampler (resample.hip): the half window before a ratio's scale, and the phase-major tables per ratio on the device
+    struct {
+        std::vector<double> base;
+        std::map<uint64_t, double*> tabs;
+    } rs;
+
     // analysis-side tables (STFT window, mel basis)
     struct {
         int win = 0;
@@ -531,6 +543,12 @@ int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, i
 // speaking rate (stretch.hip): both layouts of the time-stretch, arguments checked by the caller (stretch_plan.h)
 int stretch_impl(tts_handle_t h, const float* in, int B, int T, int F, int row_stride, bool time_major, const int32_t* n_frames, double rate,
                  int T_out, float* out);
+// the resampler (resample.hip): arguments checked by the caller (resample_plan.h).  resample_table makes a ratio's table ahead
+// of a call that must not allocate once it has begun to enqueue
+int resample_table(tts_handle_t h, double rho, const double** tab);
+int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double rho, int N_out, const int32_t* keep_cap,
+                  float* out);
+void resample_release(tts_handle_t h);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);
 int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memory);

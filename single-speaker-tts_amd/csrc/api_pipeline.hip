@@ -2,6 +2,7 @@
 // call parity, the wide Griffin-Lim launches), its host-memory form and the tickets of tts_wait_host.
 #include "api_internal.h"
 #include "stretch_plan.h"
+#include "resample_plan.h"
 
 namespace tts_api {
 
@@ -75,6 +76,14 @@ struct SynthCall {
     int Tg = 0;
     float* mags = nullptr;
     bool st_grows = false;       // this call allocates (or grows) the stretched magnitudes
+    // pitch (tts_set_pitch), likewise.  `rate` is then the speaking rate times rho = exp2(-octaves), Griffin-Lim writes its
+    // hop (Tg - 1) samples to `gl_wav` without normalising them, and the resampler takes them by rho into the rows of `wav`,
+    // hop (Tw - 1) samples, Tw = stretched_frames(T, rate_s): the shapes and lengths of the call without pitch
+    bool pitch = false;
+    double rho = 1.0, rate_s = 1.0;
+    int Tw = 0;
+    float* gl_wav = nullptr;
+    bool pt_grows = false;       // this call allocates (or grows) Griffin-Lim's own waveform buffer
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -145,6 +154,15 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "gl.mag_st", float, (size_t)B * Tg * FP, mags);
         k.mags = mags;
     }
+    // (the pitch switched on, off or to another shift between two calls of a shape: this call is unpipelined, as with the rate)
+    k.pt_grows = pl.syn_rho != (k.pitch ? k.rho : 0.0);
+    pl.syn_rho = k.pitch ? k.rho : 0.0;
+    if (k.pitch) {
+        const size_t n_gl = (size_t)B * sp->hop_length * (size_t)(Tg - 1);
+        k.pt_grows = k.pt_grows || h->ws["gl.wav_pitch"].bytes < n_gl * sizeof(float);
+        WS(h, "gl.wav_pitch", float, n_gl, glw);
+        k.gl_wav = glw;
+    }
     // Under the call pipeline the initial phasors of a call are written on the FRONT stream, behind its decoder (that
     // stream has slack, the main one bounds the step): the phasor-code buffers are then a pair per call parity, so that
     // the write does not wait for the previous call's Griffin-Lim.  All four are sized here, before anything is enqueued
@@ -197,7 +215,7 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     // (the momentum option switched on between two calls of a shape: its buffer is new, and this call is unpipelined like the
     //  first of a shape; likewise the end-of-speech setting and its buffers)
     const bool same_shape = pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps && !k.mom_grows && !k.eos_grows &&
-                            pl.syn_tg == Tg && !k.st_grows;
+                            pl.syn_tg == Tg && !k.st_grows && !k.pt_grows;
     pl.syn_tg = Tg;
     pl.syn_shape[0] = B; pl.syn_shape[1] = Ts; pl.syn_shape[2] = sp->n_steps;
     // (a borrowed stream is pipelined only on request, pipeline = 2: the caller then vouches that the inputs of a call
@@ -408,16 +426,27 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
         // Frames behind an utterance's end are not read; the lengths become min(Tg, max(min_frames, stretched_frames(n))) --
         // whatever that adds to an utterance is the vocoder's zero padding, which the pass writes.
         if ((rc = stretch_impl(h, k.magi, B, T, k.F, k.FP, true, k.eos ? h->eos.last.data() : nullptr, k.rate, Tg, k.mags))) return rc;
+        // (with a pitch Griffin-Lim runs on the lengths at rate s rho, and the call reports those at rate s: the un-shifted call's)
+        h->pitch_lens.resize(k.pitch ? (size_t)B : 0);
         for (int b = 0; b < B; ++b) {
-            const long long m = std::max<long long>(k.eos_min, stretched_frames(h->eos.last[b], k.rate));
-            h->eos.last[b] = (int32_t)std::min<long long>(Tg, m);
+            const int n = h->eos.last[b];
+            const long long m = std::max<long long>(k.eos_min, stretched_frames(n, k.rate));
+            const int32_t n_gl = (int32_t)std::min<long long>(Tg, m);
+            if (!k.pitch) {
+                h->eos.last[b] = n_gl;
+                continue;
+            }
+            h->pitch_lens[b] = n_gl;
+            if (k.rate_s != 1.0)
+                h->eos.last[b] = (int32_t)std::min<long long>(k.Tw, std::max<long long>(k.eos_min, stretched_frames(n, k.rate_s)));
         }
     }
+    const std::vector<int32_t>& gl_lens = k.pitch ? h->pitch_lens : h->eos.last;
     if (k.eos) {
         long long sum = 0;
-        for (int b = 0; b < B; ++b) sum += h->eos.last[b];
+        for (int b = 0; b < B; ++b) sum += gl_lens[b];
         if (sum != (long long)B * Tg) {
-            n_frames = h->eos.last.data();
+            n_frames = gl_lens.data();
             T_model = (int)((sum + B - 1) / B);
         }
     }
@@ -426,12 +455,32 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     const int* d_frames = (n_frames && !k.stretch) ? k.d_frames : nullptr;
     const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
+    float* gl_wav = k.pitch ? k.gl_wav : k.wav;
+    const bool gl_peak = sp->peak_normalize != 0 && !k.pitch;   // (a shifted call normalises what the resampler leaves)
     if (k.gl_streaming)
-        rc = gl_run(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav, nullptr,
-                    sp->peak_normalize != 0, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
+        rc = gl_run(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
+                    gl_peak, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
     else
-        rc = gl_run_generic(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, k.wav,
-                            nullptr, sp->peak_normalize != 0, n_frames, d_frames);
+        rc = gl_run_generic(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav,
+                            nullptr, gl_peak, n_frames, d_frames);
+    if (k.pitch && !rc) {
+        // The pitch: the hop (Tg - 1) samples Griffin-Lim made, resampled by rho into the rows of the call without pitch.  With
+        // end-of-speech stopping utterance b has hop (n'[b] - 1) samples, and its row ends where the un-shifted call's does.
+        const int n_gl = sp->hop_length * (Tg - 1), N_out = sp->hop_length * (k.Tw - 1);
+        const int32_t *ns = nullptr, *cap = nullptr;
+        if (k.eos) {
+            h->pitch_samples.resize((size_t)B);
+            h->pitch_keep.resize((size_t)B);
+            for (int b = 0; b < B; ++b) {
+                h->pitch_samples[b] = sp->hop_length * (h->pitch_lens[b] - 1);
+                h->pitch_keep[b] = sp->hop_length * (h->eos.last[b] - 1);
+            }
+            ns = h->pitch_samples.data();
+            cap = h->pitch_keep.data();
+        }
+        rc = resample_impl(h, k.gl_wav, B, n_gl, ns, k.rho, N_out, cap, k.wav);
+        if (!rc && sp->peak_normalize) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
+    }
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
 }
@@ -451,13 +500,32 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
                 1 + c.n_fft / 2, gl_fp(c.n_fft), gl_is_streaming(c.n_fft, sp->win_length, sp->hop_length)};
     k.Tg = k.T;
     k.eos_min = sp->hop_length >= 1 ? speech_min_frames(c.n_fft, sp->hop_length) : 1;   // (the hop is checked below)
-    if (h->speaking_rate != 1.0) {   // (read here, once, as the end-of-speech setting below; 1.0: nothing of this call changes)
+    k.Tw = k.T;
+    // (read here, once, as the end-of-speech setting below; rate 1.0 and pitch 0: nothing of this call changes)
+    if (h->speaking_rate != 1.0 || h->pitch_octaves != 0.0) {
         if (sp->hop_length < 1) return fail(h, TTS_ERR_INVALID, "synthesize: hop_length >= 1");
         k.stretch = true;
         k.rate = h->speaking_rate;
+        if (k.rate != 1.0) k.Tw = (int)stretched_frames(k.T, k.rate);
+        if (h->pitch_octaves != 0.0) {
+            k.pitch = true;
+            k.rho = std::exp2(-h->pitch_octaves);
+            k.rate_s = h->speaking_rate;
+            k.rate = k.rate_s * k.rho;
+            if (!stretch_rate_ok(k.rate))
+                return fail(h, TTS_ERR_INVALID, "synthesize: the speaking rate times 2 ** -octaves of the pitch is " + std::to_string(k.rate) +
+                                                    ", outside [0.25, 4]");
+            // (the rows of a shifted call are those of the call without pitch, which this refusal is of: T_s = T at rate 1.0)
+            if (k.Tw < k.eos_min)
+                return fail(h, TTS_ERR_INVALID, "synthesize: with a pitch the call's rows hold " + std::to_string(k.Tw) + " frames" +
+                                                    (k.rate_s != 1.0 ? " at this speaking rate" : "") + ", the call without pitch needs at least " +
+                                                    std::to_string(k.eos_min) + " (hop (n - 1) > n_fft / 2)");
+            const double* tab_unused = nullptr;   // (the ratio's table, made before anything of this call is enqueued)
+            if ((rc = resample_table(h, k.rho, &tab_unused))) return rc;
+        }
         k.Tg = (int)stretched_frames(k.T, k.rate);
         if (k.Tg < k.eos_min)
-            return fail(h, TTS_ERR_INVALID, "synthesize: the speaking rate leaves " + std::to_string(k.Tg) + " frames, Griffin-Lim needs at least " +
+            return fail(h, TTS_ERR_INVALID, std::string("synthesize: the speaking rate") + (k.pitch ? " and the pitch leave " : " leaves ") + std::to_string(k.Tg) + " frames, Griffin-Lim needs at least " +
                                                 std::to_string(k.eos_min) + " (hop (n - 1) > n_fft / 2)");
     }
     if (k.gl_streaming && (rc = gl_prepare(h, k.Tg, sp->win_length, sp->hop_length, c.n_fft))) return rc;

@@ -8,7 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import momentum_thousandths, speaking_rate_value, stretched_frames
+from .._hip import momentum_thousandths, pitch_frames, pitch_octaves_value, speaking_rate_value, stretched_frames
 from ..audio.conversion import ms_to_samples
 from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_sentence, stop_setting
 from .model import Mode, Tacotron
@@ -24,17 +24,23 @@ def pre_process_sentences(_sentences, dataset):
 
 
 def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0, stop_at_silence_db=None,
-                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0):
+                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
     constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86); ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: every utterance is reconstructed only up to
     ``silence_keep_ms`` behind its last frame whose loudest bin is above that many dB (``Engine.speech_frames`` on the
     normalised spectrograms, then one ragged Griffin-Lim call) and returned at its own length.  ``speaking_rate``: 1.0, or a
     rate in [0.25, 4] -- the magnitudes are time-stretched (``Engine.stretch_magnitudes``) ahead of Griffin-Lim: T' =
-    ceil(T / rate) frames, ``init_phase`` (B, F, T'), lengths min(T', max(min_frames, ceil(n / rate)))."""
+    ceil(T / rate) frames, ``init_phase`` (B, F, T'), lengths min(T', max(min_frames, ceil(n / rate))).  ``pitch``: 0.0, or a
+    shift in [-1, 1] octaves -- the magnitudes are stretched by rate * 2 ** -pitch instead (``init_phase`` has that many
+    frames) and ``Engine.resample`` takes Griffin-Lim's samples by 2 ** -pitch back to the lengths they have without it."""
     momentum_thousandths(momentum)
     stop = stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
     rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
+    octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
+    rho = float(np.exp2(-np.float64(octaves)))
+    if octaves != 0.0:
+        pitch_frames(1, rate, octaves)   # (ValueError where rate * rho leaves [0.25, 4])
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
     win_hop = ms_to_samples(model_params.win_hop, model_params.sampling_rate)
@@ -52,13 +58,32 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
         thr = engine.speech_threshold(stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
         n_frames = engine.speech_frames(spec, thr, keep_frames=stop[1], min_frames=min_frames)[0].to_host()
     mag = engine.denorm_power(spec, loader.mel_mag_ref_db, loader.mel_mag_max_db, model_params.magnitude_power)
-    if rate != 1.0:
-        T_out = stretched_frames(T, rate)
-        mag = engine.stretch_magnitudes(mag, rate, n_frames=n_frames, T_out=T_out)
+    def stretched(lengths, r, T_r):
+        return np.array([min(T_r, max(min_frames, stretched_frames(int(n), r))) for n in lengths], np.int32)
+
+    T_s = T if rate == 1.0 else stretched_frames(T, rate)   # the frames of the waveforms, with or without a pitch
+    n_gl = n_frames                                          # the frames Griffin-Lim runs on
+    if octaves != 0.0:
+        eff = rate * rho
+        T_g = stretched_frames(T, eff)
+        if T_g < min_frames:
+            raise ValueError('pitch {} at speaking_rate {}: {} frames are left of {}, at least {} needed'.format(octaves, rate, T_g, T, min_frames))
+        mag = engine.stretch_magnitudes(mag, eff, n_frames=n_frames, T_out=T_g)
         if n_frames is not None:
-            n_frames = np.array([min(T_out, max(min_frames, stretched_frames(int(n), rate))) for n in n_frames], np.int32)
+            n_gl = stretched(n_frames, eff, T_g)
+            n_frames = stretched(n_frames, rate, T_s) if rate != 1.0 else n_frames
+    elif rate != 1.0:
+        mag = engine.stretch_magnitudes(mag, rate, n_frames=n_frames, T_out=T_s)
+        if n_frames is not None:
+            n_gl = n_frames = stretched(n_frames, rate, T_s)
     wav, _ = engine.griffin_lim(mag, model_params.reconstruction_iterations, win_len, win_hop, model_params.n_fft,
-                                init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_frames)
+                                init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_gl)
+    if octaves != 0.0:
+        gl_wav = wav
+        try:
+            wav = engine.resample(gl_wav, rho, n_samples=None if n_gl is None else win_hop * (n_gl - 1), N_out=win_hop * (T_s - 1))
+        finally:
+            gl_wav.free()   # (tts_free waits for the device: the resampling that reads it has run)
     wav = wav.to_host()
     if n_frames is not None:
         return cut_waveforms(wav, n_frames, win_hop)
@@ -66,7 +91,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
-          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0):
+          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -77,10 +102,11 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     generator ends), which on a request-driven generator would hold every answer back by two requests.
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db`` /
     ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech;
-    ``speaking_rate`` likewise."""
+    ``speaking_rate`` and ``pitch`` likewise."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
     stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
     speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
+    pitch_octaves_value(0.0 if pitch is None else pitch)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
@@ -90,11 +116,12 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
             ids = pre_process_sentences(sentences, dataset)
             spectrograms = model.run(model.output_linear_spec, {model.inp_sentences: ids})
             yield post_process_spectrograms(spectrograms, model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
-                                            silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate)
+                                            silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch)
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
     for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
-                                  stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate):
+                                  stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
+                                  pitch=pitch):
         yield [wavs[b] for b in range(len(wavs))]

@@ -241,21 +241,23 @@ def momentum_thousandths(momentum):
     return min(999, int(round(m * 1000.0)))
 
 
-class _MomentumScope(object):
-    """``gl_momentum`` set for the calls made inside the block and put back afterwards; None: the handle's current value."""
+class _SettingScope(object):
+    """One setting of the handle put to ``value`` for the calls made inside the block and put back afterwards, also after an
+    exception; None: the handle's setting as it stands.  ``attr``: the engine's attribute that mirrors the setting (the C ABI
+    has no getters), ``setter(value)``: sets both.  ``value`` is checked by whoever makes the scope, before a handle is
+    touched."""
 
-    def __init__(self, engine, momentum):
-        self.engine = engine
-        self.value = None if momentum is None else momentum_thousandths(momentum)
+    def __init__(self, engine, attr, setter, value):
+        self.engine, self.attr, self.setter, self.value = engine, attr, setter, value
 
     def __enter__(self):
-        self.saved = self.engine._gl_momentum
+        self.saved = getattr(self.engine, self.attr)
         if self.value is not None and self.value != self.saved:
-            self.engine.set_option('gl_momentum', self.value)
+            self.setter(self.value)
 
     def __exit__(self, *exc):
-        if self.engine._gl_momentum != self.saved:
-            self.engine.set_option('gl_momentum', self.saved)
+        if getattr(self.engine, self.attr) != self.saved:
+            self.setter(self.saved)
         return False
 
 
@@ -282,25 +284,6 @@ def silence_keep_frames(keep_samples, hop_length):
     if not keep_samples >= 0 or hop_length < 1:
         raise ValueError('the audio kept behind the speech must be >= 0 samples, got {!r} (hop {!r})'.format(keep_samples, hop_length))
     return -(-int(keep_samples) // int(hop_length))
-
-
-class _EndOfSpeechScope(object):
-    """End-of-speech stopping switched on for the calls made inside the block and put back afterwards, as _MomentumScope
-    does for the momentum; None: the handle's setting as it stands."""
-
-    def __init__(self, engine, stop_at_silence):
-        self.engine = engine
-        self.value = stop_at_silence_setting(stop_at_silence)
-
-    def __enter__(self):
-        self.saved = self.engine._end_of_speech
-        if self.value is not None:
-            self.engine.set_end_of_speech(True, *self.value)
-
-    def __exit__(self, *exc):
-        if self.engine._end_of_speech != self.saved:
-            self.engine.set_end_of_speech(*self.saved)
-        return False
 
 
 SPEAKING_RATE_MIN, SPEAKING_RATE_MAX = 0.25, 4.0
@@ -344,25 +327,6 @@ def stretch_frame_counts(n_frames, B, T):
         if not 1 <= n <= T:
             raise ValueError('n_frames[{}] = {} is not in 1 .. T = {}'.format(b, n, T))
     return np.ascontiguousarray(nf, dtype=np.int32)
-
-
-class _SpeakingRateScope(object):
-    """The speaking rate set for the calls made inside the block and put back afterwards, as _EndOfSpeechScope does for its
-    setting; None: the handle's rate as it stands."""
-
-    def __init__(self, engine, rate):
-        self.engine = engine
-        self.value = speaking_rate_value(rate)
-
-    def __enter__(self):
-        self.saved = self.engine._speaking_rate
-        if self.value is not None and self.value != self.saved:
-            self.engine.set_speaking_rate(self.value)
-
-    def __exit__(self, *exc):
-        if self.engine._speaking_rate != self.saved:
-            self.engine.set_speaking_rate(self.saved)
-        return False
 
 
 RESAMPLE_RATIO_MIN, RESAMPLE_RATIO_MAX = 0.25, 4.0
@@ -423,33 +387,51 @@ def pitch_semitones_value(semitones):
     return st / 12.0
 
 
-def pitch_frames(T, speaking_rate, octaves):
-    """The frames Griffin-Lim reconstructs from in a call of T frames at ``speaking_rate`` shifted by ``octaves``:
-    stretched_frames(T, speaking_rate * 2 ** -octaves) -- the length of ``init_phase``'s last axis.  ValueError where the
-    product leaves [0.25, 4]."""
+def synth_frame_counts(T, speaking_rate, octaves):
+    """``(T_wav, T_gl)`` of a synthesis call of T frames at ``speaking_rate`` shifted by ``octaves``, as csrc/synth_plan.h has
+    them: the waveform rows hold hop (T_wav - 1) samples, T_wav = stretched_frames(T, speaking_rate) -- the pitch changes no
+    shape -- and Griffin-Lim reconstructs from T_gl = stretched_frames(T, speaking_rate * 2 ** -octaves) frames.  Rate 1.0 and
+    pitch 0: (T, T).  ValueError where the product leaves [0.25, 4]."""
     eff = float(speaking_rate) * float(np.exp2(-np.float64(octaves)))
     if not SPEAKING_RATE_MIN <= eff <= SPEAKING_RATE_MAX:
         raise ValueError('speaking rate {} times 2 ** -{} octaves = {} is outside [0.25, 4]'.format(speaking_rate, octaves, eff))
-    return stretched_frames(T, eff)
+    T_wav = int(T) if speaking_rate == 1.0 else stretched_frames(T, speaking_rate)
+    return T_wav, T_wav if octaves == 0.0 else stretched_frames(T, eff)
 
 
-class _PitchScope(object):
-    """The pitch set for the calls made inside the block and put back afterwards, as _SpeakingRateScope does for its setting;
-    None: the handle's pitch as it stands."""
+def synth_lengths(n_frames, T, speaking_rate, octaves, min_frames):
+    """``(reported, gl)``, int32 arrays: the lengths such a call reports for utterances of ``n_frames`` frames -- those of the
+    call without pitch -- and the lengths its Griffin-Lim runs on.  An utterance has min(T_r, max(min_frames,
+    stretched_frames(n, r))) frames at rate r in rows of T_r; at rate 1.0 its length is n untouched."""
+    T_wav, T_gl = synth_frame_counts(T, speaking_rate, octaves)
+    n = np.asarray(n_frames, dtype=np.int32)
 
-    def __init__(self, engine, octaves):
-        self.engine = engine
-        self.value = pitch_octaves_value(octaves)
+    def at_rate(r, T_r):
+        return np.array([min(T_r, max(min_frames, stretched_frames(int(v), r))) for v in n], np.int32)
 
-    def __enter__(self):
-        self.saved = self.engine._pitch
-        if self.value is not None and self.value != self.saved:
-            self.engine.set_pitch(self.value)
+    stretch = speaking_rate != 1.0 or octaves != 0.0
+    gl = at_rate(float(speaking_rate) * float(np.exp2(-np.float64(octaves))), T_gl) if stretch else n
+    if octaves == 0.0:
+        return gl, gl
+    return (at_rate(speaking_rate, T_wav) if speaking_rate != 1.0 else n), gl
 
-    def __exit__(self, *exc):
-        if self.engine._pitch != self.saved:
-            self.engine.set_pitch(self.saved)
-        return False
+
+def pitch_frames(T, speaking_rate, octaves):
+    """The frames Griffin-Lim reconstructs from in a call of T frames at ``speaking_rate`` shifted by ``octaves`` -- the
+    length of ``init_phase``'s last axis.  ValueError where the product of the rate and 2 ** -octaves leaves [0.25, 4]."""
+    return synth_frame_counts(T, speaking_rate, octaves)[1]
+
+
+def _padded_rows(spec, B, T, F, stride):
+    """A host ``spec`` (B, T, F) as the (B, T, stride) float32 array that is uploaded for rows ``stride`` > F floats apart:
+    the contiguous array ``spec`` is the view ``a[:, :, :F]`` of, as it is, or a copy with NaN in the padding columns."""
+    base = spec.base if isinstance(spec, np.ndarray) else None
+    if (isinstance(base, np.ndarray) and base.shape == (B, T, stride) and base.dtype == np.float32 and
+            base.flags['C_CONTIGUOUS'] and spec.ctypes.data == base.ctypes.data):
+        return base
+    padded = np.full((B, T, stride), np.nan, dtype=np.float32)
+    padded[:, :, :F] = spec
+    return padded
 
 
 class Engine(object):
@@ -500,6 +482,7 @@ class Engine(object):
         self._end_of_speech = (False, 0.0, 0)   # ... and its end-of-speech setting (set_end_of_speech keeps it)
         self._speaking_rate = 1.0               # ... and its speaking rate (set_speaking_rate keeps it)
         self._pitch = 0.0                       # ... and its pitch in octaves (set_pitch keeps it)
+        self._host_shapes, self._host_out_shapes = {}, {}   # per ticket of synthesize_host, until its wait_host* call
         if stream is not None:
             self._check(self.lib.tts_set_stream(self.handle, c_void_p(stream)))
 
@@ -555,6 +538,18 @@ class Engine(object):
             raise ValueError('set_pitch: a shift in [-1, 1] octaves is needed')
         self._check(self.lib.tts_set_pitch(self.handle, o))
         self._pitch = o
+
+    def _momentum_scope(self, momentum):
+        return _SettingScope(self, '_gl_momentum', lambda v: self.set_option('gl_momentum', v),
+                             None if momentum is None else momentum_thousandths(momentum))
+
+    def _synth_scopes(self, momentum, stop_at_silence, speaking_rate, pitch):
+        """the scopes of a synthesis call's four settings (momentum, end of speech, rate, pitch), every value checked"""
+        stop = stop_at_silence_setting(stop_at_silence)
+        return (self._momentum_scope(momentum),
+                _SettingScope(self, '_end_of_speech', lambda v: self.set_end_of_speech(*v), None if stop is None else (True,) + stop),
+                _SettingScope(self, '_speaking_rate', self.set_speaking_rate, speaking_rate_value(speaking_rate)),
+                _SettingScope(self, '_pitch', self.set_pitch, pitch_octaves_value(pitch)))
 
     def synchronize(self):
         self._check(self.lib.tts_synchronize(self.handle))
@@ -766,7 +761,7 @@ class Engine(object):
         ``n_frames``: B frame counts -- a ragged batch (tts_griffin_lim_ragged): ``mag`` and ``init_phase`` are padded to
         (B, F, T_max), utterance b is reconstructed from its first n_frames[b] columns alone (the padding never reaches a
         result), row b of ``wav`` holds its hop (n_frames[b] - 1) samples followed by zeros and ``mse[b]`` is its own."""
-        scope = _MomentumScope(self, momentum)
+        scope = self._momentum_scope(momentum)
         B, F, T = mag.shape
         nf = ragged_frame_counts(n_frames, B, T, hop_length, n_fft) if n_frames is not None else None
         p_mag, _k1 = self._in(mag, np.float32)
@@ -818,14 +813,7 @@ class Engine(object):
         B, T, F = (int(d) for d in spec.shape)
         stride = F if row_stride is None else int(row_stride)
         if not _is_device(spec) and stride > F:
-            base = spec.base if isinstance(spec, np.ndarray) else None
-            if (isinstance(base, np.ndarray) and base.shape == (B, T, stride) and base.dtype == np.float32 and
-                    base.flags['C_CONTIGUOUS'] and spec.ctypes.data == base.ctypes.data):
-                spec = base
-            else:
-                padded = np.full((B, T, stride), np.nan, dtype=np.float32)
-                padded[:, :, :F] = spec
-                spec = padded
+            spec = _padded_rows(spec, B, T, F, stride)
         p_spec, _k = self._in(spec, np.float32)
         n_frames = self.empty((max(B, 1),), np.int32)
         last = self.empty((max(B, 1),), np.int32)
@@ -897,14 +885,7 @@ class Engine(object):
         if stride < F:
             raise ValueError('stretch_rows: row_stride {} < F = {}'.format(stride, F))
         if not _is_device(spec) and stride > F:
-            base = spec.base if isinstance(spec, np.ndarray) else None
-            if (isinstance(base, np.ndarray) and base.shape == (B, T, stride) and base.dtype == np.float32 and
-                    base.flags['C_CONTIGUOUS'] and spec.ctypes.data == base.ctypes.data):
-                spec = base
-            else:
-                padded = np.full((B, T, stride), np.nan, dtype=np.float32)
-                padded[:, :, :F] = spec
-                spec = padded
+            spec = _padded_rows(spec, B, T, F, stride)
         p_spec, _k = self._in(spec, np.float32)
         out = self.empty((B, T_out, stride))
         try:
@@ -1034,17 +1015,14 @@ class Engine(object):
         (tts_set_pitch): the magnitudes are stretched by rate * 2 ** -pitch, and the resampler takes Griffin-Lim's samples
         back to the length of the call without pitch.  No shape and no reported length changes but ``init_phase``'s, which is
         (B, F, ``pitch_frames(T, rate, pitch)``)."""
-        scope = _MomentumScope(self, momentum)   # (as in griffin_lim)
-        eos = _EndOfSpeechScope(self, stop_at_silence)
-        rate = _SpeakingRateScope(self, speaking_rate)
-        shift = _PitchScope(self, pitch)
+        scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call = self._speaking_rate if rate.value is None else rate.value
         o_call = self._pitch if shift.value is None else shift.value
-        T_wav = T if r_call == 1.0 else stretched_frames(T, r_call)
-        # (a product of rate and 2 ** -pitch outside [0.25, 4] is the library's to refuse, at the call)
-        T_init = T_wav if o_call == 0.0 or init_phase is None else pitch_frames(T, r_call, o_call)
+        # (without init_phase the pitch changes no shape here, and a product of rate and 2 ** -pitch outside [0.25, 4] is the
+        #  library's to refuse, at the call)
+        T_wav, T_init = synth_frame_counts(T, r_call, o_call if init_phase is not None else 0.0)
         F = 1 + self.cfg.n_fft // 2
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed,
                             1 if peak_normalize else 0)
@@ -1096,10 +1074,7 @@ class Engine(object):
         ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
         has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1))); ``pitch`` as in
         ``synthesize`` (no shape changes)."""
-        scope = _MomentumScope(self, momentum)
-        eos = _EndOfSpeechScope(self, stop_at_silence)
-        rate = _SpeakingRateScope(self, speaking_rate)
-        shift = _PitchScope(self, pitch)
+        scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -1107,13 +1082,10 @@ class Engine(object):
                             (1 if want_linear else 0) | (2 if want_alignments else 0))
         t = c_int(-1)
         r_call = self._speaking_rate if rate.value is None else rate.value
-        T = n_steps * self.cfg.reduction
-        T_wav = T if r_call == 1.0 else stretched_frames(T, r_call)
+        T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, r_call, 0.0)   # (the pitch changes no shape)
         with scope, eos, rate, shift:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
-        self._host_shapes = getattr(self, '_host_shapes', {})
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
-        self._host_out_shapes = getattr(self, '_host_out_shapes', {})
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))
         return t.value
 

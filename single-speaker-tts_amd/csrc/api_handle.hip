@@ -427,6 +427,7 @@ int ws_get(tts_handle_t h, const char* name, size_t bytes, void** out) {
         }
         HIPCHK(h, hipMalloc(&b.p, bytes));
         b.bytes = bytes;
+        ++h->ws_allocs;
     }
     *out = b.p;
     return TTS_OK;

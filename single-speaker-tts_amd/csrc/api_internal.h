@@ -13,6 +13,7 @@
 #include <vector>
 #include "decoder.h"
 #include "griffin_lim.h"
+#include "synth_plan.h"
 #include "tts_common.h"
 #include <algorithm>
 #include <map>
@@ -197,9 +198,15 @@ struct CallPipeline {
     // front and encoder streams have waited for it
     Signal serial_done;
     unsigned syn_calls = 0;
-    int syn_shape[3] = {0, 0, 0};   // (B, Ts, n_steps) of the previous tts_synthesize call
-    double syn_rho = 0.0;           // ... and the resampling ratio of its pitch (0: none)
-    int syn_tg = 0;                 // ... and the frames its Griffin-Lim reconstructed from (T, or T' with a speaking rate)
+    // The previous tts_synthesize call: its shape, the frames its Griffin-Lim reconstructed from (T, or what the speaking
+    // rate and the pitch made of them) and the resampling ratio of its pitch (0: none).  A call is pipelined from the second
+    // of a key on.
+    struct SynKey {
+        int B = 0, Ts = 0, n_steps = 0, Tg = 0;
+        double rho = 0.0;
+        bool same_network(int B_, int Ts_, int n_steps_) const { return B == B_ && Ts == Ts_ && n_steps == n_steps_; }
+        bool operator==(const SynKey& o) const { return same_network(o.B, o.Ts, o.n_steps) && Tg == o.Tg && rho == o.rho; }
+    } syn_prev;
     int last_enc_ahead = -1;        // did the previous PIPELINED call run its encoder ahead on `encs` (1) or on `front` (0)?
 
     // Every stream has been synchronised (sync_all): nothing recorded so far orders anything any more
@@ -340,8 +347,10 @@ struct tts_handle_s {
     const float* dense_b = nullptr;
     const float* zeros = nullptr;   // TTS_MAX_N_MELS zero floats inside the arena
 
-    // workspace (grow-only)
+    // workspace (grow-only); ws_allocs: the allocations ws_get has made -- a caller that reads it around a request knows
+    // whether the buffer is new or grew
     std::map<std::string, DevBuf> ws;
+    unsigned ws_allocs = 0;
 
     // decoder graph cache
     hipGraphExec_t dec_graph = nullptr;
@@ -406,10 +415,11 @@ struct tts_handle_s {
     // speaking rate (tts_set_speaking_rate): read when a call is made; 1.0 = off, the call then enqueues what it always did
     double speaking_rate = 1.0;
 
-    // pitch (tts_set_pitch), in octaves: read when a call is made; 0 = off, the call then enqueues what it always did.
-    // pitch_lens: the frames the last shifted call's Griffin-Lim ran on (the call reports the un-shifted call's lengths)
+    // pitch (tts_set_pitch), in octaves: read when a call is made; 0 = off, the call then enqueues what it always did
     double pitch_octaves = 0.0;
-    std::vector<int32_t> pitch_lens, pitch_samples, pitch_keep;
+
+    // the per-utterance lengths of the last tts_synthesize call (synth_plan.h): Griffin-Lim and the resampler are given them
+    SynthLengths syn_lens;
 
     // the resampler (resample.hip): the half window before a ratio's scale, and the phase-major tables per ratio on the device
     struct {
@@ -538,7 +548,6 @@ int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers,
 int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr, const int* d_frames = nullptr);
 // end of speech (speech_end.hip / api_stages.hip)
 int speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
-int speech_min_frames(int n_fft, int hop);   // the smallest n with hop (n - 1) > n_fft / 2
 int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int keep_frames, int min_frames, int32_t* n_frames, int32_t* last_active);
 // speaking rate (stretch.hip): both layouts of the time-stretch, arguments checked by the caller (stretch_plan.h)
 int stretch_impl(tts_handle_t h, const float* in, int B, int T, int F, int row_stride, bool time_major, const int32_t* n_frames, double rate,

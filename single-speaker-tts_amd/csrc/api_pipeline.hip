@@ -1,8 +1,6 @@
 // C ABI, part 3: the call pipeline -- tts_synthesize (three calls in flight on the main, front and encoder streams, events per
 // call parity, the wide Griffin-Lim launches), its host-memory form and the tickets of tts_wait_host.
 #include "api_internal.h"
-#include "stretch_plan.h"
-#include "resample_plan.h"
 
 namespace tts_api {
 
@@ -58,32 +56,19 @@ struct SynthCall {
     float2* phase_pair[2] = {nullptr, nullptr};
     int parity = 0;
     bool enc_ahead_cfg = false;
-    bool mom_grows = false;      // this call allocates (or grows) the momentum buffer
-    bool eos_grows = false;      // ... or a buffer of end-of-speech stopping
     bool pipelined = false;
     int* hold_flag = nullptr;    // synth_order_front: the sleepers' flag, where sleepers hold compute units for this call
     std::optional<GemmGroup> proj;   // synth_front: the decoder's output projection, left to the main stream
     // end-of-speech stopping (tts_set_end_of_speech), as the handle's setting stood when the call was made: the threshold in the
-    // units of `magi`, the frames kept behind the last active one, the shortest utterance Griffin-Lim takes
+    // units of `magi` and the frames kept behind the last active one
     bool eos = false;
     float eos_thr = 0.f;
-    int eos_keep = 0, eos_min = 1;
+    int eos_keep = 0;
     int32_t* d_frames = nullptr;   // the lengths on the device (workspace "eos.frames")
-    // speaking rate (tts_set_speaking_rate), as the handle's setting stood when the call was made.  Tg: the frames Griffin-Lim
-    // reconstructs from -- T with the setting off, else stretched_frames(T, rate) rows of `mags`, the time-stretch of `magi`
-    bool stretch = false;
-    double rate = 1.0;
-    int Tg = 0;
-    float* mags = nullptr;
-    bool st_grows = false;       // this call allocates (or grows) the stretched magnitudes
-    // pitch (tts_set_pitch), likewise.  `rate` is then the speaking rate times rho = exp2(-octaves), Griffin-Lim writes its
-    // hop (Tg - 1) samples to `gl_wav` without normalising them, and the resampler takes them by rho into the rows of `wav`,
-    // hop (Tw - 1) samples, Tw = stretched_frames(T, rate_s): the shapes and lengths of the call without pitch
-    bool pitch = false;
-    double rho = 1.0, rate_s = 1.0;
-    int Tw = 0;
-    float* gl_wav = nullptr;
-    bool pt_grows = false;       // this call allocates (or grows) Griffin-Lim's own waveform buffer
+    // what the speaking rate (tts_set_speaking_rate) and the pitch (tts_set_pitch) make of the call's frames, likewise
+    SynthShape shape;
+    float* mags = nullptr;         // the time-stretch of `magi`, shape.Tg rows: what Griffin-Lim reconstructs from
+    float* gl_wav = nullptr;       // a shifted call: Griffin-Lim's hop (Tg - 1) samples, which the resampler takes into `wav`
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -102,7 +87,13 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     auto& pl = h->pl;
     const tts_synth_params_t* sp = k.sp;
     const int B = k.B, Ts = k.Ts, T = k.T, FP = k.FP;
-    const int Tg = k.Tg;   // (everything of Griffin-Lim is sized for the frames it reconstructs from)
+    const int Tg = k.shape.Tg;   // (everything of Griffin-Lim is sized for the frames it reconstructs from)
+    // A buffer of this call's settings -- momentum, speaking rate, pitch, end-of-speech stopping -- is new or grew: counted in
+    // the allocations ws_get makes (h->ws_allocs) across those blocks alone.  The setting was switched on, or to another
+    // value, between two calls of a shape, and this call is unpipelined like the first of a shape.  (Not across the other
+    // workspaces: a call whose caller stops passing mel_out allocates "syn.mel0" and stays pipelined.)
+    bool setting_grew = false;
+    unsigned allocs = 0;
     if (!k.gl_streaming) {
         // the general kernels' tables and workspaces, sized HERE, before anything of this call is enqueued on the front or
         // encoder streams (a growing workspace synchronises every stream; gl_run_generic finds them in place)
@@ -117,9 +108,10 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "glg.mse_partial", float, (size_t)B * Tg, glg_ms);
         (void)glg_ph; (void)glg_fr; (void)glg_ms;
         if (h->gl_momentum > 0 && sp->n_iter > 1) {
-            k.mom_grows = h->ws["glg.mom"].bytes < (size_t)B * Tg * FP * sizeof(float2);
+            allocs = h->ws_allocs;
             WS(h, "glg.mom", float2, (size_t)B * Tg * FP, glg_mc);
             (void)glg_mc;
+            setting_grew |= h->ws_allocs != allocs;
         }
     }
     // (one encoder output per call parity: the encoder of call k + 1 writes one while the decoder of call k reads the other)
@@ -128,8 +120,7 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     // (alternating only where the encoder really runs ahead: under the call pipeline with the persistent decoder.  The
     //  launch-per-layer decoder replays a hipGraph with its buffers baked in -- a second `memory` would re-capture it every call)
     k.enc_ahead_cfg = h->enc_stream && h->pipeline && (h->own_stream || h->pipeline >= 2) &&
-                      pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps &&
-                      h->reserve_cus > 0 && pd_choice(h, B, Ts, h->reserve_cus, true) != 0;
+                      pl.syn_prev.same_network(B, Ts, sp->n_steps) && h->reserve_cus > 0 && pd_choice(h, B, Ts, h->reserve_cus, true) != 0;
     k.memory = (k.enc_ahead_cfg && (pl.syn_calls & 1)) ? memory_o : memory_e;   // (syn_calls is advanced below: this call's parity)
     // the attention keys of that memory, likewise: made behind the encoder on ITS stream, so that nothing but two fills
     // stands between two decoders on the front stream (the 0.04 ms GEMM was on the step's critical path there)
@@ -147,22 +138,16 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     }
     WS(h, "gl.mag", float, (size_t)B * T * FP, magi);
     k.magi = magi;
-    if (k.stretch) {
-        // (the setting switched on, or another rate, between two calls of a shape: this call is unpipelined, as with the
-        //  momentum buffer; same_shape below also compares Tg, which sizes the phasor codes)
-        k.st_grows = h->ws["gl.mag_st"].bytes < (size_t)B * Tg * FP * sizeof(float);
+    allocs = h->ws_allocs;
+    if (k.shape.stretch) {   // (same_call below also compares Tg, which sizes the phasor codes)
         WS(h, "gl.mag_st", float, (size_t)B * Tg * FP, mags);
         k.mags = mags;
     }
-    // (the pitch switched on, off or to another shift between two calls of a shape: this call is unpipelined, as with the rate)
-    k.pt_grows = pl.syn_rho != (k.pitch ? k.rho : 0.0);
-    pl.syn_rho = k.pitch ? k.rho : 0.0;
-    if (k.pitch) {
-        const size_t n_gl = (size_t)B * sp->hop_length * (size_t)(Tg - 1);
-        k.pt_grows = k.pt_grows || h->ws["gl.wav_pitch"].bytes < n_gl * sizeof(float);
-        WS(h, "gl.wav_pitch", float, n_gl, glw);
+    if (k.shape.pitch) {
+        WS(h, "gl.wav_pitch", float, (size_t)B * sp->hop_length * (size_t)(Tg - 1), glw);
         k.gl_wav = glw;
     }
+    setting_grew |= h->ws_allocs != allocs;
     // Under the call pipeline the initial phasors of a call are written on the FRONT stream, behind its decoder (that
     // stream has slack, the main one bounds the step): the phasor-code buffers are then a pair per call parity, so that
     // the write does not wait for the previous call's Griffin-Lim.  All four are sized here, before anything is enqueued
@@ -174,8 +159,8 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     WS(h, "syn.phase1.odd", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph1o);
     // (momentum: the previous projection, 8 bytes per bin; ONE buffer -- only Griffin-Lim launches touch it, and those of
     //  consecutive calls follow each other on the main stream)
+    allocs = h->ws_allocs;
     if (k.gl_streaming && h->gl_momentum > 0 && sp->n_iter > 1) {
-        k.mom_grows = h->ws["gl.mom"].bytes < (size_t)B * Tg * FP * sizeof(float2);
         WS(h, "gl.mom", float2, (size_t)B * Tg * FP, gl_mc);
         (void)gl_mc;
     }
@@ -184,22 +169,19 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         // size and finds them in place) and the pinned words the host reads the lengths from: nothing grows in mid-call
         const size_t rw_row = k.gl_streaming ? 2 * (size_t)gl_rw_edge_len(c.n_fft, sp->win_length, sp->hop_length)
                                              : (size_t)c.n_fft + (size_t)sp->hop_length * (Tg - 1);
-        // (the setting switched on between two calls of a shape: a buffer that is new or grows -- a larger stand-alone ragged
-        //  call may have left a smaller one -- makes this call unpipelined, as the momentum buffer does)
-        k.eos_grows = h->ws["eos.active"].bytes < (size_t)B * T || h->ws["eos.frames"].bytes < (size_t)B * sizeof(int32_t) ||
-                      h->ws["gl.rag_rw"].bytes < (size_t)B * rw_row * sizeof(float) || h->eos.pinned_room < B;
+        // (a larger stand-alone ragged call may have left smaller buffers: growing them counts like making them)
         WS(h, "eos.active", unsigned char, (size_t)B * T, eos_act);
         WS(h, "eos.frames", int32_t, (size_t)B, eos_fr);
         (void)eos_act;
         k.d_frames = eos_fr;
         WS(h, "gl.rag_rw", float, (size_t)B * rw_row, eos_rw);
         (void)eos_rw;
-        if (k.stretch) {   // (the stretched lengths are the host's: the ragged Griffin-Lim uploads them, gl_rag_tables)
-            k.eos_grows = k.eos_grows || h->ws["gl.rag_lens"].bytes < (size_t)B * sizeof(int);
+        if (k.shape.stretch) {   // (the stretched lengths are the host's: the ragged Griffin-Lim uploads them, gl_rag_tables)
             WS(h, "gl.rag_lens", int, (size_t)B, eos_lens);
             (void)eos_lens;
         }
         if (h->eos.pinned_room < B) {   // (read behind a synchronisation inside the call that filled it: never in flight here)
+            setting_grew = true;
             if (h->eos.pinned) HIPCHK(h, hipHostFree(h->eos.pinned));
             h->eos.pinned = nullptr;
             h->eos.pinned_room = 0;
@@ -207,20 +189,20 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
             h->eos.pinned_room = B;
         }
     }
+    setting_grew |= h->ws_allocs != allocs;
     k.phase_pair[0] = reinterpret_cast<float2*>(parity ? gph0o : gph0e);
     k.phase_pair[1] = reinterpret_cast<float2*>(parity ? gph1o : gph1e);
     // Pipelined only while the library owns its stream (inputs on a borrowed stream may still be in flight) and
     // from the second call of a shape on: the first call of a new (B, Ts, n_steps) grows the workspaces, which
     // synchronises every stream -- under the CU reservation that would park the host on the sleepers' 100 ms bound.
-    // (the momentum option switched on between two calls of a shape: its buffer is new, and this call is unpipelined like the
-    //  first of a shape; likewise the end-of-speech setting and its buffers)
-    const bool same_shape = pl.syn_shape[0] == B && pl.syn_shape[1] == Ts && pl.syn_shape[2] == sp->n_steps && !k.mom_grows && !k.eos_grows &&
-                            pl.syn_tg == Tg && !k.st_grows && !k.pt_grows;
-    pl.syn_tg = Tg;
-    pl.syn_shape[0] = B; pl.syn_shape[1] = Ts; pl.syn_shape[2] = sp->n_steps;
+    // (a setting switched between two calls of a shape: another Tg or another pitch in the key, or a buffer of the setting
+    //  that is new -- setting_grew above)
+    const CallPipeline::SynKey key{B, Ts, sp->n_steps, Tg, k.shape.pitch ? k.shape.rho : 0.0};
+    const bool same_call = key == pl.syn_prev && !setting_grew;
+    pl.syn_prev = key;
     // (a borrowed stream is pipelined only on request, pipeline = 2: the caller then vouches that the inputs of a call
     //  are complete when it is made -- the library cannot tell them from the previous call's work on that stream)
-    k.pipelined = h->pipeline && (h->own_stream || h->pipeline >= 2) && same_shape;
+    k.pipelined = h->pipeline && (h->own_stream || h->pipeline >= 2) && same_call;
     return TTS_OK;
 }
 
@@ -361,25 +343,24 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
     return TTS_OK;
 }
 
-// Step 5a, end-of-speech stopping: the lengths of this call's utterances, from its magnitudes on the main stream to h->eos.last.
+// Step 5a, end-of-speech stopping: the lengths of this call's utterances, from its magnitudes on the main stream to h->eos.pinned.
 // The HOST waits here for the post-net.  Everything this call puts on the front and encoder streams has been enqueued by now,
 // and the call returns as soon as the lengths are read and its Griffin-Lim is enqueued: the next call's encoder and decoder,
 // enqueued by that call, run beside this call's Griffin-Lim as they do without the wait.  What the wait costs (1.0 ms per
 // batch at 64 x 1000 frames, profiles/eos.txt) is mostly WHEN the next call gets made: its encoder starts beside the first
 // Griffin-Lim launches instead of beside this post-net; the detection is 0.06 ms, the read-back and the enqueue a launch gap.
-static int synth_lengths(tts_handle_t h, SynthCall& k) {
-    const int B = k.B, T = k.T;
-    int rc = speech_frames_impl(h, k.magi, B, T, k.F, k.FP, k.eos_thr, k.eos_keep, k.eos_min, k.d_frames, nullptr);
+static int synth_detect(tts_handle_t h, SynthCall& k) {
+    const int B = k.B, T = k.T, min_frames = k.shape.min_frames;
+    int rc = speech_frames_impl(h, k.magi, B, T, k.F, k.FP, k.eos_thr, k.eos_keep, min_frames, k.d_frames, nullptr);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->eos.pinned, k.d_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     // (what the launches below are cut for and index with: checked again on this side)
     for (int b = 0; b < B; ++b)
-        if (h->eos.pinned[b] < k.eos_min || h->eos.pinned[b] > T)
+        if (h->eos.pinned[b] < min_frames || h->eos.pinned[b] > T)
             return fail(h, TTS_ERR_HIP, "synthesize: the end-of-speech detection returned " + std::to_string(h->eos.pinned[b]) +
-                                            " frames for utterance " + std::to_string(b) + ", outside [" + std::to_string(k.eos_min) +
+                                            " frames for utterance " + std::to_string(b) + ", outside [" + std::to_string(min_frames) +
                                             ", " + std::to_string(T) + "]");
-    h->eos.last.assign(h->eos.pinned, h->eos.pinned + B);
     return TTS_OK;
 }
 
@@ -387,7 +368,8 @@ static int synth_lengths(tts_handle_t h, SynthCall& k) {
 static int synth_main(tts_handle_t h, SynthCall& k) {
     auto& pl = h->pl;
     const tts_synth_params_t* sp = k.sp;
-    const int B = k.B, T = k.T, Tg = k.Tg, parity = k.parity;
+    const SynthShape& s = k.shape;
+    const int B = k.B, T = k.T, Tg = s.Tg, parity = k.parity;
     int rc = TTS_OK;
     // (a seeded start with iterations needs no initial codes at all: gl_run)
     const bool phase_on_front = k.gl_streaming && k.pipelined && sp->n_iter >= 0 && (k.init_phase != nullptr || sp->n_iter == 0);
@@ -413,72 +395,38 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     if (db_flag && (rc = denorm_flag_read(h))) return rc;   // as the reference: no waveform for such a spectrogram
     // (also for an unpipelined call between pipelined ones: its buffers are the same ones)
     if (pl.front) HIPCHK(h, pl.post_done[parity].record(h->stream));
-    // the lengths: all T without end-of-speech stopping -- and a call that stops nowhere IS the uniform call
-    const int32_t* n_frames = nullptr;
-    int T_model = Tg;   // (gl_wide_from's model counts frames: a ragged batch is as long as its mean length)
+    // the lengths (synth_plan.h): all T without end-of-speech stopping -- and a call that stops nowhere IS the uniform call
+    const int32_t* detected = nullptr;
     if (k.eos) {
-        if ((rc = synth_lengths(h, k))) return rc;
-    } else {
-        h->eos.last.assign((size_t)B, T);
+        if ((rc = synth_detect(h, k))) return rc;
+        detected = h->eos.pinned;
     }
-    if (k.stretch) {
-        // The speaking rate: Griffin-Lim reconstructs from the time-stretch of this call's magnitudes (one pass, stretch.hip).
-        // Frames behind an utterance's end are not read; the lengths become min(Tg, max(min_frames, stretched_frames(n))) --
-        // whatever that adds to an utterance is the vocoder's zero padding, which the pass writes.
-        if ((rc = stretch_impl(h, k.magi, B, T, k.F, k.FP, true, k.eos ? h->eos.last.data() : nullptr, k.rate, Tg, k.mags))) return rc;
-        // (with a pitch Griffin-Lim runs on the lengths at rate s rho, and the call reports those at rate s: the un-shifted call's)
-        h->pitch_lens.resize(k.pitch ? (size_t)B : 0);
-        for (int b = 0; b < B; ++b) {
-            const int n = h->eos.last[b];
-            const long long m = std::max<long long>(k.eos_min, stretched_frames(n, k.rate));
-            const int32_t n_gl = (int32_t)std::min<long long>(Tg, m);
-            if (!k.pitch) {
-                h->eos.last[b] = n_gl;
-                continue;
-            }
-            h->pitch_lens[b] = n_gl;
-            if (k.rate_s != 1.0)
-                h->eos.last[b] = (int32_t)std::min<long long>(k.Tw, std::max<long long>(k.eos_min, stretched_frames(n, k.rate_s)));
-        }
-    }
-    const std::vector<int32_t>& gl_lens = k.pitch ? h->pitch_lens : h->eos.last;
-    if (k.eos) {
-        long long sum = 0;
-        for (int b = 0; b < B; ++b) sum += gl_lens[b];
-        if (sum != (long long)B * Tg) {
-            n_frames = gl_lens.data();
-            T_model = (int)((sum + B - 1) / B);
-        }
-    }
-    const float* gl_mag = k.stretch ? k.mags : k.magi;
+    SynthLengths& L = h->syn_lens;
+    synth_lengths(s, T, sp->hop_length, B, detected, &L);
+    h->eos.last = L.reported;
+    // The speaking rate: Griffin-Lim reconstructs from the time-stretch of this call's magnitudes (one pass, stretch.hip).
+    // Frames behind an utterance's end are not read; whatever the stretched length adds to an utterance is the vocoder's zero
+    // padding, which the pass writes.
+    if (s.stretch && (rc = stretch_impl(h, k.magi, B, T, k.F, k.FP, true, detected, s.rate, Tg, k.mags))) return rc;
+    const int32_t* n_frames = L.ragged ? L.gl.data() : nullptr;
+    const float* gl_mag = s.stretch ? k.mags : k.magi;
     // (the device's lengths are those of the detection: with a speaking rate the host's stretched ones are uploaded instead)
-    const int* d_frames = (n_frames && !k.stretch) ? k.d_frames : nullptr;
-    const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, T_model, sp->n_iter) : -1;
+    const int* d_frames = (n_frames && !s.stretch) ? k.d_frames : nullptr;
+    const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, L.T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
-    float* gl_wav = k.pitch ? k.gl_wav : k.wav;
-    const bool gl_peak = sp->peak_normalize != 0 && !k.pitch;   // (a shifted call normalises what the resampler leaves)
+    float* gl_wav = s.pitch ? k.gl_wav : k.wav;
+    const bool gl_peak = sp->peak_normalize != 0 && !s.pitch;   // (a shifted call normalises what the resampler leaves)
     if (k.gl_streaming)
         rc = gl_run(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
                     gl_peak, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
     else
         rc = gl_run_generic(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav,
                             nullptr, gl_peak, n_frames, d_frames);
-    if (k.pitch && !rc) {
+    if (s.pitch && !rc) {
         // The pitch: the hop (Tg - 1) samples Griffin-Lim made, resampled by rho into the rows of the call without pitch.  With
         // end-of-speech stopping utterance b has hop (n'[b] - 1) samples, and its row ends where the un-shifted call's does.
-        const int n_gl = sp->hop_length * (Tg - 1), N_out = sp->hop_length * (k.Tw - 1);
-        const int32_t *ns = nullptr, *cap = nullptr;
-        if (k.eos) {
-            h->pitch_samples.resize((size_t)B);
-            h->pitch_keep.resize((size_t)B);
-            for (int b = 0; b < B; ++b) {
-                h->pitch_samples[b] = sp->hop_length * (h->pitch_lens[b] - 1);
-                h->pitch_keep[b] = sp->hop_length * (h->eos.last[b] - 1);
-            }
-            ns = h->pitch_samples.data();
-            cap = h->pitch_keep.data();
-        }
-        rc = resample_impl(h, k.gl_wav, B, n_gl, ns, k.rho, N_out, cap, k.wav);
+        const int n_gl = sp->hop_length * (Tg - 1), N_out = sp->hop_length * (s.Tw - 1);
+        rc = resample_impl(h, k.gl_wav, B, n_gl, detected ? L.n_samples.data() : nullptr, s.rho, N_out, detected ? L.keep.data() : nullptr, k.wav);
         if (!rc && sp->peak_normalize) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
     }
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
@@ -498,44 +446,17 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
         return fail(h, TTS_ERR_UNSUPPORTED, "synthesize: n_fft must be a power of two between 256 and 4096");
     SynthCall k{ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, &host, sp->n_steps * c.reduction,
                 1 + c.n_fft / 2, gl_fp(c.n_fft), gl_is_streaming(c.n_fft, sp->win_length, sp->hop_length)};
-    k.Tg = k.T;
-    k.eos_min = sp->hop_length >= 1 ? speech_min_frames(c.n_fft, sp->hop_length) : 1;   // (the hop is checked below)
-    k.Tw = k.T;
-    // (read here, once, as the end-of-speech setting below; rate 1.0 and pitch 0: nothing of this call changes)
-    if (h->speaking_rate != 1.0 || h->pitch_octaves != 0.0) {
-        if (sp->hop_length < 1) return fail(h, TTS_ERR_INVALID, "synthesize: hop_length >= 1");
-        k.stretch = true;
-        k.rate = h->speaking_rate;
-        if (k.rate != 1.0) k.Tw = (int)stretched_frames(k.T, k.rate);
-        if (h->pitch_octaves != 0.0) {
-            k.pitch = true;
-            k.rho = std::exp2(-h->pitch_octaves);
-            k.rate_s = h->speaking_rate;
-            k.rate = k.rate_s * k.rho;
-            if (!stretch_rate_ok(k.rate))
-                return fail(h, TTS_ERR_INVALID, "synthesize: the speaking rate times 2 ** -octaves of the pitch is " + std::to_string(k.rate) +
-                                                    ", outside [0.25, 4]");
-            // (the rows of a shifted call are those of the call without pitch, which this refusal is of: T_s = T at rate 1.0)
-            if (k.Tw < k.eos_min)
-                return fail(h, TTS_ERR_INVALID, "synthesize: with a pitch the call's rows hold " + std::to_string(k.Tw) + " frames" +
-                                                    (k.rate_s != 1.0 ? " at this speaking rate" : "") + ", the call without pitch needs at least " +
-                                                    std::to_string(k.eos_min) + " (hop (n - 1) > n_fft / 2)");
-            const double* tab_unused = nullptr;   // (the ratio's table, made before anything of this call is enqueued)
-            if ((rc = resample_table(h, k.rho, &tab_unused))) return rc;
-        }
-        k.Tg = (int)stretched_frames(k.T, k.rate);
-        if (k.Tg < k.eos_min)
-            return fail(h, TTS_ERR_INVALID, std::string("synthesize: the speaking rate") + (k.pitch ? " and the pitch leave " : " leaves ") + std::to_string(k.Tg) + " frames, Griffin-Lim needs at least " +
-                                                std::to_string(k.eos_min) + " (hop (n - 1) > n_fft / 2)");
-    }
-    if (k.gl_streaming && (rc = gl_prepare(h, k.Tg, sp->win_length, sp->hop_length, c.n_fft))) return rc;
+    // (the settings are read here, once: refusals come before anything is enqueued; rate 1.0 and pitch 0: nothing of this call changes)
+    const std::string refusal = synth_shape(k.T, c.n_fft, sp->hop_length, h->speaking_rate, h->pitch_octaves, h->eos.enabled != 0, &k.shape);
+    if (!refusal.empty()) return fail(h, TTS_ERR_INVALID, "synthesize: " + refusal);
+    const double* tab_unused = nullptr;   // (the ratio's table, made before anything of this call is enqueued)
+    if (k.shape.pitch && (rc = resample_table(h, k.shape.rho, &tab_unused))) return rc;
+    if (k.gl_streaming && (rc = gl_prepare(h, k.shape.Tg, sp->win_length, sp->hop_length, c.n_fft))) return rc;
     if (!k.gl_streaming && (sp->win_length < 2 || sp->win_length > c.n_fft || sp->hop_length < 1))
         return fail(h, TTS_ERR_INVALID, "synthesize: need 2 <= win_length <= n_fft, hop_length >= 1");
-    if (h->eos.enabled) {   // (the setting is read here, once: refusals come before anything is enqueued)
+    if (h->eos.enabled) {
         k.eos = true;
         k.eos_keep = h->eos.keep_frames;
-        if (k.T < k.eos_min)
-            return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs at least " + std::to_string(k.eos_min) + " frames (hop (n - 1) > n_fft / 2)");
         if (speech_threshold(h->eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
             return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
     }
@@ -574,10 +495,12 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
         return fail(h, TTS_ERR_INVALID, "synthesize_host: bad arguments");
     auto& io = h->hio;
     const int T = sp->n_steps * h->cfg.reduction;
-    // (with a speaking rate the waveforms have hop (T' - 1) samples: the pinned and device buffers are sized for them)
-    const long long Tg = h->speaking_rate != 1.0 ? stretched_frames(T, h->speaking_rate) : T;
+    // (with a speaking rate the waveforms have hop (Tw - 1) samples: the pinned and device buffers are sized for them.  What
+    //  the plan refuses is synthesize_impl's to report, below; Tw = stretched_frames(T, speaking_rate) stands either way)
+    SynthShape shape;
+    synth_shape(T, h->cfg.n_fft, sp->hop_length, h->speaking_rate, h->pitch_octaves, h->eos.enabled != 0, &shape);
     const size_t ids_bytes = (size_t)B * Ts * sizeof(int32_t);
-    const size_t n_wav = (size_t)B * sp->hop_length * (size_t)(Tg - 1);
+    const size_t n_wav = (size_t)B * sp->hop_length * (size_t)(shape.Tw - 1);
     const bool want_lin = (sp->host_outputs & TTS_HOST_LINEAR) != 0, want_ali = (sp->host_outputs & TTS_HOST_ALIGNMENTS) != 0;
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;

@@ -74,8 +74,6 @@ __global__ __launch_bounds__(SE_THREADS) void speech_last_kernel(const unsigned 
 
 namespace tts_api {
 
-int speech_min_frames(int n_fft, int hop) { return (n_fft / 2) / hop + 2; }
-
 int speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out) {
     if (!out || threshold_db != threshold_db) return TTS_ERR_INVALID;
     double v;

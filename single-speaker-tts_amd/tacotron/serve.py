@@ -8,7 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import momentum_thousandths, pitch_frames, pitch_octaves_value, speaking_rate_value, stretched_frames
+from .._hip import momentum_thousandths, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
 from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_sentence, stop_setting
 from .model import Mode, Tacotron
@@ -39,8 +39,6 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
     rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
     rho = float(np.exp2(-np.float64(octaves)))
-    if octaves != 0.0:
-        pitch_frames(1, rate, octaves)   # (ValueError where rate * rho leaves [0.25, 4])
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
     win_hop = ms_to_samples(model_params.win_hop, model_params.sampling_rate)
@@ -50,32 +48,24 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
     n_frames = None
     T = spec.shape[1]
     min_frames = (model_params.n_fft // 2) // win_hop + 2   # the shortest signal Griffin-Lim takes: hop (n - 1) > n_fft / 2
-    if rate != 1.0 and stretched_frames(T, rate) < min_frames:
-        raise ValueError('speaking_rate {}: {} frames are left of {}, at least {} needed'.format(rate, stretched_frames(T, rate), T, min_frames))
+    # the frames of the waveforms, with or without a pitch, and the frames Griffin-Lim reconstructs from (ValueError where
+    # rate * rho leaves [0.25, 4])
+    T_s, T_g = synth_frame_counts(T, rate, octaves)
+    if rate != 1.0 and T_s < min_frames:
+        raise ValueError('speaking_rate {}: {} frames are left of {}, at least {} needed'.format(rate, T_s, T, min_frames))
+    if octaves != 0.0 and T_g < min_frames:
+        raise ValueError('pitch {} at speaking_rate {}: {} frames are left of {}, at least {} needed'.format(octaves, rate, T_g, T, min_frames))
     if stop is not None:
         if T < min_frames:
             raise ValueError('stop_at_silence_db: spectrograms of {} frames, at least {} needed'.format(T, min_frames))
         thr = engine.speech_threshold(stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
         n_frames = engine.speech_frames(spec, thr, keep_frames=stop[1], min_frames=min_frames)[0].to_host()
     mag = engine.denorm_power(spec, loader.mel_mag_ref_db, loader.mel_mag_max_db, model_params.magnitude_power)
-    def stretched(lengths, r, T_r):
-        return np.array([min(T_r, max(min_frames, stretched_frames(int(n), r))) for n in lengths], np.int32)
-
-    T_s = T if rate == 1.0 else stretched_frames(T, rate)   # the frames of the waveforms, with or without a pitch
-    n_gl = n_frames                                          # the frames Griffin-Lim runs on
-    if octaves != 0.0:
-        eff = rate * rho
-        T_g = stretched_frames(T, eff)
-        if T_g < min_frames:
-            raise ValueError('pitch {} at speaking_rate {}: {} frames are left of {}, at least {} needed'.format(octaves, rate, T_g, T, min_frames))
-        mag = engine.stretch_magnitudes(mag, eff, n_frames=n_frames, T_out=T_g)
+    n_gl = n_frames   # the frames Griffin-Lim runs on
+    if rate != 1.0 or octaves != 0.0:
+        mag = engine.stretch_magnitudes(mag, rate * rho, n_frames=n_frames, T_out=T_g)
         if n_frames is not None:
-            n_gl = stretched(n_frames, eff, T_g)
-            n_frames = stretched(n_frames, rate, T_s) if rate != 1.0 else n_frames
-    elif rate != 1.0:
-        mag = engine.stretch_magnitudes(mag, rate, n_frames=n_frames, T_out=T_s)
-        if n_frames is not None:
-            n_gl = n_frames = stretched(n_frames, rate, T_s)
+            n_frames, n_gl = synth_lengths(n_frames, T, rate, octaves, min_frames)
     wav, _ = engine.griffin_lim(mag, model_params.reconstruction_iterations, win_len, win_hop, model_params.n_fft,
                                 init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_gl)
     if octaves != 0.0:

@@ -180,6 +180,54 @@ def test_host_form_is_the_device_form(case):
     assert np.array_equal(bits(eng.wait_host(off)), bits(c.off['wav']))
 
 
+def test_settings_in_sequence_on_one_handle_are_the_fresh_handles_calls(case):
+    """What a handle carries from call to call -- the plan's per-utterance lengths, the previous call's key, the buffers of the
+    settings -- reaches no result: one handle taken through off, momentum, stopping, rate, pitch, all three and off again, every
+    call made twice in a row (the first grows that setting's buffers, the second goes through the pipeline's streams), returns
+    the waveforms and the frame counts, bit for bit, of a fresh handle that makes that one call."""
+    c, cs = case, case.case
+    settings = [('off', {}), ('momentum', dict(momentum=0.99)), ('stopping', dict(stop_at_silence=c.stop)),
+                ('rate', dict(speaking_rate=1.2)), ('pitch', dict(pitch=UP)),
+                ('all', dict(stop_at_silence=c.stop, speaking_rate=1.2, pitch=UP)), ('off', {})]
+
+    def engine():
+        eng = pkg().Engine(c.hp)
+        eng.load_weights(E.weights_of(cs))
+        return eng
+
+    def call(eng, kw):
+        out = eng.synthesize(c.ids, cs['S'], E.REF_DB, E.MAX_DB, E.POWER, cs['n_iter'], cs['win'], cs['hop'], seed=SEED,
+                             peak_normalize=False, **kw)
+        return out['wav'].to_host(), eng.synth_frames(c.B).tolist()
+
+    fresh = {}
+    for name, kw in settings:
+        if name not in fresh:
+            eng = engine()
+            try:
+                fresh[name] = call(eng, kw)
+            finally:
+                eng.close()
+    # the settings are six different calls
+    assert fresh['off'][1] == fresh['momentum'][1] == fresh['pitch'][1] == [c.T] * c.B
+    assert fresh['stopping'][1] == c.detected.tolist() and fresh['rate'][1] == [S.stretched_frames(c.T, 1.2)] * c.B
+    assert fresh['all'][1] == c.lengths(1.2, S.stretched_frames(c.T, 1.2)).tolist()
+    assert fresh['pitch'][0].shape == fresh['off'][0].shape and fresh['all'][0].shape == fresh['rate'][0].shape != fresh['off'][0].shape
+    for name in ('momentum', 'stopping', 'pitch'):
+        assert not np.array_equal(bits(fresh[name][0]), bits(fresh['off'][0])), name
+    assert not np.array_equal(bits(fresh['all'][0]), bits(fresh['rate'][0]))
+    eng = engine()
+    try:
+        for name, kw in settings:
+            for nth in (1, 2):
+                wav, frames = call(eng, kw)
+                assert frames == fresh[name][1], (name, nth)
+                assert wav.shape == fresh[name][0].shape and np.array_equal(bits(wav), bits(fresh[name][0])), (name, nth)
+        assert eng._gl_momentum == 0 and eng._end_of_speech == (False, 0.0, 0) and eng._speaking_rate == 1.0 and eng._pitch == 0.0
+    finally:
+        eng.close()
+
+
 def test_momentum_composes(case):
     c = case
     out = c.run(pitch=UP, momentum=0.99)['wav'].to_host()

@@ -138,6 +138,14 @@ int tts_set_stream(tts_handle_t h, void* hip_stream);
  * by the first such call) and every iteration is a launch of its own whatever "gl_pair" says; utterances stay independent
  * of each other, a call's waveform and mse are the same bits from run to run and whatever the cut into runs, and a NaN
  * magnitude makes its own utterance's waveform non-finite and its mse NaN and touches no other, all as for alpha = 0),
+ * "gl_init" (how a Griffin-Lim call without an explicit `init_phase` starts: 0 (default) = random phases from `seed`,
+ * 1 = phases estimated from the magnitudes the call reconstructs from, tts_phase_estimate below; any other value is
+ * TTS_ERR_INVALID and leaves the option as it was.  With 1, a call of tts_griffin_lim, tts_griffin_lim_ragged, tts_synthesize
+ * or tts_synthesize_host whose init_phase is NULL gives the bits of the same call with "gl_init" = 0 and init_phase =
+ * tts_phase_estimate of its magnitudes -- in tts_synthesize those behind the speaking-rate / pitch stretch, at each
+ * utterance's own frame count under end-of-speech stopping; `seed` is then unused, and in a pipelined call the estimate runs
+ * on the main stream between the post-net (or the stretch) and the first Griffin-Lim launch.  An explicit init_phase always
+ * wins.  With 0 nothing of a call changes),
  * "gl_wide_from" (pipelined calls: the first Griffin-Lim launch that is cut
  * for all compute units instead of all but "reserve_cus" -- the next call's decoder has left them by then; -1 (default) =
  * from a model of the two durations, -2 = never, n >= 0 = launch n; the waveform's bits do not depend on the cut),
@@ -344,6 +352,41 @@ int tts_stretch_magnitudes(tts_handle_t h, const float* mag, int B, int F, int T
  * row_stride < F. */
 int tts_stretch_rows(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, const int32_t* n_frames, double rate,
                      int T_out, float* out);
+
+/* ---- estimated initial phases ----------------------------------------------------------- */
+/* A start for Griffin-Lim from the magnitudes alone: one pass that tracks spectral peaks from frame to frame (after Beauregard,
+ * Harish and Wyse, "Single pass spectrogram inversion", 2015), in the format of `init_phase`.  The reference starts from
+ * np.random.rand (audio/synthesis.py:85); from this estimate the loop reaches the mse of 60 iterations in about 12.
+ * Phases are turns in unsigned 32-bit fixed point (angle = 2 pi phi / 2^32, additions wrap), phi_{-1}[k] = 0.  For frame t of
+ * an utterance with m = mag[:, t], F = 1 + n_fft / 2, every comparison on the float32 values:
+ *   bin j, 1 <= j <= F - 2, is a peak if m[j] > m[j-1] and m[j] > m[j+1].  With a, b, g = m[j-1], m[j], m[j+1] as doubles,
+ *     p = 0.5 * (a - g) / ((a - 2.0 * b) + g);  x = ((double)hop_length * ((double)j + p)) / (double)n_fft;  fr = x - floor(x)
+ *     adv = (uint32)floor(fr * 4294967296.0)   (every operation rounded on its own, no FMA; 0 where fr is not finite)
+ *     phi_t[j] = phi_{t-1}[j] + adv
+ *   a bin k that is no peak walks right while m[i] < m[i+1]; if the walk ends at a peak j, j owns k.  Otherwise it walks left
+ *     while m[i] < m[i-1], likewise.  A walk that ends at a tie or at an edge finds no owner; comparisons with NaN are false,
+ *     so a NaN bin is no peak and ends every walk.  An owned bin takes phi_t[k] = phi_t[j] + ((k - j) & 1) * 0x80000000 (the
+ *     centred, unrotated frames of librosa's stft carry (-1)^k across a lobe); any other bin keeps phi_{t-1}[k].
+ *   init_phase_out[b][k][t] = (float)(phi_t[k] >> 8) * 2^-24: exact, in [0, 1).
+ * Everything but adv is integer arithmetic, so the result is the same bits whatever B is, wherever an utterance sits in the batch
+ * and however the library cuts the frames (chunks of tts_phase_chunk_frames() frames whose maps are composed, chained and
+ * applied); tests/phase_oracle.py restates the definition sequentially.
+ * mag [B][F][T] as tts_griffin_lim takes it -> init_phase_out [B][F][T].  n_frames: HOST int32 [B], the frames of each utterance,
+ * or NULL (all T); columns t >= n_frames[b] of mag are never read and those of init_phase_out never written.  Asynchronous on the
+ * handle's stream (the lengths travel in the launches), no atomics, no loop bound or wait that depends on the data, no model
+ * needed; profile stage "phase_init".  TTS_ERR_INVALID, before anything is enqueued: a NULL mag or init_phase_out, an n_fft that
+ * is no power of two in 256 .. 4096, hop_length outside 1 .. n_fft, B or T < 1, T > 2^22, an n_frames[b] outside [1, T]. */
+int tts_phase_estimate(tts_handle_t h, const float* mag, int B, int T, const int32_t* n_frames /* may be NULL */, int n_fft,
+                       int hop_length, float* init_phase_out);
+/* The same estimate (the same bits for the same values) from time-major padded rows, the layout of tts_speech_frames and of the
+ * call pipeline -- what Griffin-Lim itself reads: spec [B][T][row_stride], the first 1 + n_fft / 2 floats of a row are its data,
+ * the rest and rows t >= n_frames[b] are never read.  init_phase_out is the public [B][F][T] array all the same.  Arguments and
+ * refusals as tts_phase_estimate, and row_stride < 1 + n_fft / 2. */
+int tts_phase_estimate_rows(tts_handle_t h, const float* spec, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
+                            int hop_length, float* init_phase_out);
+/* Host only: the frames of one chunk of the estimate's cut in time (the results do not depend on it; tests place their shapes
+ * around it). */
+int tts_phase_chunk_frames(void);
 
 /* ---- resampling ------------------------------------------------------------------------- */
 /* librosa 0.6 resample(..., res_type='kaiser_best') = resampy 0.2 resample_f with the 'kaiser_best' windowed sinc: the second half

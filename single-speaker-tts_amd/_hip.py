@@ -115,6 +115,9 @@ _PROTOTYPES = {
     'tts_resampled_length': (c_int, [c_int, ctypes.c_double, POINTER(c_int)]),
     'tts_resample': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_void_p]),
     'tts_set_pitch': (c_int, [c_void_p, ctypes.c_double]),
+    'tts_phase_estimate': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p]),
+    'tts_phase_estimate_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p]),
+    'tts_phase_chunk_frames': (c_int, []),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -239,6 +242,48 @@ def momentum_thousandths(momentum):
     if not 0.0 <= m < 1.0:
         raise ValueError('momentum must be in [0, 1), got {!r}'.format(momentum))
     return min(999, int(round(m * 1000.0)))
+
+
+PHASE_INIT_VALUES = {'random': 0, 'estimate': 1}
+
+
+def phase_init_value(phase_init):
+    """``phase_init`` of the Griffin-Lim and synthesis calls as the ``gl_init`` option value: 'random' -> 0 (phases drawn
+    from the seed, or the caller's ``init_phase``), 'estimate' -> 1 (phases estimated from the call's own magnitudes,
+    tts_phase_estimate); None stays None (the handle's option as it stands).  Anything else is a ValueError -- raised here,
+    before a handle is touched."""
+    if phase_init is None:
+        return None
+    if not isinstance(phase_init, str) or phase_init not in PHASE_INIT_VALUES:
+        raise ValueError("phase_init must be None, 'random' or 'estimate', got {!r}".format(phase_init))
+    return PHASE_INIT_VALUES[phase_init]
+
+
+def phase_init_kwargs(engine, phase_init):
+    """The keyword a wrapper that states the start of every call hands to ``engine.griffin_lim``: none where the engine's
+    ``gl_init`` option already is what the call asks for (any engine-like object serves the default), ``phase_init=...`` where
+    the call has to switch it."""
+    v = phase_init_value(phase_init)
+    if v is None or v == getattr(engine, '_gl_init', 0):
+        return {}
+    return {'phase_init': phase_init}
+
+
+def phase_estimate_args(shape, n_fft, hop_length, n_frames, time_major=False):
+    """The checked arguments of a phase-estimate call on an array of ``shape`` -- (B, F, T), or (B, T, F) time-major:
+    ``(B, T, F, n_frames)`` with n_frames a contiguous int32 array or None.  ValueError, raised before a handle is touched,
+    for what tts_phase_estimate refuses."""
+    if int(n_fft) != n_fft or not 256 <= n_fft <= 4096 or (int(n_fft) & (int(n_fft) - 1)):
+        raise ValueError('phase_estimate: n_fft must be a power of two between 256 and 4096, got {!r}'.format(n_fft))
+    if int(hop_length) != hop_length or not 1 <= hop_length <= n_fft:
+        raise ValueError('phase_estimate: need 1 <= hop_length <= n_fft, got {!r}'.format(hop_length))
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError('phase_estimate: a non-empty 3-D array is needed, got shape {}'.format(tuple(shape)))
+    B = int(shape[0])
+    T, F = (int(shape[1]), int(shape[2])) if time_major else (int(shape[2]), int(shape[1]))
+    if F != 1 + int(n_fft) // 2:
+        raise ValueError('phase_estimate: {} bins given, n_fft = {} has {}'.format(F, n_fft, 1 + int(n_fft) // 2))
+    return B, T, F, stretch_frame_counts(n_frames, B, T)
 
 
 class _SettingScope(object):
@@ -437,6 +482,8 @@ def _padded_rows(spec, B, T, F, stride):
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
+    _gl_init = 0   # the handle's "gl_init" option (the C ABI has no getter: set_option keeps it)
+
     def __init__(self, hparams=None, device_id=0, stream=None):
         self.lib = load_library()
         cfg = TtsConfig()
@@ -516,6 +563,8 @@ class Engine(object):
         self._check(self.lib.tts_set_option(self.handle, key.encode(), int(value)))
         if key == 'gl_momentum':
             self._gl_momentum = int(value)
+        if key == 'gl_init':
+            self._gl_init = int(value)
 
     def set_end_of_speech(self, enabled, threshold_db=0.0, keep_frames=0):
         """tts_set_end_of_speech: the handle's setting, read by every synthesize / synthesize_host call made after it."""
@@ -542,6 +591,9 @@ class Engine(object):
     def _momentum_scope(self, momentum):
         return _SettingScope(self, '_gl_momentum', lambda v: self.set_option('gl_momentum', v),
                              None if momentum is None else momentum_thousandths(momentum))
+
+    def _phase_init_scope(self, phase_init):
+        return _SettingScope(self, '_gl_init', lambda v: self.set_option('gl_init', v), phase_init_value(phase_init))
 
     def _synth_scopes(self, momentum, stop_at_silence, speaking_rate, pitch):
         """the scopes of a synthesis call's four settings (momentum, end of speech, rate, pitch), every value checked"""
@@ -755,13 +807,17 @@ class Engine(object):
         return mag
 
     def griffin_lim(self, mag, n_iter, win_length, hop_length, n_fft, init_phase=None, seed=0, want_mse=True, momentum=None,
-                    n_frames=None):
+                    n_frames=None, phase_init=None):
         """``momentum``: the fast Griffin-Lim momentum in [0, 1) for this call (librosa's and torchaudio's ``momentum``;
         0 = the reference's plain loop); None: the handle's ``gl_momentum`` option as it stands.
         ``n_frames``: B frame counts -- a ragged batch (tts_griffin_lim_ragged): ``mag`` and ``init_phase`` are padded to
         (B, F, T_max), utterance b is reconstructed from its first n_frames[b] columns alone (the padding never reaches a
-        result), row b of ``wav`` holds its hop (n_frames[b] - 1) samples followed by zeros and ``mse[b]`` is its own."""
+        result), row b of ``wav`` holds its hop (n_frames[b] - 1) samples followed by zeros and ``mse[b]`` is its own.
+        ``phase_init``: how the call starts when ``init_phase`` is None -- 'random' (from ``seed``), 'estimate' (phases
+        estimated from ``mag``, :meth:`phase_estimate`; ``seed`` is then unused) or None: the handle's ``gl_init`` option as it
+        stands.  An explicit ``init_phase`` always wins."""
         scope = self._momentum_scope(momentum)
+        start = self._phase_init_scope(phase_init)
         B, F, T = mag.shape
         nf = ragged_frame_counts(n_frames, B, T, hop_length, n_fft) if n_frames is not None else None
         p_mag, _k1 = self._in(mag, np.float32)
@@ -769,15 +825,57 @@ class Engine(object):
         wav = self.empty((B, hop_length * (T - 1)))
         mse = self.empty((B,)) if want_mse else None
         if nf is not None:
-            with scope:
+            with scope, start:
                 self._check(self.lib.tts_griffin_lim_ragged(self.handle, p_mag, p_init, seed, B, T, nf.ctypes.data_as(POINTER(c_int32)),
                                                             n_iter, win_length, hop_length, n_fft, wav.data_ptr(),
                                                             mse.data_ptr() if mse is not None else None))
             return wav, mse
-        with scope:
+        with scope, start:
             self._check(self.lib.tts_griffin_lim(self.handle, p_mag, p_init, seed, B, T, n_iter, win_length, hop_length,
                                                  n_fft, wav.data_ptr(), mse.data_ptr() if mse is not None else None))
         return wav, mse
+
+    # ------------------------------------------------------------------ estimated initial phases
+    def phase_chunk_frames(self):
+        """tts_phase_chunk_frames: the frames of one chunk of the estimate's cut in time (no result depends on it)."""
+        return int(self.lib.tts_phase_chunk_frames())
+
+    def phase_estimate(self, mag, n_fft, hop_length, n_frames=None):
+        """tts_phase_estimate: initial phases for Griffin-Lim estimated from the magnitudes alone -- spectral peaks tracked
+        from frame to frame, every other bin locked to the peak that owns it (include/sstts_hip.h has the definition,
+        tests/phase_oracle.py restates it).  ``mag`` (B, F, T), the layout of ``griffin_lim`` -- a host array or a device
+        buffer.  ``n_frames``: B lengths (host integers) -- columns at or behind them are neither read nor written; None: all T.
+        Returns a device array (B, F, T) of numbers in [0, 1), the format of ``init_phase``."""
+        B, T, F, nf = phase_estimate_args(mag.shape, n_fft, hop_length, n_frames)
+        p_mag, _k = self._in(mag, np.float32)
+        out = self.empty((B, F, T))
+        try:
+            self._check(self.lib.tts_phase_estimate(self.handle, p_mag, B, T, nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None,
+                                                    int(n_fft), int(hop_length), out.data_ptr()))
+        except Exception:   # (a refusal: nothing was enqueued)
+            out.free()
+            raise
+        return out
+
+    def phase_estimate_rows(self, spec, n_fft, hop_length, n_frames=None, row_stride=None):
+        """tts_phase_estimate_rows: the same estimate from time-major rows, ``spec`` (B, T, F) as ``speech_frames`` takes it
+        (``row_stride`` as there).  Returns the same device array (B, F, T) as :meth:`phase_estimate`."""
+        B, T, F, nf = phase_estimate_args(spec.shape, n_fft, hop_length, n_frames, time_major=True)
+        stride = F if row_stride is None else int(row_stride)
+        if stride < F:
+            raise ValueError('phase_estimate_rows: row_stride {} < F = {}'.format(stride, F))
+        if not _is_device(spec) and stride > F:
+            spec = _padded_rows(spec, B, T, F, stride)
+        p_spec, _k = self._in(spec, np.float32)
+        out = self.empty((B, F, T))
+        try:
+            self._check(self.lib.tts_phase_estimate_rows(self.handle, p_spec, B, T, stride,
+                                                         nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None,
+                                                         int(n_fft), int(hop_length), out.data_ptr()))
+        except Exception:
+            out.free()
+            raise
+        return out
 
     def peak_normalize(self, wav):
         B, n = wav.shape
@@ -1001,8 +1099,10 @@ class Engine(object):
 
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
-                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None):
-        """``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
+                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None):
+        """``phase_init`` as in ``griffin_lim``: 'estimate' starts Griffin-Lim from phases estimated from the call's own
+        magnitudes (behind the stretch, at each utterance's own length) when ``init_phase`` is None.
+        ``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
         (tts_set_end_of_speech): every utterance is reconstructed from its frames up to the last one whose loudest bin is
         above ``threshold_db``, plus ``keep_frames``; ``wav`` keeps its shape, row b holds hop (n_frames[b] - 1) samples
         followed by zeros.  The result of a call made with stopping on (here or by ``set_end_of_speech``) carries ``n_frames``,
@@ -1016,6 +1116,7 @@ class Engine(object):
         back to the length of the call without pitch.  No shape and no reported length changes but ``init_phase``'s, which is
         (B, F, ``pitch_frames(T, rate, pitch)``)."""
         scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
+        start = self._phase_init_scope(phase_init)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call = self._speaking_rate if rate.value is None else rate.value
@@ -1046,7 +1147,7 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope, eos, rate, shift:
+        with scope, eos, rate, shift, start:
             stopping = self._end_of_speech[0]
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
@@ -1066,15 +1167,16 @@ class Engine(object):
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
-                        speaking_rate=None, pitch=None):
+                        speaking_rate=None, pitch=None, phase_init=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
         ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
         has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1))); ``pitch`` as in
-        ``synthesize`` (no shape changes)."""
+        ``synthesize`` (no shape changes); ``phase_init`` as in ``synthesize``."""
         scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
+        start = self._phase_init_scope(phase_init)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -1083,7 +1185,7 @@ class Engine(object):
         t = c_int(-1)
         r_call = self._speaking_rate if rate.value is None else rate.value
         T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, r_call, 0.0)   # (the pitch changes no shape)
-        with scope, eos, rate, shift:
+        with scope, eos, rate, shift, start:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))

@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -754,6 +754,10 @@ int tts_set_option(tts_handle_t h, const char* key, int value) {
     else if (!std::strcmp(key, "gl_momentum")) {
         if (value < 0 || value > 999) return fail(h, TTS_ERR_INVALID, "gl_momentum: thousandths of the momentum, 0 .. 999");
         h->gl_momentum = value;
+    }
+    else if (!std::strcmp(key, "gl_init")) {
+        if (value != 0 && value != 1) return fail(h, TTS_ERR_INVALID, "gl_init: 0 (random phases or the caller's) or 1 (estimated phases)");
+        h->gl_init = value;
     }
     else if (!std::strcmp(key, "gl_wide_from")) h->gl_wide = value < -2 ? -2 : value;
     else if (!std::strcmp(key, "pd_ws")) {

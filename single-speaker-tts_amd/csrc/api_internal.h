@@ -55,7 +55,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -303,6 +303,9 @@ struct tts_handle_s {
     // fast Griffin-Lim: the momentum alpha in thousandths, 0 (default: the reference's plain loop) .. 999; alpha > 0 runs one
     // iteration per launch whatever gl_pair says (gl_stream_kernel, MOM)
     int gl_momentum = 0;
+    // how a Griffin-Lim call without explicit `init_phase` starts: 0 (default) = the seed's random phases, 1 = phases estimated
+    // from the call's own magnitudes (phase_init.hip) and handed to the launches as an explicit init_phase would be
+    int gl_init = 0;
     // First Griffin-Lim launch of a pipelined call that is cut for all compute units (gl_run, `wide_from`): -1 = by the rule
     // in gl_wide_from() below, -2 = never, >= 0 = that launch index.
     int gl_wide = -1;
@@ -558,6 +561,16 @@ int resample_table(tts_handle_t h, double rho, const double** tab);
 int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double rho, int N_out, const int32_t* keep_cap,
                   float* out);
 void resample_release(tts_handle_t h);
+// estimated initial phases (phase_init.hip): both input layouts -> the public (B, F, T) array on h->stream, arguments checked by
+// the caller (phase_plan.h).  phase_estimate_workspaces sizes its buffers ahead of a call that must not allocate once it has
+// begun to enqueue.  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with the option "gl_init" the
+// estimate from the time-major magnitudes `magi` in the workspace "gl.init_est" (sized by gl_init_workspace), or null.
+int phase_estimate_workspaces(tts_handle_t h, int B, int T, int n_fft, bool from_public);
+int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_stride, bool time_major, const int32_t* n_frames, int n_fft,
+                        int hop, float* out);
+int gl_init_workspace(tts_handle_t h, int B, int T, int n_fft);
+int gl_init_phase(tts_handle_t h, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
+                  int hop, const float** out);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);
 int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memory);

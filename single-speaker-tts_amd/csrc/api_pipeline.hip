@@ -40,7 +40,7 @@ struct SynthCall {
     const int32_t* ids;
     int B, Ts;
     const tts_synth_params_t* sp;
-    const float* init_phase;
+    const float* init_phase;     // the caller's, or null; synth_main puts the estimate here under the option "gl_init"
     float* wav;
     float* mel_out;
     float* align_out;
@@ -146,6 +146,11 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     if (k.shape.pitch) {
         WS(h, "gl.wav_pitch", float, (size_t)B * sp->hop_length * (size_t)(Tg - 1), glw);
         k.gl_wav = glw;
+    }
+    // (estimated initial phases, option "gl_init": the estimate's buffers, for the frames Griffin-Lim reconstructs from)
+    if (h->gl_init && !k.init_phase) {
+        const int rc = gl_init_workspace(h, B, Tg, c.n_fft);
+        if (rc) return rc;
     }
     setting_grew |= h->ws_allocs != allocs;
     // Under the call pipeline the initial phasors of a call are written on the FRONT stream, behind its decoder (that
@@ -371,8 +376,10 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     const SynthShape& s = k.shape;
     const int B = k.B, T = k.T, Tg = s.Tg, parity = k.parity;
     int rc = TTS_OK;
-    // (a seeded start with iterations needs no initial codes at all: gl_run)
-    const bool phase_on_front = k.gl_streaming && k.pipelined && sp->n_iter >= 0 && (k.init_phase != nullptr || sp->n_iter == 0);
+    // (a seeded start with iterations needs no initial codes at all: gl_run.  Estimated phases -- option "gl_init" without an
+    //  explicit init_phase -- come from this call's magnitudes, which do not exist yet: they are made on the main stream below)
+    const bool estimate = h->gl_init && !k.init_phase;
+    const bool phase_on_front = !estimate && k.gl_streaming && k.pipelined && sp->n_iter >= 0 && (k.init_phase != nullptr || sp->n_iter == 0);
     if (k.pipelined) {
         if (k.hold_flag) HIPCHK(h, hipMemsetAsync(k.hold_flag, 1, sizeof(int), pl.front));   // release the held CUs
         if (phase_on_front) {
@@ -412,15 +419,19 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     const float* gl_mag = s.stretch ? k.mags : k.magi;
     // (the device's lengths are those of the detection: with a speaking rate the host's stretched ones are uploaded instead)
     const int* d_frames = (n_frames && !s.stretch) ? k.d_frames : nullptr;
+    // estimated initial phases: from the magnitudes Griffin-Lim reconstructs from, at each utterance's own length, between the
+    // post-net (or the stretch) and the first Griffin-Lim launch; from here on they are the call's explicit init_phase
+    const float* init_phase = k.init_phase;
+    if (estimate && (rc = gl_init_phase(h, gl_mag, nullptr, B, Tg, k.FP, n_frames, h->cfg.n_fft, sp->hop_length, &init_phase))) return rc;
     const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, L.T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
     float* gl_wav = s.pitch ? k.gl_wav : k.wav;
     const bool gl_peak = sp->peak_normalize != 0 && !s.pitch;   // (a shifted call normalises what the resampler leaves)
     if (k.gl_streaming)
-        rc = gl_run(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
+        rc = gl_run(h, gl_mag, init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
                     gl_peak, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
     else
-        rc = gl_run_generic(h, gl_mag, k.init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav,
+        rc = gl_run_generic(h, gl_mag, init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav,
                             nullptr, gl_peak, n_frames, d_frames);
     if (s.pitch && !rc) {
         // The pitch: the hop (Tg - 1) samples Griffin-Lim made, resampled by rho into the rows of the call without pitch.  With

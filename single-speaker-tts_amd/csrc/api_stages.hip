@@ -1193,6 +1193,35 @@ int tts_denorm_power(tts_handle_t h, const float* linear, int B, int T, int F, f
 }
 
 
+}  // extern "C"
+
+namespace tts_api {
+
+// The init_phase of a Griffin-Lim call.  An explicit one always wins; otherwise, with the option "gl_init" = 1, the phases are
+// estimated from the magnitudes the call reconstructs from (time-major rows, `magi`) into a workspace in the public layout and
+// handed on exactly as a caller's array would be -- the launches cannot tell the two apart, so the waveform has the same bits.
+int gl_init_workspace(tts_handle_t h, int B, int T, int n_fft) {
+    WS(h, "gl.init_est", float, (size_t)B * (1 + n_fft / 2) * T, est);
+    (void)est;
+    return phase_estimate_workspaces(h, B, T, n_fft, false);
+}
+
+int gl_init_phase(tts_handle_t h, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
+                  int hop, const float** out) {
+    *out = init_phase;
+    if (init_phase || !h->gl_init) return TTS_OK;
+    int rc = gl_init_workspace(h, B, T, n_fft);
+    if (rc) return rc;
+    WS(h, "gl.init_est", float, (size_t)B * (1 + n_fft / 2) * T, est);
+    if ((rc = phase_estimate_impl(h, magi, B, T, row_stride, true, n_frames, n_fft, hop, est))) return rc;
+    *out = est;
+    return TTS_OK;
+}
+
+}  // namespace tts_api
+
+extern "C" {
+
 int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, uint64_t seed, int B, int T, int n_iter,
                     int win_length, int hop_length, int n_fft, float* wav, float* mse) {
     DeviceScope dev_scope(h);
@@ -1205,6 +1234,8 @@ int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, u
         const int Fg = 1 + n_fft / 2, Fp = gl_fp(n_fft);
         WS(h, "gl.mag", float, (size_t)B * T * Fp, magg);
         HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magg, B, Fg, T, Fp));
+        int rcg = gl_init_phase(h, magg, init_phase, B, T, Fp, nullptr, n_fft, hop_length, &init_phase);
+        if (rcg) return rcg;
         return gl_run_generic(h, magg, init_phase, seed, B, T, n_iter, win_length, hop_length, n_fft, wav, mse, false);
     }
     int rc = gl_prepare(h, T, win_length, hop_length, n_fft);
@@ -1212,6 +1243,7 @@ int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, u
     const int F = 1 + n_fft / 2, FP = TTS_GL_FP;
     WS(h, "gl.mag", float, (size_t)B * T * FP, magi);
     HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magi, B, F, T, FP));
+    if ((rc = gl_init_phase(h, magi, init_phase, B, T, FP, nullptr, n_fft, hop_length, &init_phase))) return rc;
     return gl_run(h, magi, init_phase, seed, B, T, n_iter, win_length, hop_length, n_fft, wav, mse);
 }
 
@@ -1241,6 +1273,7 @@ int tts_griffin_lim_ragged(tts_handle_t h, const float* mag, const float* init_p
     if ((rc = gl_rag_tables(h, n_frames, B, T_max, win_length, hop_length, n_fft, streaming))) return rc;
     WS(h, "gl.mag", float, (size_t)B * T_max * Fp, magi);
     HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magi, B, F, T_max, Fp, h->rag.lens));
+    if ((rc = gl_init_phase(h, magi, init_phase, B, T_max, Fp, n_frames, n_fft, hop_length, &init_phase))) return rc;
     if (!streaming) return gl_run_generic(h, magi, init_phase, seed, B, T_max, n_iter, win_length, hop_length, n_fft, wav, mse, false, n_frames);
     return gl_run(h, magi, init_phase, seed, B, T_max, n_iter, win_length, hop_length, n_fft, wav, mse, false, false, nullptr, false, -1, n_frames);
 }

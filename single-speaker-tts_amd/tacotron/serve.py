@@ -8,7 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import momentum_thousandths, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
+from .._hip import momentum_thousandths, phase_init_value, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
 from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_sentence, stop_setting
 from .model import Mode, Tacotron
@@ -24,7 +24,7 @@ def pre_process_sentences(_sentences, dataset):
 
 
 def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0, stop_at_silence_db=None,
-                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0):
+                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random'):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
     constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86); ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: every utterance is reconstructed only up to
@@ -33,8 +33,11 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
     rate in [0.25, 4] -- the magnitudes are time-stretched (``Engine.stretch_magnitudes``) ahead of Griffin-Lim: T' =
     ceil(T / rate) frames, ``init_phase`` (B, F, T'), lengths min(T', max(min_frames, ceil(n / rate))).  ``pitch``: 0.0, or a
     shift in [-1, 1] octaves -- the magnitudes are stretched by rate * 2 ** -pitch instead (``init_phase`` has that many
-    frames) and ``Engine.resample`` takes Griffin-Lim's samples by 2 ** -pitch back to the lengths they have without it."""
+    frames) and ``Engine.resample`` takes Griffin-Lim's samples by 2 ** -pitch back to the lengths they have without it.
+    ``phase_init``: 'random', 'estimate' (start phases estimated from the magnitudes Griffin-Lim runs on) or None (the
+    engine's option), as in ``audio.synthesis``."""
     momentum_thousandths(momentum)
+    phase_init_value(phase_init)
     stop = stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
     rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
@@ -67,7 +70,8 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
         if n_frames is not None:
             n_frames, n_gl = synth_lengths(n_frames, T, rate, octaves, min_frames)
     wav, _ = engine.griffin_lim(mag, model_params.reconstruction_iterations, win_len, win_hop, model_params.n_fft,
-                                init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_gl)
+                                init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_gl,
+                                phase_init=phase_init)
     if octaves != 0.0:
         gl_wav = wav
         try:
@@ -81,7 +85,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
-          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0):
+          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random'):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -92,8 +96,9 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     generator ends), which on a request-driven generator would hold every answer back by two requests.
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db`` /
     ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech;
-    ``speaking_rate`` and ``pitch`` likewise."""
+    ``speaking_rate``, ``pitch`` and ``phase_init`` likewise."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
+    phase_init_value(phase_init)
     stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
     speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     pitch_octaves_value(0.0 if pitch is None else pitch)
@@ -106,12 +111,13 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
             ids = pre_process_sentences(sentences, dataset)
             spectrograms = model.run(model.output_linear_spec, {model.inp_sentences: ids})
             yield post_process_spectrograms(spectrograms, model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
-                                            silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch)
+                                            silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch,
+                                            phase_init=phase_init)
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
     for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
                                   stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                                  pitch=pitch):
+                                  pitch=pitch, phase_init=phase_init):
         yield [wavs[b] for b in range(len(wavs))]

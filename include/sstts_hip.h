@@ -482,6 +482,59 @@ int tts_plan_features(tts_handle_t h, const float* wav, const int64_t* offsets, 
 int tts_extract_features(tts_handle_t h, const float* wav, const int64_t* offsets, int B, const tts_feature_params_t* p,
                          const int64_t* plan, float* mel_out, float* lin_out);
 
+/* ---- cepstra and alignment: mel-cepstral distortion --------------------------------------- */
+/* calculate_mfccs (audio/features.py:89-113): librosa.feature.mfcc(S=mel_spec, n_mfcc=n) with S given is the orthonormal DCT-II of
+ * S along the mel axis, first n rows, with no dB conversion of its own.  On time-major rows, the layout of the network's mel output
+ * and of the dataset features: spec DEVICE [B][T][row_stride] -> out DEVICE [B][T][n_mfcc],
+ *   out[b][t][k] = (float) sum_{n = 0 .. n_mels - 1} d[k][n] x[n]
+ *   d[k][n] = sqrt(2 / n_mels) cos(pi k (2 n + 1) / (2 n_mels)), row 0 times 1 / sqrt(2), built on the host in double
+ *   x[n] = (double)spec[b][t][n], or with clip01 != 0 np.clip(spec, 0, 1) of it as numpy clips (a NaN stays NaN; the reference
+ *          clips the network's output before it de-normalises it, tacotron/inference.py:93-101)
+ * products and the sum in double, n ascending, the result rounded once to float32: against a float64 evaluation y of the same sum
+ * |out - y| <= 2^-24 |y| + 2^-40 sum_n |d[k][n]| |x[n]|.  n_frames: HOST int32 [B], the frames of each utterance, or NULL (all T);
+ * rows t >= n_frames[b] are never read and are written as 0; columns n_mels .. row_stride - 1 are never read.  A NaN input makes
+ * its own frame's coefficients NaN and touches nothing else.  No model needed, no atomics; asynchronous on the handle's stream
+ * (the lengths travel in the launch; the first call at a pair (n_mels, n_mfcc) builds that table on the host and uploads it with
+ * a synchronous copy); one launch per 64 utterances; profile stage "mfcc".  TTS_ERR_INVALID, before anything is enqueued: a
+ * NULL spec or out, B, T, n_mels or n_mfcc < 1, n_mels > 1024, n_mfcc > n_mels, row_stride < n_mels, an n_frames[b] outside
+ * [1, T]. */
+int tts_mfcc(tts_handle_t h, const float* spec, int B, int T, int n_mels, int row_stride,
+             const int32_t* n_frames /* HOST [B] or NULL */, int n_mfcc, int clip01, float* out /* [B][T][n_mfcc] */);
+/* Dynamic time warping of B pairs of feature sequences (no reference counterpart: the alignment under which audio/metrics.py
+ * measures mel-cepstral distortion).  a DEVICE [B][Ta][stride_a], b DEVICE [B][Tb][stride_b]: the first D floats of a row are the
+ * frame, the rest is never read (a caller skips c0 by passing ptr + 1, D = K, stride = K + 1).  n_a / n_b: HOST int32 [B], the
+ * frames of each sequence, or NULL (all Ta / Tb); frames at or behind them are never read.  For one pair with na and nb frames:
+ *   local cost   c(i, j) = sqrt(s) with s = 0.0; for d in 0 .. D - 1: t = (double)a[i][d] - (double)b[j][d]; s = s + t * t
+ *                every operation an IEEE double operation rounded on its own (no FMA), sqrt correctly rounded
+ *   first cell   Dm(0, 0) = c(0, 0), L(0, 0) = 1
+ *   other cells  candidates in the order diagonal (i - 1, j - 1), up (i - 1, j), left (i, j - 1), those inside the table only;
+ *                best = the first that exists, a later one replaces it iff its Dm is strictly smaller;
+ *                Dm(i, j) = c(i, j) + Dm(best), L(i, j) = L(best) + 1
+ *   cost[p] = Dm(na - 1, nb - 1) (DEVICE double [B]), path_len[p] = L(na - 1, nb - 1) (DEVICE int32 [B])
+ *   path[p][k] = (i_k, j_k), k < path_len[p]: the chain of `best` choices from (0, 0) to (na - 1, nb - 1) in forward order; rows
+ *                k >= path_len[p] are written as (-1, -1).  DEVICE int32 [B][Ta + Tb - 1][2], or NULL.
+ * Exactness: every operation is an individually rounded double operation or an integer one, so cost is the bits of the sequential
+ * evaluation (tests/dtw_oracle.py) and path_len and path are integer-equal to it, whatever order the library walks the table in
+ * (anti-diagonals, cut into pieces of tts_dtw_tile() cells).  Independence: a pair's results do not depend on B, on its place in
+ * the batch, on Ta / Tb or on earlier calls.  NaN: comparisons with NaN are false, so a NaN anywhere in the first D floats of a
+ * frame < na / < nb makes that pair's cost NaN (every monotone path crosses every row and column); its path_len and path are
+ * still what the rule gives, and the other pairs keep the bits of a clean run.  Inf follows IEEE arithmetic.  No loop bound or
+ * wait depends on the data: the table is walked in na + nb - 1 diagonals and the path in at most na + nb - 1 steps, both from
+ * the host lengths, which travel in the launch.  No atomics.  No model needed; asynchronous on the handle's stream, one launch
+ * per 64 pairs; profile stage "dtw".  With a path the call keeps 2 bits per cell in workspace of the handle, which grows as the
+ * other workspaces do (a call that needs more than any before synchronises the handle).
+ * Limits: 1 <= D <= 128 and na, nb <= tts_dtw_max_frames() (2048: 25 s at a hop of 275 samples of 22050 Hz); beyond them
+ * TTS_ERR_UNSUPPORTED, and the message names the limit.  TTS_ERR_INVALID, before anything is enqueued: a NULL a, b, cost or
+ * path_len, B, Ta, Tb or D < 1, a stride < D, a length outside [1, Ta] / [1, Tb], a cost that is not 8-byte aligned. */
+int tts_dtw(tts_handle_t h, const float* a, int Ta, int stride_a, const int32_t* n_a /* HOST [B] or NULL */,
+            const float* b, int Tb, int stride_b, const int32_t* n_b /* HOST [B] or NULL */,
+            int B, int D, double* cost /* [B] */, int32_t* path_len /* [B] */,
+            int32_t* path /* [B][Ta + Tb - 1][2] or NULL */);
+/* Host only: the longest sequence tts_dtw takes. */
+int tts_dtw_max_frames(void);
+/* Host only: the cells of one piece of the cut of an anti-diagonal (no result depends on it; tests place their shapes around it). */
+int tts_dtw_tile(void);
+
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,
  * optional peak normalisation; replaces tacotron/inference.py:162-200 minus file IO.
@@ -588,7 +641,8 @@ int tts_set_pitch(tts_handle_t h, double octaves);
  * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate), "features" (tts_trim_bounds, the trim of tts_plan_features and
  * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize),
  * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
- * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch).
+ * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
+ * "mfcc" (tts_mfcc), "dtw" (tts_dtw).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

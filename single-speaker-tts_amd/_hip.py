@@ -118,6 +118,11 @@ _PROTOTYPES = {
     'tts_phase_estimate': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p]),
     'tts_phase_estimate_rows': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p]),
     'tts_phase_chunk_frames': (c_int, []),
+    'tts_mfcc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, c_int, c_void_p]),
+    'tts_dtw': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int,
+                        c_void_p, c_void_p, c_void_p]),
+    'tts_dtw_max_frames': (c_int, []),
+    'tts_dtw_tile': (c_int, []),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -923,6 +928,78 @@ class Engine(object):
             last.free()
             raise
         return n_frames, last
+
+    # ------------------------------------------------------------------ cepstra and alignment
+    def mfcc(self, rows, n_mfcc, n_frames=None, clip01=False, row_stride=None):
+        """tts_mfcc: the orthonormal DCT-II of ``rows`` (B, T, n_mels) along the mel axis, first ``n_mfcc`` coefficients -- the
+        reference's calculate_mfccs (audio/features.py:89-113) on time-major rows, a host array or a device buffer
+        (``row_stride`` as :meth:`speech_frames` takes it).  ``clip01``: np.clip(rows, 0, 1) first.  ``n_frames``: B lengths
+        (host integers); rows at or behind them are never read and come back 0.  Returns a device array (B, T, n_mfcc)."""
+        if len(rows.shape) != 3 or min(rows.shape) < 1:
+            raise ValueError('mfcc: rows must be a non-empty (B, T, n_mels) array, got shape {}'.format(tuple(rows.shape)))
+        B, T, n_mels = (int(d) for d in rows.shape)
+        if int(n_mfcc) != n_mfcc or not 1 <= n_mfcc <= n_mels or n_mels > 1024:
+            raise ValueError('mfcc: need 1 <= n_mfcc <= n_mels <= 1024, got n_mfcc = {!r}, n_mels = {}'.format(n_mfcc, n_mels))
+        stride = n_mels if row_stride is None else int(row_stride)
+        if stride < n_mels:
+            raise ValueError('mfcc: row_stride {} < n_mels = {}'.format(stride, n_mels))
+        nf = stretch_frame_counts(n_frames, B, T)
+        if not _is_device(rows) and stride > n_mels:
+            rows = _padded_rows(rows, B, T, n_mels, stride)
+        p_rows, _k = self._in(rows, np.float32)
+        out = self.empty((B, T, int(n_mfcc)))
+        try:
+            self._check(self.lib.tts_mfcc(self.handle, p_rows, B, T, n_mels, stride,
+                                          nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None, int(n_mfcc),
+                                          1 if clip01 else 0, out.data_ptr()))
+        except Exception:   # (a refusal: nothing was enqueued)
+            out.free()
+            raise
+        return out
+
+    def dtw_max_frames(self):
+        """tts_dtw_max_frames: the longest sequence :meth:`dtw` takes."""
+        return int(self.lib.tts_dtw_max_frames())
+
+    def dtw_tile(self):
+        """tts_dtw_tile: the cells of one piece of the kernel's cut of an anti-diagonal (no result depends on it)."""
+        return int(self.lib.tts_dtw_tile())
+
+    def dtw(self, a, b, n_a=None, n_b=None, D=None, want_path=False, skip=0):
+        """tts_dtw: dynamic time warping of B pairs, ``a`` (B, Ta, K) against ``b`` (B, Tb, K), host arrays or device buffers,
+        under the Euclidean distance of the frames -- floats ``skip`` .. ``skip + D - 1`` of every row (``D`` None: all behind
+        ``skip``; ``skip`` = 1 leaves c0 out).  ``n_a`` / ``n_b``: B lengths (host integers); frames at or behind them are
+        never read.  Returns the device arrays ``(cost, path_len)`` -- float64 (B,) and int32 (B,) -- and with ``want_path``
+        also ``path`` int32 (B, Ta + Tb - 1, 2): rows k < path_len[b] are the (i, j) of the path from (0, 0), the rest
+        (-1, -1).  include/sstts_hip.h has the definition: costs are the bits of tests/dtw_oracle.py."""
+        if len(a.shape) != 3 or len(b.shape) != 3 or min(a.shape) < 1 or min(b.shape) < 1:
+            raise ValueError('dtw: a and b must be non-empty (B, T, K) arrays, got shapes {} and {}'.format(tuple(a.shape), tuple(b.shape)))
+        B, Ta, Ka = (int(d) for d in a.shape)
+        Bb, Tb, Kb = (int(d) for d in b.shape)
+        if Bb != B:
+            raise ValueError('dtw: {} sequences in a and {} in b'.format(B, Bb))
+        skip = int(skip)
+        if skip < 0:
+            raise ValueError('dtw: skip must be >= 0')
+        D = min(Ka, Kb) - skip if D is None else D
+        if int(D) != D or D < 1 or skip + D > min(Ka, Kb):
+            raise ValueError('dtw: need 1 <= D and skip + D <= the row length, got D = {!r}, skip = {}, rows of {} and {}'.format(D, skip, Ka, Kb))
+        na, nb = stretch_frame_counts(n_a, B, Ta), stretch_frame_counts(n_b, B, Tb)
+        p_a, _ka = self._in(a, np.float32)
+        p_b, _kb = self._in(b, np.float32)
+        cost = self.empty((B,), np.float64)
+        plen = self.empty((B,), np.int32)
+        path = self.empty((B, Ta + Tb - 1, 2), np.int32) if want_path else None
+        ptr = lambda n: n.ctypes.data_as(POINTER(c_int32)) if n is not None else None
+        try:
+            self._check(self.lib.tts_dtw(self.handle, p_a + 4 * skip, Ta, Ka, ptr(na), p_b + 4 * skip, Tb, Kb, ptr(nb), B, int(D),
+                                         cost.data_ptr(), plen.data_ptr(), path.data_ptr() if want_path else None))
+        except Exception:   # (a refusal: nothing was enqueued)
+            for x in (cost, plen, path):
+                if x is not None:
+                    x.free()
+            raise
+        return (cost, plen, path) if want_path else (cost, plen)
 
     # ------------------------------------------------------------------ speaking rate
     def stretched_frames(self, n, rate):

@@ -22,5 +22,14 @@ def mel_scale_spectrogram(wav, n_fft, sampling_rate, n_mels, fmin, fmax, hop_len
     return eng.mel_spectrogram(lin, n_fft, sampling_rate, n_mels, fmin, fmax).to_host()[0]
 
 
-def calculate_mfccs(mel_spec, sampling_rate, n_mfcc):
-    raise NotImplementedError('calculate_mfccs is unused by the reference (audio/features.py:89-113) and out of scope')
+def calculate_mfccs(mel_spec, sampling_rate, n_mfcc, engine=None):
+    """reference audio/features.py:89-113: librosa.feature.mfcc(S=mel_spec, n_mfcc=n_mfcc) -- with S given, the orthonormal DCT-II
+    of ``mel_spec`` (n_mels, t) along the mel axis, first ``n_mfcc`` rows: (n_mfcc, t) float32.  No dB conversion happens here:
+    pass a dB-scaled spectrogram, as the reference's docstring asks.  ``sampling_rate`` is unused, as in librosa when S is
+    given.  The rows are transposed on the host; the transform runs in tts_mfcc."""
+    eng = engine or default_engine()
+    mel_spec = np.asarray(mel_spec, dtype=np.float32)
+    if mel_spec.ndim != 2:
+        raise ValueError('calculate_mfccs: mel_spec must be (n_mels, t), got shape {}'.format(mel_spec.shape))
+    rows = np.ascontiguousarray(mel_spec.T)[None]
+    return np.ascontiguousarray(eng.mfcc(rows, n_mfcc).to_host()[0].T)

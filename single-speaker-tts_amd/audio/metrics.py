@@ -1,0 +1,54 @@
+"""Objective measures of a synthesised spectrogram against its recording.  No reference counterpart: the reference's only
+measure is the frame-by-frame L1 loss of ``tacotron.evaluate``, which measures the drift as soon as the free-running decoder
+speaks a little faster or slower than the recording.  Mel-cepstral distortion along a dynamic-time-warping path compares the
+spectra at the frames that belong together.  The cepstra (tts_mfcc) and the alignment (tts_dtw) run on the device."""
+import math
+
+import numpy as np
+
+from . import default_engine
+from ..tacotron.params import LJSpeechConstants
+
+MCD_COEFFS = 13
+
+
+def mcd_scale(ref_db, max_db):
+    """(sqrt(2) / 2) (|ref_db| + |max_db|): the factor from the Euclidean distance of the cepstra of NORMALISED-dB mel rows to
+    mel-cepstral distortion in dB.  De-normalisation is affine, x_db = clip(x, 0, 1) (|ref_db| + |max_db|) - |max_db| + ref_db
+    (audio/conversion.py:81-102): its constant moves c0 alone, which is left out, and its factor scales every other coefficient.
+    A 20 log10 spectrum is 20 / ln 10 times the natural-log one, so the textbook (10 / ln 10) sqrt(2 sum dc^2) on natural-log
+    cepstra is sqrt(2) / 2 times the distance of dB cepstra."""
+    return math.sqrt(2.0) / 2.0 * (abs(float(ref_db)) + abs(float(max_db)))
+
+
+def mel_cepstral_distortion(mel_a, mel_b, n_a=None, n_b=None, n_coeffs=MCD_COEFFS, ref_db=LJSpeechConstants.mel_mag_ref_db,
+                            max_db=LJSpeechConstants.mel_mag_max_db, engine=None, want_path=False):
+    """Mel-cepstral distortion of B pairs of normalised-dB mel rows, ``mel_a`` (B, Ta, n_mels) against ``mel_b`` (B, Tb, n_mels)
+    -- host arrays or device buffers, as the network emits them and the dataset stores them.  ``n_a`` / ``n_b``: B lengths (host
+    integers), None: all frames.  Both sides are clipped to [0, 1] as the reference clips before it de-normalises
+    (tacotron/inference.py:93-101) and transformed by tts_mfcc to ``n_coeffs`` + 1 orthonormal-DCT coefficients; tts_dtw aligns
+    coefficients 1 .. ``n_coeffs`` (c0, the level, is left out), and
+        mcd_b = (sqrt(2) / 2) (|ref_db| + |max_db|) cost_b / path_len_b        in dB.
+    The orthonormal DCT makes the figure comparable within this project, not with tools of another cepstral convention.
+    Returns a dict of host arrays: ``mcd`` (B,) float64, ``cost`` (B,) float64, ``path_len`` (B,) int32 and, with
+    ``want_path``, ``path`` (B, Ta + Tb - 1, 2) int32 whose rows behind path_len are (-1, -1)."""
+    eng = engine or default_engine()
+    if int(n_coeffs) != n_coeffs or n_coeffs < 1:
+        raise ValueError('mel_cepstral_distortion: n_coeffs must be an integer >= 1, got {!r}'.format(n_coeffs))
+    n_coeffs = int(n_coeffs)
+    if len(mel_a.shape) != 3 or len(mel_b.shape) != 3 or mel_a.shape[0] != mel_b.shape[0] or mel_a.shape[2] != mel_b.shape[2]:
+        raise ValueError('mel_cepstral_distortion: (B, Ta, n_mels) and (B, Tb, n_mels) rows are needed, got shapes {} and {}'.format(
+            tuple(mel_a.shape), tuple(mel_b.shape)))
+    if n_coeffs + 1 > mel_a.shape[2]:
+        raise ValueError('mel_cepstral_distortion: n_coeffs + 1 = {} coefficients from {} mel bands'.format(n_coeffs + 1, mel_a.shape[2]))
+    scale = mcd_scale(ref_db, max_db)
+    ca = eng.mfcc(mel_a, n_coeffs + 1, n_frames=n_a, clip01=True)
+    cb = eng.mfcc(mel_b, n_coeffs + 1, n_frames=n_b, clip01=True)
+    res = eng.dtw(ca, cb, n_a=n_a, n_b=n_b, D=n_coeffs, want_path=want_path, skip=1)
+    cost, path_len = res[0].to_host(), res[1].to_host()
+    out = dict(mcd=scale * cost / path_len.astype(np.float64), cost=cost, path_len=path_len)
+    if want_path:
+        out['path'] = res[2].to_host()
+    for d in (ca, cb) + tuple(res):
+        d.free()
+    return out

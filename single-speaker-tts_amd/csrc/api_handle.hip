@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -647,6 +647,7 @@ int tts_destroy(tts_handle_t h) {
     if (h->an.mel_wt) hipFree(h->an.mel_wt);
     feat_release(h);
     resample_release(h);
+    mfcc_release(h);
     if (h->eos.pinned) hipHostFree(h->eos.pinned);
     if (h->an.flag) hipFree(h->an.flag);
     for (auto& kv : h->glg.tw) hipFree(kv.second);

@@ -55,7 +55,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -430,6 +430,9 @@ struct tts_handle_s {
         std::map<uint64_t, double*> tabs;
     } rs;
 
+    // cepstra (cepstrum.hip): the DCT tables on the device, one per (n_mels << 32 | n_mfcc)
+    std::map<uint64_t, double*> mfcc_tabs;
+
     // analysis-side tables (STFT window, mel basis)
     struct {
         int win = 0;
@@ -561,6 +564,7 @@ int resample_table(tts_handle_t h, double rho, const double** tab);
 int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double rho, int N_out, const int32_t* keep_cap,
                   float* out);
 void resample_release(tts_handle_t h);
+void mfcc_release(tts_handle_t h);   // cepstrum.hip: the DCT tables
 // estimated initial phases (phase_init.hip): both input layouts -> the public (B, F, T) array on h->stream, arguments checked by
 // the caller (phase_plan.h).  phase_estimate_workspaces sizes its buffers ahead of a call that must not allocate once it has
 // begun to enqueue.  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with the option "gl_init" the

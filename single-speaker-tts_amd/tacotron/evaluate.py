@@ -12,6 +12,12 @@ the buckets then follow, in ascending bucket order, as smaller batches (without 
 TensorFlow drops them).  Because the losses are averaged per batch, the batch composition -- not the order --
 decides the result.
 
+Mel-cepstral distortion.  With ``mcd`` (``--mcd``) every utterance's free-running mel prediction is also compared with its
+target along a dynamic-time-warping path (``audio.metrics.mel_cepstral_distortion``): a measure of the spectra that does not
+count a prediction that speaks a little faster or slower than the recording as wrong at every frame.  The target side is the
+utterance's unpadded ``ph_time_frames * r`` frames; the prediction side the same count, or with ``mcd_stop_at_silence``
+(``--mcd-stop-at-silence DB``) the frames up to the last one of the predicted linear spectrogram that rises above that level.
+
 TensorBoard events are not written: every evaluated checkpoint appends one JSON line with the reference's
 summary tags (``loss/loss``, ``loss/loss_decoder``, ``loss/loss_post_processing``) and its global step to
 ``<checkpoint_dir>/<checkpoint_save_run>/eval_summaries.jsonl``.
@@ -23,7 +29,7 @@ import os
 import numpy as np
 
 from .model import Mode, Tacotron
-from .params import dataset_params, evaluation_params, model_params
+from .params import LJSpeechConstants, dataset_params, evaluation_params, model_params
 
 SUMMARY_FILE = 'eval_summaries.jsonl'
 
@@ -106,11 +112,35 @@ def global_step_of(checkpoint_file):
     return int(checkpoint_file.split('-')[-1])
 
 
-def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_save_run=None, verbose=True):
+def batch_mcd(model, feed, out, mcd_coeffs=13, mcd_stop_at_silence=None):
+    """The mel-cepstral distortion of every utterance of one evaluated batch: ``out`` is what ``evaluate_device`` returned for
+    ``feed`` (its ``mel``, and with ``mcd_stop_at_silence`` its ``linear``).  -> (B,) float64"""
+    from ..audio.metrics import mel_cepstral_distortion
+    eng = model.engine
+    r, nm = eng.cfg.reduction, eng.cfg.n_mels
+    B = feed['ph_sentences'].shape[0]
+    target = np.ascontiguousarray(feed['ph_mel_specs'], dtype=np.float32).reshape(B, -1, nm)
+    n_target = np.asarray(feed['ph_time_frames'], np.int32) * r
+    n_pred = n_target
+    if mcd_stop_at_silence is not None:
+        thr = eng.speech_threshold(mcd_stop_at_silence, LJSpeechConstants.linear_ref_db, LJSpeechConstants.linear_mag_max_db)
+        n_frames, last = eng.speech_frames(out['linear'], thr, keep_frames=0, min_frames=1)
+        n_pred = n_frames.to_host()
+        n_frames.free()
+        last.free()
+    res = mel_cepstral_distortion(out['mel'], target, n_a=n_pred, n_b=n_target, n_coeffs=mcd_coeffs,
+                                  ref_db=LJSpeechConstants.mel_mag_ref_db, max_db=LJSpeechConstants.mel_mag_max_db, engine=eng)
+    return res['mcd']
+
+
+def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_save_run=None, verbose=True, mcd=False, mcd_coeffs=13,
+             mcd_stop_at_silence=None):
     """reference :153-257.  Restores ``checkpoint_file`` into ``model`` (a ``Tacotron(..., Mode.EVAL)``) once, runs every
     feed dict of ``batches`` through tts_evaluate and returns ``{loss, loss_decoder, loss_post_processing, global_step,
     n_batches}``: the per-batch float32 losses averaged unweighted over the batches.  Raises if no batch ran.  Appends
-    the summary line (module docstring) when ``checkpoint_dir`` (default ``evaluation_params.checkpoint_dir``) is set."""
+    the summary line (module docstring) when ``checkpoint_dir`` (default ``evaluation_params.checkpoint_dir``) is set.
+    With ``mcd`` the result gains ``mcd`` -- the mean mel-cepstral distortion over all utterances of the epoch, in dB -- and
+    ``mcd_utterances``, and the summary line ``metric/mcd``; without it nothing of the run, the result or the line changes."""
     if model._mode != Mode.EVAL:
         raise ValueError('evaluate() needs a Tacotron in Mode.EVAL')
     global_step = global_step_of(checkpoint_file)
@@ -122,19 +152,29 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
         print('Restoring finished')
     sums = np.zeros(3, np.float64)
     n_batches = 0
+    mcds = []
     for feed in batches:
         out = model.evaluate_device(feed['ph_sentences'], feed['ph_mel_specs'], feed['ph_lin_specs'],
-                                    want_mel=False, want_alignments=False, want_linear=False)
+                                    want_mel=bool(mcd), want_alignments=False,
+                                    want_linear=bool(mcd) and mcd_stop_at_silence is not None)
         sums += out['losses'].to_host().astype(np.float64)
+        if mcd:
+            mcds.append(batch_mcd(model, feed, out, mcd_coeffs, mcd_stop_at_silence))
         n_batches += 1
     if n_batches == 0:
         raise Exception('Error: No batches were processed!')
     avg = sums / n_batches
     result = dict(loss=float(avg[0]), loss_decoder=float(avg[1]), loss_post_processing=float(avg[2]),
                   global_step=global_step, n_batches=n_batches)
+    if mcd:
+        per_utterance = np.concatenate(mcds).astype(np.float64)
+        result['mcd'] = float(np.mean(per_utterance))
+        result['mcd_utterances'] = int(per_utterance.shape[0])
     if verbose:
         print('[evaluate] step: {}, batches: {}, loss: {:.6f}, loss_decoder: {:.6f}, loss_post_processing: {:.6f}'.format(
             global_step, n_batches, result['loss'], result['loss_decoder'], result['loss_post_processing']))
+        if mcd:
+            print('[evaluate] step: {}, utterances: {}, mcd: {:.6f} dB'.format(global_step, result['mcd_utterances'], result['mcd']))
     checkpoint_dir = evaluation_params.checkpoint_dir if checkpoint_dir is None else checkpoint_dir
     if checkpoint_dir:
         save_dir = os.path.join(checkpoint_dir, checkpoint_save_run or evaluation_params.checkpoint_save_run)
@@ -142,6 +182,8 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
         line = {'global_step': global_step, 'checkpoint': checkpoint_file, 'n_batches': n_batches,
                 'loss/loss': result['loss'], 'loss/loss_decoder': result['loss_decoder'],
                 'loss/loss_post_processing': result['loss_post_processing']}
+        if mcd:
+            line['metric/mcd'] = result['mcd']
         with open(os.path.join(save_dir, SUMMARY_FILE), 'a') as f:
             f.write(json.dumps(line) + '\n')
     return result
@@ -159,7 +201,8 @@ def collect_checkpoint_paths(checkpoint_dir):
 
 
 def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, batch_size=None, checkpoint_dir=None,
-                        checkpoint_save_run=None, hparams=None, device_id=0, verbose=True):
+                        checkpoint_save_run=None, hparams=None, device_id=0, verbose=True, mcd=False, mcd_coeffs=13,
+                        mcd_stop_at_silence=None):
     """One cycle of the reference's ``__eval_cycle`` (:336-352): a dataset loader, the batches, a model with its own
     engine, :func:`evaluate`; the engine is released afterwards."""
     from ..datasets.lj_speech import LJSpeechDatasetHelper
@@ -171,7 +214,8 @@ def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, 
     model = Tacotron(Tacotron.model_placeholders(), Mode.EVAL, hparams=hparams or model_params, device_id=device_id)
     try:
         return evaluate(model, checkpoint_file, batches, checkpoint_dir=checkpoint_dir,
-                        checkpoint_save_run=checkpoint_save_run, verbose=verbose)
+                        checkpoint_save_run=checkpoint_save_run, verbose=verbose, mcd=mcd, mcd_coeffs=mcd_coeffs,
+                        mcd_stop_at_silence=mcd_stop_at_silence)
     finally:
         model.engine.close()
 
@@ -181,10 +225,12 @@ def main(argv=None):
 
         python -m single-speaker-tts_amd.tacotron.evaluate [--all] [--checkpoint-dir D] [--load-run R] [--save-run S]
                                                            [--dataset-folder F] [--max-samples N] [--batch-size B]
+                                                           [--mcd [--mcd-coeffs K] [--mcd-stop-at-silence DB]]
 
     The options override the ``evaluation_params`` / ``dataset_params`` fields of the same name.  Without ``--all``
     (``evaluate_all_checkpoints``) the latest checkpoint of ``<checkpoint_dir>/<load_run>`` is evaluated, with it every
-    checkpoint its listing file names.  Prints one JSON line per checkpoint."""
+    checkpoint its listing file names.  ``--mcd`` adds the mel-cepstral distortion (module docstring).  Prints one JSON line
+    per checkpoint."""
     import argparse
     from .checkpoint import latest_checkpoint
     ap = argparse.ArgumentParser(prog='tacotron.evaluate')
@@ -196,7 +242,13 @@ def main(argv=None):
     ap.add_argument('--max-samples', type=int, default=evaluation_params.max_samples)
     ap.add_argument('--batch-size', type=int, default=evaluation_params.batch_size)
     ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--mcd', action='store_true', help='also report the DTW-aligned mel-cepstral distortion in dB')
+    ap.add_argument('--mcd-coeffs', type=int, default=13, help='cepstral coefficients 1 .. K are compared (default 13)')
+    ap.add_argument('--mcd-stop-at-silence', type=float, default=None, metavar='DB',
+                    help='end every prediction behind its last linear frame above DB decibels')
     args = ap.parse_args(argv)
+    if not args.mcd and (args.mcd_coeffs != 13 or args.mcd_stop_at_silence is not None):
+        ap.error('--mcd-coeffs and --mcd-stop-at-silence need --mcd')
     load_dir = os.path.join(args.checkpoint_dir, args.load_run)
     if args.all:
         files = collect_checkpoint_paths(load_dir)
@@ -209,7 +261,8 @@ def main(argv=None):
     for checkpoint_file in files:
         res = evaluate_checkpoint(checkpoint_file, dataset_folder=args.dataset_folder, max_samples=args.max_samples,
                                   batch_size=args.batch_size, checkpoint_dir=args.checkpoint_dir,
-                                  checkpoint_save_run=args.save_run, device_id=args.device)
+                                  checkpoint_save_run=args.save_run, device_id=args.device, mcd=args.mcd,
+                                  mcd_coeffs=args.mcd_coeffs, mcd_stop_at_silence=args.mcd_stop_at_silence)
         print(json.dumps(dict(res, checkpoint=checkpoint_file)))
     return 0
 

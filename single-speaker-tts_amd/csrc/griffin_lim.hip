@@ -186,9 +186,14 @@ size_t gl_state_bytes() { return sizeof(gl_state_t); }
 // (bit-reproducible) and is the only synchronisation inside a run: once index i has been added, every frame <= i - halo
 // has its final signal, and what the forward FFT of frame i - halo reads is not written again before the ring comes
 // round (R >= 9 + halo + ceil(S / hop) + 1: by the time an index may overwrite a position, every wave has finished the
-// iteration that read it; gl_stream_ring_frames).  Frames whose window leaves the signal (reflect padding) or whose
-// span crosses the lap end (the final values of the wrapped part are at the ring's start, not in the guard) take an
-// index-mapped read path: 4 + (halo + ceil(S / hop)) / R of the frames.
+// iteration that read it; gl_stream_ring_frames).  The forward transform's input is read linearly, a ds_read2 and a packed
+// multiply per slot.  A frame whose span crosses the end of the ring after the next lap has folded (the final values of the
+// wrapped part are at the ring's start, not in the guard: ring slots sm with hop sm + S > hop R and R - sm <= lag, the last
+// min(lag, ceil(S / hop) - 1) of every R frames -- 4 of 24 with three iterations per launch at 1102 / 275, 4 of 38 with two,
+// 4 of 64 with one) reads its slots at or above the end ring_len lower and the one slot that straddles it element by element
+// (fft_input).  Until round 7 those frames took the index-mapped path -- an address computation and a ds_read_b32 per sample,
+// ~500 VALU instructions per frame against ~55 -- that only the frames whose window leaves the signal (reflect padding: 4 to
+// 12 per utterance and iteration) need and take now.
 // MODE 1 writes out, straight from the overlap-add's registers, the hop samples that index i makes final.
 #define GL_NO_ITEM 0x7FFFFFFEu   // "not drawn yet" in the control word of the next item (item ids are < 2^31 - 2)
 enum { CT_OLA = 0, CT_SNEXT = 1, CT_OLB = 2 /* chain words of stages 1, 2 */ };   // of the CT_SWORDS control words (gl_plan.h)
@@ -505,16 +510,29 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
     auto fft_input = [&](const float* ring, int idx, int sm, int tm, int y_base, cf (&v)[16]) __attribute__((always_inline)) {
         const int ylo = tm * hop + wpad - MH;                    // y index of window sample 0
         const bool edge = ylo < 0 || ylo + win > GL_L;              // reflect padding needed
-        // The span is read linearly when it does not cross the end of the lap, or when the next lap's fold (index
-        // m + R - sm) has not happened yet: what it will fold is still in the guard, behind the ring.
-        if (!edge && (hop * sm + S <= ring_len || R - sm > lag)) {
+        // Three read paths.  LINEAR: the span does not cross the end of the ring, or the next lap's fold (index m + R - sm,
+        // m = idx - lag) has not happened yet -- what it will fold is still in the guard, behind the ring.  WRAPPED LINEAR:
+        // the span crosses the end and the fold has happened (R - sm <= lag): the final values of the wrapped part are at the
+        // ring's start, so the span sample at ring position pos = hop sm + q is at pos below ring_len and at pos - ring_len
+        // from there on.  Both are ONE loop: sm, hop and R are wave-uniform, so the 128-sample slots are classified with
+        // scalars.  j_sel is the first slot that is not wholly below ring_len (past every slot on the linear path); the
+        // pairs of slots from there on take their base ring_len lower, which is right for every slot wholly below and every
+        // slot wholly at or above the end, and slot j_sel -- the only one that can straddle it, and with an odd hop one of
+        // its pairs can, too -- is read again behind the loop, two ds_read_b32 with a compare and a select per address.
+        // (What the loop read for that slot lies within the workgroup's LDS: at most 128 floats into the guard, or in front
+        // of the ring, where the control words and the exchange buffers are.)  INDEX-MAPPED: reflect padding only.
+        if (!edge) {
             // (one opaque LDS base per pair of slots, as in overlap_add; a packed multiply per slot)
             const float* const lds_f = reinterpret_cast<const float*>(smem_raw);
-            const int e_rd = (int)(ring - lds_f) + hop * sm + 2 * lane;
+            const int pos0 = hop * sm;                               // ring position of span sample 0
+            const int ring_e = (int)(ring - lds_f);
+            const int e_rd = ring_e + pos0 + 2 * lane;
+            const bool folded = pos0 + S > ring_len && R - sm <= lag;
+            const int j_sel = folded ? (ring_len - pos0) >> 7 : 0x7fff;
             int ro[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                ro[k] = e_rd + 256 * k;
+                ro[k] = e_rd + (256 * k - (2 * k >= j_sel ? ring_len : 0));
                 if (2 * k < n_sl) asm("" : "+v"(ro[k]));
             }
 #pragma unroll
@@ -523,6 +541,21 @@ __global__ __launch_bounds__(GL_THREADS) void gl_stream_kernel(GlParams p) {
                 if (j < 0 || j >= n_sl) { v[c] = cmk(0.f, 0.f); continue; }
                 const float* sf = lds_f + ro[j >> 1] + 128 * (j & 1);
                 v[c] = cmk(wana[c][0], wana[c][1]) * cmk(sf[0], sf[1]);
+            }
+            if (j_sel < n_sl) {
+                const int q0 = pos0 + 128 * j_sel + 2 * lane;        // < ring_len + 128
+                const int a0 = ring_e + (q0 >= ring_len ? q0 - ring_len : q0);
+                const int a1 = ring_e + (q0 + 1 >= ring_len ? q0 + 1 - ring_len : q0 + 1);
+                const cf x = cmk(lds_f[a0], lds_f[a1]);
+                // (selects, not branches: as `if (c - c_lo == j_sel) v[c] = ...` this was a switch whose every case copied the
+                // other slots' registers -- 380 instructions per call site for the 40 of a multiply and two selects per slot)
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    if (c < c_lo || c > c_hi) continue;
+                    const cf y = cmk(wana[c][0], wana[c][1]) * x;
+                    const bool hit = c - c_lo == j_sel;              // (wave-uniform)
+                    v[c] = cmk(hit ? y.x : v[c].x, hit ? y.y : v[c].y);
+                }
             }
         } else {
             // index-mapped reads: reflect at the signal's ends; run coordinate u = lap * ring_len + off lives at

@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 def main():
     src, dst = sys.argv[1], sys.argv[2]
     per = int(sys.argv[3]) if len(sys.argv) > 3 else 3
-    want = 'false, {}, false>'.format(per)
+    want = ', false, {}, false, false, false>'.format(per)   # <MODE, WIN, HOP, MSE, NST, SEEDED, MOM, RAG>: the plain form
     cur = None
     vals = {}
     dur_us = None

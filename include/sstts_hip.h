@@ -173,9 +173,10 @@ int tts_synchronize(tts_handle_t h);
  * difference from IEEE f32 arithmetic on non-finite values: an output that depends on a +-Inf operand is NaN (the split of Inf
  * contains Inf - Inf), not +-Inf; NaN operands give NaN; every output that depends on finite operands only is unaffected.
  * Non-finite values on the audio side: a NaN is never turned into a plausible finite number.  Where the reference clips
- * (np.clip, np.maximum: tts_denorm_power, the de-normalising epilogue of tts_synthesize's final Dense, tts_db_convert) a NaN
- * input gives a NaN output at the same element, as in numpy, and +-Inf clip like any other value; every element that does not
- * depend on the NaN keeps the bits of a clean run.  A NaN magnitude makes the waveform of ITS utterance non-finite and its
+ * (np.clip, np.maximum: tts_denorm_power, the de-normalising epilogue of tts_synthesize's final Dense, tts_db_convert, the dB
+ * and normalisation lines of tts_extract_features in features.hip) a NaN input gives a NaN output at the same element, as in
+ * numpy, and +-Inf clip like any other value; every element that does not depend on the NaN keeps the bits of a clean run.
+ * Where the reference takes a maximum (np.max: the loudest frame of tts_trim_bounds in features.hip) a NaN operand gives NaN.  A NaN magnitude makes the waveform of ITS utterance non-finite and its
  * Griffin-Lim mse NaN (the other utterances of the batch are untouched); no loop bound or wait of a kernel depends on data. */
 
 /* ---- weights: replaces tf.train.Saver().restore (tacotron/inference.py:55,71) ---------- */
@@ -441,7 +442,10 @@ int tts_db_convert(tts_handle_t h, const float* in, size_t n, int mode, float re
  * mse_k = mean square of the frame (float64), frame k non-silent iff 10 log10(max(1e-10, mse_k)) - 10 log10(max(1e-10,
  * max mse)) > -top_db (float64), bounds[2b] = first * hop, bounds[2b + 1] = min(n, (last + 1) * hop).  bounds: DEVICE int64
  * [2B].  Needs n > frame_length / 2 for every recording (TTS_ERR_INVALID otherwise) and top_db > 0.  Two launches whatever
- * B and the lengths are; asynchronous. */
+ * B and the lengths are; asynchronous.
+ * Non-finite samples are decided as numpy decides them: a NaN anywhere in a recording makes the maximum, and with it the
+ * reference level, NaN, every comparison is false, no frame is non-silent and the bounds are {0, 0}; a +-Inf sample gives
+ * {0, 0} too (Inf - Inf in its frames, -Inf in the others).  The other recordings of the batch are untouched. */
 int tts_trim_bounds(tts_handle_t h, const float* wav, const int64_t* offsets, int B, int frame_length, int hop_length,
                     float top_db, int64_t* bounds);
 
@@ -478,7 +482,12 @@ int tts_plan_features(tts_handle_t h, const float* wav, const int64_t* offsets, 
  * (raw dB when p->normalize is 0), and 0 in the padding rows t >= 1 + (end - start) / hop.  Outputs (device, float32) are
  * time-major and ragged: recording b's rows follow those of recording b - 1, mel_out [sum T_pad][n_mels], lin_out
  * [sum T_pad][F] -- per recording the reference's (T_pad / r, n_mels r) / (T_pad / r, F r) arrays.  One launch; a recording's
- * rows are the same bits whatever batch it is in and at whatever position.  Asynchronous; the plan is read on the host. */
+ * rows are the same bits whatever batch it is in and at whatever position.  Asynchronous; the plan is read on the host.
+ * Non-finite samples: a NaN sample makes every linear value NaN, and every mel value whose band is not empty, in exactly the
+ * frames whose win_length span holds it, raw or normalised (np.maximum(1e-5, nan) and np.clip(nan, 0, 1) are NaN: it never
+ * comes out as -100 dB or 0.0); a +-Inf sample gives NaN or the image of +Inf (inf raw, 1.0 normalised) there.  Every other
+ * frame and recording keeps the bits of a clean run.  With p->trim, tts_plan_features refuses a recording that holds a
+ * non-finite sample: its trim bounds are {0, 0}, "at most n_fft / 2" samples. */
 int tts_extract_features(tts_handle_t h, const float* wav, const int64_t* offsets, int B, const tts_feature_params_t* p,
                          const int64_t* plan, float* mel_out, float* lin_out);
 

@@ -60,15 +60,20 @@ __device__ __forceinline__ int find_item(const D* __restrict__ d, int B, long lo
     return lo;
 }
 
+// numpy's max: a NaN operand gives the NaN (fmax would return the other operand)
+__device__ __forceinline__ double max_keep_nan(double a, double b) { return a != a ? a : (b != b ? b : fmax(a, b)); }
+
 __device__ __forceinline__ int reflect_index(long long i, int n) {   // numpy.pad(mode='reflect'), one bounce (pad < n)
     i = i < 0 ? -i : i;
     return (int)(i >= n ? 2 * (long long)(n - 1) - i : i);
 }
 
-// magnitude_to_decibel (float64 log, as tts_db_convert mode 0) and, when norm, normalize_decibel (as mode 2)
+// magnitude_to_decibel (float64 log, as tts_db_convert mode 0) and, when norm, normalize_decibel (as mode 2).  A NaN
+// magnitude stays a NaN in both forms, as np.maximum and np.clip leave it (fmaxf / fminf alone would return 1e-5 and the
+// clip edge: "Non-finite values" in include/sstts_hip.h); every other x takes the fmaxf / fminf path bit for bit.
 __device__ __forceinline__ float feat_db(float x, int norm, float ref_db, float range) {
-    const float db = (float)(20.0 * log10((double)fmaxf(1e-5f, x)));
-    return norm ? fminf(fmaxf(1.0f + (db - ref_db) / range, 0.f), 1.f) : db;
+    const float db = (float)(20.0 * log10((double)(x != x ? x : fmaxf(1e-5f, x))));
+    return norm ? clip_keep_nan(1.0f + (db - ref_db) / range, 0.f, 1.f) : db;
 }
 
 struct FeatArgs {
@@ -117,15 +122,17 @@ __global__ __launch_bounds__(TRIM_THREADS) void trim_bounds_kernel(const TrimDes
     const int nf = r.n / H + 1;
     const double* m = mse + r.fr0;
     double mx = 0.0;
-    for (int k = tid; k < nf; k += TRIM_THREADS) mx = fmax(mx, m[k]);
+    for (int k = tid; k < nf; k += TRIM_THREADS) mx = max_keep_nan(mx, m[k]);
     red[tid] = mx;
     if (tid == 0) { first_s = nf; last_s = -1; }
     __syncthreads();
     for (int s = TRIM_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+        if (tid < s) red[tid] = max_keep_nan(red[tid], red[tid + s]);
         __syncthreads();
     }
-    const double ref = 10.0 * log10(fmax(1e-10, red[0]));
+    // A NaN sample makes its frames' mse and so the maximum NaN: ref is NaN, every comparison below is false and the
+    // bounds are (0, 0), as numpy decides; a +-Inf sample ends there too (Inf - Inf in its frames, -Inf in the others).
+    const double ref = 10.0 * log10(red[0] != red[0] ? red[0] : fmax(1e-10, red[0]));
     int first = nf, last = -1;
     for (int k = tid; k < nf; k += TRIM_THREADS)
         if (10.0 * log10(fmax(1e-10, m[k])) - ref > -top_db) {
@@ -136,7 +143,7 @@ __global__ __launch_bounds__(TRIM_THREADS) void trim_bounds_kernel(const TrimDes
     atomicMax(&last_s, last);
     __syncthreads();
     if (tid == 0) {
-        long long start = 0, end = 0;   // (no frame qualifies only for top_db <= 0, which the host refuses)
+        long long start = 0, end = 0;   // (no frame qualifies: a non-finite sample; top_db <= 0 is refused by the host)
         if (last_s >= 0) {
             start = (long long)first_s * H;
             const long long e = (long long)(last_s + 1) * H;

@@ -37,6 +37,35 @@ def test_trim_threshold_depends_on_top_db():
     assert s60 == 0 and s40 == 4 * 512
 
 
+def test_trim_of_a_recording_with_a_nan_is_empty():
+    # frame k covers [512 k - 1024, 512 k + 1024): sample 2500 lies in frames 3 .. 6 only, yet the NaN reaches the maximum and
+    # with it the reference level of every frame -- numpy finds no frame above the threshold
+    y = np.zeros(5000, np.float32)
+    y[2000:3000] = np.sin(0.1 * np.arange(1000))
+    y[2500] = np.nan
+    mse, db = T.frame_power_db(y)
+    assert np.flatnonzero(np.isnan(mse)).tolist() == [3, 4, 5, 6] and np.isnan(db).all()
+    assert T.trim_bounds(y) == (0, 0) and T.trim_bounds(y, top_db=20) == (0, 0)
+    # ... wherever it is: in the first frame (through the reflection), in the last sample
+    for pos in (0, 4999):
+        y = np.zeros(5000, np.float32)
+        y[2000:3000] = np.sin(0.1 * np.arange(1000))
+        y[pos] = np.nan
+        assert T.trim_bounds(y) == (0, 0)
+
+
+def test_trim_of_a_recording_with_an_infinity_is_empty():
+    # the frames that hold the sample are Inf - Inf = NaN against the reference level, the others finite - Inf = -Inf
+    for value in (np.inf, -np.inf):
+        y = np.zeros(5000, np.float32)
+        y[2000:3000] = np.sin(0.1 * np.arange(1000))
+        y[2500] = value
+        mse, db = T.frame_power_db(y)
+        assert np.flatnonzero(np.isinf(mse)).tolist() == [3, 4, 5, 6]
+        assert np.isnan(db[3:7]).all() and np.isneginf(np.delete(db, [3, 4, 5, 6])).all()
+        assert T.trim_bounds(y) == (0, 0)
+
+
 def test_silence_interval_from_spectrogram():
     E = pkg('audio.effects')
     spec = np.full((5, 8), -80.0)

@@ -9,31 +9,14 @@ import wave
 import numpy as np
 import pytest
 
+import feature_cases as FC
 import trim_oracle as T
 from conftest import ROOT, pkg
+from feature_cases import speechlike
 from parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 SR = 22050
-
-
-def speechlike(rng, n, lead=0, trail=0, floor_db=-40.0, quiet=1e-5):
-    """Tones with a syllable envelope plus a noise floor `floor_db` below the peak, between margins of quiet noise.  A small DC
-    offset and a small component at the Nyquist frequency keep the two real-valued bins off the 1e-5 magnitude floor: under
-    noise alone they are Gaussian, not Rayleigh, and come near zero in about one frame in a thousand, where the float32
-    transform's absolute error (~4e-7 here) is a large part of a dB value."""
-    t = np.arange(n) / SR
-    f0 = rng.uniform(90, 220)
-    x = np.zeros(n)
-    for h in range(1, 12):
-        x += rng.uniform(0.2, 1.0) / h * np.sin(2 * np.pi * f0 * h * t * (1 + 0.02 * np.sin(2 * np.pi * 3 * t)) + rng.uniform(0, 6.3))
-    x *= 0.55 + 0.45 * np.sin(2 * np.pi * rng.uniform(2, 5) * t + rng.uniform(0, 6.3))
-    x *= 0.5 / np.max(np.abs(x))
-    x += 0.5 * 10 ** (floor_db / 20) * rng.standard_normal(n)
-    x += 2e-3 * (1.0 + (-1.0) ** np.arange(n))
-    out = quiet * rng.standard_normal(lead + n + trail)
-    out[lead:lead + n] = x
-    return out.astype(np.float32)
 
 
 def _batch(rng, B, lo=0.3, hi=3.0):
@@ -97,6 +80,10 @@ def _check_features(got, w, label, **kw):
     Tf = 1 + (e - s) // hop
     assert not np.any(mel_g.reshape(-1, n_mels)[Tf:]) and not np.any(lin_g.reshape(-1, F)[Tf:])
     assert mel_g.reshape(-1, n_mels).shape[0] - Tf < r
+    # every element inside the interval of feature_cases.py, with its exact checks (floor, padding rows)
+    cfg = (kw.get('n_fft', 2048), kw.get('win', 1102), hop, kw.get('sr', SR), n_mels, kw.get('fmin', 0.0), kw.get('fmax', 8000.0))
+    bad, _ = FC.check_rows(mel_g.reshape(-1, n_mels), lin_g.reshape(-1, F), FC.oracle(w, cfg, r, (s, e)), kw.get('normalize', True), label)
+    assert not bad, bad
 
 
 def test_feature_parity_model_configuration(eng):

@@ -2,7 +2,11 @@
 106-156 load_audio), composed from ``oracle.audio_oracle`` (a plain helper module, imported like conftest's helpers).
 
 trim: reflect-pad y by frame_length // 2, frames k = 0 .. n // hop, mse_k = mean(frame ** 2); frame k is non-silent iff
-10 log10(max(1e-10, mse_k)) - 10 log10(max(1e-10, max mse)) > -top_db; start = first * hop, end = min(n, (last + 1) * hop)."""
+10 log10(max(1e-10, mse_k)) - 10 log10(max(1e-10, max mse)) > -top_db; start = first * hop, end = min(n, (last + 1) * hop).
+
+Non-finite samples are decided as numpy decides them: ``mse.max()`` and ``np.maximum`` carry a NaN, so one NaN sample makes the
+reference level NaN and every comparison false -- no frame is non-silent and the bounds are (0, 0).  A +-Inf sample ends there
+too: its frames are Inf - Inf = NaN against the reference, all others -Inf."""
 import numpy as np
 
 from oracle import audio_oracle as A
@@ -14,8 +18,9 @@ def frame_power_db(y, frame_length=2048, hop_length=512):
     yp = np.pad(y, frame_length // 2, mode='reflect')
     n_frames = 1 + len(y) // hop_length
     idx = np.arange(frame_length)[None, :] + hop_length * np.arange(n_frames)[:, None]
-    mse = np.mean(yp[idx] ** 2, axis=1)
-    db = 10.0 * np.log10(np.maximum(1e-10, mse)) - 10.0 * np.log10(np.maximum(1e-10, mse.max()))
+    with np.errstate(invalid='ignore', over='ignore'):
+        mse = np.mean(yp[idx] ** 2, axis=1)
+        db = 10.0 * np.log10(np.maximum(1e-10, mse)) - 10.0 * np.log10(np.maximum(1e-10, mse.max()))   # numpy's own max: NaN stays
     return mse, db
 
 

@@ -544,6 +544,58 @@ int tts_dtw_max_frames(void);
 /* Host only: the cells of one piece of the cut of an anti-diagonal (no result depends on it; tests place their shapes around it). */
 int tts_dtw_tile(void);
 
+/* ---- F0 tracking: F0 RMSE, voicing error and gross pitch error ------------------------------ */
+/* The fundamental frequency of B waveforms by YIN (de Cheveigne and Kawahara 2002, steps 2 to 5; no reference counterpart: the
+ * track under which audio/metrics.py measures F0 RMSE, voicing error and gross pitch error).  wav DEVICE [B][N]; n_samples: HOST
+ * int32 [B], the samples of each utterance, or NULL (all N).  T = tts_f0_frames(N, hop) = 1 + N / hop values per row; utterance b
+ * has T_b = tts_f0_frames(n_b, hop) frames, frame t at sample t * hop -- the frames of the centred STFT: a hop (T - 1)-sample
+ * Griffin-Lim waveform gives T values.  x(i) = (double)wav[b][i] for 0 <= i < n_b and 0.0 otherwise; samples at or behind n_b are
+ * never read.  For frame t, with s0 = t * hop - (W + tau_max) / 2 (integer division):
+ *   difference     for tau in 1 .. tau_max: s = 0.0; for j in 0 .. W - 1: u = x(s0 + j) - x(s0 + j + tau); s = s + u * u; d[tau] = s
+ *                  every operation an IEEE double operation rounded on its own (no FMA)
+ *   normalisation  c = 0.0; for tau ascending: c = c + d[tau]; q[tau] = (c == 0.0) ? 1.0 : (d[tau] * (double)tau) / c
+ *   non-finite     a final c that is not finite (a NaN or Inf sample in the span): f0 and aperiodicity of the frame are NaN, and
+ *                  nothing below applies; no other frame and no other utterance is touched
+ *   threshold      tau1 = the smallest tau in [tau_min, tau_max] with q[tau] < threshold.  None: the frame is unvoiced, f0 = 0 and
+ *                  aperiodicity = (float)q[best], best = the first index of the minimum over [tau_min, tau_max] (a later value
+ *                  replaces it only if strictly smaller)
+ *   descent        tau* = the smallest tau >= tau1 with tau == tau_max or not q[tau + 1] < q[tau]
+ *   interpolation  delta = 0.0; if tau* < tau_max: a = q[tau* - 1], b = q[tau*], g = q[tau* + 1], den = (a + g) - (b + b), and
+ *                  if a >= b && g >= b && den > 0: delta = (0.5 * (a - g)) / den
+ *   f0[b][t] = (float)(sampling_rate / ((double)tau* + delta)), aperiodicity[b][t] = (float)q[tau*]
+ *   padding        frames t >= T_b are written as 0
+ * f0 DEVICE float [B][T]; aperiodicity DEVICE float [B][T] or NULL.  Exactness: f0 and aperiodicity are the bits of the sequential
+ * evaluation (tests/f0_oracle.py) whatever the library's cut into lags, frames and workgroups.  Independence: an utterance's
+ * results do not depend on B, on its place in the batch, on N or on earlier calls.  No loop bound or wait depends on the data;
+ * no atomics.  No model needed; asynchronous on the handle's stream, one launch per 64 utterances (the lengths travel in the
+ * launch); profile stage "f0".
+ * Limits: 1 <= W <= tts_f0_max_window() (2048) and 2 <= tau_min <= tau_max <= tts_f0_max_lag() (1024: 21.5 Hz at 22050 Hz); beyond
+ * them TTS_ERR_UNSUPPORTED, and the message names the limit.  TTS_ERR_INVALID, before anything is enqueued: a NULL wav or f0, B,
+ * N or hop < 1, a length outside [1, N], a sampling_rate that is not finite and positive, a NaN threshold. */
+int tts_f0(tts_handle_t h, const float* wav /* [B][N] */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+           double sampling_rate, int hop, int W, int tau_min, int tau_max, double threshold,
+           float* f0 /* [B][T] */, float* aperiodicity /* [B][T] or NULL */);
+/* Host only: the values tts_f0 writes for n samples, 1 + n / hop (0 for n < 0 or hop < 1). */
+int tts_f0_frames(int n, int hop);
+/* Host only: the largest W and the largest tau_max tts_f0 takes. */
+int tts_f0_max_window(void);
+int tts_f0_max_lag(void);
+/* The F0 and voicing errors of B pairs of tracks along alignment paths.  f0_a DEVICE [B][Ta], f0_b DEVICE [B][Tb] (side b is the
+ * recording); path DEVICE int32 [B][rows][2] as tts_dtw writes it: all `rows` rows are walked, and rows with a negative entry
+ * (those behind the path), or an entry at or beyond Ta / Tb, are skipped.  For every step (i, j) in row order, with
+ * fa = (double)f0_a[i], fb = (double)f0_b[j]; voiced means > 0:
+ *   counts[0] every step;  counts[4] a step with a NaN on either side, which counts nowhere else
+ *   counts[2] exactly one side voiced
+ *   both voiced: counts[1]; u = fa - fb, sums[0] = sums[0] + u * u (a product and a sum, in row order: the bits of
+ *                tests/f0_oracle.py); counts[3] when fabs(u) > 0.2 * fb (gross pitch error, 20 %);
+ *                z = 1200.0 * log2(fa / fb), sums[1] = sums[1] + z * z (through the device's log2: against a float64 evaluation
+ *                S64, |sums[1] - S64| <= 2e-12 sum |z_k| + 1e-15 S64)
+ * counts DEVICE int32 [B][5], sums DEVICE double [B][2] (8-byte aligned).  No atomics, the loop bound is `rows`; one launch,
+ * asynchronous on the handle's stream; profile stage "f0".  TTS_ERR_INVALID, before anything is enqueued: a NULL pointer, B, Ta,
+ * Tb or rows < 1, sums not 8-byte aligned. */
+int tts_f0_compare(tts_handle_t h, const float* f0_a, int Ta, const float* f0_b, int Tb, const int32_t* path /* [B][rows][2] */,
+                   int rows, int B, int32_t* counts /* [B][5] */, double* sums /* [B][2] */);
+
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,
  * optional peak normalisation; replaces tacotron/inference.py:162-200 minus file IO.
@@ -651,7 +703,7 @@ int tts_set_pitch(tts_handle_t h, double octaves);
  * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize),
  * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
  * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
- * "mfcc" (tts_mfcc), "dtw" (tts_dtw).
+ * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

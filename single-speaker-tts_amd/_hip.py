@@ -123,6 +123,12 @@ _PROTOTYPES = {
                         c_void_p, c_void_p, c_void_p]),
     'tts_dtw_max_frames': (c_int, []),
     'tts_dtw_tile': (c_int, []),
+    'tts_f0': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_int, c_int, c_int, ctypes.c_double,
+                       c_void_p, c_void_p]),
+    'tts_f0_frames': (c_int, [c_int, c_int]),
+    'tts_f0_max_window': (c_int, []),
+    'tts_f0_max_lag': (c_int, []),
+    'tts_f0_compare': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -361,6 +367,23 @@ def stretched_frames(n, rate):
     if r is None or int(n) != n or n < 1:
         raise ValueError('stretched_frames: need n >= 1 frames and a rate, got {!r}, {!r}'.format(n, rate))
     return int(np.ceil(np.float64(int(n)) / np.float64(r)))
+
+
+F0_MAX_WINDOW = 2048   # tts_f0_max_window()
+F0_MAX_LAG = 1024      # tts_f0_max_lag()
+
+
+def f0_lag_bounds(sampling_rate, fmin, fmax):
+    """(tau_min, tau_max) of an F0 search between ``fmin`` and ``fmax`` Hz: max(2, int(sr // fmax)) and ceil(sr / fmin)."""
+    sr, fmin, fmax = float(sampling_rate), float(fmin), float(fmax)
+    if not (np.isfinite(sr) and sr > 0 and np.isfinite(fmin) and np.isfinite(fmax) and 0 < fmin <= fmax):
+        raise ValueError('f0: need a positive finite sampling rate and 0 < fmin <= fmax, got {!r}, {!r}, {!r}'.format(sampling_rate, fmin, fmax))
+    return max(2, int(sr // fmax)), int(np.ceil(sr / fmin))
+
+
+def f0_frames(n, hop_length):
+    """tts_f0_frames: the values tts_f0 writes for ``n`` samples, 1 + n // hop_length."""
+    return 1 + int(n) // int(hop_length)
 
 
 def stretch_frame_counts(n_frames, B, T):
@@ -1000,6 +1023,79 @@ class Engine(object):
                     x.free()
             raise
         return (cost, plen, path) if want_path else (cost, plen)
+
+    # ------------------------------------------------------------------ F0 tracking
+    def f0(self, wavs, sampling_rate, hop_length, fmin=60.0, fmax=500.0, window=1024, threshold=0.1, n_samples=None,
+           want_aperiodicity=False, tau_min=None, tau_max=None):
+        """tts_f0: the fundamental frequency of ``wavs`` -- one waveform (n,) or a batch (B, n), a host array or a device buffer --
+        by YIN, one value per ``hop_length`` samples: frame t sits at sample t hop_length, 1 + n // hop_length frames.  The lags
+        searched are tau_min = max(2, int(sr // fmax)) .. tau_max = ceil(sr / fmin) (or ``tau_min`` / ``tau_max`` as given), the
+        sums run over ``window`` samples, a frame is voiced where the normalised difference falls below ``threshold``.
+        ``n_samples``: B lengths (host integers) -- samples at or behind them are never read; None: all n.  Returns a device
+        array (B, T) of Hz, 0 in unvoiced and padding frames and NaN where a frame's span holds a non-finite sample -- (T,) for
+        a 1-D input -- and with ``want_aperiodicity`` also the normalised difference at the chosen lag, of the same shape.
+        include/sstts_hip.h has the definition: the results are the bits of tests/f0_oracle.py."""
+        single = len(wavs.shape) == 1
+        if single and not _is_device(wavs):
+            wavs = np.asarray(wavs).reshape(1, -1)
+        if len(wavs.shape) not in (1, 2) or min(wavs.shape) < 1:
+            raise ValueError('f0: one waveform (n,) or a batch (B, n) is needed, got shape {}'.format(tuple(wavs.shape)))
+        B, n = (1, int(wavs.shape[0])) if len(wavs.shape) == 1 else (int(d) for d in wavs.shape)
+        lo, hi = f0_lag_bounds(sampling_rate, fmin, fmax)
+        lo = lo if tau_min is None else tau_min
+        hi = hi if tau_max is None else tau_max
+        if int(hop_length) != hop_length or hop_length < 1 or int(window) != window or int(lo) != lo or int(hi) != hi:
+            raise ValueError('f0: hop_length >= 1, window and the lags must be integers, got {!r}, {!r}, {!r}, {!r}'.format(hop_length, window, lo, hi))
+        if not 1 <= window <= F0_MAX_WINDOW:
+            raise ValueError('f0: window = {} is not in 1 .. {} (tts_f0_max_window)'.format(window, F0_MAX_WINDOW))
+        if not 2 <= lo <= hi <= F0_MAX_LAG:
+            raise ValueError('f0: the lags {} .. {} are not 2 <= tau_min <= tau_max <= {} (tts_f0_max_lag): fmin is at least '
+                             'sampling_rate / {}'.format(lo, hi, F0_MAX_LAG, F0_MAX_LAG))
+        if np.isnan(float(threshold)):
+            raise ValueError('f0: the threshold is NaN')
+        ns = stretch_frame_counts(n_samples, B, n)
+        p_wav, _k = self._in(wavs, np.float32)
+        T = f0_frames(n, hop_length)
+        out = self.empty((T,) if single else (B, T))
+        ap = self.empty((T,) if single else (B, T)) if want_aperiodicity else None
+        try:
+            self._check(self.lib.tts_f0(self.handle, p_wav, B, n, ns.ctypes.data_as(POINTER(c_int32)) if ns is not None else None,
+                                        float(sampling_rate), int(hop_length), int(window), int(lo), int(hi), float(threshold),
+                                        out.data_ptr(), ap.data_ptr() if ap is not None else None))
+        except Exception:   # (a refusal: nothing was enqueued)
+            out.free()
+            if ap is not None:
+                ap.free()
+            raise
+        return (out, ap) if want_aperiodicity else out
+
+    def f0_compare(self, f0_a, f0_b, path):
+        """tts_f0_compare: the F0 and voicing errors of B pairs of tracks, ``f0_a`` (B, Ta) against ``f0_b`` (B, Tb) -- side b is
+        the recording -- along ``path`` (B, rows, 2) int32 as :meth:`dtw` writes it (rows with a negative entry are skipped); host
+        arrays or device buffers.  Returns the device arrays ``(counts, sums)``: int32 (B, 5) = steps, both voiced, one side
+        voiced, gross pitch errors (beyond 20 %), NaN steps; float64 (B, 2) = the sums of (fa - fb) ** 2 in Hz ** 2 and of
+        (1200 log2(fa / fb)) ** 2 in cents ** 2 over the steps voiced on both sides."""
+        if len(f0_a.shape) != 2 or len(f0_b.shape) != 2 or len(path.shape) != 3 or min(f0_a.shape) < 1 or min(f0_b.shape) < 1 or \
+                min(path.shape) < 1 or path.shape[2] != 2:
+            raise ValueError('f0_compare: (B, Ta) and (B, Tb) tracks and a (B, rows, 2) path are needed, got shapes {}, {} and {}'.format(
+                tuple(f0_a.shape), tuple(f0_b.shape), tuple(path.shape)))
+        B, Ta = (int(d) for d in f0_a.shape)
+        Bb, Tb = (int(d) for d in f0_b.shape)
+        rows = int(path.shape[1])
+        if Bb != B or int(path.shape[0]) != B:
+            raise ValueError('f0_compare: {} tracks in f0_a, {} in f0_b and {} paths'.format(B, Bb, path.shape[0]))
+        p_a, _ka = self._in(f0_a, np.float32)
+        p_b, _kb = self._in(f0_b, np.float32)
+        p_p, _kp = self._in(path, np.int32)
+        counts = self.empty((B, 5), np.int32)
+        sums = self.empty((B, 2), np.float64)
+        try:
+            self._check(self.lib.tts_f0_compare(self.handle, p_a, Ta, p_b, Tb, p_p, rows, B, counts.data_ptr(), sums.data_ptr()))
+        except Exception:   # (a refusal: nothing was enqueued)
+            counts.free()
+            sums.free()
+            raise
+        return counts, sums
 
     # ------------------------------------------------------------------ speaking rate
     def stretched_frames(self, n, rate):

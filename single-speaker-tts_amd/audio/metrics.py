@@ -1,7 +1,9 @@
 """Objective measures of a synthesised spectrogram against its recording.  No reference counterpart: the reference's only
 measure is the frame-by-frame L1 loss of ``tacotron.evaluate``, which measures the drift as soon as the free-running decoder
 speaks a little faster or slower than the recording.  Mel-cepstral distortion along a dynamic-time-warping path compares the
-spectra at the frames that belong together.  The cepstra (tts_mfcc) and the alignment (tts_dtw) run on the device."""
+spectra at the frames that belong together.  The cepstra (tts_mfcc) and the alignment (tts_dtw) run on the device.  Along the
+same path, F0 RMSE, voicing error and gross pitch error compare the prosody (tts_f0, tts_f0_compare), which the cepstra do not
+see."""
 import math
 
 import numpy as np
@@ -52,3 +54,30 @@ def mel_cepstral_distortion(mel_a, mel_b, n_a=None, n_b=None, n_coeffs=MCD_COEFF
     for d in (ca, cb) + tuple(res):
         d.free()
     return out
+
+
+def f0_errors(f0_a, f0_b, path, engine=None):
+    """The F0 and voicing errors of B pairs of F0 tracks, ``f0_a`` (B, Ta) against ``f0_b`` (B, Tb) in Hz -- 0 is unvoiced, side
+    b is the recording -- along ``path`` (B, rows, 2), the alignment :func:`mel_cepstral_distortion` returns with ``want_path``
+    (rows of (-1, -1) lie behind a path).  Host arrays or device buffers; the reduction runs in tts_f0_compare.  Returns a dict
+    of host arrays of B entries:
+        f0_rmse_hz         sqrt(sum (fa - fb) ** 2 / n) over the n steps voiced on both sides
+        f0_rmse_cents      sqrt(sum (1200 log2(fa / fb)) ** 2 / n) over the same steps
+        vuv_error          steps voiced on exactly one side / all steps
+        gross_pitch_error  steps voiced on both sides with |fa - fb| > 0.2 fb / steps voiced on both sides
+        counts             int32 (B, 5): steps, both voiced, one side voiced, gross pitch errors, NaN steps
+    The two RMSEs are NaN where a step holds a NaN (counts[4] > 0) or no step is voiced on both sides; gross_pitch_error is NaN
+    where no step is voiced on both sides, vuv_error where the path is empty."""
+    eng = engine or default_engine()
+    counts_d, sums_d = eng.f0_compare(f0_a, f0_b, path)
+    counts, sums = counts_d.to_host(), sums_d.to_host()
+    counts_d.free()
+    sums_d.free()
+    steps, both = counts[:, 0].astype(np.float64), counts[:, 1].astype(np.float64)
+    has = (counts[:, 1] > 0) & (counts[:, 4] == 0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        rmse_hz = np.where(has, np.sqrt(sums[:, 0] / both), np.nan)
+        rmse_cents = np.where(has, np.sqrt(sums[:, 1] / both), np.nan)
+        vuv = np.where(steps > 0, counts[:, 2] / steps, np.nan)
+        gpe = np.where(both > 0, counts[:, 3] / both, np.nan)
+    return dict(f0_rmse_hz=rmse_hz, f0_rmse_cents=rmse_cents, vuv_error=vuv, gross_pitch_error=gpe, counts=counts)

@@ -18,6 +18,12 @@ count a prediction that speaks a little faster or slower than the recording as w
 utterance's unpadded ``ph_time_frames * r`` frames; the prediction side the same count, or with ``mcd_stop_at_silence``
 (``--mcd-stop-at-silence DB``) the frames up to the last one of the predicted linear spectrogram that rises above that level.
 
+F0 errors.  With ``f0`` (``--f0``) the prosody is measured along the same path: the predicted and the target linear spectrograms of
+a batch both go through the same vocoder -- the de-normalisation, ``** magnitude_power`` and the ragged Griffin-Lim at the
+lengths the distortion uses -- so that its colouring cancels, tts_f0 tracks both waveforms, and ``audio.metrics.f0_errors`` gives
+every utterance its F0 RMSE in cents and Hz, its voicing error and its gross pitch error.  The path is computed whether or not
+``mcd`` reports its figure.
+
 TensorBoard events are not written: every evaluated checkpoint appends one JSON line with the reference's
 summary tags (``loss/loss``, ``loss/loss_decoder``, ``loss/loss_post_processing``) and its global step to
 ``<checkpoint_dir>/<checkpoint_save_run>/eval_summaries.jsonl``.
@@ -115,6 +121,12 @@ def global_step_of(checkpoint_file):
 def batch_mcd(model, feed, out, mcd_coeffs=13, mcd_stop_at_silence=None):
     """The mel-cepstral distortion of every utterance of one evaluated batch: ``out`` is what ``evaluate_device`` returned for
     ``feed`` (its ``mel``, and with ``mcd_stop_at_silence`` its ``linear``).  -> (B,) float64"""
+    return batch_alignment(model, feed, out, mcd_coeffs, mcd_stop_at_silence)[0]['mcd']
+
+
+def batch_alignment(model, feed, out, mcd_coeffs=13, mcd_stop_at_silence=None, want_path=False):
+    """The distortion of :func:`batch_mcd` with what it was measured on: (the dict of ``mel_cepstral_distortion`` -- with
+    ``want_path`` its ``path`` --, the prediction's frame counts, the target's frame counts)."""
     from ..audio.metrics import mel_cepstral_distortion
     eng = model.engine
     r, nm = eng.cfg.reduction, eng.cfg.n_mels
@@ -129,18 +141,58 @@ def batch_mcd(model, feed, out, mcd_coeffs=13, mcd_stop_at_silence=None):
         n_frames.free()
         last.free()
     res = mel_cepstral_distortion(out['mel'], target, n_a=n_pred, n_b=n_target, n_coeffs=mcd_coeffs,
-                                  ref_db=LJSpeechConstants.mel_mag_ref_db, max_db=LJSpeechConstants.mel_mag_max_db, engine=eng)
-    return res['mcd']
+                                  ref_db=LJSpeechConstants.mel_mag_ref_db, max_db=LJSpeechConstants.mel_mag_max_db, engine=eng,
+                                  want_path=want_path)
+    return res, np.asarray(n_pred, np.int32), np.asarray(n_target, np.int32)
+
+
+F0_KEYS = ('f0_rmse_cents', 'f0_rmse_hz', 'vuv_error', 'gross_pitch_error')
+
+
+def batch_f0(model, feed, out, path, n_pred, n_target, f0_iters=None, f0_min=60.0, f0_max=500.0, seed=0):
+    """The F0 errors of every utterance of one evaluated batch along ``path`` (B, 2 T - 1, 2), the alignment of
+    :func:`batch_alignment` at the frame counts ``n_pred`` / ``n_target``: the predicted linear spectrogram ``out['linear']`` and
+    the target's both become waveforms through the same vocoder and tracks through tts_f0.  -> the dict of
+    ``audio.metrics.f0_errors``, or None where the batch is shorter than the vocoder's shortest signal."""
+    from ..audio.metrics import f0_errors
+    from ..audio.conversion import ms_to_samples
+    eng, hp = model.engine, model.hparams
+    loader = dataset_params.dataset_loader
+    win_len, hop = ms_to_samples(hp.win_len, hp.sampling_rate), ms_to_samples(hp.win_hop, hp.sampling_rate)
+    B = feed['ph_sentences'].shape[0]
+    F = 1 + hp.n_fft // 2
+    target = np.ascontiguousarray(feed['ph_lin_specs'], dtype=np.float32).reshape(B, -1, F)
+    T = target.shape[1]
+    min_frames = hp.n_fft // 2 // hop + 2            # the smallest n with hop (n - 1) > n_fft / 2
+    if T < min_frames:
+        return None
+    tracks = []
+    for lin, n in ((out['linear'], n_pred), (target, n_target)):
+        frames = np.minimum(T, np.maximum(min_frames, np.asarray(n, np.int32))).astype(np.int32)
+        mag = eng.denorm_power(lin, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power)
+        wav, _ = eng.griffin_lim(mag, hp.reconstruction_iterations if f0_iters is None else f0_iters, win_len, hop, hp.n_fft,
+                                 seed=seed, want_mse=False, momentum=0.0, n_frames=frames)
+        tracks.append(eng.f0(wav, hp.sampling_rate, hop, fmin=f0_min, fmax=f0_max, n_samples=hop * (frames - 1)))
+        mag.free()
+        wav.free()
+    res = f0_errors(tracks[0], tracks[1], path, engine=eng)
+    for t in tracks:
+        t.free()
+    return res
 
 
 def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_save_run=None, verbose=True, mcd=False, mcd_coeffs=13,
-             mcd_stop_at_silence=None):
+             mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0):
     """reference :153-257.  Restores ``checkpoint_file`` into ``model`` (a ``Tacotron(..., Mode.EVAL)``) once, runs every
     feed dict of ``batches`` through tts_evaluate and returns ``{loss, loss_decoder, loss_post_processing, global_step,
     n_batches}``: the per-batch float32 losses averaged unweighted over the batches.  Raises if no batch ran.  Appends
     the summary line (module docstring) when ``checkpoint_dir`` (default ``evaluation_params.checkpoint_dir``) is set.
     With ``mcd`` the result gains ``mcd`` -- the mean mel-cepstral distortion over all utterances of the epoch, in dB -- and
-    ``mcd_utterances``, and the summary line ``metric/mcd``; without it nothing of the run, the result or the line changes."""
+    ``mcd_utterances``, and the summary line ``metric/mcd``; without it nothing of the run, the result or the line changes.
+    With ``f0`` the result and the summary line gain ``metric/f0_rmse_cents``, ``metric/f0_rmse_hz``, ``metric/vuv_error`` and
+    ``metric/gross_pitch_error`` -- each the mean over the utterances that have that figure -- and ``f0_utterances``, the
+    utterances that have an F0 RMSE (``f0_iters``: Griffin-Lim iterations, default the model's ``reconstruction_iterations``;
+    ``f0_min`` / ``f0_max``: the search range in Hz); without it nothing of the run, the result or the line changes."""
     if model._mode != Mode.EVAL:
         raise ValueError('evaluate() needs a Tacotron in Mode.EVAL')
     global_step = global_step_of(checkpoint_file)
@@ -153,12 +205,20 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
     sums = np.zeros(3, np.float64)
     n_batches = 0
     mcds = []
+    f0s = []
     for feed in batches:
         out = model.evaluate_device(feed['ph_sentences'], feed['ph_mel_specs'], feed['ph_lin_specs'],
-                                    want_mel=bool(mcd), want_alignments=False,
-                                    want_linear=bool(mcd) and mcd_stop_at_silence is not None)
+                                    want_mel=bool(mcd) or bool(f0), want_alignments=False,
+                                    want_linear=(bool(mcd) and mcd_stop_at_silence is not None) or bool(f0))
         sums += out['losses'].to_host().astype(np.float64)
-        if mcd:
+        if f0:
+            res, n_pred, n_target = batch_alignment(model, feed, out, mcd_coeffs, mcd_stop_at_silence, want_path=True)
+            if mcd:
+                mcds.append(res['mcd'])
+            errs = batch_f0(model, feed, out, res['path'], n_pred, n_target, f0_iters, f0_min, f0_max)
+            if errs is not None:
+                f0s.append(errs)
+        elif mcd:
             mcds.append(batch_mcd(model, feed, out, mcd_coeffs, mcd_stop_at_silence))
         n_batches += 1
     if n_batches == 0:
@@ -170,11 +230,21 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
         per_utterance = np.concatenate(mcds).astype(np.float64)
         result['mcd'] = float(np.mean(per_utterance))
         result['mcd_utterances'] = int(per_utterance.shape[0])
+    if f0:
+        for key in F0_KEYS:
+            values = np.concatenate([e[key] for e in f0s]) if f0s else np.zeros(0)
+            values = values[np.isfinite(values)]
+            result['metric/' + key] = float(np.mean(values)) if values.size else float('nan')
+            if key == 'f0_rmse_cents':
+                result['f0_utterances'] = int(values.size)
     if verbose:
         print('[evaluate] step: {}, batches: {}, loss: {:.6f}, loss_decoder: {:.6f}, loss_post_processing: {:.6f}'.format(
             global_step, n_batches, result['loss'], result['loss_decoder'], result['loss_post_processing']))
         if mcd:
             print('[evaluate] step: {}, utterances: {}, mcd: {:.6f} dB'.format(global_step, result['mcd_utterances'], result['mcd']))
+        if f0:
+            print('[evaluate] step: {}, utterances: {}, f0_rmse: {:.3f} cents / {:.3f} Hz, vuv_error: {:.4f}, gross_pitch_error: {:.4f}'.format(
+                global_step, result['f0_utterances'], *(result['metric/' + key] for key in F0_KEYS)))
     checkpoint_dir = evaluation_params.checkpoint_dir if checkpoint_dir is None else checkpoint_dir
     if checkpoint_dir:
         save_dir = os.path.join(checkpoint_dir, checkpoint_save_run or evaluation_params.checkpoint_save_run)
@@ -184,6 +254,10 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
                 'loss/loss_post_processing': result['loss_post_processing']}
         if mcd:
             line['metric/mcd'] = result['mcd']
+        if f0:
+            for key in F0_KEYS:
+                line['metric/' + key] = result['metric/' + key]
+            line['f0_utterances'] = result['f0_utterances']
         with open(os.path.join(save_dir, SUMMARY_FILE), 'a') as f:
             f.write(json.dumps(line) + '\n')
     return result
@@ -202,7 +276,7 @@ def collect_checkpoint_paths(checkpoint_dir):
 
 def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, batch_size=None, checkpoint_dir=None,
                         checkpoint_save_run=None, hparams=None, device_id=0, verbose=True, mcd=False, mcd_coeffs=13,
-                        mcd_stop_at_silence=None):
+                        mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0):
     """One cycle of the reference's ``__eval_cycle`` (:336-352): a dataset loader, the batches, a model with its own
     engine, :func:`evaluate`; the engine is released afterwards."""
     from ..datasets.lj_speech import LJSpeechDatasetHelper
@@ -215,7 +289,7 @@ def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, 
     try:
         return evaluate(model, checkpoint_file, batches, checkpoint_dir=checkpoint_dir,
                         checkpoint_save_run=checkpoint_save_run, verbose=verbose, mcd=mcd, mcd_coeffs=mcd_coeffs,
-                        mcd_stop_at_silence=mcd_stop_at_silence)
+                        mcd_stop_at_silence=mcd_stop_at_silence, f0=f0, f0_iters=f0_iters, f0_min=f0_min, f0_max=f0_max)
     finally:
         model.engine.close()
 
@@ -226,11 +300,12 @@ def main(argv=None):
         python -m single-speaker-tts_amd.tacotron.evaluate [--all] [--checkpoint-dir D] [--load-run R] [--save-run S]
                                                            [--dataset-folder F] [--max-samples N] [--batch-size B]
                                                            [--mcd [--mcd-coeffs K] [--mcd-stop-at-silence DB]]
+                                                           [--f0 [--f0-iters N] [--f0-min HZ] [--f0-max HZ]]
 
     The options override the ``evaluation_params`` / ``dataset_params`` fields of the same name.  Without ``--all``
     (``evaluate_all_checkpoints``) the latest checkpoint of ``<checkpoint_dir>/<load_run>`` is evaluated, with it every
-    checkpoint its listing file names.  ``--mcd`` adds the mel-cepstral distortion (module docstring).  Prints one JSON line
-    per checkpoint."""
+    checkpoint its listing file names.  ``--mcd`` adds the mel-cepstral distortion, ``--f0`` the F0 RMSE, voicing error
+    and gross pitch error along the same alignment (module docstring).  Prints one JSON line per checkpoint."""
     import argparse
     from .checkpoint import latest_checkpoint
     ap = argparse.ArgumentParser(prog='tacotron.evaluate')
@@ -246,7 +321,19 @@ def main(argv=None):
     ap.add_argument('--mcd-coeffs', type=int, default=13, help='cepstral coefficients 1 .. K are compared (default 13)')
     ap.add_argument('--mcd-stop-at-silence', type=float, default=None, metavar='DB',
                     help='end every prediction behind its last linear frame above DB decibels')
+    ap.add_argument('--f0', action='store_true', help='also report F0 RMSE, voicing error and gross pitch error along the DTW path')
+    ap.add_argument('--f0-iters', type=int, default=None, metavar='N',
+                    help="Griffin-Lim iterations of --f0 (default: the model's reconstruction_iterations)")
+    ap.add_argument('--f0-min', type=float, default=None, metavar='HZ', help='lowest F0 searched (default 60)')
+    ap.add_argument('--f0-max', type=float, default=None, metavar='HZ', help='highest F0 searched (default 500)')
     args = ap.parse_args(argv)
+    if not args.f0 and (args.f0_iters is not None or args.f0_min is not None or args.f0_max is not None):
+        ap.error('--f0-iters, --f0-min and --f0-max need --f0')
+    if args.f0_iters is not None and args.f0_iters < 0:
+        ap.error('--f0-iters must be >= 0')
+    f0_min, f0_max = 60.0 if args.f0_min is None else args.f0_min, 500.0 if args.f0_max is None else args.f0_max
+    if args.f0 and not 0 < f0_min <= f0_max:
+        ap.error('need 0 < --f0-min <= --f0-max')
     if not args.mcd and (args.mcd_coeffs != 13 or args.mcd_stop_at_silence is not None):
         ap.error('--mcd-coeffs and --mcd-stop-at-silence need --mcd')
     load_dir = os.path.join(args.checkpoint_dir, args.load_run)
@@ -262,7 +349,8 @@ def main(argv=None):
         res = evaluate_checkpoint(checkpoint_file, dataset_folder=args.dataset_folder, max_samples=args.max_samples,
                                   batch_size=args.batch_size, checkpoint_dir=args.checkpoint_dir,
                                   checkpoint_save_run=args.save_run, device_id=args.device, mcd=args.mcd,
-                                  mcd_coeffs=args.mcd_coeffs, mcd_stop_at_silence=args.mcd_stop_at_silence)
+                                  mcd_coeffs=args.mcd_coeffs, mcd_stop_at_silence=args.mcd_stop_at_silence, f0=args.f0,
+                                  f0_iters=args.f0_iters, f0_min=f0_min, f0_max=f0_max)
         print(json.dumps(dict(res, checkpoint=checkpoint_file)))
     return 0
 

@@ -231,6 +231,34 @@ def _is_device(x):
     return hasattr(x, 'data_ptr') and not isinstance(x, np.ndarray)
 
 
+def _int32_ptr(a):
+    """a host int32 array as the ``const int32_t*`` of a call; None: NULL"""
+    return a.ctypes.data_as(POINTER(c_int32)) if a is not None else None
+
+
+def _checked_lengths(lengths, hi, name, bound):
+    """Host lengths -- an integer array of the batch's shape already -- as a contiguous int32 array, every one in 1 .. ``hi``;
+    the ValueError speaks of the caller's argument ``name`` and of its ``bound``."""
+    for b, n in enumerate(lengths.tolist()):
+        if not 1 <= n <= hi:
+            raise ValueError('{}[{}] = {} is not in 1 .. {} = {}'.format(name, b, n, bound, hi))
+    return np.ascontiguousarray(lengths, dtype=np.int32)
+
+
+def _waveforms(what, wavs, uniform=False):
+    """``wavs`` -- one waveform (n,) or a batch (B, n), host or device -- as ``(wavs, single, B, n)``: a 1-D host array becomes
+    one row, a 1-D device buffer is one row as it lies.  ``uniform``: the compositions' rule -- two dimensions from here on (no
+    1-D device buffer), and whether the signal is long enough is theirs to say."""
+    single = len(wavs.shape) == 1
+    if single and not _is_device(wavs):
+        wavs = np.asarray(wavs).reshape(1, -1)
+    if (len(wavs.shape) != 2) if uniform else (len(wavs.shape) not in (1, 2) or min(wavs.shape) < 1):
+        raise ValueError('{}: one waveform (n,) or a {}batch (B, n) is needed, got shape {}'.format(
+            what, 'uniform ' if uniform else '', tuple(wavs.shape)))
+    B, n = (1, int(wavs.shape[0])) if len(wavs.shape) == 1 else (int(d) for d in wavs.shape)
+    return wavs, single, B, n
+
+
 def ragged_frame_counts(n_frames, B, T_max, hop_length, n_fft):
     """The ``n_frames`` argument of a ragged Griffin-Lim call as a contiguous int32 array of B lengths, checked as
     tts_griffin_lim_ragged checks them (ValueError, raised before a handle is touched): 1 <= n_frames[b] <= T_max and a
@@ -396,10 +424,7 @@ def stretch_frame_counts(n_frames, B, T):
         raise ValueError('n_frames: shape {} for a batch of {}'.format(nf.shape, B))
     if nf.dtype.kind not in 'iu':
         raise ValueError('n_frames must be integers, got {}'.format(nf.dtype))
-    for b, n in enumerate(nf.tolist()):
-        if not 1 <= n <= T:
-            raise ValueError('n_frames[{}] = {} is not in 1 .. T = {}'.format(b, n, T))
-    return np.ascontiguousarray(nf, dtype=np.int32)
+    return _checked_lengths(nf, T, 'n_frames', 'T')
 
 
 RESAMPLE_RATIO_MIN, RESAMPLE_RATIO_MAX = 0.25, 4.0
@@ -507,6 +532,18 @@ def _padded_rows(spec, B, T, F, stride):
     return padded
 
 
+def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
+    """Time-major rows ``spec`` (B, T, F) whose rows lie ``row_stride`` floats apart (None: F) as ``(what is uploaded, the
+    stride)``: a device buffer as it is, a host array through :func:`_padded_rows`.  A stride below F is a ValueError in the name
+    of ``what`` -- or, with ``what`` None, the library's to refuse."""
+    stride = F if row_stride is None else int(row_stride)
+    if what is not None and stride < F:
+        raise ValueError('{}: row_stride {} < {} = {}'.format(what, stride, width, F))
+    if not _is_device(spec) and stride > F:
+        spec = _padded_rows(spec, B, T, F, stride)
+    return spec, stride
+
+
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
@@ -572,6 +609,16 @@ class Engine(object):
             if rc == TTS_ERR_DB_RANGE:
                 raise AssertionError(msg)   # reference audio/conversion.py:47-49
             raise TtsError(rc, msg)
+
+    def _check_or_free(self, rc, *outputs):
+        """``_check`` for a call that enqueues nothing where it refuses: its fresh ``outputs`` (None among them) go back at once"""
+        try:
+            self._check(rc)
+        except Exception:
+            for a in outputs:
+                if a is not None:
+                    a.free()
+            raise
 
     def close(self):
         if getattr(self, 'handle', None):
@@ -738,35 +785,12 @@ class Engine(object):
         device buffers.  The decoder free-runs for n_steps = T_red.  Returns a dict with the device arrays ``losses``
         (3,) = [loss, loss_decoder, loss_post_processing] and, where asked for, ``l1_sums`` (B, 2) float64, ``mel``
         (B, T, n_mels), ``alignments`` (T_red, B, T_sent), ``linear`` (B, T, F)."""
-        B, Ts = ids.shape
-        r, nm, F = self.cfg.reduction, self.cfg.n_mels, 1 + self.cfg.n_fft // 2
-        mel_sz, lin_sz = int(np.prod(mel_target.shape)), int(np.prod(linear_target.shape))
-        if mel_target.shape[0] != B or mel_sz % (B * r * nm):
-            raise ValueError('evaluate: mel target of shape {} for B = {}, r * n_mels = {}'.format(mel_target.shape, B, r * nm))
-        n_steps = mel_sz // (B * r * nm)
-        T = n_steps * r
-        if linear_target.shape[0] != B or lin_sz != B * T * F:
-            raise ValueError('evaluate: linear target of shape {}, ({}, {}, {}) floats needed'.format(
-                linear_target.shape, B, T, F))
-        self._check_ids(ids)
-        p_ids, _k1 = self._in(ids, np.int32, 'ids')
-        p_mel, _k2 = self._in(mel_target, np.float32, 'eval_mel_target')
-        p_lin, _k3 = self._in(linear_target, np.float32, 'eval_linear_target')
-        out = dict(losses=losses if losses is not None else self.empty((3,)))
-        out['l1_sums'] = self.empty((B, 2), np.float64) if want_sums else None
-        out['mel'] = self.empty((B, T, nm)) if want_mel else None
-        out['alignments'] = self.empty((n_steps, B, Ts)) if want_alignments else None
-        out['linear'] = self.empty((B, T, F)) if want_linear else None
-        ptr = lambda a: a.data_ptr() if a is not None else None
-        self._check(self.lib.tts_evaluate(self.handle, p_ids, B, Ts, n_steps, p_mel, p_lin, out['losses'].data_ptr(),
-                                          ptr(out['l1_sums']), ptr(out['mel']), ptr(out['alignments']), ptr(out['linear'])))
-        out['n_steps'] = n_steps
-        return out
+        return self._with_targets(False, ids, mel_target, linear_target, want_sums, want_mel, want_alignments, want_linear, losses)
 
-    def _teacher_steps(self, mel_target, B, what):
+    def _teacher_steps(self, mel_target, B, what, empty_ok=False):
         r, nm = self.cfg.reduction, self.cfg.n_mels
         mel_sz = int(np.prod(mel_target.shape))
-        if mel_target.shape[0] != B or mel_sz == 0 or mel_sz % (B * r * nm):
+        if mel_target.shape[0] != B or (mel_sz == 0 and not empty_ok) or mel_sz % (B * r * nm):
             raise ValueError('{}: mel target of shape {} for B = {}, r * n_mels = {}'.format(what, mel_target.shape, B, r * nm))
         return mel_sz // (B * r * nm)
 
@@ -796,27 +820,33 @@ class Engine(object):
         gradient (not Mode.TRAIN).  Returns a dict of device arrays: ``mel`` (B, T, n_mels), ``alignments``
         (T_red, B, T_sent), ``linear`` (B, T, F) where asked for, ``losses`` (3,) and ``l1_sums`` (B, 2) float64 (with
         ``want_sums``) when a linear target is given, else None; and ``n_steps``."""
+        return self._with_targets(True, ids, mel_target, linear_target, want_sums, want_mel, want_alignments, want_linear, losses)
+
+    def _with_targets(self, teacher, ids, mel_target, linear_target, want_sums, want_mel, want_alignments, want_linear, losses):
+        """:meth:`evaluate` (the decoder free-runs, both targets are required and losses always come back) and
+        :meth:`teacher_forced` (the decoder reads ``mel_target``; losses with a ``linear_target`` alone)"""
+        what = 'teacher_forced' if teacher else 'evaluate'
         B, Ts = ids.shape
         r, nm, F = self.cfg.reduction, self.cfg.n_mels, 1 + self.cfg.n_fft // 2
-        n_steps = self._teacher_steps(mel_target, B, 'teacher_forced')
+        n_steps = self._teacher_steps(mel_target, B, what, empty_ok=not teacher)
         T = n_steps * r
-        if linear_target is not None and (linear_target.shape[0] != B or int(np.prod(linear_target.shape)) != B * T * F):
-            raise ValueError('teacher_forced: linear target of shape {}, ({}, {}, {}) floats needed'.format(
-                linear_target.shape, B, T, F))
+        with_losses = linear_target is not None or not teacher
+        if with_losses and (linear_target.shape[0] != B or int(np.prod(linear_target.shape)) != B * T * F):
+            raise ValueError('{}: linear target of shape {}, ({}, {}, {}) floats needed'.format(what, linear_target.shape, B, T, F))
         self._check_ids(ids)
+        role = 'teacher' if teacher else 'eval'
         p_ids, _k1 = self._in(ids, np.int32, 'ids')
-        p_mel, _k2 = self._in(mel_target, np.float32, 'teacher_mel_target')
-        p_lin, _k3 = self._in(linear_target, np.float32, 'teacher_linear_target')
-        with_losses = linear_target is not None
+        p_mel, _k2 = self._in(mel_target, np.float32, role + '_mel_target')
+        p_lin, _k3 = self._in(linear_target, np.float32, role + '_linear_target')
         out = dict(losses=(losses if losses is not None else self.empty((3,))) if with_losses else None)
         out['l1_sums'] = self.empty((B, 2), np.float64) if want_sums and with_losses else None
         out['mel'] = self.empty((B, T, nm)) if want_mel else None
         out['alignments'] = self.empty((n_steps, B, Ts)) if want_alignments else None
         out['linear'] = self.empty((B, T, F)) if want_linear else None
         ptr = lambda a: a.data_ptr() if a is not None else None
-        self._check(self.lib.tts_teacher_forced(self.handle, p_ids, B, Ts, n_steps, p_mel, p_lin, ptr(out['losses']),
-                                                ptr(out['l1_sums']), ptr(out['mel']), ptr(out['alignments']),
-                                                ptr(out['linear'])))
+        call = self.lib.tts_teacher_forced if teacher else self.lib.tts_evaluate
+        self._check(call(self.handle, p_ids, B, Ts, n_steps, p_mel, p_lin, ptr(out['losses']), ptr(out['l1_sums']), ptr(out['mel']),
+                         ptr(out['alignments']), ptr(out['linear'])))
         out['n_steps'] = n_steps
         return out
 
@@ -854,7 +884,7 @@ class Engine(object):
         mse = self.empty((B,)) if want_mse else None
         if nf is not None:
             with scope, start:
-                self._check(self.lib.tts_griffin_lim_ragged(self.handle, p_mag, p_init, seed, B, T, nf.ctypes.data_as(POINTER(c_int32)),
+                self._check(self.lib.tts_griffin_lim_ragged(self.handle, p_mag, p_init, seed, B, T, _int32_ptr(nf),
                                                             n_iter, win_length, hop_length, n_fft, wav.data_ptr(),
                                                             mse.data_ptr() if mse is not None else None))
             return wav, mse
@@ -877,32 +907,18 @@ class Engine(object):
         B, T, F, nf = phase_estimate_args(mag.shape, n_fft, hop_length, n_frames)
         p_mag, _k = self._in(mag, np.float32)
         out = self.empty((B, F, T))
-        try:
-            self._check(self.lib.tts_phase_estimate(self.handle, p_mag, B, T, nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None,
-                                                    int(n_fft), int(hop_length), out.data_ptr()))
-        except Exception:   # (a refusal: nothing was enqueued)
-            out.free()
-            raise
+        self._check_or_free(self.lib.tts_phase_estimate(self.handle, p_mag, B, T, _int32_ptr(nf), int(n_fft), int(hop_length), out.data_ptr()), out)
         return out
 
     def phase_estimate_rows(self, spec, n_fft, hop_length, n_frames=None, row_stride=None):
         """tts_phase_estimate_rows: the same estimate from time-major rows, ``spec`` (B, T, F) as ``speech_frames`` takes it
         (``row_stride`` as there).  Returns the same device array (B, F, T) as :meth:`phase_estimate`."""
         B, T, F, nf = phase_estimate_args(spec.shape, n_fft, hop_length, n_frames, time_major=True)
-        stride = F if row_stride is None else int(row_stride)
-        if stride < F:
-            raise ValueError('phase_estimate_rows: row_stride {} < F = {}'.format(stride, F))
-        if not _is_device(spec) and stride > F:
-            spec = _padded_rows(spec, B, T, F, stride)
+        spec, stride = _strided_rows('phase_estimate_rows', spec, B, T, F, row_stride)
         p_spec, _k = self._in(spec, np.float32)
         out = self.empty((B, F, T))
-        try:
-            self._check(self.lib.tts_phase_estimate_rows(self.handle, p_spec, B, T, stride,
-                                                         nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None,
-                                                         int(n_fft), int(hop_length), out.data_ptr()))
-        except Exception:
-            out.free()
-            raise
+        self._check_or_free(self.lib.tts_phase_estimate_rows(self.handle, p_spec, B, T, stride, _int32_ptr(nf), int(n_fft), int(hop_length),
+                                                             out.data_ptr()), out)
         return out
 
     def peak_normalize(self, wav):
@@ -937,19 +953,12 @@ class Engine(object):
         if len(spec.shape) != 3:
             raise ValueError('speech_frames: spec must be (B, T, F), got shape {}'.format(tuple(spec.shape)))
         B, T, F = (int(d) for d in spec.shape)
-        stride = F if row_stride is None else int(row_stride)
-        if not _is_device(spec) and stride > F:
-            spec = _padded_rows(spec, B, T, F, stride)
+        spec, stride = _strided_rows(None, spec, B, T, F, row_stride)   # (a stride below F: the library refuses it)
         p_spec, _k = self._in(spec, np.float32)
         n_frames = self.empty((max(B, 1),), np.int32)
         last = self.empty((max(B, 1),), np.int32)
-        try:
-            self._check(self.lib.tts_speech_frames(self.handle, p_spec, B, T, F, stride, float(threshold), int(keep_frames),
-                                                   int(min_frames), n_frames.data_ptr(), last.data_ptr()))
-        except Exception:   # (a refusal: nothing was enqueued, the outputs go back at once)
-            n_frames.free()
-            last.free()
-            raise
+        self._check_or_free(self.lib.tts_speech_frames(self.handle, p_spec, B, T, F, stride, float(threshold), int(keep_frames), int(min_frames),
+                                                       n_frames.data_ptr(), last.data_ptr()), n_frames, last)
         return n_frames, last
 
     # ------------------------------------------------------------------ cepstra and alignment
@@ -963,21 +972,12 @@ class Engine(object):
         B, T, n_mels = (int(d) for d in rows.shape)
         if int(n_mfcc) != n_mfcc or not 1 <= n_mfcc <= n_mels or n_mels > 1024:
             raise ValueError('mfcc: need 1 <= n_mfcc <= n_mels <= 1024, got n_mfcc = {!r}, n_mels = {}'.format(n_mfcc, n_mels))
-        stride = n_mels if row_stride is None else int(row_stride)
-        if stride < n_mels:
-            raise ValueError('mfcc: row_stride {} < n_mels = {}'.format(stride, n_mels))
+        rows, stride = _strided_rows('mfcc', rows, B, T, n_mels, row_stride, 'n_mels')
         nf = stretch_frame_counts(n_frames, B, T)
-        if not _is_device(rows) and stride > n_mels:
-            rows = _padded_rows(rows, B, T, n_mels, stride)
         p_rows, _k = self._in(rows, np.float32)
         out = self.empty((B, T, int(n_mfcc)))
-        try:
-            self._check(self.lib.tts_mfcc(self.handle, p_rows, B, T, n_mels, stride,
-                                          nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None, int(n_mfcc),
-                                          1 if clip01 else 0, out.data_ptr()))
-        except Exception:   # (a refusal: nothing was enqueued)
-            out.free()
-            raise
+        self._check_or_free(self.lib.tts_mfcc(self.handle, p_rows, B, T, n_mels, stride, _int32_ptr(nf), int(n_mfcc), 1 if clip01 else 0,
+                                              out.data_ptr()), out)
         return out
 
     def dtw_max_frames(self):
@@ -1013,15 +1013,8 @@ class Engine(object):
         cost = self.empty((B,), np.float64)
         plen = self.empty((B,), np.int32)
         path = self.empty((B, Ta + Tb - 1, 2), np.int32) if want_path else None
-        ptr = lambda n: n.ctypes.data_as(POINTER(c_int32)) if n is not None else None
-        try:
-            self._check(self.lib.tts_dtw(self.handle, p_a + 4 * skip, Ta, Ka, ptr(na), p_b + 4 * skip, Tb, Kb, ptr(nb), B, int(D),
-                                         cost.data_ptr(), plen.data_ptr(), path.data_ptr() if want_path else None))
-        except Exception:   # (a refusal: nothing was enqueued)
-            for x in (cost, plen, path):
-                if x is not None:
-                    x.free()
-            raise
+        self._check_or_free(self.lib.tts_dtw(self.handle, p_a + 4 * skip, Ta, Ka, _int32_ptr(na), p_b + 4 * skip, Tb, Kb, _int32_ptr(nb), B, int(D),
+                                             cost.data_ptr(), plen.data_ptr(), path.data_ptr() if want_path else None), cost, plen, path)
         return (cost, plen, path) if want_path else (cost, plen)
 
     # ------------------------------------------------------------------ F0 tracking
@@ -1035,12 +1028,7 @@ class Engine(object):
         array (B, T) of Hz, 0 in unvoiced and padding frames and NaN where a frame's span holds a non-finite sample -- (T,) for
         a 1-D input -- and with ``want_aperiodicity`` also the normalised difference at the chosen lag, of the same shape.
         include/sstts_hip.h has the definition: the results are the bits of tests/f0_oracle.py."""
-        single = len(wavs.shape) == 1
-        if single and not _is_device(wavs):
-            wavs = np.asarray(wavs).reshape(1, -1)
-        if len(wavs.shape) not in (1, 2) or min(wavs.shape) < 1:
-            raise ValueError('f0: one waveform (n,) or a batch (B, n) is needed, got shape {}'.format(tuple(wavs.shape)))
-        B, n = (1, int(wavs.shape[0])) if len(wavs.shape) == 1 else (int(d) for d in wavs.shape)
+        wavs, single, B, n = _waveforms('f0', wavs)
         lo, hi = f0_lag_bounds(sampling_rate, fmin, fmax)
         lo = lo if tau_min is None else tau_min
         hi = hi if tau_max is None else tau_max
@@ -1058,15 +1046,8 @@ class Engine(object):
         T = f0_frames(n, hop_length)
         out = self.empty((T,) if single else (B, T))
         ap = self.empty((T,) if single else (B, T)) if want_aperiodicity else None
-        try:
-            self._check(self.lib.tts_f0(self.handle, p_wav, B, n, ns.ctypes.data_as(POINTER(c_int32)) if ns is not None else None,
-                                        float(sampling_rate), int(hop_length), int(window), int(lo), int(hi), float(threshold),
-                                        out.data_ptr(), ap.data_ptr() if ap is not None else None))
-        except Exception:   # (a refusal: nothing was enqueued)
-            out.free()
-            if ap is not None:
-                ap.free()
-            raise
+        self._check_or_free(self.lib.tts_f0(self.handle, p_wav, B, n, _int32_ptr(ns), float(sampling_rate), int(hop_length), int(window), int(lo),
+                                            int(hi), float(threshold), out.data_ptr(), ap.data_ptr() if ap is not None else None), out, ap)
         return (out, ap) if want_aperiodicity else out
 
     def f0_compare(self, f0_a, f0_b, path):
@@ -1089,12 +1070,7 @@ class Engine(object):
         p_p, _kp = self._in(path, np.int32)
         counts = self.empty((B, 5), np.int32)
         sums = self.empty((B, 2), np.float64)
-        try:
-            self._check(self.lib.tts_f0_compare(self.handle, p_a, Ta, p_b, Tb, p_p, rows, B, counts.data_ptr(), sums.data_ptr()))
-        except Exception:   # (a refusal: nothing was enqueued)
-            counts.free()
-            sums.free()
-            raise
+        self._check_or_free(self.lib.tts_f0_compare(self.handle, p_a, Ta, p_b, Tb, p_p, rows, B, counts.data_ptr(), sums.data_ptr()), counts, sums)
         return counts, sums
 
     # ------------------------------------------------------------------ speaking rate
@@ -1135,13 +1111,7 @@ class Engine(object):
         B, F, T = (int(d) for d in mag.shape)
         p_mag, _k = self._in(mag, np.float32)
         out = self.empty((B, F, T_out))
-        try:
-            self._check(self.lib.tts_stretch_magnitudes(self.handle, p_mag, B, F, T,
-                                                        nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None, r, T_out,
-                                                        out.data_ptr()))
-        except Exception:   # (a refusal: nothing was enqueued)
-            out.free()
-            raise
+        self._check_or_free(self.lib.tts_stretch_magnitudes(self.handle, p_mag, B, F, T, _int32_ptr(nf), r, T_out, out.data_ptr()), out)
         return out
 
     def stretch_rows(self, spec, rate, n_frames=None, T_out=None, row_stride=None):
@@ -1152,20 +1122,10 @@ class Engine(object):
         r, nf, T_out = self._stretch_args('stretch_rows', spec.shape, int(spec.shape[1]) if len(spec.shape) == 3 else 0,
                                           rate, n_frames, T_out)
         B, T, F = (int(d) for d in spec.shape)
-        stride = F if row_stride is None else int(row_stride)
-        if stride < F:
-            raise ValueError('stretch_rows: row_stride {} < F = {}'.format(stride, F))
-        if not _is_device(spec) and stride > F:
-            spec = _padded_rows(spec, B, T, F, stride)
+        spec, stride = _strided_rows('stretch_rows', spec, B, T, F, row_stride)
         p_spec, _k = self._in(spec, np.float32)
         out = self.empty((B, T_out, stride))
-        try:
-            self._check(self.lib.tts_stretch_rows(self.handle, p_spec, B, T, F, stride,
-                                                  nf.ctypes.data_as(POINTER(c_int32)) if nf is not None else None, r, T_out,
-                                                  out.data_ptr()))
-        except Exception:
-            out.free()
-            raise
+        self._check_or_free(self.lib.tts_stretch_rows(self.handle, p_spec, B, T, F, stride, _int32_ptr(nf), r, T_out, out.data_ptr()), out)
         return out
 
     def time_stretch(self, wavs, rate, n_iter=25, seed=0, want_magnitudes=False):
@@ -1178,15 +1138,11 @@ class Engine(object):
         r = speaking_rate_value(rate)
         if r is None:
             raise ValueError('time_stretch: a rate in [0.25, 4] is needed')
-        single = len(wavs.shape) == 1
-        if single and not _is_device(wavs):
-            wavs = np.asarray(wavs).reshape(1, -1)
-        if len(wavs.shape) != 2:
-            raise ValueError('time_stretch: one waveform (n,) or a uniform batch (B, n) is needed, got shape {}'.format(tuple(wavs.shape)))
+        wavs, single, _B, n = _waveforms('time_stretch', wavs, uniform=True)
         n_fft, win, hop = 1024, 1024, 256
-        T = 1 + int(wavs.shape[1]) // hop
+        T = 1 + n // hop
         if hop * (stretched_frames(T, r) - 1) <= n_fft // 2:
-            raise ValueError('time_stretch: {} samples at rate {} leave a signal shorter than n_fft / 2'.format(int(wavs.shape[1]), r))
+            raise ValueError('time_stretch: {} samples at rate {} leave a signal shorter than n_fft / 2'.format(n, r))
         mag = self.stft_magnitude(wavs, n_fft, win, hop, 1.0)
         st = self.stretch_magnitudes(mag, r)
         wav, _mse = self.griffin_lim(st, int(n_iter), win, hop, n_fft, seed=seed, want_mse=False)
@@ -1212,22 +1168,13 @@ class Engine(object):
         array (B, N_out) -- (N_out,) for one waveform given as a 1-D array, host or device: utterance b holds min(int(n_samples[b] * ratio),
         N_out) resampled samples and zeros behind them; ``N_out`` None: ceil(longest * ratio), librosa's length."""
         r = resample_ratio_value(ratio)
-        single = len(wavs.shape) == 1
-        if single and not _is_device(wavs):
-            wavs = np.asarray(wavs).reshape(1, -1)
-        if len(wavs.shape) not in (1, 2) or min(wavs.shape) < 1:
-            raise ValueError('resample: one waveform (n,) or a batch (B, n) is needed, got shape {}'.format(tuple(wavs.shape)))
-        # (a 1-D device buffer is one row as it lies)
-        B, n = (1, int(wavs.shape[0])) if len(wavs.shape) == 1 else (int(d) for d in wavs.shape)
+        wavs, single, B, n = _waveforms('resample', wavs)
         ns = None
         if n_samples is not None:
             ns = np.asarray(n_samples)
             if ns.shape != (B,) or ns.dtype.kind not in 'iu':
                 raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-            for b, m in enumerate(ns.tolist()):
-                if not 1 <= m <= n:
-                    raise ValueError('n_samples[{}] = {} is not in 1 .. n = {}'.format(b, m, n))
-            ns = np.ascontiguousarray(ns, dtype=np.int32)
+            ns = _checked_lengths(ns, n, 'n_samples', 'n')
         if N_out is None:
             N_out = resampled_length(int(ns.max()) if ns is not None else n, r)
         N_out = int(N_out)
@@ -1235,12 +1182,7 @@ class Engine(object):
             raise ValueError('resample: N_out = {} < 1'.format(N_out))
         p_wav, _k = self._in(wavs, np.float32)
         out = self.empty((B, N_out))
-        try:
-            self._check(self.lib.tts_resample(self.handle, p_wav, B, n, ns.ctypes.data_as(POINTER(c_int32)) if ns is not None else None,
-                                              r, N_out, out.data_ptr()))
-        except Exception:   # (a refusal: nothing was enqueued)
-            out.free()
-            raise
+        self._check_or_free(self.lib.tts_resample(self.handle, p_wav, B, n, _int32_ptr(ns), r, N_out, out.data_ptr()), out)
         if single:
             out.shape = (N_out,)
         return out
@@ -1335,7 +1277,7 @@ class Engine(object):
         """tts_synth_frames: the B frame counts (int32 host array) of the last ``synthesize`` / ``synthesize_host`` call made
         on the handle -- all T for a call made without end-of-speech stopping."""
         n_frames = np.zeros(int(B), dtype=np.int32)
-        self._check(self.lib.tts_synth_frames(self.handle, n_frames.ctypes.data_as(POINTER(c_int32)), int(B)))
+        self._check(self.lib.tts_synth_frames(self.handle, _int32_ptr(n_frames), int(B)))
         return n_frames
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,

@@ -1011,6 +1011,54 @@ int denorm_flag_read(tts_handle_t h) {
     return TTS_OK;
 }
 
+// What tts_evaluate and tts_teacher_forced share once their own arguments are checked: the stand-alone encoder, the decoder --
+// teacher: fed from mel_target, else free-running -- and the post-net, then with a linear_target the L1 losses against the targets
+// (eval_loss.hip); without one there are no losses, and no post-net either unless `linear` is asked for.  who: the entry point, for
+// the messages.  Spectrograms the caller does not ask for go to workspaces of the handle.
+static int evaluate_impl(tts_handle_t h, const std::string& who, bool teacher, const int32_t* ids, int B, int Ts, int n_steps,
+                         const float* mel_target, const float* linear_target, float* losses, double* l1_sums, float* mel, float* alignments,
+                         float* linear) {
+    const tts_config_t& c = h->cfg;
+    const int T = n_steps * c.reduction, F = 1 + c.n_fft / 2;
+    for (const void* p : {(const void*)mel_target, (const void*)linear_target, (const void*)mel, (const void*)linear, (const void*)losses})
+        if ((uintptr_t)p & 3) return fail(h, TTS_ERR_INVALID, who + ": float buffers must be 4-byte aligned");
+    if (linear_target && ((uintptr_t)l1_sums & 7)) return fail(h, TTS_ERR_INVALID, who + ": l1_sums must be 8-byte aligned");
+    const size_t n_mel = (size_t)B * T * c.n_mels, n_lin = (size_t)B * T * F;
+    WS(h, "eval.memory", float, (size_t)B * Ts * 2 * c.n_gru_units, memory);
+    float* mel_o = mel;
+    if (!mel_o) {
+        WS(h, "eval.mel", float, n_mel, mel_ws);
+        mel_o = mel_ws;
+    }
+    float* lin_o = linear;
+    if (!lin_o && linear_target) {
+        WS(h, "eval.linear", float, n_lin, lin_ws);
+        lin_o = lin_ws;
+    }
+    double* partial = nullptr;
+    double* sums = l1_sums;
+    if (linear_target) {
+        WS(h, "eval.partial", double, eval_loss_partial_count(B, T, c.n_mels, F), partial_ws);
+        partial = partial_ws;
+        if (!sums) {
+            WS(h, "eval.sums", double, (size_t)2 * B, sums_ws);
+            sums = sums_ws;
+        }
+    }
+    int rc = standalone_begin(h);
+    if (rc) return rc;
+    if ((rc = encoder_impl(h, ids, B, Ts, memory))) return rc;
+    if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel_o, alignments, teacher ? mel_target : nullptr))) return rc;
+    if (lin_o && (rc = postnet_impl(h, mel_o, B, T, lin_o, nullptr, 0.f, 0.f, 1.f))) return rc;
+    if (linear_target) {
+        ProfScope ps(h, ST_EVAL_LOSS, 2);
+        const int blocks = 8 * std::max(1, h->n_cus_dev);   // memory-bound: 8 workgroups of 256 threads per compute unit
+        HIPCHK(h, launch_eval_loss(h->stream, mel_target, mel_o, linear_target, lin_o, B, T, c.n_mels, F, blocks, partial, sums,
+                                   losses));
+    }
+    return standalone_end(h);
+}
+
 }  // namespace tts_api
 
 // ======================================================================================== C ABI
@@ -1077,39 +1125,7 @@ int tts_evaluate(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_steps,
     const int T = n_steps * c.reduction, F = 1 + c.n_fft / 2;
     if ((long long)n_steps * c.reduction > (1 << 24) || (double)B * T * F >= 9.0e18)
         return fail(h, TTS_ERR_INVALID, "evaluate: sizes out of range");
-    for (const void* p : {(const void*)mel_target, (const void*)linear_target, (const void*)mel, (const void*)linear,
-                          (const void*)losses})
-        if ((uintptr_t)p & 3) return fail(h, TTS_ERR_INVALID, "evaluate: float buffers must be 4-byte aligned");
-    if ((uintptr_t)l1_sums & 7) return fail(h, TTS_ERR_INVALID, "evaluate: l1_sums must be 8-byte aligned");
-    const size_t n_mel = (size_t)B * T * c.n_mels, n_lin = (size_t)B * T * F;
-    WS(h, "eval.memory", float, (size_t)B * Ts * 2 * c.n_gru_units, memory);
-    float* mel_o = mel;
-    if (!mel_o) {
-        WS(h, "eval.mel", float, n_mel, mel_ws);
-        mel_o = mel_ws;
-    }
-    float* lin_o = linear;
-    if (!lin_o) {
-        WS(h, "eval.linear", float, n_lin, lin_ws);
-        lin_o = lin_ws;
-    }
-    WS(h, "eval.partial", double, eval_loss_partial_count(B, T, c.n_mels, F), partial);
-    double* sums = l1_sums;
-    if (!sums) {
-        WS(h, "eval.sums", double, (size_t)2 * B, sums_ws);
-        sums = sums_ws;
-    }
-    if ((rc = standalone_begin(h))) return rc;
-    if ((rc = encoder_impl(h, ids, B, Ts, memory))) return rc;
-    if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel_o, alignments))) return rc;
-    if ((rc = postnet_impl(h, mel_o, B, T, lin_o, nullptr, 0.f, 0.f, 1.f))) return rc;
-    {
-        ProfScope ps(h, ST_EVAL_LOSS, 2);
-        const int blocks = 8 * std::max(1, h->n_cus_dev);   // memory-bound: 8 workgroups of 256 threads per compute unit
-        HIPCHK(h, launch_eval_loss(h->stream, mel_target, mel_o, linear_target, lin_o, B, T, c.n_mels, F, blocks, partial, sums,
-                                   losses));
-    }
-    return standalone_end(h);
+    return evaluate_impl(h, "evaluate", false, ids, B, Ts, n_steps, mel_target, linear_target, losses, l1_sums, mel, alignments, linear);
 }
 
 
@@ -1128,43 +1144,8 @@ int tts_teacher_forced(tts_handle_t h, const int32_t* ids, int B, int Ts, int n_
     if ((long long)n_steps * c.reduction > (1 << 24) || (double)B * T * F >= 9.0e18 ||
         (long long)n_steps * c.reduction * c.n_mels > 0x7FFFFFFFll)   // (the target's row stride: tts_decoder_forward_teacher)
         return fail(h, TTS_ERR_INVALID, "teacher_forced: sizes out of range");
-    for (const void* p : {(const void*)linear_target, (const void*)mel, (const void*)linear, (const void*)losses})
-        if ((uintptr_t)p & 3) return fail(h, TTS_ERR_INVALID, "teacher_forced: float buffers must be 4-byte aligned");
     if ((uintptr_t)mel_target & 15) return fail(h, TTS_ERR_INVALID, "teacher_forced: mel_target must be 16-byte aligned");
-    if (linear_target && ((uintptr_t)l1_sums & 7)) return fail(h, TTS_ERR_INVALID, "teacher_forced: l1_sums must be 8-byte aligned");
-    const size_t n_mel = (size_t)B * T * c.n_mels, n_lin = (size_t)B * T * F;
-    WS(h, "eval.memory", float, (size_t)B * Ts * 2 * c.n_gru_units, memory);
-    float* mel_o = mel;
-    if (!mel_o) {
-        WS(h, "eval.mel", float, n_mel, mel_ws);
-        mel_o = mel_ws;
-    }
-    float* lin_o = linear;
-    if (!lin_o && linear_target) {
-        WS(h, "eval.linear", float, n_lin, lin_ws);
-        lin_o = lin_ws;
-    }
-    double* partial = nullptr;
-    double* sums = l1_sums;
-    if (linear_target) {
-        WS(h, "eval.partial", double, eval_loss_partial_count(B, T, c.n_mels, F), partial_ws);
-        partial = partial_ws;
-        if (!sums) {
-            WS(h, "eval.sums", double, (size_t)2 * B, sums_ws);
-            sums = sums_ws;
-        }
-    }
-    if ((rc = standalone_begin(h))) return rc;
-    if ((rc = encoder_impl(h, ids, B, Ts, memory))) return rc;
-    if ((rc = decoder_impl(h, memory, B, Ts, n_steps, mel_o, alignments, mel_target))) return rc;
-    if (lin_o && (rc = postnet_impl(h, mel_o, B, T, lin_o, nullptr, 0.f, 0.f, 1.f))) return rc;
-    if (linear_target) {
-        ProfScope ps(h, ST_EVAL_LOSS, 2);
-        const int blocks = 8 * std::max(1, h->n_cus_dev);   // (as tts_evaluate)
-        HIPCHK(h, launch_eval_loss(h->stream, mel_target, mel_o, linear_target, lin_o, B, T, c.n_mels, F, blocks, partial, sums,
-                                   losses));
-    }
-    return standalone_end(h);
+    return evaluate_impl(h, "teacher_forced", true, ids, B, Ts, n_steps, mel_target, linear_target, losses, l1_sums, mel, alignments, linear);
 }
 
 

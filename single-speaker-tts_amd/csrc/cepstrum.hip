@@ -98,13 +98,11 @@ int tts_mfcc(tts_handle_t h, const float* spec, int B, int T, int n_mels, int ro
     const double* tab = nullptr;
     int rc = mfcc_table_dev(h, n_mels, n_mfcc, &tab);
     if (rc) return rc;
-    const int n_launches = (B + MFCC_UTTS - 1) / MFCC_UTTS;
-    ProfScope ps(h, ST_MFCC, n_launches);
+    ProfScope ps(h, ST_MFCC, length_chunks(B, MFCC_UTTS));
     for (int b0 = 0; b0 < B; b0 += MFCC_UTTS) {
         const int nb = std::min(MFCC_UTTS, B - b0);
         MfccLens lens;
-        std::memset(&lens, 0, sizeof(lens));
-        for (int b = 0; b < nb; ++b) lens.n[b] = n_frames ? n_frames[b0 + b] : T;
+        fill_lengths(lens.n, n_frames, b0, nb, T);
         const long long want = ((long long)nb * T + MFCC_ROWS - 1) / MFCC_ROWS;
         const unsigned grid = (unsigned)std::min<long long>(want, 1 << 16);   // (the rows beyond take another round)
         hipLaunchKernelGGL(mfcc_kernel, dim3(grid), dim3(MFCC_THREADS), 0, h->stream, spec + (size_t)b0 * T * row_stride,

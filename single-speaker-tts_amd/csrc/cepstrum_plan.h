@@ -3,6 +3,7 @@
 //   calculate_mfccs             reference audio/features.py:89-113: librosa.feature.mfcc(S=mel_spec, n_mfcc=n), which with S given is
 //                               scipy.fftpack.dct(S, axis=0, type=2, norm='ortho')[:n_mfcc]
 #pragma once
+#include "lengths.h"
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -35,10 +36,7 @@ inline std::string mfcc_check(bool have_ptrs, int B, int T, int n_mels, int row_
     if (n_mels > MFCC_MAX_MELS) return "n_mels is larger than " + std::to_string(MFCC_MAX_MELS);
     if (n_mfcc > n_mels) return "n_mfcc > n_mels";
     if (row_stride < n_mels) return "row_stride < n_mels";
-    for (int b = 0; n_frames && b < B; ++b)
-        if (n_frames[b] < 1 || n_frames[b] > T)
-            return "n_frames[" + std::to_string(b) + "] = " + std::to_string(n_frames[b]) + " is not in 1 .. T = " + std::to_string(T);
-    return std::string();
+    return lengths_refusal("n_frames", n_frames, B, "T", T);
 }
 
 }  // namespace tts

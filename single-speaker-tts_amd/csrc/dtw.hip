@@ -163,17 +163,13 @@ static int dtw_impl(tts_handle_t h, const float* a, int Ta, int stride_a, const 
         WS(h, "dtw.dir", uint32_t, (size_t)B * dir_pair, d);
         dir = d;
     }
-    const int n_launches = (B + DTW_PAIRS - 1) / DTW_PAIRS;
-    ProfScope ps(h, ST_DTW, n_launches);
+    ProfScope ps(h, ST_DTW, length_chunks(B, DTW_PAIRS));
     const size_t pair_a = (size_t)Ta * stride_a, pair_b = (size_t)Tb * stride_b, path_rows = (size_t)Ta + Tb - 1;
     for (int p0 = 0; p0 < B; p0 += DTW_PAIRS) {
         const int np = std::min(DTW_PAIRS, B - p0);
         DtwLens lens;
-        std::memset(&lens, 0, sizeof(lens));
-        for (int p = 0; p < np; ++p) {
-            lens.na[p] = n_a ? n_a[p0 + p] : Ta;
-            lens.nb[p] = n_b ? n_b[p0 + p] : Tb;
-        }
+        fill_lengths(lens.na, n_a, p0, np, Ta);
+        fill_lengths(lens.nb, n_b, p0, np, Tb);
         const float* pa = a + (size_t)p0 * pair_a;
         const float* pb = b + (size_t)p0 * pair_b;
         int32_t* pp = path ? path + (size_t)p0 * path_rows * 2 : nullptr;

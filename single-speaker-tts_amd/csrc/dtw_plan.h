@@ -7,6 +7,7 @@
 // i / DTW_TILE: a lane keeps its rows for the whole call, so what it needs of the diagonals k - 1 and k - 2 is its own last
 // result (left), its upper neighbour's last result (up) and the `up` it read one diagonal earlier (diagonal).
 #pragma once
+#include "lengths.h"
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -49,8 +50,9 @@ inline std::string dtw_check(bool have_ptrs, int Ta, int stride_a, const int32_t
     int longest_a = 0, longest_b = 0;
     for (int p = 0; p < B; ++p) {
         const int na = n_a ? n_a[p] : Ta, nb = n_b ? n_b[p] : Tb;
-        if (na < 1 || na > Ta) return "n_a[" + std::to_string(p) + "] = " + std::to_string(na) + " is not in 1 .. Ta = " + std::to_string(Ta);
-        if (nb < 1 || nb > Tb) return "n_b[" + std::to_string(p) + "] = " + std::to_string(nb) + " is not in 1 .. Tb = " + std::to_string(Tb);
+        std::string why = length_refusal("n_a", p, na, "Ta", Ta);   // (pair by pair, a ahead of b)
+        if (why.empty()) why = length_refusal("n_b", p, nb, "Tb", Tb);
+        if (!why.empty()) return why;
         longest_a = na > longest_a ? na : longest_a;
         longest_b = nb > longest_b ? nb : longest_b;
     }

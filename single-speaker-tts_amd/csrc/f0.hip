@@ -225,13 +225,11 @@ static int f0_impl(tts_handle_t h, const float* wav, int B, int N, const int32_t
     const int frames = f0_group_frames(W, tau_max, hop);
     const size_t lds = f0_lds_bytes(W, tau_max, hop, frames);
     const int groups = f0_groups(T, frames);
-    const int n_launches = (B + F0_UTTS - 1) / F0_UTTS;
-    ProfScope ps(h, ST_F0, n_launches);
+    ProfScope ps(h, ST_F0, length_chunks(B, F0_UTTS));
     for (int b0 = 0; b0 < B; b0 += F0_UTTS) {
         const int nb = std::min(F0_UTTS, B - b0);
         F0Lens lens;
-        std::memset(&lens, 0, sizeof(lens));
-        for (int b = 0; b < nb; ++b) lens.n[b] = n_samples ? n_samples[b0 + b] : N;
+        fill_lengths(lens.n, n_samples, b0, nb, N);
         const float* pw = wav + (size_t)b0 * N;
         float* pf = f0 + (size_t)b0 * T;
         float* pa = ap ? ap + (size_t)b0 * T : nullptr;

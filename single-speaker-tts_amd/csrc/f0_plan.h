@@ -7,6 +7,7 @@
 // samples, as doubles -- in LDS once, beside two tables of `frames` rows of f0_row_stride(tau_max) doubles: the difference
 // function (then its normalised form) and the running sums of the normalisation.
 #pragma once
+#include "lengths.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -60,10 +61,8 @@ inline std::string f0_check(bool have_ptrs, int B, int N, const int32_t* n_sampl
     if (!have_ptrs) return "a NULL pointer (wav and f0 are required)";
     if (B < 1 || N < 1 || hop < 1) return "need B, N, hop >= 1";
     if (N / hop >= 2147483647) return "1 + N / hop frames do not fit an int";
-    if (n_samples)
-        for (int b = 0; b < B; ++b)
-            if (n_samples[b] < 1 || n_samples[b] > N)
-                return "n_samples[" + std::to_string(b) + "] = " + std::to_string(n_samples[b]) + " is not in 1 .. N = " + std::to_string(N);
+    const std::string bad = lengths_refusal("n_samples", n_samples, B, "N", N);
+    if (!bad.empty()) return bad;
     if (!(std::isfinite(sampling_rate) && sampling_rate > 0.0)) return "the sampling rate must be finite and positive";
     if (std::isnan(threshold)) return "the threshold is NaN";
     if (W < 1 || W > F0_MAX_WINDOW) {

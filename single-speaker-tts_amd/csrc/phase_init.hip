@@ -324,18 +324,13 @@ int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_
         WS(h, "pe.start", unsigned, (size_t)B * n_chunks * F, st);
         map_s = ms; map_o = mo; start = st;
     }
-    const int n_groups = (B + PE_UTTS - 1) / PE_UTTS;
-    ProfScope ps(h, ST_PHASE_INIT, (int64_t)n_groups * ((time_major ? 2 : 3) + (n_chunks > 1 ? 2 : 0)));
+    ProfScope ps(h, ST_PHASE_INIT, (int64_t)length_chunks(B, PE_UTTS) * ((time_major ? 2 : 3) + (n_chunks > 1 ? 2 : 0)));
     const dim3 tile_grid_in((T + 31) / 32, (F + 31) / 32), tile_grid_out((F + 31) / 32, (T + 31) / 32);
     for (int b0 = 0; b0 < B; b0 += PE_UTTS) {
         const int nb = std::min(PE_UTTS, B - b0);
         PeLens lens;
-        std::memset(&lens, 0, sizeof(lens));
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) {
-            lens.n[b] = n_frames ? n_frames[b0 + b] : T;
-            longest = std::max(longest, lens.n[b]);
-        }
+        fill_lengths(lens.n, n_frames, b0, nb, T);
+        const int longest = *std::max_element(lens.n, lens.n + nb);
         const float* rows = mag + (size_t)b0 * T * row_stride;
         int stride = row_stride;
         if (!time_major) {

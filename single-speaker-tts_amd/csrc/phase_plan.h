@@ -1,6 +1,7 @@
 // Estimated initial phases, host side: how the frames of an utterance are cut into chunks and the argument checks of the
 // estimate's entry points.  Plain C++ (no HIP, no handle): phase_init.hip includes it, and tests/phase_check.cpp compiles it alone.
 #pragma once
+#include "lengths.h"
 #include <cstdint>
 #include <string>
 
@@ -26,10 +27,7 @@ inline std::string phase_check(bool have_ptrs, int B, int T, int row_stride, con
     if (B < 1 || T < 1) return "need B, T >= 1";
     if (T > PE_MAX_FRAMES) return "T is larger than " + std::to_string(PE_MAX_FRAMES);
     if (row_stride < 1 + n_fft / 2) return "row_stride < 1 + n_fft / 2";
-    for (int b = 0; n_frames && b < B; ++b)
-        if (n_frames[b] < 1 || n_frames[b] > T)
-            return "n_frames[" + std::to_string(b) + "] = " + std::to_string(n_frames[b]) + " is not in 1 .. T = " + std::to_string(T);
-    return std::string();
+    return lengths_refusal("n_frames", n_frames, B, "T", T);
 }
 
 }  // namespace tts

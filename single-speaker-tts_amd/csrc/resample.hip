@@ -172,10 +172,9 @@ int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t*
     const double2* tab2 = reinterpret_cast<const double2*>(tab);
     for (int b0 = 0; b0 < B; b0 += RS_CHUNK) {
         const int nb = std::min(RS_CHUNK, B - b0);
-        ResampleLens lens;
-        std::memset(&lens, 0, sizeof(lens));
+        ResampleLens lens = {};
+        fill_lengths(lens.n_in, n_samples, b0, nb, n);
         for (int b = 0; b < nb; ++b) {
-            lens.n_in[b] = n_samples ? n_samples[b0 + b] : n;
             long long keep = std::min<long long>(resampled_valid(lens.n_in[b], rho), N_out);
             if (keep_cap) keep = std::min<long long>(keep, std::max(0, keep_cap[b0 + b]));
             lens.keep[b] = (int)keep;

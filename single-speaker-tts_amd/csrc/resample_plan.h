@@ -5,6 +5,7 @@
 //   pitch_shift (reference audio/effects.py:9-43) and load_wav(sampling_rate=...) run.
 // resampy ships the filter as a data file; it is regenerated here from the published design parameters.
 #pragma once
+#include "lengths.h"
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -145,10 +146,7 @@ inline std::string resample_check(bool have_ptrs, int B, int n, const int32_t* n
     if (!have_ptrs) return "a NULL pointer";
     if (!resample_ratio_ok(rho)) return "the ratio must be finite and lie in [0.25, 4]";
     if (B < 1 || n < 1 || N_out < 1) return "need B, n, N_out >= 1";
-    for (int b = 0; n_samples && b < B; ++b)
-        if (n_samples[b] < 1 || n_samples[b] > n)
-            return "n_samples[" + std::to_string(b) + "] = " + std::to_string(n_samples[b]) + " is not in 1 .. n = " + std::to_string(n);
-    return std::string();
+    return lengths_refusal("n_samples", n_samples, B, "n", n);
 }
 
 }  // namespace tts

@@ -113,19 +113,15 @@ namespace tts_api {
 // h->stream.  n_frames: HOST lengths or null (all T); they and everything else have been checked (stretch_check).
 int stretch_impl(tts_handle_t h, const float* in, int B, int T, int F, int row_stride, bool time_major, const int32_t* n_frames, double rate,
                  int T_out, float* out) {
-    const int n_launches = (B + ST_CHUNK - 1) / ST_CHUNK;
-    ProfScope ps(h, ST_STRETCH, n_launches);
+    ProfScope ps(h, ST_STRETCH, length_chunks(B, ST_CHUNK));
     const size_t per_in = time_major ? (size_t)T * row_stride : (size_t)F * T;
     const size_t per_out = time_major ? (size_t)T_out * row_stride : (size_t)F * T_out;
     const bool vec = time_major && row_stride % 4 == 0 && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     for (int b0 = 0; b0 < B; b0 += ST_CHUNK) {
         const int nb = std::min(ST_CHUNK, B - b0);
-        StretchLens lens;
-        std::memset(&lens, 0, sizeof(lens));
-        for (int b = 0; b < nb; ++b) {
-            lens.n_in[b] = n_frames ? n_frames[b0 + b] : T;
-            lens.n_out[b] = (int)std::min<long long>(stretched_frames(lens.n_in[b], rate), T_out);
-        }
+        StretchLens lens = {};
+        fill_lengths(lens.n_in, n_frames, b0, nb, T);
+        for (int b = 0; b < nb; ++b) lens.n_out[b] = (int)std::min<long long>(stretched_frames(lens.n_in[b], rate), T_out);
         const float* src = in + (size_t)b0 * per_in;
         float* dst = out + (size_t)b0 * per_out;
         if (time_major) {

@@ -2,6 +2,7 @@
 // Plain C++ (no HIP, no handle): stretch.hip and the pipeline include it, and tests/stretch_check.cpp compiles it alone.
 //   time_stretch                reference audio/effects.py:46-88 (librosa 0.6 phase_vocoder, of which only np.abs is kept)
 #pragma once
+#include "lengths.h"
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -30,7 +31,8 @@ inline std::string stretch_check(bool have_ptrs, int B, int F, int T, int row_st
     long long longest = 0;
     for (int b = 0; b < B; ++b) {
         const int n = n_frames ? n_frames[b] : T;
-        if (n < 1 || n > T) return "n_frames[" + std::to_string(b) + "] = " + std::to_string(n) + " is not in 1 .. T = " + std::to_string(T);
+        const std::string why = length_refusal("n_frames", b, n, "T", T);
+        if (!why.empty()) return why;
         const long long m = stretched_frames(n, rate);
         longest = m > longest ? m : longest;
     }

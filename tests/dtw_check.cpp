@@ -5,20 +5,14 @@
 // the runtimes.
 #include "cepstrum_plan.h"
 #include "dtw_plan.h"
+#include "check_expect.h"
 #include <cstdio>
 #include <string>
 #include <vector>
 
 using namespace tts;
 
-static int g_failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        ++g_failures;
-        std::fprintf(stderr, "FAIL %s\n", what);
-    }
-}
+static std::string g_why;   // the refusal text of the last dtw_answer
 
 // 0: legal, 1: TTS_ERR_INVALID, 2: TTS_ERR_UNSUPPORTED
 static int dtw_answer(bool ptrs, int Ta, int sa, const std::vector<int32_t>* na, int Tb, int sb, const std::vector<int32_t>* nb, int B, int D,
@@ -26,6 +20,7 @@ static int dtw_answer(bool ptrs, int Ta, int sa, const std::vector<int32_t>* na,
     bool unsupported = false;
     int r = 0, c = 0;
     const std::string why = dtw_check(ptrs, Ta, sa, na ? na->data() : nullptr, Tb, sb, nb ? nb->data() : nullptr, B, D, &unsupported, &r, &c);
+    g_why = why;
     if (rows) *rows = r;
     if (cols) *cols = c;
     expect(why.empty() ? !unsupported : true, "unsupported is set with a reason only");
@@ -93,11 +88,20 @@ int main() {
         std::vector<int32_t> l = la;
         l[2] = bad;
         std::printf("dtw_check n_a=%d %d\n", bad, dtw_answer(true, 12, 13, &l, 20, 13, &lb, 3, 13));
+        std::printf("msg n_a=%d %s\n", bad, g_why.c_str());
     }
     for (int bad : {0, -5, 21}) {
         std::vector<int32_t> l = lb;
         l[0] = bad;
         std::printf("dtw_check n_b=%d %d\n", bad, dtw_answer(true, 12, 13, &la, 20, 13, &l, 3, 13));
+        std::printf("msg n_b=%d %s\n", bad, g_why.c_str());
+    }
+    {   // the lengths are checked pair by pair, n_a[p] ahead of n_b[p]: the first refusal is the earlier pair's
+        const std::vector<int32_t> a2 = {12, 7, 0}, b2 = {0, 20, 20}, a3 = {12, 0, 1}, b3 = {3, 21, 20};
+        dtw_answer(true, 12, 13, &a2, 20, 13, &b2, 3, 13);
+        std::printf("msg order_pairs %s\n", g_why.c_str());
+        dtw_answer(true, 12, 13, &a3, 20, 13, &b3, 3, 13);
+        std::printf("msg order_sides %s\n", g_why.c_str());
     }
     std::printf("dtw_check D_above %d\n", dtw_answer(true, 12, 200, nullptr, 20, 200, nullptr, 3, DTW_MAX_D + 1));
     std::printf("dtw_check Ta_above %d\n", dtw_answer(true, DTW_MAX_FRAMES + 1, 13, nullptr, 20, 13, nullptr, 1, 13));
@@ -123,6 +127,7 @@ int main() {
         std::vector<int32_t> l = lf;
         l[1] = bad;
         expect(mfcc_refused(true, 3, 12, 80, 80, &l, 13), "n_frames outside [1, T]");
+        std::printf("msg n_frames=%d %s\n", bad, mfcc_check(true, 3, 12, 80, 80, l.data(), 13).c_str());
     }
 
     // ---- the DCT table, laid out [n][k]
@@ -135,9 +140,5 @@ int main() {
                 for (int k : {0, 1, n_mfcc / 2, n_mfcc - 1})
                     if (n >= 0 && n < n_mels && k >= 0 && k < n_mfcc) std::printf("tab %d %d %d %d %.17g\n", n_mels, n_mfcc, n, k, tab[(size_t)n * n_mfcc + k]);
         }
-    if (g_failures) {
-        std::fprintf(stderr, "%d checks failed\n", g_failures);
-        return 1;
-    }
-    return 0;
+    return exit_status();
 }

@@ -3,6 +3,7 @@
 // and tts_f0_compare answer to a list of argument sets, for tests/test_f0_program.py to hold against tests/f0_oracle.py.  Built
 // with -fsanitize=address,undefined where the compiler has the runtimes.
 #include "f0_plan.h"
+#include "check_expect.h"
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -11,19 +12,13 @@
 
 using namespace tts;
 
-static int g_failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        ++g_failures;
-        std::fprintf(stderr, "FAIL %s\n", what);
-    }
-}
+static std::string g_why;   // the refusal text of the last f0_answer
 
 // 0: legal, 1: TTS_ERR_INVALID, 2: TTS_ERR_UNSUPPORTED
 static int f0_answer(bool ptrs, int B, int N, const std::vector<int32_t>* n, double sr, int hop, int W, int lo, int hi, double thr) {
     bool unsupported = false;
     const std::string why = f0_check(ptrs, B, N, n ? n->data() : nullptr, sr, hop, W, lo, hi, thr, &unsupported);
+    g_why = why;
     expect(why.empty() ? !unsupported : true, "unsupported is set with a reason only");
     return why.empty() ? 0 : unsupported ? 2 : 1;
 }
@@ -80,6 +75,7 @@ int main() {
         std::vector<int32_t> l = ls;
         l[1] = bad;
         std::printf("f0_check n=%d %d\n", bad, f0_answer(true, 3, 5000, &l, 22050.0, 275, 1024, 44, 368, 0.1));
+        std::printf("msg n_samples=%d %s\n", bad, g_why.c_str());
     }
     std::printf("f0_check sr0 %d\n", f0_answer(true, 3, 5000, nullptr, 0.0, 275, 1024, 44, 368, 0.1));
     std::printf("f0_check sr_negative %d\n", f0_answer(true, 3, 5000, nullptr, -22050.0, 275, 1024, 44, 368, 0.1));
@@ -98,9 +94,5 @@ int main() {
     expect(!f0_compare_check(true, 0, 55, 94, 3).empty() && !f0_compare_check(true, 40, 0, 94, 3).empty(), "Ta, Tb below 1");
     expect(!f0_compare_check(true, 40, 55, 0, 3).empty() && !f0_compare_check(true, 40, 55, 94, 0).empty(), "rows, B below 1");
 
-    if (g_failures) {
-        std::fprintf(stderr, "%d checks failed\n", g_failures);
-        return 1;
-    }
-    return 0;
+    return exit_status();
 }

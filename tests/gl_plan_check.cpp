@@ -2,6 +2,7 @@
 // batches the runs must tile every utterance exactly, stay inside it, and carry slot words that agree with slots_per_utt.
 // Built and run by tests/test_gl_plan_program.py, with -fsanitize=address,undefined where the compiler has the runtimes.
 #include "gl_plan.h"
+#include "check_expect.h"
 #include <algorithm>
 #include <cstdio>
 #include <string>
@@ -9,7 +10,7 @@
 
 using namespace tts;
 
-static int g_failures = 0, g_cases = 0;
+static int g_cases = 0;
 
 static void fail(const std::string& what, const std::string& why) {
     if (++g_failures <= 20) std::fprintf(stderr, "FAIL %s: %s\n", what.c_str(), why.c_str());
@@ -129,5 +130,5 @@ int main() {
                 }
     }
     std::printf("gl_plan_check: %d cases, %d failures\n", g_cases, g_failures);
-    return g_failures ? 1 : 0;
+    return exit_status();
 }

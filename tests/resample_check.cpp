@@ -3,21 +3,13 @@
 // outputs for tests/test_resample_program.py to hold against the numpy oracle, and runs the argument checks of tts_resample
 // through every refusal the header lists.  Built with -fsanitize=address,undefined where the compiler has the runtimes.
 #include "resample_plan.h"
+#include "check_expect.h"
 #include <cstdio>
 #include <limits>
 #include <string>
 #include <vector>
 
 using namespace tts;
-
-static int g_failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        ++g_failures;
-        std::fprintf(stderr, "FAIL %s\n", what);
-    }
-}
 
 static bool refused(bool ptrs, int B, int n, const int32_t* ns, double rho, int N_out) { return !resample_check(ptrs, B, n, ns, rho, N_out).empty(); }
 
@@ -78,14 +70,11 @@ int main() {
         std::vector<int32_t> l = lens;
         l[1] = bad;
         expect(refused(true, B, n, l.data(), 1.3, 130), "n_samples outside [1, n]");
+        std::printf("msg n_samples=%d %s\n", bad, resample_check(true, B, n, l.data(), 1.3, 130).c_str());
     }
     // the order of the header's list: the pointer before the ratio before the sizes before the lengths
     expect(resample_check(false, 0, 0, nullptr, nan, 0) == "a NULL pointer", "NULL first");
     expect(resample_check(true, 0, 0, nullptr, nan, 0).find("ratio") != std::string::npos, "then the ratio");
     expect(resample_check(true, 0, 0, nullptr, 1.0, 0).find("B, n, N_out") != std::string::npos, "then the sizes");
-    if (g_failures) {
-        std::fprintf(stderr, "%d checks failed\n", g_failures);
-        return 1;
-    }
-    return 0;
+    return exit_status();
 }

@@ -8,20 +8,12 @@
 // "detected reported gl n_samples keep kept" (-1: the call has no such value).  kept: the samples the resampler leaves in the
 // row, min(resampled_valid(its input, rho), its cap).
 #include "synth_plan.h"
+#include "check_expect.h"
 #include <cstdio>
 #include <string>
 #include <vector>
 
 using namespace tts;
-
-static int g_failures = 0;
-
-static void expect(bool ok, const char* what) {
-    if (!ok) {
-        ++g_failures;
-        std::fprintf(stderr, "FAIL %s\n", what);
-    }
-}
 
 // which refusal, in the order a call meets them; 0: none
 static int which(const std::string& why) {
@@ -104,9 +96,5 @@ int main() {
         expect(synth_shape(15, 2048, 275, 4.0, 1.0, false, &sh).find("at this speaking rate") != std::string::npos, "the rows' refusal names the rate");
         expect(synth_shape(4, 2048, 275, 1.0, 1.0, false, &sh).find("at this speaking rate") == std::string::npos, "... only where one is set");
     }
-    if (g_failures) {
-        std::fprintf(stderr, "%d checks failed\n", g_failures);
-        return 1;
-    }
-    return 0;
+    return exit_status();
 }

@@ -11,6 +11,7 @@ import cepstrum_oracle as C
 import dtw_cases as K
 import dtw_oracle as W
 from conftest import pkg
+from host_checks import no_device_engine
 
 
 # ---------------------------------------------------------------------------------------------- the oracle
@@ -226,16 +227,8 @@ def test_the_library_refuses_bad_arguments_before_it_touches_a_device():
     assert lib.tts_mfcc(None, p, 3, 12, 80, 80, None, 13, 1, p) == INV and why() == before
 
 
-def _no_device_engine():
-    H = pkg('_hip')
-    eng = H.Engine.__new__(H.Engine)
-    eng.handle = None
-    eng.lib = None
-    return eng
-
-
 def test_python_refuses_bad_arguments_before_any_device_call():
-    eng = _no_device_engine()
+    eng = no_device_engine()
     rows = np.ones((3, 12, 80), np.float32)
     for n_mfcc in (0, 81, 2.5):
         with pytest.raises(ValueError):

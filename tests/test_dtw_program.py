@@ -3,52 +3,15 @@ direction-bit workspace and the argument checks of tts_dtw; csrc/cepstrum_plan.h
 stand-alone host program: tests/dtw_check.cpp with its own main, compiled as plain C++ -- with AddressSanitizer and UBSan where the
 host compiler has their runtimes (linked statically: the program needs nothing preloaded) -- and run.  What it prints is held
 against the numpy oracles here: every integer exactly, table values to 4 ulp.  No GPU, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 
-from conftest import PKG, ROOT
 import cepstrum_oracle as C
 import dtw_oracle as W
-
-CSRC = os.path.join(ROOT, PKG, 'csrc')
-
-
-def _compilers():
-    names = [os.environ['CXX']] if os.environ.get('CXX') else []
-    return [c for c in names + ['g++', 'c++', 'clang++', 'amdclang++'] if shutil.which(c)]
-
-
-def _build(cxx, out, sanitize):
-    cmd = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-I', CSRC]
-    if sanitize:
-        cmd += ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer']
-        if 'clang' not in subprocess.run([cxx, '--version'], stdout=subprocess.PIPE).stdout.decode():
-            cmd += ['-static-libasan', '-static-libubsan']   # (clang links its sanitizer runtimes statically by default)
-    cmd += [os.path.join(ROOT, 'tests', 'dtw_check.cpp'), '-o', out]
-    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+from host_checks import LENGTH_REFUSAL, build_and_run, length_refusals
 
 
 def test_dtw_check_program(tmp_path):
-    compilers = _compilers()
-    assert compilers, 'no host C++ compiler (g++, c++, clang++, amdclang++ or $CXX)'
-    exe = str(tmp_path / 'dtw_check')
-    built, log = None, ''
-    for sanitize in (True, False):   # without the flag only where no compiler can link the sanitizers' runtimes
-        for cxx in compilers:
-            r = _build(cxx, exe, sanitize)
-            if r.returncode == 0:
-                built = (cxx, sanitize)
-                break
-            log = r.stdout.decode(errors='replace')
-        if built:
-            break
-    assert built, log[-3000:]
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
-    assert run.returncode == 0, run.stderr.decode(errors='replace')[-3000:]
-    rows = [line.split() for line in run.stdout.decode().splitlines()]
+    rows, refusals = length_refusals(build_and_run('dtw_check.cpp', tmp_path)[0])
     kinds = {k: [r[1:] for r in rows if r[0] == k] for k in ('consts', 'shape', 'diag', 'slots', 'dir', 'dtw_check', 'tab')}
     tile, slots, max_frames, max_d, pairs, dir_cells = (int(v) for v in kinds['consts'][0])
     assert max_frames >= 2048 and max_frames == tile * slots and max_d == 128 and dir_cells == 16 and pairs >= 1
@@ -88,4 +51,12 @@ def test_dtw_check_program(tmp_path):
             mats[key] = C.dct_matrix(*key)
         want = mats[key][int(k), int(n)]
         assert abs(float(v) - want) <= 4 * np.spacing(abs(want)) + 1e-300, (key, n, k, v, want)
-    print('built with {} (sanitizers: {})'.format(*built))
+
+    # the refusal texts of the bad lengths, tts_mfcc's (n_frames) among them; a pair's n_a is looked at ahead of its n_b and
+    # an earlier pair ahead of a later one
+    want = {'n_a=%d' % n: LENGTH_REFUSAL.format(name='n_a', b=2, n=n, bound='Ta', hi=12) for n in (0, -1, 13)}
+    want.update({'n_b=%d' % n: LENGTH_REFUSAL.format(name='n_b', b=0, n=n, bound='Tb', hi=20) for n in (0, -5, 21)})
+    want.update({'n_frames=%d' % n: LENGTH_REFUSAL.format(name='n_frames', b=1, n=n, bound='T', hi=12) for n in (0, -1, 13)})
+    want['order_pairs'] = LENGTH_REFUSAL.format(name='n_b', b=0, n=0, bound='Tb', hi=20)
+    want['order_sides'] = LENGTH_REFUSAL.format(name='n_a', b=1, n=0, bound='Ta', hi=12)
+    assert refusals == want

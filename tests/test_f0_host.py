@@ -10,6 +10,7 @@ import pytest
 import f0_cases as K
 import f0_oracle as Y
 from conftest import pkg
+from host_checks import no_device_engine
 
 E = K.EVAL
 
@@ -249,16 +250,8 @@ def test_the_library_refuses_bad_arguments_before_it_touches_a_device():
     assert lib.tts_f0_compare(None, *good2) == INV and why() == before
 
 
-def _no_device_engine():
-    H = pkg('_hip')
-    eng = H.Engine.__new__(H.Engine)
-    eng.handle = None
-    eng.lib = None
-    return eng
-
-
 def test_python_refuses_bad_arguments_before_any_device_call():
-    eng = _no_device_engine()
+    eng = no_device_engine()
     x = np.zeros((2, 5000), np.float32)
     with pytest.raises(ValueError, match='2048'):
         eng.f0(x, 22050, 275, window=2049)

@@ -3,49 +3,12 @@ LDS bytes, the lag bounds and the argument checks of tts_f0 and tts_f0_compare) 
 with its own main, compiled as plain C++ -- with AddressSanitizer and UBSan where the host compiler has their runtimes (linked
 statically: the program needs nothing preloaded) -- and run.  What it prints is held against tests/f0_oracle.py here, every
 integer exactly.  No GPU, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
-
-from conftest import PKG, ROOT
 import f0_oracle as Y
-
-CSRC = os.path.join(ROOT, PKG, 'csrc')
-
-
-def _compilers():
-    names = [os.environ['CXX']] if os.environ.get('CXX') else []
-    return [c for c in names + ['g++', 'c++', 'clang++', 'amdclang++'] if shutil.which(c)]
-
-
-def _build(cxx, out, sanitize):
-    cmd = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-I', CSRC]
-    if sanitize:
-        cmd += ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer']
-        if 'clang' not in subprocess.run([cxx, '--version'], stdout=subprocess.PIPE).stdout.decode():
-            cmd += ['-static-libasan', '-static-libubsan']   # (clang links its sanitizer runtimes statically by default)
-    cmd += [os.path.join(ROOT, 'tests', 'f0_check.cpp'), '-o', out]
-    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+from host_checks import LENGTH_REFUSAL, build_and_run, length_refusals
 
 
 def test_f0_check_program(tmp_path):
-    compilers = _compilers()
-    assert compilers, 'no host C++ compiler (g++, c++, clang++, amdclang++ or $CXX)'
-    exe = str(tmp_path / 'f0_check')
-    built, log = None, ''
-    for sanitize in (True, False):   # without the flag only where no compiler can link the sanitizers' runtimes
-        for cxx in compilers:
-            r = _build(cxx, exe, sanitize)
-            if r.returncode == 0:
-                built = (cxx, sanitize)
-                break
-            log = r.stdout.decode(errors='replace')
-        if built:
-            break
-    assert built, log[-3000:]
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
-    assert run.returncode == 0, run.stderr.decode(errors='replace')[-3000:]
-    rows = [line.split() for line in run.stdout.decode().splitlines()]
+    rows, refusals = length_refusals(build_and_run('f0_check.cpp', tmp_path)[0])
     kinds = {k: [r[1:] for r in rows if r[0] == k] for k in ('consts', 'frames', 'first', 'group', 'groups', 'lags', 'f0_check')}
     max_w, max_lag, lanes, slots, max_group, utts, budget = (int(v) for v in kinds['consts'][0])
     assert (max_w, max_lag) == (2048, 1024) and lanes * slots == max_lag and max_group >= 1 and utts >= 1 and budget <= 64 * 1024
@@ -75,4 +38,4 @@ def test_f0_check_program(tmp_path):
     for name, code in answers.items():
         want = 0 if name.startswith('legal') else 2 if name.endswith('_above') else 1
         assert code == want, (name, code)
-    print('built with {} (sanitizers: {})'.format(*built))
+    assert refusals == {'n_samples=%d' % n: LENGTH_REFUSAL.format(name='n_samples', b=1, n=n, bound='N', hi=5000) for n in (0, -1, 5001)}

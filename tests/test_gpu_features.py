@@ -13,6 +13,7 @@ import feature_cases as FC
 import trim_oracle as T
 from conftest import ROOT, pkg
 from feature_cases import speechlike
+from neighbour_fixture import neighbour   # noqa: F401
 from parity import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -199,37 +200,21 @@ def test_precalc_entry_point_end_to_end(tmp_path):
         _check_features((mel, lin), w, 'npz %d' % i)
 
 
-def test_features_beside_gemm_launches_of_another_handle(eng, hparams, weights):
-    eng2 = pkg().Engine(hparams)
-    eng2.load_weights(weights)
-    rng = np.random.default_rng(7)
-    x = eng2.to_device(rng.standard_normal((9600, 256)).astype(np.float32))
-    w = eng2.to_device(rng.standard_normal((256, 256)).astype(np.float32))
-    c = eng2.empty((9600, 256))
-
-    def launch(n=30):
-        for _ in range(n):
-            eng2._check(eng2.lib.tts_debug_gemm(eng2.handle, x.data_ptr(), w.data_ptr(), c.data_ptr(), 9600, 256, 256, 1, 150, 0))
-
-    try:
-        wavs = _batch(np.random.default_rng(10), 16, 0.3, 2.0)
-        configs = [None, eng.feature_params(n_fft=1024, win_length=1024, hop_length=256, normalize=0, reduction=1, trim=0)]
-        for p in configs:
-            quiet = eng.extract_features(wavs, p)
-            bad = n = 0
-            for _ in range(10):
-                launch()
-                outs = eng.extract_features(wavs, p)
-                eng2.synchronize()
-                for q, o in zip(quiet, outs):
-                    n += 1
-                    bad += not (np.array_equal(q[0], o[0]) and np.array_equal(q[1], o[1]))
-            assert bad == 0, '%d of %d recordings differ from the quiet run' % (bad, n)
-    finally:
-        eng2.synchronize()
-        for a in (x, w, c):
-            a.free()
-        eng2.close()
+def test_features_beside_gemm_launches_of_another_handle(eng, neighbour):
+    eng2, launch = neighbour
+    wavs = _batch(np.random.default_rng(10), 16, 0.3, 2.0)
+    configs = [None, eng.feature_params(n_fft=1024, win_length=1024, hop_length=256, normalize=0, reduction=1, trim=0)]
+    for p in configs:
+        quiet = eng.extract_features(wavs, p)
+        bad = n = 0
+        for _ in range(10):
+            launch()
+            outs = eng.extract_features(wavs, p)
+            eng2.synchronize()
+            for q, o in zip(quiet, outs):
+                n += 1
+                bad += not (np.array_equal(q[0], o[0]) and np.array_equal(q[1], o[1]))
+        assert bad == 0, '%d of %d recordings differ from the quiet run' % (bad, n)
 
 
 def test_decibel_statistics_match_the_restatement(eng, tmp_path):

@@ -7,30 +7,9 @@ import pytest
 
 import resample_cases as K
 import resample_oracle as R
-from conftest import pkg
+from neighbour_fixture import neighbour   # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def neighbour(hparams, weights):
-    """A second handle whose only job is to keep MFMA GEMM waves on the chip."""
-    eng2 = pkg().Engine(hparams)
-    eng2.load_weights(weights)
-    rng = np.random.default_rng(7)
-    x = eng2.to_device(rng.standard_normal((9600, 256)).astype(np.float32))
-    w = eng2.to_device(rng.standard_normal((256, 256)).astype(np.float32))
-    c = eng2.empty((9600, 256))
-
-    def launch(n=30):
-        for _ in range(n):
-            eng2._check(eng2.lib.tts_debug_gemm(eng2.handle, x.data_ptr(), w.data_ptr(), c.data_ptr(), 9600, 256, 256, 1, 150, 0))
-
-    yield eng2, launch
-    eng2.synchronize()
-    for a in (x, w, c):
-        a.free()
-    eng2.close()
 
 
 @pytest.mark.parametrize('rho', [2.0 ** (-4.0 / 12.0), 2.0 ** (3.0 / 12.0)], ids=['down4st', 'up3st'])

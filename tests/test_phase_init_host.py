@@ -10,6 +10,7 @@ import momentum_oracle as M
 import phase_cases as K
 import phase_oracle as P
 from conftest import pkg
+from host_checks import no_device_engine
 
 HALF = np.uint32(0x80000000)
 
@@ -137,20 +138,6 @@ def test_the_estimate_reaches_in_20_iterations_what_random_phases_reach_in_60():
 
 
 # ---------------------------------------------------------------------------------------------- the surface
-def _no_device_engine():
-    """an Engine object that was never given a handle: every call on it must raise before it reaches the library"""
-    H = pkg('_hip')
-    eng = H.Engine.__new__(H.Engine)
-    eng.handle = None
-    eng.lib = None
-    eng._speaking_rate = 1.0
-    eng._pitch = 0.0
-    eng._gl_momentum = 0
-    eng._gl_init = 0
-    eng._end_of_speech = (False, 0.0, 0)
-    return eng
-
-
 def test_the_library_refuses_without_a_device():
     H = pkg('_hip')
     lib = H.load_library()
@@ -172,7 +159,7 @@ def test_python_refuses_bad_phase_init_before_any_device_call(bad, tmp_path):
     I = pkg('tacotron.inference')   # noqa: E741
     V = pkg('tacotron.serve')
     Y = pkg('audio.synthesis')
-    eng = _no_device_engine()
+    eng = no_device_engine()
     ids = np.ones((2, 5), np.int32)
     mag = np.ones((1, 1025, 12), np.float32)
     with pytest.raises(ValueError):
@@ -202,7 +189,7 @@ def test_python_refuses_bad_phase_init_before_any_device_call(bad, tmp_path):
 
 
 def test_python_refuses_bad_estimate_arguments_before_any_device_call():
-    eng = _no_device_engine()
+    eng = no_device_engine()
     mag = np.ones((3, 129, 10), np.float32)
     for n_fft, hop in [(250, 64), (128, 32), (8192, 64), (256.5, 64), (256, 0), (256, 257), (256, 1.5), (512, 64)]:
         with pytest.raises(ValueError):

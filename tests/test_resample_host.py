@@ -10,6 +10,7 @@ import pytest
 import resample_cases as K
 import resample_oracle as R
 from conftest import pkg
+from host_checks import no_device_engine
 
 EDGE = 400      # samples at each end of a result that the filter's run-in reaches (64 zero crossings: 256 outputs at ratio 4)
 N_IN = 8000
@@ -148,19 +149,6 @@ def test_covers_is_the_window():
 
 
 # ---------------------------------------------------------------------------------------------- the surface
-def _no_device_engine():
-    """an Engine object that was never given a handle: every call on it must raise before it reaches the library"""
-    H = pkg('_hip')
-    eng = H.Engine.__new__(H.Engine)
-    eng.handle = None
-    eng.lib = None
-    eng._speaking_rate = 1.0
-    eng._pitch = 0.0
-    eng._gl_momentum = 0
-    eng._end_of_speech = (False, 0.0, 0)
-    return eng
-
-
 def test_host_helpers_agree_with_the_oracle():
     H = pkg('_hip')
     for n in (1, 2, 63, 441, 5000, 22050, 275000):
@@ -174,7 +162,7 @@ def test_host_helpers_agree_with_the_oracle():
 @pytest.mark.parametrize('bad', [float('nan'), float('inf'), 0.0, 0.2, 4.5, -1.0, 'fast'])
 def test_python_refuses_bad_ratios_before_any_device_call(bad):
     H = pkg('_hip')
-    eng = _no_device_engine()
+    eng = no_device_engine()
     with pytest.raises(ValueError):
         H.resample_ratio_value(bad)
     with pytest.raises(ValueError):
@@ -190,7 +178,7 @@ def test_python_refuses_bad_pitches_before_any_device_call(bad):
     H = pkg('_hip')
     I = pkg('tacotron.inference')   # noqa: E741
     V = pkg('tacotron.serve')
-    eng = _no_device_engine()
+    eng = no_device_engine()
     ids = np.ones((2, 5), np.int32)
     with pytest.raises(ValueError):
         H.pitch_octaves_value(bad)
@@ -215,7 +203,7 @@ def test_python_refuses_bad_pitches_before_any_device_call(bad):
 
 
 def test_python_refuses_wrong_shapes_and_lengths_before_any_device_call():
-    eng = _no_device_engine()
+    eng = no_device_engine()
     x = np.zeros((3, 20), np.float32)
     for bad in [[20, 7], [[20, 7, 1]], 20, [20, 0, 1], [20, 21, 1], [20.0, 7.0, 1.0]]:
         with pytest.raises(ValueError):
@@ -274,6 +262,6 @@ def test_the_module_level_effects_keep_raising_and_point_to_the_engine():
     x = np.zeros(10, np.float32)
     assert io.resample(x, 22050, 22050) is x      # librosa returns its input for equal rates
     with pytest.raises(ValueError):
-        io.resample(x, 22050, 2000, engine=_no_device_engine())
+        io.resample(x, 22050, 2000, engine=no_device_engine())
     with pytest.raises(ValueError):
-        io.resample(np.zeros((2, 10), np.float32), 22050, 16000, engine=_no_device_engine())
+        io.resample(np.zeros((2, 10), np.float32), 22050, 16000, engine=no_device_engine())

@@ -3,52 +3,16 @@ of an output and the argument checks of tts_resample) as a stand-alone host prog
 compiled as plain C++ -- with AddressSanitizer and UBSan where the host compiler has their runtimes (linked statically: the
 program needs nothing preloaded) -- and run.  What it prints is held against the numpy oracle here: lengths and integers exactly,
 table values to 1e-13 of max |win|.  No GPU, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 
-from conftest import PKG, ROOT
 import resample_oracle as R
+from host_checks import LENGTH_REFUSAL, build_and_run, length_refusals
 
-CSRC = os.path.join(ROOT, PKG, 'csrc')
 TABLE_TOL = 1e-13
 
 
-def _compilers():
-    names = [os.environ['CXX']] if os.environ.get('CXX') else []
-    return [c for c in names + ['g++', 'c++', 'clang++', 'amdclang++'] if shutil.which(c)]
-
-
-def _build(cxx, out, sanitize):
-    cmd = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-I', CSRC]
-    if sanitize:
-        cmd += ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer']
-        if 'clang' not in subprocess.run([cxx, '--version'], stdout=subprocess.PIPE).stdout.decode():
-            cmd += ['-static-libasan', '-static-libubsan']   # (clang links its sanitizer runtimes statically by default)
-    cmd += [os.path.join(ROOT, 'tests', 'resample_check.cpp'), '-o', out]
-    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-
-
 def test_resample_check_program(tmp_path):
-    compilers = _compilers()
-    assert compilers, 'no host C++ compiler (g++, c++, clang++, amdclang++ or $CXX)'
-    exe = str(tmp_path / 'resample_check')
-    built, log = None, ''
-    for sanitize in (True, False):   # without the flag only where no compiler can link the sanitizers' runtimes
-        for cxx in compilers:
-            r = _build(cxx, exe, sanitize)
-            if r.returncode == 0:
-                built = (cxx, sanitize)
-                break
-            log = r.stdout.decode(errors='replace')
-        if built:
-            break
-    assert built, log[-3000:]
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
-    assert run.returncode == 0, run.stderr.decode(errors='replace')[-3000:]
-    rows = [line.split() for line in run.stdout.decode().splitlines()]
+    rows, refusals = length_refusals(build_and_run('resample_check.cpp', tmp_path)[0])
     kinds = {k: [r[1:] for r in rows if r[0] == k] for k in ('len', 'win', 'consts', 'tab', 'phase')}
     assert len(kinds['len']) == 8 * 11 and len(kinds['consts']) == 8 and len(kinds['phase']) == 8 * 11 and len(kinds['tab']) > 8 * 40
     for n, rho, valid, length in kinds['len']:
@@ -75,4 +39,4 @@ def test_resample_check_program(tmp_path):
         wm, (o0, e0, k0), (o1, e1, k1) = R.phase(int(t), int(n_in), float(rho))
         assert (int(m), int(off0), int(taps0), int(off1), int(taps1)) == (int(wm), int(o0), int(k0), int(o1), int(k1)), (rho, t)
         assert float(eta0) == float(e0) and float(eta1) == float(e1), (rho, t)
-    print('built with {} (sanitizers: {})'.format(*built))
+    assert refusals == {'n_samples=%d' % n: LENGTH_REFUSAL.format(name='n_samples', b=1, n=n, bound='n', hi=100) for n in (0, -1, 101)}

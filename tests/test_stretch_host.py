@@ -10,6 +10,7 @@ import pytest
 import stretch_cases as K
 import stretch_oracle as S
 from conftest import pkg
+from host_checks import no_device_engine
 
 # the issue's bar: four times the derived 2^-22 (complex64 cast 2^-24, float32 abs 2^-23, the blend's own rounding 2^-24)
 FULL_PATH_TOL = 1e-6
@@ -83,12 +84,6 @@ def test_oracle_batch_form_and_rate_one():
     assert S.stretched_lengths([12, 7, 5], 1.25, 10, 5).tolist() == [10, 6, 5]
 
 
-def _no_device_engine():
-    """an Engine that was never created: any use of the library or a handle is an AttributeError"""
-    H = pkg('_hip')
-    return H.Engine.__new__(H.Engine)
-
-
 BAD_RATES = [float('nan'), 0, 0.2, 4.5, float('inf'), 'fast']
 
 
@@ -97,7 +92,7 @@ def test_python_refuses_a_bad_rate_before_any_device_call(rate):
     H = pkg('_hip')
     I = pkg('tacotron.inference')   # noqa: E741
     V = pkg('tacotron.serve')
-    eng = _no_device_engine()
+    eng = no_device_engine()
     mag = np.ones((2, 3, 4), np.float32)
     ids = np.ones((2, 5), np.int32)
     with pytest.raises(ValueError):
@@ -131,7 +126,7 @@ def test_python_refuses_a_bad_rate_before_any_device_call(rate):
 
 def test_python_refuses_wrong_frame_counts_before_any_device_call():
     H = pkg('_hip')
-    eng = _no_device_engine()
+    eng = no_device_engine()
     mag = np.ones((3, 5, 12), np.float32)
     for bad in [[12, 7], [[12, 7, 1]], [12, 7, 1, 1], 12, [12, 0, 1], [12, 13, 1], [12.0, 7.0, 1.0]]:
         with pytest.raises(ValueError):

@@ -4,39 +4,19 @@ own main, compiled as plain C++ -- with AddressSanitizer and UBSan where the hos
 the program needs nothing preloaded) -- and run.  Every row of its grid is held against the tests' own oracles here
 (stretch_oracle, resample_oracle: numpy restatements of the reference's arithmetic), and the same grid against the two
 functions of _hip.py that restate the plan for the Python callers.  No GPU, nothing loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import resample_oracle as R
 import stretch_oracle as S
-from conftest import PKG, ROOT, pkg
-
-CSRC = os.path.join(ROOT, PKG, 'csrc')
+from conftest import pkg
+from host_checks import build_and_run
 
 SIZES = [(2048, 275), (512, 100)]
 FRAMES = range(4, 49)
 RATES = [0.25, 0.8, 1.0, 1.2, 2.5, 4.0]
 OCTAVES = [-1.0, -1.0 / 3.0, 0.0, 1.0 / 3.0, 1.0]
 B = 3
-
-
-def _compilers():
-    names = [os.environ['CXX']] if os.environ.get('CXX') else []
-    return [c for c in names + ['g++', 'c++', 'clang++', 'amdclang++'] if shutil.which(c)]
-
-
-def _build(cxx, out, sanitize):
-    cmd = [cxx, '-std=c++17', '-O1', '-g', '-Wall', '-I', CSRC]
-    if sanitize:
-        cmd += ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer']
-        if 'clang' not in subprocess.run([cxx, '--version'], stdout=subprocess.PIPE).stdout.decode():
-            cmd += ['-static-libasan', '-static-libubsan']   # (clang links its sanitizer runtimes statically by default)
-    cmd += [os.path.join(ROOT, 'tests', 'synth_plan_check.cpp'), '-o', out]
-    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
 
 
 def oracle_plan(n_fft, hop, T, s, octaves, stopping):
@@ -74,24 +54,7 @@ def oracle_plan(n_fft, hop, T, s, octaves, stopping):
 
 @pytest.fixture(scope='module')
 def rows(tmp_path_factory):
-    compilers = _compilers()
-    assert compilers, 'no host C++ compiler (g++, c++, clang++, amdclang++ or $CXX)'
-    exe = str(tmp_path_factory.mktemp('synth_plan') / 'synth_plan_check')
-    built, log = None, ''
-    for sanitize in (True, False):   # without the flag only where no compiler can link the sanitizers' runtimes
-        for cxx in compilers:
-            r = _build(cxx, exe, sanitize)
-            if r.returncode == 0:
-                built = (cxx, sanitize)
-                break
-            log = r.stdout.decode(errors='replace')
-        if built:
-            break
-    assert built, log[-3000:]
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
-    assert run.returncode == 0, run.stderr.decode(errors='replace')[-3000:]
-    print('built with {} (sanitizers: {})'.format(*built))
-    return [line.split() for line in run.stdout.decode().splitlines()]
+    return build_and_run('synth_plan_check.cpp', tmp_path_factory.mktemp('synth_plan'))[0]
 
 
 def _grid():

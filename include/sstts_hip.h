@@ -596,6 +596,56 @@ int tts_f0_max_lag(void);
 int tts_f0_compare(tts_handle_t h, const float* f0_a, int Ta, const float* f0_b, int Tb, const int32_t* path /* [B][rows][2] */,
                    int rows, int B, int32_t* counts /* [B][5] */, double* sums /* [B][2] */);
 
+/* ---- loudness: ITU-R BS.1770-4 / EBU R 128 ------------------------------------------------ */
+/* Integrated loudness of B mono utterances (no reference counterpart: the reference's only level control is the peak
+ * normalisation of save_wav).  wav DEVICE [B][N]; n_samples: HOST int32 [B], the samples of each utterance, or NULL (all N) --
+ * samples at or behind n_samples[b] are never read.  sampling_rate: an integer in 8000 .. 192000.  Every product, sum and
+ * quotient below is an individually rounded IEEE double operation on x = (double)wav[b][i]:
+ *   K-weighting    two biquads, b0 b1 b2 a1 a2 each (tts_loudness_filter: the bilinear transform, at this sampling rate, of the
+ *                  analogue shelf and high-pass that give the standard's tables at 48 kHz), each in direct form II transposed:
+ *                  y = b0 x + z1;  z1 = (b1 x - a1 y) + z2;  z2 = b2 x - a2 y
+ *   the cut        s = sampling_rate / 10 samples are a step, K = n / s steps are read (none when K < 4), and the samples behind
+ *                  them count for nothing.  A step is cut into 8 segments of c = tts_loudness_segment(sampling_rate) =
+ *                  ceil(s / 8) samples, the last of s - 7 c.  Pass 1 runs the cascade over each segment from the zero state and
+ *                  keeps the four state values e_i it ends in; pass 2 chains them, S_0 = 0 and
+ *                  S_{i+1}[r] = ((((M[r][0] S_i[0] + M[r][1] S_i[1]) + M[r][2] S_i[2]) + M[r][3] S_i[3]) + e_i[r], where column j
+ *                  of the segment's transition M is the state the same recurrence ends in from the unit state j on zero input;
+ *                  pass 3 runs each segment again from S_i and sums y * y in sample order.  The cut depends on the sampling
+ *                  rate alone (csrc/loudness_plan.h).
+ *   blocks         u_k = the sum of step k's 8 segment sums in order; block j = steps j .. j + 3, J = K - 3 of them, with
+ *                  z_j = (((u_j + u_j+1) + u_j+2) + u_j+3) / (4 s)
+ *   gates          absolute: z_j > 1.1724653045822981e-07 (-70 LUFS); relative: also z_j > 0.1 * (the sum of the absolutely
+ *                  gated z_j in block order / their count)
+ *   mean_square[b] = the sum, in block order, of the z_j that pass both gates / their count; 0 when J < 1 or no block passes;
+ *                  NaN when any z_j is not finite (a NaN or Inf sample inside a counted block; one behind the last block
+ *                  changes nothing).  LUFS = -0.691 + 10 log10(mean_square) is the host's to take.
+ * mean_square DEVICE double [B]; n_blocks DEVICE int32 [B][2] or NULL: J, and the blocks that passed both gates (0 where
+ * mean_square is NaN).  Exactness: the bits of tests/loudness_oracle.py.  Independence: an utterance's results are the bits of
+ * the B = 1 call on its own samples.  No model needs to be loaded.  Asynchronous on the handle's stream (4 launches per 64
+ * utterances); profile stage "loudness".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL wav or mean_square, B or N < 1, an n_samples[b] outside 1 .. N, a
+ * misaligned buffer; TTS_ERR_UNSUPPORTED: a sampling rate outside 8000 .. 192000. */
+int tts_loudness(tts_handle_t h, const float* wav /* [B][N] */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+                 int sampling_rate, double* mean_square /* [B] */, int32_t* n_blocks /* [B][2] or NULL */);
+/* The same measurement, then a gain per utterance that takes it to target_lufs, in place:
+ *   g = sqrt(Z_T / z), Z_T = 10 ** ((target_lufs + 0.691) / 10) taken on the host, z = mean_square[b];
+ *   g = min(g, max_peak / peak), peak = the largest |x| among the finite samples of the utterance;
+ *   g = 1 exactly where z is 0 or not finite, or peak is 0;
+ *   wav[b][i] = (float)(g * (double)wav[b][i]) for i < n_samples[b] (a NaN sample stays NaN)
+ * with a correctly rounded division and square root.  Samples at or behind n_samples[b] are neither read nor written.
+ * mean_square DEVICE double [B] or NULL: as measured, before the gain; gain DEVICE double [B] or NULL.  Asynchronous on the
+ * handle's stream; profile stage "loudness".  Refusals as tts_loudness (wav alone is required), and TTS_ERR_INVALID for a
+ * target that is not finite or a max_peak that is not finite and positive. */
+int tts_loudness_normalize(tts_handle_t h, float* wav /* [B][N], in place */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+                           int sampling_rate, double target_lufs, double max_peak, double* mean_square /* [B] or NULL */,
+                           double* gain /* [B] or NULL */);
+/* Host only, no handle and no device: b0 b1 b2 a1 a2 of the shelf, then of the high-pass, as the library designed them for this
+ * sampling rate (tan and pow are the host libm's: a restatement takes the coefficients from here).  TTS_ERR_INVALID: NULL;
+ * TTS_ERR_UNSUPPORTED: a sampling rate outside 8000 .. 192000. */
+int tts_loudness_filter(int sampling_rate, double coeffs[10]);
+/* Host only: the samples c of a segment at this sampling rate, ceil((sampling_rate / 10) / 8); 0 outside 8000 .. 192000. */
+int tts_loudness_segment(int sampling_rate);
+
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,
  * optional peak normalisation; replaces tacotron/inference.py:162-200 minus file IO.
@@ -696,6 +746,20 @@ int tts_set_speaking_rate(tts_handle_t h, double rate);
  * TTS_ERR_INVALID (the setting stays as it was): a shift that is not finite or |octaves| > 1. */
 int tts_set_pitch(tts_handle_t h, double octaves);
 
+/* The loudness of synthesis: a target in LUFS after ITU-R BS.1770-4 (tts_loudness_normalize).  A setting of the HANDLE, off by
+ * default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
+ * tts_synthesize and tts_synthesize_host do not peak-normalise, whatever p->peak_normalize says; they run
+ * tts_loudness_normalize(target_lufs, max_peak) at sampling_rate on the call's final rows instead -- behind Griffin-Lim, or with
+ * a pitch behind tts_resample -- on the call's stream, with no host wait.  Each utterance is measured over the samples its row
+ * holds: hop (n[b] - 1) of the reported lengths with end-of-speech stopping (tts_synth_frames), all hop (T_s - 1) otherwise.  The
+ * result is the bits of the same call made with peak_normalize = 0 followed by tts_loudness_normalize on those rows; the host
+ * form stays bit-identical to tts_synthesize + tts_memcpy_d2h.  The first call after the setting was switched on is not
+ * pipelined (its buffers are new).  sampling_rate is the caller's word for the model's rate: the library's configuration does
+ * not carry one.
+ * With enabled == 0 the other arguments are not looked at.  The setting stays as it was on TTS_ERR_INVALID (a target that is
+ * not finite, a max_peak that is not finite and positive) and on TTS_ERR_UNSUPPORTED (a sampling rate outside 8000 .. 192000). */
+int tts_set_loudness(tts_handle_t h, int enabled, double target_lufs, double max_peak, int sampling_rate);
+
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
@@ -703,7 +767,8 @@ int tts_set_pitch(tts_handle_t h, double octaves);
  * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize),
  * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
  * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
- * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare).
+ * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare), "loudness" (tts_loudness, tts_loudness_normalize, stand-alone
+ * or inside a tts_synthesize call with a loudness target).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -129,6 +129,12 @@ _PROTOTYPES = {
     'tts_f0_max_window': (c_int, []),
     'tts_f0_max_lag': (c_int, []),
     'tts_f0_compare': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'tts_loudness': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p]),
+    'tts_loudness_normalize': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, ctypes.c_double, ctypes.c_double,
+                                       c_void_p, c_void_p]),
+    'tts_loudness_filter': (c_int, [c_int, POINTER(ctypes.c_double)]),
+    'tts_loudness_segment': (c_int, [c_int]),
+    'tts_set_loudness': (c_int, [c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_int]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -414,6 +420,66 @@ def f0_frames(n, hop_length):
     return 1 + int(n) // int(hop_length)
 
 
+LOUDNESS_SR_MIN, LOUDNESS_SR_MAX = 8000, 192000   # what tts_loudness takes
+LOUDNESS_TARGET, LOUDNESS_MAX_PEAK = -23.0, 1.0   # EBU R 128's programme level, and full scale
+
+
+def loudness_sampling_rate(what, sampling_rate):
+    """the sampling rate of a loudness call as a checked int; ValueError, raised before a handle is touched, for what the
+    library refuses: a rate that is not an integer in 8000 .. 192000"""
+    try:
+        ok = int(sampling_rate) == sampling_rate and LOUDNESS_SR_MIN <= sampling_rate <= LOUDNESS_SR_MAX
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('{}: the sampling rate must be an integer in {} .. {}, got {!r}'.format(what, LOUDNESS_SR_MIN, LOUDNESS_SR_MAX, sampling_rate))
+    return int(sampling_rate)
+
+
+def loudness_target(what, target_lufs, max_peak):
+    """(target_lufs, max_peak) as checked floats; ValueError for a target that is not finite or a ceiling that is not finite and
+    positive (tts_loudness_normalize refuses the same)"""
+    try:
+        t, p = float(target_lufs), float(max_peak)
+    except (TypeError, ValueError):
+        raise ValueError('{}: target_lufs and max_peak must be numbers, got {!r}, {!r}'.format(what, target_lufs, max_peak))
+    if not np.isfinite(t):
+        raise ValueError('{}: the target must be a finite number of LUFS, got {!r}'.format(what, target_lufs))
+    if not (np.isfinite(p) and p > 0):
+        raise ValueError('{}: max_peak must be finite and positive, got {!r}'.format(what, max_peak))
+    return t, p
+
+
+def loudness_setting(loudness):
+    """``loudness`` of the synthesis calls -- None (the handle's setting as it stands), a target in LUFS or ``(target_lufs,
+    max_peak)`` -- as None or a checked tuple ``(target_lufs, max_peak)``.  ValueError, raised before a handle is touched, for
+    anything else."""
+    if loudness is None:
+        return None
+    if isinstance(loudness, (tuple, list)):
+        if len(loudness) != 2:
+            raise ValueError('loudness must be None, a target in LUFS or (target_lufs, max_peak), got {!r}'.format(loudness))
+        return loudness_target('loudness', loudness[0], loudness[1])
+    return loudness_target('loudness', loudness, LOUDNESS_MAX_PEAK)
+
+
+def lufs(mean_square):
+    """-0.691 + 10 log10(z) of the mean squares tts_loudness returns: -inf for 0 (nothing passed the gates), NaN for NaN"""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return -0.691 + 10.0 * np.log10(np.asarray(mean_square, dtype=np.float64))
+
+
+def loudness_filter(sampling_rate):
+    """tts_loudness_filter: b0 b1 b2 a1 a2 of the K-weighting shelf, then of its high-pass, as the library designed them for
+    ``sampling_rate`` (float64 (10,)); needs no device"""
+    sr = loudness_sampling_rate('loudness_filter', sampling_rate)
+    out = (ctypes.c_double * 10)()
+    rc = load_library().tts_loudness_filter(sr, out)
+    if rc != TTS_OK:
+        raise TtsError(rc, 'tts_loudness_filter({}) refused'.format(sr))
+    return np.array(out[:], dtype=np.float64)
+
+
 def stretch_frame_counts(n_frames, B, T):
     """The ``n_frames`` argument of a stretch call as a contiguous int32 array of B lengths in 1 .. T (None stays None: all
     T), checked as tts_stretch_magnitudes checks them -- ValueError, raised before a handle is touched."""
@@ -548,6 +614,8 @@ class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
     _gl_init = 0   # the handle's "gl_init" option (the C ABI has no getter: set_option keeps it)
+    _loudness = None   # ... and its loudness setting, None (off) or (target_lufs, max_peak) (set_loudness keeps it)
+    sampling_rate = 22050   # the model's (hparams.sampling_rate): what a loudness target of the synthesis calls is measured at
 
     def __init__(self, hparams=None, device_id=0, stream=None):
         self.lib = load_library()
@@ -582,6 +650,7 @@ class Engine(object):
             cfg.luong_local_window_d = att.luong_local_window_D
             cfg.luong_force_gaussian = 1 if att.luong_force_gaussian else 0
             cfg.apply_post_processing = 1 if hparams.apply_post_processing else 0
+            self.sampling_rate = int(getattr(hparams, 'sampling_rate', Engine.sampling_rate))
         self.cfg = cfg
         h = c_void_p()
         rc = self.lib.tts_create(byref(cfg), device_id, byref(h))
@@ -662,6 +731,21 @@ class Engine(object):
             raise ValueError('set_pitch: a shift in [-1, 1] octaves is needed')
         self._check(self.lib.tts_set_pitch(self.handle, o))
         self._pitch = o
+
+    def set_loudness(self, loudness, sampling_rate=None):
+        """tts_set_loudness: the handle's setting, read by every synthesize / synthesize_host call made after it.  ``loudness``:
+        None or False (off), a target in LUFS or ``(target_lufs, max_peak)``; measured at ``sampling_rate`` (None: the
+        model's)."""
+        setting = loudness_setting(None if loudness is False else loudness)
+        if setting is None:
+            self._check(self.lib.tts_set_loudness(self.handle, 0, 0.0, 1.0, 0))
+        else:
+            sr = loudness_sampling_rate('set_loudness', self.sampling_rate if sampling_rate is None else sampling_rate)
+            self._check(self.lib.tts_set_loudness(self.handle, 1, setting[0], setting[1], sr))
+        self._loudness = setting
+
+    def _loudness_scope(self, loudness):
+        return _SettingScope(self, '_loudness', self.set_loudness, loudness_setting(loudness))
 
     def _momentum_scope(self, momentum):
         return _SettingScope(self, '_gl_momentum', lambda v: self.set_option('gl_momentum', v),
@@ -1050,6 +1134,60 @@ class Engine(object):
                                             int(hi), float(threshold), out.data_ptr(), ap.data_ptr() if ap is not None else None), out, ap)
         return (out, ap) if want_aperiodicity else out
 
+    # ------------------------------------------------------------------ loudness
+    def _loudness_args(self, what, wavs, sampling_rate, n_samples):
+        sr = loudness_sampling_rate(what, sampling_rate)
+        wavs, single, B, n = _waveforms(what, wavs)
+        ns = None
+        if n_samples is not None:
+            ns = np.asarray(n_samples)
+            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+            ns = _checked_lengths(ns, n, 'n_samples', 'n')
+        return sr, wavs, single, B, n, ns
+
+    def loudness(self, wavs, sampling_rate, n_samples=None, return_mean_square=False, want_blocks=False):
+        """tts_loudness: the integrated loudness after ITU-R BS.1770-4 / EBU R 128 of ``wavs`` -- one mono waveform (n,) or a
+        batch (B, n), a host array or a device buffer -- in LUFS, a float64 host array (B,): -inf where no block passes the
+        gates (silence, or less than 400 ms), NaN where a counted block holds a non-finite sample.  ``n_samples``: B lengths
+        (host integers) -- samples at or behind them are never read; None: all n.  ``return_mean_square``: also the gated mean
+        square z the figure is taken from (LUFS = -0.691 + 10 log10 z); ``want_blocks``: also int32 (B, 2), the blocks and
+        those that passed both gates.  include/sstts_hip.h has the definition: z is the bits of tests/loudness_oracle.py."""
+        sr, wavs, _single, B, n, ns = self._loudness_args('loudness', wavs, sampling_rate, n_samples)
+        p_wav, _k = self._in(wavs, np.float32)
+        z = self.empty((B,), np.float64)
+        blocks = self.empty((B, 2), np.int32) if want_blocks else None
+        self._check_or_free(self.lib.tts_loudness(self.handle, p_wav, B, n, _int32_ptr(ns), sr, z.data_ptr(),
+                                                  blocks.data_ptr() if want_blocks else None), z, blocks)
+        z_host = z.to_host()
+        z.free()
+        out = (lufs(z_host),) + ((z_host,) if return_mean_square else ())
+        if want_blocks:
+            out += (blocks.to_host(),)
+            blocks.free()
+        return out if len(out) > 1 else out[0]
+
+    def loudness_normalize(self, wavs, sampling_rate, target_lufs=LOUDNESS_TARGET, max_peak=LOUDNESS_MAX_PEAK, n_samples=None,
+                           return_mean_square=False):
+        """tts_loudness_normalize: every utterance of ``wavs`` scaled to ``target_lufs`` by one gain, which no larger than
+        ``max_peak`` / its peak.  Returns ``(waveforms, gains)``: a device array of the input's shape -- a device input is scaled
+        in place and handed back, a host input is uploaded first -- and the float64 host array (B,) of the gains (1 where the
+        utterance is silent, shorter than a block or holds a non-finite sample in one).  ``n_samples`` as in ``loudness``:
+        samples at or behind them are neither read nor written.  ``return_mean_square``: also z as measured before the gain."""
+        sr, wavs, single, B, n, ns = self._loudness_args('loudness_normalize', wavs, sampling_rate, n_samples)
+        target, peak = loudness_target('loudness_normalize', target_lufs, max_peak)
+        fresh = not _is_device(wavs)
+        out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32)) if fresh else wavs
+        z, g = self.empty((B,), np.float64), self.empty((B,), np.float64)
+        self._check_or_free(self.lib.tts_loudness_normalize(self.handle, out.data_ptr(), B, n, _int32_ptr(ns), sr, target, peak, z.data_ptr(),
+                                                            g.data_ptr()), z, g, out if fresh else None)
+        gains, z_host = g.to_host(), z.to_host()
+        z.free()
+        g.free()
+        if fresh and single:
+            out.shape = (n,)
+        return (out, gains, z_host) if return_mean_square else (out, gains)
+
     def f0_compare(self, f0_a, f0_b, path):
         """tts_f0_compare: the F0 and voicing errors of B pairs of tracks, ``f0_a`` (B, Ta) against ``f0_b`` (B, Tb) -- side b is
         the recording -- along ``path`` (B, rows, 2) int32 as :meth:`dtw` writes it (rows with a negative entry are skipped); host
@@ -1214,8 +1352,12 @@ class Engine(object):
 
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
-                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None):
-        """``phase_init`` as in ``griffin_lim``: 'estimate' starts Griffin-Lim from phases estimated from the call's own
+                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None):
+        """``loudness``: None (the handle's setting, off unless ``set_loudness`` changed it), a target in LUFS or
+        ``(target_lufs, max_peak)`` for this call (tts_set_loudness): the call's final rows are taken to the target by
+        ``loudness_normalize`` at the model's sampling rate, each utterance over the samples its row holds, and
+        ``peak_normalize`` is not applied.
+        ``phase_init`` as in ``griffin_lim``: 'estimate' starts Griffin-Lim from phases estimated from the call's own
         magnitudes (behind the stretch, at each utterance's own length) when ``init_phase`` is None.
         ``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
         (tts_set_end_of_speech): every utterance is reconstructed from its frames up to the last one whose loudest bin is
@@ -1232,6 +1374,7 @@ class Engine(object):
         (B, F, ``pitch_frames(T, rate, pitch)``)."""
         scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
         start = self._phase_init_scope(phase_init)
+        loud = self._loudness_scope(loudness)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call = self._speaking_rate if rate.value is None else rate.value
@@ -1262,7 +1405,7 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope, eos, rate, shift, start:
+        with scope, eos, rate, shift, start, loud:
             stopping = self._end_of_speech[0]
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
@@ -1282,16 +1425,17 @@ class Engine(object):
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
-                        speaking_rate=None, pitch=None, phase_init=None):
+                        speaking_rate=None, pitch=None, phase_init=None, loudness=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
         ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
         has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1))); ``pitch`` as in
-        ``synthesize`` (no shape changes); ``phase_init`` as in ``synthesize``."""
+        ``synthesize`` (no shape changes); ``phase_init`` and ``loudness`` as in ``synthesize``."""
         scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
         start = self._phase_init_scope(phase_init)
+        loud = self._loudness_scope(loudness)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -1300,7 +1444,7 @@ class Engine(object):
         t = c_int(-1)
         r_call = self._speaking_rate if rate.value is None else rate.value
         T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, r_call, 0.0)   # (the pitch changes no shape)
-        with scope, eos, rate, shift, start:
+        with scope, eos, rate, shift, start, loud:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))

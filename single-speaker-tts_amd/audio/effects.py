@@ -10,7 +10,11 @@ argument of the synthesis calls (tts_set_speaking_rate), which stretches the mag
 Griffin-Lim.  ``pitch_shift`` (:9-43) is that time_stretch at 2 ** -octaves followed by librosa's resampler (resampy's
 'kaiser_best' windowed sinc) back to the input's length; on this path that is ``Engine.pitch_shift(wavs, sampling_rate, octaves)``
 (``Engine.time_stretch``, then ``Engine.resample``: tts_resample), and the pitch of synthesis is the ``pitch`` argument of the
-synthesis calls (tts_set_pitch), which stretches the call's magnitudes and resamples what its one Griffin-Lim made."""
+synthesis calls (tts_set_pitch), which stretches the call's magnitudes and resamples what its one Griffin-Lim made.
+
+``normalize_loudness`` has no reference counterpart (the reference's only level control is the peak normalisation of save_wav):
+one gain takes a waveform to a target integrated loudness after ITU-R BS.1770-4 (tts_loudness_normalize); the loudness of
+synthesis is the ``loudness`` argument of the synthesis calls (tts_set_loudness)."""
 import numpy as np
 
 from . import default_engine
@@ -23,6 +27,18 @@ def pitch_shift(wav, sampling_rate, octaves):
 
 def time_stretch(wav, rate):
     raise NotImplementedError('time_stretch (librosa phase vocoder, reference audio/effects.py:46-88) is out of scope')
+
+
+def normalize_loudness(wav, sampling_rate, target_lufs=-23.0, max_peak=1.0, engine=None):
+    """``wav`` -- one mono waveform (n,) or a batch (B, n) -- scaled to ``target_lufs`` of integrated loudness (ITU-R BS.1770-4),
+    each utterance by one gain that leaves no sample beyond ``max_peak`` (``Engine.loudness_normalize``).  A waveform that is
+    silent, shorter than 400 ms or holds a non-finite sample in a counted block comes back as it is.  Returns a float32 host
+    array of the input's shape."""
+    eng = engine or default_engine()
+    out, _gains = eng.loudness_normalize(np.asarray(wav, dtype=np.float32), sampling_rate, target_lufs, max_peak)
+    host = out.to_host()
+    out.free()
+    return host
 
 
 def trim_silence(wav, threshold_db=40, ref=np.max, engine=None):

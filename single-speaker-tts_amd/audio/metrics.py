@@ -3,7 +3,7 @@ measure is the frame-by-frame L1 loss of ``tacotron.evaluate``, which measures t
 speaks a little faster or slower than the recording.  Mel-cepstral distortion along a dynamic-time-warping path compares the
 spectra at the frames that belong together.  The cepstra (tts_mfcc) and the alignment (tts_dtw) run on the device.  Along the
 same path, F0 RMSE, voicing error and gross pitch error compare the prosody (tts_f0, tts_f0_compare), which the cepstra do not
-see."""
+see.  ``integrated_loudness`` is the level of a waveform as a listener hears it: ITU-R BS.1770-4 / EBU R 128 (tts_loudness)."""
 import math
 
 import numpy as np
@@ -12,6 +12,17 @@ from . import default_engine
 from ..tacotron.params import LJSpeechConstants
 
 MCD_COEFFS = 13
+
+
+def integrated_loudness(wav, sampling_rate, engine=None):
+    """The integrated loudness of one mono waveform (n,) -- or of every row of a batch (B, n) -- in LUFS after ITU-R BS.1770-4 /
+    EBU R 128: K-weighting, 400 ms blocks every 100 ms, the absolute gate at -70 LUFS and the relative gate 10 LU under the mean
+    of what passed it (``Engine.loudness``).  A float for one waveform, a float64 array (B,) for a batch: -inf for silence or
+    less than 400 ms of signal, NaN where a counted block holds a non-finite sample."""
+    eng = engine or default_engine()
+    wav = wav if hasattr(wav, 'data_ptr') and not isinstance(wav, np.ndarray) else np.asarray(wav, dtype=np.float32)
+    out = eng.loudness(wav, sampling_rate)
+    return float(out[0]) if len(wav.shape) == 1 else out
 
 
 def mcd_scale(ref_db, max_db):

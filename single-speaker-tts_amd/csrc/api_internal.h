@@ -55,7 +55,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -421,6 +421,14 @@ struct tts_handle_s {
     // pitch (tts_set_pitch), in octaves: read when a call is made; 0 = off, the call then enqueues what it always did
     double pitch_octaves = 0.0;
 
+    // loudness (tts_set_loudness): read when a call is made; off = the call then enqueues what it always did
+    struct {
+        bool enabled = false;
+        double target_lufs = -23.0;
+        double max_peak = 1.0;
+        int sampling_rate = 0;
+    } loud;
+
     // the per-utterance lengths of the last tts_synthesize call (synth_plan.h): Griffin-Lim and the resampler are given them
     SynthLengths syn_lens;
 
@@ -561,6 +569,11 @@ int stretch_impl(tts_handle_t h, const float* in, int B, int T, int F, int row_s
 // the resampler (resample.hip): arguments checked by the caller (resample_plan.h).  resample_table makes a ratio's table ahead
 // of a call that must not allocate once it has begun to enqueue
 int resample_table(tts_handle_t h, double rho, const double** tab);
+// loudness (loudness.hip): arguments checked by the caller (loudness_plan.h).  loudness_workspace sizes the buffers ahead of a
+// call that must not allocate once it has begun to enqueue
+int loudness_workspace(tts_handle_t h, int B, int N, int sr);
+int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, int sr, bool normalize, double target_lufs, double max_peak,
+                  double* mean_square, int32_t* n_blocks, double* gain);
 int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double rho, int N_out, const int32_t* keep_cap,
                   float* out);
 void resample_release(tts_handle_t h);

@@ -69,6 +69,11 @@ struct SynthCall {
     SynthShape shape;
     float* mags = nullptr;         // the time-stretch of `magi`, shape.Tg rows: what Griffin-Lim reconstructs from
     float* gl_wav = nullptr;       // a shifted call: Griffin-Lim's hop (Tg - 1) samples, which the resampler takes into `wav`
+    // loudness (tts_set_loudness), as the handle's setting stood when the call was made: the call's final rows are taken to the
+    // target instead of being peak-normalised
+    bool loud = false;
+    double loud_target = 0.0, loud_max_peak = 1.0;
+    int loud_sr = 0;
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -146,6 +151,10 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     if (k.shape.pitch) {
         WS(h, "gl.wav_pitch", float, (size_t)B * sp->hop_length * (size_t)(Tg - 1), glw);
         k.gl_wav = glw;
+    }
+    if (k.loud) {   // (the measurement's states and sums, for rows of hop (Tw - 1) samples)
+        const int rc = loudness_workspace(h, B, sp->hop_length * (k.shape.Tw - 1), k.loud_sr);
+        if (rc) return rc;
     }
     // (estimated initial phases, option "gl_init": the estimate's buffers, for the frames Griffin-Lim reconstructs from)
     if (h->gl_init && !k.init_phase) {
@@ -426,7 +435,8 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, L.T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
     float* gl_wav = s.pitch ? k.gl_wav : k.wav;
-    const bool gl_peak = sp->peak_normalize != 0 && !s.pitch;   // (a shifted call normalises what the resampler leaves)
+    // (a shifted call normalises what the resampler leaves; with a loudness target nothing is peak-normalised)
+    const bool gl_peak = sp->peak_normalize != 0 && !s.pitch && !k.loud;
     if (k.gl_streaming)
         rc = gl_run(h, gl_mag, init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
                     gl_peak, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
@@ -438,7 +448,16 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
         // end-of-speech stopping utterance b has hop (n'[b] - 1) samples, and its row ends where the un-shifted call's does.
         const int n_gl = sp->hop_length * (Tg - 1), N_out = sp->hop_length * (s.Tw - 1);
         rc = resample_impl(h, k.gl_wav, B, n_gl, detected ? L.n_samples.data() : nullptr, s.rho, N_out, detected ? L.keep.data() : nullptr, k.wav);
-        if (!rc && sp->peak_normalize) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
+        if (!rc && sp->peak_normalize && !k.loud) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
+    }
+    if (k.loud && !rc) {
+        // The loudness target: every utterance is measured over the samples its row holds -- hop (n[b] - 1) of the reported
+        // lengths with end-of-speech stopping, all of the row otherwise -- and scaled in place, behind whatever made the row.
+        std::vector<int32_t> held;
+        if (detected)
+            for (int b = 0; b < B; ++b) held.push_back(sp->hop_length * (L.reported[(size_t)b] - 1));
+        rc = loudness_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.loud_sr, true, k.loud_target,
+                           k.loud_max_peak, nullptr, nullptr, nullptr);
     }
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
@@ -470,6 +489,14 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
         k.eos_keep = h->eos.keep_frames;
         if (speech_threshold(h->eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
             return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
+    }
+    if (h->loud.enabled) {
+        k.loud = true;
+        k.loud_target = h->loud.target_lufs;
+        k.loud_max_peak = h->loud.max_peak;
+        k.loud_sr = h->loud.sampling_rate;
+        if (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX)
+            return fail(h, TTS_ERR_INVALID, "synthesize: a loudness target needs rows of 1 .. 2^31 - 1 samples");
     }
     if ((rc = synth_workspaces(h, k))) return rc;
     if (k.pipelined && (rc = synth_streams(h))) return rc;

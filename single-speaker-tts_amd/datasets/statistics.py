@@ -5,7 +5,8 @@ window 1024, 80 HTK mel bands over 0 .. sr // 2); the per-file min / max are tak
 
 ``collect_reconstruction_error`` is the reference's :146-187 -- |STFT| of every recording followed by Griffin-Lim, the mean
 of the last iteration's mse -- as ragged batches: one tts_griffin_lim_ragged call reconstructs ``batch_size`` recordings of
-different lengths.  The duration statistics and the plots of the reference module (:101-143, :190-258) are out of scope."""
+different lengths.  ``collect_loudness`` has no reference counterpart: the integrated loudness (ITU-R BS.1770-4, tts_loudness)
+of every recording and its spread over the corpus, which the dB statistics do not show.  The duration statistics and the plots of the reference module (:101-143, :190-258) are out of scope."""
 import numpy as np
 
 from ..audio import default_engine
@@ -45,6 +46,31 @@ def collect_decibel_statistics(path_listing, batch_size=32, engine=None):
                 stats += _stats(mel_db, lin_db)
     stats /= len(paths)
     return stats
+
+
+def collect_loudness(path_listing, batch_size=32, engine=None):
+    """The integrated loudness of every recording, ``batch_size`` files at a time: those of one sampling rate are measured in
+    ONE ragged ``Engine.loudness`` call, so the padding is neither read nor able to change a result.  Returns a dict: ``lufs``,
+    float64 (files,) in the order of the listing (-inf: silent or shorter than 400 ms), and ``min`` / ``max`` / ``mean`` /
+    ``std`` in LUFS over the recordings with a finite figure (NaN when there is none), ``measured`` their count."""
+    eng = engine or default_engine()
+    paths = [p.decode() if isinstance(p, bytes) else p for p in path_listing]
+    lufs = np.full(len(paths), np.nan)
+    step = max(1, int(batch_size))
+    for i in range(0, len(paths), step):
+        loaded = [load_wav(p) for p in paths[i:i + step]]
+        for sr in sorted({r for _, r in loaded}):
+            group = [k for k, (_, r) in enumerate(loaded) if r == sr]
+            lens = np.array([len(loaded[k][0]) for k in group], dtype=np.int32)
+            rows = np.zeros((len(group), int(lens.max())), dtype=np.float32)
+            for row, k in enumerate(group):
+                rows[row, :lens[row]] = np.asarray(loaded[k][0], dtype=np.float32)
+            lufs[[i + k for k in group]] = eng.loudness(rows, int(sr), n_samples=lens)
+    finite = lufs[np.isfinite(lufs)]
+    nan = float('nan')
+    return dict(lufs=lufs, measured=int(finite.size), min=float(finite.min()) if finite.size else nan,
+                max=float(finite.max()) if finite.size else nan, mean=float(finite.mean()) if finite.size else nan,
+                std=float(finite.std()) if finite.size else nan)
 
 
 RECONSTRUCTION_N_FFT = 2048      # reference :149

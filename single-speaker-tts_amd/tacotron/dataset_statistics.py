@@ -3,15 +3,17 @@ constants of the feature normalisation (datasets.statistics.collect_decibel_stat
 names -- which it crosses: the mean max mel dB is printed as ``mel_mag_ref_db``, the mean min as ``mel_mag_max_db``, and
 likewise for the linear constants.
 
-    python -m single-speaker-tts_amd.tacotron.dataset_statistics [--dataset-folder DIR] [--reconstruction-iters N]
+    python -m single-speaker-tts_amd.tacotron.dataset_statistics [--dataset-folder DIR] [--reconstruction-iters N] [--loudness]
 
 ``--reconstruction-iters N`` adds the reference's Griffin-Lim reconstruction error after N iterations
-(datasets.statistics.collect_reconstruction_error) behind the dB statistics; without it the output is what it was."""
+(datasets.statistics.collect_reconstruction_error) behind the dB statistics; ``--loudness`` adds the corpus's integrated
+loudness after ITU-R BS.1770-4 (datasets.statistics.collect_loudness: min / max / mean / standard deviation in LUFS) behind
+those.  Without the switches the output is what it was."""
 import argparse
 import os
 
 from ..datasets.lj_speech import LJSpeechDatasetHelper
-from ..datasets.statistics import collect_decibel_statistics, collect_reconstruction_error
+from ..datasets.statistics import collect_decibel_statistics, collect_loudness, collect_reconstruction_error
 from .params import dataset_params
 
 
@@ -20,6 +22,8 @@ def main(argv=None):
     ap.add_argument('--dataset-folder', default=dataset_params.dataset_folder)
     ap.add_argument('--reconstruction-iters', type=int, default=None, metavar='N',
                     help='also print the mean Griffin-Lim reconstruction error after N iterations')
+    ap.add_argument('--loudness', action='store_true',
+                    help='also print the integrated loudness (ITU-R BS.1770-4) of the recordings: min / max / mean / std in LUFS')
     args = ap.parse_args(argv)
     if args.reconstruction_iters is not None and args.reconstruction_iters < 1:
         ap.error('--reconstruction-iters: at least one iteration')
@@ -46,6 +50,14 @@ def main(argv=None):
     print('linear_mag_max_db = ', min_linear_db)
     if args.reconstruction_iters is not None:
         collect_reconstruction_error(paths, args.reconstruction_iters)
+    if args.loudness:
+        print('Collecting loudness statistics for {} files ...'.format(len(paths)))
+        loud = collect_loudness(paths)
+        print('loudness_lufs_min = ', loud['min'])
+        print('loudness_lufs_max = ', loud['max'])
+        print('loudness_lufs_mean = ', loud['mean'])
+        print('loudness_lufs_std = ', loud['std'])
+        print('loudness_measured = {} of {}'.format(loud['measured'], len(paths)))
     return 0
 
 

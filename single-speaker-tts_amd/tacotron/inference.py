@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .._hip import (momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value, silence_keep_frames, speaking_rate_value,
+from .._hip import (LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value, silence_keep_frames, speaking_rate_value,
                     stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
@@ -74,7 +74,7 @@ def cut_waveforms(wavs, n_frames, hop):
 
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
                      momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                     phase_init='random'):
+                     phase_init='random', loudness=None):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind
@@ -86,9 +86,12 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     and the resampler takes Griffin-Lim's samples back); the waveforms keep the shape they have without it, ``init_phase`` is
     (B, F, ceil(T / (rate * 2 ** -pitch))).  ``phase_init``: 'random' (the reference's start, from ``seed``), 'estimate'
     (Griffin-Lim starts from phases estimated from the call's magnitudes, audio.synthesis; far fewer iterations are then
-    needed) or None (the engine's ``gl_init`` option); ``init_phase`` wins."""
+    needed) or None (the engine's ``gl_init`` option); ``init_phase`` wins.  ``loudness``: None, a target in LUFS or
+    ``(target_lufs, max_peak)`` -- every utterance is taken to that integrated loudness (ITU-R BS.1770-4, measured over the
+    samples it holds) on the device instead of being peak-normalised."""
     momentum_thousandths(momentum)   # ValueError outside [0, 1), before the engine is touched
     phase_init_value(phase_init)
+    loud = loudness_setting(loudness)
     rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
     hp = model.hparams
@@ -101,7 +104,7 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
                                   init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum,
-                                  stop_at_silence=stop, speaking_rate=rate, pitch=octaves, phase_init=phase_init)
+                                  stop_at_silence=stop, speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud)
     if stop is not None:
         return cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop)
     return out['wav'].to_host()
@@ -109,7 +112,7 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
                       want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
-                      speaking_rate=1.0, pitch=0.0, phase_init='random'):
+                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -122,9 +125,10 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db`` / ``silence_keep_ms`` as in ``synthesize_batch``: the waveforms of a batch are then a list of B
     arrays (views of the pinned rows unless ``copy``), each cut to its own length.  ``speaking_rate`` as in
-    ``synthesize_batch``, ``pitch`` and ``phase_init`` likewise."""
+    ``synthesize_batch``, ``pitch``, ``phase_init`` and ``loudness`` likewise."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before the engine is touched)
     phase_init_value(phase_init)
+    loud = loudness_setting(loudness)
     rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
     hp = model.hparams
@@ -156,7 +160,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
                                            want_alignments=want_alignments, momentum=momentum, stop_at_silence=stop,
-                                           speaking_rate=rate, pitch=octaves, phase_init=phase_init))
+                                           speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -189,16 +193,18 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
 
 def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
                          stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                         phase_init='random'):
+                         phase_init='random', loudness=None):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
     float32 WAV, save_wav(norm=True)).  Returns the list of waveforms.  With ``stop_at_silence_db`` every file ends
     ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames.
     ``speaking_rate``: as in ``synthesize_batch`` (1.2: a fifth faster); ``pitch``: likewise, in octaves (4 / 12: four semitones up);
-    ``phase_init``: likewise ('estimate': estimated start phases)."""
+    ``phase_init``: likewise ('estimate': estimated start phases); ``loudness``: likewise -- the files then hold the waveforms at
+    that loudness, not peak-normalised."""
     momentum_thousandths(momentum)
     phase_init_value(phase_init)
+    loud = loudness_setting(loudness)
     stop_setting(model_params, stop_at_silence_db, silence_keep_ms)   # (ValueError before anything is loaded)
     speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     pitch_octaves_value(0.0 if pitch is None else pitch)
@@ -215,9 +221,9 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
     wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum,
                             stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                            pitch=pitch, phase_init=phase_init)
+                            pitch=pitch, phase_init=phase_init, loudness=loud)
     for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, True)
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, loud is None)
     return list(wavs)
 
 
@@ -241,6 +247,7 @@ def main(argv=None):
                                                             [--stop-at-silence DB [--silence-keep-ms MS]]
                                                             [--rate R] [--pitch SEMITONES]
                                                             [--phase-init random|estimate]
+                                                            [--loudness LUFS [--max-peak P]]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
@@ -249,8 +256,11 @@ def main(argv=None):
     (de-normalised dB, e.g. -40) instead of after the full max_iterations frames: files of different lengths.
     ``--rate R``: the speaking rate, 0.25 .. 4 (1.2: a fifth faster; default 1 = as the network speaks).
     ``--pitch SEMITONES``: the pitch, -12 .. 12 semitones (4: a major third up; default 0 = as the network speaks).
-    ``--phase-init estimate``: Griffin-Lim starts from phases estimated from the magnitudes instead of random ones."""
+    ``--phase-init estimate``: Griffin-Lim starts from phases estimated from the magnitudes instead of random ones.
+    ``--loudness LUFS``: every wav is taken to that integrated loudness (ITU-R BS.1770-4; -23: EBU R 128, -16: a common
+    streaming level) with no sample beyond ``--max-peak`` (default 1), instead of being peak-normalised."""
     args = parse_args(argv)
+    loud = None if args.loudness is None else loudness_setting((args.loudness, args.max_peak))
     momentum_thousandths(args.momentum)
     phase_init_value(args.phase_init)
     stop_setting(model_params, args.stop_at_silence, args.silence_keep_ms)
@@ -274,7 +284,7 @@ def main(argv=None):
     wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
                                 momentum=args.momentum, stop_at_silence_db=args.stop_at_silence,
                                 silence_keep_ms=args.silence_keep_ms, speaking_rate=args.rate, pitch=octaves,
-                                phase_init=args.phase_init)
+                                phase_init=args.phase_init, loudness=loud)
     for i in range(len(wavs)):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
@@ -302,6 +312,10 @@ def parse_args(argv=None):
                     help='pitch shift in [-12, 12] semitones: the magnitudes are stretched and Griffin-Lim\'s samples resampled (default 0)')
     ap.add_argument('--phase-init', default='random', metavar='START',
                     help="Griffin-Lim's start phases: 'random' (default, the reference's) or 'estimate' (tracked from the magnitudes' peaks)")
+    ap.add_argument('--loudness', type=float, default=None, metavar='LUFS',
+                    help='integrated loudness (ITU-R BS.1770-4) every wav is taken to, e.g. -23; default: peak normalisation')
+    ap.add_argument('--max-peak', type=float, default=LOUDNESS_MAX_PEAK, metavar='P',
+                    help='with --loudness: the largest |sample| the gain may produce (default {:g})'.format(LOUDNESS_MAX_PEAK))
     return ap.parse_args(argv)
 
 

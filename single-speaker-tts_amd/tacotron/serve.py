@@ -8,7 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import momentum_thousandths, phase_init_value, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
+from .._hip import loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
 from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_sentence, stop_setting
 from .model import Mode, Tacotron
@@ -24,7 +24,8 @@ def pre_process_sentences(_sentences, dataset):
 
 
 def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0, stop_at_silence_db=None,
-                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random'):
+                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random',
+                              loudness=None):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
     constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86); ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: every utterance is reconstructed only up to
@@ -35,9 +36,11 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
     shift in [-1, 1] octaves -- the magnitudes are stretched by rate * 2 ** -pitch instead (``init_phase`` has that many
     frames) and ``Engine.resample`` takes Griffin-Lim's samples by 2 ** -pitch back to the lengths they have without it.
     ``phase_init``: 'random', 'estimate' (start phases estimated from the magnitudes Griffin-Lim runs on) or None (the
-    engine's option), as in ``audio.synthesis``."""
+    engine's option), as in ``audio.synthesis``.  ``loudness``: None, a target in LUFS or ``(target_lufs, max_peak)`` --
+    ``Engine.loudness_normalize`` takes every waveform there, measured over its own samples."""
     momentum_thousandths(momentum)
     phase_init_value(phase_init)
+    loud = loudness_setting(loudness)
     stop = stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
     rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
@@ -78,6 +81,9 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
             wav = engine.resample(gl_wav, rho, n_samples=None if n_gl is None else win_hop * (n_gl - 1), N_out=win_hop * (T_s - 1))
         finally:
             gl_wav.free()   # (tts_free waits for the device: the resampling that reads it has run)
+    if loud is not None:
+        engine.loudness_normalize(wav, model_params.sampling_rate, loud[0], loud[1],
+                                  n_samples=None if n_frames is None else win_hop * (np.asarray(n_frames, dtype=np.int32) - 1))
     wav = wav.to_host()
     if n_frames is not None:
         return cut_waveforms(wav, n_frames, win_hop)
@@ -85,7 +91,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
-          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random'):
+          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -96,9 +102,11 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     generator ends), which on a request-driven generator would hold every answer back by two requests.
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db`` /
     ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech;
-    ``speaking_rate``, ``pitch`` and ``phase_init`` likewise."""
+    ``speaking_rate``, ``pitch``, ``phase_init`` and ``loudness`` likewise: with a loudness every answer of the stream comes at
+    the same level."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
     phase_init_value(phase_init)
+    loud = loudness_setting(loudness)
     stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
     speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
     pitch_octaves_value(0.0 if pitch is None else pitch)
@@ -112,12 +120,12 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
             spectrograms = model.run(model.output_linear_spec, {model.inp_sentences: ids})
             yield post_process_spectrograms(spectrograms, model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
                                             silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch,
-                                            phase_init=phase_init)
+                                            phase_init=phase_init, loudness=loud)
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
     for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
                                   stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                                  pitch=pitch, phase_init=phase_init):
+                                  pitch=pitch, phase_init=phase_init, loudness=loud):
         yield [wavs[b] for b in range(len(wavs))]

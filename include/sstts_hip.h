@@ -646,6 +646,52 @@ int tts_loudness_filter(int sampling_rate, double coeffs[10]);
 /* Host only: the samples c of a segment at this sampling rate, ceil((sampling_rate / 10) / 8); 0 outside 8000 .. 192000. */
 int tts_loudness_segment(int sampling_rate);
 
+/* ---- attention diagnostics: alignment statistics ------------------------------------------- */
+/* What the decoder's alignments say about whether the sentence was read (no reference counterpart: the reference plots its
+ * alignments, tacotron/model.py:552-598, and judges them by eye).  alignments DEVICE [n_steps_max][B][Ts] as the decoder
+ * writes them.  For utterance b let S = n_steps[b], N = n_sent[b] and row_s = alignments[s][b][0 .. Ts) for s < S; all
+ * comparisons are on the float32 values:
+ *   pos[s]   = np.argmax(row_s[:N]): the lowest index of the maximum; if the slice holds a NaN, the index of the first NaN
+ *   peak[s]  = row_s[pos[s]], the bits of that element (NaN where the argmax is a NaN)
+ *   off[s]   = 1 if np.argmax(row_s[:Ts]) >= N (the whole padded row, the same NaN rule), else 0: the strongest weight of
+ *              the step lies on padding
+ *   end_step = the smallest s with pos[s] == N - 1, or -1;  E = end_step if it is >= 0, else S - 1: the spoken part is 0 .. E
+ *   d[s]     = pos[s] - pos[s-1] for 1 <= s <= E
+ *   durations[b][j] = #{s < S : pos[s] == j} for j < N, 0 for N <= j < Ts
+ * and the record of the utterance, 56 bytes: */
+typedef struct tts_alignment_stats {
+    int32_t n_sent, n_steps;   /* N and S, as used */
+    int32_t reached;           /* max_s pos[s] over s < S */
+    int32_t end_step;          /* as above */
+    int32_t backward;          /* #{s : d[s] < 0} */
+    int32_t max_back;          /* max(0, max_s -d[s]) */
+    int32_t max_jump;          /* max(0, max_s d[s]) */
+    int32_t longest_stall;     /* the longest run of equal consecutive pos[s] within 0 .. E (1 when E == 0) */
+    int32_t after_end;         /* #{s > end_step : pos[s] != N - 1}; 0 when end_step == -1 */
+    int32_t off_text;          /* sum_s off[s] over s < S */
+    int32_t skipped;           /* #{j < reached : durations[j] == 0} */
+    int32_t reserved;          /* 0 */
+    double focus_sum;          /* ((peak[0] + peak[1]) + peak[2]) + ... in ascending s, every addition an individually rounded
+                                  IEEE double addition; NaN propagates.  Mean focus = focus_sum / S is the caller's to take. */
+} tts_alignment_stats_t;
+/* Everything but focus_sum is an integer and focus_sum has a fixed order: the record is the same bits whatever B is, wherever
+ * the utterance sits in the batch and however the library cuts the work (the bits of tests/alignment_oracle.py); a NaN in one
+ * utterance touches no other.  Columns at or behind n_sent[b] are read for off alone; steps at or behind n_steps[b] are never
+ * read.  n_sent: HOST int32 [B] or NULL (all Ts); n_steps: HOST int32 [B] or NULL (all n_steps_max) -- the lengths travel in
+ * the launches, nothing is uploaded.  stats DEVICE [B]; durations DEVICE int32 [B][Ts] or NULL; pos DEVICE int32
+ * [B][n_steps_max] or NULL, -1 behind n_steps[b]; peak DEVICE float [B][n_steps_max] or NULL, 0 behind n_steps[b].
+ * No model needs to be loaded.  Asynchronous on the handle's stream (2 launches per 64 utterances); profile stage "alignment".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL alignments or stats, B, Ts or n_steps_max < 1, an n_sent[b] outside
+ * 1 .. Ts, an n_steps[b] outside 1 .. n_steps_max, a misaligned buffer (stats: 8 bytes, the others: 4). */
+int tts_alignment_stats(tts_handle_t h, const float* alignments, int n_steps_max, int B, int Ts,
+                        const int32_t* n_sent /* HOST [B] or NULL = Ts */, const int32_t* n_steps /* HOST [B] or NULL = n_steps_max */,
+                        tts_alignment_stats_t* stats /* DEVICE [B] */, int32_t* durations /* DEVICE [B][Ts] or NULL */,
+                        int32_t* pos /* DEVICE [B][n_steps_max] or NULL */, float* peak /* DEVICE [B][n_steps_max] or NULL */);
+/* The sentence lengths of padded ids: n_sent[b] = 1 + the largest j with ids[b][j] != pad_id, 1 when the whole row is padding.
+ * ids DEVICE int32 [B][Ts], n_sent DEVICE int32 [B].  Asynchronous on the handle's stream (1 launch); profile stage
+ * "alignment".  TTS_ERR_INVALID: a NULL or misaligned pointer, B or Ts < 1. */
+int tts_text_lengths(tts_handle_t h, const int32_t* ids /* DEVICE [B][Ts] */, int B, int Ts, int pad_id, int32_t* n_sent /* DEVICE [B] */);
+
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,
  * optional peak normalisation; replaces tacotron/inference.py:162-200 minus file IO.
@@ -760,6 +806,25 @@ int tts_set_pitch(tts_handle_t h, double octaves);
  * not finite, a max_peak that is not finite and positive) and on TTS_ERR_UNSUPPORTED (a sampling rate outside 8000 .. 192000). */
 int tts_set_loudness(tts_handle_t h, int enabled, double target_lufs, double max_peak, int sampling_rate);
 
+/* Attention diagnostics of synthesis: the alignment statistics of every call (tts_alignment_stats).  A setting of the HANDLE,
+ * off by default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
+ * tts_synthesize and tts_synthesize_host run tts_text_lengths(pad_id) on the call's device ids behind its encoder and
+ * tts_alignment_stats (n_steps[b] = p->n_steps for every b, the sentence lengths read from device memory) right behind the
+ * call's decoder, on the stream the decoder ran on: no host wait, and nothing changes in what runs beside what.  A call made
+ * with alignments == NULL writes them to a buffer of the handle's.  The record is the bits of tts_alignment_stats on the call's
+ * alignments output with n_sent taken from the ids on the host; waveform, mel, alignments and linear keep the bits of the call
+ * with the setting off.  The first call after the setting was switched on is not pipelined (its buffers are new).
+ * TTS_ERR_INVALID: a NULL handle. */
+int tts_set_alignment_stats(tts_handle_t h, int enabled, int pad_id);
+/* The records of the last tts_synthesize / tts_synthesize_host call made on the handle: stats_host, HOST [B].  Waits on the
+ * host until that call's decoder and statistics have run (not for its Griffin-Lim), then copies.  TTS_ERR_INVALID: a NULL
+ * pointer, a B other than that call's, or no call has been made with the setting on (the last call was made with it off). */
+int tts_synth_alignment_stats(tts_handle_t h, tts_alignment_stats_t* stats_host, int B);
+/* The records of a tts_synthesize_host call: they are downloaded with the waveforms (B x 56 bytes) and rotate with the three
+ * buffer sets.  Waits as tts_wait_host does (same ticket rules, same reports), then hands out pinned memory of the handle,
+ * valid as long as the ticket's waveform buffer.  TTS_ERR_INVALID also for a ticket whose call was made with the setting off. */
+int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignment_stats_t** stats, int* B);
+
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
@@ -768,7 +833,8 @@ int tts_set_loudness(tts_handle_t h, int enabled, double target_lufs, double max
  * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
  * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
  * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare), "loudness" (tts_loudness, tts_loudness_normalize, stand-alone
- * or inside a tts_synthesize call with a loudness target).
+ * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, stand-alone or
+ * inside a tts_synthesize call with tts_set_alignment_stats on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

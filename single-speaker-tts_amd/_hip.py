@@ -67,7 +67,23 @@ class TtsFeatureParams(ctypes.Structure):
     ]
 
 
+class TtsAlignmentStats(ctypes.Structure):
+    """struct tts_alignment_stats (include/sstts_hip.h): twelve int32 and a double, 56 bytes."""
+    _fields_ = [(name, c_int32) for name in ('n_sent', 'n_steps', 'reached', 'end_step', 'backward', 'max_back', 'max_jump',
+                                             'longest_stall', 'after_end', 'off_text', 'skipped', 'reserved')] + [('focus_sum', ctypes.c_double)]
+
+
+# ... and the same record as a numpy dtype: what Engine.alignment_stats returns an array of
+ALIGNMENT_RECORD = np.dtype([(name, np.int32) for name, _t in TtsAlignmentStats._fields_[:12]] + [('focus_sum', np.float64)])
+
+
 _PROTOTYPES = {
+    'tts_alignment_stats': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    'tts_text_lengths': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'tts_set_alignment_stats': (c_int, [c_void_p, c_int, c_int]),
+    'tts_synth_alignment_stats': (c_int, [c_void_p, c_void_p, c_int]),
+    'tts_wait_host_alignment_stats': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
     'tts_version': (c_char_p, []),
     'tts_default_config': (c_int, [POINTER(TtsConfig)]),
     'tts_create': (c_int, [POINTER(TtsConfig), c_int, POINTER(c_void_p)]),
@@ -480,6 +496,33 @@ def loudness_filter(sampling_rate):
     return np.array(out[:], dtype=np.float64)
 
 
+def alignment_stats_setting(alignment_stats):
+    """``alignment_stats`` of the synthesis calls -- None (the handle's setting as it stands), False (off), True (on, pad id 0)
+    or ``(enabled, pad_id)`` -- as None or a checked tuple ``(enabled, pad_id)``.  ValueError, raised before a handle is touched,
+    for anything else: a bare number is neither a switch nor a pad id."""
+    if alignment_stats is None:
+        return None
+    if isinstance(alignment_stats, (bool, np.bool_)):
+        return (bool(alignment_stats), 0)
+    if isinstance(alignment_stats, (tuple, list)) and len(alignment_stats) == 2:
+        enabled, pad_id = alignment_stats
+        if (isinstance(enabled, (bool, np.bool_)) and isinstance(pad_id, (int, np.integer)) and not isinstance(pad_id, (bool, np.bool_))
+                and -2 ** 31 <= int(pad_id) < 2 ** 31):
+            return (bool(enabled), int(pad_id))
+    raise ValueError('alignment_stats must be None, a bool or (enabled, pad_id), got {!r}'.format(alignment_stats))
+
+
+def alignment_lengths(lengths, B, hi, name, bound):
+    """the ``n_sent`` / ``n_steps`` argument of an alignment_stats call as None or a contiguous int32 array of B lengths in
+    1 .. ``hi``, checked as tts_alignment_stats checks them -- ValueError, raised before a handle is touched"""
+    if lengths is None:
+        return None
+    n = np.asarray(lengths)
+    if n.shape != (B,) or n.dtype.kind not in 'iu':
+        raise ValueError('{}: {} integers are needed, got shape {} of {}'.format(name, B, n.shape, n.dtype))
+    return _checked_lengths(n, hi, name, bound)
+
+
 def stretch_frame_counts(n_frames, B, T):
     """The ``n_frames`` argument of a stretch call as a contiguous int32 array of B lengths in 1 .. T (None stays None: all
     T), checked as tts_stretch_magnitudes checks them -- ValueError, raised before a handle is touched."""
@@ -615,6 +658,7 @@ class Engine(object):
 
     _gl_init = 0   # the handle's "gl_init" option (the C ABI has no getter: set_option keeps it)
     _loudness = None   # ... and its loudness setting, None (off) or (target_lufs, max_peak) (set_loudness keeps it)
+    _alignment_stats = (False, 0)   # ... and its attention diagnostics, (enabled, pad_id) (set_alignment_stats keeps them)
     sampling_rate = 22050   # the model's (hparams.sampling_rate): what a loudness target of the synthesis calls is measured at
 
     def __init__(self, hparams=None, device_id=0, stream=None):
@@ -743,6 +787,18 @@ class Engine(object):
             sr = loudness_sampling_rate('set_loudness', self.sampling_rate if sampling_rate is None else sampling_rate)
             self._check(self.lib.tts_set_loudness(self.handle, 1, setting[0], setting[1], sr))
         self._loudness = setting
+
+    def set_alignment_stats(self, enabled, pad_id=0):
+        """tts_set_alignment_stats: the handle's setting, read by every synthesize / synthesize_host call made after it.  On,
+        every call also reduces its alignments to one record per utterance (``alignment_stats``), the sentence lengths taken
+        from its ids with ``pad_id`` as the padding (``text_lengths``): ``synth_alignment_stats`` /
+        ``wait_host_alignment_stats`` fetch them."""
+        setting = alignment_stats_setting((bool(enabled), pad_id))
+        self._check(self.lib.tts_set_alignment_stats(self.handle, 1 if setting[0] else 0, setting[1]))
+        self._alignment_stats = setting
+
+    def _alignment_stats_scope(self, alignment_stats):
+        return _SettingScope(self, '_alignment_stats', lambda v: self.set_alignment_stats(*v), alignment_stats_setting(alignment_stats))
 
     def _loudness_scope(self, loudness):
         return _SettingScope(self, '_loudness', self.set_loudness, loudness_setting(loudness))
@@ -1188,6 +1244,71 @@ class Engine(object):
             out.shape = (n,)
         return (out, gains, z_host) if return_mean_square else (out, gains)
 
+    # ------------------------------------------------------------------ attention diagnostics
+    def alignment_stats(self, alignments, n_sent=None, n_steps=None, want_durations=False, want_pos=False):
+        """tts_alignment_stats: what an alignment history says about whether the sentence was read.  ``alignments``
+        (n_steps_max, B, Ts) float32 as the decoder writes them, a host array or a device buffer; ``n_sent``: B sentence lengths
+        (host integers, None: all Ts) -- columns at or behind them count as padding; ``n_steps``: B step counts (None: all
+        n_steps_max) -- steps at or behind them are never read.  Returns a host array (B,) of ``ALIGNMENT_RECORD`` -- n_sent,
+        n_steps, reached, end_step, backward, max_back, max_jump, longest_stall, after_end, off_text, skipped, reserved and
+        focus_sum (mean focus = focus_sum / n_steps) -- then, with ``want_durations``, the int32 host array (B, Ts) of the
+        steps spent on every token, and with ``want_pos`` the positions int32 (B, n_steps_max) (-1 behind an utterance's steps)
+        and their weights float32 (B, n_steps_max) (0 there).  include/sstts_hip.h has the definition: the records are the bits
+        of tests/alignment_oracle.py.  ``tacotron.attention_check.verdict`` turns them into flags."""
+        shape = tuple(int(d) for d in alignments.shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError('alignment_stats: alignments (n_steps_max, B, Ts) are needed, got shape {}'.format(shape))
+        S, B, Ts = shape
+        ns = alignment_lengths(n_sent, B, Ts, 'n_sent', 'Ts')
+        nt = alignment_lengths(n_steps, B, S, 'n_steps', 'n_steps_max')
+        p_ali, _k = self._in(alignments, np.float32)
+        stats = self.empty((B,), ALIGNMENT_RECORD)
+        dur = self.empty((B, Ts), np.int32) if want_durations else None
+        pos = self.empty((B, S), np.int32) if want_pos else None
+        peak = self.empty((B, S), np.float32) if want_pos else None
+        self._check_or_free(self.lib.tts_alignment_stats(self.handle, p_ali, S, B, Ts, _int32_ptr(ns), _int32_ptr(nt), stats.data_ptr(),
+                                                         dur.data_ptr() if dur is not None else None,
+                                                         pos.data_ptr() if pos is not None else None,
+                                                         peak.data_ptr() if peak is not None else None), stats, dur, pos, peak)
+        out = ()
+        for a in (stats, dur, pos, peak):
+            if a is not None:
+                out += (a.to_host(),)
+                a.free()
+        return out if len(out) > 1 else out[0]
+
+    def text_lengths(self, ids, pad_id=0):
+        """tts_text_lengths: the sentence lengths of padded ids (B, Ts) int32, host or device -- 1 + the last position that does
+        not hold ``pad_id``, 1 for a row of padding -- as an int32 host array (B,)."""
+        shape = tuple(int(d) for d in ids.shape)
+        if len(shape) != 2 or min(shape) < 1:
+            raise ValueError('text_lengths: ids (B, Ts) are needed, got shape {}'.format(shape))
+        if not isinstance(pad_id, (int, np.integer)) or isinstance(pad_id, bool) or not -2 ** 31 <= int(pad_id) < 2 ** 31:
+            raise ValueError('text_lengths: pad_id must be an int32, got {!r}'.format(pad_id))
+        p_ids, _k = self._in(ids, np.int32)
+        out = self.empty((shape[0],), np.int32)
+        self._check_or_free(self.lib.tts_text_lengths(self.handle, p_ids, shape[0], shape[1], int(pad_id), out.data_ptr()), out)
+        n = out.to_host()
+        out.free()
+        return n
+
+    def synth_alignment_stats(self, B):
+        """tts_synth_alignment_stats: the B records (``ALIGNMENT_RECORD``, a host array) of the last ``synthesize`` /
+        ``synthesize_host`` call made on the handle with the attention diagnostics on.  Waits for that call's decoder, not for
+        its Griffin-Lim."""
+        out = np.zeros(int(B), dtype=ALIGNMENT_RECORD)
+        self._check(self.lib.tts_synth_alignment_stats(self.handle, out.ctypes.data, int(B)))
+        return out
+
+    def wait_host_alignment_stats(self, ticket):
+        """The B records (``ALIGNMENT_RECORD``, a copy) of a ``synthesize_host`` call made with the attention diagnostics on:
+        tts_wait_host_alignment_stats.  Waits like ``wait_host`` and does not consume the ticket."""
+        p = c_void_p()
+        n = c_int(0)
+        self._check(self.lib.tts_wait_host_alignment_stats(self.handle, int(ticket), byref(p), byref(n)))
+        raw = ctypes.string_at(p.value, n.value * ALIGNMENT_RECORD.itemsize)
+        return np.frombuffer(raw, dtype=ALIGNMENT_RECORD).copy()
+
     def f0_compare(self, f0_a, f0_b, path):
         """tts_f0_compare: the F0 and voicing errors of B pairs of tracks, ``f0_a`` (B, Ta) against ``f0_b`` (B, Tb) -- side b is
         the recording -- along ``path`` (B, rows, 2) int32 as :meth:`dtw` writes it (rows with a negative entry are skipped); host
@@ -1352,8 +1473,13 @@ class Engine(object):
 
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
-                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None):
-        """``loudness``: None (the handle's setting, off unless ``set_loudness`` changed it), a target in LUFS or
+                   momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
+                   alignment_stats=None):
+        """``alignment_stats``: None (the handle's setting, off unless ``set_alignment_stats`` changed it), False, True or
+        ``(enabled, pad_id)`` for this call (tts_set_alignment_stats): the call also reduces its alignments to one record per utterance
+        behind its decoder, with no host wait; ``synth_alignment_stats(B)`` fetches them (it waits for the decoder alone).
+        Nothing else of the call changes.
+        ``loudness``: None (the handle's setting, off unless ``set_loudness`` changed it), a target in LUFS or
         ``(target_lufs, max_peak)`` for this call (tts_set_loudness): the call's final rows are taken to the target by
         ``loudness_normalize`` at the model's sampling rate, each utterance over the samples its row holds, and
         ``peak_normalize`` is not applied.
@@ -1375,6 +1501,7 @@ class Engine(object):
         scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
         start = self._phase_init_scope(phase_init)
         loud = self._loudness_scope(loudness)
+        diag = self._alignment_stats_scope(alignment_stats)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call = self._speaking_rate if rate.value is None else rate.value
@@ -1405,7 +1532,7 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope, eos, rate, shift, start, loud:
+        with scope, eos, rate, shift, start, loud, diag:
             stopping = self._end_of_speech[0]
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
@@ -1425,17 +1552,19 @@ class Engine(object):
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
-                        speaking_rate=None, pitch=None, phase_init=None, loudness=None):
+                        speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
         ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
         has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1))); ``pitch`` as in
-        ``synthesize`` (no shape changes); ``phase_init`` and ``loudness`` as in ``synthesize``."""
+        ``synthesize`` (no shape changes); ``phase_init`` and ``loudness`` as in ``synthesize``; ``alignment_stats`` likewise (the records travel with the
+        waveforms: ``wait_host_alignment_stats``)."""
         scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
         start = self._phase_init_scope(phase_init)
         loud = self._loudness_scope(loudness)
+        diag = self._alignment_stats_scope(alignment_stats)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -1444,7 +1573,7 @@ class Engine(object):
         t = c_int(-1)
         r_call = self._speaking_rate if rate.value is None else rate.value
         T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, r_call, 0.0)   # (the pitch changes no shape)
-        with scope, eos, rate, shift, start, loud:
+        with scope, eos, rate, shift, start, loud, diag:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))

@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw", "f0", "loudness"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw", "f0", "loudness", "alignment"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -655,6 +655,7 @@ int tts_destroy(tts_handle_t h) {
     if (h->glg.rwss) hipFree(h->glg.rwss);
     h->pl.teardown();
     h->hio.teardown();
+    if (h->ali.copy) hipStreamDestroy(h->ali.copy);
     if (h->own_stream) hipStreamDestroy(h->stream);
     delete h;   // frees the staging buffers and the signals' events (member destructors): keep it inside dev_scope
     return TTS_OK;

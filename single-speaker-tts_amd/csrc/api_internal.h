@@ -55,7 +55,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -163,6 +163,8 @@ struct StageArgs {
         Signal* done = nullptr;
     } upload;
     Signal* enc_done = nullptr;
+    // tts_synthesize_host with tts_set_alignment_stats on: where the call's records go on the device (its buffer set's)
+    tts_alignment_stats_t* stats_out = nullptr;
 };
 
 // tts_synthesize pipelining: encoder + decoder (latency bound, few CUs) of call k+1 run on
@@ -245,6 +247,10 @@ struct HostIo {
     StagedBuf<float> lin[3], ali[3];
     size_t n_lin[3] = {0, 0, 0}, n_ali[3] = {0, 0, 0};
     std::vector<int32_t> frames[3];   // the lengths of this set's call (tts_wait_host_frames): all T without end-of-speech stopping
+    // the alignment statistics of this set's call (tts_set_alignment_stats; tts_wait_host_alignment_stats): the call's kernels
+    // write the device side, the download takes it down with the waveforms; n_stats: the call's B, 0 = made with the setting off
+    StagedBuf<tts_alignment_stats_t> stats[3];
+    int n_stats[3] = {0, 0, 0};
     bool failed[3] = {false, false, false};   // this set's call ended on a decoder timeout: EVERY wait on its ticket fails
     int* status_pinned = nullptr;   // [3][2]: the persistent decoder's sticky status word ([.][1]) as it stood behind
                                     // each call's download
@@ -429,6 +435,18 @@ struct tts_handle_s {
         int sampling_rate = 0;
     } loud;
 
+    // attention diagnostics (tts_set_alignment_stats): read when a call is made; off = the call then enqueues what it always did.
+    // last_dev / last_B: the records of the last call on the device (null: that call was made with the setting off); done:
+    // recorded behind its statistics on the stream its decoder ran on
+    struct {
+        bool enabled = false;
+        int pad_id = 0;
+        const tts_alignment_stats_t* last_dev = nullptr;
+        int last_B = 0;
+        Signal done;
+        hipStream_t copy = nullptr;   // tts_synth_alignment_stats copies on it, behind `done` alone
+    } ali;
+
     // the per-utterance lengths of the last tts_synthesize call (synth_plan.h): Griffin-Lim and the resampler are given them
     SynthLengths syn_lens;
 
@@ -574,6 +592,12 @@ int resample_table(tts_handle_t h, double rho, const double** tab);
 int loudness_workspace(tts_handle_t h, int B, int N, int sr);
 int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, int sr, bool normalize, double target_lufs, double max_peak,
                   double* mean_square, int32_t* n_blocks, double* gain);
+// attention diagnostics (alignment.hip): arguments checked by the caller (alignment_plan.h).  alignment_workspace sizes the buffers
+// ahead of a call that must not allocate once it has begun to enqueue; d_n_sent: the sentence lengths on the device, or null
+int alignment_workspace(tts_handle_t h, int B, int n_steps_max, int Ts);
+int alignment_impl(tts_handle_t h, const float* alignments, int n_steps_max, int B, int Ts, const int32_t* n_sent, const int32_t* n_steps,
+                   const int32_t* d_n_sent, tts_alignment_stats_t* stats, int32_t* durations, int32_t* pos, float* peak);
+int text_lengths_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, int pad_id, int32_t* n_sent);
 int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double rho, int N_out, const int32_t* keep_cap,
                   float* out);
 void resample_release(tts_handle_t h);

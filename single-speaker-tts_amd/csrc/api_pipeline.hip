@@ -74,6 +74,12 @@ struct SynthCall {
     bool loud = false;
     double loud_target = 0.0, loud_max_peak = 1.0;
     int loud_sr = 0;
+    // attention diagnostics (tts_set_alignment_stats), likewise: the sentence lengths are taken from the ids behind the encoder,
+    // the statistics from `align_out` -- the caller's buffer or the handle's -- right behind the decoder, on the decoder's stream
+    bool ali = false;
+    int ali_pad = 0;
+    int32_t* ali_n_sent = nullptr;             // this call parity's lengths on the device (workspace "syn.ali_nsent")
+    tts_alignment_stats_t* ali_stats = nullptr;   // where the records go: the host form's buffer set, or workspace "syn.ali_stats"
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -154,6 +160,24 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     }
     if (k.loud) {   // (the measurement's states and sums, for rows of hop (Tw - 1) samples)
         const int rc = loudness_workspace(h, B, sp->hop_length * (k.shape.Tw - 1), k.loud_sr);
+        if (rc) return rc;
+    }
+    if (k.ali) {
+        // One alignment buffer and one set of scratch: the statistics of a call run behind its decoder on the decoder's stream,
+        // in front of whatever lets the next decoder start.  The sentence lengths are written behind the ENCODER, which may run a
+        // call ahead on its own stream: one set per call parity, like `memory`.
+        if (!k.align_out) {
+            WS(h, "syn.ali", float, (size_t)sp->n_steps * B * Ts, ali_buf);
+            k.align_out = ali_buf;
+        }
+        WS(h, "syn.ali_nsent", int32_t, 2 * (size_t)B, ali_ns);
+        k.ali_n_sent = ali_ns + (size_t)parity * B;
+        k.ali_stats = k.host->stats_out;
+        if (!k.ali_stats) {
+            WS(h, "syn.ali_stats", tts_alignment_stats_t, (size_t)B, ali_st);
+            k.ali_stats = ali_st;
+        }
+        const int rc = alignment_workspace(h, B, sp->n_steps, Ts);
         if (rc) return rc;
     }
     // (estimated initial phases, option "gl_init": the estimate's buffers, for the frames Griffin-Lim reconstructs from)
@@ -330,6 +354,8 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
         HIPCHK(h, up.done->record(h->stream));
     }
     if ((rc = encoder_impl(h, k.ids, B, Ts, k.memory))) return rc;
+    // (attention diagnostics: the sentence lengths, where the ids are certainly in place -- beside the encoder that reads them)
+    if (k.ali && (rc = text_lengths_impl(h, k.ids, B, Ts, k.ali_pad, k.ali_n_sent))) return rc;
     if (k.host->enc_done) HIPCHK(h, k.host->enc_done->record(h->stream));
     if (k.pipelined && k.keys_ahead) {
         ProfScope ps(h, ST_ENCODER, 1);
@@ -352,6 +378,15 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
     args.parity = parity;
     args.keys = k.pipelined ? k.keys_ahead : nullptr;
     if ((rc = decoder_impl(h, k.memory, B, Ts, k.sp->n_steps, k.mel, k.align_out, nullptr, args, &k.proj))) return rc;
+    if (k.ali) {
+        // Attention diagnostics: right behind the decoder on its stream and in front of the records below, so that whatever
+        // waits for this decoder -- the next one, an encoder that reuses this parity's lengths -- waits for the statistics too
+        if ((rc = alignment_impl(h, k.align_out, k.sp->n_steps, B, Ts, nullptr, nullptr, k.ali_n_sent, k.ali_stats, nullptr, nullptr, nullptr)))
+            return rc;
+        HIPCHK(h, h->ali.done.record(h->stream));
+        h->ali.last_dev = k.ali_stats;
+        h->ali.last_B = B;
+    }
     if (k.pipelined) HIPCHK(h, pl.dec_done[parity].record(pl.front));
     else if (pl.front) HIPCHK(h, pl.serial_done.record(on.main_stream));
     return TTS_OK;
@@ -498,6 +533,9 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
         if (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX)
             return fail(h, TTS_ERR_INVALID, "synthesize: a loudness target needs rows of 1 .. 2^31 - 1 samples");
     }
+    k.ali = h->ali.enabled;
+    k.ali_pad = h->ali.pad_id;
+    h->ali.last_dev = nullptr;   // (the records of a call before this one are no longer "the last call's")
     if ((rc = synth_workspaces(h, k))) return rc;
     if (k.pipelined && (rc = synth_streams(h))) return rc;
     hipStream_t enc_on = nullptr;
@@ -542,6 +580,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     const bool want_lin = (sp->host_outputs & TTS_HOST_LINEAR) != 0, want_ali = (sp->host_outputs & TTS_HOST_ALIGNMENTS) != 0;
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;
+    const size_t stats_bytes = h->ali.enabled ? (size_t)B * sizeof(tts_alignment_stats_t) : 0;
     if (!io.out) {
         // The copy stream gets the LOWEST priority: streams of one priority share a few hardware queues in creation order
         // (whatever else the process has created counts; GPU_MAX_HW_QUEUES per priority, as few as 2), and a copy stream that
@@ -555,7 +594,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     }
     // (the sets grow together and the last one last: it fits where all of them do)
     if (ids_bytes > io.ids[2].bytes || n_wav * sizeof(float) > io.wav[2].bytes || n_lin * sizeof(float) > io.lin[2].bytes ||
-        n_ali * sizeof(float) > io.ali[2].bytes) {
+        n_ali * sizeof(float) > io.ali[2].bytes || stats_bytes > io.stats[2].bytes) {
         // growing the buffers: nothing of an earlier call may be in flight
         if ((rc = sync_all(h))) return rc;
         HIPCHK(h, hipStreamSynchronize(io.out));
@@ -564,6 +603,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
             HIPCHK(h, io.wav[i].grow(n_wav * sizeof(float)));
             HIPCHK(h, io.lin[i].grow(n_lin * sizeof(float)));
             HIPCHK(h, io.ali[i].grow(n_ali * sizeof(float)));
+            HIPCHK(h, io.stats[i].grow(stats_bytes));
         }
         io.reset();
     }
@@ -581,6 +621,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     host.upload.bytes = ids_bytes;
     host.upload.done = &io.h2d[par];
     host.enc_done = &io.enc[par];
+    host.stats_out = stats_bytes ? io.stats[par].dev : nullptr;
     // (the optional outputs of this set were last read by the download of the call three back: same event as the waveforms)
     rc = synthesize_impl(h, io.ids[par].dev, B, Ts, sp, nullptr, io.wav[par].dev, nullptr, want_ali ? io.ali[par].dev : nullptr,
                          want_lin ? io.lin[par].dev : nullptr, host);
@@ -590,6 +631,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     HIPCHK(h, hipMemcpyAsync(io.wav[par].pinned, io.wav[par].dev, n_wav * sizeof(float), hipMemcpyDeviceToHost, io.out));
     if (want_lin) HIPCHK(h, hipMemcpyAsync(io.lin[par].pinned, io.lin[par].dev, n_lin * sizeof(float), hipMemcpyDeviceToHost, io.out));
     if (want_ali) HIPCHK(h, hipMemcpyAsync(io.ali[par].pinned, io.ali[par].dev, n_ali * sizeof(float), hipMemcpyDeviceToHost, io.out));
+    if (stats_bytes) HIPCHK(h, hipMemcpyAsync(io.stats[par].pinned, io.stats[par].dev, stats_bytes, hipMemcpyDeviceToHost, io.out));
+    io.n_stats[par] = stats_bytes ? B : 0;
     io.n_lin[par] = n_lin;
     io.n_ali[par] = n_ali;
     io.frames[par] = h->eos.last;   // (the call has read them: synth_main)
@@ -663,6 +706,21 @@ int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, i
     const auto& f = h->hio.frames[ticket % 3];
     *n_frames = f.data();
     if (B) *B = (int)f.size();
+    return TTS_OK;
+}
+
+
+int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignment_stats_t** stats, int* B) {
+    DeviceScope dev_scope(h);
+    if (!h || !stats) return TTS_ERR_INVALID;
+    const float* wav = nullptr;
+    const int rc = tts_wait_host(h, ticket, &wav, nullptr);   // same event, same checks (ticket range, decoder status)
+    if (rc) return rc;
+    const auto& io = h->hio;
+    const int par = ticket % 3;
+    if (!io.n_stats[par]) return fail(h, TTS_ERR_INVALID, "wait_host_alignment_stats: this ticket's call was not made with tts_set_alignment_stats on");
+    *stats = io.stats[par].pinned;
+    if (B) *B = io.n_stats[par];
     return TTS_OK;
 }
 

@@ -182,7 +182,7 @@ def batch_f0(model, feed, out, path, n_pred, n_target, f0_iters=None, f0_min=60.
 
 
 def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_save_run=None, verbose=True, mcd=False, mcd_coeffs=13,
-             mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0):
+             mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0, attention=False):
     """reference :153-257.  Restores ``checkpoint_file`` into ``model`` (a ``Tacotron(..., Mode.EVAL)``) once, runs every
     feed dict of ``batches`` through tts_evaluate and returns ``{loss, loss_decoder, loss_post_processing, global_step,
     n_batches}``: the per-batch float32 losses averaged unweighted over the batches.  Raises if no batch ran.  Appends
@@ -192,7 +192,11 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
     With ``f0`` the result and the summary line gain ``metric/f0_rmse_cents``, ``metric/f0_rmse_hz``, ``metric/vuv_error`` and
     ``metric/gross_pitch_error`` -- each the mean over the utterances that have that figure -- and ``f0_utterances``, the
     utterances that have an F0 RMSE (``f0_iters``: Griffin-Lim iterations, default the model's ``reconstruction_iterations``;
-    ``f0_min`` / ``f0_max``: the search range in Hz); without it nothing of the run, the result or the line changes."""
+    ``f0_min`` / ``f0_max``: the search range in Hz); without it nothing of the run, the result or the line changes.
+    With ``attention`` the result and the summary line gain ``attention/<flag>`` for every flag of
+    ``attention_check.FLAGS`` -- the utterances of the epoch that carry it -- ``attention/mean_focus``, the mean over the
+    utterances of focus_sum / n_steps, and ``attention_utterances``: ``Engine.alignment_stats`` on every batch's alignments, with
+    the batch's own sentence lengths and frame counts; without it nothing of the run, the result or the line changes."""
     if model._mode != Mode.EVAL:
         raise ValueError('evaluate() needs a Tacotron in Mode.EVAL')
     global_step = global_step_of(checkpoint_file)
@@ -206,11 +210,15 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
     n_batches = 0
     mcds = []
     f0s = []
+    records = []
     for feed in batches:
         out = model.evaluate_device(feed['ph_sentences'], feed['ph_mel_specs'], feed['ph_lin_specs'],
-                                    want_mel=bool(mcd) or bool(f0), want_alignments=False,
+                                    want_mel=bool(mcd) or bool(f0), want_alignments=bool(attention),
                                     want_linear=(bool(mcd) and mcd_stop_at_silence is not None) or bool(f0))
         sums += out['losses'].to_host().astype(np.float64)
+        if attention:
+            records.append(model.engine.alignment_stats(out['alignments'], n_sent=feed['ph_sentence_length'],
+                                                        n_steps=feed['ph_time_frames']))
         if f0:
             res, n_pred, n_target = batch_alignment(model, feed, out, mcd_coeffs, mcd_stop_at_silence, want_path=True)
             if mcd:
@@ -237,6 +245,14 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
             result['metric/' + key] = float(np.mean(values)) if values.size else float('nan')
             if key == 'f0_rmse_cents':
                 result['f0_utterances'] = int(values.size)
+    if attention:
+        from . import attention_check
+        every = np.concatenate(records)
+        verdicts = attention_check.verdict(every)
+        for flag in attention_check.FLAGS:
+            result['attention/' + flag] = int(sum(flag in v for v in verdicts))
+        result['attention/mean_focus'] = float(np.mean(every['focus_sum'] / every['n_steps']))
+        result['attention_utterances'] = int(every.shape[0])
     if verbose:
         print('[evaluate] step: {}, batches: {}, loss: {:.6f}, loss_decoder: {:.6f}, loss_post_processing: {:.6f}'.format(
             global_step, n_batches, result['loss'], result['loss_decoder'], result['loss_post_processing']))
@@ -258,6 +274,9 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
             for key in F0_KEYS:
                 line['metric/' + key] = result['metric/' + key]
             line['f0_utterances'] = result['f0_utterances']
+        if attention:
+            for key in sorted(k for k in result if k.startswith('attention')):
+                line[key] = result[key]
         with open(os.path.join(save_dir, SUMMARY_FILE), 'a') as f:
             f.write(json.dumps(line) + '\n')
     return result
@@ -276,7 +295,7 @@ def collect_checkpoint_paths(checkpoint_dir):
 
 def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, batch_size=None, checkpoint_dir=None,
                         checkpoint_save_run=None, hparams=None, device_id=0, verbose=True, mcd=False, mcd_coeffs=13,
-                        mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0):
+                        mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0, attention=False):
     """One cycle of the reference's ``__eval_cycle`` (:336-352): a dataset loader, the batches, a model with its own
     engine, :func:`evaluate`; the engine is released afterwards."""
     from ..datasets.lj_speech import LJSpeechDatasetHelper
@@ -289,7 +308,8 @@ def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, 
     try:
         return evaluate(model, checkpoint_file, batches, checkpoint_dir=checkpoint_dir,
                         checkpoint_save_run=checkpoint_save_run, verbose=verbose, mcd=mcd, mcd_coeffs=mcd_coeffs,
-                        mcd_stop_at_silence=mcd_stop_at_silence, f0=f0, f0_iters=f0_iters, f0_min=f0_min, f0_max=f0_max)
+                        mcd_stop_at_silence=mcd_stop_at_silence, f0=f0, f0_iters=f0_iters, f0_min=f0_min, f0_max=f0_max,
+                        attention=attention)
     finally:
         model.engine.close()
 
@@ -301,6 +321,7 @@ def main(argv=None):
                                                            [--dataset-folder F] [--max-samples N] [--batch-size B]
                                                            [--mcd [--mcd-coeffs K] [--mcd-stop-at-silence DB]]
                                                            [--f0 [--f0-iters N] [--f0-min HZ] [--f0-max HZ]]
+                                                           [--attention]
 
     The options override the ``evaluation_params`` / ``dataset_params`` fields of the same name.  Without ``--all``
     (``evaluate_all_checkpoints``) the latest checkpoint of ``<checkpoint_dir>/<load_run>`` is evaluated, with it every
@@ -326,6 +347,8 @@ def main(argv=None):
                     help="Griffin-Lim iterations of --f0 (default: the model's reconstruction_iterations)")
     ap.add_argument('--f0-min', type=float, default=None, metavar='HZ', help='lowest F0 searched (default 60)')
     ap.add_argument('--f0-max', type=float, default=None, metavar='HZ', help='highest F0 searched (default 500)')
+    ap.add_argument('--attention', action='store_true',
+                    help='also report the attention diagnostics: utterances per flag of tacotron.attention_check, and the mean focus')
     args = ap.parse_args(argv)
     if not args.f0 and (args.f0_iters is not None or args.f0_min is not None or args.f0_max is not None):
         ap.error('--f0-iters, --f0-min and --f0-max need --f0')
@@ -350,7 +373,7 @@ def main(argv=None):
                                   batch_size=args.batch_size, checkpoint_dir=args.checkpoint_dir,
                                   checkpoint_save_run=args.save_run, device_id=args.device, mcd=args.mcd,
                                   mcd_coeffs=args.mcd_coeffs, mcd_stop_at_silence=args.mcd_stop_at_silence, f0=args.f0,
-                                  f0_iters=args.f0_iters, f0_min=f0_min, f0_max=f0_max)
+                                  f0_iters=args.f0_iters, f0_min=f0_min, f0_max=f0_max, attention=args.attention)
         print(json.dumps(dict(res, checkpoint=checkpoint_file)))
     return 0
 

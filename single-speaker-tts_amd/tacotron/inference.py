@@ -7,10 +7,12 @@ de-normalise -> ``** magnitude_power`` -> Griffin-Lim -> ``{i+1}.wav``.
 Where the reference fans Griffin-Lim out to 6 worker processes, one utterance each
 (:185-188), the whole batch is reconstructed by one batched kernel sequence on the GPU.
 """
+import json
 import os
 
 import numpy as np
 
+from . import attention_check
 from .._hip import (LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value, silence_keep_frames, speaking_rate_value,
                     stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
@@ -52,6 +54,7 @@ def inference(model, sentences, n_steps=None):
     return [mag[b] for b in range(mag.shape[0])]
 
 
+REPORT_FILE = 'alignment_report.json'   # what --check-alignment writes beside the wavs
 SILENCE_KEEP_MS = 100.0   # audio kept behind the last frame above the threshold where a caller does not say
 
 
@@ -72,9 +75,14 @@ def cut_waveforms(wavs, n_frames, hop):
     return [wavs[b][:hop * (int(n_frames[b]) - 1)] for b in range(len(n_frames))]
 
 
+def pad_id():
+    """the id the sentences are padded with (``pad_sentence``): what the attention diagnostics take the sentence lengths from"""
+    return int(dataset_params.vocabulary_dict['pad'])
+
+
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
                      momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                     phase_init='random', loudness=None):
+                     phase_init='random', loudness=None, check_alignment=False):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  ``momentum``: fast Griffin-Lim
     (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind
@@ -88,7 +96,10 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     (Griffin-Lim starts from phases estimated from the call's magnitudes, audio.synthesis; far fewer iterations are then
     needed) or None (the engine's ``gl_init`` option); ``init_phase`` wins.  ``loudness``: None, a target in LUFS or
     ``(target_lufs, max_peak)`` -- every utterance is taken to that integrated loudness (ITU-R BS.1770-4, measured over the
-    samples it holds) on the device instead of being peak-normalised."""
+    samples it holds) on the device instead of being peak-normalised.  ``check_alignment``: the call also reduces its
+    alignments to one record per utterance on the device (``Engine.alignment_stats``; the sentence lengths are taken from the
+    ids' padding) and the result is ``(waveforms, records, verdicts)`` -- ``attention_check.verdict`` of every utterance, an
+    empty tuple where the attention read the sentence cleanly."""
     momentum_thousandths(momentum)   # ValueError outside [0, 1), before the engine is touched
     phase_init_value(phase_init)
     loud = loudness_setting(loudness)
@@ -104,15 +115,18 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
                                   init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum,
-                                  stop_at_silence=stop, speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud)
-    if stop is not None:
-        return cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop)
-    return out['wav'].to_host()
+                                  stop_at_silence=stop, speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud,
+                                  alignment_stats=(True, pad_id()) if check_alignment else None)
+    wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if stop is not None else out['wav'].to_host()
+    if check_alignment:
+        records = model.engine.synth_alignment_stats(len(sentences))
+        return wavs, records, attention_check.verdict(records)
+    return wavs
 
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
                       want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
-                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None):
+                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -125,7 +139,9 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db`` / ``silence_keep_ms`` as in ``synthesize_batch``: the waveforms of a batch are then a list of B
     arrays (views of the pinned rows unless ``copy``), each cut to its own length.  ``speaking_rate`` as in
-    ``synthesize_batch``, ``pitch``, ``phase_init`` and ``loudness`` likewise."""
+    ``synthesize_batch``, ``pitch``, ``phase_init`` and ``loudness`` likewise.  ``check_alignment``: every item additionally
+    carries the batch's alignment records and verdicts, ``(wavs, records, verdicts)`` or ``(wavs, linear, alignments, records,
+    verdicts)``; the 56 bytes per utterance come down with the waveforms."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before the engine is touched)
     phase_init_value(phase_init)
     loud = loudness_setting(loudness)
@@ -148,10 +164,14 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
         return cut_waveforms(eng.wait_host(ticket, copy=copy), n_frames, win_hop)
 
     def collect(ticket):
+        checked = ()
+        if check_alignment:
+            records = eng.wait_host_alignment_stats(ticket)
+            checked = (records, attention_check.verdict(records))
         if not extra:
-            return waveforms(ticket)
+            return ((waveforms(ticket),) + checked) if checked else waveforms(ticket)
         lin, ali = eng.wait_host_outputs(ticket, copy=copy)
-        return waveforms(ticket), lin, ali
+        return (waveforms(ticket), lin, ali) + checked
 
     # three batches in flight (the library's three buffer sets): the encoder of batch k + 2 runs one inter-Griffin-Lim gap
     # ahead of its decoder, which follows the decoder of batch k + 1 without a pause, beside the Griffin-Lim of batch k
@@ -160,7 +180,8 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
                                            want_alignments=want_alignments, momentum=momentum, stop_at_silence=stop,
-                                           speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud))
+                                           speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud,
+                                           alignment_stats=(True, pad_id()) if check_alignment else None))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -193,7 +214,7 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
 
 def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
                          stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                         phase_init='random', loudness=None):
+                         phase_init='random', loudness=None, check_alignment=False):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
@@ -201,7 +222,9 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames.
     ``speaking_rate``: as in ``synthesize_batch`` (1.2: a fifth faster); ``pitch``: likewise, in octaves (4 / 12: four semitones up);
     ``phase_init``: likewise ('estimate': estimated start phases); ``loudness``: likewise -- the files then hold the waveforms at
-    that loudness, not peak-normalised."""
+    that loudness, not peak-normalised.  ``check_alignment``: the attention diagnostics of ``synthesize_batch`` -- the result
+    is ``(waveforms, report)`` with ``report`` the list of ``{index, verdict, record}`` of ``attention_check.report``, also
+    written to ``alignment_report.json`` beside the wavs."""
     momentum_thousandths(momentum)
     phase_init_value(phase_init)
     loud = loudness_setting(loudness)
@@ -221,10 +244,16 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
     wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum,
                             stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                            pitch=pitch, phase_init=phase_init, loudness=loud)
+                            pitch=pitch, phase_init=phase_init, loudness=loud, check_alignment=check_alignment)
+    report = None
+    if check_alignment:
+        wavs, records, _verdicts = wavs
+        report = attention_check.report(records)
+        with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
+            json.dump(report, f, indent=1)
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, loud is None)
-    return list(wavs)
+    return (list(wavs), report) if check_alignment else list(wavs)
 
 
 def read_sentences(path):
@@ -248,6 +277,7 @@ def main(argv=None):
                                                             [--rate R] [--pitch SEMITONES]
                                                             [--phase-init random|estimate]
                                                             [--loudness LUFS [--max-peak P]]
+                                                            [--check-alignment]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
@@ -258,7 +288,9 @@ def main(argv=None):
     ``--pitch SEMITONES``: the pitch, -12 .. 12 semitones (4: a major third up; default 0 = as the network speaks).
     ``--phase-init estimate``: Griffin-Lim starts from phases estimated from the magnitudes instead of random ones.
     ``--loudness LUFS``: every wav is taken to that integrated loudness (ITU-R BS.1770-4; -23: EBU R 128, -16: a common
-    streaming level) with no sample beyond ``--max-peak`` (default 1), instead of being peak-normalised."""
+    streaming level) with no sample beyond ``--max-peak`` (default 1), instead of being peak-normalised.
+    ``--check-alignment``: the attention diagnostics (``tacotron.attention_check``) -- one JSON line per sentence (index,
+    verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts."""
     args = parse_args(argv)
     loud = None if args.loudness is None else loudness_setting((args.loudness, args.max_peak))
     momentum_thousandths(args.momentum)
@@ -284,7 +316,11 @@ def main(argv=None):
     wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
                                 momentum=args.momentum, stop_at_silence_db=args.stop_at_silence,
                                 silence_keep_ms=args.silence_keep_ms, speaking_rate=args.rate, pitch=octaves,
-                                phase_init=args.phase_init, loudness=loud)
+                                phase_init=args.phase_init, loudness=loud, check_alignment=args.check_alignment)
+    if args.check_alignment:
+        wavs, report = wavs
+        for row in report:
+            print(json.dumps(row))
     for i in range(len(wavs)):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
@@ -316,6 +352,8 @@ def parse_args(argv=None):
                     help='integrated loudness (ITU-R BS.1770-4) every wav is taken to, e.g. -23; default: peak normalisation')
     ap.add_argument('--max-peak', type=float, default=LOUDNESS_MAX_PEAK, metavar='P',
                     help='with --loudness: the largest |sample| the gain may produce (default {:g})'.format(LOUDNESS_MAX_PEAK))
+    ap.add_argument('--check-alignment', action='store_true',
+                    help='attention diagnostics: one JSON line per sentence and {} beside the wavs'.format(REPORT_FILE))
     return ap.parse_args(argv)
 
 

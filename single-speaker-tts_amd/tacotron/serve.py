@@ -10,7 +10,8 @@ import numpy as np
 
 from .._hip import loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
-from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_sentence, stop_setting
+from . import attention_check
+from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_id, pad_sentence, stop_setting
 from .model import Mode, Tacotron
 from .params import dataset_params, model_params
 
@@ -91,7 +92,8 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
-          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None):
+          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None,
+          check_alignment=False):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -103,7 +105,9 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db`` /
     ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech;
     ``speaking_rate``, ``pitch``, ``phase_init`` and ``loudness`` likewise: with a loudness every answer of the stream comes at
-    the same level."""
+    the same level.  ``check_alignment``: every answer is ``(waveforms, records, verdicts)`` -- the alignment records of the
+    batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip as the
+    waveforms: a bad utterance can be flagged before it is played."""
     momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
     phase_init_value(phase_init)
     loud = loudness_setting(loudness)
@@ -117,15 +121,23 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     if not pipelined:   # the reference's loop as it stands: one batch at a time, spectrograms through host memory
         for sentences in sentence_generator:
             ids = pre_process_sentences(sentences, dataset)
-            spectrograms = model.run(model.output_linear_spec, {model.inp_sentences: ids})
-            yield post_process_spectrograms(spectrograms, model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
-                                            silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch,
-                                            phase_init=phase_init, loudness=loud)
+            fetches = [model.output_linear_spec] + ([model.alignment_history] if check_alignment else [])
+            fetched = model.run(fetches, {model.inp_sentences: ids})
+            wavs = post_process_spectrograms(fetched[0], model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
+                                             silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch,
+                                             phase_init=phase_init, loudness=loud)
+            if check_alignment:   # (the same kernels as inside a pipelined call, on the alignments this loop fetched anyway)
+                records = model.engine.alignment_stats(fetched[1], n_sent=model.engine.text_lengths(ids, pad_id()))
+                yield wavs, records, attention_check.verdict(records)
+            else:
+                yield wavs
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
-    for wavs in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
+    for item in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
                                   stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                                  pitch=pitch, phase_init=phase_init, loudness=loud):
-        yield [wavs[b] for b in range(len(wavs))]
+                                  pitch=pitch, phase_init=phase_init, loudness=loud, check_alignment=check_alignment):
+        wavs = item[0] if check_alignment else item
+        listed = [wavs[b] for b in range(len(wavs))]
+        yield (listed, item[1], item[2]) if check_alignment else listed

@@ -7,6 +7,8 @@ Host arrays are numpy; device memory is either owned by the library's allocator
 (:class:`DeviceArray`) or borrowed from anything exposing ``data_ptr()`` (a CUDA/HIP torch
 tensor) -- PyTorch is optional plumbing, not a dependency of this module.
 """
+import collections
+import contextlib
 import ctypes
 import os
 from ctypes import (POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64,
@@ -347,26 +349,6 @@ def phase_estimate_args(shape, n_fft, hop_length, n_frames, time_major=False):
     return B, T, F, stretch_frame_counts(n_frames, B, T)
 
 
-class _SettingScope(object):
-    """One setting of the handle put to ``value`` for the calls made inside the block and put back afterwards, also after an
-    exception; None: the handle's setting as it stands.  ``attr``: the engine's attribute that mirrors the setting (the C ABI
-    has no getters), ``setter(value)``: sets both.  ``value`` is checked by whoever makes the scope, before a handle is
-    touched."""
-
-    def __init__(self, engine, attr, setter, value):
-        self.engine, self.attr, self.setter, self.value = engine, attr, setter, value
-
-    def __enter__(self):
-        self.saved = getattr(self.engine, self.attr)
-        if self.value is not None and self.value != self.saved:
-            self.setter(self.value)
-
-    def __exit__(self, *exc):
-        if getattr(self.engine, self.attr) != self.saved:
-            self.setter(self.saved)
-        return False
-
-
 def stop_at_silence_setting(stop_at_silence):
     """``stop_at_silence`` of the synthesis calls -- None (off) or ``(threshold_db, keep_frames)`` -- as a checked tuple
     ``(float, int)`` or None.  ValueError, raised before a handle is touched, for anything else: a NaN threshold, a negative
@@ -653,12 +635,85 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
     return spec, stride
 
 
+# The per-call synthesis settings.  The handle holds each of them (tts_set_* / tts_set_option; the C ABI has no getters, so the
+# engine mirrors them); ``Engine.synthesize`` and ``Engine.synthesize_host`` take all seven as keywords, ``Engine.griffin_lim``
+# takes ``momentum`` and ``phase_init``.  None always means the handle's setting as it stands; any other value holds for that
+# call alone (``Engine._settings``).  In the order they are checked and applied in:
+#   ``momentum``: the fast Griffin-Lim momentum in [0, 1) (librosa's and torchaudio's ``momentum``; 0 = the reference's plain
+#     loop) -- the ``gl_momentum`` option, off (0) unless ``set_option`` changed it.
+#   ``stop_at_silence``: ``(threshold_db, keep_frames)`` -- end-of-speech stopping (tts_set_end_of_speech, off unless
+#     ``set_end_of_speech`` changed it): every utterance is reconstructed from its frames up to the last one whose loudest bin is
+#     above ``threshold_db``, plus ``keep_frames``; ``wav`` keeps its shape, row b holds hop (n_frames[b] - 1) samples followed by
+#     zeros.  The result of a call made with stopping on carries ``n_frames``, the int32 host array of the B lengths;
+#     ``synth_frames`` / ``wait_host_frames`` return them for any call.
+#   ``speaking_rate``: a rate in [0.25, 4] (tts_set_speaking_rate, 1.0 unless ``set_speaking_rate`` changed it): the magnitudes
+#     are time-stretched ahead of Griffin-Lim, ``wav`` is (B, hop (T' - 1)) and ``init_phase`` (B, F, T') with T' =
+#     ``stretched_frames(T, rate)``; mel, alignments and linear keep their length T.
+#   ``pitch``: a shift in [-1, 1] octaves (tts_set_pitch, 0 unless ``set_pitch`` changed it): the magnitudes are stretched by
+#     rate * 2 ** -pitch, and the resampler takes Griffin-Lim's samples back to the length of the call without pitch.  No shape
+#     and no reported length changes but ``init_phase``'s, which is (B, F, ``pitch_frames(T, rate, pitch)``).
+#   ``phase_init``: how Griffin-Lim starts when ``init_phase`` is None -- 'random' (from ``seed``) or 'estimate' (phases
+#     estimated from the call's own magnitudes, ``phase_estimate``: behind the stretch, at each utterance's own length; ``seed``
+#     is then unused) -- the ``gl_init`` option.  An explicit ``init_phase`` always wins.
+#   ``loudness``: a target in LUFS or ``(target_lufs, max_peak)`` (tts_set_loudness, off unless ``set_loudness`` changed it):
+#     the call's final rows are taken to the target by ``loudness_normalize`` at the model's sampling rate, each utterance
+#     over the samples its row holds, and ``peak_normalize`` is not applied.
+#   ``alignment_stats``: False, True or ``(enabled, pad_id)`` (tts_set_alignment_stats, off unless ``set_alignment_stats``
+#     changed it): the call also reduces its alignments to one record per utterance behind its decoder, with no host wait;
+#     ``synth_alignment_stats(B)`` / ``wait_host_alignment_stats`` fetch them.  Nothing else of the call changes.
+# A row: the keyword, the Engine attribute that mirrors the handle's value, the handle's initial value, the check that turns
+# the keyword into the mirror's value (ValueError before a handle is touched), and how a value is applied -- a ``set_option``
+# key or a call of the engine's ``set_*`` method.
+Setting = collections.namedtuple('Setting', 'keyword mirror initial check apply')
+SETTINGS = (
+    Setting('momentum', '_gl_momentum', 0, momentum_thousandths, 'gl_momentum'),
+    Setting('stop_at_silence', '_end_of_speech', (False, 0.0, 0), lambda v: (True,) + stop_at_silence_setting(v),
+            lambda engine, v: engine.set_end_of_speech(*v)),
+    Setting('speaking_rate', '_speaking_rate', 1.0, speaking_rate_value, lambda engine, v: engine.set_speaking_rate(v)),
+    Setting('pitch', '_pitch', 0.0, pitch_octaves_value, lambda engine, v: engine.set_pitch(v)),
+    Setting('phase_init', '_gl_init', 0, phase_init_value, 'gl_init'),
+    Setting('loudness', '_loudness', None, loudness_setting, lambda engine, v: engine.set_loudness(v)),
+    Setting('alignment_stats', '_alignment_stats', (False, 0), alignment_stats_setting, lambda engine, v: engine.set_alignment_stats(*v)),
+)
+
+
+class _Settings(object):
+    """The settings of one call: the ``per_call`` keywords of SETTINGS, every one checked here, in the table's order.  As a
+    context manager it puts the handle to those that differ from it, in the table's order, and puts back afterwards, in reverse
+    and also after an exception, those whose mirror no longer holds what it held.  ``self[keyword]``: the value the call runs
+    with, in the mirror's form -- the keyword's, or the handle's as it stands."""
+
+    def __init__(self, engine, per_call):
+        self.engine = engine
+        self.rows = [row for row in SETTINGS if row.keyword in per_call]
+        self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
+
+    def __getitem__(self, keyword):
+        if self.values[keyword] is not None:
+            return self.values[keyword]
+        return getattr(self.engine, next(row.mirror for row in self.rows if row.keyword == keyword))
+
+    def _put(self, row, value):
+        if getattr(self.engine, row.mirror) != value:
+            self.engine.set_option(row.apply, value) if isinstance(row.apply, str) else row.apply(self.engine, value)
+
+    def __enter__(self):
+        with contextlib.ExitStack() as entered:
+            for row in self.rows:
+                saved = getattr(self.engine, row.mirror)
+                if self.values[row.keyword] is not None:
+                    self._put(row, self.values[row.keyword])
+                entered.callback(self._put, row, saved)
+            self.entered = entered.pop_all()
+        return self
+
+    def __exit__(self, *exc):
+        return self.entered.__exit__(*exc)
+
+
 class Engine(object):
     """One handle = one GPU + one stream.  Mirrors the C ABI one to one."""
 
-    _gl_init = 0   # the handle's "gl_init" option (the C ABI has no getter: set_option keeps it)
-    _loudness = None   # ... and its loudness setting, None (off) or (target_lufs, max_peak) (set_loudness keeps it)
-    _alignment_stats = (False, 0)   # ... and its attention diagnostics, (enabled, pad_id) (set_alignment_stats keeps them)
     sampling_rate = 22050   # the model's (hparams.sampling_rate): what a loudness target of the synthesis calls is measured at
 
     def __init__(self, hparams=None, device_id=0, stream=None):
@@ -703,10 +758,7 @@ class Engine(object):
         self.handle = h
         self.device_id = int(device_id)
         self._staging = {}
-        self._gl_momentum = 0   # the handle's "gl_momentum" (the C ABI has no getter: set_option keeps it)
-        self._end_of_speech = (False, 0.0, 0)   # ... and its end-of-speech setting (set_end_of_speech keeps it)
-        self._speaking_rate = 1.0               # ... and its speaking rate (set_speaking_rate keeps it)
-        self._pitch = 0.0                       # ... and its pitch in octaves (set_pitch keeps it)
+        self._init_settings()
         self._host_shapes, self._host_out_shapes = {}, {}   # per ticket of synthesize_host, until its wait_host* call
         if stream is not None:
             self._check(self.lib.tts_set_stream(self.handle, c_void_p(stream)))
@@ -749,10 +801,18 @@ class Engine(object):
 
     def set_option(self, key, value):
         self._check(self.lib.tts_set_option(self.handle, key.encode(), int(value)))
-        if key == 'gl_momentum':
-            self._gl_momentum = int(value)
-        if key == 'gl_init':
-            self._gl_init = int(value)
+        for row in SETTINGS:
+            if row.apply == key:
+                setattr(self, row.mirror, int(value))
+
+    def _init_settings(self):
+        """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
+        for row in SETTINGS:
+            setattr(self, row.mirror, row.initial)
+
+    def _settings(self, **per_call):
+        """the settings of one call (SETTINGS): checked here, applied around the ``with`` block"""
+        return _Settings(self, per_call)
 
     def set_end_of_speech(self, enabled, threshold_db=0.0, keep_frames=0):
         """tts_set_end_of_speech: the handle's setting, read by every synthesize / synthesize_host call made after it."""
@@ -796,27 +856,6 @@ class Engine(object):
         setting = alignment_stats_setting((bool(enabled), pad_id))
         self._check(self.lib.tts_set_alignment_stats(self.handle, 1 if setting[0] else 0, setting[1]))
         self._alignment_stats = setting
-
-    def _alignment_stats_scope(self, alignment_stats):
-        return _SettingScope(self, '_alignment_stats', lambda v: self.set_alignment_stats(*v), alignment_stats_setting(alignment_stats))
-
-    def _loudness_scope(self, loudness):
-        return _SettingScope(self, '_loudness', self.set_loudness, loudness_setting(loudness))
-
-    def _momentum_scope(self, momentum):
-        return _SettingScope(self, '_gl_momentum', lambda v: self.set_option('gl_momentum', v),
-                             None if momentum is None else momentum_thousandths(momentum))
-
-    def _phase_init_scope(self, phase_init):
-        return _SettingScope(self, '_gl_init', lambda v: self.set_option('gl_init', v), phase_init_value(phase_init))
-
-    def _synth_scopes(self, momentum, stop_at_silence, speaking_rate, pitch):
-        """the scopes of a synthesis call's four settings (momentum, end of speech, rate, pitch), every value checked"""
-        stop = stop_at_silence_setting(stop_at_silence)
-        return (self._momentum_scope(momentum),
-                _SettingScope(self, '_end_of_speech', lambda v: self.set_end_of_speech(*v), None if stop is None else (True,) + stop),
-                _SettingScope(self, '_speaking_rate', self.set_speaking_rate, speaking_rate_value(speaking_rate)),
-                _SettingScope(self, '_pitch', self.set_pitch, pitch_octaves_value(pitch)))
 
     def synchronize(self):
         self._check(self.lib.tts_synchronize(self.handle))
@@ -1006,16 +1045,11 @@ class Engine(object):
 
     def griffin_lim(self, mag, n_iter, win_length, hop_length, n_fft, init_phase=None, seed=0, want_mse=True, momentum=None,
                     n_frames=None, phase_init=None):
-        """``momentum``: the fast Griffin-Lim momentum in [0, 1) for this call (librosa's and torchaudio's ``momentum``;
-        0 = the reference's plain loop); None: the handle's ``gl_momentum`` option as it stands.
+        """``momentum`` and ``phase_init``: for this call, as SETTINGS has them.
         ``n_frames``: B frame counts -- a ragged batch (tts_griffin_lim_ragged): ``mag`` and ``init_phase`` are padded to
         (B, F, T_max), utterance b is reconstructed from its first n_frames[b] columns alone (the padding never reaches a
-        result), row b of ``wav`` holds its hop (n_frames[b] - 1) samples followed by zeros and ``mse[b]`` is its own.
-        ``phase_init``: how the call starts when ``init_phase`` is None -- 'random' (from ``seed``), 'estimate' (phases
-        estimated from ``mag``, :meth:`phase_estimate`; ``seed`` is then unused) or None: the handle's ``gl_init`` option as it
-        stands.  An explicit ``init_phase`` always wins."""
-        scope = self._momentum_scope(momentum)
-        start = self._phase_init_scope(phase_init)
+        result), row b of ``wav`` holds its hop (n_frames[b] - 1) samples followed by zeros and ``mse[b]`` is its own."""
+        call = self._settings(momentum=momentum, phase_init=phase_init)
         B, F, T = mag.shape
         nf = ragged_frame_counts(n_frames, B, T, hop_length, n_fft) if n_frames is not None else None
         p_mag, _k1 = self._in(mag, np.float32)
@@ -1023,12 +1057,12 @@ class Engine(object):
         wav = self.empty((B, hop_length * (T - 1)))
         mse = self.empty((B,)) if want_mse else None
         if nf is not None:
-            with scope, start:
+            with call:
                 self._check(self.lib.tts_griffin_lim_ragged(self.handle, p_mag, p_init, seed, B, T, _int32_ptr(nf),
                                                             n_iter, win_length, hop_length, n_fft, wav.data_ptr(),
                                                             mse.data_ptr() if mse is not None else None))
             return wav, mse
-        with scope, start:
+        with call:
             self._check(self.lib.tts_griffin_lim(self.handle, p_mag, p_init, seed, B, T, n_iter, win_length, hop_length,
                                                  n_fft, wav.data_ptr(), mse.data_ptr() if mse is not None else None))
         return wav, mse
@@ -1475,37 +1509,13 @@ class Engine(object):
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
                    alignment_stats=None):
-        """``alignment_stats``: None (the handle's setting, off unless ``set_alignment_stats`` changed it), False, True or
-        ``(enabled, pad_id)`` for this call (tts_set_alignment_stats): the call also reduces its alignments to one record per utterance
-        behind its decoder, with no host wait; ``synth_alignment_stats(B)`` fetches them (it waits for the decoder alone).
-        Nothing else of the call changes.
-        ``loudness``: None (the handle's setting, off unless ``set_loudness`` changed it), a target in LUFS or
-        ``(target_lufs, max_peak)`` for this call (tts_set_loudness): the call's final rows are taken to the target by
-        ``loudness_normalize`` at the model's sampling rate, each utterance over the samples its row holds, and
-        ``peak_normalize`` is not applied.
-        ``phase_init`` as in ``griffin_lim``: 'estimate' starts Griffin-Lim from phases estimated from the call's own
-        magnitudes (behind the stretch, at each utterance's own length) when ``init_phase`` is None.
-        ``stop_at_silence``: None, or ``(threshold_db, keep_frames)`` -- end-of-speech stopping for this call
-        (tts_set_end_of_speech): every utterance is reconstructed from its frames up to the last one whose loudest bin is
-        above ``threshold_db``, plus ``keep_frames``; ``wav`` keeps its shape, row b holds hop (n_frames[b] - 1) samples
-        followed by zeros.  The result of a call made with stopping on (here or by ``set_end_of_speech``) carries ``n_frames``,
-        the int32 host array of the B lengths; ``synth_frames`` returns them for any call.
-        ``speaking_rate``: None (the handle's setting, 1.0 unless ``set_speaking_rate`` changed it) or a rate in [0.25, 4]
-        for this call (tts_set_speaking_rate): the magnitudes are time-stretched ahead of Griffin-Lim, ``wav`` is
-        (B, hop (T' - 1)) and ``init_phase`` (B, F, T') with T' = ``stretched_frames(T, rate)``; mel, alignments and linear
-        keep their length T.
-        ``pitch``: None (the handle's setting, 0 unless ``set_pitch`` changed it) or a shift in [-1, 1] octaves for this call
-        (tts_set_pitch): the magnitudes are stretched by rate * 2 ** -pitch, and the resampler takes Griffin-Lim's samples
-        back to the length of the call without pitch.  No shape and no reported length changes but ``init_phase``'s, which is
-        (B, F, ``pitch_frames(T, rate, pitch)``)."""
-        scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
-        start = self._phase_init_scope(phase_init)
-        loud = self._loudness_scope(loudness)
-        diag = self._alignment_stats_scope(alignment_stats)
+        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The seven settings from ``momentum`` on hold
+        for this call alone, as SETTINGS has them."""
+        call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
-        r_call = self._speaking_rate if rate.value is None else rate.value
-        o_call = self._pitch if shift.value is None else shift.value
+        r_call, o_call = call['speaking_rate'], call['pitch']
         # (without init_phase the pitch changes no shape here, and a product of rate and 2 ** -pitch outside [0.25, 4] is the
         #  library's to refuse, at the call)
         T_wav, T_init = synth_frame_counts(T, r_call, o_call if init_phase is not None else 0.0)
@@ -1532,14 +1542,13 @@ class Engine(object):
         mel = _out(want_mel, (B, T, self.cfg.n_mels))
         ali = _out(want_alignments, (n_steps, B, Ts))
         lin = _out(want_linear, (B, T, F))
-        with scope, eos, rate, shift, start, loud, diag:
-            stopping = self._end_of_speech[0]
+        with call:
             self._check(self.lib.tts_synthesize(self.handle, p_ids, B, Ts, byref(sp), p_init, wav.data_ptr(),
                                                 mel.data_ptr() if mel is not None else None,
                                                 ali.data_ptr() if ali is not None else None,
                                                 lin.data_ptr() if lin is not None else None))
         out = dict(wav=wav, mel=mel, alignments=ali, linear=lin)
-        if stopping:
+        if call['stop_at_silence'][0]:
             out['n_frames'] = self.synth_frames(B)
         return out
 
@@ -1556,24 +1565,19 @@ class Engine(object):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
-        ``momentum`` as in ``griffin_lim`` (the option is read when the call is made, not when its work runs);
-        ``stop_at_silence`` as in ``synthesize`` (the lengths: ``wait_host_frames``; such a call returns once its post-net
-        has run); ``speaking_rate`` as in ``synthesize`` (the waveforms are (B, hop (T' - 1))); ``pitch`` as in
-        ``synthesize`` (no shape changes); ``phase_init`` and ``loudness`` as in ``synthesize``; ``alignment_stats`` likewise (the records travel with the
-        waveforms: ``wait_host_alignment_stats``)."""
-        scope, eos, rate, shift = self._synth_scopes(momentum, stop_at_silence, speaking_rate, pitch)
-        start = self._phase_init_scope(phase_init)
-        loud = self._loudness_scope(loudness)
-        diag = self._alignment_stats_scope(alignment_stats)
+        The seven settings from ``momentum`` on hold for this call alone, as SETTINGS has them: they are read when the call is
+        made, not when its work runs.  A call that stops at silence returns once its post-net has run (the lengths:
+        ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``)."""
+        call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
         sp = TtsSynthParams(n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed, 1 if peak_normalize else 0,
                             (1 if want_linear else 0) | (2 if want_alignments else 0))
         t = c_int(-1)
-        r_call = self._speaking_rate if rate.value is None else rate.value
-        T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, r_call, 0.0)   # (the pitch changes no shape)
-        with scope, eos, rate, shift, start, loud, diag:
+        T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, call['speaking_rate'], 0.0)   # (the pitch changes no shape)
+        with call:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))

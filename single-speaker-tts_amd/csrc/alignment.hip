@@ -316,8 +316,8 @@ int tts_text_lengths(tts_handle_t h, const int32_t* ids, int B, int Ts, int pad_
 
 int tts_set_alignment_stats(tts_handle_t h, int enabled, int pad_id) {
     if (!h) return TTS_ERR_INVALID;
-    h->ali.enabled = enabled != 0;
-    if (enabled) h->ali.pad_id = pad_id;
+    h->settings.ali.enabled = enabled != 0;
+    if (enabled) h->settings.ali.pad_id = pad_id;
     return TTS_OK;
 }
 

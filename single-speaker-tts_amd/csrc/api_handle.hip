@@ -693,9 +693,7 @@ int tts_set_end_of_speech(tts_handle_t h, int enabled, float threshold_db, int k
     if (!h) return TTS_ERR_INVALID;
     if (threshold_db != threshold_db) return fail(h, TTS_ERR_INVALID, "set_end_of_speech: threshold_db is NaN");
     if (keep_frames < 0) return fail(h, TTS_ERR_INVALID, "set_end_of_speech: keep_frames < 0");
-    h->eos.enabled = enabled ? 1 : 0;
-    h->eos.threshold_db = threshold_db;
-    h->eos.keep_frames = keep_frames;
+    h->settings.eos = {enabled ? 1 : 0, threshold_db, keep_frames};
     return TTS_OK;
 }
 
@@ -703,7 +701,7 @@ int tts_set_end_of_speech(tts_handle_t h, int enabled, float threshold_db, int k
 int tts_set_speaking_rate(tts_handle_t h, double rate) {
     if (!h) return TTS_ERR_INVALID;
     if (!(rate >= 0.25 && rate <= 4.0)) return fail(h, TTS_ERR_INVALID, "set_speaking_rate: the rate must be finite and lie in [0.25, 4]");
-    h->speaking_rate = rate;
+    h->settings.speaking_rate = rate;
     return TTS_OK;
 }
 
@@ -711,7 +709,7 @@ int tts_set_speaking_rate(tts_handle_t h, double rate) {
 int tts_set_pitch(tts_handle_t h, double octaves) {
     if (!h) return TTS_ERR_INVALID;
     if (!(octaves >= -1.0 && octaves <= 1.0)) return fail(h, TTS_ERR_INVALID, "set_pitch: the shift must be finite and lie in [-1, 1] octaves");
-    h->pitch_octaves = octaves;
+    h->settings.pitch_octaves = octaves;
     return TTS_OK;
 }
 
@@ -755,11 +753,11 @@ int tts_set_option(tts_handle_t h, const char* key, int value) {
     else if (!std::strcmp(key, "gl_pair")) h->gl_pair = value;
     else if (!std::strcmp(key, "gl_momentum")) {
         if (value < 0 || value > 999) return fail(h, TTS_ERR_INVALID, "gl_momentum: thousandths of the momentum, 0 .. 999");
-        h->gl_momentum = value;
+        h->settings.gl_momentum = value;
     }
     else if (!std::strcmp(key, "gl_init")) {
         if (value != 0 && value != 1) return fail(h, TTS_ERR_INVALID, "gl_init: 0 (random phases or the caller's) or 1 (estimated phases)");
-        h->gl_init = value;
+        h->settings.gl_init = value;
     }
     else if (!std::strcmp(key, "gl_wide_from")) h->gl_wide = value < -2 ? -2 : value;
     else if (!std::strcmp(key, "pd_ws")) {

@@ -266,6 +266,36 @@ struct HostIo {
     }
 };
 
+// The synthesis settings of a handle: what tts_set_end_of_speech, tts_set_speaking_rate, tts_set_pitch, tts_set_loudness,
+// tts_set_alignment_stats and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
+// copy when the call is made and read nothing but that copy from then on; with every setting off the call enqueues what it
+// always did.  (The stand-alone Griffin-Lim calls have no such copy: they read the handle's momentum and start.)
+struct SynthSettings {
+    struct {
+        int enabled = 0;
+        float threshold_db = 0.f;
+        int keep_frames = 0;
+    } eos;
+    double speaking_rate = 1.0;   // 1.0 = off
+    double pitch_octaves = 0.0;   // 0 = off
+    struct {
+        bool enabled = false;
+        double target_lufs = -23.0;
+        double max_peak = 1.0;
+        int sampling_rate = 0;
+    } loud;
+    struct {
+        bool enabled = false;
+        int pad_id = 0;
+    } ali;
+    // fast Griffin-Lim: the momentum alpha in thousandths, 0 (default: the reference's plain loop) .. 999; alpha > 0 runs one
+    // iteration per launch whatever gl_pair says (gl_stream_kernel, MOM)
+    int gl_momentum = 0;
+    // how a Griffin-Lim call without explicit `init_phase` starts: 0 (default) = the seed's random phases, 1 = phases estimated
+    // from the call's own magnitudes (phase_init.hip) and handed to the launches as an explicit init_phase would be
+    int gl_init = 0;
+};
+
 }  // namespace tts_api
 using namespace tts_api;   // (the handle is a global type: include/sstts_hip.h declares tts_handle_s)
 
@@ -306,12 +336,6 @@ struct tts_handle_s {
     //  round 5; the option that switched it is gone)
     bool ws_configured = false;
     int gl_pair = 3;                 // Griffin-Lim iterations per launch (1..3) where nothing per-iteration is asked for
-    // fast Griffin-Lim: the momentum alpha in thousandths, 0 (default: the reference's plain loop) .. 999; alpha > 0 runs one
-    // iteration per launch whatever gl_pair says (gl_stream_kernel, MOM)
-    int gl_momentum = 0;
-    // how a Griffin-Lim call without explicit `init_phase` starts: 0 (default) = the seed's random phases, 1 = phases estimated
-    // from the call's own magnitudes (phase_init.hip) and handed to the launches as an explicit init_phase would be
-    int gl_init = 0;
     // First Griffin-Lim launch of a pipelined call that is cut for all compute units (gl_run, `wide_from`): -1 = by the rule
     // in gl_wide_from() below, -2 = never, >= 0 = that launch index.
     int gl_wide = -1;
@@ -409,38 +433,21 @@ struct tts_handle_s {
         float* rw = nullptr;       // streaming [B][2][rw_E], general [B][n_fft + hop (T_max - 1)] (workspace "gl.rag_rw")
     } rag;
 
-    // end-of-speech stopping (tts_set_end_of_speech): the setting, the lengths a call's detection leaves on the device
-    // (workspace "eos.frames": one buffer -- the detection and the Griffin-Lim launches that read it follow each other on the
-    // main stream, call after call), the pinned words the host reads them from, and the last call's lengths
+    // the synthesis settings as the tts_set_* calls and the options "gl_momentum" / "gl_init" left them
+    SynthSettings settings;
+
+    // end-of-speech stopping: the lengths a call's detection leaves on the device (workspace "eos.frames": one buffer -- the
+    // detection and the Griffin-Lim launches that read it follow each other on the main stream, call after call), the pinned
+    // words the host reads them from, and the last call's lengths
     struct {
-        int enabled = 0;
-        float threshold_db = 0.f;
-        int keep_frames = 0;
         int32_t* pinned = nullptr;
         int pinned_room = 0;
         std::vector<int32_t> last;
     } eos;
 
-    // speaking rate (tts_set_speaking_rate): read when a call is made; 1.0 = off, the call then enqueues what it always did
-    double speaking_rate = 1.0;
-
-    // pitch (tts_set_pitch), in octaves: read when a call is made; 0 = off, the call then enqueues what it always did
-    double pitch_octaves = 0.0;
-
-    // loudness (tts_set_loudness): read when a call is made; off = the call then enqueues what it always did
+    // attention diagnostics: last_dev / last_B: the records of the last call on the device (null: that call was made with the
+    // setting off); done: recorded behind its statistics on the stream its decoder ran on
     struct {
-        bool enabled = false;
-        double target_lufs = -23.0;
-        double max_peak = 1.0;
-        int sampling_rate = 0;
-    } loud;
-
-    // attention diagnostics (tts_set_alignment_stats): read when a call is made; off = the call then enqueues what it always did.
-    // last_dev / last_B: the records of the last call on the device (null: that call was made with the setting off); done:
-    // recorded behind its statistics on the stream its decoder ran on
-    struct {
-        bool enabled = false;
-        int pad_id = 0;
         const tts_alignment_stats_t* last_dev = nullptr;
         int last_B = 0;
         Signal done;
@@ -625,6 +632,6 @@ int postnet_impl(tts_handle_t h, const float* mel, int B, int T, float* linear, 
 bool denorm_can_assert(float ref_db, float max_db);
 int denorm_flag_arm(tts_handle_t h, int** flag);
 int denorm_flag_read(tts_handle_t h);
-int gl_wide_from(tts_handle_t h, int B, int Ts, int n_steps, int T, int n_iter);
+int gl_wide_from(tts_handle_t h, const SynthSettings& set, int B, int Ts, int n_steps, int T, int n_iter);
 
 }  // namespace tts_api

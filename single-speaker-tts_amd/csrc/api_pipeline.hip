@@ -15,13 +15,13 @@ namespace tts_api {
 // never 14.74 ms per step, from launch 14: 14.79, 15: 14.49, 16: 14.48, 17: 14.52, 18: 14.56): decoder 0.045 ms per step (both GRU forms; measured 8.9 ms / 200
 // steps beside Griffin-Lim), Griffin-Lim 3.1 ns per frame-iteration on the reduced unit count (0.60 ms per launch of
 // 3 x 64 x 1000).  A function of the call's shape and the handle's options alone: the waveform's bits do not depend on timing.
-int gl_wide_from(tts_handle_t h, int B, int Ts, int n_steps, int T, int n_iter) {
+int gl_wide_from(tts_handle_t h, const SynthSettings& set, int B, int Ts, int n_steps, int T, int n_iter) {
     if (h->gl_wide == -2 || h->reserve_cus <= 0) return -1;
     const int pd = pd_choice(h, B, Ts, h->reserve_cus, true);
     if (pd == 0) return -1;                    // launch-per-layer decoder: sleeper workgroups hold the units through the whole phase
     if (h->gl_wide >= 0) return h->gl_wide;    // (tools: an explicit launch index)
     if (pd != 2) return -1;                    // the streamed-weights decoder outlasts Griffin-Lim
-    const int per_launch = h->gl_momentum > 0 ? 1 : (h->gl_pair < 1 ? 1 : (h->gl_pair > 3 ? 3 : h->gl_pair));   // (as gl_run)
+    const int per_launch = set.gl_momentum > 0 ? 1 : (h->gl_pair < 1 ? 1 : (h->gl_pair > 3 ? 3 : h->gl_pair));   // (as gl_run)
     // The constants were measured on 256 compute units with 32 reserved (224 for Griffin-Lim) at T_s = 150: a launch scales
     // with the units Griffin-Lim really has, a decoder step with the memory length through its attention phase (8.9 of 44.5 us
     // at T_s = 150: keys and values of the whole memory per step, decoder_ws.hip).  On a device of another size the model is
@@ -59,25 +59,16 @@ struct SynthCall {
     bool pipelined = false;
     int* hold_flag = nullptr;    // synth_order_front: the sleepers' flag, where sleepers hold compute units for this call
     std::optional<GemmGroup> proj;   // synth_front: the decoder's output projection, left to the main stream
-    // end-of-speech stopping (tts_set_end_of_speech), as the handle's setting stood when the call was made: the threshold in the
-    // units of `magi` and the frames kept behind the last active one
-    bool eos = false;
-    float eos_thr = 0.f;
-    int eos_keep = 0;
+    // the handle's settings as they stood when the call was made: nothing of the call reads the handle's own
+    SynthSettings set;
+    float eos_thr = 0.f;           // end-of-speech stopping: set.eos.threshold_db in the units of `magi`
     int32_t* d_frames = nullptr;   // the lengths on the device (workspace "eos.frames")
-    // what the speaking rate (tts_set_speaking_rate) and the pitch (tts_set_pitch) make of the call's frames, likewise
+    // what the speaking rate and the pitch make of the call's frames
     SynthShape shape;
     float* mags = nullptr;         // the time-stretch of `magi`, shape.Tg rows: what Griffin-Lim reconstructs from
     float* gl_wav = nullptr;       // a shifted call: Griffin-Lim's hop (Tg - 1) samples, which the resampler takes into `wav`
-    // loudness (tts_set_loudness), as the handle's setting stood when the call was made: the call's final rows are taken to the
-    // target instead of being peak-normalised
-    bool loud = false;
-    double loud_target = 0.0, loud_max_peak = 1.0;
-    int loud_sr = 0;
-    // attention diagnostics (tts_set_alignment_stats), likewise: the sentence lengths are taken from the ids behind the encoder,
-    // the statistics from `align_out` -- the caller's buffer or the handle's -- right behind the decoder, on the decoder's stream
-    bool ali = false;
-    int ali_pad = 0;
+    // attention diagnostics: the sentence lengths are taken from the ids behind the encoder, the statistics from `align_out` --
+    // the caller's buffer or the handle's -- right behind the decoder, on the decoder's stream
     int32_t* ali_n_sent = nullptr;             // this call parity's lengths on the device (workspace "syn.ali_nsent")
     tts_alignment_stats_t* ali_stats = nullptr;   // where the records go: the host form's buffer set, or workspace "syn.ali_stats"
 };
@@ -118,7 +109,7 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "glg.frames", float, (size_t)B * Tg * sp->win_length, glg_fr);
         WS(h, "glg.mse_partial", float, (size_t)B * Tg, glg_ms);
         (void)glg_ph; (void)glg_fr; (void)glg_ms;
-        if (h->gl_momentum > 0 && sp->n_iter > 1) {
+        if (k.set.gl_momentum > 0 && sp->n_iter > 1) {
             allocs = h->ws_allocs;
             WS(h, "glg.mom", float2, (size_t)B * Tg * FP, glg_mc);
             (void)glg_mc;
@@ -158,11 +149,11 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "gl.wav_pitch", float, (size_t)B * sp->hop_length * (size_t)(Tg - 1), glw);
         k.gl_wav = glw;
     }
-    if (k.loud) {   // (the measurement's states and sums, for rows of hop (Tw - 1) samples)
-        const int rc = loudness_workspace(h, B, sp->hop_length * (k.shape.Tw - 1), k.loud_sr);
+    if (k.set.loud.enabled) {   // (the measurement's states and sums, for rows of hop (Tw - 1) samples)
+        const int rc = loudness_workspace(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate);
         if (rc) return rc;
     }
-    if (k.ali) {
+    if (k.set.ali.enabled) {
         // One alignment buffer and one set of scratch: the statistics of a call run behind its decoder on the decoder's stream,
         // in front of whatever lets the next decoder start.  The sentence lengths are written behind the ENCODER, which may run a
         // call ahead on its own stream: one set per call parity, like `memory`.
@@ -181,7 +172,7 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         if (rc) return rc;
     }
     // (estimated initial phases, option "gl_init": the estimate's buffers, for the frames Griffin-Lim reconstructs from)
-    if (h->gl_init && !k.init_phase) {
+    if (k.set.gl_init && !k.init_phase) {
         const int rc = gl_init_workspace(h, B, Tg, c.n_fft);
         if (rc) return rc;
     }
@@ -198,11 +189,11 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     // (momentum: the previous projection, 8 bytes per bin; ONE buffer -- only Griffin-Lim launches touch it, and those of
     //  consecutive calls follow each other on the main stream)
     allocs = h->ws_allocs;
-    if (k.gl_streaming && h->gl_momentum > 0 && sp->n_iter > 1) {
+    if (k.gl_streaming && k.set.gl_momentum > 0 && sp->n_iter > 1) {
         WS(h, "gl.mom", float2, (size_t)B * Tg * FP, gl_mc);
         (void)gl_mc;
     }
-    if (k.eos) {
+    if (k.set.eos.enabled) {
         // the detection's row flags and lengths, the ragged Griffin-Lim's window sum-square tables (gl_rag_tables asks for the same
         // size and finds them in place) and the pinned words the host reads the lengths from: nothing grows in mid-call
         const size_t rw_row = k.gl_streaming ? 2 * (size_t)gl_rw_edge_len(c.n_fft, sp->win_length, sp->hop_length)
@@ -355,7 +346,7 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
     }
     if ((rc = encoder_impl(h, k.ids, B, Ts, k.memory))) return rc;
     // (attention diagnostics: the sentence lengths, where the ids are certainly in place -- beside the encoder that reads them)
-    if (k.ali && (rc = text_lengths_impl(h, k.ids, B, Ts, k.ali_pad, k.ali_n_sent))) return rc;
+    if (k.set.ali.enabled && (rc = text_lengths_impl(h, k.ids, B, Ts, k.set.ali.pad_id, k.ali_n_sent))) return rc;
     if (k.host->enc_done) HIPCHK(h, k.host->enc_done->record(h->stream));
     if (k.pipelined && k.keys_ahead) {
         ProfScope ps(h, ST_ENCODER, 1);
@@ -378,7 +369,7 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
     args.parity = parity;
     args.keys = k.pipelined ? k.keys_ahead : nullptr;
     if ((rc = decoder_impl(h, k.memory, B, Ts, k.sp->n_steps, k.mel, k.align_out, nullptr, args, &k.proj))) return rc;
-    if (k.ali) {
+    if (k.set.ali.enabled) {
         // Attention diagnostics: right behind the decoder on its stream and in front of the records below, so that whatever
         // waits for this decoder -- the next one, an encoder that reuses this parity's lengths -- waits for the statistics too
         if ((rc = alignment_impl(h, k.align_out, k.sp->n_steps, B, Ts, nullptr, nullptr, k.ali_n_sent, k.ali_stats, nullptr, nullptr, nullptr)))
@@ -400,7 +391,7 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
 // Griffin-Lim launches instead of beside this post-net; the detection is 0.06 ms, the read-back and the enqueue a launch gap.
 static int synth_detect(tts_handle_t h, SynthCall& k) {
     const int B = k.B, T = k.T, min_frames = k.shape.min_frames;
-    int rc = speech_frames_impl(h, k.magi, B, T, k.F, k.FP, k.eos_thr, k.eos_keep, min_frames, k.d_frames, nullptr);
+    int rc = speech_frames_impl(h, k.magi, B, T, k.F, k.FP, k.eos_thr, k.set.eos.keep_frames, min_frames, k.d_frames, nullptr);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->eos.pinned, k.d_frames, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -422,7 +413,7 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     int rc = TTS_OK;
     // (a seeded start with iterations needs no initial codes at all: gl_run.  Estimated phases -- option "gl_init" without an
     //  explicit init_phase -- come from this call's magnitudes, which do not exist yet: they are made on the main stream below)
-    const bool estimate = h->gl_init && !k.init_phase;
+    const bool estimate = k.set.gl_init && !k.init_phase;
     const bool phase_on_front = !estimate && k.gl_streaming && k.pipelined && sp->n_iter >= 0 && (k.init_phase != nullptr || sp->n_iter == 0);
     if (k.pipelined) {
         if (k.hold_flag) HIPCHK(h, hipMemsetAsync(k.hold_flag, 1, sizeof(int), pl.front));   // release the held CUs
@@ -448,7 +439,7 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     if (pl.front) HIPCHK(h, pl.post_done[parity].record(h->stream));
     // the lengths (synth_plan.h): all T without end-of-speech stopping -- and a call that stops nowhere IS the uniform call
     const int32_t* detected = nullptr;
-    if (k.eos) {
+    if (k.set.eos.enabled) {
         if ((rc = synth_detect(h, k))) return rc;
         detected = h->eos.pinned;
     }
@@ -467,11 +458,11 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     // post-net (or the stretch) and the first Griffin-Lim launch; from here on they are the call's explicit init_phase
     const float* init_phase = k.init_phase;
     if (estimate && (rc = gl_init_phase(h, gl_mag, nullptr, B, Tg, k.FP, n_frames, h->cfg.n_fft, sp->hop_length, &init_phase))) return rc;
-    const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, B, k.Ts, sp->n_steps, L.T_model, sp->n_iter) : -1;
+    const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, k.set, B, k.Ts, sp->n_steps, L.T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
     float* gl_wav = s.pitch ? k.gl_wav : k.wav;
     // (a shifted call normalises what the resampler leaves; with a loudness target nothing is peak-normalised)
-    const bool gl_peak = sp->peak_normalize != 0 && !s.pitch && !k.loud;
+    const bool gl_peak = sp->peak_normalize != 0 && !s.pitch && !k.set.loud.enabled;
     if (k.gl_streaming)
         rc = gl_run(h, gl_mag, init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
                     gl_peak, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
@@ -483,26 +474,26 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
         // end-of-speech stopping utterance b has hop (n'[b] - 1) samples, and its row ends where the un-shifted call's does.
         const int n_gl = sp->hop_length * (Tg - 1), N_out = sp->hop_length * (s.Tw - 1);
         rc = resample_impl(h, k.gl_wav, B, n_gl, detected ? L.n_samples.data() : nullptr, s.rho, N_out, detected ? L.keep.data() : nullptr, k.wav);
-        if (!rc && sp->peak_normalize && !k.loud) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
+        if (!rc && sp->peak_normalize && !k.set.loud.enabled) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
     }
-    if (k.loud && !rc) {
+    if (k.set.loud.enabled && !rc) {
         // The loudness target: every utterance is measured over the samples its row holds -- hop (n[b] - 1) of the reported
         // lengths with end-of-speech stopping, all of the row otherwise -- and scaled in place, behind whatever made the row.
         std::vector<int32_t> held;
         if (detected)
             for (int b = 0; b < B; ++b) held.push_back(sp->hop_length * (L.reported[(size_t)b] - 1));
-        rc = loudness_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.loud_sr, true, k.loud_target,
-                           k.loud_max_peak, nullptr, nullptr, nullptr);
+        rc = loudness_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.loud.sampling_rate, true,
+                           k.set.loud.target_lufs, k.set.loud.max_peak, nullptr, nullptr, nullptr);
     }
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
 }
 
-// tts_synthesize; `host` carries the upload of tts_synthesize_host
-static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_synth_params_t* sp, const float* init_phase,
-                           float* wav, float* mel_out, float* align_out, float* linear_out, const StageArgs& host) {
-    int rc = check_ready(h);
-    if (rc) return rc;
+// tts_synthesize on a ready handle; `set`: the copy of the handle's settings the entry point took, `host` carries the upload of
+// tts_synthesize_host
+static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32_t* ids, int B, int Ts, const tts_synth_params_t* sp,
+                           const float* init_phase, float* wav, float* mel_out, float* align_out, float* linear_out, const StageArgs& host) {
+    int rc = TTS_OK;
     if (!ids || !sp || !wav || B < 1 || Ts < 1 || sp->n_steps < 1) return fail(h, TTS_ERR_INVALID, "synthesize: bad arguments");
     const tts_config_t& c = h->cfg;
     // n_fft is a model parameter (reference tacotron/params/model.py:13-24): the final Dense has 1 + n_fft / 2 outputs, its
@@ -511,30 +502,20 @@ static int synthesize_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, co
         return fail(h, TTS_ERR_UNSUPPORTED, "synthesize: n_fft must be a power of two between 256 and 4096");
     SynthCall k{ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, &host, sp->n_steps * c.reduction,
                 1 + c.n_fft / 2, gl_fp(c.n_fft), gl_is_streaming(c.n_fft, sp->win_length, sp->hop_length)};
-    // (the settings are read here, once: refusals come before anything is enqueued; rate 1.0 and pitch 0: nothing of this call changes)
-    const std::string refusal = synth_shape(k.T, c.n_fft, sp->hop_length, h->speaking_rate, h->pitch_octaves, h->eos.enabled != 0, &k.shape);
+    k.set = set;
+    // (refusals come before anything is enqueued; rate 1.0 and pitch 0: nothing of this call changes)
+    const std::string refusal = synth_shape(k.T, c.n_fft, sp->hop_length, set.speaking_rate, set.pitch_octaves, set.eos.enabled != 0, &k.shape);
     if (!refusal.empty()) return fail(h, TTS_ERR_INVALID, "synthesize: " + refusal);
     const double* tab_unused = nullptr;   // (the ratio's table, made before anything of this call is enqueued)
     if (k.shape.pitch && (rc = resample_table(h, k.shape.rho, &tab_unused))) return rc;
     if (k.gl_streaming && (rc = gl_prepare(h, k.shape.Tg, sp->win_length, sp->hop_length, c.n_fft))) return rc;
     if (!k.gl_streaming && (sp->win_length < 2 || sp->win_length > c.n_fft || sp->hop_length < 1))
         return fail(h, TTS_ERR_INVALID, "synthesize: need 2 <= win_length <= n_fft, hop_length >= 1");
-    if (h->eos.enabled) {
-        k.eos = true;
-        k.eos_keep = h->eos.keep_frames;
-        if (speech_threshold(h->eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
-            return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
-    }
-    if (h->loud.enabled) {
-        k.loud = true;
-        k.loud_target = h->loud.target_lufs;
-        k.loud_max_peak = h->loud.max_peak;
-        k.loud_sr = h->loud.sampling_rate;
-        if (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX)
-            return fail(h, TTS_ERR_INVALID, "synthesize: a loudness target needs rows of 1 .. 2^31 - 1 samples");
-    }
-    k.ali = h->ali.enabled;
-    k.ali_pad = h->ali.pad_id;
+    if (set.eos.enabled && speech_threshold(set.eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
+        return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
+    if (set.loud.enabled &&
+        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
+        return fail(h, TTS_ERR_INVALID, "synthesize: a loudness target needs rows of 1 .. 2^31 - 1 samples");
     h->ali.last_dev = nullptr;   // (the records of a call before this one are no longer "the last call's")
     if ((rc = synth_workspaces(h, k))) return rc;
     if (k.pipelined && (rc = synth_streams(h))) return rc;
@@ -556,7 +537,9 @@ extern "C" {
 int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_synth_params_t* sp,
                    const float* init_phase, float* wav, float* mel_out, float* align_out, float* linear_out) {
     DeviceScope dev_scope(h);
-    return synthesize_impl(h, ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, StageArgs());
+    const int rc = check_ready(h);
+    if (rc) return rc;
+    return synthesize_impl(h, h->settings, ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, StageArgs());
 }
 
 
@@ -569,18 +552,19 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     if (rc) return rc;
     if (!ids_host || !sp || !ticket || B < 1 || Ts < 1 || sp->n_steps < 1)
         return fail(h, TTS_ERR_INVALID, "synthesize_host: bad arguments");
+    const SynthSettings set = h->settings;   // (the one copy this call and everything it enqueues is made from)
     auto& io = h->hio;
     const int T = sp->n_steps * h->cfg.reduction;
     // (with a speaking rate the waveforms have hop (Tw - 1) samples: the pinned and device buffers are sized for them.  What
     //  the plan refuses is synthesize_impl's to report, below; Tw = stretched_frames(T, speaking_rate) stands either way)
     SynthShape shape;
-    synth_shape(T, h->cfg.n_fft, sp->hop_length, h->speaking_rate, h->pitch_octaves, h->eos.enabled != 0, &shape);
+    synth_shape(T, h->cfg.n_fft, sp->hop_length, set.speaking_rate, set.pitch_octaves, set.eos.enabled != 0, &shape);
     const size_t ids_bytes = (size_t)B * Ts * sizeof(int32_t);
     const size_t n_wav = (size_t)B * sp->hop_length * (size_t)(shape.Tw - 1);
     const bool want_lin = (sp->host_outputs & TTS_HOST_LINEAR) != 0, want_ali = (sp->host_outputs & TTS_HOST_ALIGNMENTS) != 0;
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;
-    const size_t stats_bytes = h->ali.enabled ? (size_t)B * sizeof(tts_alignment_stats_t) : 0;
+    const size_t stats_bytes = set.ali.enabled ? (size_t)B * sizeof(tts_alignment_stats_t) : 0;
     if (!io.out) {
         // The copy stream gets the LOWEST priority: streams of one priority share a few hardware queues in creation order
         // (whatever else the process has created counts; GPU_MAX_HW_QUEUES per priority, as few as 2), and a copy stream that
@@ -623,7 +607,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     host.enc_done = &io.enc[par];
     host.stats_out = stats_bytes ? io.stats[par].dev : nullptr;
     // (the optional outputs of this set were last read by the download of the call three back: same event as the waveforms)
-    rc = synthesize_impl(h, io.ids[par].dev, B, Ts, sp, nullptr, io.wav[par].dev, nullptr, want_ali ? io.ali[par].dev : nullptr,
+    rc = synthesize_impl(h, set, io.ids[par].dev, B, Ts, sp, nullptr, io.wav[par].dev, nullptr, want_ali ? io.ali[par].dev : nullptr,
                          want_lin ? io.lin[par].dev : nullptr, host);
     if (rc) return rc;
     HIPCHK(h, io.ready[par].record(h->stream));

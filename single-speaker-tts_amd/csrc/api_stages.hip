@@ -449,9 +449,9 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
     WS(h, "glg.frames", float, (size_t)B * T * win, frames);
     WS(h, "glg.mse_partial", float, (size_t)B * T, msep);
     // fast Griffin-Lim: the previous projection per bin, allocated only for a call that has a second iteration to use it
-    const float alpha = (float)(h->gl_momentum / 1000.0);
+    const float alpha = (float)(h->settings.gl_momentum / 1000.0);
     float2* mom_c = nullptr;
-    if (h->gl_momentum > 0 && n_iter > 1) {
+    if (h->settings.gl_momentum > 0 && n_iter > 1) {
         WS(h, "glg.mom", float2, (size_t)B * T * Fp, mc);
         mom_c = mc;
     }
@@ -573,10 +573,10 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     // fast Griffin-Lim (option "gl_momentum"): the previous projection per bin, 8 bytes, allocated only for a call that has a
     // second iteration to use it; such a call runs one iteration per launch (gl_stream_kernel, MOM) and is cut for that form.
     // Without momentum nothing below differs from what it was: p.mom_c stays null and the plain instantiations are launched.
-    if (h->gl_momentum > 0 && n_iter > 1) {
+    if (h->settings.gl_momentum > 0 && n_iter > 1) {
         WS(h, "gl.mom", float2, (size_t)B * T * FP, mc);
         p.mom_c = mc;
-        p.mom_alpha = (float)(h->gl_momentum / 1000.0);
+        p.mom_alpha = (float)(h->settings.gl_momentum / 1000.0);
         per_launch = 1;
     }
     // (the cut decides who does which frames, never the waveform's bits: every sample is summed over the frames that cover it in
@@ -1190,7 +1190,7 @@ int gl_init_workspace(tts_handle_t h, int B, int T, int n_fft) {
 int gl_init_phase(tts_handle_t h, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
                   int hop, const float** out) {
     *out = init_phase;
-    if (init_phase || !h->gl_init) return TTS_OK;
+    if (init_phase || !h->settings.gl_init) return TTS_OK;
     int rc = gl_init_workspace(h, B, T, n_fft);
     if (rc) return rc;
     WS(h, "gl.init_est", float, (size_t)B * (1 + n_fft / 2) * T, est);

@@ -377,11 +377,11 @@ int tts_set_loudness(tts_handle_t h, int enabled, double target_lufs, double max
         bool unsupported = false;
         const std::string why = loudness_check(true, 1, 1, nullptr, sampling_rate, true, target_lufs, max_peak, &unsupported);
         if (!why.empty()) return fail(h, unsupported ? TTS_ERR_UNSUPPORTED : TTS_ERR_INVALID, "set_loudness: " + why);
-        h->loud.target_lufs = target_lufs;
-        h->loud.max_peak = max_peak;
-        h->loud.sampling_rate = sampling_rate;
+        h->settings.loud.target_lufs = target_lufs;
+        h->settings.loud.max_peak = max_peak;
+        h->settings.loud.sampling_rate = sampling_rate;
     }
-    h->loud.enabled = enabled != 0;
+    h->settings.loud.enabled = enabled != 0;
     return TTS_OK;
 }
 

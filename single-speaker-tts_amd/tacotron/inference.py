@@ -13,8 +13,8 @@ import os
 import numpy as np
 
 from . import attention_check
-from .._hip import (LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value, silence_keep_frames, speaking_rate_value,
-                    stop_at_silence_setting)
+from .._hip import (LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
+                    silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
 from .model import Mode, Tacotron
@@ -66,6 +66,7 @@ def stop_setting(hp, stop_at_silence_db, silence_keep_ms):
         return None
     if not float(silence_keep_ms) >= 0.0:
         raise ValueError('silence_keep_ms must be >= 0, got {!r}'.format(silence_keep_ms))
+    hp = getattr(hp, 'hparams', hp)   # (a model serves for its hyper-parameters: they are looked at only where stopping is asked for)
     hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
     return stop_at_silence_setting((stop_at_silence_db, silence_keep_frames(ms_to_samples(float(silence_keep_ms), hp.sampling_rate), hop)))
 
@@ -80,33 +81,64 @@ def pad_id():
     return int(dataset_params.vocabulary_dict['pad'])
 
 
+class SynthSettings(object):
+    """The synthesis settings every helper of this layer takes, checked once -- ValueError before an engine is touched, in the
+    order of ``_hip.SETTINGS`` -- and kept as the checked values ``momentum``, ``stop``, ``rate``, ``octaves``, ``phase_init``,
+    ``loud`` and ``check_alignment``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
+
+    ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
+    ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind its last frame whose loudest bin is above that many
+    dB (the reference's TODO at tacotron/inference.py:76-78); the waveforms of a batch are then a LIST of B arrays, each cut to its
+    own length.
+    ``speaking_rate``: 1.0 (None likewise), or a rate in [0.25, 4] -- the magnitudes are time-stretched ahead of Griffin-Lim (the
+    reference's audio.effects.time_stretch, on the one reconstruction the call runs anyway): the waveforms are (B, hop*(T'-1))
+    with T' = ceil(T / rate), ``init_phase`` is (B, F, T').
+    ``pitch``: 0.0 (None likewise), or a shift in [-1, 1] octaves (the reference's audio.effects.pitch_shift on the same
+    reconstruction: the magnitudes are stretched by rate * 2 ** -pitch and the resampler takes Griffin-Lim's samples back); the
+    waveforms keep the shape they have without it, ``init_phase`` is (B, F, ceil(T / (rate * 2 ** -pitch))).
+    ``pitch_semitones``: the same shift as the command line states it, in [-12, 12] semitones, in place of ``pitch``.
+    ``phase_init``: 'random' (the reference's start, from ``seed``), 'estimate' (Griffin-Lim starts from phases estimated from
+    the call's magnitudes, audio.synthesis; far fewer iterations are then needed) or None (the engine's ``gl_init`` option);
+    an ``init_phase`` wins.
+    ``loudness``: None (the engine's setting), a target in LUFS or ``(target_lufs, max_peak)`` -- every utterance is taken to that
+    integrated loudness (ITU-R BS.1770-4, measured over the samples it holds) on the device instead of being peak-normalised.
+    ``check_alignment``: the call also reduces its alignments to one record per utterance on the device
+    (``Engine.alignment_stats``; the sentence lengths are taken from the ids' padding) and answers with the records and
+    ``attention_check.verdict`` of every utterance, an empty tuple where the attention read the sentence cleanly."""
+
+    def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
+                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None):
+        momentum_thousandths(momentum)
+        self.momentum = momentum
+        self.stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
+        self.stop_at_silence_db, self.silence_keep_ms = stop_at_silence_db, silence_keep_ms
+        self.rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
+        self.octaves = pitch_octaves_value(0.0 if pitch is None else pitch) if pitch_semitones is None else pitch_semitones_value(pitch_semitones)
+        phase_init_value(phase_init)
+        self.phase_init = phase_init
+        self.loud = loudness_setting(loudness)
+        self.check_alignment = check_alignment
+
+    def engine_keywords(self):
+        """the settings as ``Engine.synthesize`` / ``Engine.synthesize_host`` take them"""
+        return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
+                    phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None)
+
+    def keywords(self):
+        """the settings as the helpers of this layer take them (``check_alignment`` apart, which not every one takes)"""
+        return dict(momentum=self.momentum, stop_at_silence_db=self.stop_at_silence_db, silence_keep_ms=self.silence_keep_ms,
+                    speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud)
+
+
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
                      momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
                      phase_init='random', loudness=None, check_alignment=False):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
-    of the reference (tacotron/inference.py:170-188) fused into one device call.  ``momentum``: fast Griffin-Lim
-    (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind
-    its last frame above that many dB (the reference's TODO at :76-78); the result is then a LIST of B waveforms, each cut to
-    its own length.  ``speaking_rate``: 1.0, or a rate in [0.25, 4] -- the magnitudes are time-stretched ahead of Griffin-Lim
-    (the reference's audio.effects.time_stretch, on the one reconstruction the call runs anyway): the waveforms are
-    (B, hop*(T'-1)) with T' = ceil(T / rate), ``init_phase`` is (B, F, T').  ``pitch``: 0.0, or a shift in [-1, 1] octaves
-    (the reference's audio.effects.pitch_shift on the same reconstruction: the magnitudes are stretched by rate * 2 ** -pitch
-    and the resampler takes Griffin-Lim's samples back); the waveforms keep the shape they have without it, ``init_phase`` is
-    (B, F, ceil(T / (rate * 2 ** -pitch))).  ``phase_init``: 'random' (the reference's start, from ``seed``), 'estimate'
-    (Griffin-Lim starts from phases estimated from the call's magnitudes, audio.synthesis; far fewer iterations are then
-    needed) or None (the engine's ``gl_init`` option); ``init_phase`` wins.  ``loudness``: None, a target in LUFS or
-    ``(target_lufs, max_peak)`` -- every utterance is taken to that integrated loudness (ITU-R BS.1770-4, measured over the
-    samples it holds) on the device instead of being peak-normalised.  ``check_alignment``: the call also reduces its
-    alignments to one record per utterance on the device (``Engine.alignment_stats``; the sentence lengths are taken from the
-    ids' padding) and the result is ``(waveforms, records, verdicts)`` -- ``attention_check.verdict`` of every utterance, an
-    empty tuple where the attention read the sentence cleanly."""
-    momentum_thousandths(momentum)   # ValueError outside [0, 1), before the engine is touched
-    phase_init_value(phase_init)
-    loud = loudness_setting(loudness)
-    rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
-    octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
+    of the reference (tacotron/inference.py:170-188) fused into one device call.  The settings from ``momentum`` on: as
+    ``SynthSettings`` has them.  With ``stop_at_silence_db`` the result is a list of B waveforms, with ``check_alignment`` it is
+    ``(waveforms, records, verdicts)``."""
+    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
     hp = model.hparams
-    stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
     win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
@@ -114,10 +146,8 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     out = model.engine.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), S, loader.mel_mag_ref_db,
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
-                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, momentum=momentum,
-                                  stop_at_silence=stop, speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud,
-                                  alignment_stats=(True, pad_id()) if check_alignment else None)
-    wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if stop is not None else out['wav'].to_host()
+                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, **s.engine_keywords())
+    wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if s.stop is not None else out['wav'].to_host()
     if check_alignment:
         records = model.engine.synth_alignment_stats(len(sentences))
         return wavs, records, attention_check.verdict(records)
@@ -136,19 +166,13 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     With ``want_linear`` / ``want_alignments`` every item is a tuple ``(wavs, linear, alignments)``: the normalised linear
     spectrograms (B, T, 1025) -- what ``model.output_linear_spec`` is, the thing the reference's ``inference()`` fetches
     (:75-92) -- and the alignments (n_steps, B, T_sent) of the same call, downloaded behind the waveforms (None where not
-    asked for).  ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
-    ``stop_at_silence_db`` / ``silence_keep_ms`` as in ``synthesize_batch``: the waveforms of a batch are then a list of B
-    arrays (views of the pinned rows unless ``copy``), each cut to its own length.  ``speaking_rate`` as in
-    ``synthesize_batch``, ``pitch``, ``phase_init`` and ``loudness`` likewise.  ``check_alignment``: every item additionally
-    carries the batch's alignment records and verdicts, ``(wavs, records, verdicts)`` or ``(wavs, linear, alignments, records,
-    verdicts)``; the 56 bytes per utterance come down with the waveforms."""
-    momentum_thousandths(momentum)   # (a generator: raised at its first item, before the engine is touched)
-    phase_init_value(phase_init)
-    loud = loudness_setting(loudness)
-    rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
-    octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
+    asked for).  The settings from ``momentum`` on: as ``SynthSettings`` has them.  With ``stop_at_silence_db`` the waveforms
+    of a batch are a list of B arrays (views of the pinned rows unless ``copy``), each cut to its own length.  With
+    ``check_alignment`` every item additionally carries the batch's alignment records and verdicts, ``(wavs, records,
+    verdicts)`` or ``(wavs, linear, alignments, records, verdicts)``; the 56 bytes per utterance come down with the waveforms."""
+    # (a generator: a bad setting is refused at its first item, before the engine is touched)
+    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
     hp = model.hparams
-    stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
     win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
@@ -158,7 +182,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     extra = want_linear or want_alignments
 
     def waveforms(ticket):
-        if stop is None:
+        if s.stop is None:
             return eng.wait_host(ticket, copy=copy)
         n_frames = eng.wait_host_frames(ticket)
         return cut_waveforms(eng.wait_host(ticket, copy=copy), n_frames, win_hop)
@@ -179,9 +203,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     for k, ids in enumerate(batches):
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
-                                           want_alignments=want_alignments, momentum=momentum, stop_at_silence=stop,
-                                           speaking_rate=rate, pitch=octaves, phase_init=phase_init, loudness=loud,
-                                           alignment_stats=(True, pad_id()) if check_alignment else None))
+                                           want_alignments=want_alignments, **s.engine_keywords()))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -195,13 +217,12 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
     (tacotron/inference.py:93-101; computed on the host from the downloaded network output with the conversions of
     ``audio.conversion``) -- and ``waveforms`` the Griffin-Lim reconstructions the reference's ``__main__`` makes of them
     (:170-188).  ``momentum`` and ``phase_init`` as in ``synthesize_stream``."""
-    momentum_thousandths(momentum)
-    phase_init_value(phase_init)
+    s = SynthSettings(None, momentum=momentum, phase_init=phase_init)
     loader = dataset_params.dataset_loader
     ref_db, max_db = np.float32(loader.mel_mag_ref_db), np.float32(loader.mel_mag_max_db)
     rng_db = np.float32(abs(float(ref_db)) + abs(float(max_db)))
     for wavs, lin, _ in synthesize_stream(model, batches, n_steps=n_steps, n_iter=n_iter, seed=seed, copy=True, want_linear=True,
-                                          momentum=momentum, phase_init=phase_init):
+                                          **s.keywords()):
         specs = []
         for b in range(lin.shape[0]):
             # inv_normalize_decibel, decibel_to_magnitude (reference audio/conversion.py:81-102, 32-53) in host arithmetic:
@@ -220,17 +241,12 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
     float32 WAV, save_wav(norm=True)).  Returns the list of waveforms.  With ``stop_at_silence_db`` every file ends
     ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames.
-    ``speaking_rate``: as in ``synthesize_batch`` (1.2: a fifth faster); ``pitch``: likewise, in octaves (4 / 12: four semitones up);
-    ``phase_init``: likewise ('estimate': estimated start phases); ``loudness``: likewise -- the files then hold the waveforms at
-    that loudness, not peak-normalised.  ``check_alignment``: the attention diagnostics of ``synthesize_batch`` -- the result
-    is ``(waveforms, report)`` with ``report`` the list of ``{index, verdict, record}`` of ``attention_check.report``, also
-    written to ``alignment_report.json`` beside the wavs."""
-    momentum_thousandths(momentum)
-    phase_init_value(phase_init)
-    loud = loudness_setting(loudness)
-    stop_setting(model_params, stop_at_silence_db, silence_keep_ms)   # (ValueError before anything is loaded)
-    speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
-    pitch_octaves_value(0.0 if pitch is None else pitch)
+    The other settings from ``momentum`` on: as ``SynthSettings`` has them (a ``speaking_rate`` of 1.2: a fifth faster; a
+    ``pitch`` of 4 / 12: four semitones up).  With a ``loudness`` the files hold the waveforms at that loudness, not
+    peak-normalised.  With ``check_alignment`` the result is ``(waveforms, report)`` with ``report`` the list of ``{index,
+    verdict, record}`` of ``attention_check.report``, also written to ``alignment_report.json`` beside the wavs."""
+    # (ValueError before anything is loaded)
+    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -242,9 +258,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     max_length = max(sequence_lengths)
     sentences = np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, momentum=momentum,
-                            stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                            pitch=pitch, phase_init=phase_init, loudness=loud, check_alignment=check_alignment)
+    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, check_alignment=check_alignment, **s.keywords())
     report = None
     if check_alignment:
         wavs, records, _verdicts = wavs
@@ -252,7 +266,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
         with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
             json.dump(report, f, indent=1)
     for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, loud is None)
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, s.loud is None)
     return (list(wavs), report) if check_alignment else list(wavs)
 
 
@@ -292,12 +306,9 @@ def main(argv=None):
     ``--check-alignment``: the attention diagnostics (``tacotron.attention_check``) -- one JSON line per sentence (index,
     verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts."""
     args = parse_args(argv)
-    loud = None if args.loudness is None else loudness_setting((args.loudness, args.max_peak))
-    momentum_thousandths(args.momentum)
-    phase_init_value(args.phase_init)
-    stop_setting(model_params, args.stop_at_silence, args.silence_keep_ms)
-    speaking_rate_value(args.rate)
-    octaves = pitch_semitones_value(args.pitch)
+    s = SynthSettings(model_params, args.momentum, args.stop_at_silence, args.silence_keep_ms, args.rate, pitch_semitones=args.pitch,
+                      phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
+                      check_alignment=args.check_alignment)
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -314,9 +325,7 @@ def main(argv=None):
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
     wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                momentum=args.momentum, stop_at_silence_db=args.stop_at_silence,
-                                silence_keep_ms=args.silence_keep_ms, speaking_rate=args.rate, pitch=octaves,
-                                phase_init=args.phase_init, loudness=loud, check_alignment=args.check_alignment)
+                                check_alignment=args.check_alignment, **s.keywords())
     if args.check_alignment:
         wavs, report = wavs
         for row in report:

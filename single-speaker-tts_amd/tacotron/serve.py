@@ -8,10 +8,10 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, speaking_rate_value, synth_frame_counts, synth_lengths
+from .._hip import synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
 from . import attention_check
-from .inference import SILENCE_KEEP_MS, cut_waveforms, pad_id, pad_sentence, stop_setting
+from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, pad_id, pad_sentence, synthesize_stream
 from .model import Mode, Tacotron
 from .params import dataset_params, model_params
 
@@ -28,23 +28,14 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
                               silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random',
                               loudness=None):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
-    constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86); ``momentum``: fast Griffin-Lim
-    (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db``: every utterance is reconstructed only up to
-    ``silence_keep_ms`` behind its last frame whose loudest bin is above that many dB (``Engine.speech_frames`` on the
-    normalised spectrograms, then one ragged Griffin-Lim call) and returned at its own length.  ``speaking_rate``: 1.0, or a
-    rate in [0.25, 4] -- the magnitudes are time-stretched (``Engine.stretch_magnitudes``) ahead of Griffin-Lim: T' =
-    ceil(T / rate) frames, ``init_phase`` (B, F, T'), lengths min(T', max(min_frames, ceil(n / rate))).  ``pitch``: 0.0, or a
-    shift in [-1, 1] octaves -- the magnitudes are stretched by rate * 2 ** -pitch instead (``init_phase`` has that many
-    frames) and ``Engine.resample`` takes Griffin-Lim's samples by 2 ** -pitch back to the lengths they have without it.
-    ``phase_init``: 'random', 'estimate' (start phases estimated from the magnitudes Griffin-Lim runs on) or None (the
-    engine's option), as in ``audio.synthesis``.  ``loudness``: None, a target in LUFS or ``(target_lufs, max_peak)`` --
-    ``Engine.loudness_normalize`` takes every waveform there, measured over its own samples."""
-    momentum_thousandths(momentum)
-    phase_init_value(phase_init)
-    loud = loudness_setting(loudness)
-    stop = stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
-    rate = speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
-    octaves = pitch_octaves_value(0.0 if pitch is None else pitch)
+    constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86).  The settings from ``momentum`` on mean
+    what ``inference.SynthSettings`` says, composed here from the engine's stages: with ``stop_at_silence_db``
+    ``Engine.speech_frames`` on the normalised spectrograms, then one ragged Griffin-Lim call, every utterance returned at its own
+    length; with a ``speaking_rate`` or a ``pitch`` ``Engine.stretch_magnitudes`` by rate * 2 ** -pitch ahead of Griffin-Lim
+    (``init_phase`` has that many frames; lengths min(T', max(min_frames, ceil(n / rate)))) and ``Engine.resample`` by 2 ** -pitch
+    behind it; with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples."""
+    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness)
+    stop, rate, octaves, loud = s.stop, s.rate, s.octaves, s.loud
     rho = float(np.exp2(-np.float64(octaves)))
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
@@ -102,18 +93,12 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     before it sends more).  ``pipelined=True`` keeps three batches in flight for OFFLINE streams whose batches are all
     available: batch k is then yielded only after batch k + 2 has been pulled from the generator (the last one when the
     generator ends), which on a request-driven generator would hold every answer back by two requests.
-    ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.  ``stop_at_silence_db`` /
-    ``silence_keep_ms``: as in ``inference.synthesize_batch`` -- every waveform ends behind its utterance's speech;
-    ``speaking_rate``, ``pitch``, ``phase_init`` and ``loudness`` likewise: with a loudness every answer of the stream comes at
-    the same level.  ``check_alignment``: every answer is ``(waveforms, records, verdicts)`` -- the alignment records of the
-    batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip as the
-    waveforms: a bad utterance can be flagged before it is played."""
-    momentum_thousandths(momentum)   # (a generator: raised at its first item, before a model is made)
-    phase_init_value(phase_init)
-    loud = loudness_setting(loudness)
-    stop_setting(model_params, stop_at_silence_db, silence_keep_ms)
-    speaking_rate_value(1.0 if speaking_rate is None else speaking_rate)
-    pitch_octaves_value(0.0 if pitch is None else pitch)
+    The settings from ``momentum`` on: as ``inference.SynthSettings`` has them -- with a loudness every answer of the stream
+    comes at the same level.  With ``check_alignment`` every answer is ``(waveforms, records, verdicts)`` -- the alignment
+    records of the batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip
+    as the waveforms: a bad utterance can be flagged before it is played."""
+    # (a generator: a bad setting is refused at its first item, before a model is made)
+    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
@@ -123,9 +108,7 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
             ids = pre_process_sentences(sentences, dataset)
             fetches = [model.output_linear_spec] + ([model.alignment_history] if check_alignment else [])
             fetched = model.run(fetches, {model.inp_sentences: ids})
-            wavs = post_process_spectrograms(fetched[0], model.engine, momentum=momentum, stop_at_silence_db=stop_at_silence_db,
-                                             silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate, pitch=pitch,
-                                             phase_init=phase_init, loudness=loud)
+            wavs = post_process_spectrograms(fetched[0], model.engine, **s.keywords())
             if check_alignment:   # (the same kernels as inside a pipelined call, on the alignments this loop fetched anyway)
                 records = model.engine.alignment_stats(fetched[1], n_sent=model.engine.text_lengths(ids, pad_id()))
                 yield wavs, records, attention_check.verdict(records)
@@ -133,11 +116,8 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
                 yield wavs
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
-    from .inference import synthesize_stream
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
-    for item in synthesize_stream(model, batches, peak_normalize=False, copy=True, momentum=momentum,
-                                  stop_at_silence_db=stop_at_silence_db, silence_keep_ms=silence_keep_ms, speaking_rate=speaking_rate,
-                                  pitch=pitch, phase_init=phase_init, loudness=loud, check_alignment=check_alignment):
+    for item in synthesize_stream(model, batches, peak_normalize=False, copy=True, check_alignment=check_alignment, **s.keywords()):
         wavs = item[0] if check_alignment else item
         listed = [wavs[b] for b in range(len(wavs))]
         yield (listed, item[1], item[2]) if check_alignment else listed

@@ -62,9 +62,5 @@ def no_device_engine():
     eng = H.Engine.__new__(H.Engine)
     eng.handle = None
     eng.lib = None
-    eng._speaking_rate = 1.0
-    eng._pitch = 0.0
-    eng._gl_momentum = 0
-    eng._gl_init = 0
-    eng._end_of_speech = (False, 0.0, 0)
+    eng._init_settings()
     return eng

@@ -1,7 +1,11 @@
 """What the Python binding (_hip.py) refuses before it reaches the library, pinned: the exception type and the whole message of
 every refusing call of the stages that take per-utterance lengths, strides or one-or-many waveforms, and of the shape refusals
 of evaluate / teacher_forced.  The calls are made on an Engine that has no handle and no library.  The literals are the
-binding's answers as they stood before its helpers were folded: a change of a helper that moves a message fails here."""
+binding's answers as they stood before its helpers were folded: a change of a helper that moves a message fails here.
+The per-call synthesis settings go through every call that takes them; ``check_alignment`` has no refusal of its own (any true
+value switches the diagnostics on): what it hands the engine is pinned in test_settings_host.py."""
+import types
+
 import numpy as np
 import pytest
 
@@ -48,6 +52,30 @@ GROUPS = [
      {'[10, 7]': 'n_frames: shape (2,) for a batch of 3', '[[10, 7, 1]]': 'n_frames: shape (1, 3) for a batch of 3', '10': 'n_frames: shape () for a batch of 3',
       '[10, 0, 1]': 'n_frames[1] = 0 is not in 1 .. T = 10', '[10, 11, 1]': 'n_frames[1] = 11 is not in 1 .. T = 10',
       '[10.0, 7.0, 1.0]': 'n_frames must be integers, got float64'}),
+    # the per-call synthesis settings: every keyword through every call that takes it
+    (['H.momentum_thousandths(BAD)', 'eng.griffin_lim(GMAG, 2, 1102, 275, 2048, momentum=BAD)',
+      'Y.griffin_lim_v2(GMAG[0], 1102, 275, 2048, 2, engine=eng, momentum=BAD)',
+      'next(I.inference_stream(None, [IDS], momentum=BAD))'] + [w.format('momentum') for w in WRAPPERS],
+     dict({v: 'momentum must be in [0, 1), got ' + v for v in ('nan', '1.0', '-0.1', '1.5', 'inf')},
+          **{"'fast'": "could not convert string to float: 'fast'"})),
+    (['H.stop_at_silence_setting(BAD)'] + [w.format('stop_at_silence') for w in WRAPPERS[:2]],
+     dict({v: 'stop_at_silence must be None or (threshold_db, keep_frames), got ' + v for v in ('5', "'quiet'", '(-30.0, 2, 1)', '(-30.0,)')},
+          **{'(nan, 2)': 'stop_at_silence: threshold_db is NaN', '(-30.0, -1)': 'stop_at_silence: keep_frames must be an integer >= 0, got -1',
+             '(-30.0, 1.5)': 'stop_at_silence: keep_frames must be an integer >= 0, got 1.5'})),
+    (['H.loudness_setting(BAD)', 'eng.set_loudness(BAD)'] + [w.format('loudness') for w in WRAPPERS],
+     dict({v: 'loudness must be None, a target in LUFS or (target_lufs, max_peak), got ' + v for v in ('(-23.0,)', '(-23.0, 1.0, 2.0)')},
+          **{"'loud'": "loudness: target_lufs and max_peak must be numbers, got 'loud', 1.0",
+             "(-23.0, 'x')": "loudness: target_lufs and max_peak must be numbers, got -23.0, 'x'",
+             'nan': 'loudness: the target must be a finite number of LUFS, got nan', 'inf': 'loudness: the target must be a finite number of LUFS, got inf',
+             '(-23.0, 0.0)': 'loudness: max_peak must be finite and positive, got 0.0', '(-23.0, nan)': 'loudness: max_peak must be finite and positive, got nan'})),
+    (['H.alignment_stats_setting(BAD)'] + [w.format('alignment_stats') for w in WRAPPERS[:2]],
+     dict({v: 'alignment_stats must be None, a bool or (enabled, pad_id), got ' + v for v in ('3', "'on'", '(True,)', '(True, 1.5)', '(1, 0)', '(True, 0, 0)', '1.0')},
+          **{'(True, 2 ** 31)': 'alignment_stats must be None, a bool or (enabled, pad_id), got (True, 2147483648)'})),
+    # ... and this layer's own two, through the five calls above the engine (a model that has hyper-parameters and nothing else)
+    ([w.replace('(None, ', '(M, ').format('stop_at_silence_db') for w in WRAPPERS[2:]],
+     {'nan': 'stop_at_silence: threshold_db is NaN', "'quiet'": "could not convert string to float: 'quiet'", "''": "could not convert string to float: ''"}),
+    ([w.replace('(None, ', '(M, ').format('stop_at_silence_db=-40.0, silence_keep_ms') for w in WRAPPERS[2:]],
+     dict({v: 'silence_keep_ms must be >= 0, got ' + v for v in ('-1.0', 'nan', '-inf')}, **{"'long'": "could not convert string to float: 'long'"})),
 ]
 
 F0_LAGS = ' are not 2 <= tau_min <= tau_max <= 1024 (tts_f0_max_lag): fmin is at least sampling_rate / 1024'
@@ -143,7 +171,7 @@ def names():
                 PMAG=np.ones((3, 129, 10), f32), PROWS=np.ones((3, 10, 129), f32), MEL=np.ones((3, 12, 80), f32),
                 A=np.ones((3, 12, 14), f32), B=np.ones((3, 20, 14), f32), X=np.zeros((2, 5000), f32), FA=np.zeros((2, 40), f32),
                 FB=np.zeros((2, 55), f32), PATH=np.zeros((2, 94, 2), np.int32), GMAG=np.ones((1, 1025, 12), f32),
-                TMEL=np.zeros((2, 3, 400), f32), TLIN=np.zeros((2, 15, 1025), f32))
+                TMEL=np.zeros((2, 3, 400), f32), TLIN=np.zeros((2, 15, 1025), f32), M=types.SimpleNamespace(hparams=pkg('tacotron.params').model_params))
 
 
 def _refusal(call, names):
@@ -162,4 +190,4 @@ def test_every_refusal_keeps_its_type_and_text(names):
             for call in calls:
                 assert _refusal(call, dict(names, BAD=eval(bad, names))) == (ValueError, message), (call, bad)
                 n += 1
-    assert n == len(SINGLE) + 6 * 13 + 7 * 3 + 7 * 4 + 5 * 10 + 6 + 8 * 12 + 8 + 6
+    assert n == len(SINGLE) + 6 * 13 + 7 * 3 + 7 * 4 + 5 * 10 + 6 + 8 * 12 + 8 + 6 + 6 * 11 + 7 * 3 + 8 * 9 + 8 * 3 + 3 * 5 + 4 * 5

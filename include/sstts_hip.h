@@ -323,6 +323,15 @@ int tts_speech_frames(tts_handle_t h, const float* spec, int B, int T, int F, in
 #define TTS_SPEECH_NORMALIZED_DB 0
 #define TTS_SPEECH_MAGNITUDE_POWER 1
 int tts_speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
+/* Both ends of silence_interval_from_spectrogram (audio/effects.py:218-232 returns (trim_start, trim_end); tts_speech_frames
+ * takes the end alone).  spec, row_stride, the activity rule and its NaN / Inf rules as tts_speech_frames has them:
+ *   first_active[b] = the smallest active t, last_active[b] = the largest; both -1 when utterance b has no active frame (the
+ *                     reference's None).  DEVICE int32 [B] each; last_active is what tts_speech_frames reports.
+ * Exact, and the same whatever B and the utterance's place in the batch.  Two launches (the rows, then the utterances),
+ * asynchronous, no model needed; profile stage "speech_end".  TTS_ERR_INVALID, before anything is enqueued: B, T, F < 1,
+ * row_stride < F, a NaN threshold, a NULL spec, first_active or last_active. */
+int tts_speech_interval(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold,
+                        int32_t* first_active, int32_t* last_active);
 
 /* ---- speaking rate ---------------------------------------------------------------------- */
 /* time_stretch (audio/effects.py:46-88) as far as it reaches Griffin-Lim: the reference runs librosa 0.6 phase_vocoder(stft, rate)
@@ -691,6 +700,47 @@ int tts_alignment_stats(tts_handle_t h, const float* alignments, int n_steps_max
  * ids DEVICE int32 [B][Ts], n_sent DEVICE int32 [B].  Asynchronous on the handle's stream (1 launch); profile stage
  * "alignment".  TTS_ERR_INVALID: a NULL or misaligned pointer, B or Ts < 1. */
 int tts_text_lengths(tts_handle_t h, const int32_t* ids /* DEVICE [B][Ts] */, int B, int Ts, int pad_id, int32_t* n_sent /* DEVICE [B] */);
+
+/* ---- the join: an edit list over the rows of a waveform batch ------------------------------- */
+/* Pieces of the rows of wav DEVICE [B][N], laid one behind the other into the rows of out DEVICE [G][N_out], with pauses or
+ * cross-fades between them (no reference counterpart: the reference writes one file per line and stops at max_iterations
+ * frames).  Piece p is samples [first, first + count) of row `row`; a row may be used any number of times, or never, in any
+ * order.  group[p] (HOST int32 [P]) is the output row of piece p: non-decreasing over 0 .. G - 1, no group empty.
+ *   layout   within a group piece p starts at output offset o[p]: 0 for the group's first piece, o[p+1] = o[p] + count[p] +
+ *            gap[p]; the group is n_out[g] = o[last] + count[last] samples long, and the gap of a group's last piece is ignored.
+ *   fades    piece p fades over f_p = min(fade, count[p] / 2) samples (integer division) at either edge: the gain of its sample i
+ *            is s((2 i + 1) / (2 f_p)) for i < f_p, s((2 (count - 1 - i) + 1) / (2 f_p)) for i >= count - f_p and 1 elsewhere,
+ *            with s(t) = (t * t) * (3.0 - 2.0 * t).  Numerator and denominator are exact integers converted to double, and
+ *            every operation is an individually rounded IEEE double operation.
+ *   overlap  a negative gap lays the head of piece p + 1 over the tail of piece p -- a cross-fade, s(t) + s(1 - t) being 1 up to
+ *            rounding.  -gap[p] <= min(f_p, f_p+1) is required, so no output sample has more than two contributors and every
+ *            overlap lies inside both fades.
+ *   samples  with two contributors, out = (float)((double)x_a * w_a + (double)x_b * w_b), the earlier piece first, each product
+ *            and the sum individually rounded, one rounding to float; with one contributor of gain w != 1, (float)((double)x * w);
+ *            with one contributor of gain 1 the source's bits.  Gap samples and [n_out[g], N_out) are +0.0.  A NaN source sample
+ *            is NaN in exactly the output samples it contributes to.
+ * Every element of out[G][N_out] is written exactly once per call: no atomics, no memset, nothing read from out; the result
+ * depends neither on what the handle ran before nor on how the list is cut into launches (the bits of tests/join_oracle.py).
+ * The list travels by value, 128 pieces per launch: a call makes ceil(P / 128) launches, uploads nothing and waits for nothing.
+ * Asynchronous on the handle's stream, no model needed; profile stage "join".
+ * TTS_ERR_INVALID with a message, before anything is enqueued: a NULL pointer; B, N, P or G < 1; fade < 0 or above
+ * tts_join_max_fade(); P above tts_join_max_pieces(); G above P; a row outside 0 .. B - 1, a first outside 0 .. N - 1, a count outside
+ * 1 .. N - first; a group list that does not start at 0, decreases, skips a group or does not end at G - 1; a gap below
+ * -min(f_p, f_p+1); N_out below the largest n_out[g] or G * N_out above 2^33; a misaligned buffer (4 bytes). */
+typedef struct tts_join_piece {
+    int32_t row, first, count, gap;
+} tts_join_piece_t;   /* HOST */
+/* Host only, no handle and no device: the checks of the list, and every group's length (tts_last_error(NULL) has the reason of
+ * a refusal). */
+int tts_join_plan(const tts_join_piece_t* pieces, int P, const int32_t* group /* HOST [P] */, int G, int B, int N, int fade,
+                  int64_t* n_out /* HOST [G] */);
+int tts_join(tts_handle_t h, const float* wav /* DEVICE [B][N] */, int B, int N, const tts_join_piece_t* pieces, int P,
+             const int32_t* group /* HOST [P] */, int G, int fade, int N_out, float* out /* DEVICE [G][N_out] */);
+/* Host only: the most pieces a call takes (4096), the longest fade in samples (2^20), and the output samples a workgroup
+ * writes (512). */
+int tts_join_max_pieces(void);
+int tts_join_max_fade(void);
+int tts_join_tile(void);
 
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,

@@ -79,6 +79,12 @@ class TtsAlignmentStats(ctypes.Structure):
 ALIGNMENT_RECORD = np.dtype([(name, np.int32) for name, _t in TtsAlignmentStats._fields_[:12]] + [('focus_sum', np.float64)])
 
 
+class TtsJoinPiece(ctypes.Structure):
+    """tts_join_piece_t: samples [first, first + count) of a row and the pause behind them; a row of the (P, 4) int32 arrays
+    ``Engine.join`` hands the library"""
+    _fields_ = [('row', c_int32), ('first', c_int32), ('count', c_int32), ('gap', c_int32)]
+
+
 _PROTOTYPES = {
     'tts_alignment_stats': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
@@ -86,6 +92,12 @@ _PROTOTYPES = {
     'tts_set_alignment_stats': (c_int, [c_void_p, c_int, c_int]),
     'tts_synth_alignment_stats': (c_int, [c_void_p, c_void_p, c_int]),
     'tts_wait_host_alignment_stats': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
+    'tts_speech_interval': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    'tts_join_plan': (c_int, [c_void_p, c_int, POINTER(c_int32), c_int, c_int, c_int, c_int, POINTER(c_int64)]),
+    'tts_join': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, POINTER(c_int32), c_int, c_int, c_int, c_void_p]),
+    'tts_join_max_pieces': (c_int, []),
+    'tts_join_max_fade': (c_int, []),
+    'tts_join_tile': (c_int, []),
     'tts_version': (c_char_p, []),
     'tts_default_config': (c_int, [POINTER(TtsConfig)]),
     'tts_create': (c_int, [POINTER(TtsConfig), c_int, POINTER(c_void_p)]),
@@ -503,6 +515,75 @@ def alignment_lengths(lengths, B, hi, name, bound):
     if n.shape != (B,) or n.dtype.kind not in 'iu':
         raise ValueError('{}: {} integers are needed, got shape {} of {}'.format(name, B, n.shape, n.dtype))
     return _checked_lengths(n, hi, name, bound)
+
+
+JOIN_MAX_PIECES = 4096      # tts_join_max_pieces()
+JOIN_MAX_FADE = 1 << 20     # tts_join_max_fade()
+JOIN_MAX_SAMPLES = 1 << 33  # the most output samples G * N_out of a call
+
+
+def join_fades(counts, fade):
+    """f_p = min(fade, count[p] // 2) of every piece: the samples either edge fades over"""
+    return np.minimum(np.int64(fade), np.asarray(counts, dtype=np.int64) // 2)
+
+
+def join_list(pieces, groups, B, N, fade):
+    """The edit list of a join on a batch (B, N) as ``(pieces, groups, G, n_out)``: ``pieces`` a contiguous int32 array (P, 4) of
+    ``row, first, count, gap`` -- what tts_join_piece_t holds --, ``groups`` a contiguous int32 array (P,) (None: one group) and
+    ``n_out`` the int64 lengths of the G groups.  Checked as tts_join_plan checks it, in its order -- ValueError, raised before a
+    handle or the library is touched."""
+    try:
+        q = np.asarray(pieces)
+    except (TypeError, ValueError):
+        q = None
+    if q is None or q.ndim != 2 or q.shape[1] != 4 or q.shape[0] < 1 or q.dtype.kind not in 'iu':
+        raise ValueError('join: pieces must be (P, 4) integers (row, first, count, gap) with P >= 1, got {!r}'.format(
+            None if q is None else (q.shape, q.dtype)))
+    P = int(q.shape[0])
+    if groups is None:
+        g = np.zeros(P, dtype=np.int64)
+    else:
+        g = np.asarray(groups)
+        if g.shape != (P,) or g.dtype.kind not in 'iu':
+            raise ValueError('join: groups must be {} integers, got shape {} of {}'.format(P, g.shape, g.dtype))
+    if isinstance(fade, (bool, np.bool_)) or not isinstance(fade, (int, np.integer)) or fade < 0:
+        raise ValueError('join: fade must be an integer >= 0, got {!r}'.format(fade))
+    if B < 1 or N < 1:
+        raise ValueError('join: need B, N >= 1, got {}, {}'.format(B, N))
+    if fade > JOIN_MAX_FADE:
+        raise ValueError('join: fade = {} is larger than tts_join_max_fade() = {}'.format(fade, JOIN_MAX_FADE))
+    if P > JOIN_MAX_PIECES:
+        raise ValueError('join: {} pieces are more than tts_join_max_pieces() = {}'.format(P, JOIN_MAX_PIECES))
+    q64, g64 = q.astype(np.int64), g.astype(np.int64)
+    if np.abs(q64).max() >= 2 ** 31 or np.abs(g64).max() >= 2 ** 31:
+        raise ValueError('join: the list must hold 32-bit integers')
+    for p, (row, first, count, _gap) in enumerate(q64.tolist()):
+        if not 0 <= row < B:
+            raise ValueError('join: row[{}] = {} is not in 0 .. B - 1 = {}'.format(p, row, B - 1))
+        if not 0 <= first < N:
+            raise ValueError('join: first[{}] = {} is not in 0 .. N - 1 = {}'.format(p, first, N - 1))
+        if not 1 <= count <= N - first:
+            raise ValueError('join: count[{}] = {} is not in 1 .. N - first = {}'.format(p, count, N - first))
+    gl = g64.tolist()
+    if gl[0] != 0:
+        raise ValueError('join: group[0] = {}: the groups start at 0'.format(gl[0]))
+    for p in range(1, P):
+        if gl[p] - gl[p - 1] not in (0, 1):
+            raise ValueError('join: group[{}] = {} follows {}: the groups are non-decreasing and none is empty'.format(p, gl[p], gl[p - 1]))
+    G = gl[-1] + 1
+    f = join_fades(q64[:, 2], fade).tolist()
+    n_out = np.zeros(G, dtype=np.int64)
+    o = 0
+    for p, (_row, _first, count, gap) in enumerate(q64.tolist()):
+        if p + 1 == P or gl[p + 1] != gl[p]:
+            n_out[gl[p]] = o + count
+            o = 0
+            continue
+        room = min(f[p], f[p + 1])
+        if gap < -room:
+            raise ValueError('join: gap[{}] = {} overlaps more than min(f[{}], f[{}]) = {} samples'.format(p, gap, p, p + 1, room))
+        o += count + gap
+    return np.ascontiguousarray(q, dtype=np.int32), np.ascontiguousarray(g, dtype=np.int32), G, n_out
 
 
 def stretch_frame_counts(n_frames, B, T):
@@ -1134,6 +1215,97 @@ class Engine(object):
         self._check_or_free(self.lib.tts_speech_frames(self.handle, p_spec, B, T, F, stride, float(threshold), int(keep_frames), int(min_frames),
                                                        n_frames.data_ptr(), last.data_ptr()), n_frames, last)
         return n_frames, last
+
+    def speech_interval(self, spec, threshold, row_stride=None):
+        """tts_speech_interval: both ends of the reference's ``silence_interval_from_spectrogram`` on ``spec`` (B, T, F),
+        time-major, a host array or a device buffer, with ``row_stride`` as in :meth:`speech_frames`.  Returns device int32
+        arrays ``(first_active, last_active)`` of B entries: the first and the last frame t with np.max(spec[b, t]) >
+        ``threshold`` (strict; a row that holds a NaN is silent), both -1 where no frame is active.  ``last_active`` is what
+        :meth:`speech_frames` reports."""
+        if len(spec.shape) != 3 or min(spec.shape) < 1:
+            raise ValueError('speech_interval: spec must be a non-empty (B, T, F), got shape {}'.format(tuple(spec.shape)))
+        B, T, F = (int(d) for d in spec.shape)
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError('speech_interval: the threshold is NaN')
+        spec, stride = _strided_rows('speech_interval', spec, B, T, F, row_stride)
+        p_spec, _k = self._in(spec, np.float32)
+        first, last = self.empty((B,), np.int32), self.empty((B,), np.int32)
+        self._check_or_free(self.lib.tts_speech_interval(self.handle, p_spec, B, T, F, stride, threshold, first.data_ptr(), last.data_ptr()),
+                            first, last)
+        return first, last
+
+    # ------------------------------------------------------------------ the join
+    def join_max_pieces(self):
+        """tts_join_max_pieces: the most pieces :meth:`join` takes in one call."""
+        return int(self.lib.tts_join_max_pieces())
+
+    def join_max_fade(self):
+        """tts_join_max_fade: the longest fade of :meth:`join`, in samples."""
+        return int(self.lib.tts_join_max_fade())
+
+    def join_tile(self):
+        """tts_join_tile: the output samples one workgroup of the join writes."""
+        return int(self.lib.tts_join_tile())
+
+    def join_plan(self, shape, pieces, groups=None, fade=0):
+        """tts_join_plan, host only: the lengths ``n_out`` (int64 (G,)) of the groups that ``pieces`` -- (P, 4) integers ``row,
+        first, count, gap`` -- and ``groups`` (P integers, non-decreasing from 0, None: one group) make of a batch of ``shape``
+        (B, N).  ValueError for a list tts_join refuses (``join_list``), raised before the library is reached."""
+        if len(shape) != 2:
+            raise ValueError('join_plan: the shape of a batch (B, N) is needed, got {!r}'.format(tuple(shape)))
+        B, N = int(shape[0]), int(shape[1])
+        q, g, G, n_out = join_list(pieces, groups, B, N, fade)
+        out = np.zeros(G, dtype=np.int64)
+        rc = self.lib.tts_join_plan(q.ctypes.data, q.shape[0], _int32_ptr(g), G, B, N, int(fade), out.ctypes.data_as(POINTER(c_int64)))
+        if rc != TTS_OK:
+            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        assert (out == n_out).all(), (out, n_out)
+        return out
+
+    def join(self, wavs, pieces, groups=None, fade=0, N_out=None):
+        """tts_join: pieces of the rows of ``wavs`` (B, N) -- a host array, which is uploaded, or a device buffer, which is read in
+        place -- laid one behind the other into G output rows.  ``pieces``: (P, 4) integers ``row, first, count, gap`` -- samples
+        [first, first + count) of a row, and the pause behind the piece in samples (negative: a cross-fade of that many samples
+        with the next piece, at most min(f_p, f_p+1)); ``groups``: the output row of every piece, non-decreasing from 0 (None: one
+        row); ``fade``: the samples either edge of a piece fades over (f_p = min(fade, count // 2)).  include/sstts_hip.h has the
+        definition: the bits of tests/join_oracle.py.
+
+        Returns ``(out, n_out)``: a fresh device array (G, N_out) and the int64 host lengths (G,) -- row g holds n_out[g] samples
+        followed by +0.0.  ``N_out`` None: the largest length rounded up to a multiple of 4 (rows that start on a 16-byte
+        boundary); otherwise at least the largest length.  ValueError for what the library refuses, raised before it is reached."""
+        if len(wavs.shape) != 2 or min(wavs.shape) < 1:
+            raise ValueError('join: a batch (B, N) is needed, got shape {}'.format(tuple(wavs.shape)))
+        B, N = (int(d) for d in wavs.shape)
+        q, g, G, n_out = join_list(pieces, groups, B, N, fade)
+        longest = int(n_out.max())
+        if N_out is None:
+            N_out = (longest + 3) // 4 * 4
+        if int(N_out) != N_out or not longest <= N_out < 2 ** 31:
+            raise ValueError('join: N_out = {!r} is not in n_out.max() = {} .. 2^31 - 1'.format(N_out, longest))
+        if G * int(N_out) > JOIN_MAX_SAMPLES:
+            raise ValueError('join: G * N_out = {} output samples are more than 2^33 = {}'.format(G * int(N_out), JOIN_MAX_SAMPLES))
+        p_wav, _k = self._in(wavs, np.float32)
+        out = self.empty((G, int(N_out)))
+        self._check_or_free(self.lib.tts_join(self.handle, p_wav, B, N, q.ctypes.data, q.shape[0], _int32_ptr(g), G, int(fade), int(N_out),
+                                              out.data_ptr()), out)
+        return out, n_out
+
+    def download_rows(self, rows, lengths):
+        """the first ``lengths[g]`` elements of every row of the device array ``rows`` (G, N) as a list of host arrays: only
+        those bytes cross to the host (``to_host`` would bring all G * N)"""
+        G, N = rows.shape
+        lengths = [int(n) for n in lengths]
+        if len(lengths) != G or any(not 0 <= n <= N for n in lengths):
+            raise ValueError('download_rows: {} lengths in 0 .. {} are needed, got {!r}'.format(G, N, lengths))
+        out = []
+        for g, n in enumerate(lengths):
+            host = np.empty(n, dtype=rows.dtype)
+            if n:
+                self._check(self.lib.tts_memcpy_d2h(self.handle, host.ctypes.data, rows.data_ptr() + g * N * rows.dtype.itemsize,
+                                                    n * rows.dtype.itemsize))
+            out.append(host)
+        return out
 
     # ------------------------------------------------------------------ cepstra and alignment
     def mfcc(self, rows, n_mfcc, n_frames=None, clip01=False, row_stride=None):

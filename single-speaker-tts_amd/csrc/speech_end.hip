@@ -3,6 +3,7 @@
 //                                        trim_end = the last such frame) -- the criterion of the TODO at tacotron/inference.py:76-78
 // A streaming reduction: every float of the batch is read once (262 MB at 64 x 1000 x 1025), nothing is computed on the data --
 // maxima and one comparison -- so the result is exact.  Two launches: the rows (one wave each), then the utterances.
+// tts_speech_interval is the whole of the reference's function, (trim_start, trim_end): the same rows, then both ends.
 #include "api_internal.h"
 
 namespace tts {
@@ -70,6 +71,38 @@ __global__ __launch_bounds__(SE_THREADS) void speech_last_kernel(const unsigned 
     }
 }
 
+// first_active[b] = the smallest t with active[b][t], last_active[b] = the largest; both -1 without one
+__global__ __launch_bounds__(SE_THREADS) void speech_interval_kernel(const unsigned char* __restrict__ active, int T, int* __restrict__ first_active,
+                                                                     int* __restrict__ last_active) {
+    __shared__ int red[2][SE_THREADS / 64];
+    const int b = blockIdx.x;
+    const unsigned char* a = active + (size_t)b * T;
+    int first = T, last = -1;   // (T: none so far)
+    for (int t = threadIdx.x; t < T; t += SE_THREADS)
+        if (a[t]) {
+            first = min(first, t);
+            last = t;   // (ascending: the thread's largest)
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        first = min(first, __shfl_xor(first, o));
+        last = max(last, __shfl_xor(last, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = first;
+        red[1][threadIdx.x >> 6] = last;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < SE_THREADS / 64; ++w) {
+            first = min(first, red[0][w]);
+            last = max(last, red[1][w]);
+        }
+        first_active[b] = last < 0 ? -1 : first;
+        last_active[b] = last;
+    }
+}
+
 }  // namespace tts
 
 namespace tts_api {
@@ -112,6 +145,25 @@ int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, i
     return TTS_OK;
 }
 
+int speech_interval_impl(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int32_t* first_active,
+                         int32_t* last_active) {
+    if (!spec || !first_active || !last_active) return fail(h, TTS_ERR_INVALID, "speech_interval: spec, first_active and last_active must not be NULL");
+    if (B < 1 || T < 1 || F < 1) return fail(h, TTS_ERR_INVALID, "speech_interval: need B, T, F >= 1");
+    if (row_stride < F) return fail(h, TTS_ERR_INVALID, "speech_interval: row_stride < F");
+    if (threshold != threshold) return fail(h, TTS_ERR_INVALID, "speech_interval: the threshold is NaN");
+    if (!h) return TTS_ERR_INVALID;
+    const long long rows = (long long)B * T;
+    WS(h, "eos.interval_active", unsigned char, (size_t)rows, active);   // (its own: nothing orders it behind a synthesis call's eos.active)
+    ProfScope ps(h, ST_SPEECH_END, 2);
+    const long long want = (rows + SE_ROWS - 1) / SE_ROWS;
+    const unsigned grid = (unsigned)std::min<long long>(want, 1 << 18);   // (the rows beyond take another round)
+    hipLaunchKernelGGL(speech_rows_kernel, dim3(grid), dim3(SE_THREADS), 0, h->stream, spec, rows, F, row_stride, threshold, active);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(speech_interval_kernel, dim3((unsigned)B), dim3(SE_THREADS), 0, h->stream, active, T, first_active, last_active);
+    HIPCHK(h, hipGetLastError());
+    return TTS_OK;
+}
+
 }  // namespace tts_api
 
 extern "C" {
@@ -121,6 +173,12 @@ int tts_speech_frames(tts_handle_t h, const float* spec, int B, int T, int F, in
     DeviceScope dev_scope(h);
     if (!h) return TTS_ERR_INVALID;
     return speech_frames_impl(h, spec, B, T, F, row_stride, threshold, keep_frames, min_frames, n_frames, last_active);
+}
+
+int tts_speech_interval(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int32_t* first_active,
+                        int32_t* last_active) {
+    DeviceScope dev_scope(h);
+    return speech_interval_impl(h, spec, B, T, F, row_stride, threshold, first_active, last_active);
 }
 
 int tts_speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out) {

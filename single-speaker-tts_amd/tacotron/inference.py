@@ -13,10 +13,11 @@ import os
 import numpy as np
 
 from . import attention_check
-from .._hip import (LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
+from .._hip import (ALIGNMENT_RECORD, JOIN_MAX_FADE, LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
+from ..datasets.text_split import BREAKS, MAX_CHARS, abbreviations_of, split_text
 from .model import Mode, Tacotron
 from .params import dataset_params, inference_params, model_params
 
@@ -270,6 +271,244 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     return (list(wavs), report) if check_alignment else list(wavs)
 
 
+# The pause behind a piece by the break that ends it, in milliseconds.  Untuned: round figures in the range speech synthesizers
+# commonly use, not measured against recordings.
+PAUSES_MS = {'paragraph': 700.0, 'sentence': 350.0, 'clause': 120.0, 'word': 0.0, 'cut': 0.0}
+FADE_MS = 5.0               # the edge fades of a piece (110 samples at 22 050 Hz): untuned
+STOP_AT_SILENCE_DB = -40.0  # where synthesize_text ends a piece unless the caller says otherwise
+
+
+def pause_samples(pauses_ms, sampling_rate):
+    """``pauses_ms`` -- None or a dict {break: milliseconds} that overrides PAUSES_MS where it has a key -- as {break: samples}
+    for all five breaks (ms_to_samples).  ValueError for a key that is no break or a pause that is not a finite number >= 0."""
+    pauses = dict(PAUSES_MS)
+    if pauses_ms is not None:
+        if not isinstance(pauses_ms, dict):
+            raise ValueError('pauses_ms must be None or a dict of {{break: ms}} with breaks among {}, got {!r}'.format(BREAKS, pauses_ms))
+        for kind, ms in pauses_ms.items():
+            if kind not in BREAKS:
+                raise ValueError('pauses_ms: {!r} is not one of {}'.format(kind, BREAKS))
+            try:
+                ok = 0.0 <= float(ms) < float('inf')
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError('pauses_ms[{!r}] must be a finite number of milliseconds >= 0, got {!r}'.format(kind, ms))
+            pauses[kind] = float(ms)
+    out = {kind: ms_to_samples(ms, sampling_rate) for kind, ms in pauses.items()}
+    if max(out.values()) >= 2 ** 31:
+        raise ValueError('pauses_ms: a pause of {} samples does not fit the join'.format(max(out.values())))
+    return out
+
+
+def fade_samples(fade_ms, sampling_rate):
+    """``fade_ms`` as the ``fade`` of ``Engine.join`` in samples (ms_to_samples).  ValueError for a fade that is not a finite number
+    >= 0 or is longer than the join takes (tts_join_max_fade)."""
+    try:
+        ok = 0.0 <= float(fade_ms) < float('inf')
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('fade_ms must be a finite number of milliseconds >= 0, got {!r}'.format(fade_ms))
+    fade = ms_to_samples(float(fade_ms), sampling_rate)
+    if fade > JOIN_MAX_FADE:
+        raise ValueError('fade_ms = {!r} is {} samples, more than the join takes ({})'.format(fade_ms, fade, JOIN_MAX_FADE))
+    return fade
+
+
+def lead_frames(first_active, speaking_rate, keep_frames):
+    """the frames of a piece's waveform in front of its speech that the join leaves out: max(0, floor(max(0, first_active - 1) /
+    speaking_rate) - keep_frames) -- the first active frame of the network's spectrogram, one frame of margin, taken to the
+    stretched time axis, less the frames kept around speech"""
+    return max(0, int(np.floor(max(0, int(first_active) - 1) / float(speaking_rate))) - int(keep_frames))
+
+
+def pack_pieces(texts, dataset, batch_size, max_chars):
+    """Every text split (``split_text`` with the dataset's abbreviations) and the pieces packed in order into calls of at most
+    ``batch_size`` rows: ``(calls, piece_text, piece_break, pieces)`` with ``calls`` a list of ``(first piece, ids (B, T_sent)
+    int32)``, each padded to its own longest row, and per piece its text's index, the break behind it and its characters."""
+    if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError('batch_size must be an integer >= 1, got {!r}'.format(batch_size))
+    if isinstance(texts, str):
+        raise ValueError('texts must be a list of strings, not one string')
+    piece_text, piece_break, pieces = [], [], []
+    abbreviations = abbreviations_of(dataset)
+    for t, text in enumerate(texts):
+        for piece, brk in split_text(text, max_chars, abbreviations):
+            piece_text.append(t)
+            piece_break.append(brk)
+            pieces.append(piece)
+    calls = []
+    if pieces:
+        id_sequences, sequence_lengths = dataset.process_sentences(pieces)
+        rows = [np.frombuffer(q, dtype=np.int32) for q in id_sequences]
+        for p0 in range(0, len(rows), int(batch_size)):
+            chunk = rows[p0:p0 + int(batch_size)]
+            longest = max(len(r) for r in chunk)
+            calls.append((p0, np.array([pad_sentence(r, longest) for r in chunk], dtype=np.int32)))
+    return calls, piece_text, piece_break, pieces
+
+
+def join_list_of_call(piece_text, piece_break, n_frames, first_active, hop, pauses, speaking_rate, keep_frames, lead_trim):
+    """The edit list of one call: per row its text, the break behind it, the call's frame counts and first active frames ->
+    ``(pieces (P, 4), groups (P,), texts, tail, orphans)``: the kept rows as ``row, first, count, gap`` with first = hop * lead and
+    count = hop * (n_frames - 1) - first, one group per text that keeps a piece (``texts``: their indices, ascending), and ``tail``:
+    per such text the pause behind its last kept piece.  A row without an active frame (or with nothing left behind its lead) is
+    dropped and its pause kept: it goes to the kept piece in front of it in the same text and call, and where the call has none to
+    ``orphans``, a list of ``(text, pause)`` in the order of the rows -- the caller adds those to the pause behind the part of the
+    text that an earlier call said."""
+    pieces, groups, texts, tail, orphans = [], [], [], [], []
+    for b, t in enumerate(piece_text):
+        gap = pauses[piece_break[b]]
+        lead = lead_frames(first_active[b], speaking_rate, keep_frames) if lead_trim and first_active[b] >= 0 else 0
+        first = hop * lead
+        count = hop * (int(n_frames[b]) - 1) - first
+        if first_active[b] < 0 or count < 1:
+            if texts and texts[-1] == t:
+                pieces[-1][3] += gap
+                tail[-1] += gap
+            else:
+                orphans.append((t, gap))
+            continue
+        if not texts or texts[-1] != t:
+            texts.append(t)
+            tail.append(0)
+        pieces.append([b, first, count, gap])
+        groups.append(len(texts) - 1)
+        tail[-1] = gap
+    return np.array(pieces, dtype=np.int64).reshape(-1, 4), np.array(groups, dtype=np.int64), texts, tail, orphans
+
+
+def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_ms=FADE_MS, lead_trim=True, max_chars=MAX_CHARS,
+                    n_steps=None, n_iter=None, seed=0, check_alignment=False, **settings):
+    """Texts of any length -> one float32 waveform per text (no reference counterpart: tacotron/inference.py:139-200 makes one
+    file of at most max_iterations frames per line).
+
+    Every text is split into pieces of at most ``max_chars`` characters (``datasets.text_split.split_text`` with the dataset's
+    abbreviations), the pieces become ids (``process_sentences``, ``pad_sentence``) and are packed in order into calls of at most
+    ``batch_size`` rows (``pack_pieces``); call k runs ``Engine.synthesize`` with seed ``seed`` + k, no normalisation, and leaves
+    its waveforms on the device.  ``settings``: the keywords of ``SynthSettings`` (momentum, stop_at_silence_db, silence_keep_ms,
+    speaking_rate, pitch, pitch_semitones, phase_init, loudness); ``stop_at_silence_db`` defaults to -40 dB here and cannot be
+    None, because a piece that runs on to max_iterations frames is of no use in a joined text.
+
+    Piece b of a call is cut from its row as ``first = hop * lead`` and ``count = hop * (n_frames[b] - 1) - first``, with lead =
+    ``lead_frames(first_active[b], speaking_rate, keep_frames)`` -- ``first_active`` from ``Engine.speech_interval`` on the call's
+    normalised linear spectrogram at the stopping threshold -- or 0 with ``lead_trim`` off.  A piece without an active frame is
+    dropped and its pause added to the one in front of it -- the pause of the piece before it, or of the part of its text that an
+    earlier call said; in front of a text's first spoken sample nothing is kept.  The pause behind a piece follows its break (``pauses_ms`` over
+    PAUSES_MS: paragraph 700, sentence 350, clause 120, word and cut 0 ms -- untuned), every piece fades over ``fade_ms`` at
+    either edge, and one ``Engine.join`` per call lays the pieces of each text into one row on the device.  With a ``loudness``
+    one ``Engine.loudness_normalize`` runs over the joined rows, so a text is levelled as a whole and its sentences keep their
+    relative levels.  Only the n_out[g] samples of a row that were said are downloaded.
+
+    A text whose pieces span several calls is concatenated on the host, with the pause behind the earlier part as zeros between
+    them; with a ``loudness`` each part is levelled on its own.  The packing decides which pieces share a call, a call's seed
+    and the length its ids are padded to, so the bits of a text may depend on ``batch_size`` and on the texts around it.
+
+    Returns the list of waveforms (a text without a piece that speaks: an empty array); with ``check_alignment`` ``(waveforms,
+    records, verdicts, piece_text)``: the alignment record and ``attention_check.verdict`` of every piece, in order, and the
+    index of the text each piece belongs to."""
+    if settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB) is None:
+        raise ValueError('synthesize_text: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)')
+    settings.setdefault('stop_at_silence_db', STOP_AT_SILENCE_DB)
+    loud = loudness_setting(settings.pop('loudness', None))
+    s = SynthSettings(model, check_alignment=check_alignment, **settings)
+    hp = model.hparams
+    pauses = pause_samples(pauses_ms, hp.sampling_rate)
+    fade = fade_samples(fade_ms, hp.sampling_rate)
+    calls, piece_text, piece_break, _pieces = pack_pieces(texts, dataset, batch_size, max_chars)
+    loader = dataset_params.dataset_loader
+    win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
+    win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
+    S = n_steps or model.n_steps()
+    it = hp.reconstruction_iterations if n_iter is None else n_iter
+    eng = model.engine
+    keep_frames = s.stop[1]
+    threshold = eng.speech_threshold(s.stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
+    parts = [[] for _ in texts]     # per text the waveforms of its parts, one per call that says some of it
+    tails = [0 for _ in texts]      # ... and the pause behind the last part so far
+    records = []
+    for k, (p0, ids) in enumerate(calls):
+        B = ids.shape[0]
+        out = eng.synthesize(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len, win_hop, seed=seed + k,
+                             peak_normalize=False, want_linear=True, **dict(s.engine_keywords(), loudness=None))
+        first_active = eng.speech_interval(out['linear'], threshold)[0].to_host()
+        if check_alignment:
+            records.append(eng.synth_alignment_stats(B))
+        pieces, groups, said, tail, orphans = join_list_of_call(piece_text[p0:p0 + B], piece_break[p0:p0 + B], out['n_frames'], first_active,
+                                                                win_hop, pauses, s.rate, keep_frames, lead_trim)
+        for t, gap in orphans:      # (silent pieces in front of the call's first kept piece of their text)
+            if parts[t]:
+                tails[t] += gap
+        if not said:
+            continue
+        joined, n_out = eng.join(out['wav'], pieces, groups, fade)
+        if loud is not None:
+            eng.loudness_normalize(joined, eng.sampling_rate, loud[0], loud[1], n_samples=n_out)
+        for t, wav, gap in zip(said, eng.download_rows(joined, n_out), tail):
+            if parts[t]:
+                parts[t].append(np.zeros(tails[t], dtype=np.float32))
+            parts[t].append(wav)
+            tails[t] = gap
+    wavs = [np.concatenate(p) if p else np.zeros(0, dtype=np.float32) for p in parts]
+    if check_alignment:
+        records = np.concatenate(records) if records else np.zeros(0, dtype=ALIGNMENT_RECORD)
+        return wavs, records, attention_check.verdict(records), list(piece_text)
+    return wavs
+
+
+def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0, seed=0, check_alignment=False, **kw):
+    """``synthesize_sentences`` for texts of any length: every entry of ``raw_texts`` becomes one ``{i+1}.wav`` that holds the whole
+    text (``synthesize_text``; ``kw``: its keywords).  Without a ``loudness`` each file is peak-normalised once by save_wav, as
+    the sentence files are.  Returns the list of waveforms, with ``check_alignment`` ``(waveforms, report)`` -- one ``{index,
+    verdict, record}`` per PIECE, each with the index of its ``text`` -- also written to ``alignment_report.json``."""
+    from ..datasets.lj_speech import LJSpeechDatasetHelper
+    out_dir = out_dir or inference_params.synthesis_dir
+    if not os.path.isdir(out_dir):
+        raise NotADirectoryError('The specified synthesis target folder does not exist.')
+    # (ValueError before anything is loaded)
+    settings = {k: kw[k] for k in kw if k not in ('batch_size', 'pauses_ms', 'fade_ms', 'lead_trim', 'max_chars')}
+    if settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB) is None:
+        raise ValueError('synthesize_texts: stop_at_silence_db cannot be None')
+    SynthSettings(model_params, **dict(settings, stop_at_silence_db=settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB)))
+    pause_samples(kw.get('pauses_ms'), model_params.sampling_rate)
+    fade_samples(kw.get('fade_ms', FADE_MS), model_params.sampling_rate)
+    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
+                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
+    model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
+    wavs = synthesize_text(model, raw_texts, dataset, seed=seed, check_alignment=check_alignment, **kw)
+    report = None
+    if check_alignment:
+        wavs, records, _verdicts, piece_text = wavs
+        report = attention_check.report(records)
+        for row, t in zip(report, piece_text):
+            row['text'] = int(t)
+        with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
+            json.dump(report, f, indent=1)
+    for i, wav in enumerate(wavs):
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate,
+                 loudness_setting(kw.get('loudness')) is None and len(wav) > 0)   # (a text that says nothing: an empty file)
+    return (list(wavs), report) if check_alignment else list(wavs)
+
+
+def read_texts(path):
+    """``read_sentences`` for ``--text``: every line is one text, and the two-character sequence backslash-n twice in a row marks
+    a paragraph break inside it (a line cannot hold a newline)"""
+    return [line.replace('\\n\\n', '\n\n') for line in read_sentences(path)]
+
+
+def pause_option(option):
+    """``KIND=MS`` of ``--pause-ms`` as ``(kind, ms)``"""
+    import argparse
+    kind, sep, ms = option.partition('=')
+    try:
+        if not sep or kind not in BREAKS:
+            raise ValueError
+        return kind, float(ms)
+    except ValueError:
+        raise argparse.ArgumentTypeError('KIND=MS with KIND one of {} is needed, got {!r}'.format(', '.join(BREAKS), option))
+
+
 def read_sentences(path):
     """reference tacotron/inference.py:139-143: one sentence per line, the newline removed (nothing else stripped)."""
     raw_sentences = []
@@ -292,6 +531,7 @@ def main(argv=None):
                                                             [--phase-init random|estimate]
                                                             [--loudness LUFS [--max-peak P]]
                                                             [--check-alignment]
+                                                            [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
@@ -304,7 +544,12 @@ def main(argv=None):
     ``--loudness LUFS``: every wav is taken to that integrated loudness (ITU-R BS.1770-4; -23: EBU R 128, -16: a common
     streaming level) with no sample beyond ``--max-peak`` (default 1), instead of being peak-normalised.
     ``--check-alignment``: the attention diagnostics (``tacotron.attention_check``) -- one JSON line per sentence (index,
-    verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts."""
+    verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts.
+    ``--text``: every line of the synthesis file is a text of any length -- sentences, paragraphs (the two characters ``\\n``
+    twice in a row mark a paragraph break inside a line) -- and ``{i+1}.wav`` holds the whole text (``synthesize_text``): split
+    into pieces of at most ``--max-chars`` characters (default 150), each stopped at its silence (``--stop-at-silence``, -40 dB
+    unless given), joined on the device with the pause of its break (``--pause-ms sentence=350``, repeatable; paragraph,
+    sentence, clause, word, cut) and edge fades of ``--fade-ms`` (default 5).  With ``--loudness`` a text is levelled as a whole."""
     args = parse_args(argv)
     s = SynthSettings(model_params, args.momentum, args.stop_at_silence, args.silence_keep_ms, args.rate, pitch_semitones=args.pitch,
                       phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
@@ -313,8 +558,9 @@ def main(argv=None):
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
         raise NotADirectoryError('The specified synthesis target folder does not exist.')
-    raw_sentences = read_sentences(args.synthesis_file or inference_params.synthesis_file)
-    print('{} sentences were loaded for inference.'.format(len(raw_sentences)))
+    path = args.synthesis_file or inference_params.synthesis_file
+    raw_sentences = read_texts(path) if args.text else read_sentences(path)
+    print('{} {} were loaded for inference.'.format(len(raw_sentences), 'texts' if args.text else 'sentences'))
     if args.synthetic_weights is not None:
         from .weights import synthetic_weights
         weights = synthetic_weights(args.synthetic_weights, model_params)
@@ -324,8 +570,14 @@ def main(argv=None):
         weights = inference_params.checkpoint_file
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
-    wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                check_alignment=args.check_alignment, **s.keywords())
+    if args.text:
+        kw = dict(s.keywords(), stop_at_silence_db=STOP_AT_SILENCE_DB if args.stop_at_silence is None else args.stop_at_silence)
+        wavs = synthesize_texts(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
+                                check_alignment=args.check_alignment, max_chars=args.max_chars, pauses_ms=dict(args.pause_ms),
+                                fade_ms=args.fade_ms, **kw)
+    else:
+        wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
+                                    check_alignment=args.check_alignment, **s.keywords())
     if args.check_alignment:
         wavs, report = wavs
         for row in report:
@@ -363,6 +615,15 @@ def parse_args(argv=None):
                     help='with --loudness: the largest |sample| the gain may produce (default {:g})'.format(LOUDNESS_MAX_PEAK))
     ap.add_argument('--check-alignment', action='store_true',
                     help='attention diagnostics: one JSON line per sentence and {} beside the wavs'.format(REPORT_FILE))
+    ap.add_argument('--text', action='store_true',
+                    help='every line of the synthesis file is a text of any length (a literal \\n\\n marks a paragraph): one wav per text')
+    ap.add_argument('--max-chars', type=int, default=MAX_CHARS, metavar='N',
+                    help='with --text: the longest piece a text is cut into (default {}, the sentence length of the benchmark)'.format(MAX_CHARS))
+    ap.add_argument('--pause-ms', type=pause_option, action='append', default=[], metavar='KIND=MS',
+                    help='with --text: the pause behind a break, KIND one of {} (defaults {}; repeatable)'.format(
+                        ', '.join(BREAKS), ', '.join('{}={:g}'.format(k, PAUSES_MS[k]) for k in BREAKS)))
+    ap.add_argument('--fade-ms', type=float, default=FADE_MS, metavar='MS',
+                    help='with --text: the fade at either edge of a piece (default {:g} ms)'.format(FADE_MS))
     return ap.parse_args(argv)
 
 

@@ -655,6 +655,61 @@ int tts_loudness_filter(int sampling_rate, double coeffs[10]);
 /* Host only: the samples c of a segment at this sampling rate, ceil((sampling_rate / 10) / 8); 0 outside 8000 .. 192000. */
 int tts_loudness_segment(int sampling_rate);
 
+/* ---- true-peak meter and look-ahead peak limiter -------------------------------------------- */
+/* The true peak of B mono utterances after ITU-R BS.1770-4 Annex 2: the peak of the 4x oversampled signal (no reference
+ * counterpart).  wav DEVICE [B][N]; n_samples: HOST int32 [B] or NULL (all N) -- samples at or behind n_samples[b] are never read.
+ * For an utterance x[0 .. n), with x = (double)wav[b][i] and zeros outside 0 .. n - 1:
+ *   y[4 i] = x[i]
+ *   y[4 i + p] = h[p][0] * x[i - 5] + h[p][1] * x[i - 4] + ... + h[p][11] * x[i + 6],  p = 1 .. 3: the point i + p / 4
+ * the first product, then one sum per further product in ascending tap order, every product and sum an individually rounded IEEE
+ * double operation.  h (tts_true_peak_filter) is a Kaiser (beta = 4) windowed sinc; its phase 0 is the unit impulse exactly.
+ *   true_peak[b]   = the largest finite |y|, 0 where there is none: never below sample_peak[b]
+ *   sample_peak[b] = the largest finite |x|, 0 where there is none
+ * A non-finite sample makes the interpolated points within its taps' reach non-finite; they are skipped.  The maxima are taken
+ * on bit patterns: order-free.  true_peak DEVICE double [B], sample_peak DEVICE double [B] or NULL (8-byte aligned).  dBTP =
+ * 20 log10(true_peak) is the host's to take.  Exactness: the bits of tests/limiter_oracle.py.  Independence: an utterance's
+ * results are the bits of its B = 1 call.  No model needs to be loaded.  Asynchronous on the handle's stream (a fill per output
+ * and one launch per 64 utterances); profile stage "limiter".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL wav or true_peak, B or N < 1, an n_samples[b] outside 1 .. N, a misaligned
+ * buffer. */
+int tts_true_peak(tts_handle_t h, const float* wav /* [B][N] */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+                  double* true_peak /* [B] */, double* sample_peak /* [B] or NULL */);
+/* Host only, no handle and no device: h[phase][tap], 4 x 12, as the library designed them (sin and the Bessel series are the
+ * host's: a restatement takes the taps from here).  TTS_ERR_INVALID: NULL. */
+int tts_true_peak_filter(double coeffs[48]);
+
+/* What tts_limit reports per utterance; every field is order-free.  16 bytes. */
+typedef struct tts_limit_stats {
+    int32_t over;      /* finite samples whose envelope a[i] is above the ceiling */
+    int32_t limited;   /* finite samples with an applied gain g[i] < 1 */
+    double min_gain;   /* the smallest g[i] among them; 1.0 if none */
+} tts_limit_stats_t;
+/* A look-ahead peak limiter, in place: c = ceiling > 0, L = lookahead in 0 .. tts_limit_max_lookahead() samples, oversample 1
+ * (sample peaks) or 4 (the interpolated peaks of tts_true_peak).  For an utterance x[0 .. n):
+ *   envelope       a[i] = |x[i]| (oversample 1), or the largest finite |y[4 i + p]|, p = 0 .. 3 (oversample 4); 0 where x[i] is
+ *                  not finite.  Non-finite interpolated points are skipped.
+ *   required gain  r[i] = 1 where a[i] <= c, else c / a[i]
+ *   minimum        m[i] = min r[j] over |j - i| <= L, j in 0 .. n - 1
+ *   smoothed gain  s[i] = (m[cl(i - L)] + m[cl(i - L + 1)] + ... + m[cl(i + L)]) / (2 L + 1), summed in ascending order from its
+ *                  first term, cl(j) = min(max(j, 0), n - 1): a function of L, i and the utterance alone
+ *   applied gain   g[i] = min(s[i], r[i])
+ *   output         wav[b][i] keeps its bits where g[i] == 1 or x[i] is not finite; else it becomes
+ *                  copysign(min(|(float)(g[i] * x[i])|, cf), x[i]), cf the largest float <= c
+ * with correctly rounded double quotients, products and sums.  Every window s[i] averages contains i, so s[i] <= r[i] in real
+ * arithmetic; the min and the clamp make |out[i]| <= cf exact for every finite sample.  A row whose envelope stays at or below c
+ * comes back as its own bits (its tiles are read once and nothing is written).  With oversample 4 the bound is on the envelope:
+ * the gain modulation moves the interpolated peaks a little, so the output's true peak is measured (tts_true_peak), not promised.
+ * stats DEVICE [B] or NULL (8-byte aligned).  Samples at or behind n_samples[b] are neither read nor written; an utterance's
+ * result is the bits of its B = 1 call.  Asynchronous on the handle's stream, no host wait: a fill and three launches per 64
+ * utterances; the workspace is a copy of the rows, from which the tiles that changed are copied back, so no tile reads what
+ * another wrote.  Profile stage "limiter".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL wav, B or N < 1, a ceiling that is not finite and positive, a lookahead
+ * outside 0 .. tts_limit_max_lookahead(), an oversample other than 1 or 4, an n_samples[b] outside 1 .. N, a misaligned buffer. */
+int tts_limit(tts_handle_t h, float* wav /* [B][N], in place */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+              double ceiling, int lookahead, int oversample, tts_limit_stats_t* stats /* [B] or NULL */);
+/* Host only: the largest lookahead, 1024 samples. */
+int tts_limit_max_lookahead(void);
+
 /* ---- attention diagnostics: alignment statistics ------------------------------------------- */
 /* What the decoder's alignments say about whether the sentence was read (no reference counterpart: the reference plots its
  * alignments, tacotron/model.py:552-598, and judges them by eye).  alignments DEVICE [n_steps_max][B][Ts] as the decoder
@@ -856,6 +911,17 @@ int tts_set_pitch(tts_handle_t h, double octaves);
  * not finite, a max_peak that is not finite and positive) and on TTS_ERR_UNSUPPORTED (a sampling rate outside 8000 .. 192000). */
 int tts_set_loudness(tts_handle_t h, int enabled, double target_lufs, double max_peak, int sampling_rate);
 
+/* The peak limiter of synthesis (tts_limit).  A setting of the HANDLE, off by default and read when a call is made; off is the
+ * call as it always was, launch for launch.  With enabled != 0, tts_synthesize and tts_synthesize_host run
+ * tts_limit(ceiling, lookahead, oversample) last on the call's final rows -- behind the loudness normaliser, or behind the peak
+ * normalisation where there is no loudness target -- on the call's stream, with no host wait, over the samples each row holds
+ * (the lengths the loudness setting uses).  The result is the bits of the same call made with the setting off followed by
+ * tts_limit on those rows; the host form stays bit-identical to tts_synthesize + tts_memcpy_d2h.  The first call after the
+ * setting was switched on is not pipelined (its buffers are new).
+ * With enabled == 0 the other arguments are not looked at.  The setting stays as it was on TTS_ERR_INVALID (a ceiling that is
+ * not finite and positive, a lookahead outside 0 .. tts_limit_max_lookahead(), an oversample other than 1 or 4). */
+int tts_set_limiter(tts_handle_t h, int enabled, double ceiling, int lookahead, int oversample);
+
 /* Attention diagnostics of synthesis: the alignment statistics of every call (tts_alignment_stats).  A setting of the HANDLE,
  * off by default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
  * tts_synthesize and tts_synthesize_host run tts_text_lengths(pad_id) on the call's device ids behind its encoder and
@@ -884,7 +950,8 @@ int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignmen
  * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
  * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare), "loudness" (tts_loudness, tts_loudness_normalize, stand-alone
  * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, stand-alone or
- * inside a tts_synthesize call with tts_set_alignment_stats on).
+ * inside a tts_synthesize call with tts_set_alignment_stats on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
+ * stand-alone or inside a tts_synthesize call with tts_set_limiter on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -79,6 +79,15 @@ class TtsAlignmentStats(ctypes.Structure):
 ALIGNMENT_RECORD = np.dtype([(name, np.int32) for name, _t in TtsAlignmentStats._fields_[:12]] + [('focus_sum', np.float64)])
 
 
+class TtsLimitStats(ctypes.Structure):
+    """struct tts_limit_stats (include/sstts_hip.h): two int32 and a double, 16 bytes."""
+    _fields_ = [('over', c_int32), ('limited', c_int32), ('min_gain', ctypes.c_double)]
+
+
+# ... and the same record as a numpy dtype: what Engine.limit returns an array of
+LIMIT_RECORD = np.dtype([('over', np.int32), ('limited', np.int32), ('min_gain', np.float64)])
+
+
 class TtsJoinPiece(ctypes.Structure):
     """tts_join_piece_t: samples [first, first + count) of a row and the pause behind them; a row of the (P, 4) int32 arrays
     ``Engine.join`` hands the library"""
@@ -165,6 +174,11 @@ _PROTOTYPES = {
     'tts_loudness_filter': (c_int, [c_int, POINTER(ctypes.c_double)]),
     'tts_loudness_segment': (c_int, [c_int]),
     'tts_set_loudness': (c_int, [c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_int]),
+    'tts_true_peak': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p]),
+    'tts_true_peak_filter': (c_int, [POINTER(ctypes.c_double)]),
+    'tts_limit': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_int, c_void_p]),
+    'tts_limit_max_lookahead': (c_int, []),
+    'tts_set_limiter': (c_int, [c_void_p, c_int, ctypes.c_double, c_int, c_int]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -490,6 +504,81 @@ def loudness_filter(sampling_rate):
     return np.array(out[:], dtype=np.float64)
 
 
+LIMIT_MAX_LOOKAHEAD = 1024       # tts_limit_max_lookahead(), samples
+LIMIT_LOOKAHEAD_MS = 5.0         # the look-ahead of a limiter given as a bare ceiling
+LIMIT_OVERSAMPLE = 4             # ... and its mode: the interpolated peaks
+
+
+def limit_arguments(what, ceiling, lookahead, oversample):
+    """(ceiling, lookahead, oversample) of a tts_limit call as a checked float and two ints; ValueError, raised before a handle is
+    touched, for what the library refuses: a ceiling that is not finite and positive, a look-ahead that is not an integer in
+    0 .. 1024 samples, an oversample other than 1 or 4"""
+    try:
+        c = float(ceiling)
+    except (TypeError, ValueError):
+        raise ValueError('{}: the ceiling must be a number, got {!r}'.format(what, ceiling))
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError('{}: the ceiling must be finite and positive, got {!r}'.format(what, ceiling))
+    try:
+        ok = int(lookahead) == lookahead and 0 <= lookahead <= LIMIT_MAX_LOOKAHEAD
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('{}: the look-ahead must be an integer in 0 .. {} samples, got {!r}'.format(what, LIMIT_MAX_LOOKAHEAD, lookahead))
+    if isinstance(oversample, (bool, np.bool_)) or oversample not in (1, 4):
+        raise ValueError('{}: oversample must be 1 or 4, got {!r}'.format(what, oversample))
+    return c, int(lookahead), int(oversample)
+
+
+def limiter_setting(limiter):
+    """``limiter`` of the synthesis calls -- None (the handle's setting as it stands), a ceiling or ``(ceiling, lookahead_ms,
+    oversample)`` -- as None or a checked tuple ``(ceiling, lookahead_ms, oversample)``; a bare ceiling looks 5 ms ahead at the
+    interpolated peaks.  ValueError, raised before a handle is touched, for anything else.  (The look-ahead becomes samples at the
+    engine's sampling rate, where more than 1024 of them are refused: ``limiter_lookahead``.)"""
+    if limiter is None:
+        return None
+    if isinstance(limiter, (tuple, list)):
+        if len(limiter) != 3:
+            raise ValueError('limiter must be None, a ceiling or (ceiling, lookahead_ms, oversample), got {!r}'.format(limiter))
+        ceiling, ms, oversample = limiter
+    else:
+        ceiling, ms, oversample = limiter, LIMIT_LOOKAHEAD_MS, LIMIT_OVERSAMPLE
+    if isinstance(ceiling, (bool, np.bool_)):
+        raise ValueError('limiter: the ceiling must be a number, got {!r}'.format(ceiling))
+    c, _l, o = limit_arguments('limiter', ceiling, 0, oversample)
+    try:
+        ms = float(ms)
+    except (TypeError, ValueError):
+        raise ValueError('limiter: the look-ahead must be a number of milliseconds, got {!r}'.format(limiter[1]))
+    if not (np.isfinite(ms) and ms >= 0):
+        raise ValueError('limiter: the look-ahead must be finite and not negative, got {!r}'.format(ms))
+    return c, ms, o
+
+
+def limiter_lookahead(what, lookahead_ms, sampling_rate):
+    """a look-ahead in milliseconds as samples at ``sampling_rate``, rounded to the nearest; ValueError above 1024 samples"""
+    L = int(round(float(lookahead_ms) * 1e-3 * float(sampling_rate)))
+    if not 0 <= L <= LIMIT_MAX_LOOKAHEAD:
+        raise ValueError('{}: a look-ahead of {} ms is {} samples at {} Hz, more than {}'.format(what, lookahead_ms, L, sampling_rate, LIMIT_MAX_LOOKAHEAD))
+    return L
+
+
+def dbtp(peak):
+    """20 log10 of the peaks tts_true_peak returns: -inf for 0"""
+    with np.errstate(divide='ignore'):
+        return 20.0 * np.log10(np.asarray(peak, dtype=np.float64))
+
+
+def true_peak_filter():
+    """tts_true_peak_filter: the taps h[phase][tap] of the 4x interpolation as the library designed them (float64 (4, 12)); needs
+    no device"""
+    out = (ctypes.c_double * 48)()
+    rc = load_library().tts_true_peak_filter(out)
+    if rc != TTS_OK:
+        raise TtsError(rc, 'tts_true_peak_filter refused')
+    return np.array(out[:], dtype=np.float64).reshape(4, 12)
+
+
 def alignment_stats_setting(alignment_stats):
     """``alignment_stats`` of the synthesis calls -- None (the handle's setting as it stands), False (off), True (on, pad id 0)
     or ``(enabled, pad_id)`` -- as None or a checked tuple ``(enabled, pad_id)``.  ValueError, raised before a handle is touched,
@@ -717,7 +806,7 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
 
 
 # The per-call synthesis settings.  The handle holds each of them (tts_set_* / tts_set_option; the C ABI has no getters, so the
-# engine mirrors them); ``Engine.synthesize`` and ``Engine.synthesize_host`` take all seven as keywords, ``Engine.griffin_lim``
+# engine mirrors them); ``Engine.synthesize`` and ``Engine.synthesize_host`` take all eight as keywords, ``Engine.griffin_lim``
 # takes ``momentum`` and ``phase_init``.  None always means the handle's setting as it stands; any other value holds for that
 # call alone (``Engine._settings``).  In the order they are checked and applied in:
 #   ``momentum``: the fast Griffin-Lim momentum in [0, 1) (librosa's and torchaudio's ``momentum``; 0 = the reference's plain
@@ -742,6 +831,9 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
 #   ``alignment_stats``: False, True or ``(enabled, pad_id)`` (tts_set_alignment_stats, off unless ``set_alignment_stats``
 #     changed it): the call also reduces its alignments to one record per utterance behind its decoder, with no host wait;
 #     ``synth_alignment_stats(B)`` / ``wait_host_alignment_stats`` fetch them.  Nothing else of the call changes.
+#   ``limiter``: a ceiling or ``(ceiling, lookahead_ms, oversample)`` (tts_set_limiter, off unless ``set_limiter`` changed it): the
+#     call's final rows go through ``limit`` last, behind the loudness gain or the peak normalisation, each utterance over the
+#     samples its row holds; the look-ahead is taken at the model's sampling rate.
 # A row: the keyword, the Engine attribute that mirrors the handle's value, the handle's initial value, the check that turns
 # the keyword into the mirror's value (ValueError before a handle is touched), and how a value is applied -- a ``set_option``
 # key or a call of the engine's ``set_*`` method.
@@ -755,6 +847,7 @@ SETTINGS = (
     Setting('phase_init', '_gl_init', 0, phase_init_value, 'gl_init'),
     Setting('loudness', '_loudness', None, loudness_setting, lambda engine, v: engine.set_loudness(v)),
     Setting('alignment_stats', '_alignment_stats', (False, 0), alignment_stats_setting, lambda engine, v: engine.set_alignment_stats(*v)),
+    Setting('limiter', '_limiter', None, limiter_setting, lambda engine, v: engine.set_limiter(v)),
 )
 
 
@@ -928,6 +1021,18 @@ class Engine(object):
             sr = loudness_sampling_rate('set_loudness', self.sampling_rate if sampling_rate is None else sampling_rate)
             self._check(self.lib.tts_set_loudness(self.handle, 1, setting[0], setting[1], sr))
         self._loudness = setting
+
+    def set_limiter(self, limiter, sampling_rate=None):
+        """tts_set_limiter: the handle's setting, read by every synthesize / synthesize_host call made after it.  ``limiter``:
+        None or False (off), a ceiling or ``(ceiling, lookahead_ms, oversample)``; the look-ahead becomes samples at
+        ``sampling_rate`` (None: the model's)."""
+        setting = limiter_setting(None if limiter is False else limiter)
+        if setting is None:
+            self._check(self.lib.tts_set_limiter(self.handle, 0, 1.0, 0, 1))
+        else:
+            L = limiter_lookahead('set_limiter', setting[1], self.sampling_rate if sampling_rate is None else sampling_rate)
+            self._check(self.lib.tts_set_limiter(self.handle, 1, setting[0], L, setting[2]))
+        self._limiter = setting
 
     def set_alignment_stats(self, enabled, pad_id=0):
         """tts_set_alignment_stats: the handle's setting, read by every synthesize / synthesize_host call made after it.  On,
@@ -1397,8 +1502,8 @@ class Engine(object):
         return (out, ap) if want_aperiodicity else out
 
     # ------------------------------------------------------------------ loudness
-    def _loudness_args(self, what, wavs, sampling_rate, n_samples):
-        sr = loudness_sampling_rate(what, sampling_rate)
+    def _ragged_waveforms(self, what, wavs, n_samples):
+        """``(wavs, single, B, n, the checked lengths or None)`` of a call on waveforms with per-utterance lengths"""
         wavs, single, B, n = _waveforms(what, wavs)
         ns = None
         if n_samples is not None:
@@ -1406,7 +1511,10 @@ class Engine(object):
             if ns.shape != (B,) or ns.dtype.kind not in 'iu':
                 raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
             ns = _checked_lengths(ns, n, 'n_samples', 'n')
-        return sr, wavs, single, B, n, ns
+        return wavs, single, B, n, ns
+
+    def _loudness_args(self, what, wavs, sampling_rate, n_samples):
+        return (loudness_sampling_rate(what, sampling_rate),) + self._ragged_waveforms(what, wavs, n_samples)
 
     def loudness(self, wavs, sampling_rate, n_samples=None, return_mean_square=False, want_blocks=False):
         """tts_loudness: the integrated loudness after ITU-R BS.1770-4 / EBU R 128 of ``wavs`` -- one mono waveform (n,) or a
@@ -1449,6 +1557,43 @@ class Engine(object):
         if fresh and single:
             out.shape = (n,)
         return (out, gains, z_host) if return_mean_square else (out, gains)
+
+    # ------------------------------------------------------------------ true peak and limiter
+    def true_peak(self, wavs, n_samples=None, want_sample_peak=False):
+        """tts_true_peak: the peak of the 4x oversampled signal (ITU-R BS.1770-4 Annex 2) of ``wavs`` -- one mono waveform (n,)
+        or a batch (B, n), a host array or a device buffer -- as a float64 host array (B,), linear (``dbtp`` makes dBTP of it);
+        never below the sample peak, which ``want_sample_peak`` returns as well.  ``n_samples``: B lengths (host integers) --
+        samples at or behind them are never read; None: all n.  The bits of tests/limiter_oracle.py."""
+        wavs, _single, B, n, ns = self._ragged_waveforms('true_peak', wavs, n_samples)
+        p_wav, _k = self._in(wavs, np.float32)
+        tp = self.empty((B,), np.float64)
+        sp = self.empty((B,), np.float64) if want_sample_peak else None
+        self._check_or_free(self.lib.tts_true_peak(self.handle, p_wav, B, n, _int32_ptr(ns), tp.data_ptr(),
+                                                   sp.data_ptr() if want_sample_peak else None), tp, sp)
+        out = tp.to_host()
+        tp.free()
+        if want_sample_peak:
+            out = (out, sp.to_host())
+            sp.free()
+        return out
+
+    def limit(self, wavs, ceiling, lookahead=0, oversample=LIMIT_OVERSAMPLE, n_samples=None):
+        """tts_limit: a look-ahead peak limiter over every utterance of ``wavs``: no finite sample of the result is above
+        ``ceiling``, and a row that never was comes back as its own bits.  ``lookahead``: samples, 0 .. 1024; ``oversample``: 1
+        (sample peaks) or 4 (the interpolated peaks ``true_peak`` reads).  Returns ``(waveforms, stats)``: a device array of the
+        input's shape -- a device input is limited in place and handed back, a host input is uploaded first -- and a host array
+        (B,) of ``LIMIT_RECORD``.  ``n_samples`` as in ``true_peak``: samples at or behind them are neither read nor written."""
+        wavs, single, B, n, ns = self._ragged_waveforms('limit', wavs, n_samples)
+        c, L, o = limit_arguments('limit', ceiling, lookahead, oversample)
+        fresh = not _is_device(wavs)
+        out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32)) if fresh else wavs
+        st = self.empty((B, 2), np.float64)   # (B records of 16 bytes)
+        self._check_or_free(self.lib.tts_limit(self.handle, out.data_ptr(), B, n, _int32_ptr(ns), c, L, o, st.data_ptr()), st, out if fresh else None)
+        stats = st.to_host().view(LIMIT_RECORD).reshape(B)
+        st.free()
+        if fresh and single:
+            out.shape = (n,)
+        return out, stats
 
     # ------------------------------------------------------------------ attention diagnostics
     def alignment_stats(self, alignments, n_sent=None, n_steps=None, want_durations=False, want_pos=False):
@@ -1680,11 +1825,11 @@ class Engine(object):
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
-                   alignment_stats=None):
-        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The seven settings from ``momentum`` on hold
+                   alignment_stats=None, limiter=None):
+        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` on hold
         for this call alone, as SETTINGS has them."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
-                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats)
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call, o_call = call['speaking_rate'], call['pitch']
@@ -1733,15 +1878,15 @@ class Engine(object):
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
-                        speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None):
+                        speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
-        The seven settings from ``momentum`` on hold for this call alone, as SETTINGS has them: they are read when the call is
+        The eight settings from ``momentum`` on hold for this call alone, as SETTINGS has them: they are read when the call is
         made, not when its work runs.  A call that stops at silence returns once its post-net has run (the lengths:
         ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``)."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
-                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats)
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape

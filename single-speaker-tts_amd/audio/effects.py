@@ -14,11 +14,13 @@ synthesis calls (tts_set_pitch), which stretches the call's magnitudes and resam
 
 ``normalize_loudness`` has no reference counterpart (the reference's only level control is the peak normalisation of save_wav):
 one gain takes a waveform to a target integrated loudness after ITU-R BS.1770-4 (tts_loudness_normalize); the loudness of
-synthesis is the ``loudness`` argument of the synthesis calls (tts_set_loudness)."""
+synthesis is the ``loudness`` argument of the synthesis calls (tts_set_loudness).  ``limit`` is the look-ahead peak limiter behind
+it (tts_limit; the ``limiter`` argument of the synthesis calls, tts_set_limiter)."""
 import numpy as np
 
 from . import default_engine
 from .conversion import ms_to_samples
+from .._hip import limiter_lookahead
 
 
 def pitch_shift(wav, sampling_rate, octaves):
@@ -36,6 +38,20 @@ def normalize_loudness(wav, sampling_rate, target_lufs=-23.0, max_peak=1.0, engi
     array of the input's shape."""
     eng = engine or default_engine()
     out, _gains = eng.loudness_normalize(np.asarray(wav, dtype=np.float32), sampling_rate, target_lufs, max_peak)
+    host = out.to_host()
+    out.free()
+    return host
+
+
+def limit(wav, ceiling, sampling_rate=None, lookahead_ms=5.0, true_peak=True, engine=None):
+    """``wav`` -- one mono waveform (n,) or a batch (B, n) -- through the look-ahead peak limiter (``Engine.limit``): no finite
+    sample of the result is above ``ceiling`` (linear, e.g. 10 ** (-1 / 20)), the gain falls over ``lookahead_ms`` ahead of a peak and
+    recovers over as long behind it, and a waveform that never reaches the ceiling comes back as its own bits.  ``true_peak``:
+    the ceiling is held against the 4x interpolated peaks (``metrics.true_peak``), not the samples alone.  ``sampling_rate``
+    turns the look-ahead into samples (None: the engine's).  Returns a float32 host array of the input's shape."""
+    eng = engine or default_engine()
+    L = limiter_lookahead('limit', lookahead_ms, eng.sampling_rate if sampling_rate is None else sampling_rate)
+    out, _stats = eng.limit(np.asarray(wav, dtype=np.float32), ceiling, L, 4 if true_peak else 1)
     host = out.to_host()
     out.free()
     return host

@@ -3,12 +3,14 @@ measure is the frame-by-frame L1 loss of ``tacotron.evaluate``, which measures t
 speaks a little faster or slower than the recording.  Mel-cepstral distortion along a dynamic-time-warping path compares the
 spectra at the frames that belong together.  The cepstra (tts_mfcc) and the alignment (tts_dtw) run on the device.  Along the
 same path, F0 RMSE, voicing error and gross pitch error compare the prosody (tts_f0, tts_f0_compare), which the cepstra do not
-see.  ``integrated_loudness`` is the level of a waveform as a listener hears it: ITU-R BS.1770-4 / EBU R 128 (tts_loudness)."""
+see.  ``integrated_loudness`` is the level of a waveform as a listener hears it: ITU-R BS.1770-4 / EBU R 128 (tts_loudness); ``true_peak`` is its
+peak between the samples, as delivery specifications state it (tts_true_peak)."""
 import math
 
 import numpy as np
 
 from . import default_engine
+from .._hip import dbtp
 from ..tacotron.params import LJSpeechConstants
 
 MCD_COEFFS = 13
@@ -22,6 +24,16 @@ def integrated_loudness(wav, sampling_rate, engine=None):
     eng = engine or default_engine()
     wav = wav if hasattr(wav, 'data_ptr') and not isinstance(wav, np.ndarray) else np.asarray(wav, dtype=np.float32)
     out = eng.loudness(wav, sampling_rate)
+    return float(out[0]) if len(wav.shape) == 1 else out
+
+
+def true_peak(wav, engine=None):
+    """The true peak of one mono waveform (n,) -- or of every row of a batch (B, n) -- in dBTP after ITU-R BS.1770-4 Annex 2:
+    20 log10 of the largest |value| of the 4x oversampled signal (``Engine.true_peak``), never below the sample peak.  A float
+    for one waveform, a float64 array (B,) for a batch; -inf for digital silence."""
+    eng = engine or default_engine()
+    wav = wav if hasattr(wav, 'data_ptr') and not isinstance(wav, np.ndarray) else np.asarray(wav, dtype=np.float32)
+    out = dbtp(eng.true_peak(wav))
     return float(out[0]) if len(wav.shape) == 1 else out
 
 

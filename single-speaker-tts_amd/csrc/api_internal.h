@@ -55,7 +55,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -267,7 +267,7 @@ struct HostIo {
 };
 
 // The synthesis settings of a handle: what tts_set_end_of_speech, tts_set_speaking_rate, tts_set_pitch, tts_set_loudness,
-// tts_set_alignment_stats and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
+// tts_set_limiter, tts_set_alignment_stats and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
 // copy when the call is made and read nothing but that copy from then on; with every setting off the call enqueues what it
 // always did.  (The stand-alone Griffin-Lim calls have no such copy: they read the handle's momentum and start.)
 struct SynthSettings {
@@ -284,6 +284,12 @@ struct SynthSettings {
         double max_peak = 1.0;
         int sampling_rate = 0;
     } loud;
+    struct {
+        bool enabled = false;
+        double ceiling = 1.0;
+        int lookahead = 0;
+        int oversample = 1;
+    } lim;
     struct {
         bool enabled = false;
         int pad_id = 0;
@@ -599,6 +605,11 @@ int resample_table(tts_handle_t h, double rho, const double** tab);
 int loudness_workspace(tts_handle_t h, int B, int N, int sr);
 int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, int sr, bool normalize, double target_lufs, double max_peak,
                   double* mean_square, int32_t* n_blocks, double* gain);
+// the peak limiter (limiter.hip): arguments checked by the caller (limiter_plan.h).  limiter_workspace sizes the buffers ahead of a
+// call that must not allocate once it has begun to enqueue
+int limiter_workspace(tts_handle_t h, int B, int N);
+int limiter_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, double ceiling, int lookahead, int oversample,
+                 tts_limit_stats_t* stats);
 // attention diagnostics (alignment.hip): arguments checked by the caller (alignment_plan.h).  alignment_workspace sizes the buffers
 // ahead of a call that must not allocate once it has begun to enqueue; d_n_sent: the sentence lengths on the device, or null
 int alignment_workspace(tts_handle_t h, int B, int n_steps_max, int Ts);

@@ -153,6 +153,10 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         const int rc = loudness_workspace(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate);
         if (rc) return rc;
     }
+    if (k.set.lim.enabled) {   // (the limited copy of the rows and its tile flags)
+        const int rc = limiter_workspace(h, B, sp->hop_length * (k.shape.Tw - 1));
+        if (rc) return rc;
+    }
     if (k.set.ali.enabled) {
         // One alignment buffer and one set of scratch: the statistics of a call run behind its decoder on the decoder's stream,
         // in front of whatever lets the next decoder start.  The sentence lengths are written behind the ENCODER, which may run a
@@ -476,15 +480,18 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
         rc = resample_impl(h, k.gl_wav, B, n_gl, detected ? L.n_samples.data() : nullptr, s.rho, N_out, detected ? L.keep.data() : nullptr, k.wav);
         if (!rc && sp->peak_normalize && !k.set.loud.enabled) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
     }
+    // The loudness target and the limiter: every utterance is taken over the samples its row holds -- hop (n[b] - 1) of the reported
+    // lengths with end-of-speech stopping, all of the row otherwise -- in place, behind whatever made the row.
+    std::vector<int32_t> held;
+    if (detected && (k.set.loud.enabled || k.set.lim.enabled))
+        for (int b = 0; b < B; ++b) held.push_back(sp->hop_length * (L.reported[(size_t)b] - 1));
     if (k.set.loud.enabled && !rc) {
-        // The loudness target: every utterance is measured over the samples its row holds -- hop (n[b] - 1) of the reported
-        // lengths with end-of-speech stopping, all of the row otherwise -- and scaled in place, behind whatever made the row.
-        std::vector<int32_t> held;
-        if (detected)
-            for (int b = 0; b < B; ++b) held.push_back(sp->hop_length * (L.reported[(size_t)b] - 1));
         rc = loudness_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.loud.sampling_rate, true,
                            k.set.loud.target_lufs, k.set.loud.max_peak, nullptr, nullptr, nullptr);
     }
+    if (k.set.lim.enabled && !rc)   // (last: behind the loudness gain, or behind the peak normalisation)
+        rc = limiter_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.lim.ceiling, k.set.lim.lookahead,
+                          k.set.lim.oversample, nullptr);
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
 }
@@ -516,6 +523,9 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
     if (set.loud.enabled &&
         (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
         return fail(h, TTS_ERR_INVALID, "synthesize: a loudness target needs rows of 1 .. 2^31 - 1 samples");
+    if (set.lim.enabled &&
+        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
+        return fail(h, TTS_ERR_INVALID, "synthesize: the limiter needs rows of 1 .. 2^31 - 1 samples");
     h->ali.last_dev = nullptr;   // (the records of a call before this one are no longer "the last call's")
     if ((rc = synth_workspaces(h, k))) return rc;
     if (k.pipelined && (rc = synth_streams(h))) return rc;

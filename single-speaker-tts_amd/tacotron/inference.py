@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import attention_check
-from .._hip import (ALIGNMENT_RECORD, JOIN_MAX_FADE, LOUDNESS_MAX_PEAK, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
+from .._hip import (ALIGNMENT_RECORD, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
@@ -85,7 +85,7 @@ def pad_id():
 class SynthSettings(object):
     """The synthesis settings every helper of this layer takes, checked once -- ValueError before an engine is touched, in the
     order of ``_hip.SETTINGS`` -- and kept as the checked values ``momentum``, ``stop``, ``rate``, ``octaves``, ``phase_init``,
-    ``loud`` and ``check_alignment``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
+    ``loud``, ``check_alignment`` and ``limiter``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
 
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind its last frame whose loudest bin is above that many
@@ -105,10 +105,14 @@ class SynthSettings(object):
     integrated loudness (ITU-R BS.1770-4, measured over the samples it holds) on the device instead of being peak-normalised.
     ``check_alignment``: the call also reduces its alignments to one record per utterance on the device
     (``Engine.alignment_stats``; the sentence lengths are taken from the ids' padding) and answers with the records and
-    ``attention_check.verdict`` of every utterance, an empty tuple where the attention read the sentence cleanly."""
+    ``attention_check.verdict`` of every utterance, an empty tuple where the attention read the sentence cleanly.
+    ``limiter``: None (the engine's setting), a ceiling or ``(ceiling, lookahead_ms, oversample)`` -- a look-ahead peak limiter
+    (``Engine.limit``) runs last over every utterance on the device, behind the loudness gain or the peak normalisation: no
+    sample ends above the ceiling, and what never was keeps its bits.  A bare ceiling looks 5 ms ahead at the interpolated
+    (true) peaks."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None):
+                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None):
         momentum_thousandths(momentum)
         self.momentum = momentum
         self.stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
@@ -119,26 +123,29 @@ class SynthSettings(object):
         self.phase_init = phase_init
         self.loud = loudness_setting(loudness)
         self.check_alignment = check_alignment
+        self.limiter = limiter_setting(limiter)
 
     def engine_keywords(self):
         """the settings as ``Engine.synthesize`` / ``Engine.synthesize_host`` take them"""
         return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
-                    phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None)
+                    phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None,
+                    limiter=self.limiter)
 
     def keywords(self):
         """the settings as the helpers of this layer take them (``check_alignment`` apart, which not every one takes)"""
         return dict(momentum=self.momentum, stop_at_silence_db=self.stop_at_silence_db, silence_keep_ms=self.silence_keep_ms,
-                    speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud)
+                    speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter)
 
 
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
                      momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                     phase_init='random', loudness=None, check_alignment=False):
+                     phase_init='random', loudness=None, check_alignment=False, limiter=None):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  The settings from ``momentum`` on: as
     ``SynthSettings`` has them.  With ``stop_at_silence_db`` the result is a list of B waveforms, with ``check_alignment`` it is
     ``(waveforms, records, verdicts)``."""
-    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
+    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
+                      limiter=limiter)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -157,7 +164,7 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
                       want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
-                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False):
+                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False, limiter=None):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -172,7 +179,8 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     ``check_alignment`` every item additionally carries the batch's alignment records and verdicts, ``(wavs, records,
     verdicts)`` or ``(wavs, linear, alignments, records, verdicts)``; the 56 bytes per utterance come down with the waveforms."""
     # (a generator: a bad setting is refused at its first item, before the engine is touched)
-    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
+    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
+                      limiter=limiter)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -236,18 +244,19 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
 
 def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
                          stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                         phase_init='random', loudness=None, check_alignment=False):
+                         phase_init='random', loudness=None, check_alignment=False, limiter=None):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
     float32 WAV, save_wav(norm=True)).  Returns the list of waveforms.  With ``stop_at_silence_db`` every file ends
     ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames.
     The other settings from ``momentum`` on: as ``SynthSettings`` has them (a ``speaking_rate`` of 1.2: a fifth faster; a
-    ``pitch`` of 4 / 12: four semitones up).  With a ``loudness`` the files hold the waveforms at that loudness, not
-    peak-normalised.  With ``check_alignment`` the result is ``(waveforms, report)`` with ``report`` the list of ``{index,
+    ``pitch`` of 4 / 12: four semitones up).  With a ``loudness`` or a ``limiter`` the files hold the waveforms as the device left
+    them, not peak-normalised.  With ``check_alignment`` the result is ``(waveforms, report)`` with ``report`` the list of ``{index,
     verdict, record}`` of ``attention_check.report``, also written to ``alignment_report.json`` beside the wavs."""
     # (ValueError before anything is loaded)
-    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
+    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
+                      limiter=limiter)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -267,7 +276,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
         with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
             json.dump(report, f, indent=1)
     for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, s.loud is None)
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, s.loud is None and s.limiter is None)
     return (list(wavs), report) if check_alignment else list(wavs)
 
 
@@ -275,6 +284,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
 # commonly use, not measured against recordings.
 PAUSES_MS = {'paragraph': 700.0, 'sentence': 350.0, 'clause': 120.0, 'word': 0.0, 'cut': 0.0}
 FADE_MS = 5.0               # the edge fades of a piece (110 samples at 22 050 Hz): untuned
+LIMITED_MAX_PEAK = 4.0      # --loudness with --limit and no --max-peak: +12 dB of headroom for the limiter to take back; untuned
 STOP_AT_SILENCE_DB = -40.0  # where synthesize_text ends a piece unless the caller says otherwise
 
 
@@ -388,7 +398,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     abbreviations), the pieces become ids (``process_sentences``, ``pad_sentence``) and are packed in order into calls of at most
     ``batch_size`` rows (``pack_pieces``); call k runs ``Engine.synthesize`` with seed ``seed`` + k, no normalisation, and leaves
     its waveforms on the device.  ``settings``: the keywords of ``SynthSettings`` (momentum, stop_at_silence_db, silence_keep_ms,
-    speaking_rate, pitch, pitch_semitones, phase_init, loudness); ``stop_at_silence_db`` defaults to -40 dB here and cannot be
+    speaking_rate, pitch, pitch_semitones, phase_init, loudness, limiter); ``stop_at_silence_db`` defaults to -40 dB here and cannot be
     None, because a piece that runs on to max_iterations frames is of no use in a joined text.
 
     Piece b of a call is cut from its row as ``first = hop * lead`` and ``count = hop * (n_frames[b] - 1) - first``, with lead =
@@ -399,7 +409,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     PAUSES_MS: paragraph 700, sentence 350, clause 120, word and cut 0 ms -- untuned), every piece fades over ``fade_ms`` at
     either edge, and one ``Engine.join`` per call lays the pieces of each text into one row on the device.  With a ``loudness``
     one ``Engine.loudness_normalize`` runs over the joined rows, so a text is levelled as a whole and its sentences keep their
-    relative levels.  Only the n_out[g] samples of a row that were said are downloaded.
+    relative levels; with a ``limiter`` one ``Engine.limit`` runs over the joined rows behind it.  Only the n_out[g] samples of a row that were said are downloaded.
 
     A text whose pieces span several calls is concatenated on the host, with the pause behind the earlier part as zeros between
     them; with a ``loudness`` each part is levelled on its own.  The packing decides which pieces share a call, a call's seed
@@ -412,6 +422,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
         raise ValueError('synthesize_text: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)')
     settings.setdefault('stop_at_silence_db', STOP_AT_SILENCE_DB)
     loud = loudness_setting(settings.pop('loudness', None))
+    limiter = limiter_setting(settings.pop('limiter', None))
     s = SynthSettings(model, check_alignment=check_alignment, **settings)
     hp = model.hparams
     pauses = pause_samples(pauses_ms, hp.sampling_rate)
@@ -423,6 +434,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     S = n_steps or model.n_steps()
     it = hp.reconstruction_iterations if n_iter is None else n_iter
     eng = model.engine
+    lookahead = None if limiter is None else limiter_lookahead('synthesize_text', limiter[1], eng.sampling_rate)
     keep_frames = s.stop[1]
     threshold = eng.speech_threshold(s.stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
     parts = [[] for _ in texts]     # per text the waveforms of its parts, one per call that says some of it
@@ -431,7 +443,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     for k, (p0, ids) in enumerate(calls):
         B = ids.shape[0]
         out = eng.synthesize(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len, win_hop, seed=seed + k,
-                             peak_normalize=False, want_linear=True, **dict(s.engine_keywords(), loudness=None))
+                             peak_normalize=False, want_linear=True, **dict(s.engine_keywords(), loudness=None, limiter=None))
         first_active = eng.speech_interval(out['linear'], threshold)[0].to_host()
         if check_alignment:
             records.append(eng.synth_alignment_stats(B))
@@ -445,6 +457,8 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
         joined, n_out = eng.join(out['wav'], pieces, groups, fade)
         if loud is not None:
             eng.loudness_normalize(joined, eng.sampling_rate, loud[0], loud[1], n_samples=n_out)
+        if limiter is not None:
+            eng.limit(joined, limiter[0], lookahead, limiter[2], n_samples=n_out)
         for t, wav, gap in zip(said, eng.download_rows(joined, n_out), tail):
             if parts[t]:
                 parts[t].append(np.zeros(tails[t], dtype=np.float32))
@@ -459,7 +473,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
 
 def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0, seed=0, check_alignment=False, **kw):
     """``synthesize_sentences`` for texts of any length: every entry of ``raw_texts`` becomes one ``{i+1}.wav`` that holds the whole
-    text (``synthesize_text``; ``kw``: its keywords).  Without a ``loudness`` each file is peak-normalised once by save_wav, as
+    text (``synthesize_text``; ``kw``: its keywords).  Without a ``loudness`` or a ``limiter`` each file is peak-normalised once by save_wav, as
     the sentence files are.  Returns the list of waveforms, with ``check_alignment`` ``(waveforms, report)`` -- one ``{index,
     verdict, record}`` per PIECE, each with the index of its ``text`` -- also written to ``alignment_report.json``."""
     from ..datasets.lj_speech import LJSpeechDatasetHelper
@@ -487,7 +501,7 @@ def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0
             json.dump(report, f, indent=1)
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate,
-                 loudness_setting(kw.get('loudness')) is None and len(wav) > 0)   # (a text that says nothing: an empty file)
+                 loudness_setting(kw.get('loudness')) is None and limiter_setting(kw.get('limiter')) is None and len(wav) > 0)   # (a text that says nothing: an empty file)
     return (list(wavs), report) if check_alignment else list(wavs)
 
 
@@ -530,6 +544,7 @@ def main(argv=None):
                                                             [--rate R] [--pitch SEMITONES]
                                                             [--phase-init random|estimate]
                                                             [--loudness LUFS [--max-peak P]]
+                                                            [--limit DB [--limit-lookahead-ms MS] [--sample-peak]]
                                                             [--check-alignment]
                                                             [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
 
@@ -543,6 +558,10 @@ def main(argv=None):
     ``--phase-init estimate``: Griffin-Lim starts from phases estimated from the magnitudes instead of random ones.
     ``--loudness LUFS``: every wav is taken to that integrated loudness (ITU-R BS.1770-4; -23: EBU R 128, -16: a common
     streaming level) with no sample beyond ``--max-peak`` (default 1), instead of being peak-normalised.
+    ``--limit DB``: a look-ahead peak limiter runs last over every wav: no peak above DB decibels relative to full scale (e.g.
+    -1), looking ``--limit-lookahead-ms`` ahead (default 5); the ceiling holds for the interpolated (true) peaks, with
+    ``--sample-peak`` for the samples alone.  The files are then not peak-normalised.  With ``--loudness`` and no ``--max-peak``
+    the loudness gain may then produce samples up to 4.0 (+12 dB of headroom, which the limiter takes back; untuned).
     ``--check-alignment``: the attention diagnostics (``tacotron.attention_check``) -- one JSON line per sentence (index,
     verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts.
     ``--text``: every line of the synthesis file is a text of any length -- sentences, paragraphs (the two characters ``\\n``
@@ -553,7 +572,8 @@ def main(argv=None):
     args = parse_args(argv)
     s = SynthSettings(model_params, args.momentum, args.stop_at_silence, args.silence_keep_ms, args.rate, pitch_semitones=args.pitch,
                       phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
-                      check_alignment=args.check_alignment)
+                      check_alignment=args.check_alignment,
+                      limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4))
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -611,8 +631,14 @@ def parse_args(argv=None):
                     help="Griffin-Lim's start phases: 'random' (default, the reference's) or 'estimate' (tracked from the magnitudes' peaks)")
     ap.add_argument('--loudness', type=float, default=None, metavar='LUFS',
                     help='integrated loudness (ITU-R BS.1770-4) every wav is taken to, e.g. -23; default: peak normalisation')
-    ap.add_argument('--max-peak', type=float, default=LOUDNESS_MAX_PEAK, metavar='P',
-                    help='with --loudness: the largest |sample| the gain may produce (default {:g})'.format(LOUDNESS_MAX_PEAK))
+    ap.add_argument('--max-peak', type=float, default=argparse.SUPPRESS, metavar='P',
+                    help='with --loudness: the largest |sample| the gain may produce (default {:g}; with --limit {:g})'.format(
+                        LOUDNESS_MAX_PEAK, LIMITED_MAX_PEAK))
+    ap.add_argument('--limit', type=float, default=None, metavar='DB',
+                    help='a look-ahead peak limiter behind everything else: no peak above DB decibels re full scale, e.g. -1')
+    ap.add_argument('--limit-lookahead-ms', type=float, default=LIMIT_LOOKAHEAD_MS, metavar='MS',
+                    help='with --limit: how far the limiter looks ahead (default {:g} ms)'.format(LIMIT_LOOKAHEAD_MS))
+    ap.add_argument('--sample-peak', action='store_true', help='with --limit: hold the samples under the ceiling, not the interpolated peaks')
     ap.add_argument('--check-alignment', action='store_true',
                     help='attention diagnostics: one JSON line per sentence and {} beside the wavs'.format(REPORT_FILE))
     ap.add_argument('--text', action='store_true',
@@ -624,7 +650,10 @@ def parse_args(argv=None):
                         ', '.join(BREAKS), ', '.join('{}={:g}'.format(k, PAUSES_MS[k]) for k in BREAKS)))
     ap.add_argument('--fade-ms', type=float, default=FADE_MS, metavar='MS',
                     help='with --text: the fade at either edge of a piece (default {:g} ms)'.format(FADE_MS))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not hasattr(args, 'max_peak'):
+        args.max_peak = LIMITED_MAX_PEAK if args.limit is not None and args.loudness is not None else LOUDNESS_MAX_PEAK
+    return args
 
 
 if __name__ == '__main__':

@@ -8,7 +8,7 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import synth_frame_counts, synth_lengths
+from .._hip import limiter_lookahead, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
 from . import attention_check
 from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, pad_id, pad_sentence, synthesize_stream
@@ -26,16 +26,18 @@ def pre_process_sentences(_sentences, dataset):
 
 def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0, stop_at_silence_db=None,
                               silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random',
-                              loudness=None):
+                              loudness=None, limiter=None):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
     constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86).  The settings from ``momentum`` on mean
     what ``inference.SynthSettings`` says, composed here from the engine's stages: with ``stop_at_silence_db``
     ``Engine.speech_frames`` on the normalised spectrograms, then one ragged Griffin-Lim call, every utterance returned at its own
     length; with a ``speaking_rate`` or a ``pitch`` ``Engine.stretch_magnitudes`` by rate * 2 ** -pitch ahead of Griffin-Lim
     (``init_phase`` has that many frames; lengths min(T', max(min_frames, ceil(n / rate)))) and ``Engine.resample`` by 2 ** -pitch
-    behind it; with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples."""
-    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness)
+    behind it; with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
+    last, over the same samples."""
+    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, limiter=limiter)
     stop, rate, octaves, loud = s.stop, s.rate, s.octaves, s.loud
+    lookahead = None if s.limiter is None else limiter_lookahead('post_process_spectrograms', s.limiter[1], model_params.sampling_rate)
     rho = float(np.exp2(-np.float64(octaves)))
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
@@ -73,9 +75,11 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
             wav = engine.resample(gl_wav, rho, n_samples=None if n_gl is None else win_hop * (n_gl - 1), N_out=win_hop * (T_s - 1))
         finally:
             gl_wav.free()   # (tts_free waits for the device: the resampling that reads it has run)
+    held = None if n_frames is None else win_hop * (np.asarray(n_frames, dtype=np.int32) - 1)
     if loud is not None:
-        engine.loudness_normalize(wav, model_params.sampling_rate, loud[0], loud[1],
-                                  n_samples=None if n_frames is None else win_hop * (np.asarray(n_frames, dtype=np.int32) - 1))
+        engine.loudness_normalize(wav, model_params.sampling_rate, loud[0], loud[1], n_samples=held)
+    if s.limiter is not None:
+        engine.limit(wav, s.limiter[0], lookahead, s.limiter[2], n_samples=held)
     wav = wav.to_host()
     if n_frames is not None:
         return cut_waveforms(wav, n_frames, win_hop)
@@ -84,7 +88,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
           silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None,
-          check_alignment=False):
+          check_alignment=False, limiter=None):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -94,11 +98,12 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     available: batch k is then yielded only after batch k + 2 has been pulled from the generator (the last one when the
     generator ends), which on a request-driven generator would hold every answer back by two requests.
     The settings from ``momentum`` on: as ``inference.SynthSettings`` has them -- with a loudness every answer of the stream
-    comes at the same level.  With ``check_alignment`` every answer is ``(waveforms, records, verdicts)`` -- the alignment
+    comes at the same level, with a limiter under the same ceiling.  With ``check_alignment`` every answer is ``(waveforms, records, verdicts)`` -- the alignment
     records of the batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip
     as the waveforms: a bad utterance can be flagged before it is played."""
     # (a generator: a bad setting is refused at its first item, before a model is made)
-    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment)
+    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
+                      limiter=limiter)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)

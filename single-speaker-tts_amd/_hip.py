@@ -2054,3 +2054,9 @@ class Engine(object):
         assert out.nbytes <= nb.value, (name, out.nbytes, nb.value)
         self._check(self.lib.tts_memcpy_d2h(self.handle, out.ctypes.data, p, out.nbytes))
         return out
+
+    def debug_workspace_extent(self, name):
+        """(device pointer, bytes) of a workspace as it stands now; nothing is copied"""
+        p, nb = c_void_p(), c_size_t()
+        self._check(self.lib.tts_debug_workspace(self.handle, name.encode(), byref(p), byref(nb)))
+        return p.value, nb.value

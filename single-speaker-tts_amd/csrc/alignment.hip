@@ -225,29 +225,14 @@ __global__ __launch_bounds__(64 * ALIGN_ROWS) void text_lengths_kernel(const int
 
 namespace tts_api {
 
-// The scratch of a call on B utterances of n_steps_max steps and Ts positions.  Two sets: the stand-alone entry point runs on the
-// main stream, the statistics of a synthesis call behind its decoder -- under the call pipeline on the front stream -- and
-// nothing orders the one behind the other, so they share no buffer.
-struct AlignScratch {
-    int32_t* pos;
-    float* peak;
-    unsigned char* off;
-    int32_t* dur;
-};
-static int alignment_scratch(tts_handle_t h, bool in_call, int B, int n_steps_max, int Ts, AlignScratch* s) {
+// The scratch of a call on B utterances of n_steps_max steps and Ts positions: the stand-alone calls' set, or a synthesis call's.
+int alignment_scratch(tts_handle_t h, bool in_call, int B, int n_steps_max, int Ts, AlignScratch* s) {
     WS(h, in_call ? "syn.ali_pos" : "ali.pos", int32_t, (size_t)B * n_steps_max, wpos);
     WS(h, in_call ? "syn.ali_peak" : "ali.peak", float, (size_t)B * n_steps_max, wpeak);
     WS(h, in_call ? "syn.ali_off" : "ali.off", unsigned char, (size_t)B * n_steps_max, woff);
     WS(h, in_call ? "syn.ali_dur" : "ali.dur", int32_t, (size_t)B * Ts, wdur);
     *s = AlignScratch{wpos, wpeak, woff, wdur};
     return TTS_OK;
-}
-
-// The scratch of a synthesis call, sized ahead of a call that must not allocate once it has begun to enqueue (alignment_impl asks
-// for the same and finds it in place).
-int alignment_workspace(tts_handle_t h, int B, int n_steps_max, int Ts) {
-    AlignScratch s;
-    return alignment_scratch(h, true, B, n_steps_max, Ts, &s);
 }
 
 // On h->stream; everything has been checked (alignment_check).  d_n_sent: the sentence lengths on the device (a synthesis call;

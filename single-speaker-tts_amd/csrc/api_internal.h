@@ -591,7 +591,28 @@ int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
 // n_workers workgroups, from the handle's store: sets p.items / n_items / slots_per_utt / n_workers for launches on h->stream
 int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len);
 int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr, const int* d_frames = nullptr);
-// end of speech (speech_end.hip / api_stages.hip)
+// ---- Workspaces.  A stage's buffers are named in ONE function, `<stage>_scratch`, which takes the shape that decides their sizes and
+// fills a struct of typed pointers.  The stage asks it for its pointers; a synthesis call asks it ahead for the same shape, before
+// anything of the call is enqueued (synth_workspaces: a workspace that grows synchronises every stream), so the stage finds them in place.
+// Griffin-Lim's (api_stages.hip).  momentum: the handle's or the call's "gl_momentum"; `mom`, the previous projection, exists for a call
+// that has a second iteration to use it, and mom_grew says that this request made or enlarged it (what synth_workspaces counts).
+struct GlgScratch { float2* phase; float* frames; float* mse_partial; float2* mom; bool mom_grew; };   // the general kernels
+int glg_scratch(tts_handle_t h, int B, int T, int win, int n_fft, int momentum, int n_iter, GlgScratch* s);
+// The streaming kernel.  mse_partial has a slot per run of an utterance for ANY planned cut of T frames: no run is shorter than half
+// a round of the waves (tests/gl_plan_check.cpp holds the planner to it).  min_slots: the cuts in hand, which only a cut forced through
+// the debug hooks takes beyond that; frame_mse: the call wants the error, which momentum keeps per frame; own_phase: the handle's
+// pair of phasor-code buffers, for a caller that brings none.
+constexpr unsigned GL_RING = 256;   // work counters: gl_run
+struct GlScratch { float2* mom; bool mom_grew; float* mse_partial; unsigned* counter_ring; float2* phase[2]; };
+int gl_scratch(tts_handle_t h, int B, int T, int momentum, int n_iter, bool frame_mse, int min_slots, bool own_phase, GlScratch* s);
+// A ragged batch's window sum-square rows of `row` floats -- streaming: [2][gl_rw_edge_len], general kernels: n_fft + hop (T_max - 1) --
+// and, with own_lens, room for lengths that are not on the device already (gl_rag_tables fills both)
+struct RagScratch { float* rw; size_t row; int* lens; };
+int gl_rag_scratch(tts_handle_t h, int B, int T_max, int win, int hop, int n_fft, bool streaming, bool own_lens, RagScratch* s);
+int gl_mag_scratch(tts_handle_t h, int B, int T, int row_stride, float** mag);   // the time-major magnitudes Griffin-Lim reads
+// end of speech (speech_end.hip / api_stages.hip); EosScratch::frames: the lengths on the device, for a synthesis call
+struct EosScratch { unsigned char* active; int32_t* frames; };
+int eos_scratch(tts_handle_t h, int B, int T, bool with_frames, EosScratch* s);
 int speech_threshold(float threshold_db, float ref_db, float max_db, float power, int units, float* out);
 int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int keep_frames, int min_frames, int32_t* n_frames, int32_t* last_active);
 // speaking rate (stretch.hip): both layouts of the time-stretch, arguments checked by the caller (stretch_plan.h)
@@ -600,19 +621,21 @@ int stretch_impl(tts_handle_t h, const float* in, int B, int T, int F, int row_s
 // the resampler (resample.hip): arguments checked by the caller (resample_plan.h).  resample_table makes a ratio's table ahead
 // of a call that must not allocate once it has begun to enqueue
 int resample_table(tts_handle_t h, double rho, const double** tab);
-// loudness (loudness.hip): arguments checked by the caller (loudness_plan.h).  loudness_workspace sizes the buffers ahead of a
-// call that must not allocate once it has begun to enqueue
-int loudness_workspace(tts_handle_t h, int B, int N, int sr);
+// loudness (loudness.hip): arguments checked by the caller (loudness_plan.h)
+struct LoudScratch { double *ws, *z; unsigned* peak; };   // ws: the measurement's states and sums, loud_ws_doubles(N, sr) per row
+int loudness_scratch(tts_handle_t h, int B, int N, int sr, LoudScratch* s);
 int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, int sr, bool normalize, double target_lufs, double max_peak,
                   double* mean_square, int32_t* n_blocks, double* gain);
-// the peak limiter (limiter.hip): arguments checked by the caller (limiter_plan.h).  limiter_workspace sizes the buffers ahead of a
-// call that must not allocate once it has begun to enqueue
-int limiter_workspace(tts_handle_t h, int B, int N);
+// the peak limiter (limiter.hip): arguments checked by the caller (limiter_plan.h)
+struct LimScratch { float* out; int* flags; tts_limit_stats_t* stats; };   // the limited copy of the rows, a flag per tile of a row
+int limiter_scratch(tts_handle_t h, int B, int N, LimScratch* s);
 int limiter_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, double ceiling, int lookahead, int oversample,
                  tts_limit_stats_t* stats);
-// attention diagnostics (alignment.hip): arguments checked by the caller (alignment_plan.h).  alignment_workspace sizes the buffers
-// ahead of a call that must not allocate once it has begun to enqueue; d_n_sent: the sentence lengths on the device, or null
-int alignment_workspace(tts_handle_t h, int B, int n_steps_max, int Ts);
+// attention diagnostics (alignment.hip): arguments checked by the caller (alignment_plan.h); d_n_sent: the sentence lengths on the
+// device, or null.  Two sets of scratch: the stand-alone entry point runs on the main stream, the statistics of a synthesis call
+// (in_call) behind its decoder -- under the call pipeline on the front stream -- and nothing orders the one behind the other.
+struct AlignScratch { int32_t* pos; float* peak; unsigned char* off; int32_t* dur; };
+int alignment_scratch(tts_handle_t h, bool in_call, int B, int n_steps_max, int Ts, AlignScratch* s);
 int alignment_impl(tts_handle_t h, const float* alignments, int n_steps_max, int B, int Ts, const int32_t* n_sent, const int32_t* n_steps,
                    const int32_t* d_n_sent, tts_alignment_stats_t* stats, int32_t* durations, int32_t* pos, float* peak);
 int text_lengths_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, int pad_id, int32_t* n_sent);
@@ -621,13 +644,14 @@ int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t*
 void resample_release(tts_handle_t h);
 void mfcc_release(tts_handle_t h);   // cepstrum.hip: the DCT tables
 // estimated initial phases (phase_init.hip): both input layouts -> the public (B, F, T) array on h->stream, arguments checked by
-// the caller (phase_plan.h).  phase_estimate_workspaces sizes its buffers ahead of a call that must not allocate once it has
-// begun to enqueue.  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with the option "gl_init" the
-// estimate from the time-major magnitudes `magi` in the workspace "gl.init_est" (sized by gl_init_workspace), or null.
-int phase_estimate_workspaces(tts_handle_t h, int B, int T, int n_fft, bool from_public);
+// the caller (phase_plan.h).  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with the option "gl_init" the
+// estimate from the time-major magnitudes `magi` in PhaseScratch::init_est, or null.
+// mag_rows: from_public alone (the (B, F, T) input, transposed); the three chunk maps: with more than one chunk of frames alone;
+// init_est: gl_start alone, the estimate as the public-layout init_phase of a Griffin-Lim call
+struct PhaseScratch { float *u_rows, *mag_rows; unsigned short* map_s; unsigned *map_o, *start; float* init_est; };
+int phase_estimate_scratch(tts_handle_t h, int B, int T, int n_fft, bool from_public, bool gl_start, PhaseScratch* s);
 int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_stride, bool time_major, const int32_t* n_frames, int n_fft,
                         int hop, float* out);
-int gl_init_workspace(tts_handle_t h, int B, int T, int n_fft);
 int gl_init_phase(tts_handle_t h, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
                   int hop, const float** out);
 int standalone_begin(tts_handle_t h);

@@ -84,6 +84,9 @@ struct StreamScope {
 };
 
 // Step 1: every workspace of the call, sized before anything of it is enqueued (a growing workspace synchronises every stream).
+// A stage's buffers come from the stage's own `*_scratch` function (api_internal.h), which the stage asks again for the same
+// shape: no name or size of another stage stands here.  The call's own -- the per-parity "syn.*", the stretched magnitudes, the
+// shifted call's waveforms, the pinned end-of-speech words -- do.
 static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     const tts_config_t& c = h->cfg;
     auto& pl = h->pl;
@@ -96,26 +99,23 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     // workspaces: a call whose caller stops passing mel_out allocates "syn.mel0" and stays pipelined.)
     bool setting_grew = false;
     unsigned allocs = 0;
-    if (!k.gl_streaming) {
-        // the general kernels' tables and workspaces, sized HERE, before anything of this call is enqueued on the front or
-        // encoder streams (a growing workspace synchronises every stream; gl_run_generic finds them in place)
+    int rc = TTS_OK;
+    // Griffin-Lim's workspaces, from the function its kernel family asks again (gl_run_generic / gl_run); of these only the momentum
+    // buffer is a setting's.  (ONE momentum buffer: only Griffin-Lim launches touch it, and those of consecutive calls follow each
+    // other on the main stream.  The streaming kernel's partials have room for any cut the call may plan, narrow or wide.)
+    GlgScratch gg{};
+    GlScratch gs{};
+    if (!k.gl_streaming) {   // (and the general kernels' tables)
         if ((long long)sp->hop_length * (Tg - 1) <= c.n_fft / 2)
             return fail(h, TTS_ERR_INVALID, "griffin_lim: signal shorter than n_fft/2 (reflect padding undefined)");
-        int rc = glg_prepare(h, Tg, sp->win_length, sp->hop_length, c.n_fft);
-        if (rc) return rc;
         const float2* tw_unused = nullptr;
-        if ((rc = glg_twiddles(h, c.n_fft, &tw_unused))) return rc;
-        WS(h, "glg.phase", float2, (size_t)B * Tg * FP, glg_ph);
-        WS(h, "glg.frames", float, (size_t)B * Tg * sp->win_length, glg_fr);
-        WS(h, "glg.mse_partial", float, (size_t)B * Tg, glg_ms);
-        (void)glg_ph; (void)glg_fr; (void)glg_ms;
-        if (k.set.gl_momentum > 0 && sp->n_iter > 1) {
-            allocs = h->ws_allocs;
-            WS(h, "glg.mom", float2, (size_t)B * Tg * FP, glg_mc);
-            (void)glg_mc;
-            setting_grew |= h->ws_allocs != allocs;
-        }
+        if ((rc = glg_prepare(h, Tg, sp->win_length, sp->hop_length, c.n_fft)) || (rc = glg_twiddles(h, c.n_fft, &tw_unused)) ||
+            (rc = glg_scratch(h, B, Tg, sp->win_length, c.n_fft, k.set.gl_momentum, sp->n_iter, &gg)))
+            return rc;
+    } else if ((rc = gl_scratch(h, B, Tg, k.set.gl_momentum, sp->n_iter, false, 0, false, &gs))) {
+        return rc;
     }
+    setting_grew |= gg.mom_grew || gs.mom_grew;
     // (one encoder output per call parity: the encoder of call k + 1 writes one while the decoder of call k reads the other)
     WS(h, "syn.memory.even", float, (size_t)B * Ts * 2 * c.n_gru_units, memory_e);
     WS(h, "syn.memory.odd", float, (size_t)B * Ts * 2 * c.n_gru_units, memory_o);
@@ -138,8 +138,7 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "syn.mel1", float, (size_t)B * T * c.n_mels, melb1);
         k.mel = parity ? melb1 : melb0;
     }
-    WS(h, "gl.mag", float, (size_t)B * T * FP, magi);
-    k.magi = magi;
+    if ((rc = gl_mag_scratch(h, B, T, FP, &k.magi))) return rc;
     allocs = h->ws_allocs;
     if (k.shape.stretch) {   // (same_call below also compares Tg, which sizes the phasor codes)
         WS(h, "gl.mag_st", float, (size_t)B * Tg * FP, mags);
@@ -149,14 +148,11 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "gl.wav_pitch", float, (size_t)B * sp->hop_length * (size_t)(Tg - 1), glw);
         k.gl_wav = glw;
     }
-    if (k.set.loud.enabled) {   // (the measurement's states and sums, for rows of hop (Tw - 1) samples)
-        const int rc = loudness_workspace(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate);
-        if (rc) return rc;
-    }
-    if (k.set.lim.enabled) {   // (the limited copy of the rows and its tile flags)
-        const int rc = limiter_workspace(h, B, sp->hop_length * (k.shape.Tw - 1));
-        if (rc) return rc;
-    }
+    // (the loudness measurement and the limiter take rows of hop (Tw - 1) samples)
+    LoudScratch loud;
+    LimScratch lim;
+    if (k.set.loud.enabled && (rc = loudness_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate, &loud))) return rc;
+    if (k.set.lim.enabled && (rc = limiter_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), &lim))) return rc;
     if (k.set.ali.enabled) {
         // One alignment buffer and one set of scratch: the statistics of a call run behind its decoder on the decoder's stream,
         // in front of whatever lets the next decoder start.  The sentence lengths are written behind the ENCODER, which may run a
@@ -172,14 +168,12 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
             WS(h, "syn.ali_stats", tts_alignment_stats_t, (size_t)B, ali_st);
             k.ali_stats = ali_st;
         }
-        const int rc = alignment_workspace(h, B, sp->n_steps, Ts);
-        if (rc) return rc;
+        AlignScratch ali;
+        if ((rc = alignment_scratch(h, true, B, sp->n_steps, Ts, &ali))) return rc;
     }
     // (estimated initial phases, option "gl_init": the estimate's buffers, for the frames Griffin-Lim reconstructs from)
-    if (k.set.gl_init && !k.init_phase) {
-        const int rc = gl_init_workspace(h, B, Tg, c.n_fft);
-        if (rc) return rc;
-    }
+    PhaseScratch est;
+    if (k.set.gl_init && !k.init_phase && (rc = phase_estimate_scratch(h, B, Tg, c.n_fft, false, true, &est))) return rc;
     setting_grew |= h->ws_allocs != allocs;
     // Under the call pipeline the initial phasors of a call are written on the FRONT stream, behind its decoder (that
     // stream has slack, the main one bounds the step): the phasor-code buffers are then a pair per call parity, so that
@@ -190,29 +184,18 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     WS(h, "syn.phase1.even", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph1e);
     WS(h, "syn.phase0.odd", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph0o);
     WS(h, "syn.phase1.odd", unsigned, (size_t)B * Tg * FP * (gl_state_bytes() / sizeof(unsigned)), gph1o);
-    // (momentum: the previous projection, 8 bytes per bin; ONE buffer -- only Griffin-Lim launches touch it, and those of
-    //  consecutive calls follow each other on the main stream)
     allocs = h->ws_allocs;
-    if (k.gl_streaming && k.set.gl_momentum > 0 && sp->n_iter > 1) {
-        WS(h, "gl.mom", float2, (size_t)B * Tg * FP, gl_mc);
-        (void)gl_mc;
-    }
     if (k.set.eos.enabled) {
-        // the detection's row flags and lengths, the ragged Griffin-Lim's window sum-square tables (gl_rag_tables asks for the same
-        // size and finds them in place) and the pinned words the host reads the lengths from: nothing grows in mid-call
-        const size_t rw_row = k.gl_streaming ? 2 * (size_t)gl_rw_edge_len(c.n_fft, sp->win_length, sp->hop_length)
-                                             : (size_t)c.n_fft + (size_t)sp->hop_length * (Tg - 1);
+        // the detection's row flags and lengths (speech_frames_impl asks eos_scratch again), the ragged Griffin-Lim's tables
+        // (gl_rag_tables asks gl_rag_scratch again; with a speaking rate the stretched lengths are the host's, which it uploads)
+        // and the pinned words the host reads the lengths from: nothing grows in mid-call
         // (a larger stand-alone ragged call may have left smaller buffers: growing them counts like making them)
-        WS(h, "eos.active", unsigned char, (size_t)B * T, eos_act);
-        WS(h, "eos.frames", int32_t, (size_t)B, eos_fr);
-        (void)eos_act;
-        k.d_frames = eos_fr;
-        WS(h, "gl.rag_rw", float, (size_t)B * rw_row, eos_rw);
-        (void)eos_rw;
-        if (k.shape.stretch) {   // (the stretched lengths are the host's: the ragged Griffin-Lim uploads them, gl_rag_tables)
-            WS(h, "gl.rag_lens", int, (size_t)B, eos_lens);
-            (void)eos_lens;
-        }
+        EosScratch eos;
+        RagScratch rag;
+        if ((rc = eos_scratch(h, B, T, true, &eos)) ||
+            (rc = gl_rag_scratch(h, B, Tg, sp->win_length, sp->hop_length, c.n_fft, k.gl_streaming, k.shape.stretch, &rag)))
+            return rc;
+        k.d_frames = eos.frames;
         if (h->eos.pinned_room < B) {   // (read behind a synchronisation inside the call that filled it: never in flight here)
             setting_grew = true;
             if (h->eos.pinned) HIPCHK(h, hipHostFree(h->eos.pinned));

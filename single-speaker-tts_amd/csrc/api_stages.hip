@@ -174,24 +174,19 @@ int stft_prepare(tts_handle_t h, int n, int win, int hop, int n_fft) {
 
 
 int stft_run(tts_handle_t h, const float* wav, int B, int n, int n_fft, int win, int hop, float2** out, int* Tf_out) {
-    if (n_fft != TTS_GL_NFFT) {   // the general kernels: one workgroup per frame, FFT in LDS (griffin_lim_generic.hip)
+    const bool general = n_fft != TTS_GL_NFFT;   // the general kernels: one workgroup per frame, FFT in LDS (griffin_lim_generic.hip)
+    const float2* tw = nullptr;
+    int rc;
+    if (general) {
         if (n <= n_fft / 2) return fail(h, TTS_ERR_INVALID, "stft: signal shorter than n_fft/2 (reflect padding undefined)");
-        int rc = glg_prepare(h, 0, win, hop, n_fft);
-        if (rc) return rc;
-        const float2* tw = nullptr;
-        if ((rc = glg_twiddles(h, n_fft, &tw))) return rc;
-        const int Tf = 1 + n / hop, Fp = gl_fp(n_fft);
-        WS(h, "an.stft", float2, (size_t)B * Tf * Fp, buf);
-        HIPCHK(h, launch_glg_stft(h->stream, wav, n, h->glg.window, tw, buf, B, Tf, Fp, n_fft, win, hop, 1, nullptr, nullptr));
-        *out = buf;
-        *Tf_out = Tf;
-        return TTS_OK;
+        if ((rc = glg_prepare(h, 0, win, hop, n_fft)) || (rc = glg_twiddles(h, n_fft, &tw))) return rc;
+    } else if ((rc = stft_prepare(h, n, win, hop, n_fft))) {
+        return rc;
     }
-    int rc = stft_prepare(h, n, win, hop, n_fft);
-    if (rc) return rc;
-    const int Tf = 1 + n / hop;
-    WS(h, "an.stft", float2, (size_t)B * Tf * TTS_GL_FP, buf);
-    HIPCHK(h, launch_stft(h->stream, wav, B, n, Tf, h->an.window, win, hop, h->gl.tw1024, h->gl.tw2048, buf, TTS_GL_FP));
+    const int Tf = 1 + n / hop, Fp = gl_fp(n_fft);   // (TTS_GL_FP at 2048)
+    WS(h, "an.stft", float2, (size_t)B * Tf * Fp, buf);
+    if (general) HIPCHK(h, launch_glg_stft(h->stream, wav, n, h->glg.window, tw, buf, B, Tf, Fp, n_fft, win, hop, 1, nullptr, nullptr));
+    else HIPCHK(h, launch_stft(h->stream, wav, B, n, Tf, h->an.window, win, hop, h->gl.tw1024, h->gl.tw2048, buf, Fp));
     *out = buf;
     *Tf_out = Tf;
     return TTS_OK;
@@ -298,6 +293,17 @@ static void gl_rwss_edges(const std::vector<double>& wd, int n_fft, int hop, int
     std::copy(r.end() - m, r.end(), out + E);
 }
 
+int gl_rag_scratch(tts_handle_t h, int B, int T_max, int win, int hop, int n_fft, bool streaming, bool own_lens, RagScratch* s) {
+    const size_t row = streaming ? 2 * (size_t)gl_rw_edge_len(n_fft, win, hop) : (size_t)n_fft + (size_t)hop * (T_max - 1);
+    WS(h, "gl.rag_rw", float, (size_t)B * row, rw);
+    *s = RagScratch{rw, row, nullptr};
+    if (own_lens) {
+        WS(h, "gl.rag_lens", int, (size_t)B, lens);
+        s->lens = lens;
+    }
+    return TTS_OK;
+}
+
 // Uploads the lengths and the window sum-square tables of a ragged batch (h->rag.lens / rw) unless the last call's are the same.
 // streaming: [B][2][E] edge tables; general kernels: a whole row of n_fft + hop (T_max - 1) per utterance, made for its length.
 // d_frames: the lengths are in device memory already (tts_synthesize: what its detection kernel left, which the host has read
@@ -309,18 +315,15 @@ static void gl_rwss_edges(const std::vector<double>& wd, int n_fft, int hop, int
 static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_max, int win, int hop, int n_fft, bool streaming,
                          const int* d_frames = nullptr) {
     const int E = gl_rw_edge_len(n_fft, win, hop);
-    const size_t row = streaming ? 2 * (size_t)E : (size_t)n_fft + (size_t)hop * (T_max - 1);
-    const int* d_lens = d_frames;
-    int* own_lens = nullptr;
-    if (!d_frames) {
-        WS(h, "gl.rag_lens", int, (size_t)B, lens_ws);
-        d_lens = own_lens = lens_ws;
-    }
-    WS(h, "gl.rag_rw", float, (size_t)B * row, d_rw);
+    RagScratch s;
+    const int rc = gl_rag_scratch(h, B, T_max, win, hop, n_fft, streaming, !d_frames, &s);
+    if (rc) return rc;
+    const size_t row = s.row;
+    const int* d_lens = d_frames ? d_frames : s.lens;
     std::vector<int> key = {streaming ? 1 : 0, n_fft, win, hop, T_max, B};
     key.insert(key.end(), n_frames, n_frames + B);
     auto& r = h->rag;
-    if (r.lens == d_lens && r.rw == d_rw && r.tab_key == key) return TTS_OK;
+    if (r.lens == d_lens && r.rw == s.rw && r.tab_key == key) return TTS_OK;
     std::vector<double> wd;
     std::vector<float> wf;
     hann_window(win, wd, wf);
@@ -344,9 +347,9 @@ static int gl_rag_tables(tts_handle_t h, const int32_t* n_frames, int B, int T_m
     }
     r.tab_key.clear();
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (an earlier call may still read the tables)
-    if (own_lens) HIPCHK(h, hipMemcpy(own_lens, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_rw, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-    r.lens = d_lens; r.rw = d_rw; r.tab_key = key;
+    if (s.lens) HIPCHK(h, hipMemcpy(s.lens, n_frames, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(s.rw, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    r.lens = d_lens; r.rw = s.rw; r.tab_key = key;
     return TTS_OK;
 }
 
@@ -426,6 +429,24 @@ int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers,
 }
 
 
+// fast Griffin-Lim keeps the previous projection per bin for a call that has a second iteration to use it
+static bool gl_momentum_on(int momentum, int n_iter) { return momentum > 0 && n_iter > 1; }
+
+int glg_scratch(tts_handle_t h, int B, int T, int win, int n_fft, int momentum, int n_iter, GlgScratch* s) {
+    const int Fp = gl_fp(n_fft);
+    WS(h, "glg.phase", float2, (size_t)B * T * Fp, ph);
+    WS(h, "glg.frames", float, (size_t)B * T * win, frames);
+    WS(h, "glg.mse_partial", float, (size_t)B * T, msep);
+    *s = GlgScratch{ph, frames, msep, nullptr, false};
+    if (gl_momentum_on(momentum, n_iter)) {
+        const unsigned allocs = h->ws_allocs;
+        WS(h, "glg.mom", float2, (size_t)B * T * Fp, mc);
+        s->mom = mc;
+        s->mom_grew = h->ws_allocs != allocs;
+    }
+    return TTS_OK;
+}
+
 // mag_int: [B][T][Fp] (Fp = gl_fp(n_fft)); init_ft: reference-layout U[0,1) numbers or null (then the seed)
 int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win,
                    int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames, const int* d_frames) {
@@ -445,16 +466,11 @@ int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, u
     const float2* tw = nullptr;
     if ((rc = glg_twiddles(h, n_fft, &tw))) return rc;
     const int F = 1 + n_fft / 2, Fp = gl_fp(n_fft), L = hop * (T - 1);
-    WS(h, "glg.phase", float2, (size_t)B * T * Fp, ph);
-    WS(h, "glg.frames", float, (size_t)B * T * win, frames);
-    WS(h, "glg.mse_partial", float, (size_t)B * T, msep);
-    // fast Griffin-Lim: the previous projection per bin, allocated only for a call that has a second iteration to use it
+    GlgScratch g;
+    if ((rc = glg_scratch(h, B, T, win, n_fft, h->settings.gl_momentum, n_iter, &g))) return rc;
+    float2 *const ph = g.phase, *const mom_c = g.mom;   // (fast Griffin-Lim: the previous projection per bin, or null)
+    float *const frames = g.frames, *const msep = g.mse_partial;
     const float alpha = (float)(h->settings.gl_momentum / 1000.0);
-    float2* mom_c = nullptr;
-    if (h->settings.gl_momentum > 0 && n_iter > 1) {
-        WS(h, "glg.mom", float2, (size_t)B * T * Fp, mc);
-        mom_c = mc;
-    }
     float* sig = wav;   // every iteration's signal estimate lives in the caller's buffer: the last one is the result
     HIPCHK(h, launch_glg_phase_init(h->stream, init_ft, seed, ph, B, F, T, Fp, d_lens));
     {
@@ -521,6 +537,28 @@ int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft) {
 }
 
 
+int gl_scratch(tts_handle_t h, int B, int T, int momentum, int n_iter, bool frame_mse, int min_slots, bool own_phase, GlScratch* s) {
+    const int FP = TTS_GL_FP;
+    *s = GlScratch{};
+    if (gl_momentum_on(momentum, n_iter)) {   // the previous projection per bin, 8 bytes
+        const unsigned allocs = h->ws_allocs;
+        WS(h, "gl.mom", float2, (size_t)B * T * FP, mc);
+        s->mom = mc;
+        s->mom_grew = h->ws_allocs != allocs;
+    }
+    // (with momentum the squared error is kept per frame: gl_stream_kernel, MOM)
+    const int slots = std::max(min_slots, T / (GL_NW / 2) + 1);
+    WS(h, "gl.mse_partial", float, (size_t)B * ((s->mom && frame_mse) ? std::max(slots, T) : slots), msep);
+    WS(h, "gl.counter_ring", unsigned, GL_RING, ring);
+    s->mse_partial = msep; s->counter_ring = ring;
+    if (own_phase) {   // 4 bytes per bin: the state between iterations is a 32-bit phasor code (griffin_lim.hip)
+        WS(h, "gl.phase0", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), own0);
+        WS(h, "gl.phase1", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), own1);
+        s->phase[0] = reinterpret_cast<float2*>(own0); s->phase[1] = reinterpret_cast<float2*>(own1);
+    }
+    return TTS_OK;
+}
+
 // mag_int: internal [B][T][FP]; init_ft: reference-layout U[0,1) numbers or null.
 // phase_pair: the two phasor-code buffers to iterate in (null: the handle's own pair); phase_ready: phase_pair[0] already
 // holds the initial phasors (written on another stream, ordered by the caller's events).
@@ -535,14 +573,6 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     // batch (written on the front stream without lengths: a superset of what the ragged launches read)
     if (n_frames && (rc = gl_rag_tables(h, n_frames, B, T, win, hop, n_fft, true, d_frames))) return rc;
     const int F = 1 + n_fft / 2, FP = TTS_GL_FP;
-    float2 *ph0, *ph1;
-    if (phase_pair) {
-        ph0 = phase_pair[0]; ph1 = phase_pair[1];
-    } else {   // 4 bytes per bin: the state between iterations is a 32-bit phasor code (griffin_lim.hip)
-        WS(h, "gl.phase0", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), own0);
-        WS(h, "gl.phase1", unsigned, (size_t)B * T * FP * (gl_state_bytes() / sizeof(unsigned)), own1);
-        ph0 = reinterpret_cast<float2*>(own0); ph1 = reinterpret_cast<float2*>(own1);
-    }
     GlParams p;
     std::memset(&p, 0, sizeof(p));
     p.mag = mag_int;
@@ -570,12 +600,10 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     int per_launch = h->gl_pair;
     per_launch = per_launch < 1 ? 1 : (per_launch > 3 ? 3 : per_launch);
     while (per_launch > 1 && gl_stream_ring_frames(win, hop, per_launch) <= 0) --per_launch;
-    // fast Griffin-Lim (option "gl_momentum"): the previous projection per bin, 8 bytes, allocated only for a call that has a
-    // second iteration to use it; such a call runs one iteration per launch (gl_stream_kernel, MOM) and is cut for that form.
-    // Without momentum nothing below differs from what it was: p.mom_c stays null and the plain instantiations are launched.
-    if (h->settings.gl_momentum > 0 && n_iter > 1) {
-        WS(h, "gl.mom", float2, (size_t)B * T * FP, mc);
-        p.mom_c = mc;
+    // fast Griffin-Lim (option "gl_momentum"): a call that has a second iteration to use the previous projection runs one
+    // iteration per launch (gl_stream_kernel, MOM) and is cut for that form.  Without momentum nothing below differs from what
+    // it was: p.mom_c stays null and the plain instantiations are launched.
+    if (gl_momentum_on(h->settings.gl_momentum, n_iter)) {
         p.mom_alpha = (float)(h->settings.gl_momentum / 1000.0);
         per_launch = 1;
     }
@@ -591,7 +619,7 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     // A ragged batch under the pipeline (tts_synthesize with end-of-speech stopping) has new lengths in every call, so both
     // cuts are planned in the call -- on the host, behind the wait for the lengths, while the main stream is idle.  Its wide
     // cut is therefore planned where its first launch comes up: the narrow launches are enqueued by then and the planner
-    // runs beside them.  (The partials' workspace is sized for any cut: no run is shorter than half a round of the waves.)
+    // runs beside them.  (The partials' workspace is sized for any planned cut: gl_scratch.)
     bool wide_planned = !(two_cuts && n_frames);
     if (two_cuts && wide_planned && (rc = gl_plan(h, pw, n_frames, n_cus, per_launch, 0, 0))) return rc;
     auto plan_wide = [&]() -> int {
@@ -599,15 +627,20 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
         wide_planned = true;
         return gl_plan(h, pw, n_frames, n_cus, per_launch, 0, 0);
     };
-    const int nchunks = wide_planned ? std::max(p.slots_per_utt, pw.slots_per_utt) : std::max(p.slots_per_utt, T / (GL_NW / 2) + 1);
-    // (with momentum the squared error is kept per frame: gl_stream_kernel, MOM)
-    WS(h, "gl.mse_partial", float, (size_t)B * ((p.mom_c && mse) ? std::max(nchunks, T) : nchunks), msep);
+    // (a pipelined call finds these as synth_workspaces left them, asked for the same shape; the slots of the cuts in hand count
+    //  only where a forced cut has more runs than any planned one)
+    GlScratch ws;
+    if ((rc = gl_scratch(h, B, T, h->settings.gl_momentum, n_iter, mse != nullptr, std::max(p.slots_per_utt, pw.slots_per_utt), !phase_pair, &ws)))
+        return rc;
+    p.mom_c = pw.mom_c = ws.mom;
+    float* const msep = ws.mse_partial;
+    float2* cur = phase_pair ? phase_pair[0] : ws.phase[0];
+    float2* nxt = phase_pair ? phase_pair[1] : ws.phase[1];
     // One zeroed work counter per launch (the persistent workgroups draw their item ids from it): slots of a ring that is
     // zeroed ONCE; a launch takes the next slot and zeroes the slot of the launch before it on the stream, which is drained
     // by then.  (Until round 4 a memset per call: two fill kernels and their dependencies, 0.1 ms between the post-net and
     // the first Griffin-Lim launch of every call, on the stream that bounds the step.)
-    constexpr unsigned GL_RING = 256;
-    WS(h, "gl.counter_ring", unsigned, GL_RING, ring);
+    unsigned* const ring = ws.counter_ring;
     if (ring != h->gl_ring || h->gl_ring_stream != h->stream) {   // new buffer, or launches of another stream before these
         HIPCHK(h, hipMemsetAsync(ring, 0, GL_RING * sizeof(unsigned), h->stream));
         h->gl_ring = ring;
@@ -621,12 +654,10 @@ int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t 
     };
     // a seeded start with at least one iteration needs no codes: the first launch makes the initial phasors itself
     const bool seed_in_kernel = !init_ft && n_iter >= 1;
-    if (!phase_ready && !seed_in_kernel) HIPCHK(h, launch_phase_init(h->stream, init_ft, seed, ph0, B, F, T, FP, p.n_frames));
+    if (!phase_ready && !seed_in_kernel) HIPCHK(h, launch_phase_init(h->stream, init_ft, seed, cur, B, F, T, FP, p.n_frames));
     p.F = pw.F = F;
     p.seed = pw.seed = seed;
     int launch_idx = 0, mse_chunks = p.slots_per_utt, peak_chunks = p.slots_per_utt;
-    float2* cur = ph0;
-    float2* nxt = ph1;
     {
         ProfScope ps(h, ST_GL_ITER, n_iter);
         // the streaming kernel runs two iterations per launch (gl_stream_kernel, NST = 2) wherever no per-iteration result
@@ -1181,21 +1212,21 @@ namespace tts_api {
 // The init_phase of a Griffin-Lim call.  An explicit one always wins; otherwise, with the option "gl_init" = 1, the phases are
 // estimated from the magnitudes the call reconstructs from (time-major rows, `magi`) into a workspace in the public layout and
 // handed on exactly as a caller's array would be -- the launches cannot tell the two apart, so the waveform has the same bits.
-int gl_init_workspace(tts_handle_t h, int B, int T, int n_fft) {
-    WS(h, "gl.init_est", float, (size_t)B * (1 + n_fft / 2) * T, est);
-    (void)est;
-    return phase_estimate_workspaces(h, B, T, n_fft, false);
-}
-
 int gl_init_phase(tts_handle_t h, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
                   int hop, const float** out) {
     *out = init_phase;
     if (init_phase || !h->settings.gl_init) return TTS_OK;
-    int rc = gl_init_workspace(h, B, T, n_fft);
-    if (rc) return rc;
-    WS(h, "gl.init_est", float, (size_t)B * (1 + n_fft / 2) * T, est);
-    if ((rc = phase_estimate_impl(h, magi, B, T, row_stride, true, n_frames, n_fft, hop, est))) return rc;
-    *out = est;
+    PhaseScratch s;
+    int rc = phase_estimate_scratch(h, B, T, n_fft, false, true, &s);
+    if (rc || (rc = phase_estimate_impl(h, magi, B, T, row_stride, true, n_frames, n_fft, hop, s.init_est))) return rc;
+    *out = s.init_est;
+    return TTS_OK;
+}
+
+// The time-major magnitudes Griffin-Lim reconstructs from: B utterances of T rows of row_stride floats.
+int gl_mag_scratch(tts_handle_t h, int B, int T, int row_stride, float** mag) {
+    WS(h, "gl.mag", float, (size_t)B * T * row_stride, m);
+    *mag = m;
     return TTS_OK;
 }
 
@@ -1213,16 +1244,18 @@ int tts_griffin_lim(tts_handle_t h, const float* mag, const float* init_phase, u
         if (T < 1 || win_length < 2 || win_length > n_fft || hop_length < 1)
             return fail(h, TTS_ERR_INVALID, "griffin_lim: need 2 <= win_length <= n_fft, hop_length >= 1, T >= 1");
         const int Fg = 1 + n_fft / 2, Fp = gl_fp(n_fft);
-        WS(h, "gl.mag", float, (size_t)B * T * Fp, magg);
-        HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magg, B, Fg, T, Fp));
-        int rcg = gl_init_phase(h, magg, init_phase, B, T, Fp, nullptr, n_fft, hop_length, &init_phase);
+        float* magg = nullptr;
+        int rcg = gl_mag_scratch(h, B, T, Fp, &magg);
         if (rcg) return rcg;
+        HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magg, B, Fg, T, Fp));
+        if ((rcg = gl_init_phase(h, magg, init_phase, B, T, Fp, nullptr, n_fft, hop_length, &init_phase))) return rcg;
         return gl_run_generic(h, magg, init_phase, seed, B, T, n_iter, win_length, hop_length, n_fft, wav, mse, false);
     }
     int rc = gl_prepare(h, T, win_length, hop_length, n_fft);
     if (rc) return rc;
     const int F = 1 + n_fft / 2, FP = TTS_GL_FP;
-    WS(h, "gl.mag", float, (size_t)B * T * FP, magi);
+    float* magi = nullptr;
+    if ((rc = gl_mag_scratch(h, B, T, FP, &magi))) return rc;
     HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magi, B, F, T, FP));
     if ((rc = gl_init_phase(h, magi, init_phase, B, T, FP, nullptr, n_fft, hop_length, &init_phase))) return rc;
     return gl_run(h, magi, init_phase, seed, B, T, n_iter, win_length, hop_length, n_fft, wav, mse);
@@ -1252,7 +1285,8 @@ int tts_griffin_lim_ragged(tts_handle_t h, const float* mag, const float* init_p
     int rc = streaming ? gl_prepare(h, T_max, win_length, hop_length, n_fft) : TTS_OK;
     if (rc) return rc;
     if ((rc = gl_rag_tables(h, n_frames, B, T_max, win_length, hop_length, n_fft, streaming))) return rc;
-    WS(h, "gl.mag", float, (size_t)B * T_max * Fp, magi);
+    float* magi = nullptr;
+    if ((rc = gl_mag_scratch(h, B, T_max, Fp, &magi))) return rc;
     HIPCHK(h, launch_mag_ft_to_tf(h->stream, mag, magi, B, F, T_max, Fp, h->rag.lens));
     if ((rc = gl_init_phase(h, magi, init_phase, B, T_max, Fp, n_frames, n_fft, hop_length, &init_phase))) return rc;
     if (!streaming) return gl_run_generic(h, magi, init_phase, seed, B, T_max, n_iter, win_length, hop_length, n_fft, wav, mse, false, n_frames);

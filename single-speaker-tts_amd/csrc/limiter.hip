@@ -242,31 +242,30 @@ static LimCoef lim_coef() {
     return c;
 }
 
-// The workspaces of a tts_limit call on B rows of N samples, sized ahead of a call that must not allocate once it has begun to
-// enqueue (limiter_impl asks for the same and finds them in place).
-int limiter_workspace(tts_handle_t h, int B, int N) {
+// The workspaces of a tts_limit call on B rows of N samples.
+int limiter_scratch(tts_handle_t h, int B, int N, LimScratch* s) {
     WS(h, "lim.out", float, (size_t)B * N, out);
     WS(h, "lim.flags", int, (size_t)B * lim_tiles(N), flags);
     WS(h, "lim.stats", tts_limit_stats_t, (size_t)B, st);
-    (void)out; (void)flags; (void)st;
+    *s = LimScratch{out, flags, st};
     return TTS_OK;
 }
 
 // On h->stream; everything has been checked (limiter_check).
 int limiter_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, double ceiling, int lookahead, int oversample,
                  tts_limit_stats_t* stats) {
-    WS(h, "lim.out", float, (size_t)B * N, out);
-    WS(h, "lim.flags", int, (size_t)B * lim_tiles(N), flags);
-    WS(h, "lim.stats", tts_limit_stats_t, (size_t)B, own_stats);
+    LimScratch s;
+    const int rc = limiter_scratch(h, B, N, &s);
+    if (rc) return rc;
     const size_t flags_row = (size_t)lim_tiles(N);   // a flag per tile of a row
     const LimCoef coef = lim_coef();
     const float cf = lim_ceiling_float(ceiling);
     const size_t lds = lim_lds_bytes(lookahead);
     if (lds > 64 * 1024)   // (what this call asks for, not all 160 KB: the block-wide vote keeps a few bytes of its own)
         HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&lim_gain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    tts_limit_stats_t* st = stats ? stats : own_stats;
+    tts_limit_stats_t* st = stats ? stats : s.stats;
     ProfScope ps(h, ST_LIMITER, (int64_t)length_chunks(B, LIM_UTTS) * 3 + 1);
-    HIPCHK(h, hipMemsetAsync(flags, 0, (size_t)B * flags_row * sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(s.flags, 0, (size_t)B * flags_row * sizeof(int), h->stream));
     for (int b0 = 0; b0 < B; b0 += LIM_UTTS) {
         const int nb = std::min(LIM_UTTS, B - b0);
         LimLens lens;
@@ -275,8 +274,8 @@ int limiter_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samp
         for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
         const dim3 grid((unsigned)lim_tiles(longest), nb);
         float* pw = wav + (size_t)b0 * N;
-        float* po = out + (size_t)b0 * N;
-        int* pf = flags + (size_t)b0 * flags_row;
+        float* po = s.out + (size_t)b0 * N;
+        int* pf = s.flags + (size_t)b0 * flags_row;
         hipLaunchKernelGGL(lim_init_kernel, dim3(1), dim3(LIM_UTTS), 0, h->stream, st + b0, nb);
         hipLaunchKernelGGL(lim_gain_kernel, grid, dim3(LIM_LANES), lds, h->stream, pw, (size_t)N, lens, coef, ceiling, cf, lookahead,
                            oversample == 4 ? 1 : 0, po, pf, flags_row, st + b0);

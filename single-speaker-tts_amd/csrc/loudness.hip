@@ -277,13 +277,12 @@ static LoudPlan loud_plan(int sr) {
     return p;
 }
 
-// The workspaces of a measurement of B rows of N samples, sized ahead of a call that must not allocate once it has begun to
-// enqueue (loudness_impl asks for the same and finds them in place).
-int loudness_workspace(tts_handle_t h, int B, int N, int sr) {
+// The workspaces of a measurement of B rows of N samples.
+int loudness_scratch(tts_handle_t h, int B, int N, int sr, LoudScratch* s) {
     WS(h, "loud.ws", double, (size_t)B * loud_ws_doubles(N, sr), ws);
     WS(h, "loud.z", double, (size_t)2 * B, zg);
     WS(h, "loud.peak", unsigned, (size_t)B, pk);
-    (void)ws; (void)zg; (void)pk;
+    *s = LoudScratch{ws, zg, pk};
     return TTS_OK;
 }
 
@@ -291,15 +290,15 @@ int loudness_workspace(tts_handle_t h, int B, int N, int sr) {
 int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, int sr, bool normalize, double target_lufs, double max_peak,
                   double* mean_square, int32_t* n_blocks, double* gain) {
     const size_t ws_row = loud_ws_doubles(N, sr);
-    WS(h, "loud.ws", double, (size_t)B * ws_row, ws);
-    WS(h, "loud.z", double, (size_t)2 * B, zg);
-    WS(h, "loud.peak", unsigned, (size_t)B, pk);
+    LoudScratch s;
+    const int rc = loudness_scratch(h, B, N, sr, &s);
+    if (rc) return rc;
     const LoudPlan plan = loud_plan(sr);
     const size_t K = (size_t)loud_steps_read(N, sr);
     const size_t sums_at = K * LOUD_SEGS * 4, u_at = sums_at + K * LOUD_SEGS, z_at = u_at + K;
     const double z_target = normalize ? std::pow(10.0, (target_lufs + 0.691) / 10.0) : 0.0;
     ProfScope ps(h, ST_LOUDNESS, (int64_t)length_chunks(B, LOUD_UTTS) * (normalize ? 7 : 4) + (normalize ? 1 : 0));
-    if (normalize) HIPCHK(h, hipMemsetAsync(pk, 0, (size_t)B * sizeof(unsigned), h->stream));
+    if (normalize) HIPCHK(h, hipMemsetAsync(s.peak, 0, (size_t)B * sizeof(unsigned), h->stream));
     for (int b0 = 0; b0 < B; b0 += LOUD_UTTS) {
         const int nb = std::min(LOUD_UTTS, B - b0);
         LoudLens lens;
@@ -307,8 +306,8 @@ int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_sam
         int longest = 0;
         for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
         float* pw = wav + (size_t)b0 * N;
-        double* pws = ws + (size_t)b0 * ws_row;
-        double* pz = mean_square && !normalize ? mean_square + b0 : zg + b0;
+        double* pws = s.ws + (size_t)b0 * ws_row;
+        double* pz = mean_square && !normalize ? mean_square + b0 : s.z + b0;
         const long long n_seg = (long long)loud_steps_read(longest, sr) * LOUD_SEGS;
         if (n_seg) {
             const dim3 grid((unsigned)((n_seg + LOUD_LANES - 1) / LOUD_LANES), nb);
@@ -321,10 +320,10 @@ int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_sam
         if (normalize) {
             const long long per_block = (long long)LOUD_LANES * LOUD_SCALE_PER_LANE;
             const dim3 grid((unsigned)((longest + per_block - 1) / per_block), nb);
-            hipLaunchKernelGGL(loud_peak_kernel, grid, dim3(LOUD_LANES), 0, h->stream, pw, (size_t)N, lens, pk + b0);
-            hipLaunchKernelGGL(loud_gain_kernel, dim3(1), dim3(LOUD_UTTS), 0, h->stream, pz, pk + b0, nb, z_target, max_peak, zg + B + b0,
+            hipLaunchKernelGGL(loud_peak_kernel, grid, dim3(LOUD_LANES), 0, h->stream, pw, (size_t)N, lens, s.peak + b0);
+            hipLaunchKernelGGL(loud_gain_kernel, dim3(1), dim3(LOUD_UTTS), 0, h->stream, pz, s.peak + b0, nb, z_target, max_peak, s.z + B + b0,
                                mean_square ? mean_square + b0 : nullptr, gain ? gain + b0 : nullptr);
-            hipLaunchKernelGGL(loud_scale_kernel, grid, dim3(LOUD_LANES), 0, h->stream, pw, (size_t)N, lens, zg + B + b0);
+            hipLaunchKernelGGL(loud_scale_kernel, grid, dim3(LOUD_LANES), 0, h->stream, pw, (size_t)N, lens, s.z + B + b0);
         }
         HIPCHK(h, hipGetLastError());
     }

@@ -282,22 +282,27 @@ __global__ __launch_bounds__(256) void pe_transpose_kernel(const float* __restri
 
 namespace tts_api {
 
-// The workspaces of an estimate of B utterances of T frames, sized before anything is enqueued (a growing workspace
-// synchronises every stream).  from_public: the input is (B, F, T) and is transposed first.
-int phase_estimate_workspaces(tts_handle_t h, int B, int T, int n_fft, bool from_public) {
+// The workspaces of an estimate of B utterances of T frames.  from_public: the input is (B, F, T) and is transposed first;
+// gl_start: the estimate starts a Griffin-Lim call, which reads it from a workspace like a caller's init_phase (gl_init_phase).
+int phase_estimate_scratch(tts_handle_t h, int B, int T, int n_fft, bool from_public, bool gl_start, PhaseScratch* s) {
     const int F = 1 + n_fft / 2, FP = gl_fp(n_fft);
     const int n_chunks = pe_chunks(T);
+    *s = PhaseScratch{};
     WS(h, "pe.u_rows", float, (size_t)B * T * FP, u_rows);
-    (void)u_rows;
+    s->u_rows = u_rows;
     if (from_public) {
         WS(h, "pe.mag_rows", float, (size_t)B * T * FP, mag_rows);
-        (void)mag_rows;
+        s->mag_rows = mag_rows;
     }
     if (n_chunks > 1) {
         WS(h, "pe.map_s", unsigned short, (size_t)B * n_chunks * F, ms);
         WS(h, "pe.map_o", unsigned, (size_t)B * n_chunks * F, mo);
         WS(h, "pe.start", unsigned, (size_t)B * n_chunks * F, st);
-        (void)ms; (void)mo; (void)st;
+        s->map_s = ms; s->map_o = mo; s->start = st;
+    }
+    if (gl_start) {
+        WS(h, "gl.init_est", float, (size_t)B * F * T, est);
+        s->init_est = est;
     }
     return TTS_OK;
 }
@@ -308,22 +313,9 @@ int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_
                         int hop, float* out) {
     const int F = 1 + n_fft / 2, FP = gl_fp(n_fft);
     const int n_chunks = pe_chunks(T);
-    int rc = phase_estimate_workspaces(h, B, T, n_fft, !time_major);
+    PhaseScratch s;
+    const int rc = phase_estimate_scratch(h, B, T, n_fft, !time_major, false, &s);
     if (rc) return rc;
-    WS(h, "pe.u_rows", float, (size_t)B * T * FP, u_rows);
-    float* mag_rows = nullptr;
-    if (!time_major) {
-        WS(h, "pe.mag_rows", float, (size_t)B * T * FP, mr);
-        mag_rows = mr;
-    }
-    unsigned short* map_s = nullptr;
-    unsigned *map_o = nullptr, *start = nullptr;
-    if (n_chunks > 1) {
-        WS(h, "pe.map_s", unsigned short, (size_t)B * n_chunks * F, ms);
-        WS(h, "pe.map_o", unsigned, (size_t)B * n_chunks * F, mo);
-        WS(h, "pe.start", unsigned, (size_t)B * n_chunks * F, st);
-        map_s = ms; map_o = mo; start = st;
-    }
     ProfScope ps(h, ST_PHASE_INIT, (int64_t)length_chunks(B, PE_UTTS) * ((time_major ? 2 : 3) + (n_chunks > 1 ? 2 : 0)));
     const dim3 tile_grid_in((T + 31) / 32, (F + 31) / 32), tile_grid_out((F + 31) / 32, (T + 31) / 32);
     for (int b0 = 0; b0 < B; b0 += PE_UTTS) {
@@ -334,24 +326,24 @@ int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_
         const float* rows = mag + (size_t)b0 * T * row_stride;
         int stride = row_stride;
         if (!time_major) {
-            float* dst = mag_rows + (size_t)b0 * T * FP;
+            float* dst = s.mag_rows + (size_t)b0 * T * FP;
             hipLaunchKernelGGL(pe_transpose_kernel<false>, dim3(tile_grid_in.x, tile_grid_in.y, nb), dim3(256), 0, h->stream,
                                mag + (size_t)b0 * F * T, dst, lens, F, T, T, FP);
             rows = dst;
             stride = FP;
         }
-        float* u = u_rows + (size_t)b0 * T * FP;
+        float* u = s.u_rows + (size_t)b0 * T * FP;
         const size_t at = (size_t)b0 * n_chunks * F;
         const int live_chunks = pe_chunks(longest);
         if (live_chunks > 1) {
             hipLaunchKernelGGL(pe_chunk_kernel<true>, dim3(live_chunks - 1, nb), dim3(PE_THREADS), 0, h->stream, rows, lens, T, F, stride, n_chunks,
-                               (double)hop, (double)n_fft, map_s + at, map_o + at, (const unsigned*)nullptr, (float*)nullptr, 0);
-            hipLaunchKernelGGL(pe_chain_kernel, dim3(nb), dim3(PE_THREADS), 0, h->stream, lens, F, n_chunks, map_s + at, map_o + at, start + at);
+                               (double)hop, (double)n_fft, s.map_s + at, s.map_o + at, (const unsigned*)nullptr, (float*)nullptr, 0);
+            hipLaunchKernelGGL(pe_chain_kernel, dim3(nb), dim3(PE_THREADS), 0, h->stream, lens, F, n_chunks, s.map_s + at, s.map_o + at, s.start + at);
         }
         // (u's rows are FP floats apart whatever the input's stride)
         hipLaunchKernelGGL(pe_chunk_kernel<false>, dim3(live_chunks, nb), dim3(PE_THREADS), 0, h->stream, rows, lens, T, F, stride, n_chunks,
                            (double)hop, (double)n_fft, (unsigned short*)nullptr, (unsigned*)nullptr,
-                           live_chunks > 1 ? (const unsigned*)(start + at) : (const unsigned*)nullptr, u, FP);
+                           live_chunks > 1 ? (const unsigned*)(s.start + at) : (const unsigned*)nullptr, u, FP);
         hipLaunchKernelGGL(pe_transpose_kernel<true>, dim3(tile_grid_out.x, tile_grid_out.y, nb), dim3(256), 0, h->stream, u,
                            out + (size_t)b0 * F * T, lens, T, F, FP, T);
         HIPCHK(h, hipGetLastError());

@@ -124,6 +124,17 @@ int speech_threshold(float threshold_db, float ref_db, float max_db, float power
     return TTS_OK;
 }
 
+// The detection's row flags for B utterances of T frames; with_frames: and the lengths of a synthesis call on the device.
+int eos_scratch(tts_handle_t h, int B, int T, bool with_frames, EosScratch* s) {
+    WS(h, "eos.active", unsigned char, (size_t)B * T, active);
+    *s = EosScratch{active, nullptr};
+    if (with_frames) {
+        WS(h, "eos.frames", int32_t, (size_t)B, frames);
+        s->frames = frames;
+    }
+    return TTS_OK;
+}
+
 int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, int row_stride, float threshold, int keep_frames,
                        int min_frames, int32_t* n_frames, int32_t* last_active) {
     if (!spec || !n_frames) return fail(h, TTS_ERR_INVALID, "speech_frames: spec and n_frames must not be NULL");
@@ -133,13 +144,15 @@ int speech_frames_impl(tts_handle_t h, const float* spec, int B, int T, int F, i
     if (min_frames < 1 || min_frames > T) return fail(h, TTS_ERR_INVALID, "speech_frames: min_frames must lie in [1, T]");
     if (threshold != threshold) return fail(h, TTS_ERR_INVALID, "speech_frames: the threshold is NaN");
     const long long rows = (long long)B * T;
-    WS(h, "eos.active", unsigned char, (size_t)rows, active);
+    EosScratch s;
+    const int rc = eos_scratch(h, B, T, false, &s);
+    if (rc) return rc;
     ProfScope ps(h, ST_SPEECH_END, 2);
     const long long want = (rows + SE_ROWS - 1) / SE_ROWS;
     const unsigned grid = (unsigned)std::min<long long>(want, 1 << 18);   // (the rows beyond take another round)
-    hipLaunchKernelGGL(speech_rows_kernel, dim3(grid), dim3(SE_THREADS), 0, h->stream, spec, rows, F, row_stride, threshold, active);
+    hipLaunchKernelGGL(speech_rows_kernel, dim3(grid), dim3(SE_THREADS), 0, h->stream, spec, rows, F, row_stride, threshold, s.active);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(speech_last_kernel, dim3((unsigned)B), dim3(SE_THREADS), 0, h->stream, active, T, keep_frames, min_frames,
+    hipLaunchKernelGGL(speech_last_kernel, dim3((unsigned)B), dim3(SE_THREADS), 0, h->stream, s.active, T, keep_frames, min_frames,
                        n_frames, last_active);
     HIPCHK(h, hipGetLastError());
     return TTS_OK;

@@ -366,8 +366,8 @@ int check_status(tts_handle_t h) {
     if (h->pd_used) {
         h->pd_used = false;
         int status = 0;
-        HIPCHK(h, hipMemcpy(&status, h->pd_sync + 64 * h->pd_clusters + 1, sizeof(int), hipMemcpyDeviceToHost));
-        if (status) HIPCHK(h, hipMemset(h->pd_sync + 64 * h->pd_clusters + 1, 0, sizeof(int)));
+        HIPCHK(h, hipMemcpy(&status, pd_status_word(h), sizeof(int), hipMemcpyDeviceToHost));
+        if (status) HIPCHK(h, hipMemset(pd_status_word(h), 0, sizeof(int)));
         if (status) h->persistent_decoder = 0;   // every later call takes the launch-per-layer path by itself
         if (status) return pd_timed_out(h);
     }

@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 #include "decoder.h"
+#include "decoder_cluster.h"
 #include "griffin_lim.h"
 #include "synth_plan.h"
 #include "tts_common.h"
@@ -361,7 +362,7 @@ struct tts_handle_s {
     unsigned* gl_ring_last = nullptr;  // slot of the most recent launch (dirty)
     hipStream_t gl_ring_stream = nullptr;
     bool pd_used = false;            // a persistent launch has been enqueued since the last status check
-    unsigned* pd_sync = nullptr;     // counters + status word of the last persistent launch
+    unsigned* pd_sync = nullptr;     // sync words of the last persistent launch, laid out for pd_clusters (decoder_cluster.h)
     int pd_clusters = 0;
     int pd_rows = 0;                 // tests ("pd_rows" behind "debug_hooks"): utterances per cluster of the weight-stationary decoder, 16 / 32
     int pd_rows_used = 0;            // ... of the last launch
@@ -563,6 +564,7 @@ int fail(tts_handle_t h, int code, const std::string& msg);
 void build_manifest(tts_handle_t h);
 int pd_timed_out(tts_handle_t h);   // the persistent decoder's timeout, reported in ONE wording (check_status, tts_wait_host)
 int check_status(tts_handle_t h);
+inline int* pd_status_word(tts_handle_t h) { return dc_sync(h->pd_sync, h->pd_clusters).status; }   // sticky, on the device
 int sync_all(tts_handle_t h);
 int graph_quiesce(tts_handle_t h);
 int graph_drop(tts_handle_t h);

@@ -618,8 +618,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     io.status_pinned[2 * par] = io.status_pinned[2 * par + 1] = 0;
     io.failed[par] = false;   // (the set is reused: the ticket that failed can no longer be waited on)
     if (h->pd_used && h->pd_sync)
-        HIPCHK(h, hipMemcpyAsync(&io.status_pinned[2 * par + 1], h->pd_sync + 64 * h->pd_clusters + 1, sizeof(int),
-                                 hipMemcpyDeviceToHost, io.out));
+        HIPCHK(h, hipMemcpyAsync(&io.status_pinned[2 * par + 1], pd_status_word(h), sizeof(int), hipMemcpyDeviceToHost, io.out));
     HIPCHK(h, io.d2h[par].record(io.out));
     io.n_floats[par] = n_wav;
     *ticket = t;
@@ -645,7 +644,7 @@ int tts_wait_host(tts_handle_t h, int ticket, const float** wav_host, size_t* n_
         if (!io.failed[par]) {
             io.failed[par] = true;
             io.status_pinned[2 * par + 1] = 0;
-            if (h->pd_sync) HIPCHK(h, hipMemsetAsync(h->pd_sync + 64 * h->pd_clusters + 1, 0, sizeof(int), io.out));
+            if (h->pd_sync) HIPCHK(h, hipMemsetAsync(pd_status_word(h), 0, sizeof(int), io.out));
             h->persistent_decoder = 0;
             h->pd_used = false;
         }

@@ -807,6 +807,19 @@ int teacher_choice(tts_handle_t h, int B, int Ts) {
     return pd_choice(h, B, Ts, h->n_cus_dev, false) == 2 && h->dec.ws_teacher ? 2 : 0;
 }
 
+// One launch of a persistent decoder: its sync words (decoder_cluster.h) from workspace `name`, laid out for `clusters` --
+// a new buffer or a new layout starts with a clean sticky status word --, then what `enqueue(sync)` queues (0 or an error
+// code), then the handle remembers where check_status finds the status word.
+template <class Enqueue>
+static int persistent_launch(tts_handle_t h, const char* name, int clusters, Enqueue enqueue) {
+    WS(h, name, unsigned, dc_sync_words(clusters), sync);
+    if (sync != h->pd_sync || clusters != h->pd_clusters)
+        HIPCHK(h, hipMemsetAsync(dc_sync(sync, clusters).status, 0, sizeof(int), h->stream));
+    if (int rc = enqueue(sync)) return rc;
+    h->pd_sync = sync; h->pd_clusters = clusters; h->pd_used = true;
+    return TTS_OK;
+}
+
 int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps, float* mel, float* alignments,
                  const float* target, const StageArgs& args, std::optional<GemmGroup>* deferred) {
     int rc = TTS_OK;
@@ -890,36 +903,31 @@ int decoder_impl(tts_handle_t h, const float* memory, int B, int Ts, int n_steps
             rows = h->pd_rows;   // (tests: "pd_rows")
         const int clusters = decoder_ws_clusters(B, 16);   // layout of the sync words: that of the form with more clusters
         WS(h, "dec.ws_scratch", float, std::max(decoder_ws_scratch_floats(B, 16), decoder_ws_scratch_floats(B, 32)), ws_scratch);
-        WS(h, "dec.ws_sync", unsigned, (size_t)64 * clusters + 2, ws_sync);
-        if (ws_sync != h->pd_sync || clusters != h->pd_clusters)   // new buffer / new layout: the sticky status word starts clean
-            HIPCHK(h, hipMemsetAsync(ws_sync + 64 * clusters + 1, 0, sizeof(unsigned), h->stream));
-        float* xg = nullptr;
-        if (target) {   // teacher forcing: the pre-net inputs x_t W1x + b1 of all steps, one GEMM in front of the loop
-            WS(h, "dec.teacher_xg", float, (size_t)B * n_steps * c.dec_prenet_units[0], xg_ws);
-            HIPCHK(h, decoder_teacher_inputs(h->stream, h->dec, h->zeros, target, B, n_steps, xg_ws));
-            xg = xg_ws;
-        }
-        HIPCHK(h, decoder_ws_enqueue(h->stream, h->dec, ws_scratch, yhist, memory, keys, B, Ts, n_steps, alignments, ws_sync,
-                                     args.hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0, rows, clusters, sc.p_hist,
-                                     sc.err_flag, xg));
+        rc = persistent_launch(h, "dec.ws_sync", clusters, [&](unsigned* ws_sync) -> int {
+            float* xg = nullptr;
+            if (target) {   // teacher forcing: the pre-net inputs x_t W1x + b1 of all steps, one GEMM in front of the loop
+                WS(h, "dec.teacher_xg", float, (size_t)B * n_steps * c.dec_prenet_units[0], xg_ws);
+                HIPCHK(h, decoder_teacher_inputs(h->stream, h->dec, h->zeros, target, B, n_steps, xg_ws));
+                xg = xg_ws;
+            }
+            HIPCHK(h, decoder_ws_enqueue(h->stream, h->dec, ws_scratch, yhist, memory, keys, B, Ts, n_steps, alignments, ws_sync,
+                                         args.hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0, rows, clusters, sc.p_hist,
+                                         sc.err_flag, xg));
+            return TTS_OK;
+        });
+        if (rc) return rc;
         h->pd_rows_used = rows;
-        h->pd_sync = ws_sync;
-        h->pd_clusters = clusters;
-        h->pd_used = true;
     } else if (use_pd) {
         if (!h->pd_configured) {
             HIPCHK(h, decoder_persistent_configure());
             h->pd_configured = true;
         }
-        const int clusters = (B + 15) / 16;
-        WS(h, "dec.pd_sync", unsigned, (size_t)64 * clusters + 2, pd_sync);
-        if (pd_sync != h->pd_sync || clusters != h->pd_clusters)   // new buffer / new layout: the sticky status word starts clean
-            HIPCHK(h, hipMemsetAsync(pd_sync + 64 * clusters + 1, 0, sizeof(unsigned), h->stream));
-        HIPCHK(h, decoder_persistent_enqueue(h->stream, h->dec, sc, memory, keys, B, Ts, n_steps, alignments, pd_sync,
-                                             args.hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0));
-        h->pd_sync = pd_sync;
-        h->pd_clusters = clusters;
-        h->pd_used = true;
+        rc = persistent_launch(h, "dec.pd_sync", (B + 15) / 16, [&](unsigned* pd_sync) -> int {
+            HIPCHK(h, decoder_persistent_enqueue(h->stream, h->dec, sc, memory, keys, B, Ts, n_steps, alignments, pd_sync,
+                                                 args.hold_flag, c.force_cudnn, h->debug_hooks ? h->pd_debug_delay : 0));
+            return TTS_OK;
+        });
+        if (rc) return rc;
     } else if (!h->use_graph || target) {   // (a teacher-forced call is never captured)
         HIPCHK(h, decoder_enqueue(h->stream, h->dec, sc, memory, keys, B, Ts, n_steps, alignments, c.force_cudnn, target));
     } else {

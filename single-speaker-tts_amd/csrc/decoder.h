@@ -98,8 +98,8 @@ struct PdParams {
     float *h_att2[2], *h_dec2[2][2];              // recurrent states, double-buffered by step parity (zeroed per call)
     int dbg_delay;                                // tests only: workgroup 3 of every cluster sleeps this long before it stages
     float* align;                                 // [n_steps][B][Ts] or null
-    unsigned* counters;                           // [clusters][64]: one arrival counter per cluster, zeroed per call
-    unsigned* resident;                           // workgroups that have started
+    unsigned* counters;                           // the launch's sync words (decoder_cluster.h, DcSync): one arrival counter per cluster,
+    unsigned* resident;                           // workgroups that have started (both zeroed per call),
     int* status;                                  // set to 1 when a wait timed out (results are then invalid)
     int* hold_flag;                               // optional: raised once every workgroup is resident (reserve.hip sleepers)
     int B, Ts, n_steps, n_mels;
@@ -112,7 +112,7 @@ struct PdParams {
 bool decoder_persistent_supports(const DecoderWeights& w, int cudnn, int B, int Ts);
 int decoder_persistent_workgroups(int B);         // compute units the launch needs all to itself
 hipError_t decoder_persistent_configure();        // per device
-// `sync`: 64 * ceil(B / 16) + 2 unsigned words; `dbg_delay`: tests only (tts_set_option "pd_debug_delay", per handle),
+// `sync`: dc_sync_words(ceil(B / 16)) unsigned words (decoder_cluster.h); `dbg_delay`: tests only (tts_set_option "pd_debug_delay", per handle),
 // see PdParams::dbg_delay
 hipError_t decoder_persistent_enqueue(hipStream_t s, const DecoderWeights& w, const DecoderScratch& sc, const float* memory,
                                       const float* keys, int B, int Ts, int n_steps, float* align, unsigned* sync,
@@ -129,7 +129,7 @@ struct WsParams {
     float* rest;                                  // [clusters][p1 | r*h | ctx | y0 | p2]
     float* yhist;                                 // [B][n_steps][256]
     float* align;                                 // [n_steps][B][Ts] or null
-    unsigned* counters; unsigned* resident; int* status; int* hold_flag;   // as PdParams
+    unsigned* counters; unsigned* resident; int* status; int* hold_flag;   // sync words: decoder_cluster.h, DcSync; hold_flag as PdParams
     int B, Ts, n_steps, dbg_delay;
     int cudnn;                                    // CudnnCompatibleGRUCell arithmetic (the register image is packed for it)
     int local_d, local_gaussian, local_predictive;   // LocalLuongAttention (0 = global attention), as PdParams
@@ -157,7 +157,7 @@ int decoder_ws_workgroups(int B, int rows = 32);  // compute units the launch ne
 int decoder_ws_clusters(int B, int rows = 32);
 size_t decoder_ws_scratch_floats(int B, int rows = 32);
 hipError_t decoder_ws_configure();                // per device
-// `sync`: 64 * max(clusters, sync_clusters) + 2 unsigned words (counters, resident count, sticky status word)
+// `sync`: dc_sync_words(max(clusters, sync_clusters)) unsigned words (decoder_cluster.h)
 hipError_t decoder_ws_enqueue(hipStream_t s, const DecoderWeights& w, float* scratch, float* yhist, const float* memory,
                               const float* keys, int B, int Ts, int n_steps, float* align, unsigned* sync, int* hold_flag,
                               int cudnn, int dbg_delay, int rows = 32, int sync_clusters = 0, float* p_hist = nullptr, int* err_flag = nullptr,

@@ -22,6 +22,7 @@
 //  * The whole loop is captured into one hipGraph by the caller (api_stages.hip).
 #include "tts_common.h"
 #include "decoder.h"
+#include "decoder_cluster.h"
 #include <cstring>
 
 namespace tts {
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(const float* __restr
     // that leaves it has already raised the error flag, see dec_predict_centre_kernel)
     if (p_row) {
         const int c = (int)floorf(p_row[b]);
-        w_lo = min(max(c - local_d, 0), Ts - w_n);
+        w_lo = local_clamped_lo(c, local_d, Ts, w_n);
     }
     const int j_lo = w_lo + part * Tp;
     const int nj = min(Tp, w_lo + w_n - j_lo);   // may be <= 0 for an empty slice
@@ -316,16 +317,8 @@ __global__ __launch_bounds__(256) void dec_predict_centre_kernel(const float* __
         const float p = predicted_centre((red[0] + red[1]) + (red[2] + red[3]), Ts);
         p_out[b] = p;
         const int c = (int)floorf(p);
-        if (c - local_d < 0 || c + local_d + 1 > Ts) *err_flag = 1;
+        if (!local_inside_memory(c, local_d, Ts)) *err_flag = 1;
     }
-}
-
-// Window of LocalLuongAttention in MONOTONIC mode at decoder step t (reference attention.py:263-286):
-// p = min(max(t, D), Ts - (D + 1)), window [p - D, p + D + 1).  Needs Ts >= 2D + 1 (checked by the caller).
-__host__ __device__ static inline int local_center(int t, int Ts, int D) {
-    int p = t > D ? t : D;
-    const int hi = Ts - (D + 1);
-    return p < hi ? p : hi;
 }
 
 // alignment_history[t][b][j] = e * exp(m_part - m) / sum, for all steps at once (off the critical path).
@@ -342,14 +335,14 @@ __global__ void dec_align_finalize_kernel(const float* __restrict__ e, const flo
     if (local_d > 0) {
         if (p_hist) {
             pc = p_hist[tb];
-            w_lo = min(max((int)floorf(pc) - local_d, 0), Ts - (2 * local_d + 1));
+            w_lo = local_clamped_lo((int)floorf(pc), local_d, Ts, 2 * local_d + 1);
         } else {
             const int c = local_center((int)(tb / B), Ts, local_d);
             pc = (float)c;
             w_lo = c - local_d;
         }
     }
-    const float gk = 0.5f * (0.5f * local_d) * (0.5f * local_d);
+    const float gk = local_gauss_k(local_d);
     const float* st = stats + tb * TTS_ATT_PARTS * 2;
     float m = -INFINITY;
 #pragma unroll
@@ -371,10 +364,7 @@ __global__ void dec_align_finalize_kernel(const float* __restrict__ e, const flo
 #pragma unroll
             for (int i = 1; i < TTS_ATT_PARTS; ++i) wp = part == i ? w[i] : wp;
             a = e[tb * Ts + j] * wp * inv;
-            if (local_d > 0 && gaussian) {
-                const float dist = (float)j - pc;
-                a *= __expf(-(dist * dist) * gk);
-            }
+            if (local_d > 0 && gaussian) a *= local_gauss((float)j, pc, gk);
         }
         align[tb * Ts + j] = a;
     }

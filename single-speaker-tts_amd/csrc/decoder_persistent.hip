@@ -9,13 +9,9 @@
 //     and the cell state of its units never leave its LDS), K split over the waves, v_mfma_f32_16x16x4_f32;
 //   * the weights of the NEXT phase are fetched from L2 into registers BEFORE the workgroup waits for its peers
 //     (they do not depend on data);
-//   * activations travel between the workgroups of a cluster through small global buffers with the write-through
-//     hand-off of MI355X_MICROARCH.md ("valid forms"): every byte stored sc1; every storing wave waits vmcnt(0) and
-//     adds to the cluster's counter (agent scope) for itself -- a GEMM phase's stores come from its first one or two
-//     waves, and no workgroup barrier holds the other fourteen back from the next phase's weight requests (round 4:
-//     14.9 -> 13.6 ms alone; the attention phase, where every wave stores, keeps drain -> barrier -> one add);
-//     consumers poll that counter with an sc1 load in one lane, then a workgroup barrier, then sc1 loads of the
-//     bytes.  No cache-wide release or acquire anywhere, no grid-wide barrier: clusters never talk to each other;
+//   * activations travel between the workgroups of a cluster through small global buffers with the hand-off protocol of
+//     decoder_cluster.h: a GEMM phase's stores come from its first one or two waves, which signal for themselves; the
+//     attention phase, where every wave stores, keeps drain -> barrier -> one add;
 //   (Round 4 measured the alternative hand-off of cdna_hip_programming.md Guideline 16 R2 -- every value an 8-byte
 //   {value, tag} granule, the consumers sweeping the tile until the tags match, no counter and no drained stores --
 //   on one box against this form: 15.48 against 14.86 ms alone, 16.1 against 15.5 ms beside Griffin-Lim.  A phase is bound
@@ -25,11 +21,11 @@
 //   workgroups and 256 registers the dependent MFMA chain of a wave doubles: 18.3 ms.  git history has both.)
 //   * attention: workgroup j scores, normalises and contracts two of the cluster's 16 rows itself, so softmax
 //     needs no cross-workgroup merge and the alignments are written normalised.
-// Every wait is bounded (PD_SPIN_LIMIT polls); on a timeout the status word is set, every workgroup of the grid
-// sees it at its next wait and the kernel drains.  All workgroups must be co-resident: the host only uses this
+// Every wait is bounded (decoder_cluster.h).  All workgroups must be co-resident: the host only uses this
 // path when 8 * ceil(B / 16) compute units are free for it (api_stages.hip).
 #include "tts_common.h"
 #include "decoder.h"
+#include "decoder_cluster.h"
 #include <cstdio>
 
 namespace tts {
@@ -41,26 +37,12 @@ namespace tts {
 #define PD_P2 128                 // pre-net 2 units
 #define PD_LDA 516                // LDS row stride (floats) of the staged A tile: K <= 512; +4 keeps b128 reads conflict-free
 #define PD_RED_LD 20              // row stride of the per-wave partial tiles (b128 aligned)
-#define PD_SPIN_LIMIT 2000000u      // polls of ~1 us each
 // attention: key passes (32 positions each) / value rows per wave in flight together.  Same-box decoder times alone /
 // beside Griffin-Lim: one pass and two rows at a time (round-2 start) 15.16 / 17.29 ms, 2 and 4: 14.87 / 17.24, 2 and 8:
 // 15.05 / 17.27, 3 and 8: 15.78 / 17.60 (the prefetched keys live across the wait for the cluster and spill).  The phase
 // is bound by the cluster's arrival skew, not by its dependent memory trips.
 #define PD_KB 2
 #define PD_VB 4
-
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned pd_u32x4;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pd_rsrc(const void* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)0xFFFFFFF0u, 0x00020000);
-}
-// 16-byte sc1 (write-through / L1-bypassing) accesses: aux bit 4
-__device__ __forceinline__ float4 pd_ld4(const __amdgpu_buffer_rsrc_t& rs, unsigned byte_off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 16));
-}
-__device__ __forceinline__ void pd_st4(const __amdgpu_buffer_rsrc_t& rs, unsigned byte_off, float4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pd_u32x4, v), rs, (int)byte_off, 0, 16);
-}
 
 // PD_GATES + PD_CAND: TF GRUCell (candidate on [x ; r*h], two hops per cell).  PD_CUDNN_RU + PD_CUDNN_HX:
 // CudnnCompatibleGRUCell (reference layers.py:560-577, model.py:226-227,257-259): c = tanh(x Wci + bci + r*(h Wch + bch));
@@ -93,48 +75,6 @@ struct PdPhase {
 #define PD_OFF_CTRL (PD_OFF_R + 16 * 32)
 #define PD_OFF_SC (PD_OFF_CTRL + 16)
 size_t pd_lds_bytes(int Ts) { return ((size_t)PD_OFF_SC + 2 * (size_t)((Ts + 3) & ~3)) * sizeof(float); }
-
-// Start of a phase: wait until `target` arrivals have been counted on the cluster's counter (lane 0 polls, everybody
-// meets at the barrier).  The arrival of THIS workgroup for the previous phase was signalled when that phase ended
-// (pd_publish): until round 4 it was signalled here, behind the next phase's weight requests and address arithmetic --
-// 1.0-1.4 us in which the peers could not yet see that this workgroup was done, on every phase's critical path.
-__device__ __forceinline__ void pd_wait(unsigned* cnt, unsigned target, int* status, int* ctrl) {
-    if (threadIdx.x == 0 && target > 0) {
-        if (ctrl[0] == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 1023u) == 0 &&
-                    (spins > PD_SPIN_LIMIT || __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                    __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ctrl[0] = 1;   // drain: no further waits in this workgroup
-                    break;
-                }
-            }
-        }
-    }
-    __syncthreads();
-}
-
-// End of a phase: every storing wave waits for its (write-through) stores, then the workgroup barrier -- after it
-// one lane signals for all of them: the arrival on the cluster's counter (agent scope), at once.
-// A workgroup counts PD_ARRIVALS on the counter per phase, however many of its waves store.
-#define PD_ARRIVALS 2u
-__device__ __forceinline__ void pd_publish(unsigned* cnt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt, PD_ARRIVALS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// The same for a phase whose stores all come from its first one or two waves (the GEMM phases' epilogue): every storing wave
-// signals for itself when ITS stores have drained (MI355X_MICROARCH.md, valid forms: "each storing wave for itself"), and
-// no workgroup barrier stands between the other fourteen waves and the next phase's weight requests: those are in
-// flight while the epilogue runs, not behind it.  (What the barrier also did -- keep the partial tiles and the staged tile
-// from being overwritten under the epilogue's reads -- the next phase's own barrier does: nobody writes either before
-// pd_wait, and a `cont` phase is entered through the barrier of the `more` phase in front of it.)
-__device__ __forceinline__ void pd_publish_wave(unsigned* cnt, unsigned arrivals) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, arrivals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // One GEMM-shaped phase of the cluster: out[16 rows][this workgroup's units] = epi([a0 | a1] . Wt^T + bias).
 __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, int b0, int B, unsigned* cnt, unsigned target,
@@ -186,7 +126,7 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
         }
     }
 
-    if (!ph.cont) pd_wait(cnt, target, status, ctrl);
+    if (!ph.cont) dc_wait(cnt, target, status, ctrl);
     if (ph.delay && !ph.cont && j == 3)   // a late stager: what a workgroup that clears its poll late looks like to its peers
         for (int i = 0; i < ph.delay; ++i) __builtin_amdgcn_s_sleep(127);
 
@@ -194,13 +134,13 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
     // two float4 per thread, BOTH requested before either is written to LDS (written as a loop of load-then-store the
     // second request waited for the first: two fabric round trips per phase instead of one)
     if (!ph.cont) {
-        const __amdgpu_buffer_rsrc_t r0 = pd_rsrc(ph.a0 ? ph.a0 : ph.a1), r1 = pd_rsrc(ph.a1);
+        const __amdgpu_buffer_rsrc_t r0 = dc_rsrc(ph.a0 ? ph.a0 : ph.a1), r1 = dc_rsrc(ph.a1);
         float4 sv[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             sv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ssel[u] == 0) sv[u] = pd_ld4(r0, soff[u]);
-            else if (ssel[u] == 1) sv[u] = pd_ld4(r1, soff[u]);
+            if (ssel[u] == 0) sv[u] = dc_ld4(r0, soff[u]);
+            else if (ssel[u] == 1) sv[u] = dc_ld4(r1, soff[u]);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
@@ -254,7 +194,7 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
         if (ph.epi == PD_ACT) {
             float4 o = v[0];
             o.x = apply_act(o.x, ph.act); o.y = apply_act(o.y, ph.act); o.z = apply_act(o.z, ph.act); o.w = apply_act(o.w, ph.act);
-            if (row_ok) pd_st4(pd_rsrc(ph.out), (unsigned)(b * ph.ldo + unit) * 4u, o);
+            if (row_ok) dc_st4(dc_rsrc(ph.out), (unsigned)(b * ph.ldo + unit) * 4u, o);
         } else if (ph.epi == PD_GATES || ph.epi == PD_CUDNN_RU) {
             float4 rr4, uu4;
             rr4.x = sigmoidf_(v[0].x); rr4.y = sigmoidf_(v[0].y); rr4.z = sigmoidf_(v[0].z); rr4.w = sigmoidf_(v[0].w);
@@ -263,7 +203,7 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
             if (ph.epi == PD_GATES) {                          // r*h is the candidate's K operand: hand it over
                 const float4 h4 = *reinterpret_cast<const float4*>(hl);
                 rr4.x *= h4.x; rr4.y *= h4.y; rr4.z *= h4.z; rr4.w *= h4.w;
-                if (row_ok) pd_st4(pd_rsrc(ph.out), (unsigned)(b * ph.ldo + unit) * 4u, rr4);
+                if (row_ok) dc_st4(dc_rsrc(ph.out), (unsigned)(b * ph.ldo + unit) * 4u, rr4);
             } else {
                 *reinterpret_cast<float4*>(rl) = rr4;
             }
@@ -282,16 +222,16 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
             hn.z = u4.z * h4.z + (1.0f - u4.z) * tanhf_(cin.z);
             hn.w = u4.w * h4.w + (1.0f - u4.w) * tanhf_(cin.w);
             *reinterpret_cast<float4*>(hl) = hn;
-            if (row_ok) pd_st4(pd_rsrc(ph.out), (unsigned)(b * ph.ldo + unit) * 4u, hn);
+            if (row_ok) dc_st4(dc_rsrc(ph.out), (unsigned)(b * ph.ldo + unit) * 4u, hn);
             if (ph.yout) {   // ResidualWrapper: y = x + h'; x is the first K segment of the staged tile
                 const float4 x4 = *reinterpret_cast<const float4*>(As + row * PD_LDA + unit);
                 hn.x += x4.x; hn.y += x4.y; hn.z += x4.z; hn.w += x4.w;
-                if (row_ok) pd_st4(pd_rsrc(ph.yout), (unsigned)(b * ph.ldy + unit) * 4u, hn);
+                if (row_ok) dc_st4(dc_rsrc(ph.yout), (unsigned)(b * ph.ldy + unit) * 4u, hn);
             }
         }
     }
     if (ph.more) __syncthreads();   // r / u are in LDS, the partial tiles may be overwritten
-    else if (tid < tpg * 64) pd_publish_wave(cnt, PD_ARRIVALS / (unsigned)tpg);   // (tpg = 1 or 2 storing waves)
+    else if (tid < tpg * 64) dc_publish_wave(cnt, DC_ARRIVALS / (unsigned)tpg);   // (tpg = 1 or 2 storing waves)
 }
 
 // Luong dot attention for rows 2j and 2j+1 of the cluster (TF-1.8 _luong_score / _compute_attention; dot form at
@@ -299,17 +239,11 @@ __device__ __forceinline__ void pd_phase(const PdPhase& ph, float* lds, int j, i
 // LocalLuongAttention (reference attention.py:32-342; decoder.hip has the launch-per-layer form): only the window
 // of 2D+1 positions around the step index (monotonic) or around the predicted centre p = Ts sigmoid(v_p . tanh(W_p h))
 // is scored; the reported alignments are zero outside it and, with `gaussian`, weighted as the reference writes it.
-struct PdLocal {
-    int d, gaussian, predictive, step;
-    const float* wp; const float* vp;   // [256][256] (q @ W_p), [256]
-    float* p_hist_t;                    // [B] predicted centres of this step
-    int* err_flag;
-};
 template <bool LOCAL>   // the global form stays inline (one instance in the step loop); the windowed one is a call
 __device__ __forceinline__ void pd_attention_body(const float* __restrict__ query, const float* __restrict__ keys,
                                              const float* __restrict__ values, float* ctx, float* align_t, int Ts, float* lds,
                                              int j, int b0, int B, unsigned* cnt, unsigned target, int* status,
-                                             const PdLocal lc) {
+                                             const DcLocal lc) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = wave >> 3, hw = wave & 7, t512 = tid & 511;
     float* qs = lds + PD_OFF_AS + half * PD_D;                        // [2][256]
@@ -339,9 +273,9 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
     };
     if (!LOCAL) load_keys(keys + (size_t)rr * Ts * PD_D, 0, Ts);
 
-    pd_wait(cnt, target, status, ctrl);
+    dc_wait(cnt, target, status, ctrl);
 
-    if (t512 < 64) *reinterpret_cast<float4*>(qs + 4 * t512) = pd_ld4(pd_rsrc(query), (unsigned)(rr * PD_D + 4 * t512) * 4u);
+    if (t512 < 64) *reinterpret_cast<float4*>(qs + 4 * t512) = dc_ld4(dc_rsrc(query), (unsigned)(rr * PD_D + 4 * t512) * 4u);
     __syncthreads();
 
     // scored positions [w_lo, w_lo + w_n): the whole memory, or the local window
@@ -350,16 +284,9 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
     if (LOCAL && lc.d > 0) {
         w_n = 2 * lc.d + 1;
         if (lc.predictive) {
-            // (q W_p)[n] by thread n of the row's first 256, then v_p . tanh(.) over them, in double (tts_common.h,
-            // predicted_centre): waves 0..3 leave their sums as (hi, lo) pairs in redm[hw], redm[4 + hw]
+            // waves 0..3 (thread n of the row's first 256 forms (q W_p)[n]) leave their sums as (hi, lo) pairs in redm[hw], redm[4 + hw]
             if (t512 < 256) {
-                double a0 = 0.0, a1 = 0.0;
-                const float* wpn = lc.wp + t512;
-                for (int k = 0; k < PD_D; k += 2) {
-                    a0 = fma((double)qs[k], (double)wpn[(size_t)k * PD_D], a0);
-                    a1 = fma((double)qs[k + 1], (double)wpn[(size_t)(k + 1) * PD_D], a1);
-                }
-                const double v = wave_sum_f64((double)tanhf((float)(a0 + a1)) * (double)lc.vp[t512]);
+                const double v = local_predict_wave_sum(qs, lc.wp, lc.vp, t512);
                 if (lane == 0) split_f64(v, &redm[hw], &redm[4 + hw]);
             }
             __syncthreads();
@@ -368,18 +295,15 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
             for (int i = 0; i < 4; ++i) z += (double)redm[i] + (double)redm[4 + i];
             const float p = predicted_centre(z, Ts);
             const int c = (int)floorf(p);
-            // a window that leaves the memory: the reference's padding arithmetic fails there (decoder.hip)
             if (t512 == 0 && row_ok) {
                 lc.p_hist_t[row] = p;
-                if (c - lc.d < 0 || c + lc.d + 1 > Ts) *lc.err_flag = 1;
+                if (!local_inside_memory(c, lc.d, Ts)) *lc.err_flag = 1;
             }
-            w_lo = min(max(c - lc.d, 0), Ts - w_n);
+            w_lo = local_clamped_lo(c, lc.d, Ts, w_n);
             pc = p;
             __syncthreads();   // part / redm are reused below
         } else {
-            int c = lc.step > lc.d ? lc.step : lc.d;
-            const int hi = Ts - (lc.d + 1);
-            c = c < hi ? c : hi;
+            const int c = local_center(lc.step, Ts, lc.d);
             w_lo = c - lc.d;
             pc = (float)c;
         }
@@ -461,30 +385,26 @@ __device__ __forceinline__ void pd_attention_body(const float* __restrict__ quer
             a.x += t4.x; a.y += t4.y; a.z += t4.z; a.w += t4.w;
         }
         a.x *= inv; a.y *= inv; a.z *= inv; a.w *= inv;
-        if (row_ok) pd_st4(pd_rsrc(ctx), (unsigned)(row * PD_D + 4 * t512) * 4u, a);
+        if (row_ok) dc_st4(dc_rsrc(ctx), (unsigned)(row * PD_D + 4 * t512) * 4u, a);
     }
     if (align_t && row_ok) {
-        // the reference pads the window back to the memory length (attention.py:85-92) and, with `gaussian`, weights
-        // it by exp(-(j - p)^2 / 2 * (D/2)^2) as written at attention.py:73-80 (the context uses the plain softmax)
-        const float gk = 0.5f * (0.5f * lc.d) * (0.5f * lc.d);
+        // the reference pads the window back to the memory length (attention.py:85-92); `gaussian` weights the reported row
+        const float gk = local_gauss_k(lc.d);
         for (int k = t512; k < Ts; k += 512) {
             const int jw = k - w_lo;
             float a = 0.f;
             if (jw >= 0 && jw < w_n) {
                 a = sc[jw] * inv;
-                if (LOCAL && lc.d > 0 && lc.gaussian) {
-                    const float dist = (float)k - pc;
-                    a *= __expf(-(dist * dist) * gk);
-                }
+                if (LOCAL && lc.d > 0 && lc.gaussian) a *= local_gauss((float)k, pc, gk);
             }
             align_t[(size_t)row * Ts + k] = a;
         }
     }
-    pd_publish(cnt);
+    dc_publish(cnt);
 }
 __device__ __attribute__((noinline)) void pd_attention_local(const float* query, const float* keys, const float* values, float* ctx,
                                                              float* align_t, int Ts, float* lds, int j, int b0, int B, unsigned* cnt,
-                                                             unsigned target, int* status, const PdLocal lc) {
+                                                             unsigned target, int* status, const DcLocal lc) {
     pd_attention_body<true>(query, keys, values, ctx, align_t, Ts, lds, j, b0, B, cnt, target, status, lc);
 }
 
@@ -493,14 +413,12 @@ __global__ __launch_bounds__(PD_THREADS) void dec_persistent_kernel(PdParams p) 
     const int tid = threadIdx.x;
     const int cluster = blockIdx.x / PD_W, j = blockIdx.x - cluster * PD_W;
     const int b0 = cluster * 16;
-    unsigned* cnt = p.counters + 64 * cluster;
+    unsigned* cnt = p.counters + DC_CNT_LD * cluster;
     int* ctrl = reinterpret_cast<int*>(lds + PD_OFF_CTRL);
     for (int i = tid; i < 3 * 16 * 32 + 2 * 16 * 32; i += PD_THREADS) lds[PD_OFF_H + i] = 0.f;   // zero_state
     if (tid == 0) {
         ctrl[0] = 0;
-        // all workgroups resident: the CUs the call pipeline held for this stream are no longer needed
-        const unsigned n = __hip_atomic_fetch_add(p.resident, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (n + 1 == gridDim.x && p.hold_flag) __hip_atomic_store(p.hold_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (dc_all_resident(p.resident) && p.hold_flag) dc_release_held(p.hold_flag);
     }
     __syncthreads();
 
@@ -517,13 +435,13 @@ __global__ __launch_bounds__(PD_THREADS) void dec_persistent_kernel(PdParams p) 
 #pragma nounroll
         for (int k = 0; k < 10; ++k) {
             if (k == 4) {
-                PdLocal lc;
+                DcLocal lc;
                 lc.d = p.local_d; lc.gaussian = p.local_gaussian; lc.predictive = p.local_predictive; lc.step = t;
                 lc.wp = p.local_wp; lc.vp = p.local_vp; lc.p_hist_t = p.p_hist ? p.p_hist + (size_t)t * p.B : nullptr;
                 lc.err_flag = p.err_flag;
                 float* align_t = p.align ? p.align + (size_t)t * p.B * p.Ts : nullptr;
-                if (p.local_d > 0) pd_attention_local(h_att_new, p.keys, p.memory, p.ctx, align_t, p.Ts, lds, j, b0, p.B, cnt, PD_ARRIVALS * PD_W * g, p.status, lc);
-                else pd_attention_body<false>(h_att_new, p.keys, p.memory, p.ctx, align_t, p.Ts, lds, j, b0, p.B, cnt, PD_ARRIVALS * PD_W * g, p.status, lc);
+                if (p.local_d > 0) pd_attention_local(h_att_new, p.keys, p.memory, p.ctx, align_t, p.Ts, lds, j, b0, p.B, cnt, DC_ARRIVALS * PD_W * g, p.status, lc);
+                else pd_attention_body<false>(h_att_new, p.keys, p.memory, p.ctx, align_t, p.Ts, lds, j, b0, p.B, cnt, DC_ARRIVALS * PD_W * g, p.status, lc);
                 ++g;
                 continue;
             }
@@ -573,7 +491,7 @@ __global__ __launch_bounds__(PD_THREADS) void dec_persistent_kernel(PdParams p) 
                     if (second) { ph.yout = l == 0 ? p.y0 : p.yhist + (size_t)t * PD_D; ph.ldy = l == 0 ? PD_D : yld; }
                 } break;
             }
-            pd_phase(ph, lds, j, b0, p.B, cnt, PD_ARRIVALS * PD_W * g, p.status);
+            pd_phase(ph, lds, j, b0, p.B, cnt, DC_ARRIVALS * PD_W * g, p.status);
             if (!ph.more) ++g;
         }
     }
@@ -594,7 +512,7 @@ hipError_t decoder_persistent_configure() {
                                160 * 1024 - 64);
 }
 
-// Capturable: two memsets and one launch.  `sync` = 64 unsigned per cluster + 1 (resident count) + 1 (status word,
+// Capturable: two memsets and one launch.  `sync`: dc_sync_words(clusters) words (decoder_cluster.h; the status word is
 // zeroed by the caller when the buffer is created and after it has been read).
 hipError_t decoder_persistent_enqueue(hipStream_t s, const DecoderWeights& w, const DecoderScratch& sc, const float* memory,
                                       const float* keys, int B, int Ts, int n_steps, float* align, unsigned* sync,
@@ -602,10 +520,8 @@ hipError_t decoder_persistent_enqueue(hipStream_t s, const DecoderWeights& w, co
     const int clusters = (B + 15) / 16;
     hipError_t e;
     if ((e = hipMemsetAsync(sc.state, 0, sc.state_bytes, s)) != hipSuccess) return e;
-    // counters and resident count start at zero for every launch; the status word behind them is sticky (the host
-    // clears it when it has read it, api_handle.hip), so a timeout is not lost when several calls are queued before a sync
-    if ((e = hipMemsetAsync(sync, 0, ((size_t)64 * clusters + 1) * sizeof(unsigned), s)) != hipSuccess) return e;
     PdParams p;
+    if ((e = dc_launch_params(s, sync, clusters, w, sc.p_hist, sc.err_flag, p)) != hipSuccess) return e;
     p.w1 = w.prenet1_wt; p.b1 = w.prenet1_b; p.w1f = w.prenet1f_wt; p.b1f = w.prenet1f_b; p.w2 = w.prenet2_wt; p.b2 = w.prenet2_b;
     p.ag_w = w.att_gru.gates_wt; p.ag_b = w.att_gru.gates_b; p.ac_w = w.att_gru.cand_wt; p.ac_b = w.att_gru.cand_b;
     p.al_w = w.attn_layer_wt;
@@ -618,12 +534,8 @@ hipError_t decoder_persistent_enqueue(hipStream_t s, const DecoderWeights& w, co
     p.memory = memory; p.keys = keys;
     p.att = sc.att; p.p1 = sc.p1; p.p2 = sc.p2; p.rh = sc.rh; p.ctx = sc.ctx_parts; p.y0 = sc.y0;
     p.yhist = sc.yhist; p.align = align;
-    p.counters = sync; p.resident = sync + 64 * clusters; p.status = reinterpret_cast<int*>(sync + 64 * clusters + 1);
     p.hold_flag = hold_flag;
     p.B = B; p.Ts = Ts; p.n_steps = n_steps; p.n_mels = w.n_mels; p.cudnn = cudnn;
-    p.local_d = w.local_d; p.local_gaussian = w.local_gaussian; p.local_predictive = w.local_d > 0 && w.local_predictive;
-    p.local_wp = w.local_wp; p.local_vp = w.local_vp; p.p_hist = sc.p_hist; p.err_flag = sc.err_flag;
-    if (p.local_predictive && (e = hipMemsetAsync(sc.err_flag, 0, sizeof(int), s)) != hipSuccess) return e;
     hipLaunchKernelGGL(dec_persistent_kernel, dim3(PD_W * clusters), dim3(PD_THREADS), pd_lds_bytes(Ts), s, p);
     return hipGetLastError();
 }

@@ -19,15 +19,14 @@
 //     whole 128-byte lines (two rows x 16 units, eight lanes of one store instruction), a consumer stages the cluster's
 //     A tile with a linear copy (sc1 16-byte loads, no address arithmetic, conflict-free ds_write_b128), and a 16-deep k
 //     chunk of the tile is one contiguous 1 KB block for the MFMA fragment reads;
-//   * hand-off protocol as in decoder_persistent.hip (MI355X_MICROARCH.md, valid forms): every handed-off byte stored
-//     sc1, each storing wave waits vmcnt(0) and adds to the cluster's counter for itself, consumers poll the counter with
-//     an sc1 load in one lane, then a workgroup barrier, then sc1 loads.  No cache-wide release / acquire, no grid barrier;
+//   * the hand-off protocol is that of decoder_cluster.h, every storing wave signalling for itself;
 //   * attention: workgroup j scores, normalises and contracts rows (M / 16) j ... of its cluster (4 waves each).
-// Every wait is bounded; on a timeout the sticky status word is set and the grid drains.  All workgroups must be
-// co-resident: 16 * ceil(B / M) compute units (api_stages.hip checks the budget).  Configurations this kernel does not cover
-// (other layer sizes or counts) run in decoder_persistent.hip / decoder.hip.
+// Every wait is bounded (decoder_cluster.h).  All workgroups must be co-resident: 16 * ceil(B / M) compute units (api_stages.hip
+// checks the budget).  Configurations this kernel does not cover (other layer sizes or counts) run in decoder_persistent.hip /
+// decoder.hip.
 #include "tts_common.h"
 #include "decoder.h"
+#include "decoder_cluster.h"
 #include <cstring>
 #include <cstdio>
 
@@ -39,7 +38,6 @@ namespace tts {
 #define WS_D 256
 #define WS_P2 128
 #define WS_RED_LD 20
-#define WS_SPIN_LIMIT 2000000u
 #define WS_KB 2      // key passes (16 positions each) requested together per row
 #define WS_VB 8      // value rows per wave requested together
 
@@ -80,47 +78,7 @@ size_t ws_lds_bytes(int Ts, int M) { return ((size_t)WS_OFF_SC(M) + 2 * (size_t)
 #define WS_STATE_FLOATS(M) (8 * WS_BUF(M))
 #define WS_REST_FLOATS(M) (4 * WS_BUF(M) + (M) * WS_P2)          // p1 | rh | ctx | y0 | p2
 
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned ws_u32x4;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ws_rsrc(const void* p) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)0xFFFFFFF0u, 0x00020000);
-}
-// 16-byte sc1 (write-through / L1-bypassing) accesses: aux bit 4
-__device__ __forceinline__ float4 ws_ld4(const __amdgpu_buffer_rsrc_t& rs, unsigned byte_off) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 16));
-}
-__device__ __forceinline__ void ws_st4(const __amdgpu_buffer_rsrc_t& rs, unsigned byte_off, float4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ws_u32x4, v), rs, (int)byte_off, 0, 16);
-}
-
 enum WsEpi { WS_ACT = 0, WS_GATES = 1, WS_CAND = 2, WS_CUDNN_RU = 3 };
-
-// Start of a phase: wait until `target` arrivals have been counted on the cluster's counter (one lane polls, everybody
-// meets at the barrier).
-__device__ __forceinline__ void ws_wait(unsigned* cnt, unsigned target, int* status, int* ctrl) {
-    if (threadIdx.x == 0 && target > 0) {
-        if (ctrl[0] == 0) {
-            unsigned spins = 0;
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(1);
-                if ((++spins & 1023u) == 0 &&
-                    (spins > WS_SPIN_LIMIT || __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                    __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ctrl[0] = 1;   // drain: no further waits in this workgroup
-                    break;
-                }
-            }
-        }
-    }
-    __syncthreads();
-}
-// End of a phase, per storing wave: its (write-through) stores have drained, then its arrival (agent scope).  A workgroup
-// counts WS_ARRIVALS per phase, however many of its waves store.
-#define WS_ARRIVALS 2u
-__device__ __forceinline__ void ws_publish_wave(unsigned* cnt, unsigned arrivals) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(cnt, arrivals, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 struct WsPhase {
     const float* a0; const float* a1;   // the two segments of the A tile: a cluster's buffers, block format
@@ -227,7 +185,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
     }
     if (early) mma_slice();
 
-    ws_wait(cnt, ph.target, status, ctrl);
+    dc_wait(cnt, ph.target, status, ctrl);
     if (ph.delay && j == 3)   // a late stager: what a workgroup that clears its poll late looks like to its peers
         for (int i = 0; i < ph.delay; ++i) __builtin_amdgcn_s_sleep(127);
 
@@ -235,12 +193,12 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
     // (KEEP0: segment 0 is in place)
     {
         constexpr int U0 = KEEP0 ? NLD0 : 0, U1 = XG ? U0 : (EARLY1 ? NLD0 : NLD);
-        const __amdgpu_buffer_rsrc_t r0 = ws_rsrc(ph.a0), r1 = ws_rsrc((K1 > 0 && !EARLY1) ? ph.a1 : ph.a0);
+        const __amdgpu_buffer_rsrc_t r0 = dc_rsrc(ph.a0), r1 = dc_rsrc((K1 > 0 && !EARLY1) ? ph.a1 : ph.a0);
         float4 sv[NLD];
 #pragma unroll
         for (int u = U0; u < U1; ++u)
-            sv[u] = u < NLD0 ? ws_ld4(r0, (unsigned)(tid + WS_THREADS * u) * 16u)
-                             : ws_ld4(r1, (unsigned)(tid + WS_THREADS * (u - NLD0)) * 16u);
+            sv[u] = u < NLD0 ? dc_ld4(r0, (unsigned)(tid + WS_THREADS * u) * 16u)
+                             : dc_ld4(r1, (unsigned)(tid + WS_THREADS * (u - NLD0)) * 16u);
 #pragma unroll
         for (int u = U0; u < U1; ++u) *reinterpret_cast<float4*>(As + 4 * (tid + WS_THREADS * u)) = sv[u];
         __syncthreads();
@@ -255,9 +213,9 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
     }
     __syncthreads();
     if (NEXT1) {   // the next phase's early segment: requested now, in flight during this phase's epilogue and publish
-        const __amdgpu_buffer_rsrc_t rn = ws_rsrc(ph.next1);
+        const __amdgpu_buffer_rsrc_t rn = dc_rsrc(ph.next1);
 #pragma unroll
-        for (int u = 0; u < PRE; ++u) pre[u] = ws_ld4(rn, (unsigned)(tid + WS_THREADS * u) * 16u);
+        for (int u = 0; u < PRE; ++u) pre[u] = dc_ld4(rn, (unsigned)(tid + WS_THREADS * u) * 16u);
     }
 
     // ---- epilogue: thread e owns (row, 4 consecutive units) of every gate; the K slices are added in a fixed order.
@@ -293,7 +251,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
         } else if (EPI == WS_ACT) {
             float4 o = v[0];
             o.x = apply_act(o.x, ACT); o.y = apply_act(o.y, ACT); o.z = apply_act(o.z, ACT); o.w = apply_act(o.w, ACT);
-            ws_st4(ws_rsrc(ph.out), ooff, o);
+            dc_st4(dc_rsrc(ph.out), ooff, o);
         } else if (EPI == WS_GATES) {
             float4 rr4, uu4;
             rr4.x = sigmoidf_(v[0].x); rr4.y = sigmoidf_(v[0].y); rr4.z = sigmoidf_(v[0].z); rr4.w = sigmoidf_(v[0].w);
@@ -301,7 +259,7 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
             *reinterpret_cast<float4*>(ul) = uu4;               // u stays in this workgroup
             const float4 h4 = *reinterpret_cast<const float4*>(hl);
             rr4.x *= h4.x; rr4.y *= h4.y; rr4.z *= h4.z; rr4.w *= h4.w;   // r*h is the candidate's K operand: hand it over
-            ws_st4(ws_rsrc(ph.out), ooff, rr4);
+            dc_st4(dc_rsrc(ph.out), ooff, rr4);
         } else {   // WS_CAND: h' = u h + (1 - u) tanh(.)
             const float4 h4 = *reinterpret_cast<const float4*>(hl);
             const float4 u4 = *reinterpret_cast<const float4*>(ul);
@@ -311,17 +269,17 @@ __device__ __forceinline__ void ws_phase(const float (&w)[DEC_WS_NREG], const Ws
             hn.z = u4.z * h4.z + (1.0f - u4.z) * tanhf_(v[0].z);
             hn.w = u4.w * h4.w + (1.0f - u4.w) * tanhf_(v[0].w);
             *reinterpret_cast<float4*>(hl) = hn;
-            ws_st4(ws_rsrc(ph.out), ooff, hn);
+            dc_st4(dc_rsrc(ph.out), ooff, hn);
             if (ph.yout) {   // ResidualWrapper: y = x + h'; x = this workgroup's units of segment 0 of the staged tile
                 const float4 x4 = *reinterpret_cast<const float4*>(As + (j * M + row) * 16 + c4);
                 hn.x += x4.x; hn.y += x4.y; hn.z += x4.z; hn.w += x4.w;
-                ws_st4(ws_rsrc(ph.yout), ooff, hn);
+                dc_st4(dc_rsrc(ph.yout), ooff, hn);
                 if (ph.yhist && b0 + row < B)   // (read by the deferred output projection after the launch: a plain store)
                     *reinterpret_cast<float4*>(ph.yhist + (size_t)(b0 + row) * ph.yld + j * 16 + c4) = hn;
             }
         }
         // (a plain yhist store drains with the others: one wait covers both)
-        if (EPI != WS_CUDNN_RU) ws_publish_wave(cnt, WS_ARRIVALS / (unsigned)(NT >= 64 ? NT / 64 : 1));
+        if (EPI != WS_CUDNN_RU) dc_publish_wave(cnt, DC_ARRIVALS / (unsigned)(NT >= 64 ? NT / 64 : 1));
     }
     if (EPI == WS_CUDNN_RU) __syncthreads();   // r / u are in LDS, the partial tiles may be overwritten (no hand-off here)
 }
@@ -380,9 +338,9 @@ __device__ __forceinline__ void ws_phase_hx(const float (&w)[DEC_WS_NREG], const
     }
     __syncthreads();
     if (NEXT1) {   // (see ws_phase)
-        const __amdgpu_buffer_rsrc_t rn = ws_rsrc(ph.next1);
+        const __amdgpu_buffer_rsrc_t rn = dc_rsrc(ph.next1);
 #pragma unroll
-        for (int u = 0; u < PRE; ++u) pre[u] = ws_ld4(rn, (unsigned)(tid + WS_THREADS * u) * 16u);
+        for (int u = 0; u < PRE; ++u) pre[u] = dc_ld4(rn, (unsigned)(tid + WS_THREADS * u) * 16u);
     }
     if (tid < M * 4) {
         const int row = tid >> 2, c4 = (tid & 3) * 4;
@@ -408,15 +366,15 @@ __device__ __forceinline__ void ws_phase_hx(const float (&w)[DEC_WS_NREG], const
         hn.z = u4.z * h4.z + (1.0f - u4.z) * tanhf_(v[0].z + r4.z * v[1].z);
         hn.w = u4.w * h4.w + (1.0f - u4.w) * tanhf_(v[0].w + r4.w * v[1].w);
         *reinterpret_cast<float4*>(hl) = hn;
-        ws_st4(ws_rsrc(ph.out), ooff, hn);
+        dc_st4(dc_rsrc(ph.out), ooff, hn);
         if (ph.yout) {   // ResidualWrapper: y = x + h'
             const float4 x4 = *reinterpret_cast<const float4*>(As + (j * M + row) * 16 + c4);
             hn.x += x4.x; hn.y += x4.y; hn.z += x4.z; hn.w += x4.w;
-            ws_st4(ws_rsrc(ph.yout), ooff, hn);
+            dc_st4(dc_rsrc(ph.yout), ooff, hn);
             if (ph.yhist && b0 + row < B)
                 *reinterpret_cast<float4*>(ph.yhist + (size_t)(b0 + row) * ph.yld + j * 16 + c4) = hn;
         }
-        ws_publish_wave(cnt, WS_ARRIVALS / (unsigned)(M * 4 / 64));
+        dc_publish_wave(cnt, DC_ARRIVALS / (unsigned)(M * 4 / 64));
     }
 }
 
@@ -429,16 +387,10 @@ __device__ __forceinline__ void ws_phase_hx(const float (&w)[DEC_WS_NREG], const
 // p = Ts sigmoid(v_p . tanh(W_p h)) is scored; the reported alignments are zero outside it and, with `gaussian`, weighted as
 // the reference writes it (attention.py:73-80); a predicted window that leaves the memory raises the error flag (the
 // reference's padding arithmetic fails there, attention.py:288-304).
-struct WsLocal {
-    int d, gaussian, predictive, step;
-    const float* wp; const float* vp;   // [256][256] (q @ W_p), [256]
-    float* p_hist_t;                    // [B] predicted centres of this step
-    int* err_flag;
-};
 template <int M, bool LOCAL>
 __device__ __forceinline__ void ws_attention(const float* __restrict__ query, const float* __restrict__ keys,
                                              const float* __restrict__ values, float* ctx, float* align_t, int Ts, float* lds,
-                                             int j, int b0, int B, unsigned* cnt, unsigned target, int* status, const WsLocal& lc) {
+                                             int j, int b0, int B, unsigned* cnt, unsigned target, int* status, const DcLocal& lc) {
     constexpr int RPW = M / 16;            // rows per workgroup
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));   // (see ws_phase)
@@ -474,12 +426,12 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
     };
     if (active && !LOCAL) load_keys(keys + (size_t)mr * Ts * WS_D, 0, Ts);   // (the window of the local form may depend on the query)
 
-    ws_wait(cnt, target, status, ctrl);
+    dc_wait(cnt, target, status, ctrl);
 
     // the query: row rl of the attention GRU's new state (block format: unit u at ((u / 16) * M + row) * 16 + u % 16)
     if (active && t256 < 64)
         *reinterpret_cast<float4*>(qs + 4 * t256) =
-            ws_ld4(ws_rsrc(query), (unsigned)(((t256 >> 2) * M + rl) * 16 + 4 * (t256 & 3)) * 4u);
+            dc_ld4(dc_rsrc(query), (unsigned)(((t256 >> 2) * M + rl) * 16 + 4 * (t256 & 3)) * 4u);
     __syncthreads();
 
     // scored positions [w_lo, w_lo + w_n): the whole memory, or the local window
@@ -488,16 +440,9 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
     if (LOCAL) {
         w_n = 2 * lc.d + 1;
         if (lc.predictive) {
-            // (q W_p)[n] by thread n of the row's 256 (columns coalesced), then v_p . tanh(.) over them, in double
-            // (tts_common.h, predicted_centre): the waves' sums as (hi, lo) pairs in redm[hw], redm[4 + hw]
+            // thread n of the row's 256 forms (q W_p)[n] (columns coalesced); the waves' sums as (hi, lo) pairs in redm[hw], redm[4 + hw]
             if (active) {
-                double a0 = 0.0, a1 = 0.0;
-                const float* wpn = lc.wp + t256;
-                for (int k = 0; k < WS_D; k += 2) {
-                    a0 = fma((double)qs[k], (double)wpn[(size_t)k * WS_D], a0);
-                    a1 = fma((double)qs[k + 1], (double)wpn[(size_t)(k + 1) * WS_D], a1);
-                }
-                const double v = wave_sum_f64((double)tanhf((float)(a0 + a1)) * (double)lc.vp[t256]);
+                const double v = local_predict_wave_sum(qs, lc.wp, lc.vp, t256);
                 if (lane == 0) split_f64(v, &redm[hw], &redm[4 + hw]);
             }
             __syncthreads();
@@ -506,18 +451,15 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
             for (int i = 0; i < 4; ++i) z += (double)redm[i] + (double)redm[4 + i];
             const float pp = predicted_centre(z, Ts);
             const int c = (int)floorf(pp);
-            // a window that leaves the memory: the reference's padding arithmetic fails there (decoder.hip)
             if (active && t256 == 0 && row_ok) {
                 lc.p_hist_t[row] = pp;
-                if (c - lc.d < 0 || c + lc.d + 1 > Ts) *lc.err_flag = 1;
+                if (!local_inside_memory(c, lc.d, Ts)) *lc.err_flag = 1;
             }
-            w_lo = min(max(c - lc.d, 0), Ts - w_n);
+            w_lo = local_clamped_lo(c, lc.d, Ts, w_n);
             pc = pp;
             __syncthreads();   // redm is reused below
         } else {
-            int c = lc.step > lc.d ? lc.step : lc.d;
-            const int hi = Ts - (lc.d + 1);
-            c = c < hi ? c : hi;
+            const int c = local_center(lc.step, Ts, lc.d);
             w_lo = c - lc.d;
             pc = (float)c;
         }
@@ -616,26 +558,22 @@ __device__ __forceinline__ void ws_attention(const float* __restrict__ query, co
             }
             const float iv = invs[hf];
             a.x *= iv; a.y *= iv; a.z *= iv; a.w *= iv;
-            ws_st4(ws_rsrc(ctx), (unsigned)((jb * M + RPW * j + hf) * 16 + 4 * c) * 4u, a);
+            dc_st4(dc_rsrc(ctx), (unsigned)((jb * M + RPW * j + hf) * 16 + 4 * c) * 4u, a);
         }
-        ws_publish_wave(cnt, WS_ARRIVALS);
+        dc_publish_wave(cnt, DC_ARRIVALS);
     }
     if (active && align_t && row_ok) {
         if (!LOCAL) {
             for (int k = t256; k < Ts; k += 256) align_t[(size_t)row * Ts + k] = sc[k] * inv;
         } else {
-            // the reference pads the window back to the memory length (attention.py:85-92) and, with `gaussian`, weights it by
-            // exp(-(j - p)^2 / 2 * (D/2)^2) as written at attention.py:73-80 (the context uses the plain softmax)
-            const float gk = 0.5f * (0.5f * lc.d) * (0.5f * lc.d);
+            // the reference pads the window back to the memory length (attention.py:85-92); `gaussian` weights the reported row
+            const float gk = local_gauss_k(lc.d);
             for (int k = t256; k < Ts; k += 256) {
                 const int jw = k - w_lo;
                 float a = 0.f;
                 if (jw >= 0 && jw < w_n) {
                     a = sc[jw] * inv;
-                    if (lc.gaussian) {
-                        const float dist = (float)k - pc;
-                        a *= __expf(-(dist * dist) * gk);
-                    }
+                    if (lc.gaussian) a *= local_gauss((float)k, pc, gk);
                 }
                 align_t[(size_t)row * Ts + k] = a;
             }
@@ -653,7 +591,7 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cluster = blockIdx.x / WS_W, j = blockIdx.x - cluster * WS_W;
     const int b0 = cluster * M;
-    unsigned* cnt = p.counters + 64 * cluster;
+    unsigned* cnt = p.counters + DC_CNT_LD * cluster;
     int* ctrl = reinterpret_cast<int*>(lds + WS_OFF_CTRL(M));
 
     // ---- this wave's weights: up to 176 registers per lane, once, from the register-order image (decoder_ws_pack)
@@ -673,9 +611,7 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
     for (int i = tid; i < DEC_WS_BIAS_SLOTS * 32; i += WS_THREADS) lds[WS_OFF_BIAS(M) + i] = p.bimg[j * (DEC_WS_BIAS_SLOTS * 32) + i];
     if (tid == 0) {
         ctrl[0] = 0;
-        // all workgroups resident: the CUs the call pipeline held for this stream are no longer needed
-        const unsigned n = __hip_atomic_fetch_add(p.resident, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (n + 1 == gridDim.x && p.hold_flag) __hip_atomic_store(p.hold_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (dc_all_resident(p.resident) && p.hold_flag) dc_release_held(p.hold_flag);
     }
     __syncthreads();
 
@@ -685,14 +621,14 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
     float* p1 = rs, *rh = rs + WS_BUF(M), *ctx = rs + 2 * WS_BUF(M), *y0 = rs + 3 * WS_BUF(M), *p2 = rs + 4 * WS_BUF(M);
     const int yld = p.n_steps * WS_D;
     unsigned g = 0;   // hand-offs completed by the cluster
-    const unsigned per = WS_ARRIVALS * WS_W;
+    const unsigned per = DC_ARRIVALS * WS_W;
 
     // segment 1 of the first phase (the attention of "step -1": zeros), as every later step gets it from the phase before
     float4 pre[4];
     {
-        const __amdgpu_buffer_rsrc_t rn = ws_rsrc(att);
+        const __amdgpu_buffer_rsrc_t rn = dc_rsrc(att);
 #pragma unroll
-        for (int u = 0; u < PRE; ++u) pre[u] = ws_ld4(rn, (unsigned)(tid + WS_THREADS * u) * 16u);
+        for (int u = 0; u < PRE; ++u) pre[u] = dc_ld4(rn, (unsigned)(tid + WS_THREADS * u) * 16u);
     }
     for (int t = 0; t < p.n_steps; ++t) {
         // cell states by step parity: step t reads [t & 1] and writes [(t + 1) & 1]
@@ -723,7 +659,7 @@ __global__ __launch_bounds__(WS_THREADS) void dec_ws_kernel(WsParams p) {
             ws_phase<M, WS_P2, 8, WS_D, 1, 16, WS_CAND, ACT_NONE, WS_R3, true, 4, false, false>(w, ph, lds, j, b0, p.B, cnt, p.status, pre);
         }
         {
-            WsLocal lc;
+            DcLocal lc;
             lc.d = p.local_d; lc.gaussian = p.local_gaussian; lc.predictive = p.local_predictive; lc.step = t;
             lc.wp = p.local_wp; lc.vp = p.local_vp; lc.p_hist_t = p.p_hist ? p.p_hist + (size_t)t * p.B : nullptr;
             lc.err_flag = p.err_flag;
@@ -777,17 +713,17 @@ size_t decoder_ws_scratch_floats(int B, int rows) {
 }
 int decoder_ws_clusters(int B, int rows) { const int M = ws_rows(rows); return (B + M - 1) / M; }
 
+// Every instantiation of the kernel, at index cudnn + 2 * (rows == 16) + 4 * local + 8 * teach
+typedef void (*WsKernel)(WsParams);
+static const WsKernel ws_kernels[16] = {
+    dec_ws_kernel<false, 32, false, false>, dec_ws_kernel<true, 32, false, false>, dec_ws_kernel<false, 16, false, false>, dec_ws_kernel<true, 16, false, false>,
+    dec_ws_kernel<false, 32, true, false>,  dec_ws_kernel<true, 32, true, false>,  dec_ws_kernel<false, 16, true, false>,  dec_ws_kernel<true, 16, true, false>,
+    dec_ws_kernel<false, 32, false, true>,  dec_ws_kernel<true, 32, false, true>,  dec_ws_kernel<false, 16, false, true>,  dec_ws_kernel<true, 16, false, true>,
+    dec_ws_kernel<false, 32, true, true>,   dec_ws_kernel<true, 32, true, true>,   dec_ws_kernel<false, 16, true, true>,   dec_ws_kernel<true, 16, true, true>};
+
 hipError_t decoder_ws_configure() {
-    const void* fns[16] = {reinterpret_cast<const void*>(&dec_ws_kernel<false, 32>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, true>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, true>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, false, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, false, true>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, false, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, false, true>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 32, true, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 32, true, true>),
-                           reinterpret_cast<const void*>(&dec_ws_kernel<false, 16, true, true>), reinterpret_cast<const void*>(&dec_ws_kernel<true, 16, true, true>)};
-    for (const void* f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+    for (const WsKernel f : ws_kernels) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -877,50 +813,28 @@ size_t decoder_ws_wimg_floats() { return (size_t)WS_W * WS_NW * DEC_WS_NREG * 64
 size_t decoder_ws_bimg_floats() { return (size_t)WS_W * DEC_WS_BIAS_SLOTS * 32; }
 
 // Capturable: two memsets and one launch.  `scratch`: decoder_ws_scratch_floats(B, rows) floats (the state blocks of all clusters
-// first: zeroed here); `sync` = 64 unsigned per cluster (of sync_clusters >= the launch's) + 1 (resident count) + 1 (sticky status
-// word, see decoder_persistent.hip).
+// first: zeroed here); `sync`: dc_sync_words(max(clusters, sync_clusters)) words (decoder_cluster.h).
 // rows: utterances per cluster (32: 16 compute units per 32 utterances; 16: per 16 -- same bits, see the LDS map)
 hipError_t decoder_ws_enqueue(hipStream_t s, const DecoderWeights& w, float* scratch, float* yhist, const float* memory,
                               const float* keys, int B, int Ts, int n_steps, float* align, unsigned* sync, int* hold_flag,
                               int cudnn, int dbg_delay, int rows, int sync_clusters, float* p_hist, int* err_flag, const float* xg) {
     const int M = ws_rows(rows);
     const int clusters = (B + M - 1) / M;
-    // (the resident count and the sticky status word sit behind the counters of `sync_clusters` clusters: one place for
-    //  both forms of one batch size, so that a status raised by a launch of one form is found after a launch of the other)
-    if (sync_clusters < clusters) sync_clusters = clusters;
     const size_t state_floats = M == 16 ? WS_STATE_FLOATS(16) : WS_STATE_FLOATS(32);
     hipError_t e;
     if ((e = hipMemsetAsync(scratch, 0, (size_t)clusters * state_floats * sizeof(float), s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sync, 0, ((size_t)64 * sync_clusters + 1) * sizeof(unsigned), s)) != hipSuccess) return e;
+    if (xg && !w.ws_teacher) return hipErrorInvalidValue;
     WsParams p;
+    if ((e = dc_launch_params(s, sync, dc_layout_clusters(clusters, sync_clusters), w, p_hist, err_flag, p)) != hipSuccess) return e;
     p.wimg = w.ws_wimg; p.bimg = w.ws_bimg;
     p.memory = memory; p.keys = keys;
     p.state = scratch; p.rest = scratch + (size_t)clusters * state_floats;
     p.yhist = yhist; p.align = align;
-    p.counters = sync; p.resident = sync + 64 * sync_clusters; p.status = reinterpret_cast<int*>(sync + 64 * sync_clusters + 1);
     p.hold_flag = hold_flag;
     p.B = B; p.Ts = Ts; p.n_steps = n_steps; p.dbg_delay = dbg_delay; p.cudnn = cudnn;
-    p.local_d = w.local_d; p.local_gaussian = w.local_gaussian; p.local_predictive = w.local_d > 0 && w.local_predictive;
-    p.local_wp = w.local_wp; p.local_vp = w.local_vp; p.p_hist = p_hist; p.err_flag = err_flag;
     p.xg = xg;
-    if (xg && !w.ws_teacher) return hipErrorInvalidValue;
-    if (p.local_predictive) {
-        if (!p_hist || !err_flag) return hipErrorInvalidValue;
-        if ((e = hipMemsetAsync(err_flag, 0, sizeof(int), s)) != hipSuccess) return e;
-    }
-    const dim3 grid(WS_W * clusters), block(WS_THREADS);
-    const size_t lds = ws_lds_bytes(Ts, M);
-#define WS_LAUNCH(C, MM, L, T) hipLaunchKernelGGL((dec_ws_kernel<C, MM, L, T>), grid, block, lds, s, p)
-#define WS_LAUNCH_T(C, MM, L) do { if (xg) WS_LAUNCH(C, MM, L, true); else WS_LAUNCH(C, MM, L, false); } while (0)
-    if (w.local_d > 0) {
-        if (M == 16) { if (cudnn) WS_LAUNCH_T(true, 16, true); else WS_LAUNCH_T(false, 16, true); }
-        else { if (cudnn) WS_LAUNCH_T(true, 32, true); else WS_LAUNCH_T(false, 32, true); }
-    } else {
-        if (M == 16) { if (cudnn) WS_LAUNCH_T(true, 16, false); else WS_LAUNCH_T(false, 16, false); }
-        else { if (cudnn) WS_LAUNCH_T(true, 32, false); else WS_LAUNCH_T(false, 32, false); }
-    }
-#undef WS_LAUNCH_T
-#undef WS_LAUNCH
+    const WsKernel kernel = ws_kernels[(cudnn != 0) + 2 * (M == 16) + 4 * (w.local_d > 0) + 8 * (xg != nullptr)];
+    hipLaunchKernelGGL(kernel, dim3(WS_W * clusters), dim3(WS_THREADS), ws_lds_bytes(Ts, M), s, p);
     return hipGetLastError();
 }
 

@@ -797,6 +797,48 @@ int tts_join_max_pieces(void);
 int tts_join_max_fade(void);
 int tts_join_tile(void);
 
+/* ---- delivery formats: 16-bit PCM, 8-bit PCM and G.711 --------------------------------------- */
+#define TTS_FMT_F32 0        /* float32 as the library makes it: no encoding */
+#define TTS_FMT_PCM_S16 1    /* signed 16-bit PCM, 2 bytes per code */
+#define TTS_FMT_PCM_U8 2     /* unsigned 8-bit PCM (WAV's), offset 128 */
+#define TTS_FMT_MULAW 3      /* ITU-T G.711 mu-law, 1 byte per code */
+#define TTS_FMT_ALAW 4       /* ITU-T G.711 A-law, 1 byte per code */
+#define TTS_DITHER_NONE 0
+#define TTS_DITHER_TPDF 1    /* triangular, (-1, 1) LSB, added before the rounding */
+/* What tts_encode reports per row; every field is order-free.  16 bytes. */
+typedef struct tts_encode_stats {
+    int32_t clipped;   /* samples whose rounded value lay outside the format's range (+-Inf included) and was saturated */
+    int32_t nans;      /* NaN samples: encoded as zero */
+    int32_t peak;      /* the largest |q| after saturation */
+    int32_t n;         /* the samples the row holds: n_samples[b], or N */
+} tts_encode_stats_t;
+/* Float32 rows to delivery codes, one streaming pass (no reference counterpart).  wav DEVICE [B][N] (4-byte aligned); out
+ * DEVICE [B][N] codes of tts_encode_width(format) bytes, rows N codes apart with no padding (aligned as a code is: 2 bytes for
+ * TTS_FMT_PCM_S16); n_samples: HOST int32 [B] or NULL (all N), 0 .. N each.  Sample i < n_samples[b] of row b:
+ *   scale   v = (double)x * Q, Q = 128 (PCM_U8) or 32768 (the others): exact
+ *   dither  d = 0 (TTS_DITHER_NONE), or with TTS_DITHER_TPDF, in arithmetic modulo 2^64,
+ *             z = seed + 0x9E3779B97F4A7C15 * (((uint64)b << 32 | i) + 1)
+ *             z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31
+ *             d = ((double)(z >> 32) - (double)(z & 0xFFFFFFFF)) * 2^-32
+ *           exact, triangular on (-1, 1) LSB, a function of (seed, b, i) alone: never of the tiling or the grid
+ *   round   q = rint(v + d), ties to even.  A NaN gives q = 0 and counts in `nans`; q outside [-Q, Q - 1] (+-Inf included) is
+ *           saturated and counts in `clipped`
+ *   code    PCM_S16: q.  PCM_U8: q + 128.  MULAW / ALAW: ITU-T G.711 from the 16-bit q by the CCITT / Sun g711.c arithmetic, which
+ *           Python's audioop.lin2ulaw(., 2) / lin2alaw(., 2) run: mu-law from q >> 2 (clip 8159, bias 33), A-law from q >> 3
+ *           (negative magnitudes -v - 1).  Digital silence is 0xFF (mu-law) and 0xD5 (A-law).
+ * Samples i >= n_samples[b] are written as the format's code for zero, undithered, and count nowhere: every code of out is
+ * written by every call.  stats DEVICE [B] or NULL (4-byte aligned): peak the largest |q| after saturation, n = n_samples[b].
+ * Exactness: the bits of tests/encode_oracle.py.  No model needs to be loaded.  Asynchronous on the handle's stream, no host wait:
+ * two launches per 64 rows (the records, the pass); profile stage "encode".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL wav or out, B or N < 1, an unknown format or TTS_FMT_F32 (no encoding), an
+ * unknown dither, an n_samples[b] outside 0 .. N, a misaligned buffer. */
+int tts_encode(tts_handle_t h, const float* wav /* DEVICE [B][N] */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+               int format, int dither, uint64_t seed, void* out /* DEVICE [B][N] codes */, tts_encode_stats_t* stats /* DEVICE [B] or NULL */);
+/* Host only: the bytes of a code -- 2, 1, 1, 1 for the four encodings, 4 for TTS_FMT_F32; negative for an unknown format. */
+int tts_encode_width(int format);
+/* Host only: the samples of a row one workgroup takes. */
+int tts_encode_tile(void);
+
 /* ---- end to end -------------------------------------------------------------------------- */
 /* ids -> waveform: encoder, decoder (n_steps), post-net, de-normalise, ** power, Griffin-Lim,
  * optional peak normalisation; replaces tacotron/inference.py:162-200 minus file IO.
@@ -941,6 +983,32 @@ int tts_synth_alignment_stats(tts_handle_t h, tts_alignment_stats_t* stats_host,
  * valid as long as the ticket's waveform buffer.  TTS_ERR_INVALID also for a ticket whose call was made with the setting off. */
 int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignment_stats_t** stats, int* B);
 
+/* The delivery format of tts_synthesize_host: sample format and sampling rate (tts_encode, tts_resample).  A setting of the
+ * HANDLE, off by default and read when a call is made.  (TTS_FMT_F32, any dither, r, r) is off: the call as it always was, launch
+ * for launch and byte for byte.  Otherwise a tts_synthesize_host call runs, behind its last stage (the limiter, if that is on),
+ * on the call's stream and with no host wait:
+ *   rate_out != rate_in   tts_resample by rate_out / rate_in (within [0.25, 4]) of the call's rows, each over the samples it holds
+ *                         (all hop (T - 1) of them, or hop (n_frames[b] - 1) with end-of-speech stopping), into rows of
+ *                         N_out = tts_resampled_length(hop (T - 1), ratio) samples; row b then holds tts_resampled_length of what it
+ *                         held.  The ratio's table is made before anything of the call is enqueued.
+ *   format != TTS_FMT_F32 tts_encode(format, dither, seed = p->seed) of those rows over the samples they hold
+ * and only the codes and the 16-byte records travel to host memory: B * N_out * tts_encode_width(format) bytes instead of the
+ * float32 rows.  TTS_FMT_F32 with two rates resamples only: the bytes are float32 and there are no records.  The codes are the
+ * bits of tts_encode (behind tts_resample) on the rows of the same call made with the setting off.  The resampler runs behind
+ * the limiter and can overshoot its ceiling; the encoder then saturates and `clipped` counts how often: leave head room.
+ * Such a call's ticket is fetched with tts_wait_host_encoded; tts_wait_host refuses it, and tts_wait_host_encoded refuses a ticket
+ * of a call made with the setting off.  tts_wait_host_frames, tts_wait_host_outputs and tts_wait_host_alignment_stats are
+ * unchanged.  tts_synthesize does not read the setting: its callers hold device rows and call tts_resample / tts_encode themselves.
+ * The setting stays as it was on TTS_ERR_INVALID: an unknown format, an unknown dither with an encoding, rates that differ and are
+ * not positive or whose ratio lies outside [0.25, 4]. */
+int tts_set_output(tts_handle_t h, int format, int dither, int rate_in, int rate_out);
+/* The codes of a tts_synthesize_host call made with tts_set_output on: waits as tts_wait_host does (same ticket rules, same
+ * reports), then hands out pinned memory of the handle, valid as long as a ticket's waveform buffer.  data: [B][N_out] codes,
+ * `bytes` of them in all; n_samples [B]: the samples each row holds (behind them: the code for zero); stats [B], NULL for
+ * TTS_FMT_F32.  Every output but data may be NULL. */
+int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t* bytes, int* format, int* N_out,
+                          const int32_t** n_samples /* [B] held per row */, const tts_encode_stats_t** stats, int* B);
+
 /* ---- profiling -------------------------------------------------------------------------- */
 /* With option "profile"=1 the library brackets its stages with HIP events on the handle's
  * stream.  Stages: "encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm"
@@ -951,7 +1019,8 @@ int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignmen
  * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare), "loudness" (tts_loudness, tts_loudness_normalize, stand-alone
  * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, stand-alone or
  * inside a tts_synthesize call with tts_set_alignment_stats on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
- * stand-alone or inside a tts_synthesize call with tts_set_limiter on).
+ * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
+ * tts_synthesize_host call with tts_set_output on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -88,6 +88,15 @@ class TtsLimitStats(ctypes.Structure):
 LIMIT_RECORD = np.dtype([('over', np.int32), ('limited', np.int32), ('min_gain', np.float64)])
 
 
+class TtsEncodeStats(ctypes.Structure):
+    """struct tts_encode_stats (include/sstts_hip.h): four int32, 16 bytes."""
+    _fields_ = [('clipped', c_int32), ('nans', c_int32), ('peak', c_int32), ('n', c_int32)]
+
+
+# ... and the same record as a numpy dtype: what Engine.encode and Engine.wait_host_encoded return an array of
+ENCODE_RECORD = np.dtype([('clipped', np.int32), ('nans', np.int32), ('peak', np.int32), ('n', np.int32)])
+
+
 class TtsJoinPiece(ctypes.Structure):
     """tts_join_piece_t: samples [first, first + count) of a row and the pause behind them; a row of the (P, 4) int32 arrays
     ``Engine.join`` hands the library"""
@@ -179,6 +188,12 @@ _PROTOTYPES = {
     'tts_limit': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_int, c_void_p]),
     'tts_limit_max_lookahead': (c_int, []),
     'tts_set_limiter': (c_int, [c_void_p, c_int, ctypes.c_double, c_int, c_int]),
+    'tts_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
+    'tts_encode_width': (c_int, [c_int]),
+    'tts_encode_tile': (c_int, []),
+    'tts_set_output': (c_int, [c_void_p, c_int, c_int, c_int, c_int]),
+    'tts_wait_host_encoded': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_size_t), POINTER(c_int), POINTER(c_int), POINTER(c_void_p),
+                                      POINTER(c_void_p), POINTER(c_int)]),
     'tts_stft': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'tts_db_convert': (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_void_p]),
     'tts_stft_magnitude': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
@@ -579,6 +594,83 @@ def true_peak_filter():
     return np.array(out[:], dtype=np.float64).reshape(4, 12)
 
 
+# The delivery formats (TTS_FMT_* of include/sstts_hip.h) by the names every layer above uses, the numpy type of a code and the
+# dither modes (TTS_DITHER_*)
+FMT_F32, FMT_PCM_S16, FMT_PCM_U8, FMT_MULAW, FMT_ALAW = range(5)
+FORMATS = {'float32': FMT_F32, 'pcm16': FMT_PCM_S16, 'pcm8': FMT_PCM_U8, 'mulaw': FMT_MULAW, 'alaw': FMT_ALAW}
+FORMAT_NAMES = {v: k for k, v in FORMATS.items()}
+FORMAT_DTYPES = {FMT_F32: np.float32, FMT_PCM_S16: np.int16, FMT_PCM_U8: np.uint8, FMT_MULAW: np.uint8, FMT_ALAW: np.uint8}
+DITHER_NONE, DITHER_TPDF = 0, 1
+ENCODE_TILE = 4096               # tts_encode_tile(), samples
+OUTPUT_OFF = (FMT_F32, DITHER_NONE, 0, 0)   # the checked ``output`` of a call as it always was: float32 at the model's rate
+
+
+def format_value(what, fmt, encoding=False):
+    """a format -- one of the names of FORMATS or its TTS_FMT_* number -- as that number; ``encoding``: 'float32' is refused
+    too.  ValueError, raised before a handle is touched."""
+    if isinstance(fmt, str) and fmt in FORMATS:
+        f = FORMATS[fmt]
+    elif not isinstance(fmt, (bool, np.bool_, str)) and fmt in FORMAT_NAMES:
+        f = int(fmt)
+    else:
+        raise ValueError('{}: the format must be one of {}, got {!r}'.format(what, ', '.join(sorted(FORMATS)), fmt))
+    if encoding and f == FMT_F32:
+        raise ValueError('{}: float32 is no encoding (the rows are float32 already)'.format(what))
+    return f
+
+
+def dither_value(what, dither):
+    """``dither`` -- 'tpdf', True or TTS_DITHER_TPDF; None, False, 'none' or TTS_DITHER_NONE -- as TTS_DITHER_*; ValueError for
+    anything else"""
+    number = isinstance(dither, (int, np.integer)) and not isinstance(dither, (bool, np.bool_))
+    if dither is None or dither is False or (isinstance(dither, str) and dither == 'none') or (number and dither == DITHER_NONE):
+        return DITHER_NONE
+    if dither is True or (isinstance(dither, str) and dither == 'tpdf') or (number and dither == DITHER_TPDF):
+        return DITHER_TPDF
+    raise ValueError("{}: dither must be 'tpdf' or None, got {!r}".format(what, dither))
+
+
+def output_setting(output):
+    """``output`` of ``synthesize_host`` and the layers above -- None (the handle's setting as it stands), a format name or
+    ``(format, dither, rate_in, rate_out)`` (rates in Hz; both None: no resampling) -- as None or a checked tuple ``(format number,
+    dither number, rate_in, rate_out)``; a bare name is dithered and keeps the rate, and whatever changes nothing of a call --
+    'float32' with equal rates or none -- is ``OUTPUT_OFF``.  ValueError, raised before a handle is
+    touched, for what tts_set_output refuses: an unknown format or dither, rates that are not positive integers or whose ratio
+    lies outside [0.25, 4]."""
+    if output is None:
+        return None
+    if isinstance(output, (tuple, list)):
+        if len(output) != 4:
+            raise ValueError('output must be None, a format name or (format, dither, rate_in, rate_out), got {!r}'.format(output))
+        fmt, dither, rate_in, rate_out = output
+    else:
+        fmt, dither, rate_in, rate_out = output, 'tpdf', None, None
+    f = format_value('output', fmt)
+    d = DITHER_NONE if f == FMT_F32 else dither_value('output', dither)
+    if (rate_in is None) != (rate_out is None):
+        raise ValueError('output: both rates or neither, got {!r} and {!r}'.format(rate_in, rate_out))
+    if rate_in is None or (rate_in == 0 and rate_out == 0 and not isinstance(rate_in, (bool, np.bool_))):   # (0, 0: the checked form)
+        return (f, d, 0, 0) if f != FMT_F32 else OUTPUT_OFF
+    for r in (rate_in, rate_out):
+        if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)) or r < 1 or r > 2 ** 31 - 1:
+            raise ValueError('output: a rate must be a positive integer of Hz, got {!r}'.format(r))
+    if rate_in != rate_out:
+        resample_ratio_value(float(rate_out) / float(rate_in))
+    elif f == FMT_F32:
+        return OUTPUT_OFF
+    return f, d, int(rate_in), int(rate_out)
+
+
+def output_is_on(setting):
+    """whether a checked ``output`` changes anything of a call: an encoding, or two different rates"""
+    return setting is not None and tuple(setting) != OUTPUT_OFF
+
+
+def output_ratio(setting):
+    """rate_out / rate_in of a checked ``output``; 1.0 without resampling"""
+    return float(setting[3]) / float(setting[2]) if setting is not None and setting[2] != setting[3] else 1.0
+
+
 def alignment_stats_setting(alignment_stats):
     """``alignment_stats`` of the synthesis calls -- None (the handle's setting as it stands), False (off), True (on, pad id 0)
     or ``(enabled, pad_id)`` -- as None or a checked tuple ``(enabled, pad_id)``.  ValueError, raised before a handle is touched,
@@ -834,6 +926,10 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
 #   ``limiter``: a ceiling or ``(ceiling, lookahead_ms, oversample)`` (tts_set_limiter, off unless ``set_limiter`` changed it): the
 #     call's final rows go through ``limit`` last, behind the loudness gain or the peak normalisation, each utterance over the
 #     samples its row holds; the look-ahead is taken at the model's sampling rate.
+#   ``output`` (the one row of HOST_SETTINGS, behind the eight of SETTINGS): a format name or ``(format, dither, rate_in,
+#     rate_out)`` (tts_set_output, off unless ``set_output`` changed it): ``synthesize_host`` alone -- the call's final rows are resampled and encoded on the device, behind the limiter, and only the
+#     codes and their records travel to the host (``wait_host_encoded``).  ``synthesize`` hands out device rows: ``encode`` is
+#     its callers' to call.
 # A row: the keyword, the Engine attribute that mirrors the handle's value, the handle's initial value, the check that turns
 # the keyword into the mirror's value (ValueError before a handle is touched), and how a value is applied -- a ``set_option``
 # key or a call of the engine's ``set_*`` method.
@@ -849,6 +945,10 @@ SETTINGS = (
     Setting('alignment_stats', '_alignment_stats', (False, 0), alignment_stats_setting, lambda engine, v: engine.set_alignment_stats(*v)),
     Setting('limiter', '_limiter', None, limiter_setting, lambda engine, v: engine.set_limiter(v)),
 )
+# ... and the one setting of the host form alone, checked and applied behind those (``Engine.synthesize`` refuses the keyword):
+HOST_SETTINGS = (
+    Setting('output', '_output', OUTPUT_OFF, output_setting, lambda engine, v: engine.set_output(v)),
+)
 
 
 class _Settings(object):
@@ -859,7 +959,7 @@ class _Settings(object):
 
     def __init__(self, engine, per_call):
         self.engine = engine
-        self.rows = [row for row in SETTINGS if row.keyword in per_call]
+        self.rows = [row for row in SETTINGS + HOST_SETTINGS if row.keyword in per_call]
         self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
 
     def __getitem__(self, keyword):
@@ -981,7 +1081,7 @@ class Engine(object):
 
     def _init_settings(self):
         """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
-        for row in SETTINGS:
+        for row in SETTINGS + HOST_SETTINGS:
             setattr(self, row.mirror, row.initial)
 
     def _settings(self, **per_call):
@@ -1033,6 +1133,14 @@ class Engine(object):
             L = limiter_lookahead('set_limiter', setting[1], self.sampling_rate if sampling_rate is None else sampling_rate)
             self._check(self.lib.tts_set_limiter(self.handle, 1, setting[0], L, setting[2]))
         self._limiter = setting
+
+    def set_output(self, output):
+        """tts_set_output: the handle's setting, read by every synthesize_host call made after it.  ``output``: None, False or
+        'float32' (off), a format name ('pcm16', 'pcm8', 'mulaw', 'alaw': TPDF dither, the model's rate) or ``(format, dither,
+        rate_in, rate_out)`` as ``output_setting`` reads it."""
+        setting = OUTPUT_OFF if output is None or output is False else output_setting(output)
+        self._check(self.lib.tts_set_output(self.handle, *setting))
+        self._output = setting
 
     def set_alignment_stats(self, enabled, pad_id=0):
         """tts_set_alignment_stats: the handle's setting, read by every synthesize / synthesize_host call made after it.  On,
@@ -1595,6 +1703,42 @@ class Engine(object):
             out.shape = (n,)
         return out, stats
 
+    # ------------------------------------------------------------------ delivery formats
+    def encode(self, wav, format, dither='tpdf', seed=0, n_samples=None):
+        """tts_encode: float32 rows to delivery codes -- ``format`` 'pcm16' (int16), 'pcm8', 'mulaw' or 'alaw' (uint8) -- in one
+        pass on the device: scaled, dithered (``dither`` 'tpdf' or None; a function of ``seed``, the row and the sample index
+        alone), rounded to the nearest with ties to even, saturated.  ``wav``: one waveform (n,) or a batch (B, n), a host array
+        or a device buffer.  ``n_samples``: B lengths in 0 .. n (host integers) -- samples at or behind them are not read and come
+        out as the format's silence; None: all n.  Returns ``(codes, stats)``: the codes in the input's shape -- a device array for
+        a device input, a host array for a host input -- and a host array (B,) of ``ENCODE_RECORD``.  The bits of
+        tests/encode_oracle.py."""
+        f = format_value('encode', format, encoding=True)
+        d = dither_value('encode', dither)
+        if isinstance(seed, (bool, np.bool_)) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError('encode: the seed must be an integer in 0 .. 2^64 - 1, got {!r}'.format(seed))
+        wav, single, B, n = _waveforms('encode', wav)
+        ns = None
+        if n_samples is not None:
+            ns = np.asarray(n_samples)
+            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+            for b, k in enumerate(ns.tolist()):
+                if not 0 <= k <= n:
+                    raise ValueError('n_samples[{}] = {} is not in 0 .. n = {}'.format(b, k, n))
+            ns = np.ascontiguousarray(ns, dtype=np.int32)
+        on_device = _is_device(wav)
+        p_wav, _k = self._in(wav, np.float32)
+        out = self.empty((n,) if single else (B, n), FORMAT_DTYPES[f])
+        st = self.empty((B, 4), np.int32)   # (B records of 16 bytes)
+        self._check_or_free(self.lib.tts_encode(self.handle, p_wav, B, n, _int32_ptr(ns), f, d, int(seed), out.data_ptr(), st.data_ptr()), out, st)
+        stats = st.to_host().view(ENCODE_RECORD).reshape(B)
+        st.free()
+        if not on_device:
+            codes = out.to_host()
+            out.free()
+            return codes, stats
+        return out, stats
+
     # ------------------------------------------------------------------ attention diagnostics
     def alignment_stats(self, alignments, n_sent=None, n_steps=None, want_durations=False, want_pos=False):
         """tts_alignment_stats: what an alignment history says about whether the sentence was read.  ``alignments``
@@ -1825,9 +1969,15 @@ class Engine(object):
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
-                   alignment_stats=None, limiter=None):
-        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` on hold
-        for this call alone, as SETTINGS has them."""
+                   alignment_stats=None, limiter=None, **refused):
+        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` to
+        ``limiter`` hold for this call alone, as SETTINGS has them.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
+        call's rows stay on the device, where ``resample`` and ``encode`` take them."""
+        if 'output' in refused:
+            raise ValueError('synthesize: no output= here -- the waveforms stay on the device as float32; resample and encode them there '
+                             'with Engine.resample and Engine.encode, or call synthesize_host')
+        if refused:
+            raise TypeError('synthesize() got an unexpected keyword argument {!r}'.format(sorted(refused)[0]))
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter)
         B, Ts = ids.shape
@@ -1878,15 +2028,16 @@ class Engine(object):
 
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
-                        speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None):
+                        speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None,
+                        output=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
-        The eight settings from ``momentum`` on hold for this call alone, as SETTINGS has them: they are read when the call is
-        made, not when its work runs.  A call that stops at silence returns once its post-net has run (the lengths:
+        The nine settings from ``momentum`` on hold for this call alone, as SETTINGS and HOST_SETTINGS have them: they are read when the call is
+        made, not when its work runs.  A call made with an ``output`` is fetched with ``wait_host_encoded``, not ``wait_host``.  A call that stops at silence returns once its post-net has run (the lengths:
         ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``)."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
-                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter)
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -1924,6 +2075,26 @@ class Engine(object):
         if not n.value:
             return np.zeros(0, dtype=np.int32)
         return np.ctypeslib.as_array(ctypes.cast(p, POINTER(c_int32)), shape=(n.value,)).copy()
+
+    def wait_host_encoded(self, ticket, copy=True):
+        """tts_wait_host_encoded: ``(codes, n_samples, stats)`` of a ``synthesize_host`` call made with an ``output``: the codes
+        (B, N_out) as int16 ('pcm16'), uint8 ('pcm8', 'mulaw', 'alaw') or float32 ('float32' at another rate), the samples each
+        row holds (int32 (B,): behind them the row is the format's silence) and the encoder's records ((B,) of
+        ``ENCODE_RECORD``; None for float32).  ``copy=False``: the codes are a view of the library's pinned buffer, valid until
+        the THIRD ``synthesize_host`` call after the one that produced it."""
+        data, held, st = c_void_p(), c_void_p(), c_void_p()
+        nbytes = c_size_t(0)
+        fmt, N_out, B = c_int(0), c_int(0), c_int(0)
+        self._check(self.lib.tts_wait_host_encoded(self.handle, int(ticket), byref(data), byref(nbytes), byref(fmt), byref(N_out), byref(held),
+                                                   byref(st), byref(B)))
+        self._host_shapes.pop(ticket, None)
+        raw = np.ctypeslib.as_array(ctypes.cast(data, POINTER(ctypes.c_uint8)), shape=(nbytes.value,))
+        codes = raw.view(FORMAT_DTYPES[fmt.value]).reshape(B.value, N_out.value)
+        n_samples = np.ctypeslib.as_array(ctypes.cast(held, POINTER(c_int32)), shape=(B.value,)).copy()
+        stats = None
+        if st.value:
+            stats = np.ctypeslib.as_array(ctypes.cast(st, POINTER(c_int32)), shape=(B.value * 4,)).copy().view(ENCODE_RECORD).reshape(B.value)
+        return (codes.copy() if copy else codes), n_samples, stats
 
     def wait_host(self, ticket, copy=True):
         """Waveforms (B, hop*(T-1)) float32 of a ``synthesize_host`` call.  ``copy=False`` returns a view of the library's

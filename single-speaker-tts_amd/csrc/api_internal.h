@@ -56,7 +56,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -252,6 +252,15 @@ struct HostIo {
     // write the device side, the download takes it down with the waveforms; n_stats: the call's B, 0 = made with the setting off
     StagedBuf<tts_alignment_stats_t> stats[3];
     int n_stats[3] = {0, 0, 0};
+    // the delivery format of this set's call (tts_set_output; tts_wait_host_encoded): the codes -- or the resampled float32 rows --
+    // and the encoder's records, which travel instead of the float32 rows; enc_format < 0: made with the setting off.  The rows
+    // the call synthesises are the set's `wav` as ever; what the resampler makes of them for the encoder is the workspace "out.resampled"
+    StagedBuf<unsigned char> codes[3];
+    StagedBuf<tts_encode_stats_t> enc_stats[3];
+    int enc_format[3] = {-1, -1, -1}, enc_N[3] = {0, 0, 0}, enc_B[3] = {0, 0, 0};
+    size_t enc_bytes[3] = {0, 0, 0};
+    bool enc_records[3] = {false, false, false};
+    std::vector<int32_t> enc_held[3];   // the samples each row holds, at the output rate
     bool failed[3] = {false, false, false};   // this set's call ended on a decoder timeout: EVERY wait on its ticket fails
     int* status_pinned = nullptr;   // [3][2]: the persistent decoder's sticky status word ([.][1]) as it stood behind
                                     // each call's download
@@ -268,7 +277,7 @@ struct HostIo {
 };
 
 // The synthesis settings of a handle: what tts_set_end_of_speech, tts_set_speaking_rate, tts_set_pitch, tts_set_loudness,
-// tts_set_limiter, tts_set_alignment_stats and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
+// tts_set_limiter, tts_set_alignment_stats, tts_set_output and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
 // copy when the call is made and read nothing but that copy from then on; with every setting off the call enqueues what it
 // always did.  (The stand-alone Griffin-Lim calls have no such copy: they read the handle's momentum and start.)
 struct SynthSettings {
@@ -295,6 +304,13 @@ struct SynthSettings {
         bool enabled = false;
         int pad_id = 0;
     } ali;
+    // the delivery format of tts_synthesize_host (tts_set_output): enabled = an encoding or a ratio other than 1
+    struct {
+        bool enabled = false;
+        int format = 0;       // TTS_FMT_*
+        int dither = 0;       // TTS_DITHER_*
+        double ratio = 1.0;   // rate_out / rate_in; 1.0: no resampling
+    } out;
     // fast Griffin-Lim: the momentum alpha in thousandths, 0 (default: the reference's plain loop) .. 999; alpha > 0 runs one
     // iteration per launch whatever gl_pair says (gl_stream_kernel, MOM)
     int gl_momentum = 0;
@@ -633,6 +649,11 @@ struct LimScratch { float* out; int* flags; tts_limit_stats_t* stats; };   // th
 int limiter_scratch(tts_handle_t h, int B, int N, LimScratch* s);
 int limiter_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samples, double ceiling, int lookahead, int oversample,
                  tts_limit_stats_t* stats);
+// the delivery encoder (encode.hip): arguments checked by the caller (encode_plan.h).  The records of a call that takes none
+struct EncScratch { tts_encode_stats_t* stats; };
+int encode_scratch(tts_handle_t h, int B, EncScratch* s);
+int encode_impl(tts_handle_t h, const float* wav, int B, int N, const int32_t* n_samples, int format, int dither, uint64_t seed, void* out,
+                tts_encode_stats_t* stats);
 // attention diagnostics (alignment.hip): arguments checked by the caller (alignment_plan.h); d_n_sent: the sentence lengths on the
 // device, or null.  Two sets of scratch: the stand-alone entry point runs on the main stream, the statistics of a synthesis call
 // (in_call) behind its decoder -- under the call pipeline on the front stream -- and nothing orders the one behind the other.

@@ -1,6 +1,7 @@
 // C ABI, part 3: the call pipeline -- tts_synthesize (three calls in flight on the main, front and encoder streams, events per
 // call parity, the wide Griffin-Lim launches), its host-memory form and the tickets of tts_wait_host.
 #include "api_internal.h"
+#include "encode_plan.h"
 
 namespace tts_api {
 
@@ -558,6 +559,27 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;
     const size_t stats_bytes = set.ali.enabled ? (size_t)B * sizeof(tts_alignment_stats_t) : 0;
+    // The delivery format (tts_set_output): the float32 rows stay on the device, the resampler takes them -- each over the samples
+    // it holds -- into rows of N_enc samples, and the encoder's codes travel instead.  Everything that may allocate -- the staging
+    // buffers, the ratio's table, the resampled rows, which are a workspace -- is made here, before anything is enqueued.
+    const bool encoded = set.out.enabled, resampled = encoded && set.out.ratio != 1.0, coded = encoded && set.out.format != ENC_F32;
+    const long long N_rows = (long long)sp->hop_length * (shape.Tw - 1);
+    long long N_enc = N_rows;
+    if (encoded && (sp->hop_length < 1 || N_rows < 1 || N_rows > INT32_MAX))
+        return fail(h, TTS_ERR_INVALID, "synthesize_host: a delivery format needs rows of 1 .. 2^31 - 1 samples");
+    if (resampled && (N_enc = resampled_length((int)N_rows, set.out.ratio)) > INT32_MAX)
+        return fail(h, TTS_ERR_INVALID, "synthesize_host: the resampled rows have more than 2^31 - 1 samples");
+    const size_t code_bytes = encoded ? (size_t)B * (size_t)N_enc * (size_t)enc_width(set.out.format) : 0;
+    const size_t rec_bytes = coded ? (size_t)B * sizeof(tts_encode_stats_t) : 0;
+    float* rs_rows = nullptr;
+    if (resampled) {
+        const double* tab_unused = nullptr;
+        if ((rc = resample_table(h, set.out.ratio, &tab_unused))) return rc;
+        if (coded) {   // (without an encoding the resampler writes the set's buffer itself)
+            WS(h, "out.resampled", float, (size_t)B * (size_t)N_enc, rows);
+            rs_rows = rows;
+        }
+    }
     if (!io.out) {
         // The copy stream gets the LOWEST priority: streams of one priority share a few hardware queues in creation order
         // (whatever else the process has created counts; GPU_MAX_HW_QUEUES per priority, as few as 2), and a copy stream that
@@ -571,7 +593,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     }
     // (the sets grow together and the last one last: it fits where all of them do)
     if (ids_bytes > io.ids[2].bytes || n_wav * sizeof(float) > io.wav[2].bytes || n_lin * sizeof(float) > io.lin[2].bytes ||
-        n_ali * sizeof(float) > io.ali[2].bytes || stats_bytes > io.stats[2].bytes) {
+        n_ali * sizeof(float) > io.ali[2].bytes || stats_bytes > io.stats[2].bytes || code_bytes > io.codes[2].bytes ||
+        rec_bytes > io.enc_stats[2].bytes) {
         // growing the buffers: nothing of an earlier call may be in flight
         if ((rc = sync_all(h))) return rc;
         HIPCHK(h, hipStreamSynchronize(io.out));
@@ -581,6 +604,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
             HIPCHK(h, io.lin[i].grow(n_lin * sizeof(float)));
             HIPCHK(h, io.ali[i].grow(n_ali * sizeof(float)));
             HIPCHK(h, io.stats[i].grow(stats_bytes));
+            HIPCHK(h, io.codes[i].grow(code_bytes));
+            HIPCHK(h, io.enc_stats[i].grow(rec_bytes));
         }
         io.reset();
     }
@@ -603,9 +628,38 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     rc = synthesize_impl(h, set, io.ids[par].dev, B, Ts, sp, nullptr, io.wav[par].dev, nullptr, want_ali ? io.ali[par].dev : nullptr,
                          want_lin ? io.lin[par].dev : nullptr, host);
     if (rc) return rc;
+    io.enc_format[par] = -1;
+    if (encoded) {
+        // behind the call's last stage on its stream: the lengths are the host's already (synth_main has read them)
+        std::vector<int32_t>& held = io.enc_held[par];
+        held.assign((size_t)B, (int32_t)N_rows);
+        const bool ragged = set.eos.enabled != 0;
+        if (ragged)
+            for (int b = 0; b < B; ++b) held[(size_t)b] = sp->hop_length * (h->eos.last[(size_t)b] - 1);
+        const float* rows = io.wav[par].dev;
+        if (resampled) {
+            float* dst = coded ? rs_rows : reinterpret_cast<float*>(io.codes[par].dev);
+            if ((rc = resample_impl(h, rows, B, (int)N_rows, ragged ? held.data() : nullptr, set.out.ratio, (int)N_enc, nullptr, dst))) return rc;
+            for (int b = 0; b < B; ++b) held[(size_t)b] = (int32_t)resampled_length(held[(size_t)b], set.out.ratio);
+            rows = dst;
+        }
+        if (coded && (rc = encode_impl(h, rows, B, (int)N_enc, ragged ? held.data() : nullptr, set.out.format, set.out.dither, sp->seed,
+                                       io.codes[par].dev, io.enc_stats[par].dev)))
+            return rc;
+        io.enc_format[par] = set.out.format;
+        io.enc_N[par] = (int)N_enc;
+        io.enc_B[par] = B;
+        io.enc_bytes[par] = code_bytes;
+        io.enc_records[par] = coded;
+    }
     HIPCHK(h, io.ready[par].record(h->stream));
     HIPCHK(h, io.ready[par].wait(io.out));
-    HIPCHK(h, hipMemcpyAsync(io.wav[par].pinned, io.wav[par].dev, n_wav * sizeof(float), hipMemcpyDeviceToHost, io.out));
+    if (encoded) {
+        HIPCHK(h, hipMemcpyAsync(io.codes[par].pinned, io.codes[par].dev, code_bytes, hipMemcpyDeviceToHost, io.out));
+        if (coded) HIPCHK(h, hipMemcpyAsync(io.enc_stats[par].pinned, io.enc_stats[par].dev, rec_bytes, hipMemcpyDeviceToHost, io.out));
+    } else {
+        HIPCHK(h, hipMemcpyAsync(io.wav[par].pinned, io.wav[par].dev, n_wav * sizeof(float), hipMemcpyDeviceToHost, io.out));
+    }
     if (want_lin) HIPCHK(h, hipMemcpyAsync(io.lin[par].pinned, io.lin[par].dev, n_lin * sizeof(float), hipMemcpyDeviceToHost, io.out));
     if (want_ali) HIPCHK(h, hipMemcpyAsync(io.ali[par].pinned, io.ali[par].dev, n_ali * sizeof(float), hipMemcpyDeviceToHost, io.out));
     if (stats_bytes) HIPCHK(h, hipMemcpyAsync(io.stats[par].pinned, io.stats[par].dev, stats_bytes, hipMemcpyDeviceToHost, io.out));
@@ -626,9 +680,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
 }
 
 
-int tts_wait_host(tts_handle_t h, int ticket, const float** wav_host, size_t* n_floats) {
-    DeviceScope dev_scope(h);
-    if (!h || !wav_host) return TTS_ERR_INVALID;
+// What every tts_wait_host* call does first: the ticket's range, the host's wait for its download, the decoder's status
+static int wait_host_ticket(tts_handle_t h, int ticket) {
     auto& io = h->hio;
     if (ticket < 0 || ticket >= io.tickets || ticket < io.tickets - 3)
         return fail(h, TTS_ERR_INVALID, "wait_host: this ticket's buffer has been handed to a later call (at most three calls in flight)");
@@ -650,8 +703,42 @@ int tts_wait_host(tts_handle_t h, int ticket, const float** wav_host, size_t* n_
         }
         return pd_timed_out(h);
     }
+    return TTS_OK;
+}
+
+
+int tts_wait_host(tts_handle_t h, int ticket, const float** wav_host, size_t* n_floats) {
+    DeviceScope dev_scope(h);
+    if (!h || !wav_host) return TTS_ERR_INVALID;
+    const int rc = wait_host_ticket(h, ticket);
+    if (rc) return rc;
+    auto& io = h->hio;
+    const int par = ticket % 3;
+    if (io.enc_format[par] >= 0)
+        return fail(h, TTS_ERR_INVALID, "wait_host: this ticket's call was made with tts_set_output on: its codes are fetched with tts_wait_host_encoded");
     *wav_host = io.wav[par].pinned;
     if (n_floats) *n_floats = io.n_floats[par];
+    return TTS_OK;
+}
+
+
+int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t* bytes, int* format, int* N_out, const int32_t** n_samples,
+                          const tts_encode_stats_t** stats, int* B) {
+    DeviceScope dev_scope(h);
+    if (!h || !data) return TTS_ERR_INVALID;
+    const int rc = wait_host_ticket(h, ticket);
+    if (rc) return rc;
+    auto& io = h->hio;
+    const int par = ticket % 3;
+    if (io.enc_format[par] < 0)
+        return fail(h, TTS_ERR_INVALID, "wait_host_encoded: this ticket's call was made with tts_set_output off: its waveforms are fetched with tts_wait_host");
+    *data = io.codes[par].pinned;
+    if (bytes) *bytes = io.enc_bytes[par];
+    if (format) *format = io.enc_format[par];
+    if (N_out) *N_out = io.enc_N[par];
+    if (n_samples) *n_samples = io.enc_held[par].data();
+    if (stats) *stats = io.enc_records[par] ? io.enc_stats[par].pinned : nullptr;
+    if (B) *B = io.enc_B[par];
     return TTS_OK;
 }
 
@@ -660,8 +747,7 @@ int tts_wait_host_outputs(tts_handle_t h, int ticket, const float** linear_host,
                           size_t* n_align) {
     DeviceScope dev_scope(h);
     if (!h) return TTS_ERR_INVALID;
-    const float* wav = nullptr;
-    const int rc = tts_wait_host(h, ticket, &wav, nullptr);   // same event, same checks (ticket range, decoder status)
+    const int rc = wait_host_ticket(h, ticket);   // same event, same checks (ticket range, decoder status)
     if (rc) return rc;
     auto& io = h->hio;
     const int par = ticket % 3;
@@ -676,8 +762,7 @@ int tts_wait_host_outputs(tts_handle_t h, int ticket, const float** linear_host,
 int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, int* B) {
     DeviceScope dev_scope(h);
     if (!h || !n_frames) return TTS_ERR_INVALID;
-    const float* wav = nullptr;
-    const int rc = tts_wait_host(h, ticket, &wav, nullptr);   // same event, same checks (ticket range, decoder status)
+    const int rc = wait_host_ticket(h, ticket);   // same event, same checks (ticket range, decoder status)
     if (rc) return rc;
     const auto& f = h->hio.frames[ticket % 3];
     *n_frames = f.data();
@@ -689,8 +774,7 @@ int tts_wait_host_frames(tts_handle_t h, int ticket, const int32_t** n_frames, i
 int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignment_stats_t** stats, int* B) {
     DeviceScope dev_scope(h);
     if (!h || !stats) return TTS_ERR_INVALID;
-    const float* wav = nullptr;
-    const int rc = tts_wait_host(h, ticket, &wav, nullptr);   // same event, same checks (ticket range, decoder status)
+    const int rc = wait_host_ticket(h, ticket);   // same event, same checks (ticket range, decoder status)
     if (rc) return rc;
     const auto& io = h->hio;
     const int par = ticket % 3;

@@ -8,12 +8,13 @@ Where the reference fans Griffin-Lim out to 6 worker processes, one utterance ea
 (:185-188), the whole batch is reconstructed by one batched kernel sequence on the GPU.
 """
 import json
+import logging
 import os
 
 import numpy as np
 
 from . import attention_check
-from .._hip import (ALIGNMENT_RECORD, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
+from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, output_is_on, output_ratio, output_setting, resampled_length, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
@@ -82,10 +83,102 @@ def pad_id():
     return int(dataset_params.vocabulary_dict['pad'])
 
 
+log = logging.getLogger(__name__)
+
+
+def output_of(hp, output):
+    """``output`` of the helpers below -- None, a format name ('pcm16', 'pcm8', 'mulaw', 'alaw', 'float32') or ``(format, dither,
+    rate_out)`` with ``dither`` 'tpdf' or None and ``rate_out`` in Hz or None (the model's rate) -- as the engine's checked
+    ``output`` at the model's sampling rate (``_hip.output_setting``), or None where it changes nothing.  A bare name is dithered
+    and keeps the rate.  ValueError for anything else."""
+    if output is None:
+        return None
+    if isinstance(output, (tuple, list)):
+        if len(output) != 3:
+            raise ValueError('output must be None, a format name or (format, dither, rate_out), got {!r}'.format(output))
+        fmt, dither, rate_out = output
+    else:
+        fmt, dither, rate_out = output, 'tpdf', None
+    rate_in = int(getattr(hp, 'hparams', hp).sampling_rate)
+    setting = output_setting((fmt, dither, rate_in, rate_in if rate_out is None else rate_out))
+    return setting if output_is_on(setting) else None
+
+
+def output_rate(hp, setting):
+    """the sampling rate of what a checked ``output`` (``output_of``) delivers"""
+    return int(getattr(hp, 'hparams', hp).sampling_rate) if setting is None or setting[2] == setting[3] else setting[3]
+
+
+def output_encoding(setting):
+    """the ``encoding`` ``audio.io.save_wav`` takes for what a checked ``output`` delivers"""
+    return 'float32' if setting is None else FORMAT_NAMES[setting[0]]
+
+
+def log_clipped(stats, first=0, what='utterance'):
+    """one line per row whose record counts clipped samples"""
+    for b, rec in enumerate(() if stats is None else stats):
+        if rec['clipped'] > 0:
+            log.warning('%s %d: %d of %d samples clipped in the encoder (leave head room: a limiter at -1 dB)', what, first + b + 1,
+                        int(rec['clipped']), int(rec['n']))
+
+
+def deliver_rows(engine, rows, lengths, setting, seed=0, first=0, what='utterance'):
+    """Device rows (B, N) float32, each holding ``lengths[b]`` samples (None: all N), in the delivery format of a checked
+    ``output``: ``Engine.resample`` where the rates differ, then ``Engine.encode`` with the dither's ``seed``, on the device.
+    Returns the codes as host arrays -- a list of B rows cut to what they hold where ``lengths`` is given, else one (B, N') array --
+    and logs every row that clipped.  ``rows`` is left as it was."""
+    ratio = output_ratio(setting)
+    lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.int32)
+    work = rows
+    if ratio != 1.0:
+        N_out = resampled_length(int(rows.shape[-1]), ratio)
+        work = engine.resample(rows, ratio, n_samples=lens, N_out=N_out)
+        if lens is not None:
+            lens = np.array([resampled_length(int(n), ratio) for n in lens], dtype=np.int32)
+    try:
+        if setting[0] != FMT_F32:
+            codes, stats = engine.encode(work, setting[0], dither=setting[1], seed=seed, n_samples=lens)
+            host = codes.to_host()
+            codes.free()
+            log_clipped(stats, first, what)
+        else:
+            host = work.to_host()
+    finally:
+        if work is not rows:
+            work.free()
+    if host.ndim == 1:
+        host = host[None]
+    return host if lens is None else [host[b, :int(n)] for b, n in enumerate(lens)]
+
+
+def deliver(engine, wavs, setting, seed=0, norm=False, what='utterance'):
+    """Host waveforms -- a list of float32 arrays of any lengths -- in the delivery format of a checked ``output``: padded to one
+    batch, uploaded, peak-normalised row by row with ``norm``, then ``deliver_rows``.  Returns the list of code arrays; an empty
+    waveform stays empty."""
+    wavs = [np.asarray(w, dtype=np.float32) for w in wavs]
+    kept = [b for b, w in enumerate(wavs) if len(w)]
+    dtype = np.float32 if setting[0] == FMT_F32 else (np.int16 if FORMAT_NAMES[setting[0]] == 'pcm16' else np.uint8)
+    out = [np.zeros(0, dtype=dtype) for _ in wavs]
+    if kept:
+        lens = np.array([len(wavs[b]) for b in kept], dtype=np.int32)
+        batch = np.zeros((len(kept), int(lens.max())), dtype=np.float32)
+        for r, b in enumerate(kept):
+            batch[r, :lens[r]] = wavs[b]
+        rows = engine.to_device(batch)
+        try:
+            if norm:
+                engine.peak_normalize(rows)
+            for b, codes in zip(kept, deliver_rows(engine, rows, lens, setting, seed, 0, what)):
+                out[b] = codes
+        finally:
+            rows.free()
+    return out
+
+
 class SynthSettings(object):
     """The synthesis settings every helper of this layer takes, checked once -- ValueError before an engine is touched, in the
     order of ``_hip.SETTINGS`` -- and kept as the checked values ``momentum``, ``stop``, ``rate``, ``octaves``, ``phase_init``,
-    ``loud``, ``check_alignment`` and ``limiter``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
+    ``loud``, ``check_alignment``, ``limiter`` and ``output`` (``output_of``).  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
 
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind its last frame whose loudest bin is above that many
@@ -109,10 +202,14 @@ class SynthSettings(object):
     ``limiter``: None (the engine's setting), a ceiling or ``(ceiling, lookahead_ms, oversample)`` -- a look-ahead peak limiter
     (``Engine.limit``) runs last over every utterance on the device, behind the loudness gain or the peak normalisation: no
     sample ends above the ceiling, and what never was keeps its bits.  A bare ceiling looks 5 ms ahead at the interpolated
-    (true) peaks."""
+    (true) peaks.
+    ``output``: None (float32 at the model's rate), a format name -- 'pcm16', 'pcm8', 'mulaw', 'alaw' -- or ``(format, dither,
+    rate_out)``: what the helper hands back (and writes) is in that sample format and at that rate, resampled and encoded on the
+    device behind everything else (``Engine.resample``, ``Engine.encode``: TPDF dither unless ``dither`` is None, saturation;
+    a row that clipped is logged with its count).  The resampler can overshoot a limiter's ceiling: leave head room."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None):
+                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None):
         momentum_thousandths(momentum)
         self.momentum = momentum
         self.stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
@@ -124,12 +221,17 @@ class SynthSettings(object):
         self.loud = loudness_setting(loudness)
         self.check_alignment = check_alignment
         self.limiter = limiter_setting(limiter)
+        self.output = output_of(hp, output)
 
     def engine_keywords(self):
         """the settings as ``Engine.synthesize`` / ``Engine.synthesize_host`` take them"""
         return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
                     phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None,
                     limiter=self.limiter)
+
+    def host_keywords(self):
+        """... and as ``Engine.synthesize_host`` alone takes them: with the delivery format"""
+        return dict(self.engine_keywords(), output=self.output)
 
     def keywords(self):
         """the settings as the helpers of this layer take them (``check_alignment`` apart, which not every one takes)"""
@@ -139,13 +241,14 @@ class SynthSettings(object):
 
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
                      momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                     phase_init='random', loudness=None, check_alignment=False, limiter=None):
+                     phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  The settings from ``momentum`` on: as
     ``SynthSettings`` has them.  With ``stop_at_silence_db`` the result is a list of B waveforms, with ``check_alignment`` it is
-    ``(waveforms, records, verdicts)``."""
+    ``(waveforms, records, verdicts)``.  With an ``output`` the waveforms are that format's codes at its rate, made of the call's
+    device rows (``deliver_rows``; the dither's seed is ``seed``)."""
     s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter)
+                      limiter=limiter, output=output)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -155,7 +258,11 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
                                   loader.mel_mag_max_db, hp.magnitude_power,
                                   hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
                                   init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, **s.engine_keywords())
-    wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if s.stop is not None else out['wav'].to_host()
+    if s.output is not None:
+        held = win_hop * (np.asarray(out['n_frames'], dtype=np.int32) - 1) if s.stop is not None else None
+        wavs = deliver_rows(model.engine, out['wav'], held, s.output, seed)
+    else:
+        wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if s.stop is not None else out['wav'].to_host()
     if check_alignment:
         records = model.engine.synth_alignment_stats(len(sentences))
         return wavs, records, attention_check.verdict(records)
@@ -164,7 +271,8 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
                       want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
-                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False, limiter=None):
+                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False, limiter=None,
+                      output=None):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -177,10 +285,13 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     asked for).  The settings from ``momentum`` on: as ``SynthSettings`` has them.  With ``stop_at_silence_db`` the waveforms
     of a batch are a list of B arrays (views of the pinned rows unless ``copy``), each cut to its own length.  With
     ``check_alignment`` every item additionally carries the batch's alignment records and verdicts, ``(wavs, records,
-    verdicts)`` or ``(wavs, linear, alignments, records, verdicts)``; the 56 bytes per utterance come down with the waveforms."""
+    verdicts)`` or ``(wavs, linear, alignments, records, verdicts)``; the 56 bytes per utterance come down with the waveforms.
+    With an ``output`` the call itself resamples and encodes its rows on the device (tts_set_output: the dither's seed is the
+    call's) and only the codes are downloaded: the waveforms are int16 or uint8 arrays (float32 for 'float32' at another rate) at
+    the output rate, cut to what each row holds with ``stop_at_silence_db``; a row that clipped is logged with its count."""
     # (a generator: a bad setting is refused at its first item, before the engine is touched)
     s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter)
+                      limiter=limiter, output=output)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -190,7 +301,14 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     eng = model.engine
     extra = want_linear or want_alignments
 
+    served = [0]   # utterances answered so far: what a clipped row is logged by
+
     def waveforms(ticket):
+        if s.output is not None:
+            codes, held, stats = eng.wait_host_encoded(ticket, copy=copy)
+            log_clipped(stats, served[0])
+            served[0] += len(held)
+            return codes if s.stop is None else [codes[b, :int(n)] for b, n in enumerate(held)]
         if s.stop is None:
             return eng.wait_host(ticket, copy=copy)
         n_frames = eng.wait_host_frames(ticket)
@@ -212,7 +330,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     for k, ids in enumerate(batches):
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
-                                           want_alignments=want_alignments, **s.engine_keywords()))
+                                           want_alignments=want_alignments, **s.host_keywords()))
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -244,7 +362,7 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
 
 def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
                          stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                         phase_init='random', loudness=None, check_alignment=False, limiter=None):
+                         phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
@@ -253,10 +371,12 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     The other settings from ``momentum`` on: as ``SynthSettings`` has them (a ``speaking_rate`` of 1.2: a fifth faster; a
     ``pitch`` of 4 / 12: four semitones up).  With a ``loudness`` or a ``limiter`` the files hold the waveforms as the device left
     them, not peak-normalised.  With ``check_alignment`` the result is ``(waveforms, report)`` with ``report`` the list of ``{index,
-    verdict, record}`` of ``attention_check.report``, also written to ``alignment_report.json`` beside the wavs."""
+    verdict, record}`` of ``attention_check.report``, also written to ``alignment_report.json`` beside the wavs.  With an
+    ``output`` the files and the returned arrays are in that format and at that rate (16-bit or 8-bit PCM, G.711), peak-normalised
+    on the device ahead of the encoder where the float files would have been on the way to the disk."""
     # (ValueError before anything is loaded)
     s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter)
+                      limiter=limiter, output=output)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -268,7 +388,9 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     max_length = max(sequence_lengths)
     sentences = np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=False, check_alignment=check_alignment, **s.keywords())
+    norm = s.loud is None and s.limiter is None
+    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=norm and s.output is not None, check_alignment=check_alignment,
+                            output=output, **s.keywords())
     report = None
     if check_alignment:
         wavs, records, _verdicts = wavs
@@ -276,7 +398,8 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
         with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
             json.dump(report, f, indent=1)
     for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate, s.loud is None and s.limiter is None)
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, s.output), norm and s.output is None,
+                 encoding=output_encoding(s.output))
     return (list(wavs), report) if check_alignment else list(wavs)
 
 
@@ -390,7 +513,7 @@ def join_list_of_call(piece_text, piece_break, n_frames, first_active, hop, paus
 
 
 def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_ms=FADE_MS, lead_trim=True, max_chars=MAX_CHARS,
-                    n_steps=None, n_iter=None, seed=0, check_alignment=False, **settings):
+                    n_steps=None, n_iter=None, seed=0, check_alignment=False, output=None, peak_normalize=False, **settings):
     """Texts of any length -> one float32 waveform per text (no reference counterpart: tacotron/inference.py:139-200 makes one
     file of at most max_iterations frames per line).
 
@@ -415,6 +538,10 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     them; with a ``loudness`` each part is levelled on its own.  The packing decides which pieces share a call, a call's seed
     and the length its ids are padded to, so the bits of a text may depend on ``batch_size`` and on the texts around it.
 
+    With an ``output`` the JOINED texts, not the pieces, are resampled and encoded (``deliver``: one batch of all the texts, the
+    dither's seed ``seed``, text t dithered as row t of the texts that say something), behind a peak normalisation of each whole
+    text with ``peak_normalize``; the waveforms are then that format's codes at its rate.
+
     Returns the list of waveforms (a text without a piece that speaks: an empty array); with ``check_alignment`` ``(waveforms,
     records, verdicts, piece_text)``: the alignment record and ``attention_check.verdict`` of every piece, in order, and the
     index of the text each piece belongs to."""
@@ -424,6 +551,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     loud = loudness_setting(settings.pop('loudness', None))
     limiter = limiter_setting(settings.pop('limiter', None))
     s = SynthSettings(model, check_alignment=check_alignment, **settings)
+    out_setting = output_of(model, output)
     hp = model.hparams
     pauses = pause_samples(pauses_ms, hp.sampling_rate)
     fade = fade_samples(fade_ms, hp.sampling_rate)
@@ -465,6 +593,10 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
             parts[t].append(wav)
             tails[t] = gap
     wavs = [np.concatenate(p) if p else np.zeros(0, dtype=np.float32) for p in parts]
+    if out_setting is not None:
+        wavs = deliver(eng, wavs, out_setting, seed, norm=peak_normalize, what='text')
+    elif peak_normalize:
+        raise ValueError('synthesize_text: peak_normalize goes with an output (save_wav normalises float32 files)')
     if check_alignment:
         records = np.concatenate(records) if records else np.zeros(0, dtype=ALIGNMENT_RECORD)
         return wavs, records, attention_check.verdict(records), list(piece_text)
@@ -481,7 +613,9 @@ def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0
     if not os.path.isdir(out_dir):
         raise NotADirectoryError('The specified synthesis target folder does not exist.')
     # (ValueError before anything is loaded)
-    settings = {k: kw[k] for k in kw if k not in ('batch_size', 'pauses_ms', 'fade_ms', 'lead_trim', 'max_chars')}
+    settings = {k: kw[k] for k in kw if k not in ('batch_size', 'pauses_ms', 'fade_ms', 'lead_trim', 'max_chars', 'output')}
+    out_setting = output_of(model_params, kw.get('output'))
+    norm = loudness_setting(kw.get('loudness')) is None and limiter_setting(kw.get('limiter')) is None
     if settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB) is None:
         raise ValueError('synthesize_texts: stop_at_silence_db cannot be None')
     SynthSettings(model_params, **dict(settings, stop_at_silence_db=settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB)))
@@ -490,7 +624,8 @@ def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    wavs = synthesize_text(model, raw_texts, dataset, seed=seed, check_alignment=check_alignment, **kw)
+    wavs = synthesize_text(model, raw_texts, dataset, seed=seed, check_alignment=check_alignment,
+                           peak_normalize=norm and out_setting is not None, **kw)
     report = None
     if check_alignment:
         wavs, records, _verdicts, piece_text = wavs
@@ -500,8 +635,8 @@ def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0
         with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
             json.dump(report, f, indent=1)
     for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, model_params.sampling_rate,
-                 loudness_setting(kw.get('loudness')) is None and limiter_setting(kw.get('limiter')) is None and len(wav) > 0)   # (a text that says nothing: an empty file)
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, out_setting),
+                 norm and out_setting is None and len(wav) > 0, encoding=output_encoding(out_setting))   # (a text that says nothing: an empty file)
     return (list(wavs), report) if check_alignment else list(wavs)
 
 
@@ -545,6 +680,7 @@ def main(argv=None):
                                                             [--phase-init random|estimate]
                                                             [--loudness LUFS [--max-peak P]]
                                                             [--limit DB [--limit-lookahead-ms MS] [--sample-peak]]
+                                                            [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment]
                                                             [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
 
@@ -562,6 +698,10 @@ def main(argv=None):
     -1), looking ``--limit-lookahead-ms`` ahead (default 5); the ceiling holds for the interpolated (true) peaks, with
     ``--sample-peak`` for the samples alone.  The files are then not peak-normalised.  With ``--loudness`` and no ``--max-peak``
     the loudness gain may then produce samples up to 4.0 (+12 dB of headroom, which the limiter takes back; untuned).
+    ``--format``: the sample format of the files -- 16-bit PCM, unsigned 8-bit PCM, ITU-T G.711 mu-law or A-law, or the
+    reference's float32 (default) -- at ``--out-rate`` Hz (default: the model's rate; within a factor of 4 of it), encoded on
+    the device with TPDF dither unless ``--no-dither``; e.g. ``--format mulaw --out-rate 8000`` for telephony.  A file whose
+    samples clipped in the encoder is reported with its count: with ``--limit -1`` there is head room for the resampler.
     ``--check-alignment``: the attention diagnostics (``tacotron.attention_check``) -- one JSON line per sentence (index,
     verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts.
     ``--text``: every line of the synthesis file is a text of any length -- sentences, paragraphs (the two characters ``\\n``
@@ -573,7 +713,8 @@ def main(argv=None):
     s = SynthSettings(model_params, args.momentum, args.stop_at_silence, args.silence_keep_ms, args.rate, pitch_semitones=args.pitch,
                       phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
                       check_alignment=args.check_alignment,
-                      limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4))
+                      limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
+                      output=output_option(args))
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -594,10 +735,10 @@ def main(argv=None):
         kw = dict(s.keywords(), stop_at_silence_db=STOP_AT_SILENCE_DB if args.stop_at_silence is None else args.stop_at_silence)
         wavs = synthesize_texts(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
                                 check_alignment=args.check_alignment, max_chars=args.max_chars, pauses_ms=dict(args.pause_ms),
-                                fade_ms=args.fade_ms, **kw)
+                                fade_ms=args.fade_ms, output=output_option(args), **kw)
     else:
         wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                    check_alignment=args.check_alignment, **s.keywords())
+                                    check_alignment=args.check_alignment, output=output_option(args), **s.keywords())
     if args.check_alignment:
         wavs, report = wavs
         for row in report:
@@ -605,6 +746,13 @@ def main(argv=None):
     for i in range(len(wavs)):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
+
+
+def output_option(args):
+    """``--format`` / ``--out-rate`` / ``--no-dither`` as the ``output`` of the helpers above"""
+    if args.format == 'float32' and args.out_rate is None:
+        return None
+    return (args.format, None if args.no_dither else 'tpdf', args.out_rate)
 
 
 def parse_args(argv=None):
@@ -639,6 +787,11 @@ def parse_args(argv=None):
     ap.add_argument('--limit-lookahead-ms', type=float, default=LIMIT_LOOKAHEAD_MS, metavar='MS',
                     help='with --limit: how far the limiter looks ahead (default {:g} ms)'.format(LIMIT_LOOKAHEAD_MS))
     ap.add_argument('--sample-peak', action='store_true', help='with --limit: hold the samples under the ceiling, not the interpolated peaks')
+    ap.add_argument('--format', default='float32', choices=['float32', 'pcm16', 'pcm8', 'mulaw', 'alaw'],
+                    help='the sample format of the wavs: float32 (default, the reference\'s), 16-bit or 8-bit PCM, G.711 mu-law or A-law')
+    ap.add_argument('--out-rate', type=int, default=None, metavar='HZ',
+                    help='the sampling rate of the wavs (default: the model\'s; within a factor of 4 of it), e.g. 8000 for telephony')
+    ap.add_argument('--no-dither', action='store_true', help='with --format: round without the TPDF dither')
     ap.add_argument('--check-alignment', action='store_true',
                     help='attention diagnostics: one JSON line per sentence and {} beside the wavs'.format(REPORT_FILE))
     ap.add_argument('--text', action='store_true',

@@ -11,7 +11,7 @@ import numpy as np
 from .._hip import limiter_lookahead, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
 from . import attention_check
-from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, pad_id, pad_sentence, synthesize_stream
+from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, deliver, pad_id, pad_sentence, synthesize_stream
 from .model import Mode, Tacotron
 from .params import dataset_params, model_params
 
@@ -88,7 +88,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
           silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None,
-          check_alignment=False, limiter=None):
+          check_alignment=False, limiter=None, output=None):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -100,20 +100,24 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     The settings from ``momentum`` on: as ``inference.SynthSettings`` has them -- with a loudness every answer of the stream
     comes at the same level, with a limiter under the same ceiling.  With ``check_alignment`` every answer is ``(waveforms, records, verdicts)`` -- the alignment
     records of the batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip
-    as the waveforms: a bad utterance can be flagged before it is played."""
+    as the waveforms: a bad utterance can be flagged before it is played.  With an ``output`` (``inference.SynthSettings``) every
+    answer is in that sample format and at that rate -- 16-bit PCM, or G.711 at 8 kHz for telephony -- resampled and encoded on
+    the device: pipelined, inside the call, so that only the codes cross the host boundary."""
     # (a generator: a bad setting is refused at its first item, before a model is made)
     s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter)
+                      limiter=limiter, output=output)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
     if not pipelined:   # the reference's loop as it stands: one batch at a time, spectrograms through host memory
-        for sentences in sentence_generator:
+        for k, sentences in enumerate(sentence_generator):
             ids = pre_process_sentences(sentences, dataset)
             fetches = [model.output_linear_spec] + ([model.alignment_history] if check_alignment else [])
             fetched = model.run(fetches, {model.inp_sentences: ids})
             wavs = post_process_spectrograms(fetched[0], model.engine, **s.keywords())
+            if s.output is not None:
+                wavs = deliver(model.engine, wavs, s.output, seed=k)
             if check_alignment:   # (the same kernels as inside a pipelined call, on the alignments this loop fetched anyway)
                 records = model.engine.alignment_stats(fetched[1], n_sent=model.engine.text_lengths(ids, pad_id()))
                 yield wavs, records, attention_check.verdict(records)
@@ -122,7 +126,8 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
-    for item in synthesize_stream(model, batches, peak_normalize=False, copy=True, check_alignment=check_alignment, **s.keywords()):
+    for item in synthesize_stream(model, batches, peak_normalize=False, copy=True, check_alignment=check_alignment, output=output,
+                                  **s.keywords()):
         wavs = item[0] if check_alignment else item
         listed = [wavs[b] for b in range(len(wavs))]
         yield (listed, item[1], item[2]) if check_alignment else listed

@@ -756,6 +756,48 @@ int tts_alignment_stats(tts_handle_t h, const float* alignments, int n_steps_max
  * "alignment".  TTS_ERR_INVALID: a NULL or misaligned pointer, B or Ts < 1. */
 int tts_text_lengths(tts_handle_t h, const int32_t* ids /* DEVICE [B][Ts] */, int B, int Ts, int pad_id, int32_t* n_sent /* DEVICE [B] */);
 
+/* ---- timing marks: a monotonic alignment search ---------------------------------------------- */
+/* When every token is spoken: the best monotone path through an alignment history (no reference counterpart).  The argmax
+ * track of tts_alignment_stats is no segmentation -- it jumps back, and a token's steps need not be contiguous --; this is one:
+ * a non-decreasing position per step that advances by at most J = max_jump (1 .. 15) tokens a step.  alignments DEVICE
+ * [n_steps_max][B][Ts] as the decoder writes them.  For utterance b let S = n_steps[b] and N = n_sent[b]:
+ *   weight   w(s, j), j < N: the float32 element's own bit pattern read as an unsigned integer where the element is greater
+ *            than 0 (+Inf included); 0 where it is a NaN, a zero of either sign or negative.  For positive floats that is a
+ *            monotone piecewise-linear log2 scaled by 2^23: the path of the largest sum is the path of the largest product
+ *            of weights up to 0.086 octave per factor, with no transcendental function and no rounding
+ *   table    int64, unreachable cells -1:  D[0][j] = w(0, j) for j <= min(J, N - 1);
+ *            D[s][j] = w(s, j) + max over 0 <= d <= min(J, j) of D[s-1][j-d] over the reachable predecessors (none: the cell
+ *            is unreachable); among equal predecessors the smallest d wins and is d(s, j)
+ *   path     last = the lowest j that maximises D[S-1][.];  q[S-1] = last, q[s-1] = q[s] - d(s, q[s])
+ *   start    start[b][j] = #{s < S : q[s] < j} for 0 <= j <= N, and S for N < j <= Ts: token j is spoken during the steps
+ *            [start[j], start[j+1])
+ *   path     path[b][s] = q[s], -1 at or behind S
+ * and the record of the utterance, 32 bytes: */
+typedef struct tts_token_times_stats {
+    int64_t score;             /* D[S-1][last] */
+    int32_t n_sent, n_steps;   /* N and S, as used */
+    int32_t last;              /* as above */
+    int32_t jumps;             /* #{s >= 1 : q[s] - q[s-1] > 1}, plus 1 if q[0] > 1 */
+    int32_t skipped;           /* #{j < last : start[j+1] == start[j]}: tokens the path gives no step */
+    int32_t agree;             /* #{s < S : q[s] == pos[s]}, pos the argmax of tts_alignment_stats */
+} tts_token_times_stats_t;
+/* Every quantity is an integer and every sum exact: the result is the same bits whatever B is, wherever the utterance sits in
+ * the batch and however the library cuts the work (the bits of tests/marks_oracle.py); a NaN in one utterance touches no
+ * other.  Columns at or behind n_sent[b] and steps at or behind n_steps[b] are never read.  n_sent: HOST int32 [B] or NULL (all
+ * Ts); n_steps: HOST int32 [B] or NULL (all n_steps_max) -- the lengths travel in the launches, nothing is uploaded.  start
+ * DEVICE int32 [B][Ts + 1]; path DEVICE int32 [B][n_steps_max] or NULL; stats DEVICE [B].  No model needs to be loaded.
+ * Asynchronous on the handle's stream (2 launches per 64 utterances: the positions, then one workgroup per utterance that
+ * fills the table row by row and walks back); profile stage "alignment".
+ * TTS_ERR_INVALID, before anything is enqueued: a NULL alignments, start or stats, B, Ts or n_steps_max < 1, an n_sent[b]
+ * outside 1 .. Ts, an n_steps[b] outside 1 .. n_steps_max, a max_jump outside 1 .. 15, a misaligned buffer (stats: 8 bytes, the
+ * others: 4).  TTS_ERR_UNSUPPORTED: Ts above tts_token_times_max_tokens(). */
+int tts_token_times(tts_handle_t h, const float* alignments, int n_steps_max, int B, int Ts,
+                    const int32_t* n_sent /* HOST [B] or NULL = Ts */, const int32_t* n_steps /* HOST [B] or NULL = n_steps_max */,
+                    int max_jump, int32_t* start /* DEVICE [B][Ts + 1] */, int32_t* path /* DEVICE [B][n_steps_max] or NULL */,
+                    tts_token_times_stats_t* stats /* DEVICE [B] */);
+/* Host only: the most tokens Ts of a call, 1024. */
+int tts_token_times_max_tokens(void);
+
 /* ---- the join: an edit list over the rows of a waveform batch ------------------------------- */
 /* Pieces of the rows of wav DEVICE [B][N], laid one behind the other into the rows of out DEVICE [G][N_out], with pauses or
  * cross-fades between them (no reference counterpart: the reference writes one file per line and stops at max_iterations
@@ -983,6 +1025,32 @@ int tts_synth_alignment_stats(tts_handle_t h, tts_alignment_stats_t* stats_host,
  * valid as long as the ticket's waveform buffer.  TTS_ERR_INVALID also for a ticket whose call was made with the setting off. */
 int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignment_stats_t** stats, int* B);
 
+/* Timing marks of synthesis: when every token of every call is spoken (tts_token_times).  A setting of the HANDLE, off by
+ * default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
+ * tts_synthesize and tts_synthesize_host run tts_text_lengths(pad_id) on the call's device ids behind its encoder -- once: with
+ * tts_set_alignment_stats on as well its lengths, and its pad_id, serve both -- and tts_token_times (n_steps[b] = p->n_steps for
+ * every b, the sentence lengths read from device memory, max_jump in 1 .. 15) right behind the call's decoder and statistics, on
+ * the stream the decoder ran on: no host wait, and nothing changes in what runs beside what.  A call made with alignments ==
+ * NULL writes them to a buffer of the handle's.  start and the records are the bits of tts_token_times on the call's
+ * alignments output with n_sent taken from the ids on the host; waveform, mel, alignments, linear and the alignment records
+ * keep the bits of the call with the setting off.  The steps are the decoder's: what a step is in samples of what the call
+ * delivers -- through the speaking rate, the end-of-speech cut, the output rate -- is host arithmetic (tacotron/marks.py).  The
+ * first call after the setting was switched on is not pipelined (its buffers are new).  A call with Ts above
+ * tts_token_times_max_tokens() is refused with TTS_ERR_UNSUPPORTED before anything is enqueued.
+ * TTS_ERR_INVALID: a NULL handle; enabled with a max_jump outside 1 .. 15 (the setting stays as it was). */
+int tts_set_token_times(tts_handle_t h, int enabled, int pad_id, int max_jump);
+/* The results of the last tts_synthesize / tts_synthesize_host call made on the handle: start_host, HOST int32 [B][Ts + 1],
+ * and stats_host, HOST [B].  Waits on the host until that call's decoder and search have run (not for its Griffin-Lim), then
+ * copies on a side stream.  TTS_ERR_INVALID: a NULL pointer, a B other than that call's, or the last call was made with the
+ * setting off. */
+int tts_synth_token_times(tts_handle_t h, int32_t* start_host, tts_token_times_stats_t* stats_host, int B);
+/* The results of a tts_synthesize_host call: they are downloaded with the waveforms (B x (4 Ts + 36) bytes) and rotate with the
+ * three buffer sets.  Waits as tts_wait_host does (same ticket rules, same reports), then hands out pinned memory of the
+ * handle, valid as long as the ticket's waveform buffer.  B and Ts may be NULL.  TTS_ERR_INVALID also for a ticket whose call
+ * was made with the setting off. */
+int tts_wait_host_token_times(tts_handle_t h, int ticket, const int32_t** start /* [B][Ts + 1] */,
+                              const tts_token_times_stats_t** stats /* [B] */, int* B, int* Ts);
+
 /* The delivery format of tts_synthesize_host: sample format and sampling rate (tts_encode, tts_resample).  A setting of the
  * HANDLE, off by default and read when a call is made.  (TTS_FMT_F32, any dither, r, r) is off: the call as it always was, launch
  * for launch and byte for byte.  Otherwise a tts_synthesize_host call runs, behind its last stage (the limiter, if that is on),
@@ -1017,8 +1085,8 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
  * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
  * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare), "loudness" (tts_loudness, tts_loudness_normalize, stand-alone
- * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, stand-alone or
- * inside a tts_synthesize call with tts_set_alignment_stats on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
+ * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, tts_token_times, stand-alone
+ * or inside a tts_synthesize call with tts_set_alignment_stats or tts_set_token_times on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
  * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
  * tts_synthesize_host call with tts_set_output on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last

@@ -79,6 +79,17 @@ class TtsAlignmentStats(ctypes.Structure):
 ALIGNMENT_RECORD = np.dtype([(name, np.int32) for name, _t in TtsAlignmentStats._fields_[:12]] + [('focus_sum', np.float64)])
 
 
+class TtsTokenTimesStats(ctypes.Structure):
+    """struct tts_token_times_stats (include/sstts_hip.h): an int64 and six int32, 32 bytes."""
+    _fields_ = [('score', c_int64)] + [(name, c_int32) for name in ('n_sent', 'n_steps', 'last', 'jumps', 'skipped', 'agree')]
+
+
+# ... and the same record as a numpy dtype: what Engine.token_times returns an array of
+TOKEN_TIMES_RECORD = np.dtype([('score', np.int64)] + [(name, np.int32) for name, _t in TtsTokenTimesStats._fields_[1:]])
+TOKEN_TIMES_MAX_TOKENS = 1024    # tts_token_times_max_tokens()
+TOKEN_TIMES_MAX_JUMP = 15        # the largest max_jump of tts_token_times
+
+
 class TtsLimitStats(ctypes.Structure):
     """struct tts_limit_stats (include/sstts_hip.h): two int32 and a double, 16 bytes."""
     _fields_ = [('over', c_int32), ('limited', c_int32), ('min_gain', ctypes.c_double)]
@@ -107,6 +118,12 @@ _PROTOTYPES = {
     'tts_alignment_stats': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
     'tts_text_lengths': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    'tts_token_times': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_int, c_void_p, c_void_p,
+                                c_void_p]),
+    'tts_token_times_max_tokens': (c_int, []),
+    'tts_set_token_times': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'tts_synth_token_times': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'tts_wait_host_token_times': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int), POINTER(c_int)]),
     'tts_set_alignment_stats': (c_int, [c_void_p, c_int, c_int]),
     'tts_synth_alignment_stats': (c_int, [c_void_p, c_void_p, c_int]),
     'tts_wait_host_alignment_stats': (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int)]),
@@ -698,6 +715,33 @@ def alignment_lengths(lengths, B, hi, name, bound):
     return _checked_lengths(n, hi, name, bound)
 
 
+def token_times_jump(max_jump, what='token_times'):
+    """``max_jump`` of a tts_token_times call -- the most tokens a decoder step may advance over -- as an int in 1 .. 15;
+    ValueError, raised before a handle is touched, for anything else"""
+    if isinstance(max_jump, (bool, np.bool_)) or not isinstance(max_jump, (int, np.integer)) or not 1 <= int(max_jump) <= TOKEN_TIMES_MAX_JUMP:
+        raise ValueError('{}: max_jump must be an integer in 1 .. {}, got {!r}'.format(what, TOKEN_TIMES_MAX_JUMP, max_jump))
+    return int(max_jump)
+
+
+TOKEN_TIMES_OFF = (False, 0, 4)   # tts_set_token_times as a fresh handle has it; 4: untuned, four characters per decoder step
+
+
+def token_times_setting(token_times):
+    """``token_times`` of the synthesis calls -- None (the handle's setting as it stands), False (off), True (on, pad id 0,
+    max_jump 4) or ``(enabled, pad_id, max_jump)`` -- as None or a checked tuple ``(enabled, pad_id, max_jump)``; ValueError, raised
+    before a handle is touched, for anything else"""
+    if token_times is None:
+        return None
+    if isinstance(token_times, (bool, np.bool_)):
+        return (bool(token_times),) + TOKEN_TIMES_OFF[1:]
+    if isinstance(token_times, (tuple, list)) and len(token_times) == 3:
+        enabled, pad_id, max_jump = token_times
+        if isinstance(enabled, (bool, np.bool_)) and isinstance(pad_id, (int, np.integer)) and not isinstance(pad_id, bool) and \
+                -2 ** 31 <= int(pad_id) < 2 ** 31:
+            return (bool(enabled), int(pad_id), token_times_jump(max_jump, 'token_times'))
+    raise ValueError('token_times must be None, a bool or (enabled, pad_id, max_jump), got {!r}'.format(token_times))
+
+
 JOIN_MAX_PIECES = 4096      # tts_join_max_pieces()
 JOIN_MAX_FADE = 1 << 20     # tts_join_max_fade()
 JOIN_MAX_SAMPLES = 1 << 33  # the most output samples G * N_out of a call
@@ -930,6 +974,10 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
 #     rate_out)`` (tts_set_output, off unless ``set_output`` changed it): ``synthesize_host`` alone -- the call's final rows are resampled and encoded on the device, behind the limiter, and only the
 #     codes and their records travel to the host (``wait_host_encoded``).  ``synthesize`` hands out device rows: ``encode`` is
 #     its callers' to call.
+#   ``token_times`` (the one row of MARK_SETTINGS, behind those nine): False, True or ``(enabled, pad_id, max_jump)``
+#     (tts_set_token_times, off unless ``set_token_times`` changed it): the call also searches its alignments for the best monotone
+#     path behind its decoder, with no host wait; ``synth_token_times(B)`` / ``wait_host_token_times`` fetch the step every token
+#     starts at.  Nothing else of the call changes.
 # A row: the keyword, the Engine attribute that mirrors the handle's value, the handle's initial value, the check that turns
 # the keyword into the mirror's value (ValueError before a handle is touched), and how a value is applied -- a ``set_option``
 # key or a call of the engine's ``set_*`` method.
@@ -949,6 +997,10 @@ SETTINGS = (
 HOST_SETTINGS = (
     Setting('output', '_output', OUTPUT_OFF, output_setting, lambda engine, v: engine.set_output(v)),
 )
+# ... and the timing marks, a table of their own behind both: checked last, applied last, put back first
+MARK_SETTINGS = (
+    Setting('token_times', '_token_times', TOKEN_TIMES_OFF, token_times_setting, lambda engine, v: engine.set_token_times(*v)),
+)
 
 
 class _Settings(object):
@@ -959,7 +1011,7 @@ class _Settings(object):
 
     def __init__(self, engine, per_call):
         self.engine = engine
-        self.rows = [row for row in SETTINGS + HOST_SETTINGS if row.keyword in per_call]
+        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS if row.keyword in per_call]
         self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
 
     def __getitem__(self, keyword):
@@ -1081,7 +1133,7 @@ class Engine(object):
 
     def _init_settings(self):
         """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
-        for row in SETTINGS + HOST_SETTINGS:
+        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS:
             setattr(self, row.mirror, row.initial)
 
     def _settings(self, **per_call):
@@ -1772,6 +1824,36 @@ class Engine(object):
                 a.free()
         return out if len(out) > 1 else out[0]
 
+    def set_token_times(self, enabled, pad_id=0, max_jump=4):
+        """tts_set_token_times: the handle's setting, read by every synthesize / synthesize_host call made after it.  On, every
+        call also searches its alignments for the best monotone path (``token_times``), the sentence lengths taken from its ids
+        with ``pad_id`` as the padding: ``synth_token_times`` / ``wait_host_token_times`` fetch the results."""
+        setting = token_times_setting((bool(enabled), pad_id, max_jump))
+        self._check(self.lib.tts_set_token_times(self.handle, 1 if setting[0] else 0, setting[1], setting[2]))
+        self._token_times = setting
+
+    def synth_token_times(self, B):
+        """tts_synth_token_times: ``(start, stats)`` -- int32 (B, Ts + 1) and (B,) of ``TOKEN_TIMES_RECORD``, host arrays -- of the
+        last ``synthesize`` / ``synthesize_host`` call made on the handle with the timing marks on.  Waits for that call's
+        decoder, not for its Griffin-Lim."""
+        Ts = getattr(self, '_token_times_Ts', None)
+        if Ts is None:
+            raise ValueError('synth_token_times: no synthesize call has been made with token_times on')
+        start = np.zeros((int(B), Ts + 1), dtype=np.int32)
+        stats = np.zeros(int(B), dtype=TOKEN_TIMES_RECORD)
+        self._check(self.lib.tts_synth_token_times(self.handle, start.ctypes.data, stats.ctypes.data, int(B)))
+        return start, stats
+
+    def wait_host_token_times(self, ticket):
+        """``(start, stats)`` (copies) of a ``synthesize_host`` call made with the timing marks on: tts_wait_host_token_times.
+        Waits like ``wait_host`` and does not consume the ticket."""
+        ps, pr = c_void_p(), c_void_p()
+        n, ts = c_int(0), c_int(0)
+        self._check(self.lib.tts_wait_host_token_times(self.handle, int(ticket), byref(ps), byref(pr), byref(n), byref(ts)))
+        start = np.frombuffer(ctypes.string_at(ps.value, n.value * (ts.value + 1) * 4), dtype=np.int32).reshape(n.value, ts.value + 1).copy()
+        stats = np.frombuffer(ctypes.string_at(pr.value, n.value * TOKEN_TIMES_RECORD.itemsize), dtype=TOKEN_TIMES_RECORD).copy()
+        return start, stats
+
     def text_lengths(self, ids, pad_id=0):
         """tts_text_lengths: the sentence lengths of padded ids (B, Ts) int32, host or device -- 1 + the last position that does
         not hold ``pad_id``, 1 for a row of padding -- as an int32 host array (B,)."""
@@ -1786,6 +1868,38 @@ class Engine(object):
         n = out.to_host()
         out.free()
         return n
+
+    def token_times(self, alignments, n_sent=None, n_steps=None, max_jump=4, want_path=False):
+        """tts_token_times: when every token is spoken -- the best monotone path through an alignment history, a position per
+        step that never goes back and advances by at most ``max_jump`` (1 .. 15) tokens a step.  ``alignments`` (n_steps_max, B,
+        Ts) float32 as the decoder writes them, a host array or a device buffer; ``n_sent`` / ``n_steps`` as ``alignment_stats``
+        takes them -- columns and steps at or behind them are never read.  Returns ``start``, the int32 host array (B, Ts + 1) --
+        token j of utterance b is spoken during the decoder steps ``start[b, j] .. start[b, j + 1]`` -- and a host array (B,) of
+        ``TOKEN_TIMES_RECORD`` -- score, n_sent, n_steps, last, jumps, skipped, agree --, then with ``want_path`` the path int32
+        (B, n_steps_max) (-1 behind an utterance's steps).  ``max_jump = 4`` is untuned: four characters per step of r frames.
+        include/sstts_hip.h has the definition: everything is the bits of tests/marks_oracle.py.  ``tacotron.marks`` turns
+        ``start`` into times."""
+        shape = tuple(int(d) for d in alignments.shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError('token_times: alignments (n_steps_max, B, Ts) are needed, got shape {}'.format(shape))
+        S, B, Ts = shape
+        ns = alignment_lengths(n_sent, B, Ts, 'n_sent', 'Ts')
+        nt = alignment_lengths(n_steps, B, S, 'n_steps', 'n_steps_max')
+        J = token_times_jump(max_jump)
+        if Ts > TOKEN_TIMES_MAX_TOKENS:
+            raise ValueError('token_times: Ts = {} is above the {} tokens of a table'.format(Ts, TOKEN_TIMES_MAX_TOKENS))
+        p_ali, _k = self._in(alignments, np.float32)
+        start = self.empty((B, Ts + 1), np.int32)
+        stats = self.empty((B,), TOKEN_TIMES_RECORD)
+        path = self.empty((B, S), np.int32) if want_path else None
+        self._check_or_free(self.lib.tts_token_times(self.handle, p_ali, S, B, Ts, _int32_ptr(ns), _int32_ptr(nt), J, start.data_ptr(),
+                                                     path.data_ptr() if path is not None else None, stats.data_ptr()), start, stats, path)
+        out = ()
+        for a in (start, stats, path):
+            if a is not None:
+                out += (a.to_host(),)
+                a.free()
+        return out
 
     def synth_alignment_stats(self, B):
         """tts_synth_alignment_stats: the B records (``ALIGNMENT_RECORD``, a host array) of the last ``synthesize`` /
@@ -1969,9 +2083,9 @@ class Engine(object):
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
-                   alignment_stats=None, limiter=None, **refused):
+                   alignment_stats=None, limiter=None, token_times=None, **refused):
         """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` to
-        ``limiter`` hold for this call alone, as SETTINGS has them.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
+        ``limiter`` hold for this call alone, as SETTINGS has them, and ``token_times`` as MARK_SETTINGS has it.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
         call's rows stay on the device, where ``resample`` and ``encode`` take them."""
         if 'output' in refused:
             raise ValueError('synthesize: no output= here -- the waveforms stay on the device as float32; resample and encode them there '
@@ -1979,7 +2093,8 @@ class Engine(object):
         if refused:
             raise TypeError('synthesize() got an unexpected keyword argument {!r}'.format(sorted(refused)[0]))
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
-                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter)
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter,
+                              token_times=token_times)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call, o_call = call['speaking_rate'], call['pitch']
@@ -2017,6 +2132,8 @@ class Engine(object):
         out = dict(wav=wav, mel=mel, alignments=ali, linear=lin)
         if call['stop_at_silence'][0]:
             out['n_frames'] = self.synth_frames(B)
+        if call['token_times'][0]:
+            self._token_times_Ts = Ts   # (what synth_token_times sizes its rows by)
         return out
 
     def synth_frames(self, B):
@@ -2029,15 +2146,17 @@ class Engine(object):
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
                         speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None,
-                        output=None):
+                        output=None, token_times=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         The nine settings from ``momentum`` on hold for this call alone, as SETTINGS and HOST_SETTINGS have them: they are read when the call is
         made, not when its work runs.  A call made with an ``output`` is fetched with ``wait_host_encoded``, not ``wait_host``.  A call that stops at silence returns once its post-net has run (the lengths:
-        ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``)."""
+        ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``), and so do the
+        timing marks of a call made with ``token_times`` (MARK_SETTINGS; ``wait_host_token_times``)."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
-                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output)
+                              phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output,
+                              token_times=token_times)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape
@@ -2047,6 +2166,8 @@ class Engine(object):
         T_wav, _T_gl = synth_frame_counts(n_steps * self.cfg.reduction, call['speaking_rate'], 0.0)   # (the pitch changes no shape)
         with call:
             self._check(self.lib.tts_synthesize_host(self.handle, ids.ctypes.data, B, Ts, byref(sp), byref(t)))
+        if call['token_times'][0]:
+            self._token_times_Ts = Ts
         self._host_shapes[t.value] = (B, hop_length * (T_wav - 1))
         self._host_out_shapes[t.value] = ((B, n_steps * self.cfg.reduction, 1 + self.cfg.n_fft // 2), (n_steps, B, Ts))
         return t.value

@@ -265,6 +265,28 @@ int alignment_impl(tts_handle_t h, const float* alignments, int n_steps_max, int
     return TTS_OK;
 }
 
+// The positions alone -- pos[s] for s < n_steps[b], what tts_token_times compares its path with -- in the scratch alignment_impl
+// would use: one launch per 64 utterances, counted by the caller's profile scope.  run false: alignment_impl has just left them there.
+int alignment_positions_impl(tts_handle_t h, bool in_call, const float* alignments, int n_steps_max, int B, int Ts, const int32_t* n_sent,
+                             const int32_t* n_steps, const int32_t* d_n_sent, bool run, const int32_t** pos) {
+    AlignScratch s;
+    const int rc = alignment_scratch(h, in_call, B, n_steps_max, Ts, &s);
+    if (rc) return rc;
+    *pos = s.pos;
+    for (int b0 = 0; run && b0 < B; b0 += ALIGN_UTTS) {
+        const int nb = std::min(ALIGN_UTTS, B - b0);
+        AlignLens lens;
+        fill_lengths(lens.n_sent, n_sent, b0, nb, Ts);
+        fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
+        int longest = 0;
+        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n_steps[b]);
+        hipLaunchKernelGGL(align_rows_kernel, dim3(align_row_blocks(longest), nb), dim3(64 * ALIGN_ROWS), 0, h->stream, alignments, B, Ts, b0,
+                           lens, d_n_sent, longest, n_steps_max, s.pos, s.peak, s.off);
+        HIPCHK(h, hipGetLastError());
+    }
+    return TTS_OK;
+}
+
 int text_lengths_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, int pad_id, int32_t* n_sent) {
     ProfScope ps(h, ST_ALIGNMENT, 1);
     hipLaunchKernelGGL(text_lengths_kernel, dim3((B + ALIGN_ROWS - 1) / ALIGN_ROWS), dim3(64 * ALIGN_ROWS), 0, h->stream, ids, B, Ts, pad_id,

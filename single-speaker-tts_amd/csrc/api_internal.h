@@ -166,6 +166,9 @@ struct StageArgs {
     Signal* enc_done = nullptr;
     // tts_synthesize_host with tts_set_alignment_stats on: where the call's records go on the device (its buffer set's)
     tts_alignment_stats_t* stats_out = nullptr;
+    // ... and with tts_set_token_times on: where its start steps and records go
+    int32_t* tt_start_out = nullptr;
+    tts_token_times_stats_t* tt_stats_out = nullptr;
 };
 
 // tts_synthesize pipelining: encoder + decoder (latency bound, few CUs) of call k+1 run on
@@ -252,6 +255,11 @@ struct HostIo {
     // write the device side, the download takes it down with the waveforms; n_stats: the call's B, 0 = made with the setting off
     StagedBuf<tts_alignment_stats_t> stats[3];
     int n_stats[3] = {0, 0, 0};
+    // the timing marks of this set's call (tts_set_token_times; tts_wait_host_token_times), likewise; n_tt: the call's B, 0 = made
+    // with the setting off; tt_Ts: its Ts
+    StagedBuf<int32_t> tt_start[3];
+    StagedBuf<tts_token_times_stats_t> tt_stats[3];
+    int n_tt[3] = {0, 0, 0}, tt_Ts[3] = {0, 0, 0};
     // the delivery format of this set's call (tts_set_output; tts_wait_host_encoded): the codes -- or the resampled float32 rows --
     // and the encoder's records, which travel instead of the float32 rows; enc_format < 0: made with the setting off.  The rows
     // the call synthesises are the set's `wav` as ever; what the resampler makes of them for the encoder is the workspace "out.resampled"
@@ -277,7 +285,7 @@ struct HostIo {
 };
 
 // The synthesis settings of a handle: what tts_set_end_of_speech, tts_set_speaking_rate, tts_set_pitch, tts_set_loudness,
-// tts_set_limiter, tts_set_alignment_stats, tts_set_output and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
+// tts_set_limiter, tts_set_alignment_stats, tts_set_token_times, tts_set_output and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
 // copy when the call is made and read nothing but that copy from then on; with every setting off the call enqueues what it
 // always did.  (The stand-alone Griffin-Lim calls have no such copy: they read the handle's momentum and start.)
 struct SynthSettings {
@@ -304,6 +312,11 @@ struct SynthSettings {
         bool enabled = false;
         int pad_id = 0;
     } ali;
+    struct {
+        bool enabled = false;
+        int pad_id = 0;
+        int max_jump = 4;
+    } tt;
     // the delivery format of tts_synthesize_host (tts_set_output): enabled = an encoding or a ratio other than 1
     struct {
         bool enabled = false;
@@ -474,8 +487,16 @@ struct tts_handle_s {
         const tts_alignment_stats_t* last_dev = nullptr;
         int last_B = 0;
         Signal done;
-        hipStream_t copy = nullptr;   // tts_synth_alignment_stats copies on it, behind `done` alone
+        hipStream_t copy = nullptr;   // tts_synth_alignment_stats and tts_synth_token_times copy on it, behind `done` alone
     } ali;
+
+    // timing marks, likewise: the start steps and records of the last call on the device (null: made with the setting off)
+    struct {
+        const int32_t* last_start = nullptr;
+        const tts_token_times_stats_t* last_stats = nullptr;
+        int last_B = 0, last_Ts = 0;
+        Signal done;
+    } tt;
 
     // the per-utterance lengths of the last tts_synthesize call (synth_plan.h): Griffin-Lim and the resampler are given them
     SynthLengths syn_lens;
@@ -661,6 +682,14 @@ struct AlignScratch { int32_t* pos; float* peak; unsigned char* off; int32_t* du
 int alignment_scratch(tts_handle_t h, bool in_call, int B, int n_steps_max, int Ts, AlignScratch* s);
 int alignment_impl(tts_handle_t h, const float* alignments, int n_steps_max, int B, int Ts, const int32_t* n_sent, const int32_t* n_steps,
                    const int32_t* d_n_sent, tts_alignment_stats_t* stats, int32_t* durations, int32_t* pos, float* peak);
+int alignment_positions_impl(tts_handle_t h, bool in_call, const float* alignments, int n_steps_max, int B, int Ts, const int32_t* n_sent,
+                             const int32_t* n_steps, const int32_t* d_n_sent, bool run, const int32_t** pos);
+// timing marks (token_times.hip): arguments checked by the caller (token_times_plan.h); d_n_sent and the two sets of scratch as
+// above.  start, stats: a synthesis call's results where its caller gave no room for them (null in the stand-alone set)
+struct TokenTimesScratch { int32_t* path; unsigned char* dir; int32_t* start; tts_token_times_stats_t* stats; };
+int token_times_scratch(tts_handle_t h, bool in_call, int B, int n_steps_max, int Ts, TokenTimesScratch* s);
+int token_times_impl(tts_handle_t h, const float* alignments, int n_steps_max, int B, int Ts, const int32_t* n_sent, const int32_t* n_steps,
+                     const int32_t* d_n_sent, bool have_pos, int max_jump, int32_t* start, int32_t* path, tts_token_times_stats_t* stats);
 int text_lengths_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, int pad_id, int32_t* n_sent);
 int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t* n_samples, double rho, int N_out, const int32_t* keep_cap,
                   float* out);

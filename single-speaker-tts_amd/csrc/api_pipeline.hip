@@ -2,6 +2,7 @@
 // call parity, the wide Griffin-Lim launches), its host-memory form and the tickets of tts_wait_host.
 #include "api_internal.h"
 #include "encode_plan.h"
+#include "token_times_plan.h"
 
 namespace tts_api {
 
@@ -72,6 +73,9 @@ struct SynthCall {
     // the caller's buffer or the handle's -- right behind the decoder, on the decoder's stream
     int32_t* ali_n_sent = nullptr;             // this call parity's lengths on the device (workspace "syn.ali_nsent")
     tts_alignment_stats_t* ali_stats = nullptr;   // where the records go: the host form's buffer set, or workspace "syn.ali_stats"
+    // timing marks: the search runs behind the statistics, on the same alignments and lengths
+    int32_t* tt_start = nullptr;                   // where its results go: the host form's buffer set, or the stage's scratch
+    tts_token_times_stats_t* tt_stats = nullptr;
 };
 
 // h->stream is "the stream I enqueue on" for every stage and for ProfScope: the front side of a pipelined call aims it at
@@ -154,7 +158,7 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     LimScratch lim;
     if (k.set.loud.enabled && (rc = loudness_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate, &loud))) return rc;
     if (k.set.lim.enabled && (rc = limiter_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), &lim))) return rc;
-    if (k.set.ali.enabled) {
+    if (k.set.ali.enabled || k.set.tt.enabled) {
         // One alignment buffer and one set of scratch: the statistics of a call run behind its decoder on the decoder's stream,
         // in front of whatever lets the next decoder start.  The sentence lengths are written behind the ENCODER, which may run a
         // call ahead on its own stream: one set per call parity, like `memory`.
@@ -164,13 +168,21 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         }
         WS(h, "syn.ali_nsent", int32_t, 2 * (size_t)B, ali_ns);
         k.ali_n_sent = ali_ns + (size_t)parity * B;
+        AlignScratch ali;   // (the search takes the positions from it, whoever leaves them there)
+        if ((rc = alignment_scratch(h, true, B, sp->n_steps, Ts, &ali))) return rc;
+    }
+    if (k.set.tt.enabled) {
+        TokenTimesScratch tt;
+        if ((rc = token_times_scratch(h, true, B, sp->n_steps, Ts, &tt))) return rc;
+        k.tt_start = k.host->tt_start_out ? k.host->tt_start_out : tt.start;
+        k.tt_stats = k.host->tt_stats_out ? k.host->tt_stats_out : tt.stats;
+    }
+    if (k.set.ali.enabled) {
         k.ali_stats = k.host->stats_out;
         if (!k.ali_stats) {
             WS(h, "syn.ali_stats", tts_alignment_stats_t, (size_t)B, ali_st);
             k.ali_stats = ali_st;
         }
-        AlignScratch ali;
-        if ((rc = alignment_scratch(h, true, B, sp->n_steps, Ts, &ali))) return rc;
     }
     // (estimated initial phases, option "gl_init": the estimate's buffers, for the frames Griffin-Lim reconstructs from)
     PhaseScratch est;
@@ -334,7 +346,10 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
     }
     if ((rc = encoder_impl(h, k.ids, B, Ts, k.memory))) return rc;
     // (attention diagnostics: the sentence lengths, where the ids are certainly in place -- beside the encoder that reads them)
-    if (k.set.ali.enabled && (rc = text_lengths_impl(h, k.ids, B, Ts, k.set.ali.pad_id, k.ali_n_sent))) return rc;
+    // (... once, for the statistics and the timing marks alike: with both on, the statistics' padding is the one)
+    if ((k.set.ali.enabled || k.set.tt.enabled) &&
+        (rc = text_lengths_impl(h, k.ids, B, Ts, k.set.ali.enabled ? k.set.ali.pad_id : k.set.tt.pad_id, k.ali_n_sent)))
+        return rc;
     if (k.host->enc_done) HIPCHK(h, k.host->enc_done->record(h->stream));
     if (k.pipelined && k.keys_ahead) {
         ProfScope ps(h, ST_ENCODER, 1);
@@ -365,6 +380,17 @@ static int synth_front(tts_handle_t h, SynthCall& k, hipStream_t enc_on) {
         HIPCHK(h, h->ali.done.record(h->stream));
         h->ali.last_dev = k.ali_stats;
         h->ali.last_B = B;
+    }
+    if (k.set.tt.enabled) {
+        // Timing marks: the search, behind the statistics whose positions it reads, in front of the records below like them
+        if ((rc = token_times_impl(h, k.align_out, k.sp->n_steps, B, Ts, nullptr, nullptr, k.ali_n_sent, k.set.ali.enabled, k.set.tt.max_jump,
+                                   k.tt_start, nullptr, k.tt_stats)))
+            return rc;
+        HIPCHK(h, h->tt.done.record(h->stream));
+        h->tt.last_start = k.tt_start;
+        h->tt.last_stats = k.tt_stats;
+        h->tt.last_B = B;
+        h->tt.last_Ts = Ts;
     }
     if (k.pipelined) HIPCHK(h, pl.dec_done[parity].record(pl.front));
     else if (pl.front) HIPCHK(h, pl.serial_done.record(on.main_stream));
@@ -511,6 +537,9 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
         (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
         return fail(h, TTS_ERR_INVALID, "synthesize: the limiter needs rows of 1 .. 2^31 - 1 samples");
     h->ali.last_dev = nullptr;   // (the records of a call before this one are no longer "the last call's")
+    h->tt.last_start = nullptr;
+    h->tt.last_stats = nullptr;
+    if (set.tt.enabled && Ts > TT_MAX_TOKENS) return fail(h, TTS_ERR_UNSUPPORTED, "synthesize: token times: " + token_times_unsupported(Ts));
     if ((rc = synth_workspaces(h, k))) return rc;
     if (k.pipelined && (rc = synth_streams(h))) return rc;
     hipStream_t enc_on = nullptr;
@@ -559,6 +588,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;
     const size_t stats_bytes = set.ali.enabled ? (size_t)B * sizeof(tts_alignment_stats_t) : 0;
+    const size_t tt_start_bytes = set.tt.enabled ? (size_t)B * (size_t)(Ts + 1) * sizeof(int32_t) : 0;
+    const size_t tt_stats_bytes = set.tt.enabled ? (size_t)B * sizeof(tts_token_times_stats_t) : 0;
     // The delivery format (tts_set_output): the float32 rows stay on the device, the resampler takes them -- each over the samples
     // it holds -- into rows of N_enc samples, and the encoder's codes travel instead.  Everything that may allocate -- the staging
     // buffers, the ratio's table, the resampled rows, which are a workspace -- is made here, before anything is enqueued.
@@ -594,7 +625,7 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     // (the sets grow together and the last one last: it fits where all of them do)
     if (ids_bytes > io.ids[2].bytes || n_wav * sizeof(float) > io.wav[2].bytes || n_lin * sizeof(float) > io.lin[2].bytes ||
         n_ali * sizeof(float) > io.ali[2].bytes || stats_bytes > io.stats[2].bytes || code_bytes > io.codes[2].bytes ||
-        rec_bytes > io.enc_stats[2].bytes) {
+        rec_bytes > io.enc_stats[2].bytes || tt_start_bytes > io.tt_start[2].bytes || tt_stats_bytes > io.tt_stats[2].bytes) {
         // growing the buffers: nothing of an earlier call may be in flight
         if ((rc = sync_all(h))) return rc;
         HIPCHK(h, hipStreamSynchronize(io.out));
@@ -606,6 +637,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
             HIPCHK(h, io.stats[i].grow(stats_bytes));
             HIPCHK(h, io.codes[i].grow(code_bytes));
             HIPCHK(h, io.enc_stats[i].grow(rec_bytes));
+            HIPCHK(h, io.tt_start[i].grow(tt_start_bytes));
+            HIPCHK(h, io.tt_stats[i].grow(tt_stats_bytes));
         }
         io.reset();
     }
@@ -624,6 +657,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     host.upload.done = &io.h2d[par];
     host.enc_done = &io.enc[par];
     host.stats_out = stats_bytes ? io.stats[par].dev : nullptr;
+    host.tt_start_out = tt_start_bytes ? io.tt_start[par].dev : nullptr;
+    host.tt_stats_out = tt_stats_bytes ? io.tt_stats[par].dev : nullptr;
     // (the optional outputs of this set were last read by the download of the call three back: same event as the waveforms)
     rc = synthesize_impl(h, set, io.ids[par].dev, B, Ts, sp, nullptr, io.wav[par].dev, nullptr, want_ali ? io.ali[par].dev : nullptr,
                          want_lin ? io.lin[par].dev : nullptr, host);
@@ -663,7 +698,13 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     if (want_lin) HIPCHK(h, hipMemcpyAsync(io.lin[par].pinned, io.lin[par].dev, n_lin * sizeof(float), hipMemcpyDeviceToHost, io.out));
     if (want_ali) HIPCHK(h, hipMemcpyAsync(io.ali[par].pinned, io.ali[par].dev, n_ali * sizeof(float), hipMemcpyDeviceToHost, io.out));
     if (stats_bytes) HIPCHK(h, hipMemcpyAsync(io.stats[par].pinned, io.stats[par].dev, stats_bytes, hipMemcpyDeviceToHost, io.out));
+    if (tt_start_bytes) {
+        HIPCHK(h, hipMemcpyAsync(io.tt_start[par].pinned, io.tt_start[par].dev, tt_start_bytes, hipMemcpyDeviceToHost, io.out));
+        HIPCHK(h, hipMemcpyAsync(io.tt_stats[par].pinned, io.tt_stats[par].dev, tt_stats_bytes, hipMemcpyDeviceToHost, io.out));
+    }
     io.n_stats[par] = stats_bytes ? B : 0;
+    io.n_tt[par] = tt_start_bytes ? B : 0;
+    io.tt_Ts[par] = Ts;
     io.n_lin[par] = n_lin;
     io.n_ali[par] = n_ali;
     io.frames[par] = h->eos.last;   // (the call has read them: synth_main)
@@ -781,6 +822,22 @@ int tts_wait_host_alignment_stats(tts_handle_t h, int ticket, const tts_alignmen
     if (!io.n_stats[par]) return fail(h, TTS_ERR_INVALID, "wait_host_alignment_stats: this ticket's call was not made with tts_set_alignment_stats on");
     *stats = io.stats[par].pinned;
     if (B) *B = io.n_stats[par];
+    return TTS_OK;
+}
+
+
+int tts_wait_host_token_times(tts_handle_t h, int ticket, const int32_t** start, const tts_token_times_stats_t** stats, int* B, int* Ts) {
+    DeviceScope dev_scope(h);
+    if (!h || !start || !stats) return TTS_ERR_INVALID;
+    const int rc = wait_host_ticket(h, ticket);   // same event, same checks (ticket range, decoder status)
+    if (rc) return rc;
+    const auto& io = h->hio;
+    const int par = ticket % 3;
+    if (!io.n_tt[par]) return fail(h, TTS_ERR_INVALID, "wait_host_token_times: this ticket's call was not made with tts_set_token_times on");
+    *start = io.tt_start[par].pinned;
+    *stats = io.tt_stats[par].pinned;
+    if (B) *B = io.n_tt[par];
+    if (Ts) *Ts = io.tt_Ts[par];
     return TTS_OK;
 }
 

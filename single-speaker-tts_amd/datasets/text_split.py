@@ -91,3 +91,23 @@ def split_text(text, max_chars=MAX_CHARS, abbreviations=()):
                 out.append((piece, brk or 'sentence'))
         out[-1] = (out[-1][0], 'paragraph')
     return out
+
+
+def split_text_spans(text, max_chars=MAX_CHARS, abbreviations=()):
+    """``split_text`` with the place of every piece in the raw text: a list of ``(piece, break, start, end)`` whose first two
+    fields are ``split_text``'s output, and ``text[start:end]`` with its whitespace runs collapsed is the piece.  The pieces lie
+    in the text in order and do not overlap; what lies between them is whitespace."""
+    out, at = [], 0
+    for piece, brk in split_text(text, max_chars, abbreviations):
+        while text[at].isspace():
+            at += 1
+        start = at
+        for c in piece:
+            if c == ' ':                      # one blank of a piece is a whitespace run of the text
+                while text[at].isspace():
+                    at += 1
+            else:
+                assert text[at] == c, (piece, at)
+                at += 1
+        out.append((piece, brk, start, at))
+    return out

@@ -13,12 +13,12 @@ import os
 
 import numpy as np
 
-from . import attention_check
-from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, output_is_on, output_ratio, output_setting, resampled_length, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
+from . import attention_check, marks as marks_
+from .._hip import (ALIGNMENT_RECORD, synth_frame_counts, token_times_jump, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, output_is_on, output_ratio, output_setting, resampled_length, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
-from ..datasets.text_split import BREAKS, MAX_CHARS, abbreviations_of, split_text
+from ..datasets.text_split import BREAKS, MAX_CHARS, abbreviations_of, split_text, split_text_spans
 from .model import Mode, Tacotron
 from .params import dataset_params, inference_params, model_params
 
@@ -206,10 +206,15 @@ class SynthSettings(object):
     ``output``: None (float32 at the model's rate), a format name -- 'pcm16', 'pcm8', 'mulaw', 'alaw' -- or ``(format, dither,
     rate_out)``: what the helper hands back (and writes) is in that sample format and at that rate, resampled and encoded on the
     device behind everything else (``Engine.resample``, ``Engine.encode``: TPDF dither unless ``dither`` is None, saturation;
-    a row that clipped is logged with its count).  The resampler can overshoot a limiter's ceiling: leave head room."""
+    a row that clipped is logged with its count).  The resampler can overshoot a limiter's ceiling: leave head room.
+    ``marks``: None, 'word' or 'char' -- the call also searches its alignments for the best monotone path on the device
+    (``Engine.token_times``, at most ``marks_max_jump`` tokens a decoder step; 4, untuned) and the helper answers with timing
+    marks as its last element (``tacotron.marks``): when every word -- and with 'char' every character -- is spoken, in
+    milliseconds and in samples of what is delivered."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None):
+                 phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None,
+                 marks=None, marks_max_jump=4):
         momentum_thousandths(momentum)
         self.momentum = momentum
         self.stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
@@ -222,12 +227,14 @@ class SynthSettings(object):
         self.check_alignment = check_alignment
         self.limiter = limiter_setting(limiter)
         self.output = output_of(hp, output)
+        self.marks = marks_.marks_kind(marks)
+        self.marks_max_jump = token_times_jump(marks_max_jump, 'marks_max_jump')
 
     def engine_keywords(self):
         """the settings as ``Engine.synthesize`` / ``Engine.synthesize_host`` take them"""
         return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
                     phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None,
-                    limiter=self.limiter)
+                    limiter=self.limiter, token_times=(True, pad_id(), self.marks_max_jump) if self.marks else None)
 
     def host_keywords(self):
         """... and as ``Engine.synthesize_host`` alone takes them: with the delivery format"""
@@ -239,16 +246,37 @@ class SynthSettings(object):
                     speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter)
 
 
+def marks_of_batch(hp, s, ids, start, stats, n_held, wavs, mark_texts=None):
+    """The timing marks of one call, a list of marks per row (``marks.marks_of_row``): ``start`` and ``stats`` as
+    ``Engine.synth_token_times`` returns them, ``n_held`` the samples every row holds at the model's rate, ``wavs`` what is
+    delivered (its lengths bound the marks' samples), ``s`` the call's ``SynthSettings``.  ``mark_texts``: per row ``(raw,
+    processed, spans)`` for raw offsets (``marks.token_spans``); None: the processed characters of the ids (``marks.ids_text``)."""
+    hp = getattr(hp, 'hparams', hp)
+    hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
+    out = []
+    for b in range(len(start)):
+        if mark_texts is None:
+            raw = None
+            processed, spans = marks_.ids_text(ids[b], stats['n_sent'][b], dataset_params.vocabulary_dict)
+        else:
+            raw, processed, spans = mark_texts[b]
+        out.append(marks_.marks_of_row(processed, spans, start[b], hp.reduction, hop, s.rate, int(n_held[b]), hp.sampling_rate,
+                                       output_rate(hp, s.output), len(wavs[b]), s.marks, raw=raw, stats=stats[b]))
+    return out
+
+
 def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
                      momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                     phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None):
+                     phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None, marks=None, marks_max_jump=4,
+                     mark_texts=None):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
     of the reference (tacotron/inference.py:170-188) fused into one device call.  The settings from ``momentum`` on: as
     ``SynthSettings`` has them.  With ``stop_at_silence_db`` the result is a list of B waveforms, with ``check_alignment`` it is
     ``(waveforms, records, verdicts)``.  With an ``output`` the waveforms are that format's codes at its rate, made of the call's
-    device rows (``deliver_rows``; the dither's seed is ``seed``)."""
+    device rows (``deliver_rows``; the dither's seed is ``seed``).  With ``marks`` the result gains, as its last element, a list of
+    timing marks per row -- of the processed characters of the ids, with offsets into that string (``mark_texts``: of raw texts)."""
     s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output)
+                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -263,16 +291,24 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
         wavs = deliver_rows(model.engine, out['wav'], held, s.output, seed)
     else:
         wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if s.stop is not None else out['wav'].to_host()
+    result = (wavs,)
     if check_alignment:
         records = model.engine.synth_alignment_stats(len(sentences))
-        return wavs, records, attention_check.verdict(records)
-    return wavs
+        result += (records, attention_check.verdict(records))
+    if s.marks:
+        start, stats = model.engine.synth_token_times(len(sentences))
+        if s.stop is None:   # (every row holds the call's hop (T' - 1) samples)
+            n_held = [win_hop * (synth_frame_counts(S * hp.reduction, s.rate, 0.0)[0] - 1)] * len(start)
+        else:
+            n_held = win_hop * (np.asarray(out['n_frames'], dtype=np.int64) - 1)
+        result += (marks_of_batch(hp, s, np.asarray(sentences), start, stats, n_held, wavs, mark_texts),)
+    return result if len(result) > 1 else wavs
 
 
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
                       want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
                       speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False, limiter=None,
-                      output=None):
+                      output=None, marks=None, marks_max_jump=4, mark_texts=None):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -288,10 +324,13 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     verdicts)`` or ``(wavs, linear, alignments, records, verdicts)``; the 56 bytes per utterance come down with the waveforms.
     With an ``output`` the call itself resamples and encodes its rows on the device (tts_set_output: the dither's seed is the
     call's) and only the codes are downloaded: the waveforms are int16 or uint8 arrays (float32 for 'float32' at another rate) at
-    the output rate, cut to what each row holds with ``stop_at_silence_db``; a row that clipped is logged with its count."""
+    the output rate, cut to what each row holds with ``stop_at_silence_db``; a row that clipped is logged with its count.
+    With ``marks`` every item is a tuple whose last element is the batch's timing marks, a list per row (of the processed
+    characters of the ids -- or, with ``mark_texts``, an iterator that gives per batch what ``synthesize_batch`` takes by that name,
+    of raw texts); the 4 T_sent + 36 bytes per utterance come down with the waveforms."""
     # (a generator: a bad setting is refused at its first item, before the engine is touched)
     s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output)
+                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
     hp = model.hparams
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
@@ -314,15 +353,31 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
         n_frames = eng.wait_host_frames(ticket)
         return cut_waveforms(eng.wait_host(ticket, copy=copy), n_frames, win_hop)
 
+    sent = {}   # ticket -> its ids, while the marks of the call are still to be made
+
+    def marked(ticket, wavs):
+        ids, texts = sent.pop(ticket)
+        if not s.marks:
+            return ()
+        start, stats = eng.wait_host_token_times(ticket)
+        if s.stop is None:   # (every row holds the call's hop (T' - 1) samples)
+            held = np.full(len(start), win_hop * (synth_frame_counts(S * hp.reduction, s.rate, 0.0)[0] - 1), dtype=np.int64)
+        else:
+            held = win_hop * (eng.wait_host_frames(ticket).astype(np.int64) - 1)
+        return (marks_of_batch(hp, s, ids, start, stats, held, wavs, texts),)
+
     def collect(ticket):
         checked = ()
         if check_alignment:
             records = eng.wait_host_alignment_stats(ticket)
             checked = (records, attention_check.verdict(records))
         if not extra:
-            return ((waveforms(ticket),) + checked) if checked else waveforms(ticket)
+            wavs = waveforms(ticket)
+            checked += marked(ticket, wavs)
+            return ((wavs,) + checked) if checked else wavs
         lin, ali = eng.wait_host_outputs(ticket, copy=copy)
-        return (waveforms(ticket), lin, ali) + checked
+        wavs = waveforms(ticket)
+        return (wavs, lin, ali) + checked + marked(ticket, wavs)
 
     # three batches in flight (the library's three buffer sets): the encoder of batch k + 2 runs one inter-Griffin-Lim gap
     # ahead of its decoder, which follows the decoder of batch k + 1 without a pause, beside the Griffin-Lim of batch k
@@ -331,6 +386,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
         pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
                                            win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
                                            want_alignments=want_alignments, **s.host_keywords()))
+        sent[pending[-1]] = (np.asarray(ids), next(mark_texts) if s.marks and mark_texts is not None else None)
         if len(pending) == 3:
             yield collect(pending.pop(0))
     while pending:
@@ -362,7 +418,8 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
 
 def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
                          stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                         phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None):
+                         phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None, marks=None,
+                         marks_max_jump=4):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
@@ -373,16 +430,20 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     them, not peak-normalised.  With ``check_alignment`` the result is ``(waveforms, report)`` with ``report`` the list of ``{index,
     verdict, record}`` of ``attention_check.report``, also written to ``alignment_report.json`` beside the wavs.  With an
     ``output`` the files and the returned arrays are in that format and at that rate (16-bit or 8-bit PCM, G.711), peak-normalised
-    on the device ahead of the encoder where the float files would have been on the way to the disk."""
+    on the device ahead of the encoder where the float files would have been on the way to the disk.  With ``marks`` the result
+    gains, as its last element, the timing marks of every sentence with offsets into the RAW sentence, also written as
+    ``{i+1}.marks.jsonl`` beside every wav (``marks.write_marks``); a sentence the front end cannot be mapped back to raises
+    ValueError (``marks.token_spans``)."""
     # (ValueError before anything is loaded)
     s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output)
+                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
         raise NotADirectoryError('The specified synthesis target folder does not exist.')
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
+    mark_texts = [(raw,) + marks_.token_spans(dataset, raw) for raw in raw_sentences] if s.marks else None
     id_sequences, sequence_lengths = dataset.process_sentences(raw_sentences)
     sentences = [np.frombuffer(s, dtype=np.int32) for s in id_sequences]
     max_length = max(sequence_lengths)
@@ -390,8 +451,14 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
     norm = s.loud is None and s.limiter is None
     wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=norm and s.output is not None, check_alignment=check_alignment,
-                            output=output, **s.keywords())
+                            output=output, marks=marks, marks_max_jump=marks_max_jump, mark_texts=mark_texts, **s.keywords())
     report = None
+    all_marks = None
+    if s.marks:
+        wavs, all_marks = wavs[:-1], wavs[-1]
+        wavs = wavs if check_alignment else wavs[0]
+        for i, m in enumerate(all_marks):
+            marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), m)
     if check_alignment:
         wavs, records, _verdicts = wavs
         report = attention_check.report(records)
@@ -400,7 +467,8 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, s.output), norm and s.output is None,
                  encoding=output_encoding(s.output))
-    return (list(wavs), report) if check_alignment else list(wavs)
+    result = (list(wavs),) + ((report,) if check_alignment else ()) + ((all_marks,) if s.marks else ())
+    return result if len(result) > 1 else result[0]
 
 
 # The pause behind a piece by the break that ends it, in milliseconds.  Untuned: round figures in the range speech synthesizers
@@ -513,7 +581,8 @@ def join_list_of_call(piece_text, piece_break, n_frames, first_active, hop, paus
 
 
 def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_ms=FADE_MS, lead_trim=True, max_chars=MAX_CHARS,
-                    n_steps=None, n_iter=None, seed=0, check_alignment=False, output=None, peak_normalize=False, **settings):
+                    n_steps=None, n_iter=None, seed=0, check_alignment=False, output=None, peak_normalize=False, marks=None,
+                    marks_max_jump=4, **settings):
     """Texts of any length -> one float32 waveform per text (no reference counterpart: tacotron/inference.py:139-200 makes one
     file of at most max_iterations frames per line).
 
@@ -544,18 +613,25 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
 
     Returns the list of waveforms (a text without a piece that speaks: an empty array); with ``check_alignment`` ``(waveforms,
     records, verdicts, piece_text)``: the alignment record and ``attention_check.verdict`` of every piece, in order, and the
-    index of the text each piece belongs to."""
+    index of the text each piece belongs to.  With ``marks`` ('word' or 'char') the result gains, as its last element, the timing
+    marks of every text in ITS waveform (``marks.marks_of_text``): every piece's marks taken through its lead trim, the join's
+    layout and the parts of a text that span calls, with offsets into the raw text; a dropped piece's marks have no length."""
     if settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB) is None:
         raise ValueError('synthesize_text: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)')
     settings.setdefault('stop_at_silence_db', STOP_AT_SILENCE_DB)
     loud = loudness_setting(settings.pop('loudness', None))
     limiter = limiter_setting(settings.pop('limiter', None))
-    s = SynthSettings(model, check_alignment=check_alignment, **settings)
+    s = SynthSettings(model, check_alignment=check_alignment, marks=marks, marks_max_jump=marks_max_jump, **settings)
     out_setting = output_of(model, output)
     hp = model.hparams
     pauses = pause_samples(pauses_ms, hp.sampling_rate)
     fade = fade_samples(fade_ms, hp.sampling_rate)
     calls, piece_text, piece_break, _pieces = pack_pieces(texts, dataset, batch_size, max_chars)
+    piece_at = []                   # with marks: per piece its (processed, spans) in its raw text, in the order of pack_pieces
+    if s.marks:
+        for text in texts:
+            piece_at += [marks_.piece_spans(dataset, text, a, b) for _p, _k, a, b in split_text_spans(text, max_chars, abbreviations_of(dataset))]
+    marked = [[] for _ in texts]    # ... and per text what marks_of_text takes of its pieces
     loader = dataset_params.dataset_loader
     win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
     win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
@@ -580,6 +656,23 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
         for t, gap in orphans:      # (silent pieces in front of the call's first kept piece of their text)
             if parts[t]:
                 tails[t] += gap
+        if s.marks:
+            start, tstats = eng.synth_token_times(B)
+            o, kept = marks_.join_offsets(pieces, groups), {int(row[0]): i for i, row in enumerate(pieces)}
+            for b in range(B):
+                t = piece_text[p0 + b]
+                so_far = sum(len(w) for w in parts[t])
+                entry = dict(processed=piece_at[p0 + b][0], spans=piece_at[p0 + b][1], start=start[b], stats=tstats[b])
+                if b in kept:
+                    i = kept[b]
+                    entry.update(n_held=win_hop * (int(out['n_frames'][b]) - 1), first=int(pieces[i][1]), count=int(pieces[i][2]), o=int(o[i]),
+                                 part=so_far + tails[t] if parts[t] else 0, end=0)
+                    entry['end'] = entry['o'] + entry['count'] + entry['part']
+                else:               # dropped: at the end of what its text has said so far
+                    before = [e for e in marked[t] if 'end' in e and e.get('call') == k]
+                    entry['at'] = before[-1]['end'] if before else so_far
+                entry['call'] = k
+                marked[t].append(entry)
         if not said:
             continue
         joined, n_out = eng.join(out['wav'], pieces, groups, fade)
@@ -597,17 +690,22 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
         wavs = deliver(eng, wavs, out_setting, seed, norm=peak_normalize, what='text')
     elif peak_normalize:
         raise ValueError('synthesize_text: peak_normalize goes with an output (save_wav normalises float32 files)')
+    result = (wavs,)
     if check_alignment:
         records = np.concatenate(records) if records else np.zeros(0, dtype=ALIGNMENT_RECORD)
-        return wavs, records, attention_check.verdict(records), list(piece_text)
-    return wavs
+        result += (records, attention_check.verdict(records), list(piece_text))
+    if s.marks:
+        result += ([marks_.marks_of_text(marked[t], hp.reduction, win_hop, s.rate, hp.sampling_rate, output_rate(model, out_setting),
+                                         len(wavs[t]), s.marks, raw=texts[t]) for t in range(len(texts))],)
+    return result if len(result) > 1 else wavs
 
 
 def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0, seed=0, check_alignment=False, **kw):
     """``synthesize_sentences`` for texts of any length: every entry of ``raw_texts`` becomes one ``{i+1}.wav`` that holds the whole
     text (``synthesize_text``; ``kw``: its keywords).  Without a ``loudness`` or a ``limiter`` each file is peak-normalised once by save_wav, as
     the sentence files are.  Returns the list of waveforms, with ``check_alignment`` ``(waveforms, report)`` -- one ``{index,
-    verdict, record}`` per PIECE, each with the index of its ``text`` -- also written to ``alignment_report.json``."""
+    verdict, record}`` per PIECE, each with the index of its ``text`` -- also written to ``alignment_report.json``.  With ``marks`` the
+    result gains the timing marks of every text as its last element, also written as ``{i+1}.marks.jsonl`` beside every wav."""
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     out_dir = out_dir or inference_params.synthesis_dir
     if not os.path.isdir(out_dir):
@@ -627,6 +725,12 @@ def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0
     wavs = synthesize_text(model, raw_texts, dataset, seed=seed, check_alignment=check_alignment,
                            peak_normalize=norm and out_setting is not None, **kw)
     report = None
+    all_marks = None
+    if kw.get('marks'):
+        wavs, all_marks = wavs[:-1], wavs[-1]
+        wavs = wavs if check_alignment else wavs[0]
+        for i, m in enumerate(all_marks):
+            marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), m)
     if check_alignment:
         wavs, records, _verdicts, piece_text = wavs
         report = attention_check.report(records)
@@ -637,7 +741,8 @@ def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0
     for i, wav in enumerate(wavs):
         save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, out_setting),
                  norm and out_setting is None and len(wav) > 0, encoding=output_encoding(out_setting))   # (a text that says nothing: an empty file)
-    return (list(wavs), report) if check_alignment else list(wavs)
+    result = (list(wavs),) + ((report,) if check_alignment else ()) + ((all_marks,) if all_marks is not None else ())
+    return result if len(result) > 1 else result[0]
 
 
 def read_texts(path):
@@ -681,7 +786,7 @@ def main(argv=None):
                                                             [--loudness LUFS [--max-peak P]]
                                                             [--limit DB [--limit-lookahead-ms MS] [--sample-peak]]
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
-                                                            [--check-alignment]
+                                                            [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
                                                             [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
@@ -704,6 +809,9 @@ def main(argv=None):
     samples clipped in the encoder is reported with its count: with ``--limit -1`` there is head room for the resampler.
     ``--check-alignment``: the attention diagnostics (``tacotron.attention_check``) -- one JSON line per sentence (index,
     verdict, record) and ``alignment_report.json`` beside the wavs; the exit status stays 0 whatever the verdicts.
+    ``--marks``: timing marks -- when every word (``--marks char``: and every character) is spoken, in milliseconds and in samples
+    of the file, with offsets into the line -- as JSON lines in ``{i+1}.marks.jsonl`` beside every wav (``tacotron.marks``); the
+    search lets a decoder step advance over at most ``--marks-max-jump`` characters (default 4, untuned).
     ``--text``: every line of the synthesis file is a text of any length -- sentences, paragraphs (the two characters ``\\n``
     twice in a row mark a paragraph break inside a line) -- and ``{i+1}.wav`` holds the whole text (``synthesize_text``): split
     into pieces of at most ``--max-chars`` characters (default 150), each stopped at its silence (``--stop-at-silence``, -40 dB
@@ -714,7 +822,7 @@ def main(argv=None):
                       phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
                       check_alignment=args.check_alignment,
                       limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
-                      output=output_option(args))
+                      output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump)
     out_dir = args.synthesis_dir or inference_params.synthesis_dir
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     if not os.path.isdir(out_dir):
@@ -735,10 +843,13 @@ def main(argv=None):
         kw = dict(s.keywords(), stop_at_silence_db=STOP_AT_SILENCE_DB if args.stop_at_silence is None else args.stop_at_silence)
         wavs = synthesize_texts(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
                                 check_alignment=args.check_alignment, max_chars=args.max_chars, pauses_ms=dict(args.pause_ms),
-                                fade_ms=args.fade_ms, output=output_option(args), **kw)
+                                fade_ms=args.fade_ms, output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump, **kw)
     else:
         wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                    check_alignment=args.check_alignment, output=output_option(args), **s.keywords())
+                                    check_alignment=args.check_alignment, output=output_option(args), marks=args.marks,
+                                    marks_max_jump=args.marks_max_jump, **s.keywords())
+    if args.marks:
+        wavs = wavs[:-1] if args.check_alignment else wavs[0]
     if args.check_alignment:
         wavs, report = wavs
         for row in report:
@@ -794,6 +905,10 @@ def parse_args(argv=None):
     ap.add_argument('--no-dither', action='store_true', help='with --format: round without the TPDF dither')
     ap.add_argument('--check-alignment', action='store_true',
                     help='attention diagnostics: one JSON line per sentence and {} beside the wavs'.format(REPORT_FILE))
+    ap.add_argument('--marks', nargs='?', const='word', default=None, choices=list(marks_.KINDS),
+                    help='timing marks of every word (or, with char, every character too) as JSON lines in {i+1}.marks.jsonl beside the wavs')
+    ap.add_argument('--marks-max-jump', type=int, default=4, metavar='J',
+                    help='with --marks: the most characters a decoder step may advance over, 1 .. 15 (default 4, untuned)')
     ap.add_argument('--text', action='store_true',
                     help='every line of the synthesis file is a text of any length (a literal \\n\\n marks a paragraph): one wav per text')
     ap.add_argument('--max-chars', type=int, default=MAX_CHARS, metavar='N',

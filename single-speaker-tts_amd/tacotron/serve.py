@@ -10,8 +10,8 @@ import numpy as np
 
 from .._hip import limiter_lookahead, synth_frame_counts, synth_lengths
 from ..audio.conversion import ms_to_samples
-from . import attention_check
-from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, deliver, pad_id, pad_sentence, synthesize_stream
+from . import attention_check, marks as marks_
+from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, deliver, marks_of_batch, pad_id, pad_sentence, synthesize_stream
 from .model import Mode, Tacotron
 from .params import dataset_params, model_params
 
@@ -88,7 +88,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
 
 def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
           silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None,
-          check_alignment=False, limiter=None, output=None):
+          check_alignment=False, limiter=None, output=None, marks=None, marks_max_jump=4):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -102,10 +102,12 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     records of the batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip
     as the waveforms: a bad utterance can be flagged before it is played.  With an ``output`` (``inference.SynthSettings``) every
     answer is in that sample format and at that rate -- 16-bit PCM, or G.711 at 8 kHz for telephony -- resampled and encoded on
-    the device: pipelined, inside the call, so that only the codes cross the host boundary."""
+    the device: pipelined, inside the call, so that only the codes cross the host boundary.  With ``marks`` ('word' or 'char')
+    every answer gains, as its last element, the timing marks of every sentence (``tacotron.marks``; offsets into the raw
+    sentence, samples of what is delivered): subtitles and barge-in positions in the same round trip as the waveforms."""
     # (a generator: a bad setting is refused at its first item, before a model is made)
     s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output)
+                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
     from ..datasets.lj_speech import LJSpeechDatasetHelper
     dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
                                                 char_dict=dataset_params.vocabulary_dict, fill_dict=False)
@@ -113,21 +115,38 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     if not pipelined:   # the reference's loop as it stands: one batch at a time, spectrograms through host memory
         for k, sentences in enumerate(sentence_generator):
             ids = pre_process_sentences(sentences, dataset)
-            fetches = [model.output_linear_spec] + ([model.alignment_history] if check_alignment else [])
+            texts = [(raw,) + marks_.token_spans(dataset, raw) for raw in sentences] if s.marks else None
+            fetches = [model.output_linear_spec] + ([model.alignment_history] if check_alignment or s.marks else [])
             fetched = model.run(fetches, {model.inp_sentences: ids})
             wavs = post_process_spectrograms(fetched[0], model.engine, **s.keywords())
+            held = [len(w) for w in wavs]   # (the samples every row holds at the model's rate)
             if s.output is not None:
                 wavs = deliver(model.engine, wavs, s.output, seed=k)
+            answer = (wavs,)
+            n_sent = model.engine.text_lengths(ids, pad_id()) if check_alignment or s.marks else None
             if check_alignment:   # (the same kernels as inside a pipelined call, on the alignments this loop fetched anyway)
-                records = model.engine.alignment_stats(fetched[1], n_sent=model.engine.text_lengths(ids, pad_id()))
-                yield wavs, records, attention_check.verdict(records)
-            else:
-                yield wavs
+                records = model.engine.alignment_stats(fetched[1], n_sent=n_sent)
+                answer += (records, attention_check.verdict(records))
+            if s.marks:
+                start, stats = model.engine.token_times(fetched[1], n_sent=n_sent, max_jump=s.marks_max_jump)
+                answer += (marks_of_batch(model, s, ids, start, stats, held, wavs, texts),)
+            yield answer if len(answer) > 1 else wavs
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
-    batches = (pre_process_sentences(sentences, dataset) for sentences in sentence_generator)
-    for item in synthesize_stream(model, batches, peak_normalize=False, copy=True, check_alignment=check_alignment, output=output,
-                                  **s.keywords()):
-        wavs = item[0] if check_alignment else item
+    texts = []   # per batch pulled, what its marks take of the raw sentences
+
+    def pulled():
+        for sentences in sentence_generator:
+            if s.marks:
+                texts.append([(raw,) + marks_.token_spans(dataset, raw) for raw in sentences])
+            yield pre_process_sentences(sentences, dataset)
+
+    def pulled_texts():
+        while True:
+            yield texts.pop(0)
+
+    for item in synthesize_stream(model, pulled(), peak_normalize=False, copy=True, check_alignment=check_alignment, output=output,
+                                  marks=marks, marks_max_jump=marks_max_jump, mark_texts=pulled_texts(), **s.keywords()):
+        wavs = item[0] if check_alignment or s.marks else item
         listed = [wavs[b] for b in range(len(wavs))]
-        yield (listed, item[1], item[2]) if check_alignment else listed
+        yield ((listed,) + tuple(item[1:])) if check_alignment or s.marks else listed

@@ -839,6 +839,48 @@ int tts_join_max_pieces(void);
 int tts_join_max_fade(void);
 int tts_join_tile(void);
 
+/* ---- prosody: a segment-wise warp of magnitude spectrograms ---------------------------------- */
+/* An edit list over the frames of mag DEVICE [B][F][T], written to out DEVICE [B][F][T_out] -- the layout tts_denorm_power writes
+ * and tts_griffin_lim_ragged reads (no reference counterpart: tts_stretch_magnitudes with a rate, a gain and pauses that vary
+ * along the utterance).  Segment s is either speech -- source frames [first, first + frames) of row `row`, frames >= 1 and pause
+ * == 0 -- or a pause -- frames == 0 and pause >= 1 output frames of silence; first, step and gain of a pause are ignored.  The
+ * segments of a row are consecutive in the list, rows non-decreasing over 0 .. B - 1, no row without a segment; the speech segments
+ * of a row may use any source range inside n_frames[row] (HOST int32 [B], or NULL: all T), in any order, any number of times.
+ *   lengths  count[s] = ceil(frames * 65536 / step) (int64, exact) for speech, `pause` for a pause; within a row segment s starts
+ *            at output frame o[s], the sum of the counts of the row's earlier segments, and the row holds n_out[row] = the sum of
+ *            all of them.
+ *   speech   output frame o + j, j < count: p = j * step (int64), i = first + (p >> 16), a = (p & 65535) * 2^-16 (exact),
+ *            out[:, o + j] = (float)(g * ((1 - a) * x[:, i] + a * x[:, i + 1])), g = (double)gain: every product and sum an IEEE
+ *            double operation rounded on its own (no FMA), one rounding to float32.  x[:, i + 1] reads as 0.0 where i + 1 >=
+ *            n_frames[row] and is then never fetched; otherwise it is the row's next source frame, whichever segment that lies
+ *            in.  The blend is always evaluated: 0 * NaN and 0 * Inf stay NaN, as in tts_stretch_magnitudes.
+ *   zeros    the output frames of a pause and frames n_out[row] .. T_out - 1 are +0.0.
+ * One whole-row segment {b, 0, n_frames[b], 0, q, 1.0f} per row is tts_stretch_magnitudes at rate q / 65536: the same lengths and
+ * the same bits.  Every element of out is written exactly once per call: no atomics, no memset, nothing read from out; a row's
+ * output is the same bits whatever B is and wherever the row sits in the batch, and however the list is cut into launches (the
+ * bits of tests/warp_oracle.py).  The list travels by value, 64 segments per launch: a call makes ceil(S / 64) launches, uploads
+ * nothing and waits for nothing.  Asynchronous on the handle's stream, no model needed; profile stage "warp".
+ * TTS_ERR_INVALID with a message that names the segment or row, before anything is enqueued, in this order: a NULL pointer; B, F,
+ * T or S < 1; S above tts_warp_max_segments(); B above S; an n_frames[b] outside 1 .. T; rows that do not start at 0, decrease, skip a row or
+ * do not end at B - 1; then per segment a negative frames or pause, a segment that is both a pause and speech or neither, a speech
+ * segment outside [0, n_frames[row]), a step outside 16384 .. 262144, a gain that is not finite or lies outside 0 .. 16; T_out
+ * below the largest n_out[b] or above 2^30; a misaligned buffer (4 bytes). */
+typedef struct tts_warp_segment {
+    int32_t row, first, frames, pause;
+    uint32_t step;   /* source frames per output frame, times 65536 */
+    float gain;
+} tts_warp_segment_t;   /* HOST, 24 bytes */
+/* Host only, no handle and no device: the checks of the list, and every row's length (tts_last_error(NULL) has the reason of a
+ * refusal). */
+int tts_warp_plan(const tts_warp_segment_t* segments, int S, int B, int T, const int32_t* n_frames /* HOST [B] or NULL */,
+                  int64_t* n_out /* HOST [B] */);
+int tts_warp_magnitudes(tts_handle_t h, const float* mag /* DEVICE [B][F][T] */, int B, int F, int T,
+                        const int32_t* n_frames /* HOST [B] or NULL */, const tts_warp_segment_t* segments, int S, int T_out,
+                        float* out /* DEVICE [B][F][T_out] */);
+/* Host only: the most segments a call takes (4096), and the output frames of a segment one workgroup writes (64, in 32 bins). */
+int tts_warp_max_segments(void);
+int tts_warp_tile(void);
+
 /* ---- delivery formats: 16-bit PCM, 8-bit PCM and G.711 --------------------------------------- */
 #define TTS_FMT_F32 0        /* float32 as the library makes it: no encoding */
 #define TTS_FMT_PCM_S16 1    /* signed 16-bit PCM, 2 bytes per code */
@@ -1088,7 +1130,7 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, tts_token_times, stand-alone
  * or inside a tts_synthesize call with tts_set_alignment_stats or tts_set_token_times on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
  * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
- * tts_synthesize_host call with tts_set_output on).
+ * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -114,7 +114,22 @@ class TtsJoinPiece(ctypes.Structure):
     _fields_ = [('row', c_int32), ('first', c_int32), ('count', c_int32), ('gap', c_int32)]
 
 
+class TtsWarpSegment(ctypes.Structure):
+    """tts_warp_segment_t: source frames [first, first + frames) of a row at ``step`` / 65536 source frames per output frame and a
+    gain, or (frames == 0) a pause of ``pause`` output frames; 24 bytes, a record of the WARP_SEGMENT arrays ``Engine.warp_magnitudes``
+    hands the library"""
+    _fields_ = [('row', c_int32), ('first', c_int32), ('frames', c_int32), ('pause', c_int32), ('step', ctypes.c_uint32), ('gain', c_float)]
+
+
+# ... and the same record as a numpy dtype
+WARP_SEGMENT = np.dtype([('row', np.int32), ('first', np.int32), ('frames', np.int32), ('pause', np.int32), ('step', np.uint32), ('gain', np.float32)])
+
+
 _PROTOTYPES = {
+    'tts_warp_plan': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
+    'tts_warp_magnitudes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_int, c_void_p]),
+    'tts_warp_max_segments': (c_int, []),
+    'tts_warp_tile': (c_int, []),
     'tts_alignment_stats': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
     'tts_text_lengths': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -822,6 +837,95 @@ def stretch_frame_counts(n_frames, B, T):
     if nf.dtype.kind not in 'iu':
         raise ValueError('n_frames must be integers, got {}'.format(nf.dtype))
     return _checked_lengths(nf, T, 'n_frames', 'T')
+
+
+WARP_MAX_SEGMENTS = 4096                       # tts_warp_max_segments()
+WARP_SEGMENTS_PER_LAUNCH = 64                  # segments whose entries travel with one launch
+WARP_STEP_MIN, WARP_STEP_MAX = 16384, 262144   # the rates 0.25 .. 4 times 65536
+WARP_GAIN_MAX = 16.0
+WARP_MAX_T_OUT = 1 << 30
+
+
+def warp_count(frames, step):
+    """output frames of a speech segment: ceil(frames * 65536 / step), exact"""
+    return -((-int(frames) << 16) // int(step))
+
+
+def warp_launches(S):
+    """launches of a warp of S segments"""
+    return -(-int(S) // WARP_SEGMENTS_PER_LAUNCH)
+
+
+def warp_segments(segments):
+    """``segments`` -- a WARP_SEGMENT array, or rows ``(row, first, frames, pause, step, gain)`` -- as a contiguous WARP_SEGMENT
+    array (S,).  ValueError for anything that is not such a list or does not fit the record's fields."""
+    if isinstance(segments, np.ndarray) and segments.dtype == WARP_SEGMENT and segments.ndim == 1:
+        return np.ascontiguousarray(segments)
+    try:
+        rows = [tuple(r) for r in segments]
+    except TypeError:
+        rows = None
+    if rows is None or any(len(r) != 6 for r in rows):
+        raise ValueError('warp: segments must be a WARP_SEGMENT array or rows (row, first, frames, pause, step, gain)')
+    out = np.zeros(len(rows), dtype=WARP_SEGMENT)
+    for s, r in enumerate(rows):
+        ints, gain = r[:5], r[5]
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in ints) or \
+                any(not -2 ** 31 <= v < 2 ** 31 for v in ints[:4]) or not 0 <= ints[4] < 2 ** 32:
+            raise ValueError('warp: segment {} must hold 32-bit integers row, first, frames, pause and step, got {!r}'.format(s, r))
+        try:
+            gain = float(gain)
+        except (TypeError, ValueError):
+            raise ValueError('warp: segment {} needs a number as its gain, got {!r}'.format(s, r[5]))
+        out[s] = tuple(int(v) for v in ints) + (gain,)
+    return out
+
+
+def warp_list(segments, B, T, n_frames=None):
+    """The segment list of a warp on a batch (B, F, T) as ``(segments, n_frames, n_out, count)``: a contiguous WARP_SEGMENT array,
+    the lengths as ``stretch_frame_counts`` makes them, the int64 lengths of the B output rows and the int64 output frames of
+    every segment.  Checked as tts_warp_plan checks it, in its order -- ValueError, raised before a handle or the library is
+    touched."""
+    q = warp_segments(segments)
+    S = int(q.shape[0])
+    if B < 1 or T < 1 or S < 1:
+        raise ValueError('warp: need B, T, S >= 1')
+    if S > WARP_MAX_SEGMENTS:
+        raise ValueError('warp: {} segments are more than tts_warp_max_segments() = {}'.format(S, WARP_MAX_SEGMENTS))
+    if B > S:
+        raise ValueError('warp: {} rows of {} segments: no row is without a segment'.format(B, S))
+    nf = stretch_frame_counts(n_frames, B, T)
+    rows = q['row'].tolist()
+    if rows[0] != 0:
+        raise ValueError('warp: row of segment 0 is {}: the rows start at 0'.format(rows[0]))
+    for s in range(1, S):
+        if rows[s] - rows[s - 1] not in (0, 1):
+            raise ValueError('warp: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a segment'.format(
+                s, rows[s], rows[s - 1]))
+    if rows[-1] != B - 1:
+        raise ValueError('warp: row of segment {} is {}: the last row is B - 1 = {}'.format(S - 1, rows[-1], B - 1))
+    n_out = np.zeros(B, dtype=np.int64)
+    count = np.zeros(S, dtype=np.int64)
+    for s, (row, first, frames, pause, step, gain) in enumerate(q.tolist()):
+        if frames < 0 or pause < 0:
+            raise ValueError('warp: segment {} has a negative length (frames {}, pause {})'.format(s, frames, pause))
+        if frames > 0 and pause > 0:
+            raise ValueError('warp: segment {} is both speech ({} frames) and a pause ({} frames)'.format(s, frames, pause))
+        if frames == 0 and pause == 0:
+            raise ValueError('warp: segment {} is neither speech nor a pause (frames and pause are 0)'.format(s))
+        c = pause
+        if frames > 0:
+            n = T if nf is None else int(nf[row])
+            if first < 0 or first + frames > n:
+                raise ValueError('warp: segment {} reads frames {} .. {} of row {}, which has 0 .. {}'.format(s, first, first + frames - 1, row, n - 1))
+            if not WARP_STEP_MIN <= step <= WARP_STEP_MAX:
+                raise ValueError('warp: segment {} has step {}, which is not in {} .. {}'.format(s, step, WARP_STEP_MIN, WARP_STEP_MAX))
+            if not 0.0 <= gain <= WARP_GAIN_MAX:   # (a NaN fails both comparisons)
+                raise ValueError('warp: segment {} has a gain that is not finite or lies outside 0 .. 16'.format(s))
+            c = warp_count(frames, step)
+        count[s] = c
+        n_out[row] += c
+    return q, nf, n_out, count
 
 
 RESAMPLE_RATIO_MIN, RESAMPLE_RATIO_MAX = 0.25, 4.0
@@ -1869,7 +1973,7 @@ class Engine(object):
         out.free()
         return n
 
-    def token_times(self, alignments, n_sent=None, n_steps=None, max_jump=4, want_path=False):
+    def token_times(self, alignments, n_sent=None, n_steps=None, max_jump=4, want_path=False, to_host=True):
         """tts_token_times: when every token is spoken -- the best monotone path through an alignment history, a position per
         step that never goes back and advances by at most ``max_jump`` (1 .. 15) tokens a step.  ``alignments`` (n_steps_max, B,
         Ts) float32 as the decoder writes them, a host array or a device buffer; ``n_sent`` / ``n_steps`` as ``alignment_stats``
@@ -1878,7 +1982,8 @@ class Engine(object):
         ``TOKEN_TIMES_RECORD`` -- score, n_sent, n_steps, last, jumps, skipped, agree --, then with ``want_path`` the path int32
         (B, n_steps_max) (-1 behind an utterance's steps).  ``max_jump = 4`` is untuned: four characters per step of r frames.
         include/sstts_hip.h has the definition: everything is the bits of tests/marks_oracle.py.  ``tacotron.marks`` turns
-        ``start`` into times."""
+        ``start`` into times.  ``to_host`` False: the device arrays as they are, nothing downloaded and nothing waited for (the
+        caller downloads and frees them)."""
         shape = tuple(int(d) for d in alignments.shape)
         if len(shape) != 3 or min(shape) < 1:
             raise ValueError('token_times: alignments (n_steps_max, B, Ts) are needed, got shape {}'.format(shape))
@@ -1894,6 +1999,8 @@ class Engine(object):
         path = self.empty((B, S), np.int32) if want_path else None
         self._check_or_free(self.lib.tts_token_times(self.handle, p_ali, S, B, Ts, _int32_ptr(ns), _int32_ptr(nt), J, start.data_ptr(),
                                                      path.data_ptr() if path is not None else None, stats.data_ptr()), start, stats, path)
+        if not to_host:
+            return tuple(a for a in (start, stats, path) if a is not None)
         out = ()
         for a in (start, stats, path):
             if a is not None:
@@ -1995,6 +2102,56 @@ class Engine(object):
         out = self.empty((B, T_out, stride))
         self._check_or_free(self.lib.tts_stretch_rows(self.handle, p_spec, B, T, F, stride, _int32_ptr(nf), r, T_out, out.data_ptr()), out)
         return out
+
+    # ------------------------------------------------------------------ prosody: the segment-wise warp
+    def warp_max_segments(self):
+        """tts_warp_max_segments: the most segments :meth:`warp_magnitudes` takes in one call."""
+        return int(self.lib.tts_warp_max_segments())
+
+    def warp_tile(self):
+        """tts_warp_tile: the output frames of a segment one workgroup of the warp writes."""
+        return int(self.lib.tts_warp_tile())
+
+    def warp_plan(self, shape, segments, n_frames=None):
+        """tts_warp_plan, host only: the lengths ``n_out`` (int64 (B,)) of the rows that ``segments`` -- a WARP_SEGMENT array or rows
+        ``(row, first, frames, pause, step, gain)`` -- make of a batch of ``shape`` (B, F, T) whose rows hold ``n_frames`` frames
+        (None: all T).  ValueError for a list tts_warp_magnitudes refuses (``warp_list``), raised before the library is reached."""
+        if len(shape) != 3:
+            raise ValueError('warp_plan: the shape of a batch (B, F, T) is needed, got {!r}'.format(tuple(shape)))
+        B, T = int(shape[0]), int(shape[2])
+        q, nf, n_out, _count = warp_list(segments, B, T, n_frames)
+        out = np.zeros(B, dtype=np.int64)
+        rc = self.lib.tts_warp_plan(q.ctypes.data, q.shape[0], B, T, _int32_ptr(nf), out.ctypes.data_as(POINTER(c_int64)))
+        if rc != TTS_OK:
+            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        assert (out == n_out).all(), (out, n_out)
+        return out
+
+    def warp_magnitudes(self, mag, segments, n_frames=None, T_out=None):
+        """tts_warp_magnitudes: ``stretch_magnitudes`` with a rate, a gain and pauses that vary along the utterance, on ``mag``
+        (B, F, T) -- a host array, which is uploaded, or a device buffer, which is read in place.  ``segments``: a WARP_SEGMENT
+        array or rows ``(row, first, frames, pause, step, gain)``, the segments of a row one behind the other and the rows in
+        order: source frames [first, first + frames) of the row at ``step`` / 65536 source frames per output frame, scaled by
+        ``gain``, or (frames == 0) ``pause`` output frames of silence.  ``n_frames``: B lengths (host integers) -- frames at or
+        behind them are never read; None: all T.  include/sstts_hip.h has the definition: the bits of tests/warp_oracle.py.
+
+        Returns ``(out, n_out)``: a fresh device array (B, F, T_out) and the int64 host lengths (B,) -- row b holds n_out[b] frames
+        followed by +0.0.  ``T_out`` None: the largest length.  ValueError for what the library refuses, raised before it is
+        reached."""
+        if len(mag.shape) != 3 or min(mag.shape) < 1:
+            raise ValueError('warp_magnitudes: a non-empty 3-D array is needed, got shape {}'.format(tuple(mag.shape)))
+        B, F, T = (int(d) for d in mag.shape)
+        q, nf, n_out, _count = warp_list(segments, B, T, n_frames)
+        longest = int(n_out.max())
+        if T_out is None:
+            T_out = longest
+        if int(T_out) != T_out or not longest <= T_out <= WARP_MAX_T_OUT:
+            raise ValueError('warp_magnitudes: T_out = {!r} is not in n_out.max() = {} .. 2^30'.format(T_out, longest))
+        p_mag, _k = self._in(mag, np.float32)
+        out = self.empty((B, F, int(T_out)))
+        self._check_or_free(self.lib.tts_warp_magnitudes(self.handle, p_mag, B, F, T, _int32_ptr(nf), q.ctypes.data, q.shape[0], int(T_out),
+                                                         out.data_ptr()), out)
+        return out, n_out
 
     def time_stretch(self, wavs, rate, n_iter=25, seed=0, want_magnitudes=False):
         """The reference's waveform effect time_stretch (audio/effects.py:46-88) as a composition of existing calls:

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import attention_check, marks as marks_
+from . import attention_check, marks as marks_, prosody
 from .._hip import (ALIGNMENT_RECORD, synth_frame_counts, token_times_jump, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, output_is_on, output_ratio, output_setting, resampled_length, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
 from ..audio.conversion import ms_to_samples
@@ -471,6 +471,139 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     return result if len(result) > 1 else result[0]
 
 
+def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=None, seed=0, peak_normalize=False, momentum=0.0,
+                      stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random',
+                      loudness=None, limiter=None, output=None, marks=None, marks_max_jump=4, want_plan=False):
+    """Sentences with prosody markup (``tacotron.prosody``: ``<prosody rate=.. volume=..>``, ``<emphasis>``, ``<break/>`` under an
+    optional ``<speak>``) -> a list of B waveforms, row b cut to its own hop (n_out[b] - 1) samples (no reference counterpart).
+
+    A composition of the engine's stages, in this order: ``encoder_forward``, ``decoder_forward`` with alignments,
+    ``token_times`` (at most ``marks_max_jump`` tokens a step), ``postnet_forward``, with ``stop_at_silence_db`` ``speech_frames``
+    on the normalised linear spectrogram; ONE download -- ``start`` and, with stopping on, the lengths: the path's one host wait --;
+    the planner (``prosody.token_attributes`` and ``prosody.segments_of_row``: every token's frames at its span's rate and gain,
+    every break a pause, borders at decoder steps); ``denorm_power``, ``warp_magnitudes``, the ragged Griffin-Lim on ``n_out``, a
+    peak normalisation per row (``peak_normalize``) or the ``loudness``, the ``limiter``, and ``deliver_rows`` for an
+    ``output``.  The settings: as ``SynthSettings`` has them; ``speaking_rate`` is the base rate every span's rate multiplies.  A
+    ``pitch`` other than 0 is a ValueError: a pitch that varies along the utterance needs a time-varying resampler, and the
+    global one lives inside tts_synthesize.  Sentences without markup at rate 1.0 give the bits of the same stages without the
+    warp.
+
+    With ``marks`` the result gains the timing marks of every sentence (``marks.marks_of_row`` at rate 1.0 through
+    ``prosody.warp_position``: a slowed word's mark grows with it, a break opens a gap between two words' marks; ``start`` and
+    ``end`` of a mark are offsets into the sentence with the markup removed); with ``want_plan`` a last element ``dict(plain,
+    start, n_sent, n_frames, segments, n_out)``: what the call planned from, per row."""
+    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, False,
+                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
+    if s.octaves != 0.0:
+        raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global), got {!r}'.format(pitch))
+    hp = model.hparams
+    loader = dataset_params.dataset_loader
+    win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
+    hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
+    r = hp.reduction
+    parsed = [prosody.parse_markup(text) for text in marked_sentences]
+    if not parsed:
+        raise ValueError('synthesize_marked: no sentence')
+    plains = [p[0] for p in parsed]
+    texts = [marks_.token_spans(dataset, plain) for plain in plains]
+    planned = [prosody.token_attributes(dataset, plain, spans, breaks, s.rate, hop, hp.sampling_rate) for plain, spans, breaks in parsed]
+    id_sequences, n_sent = dataset.process_sentences(plains)
+    rows = [np.frombuffer(q, dtype=np.int32) for q in id_sequences]
+    for b, (processed, _spans) in enumerate(texts):
+        if int(n_sent[b]) != len(processed) + 1:
+            raise ValueError('synthesize_marked: sentence {} has {} tokens, {} characters and the end token were expected'.format(
+                b + 1, int(n_sent[b]), len(processed)))
+    ids = np.array([pad_sentence(q, max(n_sent)) for q in rows], dtype=np.int32)
+    n_sent = np.asarray(n_sent, dtype=np.int32)
+    B = ids.shape[0]
+    S = n_steps or model.n_steps()
+    T = S * r
+    it = hp.reconstruction_iterations if n_iter is None else n_iter
+    eng = model.engine
+    min_frames = (hp.n_fft // 2) // hop + 2      # Griffin-Lim's least: hop (n - 1) > n_fft / 2
+    lookahead = None if s.limiter is None else limiter_lookahead('synthesize_marked', s.limiter[1], eng.sampling_rate)
+    memory = eng.encoder_forward(ids)
+    mel, alignments = eng.decoder_forward(memory, S)
+    d_start, d_stats = eng.token_times(alignments, n_sent=n_sent, max_jump=s.marks_max_jump, to_host=False)
+    mel.shape = (B, T, hp.n_mels)
+    linear = eng.postnet_forward(mel)
+    d_frames = d_last = None
+    if s.stop is not None:
+        threshold = eng.speech_threshold(s.stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
+        d_frames, d_last = eng.speech_frames(linear, threshold, s.stop[1], min_frames)
+    start = d_start.to_host()                    # (the one host wait)
+    stats = d_stats.to_host()
+    n_frames = d_frames.to_host().astype(np.int32) if d_frames is not None else np.full(B, T, dtype=np.int32)
+    for a in (d_start, d_stats, d_frames, d_last, memory, alignments):
+        if a is not None:
+            a.free()
+    segments, n_out, per_row = [], [], []
+    for b in range(B):
+        seg, n = prosody.segments_of_row(start[b], int(n_sent[b]), r, int(n_frames[b]), planned[b][0], planned[b][1], min_frames, row=b)
+        per_row.append(seg)
+        segments += seg
+        n_out.append(n)
+    mag = eng.denorm_power(linear, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power)
+    warped, _n = eng.warp_magnitudes(mag, segments, n_frames)
+    assert _n.tolist() == n_out, (_n, n_out)
+    wav, _mse = eng.griffin_lim(warped, it, win_len, hop, hp.n_fft, seed=seed, want_mse=False, momentum=s.momentum, n_frames=n_out,
+                                phase_init=s.phase_init)
+    held = hop * (np.asarray(n_out, dtype=np.int32) - 1)
+    if s.loud is not None:
+        eng.loudness_normalize(wav, eng.sampling_rate, s.loud[0], s.loud[1], n_samples=held)
+    elif peak_normalize:
+        eng.peak_normalize(wav)
+    if s.limiter is not None:
+        eng.limit(wav, s.limiter[0], lookahead, s.limiter[2], n_samples=held)
+    if s.output is not None:
+        wavs = deliver_rows(eng, wav, held, s.output, seed)
+    else:
+        wavs = eng.download_rows(wav, held)
+    for a in (mel, linear, mag, warped, wav):
+        a.free()
+    result = (wavs,)
+    if s.marks:
+        all_marks = []
+        for b, (processed, spans) in enumerate(texts):
+            place = lambda x, seg=per_row[b]: float(hop) * prosody.warp_position(seg, x / float(hop), 'right')
+            place_end = lambda x, seg=per_row[b]: float(hop) * prosody.warp_position(seg, x / float(hop), 'left')
+            all_marks.append(marks_.marks_of_row(processed, spans, start[b], r, hop, 1.0, hop * (int(n_frames[b]) - 1), hp.sampling_rate,
+                                                 output_rate(hp, s.output), len(wavs[b]), s.marks, raw=plains[b], stats=stats[b],
+                                                 place=place, place_end=place_end))
+        result += (all_marks,)
+    if want_plan:
+        result += (dict(plain=plains, start=start, n_sent=n_sent, n_frames=n_frames, segments=per_row, n_out=n_out),)
+    return result if len(result) > 1 else wavs
+
+
+def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, **kw):
+    """``synthesize_sentences`` for sentences with prosody markup (``synthesize_marked``; ``kw``: its settings): ``{i+1}.wav`` per
+    sentence -- peak-normalised unless a ``loudness`` or a ``limiter`` is set -- and, with ``marks``, ``{i+1}.marks.jsonl`` beside it
+    with offsets into the sentence with the markup removed.  Returns the list of waveforms, with ``marks`` ``(waveforms, marks)``."""
+    # (ValueError before anything is loaded)
+    s = SynthSettings(model_params, **kw)
+    if s.octaves != 0.0:
+        raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global)')
+    for text in raw_sentences:
+        prosody.parse_markup(text)
+    from ..datasets.lj_speech import LJSpeechDatasetHelper
+    out_dir = out_dir or inference_params.synthesis_dir
+    if not os.path.isdir(out_dir):
+        raise NotADirectoryError('The specified synthesis target folder does not exist.')
+    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
+                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
+    model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
+    norm = s.loud is None and s.limiter is None
+    result = synthesize_marked(model, raw_sentences, dataset, seed=seed, peak_normalize=norm and s.output is not None, **kw)
+    wavs, all_marks = result if s.marks else (result, None)
+    for i, wav in enumerate(wavs):
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, s.output), norm and s.output is None,
+                 encoding=output_encoding(s.output))
+        if all_marks is not None:
+            marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), all_marks[i])
+    return (list(wavs), all_marks) if s.marks else list(wavs)
+
+
 # The pause behind a piece by the break that ends it, in milliseconds.  Untuned: round figures in the range speech synthesizers
 # commonly use, not measured against recordings.
 PAUSES_MS = {'paragraph': 700.0, 'sentence': 350.0, 'clause': 120.0, 'word': 0.0, 'cut': 0.0}
@@ -788,6 +921,7 @@ def main(argv=None):
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
                                                             [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
+                                                            [--markup]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
@@ -816,7 +950,11 @@ def main(argv=None):
     twice in a row mark a paragraph break inside a line) -- and ``{i+1}.wav`` holds the whole text (``synthesize_text``): split
     into pieces of at most ``--max-chars`` characters (default 150), each stopped at its silence (``--stop-at-silence``, -40 dB
     unless given), joined on the device with the pause of its break (``--pause-ms sentence=350``, repeatable; paragraph,
-    sentence, clause, word, cut) and edge fades of ``--fade-ms`` (default 5).  With ``--loudness`` a text is levelled as a whole."""
+    sentence, clause, word, cut) and edge fades of ``--fade-ms`` (default 5).  With ``--loudness`` a text is levelled as a whole.
+    ``--markup``: every line of the synthesis file is a sentence with prosody markup (``tacotron.prosody``, a subset of SSML):
+    ``<prosody rate="80%" volume="-6 dB">``, ``<emphasis level="strong">`` and ``<break time="300ms"/>`` change the rate, the volume
+    and the pauses word by word (``synthesize_marked``; ``--rate`` is then the base rate).  Works with ``--marks``, whose offsets are
+    then into the line with the markup removed; refused together with ``--text``, ``--pitch`` and ``--check-alignment``."""
     args = parse_args(argv)
     s = SynthSettings(model_params, args.momentum, args.stop_at_silence, args.silence_keep_ms, args.rate, pitch_semitones=args.pitch,
                       phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
@@ -839,7 +977,11 @@ def main(argv=None):
         weights = inference_params.checkpoint_file
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
-    if args.text:
+    if args.markup:
+        wavs = synthesize_marked_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
+                                           output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump,
+                                           **dict(s.keywords(), pitch=0.0))
+    elif args.text:
         kw = dict(s.keywords(), stop_at_silence_db=STOP_AT_SILENCE_DB if args.stop_at_silence is None else args.stop_at_silence)
         wavs = synthesize_texts(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
                                 check_alignment=args.check_alignment, max_chars=args.max_chars, pauses_ms=dict(args.pause_ms),
@@ -849,8 +991,8 @@ def main(argv=None):
                                     check_alignment=args.check_alignment, output=output_option(args), marks=args.marks,
                                     marks_max_jump=args.marks_max_jump, **s.keywords())
     if args.marks:
-        wavs = wavs[:-1] if args.check_alignment else wavs[0]
-    if args.check_alignment:
+        wavs = wavs[:-1] if args.check_alignment and not args.markup else wavs[0]
+    if args.check_alignment and not args.markup:
         wavs, report = wavs
         for row in report:
             print(json.dumps(row))
@@ -918,7 +1060,16 @@ def parse_args(argv=None):
                         ', '.join(BREAKS), ', '.join('{}={:g}'.format(k, PAUSES_MS[k]) for k in BREAKS)))
     ap.add_argument('--fade-ms', type=float, default=FADE_MS, metavar='MS',
                     help='with --text: the fade at either edge of a piece (default {:g} ms)'.format(FADE_MS))
+    ap.add_argument('--markup', action='store_true',
+                    help='every line of the synthesis file is a sentence with prosody markup: <prosody rate= volume=>, <emphasis>, <break/> '
+                         '(not with --text, --pitch or --check-alignment)')
     args = ap.parse_args(argv)
+    if args.markup and args.text:
+        ap.error('--markup cannot be combined with --text (markup inside long texts is not supported)')
+    if args.markup and args.pitch != 0.0:
+        ap.error('--markup cannot be combined with --pitch (a pitch needs the call pipeline\'s resampler)')
+    if args.markup and args.check_alignment:
+        ap.error('--markup cannot be combined with --check-alignment')
     if not hasattr(args, 'max_peak'):
         args.max_peak = LIMITED_MAX_PEAK if args.limit is not None and args.loudness is not None else LOUDNESS_MAX_PEAK
     return args

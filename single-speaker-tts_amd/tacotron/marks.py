@@ -115,7 +115,7 @@ def words_of(processed):
 
 
 def marks_of_row(processed, spans, start, r, hop, rate=1.0, n_held=None, rate_in=22050, rate_out=None, n_out=None, kind='word',
-                 raw=None, stats=None, place=None, spoken=True, offset=0):
+                 raw=None, stats=None, place=None, spoken=True, offset=0, place_end=None):
     """The marks of one row: a list of dicts, the 'sentence' mark first, then the words (``kind`` 'word') or the words and
     characters ('char') in the order they are spoken.
 
@@ -127,7 +127,9 @@ def marks_of_row(processed, spans, start, r, hop, rate=1.0, n_held=None, rate_in
     A mark: ``type``, ``time_ms`` and ``end_ms`` (float64, at the delivered rate's clock: 1000 * position / rate_in),
     ``sample`` and ``end_sample`` (``out_sample``), ``start`` and ``end`` (offsets into ``raw`` plus ``offset``), ``value``
     (``raw[start:end]``, or the processed characters where there is no raw text) and ``spoken``; the sentence mark also carries
-    ``reliable`` where ``stats`` is given.  ``spoken`` False (a dropped, silent piece): every mark has zero length at ``place(0)``."""
+    ``reliable`` where ``stats`` is given.  ``spoken`` False (a dropped, silent piece): every mark has zero length at ``place(0)``.
+    ``place_end``: what the END of a mark goes through instead of ``place`` (None: ``place``) -- a map that jumps, as
+    ``prosody.warp_position`` does across a pause, has two values at a border: where something ends and where the next thing starts."""
     n_tok = len(processed)
     if len(start) < n_tok + 1:
         raise ValueError('marks_of_row: {} tokens and the end token need {} start steps, got {}'.format(n_tok, n_tok + 1, len(start)))
@@ -136,13 +138,13 @@ def marks_of_row(processed, spans, start, r, hop, rate=1.0, n_held=None, rate_in
     rate_out = rate_in if rate_out is None else rate_out
     place = place or (lambda x: x)
 
-    def position(j):
-        return float(place(step_sample(int(start[j]), r, hop, rate, n_held) if spoken else 0.0))
+    def position(j, through=None):
+        return float((through or place)(step_sample(int(start[j]), r, hop, rate, n_held) if spoken else 0.0))
 
     limit = None if n_out is None else n_out
 
     def mark(kind_, a, b):            # tokens a .. b inclusive
-        x0, x1 = position(a), position(b + 1)
+        x0, x1 = position(a), position(b + 1, place_end)
         x1 = max(x1, x0)
         s0, e0 = (spans[a][0], spans[b][1]) if n_tok else (0, 0)
         n_lim = limit if limit is not None else out_sample(place(float(n_held)), rate_in, rate_out, float('inf'))

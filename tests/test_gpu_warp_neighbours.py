@@ -1,0 +1,36 @@
+"""tts_warp_magnitudes beside MFMA GEMM launches of ANOTHER handle (another set of streams): the same bits as alone and as the oracle,
+in the manner of tests/test_gpu_join_neighbours.py -- a server warps one batch while a second engine may be busy on the same chip.
+csrc/warp.hip: loads, stores and double arithmetic, no packed float32 arithmetic."""
+import numpy as np
+import pytest
+
+import warp_cases as C
+import warp_oracle as O
+from conftest import pkg
+from neighbour_fixture import neighbour   # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+
+def test_warp_beside_gemm_launches_of_another_handle(engine, neighbour):
+    H = pkg('_hip')
+    eng2, launch = neighbour
+    case = C.launch_seam()
+    x = C.poisoned(C.with_specials(C.batch(case['B'], 1025, case['T'])), case['n_frames'])
+    T_out = C.t_out_of(case)
+    want, _n = O.warp(x, case['segments'], case['n_frames'], T_out)
+
+    def run():
+        rc, got, around = C.raw_warp(engine, H, x, case['n_frames'], case['segments'], T_out, shift=1)
+        assert rc == 0 and (around == C.NAN_PATTERN).all()
+        return got
+
+    ref = run()
+    C.assert_same(ref, want, 'quiet')
+    bad = 0
+    for _ in range(6):
+        launch()
+        got = run()
+        eng2.synchronize()
+        bad += not np.array_equal(got, ref)
+    assert bad == 0, '%d of 6 results differ from the quiet run' % bad

@@ -7,15 +7,20 @@ de-normalise -> ``** magnitude_power`` -> Griffin-Lim -> ``{i+1}.wav``.
 Where the reference fans Griffin-Lim out to 6 worker processes, one utterance each
 (:185-188), the whole batch is reconstructed by one batched kernel sequence on the GPU.
 """
+import functools
+import inspect
 import json
 import logging
 import os
+import types
 
 import numpy as np
 
 from . import attention_check, marks as marks_, prosody
-from .._hip import (ALIGNMENT_RECORD, synth_frame_counts, token_times_jump, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, output_is_on, output_ratio, output_setting, resampled_length, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, phase_init_value, pitch_octaves_value, pitch_semitones_value,
-                    silence_keep_frames, speaking_rate_value, stop_at_silence_setting)
+from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK,
+                    limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
+                    output_setting, phase_init_value, pitch_octaves_value, pitch_semitones_value, resampled_length,
+                    silence_keep_frames, speaking_rate_value, stop_at_silence_setting, synth_frame_counts, token_times_jump)
 from ..audio.conversion import ms_to_samples
 from ..audio.io import save_wav
 from ..datasets.text_split import BREAKS, MAX_CHARS, abbreviations_of, split_text, split_text_spans
@@ -68,7 +73,7 @@ def stop_setting(hp, stop_at_silence_db, silence_keep_ms):
         return None
     if not float(silence_keep_ms) >= 0.0:
         raise ValueError('silence_keep_ms must be >= 0, got {!r}'.format(silence_keep_ms))
-    hp = getattr(hp, 'hparams', hp)   # (a model serves for its hyper-parameters: they are looked at only where stopping is asked for)
+    hp = getattr(hp, 'hparams', hp) or model_params   # (a model serves for its hyper-parameters, None for the default ones)
     hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
     return stop_at_silence_setting((stop_at_silence_db, silence_keep_frames(ms_to_samples(float(silence_keep_ms), hp.sampling_rate), hop)))
 
@@ -241,9 +246,100 @@ class SynthSettings(object):
         return dict(self.engine_keywords(), output=self.output)
 
     def keywords(self):
-        """the settings as the helpers of this layer take them (``check_alignment`` apart, which not every one takes)"""
+        """the settings as the stand-alone stages honour them (``serve.post_process_spectrograms``): the checked values, without
+        ``check_alignment``, ``output`` and the marks"""
         return dict(momentum=self.momentum, stop_at_silence_db=self.stop_at_silence_db, silence_keep_ms=self.silence_keep_ms,
                     speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter)
+
+    def file_norm(self):
+        """the peak normalisation of the file helpers, ``(on the device, in save_wav)``: none with a loudness or a limiter, else
+        ahead of the encoder where there is an ``output`` and on the way to the disk where the files are float32"""
+        norm = self.loud is None and self.limiter is None
+        return norm and self.output is not None, norm and self.output is None
+
+
+SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:]
+
+
+def takes_settings(*refuses, only=None):
+    """Makes a helper of this layer out of a function that takes ``**settings`` -- the keywords of ``SynthSettings``, all but
+    ``refuses`` or ``only`` those named -- and returns the parts of its answer by name, a dict (a generator: yields one per item).
+    The helper refuses the keywords it does not take as Python would (TypeError) and answers in the public form its docstring
+    states: the waveforms bare where they are the only part, else a tuple of the parts in the order they were put in.  The
+    callers inside this layer read the parts, from ``helper.parts``, the function itself; ``inspect.signature(helper)`` lists the
+    keywords the helper takes, with the record's defaults, in place of ``**settings``."""
+    if only is not None:
+        refuses = tuple(k for k in SETTING_KEYWORDS if k not in only)
+
+    def make(parts):
+        def taken(keywords):
+            for k in refuses:
+                if k in keywords:
+                    raise TypeError("{}() got an unexpected keyword argument '{}'".format(parts.__name__, k))
+            return keywords
+
+        def answer(named):
+            return tuple(named.values()) if len(named) > 1 else named['wavs']
+
+        if inspect.isgeneratorfunction(parts):
+            def helper(*args, **keywords):
+                for named in parts(*args, **taken(keywords)):
+                    yield answer(named)
+        else:
+            def helper(*args, **keywords):
+                return answer(parts(*args, **taken(keywords)))
+        functools.update_wrapper(helper, parts)
+        own = [p for p in inspect.signature(parts).parameters.values() if p.kind is not p.VAR_KEYWORD]
+        record = inspect.signature(SynthSettings.__init__).parameters
+        helper.__signature__ = inspect.Signature(own + [record[k].replace(kind=inspect.Parameter.KEYWORD_ONLY)
+                                                        for k in SETTING_KEYWORDS if k not in refuses])
+        helper.parts = parts
+        return helper
+    return make
+
+
+def call_constants(hp, n_steps=None, n_iter=None):
+    """What the calls of this layer are made with, of a model or of hyper-parameters alone: ``win_len`` and ``hop`` in samples,
+    the loader's dB pair, Griffin-Lim's ``n_iter`` and the decoder steps ``S`` (the model's unless given, None without a model)
+    with their frames ``T``, and ``synth``: what ``Engine.synthesize`` and ``synthesize_host`` take behind the ids."""
+    model, hp = hp, getattr(hp, 'hparams', hp)
+    loader = dataset_params.dataset_loader
+    c = types.SimpleNamespace(win_len=ms_to_samples(hp.win_len, hp.sampling_rate), hop=ms_to_samples(hp.win_hop, hp.sampling_rate),
+                              ref_db=loader.mel_mag_ref_db, max_db=loader.mel_mag_max_db,
+                              n_iter=hp.reconstruction_iterations if n_iter is None else n_iter,
+                              S=n_steps or (model.n_steps() if hasattr(model, 'n_steps') else None))
+    c.T = None if c.S is None else c.S * hp.reduction
+    c.synth = (c.S, c.ref_db, c.max_db, hp.magnitude_power, c.n_iter, c.win_len, c.hop)
+    return c
+
+
+def held_samples(c, s, n_frames, B):
+    """The samples each of a call's B rows holds at the model's rate, (B,) int64: hop (n_frames[b] - 1) of the frame counts a call
+    with stopping reports, or (``n_frames`` None) the call's hop (T' - 1) in every row.  ``c``: the call's ``call_constants``."""
+    if n_frames is None:
+        n_frames = [synth_frame_counts(c.T, s.rate, 0.0)[0]] * B
+    return c.hop * (np.asarray(n_frames, dtype=np.int64) - 1)
+
+
+def finishing_tail(caller, s, sampling_rate, deliver=True):
+    """The tail behind a Griffin-Lim that a helper composes of stand-alone stages.  The limiter's look-ahead becomes samples here,
+    before an engine is touched (ValueError that names ``caller``); the function returned then runs, on device rows (B, N) that
+    hold ``held[b]`` samples each (None: all N), the ``loudness`` or else a peak normalisation (``peak_normalize``), the ``limiter``,
+    and hands back ``deliver_rows`` for an ``output`` (with ``deliver``; the dither's ``seed``) or else the rows downloaded, a list
+    of B arrays cut to what they hold.  ``rows`` stays the caller's to free."""
+    lookahead = None if s.limiter is None else limiter_lookahead(caller, s.limiter[1], sampling_rate)
+
+    def finish(engine, rows, held, seed=0, peak_normalize=False):
+        if s.loud is not None:
+            engine.loudness_normalize(rows, sampling_rate, s.loud[0], s.loud[1], n_samples=held)
+        elif peak_normalize:
+            engine.peak_normalize(rows)
+        if s.limiter is not None:
+            engine.limit(rows, s.limiter[0], lookahead, s.limiter[2], n_samples=held)
+        if deliver and s.output is not None:
+            return deliver_rows(engine, rows, held, s.output, seed)
+        return list(rows.to_host()) if held is None else engine.download_rows(rows, held)
+    return finish
 
 
 def marks_of_batch(hp, s, ids, start, stats, n_held, wavs, mark_texts=None):
@@ -265,50 +361,38 @@ def marks_of_batch(hp, s, ids, start, stats, n_held, wavs, mark_texts=None):
     return out
 
 
-def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False,
-                     momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                     phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None, marks=None, marks_max_jump=4,
-                     mark_texts=None):
+@takes_settings()
+def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=None, seed=0, peak_normalize=False, mark_texts=None,
+                     **settings):
     """ids (B, T_sent) -> waveforms (B, hop*(T-1)) float32: inference() + the synthesize() closure
-    of the reference (tacotron/inference.py:170-188) fused into one device call.  The settings from ``momentum`` on: as
-    ``SynthSettings`` has them.  With ``stop_at_silence_db`` the result is a list of B waveforms, with ``check_alignment`` it is
+    of the reference (tacotron/inference.py:170-188) fused into one device call.  ``settings``: the keywords of
+    ``SynthSettings``.  With ``stop_at_silence_db`` the result is a list of B waveforms, with ``check_alignment`` it is
     ``(waveforms, records, verdicts)``.  With an ``output`` the waveforms are that format's codes at its rate, made of the call's
     device rows (``deliver_rows``; the dither's seed is ``seed``).  With ``marks`` the result gains, as its last element, a list of
     timing marks per row -- of the processed characters of the ids, with offsets into that string (``mark_texts``: of raw texts)."""
-    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
-    hp = model.hparams
-    loader = dataset_params.dataset_loader
-    win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
-    win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
-    S = n_steps or model.n_steps()
-    out = model.engine.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), S, loader.mel_mag_ref_db,
-                                  loader.mel_mag_max_db, hp.magnitude_power,
-                                  hp.reconstruction_iterations if n_iter is None else n_iter, win_len, win_hop,
-                                  init_phase=init_phase, seed=seed, peak_normalize=peak_normalize, **s.engine_keywords())
+    s = SynthSettings(model, **settings)
+    c = call_constants(model, n_steps, n_iter)
+    eng, B = model.engine, len(sentences)
+    out = eng.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), *c.synth, init_phase=init_phase, seed=seed,
+                         peak_normalize=peak_normalize, **s.engine_keywords())
+    n_frames = out['n_frames'] if s.stop is not None else None
     if s.output is not None:
-        held = win_hop * (np.asarray(out['n_frames'], dtype=np.int32) - 1) if s.stop is not None else None
-        wavs = deliver_rows(model.engine, out['wav'], held, s.output, seed)
+        wavs = deliver_rows(eng, out['wav'], None if n_frames is None else held_samples(c, s, n_frames, B), s.output, seed)
     else:
-        wavs = cut_waveforms(out['wav'].to_host(), out['n_frames'], win_hop) if s.stop is not None else out['wav'].to_host()
-    result = (wavs,)
-    if check_alignment:
-        records = model.engine.synth_alignment_stats(len(sentences))
-        result += (records, attention_check.verdict(records))
+        wavs = out['wav'].to_host() if n_frames is None else cut_waveforms(out['wav'].to_host(), n_frames, c.hop)
+    parts = dict(wavs=wavs)
+    if s.check_alignment:
+        parts['records'] = eng.synth_alignment_stats(B)
+        parts['verdicts'] = attention_check.verdict(parts['records'])
     if s.marks:
-        start, stats = model.engine.synth_token_times(len(sentences))
-        if s.stop is None:   # (every row holds the call's hop (T' - 1) samples)
-            n_held = [win_hop * (synth_frame_counts(S * hp.reduction, s.rate, 0.0)[0] - 1)] * len(start)
-        else:
-            n_held = win_hop * (np.asarray(out['n_frames'], dtype=np.int64) - 1)
-        result += (marks_of_batch(hp, s, np.asarray(sentences), start, stats, n_held, wavs, mark_texts),)
-    return result if len(result) > 1 else wavs
+        start, stats = eng.synth_token_times(B)
+        parts['marks'] = marks_of_batch(model, s, np.asarray(sentences), start, stats, held_samples(c, s, n_frames, B), wavs, mark_texts)
+    return parts
 
 
+@takes_settings()
 def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_normalize=False, copy=False, want_linear=False,
-                      want_alignments=False, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS,
-                      speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None, check_alignment=False, limiter=None,
-                      output=None, marks=None, marks_max_jump=4, mark_texts=None):
+                      want_alignments=False, mark_texts=None, **settings):
     """Generator over batches of padded id sequences (each (B, T_sent) int32, HOST arrays) -> per batch the waveforms
     (B, hop*(T-1)) float32 in host memory, with THREE batches in flight: batch k + 2 is uploaded and encoded, batch k + 1
     is in its decoder, batch k in its post-net / Griffin-Lim while batch k - 1 is being downloaded (the reference runs the
@@ -318,7 +402,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     With ``want_linear`` / ``want_alignments`` every item is a tuple ``(wavs, linear, alignments)``: the normalised linear
     spectrograms (B, T, 1025) -- what ``model.output_linear_spec`` is, the thing the reference's ``inference()`` fetches
     (:75-92) -- and the alignments (n_steps, B, T_sent) of the same call, downloaded behind the waveforms (None where not
-    asked for).  The settings from ``momentum`` on: as ``SynthSettings`` has them.  With ``stop_at_silence_db`` the waveforms
+    asked for).  ``settings``: the keywords of ``SynthSettings``.  With ``stop_at_silence_db`` the waveforms
     of a batch are a list of B arrays (views of the pinned rows unless ``copy``), each cut to its own length.  With
     ``check_alignment`` every item additionally carries the batch's alignment records and verdicts, ``(wavs, records,
     verdicts)`` or ``(wavs, linear, alignments, records, verdicts)``; the 56 bytes per utterance come down with the waveforms.
@@ -329,17 +413,9 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     characters of the ids -- or, with ``mark_texts``, an iterator that gives per batch what ``synthesize_batch`` takes by that name,
     of raw texts); the 4 T_sent + 36 bytes per utterance come down with the waveforms."""
     # (a generator: a bad setting is refused at its first item, before the engine is touched)
-    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
-    hp = model.hparams
-    loader = dataset_params.dataset_loader
-    win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
-    win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
-    S = n_steps or model.n_steps()
-    it = hp.reconstruction_iterations if n_iter is None else n_iter
+    s = SynthSettings(model, **settings)
+    c = call_constants(model, n_steps, n_iter)
     eng = model.engine
-    extra = want_linear or want_alignments
-
     served = [0]   # utterances answered so far: what a clipped row is logged by
 
     def waveforms(ticket):
@@ -351,61 +427,48 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
         if s.stop is None:
             return eng.wait_host(ticket, copy=copy)
         n_frames = eng.wait_host_frames(ticket)
-        return cut_waveforms(eng.wait_host(ticket, copy=copy), n_frames, win_hop)
+        return cut_waveforms(eng.wait_host(ticket, copy=copy), n_frames, c.hop)
 
-    sent = {}   # ticket -> its ids, while the marks of the call are still to be made
-
-    def marked(ticket, wavs):
-        ids, texts = sent.pop(ticket)
-        if not s.marks:
-            return ()
-        start, stats = eng.wait_host_token_times(ticket)
-        if s.stop is None:   # (every row holds the call's hop (T' - 1) samples)
-            held = np.full(len(start), win_hop * (synth_frame_counts(S * hp.reduction, s.rate, 0.0)[0] - 1), dtype=np.int64)
-        else:
-            held = win_hop * (eng.wait_host_frames(ticket).astype(np.int64) - 1)
-        return (marks_of_batch(hp, s, ids, start, stats, held, wavs, texts),)
-
-    def collect(ticket):
-        checked = ()
-        if check_alignment:
-            records = eng.wait_host_alignment_stats(ticket)
-            checked = (records, attention_check.verdict(records))
-        if not extra:
-            wavs = waveforms(ticket)
-            checked += marked(ticket, wavs)
-            return ((wavs,) + checked) if checked else wavs
-        lin, ali = eng.wait_host_outputs(ticket, copy=copy)
-        wavs = waveforms(ticket)
-        return (wavs, lin, ali) + checked + marked(ticket, wavs)
+    def collect(ticket, ids, texts):
+        records = eng.wait_host_alignment_stats(ticket) if s.check_alignment else None
+        outputs = eng.wait_host_outputs(ticket, copy=copy) if want_linear or want_alignments else None
+        parts = dict(wavs=waveforms(ticket))
+        if outputs is not None:
+            parts['linear'], parts['alignments'] = outputs
+        if records is not None:
+            parts['records'], parts['verdicts'] = records, attention_check.verdict(records)
+        if s.marks:
+            start, stats = eng.wait_host_token_times(ticket)
+            held = held_samples(c, s, eng.wait_host_frames(ticket) if s.stop is not None else None, len(start))
+            parts['marks'] = marks_of_batch(model, s, ids, start, stats, held, parts['wavs'], texts)
+        return parts
 
     # three batches in flight (the library's three buffer sets): the encoder of batch k + 2 runs one inter-Griffin-Lim gap
     # ahead of its decoder, which follows the decoder of batch k + 1 without a pause, beside the Griffin-Lim of batch k
-    pending = []
+    pending = []   # (ticket, its ids, what its marks take of the raw texts)
     for k, ids in enumerate(batches):
-        pending.append(eng.synthesize_host(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len,
-                                           win_hop, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
-                                           want_alignments=want_alignments, **s.host_keywords()))
-        sent[pending[-1]] = (np.asarray(ids), next(mark_texts) if s.marks and mark_texts is not None else None)
+        ticket = eng.synthesize_host(ids, *c.synth, seed=seed + k, peak_normalize=peak_normalize, want_linear=want_linear,
+                                     want_alignments=want_alignments, **s.host_keywords())
+        pending.append((ticket, np.asarray(ids), next(mark_texts) if s.marks and mark_texts is not None else None))
         if len(pending) == 3:
-            yield collect(pending.pop(0))
+            yield collect(*pending.pop(0))
     while pending:
-        yield collect(pending.pop(0))
+        yield collect(*pending.pop(0))
 
 
-def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum=0.0, phase_init='random'):
+@takes_settings(only=('momentum', 'phase_init'))
+def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, **settings):
     """``inference()`` over a stream of batches with three calls in flight: per batch ``(spectrograms, waveforms)`` where
     ``spectrograms`` is what the reference's ``inference()`` returns for that batch -- per utterance the (1025, T) linear
     magnitude spectrogram ``decibel_to_magnitude(inv_normalize_decibel(spec.T, mel_ref_db, mel_max_db))``
     (tacotron/inference.py:93-101; computed on the host from the downloaded network output with the conversions of
     ``audio.conversion``) -- and ``waveforms`` the Griffin-Lim reconstructions the reference's ``__main__`` makes of them
-    (:170-188).  ``momentum`` and ``phase_init`` as in ``synthesize_stream``."""
-    s = SynthSettings(None, momentum=momentum, phase_init=phase_init)
+    (:170-188).  ``settings``: ``momentum`` and ``phase_init`` as in ``synthesize_stream``, and no other."""
     loader = dataset_params.dataset_loader
     ref_db, max_db = np.float32(loader.mel_mag_ref_db), np.float32(loader.mel_mag_max_db)
     rng_db = np.float32(abs(float(ref_db)) + abs(float(max_db)))
-    for wavs, lin, _ in synthesize_stream(model, batches, n_steps=n_steps, n_iter=n_iter, seed=seed, copy=True, want_linear=True,
-                                          **s.keywords()):
+    for parts in synthesize_stream.parts(model, batches, n_steps, n_iter, seed, copy=True, want_linear=True, **settings):
+        lin = parts['linear']
         specs = []
         for b in range(lin.shape[0]):
             # inv_normalize_decibel, decibel_to_magnitude (reference audio/conversion.py:81-102, 32-53) in host arithmetic:
@@ -413,19 +476,61 @@ def inference_stream(model, batches, n_steps=None, n_iter=None, seed=0, momentum
             db = (np.clip(lin[b].T, np.float32(0), np.float32(1)) - np.float32(1)) * rng_db + ref_db
             assert not (db < -100.0).any(), 'decibel_to_magnitude: values below -100 dB'
             specs.append(np.power(np.float32(10), db / np.float32(20)).astype(np.float32))
-        yield specs, wavs
+        yield dict(specs=specs, wavs=parts['wavs'])
 
 
-def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, momentum=0.0,
-                         stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
-                         phase_init='random', loudness=None, check_alignment=False, limiter=None, output=None, marks=None,
-                         marks_max_jump=4):
+def target_dir(out_dir):
+    """the folder the files go to -- ``inference_params.synthesis_dir`` unless given --, which has to exist (reference
+    tacotron/inference.py:131-133)"""
+    out_dir = out_dir or inference_params.synthesis_dir
+    if not os.path.isdir(out_dir):
+        raise NotADirectoryError('The specified synthesis target folder does not exist.')
+    return out_dir
+
+
+def open_model(weights, dataset, device_id):
+    """``(dataset, model)``: the LJSpeech helper where no dataset is given, and the model with ``weights`` restored"""
+    from ..datasets.lj_speech import LJSpeechDatasetHelper
+    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
+                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
+    return dataset, Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
+
+
+def open_files(weights, dataset, out_dir, device_id):
+    """what the file helpers do ahead of their synthesis: ``(out_dir, dataset, model)`` of ``target_dir`` and ``open_model``"""
+    return (target_dir(out_dir),) + open_model(weights, dataset, device_id)
+
+
+def write_files(out_dir, s, parts):
+    """What the file helpers do behind it, with the ``parts`` of the synthesis: ``{i+1}.marks.jsonl`` of the ``marks``,
+    ``alignment_report.json`` of the ``records`` (every row with the index of its ``text`` where there is a ``piece_text``) and
+    ``{i+1}.wav`` of the ``wavs``, in the format and at the rate of the ``output``; float32 files are peak-normalised on the way
+    (``SynthSettings.file_norm``) unless they are empty.  Returns the helper's own parts: ``wavs`` as a list, ``report``, ``marks``."""
+    written = dict(wavs=list(parts['wavs']))
+    for i, m in enumerate(parts.get('marks', ())):
+        marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), m)
+    if 'records' in parts:
+        written['report'] = attention_check.report(parts['records'])
+        for row, t in zip(written['report'], parts.get('piece_text', ())):
+            row['text'] = int(t)
+        with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
+            json.dump(written['report'], f, indent=1)
+    for i, wav in enumerate(written['wavs']):
+        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, s.output),
+                 s.file_norm()[1] and len(wav) > 0, encoding=output_encoding(s.output))
+    if 'marks' in parts:
+        written['marks'] = parts['marks']
+    return written
+
+
+@takes_settings()
+def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, **settings):
     """The reference's ``__main__`` (tacotron/inference.py:130-200) as a function.
 
     raw text lines -> process_sentences -> pad -> model -> wavs -> ``{i+1}.wav`` (peak-normalised
     float32 WAV, save_wav(norm=True)).  Returns the list of waveforms.  With ``stop_at_silence_db`` every file ends
     ``silence_keep_ms`` behind its utterance's last frame above that threshold instead of after max_iterations frames.
-    The other settings from ``momentum`` on: as ``SynthSettings`` has them (a ``speaking_rate`` of 1.2: a fifth faster; a
+    ``settings``: the keywords of ``SynthSettings`` (a ``speaking_rate`` of 1.2: a fifth faster; a
     ``pitch`` of 4 / 12: four semitones up).  With a ``loudness`` or a ``limiter`` the files hold the waveforms as the device left
     them, not peak-normalised.  With ``check_alignment`` the result is ``(waveforms, report)`` with ``report`` the list of ``{index,
     verdict, record}`` of ``attention_check.report``, also written to ``alignment_report.json`` beside the wavs.  With an
@@ -434,46 +539,28 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     gains, as its last element, the timing marks of every sentence with offsets into the RAW sentence, also written as
     ``{i+1}.marks.jsonl`` beside every wav (``marks.write_marks``); a sentence the front end cannot be mapped back to raises
     ValueError (``marks.token_spans``)."""
-    # (ValueError before anything is loaded)
-    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
-    from ..datasets.lj_speech import LJSpeechDatasetHelper
-    out_dir = out_dir or inference_params.synthesis_dir
-    if not os.path.isdir(out_dir):
-        raise NotADirectoryError('The specified synthesis target folder does not exist.')
-    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
-                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
+    s = SynthSettings(model_params, **settings)   # (ValueError before anything is loaded)
+    out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
     mark_texts = [(raw,) + marks_.token_spans(dataset, raw) for raw in raw_sentences] if s.marks else None
     id_sequences, sequence_lengths = dataset.process_sentences(raw_sentences)
-    sentences = [np.frombuffer(s, dtype=np.int32) for s in id_sequences]
     max_length = max(sequence_lengths)
-    sentences = np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
-    model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    norm = s.loud is None and s.limiter is None
-    wavs = synthesize_batch(model, sentences, seed=seed, peak_normalize=norm and s.output is not None, check_alignment=check_alignment,
-                            output=output, marks=marks, marks_max_jump=marks_max_jump, mark_texts=mark_texts, **s.keywords())
-    report = None
-    all_marks = None
-    if s.marks:
-        wavs, all_marks = wavs[:-1], wavs[-1]
-        wavs = wavs if check_alignment else wavs[0]
-        for i, m in enumerate(all_marks):
-            marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), m)
-    if check_alignment:
-        wavs, records, _verdicts = wavs
-        report = attention_check.report(records)
-        with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
-            json.dump(report, f, indent=1)
-    for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, s.output), norm and s.output is None,
-                 encoding=output_encoding(s.output))
-    result = (list(wavs),) + ((report,) if check_alignment else ()) + ((all_marks,) if s.marks else ())
-    return result if len(result) > 1 else result[0]
+    sentences = np.array([pad_sentence(np.frombuffer(q, dtype=np.int32), max_length) for q in id_sequences], dtype=np.int32)
+    return write_files(out_dir, s, synthesize_batch.parts(model, sentences, seed=seed, peak_normalize=s.file_norm()[0], mark_texts=mark_texts,
+                                                          **settings))
 
 
-def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=None, seed=0, peak_normalize=False, momentum=0.0,
-                      stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random',
-                      loudness=None, limiter=None, output=None, marks=None, marks_max_jump=4, want_plan=False):
+def marked_settings(hp, settings):
+    """the record of ``synthesize_marked``, for itself and for its file form: no pitch"""
+    s = SynthSettings(hp, **settings)
+    if s.octaves != 0.0:
+        raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global), got {!r}'.format(
+            settings.get('pitch') if settings.get('pitch_semitones') is None else settings['pitch_semitones']))
+    return s
+
+
+@takes_settings('check_alignment')
+def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=None, seed=0, peak_normalize=False, want_plan=False,
+                      **settings):
     """Sentences with prosody markup (``tacotron.prosody``: ``<prosody rate=.. volume=..>``, ``<emphasis>``, ``<break/>`` under an
     optional ``<speak>``) -> a list of B waveforms, row b cut to its own hop (n_out[b] - 1) samples (no reference counterpart).
 
@@ -492,15 +579,10 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
     ``prosody.warp_position``: a slowed word's mark grows with it, a break opens a gap between two words' marks; ``start`` and
     ``end`` of a mark are offsets into the sentence with the markup removed); with ``want_plan`` a last element ``dict(plain,
     start, n_sent, n_frames, segments, n_out)``: what the call planned from, per row."""
-    s = SynthSettings(model, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, False,
-                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
-    if s.octaves != 0.0:
-        raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global), got {!r}'.format(pitch))
+    s = marked_settings(model, settings)
     hp = model.hparams
-    loader = dataset_params.dataset_loader
-    win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
-    hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
-    r = hp.reduction
+    c = call_constants(model, n_steps, n_iter)
+    hop, r = c.hop, hp.reduction
     parsed = [prosody.parse_markup(text) for text in marked_sentences]
     if not parsed:
         raise ValueError('synthesize_marked: no sentence')
@@ -515,21 +597,18 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
                 b + 1, int(n_sent[b]), len(processed)))
     ids = np.array([pad_sentence(q, max(n_sent)) for q in rows], dtype=np.int32)
     n_sent = np.asarray(n_sent, dtype=np.int32)
-    B = ids.shape[0]
-    S = n_steps or model.n_steps()
-    T = S * r
-    it = hp.reconstruction_iterations if n_iter is None else n_iter
+    B, T = ids.shape[0], c.T
     eng = model.engine
     min_frames = (hp.n_fft // 2) // hop + 2      # Griffin-Lim's least: hop (n - 1) > n_fft / 2
-    lookahead = None if s.limiter is None else limiter_lookahead('synthesize_marked', s.limiter[1], eng.sampling_rate)
+    finish = finishing_tail('synthesize_marked', s, eng.sampling_rate)
     memory = eng.encoder_forward(ids)
-    mel, alignments = eng.decoder_forward(memory, S)
+    mel, alignments = eng.decoder_forward(memory, c.S)
     d_start, d_stats = eng.token_times(alignments, n_sent=n_sent, max_jump=s.marks_max_jump, to_host=False)
     mel.shape = (B, T, hp.n_mels)
     linear = eng.postnet_forward(mel)
     d_frames = d_last = None
     if s.stop is not None:
-        threshold = eng.speech_threshold(s.stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
+        threshold = eng.speech_threshold(s.stop[0], c.ref_db, c.max_db)
         d_frames, d_last = eng.speech_frames(linear, threshold, s.stop[1], min_frames)
     start = d_start.to_host()                    # (the one host wait)
     stats = d_stats.to_host()
@@ -543,25 +622,15 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
         per_row.append(seg)
         segments += seg
         n_out.append(n)
-    mag = eng.denorm_power(linear, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power)
+    mag = eng.denorm_power(linear, c.ref_db, c.max_db, hp.magnitude_power)
     warped, _n = eng.warp_magnitudes(mag, segments, n_frames)
     assert _n.tolist() == n_out, (_n, n_out)
-    wav, _mse = eng.griffin_lim(warped, it, win_len, hop, hp.n_fft, seed=seed, want_mse=False, momentum=s.momentum, n_frames=n_out,
+    wav, _mse = eng.griffin_lim(warped, c.n_iter, c.win_len, hop, hp.n_fft, seed=seed, want_mse=False, momentum=s.momentum, n_frames=n_out,
                                 phase_init=s.phase_init)
-    held = hop * (np.asarray(n_out, dtype=np.int32) - 1)
-    if s.loud is not None:
-        eng.loudness_normalize(wav, eng.sampling_rate, s.loud[0], s.loud[1], n_samples=held)
-    elif peak_normalize:
-        eng.peak_normalize(wav)
-    if s.limiter is not None:
-        eng.limit(wav, s.limiter[0], lookahead, s.limiter[2], n_samples=held)
-    if s.output is not None:
-        wavs = deliver_rows(eng, wav, held, s.output, seed)
-    else:
-        wavs = eng.download_rows(wav, held)
+    wavs = finish(eng, wav, hop * (np.asarray(n_out, dtype=np.int32) - 1), seed, peak_normalize)
     for a in (mel, linear, mag, warped, wav):
         a.free()
-    result = (wavs,)
+    parts = dict(wavs=wavs)
     if s.marks:
         all_marks = []
         for b, (processed, spans) in enumerate(texts):
@@ -570,38 +639,22 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
             all_marks.append(marks_.marks_of_row(processed, spans, start[b], r, hop, 1.0, hop * (int(n_frames[b]) - 1), hp.sampling_rate,
                                                  output_rate(hp, s.output), len(wavs[b]), s.marks, raw=plains[b], stats=stats[b],
                                                  place=place, place_end=place_end))
-        result += (all_marks,)
+        parts['marks'] = all_marks
     if want_plan:
-        result += (dict(plain=plains, start=start, n_sent=n_sent, n_frames=n_frames, segments=per_row, n_out=n_out),)
-    return result if len(result) > 1 else wavs
+        parts['plan'] = dict(plain=plains, start=start, n_sent=n_sent, n_frames=n_frames, segments=per_row, n_out=n_out)
+    return parts
 
 
-def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, **kw):
-    """``synthesize_sentences`` for sentences with prosody markup (``synthesize_marked``; ``kw``: its settings): ``{i+1}.wav`` per
+@takes_settings('check_alignment')
+def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, **settings):
+    """``synthesize_sentences`` for sentences with prosody markup (``synthesize_marked``; ``settings``: its settings): ``{i+1}.wav`` per
     sentence -- peak-normalised unless a ``loudness`` or a ``limiter`` is set -- and, with ``marks``, ``{i+1}.marks.jsonl`` beside it
     with offsets into the sentence with the markup removed.  Returns the list of waveforms, with ``marks`` ``(waveforms, marks)``."""
-    # (ValueError before anything is loaded)
-    s = SynthSettings(model_params, **kw)
-    if s.octaves != 0.0:
-        raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global)')
+    s = marked_settings(model_params, settings)   # (ValueError before anything is loaded)
     for text in raw_sentences:
         prosody.parse_markup(text)
-    from ..datasets.lj_speech import LJSpeechDatasetHelper
-    out_dir = out_dir or inference_params.synthesis_dir
-    if not os.path.isdir(out_dir):
-        raise NotADirectoryError('The specified synthesis target folder does not exist.')
-    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
-                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
-    model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    norm = s.loud is None and s.limiter is None
-    result = synthesize_marked(model, raw_sentences, dataset, seed=seed, peak_normalize=norm and s.output is not None, **kw)
-    wavs, all_marks = result if s.marks else (result, None)
-    for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, s.output), norm and s.output is None,
-                 encoding=output_encoding(s.output))
-        if all_marks is not None:
-            marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), all_marks[i])
-    return (list(wavs), all_marks) if s.marks else list(wavs)
+    out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
+    return write_files(out_dir, s, synthesize_marked.parts(model, raw_sentences, dataset, seed=seed, peak_normalize=s.file_norm()[0], **settings))
 
 
 # The pause behind a piece by the break that ends it, in milliseconds.  Untuned: round figures in the range speech synthesizers
@@ -713,18 +766,27 @@ def join_list_of_call(piece_text, piece_break, n_frames, first_active, hop, paus
     return np.array(pieces, dtype=np.int64).reshape(-1, 4), np.array(groups, dtype=np.int64), texts, tail, orphans
 
 
+def text_plan(caller, hp, pauses_ms, fade_ms, settings):
+    """What ``synthesize_text`` checks ahead of everything else, for itself and for its file form: ``(record, pauses, fade)`` --
+    the ``settings`` with ``stop_at_silence_db`` at -40 dB unless given, which cannot be None; ``pause_samples``; ``fade_samples``."""
+    s = SynthSettings(hp, **dict({'stop_at_silence_db': STOP_AT_SILENCE_DB}, **settings))
+    if s.stop is None:
+        raise ValueError('{}: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)'.format(caller))
+    rate = getattr(hp, 'hparams', hp).sampling_rate
+    return s, pause_samples(pauses_ms, rate), fade_samples(fade_ms, rate)
+
+
+@takes_settings()
 def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_ms=FADE_MS, lead_trim=True, max_chars=MAX_CHARS,
-                    n_steps=None, n_iter=None, seed=0, check_alignment=False, output=None, peak_normalize=False, marks=None,
-                    marks_max_jump=4, **settings):
+                    n_steps=None, n_iter=None, seed=0, peak_normalize=False, **settings):
     """Texts of any length -> one float32 waveform per text (no reference counterpart: tacotron/inference.py:139-200 makes one
     file of at most max_iterations frames per line).
 
     Every text is split into pieces of at most ``max_chars`` characters (``datasets.text_split.split_text`` with the dataset's
     abbreviations), the pieces become ids (``process_sentences``, ``pad_sentence``) and are packed in order into calls of at most
     ``batch_size`` rows (``pack_pieces``); call k runs ``Engine.synthesize`` with seed ``seed`` + k, no normalisation, and leaves
-    its waveforms on the device.  ``settings``: the keywords of ``SynthSettings`` (momentum, stop_at_silence_db, silence_keep_ms,
-    speaking_rate, pitch, pitch_semitones, phase_init, loudness, limiter); ``stop_at_silence_db`` defaults to -40 dB here and cannot be
-    None, because a piece that runs on to max_iterations frames is of no use in a joined text.
+    its waveforms on the device.  ``settings``: the keywords of ``SynthSettings``; ``stop_at_silence_db`` defaults to -40 dB here and
+    cannot be None, because a piece that runs on to max_iterations frames is of no use in a joined text.
 
     Piece b of a call is cut from its row as ``first = hop * lead`` and ``count = hop * (n_frames[b] - 1) - first``, with lead =
     ``lead_frames(first_active[b], speaking_rate, keep_frames)`` -- ``first_active`` from ``Engine.speech_interval`` on the call's
@@ -749,40 +811,29 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     index of the text each piece belongs to.  With ``marks`` ('word' or 'char') the result gains, as its last element, the timing
     marks of every text in ITS waveform (``marks.marks_of_text``): every piece's marks taken through its lead trim, the join's
     layout and the parts of a text that span calls, with offsets into the raw text; a dropped piece's marks have no length."""
-    if settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB) is None:
-        raise ValueError('synthesize_text: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)')
-    settings.setdefault('stop_at_silence_db', STOP_AT_SILENCE_DB)
-    loud = loudness_setting(settings.pop('loudness', None))
-    limiter = limiter_setting(settings.pop('limiter', None))
-    s = SynthSettings(model, check_alignment=check_alignment, marks=marks, marks_max_jump=marks_max_jump, **settings)
-    out_setting = output_of(model, output)
+    s, pauses, fade = text_plan('synthesize_text', model, pauses_ms, fade_ms, settings)
     hp = model.hparams
-    pauses = pause_samples(pauses_ms, hp.sampling_rate)
-    fade = fade_samples(fade_ms, hp.sampling_rate)
     calls, piece_text, piece_break, _pieces = pack_pieces(texts, dataset, batch_size, max_chars)
     piece_at = []                   # with marks: per piece its (processed, spans) in its raw text, in the order of pack_pieces
     if s.marks:
         for text in texts:
             piece_at += [marks_.piece_spans(dataset, text, a, b) for _p, _k, a, b in split_text_spans(text, max_chars, abbreviations_of(dataset))]
     marked = [[] for _ in texts]    # ... and per text what marks_of_text takes of its pieces
-    loader = dataset_params.dataset_loader
-    win_len = ms_to_samples(hp.win_len, hp.sampling_rate)
-    win_hop = ms_to_samples(hp.win_hop, hp.sampling_rate)
-    S = n_steps or model.n_steps()
-    it = hp.reconstruction_iterations if n_iter is None else n_iter
+    c = call_constants(model, n_steps, n_iter)
+    win_hop = c.hop
     eng = model.engine
-    lookahead = None if limiter is None else limiter_lookahead('synthesize_text', limiter[1], eng.sampling_rate)
+    finish = finishing_tail('synthesize_text', s, eng.sampling_rate, deliver=False)   # (the output is made of the whole texts, below)
     keep_frames = s.stop[1]
-    threshold = eng.speech_threshold(s.stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
+    threshold = eng.speech_threshold(s.stop[0], c.ref_db, c.max_db)
     parts = [[] for _ in texts]     # per text the waveforms of its parts, one per call that says some of it
     tails = [0 for _ in texts]      # ... and the pause behind the last part so far
     records = []
     for k, (p0, ids) in enumerate(calls):
         B = ids.shape[0]
-        out = eng.synthesize(ids, S, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power, it, win_len, win_hop, seed=seed + k,
-                             peak_normalize=False, want_linear=True, **dict(s.engine_keywords(), loudness=None, limiter=None))
+        out = eng.synthesize(ids, *c.synth, seed=seed + k, peak_normalize=False, want_linear=True,
+                             **dict(s.engine_keywords(), loudness=None, limiter=None))   # (both run on the joined rows)
         first_active = eng.speech_interval(out['linear'], threshold)[0].to_host()
-        if check_alignment:
+        if s.check_alignment:
             records.append(eng.synth_alignment_stats(B))
         pieces, groups, said, tail, orphans = join_list_of_call(piece_text[p0:p0 + B], piece_break[p0:p0 + B], out['n_frames'], first_active,
                                                                 win_hop, pauses, s.rate, keep_frames, lead_trim)
@@ -809,73 +860,40 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
         if not said:
             continue
         joined, n_out = eng.join(out['wav'], pieces, groups, fade)
-        if loud is not None:
-            eng.loudness_normalize(joined, eng.sampling_rate, loud[0], loud[1], n_samples=n_out)
-        if limiter is not None:
-            eng.limit(joined, limiter[0], lookahead, limiter[2], n_samples=n_out)
-        for t, wav, gap in zip(said, eng.download_rows(joined, n_out), tail):
+        for t, wav, gap in zip(said, finish(eng, joined, n_out), tail):
             if parts[t]:
                 parts[t].append(np.zeros(tails[t], dtype=np.float32))
             parts[t].append(wav)
             tails[t] = gap
     wavs = [np.concatenate(p) if p else np.zeros(0, dtype=np.float32) for p in parts]
-    if out_setting is not None:
-        wavs = deliver(eng, wavs, out_setting, seed, norm=peak_normalize, what='text')
+    if s.output is not None:
+        wavs = deliver(eng, wavs, s.output, seed, norm=peak_normalize, what='text')
     elif peak_normalize:
         raise ValueError('synthesize_text: peak_normalize goes with an output (save_wav normalises float32 files)')
-    result = (wavs,)
-    if check_alignment:
-        records = np.concatenate(records) if records else np.zeros(0, dtype=ALIGNMENT_RECORD)
-        result += (records, attention_check.verdict(records), list(piece_text))
+    named = dict(wavs=wavs)
+    if s.check_alignment:
+        named['records'] = np.concatenate(records) if records else np.zeros(0, dtype=ALIGNMENT_RECORD)
+        named['verdicts'], named['piece_text'] = attention_check.verdict(named['records']), list(piece_text)
     if s.marks:
-        result += ([marks_.marks_of_text(marked[t], hp.reduction, win_hop, s.rate, hp.sampling_rate, output_rate(model, out_setting),
-                                         len(wavs[t]), s.marks, raw=texts[t]) for t in range(len(texts))],)
-    return result if len(result) > 1 else wavs
+        named['marks'] = [marks_.marks_of_text(marked[t], hp.reduction, win_hop, s.rate, hp.sampling_rate, output_rate(model, s.output),
+                                               len(wavs[t]), s.marks, raw=texts[t]) for t in range(len(texts))]
+    return named
 
 
-def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0, seed=0, check_alignment=False, **kw):
+@takes_settings()
+def synthesize_texts(raw_texts, weights, dataset=None, out_dir=None, device_id=0, seed=0, batch_size=64, pauses_ms=None,
+                     fade_ms=FADE_MS, lead_trim=True, max_chars=MAX_CHARS, **settings):
     """``synthesize_sentences`` for texts of any length: every entry of ``raw_texts`` becomes one ``{i+1}.wav`` that holds the whole
-    text (``synthesize_text``; ``kw``: its keywords).  Without a ``loudness`` or a ``limiter`` each file is peak-normalised once by save_wav, as
-    the sentence files are.  Returns the list of waveforms, with ``check_alignment`` ``(waveforms, report)`` -- one ``{index,
-    verdict, record}`` per PIECE, each with the index of its ``text`` -- also written to ``alignment_report.json``.  With ``marks`` the
-    result gains the timing marks of every text as its last element, also written as ``{i+1}.marks.jsonl`` beside every wav."""
-    from ..datasets.lj_speech import LJSpeechDatasetHelper
-    out_dir = out_dir or inference_params.synthesis_dir
-    if not os.path.isdir(out_dir):
-        raise NotADirectoryError('The specified synthesis target folder does not exist.')
-    # (ValueError before anything is loaded)
-    settings = {k: kw[k] for k in kw if k not in ('batch_size', 'pauses_ms', 'fade_ms', 'lead_trim', 'max_chars', 'output')}
-    out_setting = output_of(model_params, kw.get('output'))
-    norm = loudness_setting(kw.get('loudness')) is None and limiter_setting(kw.get('limiter')) is None
-    if settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB) is None:
-        raise ValueError('synthesize_texts: stop_at_silence_db cannot be None')
-    SynthSettings(model_params, **dict(settings, stop_at_silence_db=settings.get('stop_at_silence_db', STOP_AT_SILENCE_DB)))
-    pause_samples(kw.get('pauses_ms'), model_params.sampling_rate)
-    fade_samples(kw.get('fade_ms', FADE_MS), model_params.sampling_rate)
-    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
-                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
-    model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
-    wavs = synthesize_text(model, raw_texts, dataset, seed=seed, check_alignment=check_alignment,
-                           peak_normalize=norm and out_setting is not None, **kw)
-    report = None
-    all_marks = None
-    if kw.get('marks'):
-        wavs, all_marks = wavs[:-1], wavs[-1]
-        wavs = wavs if check_alignment else wavs[0]
-        for i, m in enumerate(all_marks):
-            marks_.write_marks(os.path.join(out_dir, '{}.marks.jsonl'.format(i + 1)), m)
-    if check_alignment:
-        wavs, records, _verdicts, piece_text = wavs
-        report = attention_check.report(records)
-        for row, t in zip(report, piece_text):
-            row['text'] = int(t)
-        with open(os.path.join(out_dir, REPORT_FILE), 'w') as f:
-            json.dump(report, f, indent=1)
-    for i, wav in enumerate(wavs):
-        save_wav(os.path.join(out_dir, '{}.wav'.format(i + 1)), wav, output_rate(model_params, out_setting),
-                 norm and out_setting is None and len(wav) > 0, encoding=output_encoding(out_setting))   # (a text that says nothing: an empty file)
-    result = (list(wavs),) + ((report,) if check_alignment else ()) + ((all_marks,) if all_marks is not None else ())
-    return result if len(result) > 1 else result[0]
+    text (``synthesize_text``, with its keywords).  Without a ``loudness`` or a ``limiter`` each file is peak-normalised once by save_wav,
+    as the sentence files are; a text that says nothing gives an empty file.  Returns the list of waveforms, with ``check_alignment``
+    ``(waveforms, report)`` -- one ``{index, verdict, record}`` per PIECE, each with the index of its ``text`` -- also written to
+    ``alignment_report.json``.  With ``marks`` the result gains the timing marks of every text as its last element, also written as
+    ``{i+1}.marks.jsonl`` beside every wav."""
+    target_dir(out_dir)
+    s = text_plan('synthesize_texts', model_params, pauses_ms, fade_ms, settings)[0]   # (ValueError before anything is loaded)
+    out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
+    return write_files(out_dir, s, synthesize_text.parts(model, raw_texts, dataset, batch_size, pauses_ms, fade_ms, lead_trim, max_chars,
+                                                         seed=seed, peak_normalize=s.file_norm()[0], **settings))
 
 
 def read_texts(path):
@@ -956,15 +974,10 @@ def main(argv=None):
     and the pauses word by word (``synthesize_marked``; ``--rate`` is then the base rate).  Works with ``--marks``, whose offsets are
     then into the line with the markup removed; refused together with ``--text``, ``--pitch`` and ``--check-alignment``."""
     args = parse_args(argv)
-    s = SynthSettings(model_params, args.momentum, args.stop_at_silence, args.silence_keep_ms, args.rate, pitch_semitones=args.pitch,
-                      phase_init=args.phase_init, loudness=None if args.loudness is None else (args.loudness, args.max_peak),
-                      check_alignment=args.check_alignment,
-                      limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
-                      output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump)
-    out_dir = args.synthesis_dir or inference_params.synthesis_dir
+    settings = settings_option(args)
+    SynthSettings(model_params, **settings)
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
-    if not os.path.isdir(out_dir):
-        raise NotADirectoryError('The specified synthesis target folder does not exist.')
+    out_dir = target_dir(args.synthesis_dir)
     path = args.synthesis_file or inference_params.synthesis_file
     raw_sentences = read_texts(path) if args.text else read_sentences(path)
     print('{} {} were loaded for inference.'.format(len(raw_sentences), 'texts' if args.text else 'sentences'))
@@ -978,27 +991,28 @@ def main(argv=None):
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
     if args.markup:
-        wavs = synthesize_marked_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                           output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump,
-                                           **dict(s.keywords(), pitch=0.0))
+        written = synthesize_marked_sentences.parts(raw_sentences, weights, None, out_dir, args.device, args.seed, **settings)
     elif args.text:
-        kw = dict(s.keywords(), stop_at_silence_db=STOP_AT_SILENCE_DB if args.stop_at_silence is None else args.stop_at_silence)
-        wavs = synthesize_texts(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                check_alignment=args.check_alignment, max_chars=args.max_chars, pauses_ms=dict(args.pause_ms),
-                                fade_ms=args.fade_ms, output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump, **kw)
+        if args.stop_at_silence is None:
+            settings['stop_at_silence_db'] = STOP_AT_SILENCE_DB
+        written = synthesize_texts.parts(raw_sentences, weights, None, out_dir, args.device, args.seed, max_chars=args.max_chars,
+                                          pauses_ms=dict(args.pause_ms), fade_ms=args.fade_ms, **settings)
     else:
-        wavs = synthesize_sentences(raw_sentences, weights, out_dir=out_dir, device_id=args.device, seed=args.seed,
-                                    check_alignment=args.check_alignment, output=output_option(args), marks=args.marks,
-                                    marks_max_jump=args.marks_max_jump, **s.keywords())
-    if args.marks:
-        wavs = wavs[:-1] if args.check_alignment and not args.markup else wavs[0]
-    if args.check_alignment and not args.markup:
-        wavs, report = wavs
-        for row in report:
-            print(json.dumps(row))
-    for i in range(len(wavs)):
+        written = synthesize_sentences.parts(raw_sentences, weights, None, out_dir, args.device, args.seed, **settings)
+    for row in written.get('report', ()):
+        print(json.dumps(row))
+    for i in range(len(written['wavs'])):
         print('Saved: "{}"'.format(os.path.join(out_dir, '{}.wav'.format(i + 1))))
     return 0
+
+
+def settings_option(args):
+    """the command line's options as the ``settings`` of the helpers above: the keywords of ``SynthSettings``"""
+    return dict(momentum=args.momentum, stop_at_silence_db=args.stop_at_silence, silence_keep_ms=args.silence_keep_ms,
+                speaking_rate=args.rate, pitch_semitones=args.pitch, phase_init=args.phase_init,
+                loudness=None if args.loudness is None else (args.loudness, args.max_peak), check_alignment=args.check_alignment,
+                limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
+                output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump)
 
 
 def output_option(args):

@@ -8,12 +8,11 @@ of one, serve.py:58), a whole batch is supported.
 """
 import numpy as np
 
-from .._hip import limiter_lookahead, synth_frame_counts, synth_lengths
-from ..audio.conversion import ms_to_samples
+from .._hip import synth_frame_counts, synth_lengths
 from . import attention_check, marks as marks_
-from .inference import SILENCE_KEEP_MS, SynthSettings, cut_waveforms, deliver, marks_of_batch, pad_id, pad_sentence, synthesize_stream
-from .model import Mode, Tacotron
-from .params import dataset_params, model_params
+from .inference import (SynthSettings, call_constants, deliver, finishing_tail, marks_of_batch, open_model, pad_id, pad_sentence,
+                        synthesize_stream, takes_settings)
+from .params import model_params
 
 
 def pre_process_sentences(_sentences, dataset):
@@ -24,24 +23,23 @@ def pre_process_sentences(_sentences, dataset):
     return np.array([pad_sentence(s, max_length) for s in sentences], dtype=np.int32)
 
 
-def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, momentum=0.0, stop_at_silence_db=None,
-                              silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random',
-                              loudness=None, limiter=None):
+@takes_settings('check_alignment', 'output', 'marks', 'marks_max_jump')
+def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, **settings):
     """normalised linear spectrograms (B, T, 1025) -> list of waveforms: de-normalise with the mel dB
-    constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86).  The settings from ``momentum`` on mean
-    what ``inference.SynthSettings`` says, composed here from the engine's stages: with ``stop_at_silence_db``
+    constants, ``** magnitude_power``, Griffin-Lim (reference tacotron/serve.py:39-86).  ``settings`` mean what
+    ``inference.SynthSettings`` says -- the alignment check, the delivery format and the marks apart, which need more than
+    spectrograms --, composed here from the engine's stages: with ``stop_at_silence_db``
     ``Engine.speech_frames`` on the normalised spectrograms, then one ragged Griffin-Lim call, every utterance returned at its own
     length; with a ``speaking_rate`` or a ``pitch`` ``Engine.stretch_magnitudes`` by rate * 2 ** -pitch ahead of Griffin-Lim
     (``init_phase`` has that many frames; lengths min(T', max(min_frames, ceil(n / rate)))) and ``Engine.resample`` by 2 ** -pitch
     behind it; with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
     last, over the same samples."""
-    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, limiter=limiter)
-    stop, rate, octaves, loud = s.stop, s.rate, s.octaves, s.loud
-    lookahead = None if s.limiter is None else limiter_lookahead('post_process_spectrograms', s.limiter[1], model_params.sampling_rate)
+    s = SynthSettings(model_params, **settings)
+    stop, rate, octaves = s.stop, s.rate, s.octaves
+    finish = finishing_tail('post_process_spectrograms', s, model_params.sampling_rate)
     rho = float(np.exp2(-np.float64(octaves)))
-    loader = dataset_params.dataset_loader
-    win_len = ms_to_samples(model_params.win_len, model_params.sampling_rate)
-    win_hop = ms_to_samples(model_params.win_hop, model_params.sampling_rate)
+    c = call_constants(model_params)
+    win_hop = c.hop
     spec = np.asarray(_spectrograms, dtype=np.float32)
     if spec.ndim == 2:
         spec = spec[None]
@@ -58,37 +56,27 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, mo
     if stop is not None:
         if T < min_frames:
             raise ValueError('stop_at_silence_db: spectrograms of {} frames, at least {} needed'.format(T, min_frames))
-        thr = engine.speech_threshold(stop[0], loader.mel_mag_ref_db, loader.mel_mag_max_db)
+        thr = engine.speech_threshold(stop[0], c.ref_db, c.max_db)
         n_frames = engine.speech_frames(spec, thr, keep_frames=stop[1], min_frames=min_frames)[0].to_host()
-    mag = engine.denorm_power(spec, loader.mel_mag_ref_db, loader.mel_mag_max_db, model_params.magnitude_power)
+    mag = engine.denorm_power(spec, c.ref_db, c.max_db, model_params.magnitude_power)
     n_gl = n_frames   # the frames Griffin-Lim runs on
     if rate != 1.0 or octaves != 0.0:
         mag = engine.stretch_magnitudes(mag, rate * rho, n_frames=n_frames, T_out=T_g)
         if n_frames is not None:
             n_frames, n_gl = synth_lengths(n_frames, T, rate, octaves, min_frames)
-    wav, _ = engine.griffin_lim(mag, model_params.reconstruction_iterations, win_len, win_hop, model_params.n_fft,
-                                init_phase=init_phase, seed=seed, want_mse=False, momentum=momentum, n_frames=n_gl,
-                                phase_init=phase_init)
+    wav, _ = engine.griffin_lim(mag, c.n_iter, c.win_len, win_hop, model_params.n_fft, init_phase=init_phase, seed=seed, want_mse=False,
+                                momentum=s.momentum, n_frames=n_gl, phase_init=s.phase_init)
     if octaves != 0.0:
         gl_wav = wav
         try:
             wav = engine.resample(gl_wav, rho, n_samples=None if n_gl is None else win_hop * (n_gl - 1), N_out=win_hop * (T_s - 1))
         finally:
             gl_wav.free()   # (tts_free waits for the device: the resampling that reads it has run)
-    held = None if n_frames is None else win_hop * (np.asarray(n_frames, dtype=np.int32) - 1)
-    if loud is not None:
-        engine.loudness_normalize(wav, model_params.sampling_rate, loud[0], loud[1], n_samples=held)
-    if s.limiter is not None:
-        engine.limit(wav, s.limiter[0], lookahead, s.limiter[2], n_samples=held)
-    wav = wav.to_host()
-    if n_frames is not None:
-        return cut_waveforms(wav, n_frames, win_hop)
-    return [wav[b] for b in range(wav.shape[0])]
+    return dict(wavs=finish(engine, wav, None if n_frames is None else win_hop * (np.asarray(n_frames, dtype=np.int32) - 1)))
 
 
-def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, momentum=0.0, stop_at_silence_db=None,
-          silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0, phase_init='random', loudness=None,
-          check_alignment=False, limiter=None, output=None, marks=None, marks_max_jump=4):
+@takes_settings()
+def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=False, **settings):
     """Generator: for each batch of raw sentences yield the list of synthesized waveforms
     (reference tacotron/serve.py:89-126, with the SavedModel session replaced by the engine).
 
@@ -97,7 +85,7 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     before it sends more).  ``pipelined=True`` keeps three batches in flight for OFFLINE streams whose batches are all
     available: batch k is then yielded only after batch k + 2 has been pulled from the generator (the last one when the
     generator ends), which on a request-driven generator would hold every answer back by two requests.
-    The settings from ``momentum`` on: as ``inference.SynthSettings`` has them -- with a loudness every answer of the stream
+    ``settings``: the keywords of ``inference.SynthSettings`` -- with a loudness every answer of the stream
     comes at the same level, with a limiter under the same ceiling.  With ``check_alignment`` every answer is ``(waveforms, records, verdicts)`` -- the alignment
     records of the batch (``Engine.alignment_stats``) and ``attention_check.verdict`` of every utterance, in the same round trip
     as the waveforms: a bad utterance can be flagged before it is played.  With an ``output`` (``inference.SynthSettings``) every
@@ -106,31 +94,25 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     every answer gains, as its last element, the timing marks of every sentence (``tacotron.marks``; offsets into the raw
     sentence, samples of what is delivered): subtitles and barge-in positions in the same round trip as the waveforms."""
     # (a generator: a bad setting is refused at its first item, before a model is made)
-    s = SynthSettings(model_params, momentum, stop_at_silence_db, silence_keep_ms, speaking_rate, pitch, phase_init, loudness, check_alignment,
-                      limiter=limiter, output=output, marks=marks, marks_max_jump=marks_max_jump)
-    from ..datasets.lj_speech import LJSpeechDatasetHelper
-    dataset = dataset or LJSpeechDatasetHelper(dataset_folder=dataset_params.dataset_folder,
-                                                char_dict=dataset_params.vocabulary_dict, fill_dict=False)
-    model = Tacotron(inputs=Tacotron.model_placeholders(), mode=Mode.PREDICT, weights=weights, device_id=device_id)
+    s = SynthSettings(model_params, **settings)
+    dataset, model = open_model(weights, dataset, device_id)
     if not pipelined:   # the reference's loop as it stands: one batch at a time, spectrograms through host memory
         for k, sentences in enumerate(sentence_generator):
             ids = pre_process_sentences(sentences, dataset)
             texts = [(raw,) + marks_.token_spans(dataset, raw) for raw in sentences] if s.marks else None
-            fetches = [model.output_linear_spec] + ([model.alignment_history] if check_alignment or s.marks else [])
+            fetches = [model.output_linear_spec] + ([model.alignment_history] if s.check_alignment or s.marks else [])
             fetched = model.run(fetches, {model.inp_sentences: ids})
             wavs = post_process_spectrograms(fetched[0], model.engine, **s.keywords())
             held = [len(w) for w in wavs]   # (the samples every row holds at the model's rate)
-            if s.output is not None:
-                wavs = deliver(model.engine, wavs, s.output, seed=k)
-            answer = (wavs,)
-            n_sent = model.engine.text_lengths(ids, pad_id()) if check_alignment or s.marks else None
-            if check_alignment:   # (the same kernels as inside a pipelined call, on the alignments this loop fetched anyway)
-                records = model.engine.alignment_stats(fetched[1], n_sent=n_sent)
-                answer += (records, attention_check.verdict(records))
+            parts = dict(wavs=wavs if s.output is None else deliver(model.engine, wavs, s.output, seed=k))
+            n_sent = model.engine.text_lengths(ids, pad_id()) if s.check_alignment or s.marks else None
+            if s.check_alignment:   # (the same kernels as inside a pipelined call, on the alignments this loop fetched anyway)
+                parts['records'] = model.engine.alignment_stats(fetched[1], n_sent=n_sent)
+                parts['verdicts'] = attention_check.verdict(parts['records'])
             if s.marks:
                 start, stats = model.engine.token_times(fetched[1], n_sent=n_sent, max_jump=s.marks_max_jump)
-                answer += (marks_of_batch(model, s, ids, start, stats, held, wavs, texts),)
-            yield answer if len(answer) > 1 else wavs
+                parts['marks'] = marks_of_batch(model, s, ids, start, stats, held, parts['wavs'], texts)
+            yield parts
         return
     # three batches in flight, nothing but ids and waveforms crosses the host boundary (inference.synthesize_stream)
     texts = []   # per batch pulled, what its marks take of the raw sentences
@@ -145,8 +127,6 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
         while True:
             yield texts.pop(0)
 
-    for item in synthesize_stream(model, pulled(), peak_normalize=False, copy=True, check_alignment=check_alignment, output=output,
-                                  marks=marks, marks_max_jump=marks_max_jump, mark_texts=pulled_texts(), **s.keywords()):
-        wavs = item[0] if check_alignment or s.marks else item
-        listed = [wavs[b] for b in range(len(wavs))]
-        yield ((listed,) + tuple(item[1:])) if check_alignment or s.marks else listed
+    for parts in synthesize_stream.parts(model, pulled(), peak_normalize=False, copy=True, mark_texts=pulled_texts(), **settings):
+        parts['wavs'] = list(parts['wavs'])
+        yield parts

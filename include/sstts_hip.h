@@ -881,6 +881,62 @@ int tts_warp_magnitudes(tts_handle_t h, const float* mag /* DEVICE [B][F][T] */,
 int tts_warp_max_segments(void);
 int tts_warp_tile(void);
 
+/* ---- per-word pitch: a segment-wise resampler behind Griffin-Lim ----------------------------- */
+/* An edit list over the samples of wav DEVICE [B][n], written to out DEVICE [B][N_out] (no reference counterpart: tts_resample with
+ * a ratio that varies along the utterance; behind tts_warp_magnitudes and Griffin-Lim it gives a word its own pitch and leaves its
+ * duration alone).  Segment s takes source samples [first, first + samples) of row `row`, samples >= 1, at `ratio` output samples per
+ * input sample.  The segments of a row are consecutive in the list, rows non-decreasing over 0 .. B - 1, no row without a segment;
+ * the segments of a row may use any source range inside n_samples[row] (HOST int32 [B], or NULL: all n), in any order, any number
+ * of times.
+ *   lengths    count[s] = samples where ratio == 1.0 exactly (a COPY), else (long long)(samples * ratio), the product in double,
+ *              truncated (resampy's; it may be 0); within a row segment s starts at output sample o[s], the sum of the counts of the
+ *              row's earlier segments, and the row holds n_out[row] = the sum of all of them.
+ *   copy       out[row][o + j] = the bits of wav[row][first + j], j < count: NaN payloads and -0.0 survive.
+ *   resampled  output sample o + j, j < count, is tts_resample's arithmetic with the position measured from `first`: with scale,
+ *              step, inc, win and delta of `ratio` as above (see "resampling"),
+ *                tr = j inc, m = first + (long long)tr, frac = scale (tr - (long long)tr);   f = 512 frac, off = (int)f, eta = f - off
+ *                y  = sum_i fma(eta, delta[off + i step], win[off + i step]) x[m - i]          i < (32769 - off) / step
+ *                   + the same with frac = scale - frac on x[m + 1 + k]                        k < (32769 - off) / step
+ *              the position in double, every operation rounded on its own; the left wing with i ascending, then the right wing
+ *              with k ascending, each tap an FMA into ONE accumulator that starts at 0.0, in double, rounded once to float32.  x is
+ *              the ROW: the taps reach over the segment's borders into the row's own samples, whichever segment those lie in, and
+ *              are cut only at the row's ends -- a sample outside [0, n_samples[row]) is 0.0 and is never fetched.  A NaN or Inf
+ *              sample reaches every output whose window covers it and no other.
+ *   zeros      samples n_out[row] .. N_out - 1 are +0.0.
+ * One whole-row segment {b, 0, n_samples[b], 0, ratio} per row, ratio != 1, is tts_resample at that ratio with N_out: the same
+ * lengths and the same bits.  Every element of out is written exactly once per call: no atomics, no memset, nothing read from out;
+ * a row's output is the same bits whatever B is and wherever the row sits in the batch, and however the list is cut into launches
+ * (within tests/resample_segments_oracle.py's float64 by resample_oracle's bound).  The list travels by value, 64 segments per
+ * launch: a call makes at most ceil(S / 64) launches (a launch whose segments own no sample is not made) and waits for nothing.
+ * Ratios of 1 and above share one table; each distinct ratio below 1 has a table of its own (0.5 MiB, kept on the handle), at
+ * most tts_resample_segments_max_ratios() of them per call.  The FIRST use of a ratio below 1 builds its table on the host and
+ * uploads it with a synchronous copy, which blocks the calling thread, as in tts_resample; and a call whose new tables do not fit
+ * beside the 32 the handle keeps synchronises the handle's streams once and drops the kept ones before it fetches its own.
+ * Otherwise asynchronous on the handle's stream, no model needed; profile stage "resample".  n_out: HOST int32 [B], the rows'
+ * lengths, or NULL.
+ * TTS_ERR_INVALID with a message that names the segment or row, before anything is enqueued, in this order: a NULL pointer (wav,
+ * segments, out); B, n, S or N_out < 1; S above tts_resample_segments_max(); B above S; an n_samples[b] outside 1 .. n; rows that
+ * do not start at 0, decrease, skip a row or do not end at B - 1; then per segment samples < 1, first < 0 or first + samples
+ * beyond n_samples[row], a ratio that is not finite or lies outside [0.25, 4], reserved != 0; more than
+ * tts_resample_segments_max_ratios() distinct ratios below 1; N_out below the largest n_out[b] or above 2^30; a misaligned buffer
+ * (4 bytes). */
+typedef struct tts_resample_segment {
+    int32_t row, first, samples, reserved;   /* reserved must be 0 */
+    double ratio;                            /* output samples per input sample */
+} tts_resample_segment_t;   /* HOST, 24 bytes */
+/* Host only, no handle and no device: the checks of the list, and every row's length (tts_last_error(NULL) has the reason of a
+ * refusal). */
+int tts_resample_segments_plan(const tts_resample_segment_t* segments, int S, int B, int n, const int32_t* n_samples /* HOST [B] or NULL */,
+                               int64_t* n_out /* HOST [B] */);
+int tts_resample_segments(tts_handle_t h, const float* wav /* DEVICE [B][n] */, int B, int n, const int32_t* n_samples /* HOST [B] or NULL */,
+                          const tts_resample_segment_t* segments, int S, int N_out, float* out /* DEVICE [B][N_out] */,
+                          int32_t* n_out /* HOST [B] or NULL */);
+/* Host only: the most segments a call takes (4096), the most distinct ratios below 1 among them (16), and the output samples of a
+ * segment one workgroup writes (256). */
+int tts_resample_segments_max(void);
+int tts_resample_segments_max_ratios(void);
+int tts_resample_segments_tile(void);
+
 /* ---- delivery formats: 16-bit PCM, 8-bit PCM and G.711 --------------------------------------- */
 #define TTS_FMT_F32 0        /* float32 as the library makes it: no encoding */
 #define TTS_FMT_PCM_S16 1    /* signed 16-bit PCM, 2 bytes per code */
@@ -1125,7 +1181,7 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * (launches of tts_debug_gemm), "eval_loss" (the loss reduction of tts_evaluate), "features" (tts_trim_bounds, the trim of tts_plan_features and
  * tts_extract_features), "speech_end" (tts_speech_frames, stand-alone or inside tts_synthesize),
  * "stretch" (tts_stretch_magnitudes / tts_stretch_rows, stand-alone or inside tts_synthesize),
- * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch), "phase_init" (tts_phase_estimate*),
+ * "resample" (tts_resample, stand-alone or inside a tts_synthesize call with a pitch, and tts_resample_segments), "phase_init" (tts_phase_estimate*),
  * "mfcc" (tts_mfcc), "dtw" (tts_dtw), "f0" (tts_f0, tts_f0_compare), "loudness" (tts_loudness, tts_loudness_normalize, stand-alone
  * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, tts_token_times, stand-alone
  * or inside a tts_synthesize call with tts_set_alignment_stats or tts_set_token_times on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,

@@ -125,7 +125,22 @@ class TtsWarpSegment(ctypes.Structure):
 WARP_SEGMENT = np.dtype([('row', np.int32), ('first', np.int32), ('frames', np.int32), ('pause', np.int32), ('step', np.uint32), ('gain', np.float32)])
 
 
+class TtsResampleSegment(ctypes.Structure):
+    """tts_resample_segment_t: source samples [first, first + samples) of a row at ``ratio`` output samples per input sample
+    (1.0 exactly: a copy); 24 bytes, a record of the RESAMPLE_SEGMENT arrays ``Engine.resample_segments`` hands the library"""
+    _fields_ = [('row', c_int32), ('first', c_int32), ('samples', c_int32), ('reserved', c_int32), ('ratio', ctypes.c_double)]
+
+
+# ... and the same record as a numpy dtype
+RESAMPLE_SEGMENT = np.dtype([('row', np.int32), ('first', np.int32), ('samples', np.int32), ('reserved', np.int32), ('ratio', np.float64)])
+
+
 _PROTOTYPES = {
+    'tts_resample_segments_plan': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
+    'tts_resample_segments': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_int, c_void_p, POINTER(c_int32)]),
+    'tts_resample_segments_max': (c_int, []),
+    'tts_resample_segments_max_ratios': (c_int, []),
+    'tts_resample_segments_tile': (c_int, []),
     'tts_warp_plan': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
     'tts_warp_magnitudes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_int, c_void_p]),
     'tts_warp_max_segments': (c_int, []),
@@ -958,6 +973,96 @@ def resampled_length(n, ratio):
     if int(n) != n or n < 1:
         raise ValueError('resampled_length: need n >= 1 samples, got {!r}'.format(n))
     return int(np.ceil(np.float64(int(n)) * np.float64(r)))
+
+
+RESAMPLE_SEGMENTS_MAX = 4096                   # tts_resample_segments_max()
+RESAMPLE_SEGMENTS_PER_LAUNCH = 64              # segments whose entries travel with one launch
+RESAMPLE_SEGMENTS_MAX_RATIOS = 16              # tts_resample_segments_max_ratios(): distinct ratios below 1 per call
+RESAMPLE_SEGMENTS_MAX_N_OUT = 1 << 30
+
+
+def resample_segment_count(samples, ratio):
+    """output samples of a segment: ``samples`` for a copy (ratio 1.0 exactly), else int(samples * ratio), the product in double"""
+    return int(samples) if ratio == 1.0 else int(np.float64(int(samples)) * np.float64(ratio))
+
+
+def resample_segment_records(segments):
+    """``segments`` -- a RESAMPLE_SEGMENT array, or rows ``(row, first, samples, ratio)`` -- as a contiguous RESAMPLE_SEGMENT
+    array (S,).  ValueError for anything that is not such a list or does not fit the record's fields."""
+    if isinstance(segments, np.ndarray) and segments.dtype == RESAMPLE_SEGMENT and segments.ndim == 1:
+        return np.ascontiguousarray(segments)
+    try:
+        rows = [tuple(r) for r in segments]
+    except TypeError:
+        rows = None
+    if rows is None or any(len(r) != 4 for r in rows):
+        raise ValueError('resample_segments: segments must be a RESAMPLE_SEGMENT array or rows (row, first, samples, ratio)')
+    out = np.zeros(len(rows), dtype=RESAMPLE_SEGMENT)
+    for s, r in enumerate(rows):
+        ints, ratio = r[:3], r[3]
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= v < 2 ** 31 for v in ints):
+            raise ValueError('resample_segments: segment {} must hold 32-bit integers row, first and samples, got {!r}'.format(s, r))
+        try:
+            ratio = float(ratio)
+        except (TypeError, ValueError):
+            raise ValueError('resample_segments: segment {} needs a number as its ratio, got {!r}'.format(s, r[3]))
+        out[s] = tuple(int(v) for v in ints) + (0, ratio)
+    return out
+
+
+def resample_segment_list(segments, B, n, n_samples=None):
+    """The segment list of a segment-wise resampling of a batch (B, n) as ``(segments, n_samples, n_out, count)``: a contiguous
+    RESAMPLE_SEGMENT array, the lengths as a contiguous int32 array (None: all n), the int64 lengths of the B output rows and the
+    int64 output samples of every segment.  Checked as tts_resample_segments_plan checks it, in its order -- ValueError, raised
+    before a handle or the library is touched."""
+    q = resample_segment_records(segments)
+    S = int(q.shape[0])
+    if B < 1 or n < 1 or S < 1:
+        raise ValueError('resample_segments: need B, n, S >= 1')
+    if S > RESAMPLE_SEGMENTS_MAX:
+        raise ValueError('resample_segments: {} segments are more than tts_resample_segments_max() = {}'.format(S, RESAMPLE_SEGMENTS_MAX))
+    if B > S:
+        raise ValueError('resample_segments: {} rows of {} segments: no row is without a segment'.format(B, S))
+    ns = None
+    if n_samples is not None:
+        ns = np.asarray(n_samples)
+        if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+            raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+        ns = _checked_lengths(ns, n, 'n_samples', 'n')
+    rows = q['row'].tolist()
+    if rows[0] != 0:
+        raise ValueError('resample_segments: row of segment 0 is {}: the rows start at 0'.format(rows[0]))
+    for s in range(1, S):
+        if rows[s] - rows[s - 1] not in (0, 1):
+            raise ValueError('resample_segments: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a '
+                             'segment'.format(s, rows[s], rows[s - 1]))
+    if rows[-1] != B - 1:
+        raise ValueError('resample_segments: row of segment {} is {}: the last row is B - 1 = {}'.format(S - 1, rows[-1], B - 1))
+    n_out = np.zeros(B, dtype=np.int64)
+    count = np.zeros(S, dtype=np.int64)
+    below, extra_at = set(), None
+    for s, (row, first, samples, reserved, ratio) in enumerate(q.tolist()):
+        have = n if ns is None else int(ns[row])
+        if samples < 1:
+            raise ValueError('resample_segments: segment {} has {} samples: at least 1 is needed'.format(s, samples))
+        if first < 0 or first + samples > have:
+            raise ValueError('resample_segments: segment {} reads samples {} .. {} of row {}, which has 0 .. {}'.format(
+                s, first, first + samples - 1, row, have - 1))
+        if not RESAMPLE_RATIO_MIN <= ratio <= RESAMPLE_RATIO_MAX:   # (a NaN fails both comparisons)
+            raise ValueError('resample_segments: segment {} has a ratio that is not finite or lies outside [0.25, 4]'.format(s))
+        if reserved != 0:
+            raise ValueError('resample_segments: segment {} has reserved = {}, which must be 0'.format(s, reserved))
+        if ratio < 1.0 and ratio not in below:
+            if len(below) < RESAMPLE_SEGMENTS_MAX_RATIOS:
+                below.add(ratio)
+            elif extra_at is None:
+                extra_at = s
+        count[s] = resample_segment_count(samples, ratio)
+        n_out[row] += count[s]
+    if extra_at is not None:
+        raise ValueError('resample_segments: segment {} brings distinct ratio below 1 number {}: a call takes '
+                         'tts_resample_segments_max_ratios() = {}'.format(extra_at, RESAMPLE_SEGMENTS_MAX_RATIOS + 1, RESAMPLE_SEGMENTS_MAX_RATIOS))
+    return q, ns, n_out, count
 
 
 def pitch_octaves_value(octaves):
@@ -2211,6 +2316,63 @@ class Engine(object):
         if single:
             out.shape = (N_out,)
         return out
+
+    def resample_segments_max(self):
+        """tts_resample_segments_max: the most segments :meth:`resample_segments` takes in one call."""
+        return int(self.lib.tts_resample_segments_max())
+
+    def resample_segments_max_ratios(self):
+        """tts_resample_segments_max_ratios: the most distinct ratios below 1 among the segments of one call."""
+        return int(self.lib.tts_resample_segments_max_ratios())
+
+    def resample_segments_tile(self):
+        """tts_resample_segments_tile: the output samples of a segment one workgroup writes."""
+        return int(self.lib.tts_resample_segments_tile())
+
+    def resample_segments_plan(self, shape, segments, n_samples=None):
+        """tts_resample_segments_plan, host only: the lengths ``n_out`` (int64 (B,)) of the rows that ``segments`` -- a
+        RESAMPLE_SEGMENT array or rows ``(row, first, samples, ratio)`` -- make of a batch of ``shape`` (B, n) whose rows hold
+        ``n_samples`` samples (None: all n).  ValueError for a list tts_resample_segments refuses (``resample_segment_list``),
+        raised before the library is reached."""
+        if len(shape) != 2:
+            raise ValueError('resample_segments_plan: the shape of a batch (B, n) is needed, got {!r}'.format(tuple(shape)))
+        B, n = int(shape[0]), int(shape[1])
+        q, ns, n_out, _count = resample_segment_list(segments, B, n, n_samples)
+        out = np.zeros(B, dtype=np.int64)
+        rc = self.lib.tts_resample_segments_plan(q.ctypes.data, q.shape[0], B, n, _int32_ptr(ns), out.ctypes.data_as(POINTER(c_int64)))
+        if rc != TTS_OK:
+            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        assert (out == n_out).all(), (out, n_out)
+        return out
+
+    def resample_segments(self, wav, segments, n_samples=None, N_out=None):
+        """tts_resample_segments: ``resample`` with a ratio that varies along the utterance, on ``wav`` (B, n) -- a host array,
+        which is uploaded, or a device buffer, which is read in place.  ``segments``: a RESAMPLE_SEGMENT array or rows ``(row,
+        first, samples, ratio)``, the segments of a row one behind the other and the rows in order: source samples [first, first +
+        samples) of the row at ``ratio`` output samples per input sample -- 1.0 exactly: copied bit for bit; otherwise
+        tts_resample's windowed sinc with its position measured from ``first``, the taps reaching over the segment's borders into
+        the row.  ``n_samples``: B lengths (host integers) -- samples at or behind them are never read; None: all n.
+        include/sstts_hip.h has the definition.
+
+        Returns ``(out, n_out)``: a fresh device array (B, N_out) and the int64 host lengths (B,) -- row b holds n_out[b] samples
+        followed by +0.0.  ``N_out`` None: the largest length (at least 1).  ValueError for what the library refuses, raised
+        before it is reached."""
+        if len(wav.shape) != 2 or min(wav.shape) < 1:
+            raise ValueError('resample_segments: a non-empty batch (B, n) is needed, got shape {}'.format(tuple(wav.shape)))
+        B, n = (int(d) for d in wav.shape)
+        q, ns, n_out, _count = resample_segment_list(segments, B, n, n_samples)
+        longest = int(n_out.max())
+        if N_out is None:
+            N_out = max(longest, 1)
+        if int(N_out) != N_out or not max(longest, 1) <= N_out <= RESAMPLE_SEGMENTS_MAX_N_OUT:
+            raise ValueError('resample_segments: N_out = {!r} is not in max(n_out.max(), 1) = {} .. 2^30'.format(N_out, max(longest, 1)))
+        p_wav, _k = self._in(wav, np.float32)
+        out = self.empty((B, int(N_out)))
+        got = np.zeros(B, dtype=np.int32)
+        self._check_or_free(self.lib.tts_resample_segments(self.handle, p_wav, B, n, _int32_ptr(ns), q.ctypes.data, q.shape[0], int(N_out),
+                                                           out.data_ptr(), _int32_ptr(got)), out)
+        assert (got == n_out).all(), (got, n_out)
+        return out, n_out
 
     def pitch_shift(self, wavs, sampling_rate, octaves, n_iter=25, seed=0):
         """The reference's waveform effect pitch_shift (audio/effects.py:9-43) as a composition of existing calls:

@@ -17,7 +17,7 @@ import types
 import numpy as np
 
 from . import attention_check, marks as marks_, prosody
-from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK,
+from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, RESAMPLE_SEGMENTS_MAX_RATIOS,
                     limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
                     output_setting, phase_init_value, pitch_octaves_value, pitch_semitones_value, resampled_length,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting, synth_frame_counts, token_times_jump)
@@ -560,7 +560,7 @@ def marked_settings(hp, settings):
 
 @takes_settings('check_alignment')
 def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=None, seed=0, peak_normalize=False, want_plan=False,
-                      **settings):
+                      markup_pitch=False, **settings):
     """Sentences with prosody markup (``tacotron.prosody``: ``<prosody rate=.. volume=..>``, ``<emphasis>``, ``<break/>`` under an
     optional ``<speak>``) -> a list of B waveforms, row b cut to its own hop (n_out[b] - 1) samples (no reference counterpart).
 
@@ -571,24 +571,40 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
     every break a pause, borders at decoder steps); ``denorm_power``, ``warp_magnitudes``, the ragged Griffin-Lim on ``n_out``, a
     peak normalisation per row (``peak_normalize``) or the ``loudness``, the ``limiter``, and ``deliver_rows`` for an
     ``output``.  The settings: as ``SynthSettings`` has them; ``speaking_rate`` is the base rate every span's rate multiplies.  A
-    ``pitch`` other than 0 is a ValueError: a pitch that varies along the utterance needs a time-varying resampler, and the
-    global one lives inside tts_synthesize.  Sentences without markup at rate 1.0 give the bits of the same stages without the
+    ``pitch`` other than 0 is a ValueError: the global resampler lives inside tts_synthesize; a pitch per word comes from the
+    markup itself, with ``markup_pitch`` (below).  Sentences without markup at rate 1.0 give the bits of the same stages without the
     warp.
 
     With ``marks`` the result gains the timing marks of every sentence (``marks.marks_of_row`` at rate 1.0 through
     ``prosody.warp_position``: a slowed word's mark grows with it, a break opens a gap between two words' marks; ``start`` and
     ``end`` of a mark are offsets into the sentence with the markup removed); with ``want_plan`` a last element ``dict(plain,
-    start, n_sent, n_frames, segments, n_out)``: what the call planned from, per row."""
+    start, n_sent, n_frames, segments, n_out)``: what the call planned from, per row.
+
+    ``markup_pitch``: ``<prosody pitch=..>`` is accepted (``prosody.parse_markup(.., pitch=True)``).  A word ``st`` semitones up
+    is stretched by a further 2 ** (-st / 12) in the warp, and between Griffin-Lim and the finishing tail ``resample_segments``
+    (tts_resample_segments) takes its samples back by that ratio (``prosody.pitch_segments_of_row``): the word lasts as long as it
+    would without the pitch, a row without a pitch inside such a call is one copy segment and keeps its bits, and the tail gets
+    the retimed rows' lengths.  The marks then go through ``prosody.pitch_position(hop * prosody.warp_position(..))``, and the
+    plan gains ``pitch_segments`` and ``n_samples``, per row (None and hop (n_out - 1) where no pass ran).  If no sentence of the
+    call holds a pitch other than 0 the pass is not launched: the bits of the call without the option.  More than
+    ``RESAMPLE_SEGMENTS_MAX_RATIOS`` distinct ratios below 1 (pitches above 0) in one call is a ValueError that gives the count;
+    the global ``pitch`` stays refused."""
     s = marked_settings(model, settings)
     hp = model.hparams
     c = call_constants(model, n_steps, n_iter)
     hop, r = c.hop, hp.reduction
-    parsed = [prosody.parse_markup(text) for text in marked_sentences]
+    parsed = [prosody.parse_markup(text, pitch=bool(markup_pitch)) for text in marked_sentences]
     if not parsed:
         raise ValueError('synthesize_marked: no sentence')
     plains = [p[0] for p in parsed]
     texts = [marks_.token_spans(dataset, plain) for plain in plains]
-    planned = [prosody.token_attributes(dataset, plain, spans, breaks, s.rate, hop, hp.sampling_rate) for plain, spans, breaks in parsed]
+    planned = [prosody.token_attributes(dataset, plain, spans, breaks, s.rate, hop, hp.sampling_rate, pitch=bool(markup_pitch))
+               for plain, spans, breaks in parsed]
+    pitched = bool(markup_pitch) and any(a[2] != 1.0 for attrs, _breaks in planned for a in attrs)
+    below = {a[2] for attrs, _breaks in planned for a in attrs if a[2] < 1.0} if pitched else ()
+    if len(below) > RESAMPLE_SEGMENTS_MAX_RATIOS:
+        raise ValueError('synthesize_marked: {} distinct pitches above 0 in one call are more than the {} ratios below 1 that '
+                         'resample_segments takes'.format(len(below), RESAMPLE_SEGMENTS_MAX_RATIOS))
     id_sequences, n_sent = dataset.process_sentences(plains)
     rows = [np.frombuffer(q, dtype=np.int32) for q in id_sequences]
     for b, (processed, _spans) in enumerate(texts):
@@ -616,9 +632,11 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
     for a in (d_start, d_stats, d_frames, d_last, memory, alignments):
         if a is not None:
             a.free()
-    segments, n_out, per_row = [], [], []
+    segments, n_out, per_row, per_row_pitch = [], [], [], []
     for b in range(B):
-        seg, n = prosody.segments_of_row(start[b], int(n_sent[b]), r, int(n_frames[b]), planned[b][0], planned[b][1], min_frames, row=b)
+        seg, n, *ratios = prosody.segments_of_row(start[b], int(n_sent[b]), r, int(n_frames[b]), planned[b][0], planned[b][1], min_frames, row=b)
+        if pitched:
+            per_row_pitch.append(prosody.pitch_segments_of_row(seg, ratios[0], hop, n, row=b)[0])
         per_row.append(seg)
         segments += seg
         n_out.append(n)
@@ -627,34 +645,47 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
     assert _n.tolist() == n_out, (_n, n_out)
     wav, _mse = eng.griffin_lim(warped, c.n_iter, c.win_len, hop, hp.n_fft, seed=seed, want_mse=False, momentum=s.momentum, n_frames=n_out,
                                 phase_init=s.phase_init)
-    wavs = finish(eng, wav, hop * (np.asarray(n_out, dtype=np.int32) - 1), seed, peak_normalize)
-    for a in (mel, linear, mag, warped, wav):
-        a.free()
+    held = hop * (np.asarray(n_out, dtype=np.int32) - 1)
+    retimed = None
+    if pitched:
+        retimed, n_samples = eng.resample_segments(wav, [q for seg in per_row_pitch for q in seg], held)
+        held = n_samples.astype(np.int32)
+    wavs = finish(eng, wav if retimed is None else retimed, held, seed, peak_normalize)
+    for a in (mel, linear, mag, warped, wav, retimed):
+        if a is not None:
+            a.free()
     parts = dict(wavs=wavs)
     if s.marks:
         all_marks = []
         for b, (processed, spans) in enumerate(texts):
             place = lambda x, seg=per_row[b]: float(hop) * prosody.warp_position(seg, x / float(hop), 'right')
             place_end = lambda x, seg=per_row[b]: float(hop) * prosody.warp_position(seg, x / float(hop), 'left')
+            if pitched:
+                place = lambda x, seg=per_row_pitch[b], warped_at=place: prosody.pitch_position(seg, warped_at(x), 'right')
+                place_end = lambda x, seg=per_row_pitch[b], warped_at=place_end: prosody.pitch_position(seg, warped_at(x), 'left')
             all_marks.append(marks_.marks_of_row(processed, spans, start[b], r, hop, 1.0, hop * (int(n_frames[b]) - 1), hp.sampling_rate,
                                                  output_rate(hp, s.output), len(wavs[b]), s.marks, raw=plains[b], stats=stats[b],
                                                  place=place, place_end=place_end))
         parts['marks'] = all_marks
     if want_plan:
         parts['plan'] = dict(plain=plains, start=start, n_sent=n_sent, n_frames=n_frames, segments=per_row, n_out=n_out)
+        if markup_pitch:
+            parts['plan'].update(pitch_segments=per_row_pitch if pitched else None, n_samples=[int(v) for v in held])
     return parts
 
 
 @takes_settings('check_alignment')
-def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, **settings):
+def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, markup_pitch=False, **settings):
     """``synthesize_sentences`` for sentences with prosody markup (``synthesize_marked``; ``settings``: its settings): ``{i+1}.wav`` per
     sentence -- peak-normalised unless a ``loudness`` or a ``limiter`` is set -- and, with ``marks``, ``{i+1}.marks.jsonl`` beside it
-    with offsets into the sentence with the markup removed.  Returns the list of waveforms, with ``marks`` ``(waveforms, marks)``."""
+    with offsets into the sentence with the markup removed.  Returns the list of waveforms, with ``marks`` ``(waveforms, marks)``.
+    ``markup_pitch``: ``<prosody pitch=..>`` is accepted, as in ``synthesize_marked``."""
     s = marked_settings(model_params, settings)   # (ValueError before anything is loaded)
     for text in raw_sentences:
-        prosody.parse_markup(text)
+        prosody.parse_markup(text, pitch=bool(markup_pitch))
     out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
-    return write_files(out_dir, s, synthesize_marked.parts(model, raw_sentences, dataset, seed=seed, peak_normalize=s.file_norm()[0], **settings))
+    return write_files(out_dir, s, synthesize_marked.parts(model, raw_sentences, dataset, seed=seed, peak_normalize=s.file_norm()[0],
+                                                           markup_pitch=markup_pitch, **settings))
 
 
 # The pause behind a piece by the break that ends it, in milliseconds.  Untuned: round figures in the range speech synthesizers
@@ -939,7 +970,7 @@ def main(argv=None):
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
                                                             [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
-                                                            [--markup]
+                                                            [--markup [--markup-pitch]]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
@@ -972,7 +1003,9 @@ def main(argv=None):
     ``--markup``: every line of the synthesis file is a sentence with prosody markup (``tacotron.prosody``, a subset of SSML):
     ``<prosody rate="80%" volume="-6 dB">``, ``<emphasis level="strong">`` and ``<break time="300ms"/>`` change the rate, the volume
     and the pauses word by word (``synthesize_marked``; ``--rate`` is then the base rate).  Works with ``--marks``, whose offsets are
-    then into the line with the markup removed; refused together with ``--text``, ``--pitch`` and ``--check-alignment``."""
+    then into the line with the markup removed; refused together with ``--text``, ``--pitch`` and ``--check-alignment``.
+    ``--markup-pitch``: with ``--markup``, ``<prosody pitch="+2st">`` (or ``+N%``, x-low .. x-high; untuned presets) is accepted too
+    and changes the pitch word by word, leaving every word's duration and the marks' meaning alone (``tts_resample_segments``)."""
     args = parse_args(argv)
     settings = settings_option(args)
     SynthSettings(model_params, **settings)
@@ -991,7 +1024,8 @@ def main(argv=None):
     else:
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
     if args.markup:
-        written = synthesize_marked_sentences.parts(raw_sentences, weights, None, out_dir, args.device, args.seed, **settings)
+        written = synthesize_marked_sentences.parts(raw_sentences, weights, None, out_dir, args.device, args.seed, markup_pitch=args.markup_pitch,
+                                                    **settings)
     elif args.text:
         if args.stop_at_silence is None:
             settings['stop_at_silence_db'] = STOP_AT_SILENCE_DB
@@ -1077,7 +1111,12 @@ def parse_args(argv=None):
     ap.add_argument('--markup', action='store_true',
                     help='every line of the synthesis file is a sentence with prosody markup: <prosody rate= volume=>, <emphasis>, <break/> '
                          '(not with --text, --pitch or --check-alignment)')
+    ap.add_argument('--markup-pitch', action='store_true',
+                    help='with --markup: <prosody pitch=> is accepted too (+Nst, -Nst, +N%%, -N%%, x-low .. x-high): a pitch per word, at the '
+                         'word\'s own duration')
     args = ap.parse_args(argv)
+    if args.markup_pitch and not args.markup:
+        ap.error('--markup-pitch requires --markup')
     if args.markup and args.text:
         ap.error('--markup cannot be combined with --text (markup inside long texts is not supported)')
     if args.markup and args.pitch != 0.0:

@@ -937,6 +937,59 @@ int tts_resample_segments_max(void);
 int tts_resample_segments_max_ratios(void);
 int tts_resample_segments_tile(void);
 
+/* ---- formant-preserving pitch: a cepstral-envelope shift of magnitude spectrograms ------------ */
+/* An edit list over the frames of mag DEVICE [B][F][T], written to out DEVICE [B][F][T] -- the layout tts_denorm_power writes and
+ * tts_warp_magnitudes reads (no reference counterpart: the reference's pitch_shift resamples, which moves the formants with the
+ * pitch).  F = N + 1 with N a power of two, 128 .. 2048.  Segment s covers the frames [first, first + frames) of row `row`, frames
+ * >= 1.  The segments of a row are consecutive in the list, rows non-decreasing over 0 .. B - 1, no row without a segment; within a
+ * row the ranges ascend, do not overlap and lie inside n_frames[row] (HOST int32 [B], or NULL: all T).  Durations do not change.
+ *   copies    a frame below n_frames[row] that no segment covers, and every frame of a segment whose two steps are both 65536,
+ *             is the bits of mag: NaN payloads and -0.0 survive.
+ *   zeros     frames t >= n_frames[row] are never read and are written as +0.0.
+ *   computed  every other frame, with x[k] = (double)mag[row][k][t], k = 0 .. N, and Q = order:
+ *               L[k]  = log(max(x[k], 1e-10))                           (a NaN x[k] gives a NaN L[k])
+ *               c[q]  = (1 / N) sum_k w[k] L[k] ct[(q k) mod 2N]        q < Q; w[0] = w[N] = 1/2, else 1; ct[j] = cos(pi j / N), built
+ *                                                                       on the host in double
+ *               E[k]  = sum_{q < Q} h[q] c[q] ct[(q k) mod 2N]          h[0] = 1, h[q] = 1 + cos(pi q / Q): a raised-cosine lifter,
+ *                                                                       built on the host in double
+ *               X[k]  = x[k] exp(-E[k])                                 the fine structure (x itself, not the floored value)
+ *               p  = k * pitch_step (int64); if p > N << 16: p = (2N << 16) - p   (the band above Nyquist is filled by folding)
+ *               i  = p >> 16, a = (p & 65535) * 2^-16;    Xs[k] = (1 - a) X[i] + a X[min(i + 1, N)]
+ *               p' = min(k * formant_step, N << 16), i', a' likewise;   Ew[k] = (1 - a') E[i'] + a' E[min(i' + 1, N)]
+ *               out[row][k][t] = (float)(exp(Ew[k]) Xs[k])              in double, rounded once
+ *             The order of the sums is not prescribed (it depends on N and order alone); the result is within
+ *             2^-24 |y| + eta (|t1| + |t2|) of the same formulas in float64 (tests/shift_oracle.py), t1 and t2 the two terms of the
+ *             blend of Xs times exp(Ew), eta = 2^-53 * 8 Q (F + 2) (1 + max |L|).  An all-zero frame gives +0.0
+ *             exactly; a frame that holds a NaN or an Inf comes out all NaN and touches no other frame; the sign of a negative input
+ *             follows x.
+ * Every element of out is written exactly once per call: no atomics, no memset, nothing read from out; a row's output is the same
+ * bits whatever B is and wherever the row sits in the batch, and however the list is cut into launches.  The list travels by value,
+ * 64 segments per launch: a call makes ceil(S / 64) launches.  ct (2N doubles) is kept on the handle per N and the lifter per
+ * order: the FIRST use of an N or an order builds its table on the host and uploads it with a synchronous copy; otherwise the call
+ * is asynchronous on the handle's stream and waits for nothing.  No model needed; profile stage "shift".
+ * TTS_ERR_INVALID with a message that names the segment or row, before anything is enqueued, in this order: a NULL pointer (mag,
+ * segments, out); out == mag; B, T or S < 1; an F that is not 2^m + 1 with 2^m in 128 .. 2048; order outside 2 ..
+ * min(tts_shift_max_order(), N / 2); S above tts_shift_max_segments(); B above S; an n_frames[b] outside 1 .. T; rows that do not
+ * start at 0, decrease, skip a row or do not end at B - 1; then per segment frames < 1, a range outside [0, n_frames[row]), a range
+ * that starts in front of its predecessor's end, reserved != 0, a pitch_step and then a formant_step outside 32768 .. 131072 (one
+ * octave either way); a misaligned buffer (4 bytes). */
+typedef struct tts_shift_segment {
+    int32_t row, first, frames, reserved;   /* reserved must be 0 */
+    uint32_t pitch_step;    /* source bins per output bin of the fine structure, times 65536: round(65536 / rho) */
+    uint32_t formant_step;  /* source bins per output bin of the envelope, times 65536: round(65536 / phi) */
+} tts_shift_segment_t;   /* HOST, 24 bytes */
+/* Host only, no handle and no device: the checks of the shape, the order and the list (tts_last_error(NULL) has the reason of a
+ * refusal). */
+int tts_shift_plan(const tts_shift_segment_t* segments, int S, int B, int F, int T, const int32_t* n_frames /* HOST [B] or NULL */, int order);
+int tts_shift_magnitudes(tts_handle_t h, const float* mag /* DEVICE [B][F][T] */, int B, int F, int T,
+                         const int32_t* n_frames /* HOST [B] or NULL */, const tts_shift_segment_t* segments, int S, int order,
+                         float* out /* DEVICE [B][F][T], not mag */);
+/* Host only: the most segments a call takes (4096), the frames of a computed segment one workgroup takes (8), and the largest
+ * order (256). */
+int tts_shift_max_segments(void);
+int tts_shift_tile(void);
+int tts_shift_max_order(void);
+
 /* ---- delivery formats: 16-bit PCM, 8-bit PCM and G.711 --------------------------------------- */
 #define TTS_FMT_F32 0        /* float32 as the library makes it: no encoding */
 #define TTS_FMT_PCM_S16 1    /* signed 16-bit PCM, 2 bytes per code */
@@ -1186,7 +1239,7 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, tts_token_times, stand-alone
  * or inside a tts_synthesize call with tts_set_alignment_stats or tts_set_token_times on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
  * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
- * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes).
+ * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes), "shift" (tts_shift_magnitudes).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -135,7 +135,25 @@ class TtsResampleSegment(ctypes.Structure):
 RESAMPLE_SEGMENT = np.dtype([('row', np.int32), ('first', np.int32), ('samples', np.int32), ('reserved', np.int32), ('ratio', np.float64)])
 
 
+class TtsShiftSegment(ctypes.Structure):
+    """tts_shift_segment_t: the frames [first, first + frames) of a row with the fine structure read at ``pitch_step`` / 65536 and
+    the envelope at ``formant_step`` / 65536 source bins per output bin; 24 bytes, a record of the SHIFT_SEGMENT arrays
+    ``Engine.shift_magnitudes`` hands the library"""
+    _fields_ = [('row', c_int32), ('first', c_int32), ('frames', c_int32), ('reserved', c_int32), ('pitch_step', ctypes.c_uint32),
+                ('formant_step', ctypes.c_uint32)]
+
+
+# ... and the same record as a numpy dtype
+SHIFT_SEGMENT = np.dtype([('row', np.int32), ('first', np.int32), ('frames', np.int32), ('reserved', np.int32), ('pitch_step', np.uint32),
+                          ('formant_step', np.uint32)])
+
+
 _PROTOTYPES = {
+    'tts_shift_plan': (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int]),
+    'tts_shift_magnitudes': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_int, c_void_p]),
+    'tts_shift_max_segments': (c_int, []),
+    'tts_shift_tile': (c_int, []),
+    'tts_shift_max_order': (c_int, []),
     'tts_resample_segments_plan': (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_int32), POINTER(c_int64)]),
     'tts_resample_segments': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_int, c_void_p, POINTER(c_int32)]),
     'tts_resample_segments_max': (c_int, []),
@@ -941,6 +959,113 @@ def warp_list(segments, B, T, n_frames=None):
         count[s] = c
         n_out[row] += c
     return q, nf, n_out, count
+
+
+SHIFT_MAX_SEGMENTS = 4096                       # tts_shift_max_segments()
+SHIFT_SEGMENTS_PER_LAUNCH = 64                  # segments whose entries travel with one launch
+SHIFT_TILE = 8                                  # tts_shift_tile()
+SHIFT_MAX_ORDER = 256                           # tts_shift_max_order()
+SHIFT_N_MIN, SHIFT_N_MAX = 128, 2048            # F = N + 1 with N a power of two in this range
+SHIFT_UNITY = 65536
+SHIFT_STEP_MIN, SHIFT_STEP_MAX = 32768, 131072  # one octave either way
+SHIFT_SEMITONES_MAX = 12.0
+
+
+def shift_step(semitones):
+    """The step of ``semitones`` for a SHIFT_SEGMENT: floor(65536 * 2 ** (-st / 12) + 0.5), source bins per output bin times 65536
+    (+12 semitones: 32768, 0: 65536, -12: 131072).  ValueError for a shift that is not finite or lies outside -12 .. 12."""
+    try:
+        st = float(semitones)
+    except (TypeError, ValueError):
+        raise ValueError('shift: a number of semitones in [-12, 12] is needed, got {!r}'.format(semitones))
+    if not -SHIFT_SEMITONES_MAX <= st <= SHIFT_SEMITONES_MAX:   # (a NaN fails both comparisons)
+        raise ValueError('shift: the semitones must be finite and lie in [-12, 12], got {!r}'.format(semitones))
+    return int(np.floor(65536.0 * np.exp2(-np.float64(st) / 12.0) + 0.5))
+
+
+def shift_order(sampling_rate):
+    """the default order of the envelope: max(8, int(0.0015 * sampling_rate)), 33 at 22 050 Hz (untuned)"""
+    return max(8, int(0.0015 * float(sampling_rate)))
+
+
+def shift_launches(S):
+    """launches of a shift of S segments"""
+    return -(-int(S) // SHIFT_SEGMENTS_PER_LAUNCH)
+
+
+def shift_bins_n(F):
+    """N of F = N + 1 bins where N is a power of two in 128 .. 2048, else 0"""
+    N = int(F) - 1
+    return N if SHIFT_N_MIN <= N <= SHIFT_N_MAX and N & (N - 1) == 0 else 0
+
+
+def shift_segments(segments):
+    """``segments`` -- a SHIFT_SEGMENT array, or rows ``(row, first, frames, pitch_step, formant_step)`` -- as a contiguous
+    SHIFT_SEGMENT array (S,).  ValueError for anything that is not such a list or does not fit the record's fields."""
+    if isinstance(segments, np.ndarray) and segments.dtype == SHIFT_SEGMENT and segments.ndim == 1:
+        return np.ascontiguousarray(segments)
+    try:
+        rows = [tuple(r) for r in segments]
+    except TypeError:
+        rows = None
+    if rows is None or any(len(r) != 5 for r in rows):
+        raise ValueError('shift: segments must be a SHIFT_SEGMENT array or rows (row, first, frames, pitch_step, formant_step)')
+    out = np.zeros(len(rows), dtype=SHIFT_SEGMENT)
+    for s, r in enumerate(rows):
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in r) or \
+                any(not -2 ** 31 <= v < 2 ** 31 for v in r[:3]) or any(not 0 <= v < 2 ** 32 for v in r[3:]):
+            raise ValueError('shift: segment {} must hold 32-bit integers row, first, frames, pitch_step and formant_step, got {!r}'.format(s, r))
+        out[s] = tuple(int(v) for v in r[:3]) + (0,) + tuple(int(v) for v in r[3:])
+    return out
+
+
+def shift_list(segments, B, F, T, n_frames=None, order=33):
+    """The segment list of a shift on a batch (B, F, T) as ``(segments, n_frames)``: a contiguous SHIFT_SEGMENT array and the
+    lengths as ``stretch_frame_counts`` makes them.  Checked as tts_shift_plan checks it, in its order and its words -- ValueError,
+    raised before a handle or the library is touched."""
+    q = shift_segments(segments)
+    S = int(q.shape[0])
+    if B < 1 or T < 1 or S < 1:
+        raise ValueError('shift: need B, T, S >= 1')
+    N = shift_bins_n(F)
+    if not N:
+        raise ValueError('shift: F = {} is not 2^m + 1 with 2^m in {} .. {}'.format(F, SHIFT_N_MIN, SHIFT_N_MAX))
+    order_max = min(SHIFT_MAX_ORDER, N // 2)
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or not 2 <= order <= order_max:
+        raise ValueError('shift: order = {} is not in 2 .. {}'.format(order, order_max))
+    if S > SHIFT_MAX_SEGMENTS:
+        raise ValueError('shift: {} segments are more than tts_shift_max_segments() = {}'.format(S, SHIFT_MAX_SEGMENTS))
+    if B > S:
+        raise ValueError('shift: {} rows of {} segments: no row is without a segment'.format(B, S))
+    nf = stretch_frame_counts(n_frames, B, T)
+    rows = q['row'].tolist()
+    if rows[0] != 0:
+        raise ValueError('shift: row of segment 0 is {}: the rows start at 0'.format(rows[0]))
+    for s in range(1, S):
+        if rows[s] - rows[s - 1] not in (0, 1):
+            raise ValueError('shift: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a segment'.format(
+                s, rows[s], rows[s - 1]))
+    if rows[-1] != B - 1:
+        raise ValueError('shift: row of segment {} is {}: the last row is B - 1 = {}'.format(S - 1, rows[-1], B - 1))
+    prev_end, prev_row = 0, 0
+    for s, (row, first, frames, reserved, pitch_step, formant_step) in enumerate(q.tolist()):
+        if row != prev_row:
+            prev_end, prev_row = 0, row
+        if frames < 1:
+            raise ValueError('shift: segment {} has {} frames: at least 1 is needed'.format(s, frames))
+        n = T if nf is None else int(nf[row])
+        if first < 0 or first + frames > n:
+            raise ValueError('shift: segment {} covers frames {} .. {} of row {}, which has 0 .. {}'.format(s, first, first + frames - 1, row, n - 1))
+        if first < prev_end:
+            raise ValueError("shift: segment {} starts at frame {} of row {}, in front of its predecessor's end {}: the ranges of a row ascend "
+                             'and do not overlap'.format(s, first, row, prev_end))
+        if reserved != 0:
+            raise ValueError('shift: segment {} has reserved = {}, which must be 0'.format(s, reserved))
+        for name, step in (('pitch_step', pitch_step), ('formant_step', formant_step)):
+            if not SHIFT_STEP_MIN <= step <= SHIFT_STEP_MAX:
+                raise ValueError('shift: segment {} has {} {}, which is not in {} .. {}'.format(s, name, step, SHIFT_STEP_MIN, SHIFT_STEP_MAX))
+        prev_end = first + frames
+    return q, nf
 
 
 RESAMPLE_RATIO_MIN, RESAMPLE_RATIO_MAX = 0.25, 4.0
@@ -2258,6 +2383,63 @@ class Engine(object):
                                                          out.data_ptr()), out)
         return out, n_out
 
+    # ------------------------------------------------------------------ formant-preserving pitch: the envelope shift
+    def shift_max_segments(self):
+        """tts_shift_max_segments: the most segments :meth:`shift_magnitudes` takes in one call."""
+        return int(self.lib.tts_shift_max_segments())
+
+    def shift_tile(self):
+        """tts_shift_tile: the frames of a computed segment one workgroup of the shift takes."""
+        return int(self.lib.tts_shift_tile())
+
+    def shift_max_order(self):
+        """tts_shift_max_order: the largest order of the envelope."""
+        return int(self.lib.tts_shift_max_order())
+
+    def shift_plan(self, shape, segments, n_frames=None, order=None):
+        """tts_shift_plan, host only: the library's checks of ``segments`` -- a SHIFT_SEGMENT array or rows ``(row, first, frames,
+        pitch_step, formant_step)`` -- on a batch of ``shape`` (B, F, T) whose rows hold ``n_frames`` frames (None: all T) at
+        ``order`` (None: ``shift_order`` of the model's sampling rate).  Returns the launches the call would make.  ValueError for a
+        list tts_shift_magnitudes refuses (``shift_list``), raised before the library is reached."""
+        if len(shape) != 3:
+            raise ValueError('shift_plan: the shape of a batch (B, F, T) is needed, got {!r}'.format(tuple(shape)))
+        B, F, T = (int(d) for d in shape)
+        order = shift_order(self.sampling_rate) if order is None else order
+        q, nf = shift_list(segments, B, F, T, n_frames, order)
+        rc = self.lib.tts_shift_plan(q.ctypes.data, q.shape[0], B, F, T, _int32_ptr(nf), int(order))
+        if rc != TTS_OK:
+            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        return shift_launches(q.shape[0])
+
+    def shift_magnitudes(self, mag, segments, n_frames=None, order=None, out=None):
+        """tts_shift_magnitudes: a pitch change that leaves the formants where they are, on ``mag`` (B, F, T) -- a host array, which is
+        uploaded, or a device buffer, which is read in place; F = N + 1 with N a power of two, 128 .. 2048.  ``segments``: a
+        SHIFT_SEGMENT array or rows ``(row, first, frames, pitch_step, formant_step)``, the segments of a row ascending and
+        the rows in order: in the frames [first, first + frames) the fine structure (the harmonics) is read at ``pitch_step`` /
+        65536 and the cepstral envelope of ``order`` coefficients at ``formant_step`` / 65536 source bins per output bin
+        (``shift_step(semitones)`` makes a step).  Frames no segment covers, and segments at 65536 / 65536, are copied bit for bit;
+        frames at or behind ``n_frames`` (B host integers; None: all T) are never read and come out +0.0.  ``order`` None:
+        ``shift_order`` of the model's sampling rate (33 at 22 050 Hz).  include/sstts_hip.h has the definition.
+
+        Returns a device array (B, F, T): ``out`` where one is given (a device buffer of that shape, not ``mag``), else a fresh one.
+        ValueError for what the library refuses, raised before it is reached."""
+        if len(mag.shape) != 3 or min(mag.shape) < 1:
+            raise ValueError('shift_magnitudes: a non-empty 3-D array is needed, got shape {}'.format(tuple(mag.shape)))
+        B, F, T = (int(d) for d in mag.shape)
+        order = shift_order(self.sampling_rate) if order is None else order
+        q, nf = shift_list(segments, B, F, T, n_frames, order)
+        p_mag, _k = self._in(mag, np.float32)
+        if out is not None:
+            if tuple(out.shape) != (B, F, T) or not hasattr(out, 'data_ptr'):
+                raise ValueError('shift_magnitudes: out must be a device buffer of shape {}'.format((B, F, T)))
+            self._check(self.lib.tts_shift_magnitudes(self.handle, p_mag, B, F, T, _int32_ptr(nf), q.ctypes.data, q.shape[0], int(order),
+                                                      out.data_ptr()))
+            return out
+        res = self.empty((B, F, T))
+        self._check_or_free(self.lib.tts_shift_magnitudes(self.handle, p_mag, B, F, T, _int32_ptr(nf), q.ctypes.data, q.shape[0], int(order),
+                                                          res.data_ptr()), res)
+        return res
+
     def time_stretch(self, wavs, rate, n_iter=25, seed=0, want_magnitudes=False):
         """The reference's waveform effect time_stretch (audio/effects.py:46-88) as a composition of existing calls:
         ``stft_magnitude`` (n_fft 1024, window 1024, hop 256, power 1), ``stretch_magnitudes``, then ``griffin_lim`` in the
@@ -2374,14 +2556,44 @@ class Engine(object):
         assert (got == n_out).all(), (got, n_out)
         return out, n_out
 
-    def pitch_shift(self, wavs, sampling_rate, octaves, n_iter=25, seed=0):
+    def pitch_shift(self, wavs, sampling_rate, octaves, n_iter=25, seed=0, preserve_formants=False, order=None, init_phase=None):
         """The reference's waveform effect pitch_shift (audio/effects.py:9-43) as a composition of existing calls:
         ``time_stretch(wavs, rate)`` with rate = 2 ** -octaves, then ``resample`` from sampling_rate / rate back to
         sampling_rate, cut or zero-padded to the input's length (librosa's fix_length).  ``wavs``: one waveform (n,) or a
-        uniform batch (B, n).  Returns a device array of the input's shape."""
+        uniform batch (B, n).  Returns a device array of the input's shape.
+
+        ``preserve_formants`` (no reference counterpart): ``stft_magnitude`` (n_fft 1024, window 1024, hop 256, power 1),
+        ``shift_magnitudes`` with one segment per row at ``shift_step(12 * octaves)`` for the fine structure and 65536 for the
+        envelope (``order`` None: ``shift_order(sampling_rate)``), then ``griffin_lim`` at the same length: nothing is resampled,
+        the 256 (n // 256) samples are zero-padded to the input's length.  ``init_phase`` (B, 513, 1 + n // 256): Griffin-Lim's
+        initial phases in [0, 1) in place of the seed's."""
         o = pitch_octaves_value(octaves)
         if o is None:
             raise ValueError('pitch_shift: a shift in [-1, 1] octaves is needed')
+        if preserve_formants:
+            sr = float(sampling_rate)
+            if not sr > 0:
+                raise ValueError('pitch_shift: sampling_rate must be positive, got {!r}'.format(sampling_rate))
+            wavs, single, B, n = _waveforms('pitch_shift', wavs, uniform=True)
+            n_fft, win, hop = 1024, 1024, 256
+            T = 1 + n // hop
+            if hop * (T - 1) <= n_fft // 2:
+                raise ValueError('pitch_shift: {} samples are a signal shorter than n_fft / 2'.format(n))
+            step = shift_step(12.0 * o)
+            mag = self.stft_magnitude(wavs, n_fft, win, hop, 1.0)
+            shifted = wav = None
+            try:
+                shifted = self.shift_magnitudes(mag, [(b, 0, T, step, SHIFT_UNITY) for b in range(B)],
+                                                order=shift_order(sr) if order is None else order)
+                wav, _mse = self.griffin_lim(shifted, int(n_iter), win, hop, n_fft, init_phase=init_phase, seed=seed, want_mse=False)
+                out, _n = self.resample_segments(wav, [(b, 0, hop * (T - 1), 1.0) for b in range(B)], N_out=n)   # (copies, then +0.0)
+            finally:
+                for a in (mag, shifted, wav):
+                    if a is not None:
+                        a.free()
+            if single:
+                out.shape = (n,)
+            return out
         rate = float(np.exp2(-np.float64(o)))
         sr = float(sampling_rate)
         if not sr > 0:

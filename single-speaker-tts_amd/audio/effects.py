@@ -23,8 +23,18 @@ from .conversion import ms_to_samples
 from .._hip import limiter_lookahead
 
 
-def pitch_shift(wav, sampling_rate, octaves):
-    raise NotImplementedError('pitch_shift (librosa resampling, reference audio/effects.py:9-43) is out of scope')   # see Engine.pitch_shift
+def pitch_shift(wav, sampling_rate, octaves, preserve_formants=False, n_iter=25, seed=0, engine=None):
+    """With ``preserve_formants`` (no reference counterpart): ``wav`` -- one mono waveform (n,) or a uniform batch (B, n) -- with its
+    pitch moved by ``octaves`` and its spectral envelope left where it is, at the same length (``Engine.pitch_shift(..,
+    preserve_formants=True)``: STFT magnitude, ``shift_magnitudes``, Griffin-Lim).  Returns a float32 host array of the input's
+    shape.  Without it: the reference's resampling form, which is out of scope here."""
+    if not preserve_formants:
+        raise NotImplementedError('pitch_shift (librosa resampling, reference audio/effects.py:9-43) is out of scope')   # see Engine.pitch_shift
+    eng = engine or default_engine()
+    out = eng.pitch_shift(np.asarray(wav, dtype=np.float32), sampling_rate, octaves, n_iter=n_iter, seed=seed, preserve_formants=True)
+    host = out.to_host()
+    out.free()
+    return host
 
 
 def time_stretch(wav, rate):

@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw", "f0", "loudness", "alignment", "join", "limiter", "encode", "warp"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw", "f0", "loudness", "alignment", "join", "limiter", "encode", "warp", "shift"};
 }  // namespace tts_api
 
 namespace tts_api {
@@ -648,6 +648,7 @@ int tts_destroy(tts_handle_t h) {
     feat_release(h);
     resample_release(h);
     mfcc_release(h);
+    shift_release(h);
     if (h->eos.pinned) hipHostFree(h->eos.pinned);
     if (h->an.flag) hipFree(h->an.flag);
     for (auto& kv : h->glg.tw) hipFree(kv.second);

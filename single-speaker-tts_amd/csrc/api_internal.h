@@ -56,7 +56,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_WARP, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_WARP, ST_SHIFT, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -510,6 +510,12 @@ struct tts_handle_s {
     // cepstra (cepstrum.hip): the DCT tables on the device, one per (n_mels << 32 | n_mfcc)
     std::map<uint64_t, double*> mfcc_tabs;
 
+    // formant-preserving pitch (shift.hip): the cosine table per N and the lifter per order on the device
+    struct {
+        std::map<int, double*> ct, lifter;
+        bool configured = false;   // the kernel's LDS limit has been raised on this handle's device
+    } shift;
+
     // analysis-side tables (STFT window, mel basis)
     struct {
         int win = 0;
@@ -695,6 +701,7 @@ int resample_impl(tts_handle_t h, const float* wav, int B, int n, const int32_t*
                   float* out);
 void resample_release(tts_handle_t h);
 void mfcc_release(tts_handle_t h);   // cepstrum.hip: the DCT tables
+void shift_release(tts_handle_t h);  // shift.hip: the cosine tables and lifters
 // estimated initial phases (phase_init.hip): both input layouts -> the public (B, F, T) array on h->stream, arguments checked by
 // the caller (phase_plan.h).  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with the option "gl_init" the
 // estimate from the time-major magnitudes `magi` in PhaseScratch::init_est, or null.

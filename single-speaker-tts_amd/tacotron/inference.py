@@ -17,7 +17,7 @@ import types
 import numpy as np
 
 from . import attention_check, marks as marks_, prosody
-from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, RESAMPLE_SEGMENTS_MAX_RATIOS,
+from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, RESAMPLE_SEGMENTS_MAX_RATIOS, shift_step,
                     limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
                     output_setting, phase_init_value, pitch_octaves_value, pitch_semitones_value, resampled_length,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting, synth_frame_counts, token_times_jump)
@@ -549,10 +549,31 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
                                                           **settings))
 
 
-def marked_settings(hp, settings):
-    """the record of ``synthesize_marked``, for itself and for its file form: no pitch"""
+def envelope_mode(markup_pitch, pitch_mode, timbre):
+    """``(envelope, timbre_st)`` of ``synthesize_marked``'s three pitch arguments.  ValueError for a mode that is not one of
+    ``prosody.PITCH_MODES``, for 'envelope' without ``markup_pitch``, and for a ``timbre`` that is not a finite number of semitones
+    in [-12, 12] or is other than 0 outside the envelope mode (where nothing could apply it)."""
+    if pitch_mode not in prosody.PITCH_MODES:
+        raise ValueError('synthesize_marked: pitch_mode must be one of {}, got {!r}'.format(prosody.PITCH_MODES, pitch_mode))
+    envelope = pitch_mode == 'envelope'
+    if envelope and not markup_pitch:
+        raise ValueError("synthesize_marked: pitch_mode='envelope' needs markup_pitch=True")
+    try:
+        st = float(timbre)
+    except (TypeError, ValueError):
+        st = float('nan')
+    if not -12.0 <= st <= 12.0:
+        raise ValueError('synthesize_marked: timbre must be a finite number of semitones in [-12, 12], got {!r}'.format(timbre))
+    if st != 0.0 and not envelope:
+        raise ValueError("synthesize_marked: a timbre other than 0 needs pitch_mode='envelope', got {!r}".format(timbre))
+    return envelope, st
+
+
+def marked_settings(hp, settings, envelope=False):
+    """the record of ``synthesize_marked``, for itself and for its file form: no pitch, unless the pitch is made on the envelope's
+    side (``envelope``), where a global pitch adds to every token's"""
     s = SynthSettings(hp, **settings)
-    if s.octaves != 0.0:
+    if s.octaves != 0.0 and not envelope:
         raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global), got {!r}'.format(
             settings.get('pitch') if settings.get('pitch_semitones') is None else settings['pitch_semitones']))
     return s
@@ -560,7 +581,7 @@ def marked_settings(hp, settings):
 
 @takes_settings('check_alignment')
 def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=None, seed=0, peak_normalize=False, want_plan=False,
-                      markup_pitch=False, **settings):
+                      markup_pitch=False, pitch_mode='resample', timbre=0.0, **settings):
     """Sentences with prosody markup (``tacotron.prosody``: ``<prosody rate=.. volume=..>``, ``<emphasis>``, ``<break/>`` under an
     optional ``<speak>``) -> a list of B waveforms, row b cut to its own hop (n_out[b] - 1) samples (no reference counterpart).
 
@@ -588,8 +609,19 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
     plan gains ``pitch_segments`` and ``n_samples``, per row (None and hop (n_out - 1) where no pass ran).  If no sentence of the
     call holds a pitch other than 0 the pass is not launched: the bits of the call without the option.  More than
     ``RESAMPLE_SEGMENTS_MAX_RATIOS`` distinct ratios below 1 (pitches above 0) in one call is a ValueError that gives the count;
-    the global ``pitch`` stays refused."""
-    s = marked_settings(model, settings)
+    the global ``pitch`` stays refused.
+
+    ``pitch_mode`` 'envelope' (with ``markup_pitch``; the default 'resample' is the above): the pitch is made ahead of Griffin-Lim on
+    the frequency axis and the formants stay where they are.  ``shift_magnitudes`` (tts_shift_magnitudes) runs between
+    ``denorm_power`` and ``warp_magnitudes`` on the frames of every speech segment (``prosody.shift_segments_of_row``), nothing is
+    stretched further and no ``resample_segments`` runs: the warp's segments are planned from the attributes without the pitch, so the
+    row lengths and the marks are exactly those of the same text without any pitch (``prosody.warp_position`` alone).  Here the global ``pitch`` (octaves) is accepted and adds to every token's, and
+    ``timbre`` (semitones in [-12, 12]) moves the envelope of every frame; the sum of a token's pitches must stay within an
+    octave.  The plan gains ``shift_segments``, per row (None where the stage did not run).  If the text holds no pitch and both
+    ``pitch`` and ``timbre`` are 0 the stage is not launched: the bits of the call without the option.  The order of the envelope
+    is ``shift_order`` of the model's sampling rate; it, the lifter and the folding are untuned."""
+    envelope, timbre_st = envelope_mode(markup_pitch, pitch_mode, timbre)
+    s = marked_settings(model, settings, envelope)
     hp = model.hparams
     c = call_constants(model, n_steps, n_iter)
     hop, r = c.hop, hp.reduction
@@ -598,9 +630,12 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
         raise ValueError('synthesize_marked: no sentence')
     plains = [p[0] for p in parsed]
     texts = [marks_.token_spans(dataset, plain) for plain in plains]
-    planned = [prosody.token_attributes(dataset, plain, spans, breaks, s.rate, hop, hp.sampling_rate, pitch=bool(markup_pitch))
+    planned = [prosody.token_attributes(dataset, plain, spans, breaks, s.rate, hop, hp.sampling_rate, pitch=bool(markup_pitch), pitch_mode=pitch_mode)
                for plain, spans, breaks in parsed]
-    pitched = bool(markup_pitch) and any(a[2] != 1.0 for attrs, _breaks in planned for a in attrs)
+    pitched = bool(markup_pitch) and not envelope and any(a[2] != 1.0 for attrs, _breaks in planned for a in attrs)
+    # the envelope's side: every token's semitones with the global pitch added; the stage runs where any step is not 65536
+    global_st = 12.0 * s.octaves if envelope else 0.0
+    shifted = envelope and (timbre_st != 0.0 or any(shift_step(a[2] + global_st) != 65536 for attrs, _breaks in planned for a in attrs))
     below = {a[2] for attrs, _breaks in planned for a in attrs if a[2] < 1.0} if pitched else ()
     if len(below) > RESAMPLE_SEGMENTS_MAX_RATIOS:
         raise ValueError('synthesize_marked: {} distinct pitches above 0 in one call are more than the {} ratios below 1 that '
@@ -632,15 +667,26 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
     for a in (d_start, d_stats, d_frames, d_last, memory, alignments):
         if a is not None:
             a.free()
-    segments, n_out, per_row, per_row_pitch = [], [], [], []
+    segments, n_out, per_row, per_row_pitch, per_row_shift = [], [], [], [], []
     for b in range(B):
         seg, n, *ratios = prosody.segments_of_row(start[b], int(n_sent[b]), r, int(n_frames[b]), planned[b][0], planned[b][1], min_frames, row=b)
         if pitched:
             per_row_pitch.append(prosody.pitch_segments_of_row(seg, ratios[0], hop, n, row=b)[0])
+        if envelope:
+            # the warp's segments are those of the text without any pitch -- a border between two pitches alone must not cut a segment, or
+            # the frame it rounds up to would move --; the cut at the pitches serves the shift alone
+            if shifted:
+                per_row_shift.append(prosody.shift_segments_of_row(seg, [0.0 if q[2] == 0 else st + global_st for q, st in zip(seg, ratios[0])],
+                                                                   timbre_st, row=b))
+            seg, n = prosody.segments_of_row(start[b], int(n_sent[b]), r, int(n_frames[b]), [a[:2] for a in planned[b][0]], planned[b][1],
+                                             min_frames, row=b)
         per_row.append(seg)
         segments += seg
         n_out.append(n)
     mag = eng.denorm_power(linear, c.ref_db, c.max_db, hp.magnitude_power)
+    plain_mag = None
+    if shifted:
+        plain_mag, mag = mag, eng.shift_magnitudes(mag, [q for seg in per_row_shift for q in seg], n_frames)
     warped, _n = eng.warp_magnitudes(mag, segments, n_frames)
     assert _n.tolist() == n_out, (_n, n_out)
     wav, _mse = eng.griffin_lim(warped, c.n_iter, c.win_len, hop, hp.n_fft, seed=seed, want_mse=False, momentum=s.momentum, n_frames=n_out,
@@ -651,7 +697,7 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
         retimed, n_samples = eng.resample_segments(wav, [q for seg in per_row_pitch for q in seg], held)
         held = n_samples.astype(np.int32)
     wavs = finish(eng, wav if retimed is None else retimed, held, seed, peak_normalize)
-    for a in (mel, linear, mag, warped, wav, retimed):
+    for a in (mel, linear, plain_mag, mag, warped, wav, retimed):
         if a is not None:
             a.free()
     parts = dict(wavs=wavs)
@@ -671,21 +717,25 @@ def synthesize_marked(model, marked_sentences, dataset, n_steps=None, n_iter=Non
         parts['plan'] = dict(plain=plains, start=start, n_sent=n_sent, n_frames=n_frames, segments=per_row, n_out=n_out)
         if markup_pitch:
             parts['plan'].update(pitch_segments=per_row_pitch if pitched else None, n_samples=[int(v) for v in held])
+        if envelope:
+            parts['plan'].update(shift_segments=per_row_shift if shifted else None)
     return parts
 
 
 @takes_settings('check_alignment')
-def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, markup_pitch=False, **settings):
+def synthesize_marked_sentences(raw_sentences, weights, dataset=None, out_dir=None, device_id=0, seed=0, markup_pitch=False, pitch_mode='resample',
+                                timbre=0.0, **settings):
     """``synthesize_sentences`` for sentences with prosody markup (``synthesize_marked``; ``settings``: its settings): ``{i+1}.wav`` per
     sentence -- peak-normalised unless a ``loudness`` or a ``limiter`` is set -- and, with ``marks``, ``{i+1}.marks.jsonl`` beside it
     with offsets into the sentence with the markup removed.  Returns the list of waveforms, with ``marks`` ``(waveforms, marks)``.
-    ``markup_pitch``: ``<prosody pitch=..>`` is accepted, as in ``synthesize_marked``."""
-    s = marked_settings(model_params, settings)   # (ValueError before anything is loaded)
+    ``markup_pitch``, ``pitch_mode`` and ``timbre``: as in ``synthesize_marked``."""
+    envelope, _st = envelope_mode(markup_pitch, pitch_mode, timbre)
+    s = marked_settings(model_params, settings, envelope)   # (ValueError before anything is loaded)
     for text in raw_sentences:
         prosody.parse_markup(text, pitch=bool(markup_pitch))
     out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
     return write_files(out_dir, s, synthesize_marked.parts(model, raw_sentences, dataset, seed=seed, peak_normalize=s.file_norm()[0],
-                                                           markup_pitch=markup_pitch, **settings))
+                                                           markup_pitch=markup_pitch, pitch_mode=pitch_mode, timbre=timbre, **settings))
 
 
 # The pause behind a piece by the break that ends it, in milliseconds.  Untuned: round figures in the range speech synthesizers
@@ -970,7 +1020,7 @@ def main(argv=None):
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
                                                             [--text [--max-chars N] [--pause-ms KIND=MS ...] [--fade-ms MS]]
-                                                            [--markup [--markup-pitch]]
+                                                            [--markup [--markup-pitch [--pitch-mode resample|envelope] [--timbre ST]]]
 
     The options override the ``inference_params`` fields of the same name.  ``--weights`` takes what
     ``Tacotron.restore`` takes (a TensorFlow checkpoint prefix or run directory, or an ``.npz`` of the manifest's
@@ -1005,7 +1055,10 @@ def main(argv=None):
     and the pauses word by word (``synthesize_marked``; ``--rate`` is then the base rate).  Works with ``--marks``, whose offsets are
     then into the line with the markup removed; refused together with ``--text``, ``--pitch`` and ``--check-alignment``.
     ``--markup-pitch``: with ``--markup``, ``<prosody pitch="+2st">`` (or ``+N%``, x-low .. x-high; untuned presets) is accepted too
-    and changes the pitch word by word, leaving every word's duration and the marks' meaning alone (``tts_resample_segments``)."""
+    and changes the pitch word by word, leaving every word's duration and the marks' meaning alone (``tts_resample_segments``).
+    ``--pitch-mode envelope``: with ``--markup --markup-pitch``, the pitch is made on the frequency axis ahead of Griffin-Lim
+    (``tts_shift_magnitudes``) and the formants stay where they are; ``--pitch`` is then allowed beside ``--markup`` and adds to every
+    word, and ``--timbre ST`` moves the formants of every frame by ST semitones.  The default, ``resample``, is the above."""
     args = parse_args(argv)
     settings = settings_option(args)
     SynthSettings(model_params, **settings)
@@ -1025,7 +1078,7 @@ def main(argv=None):
         weights = os.path.join(inference_params.checkpoint_dir, inference_params.checkpoint_load_run)
     if args.markup:
         written = synthesize_marked_sentences.parts(raw_sentences, weights, None, out_dir, args.device, args.seed, markup_pitch=args.markup_pitch,
-                                                    **settings)
+                                                    pitch_mode=args.pitch_mode, timbre=args.timbre, **settings)
     elif args.text:
         if args.stop_at_silence is None:
             settings['stop_at_silence_db'] = STOP_AT_SILENCE_DB
@@ -1114,12 +1167,25 @@ def parse_args(argv=None):
     ap.add_argument('--markup-pitch', action='store_true',
                     help='with --markup: <prosody pitch=> is accepted too (+Nst, -Nst, +N%%, -N%%, x-low .. x-high): a pitch per word, at the '
                          'word\'s own duration')
+    ap.add_argument('--pitch-mode', choices=prosody.PITCH_MODES, default='resample',
+                    help='with --markup --markup-pitch: how a pitch is made -- resample (default): behind Griffin-Lim on the samples, the '
+                         'formants move with the pitch; envelope: ahead of it on the frequency axis, the formants stay (--pitch is then allowed '
+                         'and adds to every word)')
+    ap.add_argument('--timbre', type=float, default=0.0, metavar='ST',
+                    help='with --pitch-mode envelope: move the spectral envelope (the formants) of every frame by ST semitones, -12 .. 12 (untuned)')
     args = ap.parse_args(argv)
     if args.markup_pitch and not args.markup:
         ap.error('--markup-pitch requires --markup')
+    envelope = args.pitch_mode == 'envelope'
+    if envelope and not args.markup_pitch:
+        ap.error('--pitch-mode envelope requires --markup --markup-pitch')
+    if args.timbre != 0.0 and not envelope:
+        ap.error('--timbre requires --pitch-mode envelope')
+    if not -12.0 <= args.timbre <= 12.0:
+        ap.error('--timbre must lie in [-12, 12] semitones')
     if args.markup and args.text:
         ap.error('--markup cannot be combined with --text (markup inside long texts is not supported)')
-    if args.markup and args.pitch != 0.0:
+    if args.markup and args.pitch != 0.0 and not envelope:
         ap.error('--markup cannot be combined with --pitch (a pitch needs the call pipeline\'s resampler)')
     if args.markup and args.check_alignment:
         ap.error('--markup cannot be combined with --check-alignment')

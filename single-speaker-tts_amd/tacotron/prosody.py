@@ -9,6 +9,9 @@ With ``pitch=True`` the parser also takes ``<prosody pitch=..>``: a token then c
 semitones beside a step that stretches it by that much more, ``pitch_segments_of_row`` turns the warp's segments into the sample
 segments of ``Engine.resample_segments`` (tts_resample_segments), which takes Griffin-Lim's samples of the word back to the
 duration it has without the pitch, and ``pitch_position`` is the map from a Griffin-Lim sample to its place in the retimed row.
+With ``pitch_mode='envelope'`` the pitch is made ahead of Griffin-Lim on the frequency axis instead, where the formants stay put:
+a token carries its semitones beside the step of the text without any pitch, and ``shift_segments_of_row`` turns the warp
+segments' source ranges into the segments of ``Engine.shift_magnitudes`` (tts_shift_magnitudes); nothing is stretched or resampled.
 Everything here is host arithmetic on a few integers.
 
 What is NOT known: no trained checkpoint is at hand, so how any of this sounds on real speech has not been measured.  A border
@@ -24,12 +27,13 @@ from xml.parsers import expat
 import numpy as np
 
 from . import marks as marks_
-from .._hip import resample_segment_count, warp_count
+from .._hip import resample_segment_count, shift_step, warp_count
 
 RATE_MIN, RATE_MAX = 0.25, 4.0          # the rates of tts_stretch_magnitudes and of a segment's step / 65536
 GAIN_MAX = 16.0                         # the largest gain of a segment (+24.08 dB)
 STEP_ONE = 65536
 STEP_MIN, STEP_MAX = 16384, 262144      # the steps tts_warp_magnitudes takes
+PITCH_MODES = ('resample', 'envelope')  # how a <prosody pitch=..> is made: behind Griffin-Lim on the samples, or ahead of it on the frequency axis
 
 # UNTUNED presets (see the module's note)
 RATES = {'x-slow': 0.5, 'slow': 0.75, 'medium': 1.0, 'fast': 1.25, 'x-fast': 1.5}
@@ -232,7 +236,7 @@ def break_frames(ms, hop, sampling_rate):
     return max(1, int(math.floor(float(ms) * float(sampling_rate) / (1000.0 * float(hop)) + 0.5)))
 
 
-def token_attributes(dataset, plain, spans, breaks, base_rate=1.0, hop=275, sampling_rate=22050, pitch=False):
+def token_attributes(dataset, plain, spans, breaks, base_rate=1.0, hop=275, sampling_rate=22050, pitch=False, pitch_mode='resample'):
     """``(attrs, token_breaks)`` of a parsed sentence.  ``attrs``: one ``(step, gain)`` per token of the processed sentence --
     ``marks.token_spans``: lower case, abbreviations expanded -- and a last one for the end token, which carries the base
     attributes: ``step = round(65536 * base_rate * rate)`` and ``gain`` the float32 of 10 ** (volume_db / 20).  A token takes
@@ -246,12 +250,19 @@ def token_attributes(dataset, plain, spans, breaks, base_rate=1.0, hop=275, samp
     ratio)``: ``step = round(65536 * base_rate * rate * 2 ** (-st / 12))`` -- the warp stretches the token's frames by a further
     2 ** (-st / 12) -- and ``ratio = 2.0 ** (-st / 12.0)``, at which ``Engine.resample_segments`` takes the token's samples back
     to the duration they have without the pitch (1.0 where there is none).  ValueError, naming the span, for a step outside
-    [16384, 262144]."""
+    [16384, 262144].
+
+    ``pitch_mode`` 'envelope' (with ``pitch``): the pitch is made on the frequency axis (``Engine.shift_magnitudes``), so nothing is
+    stretched and an attribute is ``(step, gain, st)``: the step of the call without any pitch, ``round(65536 * base_rate * rate)``,
+    and the span's semitones (0.0 where there is none).  'resample' (the default): as above."""
+    if pitch_mode not in PITCH_MODES:
+        raise ValueError('token_attributes: pitch_mode must be one of {}, got {!r}'.format(PITCH_MODES, pitch_mode))
+    envelope = bool(pitch) and pitch_mode == 'envelope'
     base = float(base_rate)
     if not RATE_MIN <= base <= RATE_MAX:
         raise ValueError('token_attributes: the base rate must lie in [0.25, 4], got {!r}'.format(base_rate))
     processed, tok = marks_.token_spans(dataset, plain)
-    one = (int(math.floor(STEP_ONE * base + 0.5)), np.float32(1.0)) + ((1.0,) if pitch else ())
+    one = (int(math.floor(STEP_ONE * base + 0.5)), np.float32(1.0)) + (((0.0,) if envelope else (1.0,)) if pitch else ())
     attrs = [one] * (len(processed) + 1)
     for k, span in enumerate(spans):
         a, b, rate, volume_db = span[:4]
@@ -263,7 +274,9 @@ def token_attributes(dataset, plain, spans, breaks, base_rate=1.0, hop=275, samp
         if not gain <= GAIN_MAX:
             raise ValueError('token_attributes: {} has volume {:+g} dB, a gain above 16'.format(what, volume_db))
         value = (int(math.floor(STEP_ONE * product + 0.5)), gain)
-        if pitch:
+        if envelope:
+            value = value + (float(span[4]),)
+        elif pitch:
             ratio = pitch_ratio(span[4])
             step = int(math.floor(STEP_ONE * product * ratio + 0.5))
             if not STEP_MIN <= step <= STEP_MAX:
@@ -388,6 +401,28 @@ def pitch_segments_of_row(warp_segments, ratios, hop, n_out, row=0):
     if o != int(n_out):
         raise ValueError('pitch_segments_of_row: the segments make {} frames, the row has {}'.format(o, n_out))
     return [tuple(q) for q in seg], sum(resample_segment_count(q[2], q[3]) for q in seg)
+
+
+def shift_segments_of_row(warp_segments, semitones, timbre_st=0.0, row=0):
+    """The segments of one utterance for ``Engine.shift_magnitudes``, rows ``(row, first, frames, pitch_step, formant_step)``.
+    ``warp_segments`` / ``semitones``: ``segments_of_row``'s under ``token_attributes(.., pitch_mode='envelope')`` -- the SOURCE
+    frames [first, first + frames) of every speech segment (already clipped at the end-of-speech cut) get ``shift_step(st)`` for
+    the fine structure and ``shift_step(timbre_st)`` for the envelope, ``timbre_st`` the same for every frame; a pause has no
+    source frames and is skipped, and neighbours that touch and have equal steps merge.  The shift runs ahead of the warp, on the
+    frames the network made.  ValueError for semitones outside -12 .. 12."""
+    if len(semitones) != len(warp_segments):
+        raise ValueError('shift_segments_of_row: {} segments need {} pitches, got {}'.format(len(warp_segments), len(warp_segments), len(semitones)))
+    formant = shift_step(timbre_st)
+    seg = []
+    for (_row, first, frames, _pause, _step, _gain), st in zip(warp_segments, semitones):
+        if frames == 0:
+            continue
+        step = shift_step(st)
+        if seg and seg[-1][1] + seg[-1][2] == first and seg[-1][3] == step:
+            seg[-1][2] += frames
+        else:
+            seg.append([row, int(first), int(frames), step, formant])
+    return [tuple(q) for q in seg]
 
 
 def pitch_position(segments, sample, side='right'):

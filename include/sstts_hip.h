@@ -710,6 +710,53 @@ int tts_limit(tts_handle_t h, float* wav /* [B][N], in place */, int B, int N, c
 /* Host only: the largest lookahead, 1024 samples. */
 int tts_limit_max_lookahead(void);
 
+/* ---- the equaliser: a cascade of second-order sections -------------------------------------- */
+/* Kinds of tts_equalizer_design. */
+#define TTS_EQ_LOWPASS 0
+#define TTS_EQ_HIGHPASS 1
+#define TTS_EQ_PEAK 2
+#define TTS_EQ_LOWSHELF 3
+#define TTS_EQ_HIGHSHELF 4
+/* A cascade of n_sections = 1 .. tts_equalizer_max_sections() second-order sections over every utterance (no reference
+ * counterpart).  A section is the five doubles b0 b1 b2 a1 a2, normalised by a0; a sample runs through the cascade in direct form
+ * II transposed, section after section:
+ *   y = b0 x + z1;   z1 = (b1 x - a1 y) + z2;   z2 = b2 x - a2 y;   the next section's x = y
+ * every product and sum an individually rounded IEEE double operation, the state zero in front of an utterance's first sample, and
+ * the last section's y rounded to float32 once.  The recurrence is sequential, so an utterance is cut into segments of 256 samples
+ * (the cut does not depend on a sampling rate; csrc/equalizer_plan.h): pass 1 runs every segment but the last from the zero state
+ * and keeps the 2 n_sections state values it ends in, e_i; pass 2 chains them, S_0 = 0 and
+ *   S_{i+1}[r] = (((M[r][0] S_i[0] + M[r][1] S_i[1]) + M[r][2] S_i[2]) + ...) + e_i[r]
+ * in ascending column order with e_i[r] last, M the transition of 256 samples of zero input (column j: the state the recurrence
+ * ends in from the unit state j), which the device computes with the same recurrence in a small launch of its own; pass 3 runs
+ * every segment again from S_i and writes the output.  The result is the bits of tests/equalizer_oracle.py, and within 2^-30 of
+ * its largest |y| of the recurrence run without a cut (DESIGN.md has the measured figures).  A NaN or an infinite sample makes
+ * the rest of its utterance NaN, as the recurrence does.
+ * out may equal wav (in place); any other overlap is refused.  Samples at or behind n_samples[b] are neither read nor written,
+ * every other element of out is written exactly once, and an utterance's result is the bits of its B = 1 call.  Asynchronous on
+ * the handle's stream, no host wait, nothing uploaded: one launch for M and three per 64 utterances; the workspace is the segments'
+ * states.  Profile stage "equalize".
+ * TTS_ERR_INVALID, before anything is enqueued, in this order: a NULL wav, out or sos; B or N < 1; an n_samples[b] outside 1 .. N;
+ * n_sections outside 1 .. tts_equalizer_max_sections(); a coefficient that is not finite; a section outside the stability
+ * triangle (|a2| < 1 and |a1| < 1 + a2 are needed); a buffer that is not 4-byte aligned; out overlapping wav without being equal
+ * to it. */
+int tts_equalize(tts_handle_t h, const float* wav /* [B][N] */, float* out /* [B][N]; may equal wav */, int B, int N,
+                 const int32_t* n_samples /* HOST [B] or NULL */, const double* sos /* HOST [n_sections][5] */, int n_sections);
+/* Host only: one section by the bilinear transform in its tan form, K = tan(pi f0 / sr).  TTS_EQ_LOWPASS and TTS_EQ_HIGHPASS take
+ * a Q (gain_db is not looked at); TTS_EQ_PEAK, TTS_EQ_LOWSHELF and TTS_EQ_HIGHSHELF a Q and a gain in dB: a peak reads gain_db at
+ * f0, a shelf gain_db / 2 at f0, gain_db at its end of the band and 0 dB at the other.  One low-pass or high-pass section at Q =
+ * 0.7071067811865476 is a 2nd-order Butterworth filter, two at Q = 0.5411961001461969 and 1.3065629648763766 a 4th-order one.
+ * TTS_ERR_UNSUPPORTED: a sampling rate outside 8000 .. 192000, f0 / sr outside 1e-4 .. 0.49, a Q outside 0.1 .. 30, a gain outside
+ * -40 .. +24 dB.  TTS_ERR_INVALID: another kind, a NULL pointer. */
+int tts_equalizer_design(int kind, int sampling_rate, double f0_hz, double q, double gain_db, double* sos5_out);
+/* Host only: the sections of a named profile at a sampling rate -- "telephony" (4th-order Butterworth high-pass at 300 Hz, then
+ * low-pass at 3400 Hz: 4 sections), "small-speaker" (4th-order high-pass at 150 Hz and a +3 dB peak at 3 kHz, Q 1), "rumble"
+ * (2nd-order high-pass at 20 Hz, Q 0.7071), "bright" (high shelf at 6 kHz, +3 dB), "warm" (high shelf at 6 kHz, -3 dB, and a low
+ * shelf at 200 Hz, +2 dB).  Every preset is UNTUNED: nobody has listened to one.  TTS_ERR_UNSUPPORTED: the sampling rate, or a
+ * corner that does not fit under 0.49 sr (tts_last_error(NULL) names it).  TTS_ERR_INVALID: an unknown name, a NULL pointer. */
+int tts_equalizer_profile(const char* name, int sampling_rate, double* sos_out /* [8][5] */, int* n_sections_out);
+/* Host only: the largest cascade, 8 sections. */
+int tts_equalizer_max_sections(void);
+
 /* ---- attention diagnostics: alignment statistics ------------------------------------------- */
 /* What the decoder's alignments say about whether the sentence was read (no reference counterpart: the reference plots its
  * alignments, tacotron/model.py:552-598, and judges them by eye).  alignments DEVICE [n_steps_max][B][Ts] as the decoder
@@ -1157,6 +1204,18 @@ int tts_set_loudness(tts_handle_t h, int enabled, double target_lufs, double max
  * not finite and positive, a lookahead outside 0 .. tts_limit_max_lookahead(), an oversample other than 1 or 4). */
 int tts_set_limiter(tts_handle_t h, int enabled, double ceiling, int lookahead, int oversample);
 
+/* The equaliser of synthesis (tts_equalize).  A setting of the HANDLE, off by default and read when a call is made; off is the
+ * call as it always was, launch for launch.  With enabled != 0, tts_synthesize and tts_synthesize_host run
+ * tts_equalize(sos, n_sections) in place on the call's rows -- behind Griffin-Lim, the pitch resampler and the peak normalisation,
+ * ahead of the loudness normaliser and the limiter -- on the call's stream, with no host wait, over the samples each row holds
+ * (the lengths the loudness setting uses).  The sections are copied.  The result is the bits of the same call made with the
+ * setting off followed by tts_equalize on those rows.  Lengths, shapes and timing marks do not change: the group delay of a few
+ * samples is ignored.  A boost behind the peak normalisation can pass 1.0: give it a limiter or a loudness target.  The first
+ * call after the setting was switched on is not pipelined (its buffers are new).
+ * With enabled == 0 the other arguments are not looked at.  The setting stays as it was on TTS_ERR_INVALID (a NULL sos, n_sections
+ * outside 1 .. tts_equalizer_max_sections(), a coefficient that is not finite, a section that is not stable). */
+int tts_set_equalizer(tts_handle_t h, int enabled, const double* sos /* HOST [n_sections][5] */, int n_sections);
+
 /* Attention diagnostics of synthesis: the alignment statistics of every call (tts_alignment_stats).  A setting of the HANDLE,
  * off by default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
  * tts_synthesize and tts_synthesize_host run tts_text_lengths(pad_id) on the call's device ids behind its encoder and
@@ -1239,7 +1298,8 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * or inside a tts_synthesize call with a loudness target), "alignment" (tts_alignment_stats, tts_text_lengths, tts_token_times, stand-alone
  * or inside a tts_synthesize call with tts_set_alignment_stats or tts_set_token_times on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
  * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
- * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes), "shift" (tts_shift_magnitudes).
+ * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes), "shift" (tts_shift_magnitudes), "equalize" (tts_equalize,
+ * stand-alone or inside a tts_synthesize call with tts_set_equalizer on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -10,6 +10,7 @@ tensor) -- PyTorch is optional plumbing, not a dependency of this module.
 import collections
 import contextlib
 import ctypes
+import math
 import os
 from ctypes import (POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64,
                     c_void_p)
@@ -253,6 +254,11 @@ _PROTOTYPES = {
     'tts_limit': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), ctypes.c_double, c_int, c_int, c_void_p]),
     'tts_limit_max_lookahead': (c_int, []),
     'tts_set_limiter': (c_int, [c_void_p, c_int, ctypes.c_double, c_int, c_int]),
+    'tts_equalize': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), POINTER(ctypes.c_double), c_int]),
+    'tts_equalizer_design': (c_int, [c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double)]),
+    'tts_equalizer_profile': (c_int, [c_char_p, c_int, POINTER(ctypes.c_double), POINTER(c_int)]),
+    'tts_equalizer_max_sections': (c_int, []),
+    'tts_set_equalizer': (c_int, [c_void_p, c_int, POINTER(ctypes.c_double), c_int]),
     'tts_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
     'tts_encode_width': (c_int, [c_int]),
     'tts_encode_tile': (c_int, []),
@@ -657,6 +663,142 @@ def true_peak_filter():
     if rc != TTS_OK:
         raise TtsError(rc, 'tts_true_peak_filter refused')
     return np.array(out[:], dtype=np.float64).reshape(4, 12)
+
+
+# ---- the equaliser (csrc/equalizer_plan.h): the kinds of a section, the limits of a design and the profiles.  Every preset is
+# untuned: nobody has listened to one.
+EQ_MAX_SECTIONS = 8              # tts_equalizer_max_sections()
+EQ_KINDS = {'lowpass': 0, 'highpass': 1, 'peak': 2, 'lowshelf': 3, 'highshelf': 4}
+EQ_KIND_NAMES = {v: k for k, v in EQ_KINDS.items()}
+EQ_SR_MIN, EQ_SR_MAX = 8000, 192000
+EQ_F_MIN, EQ_F_MAX = 1e-4, 0.49      # f0 / sr
+EQ_Q_MIN, EQ_Q_MAX = 0.1, 30.0
+EQ_GAIN_MIN, EQ_GAIN_MAX = -40.0, 24.0
+EQ_Q_BUTTER2 = 0.7071067811865476    # one low- or high-pass section: 2nd-order Butterworth; the default Q
+EQ_Q_BUTTER4 = (0.5411961001461969, 1.3065629648763766)   # two of them: 4th-order Butterworth
+EQ_PROFILES = collections.OrderedDict((
+    ('telephony', (('highpass', 300.0, EQ_Q_BUTTER4[0], 0.0), ('highpass', 300.0, EQ_Q_BUTTER4[1], 0.0),
+                   ('lowpass', 3400.0, EQ_Q_BUTTER4[0], 0.0), ('lowpass', 3400.0, EQ_Q_BUTTER4[1], 0.0))),
+    ('small-speaker', (('highpass', 150.0, EQ_Q_BUTTER4[0], 0.0), ('highpass', 150.0, EQ_Q_BUTTER4[1], 0.0), ('peak', 3000.0, 1.0, 3.0))),
+    ('rumble', (('highpass', 20.0, 0.7071, 0.0),)),
+    ('bright', (('highshelf', 6000.0, EQ_Q_BUTTER2, 3.0),)),
+    ('warm', (('highshelf', 6000.0, EQ_Q_BUTTER2, -3.0), ('lowshelf', 200.0, EQ_Q_BUTTER2, 2.0))),
+))
+
+
+def equalizer_design(kind, sampling_rate, f0_hz, q=EQ_Q_BUTTER2, gain_db=0.0):
+    """One section ``(b0, b1, b2, a1, a2)``, normalised by a0, as tts_equalizer_design makes it (csrc/equalizer_plan.h: the
+    bilinear transform in its tan form), in Python floats; needs no library.  ``kind``: a name of ``EQ_KINDS`` or its number.
+    ValueError: a kind, sampling rate, f0 / sr, Q or gain outside the limits."""
+    k = EQ_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+    if isinstance(k, bool) or k not in EQ_KIND_NAMES:
+        raise ValueError('equalizer: the kind must be one of {}, got {!r}'.format(', '.join(EQ_KINDS), kind))
+    sr = sampling_rate
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not EQ_SR_MIN <= sr <= EQ_SR_MAX:
+        raise ValueError('equalizer: the sampling rate must be an integer in {} .. {}, got {!r}'.format(EQ_SR_MIN, EQ_SR_MAX, sr))
+    try:
+        f0, q, g = float(f0_hz), float(EQ_Q_BUTTER2 if q is None else q), float(0.0 if gain_db is None else gain_db)
+    except (TypeError, ValueError):
+        raise ValueError('equalizer: f0, Q and the gain must be numbers, got {!r}'.format((f0_hz, q, gain_db)))
+    if not EQ_F_MIN * sr <= f0 <= EQ_F_MAX * sr:   # (against the products: f0 = 0.49 * sr is inside)
+        raise ValueError('equalizer: {} at {:g} Hz: f0 / sr = {:g} at {} Hz is not in {:g} .. {:g}'.format(EQ_KIND_NAMES[k], f0, f0 / sr, sr, EQ_F_MIN, EQ_F_MAX))
+    if not EQ_Q_MIN <= q <= EQ_Q_MAX:
+        raise ValueError('equalizer: Q = {:g} is not in {:g} .. {:g}'.format(q, EQ_Q_MIN, EQ_Q_MAX))
+    if k >= 2 and not EQ_GAIN_MIN <= g <= EQ_GAIN_MAX:
+        raise ValueError('equalizer: a gain of {:g} dB is not in {:g} .. {:g}'.format(g, EQ_GAIN_MIN, EQ_GAIN_MAX))
+    K = math.tan(math.pi * f0 / sr)
+    KK, KQ = K * K, K / q
+    if k < 2:
+        a0, a1, a2 = 1.0 + KQ + KK, 2.0 * (KK - 1.0), 1.0 - KQ + KK
+        b0, b1 = (KK, 2.0 * KK) if k == 0 else (1.0, -2.0)
+        b2 = b0
+    elif k == 2:
+        A = 10.0 ** (g / 40.0)
+        b0, b1, b2 = 1.0 + KQ * A + KK, 2.0 * (KK - 1.0), 1.0 - KQ * A + KK
+        a0, a1, a2 = 1.0 + KQ / A + KK, b1, 1.0 - KQ / A + KK
+    else:
+        A = 10.0 ** (g / 40.0)
+        s = math.sqrt(A) * KQ
+        lift, rest, lift_m, rest_m = 1.0 + A * KK, A + KK, 2.0 * (A * KK - 1.0), 2.0 * (KK - A)
+        if k == 3:
+            b0, b1, b2, a0, a1, a2 = A * (lift + s), A * lift_m, A * (lift - s), rest + s, rest_m, rest - s
+        else:
+            b0, b1, b2, a0, a1, a2 = A * (rest + s), A * rest_m, A * (rest - s), lift + s, lift_m, lift - s
+    return (b0 / a0, b1 / a0, b2 / a0, a1 / a0, a2 / a0)
+
+
+def equalizer_profile(name, sampling_rate):
+    """The sections of a profile of ``EQ_PROFILES`` at a sampling rate, float64 (S, 5), as tts_equalizer_profile makes them.
+    ValueError: an unknown name, or a corner that does not fit under 0.49 sr (the message names the profile)."""
+    if name not in EQ_PROFILES:
+        raise ValueError('equalizer: no profile {!r} (there are: {})'.format(name, ', '.join(EQ_PROFILES)))
+    try:
+        return np.array([equalizer_design(k, sampling_rate, f0, q, g) for k, f0, q, g in EQ_PROFILES[name]], dtype=np.float64)
+    except ValueError as e:
+        raise ValueError("equalizer: the profile '{}' does not fit {} Hz: {}".format(name, sampling_rate, e))
+
+
+def equalizer_sos_check(what, sos):
+    """``sos`` as float64 (S, 5) rows b0 b1 b2 a1 a2, checked as tts_equalize checks them; ValueError before a handle is touched"""
+    try:
+        a = np.array(sos, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('{}: sections of five numbers b0 b1 b2 a1 a2 are needed, got {!r}'.format(what, sos))
+    if a.ndim != 2 or a.shape[1] != 5 or not 1 <= a.shape[0] <= EQ_MAX_SECTIONS:
+        raise ValueError('{}: 1 .. {} sections of five numbers b0 b1 b2 a1 a2 are needed, got shape {}'.format(what, EQ_MAX_SECTIONS, a.shape))
+    if not np.all(np.isfinite(a)):
+        raise ValueError('{}: every coefficient must be finite'.format(what))
+    for i, (a1, a2) in enumerate(a[:, 3:]):
+        if not (abs(a2) < 1.0 and abs(a1) < 1.0 + a2):
+            raise ValueError('{}: section {} is not stable: |a2| < 1 and |a1| < 1 + a2 are needed'.format(what, i))
+    return np.ascontiguousarray(a)
+
+
+def equalizer_setting(equalizer):
+    """``equalizer`` of the synthesis calls -- None (the handle's setting as it stands), a profile name of ``EQ_PROFILES``, a list
+    of ``(kind, f0_hz[, q[, gain_db]])`` sections (Q 0.7071..., 0 dB where left out) or an (S, 5) array of sections b0 b1 b2 a1
+    a2 -- as what the mirror holds: None, ``('profile', name)``, ``('design', ((kind, f0, q, gain_db), ...))`` or ``('sos', ((b0,
+    b1, b2, a1, a2), ...))``.  ValueError before a handle is touched; what depends on the sampling rate is checked where the rate
+    is known (``equalizer_sections``)."""
+    if equalizer is None:
+        return None
+    if isinstance(equalizer, str):
+        if equalizer not in EQ_PROFILES:
+            raise ValueError('equalizer: no profile {!r} (there are: {})'.format(equalizer, ', '.join(EQ_PROFILES)))
+        return ('profile', equalizer)
+    if isinstance(equalizer, tuple) and len(equalizer) == 2 and equalizer[0] in ('profile', 'design', 'sos') and not isinstance(equalizer[1], (int, float)):
+        return equalizer_setting(equalizer[1])   # (a checked value: checked again)
+    if isinstance(equalizer, np.ndarray) or (isinstance(equalizer, (list, tuple)) and len(equalizer) and
+                                             all(isinstance(r, (list, tuple, np.ndarray)) and len(r) == 5 and not isinstance(r[0], str) for r in equalizer)):
+        return ('sos', tuple(tuple(float(v) for v in row) for row in equalizer_sos_check('equalizer', equalizer)))
+    if not isinstance(equalizer, (list, tuple)) or not 1 <= len(equalizer) <= EQ_MAX_SECTIONS:
+        raise ValueError('equalizer must be None, a profile name, 1 .. {} (kind, f0_hz, q, gain_db) sections or an (S, 5) array, got {!r}'.format(
+            EQ_MAX_SECTIONS, equalizer))
+    rows = []
+    for row in equalizer:
+        if not isinstance(row, (list, tuple)) or not 2 <= len(row) <= 4:
+            raise ValueError('equalizer: a section is (kind, f0_hz[, q[, gain_db]]), got {!r}'.format(row))
+        kind, f0 = row[0], row[1]
+        q = row[2] if len(row) > 2 and row[2] is not None else EQ_Q_BUTTER2
+        g = row[3] if len(row) > 3 and row[3] is not None else 0.0
+        k = EQ_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+        if isinstance(k, bool) or k not in EQ_KIND_NAMES:
+            raise ValueError('equalizer: the kind must be one of {}, got {!r}'.format(', '.join(EQ_KINDS), kind))
+        equalizer_design(k, 48000, 1000.0, q, g)   # (Q and the gain; f0 waits for the rate)
+        if isinstance(f0, bool) or not isinstance(f0, (int, float, np.integer, np.floating)) or not (math.isfinite(f0) and f0 > 0):
+            raise ValueError('equalizer: f0 must be a positive number of Hz, got {!r}'.format(f0))
+        rows.append((EQ_KIND_NAMES[k], float(f0), float(q), float(g)))
+    return ('design', tuple(rows))
+
+
+def equalizer_sections(setting, sampling_rate):
+    """the sections, float64 (S, 5), of a checked ``equalizer_setting`` at a sampling rate; ValueError where a corner does not fit"""
+    how, what = setting
+    if how == 'profile':
+        return equalizer_profile(what, sampling_rate)
+    if how == 'design':
+        return np.array([equalizer_design(k, sampling_rate, f0, q, g) for k, f0, q, g in what], dtype=np.float64)
+    return equalizer_sos_check('equalizer', what)
 
 
 # The delivery formats (TTS_FMT_* of include/sstts_hip.h) by the names every layer above uses, the numpy type of a code and the
@@ -1335,6 +1477,15 @@ HOST_SETTINGS = (
 MARK_SETTINGS = (
     Setting('token_times', '_token_times', TOKEN_TIMES_OFF, token_times_setting, lambda engine, v: engine.set_token_times(*v)),
 )
+# ... and the tone, a table of its own behind the three (their lengths and contents are fixed): ``equalizer`` -- a profile name of
+# EQ_PROFILES, a list of ``(kind, f0_hz, q, gain_db)`` sections or an (S, 5) array of sections (tts_set_equalizer, off unless
+# ``set_equalizer`` changed it): the call's rows go through ``equalize`` in place, behind Griffin-Lim, the pitch resampler and the
+# peak normalisation and ahead of the loudness gain and the limiter, each utterance over the samples its row holds; a design is made
+# at the model's sampling rate.  Lengths, shapes and timing marks do not change (the group delay of a few samples is ignored); a
+# boost behind the peak normalisation can pass 1.0: give it a limiter or a loudness target.
+TONE_SETTINGS = (
+    Setting('equalizer', '_equalizer', None, equalizer_setting, lambda engine, v: engine.set_equalizer(v)),
+)
 
 
 class _Settings(object):
@@ -1345,7 +1496,7 @@ class _Settings(object):
 
     def __init__(self, engine, per_call):
         self.engine = engine
-        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS if row.keyword in per_call]
+        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + TONE_SETTINGS if row.keyword in per_call]
         self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
 
     def __getitem__(self, keyword):
@@ -1467,7 +1618,7 @@ class Engine(object):
 
     def _init_settings(self):
         """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
-        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS:
+        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + TONE_SETTINGS:
             setattr(self, row.mirror, row.initial)
 
     def _settings(self, **per_call):
@@ -1519,6 +1670,18 @@ class Engine(object):
             L = limiter_lookahead('set_limiter', setting[1], self.sampling_rate if sampling_rate is None else sampling_rate)
             self._check(self.lib.tts_set_limiter(self.handle, 1, setting[0], L, setting[2]))
         self._limiter = setting
+
+    def set_equalizer(self, equalizer, sampling_rate=None):
+        """tts_set_equalizer: the handle's setting, read by every synthesize / synthesize_host call made after it.  ``equalizer``:
+        None or False (off), or what ``equalizer_setting`` reads -- a profile name, ``(kind, f0_hz, q, gain_db)`` sections or an
+        (S, 5) array; a design is made at ``sampling_rate`` (None: the model's).  The library copies the sections."""
+        setting = equalizer_setting(None if equalizer is False else equalizer)
+        if setting is None:
+            self._check(self.lib.tts_set_equalizer(self.handle, 0, None, 0))
+        else:
+            sos = equalizer_sections(setting, self.sampling_rate if sampling_rate is None else sampling_rate)
+            self._check(self.lib.tts_set_equalizer(self.handle, 1, sos.ctypes.data_as(POINTER(ctypes.c_double)), len(sos)))
+        self._equalizer = setting
 
     def set_output(self, output):
         """tts_set_output: the handle's setting, read by every synthesize_host call made after it.  ``output``: None, False or
@@ -2089,6 +2252,35 @@ class Engine(object):
             out.shape = (n,)
         return out, stats
 
+    # ------------------------------------------------------------------ the equaliser
+    def equalize(self, wavs, sections, n_samples=None, out=None):
+        """tts_equalize: every utterance of ``wavs`` -- one mono waveform (n,) or a batch (B, n), a host array or a device buffer --
+        through a cascade of second-order sections.  ``sections``: an (S, 5) array of rows b0 b1 b2 a1 a2, S in 1 .. 8, or anything
+        else ``equalizer_setting`` reads (a profile name, ``(kind, f0_hz, q, gain_db)`` sections: designed at the model's sampling
+        rate).  Returns a device array of the input's shape: ``out`` where one is given (a device buffer of the input's size, which
+        may be the input), else a device input filtered in place and handed back, a host input uploaded first.  ``n_samples``: B
+        lengths (host integers) -- samples at or behind them are neither read nor written; None: all n.  The bits of
+        tests/equalizer_oracle.py."""
+        wavs, single, B, n, ns = self._ragged_waveforms('equalize', wavs, n_samples)
+        setting = equalizer_setting(sections)
+        if setting is None:
+            raise ValueError('equalize: sections are needed')
+        sos = equalizer_sections(setting, self.sampling_rate)
+        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
+            raise ValueError('equalize: out must be a device buffer of {} floats'.format(B * n))
+        fresh = out is None and not _is_device(wavs)
+        if fresh:
+            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
+            p_wav = out.data_ptr()
+        else:
+            p_wav, _k = self._in(wavs, np.float32)
+            out = wavs if out is None else out
+        self._check_or_free(self.lib.tts_equalize(self.handle, p_wav, out.data_ptr(), B, n, _int32_ptr(ns),
+                                                  sos.ctypes.data_as(POINTER(ctypes.c_double)), len(sos)), out if fresh else None)
+        if fresh and single:
+            out.shape = (n,)
+        return out
+
     # ------------------------------------------------------------------ delivery formats
     def encode(self, wav, format, dither='tpdf', seed=0, n_samples=None):
         """tts_encode: float32 rows to delivery codes -- ``format`` 'pcm16' (int16), 'pcm8', 'mulaw' or 'alaw' (uint8) -- in one
@@ -2614,9 +2806,10 @@ class Engine(object):
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
-                   alignment_stats=None, limiter=None, token_times=None, **refused):
+                   alignment_stats=None, limiter=None, token_times=None, equalizer=None, **refused):
         """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` to
-        ``limiter`` hold for this call alone, as SETTINGS has them, and ``token_times`` as MARK_SETTINGS has it.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
+        ``limiter`` hold for this call alone, as SETTINGS has them, ``token_times`` as MARK_SETTINGS has it and ``equalizer`` as
+        TONE_SETTINGS has it.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
         call's rows stay on the device, where ``resample`` and ``encode`` take them."""
         if 'output' in refused:
             raise ValueError('synthesize: no output= here -- the waveforms stay on the device as float32; resample and encode them there '
@@ -2625,7 +2818,7 @@ class Engine(object):
             raise TypeError('synthesize() got an unexpected keyword argument {!r}'.format(sorted(refused)[0]))
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter,
-                              token_times=token_times)
+                              token_times=token_times, equalizer=equalizer)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call, o_call = call['speaking_rate'], call['pitch']
@@ -2677,17 +2870,18 @@ class Engine(object):
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
                         speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None,
-                        output=None, token_times=None):
+                        output=None, token_times=None, equalizer=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
         The nine settings from ``momentum`` on hold for this call alone, as SETTINGS and HOST_SETTINGS have them: they are read when the call is
         made, not when its work runs.  A call made with an ``output`` is fetched with ``wait_host_encoded``, not ``wait_host``.  A call that stops at silence returns once its post-net has run (the lengths:
         ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``), and so do the
-        timing marks of a call made with ``token_times`` (MARK_SETTINGS; ``wait_host_token_times``)."""
+        timing marks of a call made with ``token_times`` (MARK_SETTINGS; ``wait_host_token_times``).  ``equalizer`` (TONE_SETTINGS)
+        holds for this call alone too."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output,
-                              token_times=token_times)
+                              token_times=token_times, equalizer=equalizer)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape

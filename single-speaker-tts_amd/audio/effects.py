@@ -15,12 +15,13 @@ synthesis calls (tts_set_pitch), which stretches the call's magnitudes and resam
 ``normalize_loudness`` has no reference counterpart (the reference's only level control is the peak normalisation of save_wav):
 one gain takes a waveform to a target integrated loudness after ITU-R BS.1770-4 (tts_loudness_normalize); the loudness of
 synthesis is the ``loudness`` argument of the synthesis calls (tts_set_loudness).  ``limit`` is the look-ahead peak limiter behind
-it (tts_limit; the ``limiter`` argument of the synthesis calls, tts_set_limiter)."""
+it (tts_limit; the ``limiter`` argument of the synthesis calls, tts_set_limiter).  ``equalize`` shapes the spectrum with a cascade
+of second-order sections (tts_equalize; the ``equalizer`` argument of the synthesis calls, tts_set_equalizer)."""
 import numpy as np
 
 from . import default_engine
 from .conversion import ms_to_samples
-from .._hip import limiter_lookahead
+from .._hip import equalizer_sections, equalizer_setting, limiter_lookahead
 
 
 def pitch_shift(wav, sampling_rate, octaves, preserve_formants=False, n_iter=25, seed=0, engine=None):
@@ -62,6 +63,23 @@ def limit(wav, ceiling, sampling_rate=None, lookahead_ms=5.0, true_peak=True, en
     eng = engine or default_engine()
     L = limiter_lookahead('limit', lookahead_ms, eng.sampling_rate if sampling_rate is None else sampling_rate)
     out, _stats = eng.limit(np.asarray(wav, dtype=np.float32), ceiling, L, 4 if true_peak else 1)
+    host = out.to_host()
+    out.free()
+    return host
+
+
+def equalize(wav, sampling_rate, equalizer, engine=None):
+    """``wav`` -- one mono waveform (n,) or a batch (B, n) -- through a cascade of up to 8 second-order sections
+    (``Engine.equalize``).  ``equalizer``: a profile name -- 'telephony', 'small-speaker', 'rumble', 'bright', 'warm'; every preset is
+    untuned --, a list of ``(kind, f0_hz[, q[, gain_db]])`` sections or an (S, 5) array of sections b0 b1 b2 a1 a2; a profile
+    or a design is made at ``sampling_rate`` (None: the engine's), and a corner that does not fit under 0.49 of it is a
+    ValueError.  The length does not change: the group delay of a few samples stays in.  Returns a float32 host array of the
+    input's shape."""
+    setting = equalizer_setting(equalizer)
+    if setting is None:
+        raise ValueError('equalize: an equalizer is needed')
+    eng = engine or default_engine()
+    out = eng.equalize(np.asarray(wav, dtype=np.float32), equalizer_sections(setting, eng.sampling_rate if sampling_rate is None else int(sampling_rate)))
     host = out.to_host()
     out.free()
     return host

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import attention_check, marks as marks_, prosody
 from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, RESAMPLE_SEGMENTS_MAX_RATIOS, shift_step,
-                    limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
+                    equalizer_sections, equalizer_setting, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
                     output_setting, phase_init_value, pitch_octaves_value, pitch_semitones_value, resampled_length,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting, synth_frame_counts, token_times_jump)
 from ..audio.conversion import ms_to_samples
@@ -183,7 +183,7 @@ def deliver(engine, wavs, setting, seed=0, norm=False, what='utterance'):
 class SynthSettings(object):
     """The synthesis settings every helper of this layer takes, checked once -- ValueError before an engine is touched, in the
     order of ``_hip.SETTINGS`` -- and kept as the checked values ``momentum``, ``stop``, ``rate``, ``octaves``, ``phase_init``,
-    ``loud``, ``check_alignment``, ``limiter`` and ``output`` (``output_of``).  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
+    ``loud``, ``check_alignment``, ``limiter``, ``output`` (``output_of``) and ``equalizer``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
 
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind its last frame whose loudest bin is above that many
@@ -215,7 +215,13 @@ class SynthSettings(object):
     ``marks``: None, 'word' or 'char' -- the call also searches its alignments for the best monotone path on the device
     (``Engine.token_times``, at most ``marks_max_jump`` tokens a decoder step; 4, untuned) and the helper answers with timing
     marks as its last element (``tacotron.marks``): when every word -- and with 'char' every character -- is spoken, in
-    milliseconds and in samples of what is delivered."""
+    milliseconds and in samples of what is delivered.
+    ``equalizer`` (taken by ``SynthSettings.of``, behind the constructor's keywords): None (the engine's setting), a profile name -- 'telephony', 'small-speaker', 'rumble', 'bright', 'warm'; every
+    preset is untuned -- a list of ``(kind, f0_hz[, q[, gain_db]])`` sections (kinds 'lowpass', 'highpass', 'peak', 'lowshelf',
+    'highshelf') or an (S, 5) array of second-order sections: a cascade of up to 8 biquads (``Engine.equalize``) shapes the
+    spectrum of every utterance on the device, behind Griffin-Lim, the pitch and the peak normalisation and ahead of the loudness
+    gain and the limiter.  Lengths and timing marks do not change (the group delay of a few samples is ignored).  A boost behind
+    the peak normalisation can pass 1.0: give it a limiter or a loudness target."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
                  phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None,
@@ -234,12 +240,26 @@ class SynthSettings(object):
         self.output = output_of(hp, output)
         self.marks = marks_.marks_kind(marks)
         self.marks_max_jump = token_times_jump(marks_max_jump, 'marks_max_jump')
+        self.equalizer = None
+
+    @classmethod
+    def of(cls, hp, equalizer=None, **settings):
+        """The record of a helper's ``**settings``: the constructor's keywords and, checked behind them, the tone keywords
+        (TONE_KEYWORDS; ``_hip.TONE_SETTINGS`` is likewise a table behind the others) -- ``equalizer``, refused here too where a
+        corner does not fit the model's sampling rate."""
+        s = cls(hp, **settings)
+        s.equalizer = equalizer_setting(equalizer)
+        rate = getattr(getattr(hp, 'hparams', hp), 'sampling_rate', None)
+        if s.equalizer is not None and rate:
+            equalizer_sections(s.equalizer, int(rate))
+        return s
 
     def engine_keywords(self):
         """the settings as ``Engine.synthesize`` / ``Engine.synthesize_host`` take them"""
         return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
                     phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None,
-                    limiter=self.limiter, token_times=(True, pad_id(), self.marks_max_jump) if self.marks else None)
+                    limiter=self.limiter, token_times=(True, pad_id(), self.marks_max_jump) if self.marks else None,
+                    equalizer=self.equalizer)
 
     def host_keywords(self):
         """... and as ``Engine.synthesize_host`` alone takes them: with the delivery format"""
@@ -249,7 +269,8 @@ class SynthSettings(object):
         """the settings as the stand-alone stages honour them (``serve.post_process_spectrograms``): the checked values, without
         ``check_alignment``, ``output`` and the marks"""
         return dict(momentum=self.momentum, stop_at_silence_db=self.stop_at_silence_db, silence_keep_ms=self.silence_keep_ms,
-                    speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter)
+                    speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter,
+                    equalizer=self.equalizer)
 
     def file_norm(self):
         """the peak normalisation of the file helpers, ``(on the device, in save_wav)``: none with a loudness or a limiter, else
@@ -258,7 +279,8 @@ class SynthSettings(object):
         return norm and self.output is not None, norm and self.output is None
 
 
-SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:]
+TONE_KEYWORDS = tuple(inspect.signature(SynthSettings.of).parameters)[1:-1]      # ('equalizer',)
+SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:] + TONE_KEYWORDS
 
 
 def takes_settings(*refuses, only=None):
@@ -290,7 +312,7 @@ def takes_settings(*refuses, only=None):
                 return answer(parts(*args, **taken(keywords)))
         functools.update_wrapper(helper, parts)
         own = [p for p in inspect.signature(parts).parameters.values() if p.kind is not p.VAR_KEYWORD]
-        record = inspect.signature(SynthSettings.__init__).parameters
+        record = dict(inspect.signature(SynthSettings.__init__).parameters, **{k: inspect.signature(SynthSettings.of).parameters[k] for k in TONE_KEYWORDS})
         helper.__signature__ = inspect.Signature(own + [record[k].replace(kind=inspect.Parameter.KEYWORD_ONLY)
                                                         for k in SETTING_KEYWORDS if k not in refuses])
         helper.parts = parts
@@ -324,16 +346,20 @@ def held_samples(c, s, n_frames, B):
 def finishing_tail(caller, s, sampling_rate, deliver=True):
     """The tail behind a Griffin-Lim that a helper composes of stand-alone stages.  The limiter's look-ahead becomes samples here,
     before an engine is touched (ValueError that names ``caller``); the function returned then runs, on device rows (B, N) that
-    hold ``held[b]`` samples each (None: all N), the ``loudness`` or else a peak normalisation (``peak_normalize``), the ``limiter``,
+    hold ``held[b]`` samples each (None: all N), a peak normalisation (``peak_normalize``, where there is no ``loudness``), the
+    ``equalizer`` (its sections are made here too, at ``sampling_rate``), the ``loudness``, the ``limiter``,
     and hands back ``deliver_rows`` for an ``output`` (with ``deliver``; the dither's ``seed``) or else the rows downloaded, a list
     of B arrays cut to what they hold.  ``rows`` stays the caller's to free."""
     lookahead = None if s.limiter is None else limiter_lookahead(caller, s.limiter[1], sampling_rate)
+    sections = None if s.equalizer is None else equalizer_sections(s.equalizer, sampling_rate)
 
     def finish(engine, rows, held, seed=0, peak_normalize=False):
+        if s.loud is None and peak_normalize:
+            engine.peak_normalize(rows)
+        if sections is not None:
+            engine.equalize(rows, sections, n_samples=held)
         if s.loud is not None:
             engine.loudness_normalize(rows, sampling_rate, s.loud[0], s.loud[1], n_samples=held)
-        elif peak_normalize:
-            engine.peak_normalize(rows)
         if s.limiter is not None:
             engine.limit(rows, s.limiter[0], lookahead, s.limiter[2], n_samples=held)
         if deliver and s.output is not None:
@@ -370,7 +396,7 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     ``(waveforms, records, verdicts)``.  With an ``output`` the waveforms are that format's codes at its rate, made of the call's
     device rows (``deliver_rows``; the dither's seed is ``seed``).  With ``marks`` the result gains, as its last element, a list of
     timing marks per row -- of the processed characters of the ids, with offsets into that string (``mark_texts``: of raw texts)."""
-    s = SynthSettings(model, **settings)
+    s = SynthSettings.of(model, **settings)
     c = call_constants(model, n_steps, n_iter)
     eng, B = model.engine, len(sentences)
     out = eng.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), *c.synth, init_phase=init_phase, seed=seed,
@@ -413,7 +439,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     characters of the ids -- or, with ``mark_texts``, an iterator that gives per batch what ``synthesize_batch`` takes by that name,
     of raw texts); the 4 T_sent + 36 bytes per utterance come down with the waveforms."""
     # (a generator: a bad setting is refused at its first item, before the engine is touched)
-    s = SynthSettings(model, **settings)
+    s = SynthSettings.of(model, **settings)
     c = call_constants(model, n_steps, n_iter)
     eng = model.engine
     served = [0]   # utterances answered so far: what a clipped row is logged by
@@ -539,7 +565,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     gains, as its last element, the timing marks of every sentence with offsets into the RAW sentence, also written as
     ``{i+1}.marks.jsonl`` beside every wav (``marks.write_marks``); a sentence the front end cannot be mapped back to raises
     ValueError (``marks.token_spans``)."""
-    s = SynthSettings(model_params, **settings)   # (ValueError before anything is loaded)
+    s = SynthSettings.of(model_params, **settings)   # (ValueError before anything is loaded)
     out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
     mark_texts = [(raw,) + marks_.token_spans(dataset, raw) for raw in raw_sentences] if s.marks else None
     id_sequences, sequence_lengths = dataset.process_sentences(raw_sentences)
@@ -572,7 +598,7 @@ def envelope_mode(markup_pitch, pitch_mode, timbre):
 def marked_settings(hp, settings, envelope=False):
     """the record of ``synthesize_marked``, for itself and for its file form: no pitch, unless the pitch is made on the envelope's
     side (``envelope``), where a global pitch adds to every token's"""
-    s = SynthSettings(hp, **settings)
+    s = SynthSettings.of(hp, **settings)
     if s.octaves != 0.0 and not envelope:
         raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global), got {!r}'.format(
             settings.get('pitch') if settings.get('pitch_semitones') is None else settings['pitch_semitones']))
@@ -850,7 +876,7 @@ def join_list_of_call(piece_text, piece_break, n_frames, first_active, hop, paus
 def text_plan(caller, hp, pauses_ms, fade_ms, settings):
     """What ``synthesize_text`` checks ahead of everything else, for itself and for its file form: ``(record, pauses, fade)`` --
     the ``settings`` with ``stop_at_silence_db`` at -40 dB unless given, which cannot be None; ``pause_samples``; ``fade_samples``."""
-    s = SynthSettings(hp, **dict({'stop_at_silence_db': STOP_AT_SILENCE_DB}, **settings))
+    s = SynthSettings.of(hp, **dict({'stop_at_silence_db': STOP_AT_SILENCE_DB}, **settings))
     if s.stop is None:
         raise ValueError('{}: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)'.format(caller))
     rate = getattr(hp, 'hparams', hp).sampling_rate
@@ -877,7 +903,8 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     PAUSES_MS: paragraph 700, sentence 350, clause 120, word and cut 0 ms -- untuned), every piece fades over ``fade_ms`` at
     either edge, and one ``Engine.join`` per call lays the pieces of each text into one row on the device.  With a ``loudness``
     one ``Engine.loudness_normalize`` runs over the joined rows, so a text is levelled as a whole and its sentences keep their
-    relative levels; with a ``limiter`` one ``Engine.limit`` runs over the joined rows behind it.  Only the n_out[g] samples of a row that were said are downloaded.
+    relative levels; with a ``limiter`` one ``Engine.limit`` runs over the joined rows behind it, and with an ``equalizer`` one
+    ``Engine.equalize`` ahead of both.  Only the n_out[g] samples of a row that were said are downloaded.
 
     A text whose pieces span several calls is concatenated on the host, with the pause behind the earlier part as zeros between
     them; with a ``loudness`` each part is levelled on its own.  The packing decides which pieces share a call, a call's seed
@@ -912,7 +939,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     for k, (p0, ids) in enumerate(calls):
         B = ids.shape[0]
         out = eng.synthesize(ids, *c.synth, seed=seed + k, peak_normalize=False, want_linear=True,
-                             **dict(s.engine_keywords(), loudness=None, limiter=None))   # (both run on the joined rows)
+                             **dict(s.engine_keywords(), loudness=None, limiter=None, equalizer=None))   # (all three run on the joined rows)
         first_active = eng.speech_interval(out['linear'], threshold)[0].to_host()
         if s.check_alignment:
             records.append(eng.synth_alignment_stats(B))
@@ -1016,6 +1043,7 @@ def main(argv=None):
                                                             [--rate R] [--pitch SEMITONES]
                                                             [--phase-init random|estimate]
                                                             [--loudness LUFS [--max-peak P]]
+                                                            [--eq PROFILE|kind:f0[:q][:gain_db],...]
                                                             [--limit DB [--limit-lookahead-ms MS] [--sample-peak]]
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
@@ -1032,6 +1060,11 @@ def main(argv=None):
     ``--phase-init estimate``: Griffin-Lim starts from phases estimated from the magnitudes instead of random ones.
     ``--loudness LUFS``: every wav is taken to that integrated loudness (ITU-R BS.1770-4; -23: EBU R 128, -16: a common
     streaming level) with no sample beyond ``--max-peak`` (default 1), instead of being peak-normalised.
+    ``--eq``: an equaliser shapes the spectrum of every wav ahead of the loudness gain and the limiter: a profile -- ``telephony``
+    (300 .. 3400 Hz, 4th-order Butterworth edges: what ``--format mulaw --out-rate 8000`` wants in front of it), ``small-speaker``,
+    ``rumble``, ``bright``, ``warm``; every preset is untuned -- or up to 8 sections ``kind:f0[:q][:gain_db]`` separated by commas,
+    kinds lowpass, highpass, peak, lowshelf, highshelf, e.g. ``--eq highpass:120,peak:3000:1.0:+3,highshelf:6000:+2``.  A boost can
+    take samples beyond 1: give it ``--limit`` or ``--loudness``.
     ``--limit DB``: a look-ahead peak limiter runs last over every wav: no peak above DB decibels relative to full scale (e.g.
     -1), looking ``--limit-lookahead-ms`` ahead (default 5); the ceiling holds for the interpolated (true) peaks, with
     ``--sample-peak`` for the samples alone.  The files are then not peak-normalised.  With ``--loudness`` and no ``--max-peak``
@@ -1061,7 +1094,7 @@ def main(argv=None):
     word, and ``--timbre ST`` moves the formants of every frame by ST semitones.  The default, ``resample``, is the above."""
     args = parse_args(argv)
     settings = settings_option(args)
-    SynthSettings(model_params, **settings)
+    SynthSettings.of(model_params, **settings)
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     out_dir = target_dir(args.synthesis_dir)
     path = args.synthesis_file or inference_params.synthesis_file
@@ -1099,7 +1132,29 @@ def settings_option(args):
                 speaking_rate=args.rate, pitch_semitones=args.pitch, phase_init=args.phase_init,
                 loudness=None if args.loudness is None else (args.loudness, args.max_peak), check_alignment=args.check_alignment,
                 limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
-                output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump)
+                output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump, equalizer=eq_option(args.eq))
+
+
+def eq_option(text):
+    """``--eq`` as the ``equalizer`` of the helpers above: None, a profile name, or ``kind:f0[:q][:gain_db]`` sections separated by
+    commas -- a low-pass or high-pass takes ``kind:f0[:q]``, a peak or shelf with three fields ``kind:f0:gain_db`` (Q 0.7071...)
+    and with four ``kind:f0:q:gain_db``.  ValueError names the field."""
+    if text is None or ':' not in text:
+        return text
+    sections = []
+    for part in text.split(','):
+        kind, *fields = part.strip().split(':')
+        try:
+            numbers = [float(v) for v in fields]
+        except ValueError:
+            raise ValueError('--eq: {!r}: the fields behind the kind must be numbers'.format(part))
+        gained = kind in ('peak', 'lowshelf', 'highshelf')
+        if not 1 <= len(numbers) <= (3 if gained else 2):
+            raise ValueError('--eq: {!r}: kind:f0[:q]{} is needed'.format(part, '[:gain_db]' if gained else ''))
+        if gained and len(numbers) == 2:
+            numbers = [numbers[0], None, numbers[1]]
+        sections.append((kind,) + tuple(numbers))
+    return sections
 
 
 def output_option(args):
@@ -1136,6 +1191,9 @@ def parse_args(argv=None):
     ap.add_argument('--max-peak', type=float, default=argparse.SUPPRESS, metavar='P',
                     help='with --loudness: the largest |sample| the gain may produce (default {:g}; with --limit {:g})'.format(
                         LOUDNESS_MAX_PEAK, LIMITED_MAX_PEAK))
+    ap.add_argument('--eq', default=None, metavar='PROFILE|SECTIONS',
+                    help='an equaliser ahead of the loudness gain and the limiter: a profile (telephony, small-speaker, rumble, bright, warm; '
+                         'untuned) or sections kind:f0[:q][:gain_db], e.g. highpass:120,peak:3000:1.0:+3,highshelf:6000:+2')
     ap.add_argument('--limit', type=float, default=None, metavar='DB',
                     help='a look-ahead peak limiter behind everything else: no peak above DB decibels re full scale, e.g. -1')
     ap.add_argument('--limit-lookahead-ms', type=float, default=LIMIT_LOOKAHEAD_MS, metavar='MS',

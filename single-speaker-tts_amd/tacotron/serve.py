@@ -34,7 +34,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, **
     (``init_phase`` has that many frames; lengths min(T', max(min_frames, ceil(n / rate)))) and ``Engine.resample`` by 2 ** -pitch
     behind it; with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
     last, over the same samples."""
-    s = SynthSettings(model_params, **settings)
+    s = SynthSettings.of(model_params, **settings)
     stop, rate, octaves = s.stop, s.rate, s.octaves
     finish = finishing_tail('post_process_spectrograms', s, model_params.sampling_rate)
     rho = float(np.exp2(-np.float64(octaves)))
@@ -94,7 +94,7 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     every answer gains, as its last element, the timing marks of every sentence (``tacotron.marks``; offsets into the raw
     sentence, samples of what is delivered): subtitles and barge-in positions in the same round trip as the waveforms."""
     # (a generator: a bad setting is refused at its first item, before a model is made)
-    s = SynthSettings(model_params, **settings)
+    s = SynthSettings.of(model_params, **settings)
     dataset, model = open_model(weights, dataset, device_id)
     if not pipelined:   # the reference's loop as it stands: one batch at a time, spectrograms through host memory
         for k, sentences in enumerate(sentence_generator):

@@ -1014,8 +1014,67 @@ def stretch_frame_counts(n_frames, B, T):
     return _checked_lengths(nf, T, 'n_frames', 'T')
 
 
-WARP_MAX_SEGMENTS = 4096                       # tts_warp_max_segments()
-WARP_SEGMENTS_PER_LAUNCH = 64                  # segments whose entries travel with one launch
+MAX_SEGMENTS = 4096                            # segments of a call of a segment-wise stage (csrc/segments.h)
+SEGMENTS_PER_LAUNCH = 64                       # ... whose entries travel with one launch
+
+
+def segment_launches(S):
+    """launches of a segment-wise stage (the warp, the shift, the segment-wise resampler) on S segments"""
+    return -(-int(S) // SEGMENTS_PER_LAUNCH)
+
+
+def _segment_records(what, segments, dtype, name):
+    """``segments`` -- an array of the record ``dtype`` (called ``name``), or rows of its fields without the ``reserved`` ones, which
+    are 0 -- as a contiguous array (S,) of ``dtype``.  ValueError for anything that is not such a list or does not fit the record's
+    fields: an int32 field takes a signed, a uint32 field an unsigned 32-bit integer, a float field a number."""
+    if isinstance(segments, np.ndarray) and segments.dtype == dtype and segments.ndim == 1:
+        return np.ascontiguousarray(segments)
+    fields = [(f, dtype[f]) for f in dtype.names if f != 'reserved']
+    ints = [f for f, t in fields if t.kind in 'iu']
+    try:
+        rows = [tuple(r) for r in segments]
+    except TypeError:
+        rows = None
+    if rows is None or any(len(r) != len(fields) for r in rows):
+        raise ValueError('{}: segments must be a {} array or rows ({})'.format(what, name, ', '.join(f for f, _t in fields)))
+    out = np.zeros(len(rows), dtype=dtype)
+    for s, r in enumerate(rows):
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not np.iinfo(t).min <= v <= np.iinfo(t).max
+               for v, (_f, t) in zip(r, fields) if t.kind in 'iu'):
+            raise ValueError('{}: segment {} must hold 32-bit integers {} and {}, got {!r}'.format(what, s, ', '.join(ints[:-1]), ints[-1], r))
+        for v, (f, t) in zip(r, fields):
+            if t.kind in 'iu':
+                out[f][s] = int(v)
+                continue
+            try:
+                out[f][s] = float(v)
+            except (TypeError, ValueError):
+                raise ValueError('{}: segment {} needs a number as its {}, got {!r}'.format(what, s, f, v))
+    return out
+
+
+def _segment_counts_check(what, S, B, max_name):
+    """the counts of a segment list as every plan checks them (``max_name``: the stage's tts_*_max...() of the public header)"""
+    if S > MAX_SEGMENTS:
+        raise ValueError('{}: {} segments are more than {} = {}'.format(what, S, max_name, MAX_SEGMENTS))
+    if B > S:
+        raise ValueError('{}: {} rows of {} segments: no row is without a segment'.format(what, B, S))
+
+
+def _segment_rows_check(what, rows, B):
+    """the order of a segment list's rows as every plan checks it: from 0 to B - 1, never decreasing, none skipped"""
+    if rows[0] != 0:
+        raise ValueError('{}: row of segment 0 is {}: the rows start at 0'.format(what, rows[0]))
+    for s in range(1, len(rows)):
+        if rows[s] - rows[s - 1] not in (0, 1):
+            raise ValueError('{}: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a segment'.format(
+                what, s, rows[s], rows[s - 1]))
+    if rows[-1] != B - 1:
+        raise ValueError('{}: row of segment {} is {}: the last row is B - 1 = {}'.format(what, len(rows) - 1, rows[-1], B - 1))
+
+
+WARP_MAX_SEGMENTS = MAX_SEGMENTS               # tts_warp_max_segments()
+WARP_SEGMENTS_PER_LAUNCH = SEGMENTS_PER_LAUNCH
 WARP_STEP_MIN, WARP_STEP_MAX = 16384, 262144   # the rates 0.25 .. 4 times 65536
 WARP_GAIN_MAX = 16.0
 WARP_MAX_T_OUT = 1 << 30
@@ -1026,34 +1085,13 @@ def warp_count(frames, step):
     return -((-int(frames) << 16) // int(step))
 
 
-def warp_launches(S):
-    """launches of a warp of S segments"""
-    return -(-int(S) // WARP_SEGMENTS_PER_LAUNCH)
+warp_launches = segment_launches
 
 
 def warp_segments(segments):
     """``segments`` -- a WARP_SEGMENT array, or rows ``(row, first, frames, pause, step, gain)`` -- as a contiguous WARP_SEGMENT
     array (S,).  ValueError for anything that is not such a list or does not fit the record's fields."""
-    if isinstance(segments, np.ndarray) and segments.dtype == WARP_SEGMENT and segments.ndim == 1:
-        return np.ascontiguousarray(segments)
-    try:
-        rows = [tuple(r) for r in segments]
-    except TypeError:
-        rows = None
-    if rows is None or any(len(r) != 6 for r in rows):
-        raise ValueError('warp: segments must be a WARP_SEGMENT array or rows (row, first, frames, pause, step, gain)')
-    out = np.zeros(len(rows), dtype=WARP_SEGMENT)
-    for s, r in enumerate(rows):
-        ints, gain = r[:5], r[5]
-        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in ints) or \
-                any(not -2 ** 31 <= v < 2 ** 31 for v in ints[:4]) or not 0 <= ints[4] < 2 ** 32:
-            raise ValueError('warp: segment {} must hold 32-bit integers row, first, frames, pause and step, got {!r}'.format(s, r))
-        try:
-            gain = float(gain)
-        except (TypeError, ValueError):
-            raise ValueError('warp: segment {} needs a number as its gain, got {!r}'.format(s, r[5]))
-        out[s] = tuple(int(v) for v in ints) + (gain,)
-    return out
+    return _segment_records('warp', segments, WARP_SEGMENT, 'WARP_SEGMENT')
 
 
 def warp_list(segments, B, T, n_frames=None):
@@ -1065,20 +1103,9 @@ def warp_list(segments, B, T, n_frames=None):
     S = int(q.shape[0])
     if B < 1 or T < 1 or S < 1:
         raise ValueError('warp: need B, T, S >= 1')
-    if S > WARP_MAX_SEGMENTS:
-        raise ValueError('warp: {} segments are more than tts_warp_max_segments() = {}'.format(S, WARP_MAX_SEGMENTS))
-    if B > S:
-        raise ValueError('warp: {} rows of {} segments: no row is without a segment'.format(B, S))
+    _segment_counts_check('warp', S, B, 'tts_warp_max_segments()')
     nf = stretch_frame_counts(n_frames, B, T)
-    rows = q['row'].tolist()
-    if rows[0] != 0:
-        raise ValueError('warp: row of segment 0 is {}: the rows start at 0'.format(rows[0]))
-    for s in range(1, S):
-        if rows[s] - rows[s - 1] not in (0, 1):
-            raise ValueError('warp: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a segment'.format(
-                s, rows[s], rows[s - 1]))
-    if rows[-1] != B - 1:
-        raise ValueError('warp: row of segment {} is {}: the last row is B - 1 = {}'.format(S - 1, rows[-1], B - 1))
+    _segment_rows_check('warp', q['row'].tolist(), B)
     n_out = np.zeros(B, dtype=np.int64)
     count = np.zeros(S, dtype=np.int64)
     for s, (row, first, frames, pause, step, gain) in enumerate(q.tolist()):
@@ -1103,8 +1130,8 @@ def warp_list(segments, B, T, n_frames=None):
     return q, nf, n_out, count
 
 
-SHIFT_MAX_SEGMENTS = 4096                       # tts_shift_max_segments()
-SHIFT_SEGMENTS_PER_LAUNCH = 64                  # segments whose entries travel with one launch
+SHIFT_MAX_SEGMENTS = MAX_SEGMENTS               # tts_shift_max_segments()
+SHIFT_SEGMENTS_PER_LAUNCH = SEGMENTS_PER_LAUNCH
 SHIFT_TILE = 8                                  # tts_shift_tile()
 SHIFT_MAX_ORDER = 256                           # tts_shift_max_order()
 SHIFT_N_MIN, SHIFT_N_MAX = 128, 2048            # F = N + 1 with N a power of two in this range
@@ -1130,10 +1157,7 @@ def shift_order(sampling_rate):
     return max(8, int(0.0015 * float(sampling_rate)))
 
 
-def shift_launches(S):
-    """launches of a shift of S segments"""
-    return -(-int(S) // SHIFT_SEGMENTS_PER_LAUNCH)
-
+shift_launches = segment_launches
 
 def shift_bins_n(F):
     """N of F = N + 1 bins where N is a power of two in 128 .. 2048, else 0"""
@@ -1144,21 +1168,7 @@ def shift_bins_n(F):
 def shift_segments(segments):
     """``segments`` -- a SHIFT_SEGMENT array, or rows ``(row, first, frames, pitch_step, formant_step)`` -- as a contiguous
     SHIFT_SEGMENT array (S,).  ValueError for anything that is not such a list or does not fit the record's fields."""
-    if isinstance(segments, np.ndarray) and segments.dtype == SHIFT_SEGMENT and segments.ndim == 1:
-        return np.ascontiguousarray(segments)
-    try:
-        rows = [tuple(r) for r in segments]
-    except TypeError:
-        rows = None
-    if rows is None or any(len(r) != 5 for r in rows):
-        raise ValueError('shift: segments must be a SHIFT_SEGMENT array or rows (row, first, frames, pitch_step, formant_step)')
-    out = np.zeros(len(rows), dtype=SHIFT_SEGMENT)
-    for s, r in enumerate(rows):
-        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in r) or \
-                any(not -2 ** 31 <= v < 2 ** 31 for v in r[:3]) or any(not 0 <= v < 2 ** 32 for v in r[3:]):
-            raise ValueError('shift: segment {} must hold 32-bit integers row, first, frames, pitch_step and formant_step, got {!r}'.format(s, r))
-        out[s] = tuple(int(v) for v in r[:3]) + (0,) + tuple(int(v) for v in r[3:])
-    return out
+    return _segment_records('shift', segments, SHIFT_SEGMENT, 'SHIFT_SEGMENT')
 
 
 def shift_list(segments, B, F, T, n_frames=None, order=33):
@@ -1175,20 +1185,9 @@ def shift_list(segments, B, F, T, n_frames=None, order=33):
     order_max = min(SHIFT_MAX_ORDER, N // 2)
     if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or not 2 <= order <= order_max:
         raise ValueError('shift: order = {} is not in 2 .. {}'.format(order, order_max))
-    if S > SHIFT_MAX_SEGMENTS:
-        raise ValueError('shift: {} segments are more than tts_shift_max_segments() = {}'.format(S, SHIFT_MAX_SEGMENTS))
-    if B > S:
-        raise ValueError('shift: {} rows of {} segments: no row is without a segment'.format(B, S))
+    _segment_counts_check('shift', S, B, 'tts_shift_max_segments()')
     nf = stretch_frame_counts(n_frames, B, T)
-    rows = q['row'].tolist()
-    if rows[0] != 0:
-        raise ValueError('shift: row of segment 0 is {}: the rows start at 0'.format(rows[0]))
-    for s in range(1, S):
-        if rows[s] - rows[s - 1] not in (0, 1):
-            raise ValueError('shift: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a segment'.format(
-                s, rows[s], rows[s - 1]))
-    if rows[-1] != B - 1:
-        raise ValueError('shift: row of segment {} is {}: the last row is B - 1 = {}'.format(S - 1, rows[-1], B - 1))
+    _segment_rows_check('shift', q['row'].tolist(), B)
     prev_end, prev_row = 0, 0
     for s, (row, first, frames, reserved, pitch_step, formant_step) in enumerate(q.tolist()):
         if row != prev_row:
@@ -1242,8 +1241,8 @@ def resampled_length(n, ratio):
     return int(np.ceil(np.float64(int(n)) * np.float64(r)))
 
 
-RESAMPLE_SEGMENTS_MAX = 4096                   # tts_resample_segments_max()
-RESAMPLE_SEGMENTS_PER_LAUNCH = 64              # segments whose entries travel with one launch
+RESAMPLE_SEGMENTS_MAX = MAX_SEGMENTS           # tts_resample_segments_max()
+RESAMPLE_SEGMENTS_PER_LAUNCH = SEGMENTS_PER_LAUNCH
 RESAMPLE_SEGMENTS_MAX_RATIOS = 16              # tts_resample_segments_max_ratios(): distinct ratios below 1 per call
 RESAMPLE_SEGMENTS_MAX_N_OUT = 1 << 30
 
@@ -1256,25 +1255,7 @@ def resample_segment_count(samples, ratio):
 def resample_segment_records(segments):
     """``segments`` -- a RESAMPLE_SEGMENT array, or rows ``(row, first, samples, ratio)`` -- as a contiguous RESAMPLE_SEGMENT
     array (S,).  ValueError for anything that is not such a list or does not fit the record's fields."""
-    if isinstance(segments, np.ndarray) and segments.dtype == RESAMPLE_SEGMENT and segments.ndim == 1:
-        return np.ascontiguousarray(segments)
-    try:
-        rows = [tuple(r) for r in segments]
-    except TypeError:
-        rows = None
-    if rows is None or any(len(r) != 4 for r in rows):
-        raise ValueError('resample_segments: segments must be a RESAMPLE_SEGMENT array or rows (row, first, samples, ratio)')
-    out = np.zeros(len(rows), dtype=RESAMPLE_SEGMENT)
-    for s, r in enumerate(rows):
-        ints, ratio = r[:3], r[3]
-        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not -2 ** 31 <= v < 2 ** 31 for v in ints):
-            raise ValueError('resample_segments: segment {} must hold 32-bit integers row, first and samples, got {!r}'.format(s, r))
-        try:
-            ratio = float(ratio)
-        except (TypeError, ValueError):
-            raise ValueError('resample_segments: segment {} needs a number as its ratio, got {!r}'.format(s, r[3]))
-        out[s] = tuple(int(v) for v in ints) + (0, ratio)
-    return out
+    return _segment_records('resample_segments', segments, RESAMPLE_SEGMENT, 'RESAMPLE_SEGMENT')
 
 
 def resample_segment_list(segments, B, n, n_samples=None):
@@ -1286,25 +1267,14 @@ def resample_segment_list(segments, B, n, n_samples=None):
     S = int(q.shape[0])
     if B < 1 or n < 1 or S < 1:
         raise ValueError('resample_segments: need B, n, S >= 1')
-    if S > RESAMPLE_SEGMENTS_MAX:
-        raise ValueError('resample_segments: {} segments are more than tts_resample_segments_max() = {}'.format(S, RESAMPLE_SEGMENTS_MAX))
-    if B > S:
-        raise ValueError('resample_segments: {} rows of {} segments: no row is without a segment'.format(B, S))
+    _segment_counts_check('resample_segments', S, B, 'tts_resample_segments_max()')
     ns = None
     if n_samples is not None:
         ns = np.asarray(n_samples)
         if ns.shape != (B,) or ns.dtype.kind not in 'iu':
             raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
         ns = _checked_lengths(ns, n, 'n_samples', 'n')
-    rows = q['row'].tolist()
-    if rows[0] != 0:
-        raise ValueError('resample_segments: row of segment 0 is {}: the rows start at 0'.format(rows[0]))
-    for s in range(1, S):
-        if rows[s] - rows[s - 1] not in (0, 1):
-            raise ValueError('resample_segments: row of segment {} is {} and follows {}: the rows are non-decreasing and none is without a '
-                             'segment'.format(s, rows[s], rows[s - 1]))
-    if rows[-1] != B - 1:
-        raise ValueError('resample_segments: row of segment {} is {}: the last row is B - 1 = {}'.format(S - 1, rows[-1], B - 1))
+    _segment_rows_check('resample_segments', q['row'].tolist(), B)
     n_out = np.zeros(B, dtype=np.int64)
     count = np.zeros(S, dtype=np.int64)
     below, extra_at = set(), None
@@ -1585,6 +1555,11 @@ class Engine(object):
             if rc == TTS_ERR_DB_RANGE:
                 raise AssertionError(msg)   # reference audio/conversion.py:47-49
             raise TtsError(rc, msg)
+
+    def _host_plan_check(self, rc):
+        """``_check`` for a tts_*_plan call, which takes no handle: the text is tts_last_error(NULL)'s"""
+        if rc != TTS_OK:
+            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
 
     def _check_or_free(self, rc, *outputs):
         """``_check`` for a call that enqueues nothing where it refuses: its fresh ``outputs`` (None among them) go back at once"""
@@ -2020,8 +1995,7 @@ class Engine(object):
         q, g, G, n_out = join_list(pieces, groups, B, N, fade)
         out = np.zeros(G, dtype=np.int64)
         rc = self.lib.tts_join_plan(q.ctypes.data, q.shape[0], _int32_ptr(g), G, B, N, int(fade), out.ctypes.data_as(POINTER(c_int64)))
-        if rc != TTS_OK:
-            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        self._host_plan_check(rc)
         assert (out == n_out).all(), (out, n_out)
         return out
 
@@ -2544,8 +2518,7 @@ class Engine(object):
         q, nf, n_out, _count = warp_list(segments, B, T, n_frames)
         out = np.zeros(B, dtype=np.int64)
         rc = self.lib.tts_warp_plan(q.ctypes.data, q.shape[0], B, T, _int32_ptr(nf), out.ctypes.data_as(POINTER(c_int64)))
-        if rc != TTS_OK:
-            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        self._host_plan_check(rc)
         assert (out == n_out).all(), (out, n_out)
         return out
 
@@ -2599,8 +2572,7 @@ class Engine(object):
         order = shift_order(self.sampling_rate) if order is None else order
         q, nf = shift_list(segments, B, F, T, n_frames, order)
         rc = self.lib.tts_shift_plan(q.ctypes.data, q.shape[0], B, F, T, _int32_ptr(nf), int(order))
-        if rc != TTS_OK:
-            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        self._host_plan_check(rc)
         return shift_launches(q.shape[0])
 
     def shift_magnitudes(self, mag, segments, n_frames=None, order=None, out=None):
@@ -2714,8 +2686,7 @@ class Engine(object):
         q, ns, n_out, _count = resample_segment_list(segments, B, n, n_samples)
         out = np.zeros(B, dtype=np.int64)
         rc = self.lib.tts_resample_segments_plan(q.ctypes.data, q.shape[0], B, n, _int32_ptr(ns), out.ctypes.data_as(POINTER(c_int64)))
-        if rc != TTS_OK:
-            raise TtsError(rc, (self.lib.tts_last_error(None) or b'').decode())
+        self._host_plan_check(rc)
         assert (out == n_out).all(), (out, n_out)
         return out
 

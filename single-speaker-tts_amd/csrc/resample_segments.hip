@@ -10,12 +10,11 @@
 // by operation (no contraction: the file is built with -ffp-contract=off); the weights and the sum use explicit FMAs.
 //
 // warp.hip's scheme: the list travels by value, RSEG_SEGMENTS segments per launch; a workgroup takes one tile of RSEG_TILE
-// consecutive output samples of one segment -- blockIdx.x is the tile in the launch's numbering, and the segment is the last entry
-// whose first tile is not behind it (workgroup-uniform, six scalar steps).  resample_kernel<1>'s tile: the samples the windows of
-// the tile's outputs cover are staged in LDS, zero-filled outside the row, and one thread per output walks its two wings over its
-// ratio's phase-major table (resample_plan.h), read out of L2.  Every row carries its own ratios, so a weight serves one sample,
-// not the RS_U = 8 of the batched resampler.  No atomics; a row's output does not depend on the batch it is in nor on where its
-// segments fall among the launches.
+// consecutive output samples of one segment -- blockIdx.x is the tile in the launch's numbering (segment_find).  resample_kernel<1>'s
+// tile: the samples the windows of the tile's outputs cover are staged in LDS, zero-filled outside the row, and one thread per
+// output walks its two wings over its ratio's phase-major table (resample_plan.h), read out of L2.  Every row carries its own
+// ratios, so a weight serves one sample, not the RS_U = 8 of the batched resampler.  No atomics; a row's output does not depend on
+// the batch it is in nor on where its segments fall among the launches.
 #include "api_internal.h"
 #include "resample_segments_plan.h"
 
@@ -44,13 +43,7 @@ __global__ __launch_bounds__(RSEG_TILE) void resample_segments_kernel(const floa
                                                                       const RsegTables tabs, int n_seg, int n, int N_out, int lds_floats) {
     extern __shared__ __align__(16) float rseg_xs[];
     const int tile = blockIdx.x;
-    int lo_e = 0, hi_e = n_seg - 1;
-    while (lo_e < hi_e) {
-        const int mid = (lo_e + hi_e + 1) >> 1;
-        if (c.e[mid].tile0 <= tile) lo_e = mid;
-        else hi_e = mid - 1;
-    }
-    const RsegEntry E = c.e[lo_e];
+    const RsegEntry E = c.e[segment_find(c.e, n_seg, tile)];
     const int j0 = (tile - E.tile0) * RSEG_TILE;
     const int j = j0 + (int)threadIdx.x;
     const float* src = x + (size_t)E.row * n;
@@ -136,21 +129,18 @@ static int rseg_tables(tts_handle_t h, const std::vector<double>& below, bool ab
 
 // On h->stream; everything has been checked.  e, tiles, lds: resample_segments_entries' S entries and every launch's tiles and LDS.
 static int resample_segments_impl(tts_handle_t h, const float* wav, int n, const std::vector<RsegEntry>& e, const std::vector<int64_t>& tiles,
-                                  const std::vector<int>& lds, const RsegTables& tabs, int S, int N_out, float* out) {
+                                  const std::vector<int>& lds, const RsegTables& tabs, int N_out, float* out) {
     int launches = 0;
     for (int64_t t : tiles) launches += t > 0;
     ProfScope ps(h, ST_RESAMPLE, launches);
-    for (int s0 = 0, l = 0; s0 < S; s0 += RSEG_SEGMENTS, ++l) {
-        if (tiles[(size_t)l] == 0) continue;   // (segments that own nothing)
-        const int ns = std::min(RSEG_SEGMENTS, S - s0);
-        RsegChunk c;
-        for (int q = 0; q < RSEG_SEGMENTS; ++q) c.e[q] = q < ns ? e[(size_t)s0 + q] : RsegEntry{0, 0, 0, 0, 0, 0, 0, -1, 1.0, 1.0};
+    return for_each_segment_launch(e, RSEG_NO_ENTRY, [&](const RsegChunk& c, int ns, int l) -> int {
+        if (tiles[(size_t)l] == 0) return TTS_OK;   // (segments that own nothing)
         const int floats = lds[(size_t)l];
         hipLaunchKernelGGL(resample_segments_kernel, dim3((unsigned)tiles[(size_t)l]), dim3(RSEG_TILE), (size_t)floats * sizeof(float), h->stream, wav,
                            out, c, tabs, ns, n, N_out, floats);
         HIPCHK(h, hipGetLastError());
-    }
-    return TTS_OK;
+        return TTS_OK;
+    });
 }
 
 }  // namespace tts_api
@@ -193,7 +183,7 @@ int tts_resample_segments(tts_handle_t h, const float* wav, int B, int n, const 
     resample_segments_entries(segments, S, n, n_samples, N_out, count.data(), below, e, tiles, lds);
     if (n_out)
         for (int b = 0; b < B; ++b) n_out[b] = (int32_t)rows[(size_t)b];
-    return resample_segments_impl(h, wav, n, e, tiles, lds, tabs, S, N_out, out);
+    return resample_segments_impl(h, wav, n, e, tiles, lds, tabs, N_out, out);
 }
 
 int tts_resample_segments_max(void) { return RSEG_MAX_SEGMENTS; }

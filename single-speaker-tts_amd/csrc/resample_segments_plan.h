@@ -8,12 +8,11 @@
 // other resampled_valid(samples, ratio) = (long long)(samples * ratio), resampy's; a segment may produce no sample.
 //
 // The cut: every output sample of a row is OWNED by exactly one segment -- segment s owns [o[s], o[s+1]), a row's last segment
-// [o[s], N_out): its own samples and behind them the zeros of the row's rest.  A launch takes RSEG_SEGMENTS consecutive segments,
-// a workgroup RSEG_TILE consecutive samples of what one segment owns; the tiles of a launch are numbered segment after segment (a
-// segment that owns nothing has none), and a workgroup finds its segment in the launch's table of first tiles.  The launches of a
-// call write disjoint ranges that cover out[B][N_out]: every element once.
+// [o[s], N_out): its own samples and behind them the zeros of the row's rest.  A workgroup takes RSEG_TILE consecutive samples of
+// what one segment owns, and a segment that owns nothing has no tile; segments.h has the list's order, the launches and the
+// numbering of their tiles.  The launches of a call write disjoint ranges that cover out[B][N_out]: every element once.
 #pragma once
-#include "lengths.h"
+#include "segments.h"
 #include "resample_plan.h"
 #include <cmath>
 #include <cstddef>
@@ -26,13 +25,12 @@
 
 namespace tts {
 
-constexpr int RSEG_SEGMENTS = 64;          // segments per launch: their entries travel by value
-constexpr int RSEG_MAX_SEGMENTS = 4096;    // segments per call (64 launches)
+constexpr int RSEG_SEGMENTS = SEGMENTS_PER_LAUNCH, RSEG_MAX_SEGMENTS = MAX_SEGMENTS;
 constexpr int RSEG_MAX_RATIOS = 16;        // distinct ratios below 1 per call: each has a table of its own (0.5 MiB)
 constexpr int RSEG_TILE = 256;             // output samples of a workgroup, one per thread (resample.hip's RS_TILE)
 constexpr int RSEG_MAX_N_OUT = 1 << 30;
 
-constexpr int rseg_launches(int S) { return (S + RSEG_SEGMENTS - 1) / RSEG_SEGMENTS; }
+constexpr int rseg_launches(int S) { return segment_launches(S); }
 constexpr int64_t rseg_tiles(int64_t span) { return (span + RSEG_TILE - 1) / RSEG_TILE; }
 
 inline bool rseg_is_copy(double ratio) { return ratio == 1.0; }
@@ -45,9 +43,8 @@ struct RsegEntry {
     int32_t row, first, o, count, span, n, tile0, tab;
     double inc, scale;
 };
-struct RsegChunk {
-    RsegEntry e[RSEG_SEGMENTS];
-};
+using RsegChunk = SegmentChunk<RsegEntry>;
+constexpr RsegEntry RSEG_NO_ENTRY{0, 0, 0, 0, 0, 0, 0, -1, 1.0, 1.0};   // a copy of nothing: what pads a launch's chunk
 
 // The checks of tts_resample_segments_plan and tts_resample_segments on the list, in the order the header lists them, and the
 // lengths.  An empty string: the list is legal (TTS_ERR_INVALID otherwise).  n_out [B], and count [S] where it is given, are filled.
@@ -55,18 +52,8 @@ inline std::string resample_segments_plan(const tts_resample_segment_t* seg, int
                                           int64_t* count = nullptr) {
     if (!seg || !n_out) return "a NULL pointer (segments and n_out are required)";
     if (B < 1 || n < 1 || S < 1) return "need B, n, S >= 1";
-    if (S > RSEG_MAX_SEGMENTS)
-        return std::to_string(S) + " segments are more than tts_resample_segments_max() = " + std::to_string(RSEG_MAX_SEGMENTS);
-    if (B > S) return std::to_string(B) + " rows of " + std::to_string(S) + " segments: no row is without a segment";
-    const std::string bad = lengths_refusal("n_samples", n_samples, B, "n", n);
+    const std::string bad = segment_rows_refusal(seg, S, B, "tts_resample_segments_max()", "n_samples", n_samples, "n", n);
     if (!bad.empty()) return bad;
-    if (seg[0].row != 0) return "row of segment 0 is " + std::to_string(seg[0].row) + ": the rows start at 0";
-    for (int s = 1; s < S; ++s)
-        if (seg[s].row != seg[s - 1].row && seg[s].row != seg[s - 1].row + 1)
-            return "row of segment " + std::to_string(s) + " is " + std::to_string(seg[s].row) + " and follows " + std::to_string(seg[s - 1].row) +
-                   ": the rows are non-decreasing and none is without a segment";
-    if (seg[S - 1].row != B - 1)
-        return "row of segment " + std::to_string(S - 1) + " is " + std::to_string(seg[S - 1].row) + ": the last row is B - 1 = " + std::to_string(B - 1);
     int64_t o = 0;
     uint64_t below[RSEG_MAX_RATIOS];
     int n_below = 0, extra_at = -1;   // extra_at: the segment that brings one ratio too many (the later segments are still checked)
@@ -105,13 +92,7 @@ inline std::string resample_segments_plan(const tts_resample_segment_t* seg, int
 }
 
 // ... and of tts_resample_segments' own arguments behind a legal list
-inline std::string resample_segments_room(const int64_t* n_out, int B, int N_out) {
-    for (int b = 0; b < B; ++b)
-        if (n_out[b] > (int64_t)N_out) return "N_out = " + std::to_string(N_out) + " is below n_out[" + std::to_string(b) + "] = " + std::to_string(n_out[b]);
-    // (a launch's RSEG_SEGMENTS segments then own fewer than 2^31 tiles, which is what a launch takes)
-    if (N_out > RSEG_MAX_N_OUT) return "N_out = " + std::to_string(N_out) + " is above 2^30 = " + std::to_string(RSEG_MAX_N_OUT);
-    return std::string();
-}
+inline std::string resample_segments_room(const int64_t* n_out, int B, int N_out) { return segment_room("N_out", n_out, B, N_out, RSEG_MAX_N_OUT); }
 
 // The distinct ratios below 1 of a legal list, in the order they first appear (at most RSEG_MAX_RATIOS): table k + 1 of the call
 // is below[k]'s.  *above: some segment has a ratio above 1 -- table 0, the one all of them share.
@@ -137,8 +118,8 @@ inline int rseg_span_max(const ResampleConsts& c) { return (int)((double)(RSEG_T
 // of its resampled segments stages (0: copies alone).
 inline void resample_segments_entries(const tts_resample_segment_t* seg, int S, int n, const int32_t* n_samples, int N_out, const int64_t* count,
                                       const std::vector<double>& below, std::vector<RsegEntry>& e, std::vector<int64_t>& tiles, std::vector<int>& lds) {
-    e.assign((size_t)S, RsegEntry{0, 0, 0, 0, 0, 0, 0, -1, 1.0, 1.0});
-    tiles.assign((size_t)rseg_launches(S), 0);
+    e.assign((size_t)S, RSEG_NO_ENTRY);
+    tiles.assign((size_t)segment_launches(S), 0);
     lds.assign((size_t)rseg_launches(S), 0);
     int64_t o = 0;
     for (int s = 0; s < S; ++s) {
@@ -161,9 +142,7 @@ inline void resample_segments_entries(const tts_resample_segment_t* seg, int S, 
             int& most = lds[(size_t)(s / RSEG_SEGMENTS)];
             if (w.count > 0 && rseg_span_max(c) > most) most = rseg_span_max(c);
         }
-        int64_t& t = tiles[(size_t)(s / RSEG_SEGMENTS)];
-        w.tile0 = (int32_t)t;
-        t += rseg_tiles(w.span);
+        w.tile0 = segment_take_tiles(tiles, s, rseg_tiles(w.span));
         o = last ? 0 : o + count[s];
     }
 }

@@ -106,19 +106,12 @@ __device__ __forceinline__ void shift_pass(const float* __restrict__ in, float* 
     __syncthreads();   // (the next pass overwrites xs, LE and bad)
 }
 
-// mag [B][F][T] -> out [B][F][T].  blockIdx.x is the tile in the launch's numbering, and the segment is the last entry whose first
-// tile is not behind it (workgroup-uniform, six scalar steps).
+// mag [B][F][T] -> out [B][F][T].  blockIdx.x is the tile in the launch's numbering (segment_find).
 __global__ __launch_bounds__(SHIFT_THREADS) void shift_kernel(const float* __restrict__ in, float* __restrict__ out, const ShiftChunk c, int n_seg,
                                                               int N, int Q, int T, const double* __restrict__ ct_g, const double* __restrict__ h_g) {
     extern __shared__ __align__(16) double shift_lds[];
     const int tile = blockIdx.x;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) {
-        const int m = (lo + hi + 1) >> 1;
-        if (c.e[m].tile0 <= tile) lo = m;
-        else hi = m - 1;
-    }
-    const ShiftEntry E = c.e[lo];
+    const ShiftEntry E = c.e[segment_find(c.e, n_seg, tile)];
     const ShiftTile w = shift_tile_of(E, tile - E.tile0);
     const int F = N + 1;
     const size_t base = (size_t)E.row * F * T;
@@ -194,21 +187,17 @@ void shift_release(tts_handle_t h) {
 }
 
 // On h->stream; everything has been checked.  e, tiles: shift_entries' S entries and the tiles of every launch.
-static int shift_impl(tts_handle_t h, const float* mag, int N, int T, const std::vector<ShiftEntry>& e, const std::vector<int64_t>& tiles, int S, int Q,
-                      float* out) {
+static int shift_impl(tts_handle_t h, const float* mag, int N, int T, const std::vector<ShiftEntry>& e, const std::vector<int64_t>& tiles, int Q, float* out) {
     const double *ct = nullptr, *lifter = nullptr;
     const int rc = shift_tables(h, N, Q, &ct, &lifter);
     if (rc != TTS_OK) return rc;
-    ProfScope ps(h, ST_SHIFT, shift_launches(S));
+    ProfScope ps(h, ST_SHIFT, (int64_t)tiles.size());
     const size_t lds = shift_lds_bytes(N, Q);
-    for (int s0 = 0, l = 0; s0 < S; s0 += SHIFT_SEGMENTS, ++l) {
-        const int n = std::min(SHIFT_SEGMENTS, S - s0);
-        ShiftChunk c;
-        for (int q = 0; q < SHIFT_SEGMENTS; ++q) c.e[q] = q < n ? e[(size_t)s0 + q] : ShiftEntry{0, 0, 0, 0, 0, 0, 0, SHIFT_UNITY, SHIFT_UNITY};
+    return for_each_segment_launch(e, SHIFT_NO_ENTRY, [&](const ShiftChunk& c, int n, int l) -> int {
         hipLaunchKernelGGL(shift_kernel, dim3((unsigned)tiles[(size_t)l]), dim3(SHIFT_THREADS), lds, h->stream, mag, out, c, n, N, Q, T, ct, lifter);
         HIPCHK(h, hipGetLastError());
-    }
-    return TTS_OK;
+        return TTS_OK;
+    });
 }
 
 }  // namespace tts_api
@@ -233,7 +222,7 @@ int tts_shift_magnitudes(tts_handle_t h, const float* mag, int B, int F, int T, 
     std::vector<ShiftEntry> e;
     std::vector<int64_t> tiles;
     shift_entries(segments, S, T, n_frames, e, tiles);
-    return shift_impl(h, mag, F - 1, T, e, tiles, S, order, out);
+    return shift_impl(h, mag, F - 1, T, e, tiles, order, out);
 }
 
 int tts_shift_max_segments(void) { return SHIFT_MAX_SEGMENTS; }

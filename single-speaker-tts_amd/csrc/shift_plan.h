@@ -9,10 +9,10 @@
 //   body   [first, end)    SHIFT_TILE frames per workgroup where the segment is computed; a segment whose two steps are both
 //                          65536 is a copy and takes SHIFT_COPY_TILE frames per workgroup
 //   rest   [end, own_end)  copies below n_frames[row], +0.0 from there on, SHIFT_COPY_TILE frames per workgroup
-// A launch takes SHIFT_SEGMENTS consecutive segments; its tiles are numbered segment after segment, and a workgroup finds its
-// segment in the launch's table of first tiles.  The launches of a call write disjoint ranges that cover out: every element once.
+// segments.h has the list's order, the launches and the numbering of their tiles.  The launches of a call write disjoint ranges
+// that cover out: every element once.
 #pragma once
-#include "lengths.h"
+#include "segments.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -23,8 +23,7 @@
 
 namespace tts {
 
-constexpr int SHIFT_SEGMENTS = 64;           // segments per launch: their entries travel by value
-constexpr int SHIFT_MAX_SEGMENTS = 4096;     // segments per call (64 launches)
+constexpr int SHIFT_SEGMENTS = SEGMENTS_PER_LAUNCH, SHIFT_MAX_SEGMENTS = MAX_SEGMENTS;
 constexpr int SHIFT_THREADS = 512;
 constexpr int SHIFT_TILE = 8;                // frames of a computed segment one workgroup takes
 constexpr int SHIFT_COPY_TILE = 64;          // frames of a copied run one workgroup takes: a wave along the frames
@@ -34,7 +33,7 @@ constexpr uint32_t SHIFT_UNITY = 65536, SHIFT_STEP_MIN = 32768, SHIFT_STEP_MAX =
 constexpr int SHIFT_PARTS = 8;               // the lanes that share one cepstral sum: lane p takes the bins k = 8 j + p
 constexpr int SHIFT_LDS_FLOATS_PER_PASS = 8 * 1032;   // the frames of a pass times their padded row: 8 at N <= 1024, 4 at N = 2048
 
-constexpr int shift_launches(int S) { return (S + SHIFT_SEGMENTS - 1) / SHIFT_SEGMENTS; }
+constexpr int shift_launches(int S) { return segment_launches(S); }
 constexpr int64_t shift_tiles(int64_t frames, int tile) { return (frames + tile - 1) / tile; }
 
 // ---- the LDS image of a compute workgroup.  A frame's row is N + 8 elements: 8 (mod 32) doubles, so that the 8 frames x 4 bins (or
@@ -85,9 +84,8 @@ struct ShiftEntry {
     int32_t row, lead, first, end, own_end, n, tile0;
     uint32_t pitch_step, formant_step;
 };
-struct ShiftChunk {
-    ShiftEntry e[SHIFT_SEGMENTS];
-};
+using ShiftChunk = SegmentChunk<ShiftEntry>;
+constexpr ShiftEntry SHIFT_NO_ENTRY{0, 0, 0, 0, 0, 0, 0, SHIFT_UNITY, SHIFT_UNITY};   // a copy of nothing: what pads a launch's chunk
 constexpr bool shift_is_copy(uint32_t pitch_step, uint32_t formant_step) { return pitch_step == SHIFT_UNITY && formant_step == SHIFT_UNITY; }
 inline int64_t shift_lead_tiles(const ShiftEntry& w) { return shift_tiles((int64_t)w.first - w.lead, SHIFT_COPY_TILE); }
 inline int64_t shift_body_tiles(const ShiftEntry& w) {
@@ -104,17 +102,8 @@ inline std::string shift_plan(const tts_shift_segment_t* seg, int S, int B, int 
     if (!N) return "F = " + std::to_string(F) + " is not 2^m + 1 with 2^m in " + std::to_string(SHIFT_N_MIN) + " .. " + std::to_string(SHIFT_N_MAX);
     const int order_max = SHIFT_MAX_ORDER < N / 2 ? SHIFT_MAX_ORDER : N / 2;
     if (order < 2 || order > order_max) return "order = " + std::to_string(order) + " is not in 2 .. " + std::to_string(order_max);
-    if (S > SHIFT_MAX_SEGMENTS) return std::to_string(S) + " segments are more than tts_shift_max_segments() = " + std::to_string(SHIFT_MAX_SEGMENTS);
-    if (B > S) return std::to_string(B) + " rows of " + std::to_string(S) + " segments: no row is without a segment";
-    const std::string bad = lengths_refusal("n_frames", n_frames, B, "T", T);
+    const std::string bad = segment_rows_refusal(seg, S, B, "tts_shift_max_segments()", "n_frames", n_frames, "T", T);
     if (!bad.empty()) return bad;
-    if (seg[0].row != 0) return "row of segment 0 is " + std::to_string(seg[0].row) + ": the rows start at 0";
-    for (int s = 1; s < S; ++s)
-        if (seg[s].row != seg[s - 1].row && seg[s].row != seg[s - 1].row + 1)
-            return "row of segment " + std::to_string(s) + " is " + std::to_string(seg[s].row) + " and follows " + std::to_string(seg[s - 1].row) +
-                   ": the rows are non-decreasing and none is without a segment";
-    if (seg[S - 1].row != B - 1)
-        return "row of segment " + std::to_string(S - 1) + " is " + std::to_string(seg[S - 1].row) + ": the last row is B - 1 = " + std::to_string(B - 1);
     int64_t prev_end = 0;
     for (int s = 0; s < S; ++s) {
         const tts_shift_segment_t& q = seg[s];
@@ -142,8 +131,8 @@ inline std::string shift_plan(const tts_shift_segment_t* seg, int S, int B, int 
 
 // The entries of a legal list with every launch's own tile numbering: entry s is segment s, and tiles[l] the workgroups of launch l.
 inline void shift_entries(const tts_shift_segment_t* seg, int S, int T, const int32_t* n_frames, std::vector<ShiftEntry>& e, std::vector<int64_t>& tiles) {
-    e.assign((size_t)S, ShiftEntry{0, 0, 0, 0, 0, 0, 0, SHIFT_UNITY, SHIFT_UNITY});
-    tiles.assign((size_t)shift_launches(S), 0);
+    e.assign((size_t)S, SHIFT_NO_ENTRY);
+    tiles.assign((size_t)segment_launches(S), 0);
     int32_t prev_end = 0;
     for (int s = 0; s < S; ++s) {
         const tts_shift_segment_t& q = seg[s];
@@ -158,9 +147,7 @@ inline void shift_entries(const tts_shift_segment_t* seg, int S, int T, const in
         w.n = n_frames ? n_frames[q.row] : T;
         w.pitch_step = q.pitch_step;
         w.formant_step = q.formant_step;
-        int64_t& t = tiles[(size_t)(s / SHIFT_SEGMENTS)];
-        w.tile0 = (int32_t)t;
-        t += shift_lead_tiles(w) + shift_body_tiles(w) + shift_rest_tiles(w);
+        w.tile0 = segment_take_tiles(tiles, s, shift_lead_tiles(w) + shift_body_tiles(w) + shift_rest_tiles(w));
         prev_end = w.end;
     }
 }

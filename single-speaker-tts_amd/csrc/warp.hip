@@ -18,19 +18,12 @@ namespace tts {
 // mag [B][F][T] -> out [B][F][T_out]; the parent is stretch_cols_kernel: threads along the output frames, so the stores are
 // contiguous along T, and the loads of a wave gather along the contiguous axis at stride `step` (0.25 .. 4 floats), two
 // neighbours per output, inside the few cache lines its 64 outputs span: no staging.  Here a workgroup takes one tile of one
-// segment -- blockIdx.x is the tile in the launch's numbering, and the segment is the last entry whose first tile is not behind
-// it (workgroup-uniform, six scalar steps) -- in the bins blockIdx.y * WARP_BINS ..: a thread computes i and a of its frame once
-// and then walks the bins, wave w of the workgroup the bins w, w + 4, ...
+// segment -- blockIdx.x is the tile in the launch's numbering (segment_find) -- in the bins blockIdx.y * WARP_BINS ..: a thread
+// computes i and a of its frame once and then walks the bins, wave w of the workgroup the bins w, w + 4, ...
 __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(const float* __restrict__ in, float* __restrict__ out, const WarpChunk c, int n_seg, int F,
                                                             int T, int T_out) {
     const int tile = blockIdx.x;
-    int lo = 0, hi = n_seg - 1;
-    while (lo < hi) {
-        const int m = (lo + hi + 1) >> 1;
-        if (c.e[m].tile0 <= tile) lo = m;
-        else hi = m - 1;
-    }
-    const WarpEntry E = c.e[lo];
+    const WarpEntry E = c.e[segment_find(c.e, n_seg, tile)];
     const int j = (tile - E.tile0) * WARP_TILE + (threadIdx.x & (WARP_TILE - 1));
     if (j >= E.span) return;   // (behind what the segment owns: the next tile is the next segment's)
     const bool live = j < E.count;
@@ -60,18 +53,15 @@ __global__ __launch_bounds__(WARP_THREADS) void warp_kernel(const float* __restr
 namespace tts_api {
 
 // On h->stream; everything has been checked.  e, tiles: warp_entries' S entries and the tiles of every launch.
-static int warp_impl(tts_handle_t h, const float* mag, int F, int T, const std::vector<WarpEntry>& e, const std::vector<int64_t>& tiles, int S, int T_out,
+static int warp_impl(tts_handle_t h, const float* mag, int F, int T, const std::vector<WarpEntry>& e, const std::vector<int64_t>& tiles, int T_out,
                      float* out) {
-    ProfScope ps(h, ST_WARP, warp_launches(S));
+    ProfScope ps(h, ST_WARP, (int64_t)tiles.size());
     const unsigned bins = (unsigned)std::min((F + WARP_BINS - 1) / WARP_BINS, 65535);
-    for (int s0 = 0, l = 0; s0 < S; s0 += WARP_SEGMENTS, ++l) {
-        const int n = std::min(WARP_SEGMENTS, S - s0);
-        WarpChunk c;
-        for (int q = 0; q < WARP_SEGMENTS; ++q) c.e[q] = q < n ? e[(size_t)s0 + q] : WarpEntry{0, 0, 0, 0, 0, 0, 0, 0, 0.f};
+    return for_each_segment_launch(e, WARP_NO_ENTRY, [&](const WarpChunk& c, int n, int l) -> int {
         hipLaunchKernelGGL(warp_kernel, dim3((unsigned)tiles[(size_t)l], bins), dim3(WARP_THREADS), 0, h->stream, mag, out, c, n, F, T, T_out);
         HIPCHK(h, hipGetLastError());
-    }
-    return TTS_OK;
+        return TTS_OK;
+    });
 }
 
 }  // namespace tts_api
@@ -105,7 +95,7 @@ int tts_warp_magnitudes(tts_handle_t h, const float* mag, int B, int F, int T, c
     std::vector<WarpEntry> e;
     std::vector<int64_t> tiles;
     warp_entries(segments, S, T, n_frames, T_out, count.data(), e, tiles);
-    return warp_impl(h, mag, F, T, e, tiles, S, T_out, out);
+    return warp_impl(h, mag, F, T, e, tiles, T_out, out);
 }
 
 int tts_warp_max_segments(void) { return WARP_MAX_SEGMENTS; }

@@ -7,12 +7,11 @@
 // whose source position j * step / 65536 lies inside the segment --, of a pause its `pause`.
 //
 // The cut: every output frame of a row is OWNED by exactly one segment -- segment s owns [o[s], o[s+1]), a row's last segment
-// [o[s], T_out): its own frames and behind them the zeros of the row's rest.  A launch takes WARP_SEGMENTS consecutive segments,
-// a workgroup WARP_TILE consecutive frames of what one segment owns, in WARP_BINS bins; the tiles of a launch are numbered segment
-// after segment, and a workgroup finds its segment in the launch's table of first tiles.  The launches of a call write disjoint
-// ranges that cover out[B][F][T_out]: every element once.
+// [o[s], T_out): its own frames and behind them the zeros of the row's rest.  A workgroup takes WARP_TILE consecutive frames of what
+// one segment owns, in WARP_BINS bins; segments.h has the list's order, the launches and the numbering of their tiles.  The launches
+// of a call write disjoint ranges that cover out[B][F][T_out]: every element once.
 #pragma once
-#include "lengths.h"
+#include "segments.h"
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -23,8 +22,7 @@
 
 namespace tts {
 
-constexpr int WARP_SEGMENTS = 64;            // segments per launch: their entries travel by value
-constexpr int WARP_MAX_SEGMENTS = 4096;      // segments per call (64 launches)
+constexpr int WARP_SEGMENTS = SEGMENTS_PER_LAUNCH, WARP_MAX_SEGMENTS = MAX_SEGMENTS;
 constexpr int WARP_THREADS = 256;
 constexpr int WARP_TILE = 64;                // output frames of a workgroup: one wave along the frames, a bin per wave and round
 constexpr int WARP_BINS = 32;                // bins of a workgroup: WARP_BINS / (WARP_THREADS / WARP_TILE) rounds
@@ -32,7 +30,7 @@ constexpr uint32_t WARP_STEP_MIN = 16384, WARP_STEP_MAX = 262144;   // the rates
 constexpr float WARP_GAIN_MAX = 16.f;
 constexpr int WARP_MAX_T_OUT = 1 << 30;
 
-constexpr int warp_launches(int S) { return (S + WARP_SEGMENTS - 1) / WARP_SEGMENTS; }
+constexpr int warp_launches(int S) { return segment_launches(S); }
 constexpr int64_t warp_tiles(int64_t span) { return (span + WARP_TILE - 1) / WARP_TILE; }
 
 // output frames of a speech segment: the j >= 0 with j * step < frames * 65536 (exact in int64: frames < 2^31)
@@ -45,26 +43,16 @@ struct WarpEntry {
     uint32_t step;
     float gain;
 };
-struct WarpChunk {
-    WarpEntry e[WARP_SEGMENTS];
-};
+using WarpChunk = SegmentChunk<WarpEntry>;
+constexpr WarpEntry WARP_NO_ENTRY{0, 0, 0, 0, 0, 0, 0, 0, 0.f};   // what pads a launch's chunk
 
 // The checks of tts_warp_plan and tts_warp_magnitudes on the list, in the order the header lists them, and the lengths.  An
 // empty string: the list is legal (TTS_ERR_INVALID otherwise).  n_out [B], and count [S] where it is given, are filled.
 inline std::string warp_plan(const tts_warp_segment_t* seg, int S, int B, int T, const int32_t* n_frames, int64_t* n_out, int64_t* count = nullptr) {
     if (!seg || !n_out) return "a NULL pointer (segments and n_out are required)";
     if (B < 1 || T < 1 || S < 1) return "need B, T, S >= 1";
-    if (S > WARP_MAX_SEGMENTS) return std::to_string(S) + " segments are more than tts_warp_max_segments() = " + std::to_string(WARP_MAX_SEGMENTS);
-    if (B > S) return std::to_string(B) + " rows of " + std::to_string(S) + " segments: no row is without a segment";
-    const std::string bad = lengths_refusal("n_frames", n_frames, B, "T", T);
+    const std::string bad = segment_rows_refusal(seg, S, B, "tts_warp_max_segments()", "n_frames", n_frames, "T", T);
     if (!bad.empty()) return bad;
-    if (seg[0].row != 0) return "row of segment 0 is " + std::to_string(seg[0].row) + ": the rows start at 0";
-    for (int s = 1; s < S; ++s)
-        if (seg[s].row != seg[s - 1].row && seg[s].row != seg[s - 1].row + 1)
-            return "row of segment " + std::to_string(s) + " is " + std::to_string(seg[s].row) + " and follows " + std::to_string(seg[s - 1].row) +
-                   ": the rows are non-decreasing and none is without a segment";
-    if (seg[S - 1].row != B - 1)
-        return "row of segment " + std::to_string(S - 1) + " is " + std::to_string(seg[S - 1].row) + ": the last row is B - 1 = " + std::to_string(B - 1);
     int64_t o = 0;
     for (int s = 0; s < S; ++s) {
         const tts_warp_segment_t& q = seg[s];
@@ -96,20 +84,14 @@ inline std::string warp_plan(const tts_warp_segment_t* seg, int S, int B, int T,
 }
 
 // ... and of tts_warp_magnitudes' own arguments behind a legal list
-inline std::string warp_room(const int64_t* n_out, int B, int T_out) {
-    for (int b = 0; b < B; ++b)
-        if (n_out[b] > (int64_t)T_out) return "T_out = " + std::to_string(T_out) + " is below n_out[" + std::to_string(b) + "] = " + std::to_string(n_out[b]);
-    // (a launch's WARP_SEGMENTS segments then own fewer than 2^31 tiles, which is what a launch takes)
-    if (T_out > WARP_MAX_T_OUT) return "T_out = " + std::to_string(T_out) + " is above 2^30 = " + std::to_string(WARP_MAX_T_OUT);
-    return std::string();
-}
+inline std::string warp_room(const int64_t* n_out, int B, int T_out) { return segment_room("T_out", n_out, B, T_out, WARP_MAX_T_OUT); }
 
 // The entries of a legal list (count from warp_plan, every n_out <= T_out) with every launch's own tile numbering: entry s is
 // segment s, and tiles[l] the workgroups along the frames of launch l.
 inline void warp_entries(const tts_warp_segment_t* seg, int S, int T, const int32_t* n_frames, int T_out, const int64_t* count, std::vector<WarpEntry>& e,
                          std::vector<int64_t>& tiles) {
-    e.assign((size_t)S, WarpEntry{0, 0, 0, 0, 0, 0, 0, 0, 0.f});
-    tiles.assign((size_t)warp_launches(S), 0);
+    e.assign((size_t)S, WARP_NO_ENTRY);
+    tiles.assign((size_t)segment_launches(S), 0);
     int64_t o = 0;
     for (int s = 0; s < S; ++s) {
         const tts_warp_segment_t& q = seg[s];
@@ -124,9 +106,7 @@ inline void warp_entries(const tts_warp_segment_t* seg, int S, int T, const int3
         w.n = n_frames ? n_frames[q.row] : T;
         w.step = speech ? q.step : 65536u;
         w.gain = speech ? q.gain : 0.f;
-        int64_t& t = tiles[(size_t)(s / WARP_SEGMENTS)];
-        w.tile0 = (int32_t)t;
-        t += warp_tiles(w.span);
+        w.tile0 = segment_take_tiles(tiles, s, warp_tiles(w.span));
         o = last ? 0 : o + count[s];
     }
 }

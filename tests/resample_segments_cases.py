@@ -8,10 +8,11 @@ import numpy as np
 
 import resample_cases as RC
 import resample_segments_oracle as O
+import segment_cases as SC
+from segment_cases import NAN_PATTERN   # noqa: F401 (re-exported)
 
 TILE = O.TILE
 PER_LAUNCH = O.SEGMENTS_PER_LAUNCH
-NAN_PATTERN = 0x7fc0beef            # what `out` holds before every call: a NaN no computation makes
 R025, R05, DOWN4, R16K, ONE, UP3, R2, R4 = RC.RATIOS
 N = RC.RAGGED_N
 RAGGED = RC.RAGGED
@@ -100,11 +101,9 @@ def oracle(name, extra=0):
 
 
 def segment_array(H, segments):
-    """the rows as the contiguous RESAMPLE_SEGMENT array the library reads (unchecked: refusals travel through it too)"""
-    q = np.zeros(len(segments), dtype=H.RESAMPLE_SEGMENT)
-    for s, r in enumerate(segments):
-        q[s] = (r[0], r[1], r[2], r[4] if len(r) > 4 else 0, r[3])
-    return q
+    """the rows as the contiguous RESAMPLE_SEGMENT array the library reads (unchecked: refusals travel through it too); a row of
+    five has ``reserved`` last"""
+    return SC.segment_array(H.RESAMPLE_SEGMENT, [(r[0], r[1], r[2], r[4], r[3]) if len(r) > 4 else r for r in segments])
 
 
 def raw_call(eng, H, x, n_samples, segments, N_out, shift=0, S=None, B=None, want_n=True):

@@ -6,11 +6,12 @@ import ctypes
 
 import numpy as np
 
+import segment_cases as SC
 import shift_oracle as O
+from segment_cases import NAN_PATTERN, poisoned   # noqa: F401 (re-exported)
 
 TILE = O.TILE
 PER_LAUNCH = O.SEGMENTS_PER_LAUNCH
-NAN_PATTERN = 0x7fc0beef            # what `out` holds before every call: a NaN no computation makes
 SR, N_FFT, WIN = 22050, 2048, 1102  # the listening test's analysis
 TONES = (100.0, 150.0, 220.0)
 UP4, DOWN4 = O.step(4), O.step(-4)
@@ -73,15 +74,6 @@ def with_specials(x):
     return x
 
 
-def poisoned(x, n_frames):
-    """x with NaN in every frame at or behind n_frames[b]: what the kernel must never read"""
-    y = x.copy()
-    if n_frames is not None:
-        for b, n in enumerate(n_frames):
-            y[b, :, n:] = np.nan
-    return y
-
-
 def mixed():
     """B = 3, T = 70, ragged: uncovered gaps in front, between and behind; segments of TILE - 1, TILE and TILE + 1 frames; the pitch
     step alone, the formant step alone, both; folding (pitch_step > 65536); both ends of the range; a copy segment; a whole row; a
@@ -113,10 +105,7 @@ LISTS = dict(mixed=mixed, launch_seam=launch_seam)
 def segment_array(H, segments):
     """the rows as the contiguous SHIFT_SEGMENT array the library reads (unchecked: refusals travel through it too); six fields:
     ``reserved`` in fourth place"""
-    q = np.zeros(len(segments), dtype=H.SHIFT_SEGMENT)
-    for s, r in enumerate(segments):
-        q[s] = tuple(r) if len(r) == 6 else tuple(r[:3]) + (0,) + tuple(r[3:])
-    return q
+    return SC.segment_array(H.SHIFT_SEGMENT, segments)
 
 
 def raw_shift(eng, H, x, n_frames, segments, order, shift=0, S=None, B=None, F=None, T=None, in_place=False):

@@ -6,11 +6,12 @@ import ctypes
 
 import numpy as np
 
+import segment_cases as SC
 import warp_oracle as O
+from segment_cases import NAN_PATTERN, poisoned   # noqa: F401 (re-exported)
 
 TILE = O.TILE                       # tts_warp_tile(): the output frames of a segment one workgroup writes
 PER_LAUNCH = O.SEGMENTS_PER_LAUNCH  # segments whose entries travel with one launch
-NAN_PATTERN = 0x7fc0beef            # what `out` holds before every call: a NaN no computation makes
 STEPS = (16384, 65536, 65537, 262144)
 GAINS = (0.0, 1.0, 0.5, 16.0)
 CONTAINED_STEPS = (16384, 52429, 65536, 78643, 262144)
@@ -35,15 +36,6 @@ def with_specials(x):
         if t + 20 < T:
             x[0, -1, t + 20] = v
     return x
-
-
-def poisoned(x, n_frames):
-    """x with a signalling pattern in every frame at or behind n_frames[b]: what the kernel must never read (it would show as NaN)"""
-    y = x.copy()
-    if n_frames is not None:
-        for b, n in enumerate(n_frames):
-            y[b, :, n:] = np.nan
-    return y
 
 
 def mixed():
@@ -112,10 +104,7 @@ def t_out_of(case, extra=3):
 
 def segment_array(H, segments):
     """the rows as the contiguous WARP_SEGMENT array the library reads (unchecked: refusals travel through it too)"""
-    q = np.zeros(len(segments), dtype=H.WARP_SEGMENT)
-    for s, r in enumerate(segments):
-        q[s] = tuple(r)
-    return q
+    return SC.segment_array(H.WARP_SEGMENT, segments)
 
 
 def raw_warp(eng, H, x, n_frames, segments, T_out, shift=0, S=None, B=None):

@@ -1,6 +1,7 @@
-// Internals shared by the three translation units of the C ABI (api_handle.hip: handle, workspace allocator, weights, options;
-// api_stages.hip: the stage entry points and what they enqueue; api_pipeline.hip: tts_synthesize and its host-memory form,
-// the scheduler of the three streams).  Not part of the interface: include/sstts_hip.h is.
+// Internals shared by the four translation units of the C ABI (api_handle.hip: handle, workspace allocator, weights, options;
+// api_stages.hip: the network's stage entry points and what they enqueue; api_griffin_lim.hip: Griffin-Lim's and the analysis
+// side's host code; api_pipeline.hip: tts_synthesize and its host-memory form, the scheduler of the three streams).  Not part of
+// the interface: include/sstts_hip.h is.
 #pragma once
 #include <cmath>
 #include <cstdio>
@@ -88,7 +89,7 @@ struct Signal {
     void disarm() { armed = false; }   // what was recorded is known to be complete, or has been waited for by all it concerns
 };
 
-// The run tables of the streaming Griffin-Lim kernel, owned by the handle: one entry per cut (gl_plan in api_stages.hip makes
+// The run tables of the streaming Griffin-Lim kernel, owned by the handle: one entry per cut (gl_plan in api_griffin_lim.hip makes
 // and finds them; DESIGN.md 4.5 has the rules).  A call that finds its cut allocates, copies and waits for nothing; a new one
 // costs one asynchronous copy on the call's stream and at most one hipMalloc.  The least recently used entry is replaced: two
 // per shape (a pipelined call's narrow and wide cut) for the shapes a server runs; a dataset's length vectors come and go.
@@ -113,6 +114,18 @@ struct GlPlanStore {
     std::vector<std::vector<GlItem>> retired_host;
     void synced();    // every stream of the handle has been synchronised (sync_all)
     void release();   // tts_destroy
+};
+
+// Griffin-Lim's work counters (the streaming family of gl_run): a ring of slots, zeroed once; a launch takes the next slot and
+// zeroes its predecessor's
+constexpr unsigned GL_RING = 256;
+struct GlCounterRing {
+    unsigned* ring = nullptr;      // the buffer the bookkeeping refers to
+    unsigned seq = 0;
+    unsigned* last = nullptr;      // slot of the most recent launch (dirty)
+    hipStream_t stream = nullptr;
+    hipError_t start(unsigned* buf, hipStream_t on);   // starts over where the buffer (a re-allocated workspace) or the stream changed
+    void next(GlParams& q);                            // q's launch takes the next slot and zeroes the one before
 };
 
 // A pinned host buffer and the device buffer it is copied to or from (tts_synthesize_host); sizes only increase.
@@ -391,11 +404,7 @@ struct tts_handle_s {
     int gl_run_len = 0;       // ... or frames per full run (0 = planned)
     int timeline = 0;         // print the absolute stage times of every profiled span (prof_collect)
     int gl_workers = 0;       // Griffin-Lim: plan and launch for this many workgroups (0 = the free compute units)
-    // Griffin-Lim work counters: a ring of slots, zeroed once; a launch takes the next slot and zeroes its predecessor's
-    unsigned* gl_ring = nullptr;       // the ring the bookkeeping below refers to (a re-allocated workspace starts over)
-    unsigned gl_ring_seq = 0;
-    unsigned* gl_ring_last = nullptr;  // slot of the most recent launch (dirty)
-    hipStream_t gl_ring_stream = nullptr;
+    GlCounterRing gl_ring;    // Griffin-Lim's work counters
     bool pd_used = false;            // a persistent launch has been enqueued since the last status check
     unsigned* pd_sync = nullptr;     // sync words of the last persistent launch, laid out for pd_clusters (decoder_cluster.h)
     int pd_clusters = 0;
@@ -453,7 +462,6 @@ struct tts_handle_s {
         float2* tw2048 = nullptr;
         float2* tables = nullptr;
         bool configured = false;
-        int n_cus = 0;
     } gl;
 
     // general power-of-two path (griffin_lim_generic.hip): twiddles per n_fft, window tables of the last configuration
@@ -608,7 +616,7 @@ struct ProfScope {
     }
 };
 
-// ---- defined in api_handle.hip / api_stages.hip / api_pipeline.hip
+// ---- defined in api_handle.hip / api_stages.hip / api_griffin_lim.hip / api_pipeline.hip
 int fail(tts_handle_t h, int code, const std::string& msg);
 void build_manifest(tts_handle_t h);
 int pd_timed_out(tts_handle_t h);   // the persistent decoder's timeout, reported in ONE wording (check_status, tts_wait_host)
@@ -628,24 +636,35 @@ int run_cbhg(tts_handle_t h, const CbhgWeights& w, const char* tag, const float*
 int check_ready(tts_handle_t h);
 int gl_tables(tts_handle_t h);
 int device_cus(tts_handle_t h);
-int stft_prepare(tts_handle_t h, int n, int win, int hop, int n_fft);
-int stft_run(tts_handle_t h, const float* wav, int B, int n, int n_fft, int win, int hop, float2** out, int* Tf_out);
 int gl_fp(int n_fft);
 bool gl_is_streaming(int n_fft, int win, int hop);
 int glg_twiddles(tts_handle_t h, int n_fft, const float2** out);
 int glg_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
-// a ragged batch: host lengths [B] (T is then T_max); null everywhere = one length
-// d_frames: the same lengths, already in device memory (null: they are uploaded)
-int gl_run_generic(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize, const int32_t* n_frames = nullptr, const int* d_frames = nullptr);
+int gl_refuse(tts_handle_t h, const GlRefusal& r);   // gl_refusal's answer (gl_plan.h) as a return code: fail() with its text, or TTS_OK
 int gl_prepare(tts_handle_t h, int T, int win, int hop, int n_fft);
-// the cut of p's batch (T, B, win, hop; n_frames: host lengths of a ragged batch or null) for launches of n_stage iterations on
-// n_workers workgroups, from the handle's store: sets p.items / n_items / slots_per_utt / n_workers for launches on h->stream
-int gl_plan(tts_handle_t h, GlParams& p, const int32_t* n_frames, int n_workers, int n_stage, int force_runs, int force_run_len);
-int gl_run(tts_handle_t h, const float* mag_int, const float* init_ft, uint64_t seed, int B, int T, int n_iter, int win, int hop, int n_fft, float* wav, float* mse, bool peak_normalize = false, bool under_reservation = false, float2* const* phase_pair = nullptr, bool phase_ready = false, int wide_from = -1, const int32_t* n_frames = nullptr, const int* d_frames = nullptr);
+// One Griffin-Lim call: what tts_griffin_lim / tts_griffin_lim_ragged and synth_main ask of gl_run, which takes the streaming kernel
+// where gl_is_streaming says so and the general kernels elsewhere.  Nothing behind it reads the handle's settings.
+struct GlCall {
+    const float* mag = nullptr;           // time-major magnitudes [B][T][gl_fp(n_fft)]
+    const float* init_ft = nullptr;       // reference-layout U[0,1) numbers, or null: then the seed
+    uint64_t seed = 0;
+    int B = 0, T = 0, n_iter = 0, win = 0, hop = 0, n_fft = 0;   // T: T_max of a ragged batch
+    float *wav = nullptr, *mse = nullptr; // the waveforms; the last iteration's error per utterance, or null
+    bool peak_normalize = false;
+    const int32_t* n_frames = nullptr;    // a ragged batch: host lengths [B]; null = one length
+    const int* d_frames = nullptr;        // the same lengths, already in device memory (null: they are uploaded)
+    int momentum = 0;                     // "gl_momentum": alpha in thousandths
+    // what only a pipelined call sets (the streaming kernel)
+    bool under_reservation = false;       // `reserve_cus` compute units are kept free of Griffin-Lim
+    float2* const* phase_pair = nullptr;  // the two phasor-code buffers to iterate in (null: the handle's own pair)
+    bool phase_ready = false;             // phase_pair[0] already holds the initial phasors (another stream, the caller's events)
+    int wide_from = -1;                   // launches from this index on are cut for ALL compute units (gl_wide_from); -1: none
+};
+int gl_run(tts_handle_t h, const GlCall& c);
 // ---- Workspaces.  A stage's buffers are named in ONE function, `<stage>_scratch`, which takes the shape that decides their sizes and
 // fills a struct of typed pointers.  The stage asks it for its pointers; a synthesis call asks it ahead for the same shape, before
 // anything of the call is enqueued (synth_workspaces: a workspace that grows synchronises every stream), so the stage finds them in place.
-// Griffin-Lim's (api_stages.hip).  momentum: the handle's or the call's "gl_momentum"; `mom`, the previous projection, exists for a call
+// Griffin-Lim's (api_griffin_lim.hip).  momentum: the handle's or the call's "gl_momentum"; `mom`, the previous projection, exists for a call
 // that has a second iteration to use it, and mom_grew says that this request made or enlarged it (what synth_workspaces counts).
 struct GlgScratch { float2* phase; float* frames; float* mse_partial; float2* mom; bool mom_grew; };   // the general kernels
 int glg_scratch(tts_handle_t h, int B, int T, int win, int n_fft, int momentum, int n_iter, GlgScratch* s);
@@ -653,7 +672,6 @@ int glg_scratch(tts_handle_t h, int B, int T, int win, int n_fft, int momentum, 
 // a round of the waves (tests/gl_plan_check.cpp holds the planner to it).  min_slots: the cuts in hand, which only a cut forced through
 // the debug hooks takes beyond that; frame_mse: the call wants the error, which momentum keeps per frame; own_phase: the handle's
 // pair of phasor-code buffers, for a caller that brings none.
-constexpr unsigned GL_RING = 256;   // work counters: gl_run
 struct GlScratch { float2* mom; bool mom_grew; float* mse_partial; unsigned* counter_ring; float2* phase[2]; };
 int gl_scratch(tts_handle_t h, int B, int T, int momentum, int n_iter, bool frame_mse, int min_slots, bool own_phase, GlScratch* s);
 // A ragged batch's window sum-square rows of `row` floats -- streaming: [2][gl_rw_edge_len], general kernels: n_fft + hop (T_max - 1) --
@@ -713,7 +731,7 @@ void resample_release(tts_handle_t h);
 void mfcc_release(tts_handle_t h);   // cepstrum.hip: the DCT tables
 void shift_release(tts_handle_t h);  // shift.hip: the cosine tables and lifters
 // estimated initial phases (phase_init.hip): both input layouts -> the public (B, F, T) array on h->stream, arguments checked by
-// the caller (phase_plan.h).  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with the option "gl_init" the
+// the caller (phase_plan.h).  gl_init_phase: the init_phase of a Griffin-Lim call -- the caller's, or with gl_init (the option "gl_init" of the handle or the call) the
 // estimate from the time-major magnitudes `magi` in PhaseScratch::init_est, or null.
 // mag_rows: from_public alone (the (B, F, T) input, transposed); the three chunk maps: with more than one chunk of frames alone;
 // init_est: gl_start alone, the estimate as the public-layout init_phase of a Griffin-Lim call
@@ -721,8 +739,8 @@ struct PhaseScratch { float *u_rows, *mag_rows; unsigned short* map_s; unsigned 
 int phase_estimate_scratch(tts_handle_t h, int B, int T, int n_fft, bool from_public, bool gl_start, PhaseScratch* s);
 int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_stride, bool time_major, const int32_t* n_frames, int n_fft,
                         int hop, float* out);
-int gl_init_phase(tts_handle_t h, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames, int n_fft,
-                  int hop, const float** out);
+int gl_init_phase(tts_handle_t h, int gl_init, const float* magi, const float* init_phase, int B, int T, int row_stride, const int32_t* n_frames,
+                  int n_fft, int hop, const float** out);
 int standalone_begin(tts_handle_t h);
 int standalone_end(tts_handle_t h);
 int encoder_impl(tts_handle_t h, const int32_t* ids, int B, int Ts, float* memory);

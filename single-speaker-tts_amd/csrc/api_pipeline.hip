@@ -105,16 +105,15 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     bool setting_grew = false;
     unsigned allocs = 0;
     int rc = TTS_OK;
-    // Griffin-Lim's workspaces, from the function its kernel family asks again (gl_run_generic / gl_run); of these only the momentum
+    // Griffin-Lim's workspaces, from the function its kernel family asks again (the two of gl_run); of these only the momentum
     // buffer is a setting's.  (ONE momentum buffer: only Griffin-Lim launches touch it, and those of consecutive calls follow each
     // other on the main stream.  The streaming kernel's partials have room for any cut the call may plan, narrow or wide.)
     GlgScratch gg{};
     GlScratch gs{};
     if (!k.gl_streaming) {   // (and the general kernels' tables)
-        if ((long long)sp->hop_length * (Tg - 1) <= c.n_fft / 2)
-            return fail(h, TTS_ERR_INVALID, "griffin_lim: signal shorter than n_fft/2 (reflect padding undefined)");
         const float2* tw_unused = nullptr;
-        if ((rc = glg_prepare(h, Tg, sp->win_length, sp->hop_length, c.n_fft)) || (rc = glg_twiddles(h, c.n_fft, &tw_unused)) ||
+        if ((rc = gl_refuse(h, gl_refusal("griffin_lim: ", GL_RULE_SIGNAL, c.n_fft, sp->win_length, sp->hop_length, Tg))) ||
+            (rc = glg_prepare(h, Tg, sp->win_length, sp->hop_length, c.n_fft)) || (rc = glg_twiddles(h, c.n_fft, &tw_unused)) ||
             (rc = glg_scratch(h, B, Tg, sp->win_length, c.n_fft, k.set.gl_momentum, sp->n_iter, &gg)))
             return rc;
     } else if ((rc = gl_scratch(h, B, Tg, k.set.gl_momentum, sp->n_iter, false, 0, false, &gs))) {
@@ -473,18 +472,19 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     // estimated initial phases: from the magnitudes Griffin-Lim reconstructs from, at each utterance's own length, between the
     // post-net (or the stretch) and the first Griffin-Lim launch; from here on they are the call's explicit init_phase
     const float* init_phase = k.init_phase;
-    if (estimate && (rc = gl_init_phase(h, gl_mag, nullptr, B, Tg, k.FP, n_frames, h->cfg.n_fft, sp->hop_length, &init_phase))) return rc;
+    if (estimate && (rc = gl_init_phase(h, k.set.gl_init, gl_mag, nullptr, B, Tg, k.FP, n_frames, h->cfg.n_fft, sp->hop_length, &init_phase))) return rc;
     const int wide_from = (k.pipelined && k.gl_streaming) ? gl_wide_from(h, k.set, B, k.Ts, sp->n_steps, L.T_model, sp->n_iter) : -1;
     pl.gl_wide_used[parity] = wide_from >= 0;
     float* gl_wav = s.pitch ? k.gl_wav : k.wav;
     // (a shifted call normalises what the resampler leaves; with a loudness target nothing is peak-normalised)
     const bool gl_peak = sp->peak_normalize != 0 && !s.pitch && !k.set.loud.enabled;
-    if (k.gl_streaming)
-        rc = gl_run(h, gl_mag, init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav, nullptr,
-                    gl_peak, k.pipelined, k.phase_pair, phase_on_front, wide_from, n_frames, d_frames);
-    else
-        rc = gl_run_generic(h, gl_mag, init_phase, sp->seed, B, Tg, sp->n_iter, sp->win_length, sp->hop_length, h->cfg.n_fft, gl_wav,
-                            nullptr, gl_peak, n_frames, d_frames);
+    GlCall gl;
+    gl.mag = gl_mag; gl.init_ft = init_phase; gl.seed = sp->seed;
+    gl.B = B; gl.T = Tg; gl.n_iter = sp->n_iter; gl.win = sp->win_length; gl.hop = sp->hop_length; gl.n_fft = h->cfg.n_fft;
+    gl.wav = gl_wav; gl.peak_normalize = gl_peak; gl.n_frames = n_frames; gl.d_frames = d_frames;
+    gl.momentum = k.set.gl_momentum;   // (the call's own copy of the setting, as synth_workspaces and gl_wide_from took it)
+    gl.under_reservation = k.pipelined; gl.phase_pair = k.phase_pair; gl.phase_ready = phase_on_front; gl.wide_from = wide_from;
+    rc = gl_run(h, gl);   // (the family k.gl_streaming names: gl_is_streaming of the same three numbers)
     if (s.pitch && !rc) {
         // The pitch: the hop (Tg - 1) samples Griffin-Lim made, resampled by rho into the rows of the call without pitch.  With
         // end-of-speech stopping utterance b has hop (n'[b] - 1) samples, and its row ends where the un-shifted call's does.
@@ -519,8 +519,7 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
     const tts_config_t& c = h->cfg;
     // n_fft is a model parameter (reference tacotron/params/model.py:13-24): the final Dense has 1 + n_fft / 2 outputs, its
     // de-normalising epilogue writes rows padded to gl_fp(n_fft), and every size but 2048 reconstructs in the general kernels
-    if (!glg_supports(c.n_fft))
-        return fail(h, TTS_ERR_UNSUPPORTED, "synthesize: n_fft must be a power of two between 256 and 4096");
+    if ((rc = gl_refuse(h, gl_refusal("synthesize: ", GL_RULE_NFFT, c.n_fft, 0, 0, 0)))) return rc;
     SynthCall k{ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, &host, sp->n_steps * c.reduction,
                 1 + c.n_fft / 2, gl_fp(c.n_fft), gl_is_streaming(c.n_fft, sp->win_length, sp->hop_length)};
     k.set = set;
@@ -530,8 +529,7 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
     const double* tab_unused = nullptr;   // (the ratio's table, made before anything of this call is enqueued)
     if (k.shape.pitch && (rc = resample_table(h, k.shape.rho, &tab_unused))) return rc;
     if (k.gl_streaming && (rc = gl_prepare(h, k.shape.Tg, sp->win_length, sp->hop_length, c.n_fft))) return rc;
-    if (!k.gl_streaming && (sp->win_length < 2 || sp->win_length > c.n_fft || sp->hop_length < 1))
-        return fail(h, TTS_ERR_INVALID, "synthesize: need 2 <= win_length <= n_fft, hop_length >= 1");
+    if (!k.gl_streaming && (rc = gl_refuse(h, gl_refusal("synthesize: ", GL_RULE_WINDOW, c.n_fft, sp->win_length, sp->hop_length, 0)))) return rc;
     if (set.eos.enabled && speech_threshold(set.eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
         return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
     if (set.loud.enabled &&

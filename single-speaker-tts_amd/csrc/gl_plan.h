@@ -3,6 +3,7 @@
 // runtime call -- so that the planner can be compiled and checked without the library (tests/gl_plan_check.cpp).
 #pragma once
 #include <cstddef>
+#include <string>
 #include <vector>
 
 namespace tts {
@@ -38,5 +39,38 @@ void gl_build_wlane(const float* window, const float* rwss, int win, int hop, in
 // returns their number.  lens[b]: frames of utterance b (null: T in every one).  force_*: gl_plan.hip.
 int gl_plan_items(const int* lens, int T, int B, int win, int hop, int n_workers, int n_stage, int force_runs, int force_run_len,
                   std::vector<GlItem>* items, int* slots_per_utt, int* workers_out = nullptr);
+
+// ---- The argument rules of the Griffin-Lim and STFT entry points, said once.  A site names the rules it holds in `rules` and the
+// name its messages begin with in `who` ("griffin_lim: ", "stft: ", "" for the general kernels' tables); the answer is the refusal
+// text -- empty for a legal call -- and whether it is TTS_ERR_UNSUPPORTED (else TTS_ERR_INVALID).  Where several rules are broken the
+// first in this order answers: n_fft, window / hop / T, the lengths of a ragged batch utterance by utterance, the signal's length.
+enum : unsigned {
+    GL_RULE_NFFT = 1,       // n_fft a power of two, 256 .. 4096 (glg_supports)
+    GL_RULE_WINDOW = 2,     // 2 <= window <= n_fft, hop >= 1
+    GL_RULE_FRAMES = 4,     // T >= 1
+    GL_RULE_SIGNAL = 8,     // hop (T - 1) samples reach beyond the reflect padding
+    GL_RULE_ANALYSIS = 16   // the STFT side: T is the signal's samples, and the hop is called "hop"
+};
+struct GlRefusal { std::string text; bool unsupported = false; };
+// lens: the B frame counts of a ragged batch (T is then T_max), each held to 1 .. T_max and to the signal rule; null: none
+inline GlRefusal gl_refusal(const std::string& who, unsigned rules, int n_fft, int win, int hop, int T, const int* lens = nullptr, int B = 0) {
+    const auto too_short = [&](long long samples) { return samples <= n_fft / 2; };
+    const char* const short_text = "signal shorter than n_fft/2 (reflect padding undefined)";
+    if ((rules & GL_RULE_NFFT) && (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1)) != 0))
+        return {who + "n_fft must be a power of two between 256 and 4096", true};
+    if (((rules & GL_RULE_WINDOW) && (win < 2 || win > n_fft || hop < 1)) || ((rules & GL_RULE_FRAMES) && T < 1)) {
+        if (!(rules & GL_RULE_WINDOW)) return {who + "T >= 1"};
+        return {who + "need 2 <= win_length <= n_fft, " + ((rules & GL_RULE_ANALYSIS) ? "hop" : "hop_length") + " >= 1" +
+                ((rules & GL_RULE_FRAMES) ? ", T >= 1" : "")};
+    }
+    for (int b = 0; lens && b < B; ++b) {
+        if (lens[b] < 1 || lens[b] > T)
+            return {who + "n_frames[" + std::to_string(b) + "] = " + std::to_string(lens[b]) + " is not in 1 .. T_max = " + std::to_string(T)};
+        if (too_short((long long)hop * (lens[b] - 1)))
+            return {who + "utterance " + std::to_string(b) + " (" + std::to_string(lens[b]) + " frames): " + short_text};
+    }
+    if ((rules & GL_RULE_SIGNAL) && too_short((rules & GL_RULE_ANALYSIS) ? (long long)T : (long long)hop * (T - 1))) return {who + short_text};
+    return {};
+}
 
 }  // namespace tts

@@ -33,7 +33,7 @@ static std::vector<GlItem> check_case(const std::vector<int>& lens, bool uniform
     if (spu < 1) fail(tag, "slots_per_utt " + std::to_string(spu));
     const bool forced = force_runs >= 1 || force_run_len >= GL_NW;
     if (used < 1 || (!forced && used > workers)) fail(tag, "workers_out " + std::to_string(used));
-    // what the library sizes the per-run partials by before a cut is planned (gl_scratch, api_stages.hip): no planned run is
+    // what the library sizes the per-run partials by before a cut is planned (gl_scratch, api_griffin_lim.hip): no planned run is
     // shorter than half a round of the waves
     if (!forced && spu > T_max / (GL_NW / 2) + 1)
         fail(tag, "slots_per_utt " + std::to_string(spu) + " beyond T_max / (GL_NW / 2) + 1 = " + std::to_string(T_max / (GL_NW / 2) + 1));

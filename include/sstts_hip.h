@@ -757,6 +757,55 @@ int tts_equalizer_profile(const char* name, int sampling_rate, double* sos_out /
 /* Host only: the largest cascade, 8 sections. */
 int tts_equalizer_max_sections(void);
 
+/* ---- the dynamics compressor: an envelope follower and a gain computer ----------------------- */
+/* The parameters of tts_compress, by value.  threshold_db in -80 .. 0 (dB re full scale); slope = 1 / ratio in 0 .. 1 (0: ratio
+ * infinity, 1: no compression); knee_db in 0 .. 40, the whole width W of the soft knee around the threshold; makeup_db in -24 .. +24;
+ * attack_coeff = aA and release_coeff = aR in [0, 1), the one-pole coefficients tts_compressor_design makes of times in ms. */
+typedef struct {
+    double threshold_db, slope, knee_db, makeup_db, attack_coeff, release_coeff;
+} tts_compressor_t;
+/* What tts_compress can tell of a row: the samples it held, those whose gain reduction r was below 0, the largest reduction -r in
+ * dB (0: none) and the largest |out| (NaN passed over). */
+typedef struct {
+    int32_t n;
+    int32_t reduced;
+    float max_reduction_db;
+    float peak_out;
+} tts_compress_stats_t;
+/* A feed-forward peak compressor over every utterance (no reference counterpart).  Per row, x the sample as a double, the states e1
+ * and e zero in front of its first sample:
+ *   v  = |x|, or 0 where x is not finite                     the detector's input
+ *   e1 = max(v, aR e1)                                        the release: a peak held and let go
+ *   e  = aA e + bA e1,  bA = 1 - aA rounded once             the attack: two products and a sum, each individually rounded
+ *   L  = 20 log10(e),  d = L - threshold_db,  W = knee_db
+ *   r  = 0 where 2 d <= -W;  (slope - 1) d where 2 d >= W;  (slope - 1) (d + W / 2)^2 / (2 W) between them
+ *   out = float32(x * 10^((r + makeup_db) / 20)), rounded once; x's own bits where r + makeup_db is exactly 0
+ * r is computed directly and never as a difference of levels, so e = 0 gives r = 0.  A NaN sample is NaN at its own position and
+ * silence to the detector; an infinite one stays infinite.  The recurrences are sequential, so an utterance is cut into the
+ * equaliser's segments of 256 samples (csrc/compressor_plan.h): both maps compose in closed form over a segment, e1 -> max(c, AR e1)
+ * and e -> AA e + q with AR and AA the coefficients multiplied out 256 times on the host.  Pass A keeps c of every segment but the
+ * last, a chain makes the e1 every segment starts from, pass B keeps q (which depends on that e1), a second chain makes the e, and
+ * pass C writes.  envelope is the bits of tests/compressor_oracle.py and within 2^-30 of its largest value of the recurrence run
+ * without a cut; out is within 2^-24 |y| + 2^-40 |y| + 2^-150 of that oracle's double y.
+ * out may equal wav (in place); any other overlap is refused.  Samples at or behind n_samples[b] are neither read nor written, every
+ * other element of out is written exactly once, and an utterance's result is the bits of its B = 1 call.  envelope: DEVICE [B][N]
+ * doubles, e of every sample, or NULL.  stats: DEVICE [B] records, or NULL.  Asynchronous on the handle's stream, no host wait,
+ * nothing uploaded: five launches per 64 utterances, a sixth where records are asked for.  Profile stage "compress".
+ * TTS_ERR_INVALID, before anything is enqueued, in this order: a NULL wav, out or params; B or N < 1; an n_samples[b] outside 1 .. N;
+ * a parameter outside its range (threshold, slope, knee, make-up, attack, release, in that order); a wav or out that is not 4-byte
+ * aligned; an envelope that is not 8-byte aligned; out overlapping wav without being equal to it. */
+int tts_compress(tts_handle_t h, const float* wav /* [B][N] */, float* out /* [B][N]; may equal wav */, int B, int N,
+                 const int32_t* n_samples /* HOST [B] or NULL */, const tts_compressor_t* params /* HOST, read before the call returns */,
+                 double* envelope /* [B][N] or NULL */, tts_compress_stats_t* stats /* [B] or NULL */);
+/* Host only: the coefficients of an attack and a release time, exp(-1 / (ms * 1e-3 * sampling_rate)); 0 ms gives 0 (no smoothing).
+ * TTS_ERR_UNSUPPORTED: a sampling rate outside 8000 .. 192000, a time outside 0 .. 10000 ms.  TTS_ERR_INVALID: a NULL pointer. */
+int tts_compressor_design(int sampling_rate, double attack_ms, double release_ms, double* attack_coeff_out, double* release_coeff_out);
+/* Host only: the parameters of a named profile at a sampling rate, as threshold / ratio / knee / attack / release / make-up --
+ * "speech" (-18 dB, 3:1, 6 dB, 5 ms, 100 ms, +3 dB), "telephony" (-20 dB, 4:1, 6 dB, 3 ms, 80 ms, +6 dB), "small-speaker" (-24 dB,
+ * 6:1, 10 dB, 2 ms, 60 ms, +8 dB).  Every preset is UNTUNED: nobody has listened to one.  TTS_ERR_UNSUPPORTED: the sampling rate.
+ * TTS_ERR_INVALID: an unknown name, a NULL pointer. */
+int tts_compressor_profile(const char* name, int sampling_rate, tts_compressor_t* params_out);
+
 /* ---- attention diagnostics: alignment statistics ------------------------------------------- */
 /* What the decoder's alignments say about whether the sentence was read (no reference counterpart: the reference plots its
  * alignments, tacotron/model.py:552-598, and judges them by eye).  alignments DEVICE [n_steps_max][B][Ts] as the decoder
@@ -1216,6 +1265,17 @@ int tts_set_limiter(tts_handle_t h, int enabled, double ceiling, int lookahead, 
  * outside 1 .. tts_equalizer_max_sections(), a coefficient that is not finite, a section that is not stable). */
 int tts_set_equalizer(tts_handle_t h, int enabled, const double* sos /* HOST [n_sections][5] */, int n_sections);
 
+/* The compressor of synthesis (tts_compress).  A setting of the HANDLE, off by default and read when a call is made; off is the
+ * call as it always was, launch for launch.  With enabled != 0, tts_synthesize and tts_synthesize_host run tts_compress(params) in
+ * place on the call's rows -- behind the equaliser, ahead of the loudness normaliser and the limiter -- on the call's stream, with
+ * no host wait, over the samples each row holds (the lengths the loudness setting uses).  The parameters are copied.  The result is
+ * the bits of the same call made with the setting off followed by tts_compress on those rows.  Lengths, shapes and timing marks do
+ * not change.  A make-up gain behind the peak normalisation can pass 1.0: give it a limiter or a loudness target.  The first call
+ * after the setting was switched on is not pipelined (its buffers are new).
+ * With enabled == 0 params is not looked at.  The setting stays as it was on TTS_ERR_INVALID (a NULL params, a parameter outside
+ * its range). */
+int tts_set_compressor(tts_handle_t h, int enabled, const tts_compressor_t* params);
+
 /* Attention diagnostics of synthesis: the alignment statistics of every call (tts_alignment_stats).  A setting of the HANDLE,
  * off by default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
  * tts_synthesize and tts_synthesize_host run tts_text_lengths(pad_id) on the call's device ids behind its encoder and
@@ -1299,7 +1359,8 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * or inside a tts_synthesize call with tts_set_alignment_stats or tts_set_token_times on), "join" (tts_join), "limiter" (tts_true_peak, tts_limit,
  * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
  * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes), "shift" (tts_shift_magnitudes), "equalize" (tts_equalize,
- * stand-alone or inside a tts_synthesize call with tts_set_equalizer on).
+ * stand-alone or inside a tts_synthesize call with tts_set_equalizer on), "compress" (tts_compress, stand-alone or inside a
+ * tts_synthesize call with tts_set_compressor on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

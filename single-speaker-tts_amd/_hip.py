@@ -259,6 +259,10 @@ _PROTOTYPES = {
     'tts_equalizer_profile': (c_int, [c_char_p, c_int, POINTER(ctypes.c_double), POINTER(c_int)]),
     'tts_equalizer_max_sections': (c_int, []),
     'tts_set_equalizer': (c_int, [c_void_p, c_int, POINTER(ctypes.c_double), c_int]),
+    'tts_compress': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p, c_void_p]),
+    'tts_compressor_design': (c_int, [c_int, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
+    'tts_compressor_profile': (c_int, [c_char_p, c_int, c_void_p]),
+    'tts_set_compressor': (c_int, [c_void_p, c_int, c_void_p]),
     'tts_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
     'tts_encode_width': (c_int, [c_int]),
     'tts_encode_tile': (c_int, []),
@@ -799,6 +803,98 @@ def equalizer_sections(setting, sampling_rate):
     if how == 'design':
         return np.array([equalizer_design(k, sampling_rate, f0, q, g) for k, f0, q, g in what], dtype=np.float64)
     return equalizer_sos_check('equalizer', what)
+
+
+# ---- the compressor (csrc/compressor_plan.h): the limits of its parameters and the profiles.  Every preset is untuned: nobody has
+# listened to one.
+CMP_THRESHOLD_MIN, CMP_THRESHOLD_MAX = -80.0, 0.0      # dB re full scale
+CMP_KNEE_MAX = 40.0
+CMP_MAKEUP_MIN, CMP_MAKEUP_MAX = -24.0, 24.0
+CMP_MS_MAX = 10000.0
+# threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db
+CMP_PROFILES = collections.OrderedDict((
+    ('speech', (-18.0, 3.0, 6.0, 5.0, 100.0, 3.0)),
+    ('telephony', (-20.0, 4.0, 6.0, 3.0, 80.0, 6.0)),
+    ('small-speaker', (-24.0, 6.0, 10.0, 2.0, 60.0, 8.0)),
+))
+CMP_DEFAULTS = (None, None, 6.0, 5.0, 100.0, 0.0)     # what a short tuple leaves out: knee, attack, release, make-up
+COMPRESS_RECORD = np.dtype([('n', np.int32), ('reduced', np.int32), ('max_reduction_db', np.float32), ('peak_out', np.float32)])
+
+
+class TtsCompressor(ctypes.Structure):
+    """tts_compressor_t"""
+    _fields_ = [(name, ctypes.c_double) for name in ('threshold_db', 'slope', 'knee_db', 'makeup_db', 'attack_coeff', 'release_coeff')]
+
+
+def compressor_design(sampling_rate, attack_ms, release_ms):
+    """``(attack_coeff, release_coeff)`` as tts_compressor_design makes them, exp(-1 / (ms * 1e-3 * sr)) and 0 for 0 ms, in Python
+    floats; needs no library.  ValueError: a sampling rate or a time outside the limits."""
+    sr = sampling_rate
+    if isinstance(sr, bool) or not isinstance(sr, (int, np.integer)) or not EQ_SR_MIN <= sr <= EQ_SR_MAX:
+        raise ValueError('compressor: the sampling rate must be an integer in {} .. {}, got {!r}'.format(EQ_SR_MIN, EQ_SR_MAX, sr))
+    out = []
+    for what, ms in (('attack', attack_ms), ('release', release_ms)):
+        if not 0.0 <= ms <= CMP_MS_MAX:
+            raise ValueError('compressor: the {} of {!r} ms is not in 0 .. {:g}'.format(what, ms, CMP_MS_MAX))
+        out.append(0.0 if ms == 0 else math.exp(-1.0 / (ms * 1e-3 * sr)))
+    return tuple(out)
+
+
+def compressor_params_check(what, values):
+    """``(threshold_db, slope, knee_db, makeup_db, attack_coeff, release_coeff)`` as six floats, checked as tts_compress checks them"""
+    try:
+        T, slope, W, makeup, aA, aR = (float(v) for v in values)
+    except (TypeError, ValueError):
+        raise ValueError('{}: threshold_db, slope, knee_db, makeup_db, attack_coeff and release_coeff are needed, got {!r}'.format(what, values))
+    for name, v, lo, hi in (('threshold_db', T, CMP_THRESHOLD_MIN, CMP_THRESHOLD_MAX), ('slope', slope, 0.0, 1.0), ('knee_db', W, 0.0, CMP_KNEE_MAX),
+                            ('makeup_db', makeup, CMP_MAKEUP_MIN, CMP_MAKEUP_MAX)):
+        if not lo <= v <= hi:
+            raise ValueError('{}: {} = {!r} is not in {:g} .. {:g}'.format(what, name, v, lo, hi))
+    for name, v in (('attack_coeff', aA), ('release_coeff', aR)):
+        if not 0.0 <= v < 1.0:
+            raise ValueError('{}: {} = {!r} is not in [0, 1)'.format(what, name, v))
+    return (T, slope, W, makeup, aA, aR)
+
+
+def compressor_setting(compressor):
+    """``compressor`` of the synthesis calls -- None (the handle's setting as it stands), a profile name of ``CMP_PROFILES``, or
+    ``(threshold_db, ratio[, knee_db[, attack_ms[, release_ms[, makeup_db]]]])`` (ratio >= 1, inf allowed; 6 dB, 5 ms, 100 ms and
+    0 dB where left out) -- as what the mirror holds: None, ``('profile', name)``, ``('design', (T, ratio, knee, attack_ms,
+    release_ms, makeup))`` or, for coefficients made elsewhere, ``('params', (threshold_db, slope, knee_db, makeup_db, attack_coeff,
+    release_coeff))``.  ValueError before a handle is touched; the coefficients are made where the rate is known
+    (``compressor_params``)."""
+    if compressor is None:
+        return None
+    if isinstance(compressor, str):
+        if compressor not in CMP_PROFILES:
+            raise ValueError('compressor: no profile {!r} (there are: {})'.format(compressor, ', '.join(CMP_PROFILES)))
+        return ('profile', compressor)
+    if isinstance(compressor, tuple) and len(compressor) == 2 and compressor[0] in ('profile', 'design', 'params'):
+        if compressor[0] == 'params':
+            return ('params', compressor_params_check('compressor', compressor[1]))
+        return compressor_setting(compressor[1])   # (a checked value: checked again)
+    if not isinstance(compressor, (list, tuple)) or not 2 <= len(compressor) <= 6:
+        raise ValueError('compressor must be None, a profile name or (threshold_db, ratio[, knee_db[, attack_ms[, release_ms[, makeup_db]]]]), '
+                         'got {!r}'.format(compressor))
+    values = [CMP_DEFAULTS[i] if i >= len(compressor) or compressor[i] is None else compressor[i] for i in range(6)]
+    if any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) for v in values):
+        raise ValueError('compressor: threshold, ratio, knee, attack, release and make-up must be numbers, got {!r}'.format(compressor))
+    T, ratio, W, attack, release, makeup = (float(v) for v in values)
+    if not ratio >= 1.0:
+        raise ValueError('compressor: the ratio must be 1 or more (inf: a hard ceiling on the envelope), got {!r}'.format(ratio))
+    compressor_params_check('compressor', (T, 1.0 / ratio, W, makeup, 0.0, 0.0))
+    compressor_design(48000, attack, release)
+    return ('design', (T, ratio, W, attack, release, makeup))
+
+
+def compressor_params(setting, sampling_rate):
+    """the six parameters of a checked ``compressor_setting`` at a sampling rate"""
+    how, what = setting
+    if how == 'params':
+        return compressor_params_check('compressor', what)
+    T, ratio, W, attack, release, makeup = CMP_PROFILES[what] if how == 'profile' else what
+    aA, aR = compressor_design(sampling_rate, attack, release)
+    return compressor_params_check('compressor', (T, 1.0 / ratio, W, makeup, aA, aR))
 
 
 # The delivery formats (TTS_FMT_* of include/sstts_hip.h) by the names every layer above uses, the numpy type of a code and the
@@ -1453,6 +1549,14 @@ MARK_SETTINGS = (
 # peak normalisation and ahead of the loudness gain and the limiter, each utterance over the samples its row holds; a design is made
 # at the model's sampling rate.  Lengths, shapes and timing marks do not change (the group delay of a few samples is ignored); a
 # boost behind the peak normalisation can pass 1.0: give it a limiter or a loudness target.
+# ... and the dynamics, a fifth table, checked and applied AHEAD of the tone (the equaliser stays the last one set and the first
+# one put back): ``compressor`` -- a profile name of CMP_PROFILES or ``(threshold_db, ratio, knee_db, attack_ms, release_ms,
+# makeup_db)`` (tts_set_compressor, off unless ``set_compressor`` changed it): the call's rows go through ``compress`` in place,
+# behind the equaliser and ahead of the loudness gain and the limiter, each utterance over the samples its row holds; the
+# coefficients are made at the model's sampling rate.  Lengths, shapes and timing marks do not change.
+DYNAMICS_SETTINGS = (
+    Setting('compressor', '_compressor', None, compressor_setting, lambda engine, v: engine.set_compressor(v)),
+)
 TONE_SETTINGS = (
     Setting('equalizer', '_equalizer', None, equalizer_setting, lambda engine, v: engine.set_equalizer(v)),
 )
@@ -1466,7 +1570,7 @@ class _Settings(object):
 
     def __init__(self, engine, per_call):
         self.engine = engine
-        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + TONE_SETTINGS if row.keyword in per_call]
+        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS if row.keyword in per_call]
         self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
 
     def __getitem__(self, keyword):
@@ -1593,7 +1697,7 @@ class Engine(object):
 
     def _init_settings(self):
         """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
-        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + TONE_SETTINGS:
+        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS:
             setattr(self, row.mirror, row.initial)
 
     def _settings(self, **per_call):
@@ -1657,6 +1761,18 @@ class Engine(object):
             sos = equalizer_sections(setting, self.sampling_rate if sampling_rate is None else sampling_rate)
             self._check(self.lib.tts_set_equalizer(self.handle, 1, sos.ctypes.data_as(POINTER(ctypes.c_double)), len(sos)))
         self._equalizer = setting
+
+    def set_compressor(self, compressor, sampling_rate=None):
+        """tts_set_compressor: the handle's setting, read by every synthesize / synthesize_host call made after it.  ``compressor``:
+        None or False (off), or what ``compressor_setting`` reads -- a profile name or ``(threshold_db, ratio, knee_db, attack_ms,
+        release_ms, makeup_db)``; the coefficients are made at ``sampling_rate`` (None: the model's).  The library copies them."""
+        setting = compressor_setting(None if compressor is False else compressor)
+        if setting is None:
+            self._check(self.lib.tts_set_compressor(self.handle, 0, None))
+        else:
+            p = TtsCompressor(*compressor_params(setting, self.sampling_rate if sampling_rate is None else sampling_rate))
+            self._check(self.lib.tts_set_compressor(self.handle, 1, ctypes.addressof(p)))
+        self._compressor = setting
 
     def set_output(self, output):
         """tts_set_output: the handle's setting, read by every synthesize_host call made after it.  ``output``: None, False or
@@ -2255,6 +2371,44 @@ class Engine(object):
             out.shape = (n,)
         return out
 
+    # ------------------------------------------------------------------ the compressor
+    def compress(self, wavs, params, n_samples=None, out=None, envelope=False, stats=False):
+        """tts_compress: a feed-forward peak compressor over every utterance of ``wavs`` -- one mono waveform (n,) or a batch (B, n),
+        a host array or a device buffer.  ``params``: what ``compressor_setting`` reads -- a profile name, ``(threshold_db, ratio,
+        knee_db, attack_ms, release_ms, makeup_db)`` (coefficients made at the model's sampling rate) or ``('params', (threshold_db,
+        slope, knee_db, makeup_db, attack_coeff, release_coeff))``.  Returns a device array of the input's shape: ``out`` where one
+        is given (a device buffer of the input's size, which may be the input), else a device input compressed in place and handed
+        back, a host input uploaded first.  ``n_samples``: B lengths (host integers) -- samples at or behind them are neither read
+        nor written; None: all n.  ``envelope``: also a float64 device array (B, n), the detector's e of every sample (what lies at
+        or behind a row's length is not written); ``stats``: also a host array (B,) of ``COMPRESS_RECORD``.  The envelope is the
+        bits of tests/compressor_oracle.py."""
+        wavs, single, B, n, ns = self._ragged_waveforms('compress', wavs, n_samples)
+        setting = compressor_setting(params)
+        if setting is None:
+            raise ValueError('compress: parameters are needed')
+        p = TtsCompressor(*compressor_params(setting, self.sampling_rate))
+        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
+            raise ValueError('compress: out must be a device buffer of {} floats'.format(B * n))
+        fresh = out is None and not _is_device(wavs)
+        if fresh:
+            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
+            p_wav = out.data_ptr()
+        else:
+            p_wav, _k = self._in(wavs, np.float32)
+            out = wavs if out is None else out
+        env = self.empty((B, n), np.float64) if envelope else None
+        st = self.empty((B, 2), np.float64) if stats else None   # (B records of 16 bytes)
+        self._check_or_free(self.lib.tts_compress(self.handle, p_wav, out.data_ptr(), B, n, _int32_ptr(ns), ctypes.addressof(p),
+                                                  env.data_ptr() if envelope else None, st.data_ptr() if stats else None),
+                            out if fresh else None, env, st)
+        if fresh and single:
+            out.shape = (n,)
+        answer = (out,) + ((env,) if envelope else ())
+        if stats:
+            answer += (st.to_host().view(COMPRESS_RECORD).reshape(B),)
+            st.free()
+        return answer if len(answer) > 1 else out
+
     # ------------------------------------------------------------------ delivery formats
     def encode(self, wav, format, dither='tpdf', seed=0, n_samples=None):
         """tts_encode: float32 rows to delivery codes -- ``format`` 'pcm16' (int16), 'pcm8', 'mulaw' or 'alaw' (uint8) -- in one
@@ -2777,10 +2931,10 @@ class Engine(object):
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
-                   alignment_stats=None, limiter=None, token_times=None, equalizer=None, **refused):
+                   alignment_stats=None, limiter=None, token_times=None, equalizer=None, compressor=None, **refused):
         """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` to
-        ``limiter`` hold for this call alone, as SETTINGS has them, ``token_times`` as MARK_SETTINGS has it and ``equalizer`` as
-        TONE_SETTINGS has it.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
+        ``limiter`` hold for this call alone, as SETTINGS has them, ``token_times`` as MARK_SETTINGS has it, ``compressor`` as
+        DYNAMICS_SETTINGS and ``equalizer`` as TONE_SETTINGS have them.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
         call's rows stay on the device, where ``resample`` and ``encode`` take them."""
         if 'output' in refused:
             raise ValueError('synthesize: no output= here -- the waveforms stay on the device as float32; resample and encode them there '
@@ -2789,7 +2943,7 @@ class Engine(object):
             raise TypeError('synthesize() got an unexpected keyword argument {!r}'.format(sorted(refused)[0]))
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter,
-                              token_times=token_times, equalizer=equalizer)
+                              token_times=token_times, compressor=compressor, equalizer=equalizer)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call, o_call = call['speaking_rate'], call['pitch']
@@ -2841,7 +2995,7 @@ class Engine(object):
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
                         speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None,
-                        output=None, token_times=None, equalizer=None):
+                        output=None, token_times=None, equalizer=None, compressor=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
@@ -2849,10 +3003,10 @@ class Engine(object):
         made, not when its work runs.  A call made with an ``output`` is fetched with ``wait_host_encoded``, not ``wait_host``.  A call that stops at silence returns once its post-net has run (the lengths:
         ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``), and so do the
         timing marks of a call made with ``token_times`` (MARK_SETTINGS; ``wait_host_token_times``).  ``equalizer`` (TONE_SETTINGS)
-        holds for this call alone too."""
+        and ``compressor`` (DYNAMICS_SETTINGS) hold for this call alone too."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output,
-                              token_times=token_times, equalizer=equalizer)
+                              token_times=token_times, compressor=compressor, equalizer=equalizer)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape

@@ -16,12 +16,13 @@ synthesis calls (tts_set_pitch), which stretches the call's magnitudes and resam
 one gain takes a waveform to a target integrated loudness after ITU-R BS.1770-4 (tts_loudness_normalize); the loudness of
 synthesis is the ``loudness`` argument of the synthesis calls (tts_set_loudness).  ``limit`` is the look-ahead peak limiter behind
 it (tts_limit; the ``limiter`` argument of the synthesis calls, tts_set_limiter).  ``equalize`` shapes the spectrum with a cascade
-of second-order sections (tts_equalize; the ``equalizer`` argument of the synthesis calls, tts_set_equalizer)."""
+of second-order sections (tts_equalize; the ``equalizer`` argument of the synthesis calls, tts_set_equalizer), and ``compress``
+lowers the crest factor with a feed-forward peak compressor (tts_compress; the ``compressor`` argument, tts_set_compressor)."""
 import numpy as np
 
 from . import default_engine
 from .conversion import ms_to_samples
-from .._hip import equalizer_sections, equalizer_setting, limiter_lookahead
+from .._hip import compressor_params, compressor_setting, equalizer_sections, equalizer_setting, limiter_lookahead
 
 
 def pitch_shift(wav, sampling_rate, octaves, preserve_formants=False, n_iter=25, seed=0, engine=None):
@@ -80,6 +81,22 @@ def equalize(wav, sampling_rate, equalizer, engine=None):
         raise ValueError('equalize: an equalizer is needed')
     eng = engine or default_engine()
     out = eng.equalize(np.asarray(wav, dtype=np.float32), equalizer_sections(setting, eng.sampling_rate if sampling_rate is None else int(sampling_rate)))
+    host = out.to_host()
+    out.free()
+    return host
+
+
+def compress(wav, sampling_rate, compressor, engine=None):
+    """``wav`` -- one mono waveform (n,) or a batch (B, n) -- through a feed-forward peak compressor (``Engine.compress``).
+    ``compressor``: a profile name -- 'speech', 'telephony', 'small-speaker'; every preset is untuned -- or ``(threshold_db, ratio[,
+    knee_db[, attack_ms[, release_ms[, makeup_db]]]])``; the attack and release become coefficients at ``sampling_rate`` (None: the
+    engine's).  The length does not change.  Returns a float32 host array of the input's shape."""
+    setting = compressor_setting(compressor)
+    if setting is None:
+        raise ValueError('compress: a compressor is needed')
+    eng = engine or default_engine()
+    params = compressor_params(setting, eng.sampling_rate if sampling_rate is None else int(sampling_rate))
+    out = eng.compress(np.asarray(wav, dtype=np.float32), ('params', params))
     host = out.to_host()
     out.free()
     return host

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import attention_check, marks as marks_, prosody
 from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, RESAMPLE_SEGMENTS_MAX_RATIOS, shift_step,
-                    equalizer_sections, equalizer_setting, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
+                    compressor_params, compressor_setting, equalizer_sections, equalizer_setting, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
                     output_setting, phase_init_value, pitch_octaves_value, pitch_semitones_value, resampled_length,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting, synth_frame_counts, token_times_jump)
 from ..audio.conversion import ms_to_samples
@@ -183,7 +183,7 @@ def deliver(engine, wavs, setting, seed=0, norm=False, what='utterance'):
 class SynthSettings(object):
     """The synthesis settings every helper of this layer takes, checked once -- ValueError before an engine is touched, in the
     order of ``_hip.SETTINGS`` -- and kept as the checked values ``momentum``, ``stop``, ``rate``, ``octaves``, ``phase_init``,
-    ``loud``, ``check_alignment``, ``limiter``, ``output`` (``output_of``) and ``equalizer``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
+    ``loud``, ``check_alignment``, ``limiter``, ``output`` (``output_of``), ``compressor`` and ``equalizer``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
 
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind its last frame whose loudest bin is above that many
@@ -221,7 +221,12 @@ class SynthSettings(object):
     'highshelf') or an (S, 5) array of second-order sections: a cascade of up to 8 biquads (``Engine.equalize``) shapes the
     spectrum of every utterance on the device, behind Griffin-Lim, the pitch and the peak normalisation and ahead of the loudness
     gain and the limiter.  Lengths and timing marks do not change (the group delay of a few samples is ignored).  A boost behind
-    the peak normalisation can pass 1.0: give it a limiter or a loudness target."""
+    the peak normalisation can pass 1.0: give it a limiter or a loudness target.
+    ``compressor`` (taken by ``SynthSettings.of`` too): None (the engine's setting), a profile name -- 'speech', 'telephony',
+    'small-speaker'; every preset is untuned -- or ``(threshold_db, ratio[, knee_db[, attack_ms[, release_ms[, makeup_db]]]])``: a
+    feed-forward peak compressor (``Engine.compress``) lowers the crest factor of every utterance on the device, behind the
+    equaliser and ahead of the loudness gain and the limiter.  Lengths and timing marks do not change.  A make-up gain behind the
+    peak normalisation can pass 1.0: give it a limiter or a loudness target."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
                  phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None,
@@ -241,15 +246,21 @@ class SynthSettings(object):
         self.marks = marks_.marks_kind(marks)
         self.marks_max_jump = token_times_jump(marks_max_jump, 'marks_max_jump')
         self.equalizer = None
+        self.compressor = None
 
     @classmethod
     def of(cls, hp, equalizer=None, **settings):
-        """The record of a helper's ``**settings``: the constructor's keywords and, checked behind them, the tone keywords
-        (TONE_KEYWORDS; ``_hip.TONE_SETTINGS`` is likewise a table behind the others) -- ``equalizer``, refused here too where a
-        corner does not fit the model's sampling rate."""
+        """The record of a helper's ``**settings``: the constructor's keywords and, checked behind them, the dynamics keywords
+        (DYNAMICS_KEYWORDS: ``compressor``, read out of ``settings``) and then the tone keywords (TONE_KEYWORDS;
+        ``_hip.DYNAMICS_SETTINGS`` and ``_hip.TONE_SETTINGS`` are likewise tables behind the others) -- ``equalizer``, refused
+        here too where a corner does not fit the model's sampling rate."""
+        compressor = settings.pop('compressor', None)
         s = cls(hp, **settings)
+        s.compressor = compressor_setting(compressor)
         s.equalizer = equalizer_setting(equalizer)
         rate = getattr(getattr(hp, 'hparams', hp), 'sampling_rate', None)
+        if s.compressor is not None and rate:
+            compressor_params(s.compressor, int(rate))
         if s.equalizer is not None and rate:
             equalizer_sections(s.equalizer, int(rate))
         return s
@@ -259,7 +270,7 @@ class SynthSettings(object):
         return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
                     phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None,
                     limiter=self.limiter, token_times=(True, pad_id(), self.marks_max_jump) if self.marks else None,
-                    equalizer=self.equalizer)
+                    compressor=self.compressor, equalizer=self.equalizer)
 
     def host_keywords(self):
         """... and as ``Engine.synthesize_host`` alone takes them: with the delivery format"""
@@ -270,7 +281,7 @@ class SynthSettings(object):
         ``check_alignment``, ``output`` and the marks"""
         return dict(momentum=self.momentum, stop_at_silence_db=self.stop_at_silence_db, silence_keep_ms=self.silence_keep_ms,
                     speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter,
-                    equalizer=self.equalizer)
+                    compressor=self.compressor, equalizer=self.equalizer)
 
     def file_norm(self):
         """the peak normalisation of the file helpers, ``(on the device, in save_wav)``: none with a loudness or a limiter, else
@@ -280,7 +291,8 @@ class SynthSettings(object):
 
 
 TONE_KEYWORDS = tuple(inspect.signature(SynthSettings.of).parameters)[1:-1]      # ('equalizer',)
-SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:] + TONE_KEYWORDS
+DYNAMICS_KEYWORDS = ('compressor',)                                              # ahead of the tone, as _hip.DYNAMICS_SETTINGS is
+SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:] + DYNAMICS_KEYWORDS + TONE_KEYWORDS
 
 
 def takes_settings(*refuses, only=None):
@@ -313,6 +325,7 @@ def takes_settings(*refuses, only=None):
         functools.update_wrapper(helper, parts)
         own = [p for p in inspect.signature(parts).parameters.values() if p.kind is not p.VAR_KEYWORD]
         record = dict(inspect.signature(SynthSettings.__init__).parameters, **{k: inspect.signature(SynthSettings.of).parameters[k] for k in TONE_KEYWORDS})
+        record.update({k: inspect.Parameter(k, inspect.Parameter.KEYWORD_ONLY, default=None) for k in DYNAMICS_KEYWORDS})
         helper.__signature__ = inspect.Signature(own + [record[k].replace(kind=inspect.Parameter.KEYWORD_ONLY)
                                                         for k in SETTING_KEYWORDS if k not in refuses])
         helper.parts = parts
@@ -347,17 +360,21 @@ def finishing_tail(caller, s, sampling_rate, deliver=True):
     """The tail behind a Griffin-Lim that a helper composes of stand-alone stages.  The limiter's look-ahead becomes samples here,
     before an engine is touched (ValueError that names ``caller``); the function returned then runs, on device rows (B, N) that
     hold ``held[b]`` samples each (None: all N), a peak normalisation (``peak_normalize``, where there is no ``loudness``), the
-    ``equalizer`` (its sections are made here too, at ``sampling_rate``), the ``loudness``, the ``limiter``,
+    ``equalizer`` (its sections are made here too, at ``sampling_rate``), the ``compressor`` (its coefficients likewise; an
+    engine's ``compress`` is not touched without one), the ``loudness``, the ``limiter``,
     and hands back ``deliver_rows`` for an ``output`` (with ``deliver``; the dither's ``seed``) or else the rows downloaded, a list
     of B arrays cut to what they hold.  ``rows`` stays the caller's to free."""
     lookahead = None if s.limiter is None else limiter_lookahead(caller, s.limiter[1], sampling_rate)
     sections = None if s.equalizer is None else equalizer_sections(s.equalizer, sampling_rate)
+    dynamics = None if s.compressor is None else ('params', compressor_params(s.compressor, sampling_rate))
 
     def finish(engine, rows, held, seed=0, peak_normalize=False):
         if s.loud is None and peak_normalize:
             engine.peak_normalize(rows)
         if sections is not None:
             engine.equalize(rows, sections, n_samples=held)
+        if dynamics is not None:
+            engine.compress(rows, dynamics, n_samples=held)
         if s.loud is not None:
             engine.loudness_normalize(rows, sampling_rate, s.loud[0], s.loud[1], n_samples=held)
         if s.limiter is not None:
@@ -904,7 +921,8 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     either edge, and one ``Engine.join`` per call lays the pieces of each text into one row on the device.  With a ``loudness``
     one ``Engine.loudness_normalize`` runs over the joined rows, so a text is levelled as a whole and its sentences keep their
     relative levels; with a ``limiter`` one ``Engine.limit`` runs over the joined rows behind it, and with an ``equalizer`` one
-    ``Engine.equalize`` ahead of both.  Only the n_out[g] samples of a row that were said are downloaded.
+    ``Engine.equalize`` and with a ``compressor`` one ``Engine.compress`` ahead of both, in that order: a text is compressed as a
+    whole, after the join.  Only the n_out[g] samples of a row that were said are downloaded.
 
     A text whose pieces span several calls is concatenated on the host, with the pause behind the earlier part as zeros between
     them; with a ``loudness`` each part is levelled on its own.  The packing decides which pieces share a call, a call's seed
@@ -939,7 +957,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     for k, (p0, ids) in enumerate(calls):
         B = ids.shape[0]
         out = eng.synthesize(ids, *c.synth, seed=seed + k, peak_normalize=False, want_linear=True,
-                             **dict(s.engine_keywords(), loudness=None, limiter=None, equalizer=None))   # (all three run on the joined rows)
+                             **dict(s.engine_keywords(), loudness=None, limiter=None, equalizer=None, compressor=None))   # (all four run on the joined rows)
         first_active = eng.speech_interval(out['linear'], threshold)[0].to_host()
         if s.check_alignment:
             records.append(eng.synth_alignment_stats(B))
@@ -1044,6 +1062,7 @@ def main(argv=None):
                                                             [--phase-init random|estimate]
                                                             [--loudness LUFS [--max-peak P]]
                                                             [--eq PROFILE|kind:f0[:q][:gain_db],...]
+                                                            [--compress PROFILE|T:R[:knee[:attack[:release[:makeup]]]]]
                                                             [--limit DB [--limit-lookahead-ms MS] [--sample-peak]]
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
@@ -1065,6 +1084,11 @@ def main(argv=None):
     ``rumble``, ``bright``, ``warm``; every preset is untuned -- or up to 8 sections ``kind:f0[:q][:gain_db]`` separated by commas,
     kinds lowpass, highpass, peak, lowshelf, highshelf, e.g. ``--eq highpass:120,peak:3000:1.0:+3,highshelf:6000:+2``.  A boost can
     take samples beyond 1: give it ``--limit`` or ``--loudness``.
+    ``--compress``: a feed-forward peak compressor lowers the crest factor of every wav behind the equaliser and ahead of the
+    loudness gain and the limiter: a profile -- ``speech``, ``telephony``, ``small-speaker``; every preset is untuned -- or
+    ``T:R[:knee[:attack[:release[:makeup]]]]``: the threshold in dB re full scale, the ratio (``inf`` allowed), the knee's width in
+    dB (6), the attack and release in ms (5 and 100) and the make-up gain in dB (0), e.g. ``--compress=-18:3:6:5:100:3`` (with the equals sign: the value begins with a minus).  A make-up
+    gain can take samples beyond 1: give it ``--limit`` or ``--loudness``.
     ``--limit DB``: a look-ahead peak limiter runs last over every wav: no peak above DB decibels relative to full scale (e.g.
     -1), looking ``--limit-lookahead-ms`` ahead (default 5); the ceiling holds for the interpolated (true) peaks, with
     ``--sample-peak`` for the samples alone.  The files are then not peak-normalised.  With ``--loudness`` and no ``--max-peak``
@@ -1132,7 +1156,22 @@ def settings_option(args):
                 speaking_rate=args.rate, pitch_semitones=args.pitch, phase_init=args.phase_init,
                 loudness=None if args.loudness is None else (args.loudness, args.max_peak), check_alignment=args.check_alignment,
                 limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
-                output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump, equalizer=eq_option(args.eq))
+                output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump, equalizer=eq_option(args.eq),
+                compressor=compress_option(args.compress))
+
+
+def compress_option(text):
+    """``--compress`` as the ``compressor`` of the helpers above: None, a profile name, or ``T:R[:knee[:attack[:release[:makeup]]]]``
+    as a tuple of numbers.  ValueError names the field."""
+    if text is None or ':' not in text:
+        return text
+    fields = text.split(':')
+    if not 2 <= len(fields) <= 6:
+        raise ValueError('--compress: {!r}: T:R[:knee[:attack[:release[:makeup]]]] is needed'.format(text))
+    try:
+        return tuple(float(v) for v in fields)
+    except ValueError:
+        raise ValueError('--compress: {!r}: the fields must be numbers'.format(text))
 
 
 def eq_option(text):
@@ -1194,6 +1233,9 @@ def parse_args(argv=None):
     ap.add_argument('--eq', default=None, metavar='PROFILE|SECTIONS',
                     help='an equaliser ahead of the loudness gain and the limiter: a profile (telephony, small-speaker, rumble, bright, warm; '
                          'untuned) or sections kind:f0[:q][:gain_db], e.g. highpass:120,peak:3000:1.0:+3,highshelf:6000:+2')
+    ap.add_argument('--compress', default=None, metavar='PROFILE|T:R[:KNEE[:ATTACK[:RELEASE[:MAKEUP]]]]',
+                    help='a peak compressor behind the equaliser, ahead of the loudness gain and the limiter: a profile (speech, telephony, '
+                         'small-speaker; untuned) or threshold dB : ratio [: knee dB : attack ms : release ms : make-up dB], e.g. --compress=-18:3:6:5:100:3')
     ap.add_argument('--limit', type=float, default=None, metavar='DB',
                     help='a look-ahead peak limiter behind everything else: no peak above DB decibels re full scale, e.g. -1')
     ap.add_argument('--limit-lookahead-ms', type=float, default=LIMIT_LOOKAHEAD_MS, metavar='MS',

@@ -32,7 +32,8 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, **
     ``Engine.speech_frames`` on the normalised spectrograms, then one ragged Griffin-Lim call, every utterance returned at its own
     length; with a ``speaking_rate`` or a ``pitch`` ``Engine.stretch_magnitudes`` by rate * 2 ** -pitch ahead of Griffin-Lim
     (``init_phase`` has that many frames; lengths min(T', max(min_frames, ceil(n / rate)))) and ``Engine.resample`` by 2 ** -pitch
-    behind it; with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
+    behind it; with an ``equalizer`` ``Engine.equalize`` and with a ``compressor`` ``Engine.compress`` behind it, in that order;
+    with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
     last, over the same samples."""
     s = SynthSettings.of(model_params, **settings)
     stop, rate, octaves = s.stop, s.rate, s.octaves

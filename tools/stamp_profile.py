@@ -4,7 +4,12 @@
     python tools/stamp_profile.py gpurun_out/r04/x.json profiles/r04_x.json
 
 `commit` = git HEAD of this checkout (the GPU box has no .git); refuses when the record's kernel_sha16 is not the hash of
-the Griffin-Lim sources of this tree (the record would be refused by bench.py anyway)."""
+the Griffin-Lim sources of this tree (the record would be refused by bench.py anyway).
+
+A text record (.txt: a table printed by the tests or a tool) is copied behind one line that names the commit of the library
+sources it was measured on:
+
+    python tools/stamp_profile.py gru_step_table.txt profiles/gru_step.txt"""
 import json
 import os
 import subprocess
@@ -15,11 +20,24 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 src, dst = sys.argv[1], sys.argv[2]
+
+
+def head_commit():
+    commit = subprocess.check_output(['git', '-C', ROOT, 'rev-parse', 'HEAD']).decode().strip()
+    if subprocess.check_output(['git', '-C', ROOT, 'status', '--porcelain', '--', 'single-speaker-tts_amd/csrc']).decode().strip():
+        commit += ' + uncommitted changes under csrc/'
+    return commit
+
+
+if src.endswith('.txt'):
+    with open(dst, 'w') as f:
+        f.write('library sources (csrc/): commit {}\n'.format(head_commit()))
+        f.write(open(src).read())
+    print(dst, head_commit())
+    sys.exit(0)
 rec = json.load(open(src))
 if rec.get('kernel_sha16') != bench.gl_kernel_sha16():
     raise SystemExit('{}: kernel_sha16 {} != {} of this tree'.format(src, rec.get('kernel_sha16'), bench.gl_kernel_sha16()))
-rec['commit'] = subprocess.check_output(['git', '-C', ROOT, 'rev-parse', 'HEAD']).decode().strip()
-if subprocess.check_output(['git', '-C', ROOT, 'status', '--porcelain', '--', 'single-speaker-tts_amd/csrc']).decode().strip():
-    rec['commit'] += ' + uncommitted changes under csrc/'
+rec['commit'] = head_commit()
 json.dump(rec, open(dst, 'w'), indent=1)
 print(dst, rec['commit'], rec['kernel_sha16'])

@@ -806,6 +806,77 @@ int tts_compressor_design(int sampling_rate, double attack_ms, double release_ms
  * TTS_ERR_INVALID: an unknown name, a NULL pointer. */
 int tts_compressor_profile(const char* name, int sampling_rate, tts_compressor_t* params_out);
 
+/* ---- the audio watermark: a keyed spread-spectrum carrier, embedded and detected -------------- */
+/* The parameters of both stages, by value.  key: any 64 bits.  payload: its low payload_bits bits travel.  payload_bits = P in
+ * 1 .. 32.  chip = L, the samples of a chip, even, 2 .. 16.  chips_per_symbol = C in 1 .. 65536.  strength = G in 0 .. 0.25, the
+ * carrier's amplitude as a fraction of the local envelope (the detector does not read it, and checks it all the same).  The
+ * defaults of the layers above -- L = 8, C = 64, P = 16, G = 0.02 -- are UNTUNED: no trained checkpoint was at hand and nobody has
+ * listened. */
+typedef struct {
+    uint64_t key;
+    uint32_t payload;
+    int32_t payload_bits;
+    int32_t chip;
+    int32_t chips_per_symbol;
+    double strength;
+} tts_watermark_t;
+/* What tts_watermark_embed can tell of a row: the samples it held, those that were marked (finite, under a non-zero G e) and the
+ * largest |out| among the samples it held (NaN passed over). */
+typedef struct {
+    int32_t n;
+    int32_t marked;
+    float peak_out;
+    int32_t spare;
+} tts_watermark_embed_stats_t;
+/* What tts_watermark_detect says of a row: the lowest offset d with the largest T, the samples the row held, score = T[offset],
+ * energy = E[offset], and the payload read there (bit j set where S[offset][j] < 0). */
+typedef struct {
+    int32_t offset;
+    int32_t n;
+    int64_t score;
+    int64_t energy;
+    uint32_t payload;
+    uint32_t spare;
+} tts_watermark_detect_t;
+/* The carrier at position p >= 0, the same for every row (a detector need not know which row it holds):
+ *   q = p / L, u = q / C, j = u mod P
+ *   c(q) = +1 where bit 63 of splitmix64's finaliser of key + 0x9E3779B97F4A7C15 (q + 1) is 0, else -1
+ *   m(t) = +1 for t < L / 2, else -1        no DC, a peak near fs / L: in the telephone band for L = 8 at 22 050 Hz
+ *   s(p) = c(q) m(p mod L) (1 - 2 bit_j(payload))
+ * The block envelope of a row, blocks of 64 samples from its first: E[k] the largest |x| of the finite samples of block k (0
+ * where there is none or the block lies outside the row), e[i] = min(E[k - 1], E[k], E[k + 1]) for the block k that holds i --
+ * so the first and the last block of a row carry no mark, nor does the block ahead of an onset.
+ * Embed: out[i] = float32(double(wav[i]) + (G double(e[i])) s(i)), every double operation individually rounded and one rounding
+ * to float32.  A sample that is not finite, and one with G e[i] == 0 (-0.0 and everything at or behind n_samples[b] among
+ * them), comes back as its own bits.  The result is the bits of tests/watermark_oracle.py.
+ * out may equal wav (in place: only marked samples are written); any other overlap is refused; apart, every element of out is
+ * written exactly once.  An utterance's result is the bits of its B = 1 call.  n_samples: HOST [B] lengths in 0 .. N, or NULL
+ * (all N).  stats: DEVICE [B] records, or NULL.  Asynchronous on the handle's stream, no host wait, nothing uploaded, no
+ * atomics: two launches per 64 utterances, a third where records are asked for.  Profile stage "watermark".
+ * TTS_ERR_INVALID, before anything is enqueued, in this order: a NULL wav, out or params; B or N < 1; an n_samples[b] outside
+ * 0 .. N; a parameter outside its range (payload_bits, chip, chips_per_symbol, strength, in that order); a wav or out that is
+ * not 4-byte aligned; out overlapping wav without being equal to it. */
+int tts_watermark_embed(tts_handle_t h, const float* wav /* [B][N] */, float* out /* [B][N]; may equal wav */, int B, int N,
+                        const int32_t* n_samples /* HOST [B] or NULL */, const tts_watermark_t* params /* HOST, read before the call returns */,
+                        tts_watermark_embed_stats_t* stats /* [B] or NULL */);
+/* The search for the carrier in received rows that may have lost their first samples: D candidate offsets d = 0 .. D - 1, d the
+ * carrier position of the row's first sample.  With e_r the block envelope of the received row r:
+ *   v[i]    = clamp(rint(64 double(r[i]) / double(e_r[i])), -127, 127), ties to even; 0 where r[i] is not finite or e_r[i] == 0
+ *   a_q(d)  = the sum of v[i] m((i + d) mod L) over the samples with (i + d) / L == q
+ *   S[d][j] = the sum of c(q) a_q(d) over the chips of bit j;  E[d] = the sum of a_q(d)^2;  T[d] = the sum over j of |S[d][j]|
+ * all of them integers, exact in int64, whatever the order.  records: DEVICE [B].  scores: DEVICE [B][D] int64, all of T, or
+ * NULL.  sums: DEVICE [B][P] int64, S[offset][:], or NULL.  The chip sums are made once per phase d mod L and cross-correlated
+ * with the signs, about N D / L multiply-adds a row (csrc/watermark.hip); the argmax runs on the device.  Asynchronous on the
+ * handle's stream, no host wait, nothing uploaded: one launch and five per 64 utterances.  Profile stage "watermark".
+ * TTS_ERR_INVALID, before anything is enqueued, in this order: a NULL wav, records or params; B or N < 1; an n_samples[b] outside
+ * 0 .. N; a parameter outside its range, as above; D outside 1 .. tts_watermark_max_offsets(); a wav that is not 4-byte
+ * aligned; records, scores or sums that are not 8-byte aligned. */
+int tts_watermark_detect(tts_handle_t h, const float* wav /* [B][N] */, int B, int N, const int32_t* n_samples /* HOST [B] or NULL */,
+                         const tts_watermark_t* params /* HOST, read before the call returns */, int D,
+                         tts_watermark_detect_t* records /* [B] */, int64_t* scores /* [B][D] or NULL */, int64_t* sums /* [B][P] or NULL */);
+/* Host only: the largest D, 4096. */
+int tts_watermark_max_offsets(void);
+
 /* ---- attention diagnostics: alignment statistics ------------------------------------------- */
 /* What the decoder's alignments say about whether the sentence was read (no reference counterpart: the reference plots its
  * alignments, tacotron/model.py:552-598, and judges them by eye).  alignments DEVICE [n_steps_max][B][Ts] as the decoder
@@ -1276,6 +1347,17 @@ int tts_set_equalizer(tts_handle_t h, int enabled, const double* sos /* HOST [n_
  * its range). */
 int tts_set_compressor(tts_handle_t h, int enabled, const tts_compressor_t* params);
 
+/* The watermark of synthesis (tts_watermark_embed).  A setting of the HANDLE, off by default and read when a call is made; off is
+ * the call as it always was, launch for launch.  With enabled != 0, tts_synthesize and tts_synthesize_host run
+ * tts_watermark_embed(params) in place on the call's rows -- behind the compressor, ahead of the loudness normaliser and the
+ * limiter, so the two gains scale the mark with the speech and the limiter's ceiling stays exact -- on the call's stream, with no
+ * host wait, over the samples each row holds (the lengths the loudness setting uses).  The parameters are copied.  The result is
+ * the bits of the same call made with the setting off followed by tts_watermark_embed on those rows.  Lengths, shapes and timing
+ * marks do not change.  The first call after the setting was switched on is not pipelined (its buffers are new).
+ * With enabled == 0 params is not looked at.  The setting stays as it was on TTS_ERR_INVALID (a NULL params, a parameter outside
+ * its range). */
+int tts_set_watermark(tts_handle_t h, int enabled, const tts_watermark_t* params);
+
 /* Attention diagnostics of synthesis: the alignment statistics of every call (tts_alignment_stats).  A setting of the HANDLE,
  * off by default and read when a call is made; off is the call as it always was, launch for launch.  With enabled != 0,
  * tts_synthesize and tts_synthesize_host run tts_text_lengths(pad_id) on the call's device ids behind its encoder and
@@ -1360,7 +1442,8 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * stand-alone or inside a tts_synthesize call with tts_set_limiter on), "encode" (tts_encode, stand-alone or inside a
  * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes), "shift" (tts_shift_magnitudes), "equalize" (tts_equalize,
  * stand-alone or inside a tts_synthesize call with tts_set_equalizer on), "compress" (tts_compress, stand-alone or inside a
- * tts_synthesize call with tts_set_compressor on).
+ * tts_synthesize call with tts_set_compressor on), "watermark" (tts_watermark_embed, tts_watermark_detect, stand-alone or the
+ * embedder inside a tts_synthesize call with tts_set_watermark on).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

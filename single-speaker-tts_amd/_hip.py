@@ -263,6 +263,10 @@ _PROTOTYPES = {
     'tts_compressor_design': (c_int, [c_int, ctypes.c_double, ctypes.c_double, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     'tts_compressor_profile': (c_int, [c_char_p, c_int, c_void_p]),
     'tts_set_compressor': (c_int, [c_void_p, c_int, c_void_p]),
+    'tts_watermark_embed': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p]),
+    'tts_watermark_detect': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'tts_watermark_max_offsets': (c_int, []),
+    'tts_set_watermark': (c_int, [c_void_p, c_int, c_void_p]),
     'tts_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
     'tts_encode_width': (c_int, [c_int]),
     'tts_encode_tile': (c_int, []),
@@ -895,6 +899,71 @@ def compressor_params(setting, sampling_rate):
     T, ratio, W, attack, release, makeup = CMP_PROFILES[what] if how == 'profile' else what
     aA, aR = compressor_design(sampling_rate, attack, release)
     return compressor_params_check('compressor', (T, 1.0 / ratio, W, makeup, aA, aR))
+
+
+# ---- the watermark (csrc/watermark_plan.h): the limits of its parameters.  The defaults are UNTUNED: no trained checkpoint was at
+# hand and nobody has listened -- they say neither that the mark is inaudible nor that it survives a given channel.
+WM_BITS_MAX = 32
+WM_CHIP_MIN, WM_CHIP_MAX = 2, 16
+WM_SYMBOL_MAX = 65536
+WM_STRENGTH_MAX = 0.25
+WM_MAX_OFFSETS = 4096
+WM_DEFAULTS = (None, 0, 16, 8, 64, 0.02)     # what a short tuple leaves out: payload, payload_bits, chip, chips_per_symbol, strength
+# The detection threshold on zeta, measured on the CPU oracle (tests/test_watermark_host.py): 1.5 times the largest
+# zeta of 200 wrong keys on every signal of tests/watermark_cases.py at D = 64
+WM_THRESHOLD = 6.6
+WATERMARK_EMBED_RECORD = np.dtype([('n', np.int32), ('marked', np.int32), ('peak_out', np.float32), ('spare', np.int32)])
+WATERMARK_DETECT_RECORD = np.dtype([('offset', np.int32), ('n', np.int32), ('score', np.int64), ('energy', np.int64), ('payload', np.uint32),
+                                    ('spare', np.uint32)])
+
+
+class TtsWatermark(ctypes.Structure):
+    """tts_watermark_t"""
+    _fields_ = [('key', ctypes.c_uint64), ('payload', ctypes.c_uint32), ('payload_bits', c_int32), ('chip', c_int32),
+                ('chips_per_symbol', c_int32), ('strength', ctypes.c_double)]
+
+
+def watermark_setting(watermark):
+    """``watermark`` of the synthesis calls and of ``watermark_embed`` / ``watermark_detect`` -- None (the handle's setting as it
+    stands), a key (an integer in 0 .. 2^64 - 1), ``(key, payload)`` or ``(key, payload, payload_bits, chip, chips_per_symbol,
+    strength)`` (16 bits, 8 samples a chip, 64 chips a symbol and 0.02 where left out: UNTUNED defaults) -- as what the mirror
+    holds: None or the six values, checked as tts_watermark_embed checks them.  ValueError before a handle is touched."""
+    if watermark is None:
+        return None
+    values = (watermark,) if isinstance(watermark, (int, np.integer)) and not isinstance(watermark, (bool, np.bool_)) else watermark
+    if not isinstance(values, (list, tuple)) or not 1 <= len(values) <= 6:
+        raise ValueError('watermark must be None, a key, (key, payload) or (key, payload, payload_bits, chip, chips_per_symbol, strength), '
+                         'got {!r}'.format(watermark))
+    values = [WM_DEFAULTS[i] if i >= len(values) or values[i] is None else values[i] for i in range(6)]
+    for name, v in zip(('key', 'payload', 'payload_bits', 'chip', 'chips_per_symbol'), values):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError('watermark: {} must be an integer, got {!r}'.format(name, v))
+    key, payload, P, L, C = (int(v) for v in values[:5])
+    G = values[5]
+    if isinstance(G, (bool, np.bool_)) or not isinstance(G, (int, float, np.integer, np.floating)):
+        raise ValueError('watermark: strength must be a number, got {!r}'.format(G))
+    if not 0 <= key < 2 ** 64:
+        raise ValueError('watermark: key = {!r} is not in 0 .. 2^64 - 1'.format(key))
+    if not 0 <= payload < 2 ** 32:
+        raise ValueError('watermark: payload = {!r} is not in 0 .. 2^32 - 1'.format(payload))
+    for name, v, lo, hi in (('payload_bits', P, 1, WM_BITS_MAX), ('chip', L, WM_CHIP_MIN, WM_CHIP_MAX), ('chips_per_symbol', C, 1, WM_SYMBOL_MAX)):
+        if not lo <= v <= hi:
+            raise ValueError('watermark: {} = {!r} is not in {} .. {}'.format(name, v, lo, hi))
+        if name == 'chip' and v % 2:
+            raise ValueError('watermark: chip = {!r} is not even'.format(v))
+    if not 0.0 <= float(G) <= WM_STRENGTH_MAX:
+        raise ValueError('watermark: strength = {!r} is not in 0 .. {:g}'.format(G, WM_STRENGTH_MAX))
+    return (key, payload, P, L, C, float(G))
+
+
+def watermark_zeta(score, energy, payload_bits):
+    """the detection statistic of a record: (score - sqrt(2 P energy / pi)) / sqrt(energy (1 - 2 / pi)) -- with no mark every
+    S[j] is about normal with variance energy / P, so the score is a sum of P half-normals of total variance energy.  0.0 where the
+    energy is 0."""
+    score, energy = float(score), float(energy)
+    if energy <= 0.0:
+        return 0.0
+    return (score - math.sqrt(2.0 * payload_bits * energy / math.pi)) / math.sqrt(energy * (1.0 - 2.0 / math.pi))
 
 
 # The delivery formats (TTS_FMT_* of include/sstts_hip.h) by the names every layer above uses, the numpy type of a code and the
@@ -1554,6 +1623,13 @@ MARK_SETTINGS = (
 # makeup_db)`` (tts_set_compressor, off unless ``set_compressor`` changed it): the call's rows go through ``compress`` in place,
 # behind the equaliser and ahead of the loudness gain and the limiter, each utterance over the samples its row holds; the
 # coefficients are made at the model's sampling rate.  Lengths, shapes and timing marks do not change.
+# ... and the watermark, a table of its own ahead of the dynamics (checked and applied behind the timing marks): ``watermark`` -- a
+# key, ``(key, payload)`` or the full tuple of ``watermark_setting`` (tts_set_watermark, off unless ``set_watermark`` changed it):
+# the call's rows go through ``watermark_embed`` in place, behind the compressor and ahead of the loudness gain and the limiter, each
+# utterance over the samples its row holds.  Lengths, shapes and timing marks do not change.  The defaults are UNTUNED.
+WATERMARK_SETTINGS = (
+    Setting('watermark', '_watermark', None, watermark_setting, lambda engine, v: engine.set_watermark(v)),
+)
 DYNAMICS_SETTINGS = (
     Setting('compressor', '_compressor', None, compressor_setting, lambda engine, v: engine.set_compressor(v)),
 )
@@ -1570,7 +1646,7 @@ class _Settings(object):
 
     def __init__(self, engine, per_call):
         self.engine = engine
-        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS if row.keyword in per_call]
+        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + WATERMARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS if row.keyword in per_call]
         self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
 
     def __getitem__(self, keyword):
@@ -1697,7 +1773,7 @@ class Engine(object):
 
     def _init_settings(self):
         """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
-        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS:
+        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + WATERMARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS:
             setattr(self, row.mirror, row.initial)
 
     def _settings(self, **per_call):
@@ -1773,6 +1849,18 @@ class Engine(object):
             p = TtsCompressor(*compressor_params(setting, self.sampling_rate if sampling_rate is None else sampling_rate))
             self._check(self.lib.tts_set_compressor(self.handle, 1, ctypes.addressof(p)))
         self._compressor = setting
+
+    def set_watermark(self, watermark):
+        """tts_set_watermark: the handle's setting, read by every synthesize / synthesize_host call made after it.  ``watermark``:
+        None or False (off), or what ``watermark_setting`` reads -- a key, ``(key, payload)`` or ``(key, payload, payload_bits, chip,
+        chips_per_symbol, strength)``.  The library copies the parameters.  The defaults are UNTUNED."""
+        setting = watermark_setting(None if watermark is False else watermark)
+        if setting is None:
+            self._check(self.lib.tts_set_watermark(self.handle, 0, None))
+        else:
+            p = TtsWatermark(*setting)
+            self._check(self.lib.tts_set_watermark(self.handle, 1, ctypes.addressof(p)))
+        self._watermark = setting
 
     def set_output(self, output):
         """tts_set_output: the handle's setting, read by every synthesize_host call made after it.  ``output``: None, False or
@@ -2409,6 +2497,81 @@ class Engine(object):
             st.free()
         return answer if len(answer) > 1 else out
 
+    # ------------------------------------------------------------------ the watermark
+    def _watermark_args(self, what, wavs, watermark, n_samples):
+        wavs, single, B, n = _waveforms(what, wavs)
+        setting = watermark_setting(watermark)
+        if setting is None:
+            raise ValueError('{}: a key is needed'.format(what))
+        ns = None
+        if n_samples is not None:
+            ns = np.asarray(n_samples)
+            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+            for b, k in enumerate(ns.tolist()):
+                if not 0 <= k <= n:
+                    raise ValueError('n_samples[{}] = {} is not in 0 .. n = {}'.format(b, k, n))
+            ns = np.ascontiguousarray(ns, dtype=np.int32)
+        return wavs, single, B, n, ns, TtsWatermark(*setting)
+
+    def watermark_embed(self, wavs, watermark, n_samples=None, out=None, stats=False):
+        """tts_watermark_embed: a keyed spread-spectrum carrier under the local envelope added to every utterance of ``wavs`` -- one
+        mono waveform (n,) or a batch (B, n), a host array or a device buffer.  ``watermark``: what ``watermark_setting`` reads -- a
+        key, ``(key, payload)`` or ``(key, payload, payload_bits, chip, chips_per_symbol, strength)``; the defaults are UNTUNED.
+        Returns a device array of the input's shape: ``out`` where one is given (a device buffer of the input's size, which may be
+        the input), else a device input marked in place and handed back, a host input uploaded first.  ``n_samples``: B lengths in
+        0 .. n (host integers) -- samples at or behind them carry no mark; None: all n.  ``stats``: also a host array (B,) of
+        ``WATERMARK_EMBED_RECORD``.  The bits of tests/watermark_oracle.py."""
+        wavs, single, B, n, ns, p = self._watermark_args('watermark_embed', wavs, watermark, n_samples)
+        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
+            raise ValueError('watermark_embed: out must be a device buffer of {} floats'.format(B * n))
+        fresh = out is None and not _is_device(wavs)
+        if fresh:
+            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
+            p_wav = out.data_ptr()
+        else:
+            p_wav, _k = self._in(wavs, np.float32)
+            out = wavs if out is None else out
+        st = self.empty((B, 2), np.float64) if stats else None   # (B records of 16 bytes)
+        self._check_or_free(self.lib.tts_watermark_embed(self.handle, p_wav, out.data_ptr(), B, n, _int32_ptr(ns), ctypes.addressof(p),
+                                                         st.data_ptr() if stats else None), out if fresh else None, st)
+        if fresh and single:
+            out.shape = (n,)
+        if stats:
+            records = st.to_host().view(WATERMARK_EMBED_RECORD).reshape(B)
+            st.free()
+            return out, records
+        return out
+
+    def watermark_detect(self, wavs, watermark, offsets=64, n_samples=None, want_scores=False, want_sums=False):
+        """tts_watermark_detect: the search for the carrier of ``watermark`` (its key and its shape; the payload and the strength are
+        not read) in every utterance of ``wavs`` -- one mono waveform (n,) or a batch (B, n), a host array or a device buffer -- over
+        the offsets 0 .. ``offsets`` - 1 (1 .. 4096): how many samples the row may have lost at its front.  Returns a host array
+        (B,) of ``WATERMARK_DETECT_RECORD`` -- the lowest offset with the largest score, the score, the energy there and the payload
+        read; ``watermark_zeta`` makes the statistic of them -- then, with ``want_scores``, every offset's score, int64 (B, offsets),
+        and, with ``want_sums``, the payload bits' sums at the offset found, int64 (B, payload_bits).  ``n_samples``: B lengths in
+        0 .. n; None: all n.  The bits of tests/watermark_oracle.py."""
+        wavs, _single, B, n, ns, p = self._watermark_args('watermark_detect', wavs, watermark, n_samples)
+        D = offsets
+        if isinstance(D, (bool, np.bool_)) or not isinstance(D, (int, np.integer)) or not 1 <= D <= WM_MAX_OFFSETS:
+            raise ValueError('watermark_detect: offsets must be an integer in 1 .. {}, got {!r}'.format(WM_MAX_OFFSETS, D))
+        p_wav, keep = self._in(wavs, np.float32)
+        rec = self.empty((B, 4), np.float64)   # (B records of 32 bytes)
+        scores = self.empty((B, int(D)), np.int64) if want_scores else None
+        sums = self.empty((B, p.payload_bits), np.int64) if want_sums else None
+        self._check_or_free(self.lib.tts_watermark_detect(self.handle, p_wav, B, n, _int32_ptr(ns), ctypes.addressof(p), int(D), rec.data_ptr(),
+                                                          scores.data_ptr() if want_scores else None, sums.data_ptr() if want_sums else None),
+                            rec, scores, sums)
+        answer = (rec.to_host().view(WATERMARK_DETECT_RECORD).reshape(B),)
+        rec.free()
+        for extra in (scores, sums):
+            if extra is not None:
+                answer += (extra.to_host(),)
+                extra.free()
+        if keep is not wavs:
+            keep.free()
+        return answer if len(answer) > 1 else answer[0]
+
     # ------------------------------------------------------------------ delivery formats
     def encode(self, wav, format, dither='tpdf', seed=0, n_samples=None):
         """tts_encode: float32 rows to delivery codes -- ``format`` 'pcm16' (int16), 'pcm8', 'mulaw' or 'alaw' (uint8) -- in one
@@ -2931,10 +3094,10 @@ class Engine(object):
     def synthesize(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, init_phase=None,
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
-                   alignment_stats=None, limiter=None, token_times=None, equalizer=None, compressor=None, **refused):
+                   alignment_stats=None, limiter=None, token_times=None, equalizer=None, compressor=None, watermark=None, **refused):
         """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` to
-        ``limiter`` hold for this call alone, as SETTINGS has them, ``token_times`` as MARK_SETTINGS has it, ``compressor`` as
-        DYNAMICS_SETTINGS and ``equalizer`` as TONE_SETTINGS have them.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
+        ``limiter`` hold for this call alone, as SETTINGS has them, ``token_times`` as MARK_SETTINGS has it, ``watermark`` as
+        WATERMARK_SETTINGS, ``compressor`` as DYNAMICS_SETTINGS and ``equalizer`` as TONE_SETTINGS have them.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
         call's rows stay on the device, where ``resample`` and ``encode`` take them."""
         if 'output' in refused:
             raise ValueError('synthesize: no output= here -- the waveforms stay on the device as float32; resample and encode them there '
@@ -2943,7 +3106,7 @@ class Engine(object):
             raise TypeError('synthesize() got an unexpected keyword argument {!r}'.format(sorted(refused)[0]))
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter,
-                              token_times=token_times, compressor=compressor, equalizer=equalizer)
+                              token_times=token_times, watermark=watermark, compressor=compressor, equalizer=equalizer)
         B, Ts = ids.shape
         T = n_steps * self.cfg.reduction
         r_call, o_call = call['speaking_rate'], call['pitch']
@@ -2995,7 +3158,7 @@ class Engine(object):
     def synthesize_host(self, ids, n_steps, ref_db, max_db, power, n_iter, win_length, hop_length, seed=0,
                         peak_normalize=True, want_linear=False, want_alignments=False, momentum=None, stop_at_silence=None,
                         speaking_rate=None, pitch=None, phase_init=None, loudness=None, alignment_stats=None, limiter=None,
-                        output=None, token_times=None, equalizer=None, compressor=None):
+                        output=None, token_times=None, equalizer=None, compressor=None, watermark=None):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
@@ -3003,10 +3166,10 @@ class Engine(object):
         made, not when its work runs.  A call made with an ``output`` is fetched with ``wait_host_encoded``, not ``wait_host``.  A call that stops at silence returns once its post-net has run (the lengths:
         ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``), and so do the
         timing marks of a call made with ``token_times`` (MARK_SETTINGS; ``wait_host_token_times``).  ``equalizer`` (TONE_SETTINGS)
-        and ``compressor`` (DYNAMICS_SETTINGS) hold for this call alone too."""
+        ``compressor`` (DYNAMICS_SETTINGS) and ``watermark`` (WATERMARK_SETTINGS) hold for this call alone too."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output,
-                              token_times=token_times, compressor=compressor, equalizer=equalizer)
+                              token_times=token_times, watermark=watermark, compressor=compressor, equalizer=equalizer)
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         self._check_ids(ids)
         B, Ts = ids.shape

@@ -17,12 +17,14 @@ one gain takes a waveform to a target integrated loudness after ITU-R BS.1770-4 
 synthesis is the ``loudness`` argument of the synthesis calls (tts_set_loudness).  ``limit`` is the look-ahead peak limiter behind
 it (tts_limit; the ``limiter`` argument of the synthesis calls, tts_set_limiter).  ``equalize`` shapes the spectrum with a cascade
 of second-order sections (tts_equalize; the ``equalizer`` argument of the synthesis calls, tts_set_equalizer), and ``compress``
-lowers the crest factor with a feed-forward peak compressor (tts_compress; the ``compressor`` argument, tts_set_compressor)."""
+lowers the crest factor with a feed-forward peak compressor (tts_compress; the ``compressor`` argument, tts_set_compressor).
+``watermark`` adds a keyed spread-spectrum carrier under the local envelope (tts_watermark_embed; the ``watermark`` argument,
+tts_set_watermark); ``audio.metrics.detect_watermark`` looks for it."""
 import numpy as np
 
 from . import default_engine
 from .conversion import ms_to_samples
-from .._hip import compressor_params, compressor_setting, equalizer_sections, equalizer_setting, limiter_lookahead
+from .._hip import compressor_params, compressor_setting, equalizer_sections, equalizer_setting, limiter_lookahead, watermark_setting
 
 
 def pitch_shift(wav, sampling_rate, octaves, preserve_formants=False, n_iter=25, seed=0, engine=None):
@@ -97,6 +99,20 @@ def compress(wav, sampling_rate, compressor, engine=None):
     eng = engine or default_engine()
     params = compressor_params(setting, eng.sampling_rate if sampling_rate is None else int(sampling_rate))
     out = eng.compress(np.asarray(wav, dtype=np.float32), ('params', params))
+    host = out.to_host()
+    out.free()
+    return host
+
+
+def watermark(wav, key, payload=0, payload_bits=None, chip=None, chips_per_symbol=None, strength=None, engine=None):
+    """``wav`` -- one mono waveform (n,) or a batch (B, n) -- with the keyed carrier of ``Engine.watermark_embed`` added under its
+    local envelope; the carrier starts at every row's first sample.  ``key``: an integer in 0 .. 2^64 - 1; ``payload``: its low
+    ``payload_bits`` bits travel.  What is left out is ``_hip.WM_DEFAULTS`` -- 16 bits, 8 samples a chip, 64 chips a symbol, a
+    strength of 0.02 of the envelope: UNTUNED, nobody has listened.  The length does not change.  Returns a float32 host array of
+    the input's shape."""
+    setting = watermark_setting((key, payload, payload_bits, chip, chips_per_symbol, strength))
+    eng = engine or default_engine()
+    out = eng.watermark_embed(np.asarray(wav, dtype=np.float32), setting)
     host = out.to_host()
     out.free()
     return host

@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import default_engine
-from .._hip import dbtp
+from .._hip import WM_THRESHOLD, dbtp, watermark_setting, watermark_zeta
 from ..tacotron.params import LJSpeechConstants
 
 MCD_COEFFS = 13
@@ -35,6 +35,31 @@ def true_peak(wav, engine=None):
     wav = wav if hasattr(wav, 'data_ptr') and not isinstance(wav, np.ndarray) else np.asarray(wav, dtype=np.float32)
     out = dbtp(eng.true_peak(wav))
     return float(out[0]) if len(wav.shape) == 1 else out
+
+
+def detect_watermark(wav, sampling_rate, key, payload_bits=None, chip=None, chips_per_symbol=None, offsets=64, threshold=WM_THRESHOLD, engine=None):
+    """Looks for the carrier of ``key`` (``audio.effects.watermark``, the ``watermark`` of the synthesis calls) in ``wav`` -- one mono
+    waveform (n,) or a batch (B, n) at ``sampling_rate``, which may have lost up to ``offsets`` - 1 samples at its front.  Where the
+    rate is not the engine's (None: it is), the rows go through ``Engine.resample`` to the engine's rate first, where the carrier
+    was laid.  Returns a dict -- a list of dicts for a batch -- of ``offset`` (the samples cut at the front), ``payload`` (the
+    bits read), ``zeta`` (``_hip.watermark_zeta``: the score against what P half-normals of the same energy give) and ``detected``
+    (zeta above ``threshold``; the default is 1.5 times the largest zeta that wrong keys reached on the oracle).
+    The shape parameters left out are the UNTUNED defaults of ``_hip.WM_DEFAULTS``."""
+    setting = watermark_setting((key, 0, payload_bits, chip, chips_per_symbol, None))
+    eng = engine or default_engine()
+    rows = np.asarray(wav, dtype=np.float32)
+    single = rows.ndim == 1
+    work = None
+    if sampling_rate is not None and int(sampling_rate) != eng.sampling_rate:
+        work = eng.resample(rows, float(eng.sampling_rate) / float(int(sampling_rate)))
+    records = eng.watermark_detect(rows if work is None else work, setting, offsets=offsets)
+    if work is not None:
+        work.free()
+    found = []
+    for r in records:
+        z = watermark_zeta(r['score'], r['energy'], setting[2])
+        found.append(dict(offset=int(r['offset']), payload=int(r['payload']), zeta=z, detected=bool(z > threshold)))
+    return found[0] if single else found
 
 
 def mcd_scale(ref_db, max_db):

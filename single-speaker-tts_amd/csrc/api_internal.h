@@ -57,7 +57,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_WARP, ST_SHIFT, ST_EQUALIZE, ST_COMPRESS, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_WARP, ST_SHIFT, ST_EQUALIZE, ST_COMPRESS, ST_WATERMARK, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -298,7 +298,7 @@ struct HostIo {
 };
 
 // The synthesis settings of a handle: what tts_set_end_of_speech, tts_set_speaking_rate, tts_set_pitch, tts_set_loudness,
-// tts_set_limiter, tts_set_equalizer, tts_set_compressor, tts_set_alignment_stats, tts_set_token_times, tts_set_output and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
+// tts_set_limiter, tts_set_equalizer, tts_set_compressor, tts_set_watermark, tts_set_alignment_stats, tts_set_token_times, tts_set_output and the options "gl_momentum" / "gl_init" write.  tts_synthesize and tts_synthesize_host take ONE
 // copy when the call is made and read nothing but that copy from then on; with every setting off the call enqueues what it
 // always did.  (The stand-alone Griffin-Lim calls have no such copy: they read the handle's momentum and start.)
 struct SynthSettings {
@@ -332,6 +332,11 @@ struct SynthSettings {
         bool enabled = false;
         tts_compressor_t params = {};
     } cmp;
+    // the watermark (tts_set_watermark): the parameters are the handle's copy
+    struct {
+        bool enabled = false;
+        tts_watermark_t params = {};
+    } wm;
     struct {
         bool enabled = false;
         int pad_id = 0;
@@ -714,6 +719,11 @@ struct CmpScratch { double* state; void* partial; };   // the segments' states [
 int compressor_scratch(tts_handle_t h, int B, int N, bool records, CmpScratch* s);
 int compressor_impl(tts_handle_t h, const float* wav, float* out, int B, int N, const int32_t* n_samples, const tts_compressor_t& params,
                     double* envelope, tts_compress_stats_t* stats);
+// the watermark's embedder (watermark.hip): arguments checked by the caller (watermark_plan.h)
+struct WmScratch { float* E; void* partial; };   // the blocks' maxima [B][blocks]; the tiles' records [B][tiles], where asked for
+int watermark_scratch(tts_handle_t h, int B, int N, bool records, WmScratch* s);
+int watermark_impl(tts_handle_t h, const float* wav, float* out, int B, int N, const int32_t* n_samples, const tts_watermark_t& params,
+                   tts_watermark_embed_stats_t* stats);
 // the delivery encoder (encode.hip): arguments checked by the caller (encode_plan.h).  The records of a call that takes none
 struct EncScratch { tts_encode_stats_t* stats; };
 int encode_scratch(tts_handle_t h, int B, EncScratch* s);

@@ -159,6 +159,8 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
     if (k.set.eq.enabled && (rc = equalizer_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.eq.n_sections, &eq))) return rc;
     CmpScratch cmp;
     if (k.set.cmp.enabled && (rc = compressor_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), false, &cmp))) return rc;
+    WmScratch wm;
+    if (k.set.wm.enabled && (rc = watermark_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), false, &wm))) return rc;
     if (k.set.loud.enabled && (rc = loudness_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate, &loud))) return rc;
     if (k.set.lim.enabled && (rc = limiter_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), &lim))) return rc;
     if (k.set.ali.enabled || k.set.tt.enabled) {
@@ -497,12 +499,14 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     // The loudness target and the limiter: every utterance is taken over the samples its row holds -- hop (n[b] - 1) of the reported
     // lengths with end-of-speech stopping, all of the row otherwise -- in place, behind whatever made the row.
     std::vector<int32_t> held;
-    if (detected && (k.set.loud.enabled || k.set.lim.enabled || k.set.eq.enabled || k.set.cmp.enabled))
+    if (detected && (k.set.loud.enabled || k.set.lim.enabled || k.set.eq.enabled || k.set.cmp.enabled || k.set.wm.enabled))
         for (int b = 0; b < B; ++b) held.push_back(sp->hop_length * (L.reported[(size_t)b] - 1));
     if (k.set.eq.enabled && !rc)   // (the equaliser: behind the peak normalisation, ahead of the loudness gain and the limiter)
         rc = equalizer_impl(h, k.wav, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.eq.sos, k.set.eq.n_sections);
     if (k.set.cmp.enabled && !rc)   // (the compressor: behind the equaliser, ahead of the loudness gain and the limiter)
         rc = compressor_impl(h, k.wav, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.cmp.params, nullptr, nullptr);
+    if (k.set.wm.enabled && !rc)   // (the watermark: behind the compressor, ahead of the loudness gain and the limiter, which scale it with the speech)
+        rc = watermark_impl(h, k.wav, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.wm.params, nullptr);
     if (k.set.loud.enabled && !rc) {
         rc = loudness_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.loud.sampling_rate, true,
                            k.set.loud.target_lufs, k.set.loud.max_peak, nullptr, nullptr, nullptr);
@@ -545,6 +549,9 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
     if (set.cmp.enabled &&
         (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
         return fail(h, TTS_ERR_INVALID, "synthesize: the compressor needs rows of 1 .. 2^31 - 1 samples");
+    if (set.wm.enabled &&
+        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
+        return fail(h, TTS_ERR_INVALID, "synthesize: the watermark needs rows of 1 .. 2^31 - 1 samples");
     if (set.lim.enabled &&
         (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
         return fail(h, TTS_ERR_INVALID, "synthesize: the limiter needs rows of 1 .. 2^31 - 1 samples");

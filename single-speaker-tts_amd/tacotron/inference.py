@@ -18,7 +18,7 @@ import numpy as np
 
 from . import attention_check, marks as marks_, prosody
 from .._hip import (ALIGNMENT_RECORD, FMT_F32, FORMAT_NAMES, JOIN_MAX_FADE, LIMIT_LOOKAHEAD_MS, LOUDNESS_MAX_PEAK, RESAMPLE_SEGMENTS_MAX_RATIOS, shift_step,
-                    compressor_params, compressor_setting, equalizer_sections, equalizer_setting, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
+                    compressor_params, compressor_setting, watermark_setting, equalizer_sections, equalizer_setting, limiter_lookahead, limiter_setting, loudness_setting, momentum_thousandths, output_is_on, output_ratio,
                     output_setting, phase_init_value, pitch_octaves_value, pitch_semitones_value, resampled_length,
                     silence_keep_frames, speaking_rate_value, stop_at_silence_setting, synth_frame_counts, token_times_jump)
 from ..audio.conversion import ms_to_samples
@@ -183,7 +183,7 @@ def deliver(engine, wavs, setting, seed=0, norm=False, what='utterance'):
 class SynthSettings(object):
     """The synthesis settings every helper of this layer takes, checked once -- ValueError before an engine is touched, in the
     order of ``_hip.SETTINGS`` -- and kept as the checked values ``momentum``, ``stop``, ``rate``, ``octaves``, ``phase_init``,
-    ``loud``, ``check_alignment``, ``limiter``, ``output`` (``output_of``), ``compressor`` and ``equalizer``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
+    ``loud``, ``check_alignment``, ``limiter``, ``output`` (``output_of``), ``watermark``, ``compressor`` and ``equalizer``.  ``hp``: the hyper-parameters the stopping takes its hop from, or a model that has them.
 
     ``momentum``: fast Griffin-Lim (audio.synthesis), 0.0 = the reference's loop.
     ``stop_at_silence_db``: stop every utterance ``silence_keep_ms`` behind its last frame whose loudest bin is above that many
@@ -226,7 +226,12 @@ class SynthSettings(object):
     'small-speaker'; every preset is untuned -- or ``(threshold_db, ratio[, knee_db[, attack_ms[, release_ms[, makeup_db]]]])``: a
     feed-forward peak compressor (``Engine.compress``) lowers the crest factor of every utterance on the device, behind the
     equaliser and ahead of the loudness gain and the limiter.  Lengths and timing marks do not change.  A make-up gain behind the
-    peak normalisation can pass 1.0: give it a limiter or a loudness target."""
+    peak normalisation can pass 1.0: give it a limiter or a loudness target.
+    ``watermark`` (taken by ``SynthSettings.of`` too): None (the engine's setting), a key, ``(key, payload)`` or ``(key, payload,
+    payload_bits, chip, chips_per_symbol, strength)``: a keyed spread-spectrum carrier (``Engine.watermark_embed``) is added under
+    the local envelope of every utterance on the device, behind the compressor and ahead of the loudness gain and the limiter;
+    ``audio.metrics.detect_watermark`` finds it.  Lengths and timing marks do not change.  The defaults (16 bits, 8 samples a chip,
+    64 chips a symbol, 0.02 of the envelope) are UNTUNED: nobody has listened."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
                  phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None,
@@ -247,15 +252,18 @@ class SynthSettings(object):
         self.marks_max_jump = token_times_jump(marks_max_jump, 'marks_max_jump')
         self.equalizer = None
         self.compressor = None
+        self.watermark = None
 
     @classmethod
     def of(cls, hp, equalizer=None, **settings):
         """The record of a helper's ``**settings``: the constructor's keywords and, checked behind them, the dynamics keywords
-        (DYNAMICS_KEYWORDS: ``compressor``, read out of ``settings``) and then the tone keywords (TONE_KEYWORDS;
+        (WATERMARK_KEYWORDS and DYNAMICS_KEYWORDS: ``watermark`` and ``compressor``, read out of ``settings``) and then the tone keywords (TONE_KEYWORDS;
         ``_hip.DYNAMICS_SETTINGS`` and ``_hip.TONE_SETTINGS`` are likewise tables behind the others) -- ``equalizer``, refused
         here too where a corner does not fit the model's sampling rate."""
+        watermark = settings.pop('watermark', None)
         compressor = settings.pop('compressor', None)
         s = cls(hp, **settings)
+        s.watermark = watermark_setting(watermark)
         s.compressor = compressor_setting(compressor)
         s.equalizer = equalizer_setting(equalizer)
         rate = getattr(getattr(hp, 'hparams', hp), 'sampling_rate', None)
@@ -270,7 +278,7 @@ class SynthSettings(object):
         return dict(momentum=self.momentum, stop_at_silence=self.stop, speaking_rate=self.rate, pitch=self.octaves,
                     phase_init=self.phase_init, loudness=self.loud, alignment_stats=(True, pad_id()) if self.check_alignment else None,
                     limiter=self.limiter, token_times=(True, pad_id(), self.marks_max_jump) if self.marks else None,
-                    compressor=self.compressor, equalizer=self.equalizer)
+                    watermark=self.watermark, compressor=self.compressor, equalizer=self.equalizer)
 
     def host_keywords(self):
         """... and as ``Engine.synthesize_host`` alone takes them: with the delivery format"""
@@ -281,7 +289,7 @@ class SynthSettings(object):
         ``check_alignment``, ``output`` and the marks"""
         return dict(momentum=self.momentum, stop_at_silence_db=self.stop_at_silence_db, silence_keep_ms=self.silence_keep_ms,
                     speaking_rate=self.rate, pitch=self.octaves, phase_init=self.phase_init, loudness=self.loud, limiter=self.limiter,
-                    compressor=self.compressor, equalizer=self.equalizer)
+                    watermark=self.watermark, compressor=self.compressor, equalizer=self.equalizer)
 
     def file_norm(self):
         """the peak normalisation of the file helpers, ``(on the device, in save_wav)``: none with a loudness or a limiter, else
@@ -292,7 +300,8 @@ class SynthSettings(object):
 
 TONE_KEYWORDS = tuple(inspect.signature(SynthSettings.of).parameters)[1:-1]      # ('equalizer',)
 DYNAMICS_KEYWORDS = ('compressor',)                                              # ahead of the tone, as _hip.DYNAMICS_SETTINGS is
-SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:] + DYNAMICS_KEYWORDS + TONE_KEYWORDS
+WATERMARK_KEYWORDS = ('watermark',)                                              # ahead of the dynamics, as _hip.WATERMARK_SETTINGS is
+SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:] + WATERMARK_KEYWORDS + DYNAMICS_KEYWORDS + TONE_KEYWORDS
 
 
 def takes_settings(*refuses, only=None):
@@ -325,7 +334,7 @@ def takes_settings(*refuses, only=None):
         functools.update_wrapper(helper, parts)
         own = [p for p in inspect.signature(parts).parameters.values() if p.kind is not p.VAR_KEYWORD]
         record = dict(inspect.signature(SynthSettings.__init__).parameters, **{k: inspect.signature(SynthSettings.of).parameters[k] for k in TONE_KEYWORDS})
-        record.update({k: inspect.Parameter(k, inspect.Parameter.KEYWORD_ONLY, default=None) for k in DYNAMICS_KEYWORDS})
+        record.update({k: inspect.Parameter(k, inspect.Parameter.KEYWORD_ONLY, default=None) for k in WATERMARK_KEYWORDS + DYNAMICS_KEYWORDS})
         helper.__signature__ = inspect.Signature(own + [record[k].replace(kind=inspect.Parameter.KEYWORD_ONLY)
                                                         for k in SETTING_KEYWORDS if k not in refuses])
         helper.parts = parts
@@ -361,7 +370,8 @@ def finishing_tail(caller, s, sampling_rate, deliver=True):
     before an engine is touched (ValueError that names ``caller``); the function returned then runs, on device rows (B, N) that
     hold ``held[b]`` samples each (None: all N), a peak normalisation (``peak_normalize``, where there is no ``loudness``), the
     ``equalizer`` (its sections are made here too, at ``sampling_rate``), the ``compressor`` (its coefficients likewise; an
-    engine's ``compress`` is not touched without one), the ``loudness``, the ``limiter``,
+    engine's ``compress`` is not touched without one), the ``watermark`` (an engine's ``watermark_embed`` likewise), the ``loudness``,
+    the ``limiter``,
     and hands back ``deliver_rows`` for an ``output`` (with ``deliver``; the dither's ``seed``) or else the rows downloaded, a list
     of B arrays cut to what they hold.  ``rows`` stays the caller's to free."""
     lookahead = None if s.limiter is None else limiter_lookahead(caller, s.limiter[1], sampling_rate)
@@ -375,6 +385,8 @@ def finishing_tail(caller, s, sampling_rate, deliver=True):
             engine.equalize(rows, sections, n_samples=held)
         if dynamics is not None:
             engine.compress(rows, dynamics, n_samples=held)
+        if s.watermark is not None:
+            engine.watermark_embed(rows, s.watermark, n_samples=held)
         if s.loud is not None:
             engine.loudness_normalize(rows, sampling_rate, s.loud[0], s.loud[1], n_samples=held)
         if s.limiter is not None:
@@ -922,7 +934,8 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     one ``Engine.loudness_normalize`` runs over the joined rows, so a text is levelled as a whole and its sentences keep their
     relative levels; with a ``limiter`` one ``Engine.limit`` runs over the joined rows behind it, and with an ``equalizer`` one
     ``Engine.equalize`` and with a ``compressor`` one ``Engine.compress`` ahead of both, in that order: a text is compressed as a
-    whole, after the join.  Only the n_out[g] samples of a row that were said are downloaded.
+    whole, after the join; with a ``watermark`` one ``Engine.watermark_embed`` behind the compressor, so the carrier starts at the
+    file's first sample.  Only the n_out[g] samples of a row that were said are downloaded.
 
     A text whose pieces span several calls is concatenated on the host, with the pause behind the earlier part as zeros between
     them; with a ``loudness`` each part is levelled on its own.  The packing decides which pieces share a call, a call's seed
@@ -957,7 +970,7 @@ def synthesize_text(model, texts, dataset, batch_size=64, pauses_ms=None, fade_m
     for k, (p0, ids) in enumerate(calls):
         B = ids.shape[0]
         out = eng.synthesize(ids, *c.synth, seed=seed + k, peak_normalize=False, want_linear=True,
-                             **dict(s.engine_keywords(), loudness=None, limiter=None, equalizer=None, compressor=None))   # (all four run on the joined rows)
+                             **dict(s.engine_keywords(), loudness=None, limiter=None, equalizer=None, compressor=None, watermark=None))   # (all five run on the joined rows)
         first_active = eng.speech_interval(out['linear'], threshold)[0].to_host()
         if s.check_alignment:
             records.append(eng.synth_alignment_stats(B))
@@ -1063,6 +1076,7 @@ def main(argv=None):
                                                             [--loudness LUFS [--max-peak P]]
                                                             [--eq PROFILE|kind:f0[:q][:gain_db],...]
                                                             [--compress PROFILE|T:R[:knee[:attack[:release[:makeup]]]]]
+                                                            [--watermark KEY[:PAYLOAD]]
                                                             [--limit DB [--limit-lookahead-ms MS] [--sample-peak]]
                                                             [--format pcm16|pcm8|mulaw|alaw|float32 [--out-rate HZ] [--no-dither]]
                                                             [--check-alignment] [--marks [word|char] [--marks-max-jump J]]
@@ -1089,6 +1103,10 @@ def main(argv=None):
     ``T:R[:knee[:attack[:release[:makeup]]]]``: the threshold in dB re full scale, the ratio (``inf`` allowed), the knee's width in
     dB (6), the attack and release in ms (5 and 100) and the make-up gain in dB (0), e.g. ``--compress=-18:3:6:5:100:3`` (with the equals sign: the value begins with a minus).  A make-up
     gain can take samples beyond 1: give it ``--limit`` or ``--loudness``.
+    ``--watermark KEY[:PAYLOAD]``: a keyed spread-spectrum carrier is added under the local envelope of every wav, behind the
+    compressor and ahead of the loudness gain and the limiter; ``python -m single-speaker-tts_amd.tacotron.detect --key KEY file.wav``
+    finds it and reads the payload (16 bits) back.  KEY and PAYLOAD are integers, decimal or 0x-hexadecimal.  The carrier's shape and
+    strength are the UNTUNED defaults: nobody has listened.
     ``--limit DB``: a look-ahead peak limiter runs last over every wav: no peak above DB decibels relative to full scale (e.g.
     -1), looking ``--limit-lookahead-ms`` ahead (default 5); the ceiling holds for the interpolated (true) peaks, with
     ``--sample-peak`` for the samples alone.  The files are then not peak-normalised.  With ``--loudness`` and no ``--max-peak``
@@ -1157,7 +1175,22 @@ def settings_option(args):
                 loudness=None if args.loudness is None else (args.loudness, args.max_peak), check_alignment=args.check_alignment,
                 limiter=None if args.limit is None else (10.0 ** (args.limit / 20.0), args.limit_lookahead_ms, 1 if args.sample_peak else 4),
                 output=output_option(args), marks=args.marks, marks_max_jump=args.marks_max_jump, equalizer=eq_option(args.eq),
-                compressor=compress_option(args.compress))
+                compressor=compress_option(args.compress), watermark=watermark_option(args.watermark))
+
+
+def watermark_option(text):
+    """``--watermark`` as the ``watermark`` of the helpers above: None, or ``KEY[:PAYLOAD]`` as ``(key, payload)``, both integers,
+    decimal or 0x-hexadecimal.  ValueError names the field."""
+    if text is None:
+        return None
+    fields = text.split(':')
+    if not 1 <= len(fields) <= 2:
+        raise ValueError('--watermark: {!r}: KEY[:PAYLOAD] is needed'.format(text))
+    try:
+        values = tuple(int(v, 0) for v in fields)
+    except ValueError:
+        raise ValueError('--watermark: {!r}: the key and the payload must be integers (decimal or 0x...)'.format(text))
+    return values + (0,) * (2 - len(values))
 
 
 def compress_option(text):
@@ -1236,6 +1269,9 @@ def parse_args(argv=None):
     ap.add_argument('--compress', default=None, metavar='PROFILE|T:R[:KNEE[:ATTACK[:RELEASE[:MAKEUP]]]]',
                     help='a peak compressor behind the equaliser, ahead of the loudness gain and the limiter: a profile (speech, telephony, '
                          'small-speaker; untuned) or threshold dB : ratio [: knee dB : attack ms : release ms : make-up dB], e.g. --compress=-18:3:6:5:100:3')
+    ap.add_argument('--watermark', default=None, metavar='KEY[:PAYLOAD]',
+                    help='a keyed carrier under the local envelope, behind the compressor and ahead of the loudness gain and the limiter '
+                         '(untuned defaults); tacotron.detect --key KEY finds it, e.g. --watermark 0x5EED:0xA5C3')
     ap.add_argument('--limit', type=float, default=None, metavar='DB',
                     help='a look-ahead peak limiter behind everything else: no peak above DB decibels re full scale, e.g. -1')
     ap.add_argument('--limit-lookahead-ms', type=float, default=LIMIT_LOOKAHEAD_MS, metavar='MS',

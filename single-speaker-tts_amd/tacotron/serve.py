@@ -33,6 +33,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, **
     length; with a ``speaking_rate`` or a ``pitch`` ``Engine.stretch_magnitudes`` by rate * 2 ** -pitch ahead of Griffin-Lim
     (``init_phase`` has that many frames; lengths min(T', max(min_frames, ceil(n / rate)))) and ``Engine.resample`` by 2 ** -pitch
     behind it; with an ``equalizer`` ``Engine.equalize`` and with a ``compressor`` ``Engine.compress`` behind it, in that order;
+    with a ``watermark`` ``Engine.watermark_embed`` behind those;
     with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
     last, over the same samples."""
     s = SynthSettings.of(model_params, **settings)

@@ -605,6 +605,60 @@ int tts_f0_max_lag(void);
 int tts_f0_compare(tts_handle_t h, const float* f0_a, int Ta, const float* f0_b, int Tb, const int32_t* path /* [B][rows][2] */,
                    int rows, int B, int32_t* counts /* [B][5] */, double* sums /* [B][2] */);
 
+/* ---- intelligibility: STOI and ESTOI ------------------------------------------------------- */
+/* Short-time objective intelligibility (Taal, Hendriks, Heusdens and Jensen 2011) and its extended form (Jensen and Taal 2016)
+ * of B pairs of time-aligned mono waveforms at 10 000 Hz (no reference counterpart; resampling is the caller's job:
+ * tts_resample).  ref, deg DEVICE [B][N]; n_samples: HOST int32 [B], the samples of each row, or NULL (all N) -- samples at or
+ * behind n_samples[b] are never read.  Constants: frames of W = 256 samples, H = 128 apart, a transform of 512 points, J = 15
+ * one-third octave bands from 150 Hz, segments of 30 frames, the clip constant c = 1 + 10 ** (15 / 20), a dynamic range of 1e-4
+ * in energy (40 dB).  tts_stoi_window fills w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257) (np.hanning(258)[1:-1]) and tts_stoi_bands
+ * the bins [lo, hi) of every band, lo and hi the bins nearest to 150 * 2 ** ((2 k -/+ 1) / 6) Hz: the host's cos / pow make the
+ * tables once, and a restatement takes them from there.
+ *
+ * Per row with n samples, every operation an individually rounded IEEE double operation:
+ *  1. frames = n < 256 ? 0 : (n - 256) / 128 + 1.
+ *  2. E[m] = sum over i of t * t, t = w[i] * (double)ref[128 m + i]: E starts at 0.0 and takes the terms one by one in
+ *     ascending i, E = E + t * t (a product and a sum), the same for every frame.
+ *  3. Emax: the largest E[m] that is not NaN, or 0; frame m is kept iff E[m] > Emax * 1e-4.  kept: their count; kept_index: their
+ *     indices idx[k], ascending.  These equal tests/stoi_oracle.py exactly.
+ *  4. The compacted signals of (kept - 1) * 128 + 256 samples: xs[p] = the sum, in ascending k, of
+ *     w[p - 128 k] * (double)ref[128 idx[k] + p - 128 k] over the at most two kept frames k that cover p; ys the same from deg.
+ *  5. For m < kept: z[i] = w[i] * xs[128 m + i] zero-padded to 512 points, its DFT, P[k] = re^2 + im^2,
+ *     X[j][m] = sqrt(sum of P[k] over lo_j <= k < hi_j) in ascending k; Y from ys.  With `envelopes` they are written for
+ *     m < kept as [row][0: X, 1: Y][j][m], rows of cap = tts_stoi_frames(N) doubles; nothing else of the buffer is touched.
+ *     Each signal has its own transform: a NaN in deg leaves X as it was, and a deg of zeros has Y == 0.0 exactly.
+ *  6. segments = kept >= 30 ? kept - 29 : 0; segment s takes the frames s .. s + 29.
+ *  7. extended = 0, per segment and band: a = ||x|| / ||y|| (sums of squares from 0.0 in frame order, sqrt, a quotient),
+ *     y'_t = min(a y_t, c x_t) (a NaN on either side is a NaN), the means (a sum in frame order) / 30, and
+ *     r = sum dx dy / (sqrt(sum dx dx) * sqrt(sum dy dy)) of the centred values.  A term with ||y|| == 0, sum dx dx == 0 or
+ *     sum dy dy == 0 is 0 and counts in `degenerate`; there is no epsilon.  A segment's terms are added in band order from 0.0.
+ *  8. extended = 1, per segment: every row of the 15 x 30 blocks of X and Y minus its mean, over its centred norm (a row of
+ *     centred norm 0 becomes zeros and counts in `degenerate`), then every column of the result the same way (likewise), and
+ *     d_s = (sum over columns t, then bands j, of xn * yn) / 30.
+ *  9. value = (the segments' sums added in segment order from 0.0) / (15 * segments), extended: / segments.  segments == 0: NaN.
+ *     A NaN in a kept sample of either signal makes value NaN; a reference frame that holds a NaN is not kept (the comparison
+ *     is false); an Inf energy empties the row.
+ * The order of every sum is fixed, so a row's record has the same bits alone, in any ragged batch, at any B and whatever the
+ * handle ran before.  The envelopes and value are held to the bound of DESIGN.md against tests/stoi_oracle.py (the transform is
+ * the device's own); from given envelopes, steps 6 to 9 are the oracle's bits.
+ * records DEVICE [B] (8-byte aligned); kept_index DEVICE int32 [B][cap] or NULL; envelopes DEVICE double [B][2][15][cap] or NULL.
+ * Five launches per 64 rows (the lengths travel by value), no host wait between them, no atomics, nothing uploaded but the
+ * arguments; asynchronous on the handle's stream; profile stage "stoi".  TTS_ERR_INVALID, before anything is enqueued: a NULL
+ * ref, deg or records, B or N < 1, an n_samples[b] outside 1 .. N, extended not 0 or 1, a misaligned buffer.
+ * TTS_ERR_UNSUPPORTED: more than tts_stoi_max_frames() frames in N samples. */
+typedef struct {
+    int32_t frames, kept, segments, degenerate;
+    double value;
+} tts_stoi_record_t;                               /* 24 bytes */
+int tts_stoi(tts_handle_t h, const float* ref /* [B][N] */, const float* deg /* [B][N] */, int B, int N,
+             const int32_t* n_samples /* HOST [B] or NULL */, int extended, tts_stoi_record_t* records /* DEVICE [B] */,
+             int32_t* kept_index /* DEVICE [B][cap] or NULL */, double* envelopes /* DEVICE [B][2][15][cap] or NULL */);
+/* host only: the frames of n samples; the most frames tts_stoi takes; the window; the bands */
+int tts_stoi_frames(int n);
+int tts_stoi_max_frames(void);
+int tts_stoi_window(double w[256]);
+int tts_stoi_bands(int32_t edges[15][2]);
+
 /* ---- loudness: ITU-R BS.1770-4 / EBU R 128 ------------------------------------------------ */
 /* Integrated loudness of B mono utterances (no reference counterpart: the reference's only level control is the peak
  * normalisation of save_wav).  wav DEVICE [B][N]; n_samples: HOST int32 [B], the samples of each utterance, or NULL (all N) --
@@ -1443,7 +1497,7 @@ int tts_wait_host_encoded(tts_handle_t h, int ticket, const void** data, size_t*
  * tts_synthesize_host call with tts_set_output on), "warp" (tts_warp_magnitudes), "shift" (tts_shift_magnitudes), "equalize" (tts_equalize,
  * stand-alone or inside a tts_synthesize call with tts_set_equalizer on), "compress" (tts_compress, stand-alone or inside a
  * tts_synthesize call with tts_set_compressor on), "watermark" (tts_watermark_embed, tts_watermark_detect, stand-alone or the
- * embedder inside a tts_synthesize call with tts_set_watermark on).
+ * embedder inside a tts_synthesize call with tts_set_watermark on), "stoi" (tts_stoi).
  * Returns accumulated milliseconds and the number of kernel launches covered since the last
  * tts_profile_reset.  Synchronises the stream. */
 int tts_profile_reset(tts_handle_t h);

@@ -266,6 +266,11 @@ _PROTOTYPES = {
     'tts_watermark_embed': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_void_p]),
     'tts_watermark_detect': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'tts_watermark_max_offsets': (c_int, []),
+    'tts_stoi': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_void_p, c_void_p, c_void_p]),
+    'tts_stoi_frames': (c_int, [c_int]),
+    'tts_stoi_max_frames': (c_int, []),
+    'tts_stoi_window': (c_int, [POINTER(ctypes.c_double)]),
+    'tts_stoi_bands': (c_int, [POINTER(c_int32)]),
     'tts_set_watermark': (c_int, [c_void_p, c_int, c_void_p]),
     'tts_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_int32), c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p]),
     'tts_encode_width': (c_int, [c_int]),
@@ -536,6 +541,18 @@ def f0_lag_bounds(sampling_rate, fmin, fmax):
 def f0_frames(n, hop_length):
     """tts_f0_frames: the values tts_f0 writes for ``n`` samples, 1 + n // hop_length."""
     return 1 + int(n) // int(hop_length)
+
+
+STOI_RATE = 10000          # the analysis rate of tts_stoi
+STOI_BANDS = 15
+STOI_MAX_FRAMES = 65536    # tts_stoi_max_frames()
+STOI_RECORD = np.dtype([('frames', np.int32), ('kept', np.int32), ('segments', np.int32), ('degenerate', np.int32), ('value', np.float64)])
+
+
+def stoi_frames(n):
+    """tts_stoi_frames: the frames of 256 samples, 128 apart, in ``n`` samples -- 0 below 256."""
+    n = int(n)
+    return 0 if n < 256 else (n - 256) // 128 + 1
 
 
 LOUDNESS_SR_MIN, LOUDNESS_SR_MAX = 8000, 192000   # what tts_loudness takes
@@ -2335,6 +2352,63 @@ class Engine(object):
         self._check_or_free(self.lib.tts_f0(self.handle, p_wav, B, n, _int32_ptr(ns), float(sampling_rate), int(hop_length), int(window), int(lo),
                                             int(hi), float(threshold), out.data_ptr(), ap.data_ptr() if ap is not None else None), out, ap)
         return (out, ap) if want_aperiodicity else out
+
+    # ------------------------------------------------------------------ intelligibility
+    def stoi(self, ref, deg, n_samples=None, extended=False, want_index=False, want_envelopes=False):
+        """tts_stoi: short-time objective intelligibility (``extended``: ESTOI) of ``deg`` against the time-aligned ``ref`` -- one
+        waveform (n,) each or batches (B, n) of one shape, host arrays or device buffers, AT 10 000 Hz (``audio.metrics.stoi``
+        resamples).  ``n_samples``: B lengths (host integers) -- samples at or behind them are never read; None: all n.  Returns
+        a host array (B,) of ``STOI_RECORD`` -- the frames, those kept (within 40 dB of the reference's loudest), the segments of
+        30 kept frames, the terms that were 0 by rule, and the value: NaN with fewer than 30 kept frames or a NaN in a kept sample
+        -- then, with ``want_index``, the kept frames' indices, int32 (B, cap) with cap = ``stoi_frames(n)`` (a row's first
+        ``kept`` entries are written), and, with ``want_envelopes``, the band envelopes, float64 (B, 2, 15, cap): ref then deg (a
+        row's first ``kept`` columns are written).  include/sstts_hip.h has the definition; tests/stoi_oracle.py restates it."""
+        if isinstance(extended, (bool, np.bool_)):
+            extended = int(extended)
+        if isinstance(extended, float) or extended not in (0, 1):
+            raise ValueError('stoi: extended must be False / True (0 / 1), got {!r}'.format(extended))
+        ref, _single, B, n = _waveforms('stoi', ref)
+        deg, _single_d, Bd, nd = _waveforms('stoi', deg)
+        if (B, n) != (Bd, nd):
+            raise ValueError('stoi: ref and deg must have one shape, got {} and {}'.format((B, n), (Bd, nd)))
+        ns = None
+        if n_samples is not None:
+            ns = np.asarray(n_samples)
+            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+            ns = _checked_lengths(ns, n, 'n_samples', 'n')
+        cap = stoi_frames(n)
+        if cap > STOI_MAX_FRAMES:
+            raise ValueError('stoi: {} frames are more than {} (tts_stoi_max_frames)'.format(cap, STOI_MAX_FRAMES))
+        p_ref, keep_r = self._in(ref, np.float32)
+        p_deg, keep_d = self._in(deg, np.float32)
+        rec = self.empty((B, 3), np.float64)   # (B records of 24 bytes)
+        index = self.empty((B, max(cap, 1)), np.int32) if want_index else None
+        env = self.empty((B, 2, STOI_BANDS, max(cap, 1)), np.float64) if want_envelopes else None
+        try:
+            self._check_or_free(self.lib.tts_stoi(self.handle, p_ref, p_deg, B, n, _int32_ptr(ns), int(extended), rec.data_ptr(),
+                                                  index.data_ptr() if want_index else None, env.data_ptr() if want_envelopes else None),
+                                rec, index, env)
+            answer = (rec.to_host().view(STOI_RECORD).reshape(B),)
+            rec.free()
+            for extra in (index, env):
+                if extra is not None:
+                    answer += (extra.to_host()[..., :cap],)
+                    extra.free()
+        finally:
+            if keep_r is not ref:
+                keep_r.free()
+            if keep_d is not deg:
+                keep_d.free()
+        return answer if len(answer) > 1 else answer[0]
+
+    def stoi_tables(self):
+        """tts_stoi_window and tts_stoi_bands: the analysis window, float64 (256,), and the bands' bins [lo, hi), int32 (15, 2)."""
+        w = np.zeros(256, np.float64)
+        e = np.zeros((STOI_BANDS, 2), np.int32)
+        self._check(self.lib.tts_stoi_window(w.ctypes.data_as(POINTER(ctypes.c_double))))
+        self._check(self.lib.tts_stoi_bands(e.ctypes.data_as(POINTER(c_int32))))
+        return w, e
 
     # ------------------------------------------------------------------ loudness
     def _ragged_waveforms(self, what, wavs, n_samples):

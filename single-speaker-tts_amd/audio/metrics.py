@@ -4,13 +4,14 @@ speaks a little faster or slower than the recording.  Mel-cepstral distortion al
 spectra at the frames that belong together.  The cepstra (tts_mfcc) and the alignment (tts_dtw) run on the device.  Along the
 same path, F0 RMSE, voicing error and gross pitch error compare the prosody (tts_f0, tts_f0_compare), which the cepstra do not
 see.  ``integrated_loudness`` is the level of a waveform as a listener hears it: ITU-R BS.1770-4 / EBU R 128 (tts_loudness); ``true_peak`` is its
-peak between the samples, as delivery specifications state it (tts_true_peak)."""
+peak between the samples, as delivery specifications state it (tts_true_peak).  ``stoi`` says whether a waveform can be understood
+beside a time-aligned clean one: short-time objective intelligibility and its extended form (tts_stoi)."""
 import math
 
 import numpy as np
 
 from . import default_engine
-from .._hip import WM_THRESHOLD, dbtp, watermark_setting, watermark_zeta
+from .._hip import STOI_RATE, WM_THRESHOLD, dbtp, resampled_valid, watermark_setting, watermark_zeta
 from ..tacotron.params import LJSpeechConstants
 
 MCD_COEFFS = 13
@@ -60,6 +61,43 @@ def detect_watermark(wav, sampling_rate, key, payload_bits=None, chip=None, chip
         z = watermark_zeta(r['score'], r['energy'], setting[2])
         found.append(dict(offset=int(r['offset']), payload=int(r['payload']), zeta=z, detected=bool(z > threshold)))
     return found[0] if single else found
+
+
+STOI_RATE_MIN, STOI_RATE_MAX = STOI_RATE // 4, STOI_RATE * 4   # the resampler's ratios are 0.25 .. 4
+
+
+def stoi(ref, deg, sampling_rate, extended=False, n_samples=None, engine=None):
+    """Short-time objective intelligibility (Taal et al. 2011; ``extended``: ESTOI, Jensen and Taal 2016) of ``deg`` against the
+    clean, TIME-ALIGNED ``ref``: one mono waveform (n,) each or batches (B, n) of one shape at ``sampling_rate``, host arrays.
+    The figure is defined at 10 000 Hz: at any other rate both signals go through ``Engine.resample`` first (rates outside
+    2 500 .. 40 000 Hz are refused: the resampler's ratios are 0.25 .. 4), and ``n_samples`` -- B lengths, None: all n -- become
+    the samples the resampler writes for them, int(n * 10000 / sampling_rate).  Returns float64 (B,): about 1 for a copy,
+    falling with the damage; NaN for a row with fewer than 30 frames within 40 dB of the reference's loudest, or with a NaN in
+    a kept sample.  ``Engine.stoi`` has the frame and segment counts."""
+    try:
+        ok = int(sampling_rate) == sampling_rate and STOI_RATE_MIN <= sampling_rate <= STOI_RATE_MAX
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError('stoi: the sampling rate must be an integer in {} .. {}, got {!r}'.format(STOI_RATE_MIN, STOI_RATE_MAX, sampling_rate))
+    eng = engine or default_engine()
+    ref, deg = np.asarray(ref, dtype=np.float32), np.asarray(deg, dtype=np.float32)
+    if ref.shape != deg.shape or ref.ndim not in (1, 2) or min(ref.shape) < 1:
+        raise ValueError('stoi: ref and deg must be waveforms (n,) or batches (B, n) of one shape, got {} and {}'.format(ref.shape, deg.shape))
+    ref, deg = ref.reshape(-1, ref.shape[-1]), deg.reshape(-1, deg.shape[-1])
+    ns = None if n_samples is None else np.asarray(n_samples)
+    if int(sampling_rate) == STOI_RATE:
+        return eng.stoi(ref, deg, n_samples=ns, extended=extended)['value'].copy()
+    ratio = float(STOI_RATE) / float(int(sampling_rate))
+    r10, d10 = eng.resample(ref, ratio, n_samples=ns), eng.resample(deg, ratio, n_samples=ns)
+    try:
+        ns10 = None if ns is None else np.array([resampled_valid(n, ratio) for n in ns.tolist()], np.int32)
+        if ns is None and resampled_valid(ref.shape[1], ratio) < r10.shape[1]:   # (the buffer is ceil(n ratio) long, the signal int(n ratio))
+            ns10 = np.full(ref.shape[0], resampled_valid(ref.shape[1], ratio), np.int32)
+        return eng.stoi(r10, d10, n_samples=ns10, extended=extended)['value'].copy()
+    finally:
+        r10.free()
+        d10.free()
 
 
 def mcd_scale(ref_db, max_db):

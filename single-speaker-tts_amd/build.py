@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libsstts_hip.so')
 # SOURCES, FLAGS and EXTRA_FLAGS are also what tools/build_variant.py builds a one-unit variant of the library with
-SOURCES = ['gemm_f32.hip', 'cbhg_tail.hip', 'gru.hip', 'decoder.hip', 'decoder_persistent.hip', 'decoder_ws.hip', 'griffin_lim.hip', 'gl_plan.hip', 'griffin_lim_generic.hip', 'reserve.hip', 'eval_loss.hip', 'features.hip', 'speech_end.hip', 'stretch.hip', 'resample.hip', 'phase_init.hip', 'cepstrum.hip', 'dtw.hip', 'f0.hip', 'loudness.hip', 'alignment.hip', 'token_times.hip', 'join.hip', 'limiter.hip', 'encode.hip', 'warp.hip', 'resample_segments.hip', 'shift.hip', 'equalizer.hip', 'compressor.hip', 'watermark.hip', 'api_handle.hip', 'api_stages.hip', 'api_griffin_lim.hip', 'api_pipeline.hip']
-HEADERS = ['tts_common.h', 'fft_wave.h', 'fft_lds.h', 'decoder.h', 'decoder_cluster.h', 'griffin_lim.h', 'gl_plan.h', 'lengths.h', 'segments.h', 'stretch_plan.h', 'resample_plan.h', 'phase_plan.h', 'cepstrum_plan.h', 'dtw_plan.h', 'f0_plan.h', 'loudness_plan.h', 'alignment_plan.h', 'token_times_plan.h', 'join_plan.h', 'limiter_plan.h', 'encode_plan.h', 'warp_plan.h', 'resample_segments_plan.h', 'shift_plan.h', 'equalizer_plan.h', 'equalizer_tile.h', 'compressor_plan.h', 'watermark_plan.h', 'synth_plan.h', 'api_internal.h', os.path.join('..', '..', 'include', 'sstts_hip.h')]
+SOURCES = ['gemm_f32.hip', 'cbhg_tail.hip', 'gru.hip', 'decoder.hip', 'decoder_persistent.hip', 'decoder_ws.hip', 'griffin_lim.hip', 'gl_plan.hip', 'griffin_lim_generic.hip', 'reserve.hip', 'eval_loss.hip', 'features.hip', 'speech_end.hip', 'stretch.hip', 'resample.hip', 'phase_init.hip', 'cepstrum.hip', 'dtw.hip', 'f0.hip', 'loudness.hip', 'alignment.hip', 'token_times.hip', 'join.hip', 'limiter.hip', 'encode.hip', 'warp.hip', 'resample_segments.hip', 'shift.hip', 'equalizer.hip', 'compressor.hip', 'watermark.hip', 'stoi.hip', 'api_handle.hip', 'api_stages.hip', 'api_griffin_lim.hip', 'api_pipeline.hip']
+HEADERS = ['tts_common.h', 'fft_wave.h', 'fft_lds.h', 'fft_lds_f64.h', 'decoder.h', 'decoder_cluster.h', 'griffin_lim.h', 'gl_plan.h', 'lengths.h', 'segments.h', 'stretch_plan.h', 'resample_plan.h', 'phase_plan.h', 'cepstrum_plan.h', 'dtw_plan.h', 'f0_plan.h', 'loudness_plan.h', 'alignment_plan.h', 'token_times_plan.h', 'join_plan.h', 'limiter_plan.h', 'encode_plan.h', 'warp_plan.h', 'resample_segments_plan.h', 'shift_plan.h', 'equalizer_plan.h', 'equalizer_tile.h', 'compressor_plan.h', 'watermark_plan.h', 'stoi_plan.h', 'synth_plan.h', 'api_internal.h', os.path.join('..', '..', 'include', 'sstts_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-Wno-unused-result']
 # Packed f32 VALU ops (v_pk_add/mul/fma_f32) issue slower than the two scalar ops they replace on gfx950 and
 # need aligned register pairs (extra v_mov); the SLP vectoriser forms them from complex arithmetic.  Measured
@@ -51,13 +51,15 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-val
 # compressor.hip: the detector's two recurrences likewise (e = aA e + bA e1 is two products and a sum); the envelope is held bit for bit
 # watermark.hip: a marked sample is x + (G e) s, a product and a sum in IEEE double with one rounding to float, and v is a product,
 # a quotient and rint; both are held to a numpy oracle bit for bit
+# stoi.hip: a frame's energy (E = E + t * t with t = w x) and a compacted sample (a sum of two products) are specified operation by
+# operation in IEEE double, and the kept frames are held to a numpy oracle exactly; so are the segment terms from given envelopes
 EXTRA_FLAGS = {'griffin_lim.hip': ['-fno-slp-vectorize'], 'griffin_lim_generic.hip': ['-fno-slp-vectorize'], 'shift.hip': ['-fno-slp-vectorize'],
                'features.hip': ['-fno-slp-vectorize', '-mllvm', '-disable-vector-combine'],
                'stretch.hip': ['-ffp-contract=off'], 'resample.hip': ['-ffp-contract=off'], 'phase_init.hip': ['-ffp-contract=off'],
                'dtw.hip': ['-ffp-contract=off'], 'f0.hip': ['-ffp-contract=off'], 'loudness.hip': ['-ffp-contract=off'],
                'alignment.hip': ['-ffp-contract=off'], 'join.hip': ['-ffp-contract=off'], 'limiter.hip': ['-ffp-contract=off'],
                'encode.hip': ['-ffp-contract=off'], 'warp.hip': ['-ffp-contract=off'], 'resample_segments.hip': ['-ffp-contract=off'],
-               'equalizer.hip': ['-ffp-contract=off'], 'compressor.hip': ['-ffp-contract=off'], 'watermark.hip': ['-ffp-contract=off']}
+               'equalizer.hip': ['-ffp-contract=off'], 'compressor.hip': ['-ffp-contract=off'], 'watermark.hip': ['-ffp-contract=off'], 'stoi.hip': ['-ffp-contract=off']}
 
 
 def _digest(paths, extra=()):

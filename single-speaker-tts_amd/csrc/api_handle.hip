@@ -4,7 +4,7 @@
 
 namespace tts_api {
 thread_local std::string g_create_error;
-const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw", "f0", "loudness", "alignment", "join", "limiter", "encode", "warp", "shift", "equalize", "compress", "watermark"};
+const char* const kStageNames[ST_COUNT] = {"encoder", "decoder", "postnet", "denorm", "gl_iter", "gl_final", "debug_gemm", "eval_loss", "features", "speech_end", "stretch", "resample", "phase_init", "mfcc", "dtw", "f0", "loudness", "alignment", "join", "limiter", "encode", "warp", "shift", "equalize", "compress", "watermark", "stoi"};
 }  // namespace tts_api
 
 namespace tts_api {

@@ -57,7 +57,7 @@ struct CbhgWeights {
     const float* gru_rec;     // packed recurrent weights, both directions
 };
 
-enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_WARP, ST_SHIFT, ST_EQUALIZE, ST_COMPRESS, ST_WATERMARK, ST_COUNT };
+enum Stage { ST_ENCODER = 0, ST_DECODER, ST_POSTNET, ST_DENORM, ST_GL_ITER, ST_GL_FINAL, ST_DEBUG_GEMM, ST_EVAL_LOSS, ST_FEATURES, ST_SPEECH_END, ST_STRETCH, ST_RESAMPLE, ST_PHASE_INIT, ST_MFCC, ST_DTW, ST_F0, ST_LOUDNESS, ST_ALIGNMENT, ST_JOIN, ST_LIMITER, ST_ENCODE, ST_WARP, ST_SHIFT, ST_EQUALIZE, ST_COMPRESS, ST_WATERMARK, ST_STOI, ST_COUNT };
 extern const char* const kStageNames[ST_COUNT];
 
 struct ProfSpan {
@@ -724,6 +724,10 @@ struct WmScratch { float* E; void* partial; };   // the blocks' maxima [B][block
 int watermark_scratch(tts_handle_t h, int B, int N, bool records, WmScratch* s);
 int watermark_impl(tts_handle_t h, const float* wav, float* out, int B, int N, const int32_t* n_samples, const tts_watermark_t& params,
                    tts_watermark_embed_stats_t* stats);
+// intelligibility (stoi.hip): the frame energies, the segments' sums and degenerate counts [B][frames]; the kept frames' indices
+// [B][frames] and the envelopes [B][2][15][frames] where the caller brings no room for them
+struct StoiScratch { double *energy, *sums; int32_t* degs; int32_t* index; double* env; };
+int stoi_scratch(tts_handle_t h, int B, int N, bool own_index, bool own_envelopes, StoiScratch* s);
 // the delivery encoder (encode.hip): arguments checked by the caller (encode_plan.h).  The records of a call that takes none
 struct EncScratch { tts_encode_stats_t* stats; };
 int encode_scratch(tts_handle_t h, int B, EncScratch* s);

@@ -6,12 +6,15 @@ window 1024, 80 HTK mel bands over 0 .. sr // 2); the per-file min / max are tak
 ``collect_reconstruction_error`` is the reference's :146-187 -- |STFT| of every recording followed by Griffin-Lim, the mean
 of the last iteration's mse -- as ragged batches: one tts_griffin_lim_ragged call reconstructs ``batch_size`` recordings of
 different lengths.  ``collect_loudness`` has no reference counterpart: the integrated loudness (ITU-R BS.1770-4, tts_loudness)
-of every recording and its spread over the corpus, which the dB statistics do not show.  The duration statistics and the plots of the reference module (:101-143, :190-258) are out of scope."""
+of every recording and its spread over the corpus, which the dB statistics do not show.  ``collect_intelligibility`` has none
+either: STOI / ESTOI (tts_stoi) of every recording's Griffin-Lim reconstruction against the recording itself -- whether what the
+vocoder makes of a perfect spectrogram can be understood, beside the spectrogram mse that says how well it converged.  The duration statistics and the plots of the reference module (:101-143, :190-258) are out of scope."""
 import numpy as np
 
 from ..audio import default_engine
 from ..audio.conversion import ms_to_samples
 from ..audio.io import load_wav
+from ..audio.metrics import stoi
 from ..audio.synthesis import griffin_lim_v2
 
 N_FFT = 1024
@@ -128,3 +131,42 @@ def collect_reconstruction_error(path_listing, n_iters, batch_size=32, seed=None
     total_mse = sum(mse_errors) / len(mse_errors)
     print('Dataset MSE with {} iterations: {}'.format(n_iters, total_mse))
     return total_mse
+
+
+def collect_intelligibility(path_listing, n_iters, batch_size=32, seed=None, momentum=0.0, phase_init=None, extended=False, engine=None):
+    """STOI (``extended``: ESTOI) of every recording's Griffin-Lim reconstruction after ``n_iters`` iterations against the
+    recording itself: |STFT| at the settings of ``collect_reconstruction_error`` (n_fft 2048, a 50 ms window, a 12.5 ms hop),
+    the same grouping -- ``batch_size`` files at a time, those of one sampling rate sorted by length and reconstructed in ONE
+    ragged Griffin-Lim call -- and the same seeding (``seed`` + the batch's first index; None: unseeded).  ``momentum`` and
+    ``phase_init`` (None: 'random') are ``griffin_lim_v2``'s.  The two signals are time-aligned by construction and compared
+    over the samples both hold (the reconstruction ends at the last whole hop); ``audio.metrics.stoi`` brings them to 10 kHz.
+    Returns a dict: ``stoi``, float64 (files,) in the order of the listing (NaN: fewer than 30 frames within 40 dB of the
+    recording's loudest), and ``min`` / ``max`` / ``mean`` / ``std`` over the recordings with a finite figure (NaN when there is
+    none), ``measured`` their count."""
+    eng = engine or default_engine()
+    paths = [p.decode() if isinstance(p, bytes) else p for p in path_listing]
+    n_fft = RECONSTRUCTION_N_FFT
+    values = np.full(len(paths), np.nan)
+    step = max(1, int(batch_size))
+    for i in range(0, len(paths), step):
+        loaded = [load_wav(p) for p in paths[i:i + step]]
+        for sr in sorted({r for _, r in loaded}):
+            win = ms_to_samples(RECONSTRUCTION_WIN_MS, sampling_rate=sr)
+            hop = ms_to_samples(RECONSTRUCTION_HOP_MS, sampling_rate=sr)
+            group = sorted((k for k, (_, r) in enumerate(loaded) if r == sr), key=lambda k: len(loaded[k][0]))
+            mag, frames = _padded_magnitudes(eng, [loaded[k][0] for k in group], n_fft, win, hop)
+            batch_seed = None if seed is None else int(seed) + i
+            wavs, _ = griffin_lim_v2(mag, win_length=win, hop_length=hop, n_fft=n_fft, n_iter=n_iters, seed=batch_seed, engine=eng,
+                                     momentum=momentum, n_frames=frames, phase_init='random' if phase_init is None else phase_init)
+            lens = np.array([min(len(loaded[k][0]), len(w)) for k, w in zip(group, wavs)], dtype=np.int32)
+            ref = np.zeros((len(group), int(lens.max())), dtype=np.float32)
+            deg = np.zeros_like(ref)
+            for row, k in enumerate(group):
+                ref[row, :lens[row]] = np.asarray(loaded[k][0], dtype=np.float32)[:lens[row]]
+                deg[row, :lens[row]] = wavs[row][:lens[row]]
+            values[[i + k for k in group]] = stoi(ref, deg, int(sr), extended=extended, n_samples=lens, engine=eng)
+    finite = values[np.isfinite(values)]
+    nan = float('nan')
+    return dict(stoi=values, measured=int(finite.size), min=float(finite.min()) if finite.size else nan,
+                max=float(finite.max()) if finite.size else nan, mean=float(finite.mean()) if finite.size else nan,
+                std=float(finite.std()) if finite.size else nan)

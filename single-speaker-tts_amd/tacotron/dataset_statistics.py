@@ -4,16 +4,19 @@ names -- which it crosses: the mean max mel dB is printed as ``mel_mag_ref_db``,
 likewise for the linear constants.
 
     python -m single-speaker-tts_amd.tacotron.dataset_statistics [--dataset-folder DIR] [--reconstruction-iters N] [--loudness]
+                                                                  [--reconstruction-stoi N [--estoi]]
 
 ``--reconstruction-iters N`` adds the reference's Griffin-Lim reconstruction error after N iterations
 (datasets.statistics.collect_reconstruction_error) behind the dB statistics; ``--loudness`` adds the corpus's integrated
 loudness after ITU-R BS.1770-4 (datasets.statistics.collect_loudness: min / max / mean / standard deviation in LUFS) behind
-those.  Without the switches the output is what it was."""
+those; ``--reconstruction-stoi N`` adds the intelligibility (STOI, with ``--estoi`` ESTOI) of every recording's Griffin-Lim
+reconstruction after N iterations against the recording (datasets.statistics.collect_intelligibility) behind those.  Without the
+switches the output is what it was."""
 import argparse
 import os
 
 from ..datasets.lj_speech import LJSpeechDatasetHelper
-from ..datasets.statistics import collect_decibel_statistics, collect_loudness, collect_reconstruction_error
+from ..datasets.statistics import collect_decibel_statistics, collect_intelligibility, collect_loudness, collect_reconstruction_error
 from .params import dataset_params
 
 
@@ -24,9 +27,16 @@ def main(argv=None):
                     help='also print the mean Griffin-Lim reconstruction error after N iterations')
     ap.add_argument('--loudness', action='store_true',
                     help='also print the integrated loudness (ITU-R BS.1770-4) of the recordings: min / max / mean / std in LUFS')
+    ap.add_argument('--reconstruction-stoi', type=int, default=None, metavar='N',
+                    help="also print the STOI of the recordings' Griffin-Lim reconstructions after N iterations: min / max / mean / std")
+    ap.add_argument('--estoi', action='store_true', help='with --reconstruction-stoi: the extended form (ESTOI)')
     args = ap.parse_args(argv)
     if args.reconstruction_iters is not None and args.reconstruction_iters < 1:
         ap.error('--reconstruction-iters: at least one iteration')
+    if args.reconstruction_stoi is not None and args.reconstruction_stoi < 1:
+        ap.error('--reconstruction-stoi: at least one iteration')
+    if args.estoi and args.reconstruction_stoi is None:
+        ap.error('--estoi needs --reconstruction-stoi')
     dataset = LJSpeechDatasetHelper(dataset_folder=args.dataset_folder, char_dict={'pad': 0, 'eos': 1}, fill_dict=True)
     if not os.path.exists(args.dataset_folder):
         print("Dataset folder '{}' could not be found.".format(args.dataset_folder))
@@ -58,6 +68,13 @@ def main(argv=None):
         print('loudness_lufs_mean = ', loud['mean'])
         print('loudness_lufs_std = ', loud['std'])
         print('loudness_measured = {} of {}'.format(loud['measured'], len(paths)))
+    if args.reconstruction_stoi is not None:
+        name = 'estoi' if args.estoi else 'stoi'
+        print('Collecting reconstruction {} for {} files ...'.format(name, len(paths)))
+        res = collect_intelligibility(paths, args.reconstruction_stoi, extended=args.estoi)
+        for key in ('min', 'max', 'mean', 'std'):
+            print('reconstruction_{}_{} = '.format(name, key), res[key])
+        print('reconstruction_{}_measured = {} of {}'.format(name, res['measured'], len(paths)))
     return 0
 
 

@@ -24,6 +24,12 @@ lengths the distortion uses -- so that its colouring cancels, tts_f0 tracks both
 every utterance its F0 RMSE in cents and Hz, its voicing error and its gross pitch error.  The path is computed whether or not
 ``mcd`` reports its figure.
 
+Intelligibility.  With ``stoi`` (``--stoi``, ``--estoi`` for the extended form) every batch is also run teacher-forced
+(``Tacotron.teacher_forced_device``), so that prediction and target are aligned frame by frame; the predicted and the target linear
+spectrograms go through the same ragged Griffin-Lim -- one seed, one set of frame counts, as ``batch_f0`` does -- and
+``audio.metrics.stoi`` compares the two waveforms (tts_stoi behind the resampler): ``metric/stoi`` or ``metric/estoi``, the mean
+over the utterances with a finite figure, and ``stoi_utterances``, their count.
+
 TensorBoard events are not written: every evaluated checkpoint appends one JSON line with the reference's
 summary tags (``loss/loss``, ``loss/loss_decoder``, ``loss/loss_post_processing``) and its global step to
 ``<checkpoint_dir>/<checkpoint_save_run>/eval_summaries.jsonl``.
@@ -181,8 +187,48 @@ def batch_f0(model, feed, out, path, n_pred, n_target, f0_iters=None, f0_min=60.
     return res
 
 
+def batch_stoi(model, feed, extended=False, stoi_iters=None, seed=0, want_wavs=False):
+    """STOI (``extended``: ESTOI) of every utterance of one batch: ONE teacher-forced pass (``teacher_forced_device`` with
+    ``want_linear``), then the predicted and the target linear spectrograms both become waveforms through the same ragged
+    Griffin-Lim -- the same seed and the same frame counts, ``ph_time_frames * r`` -- and ``audio.metrics.stoi`` measures the
+    prediction's against the target's.  -> (B,) float64 (NaN: fewer than 30 frames within 40 dB of the target's loudest), or None
+    where the batch is shorter than the vocoder's shortest signal; with ``want_wavs`` also (the target's waveforms, the
+    prediction's, their lengths), host arrays."""
+    from ..audio.metrics import stoi
+    from ..audio.conversion import ms_to_samples
+    eng, hp = model.engine, model.hparams
+    loader = dataset_params.dataset_loader
+    win_len, hop = ms_to_samples(hp.win_len, hp.sampling_rate), ms_to_samples(hp.win_hop, hp.sampling_rate)
+    B = feed['ph_sentences'].shape[0]
+    F = 1 + hp.n_fft // 2
+    target = np.ascontiguousarray(feed['ph_lin_specs'], dtype=np.float32).reshape(B, -1, F)
+    T = target.shape[1]
+    min_frames = hp.n_fft // 2 // hop + 2            # the smallest n with hop (n - 1) > n_fft / 2
+    if T < min_frames:
+        return None
+    out = model.teacher_forced_device(feed['ph_sentences'], feed['ph_mel_specs'], None, want_mel=False, want_alignments=False,
+                                      want_linear=True)
+    n = np.asarray(feed['ph_time_frames'], np.int32) * eng.cfg.reduction
+    frames = np.minimum(T, np.maximum(min_frames, n)).astype(np.int32)
+    lens = (hop * (frames - 1)).astype(np.int32)
+    wavs = []
+    for lin in (target, out['linear']):
+        mag = eng.denorm_power(lin, loader.mel_mag_ref_db, loader.mel_mag_max_db, hp.magnitude_power)
+        wav, _ = eng.griffin_lim(mag, hp.reconstruction_iterations if stoi_iters is None else stoi_iters, win_len, hop, hp.n_fft,
+                                 seed=seed, want_mse=False, momentum=0.0, n_frames=frames)
+        wavs.append(wav.to_host()[:, :int(lens.max())].copy())
+        mag.free()
+        wav.free()
+    for a in out.values():
+        if hasattr(a, 'free'):
+            a.free()
+    values = stoi(wavs[0], wavs[1], hp.sampling_rate, extended=extended, n_samples=lens, engine=eng)
+    return (values, wavs[0], wavs[1], lens) if want_wavs else values
+
+
 def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_save_run=None, verbose=True, mcd=False, mcd_coeffs=13,
-             mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0, attention=False):
+             mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0, attention=False, stoi=False, estoi=False,
+             stoi_iters=None):
     """reference :153-257.  Restores ``checkpoint_file`` into ``model`` (a ``Tacotron(..., Mode.EVAL)``) once, runs every
     feed dict of ``batches`` through tts_evaluate and returns ``{loss, loss_decoder, loss_post_processing, global_step,
     n_batches}``: the per-batch float32 losses averaged unweighted over the batches.  Raises if no batch ran.  Appends
@@ -196,7 +242,13 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
     With ``attention`` the result and the summary line gain ``attention/<flag>`` for every flag of
     ``attention_check.FLAGS`` -- the utterances of the epoch that carry it -- ``attention/mean_focus``, the mean over the
     utterances of focus_sum / n_steps, and ``attention_utterances``: ``Engine.alignment_stats`` on every batch's alignments, with
-    the batch's own sentence lengths and frame counts; without it nothing of the run, the result or the line changes."""
+    the batch's own sentence lengths and frame counts; without it nothing of the run, the result or the line changes.
+    With ``stoi`` the result and the summary line gain ``metric/stoi`` -- with ``estoi`` ``metric/estoi`` instead -- the mean of
+    :func:`batch_stoi` over the utterances with a finite figure (NaN when there is none), and ``stoi_utterances``, their count
+    (``stoi_iters``: Griffin-Lim iterations, default the model's ``reconstruction_iterations``); without it nothing of the run,
+    the result or the line changes."""
+    if estoi and not stoi:
+        raise ValueError('evaluate: estoi needs stoi')
     if model._mode != Mode.EVAL:
         raise ValueError('evaluate() needs a Tacotron in Mode.EVAL')
     global_step = global_step_of(checkpoint_file)
@@ -210,6 +262,7 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
     n_batches = 0
     mcds = []
     f0s = []
+    stois = []
     records = []
     for feed in batches:
         out = model.evaluate_device(feed['ph_sentences'], feed['ph_mel_specs'], feed['ph_lin_specs'],
@@ -228,6 +281,10 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
                 f0s.append(errs)
         elif mcd:
             mcds.append(batch_mcd(model, feed, out, mcd_coeffs, mcd_stop_at_silence))
+        if stoi:
+            values = batch_stoi(model, feed, extended=bool(estoi), stoi_iters=stoi_iters)
+            if values is not None:
+                stois.append(values)
         n_batches += 1
     if n_batches == 0:
         raise Exception('Error: No batches were processed!')
@@ -245,6 +302,12 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
             result['metric/' + key] = float(np.mean(values)) if values.size else float('nan')
             if key == 'f0_rmse_cents':
                 result['f0_utterances'] = int(values.size)
+    stoi_key = 'metric/estoi' if estoi else 'metric/stoi'
+    if stoi:
+        values = np.concatenate(stois) if stois else np.zeros(0)
+        values = values[np.isfinite(values)]
+        result[stoi_key] = float(np.mean(values)) if values.size else float('nan')
+        result['stoi_utterances'] = int(values.size)
     if attention:
         from . import attention_check
         every = np.concatenate(records)
@@ -261,6 +324,8 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
         if f0:
             print('[evaluate] step: {}, utterances: {}, f0_rmse: {:.3f} cents / {:.3f} Hz, vuv_error: {:.4f}, gross_pitch_error: {:.4f}'.format(
                 global_step, result['f0_utterances'], *(result['metric/' + key] for key in F0_KEYS)))
+        if stoi:
+            print('[evaluate] step: {}, utterances: {}, {}: {:.6f}'.format(global_step, result['stoi_utterances'], stoi_key[7:], result[stoi_key]))
     checkpoint_dir = evaluation_params.checkpoint_dir if checkpoint_dir is None else checkpoint_dir
     if checkpoint_dir:
         save_dir = os.path.join(checkpoint_dir, checkpoint_save_run or evaluation_params.checkpoint_save_run)
@@ -274,6 +339,9 @@ def evaluate(model, checkpoint_file, batches, checkpoint_dir=None, checkpoint_sa
             for key in F0_KEYS:
                 line['metric/' + key] = result['metric/' + key]
             line['f0_utterances'] = result['f0_utterances']
+        if stoi:
+            line[stoi_key] = result[stoi_key]
+            line['stoi_utterances'] = result['stoi_utterances']
         if attention:
             for key in sorted(k for k in result if k.startswith('attention')):
                 line[key] = result[key]
@@ -295,7 +363,8 @@ def collect_checkpoint_paths(checkpoint_dir):
 
 def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, batch_size=None, checkpoint_dir=None,
                         checkpoint_save_run=None, hparams=None, device_id=0, verbose=True, mcd=False, mcd_coeffs=13,
-                        mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0, attention=False):
+                        mcd_stop_at_silence=None, f0=False, f0_iters=None, f0_min=60.0, f0_max=500.0, attention=False, stoi=False,
+                        estoi=False, stoi_iters=None):
     """One cycle of the reference's ``__eval_cycle`` (:336-352): a dataset loader, the batches, a model with its own
     engine, :func:`evaluate`; the engine is released afterwards."""
     from ..datasets.lj_speech import LJSpeechDatasetHelper
@@ -309,7 +378,7 @@ def evaluate_checkpoint(checkpoint_file, dataset_folder=None, max_samples=None, 
         return evaluate(model, checkpoint_file, batches, checkpoint_dir=checkpoint_dir,
                         checkpoint_save_run=checkpoint_save_run, verbose=verbose, mcd=mcd, mcd_coeffs=mcd_coeffs,
                         mcd_stop_at_silence=mcd_stop_at_silence, f0=f0, f0_iters=f0_iters, f0_min=f0_min, f0_max=f0_max,
-                        attention=attention)
+                        attention=attention, stoi=stoi, estoi=estoi, stoi_iters=stoi_iters)
     finally:
         model.engine.close()
 
@@ -321,12 +390,13 @@ def main(argv=None):
                                                            [--dataset-folder F] [--max-samples N] [--batch-size B]
                                                            [--mcd [--mcd-coeffs K] [--mcd-stop-at-silence DB]]
                                                            [--f0 [--f0-iters N] [--f0-min HZ] [--f0-max HZ]]
-                                                           [--attention]
+                                                           [--attention] [--stoi [--estoi] [--stoi-iters N]]
 
     The options override the ``evaluation_params`` / ``dataset_params`` fields of the same name.  Without ``--all``
     (``evaluate_all_checkpoints``) the latest checkpoint of ``<checkpoint_dir>/<load_run>`` is evaluated, with it every
     checkpoint its listing file names.  ``--mcd`` adds the mel-cepstral distortion, ``--f0`` the F0 RMSE, voicing error
-    and gross pitch error along the same alignment (module docstring).  Prints one JSON line per checkpoint."""
+    and gross pitch error along the same alignment, ``--stoi`` the intelligibility of the teacher-forced prediction against its
+    target (module docstring).  Prints one JSON line per checkpoint."""
     import argparse
     from .checkpoint import latest_checkpoint
     ap = argparse.ArgumentParser(prog='tacotron.evaluate')
@@ -349,7 +419,16 @@ def main(argv=None):
     ap.add_argument('--f0-max', type=float, default=None, metavar='HZ', help='highest F0 searched (default 500)')
     ap.add_argument('--attention', action='store_true',
                     help='also report the attention diagnostics: utterances per flag of tacotron.attention_check, and the mean focus')
+    ap.add_argument('--stoi', action='store_true',
+                    help="also report the STOI of the teacher-forced prediction's waveform against the target's")
+    ap.add_argument('--estoi', action='store_true', help='with --stoi: the extended form (ESTOI)')
+    ap.add_argument('--stoi-iters', type=int, default=None, metavar='N',
+                    help="Griffin-Lim iterations of --stoi (default: the model's reconstruction_iterations)")
     args = ap.parse_args(argv)
+    if not args.stoi and (args.estoi or args.stoi_iters is not None):
+        ap.error('--estoi and --stoi-iters need --stoi')
+    if args.stoi_iters is not None and args.stoi_iters < 0:
+        ap.error('--stoi-iters must be >= 0')
     if not args.f0 and (args.f0_iters is not None or args.f0_min is not None or args.f0_max is not None):
         ap.error('--f0-iters, --f0-min and --f0-max need --f0')
     if args.f0_iters is not None and args.f0_iters < 0:
@@ -373,7 +452,8 @@ def main(argv=None):
                                   batch_size=args.batch_size, checkpoint_dir=args.checkpoint_dir,
                                   checkpoint_save_run=args.save_run, device_id=args.device, mcd=args.mcd,
                                   mcd_coeffs=args.mcd_coeffs, mcd_stop_at_silence=args.mcd_stop_at_silence, f0=args.f0,
-                                  f0_iters=args.f0_iters, f0_min=f0_min, f0_max=f0_max, attention=args.attention)
+                                  f0_iters=args.f0_iters, f0_min=f0_min, f0_max=f0_max, attention=args.attention,
+                                  stoi=args.stoi, estoi=args.estoi, stoi_iters=args.stoi_iters)
         print(json.dumps(dict(res, checkpoint=checkpoint_file)))
     return 0
 

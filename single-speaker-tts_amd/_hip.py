@@ -385,13 +385,30 @@ def _int32_ptr(a):
     return a.ctypes.data_as(POINTER(c_int32)) if a is not None else None
 
 
-def _checked_lengths(lengths, hi, name, bound):
-    """Host lengths -- an integer array of the batch's shape already -- as a contiguous int32 array, every one in 1 .. ``hi``;
-    the ValueError speaks of the caller's argument ``name`` and of its ``bound``."""
+def _checked_lengths(lengths, hi, name, bound, lo=1):
+    """Host lengths -- an integer array of the batch's shape already -- as a contiguous int32 array, every one in ``lo`` .. ``hi``
+    (``lo`` 0: a row may hold nothing); the ValueError speaks of the caller's argument ``name`` and of its ``bound``."""
     for b, n in enumerate(lengths.tolist()):
-        if not 1 <= n <= hi:
-            raise ValueError('{}[{}] = {} is not in 1 .. {} = {}'.format(name, b, n, bound, hi))
+        if not lo <= n <= hi:
+            raise ValueError('{}[{}] = {} is not in {} .. {} = {}'.format(name, b, n, lo, bound, hi))
     return np.ascontiguousarray(lengths, dtype=np.int32)
+
+
+def _sample_lengths(n_samples, B, n, lo=1):
+    """``n_samples`` of a call on B rows of n samples -- None, or B host integers in ``lo`` .. n -- as None or a checked int32 array"""
+    if n_samples is None:
+        return None
+    ns = np.asarray(n_samples)
+    if ns.shape != (B,) or ns.dtype.kind not in 'iu':
+        raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
+    return _checked_lengths(ns, n, 'n_samples', 'n', lo)
+
+
+def _records(buf, record):
+    """a device buffer of B records -- (B, k) of a plain type -- as the host array (B,) of ``record``; the buffer is freed"""
+    host = buf.to_host().view(record).reshape(-1)
+    buf.free()
+    return host
 
 
 def _waveforms(what, wavs, uniform=False):
@@ -1450,12 +1467,7 @@ def resample_segment_list(segments, B, n, n_samples=None):
     if B < 1 or n < 1 or S < 1:
         raise ValueError('resample_segments: need B, n, S >= 1')
     _segment_counts_check('resample_segments', S, B, 'tts_resample_segments_max()')
-    ns = None
-    if n_samples is not None:
-        ns = np.asarray(n_samples)
-        if ns.shape != (B,) or ns.dtype.kind not in 'iu':
-            raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-        ns = _checked_lengths(ns, n, 'n_samples', 'n')
+    ns = _sample_lengths(n_samples, B, n)
     _segment_rows_check('resample_segments', q['row'].tolist(), B)
     n_out = np.zeros(B, dtype=np.int64)
     count = np.zeros(S, dtype=np.int64)
@@ -1570,7 +1582,7 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
 
 
 # The per-call synthesis settings.  The handle holds each of them (tts_set_* / tts_set_option; the C ABI has no getters, so the
-# engine mirrors them); ``Engine.synthesize`` and ``Engine.synthesize_host`` take all eight as keywords, ``Engine.griffin_lim``
+# engine mirrors them); ``Engine.synthesize`` and ``Engine.synthesize_host`` take them as keywords, ``Engine.griffin_lim``
 # takes ``momentum`` and ``phase_init``.  None always means the handle's setting as it stands; any other value holds for that
 # call alone (``Engine._settings``).  In the order they are checked and applied in:
 #   ``momentum``: the fast Griffin-Lim momentum in [0, 1) (librosa's and torchaudio's ``momentum``; 0 = the reference's plain
@@ -1598,18 +1610,28 @@ def _strided_rows(what, spec, B, T, F, row_stride, width='F'):
 #   ``limiter``: a ceiling or ``(ceiling, lookahead_ms, oversample)`` (tts_set_limiter, off unless ``set_limiter`` changed it): the
 #     call's final rows go through ``limit`` last, behind the loudness gain or the peak normalisation, each utterance over the
 #     samples its row holds; the look-ahead is taken at the model's sampling rate.
-#   ``output`` (the one row of HOST_SETTINGS, behind the eight of SETTINGS): a format name or ``(format, dither, rate_in,
-#     rate_out)`` (tts_set_output, off unless ``set_output`` changed it): ``synthesize_host`` alone -- the call's final rows are resampled and encoded on the device, behind the limiter, and only the
-#     codes and their records travel to the host (``wait_host_encoded``).  ``synthesize`` hands out device rows: ``encode`` is
-#     its callers' to call.
-#   ``token_times`` (the one row of MARK_SETTINGS, behind those nine): False, True or ``(enabled, pad_id, max_jump)``
-#     (tts_set_token_times, off unless ``set_token_times`` changed it): the call also searches its alignments for the best monotone
-#     path behind its decoder, with no host wait; ``synth_token_times(B)`` / ``wait_host_token_times`` fetch the step every token
-#     starts at.  Nothing else of the call changes.
+#   ``output``: a format name or ``(format, dither, rate_in, rate_out)`` (tts_set_output, off unless ``set_output`` changed it):
+#     ``synthesize_host`` alone -- the call's final rows are resampled and encoded on the device, behind the limiter, and only the
+#     codes and their records travel to the host (``wait_host_encoded``).  ``synthesize`` refuses the keyword: it hands out device
+#     rows, and ``encode`` is its callers' to call.
+#   ``token_times``: False, True or ``(enabled, pad_id, max_jump)`` (tts_set_token_times, off unless ``set_token_times`` changed
+#     it): the call also searches its alignments for the best monotone path behind its decoder, with no host wait;
+#     ``synth_token_times(B)`` / ``wait_host_token_times`` fetch the step every token starts at.  Nothing else of the call changes.
+#   ``watermark``: a key, ``(key, payload)`` or the full tuple of ``watermark_setting`` (tts_set_watermark, off unless
+#     ``set_watermark`` changed it): the call's rows go through ``watermark_embed``.  The defaults are UNTUNED.
+#   ``compressor``: a profile name of CMP_PROFILES or ``(threshold_db, ratio, knee_db, attack_ms, release_ms, makeup_db)``
+#     (tts_set_compressor, off unless ``set_compressor`` changed it): the call's rows go through ``compress``; the coefficients are
+#     made at the model's sampling rate.
+#   ``equalizer``: a profile name of EQ_PROFILES, a list of ``(kind, f0_hz, q, gain_db)`` sections or an (S, 5) array of sections
+#     (tts_set_equalizer, off unless ``set_equalizer`` changed it): the call's rows go through ``equalize``; a design is made at the
+#     model's sampling rate.  A boost behind the peak normalisation can pass 1.0: give it a limiter or a loudness target.
+# The last three run in place behind Griffin-Lim, the pitch resampler and the peak normalisation -- the equaliser, then the
+# compressor, then the watermark -- and ahead of the loudness gain and the limiter, each utterance over the samples its row holds.
+# Lengths, shapes and timing marks do not change (the equaliser's group delay of a few samples is ignored).
 # A row: the keyword, the Engine attribute that mirrors the handle's value, the handle's initial value, the check that turns
-# the keyword into the mirror's value (ValueError before a handle is touched), and how a value is applied -- a ``set_option``
-# key or a call of the engine's ``set_*`` method.
-Setting = collections.namedtuple('Setting', 'keyword mirror initial check apply')
+# the keyword into the mirror's value (ValueError before a handle is touched), how a value is applied -- a ``set_option``
+# key or a call of the engine's ``set_*`` method -- and whether the keyword is the host form's alone.
+Setting = collections.namedtuple('Setting', 'keyword mirror initial check apply host_only', defaults=(False,))
 SETTINGS = (
     Setting('momentum', '_gl_momentum', 0, momentum_thousandths, 'gl_momentum'),
     Setting('stop_at_silence', '_end_of_speech', (False, 0.0, 0), lambda v: (True,) + stop_at_silence_setting(v),
@@ -1620,37 +1642,10 @@ SETTINGS = (
     Setting('loudness', '_loudness', None, loudness_setting, lambda engine, v: engine.set_loudness(v)),
     Setting('alignment_stats', '_alignment_stats', (False, 0), alignment_stats_setting, lambda engine, v: engine.set_alignment_stats(*v)),
     Setting('limiter', '_limiter', None, limiter_setting, lambda engine, v: engine.set_limiter(v)),
-)
-# ... and the one setting of the host form alone, checked and applied behind those (``Engine.synthesize`` refuses the keyword):
-HOST_SETTINGS = (
-    Setting('output', '_output', OUTPUT_OFF, output_setting, lambda engine, v: engine.set_output(v)),
-)
-# ... and the timing marks, a table of their own behind both: checked last, applied last, put back first
-MARK_SETTINGS = (
+    Setting('output', '_output', OUTPUT_OFF, output_setting, lambda engine, v: engine.set_output(v), host_only=True),
     Setting('token_times', '_token_times', TOKEN_TIMES_OFF, token_times_setting, lambda engine, v: engine.set_token_times(*v)),
-)
-# ... and the tone, a table of its own behind the three (their lengths and contents are fixed): ``equalizer`` -- a profile name of
-# EQ_PROFILES, a list of ``(kind, f0_hz, q, gain_db)`` sections or an (S, 5) array of sections (tts_set_equalizer, off unless
-# ``set_equalizer`` changed it): the call's rows go through ``equalize`` in place, behind Griffin-Lim, the pitch resampler and the
-# peak normalisation and ahead of the loudness gain and the limiter, each utterance over the samples its row holds; a design is made
-# at the model's sampling rate.  Lengths, shapes and timing marks do not change (the group delay of a few samples is ignored); a
-# boost behind the peak normalisation can pass 1.0: give it a limiter or a loudness target.
-# ... and the dynamics, a fifth table, checked and applied AHEAD of the tone (the equaliser stays the last one set and the first
-# one put back): ``compressor`` -- a profile name of CMP_PROFILES or ``(threshold_db, ratio, knee_db, attack_ms, release_ms,
-# makeup_db)`` (tts_set_compressor, off unless ``set_compressor`` changed it): the call's rows go through ``compress`` in place,
-# behind the equaliser and ahead of the loudness gain and the limiter, each utterance over the samples its row holds; the
-# coefficients are made at the model's sampling rate.  Lengths, shapes and timing marks do not change.
-# ... and the watermark, a table of its own ahead of the dynamics (checked and applied behind the timing marks): ``watermark`` -- a
-# key, ``(key, payload)`` or the full tuple of ``watermark_setting`` (tts_set_watermark, off unless ``set_watermark`` changed it):
-# the call's rows go through ``watermark_embed`` in place, behind the compressor and ahead of the loudness gain and the limiter, each
-# utterance over the samples its row holds.  Lengths, shapes and timing marks do not change.  The defaults are UNTUNED.
-WATERMARK_SETTINGS = (
     Setting('watermark', '_watermark', None, watermark_setting, lambda engine, v: engine.set_watermark(v)),
-)
-DYNAMICS_SETTINGS = (
     Setting('compressor', '_compressor', None, compressor_setting, lambda engine, v: engine.set_compressor(v)),
-)
-TONE_SETTINGS = (
     Setting('equalizer', '_equalizer', None, equalizer_setting, lambda engine, v: engine.set_equalizer(v)),
 )
 
@@ -1663,7 +1658,7 @@ class _Settings(object):
 
     def __init__(self, engine, per_call):
         self.engine = engine
-        self.rows = [row for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + WATERMARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS if row.keyword in per_call]
+        self.rows = [row for row in SETTINGS if row.keyword in per_call]
         self.values = {row.keyword: None if per_call[row.keyword] is None else row.check(per_call[row.keyword]) for row in self.rows}
 
     def __getitem__(self, keyword):
@@ -1790,7 +1785,7 @@ class Engine(object):
 
     def _init_settings(self):
         """the mirrors of SETTINGS as a fresh handle has them; the ``set_*`` methods and ``set_option`` keep them"""
-        for row in SETTINGS + HOST_SETTINGS + MARK_SETTINGS + WATERMARK_SETTINGS + DYNAMICS_SETTINGS + TONE_SETTINGS:
+        for row in SETTINGS:
             setattr(self, row.mirror, row.initial)
 
     def _settings(self, **per_call):
@@ -2371,12 +2366,7 @@ class Engine(object):
         deg, _single_d, Bd, nd = _waveforms('stoi', deg)
         if (B, n) != (Bd, nd):
             raise ValueError('stoi: ref and deg must have one shape, got {} and {}'.format((B, n), (Bd, nd)))
-        ns = None
-        if n_samples is not None:
-            ns = np.asarray(n_samples)
-            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
-                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-            ns = _checked_lengths(ns, n, 'n_samples', 'n')
+        ns = _sample_lengths(n_samples, B, n)
         cap = stoi_frames(n)
         if cap > STOI_MAX_FRAMES:
             raise ValueError('stoi: {} frames are more than {} (tts_stoi_max_frames)'.format(cap, STOI_MAX_FRAMES))
@@ -2389,8 +2379,7 @@ class Engine(object):
             self._check_or_free(self.lib.tts_stoi(self.handle, p_ref, p_deg, B, n, _int32_ptr(ns), int(extended), rec.data_ptr(),
                                                   index.data_ptr() if want_index else None, env.data_ptr() if want_envelopes else None),
                                 rec, index, env)
-            answer = (rec.to_host().view(STOI_RECORD).reshape(B),)
-            rec.free()
+            answer = (_records(rec, STOI_RECORD),)
             for extra in (index, env):
                 if extra is not None:
                     answer += (extra.to_host()[..., :cap],)
@@ -2411,16 +2400,24 @@ class Engine(object):
         return w, e
 
     # ------------------------------------------------------------------ loudness
-    def _ragged_waveforms(self, what, wavs, n_samples):
-        """``(wavs, single, B, n, the checked lengths or None)`` of a call on waveforms with per-utterance lengths"""
+    def _ragged_waveforms(self, what, wavs, n_samples, lo=1):
+        """``(wavs, single, B, n, the checked lengths or None)`` of a call on waveforms with per-utterance lengths in ``lo`` .. n"""
         wavs, single, B, n = _waveforms(what, wavs)
-        ns = None
-        if n_samples is not None:
-            ns = np.asarray(n_samples)
-            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
-                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-            ns = _checked_lengths(ns, n, 'n_samples', 'n')
-        return wavs, single, B, n, ns
+        return wavs, single, B, n, _sample_lengths(n_samples, B, n, lo)
+
+    def _rows_out(self, what, wavs, single, out, B, n):
+        """Where a stage that filters B rows of n samples puts them, ``(the input's pointer, the output array, whether that is
+        fresh)``: ``out`` where one is given (a device buffer of the input's size, which may be the input), else a device input in
+        place, a host input uploaded fresh -- a single waveform as (n,).  The stages that only work in place give ``out`` None."""
+        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
+            raise ValueError('{}: out must be a device buffer of {} floats'.format(what, B * n))
+        if out is None and not _is_device(wavs):
+            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
+            if single:
+                out.shape = (n,)
+            return out.data_ptr(), out, True
+        p_wav, _k = self._in(wavs, np.float32)
+        return p_wav, wavs if out is None else out, False
 
     def _loudness_args(self, what, wavs, sampling_rate, n_samples):
         return (loudness_sampling_rate(what, sampling_rate),) + self._ragged_waveforms(what, wavs, n_samples)
@@ -2455,16 +2452,13 @@ class Engine(object):
         samples at or behind them are neither read nor written.  ``return_mean_square``: also z as measured before the gain."""
         sr, wavs, single, B, n, ns = self._loudness_args('loudness_normalize', wavs, sampling_rate, n_samples)
         target, peak = loudness_target('loudness_normalize', target_lufs, max_peak)
-        fresh = not _is_device(wavs)
-        out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32)) if fresh else wavs
+        _p, out, fresh = self._rows_out('loudness_normalize', wavs, single, None, B, n)
         z, g = self.empty((B,), np.float64), self.empty((B,), np.float64)
         self._check_or_free(self.lib.tts_loudness_normalize(self.handle, out.data_ptr(), B, n, _int32_ptr(ns), sr, target, peak, z.data_ptr(),
                                                             g.data_ptr()), z, g, out if fresh else None)
         gains, z_host = g.to_host(), z.to_host()
         z.free()
         g.free()
-        if fresh and single:
-            out.shape = (n,)
         return (out, gains, z_host) if return_mean_square else (out, gains)
 
     # ------------------------------------------------------------------ true peak and limiter
@@ -2494,15 +2488,10 @@ class Engine(object):
         (B,) of ``LIMIT_RECORD``.  ``n_samples`` as in ``true_peak``: samples at or behind them are neither read nor written."""
         wavs, single, B, n, ns = self._ragged_waveforms('limit', wavs, n_samples)
         c, L, o = limit_arguments('limit', ceiling, lookahead, oversample)
-        fresh = not _is_device(wavs)
-        out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32)) if fresh else wavs
+        _p, out, fresh = self._rows_out('limit', wavs, single, None, B, n)
         st = self.empty((B, 2), np.float64)   # (B records of 16 bytes)
         self._check_or_free(self.lib.tts_limit(self.handle, out.data_ptr(), B, n, _int32_ptr(ns), c, L, o, st.data_ptr()), st, out if fresh else None)
-        stats = st.to_host().view(LIMIT_RECORD).reshape(B)
-        st.free()
-        if fresh and single:
-            out.shape = (n,)
-        return out, stats
+        return out, _records(st, LIMIT_RECORD)
 
     # ------------------------------------------------------------------ the equaliser
     def equalize(self, wavs, sections, n_samples=None, out=None):
@@ -2518,19 +2507,9 @@ class Engine(object):
         if setting is None:
             raise ValueError('equalize: sections are needed')
         sos = equalizer_sections(setting, self.sampling_rate)
-        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
-            raise ValueError('equalize: out must be a device buffer of {} floats'.format(B * n))
-        fresh = out is None and not _is_device(wavs)
-        if fresh:
-            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
-            p_wav = out.data_ptr()
-        else:
-            p_wav, _k = self._in(wavs, np.float32)
-            out = wavs if out is None else out
+        p_wav, out, fresh = self._rows_out('equalize', wavs, single, out, B, n)
         self._check_or_free(self.lib.tts_equalize(self.handle, p_wav, out.data_ptr(), B, n, _int32_ptr(ns),
                                                   sos.ctypes.data_as(POINTER(ctypes.c_double)), len(sos)), out if fresh else None)
-        if fresh and single:
-            out.shape = (n,)
         return out
 
     # ------------------------------------------------------------------ the compressor
@@ -2549,26 +2528,13 @@ class Engine(object):
         if setting is None:
             raise ValueError('compress: parameters are needed')
         p = TtsCompressor(*compressor_params(setting, self.sampling_rate))
-        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
-            raise ValueError('compress: out must be a device buffer of {} floats'.format(B * n))
-        fresh = out is None and not _is_device(wavs)
-        if fresh:
-            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
-            p_wav = out.data_ptr()
-        else:
-            p_wav, _k = self._in(wavs, np.float32)
-            out = wavs if out is None else out
+        p_wav, out, fresh = self._rows_out('compress', wavs, single, out, B, n)
         env = self.empty((B, n), np.float64) if envelope else None
         st = self.empty((B, 2), np.float64) if stats else None   # (B records of 16 bytes)
         self._check_or_free(self.lib.tts_compress(self.handle, p_wav, out.data_ptr(), B, n, _int32_ptr(ns), ctypes.addressof(p),
                                                   env.data_ptr() if envelope else None, st.data_ptr() if stats else None),
                             out if fresh else None, env, st)
-        if fresh and single:
-            out.shape = (n,)
-        answer = (out,) + ((env,) if envelope else ())
-        if stats:
-            answer += (st.to_host().view(COMPRESS_RECORD).reshape(B),)
-            st.free()
+        answer = (out,) + ((env,) if envelope else ()) + ((_records(st, COMPRESS_RECORD),) if stats else ())
         return answer if len(answer) > 1 else out
 
     # ------------------------------------------------------------------ the watermark
@@ -2577,16 +2543,7 @@ class Engine(object):
         setting = watermark_setting(watermark)
         if setting is None:
             raise ValueError('{}: a key is needed'.format(what))
-        ns = None
-        if n_samples is not None:
-            ns = np.asarray(n_samples)
-            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
-                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-            for b, k in enumerate(ns.tolist()):
-                if not 0 <= k <= n:
-                    raise ValueError('n_samples[{}] = {} is not in 0 .. n = {}'.format(b, k, n))
-            ns = np.ascontiguousarray(ns, dtype=np.int32)
-        return wavs, single, B, n, ns, TtsWatermark(*setting)
+        return wavs, single, B, n, _sample_lengths(n_samples, B, n, 0), TtsWatermark(*setting)
 
     def watermark_embed(self, wavs, watermark, n_samples=None, out=None, stats=False):
         """tts_watermark_embed: a keyed spread-spectrum carrier under the local envelope added to every utterance of ``wavs`` -- one
@@ -2597,25 +2554,11 @@ class Engine(object):
         0 .. n (host integers) -- samples at or behind them carry no mark; None: all n.  ``stats``: also a host array (B,) of
         ``WATERMARK_EMBED_RECORD``.  The bits of tests/watermark_oracle.py."""
         wavs, single, B, n, ns, p = self._watermark_args('watermark_embed', wavs, watermark, n_samples)
-        if out is not None and (not _is_device(out) or int(np.prod(out.shape)) != B * n):
-            raise ValueError('watermark_embed: out must be a device buffer of {} floats'.format(B * n))
-        fresh = out is None and not _is_device(wavs)
-        if fresh:
-            out = self.to_device(np.ascontiguousarray(wavs, dtype=np.float32))
-            p_wav = out.data_ptr()
-        else:
-            p_wav, _k = self._in(wavs, np.float32)
-            out = wavs if out is None else out
+        p_wav, out, fresh = self._rows_out('watermark_embed', wavs, single, out, B, n)
         st = self.empty((B, 2), np.float64) if stats else None   # (B records of 16 bytes)
         self._check_or_free(self.lib.tts_watermark_embed(self.handle, p_wav, out.data_ptr(), B, n, _int32_ptr(ns), ctypes.addressof(p),
                                                          st.data_ptr() if stats else None), out if fresh else None, st)
-        if fresh and single:
-            out.shape = (n,)
-        if stats:
-            records = st.to_host().view(WATERMARK_EMBED_RECORD).reshape(B)
-            st.free()
-            return out, records
-        return out
+        return (out, _records(st, WATERMARK_EMBED_RECORD)) if stats else out
 
     def watermark_detect(self, wavs, watermark, offsets=64, n_samples=None, want_scores=False, want_sums=False):
         """tts_watermark_detect: the search for the carrier of ``watermark`` (its key and its shape; the payload and the strength are
@@ -2636,8 +2579,7 @@ class Engine(object):
         self._check_or_free(self.lib.tts_watermark_detect(self.handle, p_wav, B, n, _int32_ptr(ns), ctypes.addressof(p), int(D), rec.data_ptr(),
                                                           scores.data_ptr() if want_scores else None, sums.data_ptr() if want_sums else None),
                             rec, scores, sums)
-        answer = (rec.to_host().view(WATERMARK_DETECT_RECORD).reshape(B),)
-        rec.free()
+        answer = (_records(rec, WATERMARK_DETECT_RECORD),)
         for extra in (scores, sums):
             if extra is not None:
                 answer += (extra.to_host(),)
@@ -2659,23 +2601,13 @@ class Engine(object):
         d = dither_value('encode', dither)
         if isinstance(seed, (bool, np.bool_)) or int(seed) != seed or not 0 <= int(seed) < 2 ** 64:
             raise ValueError('encode: the seed must be an integer in 0 .. 2^64 - 1, got {!r}'.format(seed))
-        wav, single, B, n = _waveforms('encode', wav)
-        ns = None
-        if n_samples is not None:
-            ns = np.asarray(n_samples)
-            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
-                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-            for b, k in enumerate(ns.tolist()):
-                if not 0 <= k <= n:
-                    raise ValueError('n_samples[{}] = {} is not in 0 .. n = {}'.format(b, k, n))
-            ns = np.ascontiguousarray(ns, dtype=np.int32)
+        wav, single, B, n, ns = self._ragged_waveforms('encode', wav, n_samples, 0)
         on_device = _is_device(wav)
         p_wav, _k = self._in(wav, np.float32)
         out = self.empty((n,) if single else (B, n), FORMAT_DTYPES[f])
         st = self.empty((B, 4), np.int32)   # (B records of 16 bytes)
         self._check_or_free(self.lib.tts_encode(self.handle, p_wav, B, n, _int32_ptr(ns), f, d, int(seed), out.data_ptr(), st.data_ptr()), out, st)
-        stats = st.to_host().view(ENCODE_RECORD).reshape(B)
-        st.free()
+        stats = _records(st, ENCODE_RECORD)
         if not on_device:
             codes = out.to_host()
             out.free()
@@ -3036,12 +2968,7 @@ class Engine(object):
         N_out) resampled samples and zeros behind them; ``N_out`` None: ceil(longest * ratio), librosa's length."""
         r = resample_ratio_value(ratio)
         wavs, single, B, n = _waveforms('resample', wavs)
-        ns = None
-        if n_samples is not None:
-            ns = np.asarray(n_samples)
-            if ns.shape != (B,) or ns.dtype.kind not in 'iu':
-                raise ValueError('n_samples: {} integers are needed, got shape {} of {}'.format(B, ns.shape, ns.dtype))
-            ns = _checked_lengths(ns, n, 'n_samples', 'n')
+        ns = _sample_lengths(n_samples, B, n)
         if N_out is None:
             N_out = resampled_length(int(ns.max()) if ns is not None else n, r)
         N_out = int(N_out)
@@ -3169,13 +3096,13 @@ class Engine(object):
                    seed=0, peak_normalize=True, want_mel=False, want_alignments=False, want_linear=False, wav=None,
                    momentum=None, stop_at_silence=None, speaking_rate=None, pitch=None, phase_init=None, loudness=None,
                    alignment_stats=None, limiter=None, token_times=None, equalizer=None, compressor=None, watermark=None, **refused):
-        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The eight settings from ``momentum`` to
-        ``limiter`` hold for this call alone, as SETTINGS has them, ``token_times`` as MARK_SETTINGS has it, ``watermark`` as
-        WATERMARK_SETTINGS, ``compressor`` as DYNAMICS_SETTINGS and ``equalizer`` as TONE_SETTINGS have them.  ``output`` (HOST_SETTINGS) is ``synthesize_host``'s: this
-        call's rows stay on the device, where ``resample`` and ``encode`` take them."""
-        if 'output' in refused:
-            raise ValueError('synthesize: no output= here -- the waveforms stay on the device as float32; resample and encode them there '
-                             'with Engine.resample and Engine.encode, or call synthesize_host')
+        """tts_synthesize: ids -> waveforms in one call, everything on the device.  The settings from ``momentum`` to ``watermark``
+        hold for this call alone, as SETTINGS has them.  ``output`` is ``synthesize_host``'s: this call's rows stay on the device,
+        where ``resample`` and ``encode`` take them."""
+        for row in SETTINGS:
+            if row.host_only and row.keyword in refused:
+                raise ValueError('synthesize: no {}= here -- the waveforms stay on the device as float32; resample and encode them '
+                                 'there with Engine.resample and Engine.encode, or call synthesize_host'.format(row.keyword))
         if refused:
             raise TypeError('synthesize() got an unexpected keyword argument {!r}'.format(sorted(refused)[0]))
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
@@ -3236,11 +3163,10 @@ class Engine(object):
         """Asynchronous end-to-end call on HOST ids (int32 (B, T_sent)): returns a ticket at once; the upload, the
         network, Griffin-Lim and the download of the waveforms into pinned memory overlap with the neighbouring
         calls.  Keep at most three calls in flight: submit k + 2, then ``wait_host(ticket_k)``.
-        The nine settings from ``momentum`` on hold for this call alone, as SETTINGS and HOST_SETTINGS have them: they are read when the call is
+        The settings from ``momentum`` on hold for this call alone, as SETTINGS has them: they are read when the call is
         made, not when its work runs.  A call made with an ``output`` is fetched with ``wait_host_encoded``, not ``wait_host``.  A call that stops at silence returns once its post-net has run (the lengths:
         ``wait_host_frames``); the alignment records travel with the waveforms (``wait_host_alignment_stats``), and so do the
-        timing marks of a call made with ``token_times`` (MARK_SETTINGS; ``wait_host_token_times``).  ``equalizer`` (TONE_SETTINGS)
-        ``compressor`` (DYNAMICS_SETTINGS) and ``watermark`` (WATERMARK_SETTINGS) hold for this call alone too."""
+        timing marks of a call made with ``token_times`` (``wait_host_token_times``)."""
         call = self._settings(momentum=momentum, stop_at_silence=stop_at_silence, speaking_rate=speaking_rate, pitch=pitch,
                               phase_init=phase_init, loudness=loudness, alignment_stats=alignment_stats, limiter=limiter, output=output,
                               token_times=token_times, watermark=watermark, compressor=compressor, equalizer=equalizer)

@@ -251,9 +251,7 @@ int alignment_impl(tts_handle_t h, const float* alignments, int n_steps_max, int
         const int nb = std::min(ALIGN_UTTS, B - b0);
         AlignLens lens;
         fill_lengths(lens.n_sent, n_sent, b0, nb, Ts);
-        fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n_steps[b]);
+        const int longest = fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
         // (the caller's pos and peak are written to their end: -1 and 0 behind an utterance's steps)
         const int cover = (pos || peak) ? n_steps_max : longest;
         hipLaunchKernelGGL(align_rows_kernel, dim3(align_row_blocks(cover), nb), dim3(64 * ALIGN_ROWS), 0, h->stream, alignments, B, Ts, b0,
@@ -277,9 +275,7 @@ int alignment_positions_impl(tts_handle_t h, bool in_call, const float* alignmen
         const int nb = std::min(ALIGN_UTTS, B - b0);
         AlignLens lens;
         fill_lengths(lens.n_sent, n_sent, b0, nb, Ts);
-        fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n_steps[b]);
+        const int longest = fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
         hipLaunchKernelGGL(align_rows_kernel, dim3(align_row_blocks(longest), nb), dim3(64 * ALIGN_ROWS), 0, h->stream, alignments, B, Ts, b0,
                            lens, d_n_sent, longest, n_steps_max, s.pos, s.peak, s.off);
         HIPCHK(h, hipGetLastError());

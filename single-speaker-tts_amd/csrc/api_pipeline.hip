@@ -6,7 +6,6 @@
 
 namespace tts_api {
 
-
 // The launch index from which a pipelined call's Griffin-Lim launches are cut for ALL compute units (gl_run, wide_from), or -1.
 // Under the pipeline the next call's decoder starts with this call's first Griffin-Lim launch (its encoder ran in the gap
 // before it) on the `reserve_cus` units that Griffin-Lim leaves free, and with the weight-stationary kernel it is done long
@@ -67,6 +66,7 @@ struct SynthCall {
     int32_t* d_frames = nullptr;   // the lengths on the device (workspace "eos.frames")
     // what the speaking rate and the pitch make of the call's frames
     SynthShape shape;
+    int N = 0;                     // the samples of a row of `wav`, hop (Tw - 1): row_samples of that shape
     float* mags = nullptr;         // the time-stretch of `magi`, shape.Tg rows: what Griffin-Lim reconstructs from
     float* gl_wav = nullptr;       // a shifted call: Griffin-Lim's hop (Tg - 1) samples, which the resampler takes into `wav`
     // attention diagnostics: the sentence lengths are taken from the ids behind the encoder, the statistics from `align_out` --
@@ -87,6 +87,37 @@ struct StreamScope {
     void aim(hipStream_t s) { h->stream = s; }
     ~StreamScope() { h->stream = main_stream; }
 };
+
+static long long row_samples(const tts_synth_params_t* sp, const SynthShape& s) { return (long long)sp->hop_length * (s.Tw - 1); }
+
+// The finishing chain, in the order it runs: each stage takes the call's rows in place behind whatever made them (Griffin-Lim, the
+// pitch's resampler, the peak normalisation), every utterance over the samples its row holds -- `held`, hop (n[b] - 1) of the reported
+// lengths with end-of-speech stopping; null: all N.  Rows no stage can take are refused in the loudness target's name, else the first stage's.
+struct FinishStage {
+    const char* noun;   // "synthesize: NOUN needs rows of ..."
+    bool (*on)(const SynthSettings& set);
+    int (*reserve)(tts_handle_t h, int B, int N, const SynthSettings& set);   // (through the stage's own scratch function)
+    int (*run)(tts_handle_t h, float* wav, int B, int N, const int32_t* held, const SynthSettings& set);
+};
+static const FinishStage FINISH[] = {
+    {"the equaliser", [](auto& set) { return set.eq.enabled; },   // behind the peak normalisation, ahead of the loudness gain and the limiter
+     [](auto h, int B, int N, auto& set) { EqScratch s; return equalizer_scratch(h, B, N, set.eq.n_sections, &s); },
+     [](auto h, float* wav, int B, int N, auto held, auto& set) { return equalizer_impl(h, wav, wav, B, N, held, set.eq.sos, set.eq.n_sections); }},
+    {"the compressor", [](auto& set) { return set.cmp.enabled; },   // behind the equaliser, ahead of the loudness gain and the limiter
+     [](auto h, int B, int N, auto&) { CmpScratch s; return compressor_scratch(h, B, N, false, &s); },
+     [](auto h, float* wav, int B, int N, auto held, auto& set) { return compressor_impl(h, wav, wav, B, N, held, set.cmp.params, nullptr, nullptr); }},
+    {"the watermark", [](auto& set) { return set.wm.enabled; },   // behind the compressor, ahead of the loudness gain and the limiter: they scale it with the speech
+     [](auto h, int B, int N, auto&) { WmScratch s; return watermark_scratch(h, B, N, false, &s); },
+     [](auto h, float* wav, int B, int N, auto held, auto& set) { return watermark_impl(h, wav, wav, B, N, held, set.wm.params, nullptr); }},
+    {"a loudness target", [](auto& set) { return set.loud.enabled; },   // (with one, nothing ahead of the chain is peak-normalised)
+     [](auto h, int B, int N, auto& set) { LoudScratch s; return loudness_scratch(h, B, N, set.loud.sampling_rate, &s); },
+     [](auto h, float* wav, int B, int N, auto held, auto& set) {
+         return loudness_impl(h, wav, B, N, held, set.loud.sampling_rate, true, set.loud.target_lufs, set.loud.max_peak, nullptr, nullptr, nullptr); }},
+    {"the limiter", [](auto& set) { return set.lim.enabled; },   // last: behind the loudness gain, or behind the peak normalisation
+     [](auto h, int B, int N, auto&) { LimScratch s; return limiter_scratch(h, B, N, &s); },
+     [](auto h, float* wav, int B, int N, auto held, auto& set) { return limiter_impl(h, wav, B, N, held, set.lim.ceiling, set.lim.lookahead, set.lim.oversample, nullptr); }},
+};
+static const FinishStage* const FINISH_REFUSAL_ORDER[] = {&FINISH[3], &FINISH[0], &FINISH[1], &FINISH[2], &FINISH[4]};
 
 // Step 1: every workspace of the call, sized before anything of it is enqueued (a growing workspace synchronises every stream).
 // A stage's buffers come from the stage's own `*_scratch` function (api_internal.h), which the stage asks again for the same
@@ -152,17 +183,8 @@ static int synth_workspaces(tts_handle_t h, SynthCall& k) {
         WS(h, "gl.wav_pitch", float, (size_t)B * sp->hop_length * (size_t)(Tg - 1), glw);
         k.gl_wav = glw;
     }
-    // (the loudness measurement and the limiter take rows of hop (Tw - 1) samples)
-    LoudScratch loud;
-    LimScratch lim;
-    EqScratch eq;
-    if (k.set.eq.enabled && (rc = equalizer_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.eq.n_sections, &eq))) return rc;
-    CmpScratch cmp;
-    if (k.set.cmp.enabled && (rc = compressor_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), false, &cmp))) return rc;
-    WmScratch wm;
-    if (k.set.wm.enabled && (rc = watermark_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), false, &wm))) return rc;
-    if (k.set.loud.enabled && (rc = loudness_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), k.set.loud.sampling_rate, &loud))) return rc;
-    if (k.set.lim.enabled && (rc = limiter_scratch(h, B, sp->hop_length * (k.shape.Tw - 1), &lim))) return rc;
+    for (const FinishStage& st : FINISH)   // (the finishing chain takes rows of k.N samples)
+        if (st.on(k.set) && (rc = st.reserve(h, B, k.N, k.set))) return rc;
     if (k.set.ali.enabled || k.set.tt.enabled) {
         // One alignment buffer and one set of scratch: the statistics of a call run behind its decoder on the decoder's stream,
         // in front of whatever lets the next decoder start.  The sentence lengths are written behind the ENCODER, which may run a
@@ -492,28 +514,16 @@ static int synth_main(tts_handle_t h, SynthCall& k) {
     if (s.pitch && !rc) {
         // The pitch: the hop (Tg - 1) samples Griffin-Lim made, resampled by rho into the rows of the call without pitch.  With
         // end-of-speech stopping utterance b has hop (n'[b] - 1) samples, and its row ends where the un-shifted call's does.
-        const int n_gl = sp->hop_length * (Tg - 1), N_out = sp->hop_length * (s.Tw - 1);
-        rc = resample_impl(h, k.gl_wav, B, n_gl, detected ? L.n_samples.data() : nullptr, s.rho, N_out, detected ? L.keep.data() : nullptr, k.wav);
-        if (!rc && sp->peak_normalize && !k.set.loud.enabled) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, N_out));
+        const int n_gl = sp->hop_length * (Tg - 1);
+        rc = resample_impl(h, k.gl_wav, B, n_gl, detected ? L.n_samples.data() : nullptr, s.rho, k.N, detected ? L.keep.data() : nullptr, k.wav);
+        if (!rc && sp->peak_normalize && !k.set.loud.enabled) HIPCHK(h, launch_peak_normalize(h->stream, k.wav, B, k.N));
     }
-    // The loudness target and the limiter: every utterance is taken over the samples its row holds -- hop (n[b] - 1) of the reported
-    // lengths with end-of-speech stopping, all of the row otherwise -- in place, behind whatever made the row.
+    // The finishing chain (FINISH), in place, over the samples each row holds
     std::vector<int32_t> held;
-    if (detected && (k.set.loud.enabled || k.set.lim.enabled || k.set.eq.enabled || k.set.cmp.enabled || k.set.wm.enabled))
+    if (detected && std::any_of(std::begin(FINISH), std::end(FINISH), [&](const FinishStage& st) { return st.on(k.set); }))
         for (int b = 0; b < B; ++b) held.push_back(sp->hop_length * (L.reported[(size_t)b] - 1));
-    if (k.set.eq.enabled && !rc)   // (the equaliser: behind the peak normalisation, ahead of the loudness gain and the limiter)
-        rc = equalizer_impl(h, k.wav, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.eq.sos, k.set.eq.n_sections);
-    if (k.set.cmp.enabled && !rc)   // (the compressor: behind the equaliser, ahead of the loudness gain and the limiter)
-        rc = compressor_impl(h, k.wav, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.cmp.params, nullptr, nullptr);
-    if (k.set.wm.enabled && !rc)   // (the watermark: behind the compressor, ahead of the loudness gain and the limiter, which scale it with the speech)
-        rc = watermark_impl(h, k.wav, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.wm.params, nullptr);
-    if (k.set.loud.enabled && !rc) {
-        rc = loudness_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.loud.sampling_rate, true,
-                           k.set.loud.target_lufs, k.set.loud.max_peak, nullptr, nullptr, nullptr);
-    }
-    if (k.set.lim.enabled && !rc)   // (last: behind the loudness gain, or behind the peak normalisation)
-        rc = limiter_impl(h, k.wav, B, sp->hop_length * (s.Tw - 1), detected ? held.data() : nullptr, k.set.lim.ceiling, k.set.lim.lookahead,
-                          k.set.lim.oversample, nullptr);
+    for (const FinishStage& st : FINISH)
+        if (!rc && st.on(k.set)) rc = st.run(h, k.wav, B, k.N, detected ? held.data() : nullptr, k.set);
     if (pl.front && !rc) HIPCHK(h, pl.gl_done[parity].record(h->stream));
     return rc;
 }
@@ -540,21 +550,11 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
     if (!k.gl_streaming && (rc = gl_refuse(h, gl_refusal("synthesize: ", GL_RULE_WINDOW, c.n_fft, sp->win_length, sp->hop_length, 0)))) return rc;
     if (set.eos.enabled && speech_threshold(set.eos.threshold_db, sp->ref_db, sp->max_db, sp->power, TTS_SPEECH_MAGNITUDE_POWER, &k.eos_thr))
         return fail(h, TTS_ERR_INVALID, "synthesize: end-of-speech stopping needs power > 0");
-    if (set.loud.enabled &&
-        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
-        return fail(h, TTS_ERR_INVALID, "synthesize: a loudness target needs rows of 1 .. 2^31 - 1 samples");
-    if (set.eq.enabled &&
-        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
-        return fail(h, TTS_ERR_INVALID, "synthesize: the equaliser needs rows of 1 .. 2^31 - 1 samples");
-    if (set.cmp.enabled &&
-        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
-        return fail(h, TTS_ERR_INVALID, "synthesize: the compressor needs rows of 1 .. 2^31 - 1 samples");
-    if (set.wm.enabled &&
-        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
-        return fail(h, TTS_ERR_INVALID, "synthesize: the watermark needs rows of 1 .. 2^31 - 1 samples");
-    if (set.lim.enabled &&
-        (sp->hop_length < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) < 1 || (long long)sp->hop_length * (k.shape.Tw - 1) > INT32_MAX))
-        return fail(h, TTS_ERR_INVALID, "synthesize: the limiter needs rows of 1 .. 2^31 - 1 samples");
+    const long long n_rows = row_samples(sp, k.shape);
+    k.N = (int)n_rows;
+    for (const FinishStage* st : FINISH_REFUSAL_ORDER)
+        if (st->on(set) && (sp->hop_length < 1 || n_rows < 1 || n_rows > INT32_MAX))
+            return fail(h, TTS_ERR_INVALID, std::string("synthesize: ") + st->noun + " needs rows of 1 .. 2^31 - 1 samples");
     h->ali.last_dev = nullptr;   // (the records of a call before this one are no longer "the last call's")
     h->tt.last_start = nullptr;
     h->tt.last_stats = nullptr;
@@ -575,7 +575,6 @@ static int synthesize_impl(tts_handle_t h, const SynthSettings& set, const int32
 // ======================================================================================== C ABI
 extern "C" {
 
-
 int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_synth_params_t* sp,
                    const float* init_phase, float* wav, float* mel_out, float* align_out, float* linear_out) {
     DeviceScope dev_scope(h);
@@ -583,8 +582,6 @@ int tts_synthesize(tts_handle_t h, const int32_t* ids, int B, int Ts, const tts_
     if (rc) return rc;
     return synthesize_impl(h, h->settings, ids, B, Ts, sp, init_phase, wav, mel_out, align_out, linear_out, StageArgs());
 }
-
-
 
 // Host-memory form of tts_synthesize (see sstts_hip.h): uploads and downloads on copy streams, ordered by events, so that
 // consecutive calls overlap exactly like calls on device-resident buffers.
@@ -602,7 +599,8 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     SynthShape shape;
     synth_shape(T, h->cfg.n_fft, sp->hop_length, set.speaking_rate, set.pitch_octaves, set.eos.enabled != 0, &shape);
     const size_t ids_bytes = (size_t)B * Ts * sizeof(int32_t);
-    const size_t n_wav = (size_t)B * sp->hop_length * (size_t)(shape.Tw - 1);
+    const long long N_rows = row_samples(sp, shape);
+    const size_t n_wav = (size_t)B * (size_t)N_rows;
     const bool want_lin = (sp->host_outputs & TTS_HOST_LINEAR) != 0, want_ali = (sp->host_outputs & TTS_HOST_ALIGNMENTS) != 0;
     const size_t n_lin = want_lin ? (size_t)B * T * (size_t)(1 + h->cfg.n_fft / 2) : 0;
     const size_t n_ali = want_ali ? (size_t)sp->n_steps * B * Ts : 0;
@@ -613,7 +611,6 @@ int tts_synthesize_host(tts_handle_t h, const int32_t* ids_host, int B, int Ts, 
     // it holds -- into rows of N_enc samples, and the encoder's codes travel instead.  Everything that may allocate -- the staging
     // buffers, the ratio's table, the resampled rows, which are a workspace -- is made here, before anything is enqueued.
     const bool encoded = set.out.enabled, resampled = encoded && set.out.ratio != 1.0, coded = encoded && set.out.format != ENC_F32;
-    const long long N_rows = (long long)sp->hop_length * (shape.Tw - 1);
     long long N_enc = N_rows;
     if (encoded && (sp->hop_length < 1 || N_rows < 1 || N_rows > INT32_MAX))
         return fail(h, TTS_ERR_INVALID, "synthesize_host: a delivery format needs rows of 1 .. 2^31 - 1 samples");

@@ -191,9 +191,7 @@ int compressor_impl(tts_handle_t h, const float* wav, float* out, int B, int N, 
     for (int b0 = 0; b0 < B; b0 += CMP_UTTS) {
         const int nb = std::min(CMP_UTTS, B - b0);
         CmpLens lens;
-        fill_lengths(lens.n, n_samples, b0, nb, N);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         const float* w = wav + (size_t)b0 * N;
         float* o = out + (size_t)b0 * N;
         double* st = s.state + (size_t)b0 * state_row;

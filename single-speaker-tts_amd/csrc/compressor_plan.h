@@ -179,11 +179,9 @@ inline std::string compressor_check(uintptr_t wav, uintptr_t out, int B, int N, 
     std::string bad = lengths_refusal("n_samples", n_samples, B, "N", N);
     if (bad.empty()) bad = cmp_params_check(*p);
     if (!bad.empty()) return bad;
-    if ((wav | out) & 3) return "wav and out must be 4-byte aligned";
-    if (envelope & 7) return "envelope must be 8-byte aligned";
-    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)N * sizeof(float);
-    if (out != wav && out < wav + bytes && wav < out + bytes) return "out overlaps wav without being equal to it";
-    return std::string();
+    // (the envelope's alignment stands between the pair's alignment and its overlap)
+    if (!((wav | out) & 3) && (envelope & 7)) return "envelope must be 8-byte aligned";
+    return in_out_refusal(wav, out, B, N);
 }
 
 }  // namespace tts

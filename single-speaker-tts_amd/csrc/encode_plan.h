@@ -136,10 +136,7 @@ inline std::string encode_check(bool have_ptrs, int B, int N, const int32_t* n_s
     if (!enc_format_known(format)) return "the format " + std::to_string(format) + " is not one of TTS_FMT_*";
     if (format == ENC_F32) return "TTS_FMT_F32 is no encoding: the rows are float32 already";
     if (dither != ENC_DITHER_NONE && dither != ENC_DITHER_TPDF) return "the dither " + std::to_string(dither) + " is not one of TTS_DITHER_*";
-    for (int b = 0; n_samples && b < B; ++b)
-        if (n_samples[b] < 0 || n_samples[b] > N)
-            return "n_samples[" + std::to_string(b) + "] = " + std::to_string(n_samples[b]) + " is not in 0 .. N = " + std::to_string(N);
-    return std::string();
+    return lengths_refusal("n_samples", n_samples, B, "N", N, 0);
 }
 
 // The checks of tts_set_output; an empty string: legal.  *on: whether the setting changes anything of a call -- an encoding, or two

@@ -193,9 +193,7 @@ int equalizer_impl(tts_handle_t h, const float* wav, float* out, int B, int N, c
     for (int b0 = 0; b0 < B; b0 += EQ_UTTS) {
         const int nb = std::min(EQ_UTTS, B - b0);
         EqLens lens;
-        fill_lengths(lens.n, n_samples, b0, nb, N);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         hipError_t e = hipSuccess;
 #define EQ_CHUNK(S) \
     e = eq_launch_chunk<S>(h->stream, wav + (size_t)b0 * N, out + (size_t)b0 * N, (size_t)N, lens, nb, longest, coef, s.M, s.state + (size_t)b0 * state_row, state_row, segs)

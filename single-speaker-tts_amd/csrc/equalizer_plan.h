@@ -235,10 +235,7 @@ inline std::string equalizer_check(uintptr_t wav, uintptr_t out, int B, int N, c
     std::string bad = lengths_refusal("n_samples", n_samples, B, "N", N);
     if (bad.empty()) bad = eq_sections_check(sos, n_sections);
     if (!bad.empty()) return bad;
-    if ((wav | out) & 3) return "wav and out must be 4-byte aligned";
-    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)N * sizeof(float);
-    if (out != wav && out < wav + bytes && wav < out + bytes) return "out overlaps wav without being equal to it";
-    return std::string();
+    return in_out_refusal(wav, out, B, N);
 }
 
 }  // namespace tts

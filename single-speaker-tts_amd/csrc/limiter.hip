@@ -269,9 +269,7 @@ int limiter_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_samp
     for (int b0 = 0; b0 < B; b0 += LIM_UTTS) {
         const int nb = std::min(LIM_UTTS, B - b0);
         LimLens lens;
-        fill_lengths(lens.n, n_samples, b0, nb, N);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         const dim3 grid((unsigned)lim_tiles(longest), nb);
         float* pw = wav + (size_t)b0 * N;
         float* po = s.out + (size_t)b0 * N;
@@ -293,9 +291,7 @@ static int true_peak_impl(tts_handle_t h, const float* wav, int B, int N, const 
     for (int b0 = 0; b0 < B; b0 += LIM_UTTS) {
         const int nb = std::min(LIM_UTTS, B - b0);
         LimLens lens;
-        fill_lengths(lens.n, n_samples, b0, nb, N);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         hipLaunchKernelGGL(lim_peak_kernel, dim3((unsigned)lim_tiles(longest), nb), dim3(LIM_LANES), 0, h->stream, wav + (size_t)b0 * N, (size_t)N, lens,
                            coef, reinterpret_cast<unsigned long long*>(true_peak) + b0,
                            sample_peak ? reinterpret_cast<unsigned long long*>(sample_peak) + b0 : nullptr);

@@ -302,9 +302,7 @@ int loudness_impl(tts_handle_t h, float* wav, int B, int N, const int32_t* n_sam
     for (int b0 = 0; b0 < B; b0 += LOUD_UTTS) {
         const int nb = std::min(LOUD_UTTS, B - b0);
         LoudLens lens;
-        fill_lengths(lens.n, n_samples, b0, nb, N);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         float* pw = wav + (size_t)b0 * N;
         double* pws = s.ws + (size_t)b0 * ws_row;
         double* pz = mean_square && !normalize ? mean_square + b0 : s.z + b0;

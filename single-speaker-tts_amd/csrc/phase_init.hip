@@ -321,8 +321,7 @@ int phase_estimate_impl(tts_handle_t h, const float* mag, int B, int T, int row_
     for (int b0 = 0; b0 < B; b0 += PE_UTTS) {
         const int nb = std::min(PE_UTTS, B - b0);
         PeLens lens;
-        fill_lengths(lens.n, n_frames, b0, nb, T);
-        const int longest = *std::max_element(lens.n, lens.n + nb);
+        const int longest = fill_lengths(lens.n, n_frames, b0, nb, T);
         const float* rows = mag + (size_t)b0 * T * row_stride;
         int stride = row_stride;
         if (!time_major) {

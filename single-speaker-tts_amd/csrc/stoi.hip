@@ -355,9 +355,7 @@ static int stoi_impl(tts_handle_t h, const float* ref, const float* deg, int B, 
     for (int b0 = 0; b0 < B; b0 += STOI_UTTS) {
         const int nb = std::min(STOI_UTTS, B - b0);
         StoiLens lens;
-        fill_lengths(lens.n, n_samples, b0, nb, N);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n[b]);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         const int frames = stoi_frames(longest);   // the upper bound of every row's kept frames
         const float* pr = ref + (size_t)b0 * N;
         const float* pd = deg + (size_t)b0 * N;

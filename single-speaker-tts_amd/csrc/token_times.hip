@@ -233,9 +233,7 @@ int token_times_impl(tts_handle_t h, const float* alignments, int n_steps_max, i
         const int nb = std::min(TT_UTTS, B - b0);
         TtLens lens;
         fill_lengths(lens.n_sent, n_sent, b0, nb, Ts);
-        fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
-        int longest = 0;
-        for (int b = 0; b < nb; ++b) longest = std::max(longest, lens.n_steps[b]);
+        const int longest = fill_lengths(lens.n_steps, n_steps, b0, nb, n_steps_max);
         const size_t lds = tt_lds_bytes(longest, Ts);
         if (tt_dir_in_lds(longest, Ts))
             hipLaunchKernelGGL(token_times_kernel<true>, dim3(nb), dim3(TT_THREADS), lds, h->stream, alignments, B, Ts, b0, lens, d_n_sent,

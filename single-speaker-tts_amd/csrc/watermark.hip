@@ -321,12 +321,6 @@ int watermark_scratch(tts_handle_t h, int B, int N, bool records, WmScratch* s) 
     return TTS_OK;
 }
 
-static void wm_lengths(WmLens& lens, const int32_t* n_samples, int b0, int nb, int N, int* longest) {
-    fill_lengths(lens.n, n_samples, b0, nb, N);
-    *longest = 0;
-    for (int b = 0; b < nb; ++b) *longest = std::max(*longest, lens.n[b]);
-}
-
 // On h->stream; everything has been checked (wm_embed_check).
 int watermark_impl(tts_handle_t h, const float* wav, float* out, int B, int N, const int32_t* n_samples, const tts_watermark_t& params,
                    tts_watermark_embed_stats_t* stats) {
@@ -340,8 +334,7 @@ int watermark_impl(tts_handle_t h, const float* wav, float* out, int B, int N, c
     for (int b0 = 0; b0 < B; b0 += WM_UTTS) {
         const int nb = std::min(WM_UTTS, B - b0);
         WmLens lens;
-        int longest;
-        wm_lengths(lens, n_samples, b0, nb, N, &longest);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         const float* x = wav + (size_t)b0 * N;
         float* y = out + (size_t)b0 * N;
         float* E = s.E + (size_t)b0 * e_row;
@@ -383,8 +376,7 @@ static int watermark_detect_impl(tts_handle_t h, const float* wav, int B, int N,
     for (int b0 = 0; b0 < B; b0 += WM_UTTS) {
         const int nb = std::min(WM_UTTS, B - b0);
         WmLens lens;
-        int longest;
-        wm_lengths(lens, n_samples, b0, nb, N, &longest);
+        const int longest = fill_lengths(lens.n, n_samples, b0, nb, N);
         const float* x = wav + (size_t)b0 * N;
         float* Eb = E + (size_t)b0 * e_row;
         int8_t* vb = v + (size_t)b0 * N;

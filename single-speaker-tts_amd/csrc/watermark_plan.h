@@ -168,30 +168,21 @@ inline std::string wm_params_check(const WmParams& w) {
     if (bad.empty() && !(w.strength >= 0.0 && w.strength <= WM_STRENGTH_MAX)) bad = "strength is not in 0 .. 0.25";
     return bad;
 }
-inline std::string wm_lengths_refusal(const int32_t* n_samples, int B, int N) {
-    for (int b = 0; n_samples && b < B; ++b)
-        if (n_samples[b] < 0 || n_samples[b] > N)
-            return "n_samples[" + std::to_string(b) + "] = " + std::to_string(n_samples[b]) + " is not in 0 .. N = " + std::to_string(N);
-    return std::string();
-}
 // The checks of tts_watermark_embed in the order the header lists them; wav, out: the addresses.  Empty: the call is legal.
 inline std::string wm_embed_check(uintptr_t wav, uintptr_t out, int B, int N, const int32_t* n_samples, const WmParams* w) {
     if (!wav || !out || !w) return "a NULL pointer (wav, out and params are required)";
     if (B < 1 || N < 1) return "need B, N >= 1";
-    std::string bad = wm_lengths_refusal(n_samples, B, N);
+    std::string bad = lengths_refusal("n_samples", n_samples, B, "N", N, 0);
     if (bad.empty()) bad = wm_params_check(*w);
     if (!bad.empty()) return bad;
-    if ((wav | out) & 3) return "wav and out must be 4-byte aligned";
-    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)N * sizeof(float);
-    if (out != wav && out < wav + bytes && wav < out + bytes) return "out overlaps wav without being equal to it";
-    return std::string();
+    return in_out_refusal(wav, out, B, N);
 }
 // ... and of tts_watermark_detect
 inline std::string wm_detect_check(uintptr_t wav, uintptr_t records, int B, int N, const int32_t* n_samples, const WmParams* w, int D,
                                    uintptr_t scores, uintptr_t sums) {
     if (!wav || !records || !w) return "a NULL pointer (wav, records and params are required)";
     if (B < 1 || N < 1) return "need B, N >= 1";
-    std::string bad = wm_lengths_refusal(n_samples, B, N);
+    std::string bad = lengths_refusal("n_samples", n_samples, B, "N", N, 0);
     if (bad.empty()) bad = wm_params_check(*w);
     if (bad.empty()) bad = wm_range("D =", D, 1, WM_MAX_OFFSETS);
     if (!bad.empty()) return bad;

@@ -216,26 +216,25 @@ class SynthSettings(object):
     (``Engine.token_times``, at most ``marks_max_jump`` tokens a decoder step; 4, untuned) and the helper answers with timing
     marks as its last element (``tacotron.marks``): when every word -- and with 'char' every character -- is spoken, in
     milliseconds and in samples of what is delivered.
-    ``equalizer`` (taken by ``SynthSettings.of``, behind the constructor's keywords): None (the engine's setting), a profile name -- 'telephony', 'small-speaker', 'rumble', 'bright', 'warm'; every
+    ``watermark``: None (the engine's setting), a key, ``(key, payload)`` or ``(key, payload, payload_bits, chip, chips_per_symbol,
+    strength)``: a keyed spread-spectrum carrier (``Engine.watermark_embed``) is added under the local envelope of every utterance;
+    ``audio.metrics.detect_watermark`` finds it.  The defaults (16 bits, 8 samples a chip, 64 chips a symbol, 0.02 of the envelope)
+    are UNTUNED: nobody has listened.
+    ``compressor``: None (the engine's setting), a profile name -- 'speech', 'telephony', 'small-speaker'; every preset is untuned
+    -- or ``(threshold_db, ratio[, knee_db[, attack_ms[, release_ms[, makeup_db]]]])``: a feed-forward peak compressor
+    (``Engine.compress``) lowers the crest factor of every utterance.
+    ``equalizer``: None (the engine's setting), a profile name -- 'telephony', 'small-speaker', 'rumble', 'bright', 'warm'; every
     preset is untuned -- a list of ``(kind, f0_hz[, q[, gain_db]])`` sections (kinds 'lowpass', 'highpass', 'peak', 'lowshelf',
     'highshelf') or an (S, 5) array of second-order sections: a cascade of up to 8 biquads (``Engine.equalize``) shapes the
-    spectrum of every utterance on the device, behind Griffin-Lim, the pitch and the peak normalisation and ahead of the loudness
-    gain and the limiter.  Lengths and timing marks do not change (the group delay of a few samples is ignored).  A boost behind
-    the peak normalisation can pass 1.0: give it a limiter or a loudness target.
-    ``compressor`` (taken by ``SynthSettings.of`` too): None (the engine's setting), a profile name -- 'speech', 'telephony',
-    'small-speaker'; every preset is untuned -- or ``(threshold_db, ratio[, knee_db[, attack_ms[, release_ms[, makeup_db]]]])``: a
-    feed-forward peak compressor (``Engine.compress``) lowers the crest factor of every utterance on the device, behind the
-    equaliser and ahead of the loudness gain and the limiter.  Lengths and timing marks do not change.  A make-up gain behind the
-    peak normalisation can pass 1.0: give it a limiter or a loudness target.
-    ``watermark`` (taken by ``SynthSettings.of`` too): None (the engine's setting), a key, ``(key, payload)`` or ``(key, payload,
-    payload_bits, chip, chips_per_symbol, strength)``: a keyed spread-spectrum carrier (``Engine.watermark_embed``) is added under
-    the local envelope of every utterance on the device, behind the compressor and ahead of the loudness gain and the limiter;
-    ``audio.metrics.detect_watermark`` finds it.  Lengths and timing marks do not change.  The defaults (16 bits, 8 samples a chip,
-    64 chips a symbol, 0.02 of the envelope) are UNTUNED: nobody has listened."""
+    spectrum of every utterance; refused where a corner does not fit the model's sampling rate.
+    The last three run on the device behind Griffin-Lim, the pitch and the peak normalisation -- the equaliser, then the compressor,
+    then the watermark -- and ahead of the loudness gain and the limiter.  Lengths and timing marks do not change (the equaliser's
+    group delay of a few samples is ignored).  A boost or a make-up gain behind the peak normalisation can pass 1.0: give it a
+    limiter or a loudness target."""
 
     def __init__(self, hp, momentum=0.0, stop_at_silence_db=None, silence_keep_ms=SILENCE_KEEP_MS, speaking_rate=1.0, pitch=0.0,
                  phase_init='random', loudness=None, check_alignment=False, pitch_semitones=None, limiter=None, output=None,
-                 marks=None, marks_max_jump=4):
+                 marks=None, marks_max_jump=4, watermark=None, compressor=None, equalizer=None):
         momentum_thousandths(momentum)
         self.momentum = momentum
         self.stop = stop_setting(hp, stop_at_silence_db, silence_keep_ms)
@@ -250,28 +249,14 @@ class SynthSettings(object):
         self.output = output_of(hp, output)
         self.marks = marks_.marks_kind(marks)
         self.marks_max_jump = token_times_jump(marks_max_jump, 'marks_max_jump')
-        self.equalizer = None
-        self.compressor = None
-        self.watermark = None
-
-    @classmethod
-    def of(cls, hp, equalizer=None, **settings):
-        """The record of a helper's ``**settings``: the constructor's keywords and, checked behind them, the dynamics keywords
-        (WATERMARK_KEYWORDS and DYNAMICS_KEYWORDS: ``watermark`` and ``compressor``, read out of ``settings``) and then the tone keywords (TONE_KEYWORDS;
-        ``_hip.DYNAMICS_SETTINGS`` and ``_hip.TONE_SETTINGS`` are likewise tables behind the others) -- ``equalizer``, refused
-        here too where a corner does not fit the model's sampling rate."""
-        watermark = settings.pop('watermark', None)
-        compressor = settings.pop('compressor', None)
-        s = cls(hp, **settings)
-        s.watermark = watermark_setting(watermark)
-        s.compressor = compressor_setting(compressor)
-        s.equalizer = equalizer_setting(equalizer)
-        rate = getattr(getattr(hp, 'hparams', hp), 'sampling_rate', None)
-        if s.compressor is not None and rate:
-            compressor_params(s.compressor, int(rate))
-        if s.equalizer is not None and rate:
-            equalizer_sections(s.equalizer, int(rate))
-        return s
+        self.watermark = watermark_setting(watermark)
+        self.compressor = compressor_setting(compressor)
+        self.equalizer = equalizer_setting(equalizer)
+        rate = getattr(getattr(hp, 'hparams', hp), 'sampling_rate', None)   # (the coefficients, where the model's rate is known)
+        if self.compressor is not None and rate:
+            compressor_params(self.compressor, int(rate))
+        if self.equalizer is not None and rate:
+            equalizer_sections(self.equalizer, int(rate))
 
     def engine_keywords(self):
         """the settings as ``Engine.synthesize`` / ``Engine.synthesize_host`` take them"""
@@ -298,10 +283,7 @@ class SynthSettings(object):
         return norm and self.output is not None, norm and self.output is None
 
 
-TONE_KEYWORDS = tuple(inspect.signature(SynthSettings.of).parameters)[1:-1]      # ('equalizer',)
-DYNAMICS_KEYWORDS = ('compressor',)                                              # ahead of the tone, as _hip.DYNAMICS_SETTINGS is
-WATERMARK_KEYWORDS = ('watermark',)                                              # ahead of the dynamics, as _hip.WATERMARK_SETTINGS is
-SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:] + WATERMARK_KEYWORDS + DYNAMICS_KEYWORDS + TONE_KEYWORDS
+SETTING_KEYWORDS = tuple(inspect.signature(SynthSettings.__init__).parameters)[2:]
 
 
 def takes_settings(*refuses, only=None):
@@ -333,8 +315,7 @@ def takes_settings(*refuses, only=None):
                 return answer(parts(*args, **taken(keywords)))
         functools.update_wrapper(helper, parts)
         own = [p for p in inspect.signature(parts).parameters.values() if p.kind is not p.VAR_KEYWORD]
-        record = dict(inspect.signature(SynthSettings.__init__).parameters, **{k: inspect.signature(SynthSettings.of).parameters[k] for k in TONE_KEYWORDS})
-        record.update({k: inspect.Parameter(k, inspect.Parameter.KEYWORD_ONLY, default=None) for k in WATERMARK_KEYWORDS + DYNAMICS_KEYWORDS})
+        record = inspect.signature(SynthSettings.__init__).parameters
         helper.__signature__ = inspect.Signature(own + [record[k].replace(kind=inspect.Parameter.KEYWORD_ONLY)
                                                         for k in SETTING_KEYWORDS if k not in refuses])
         helper.parts = parts
@@ -425,7 +406,7 @@ def synthesize_batch(model, sentences, n_steps=None, n_iter=None, init_phase=Non
     ``(waveforms, records, verdicts)``.  With an ``output`` the waveforms are that format's codes at its rate, made of the call's
     device rows (``deliver_rows``; the dither's seed is ``seed``).  With ``marks`` the result gains, as its last element, a list of
     timing marks per row -- of the processed characters of the ids, with offsets into that string (``mark_texts``: of raw texts)."""
-    s = SynthSettings.of(model, **settings)
+    s = SynthSettings(model, **settings)
     c = call_constants(model, n_steps, n_iter)
     eng, B = model.engine, len(sentences)
     out = eng.synthesize(np.ascontiguousarray(sentences, dtype=np.int32), *c.synth, init_phase=init_phase, seed=seed,
@@ -468,7 +449,7 @@ def synthesize_stream(model, batches, n_steps=None, n_iter=None, seed=0, peak_no
     characters of the ids -- or, with ``mark_texts``, an iterator that gives per batch what ``synthesize_batch`` takes by that name,
     of raw texts); the 4 T_sent + 36 bytes per utterance come down with the waveforms."""
     # (a generator: a bad setting is refused at its first item, before the engine is touched)
-    s = SynthSettings.of(model, **settings)
+    s = SynthSettings(model, **settings)
     c = call_constants(model, n_steps, n_iter)
     eng = model.engine
     served = [0]   # utterances answered so far: what a clipped row is logged by
@@ -594,7 +575,7 @@ def synthesize_sentences(raw_sentences, weights, dataset=None, out_dir=None, dev
     gains, as its last element, the timing marks of every sentence with offsets into the RAW sentence, also written as
     ``{i+1}.marks.jsonl`` beside every wav (``marks.write_marks``); a sentence the front end cannot be mapped back to raises
     ValueError (``marks.token_spans``)."""
-    s = SynthSettings.of(model_params, **settings)   # (ValueError before anything is loaded)
+    s = SynthSettings(model_params, **settings)   # (ValueError before anything is loaded)
     out_dir, dataset, model = open_files(weights, dataset, out_dir, device_id)
     mark_texts = [(raw,) + marks_.token_spans(dataset, raw) for raw in raw_sentences] if s.marks else None
     id_sequences, sequence_lengths = dataset.process_sentences(raw_sentences)
@@ -627,7 +608,7 @@ def envelope_mode(markup_pitch, pitch_mode, timbre):
 def marked_settings(hp, settings, envelope=False):
     """the record of ``synthesize_marked``, for itself and for its file form: no pitch, unless the pitch is made on the envelope's
     side (``envelope``), where a global pitch adds to every token's"""
-    s = SynthSettings.of(hp, **settings)
+    s = SynthSettings(hp, **settings)
     if s.octaves != 0.0 and not envelope:
         raise ValueError('synthesize_marked: a pitch other than 0 is not supported with markup (the resampler is global), got {!r}'.format(
             settings.get('pitch') if settings.get('pitch_semitones') is None else settings['pitch_semitones']))
@@ -905,7 +886,7 @@ def join_list_of_call(piece_text, piece_break, n_frames, first_active, hop, paus
 def text_plan(caller, hp, pauses_ms, fade_ms, settings):
     """What ``synthesize_text`` checks ahead of everything else, for itself and for its file form: ``(record, pauses, fade)`` --
     the ``settings`` with ``stop_at_silence_db`` at -40 dB unless given, which cannot be None; ``pause_samples``; ``fade_samples``."""
-    s = SynthSettings.of(hp, **dict({'stop_at_silence_db': STOP_AT_SILENCE_DB}, **settings))
+    s = SynthSettings(hp, **dict({'stop_at_silence_db': STOP_AT_SILENCE_DB}, **settings))
     if s.stop is None:
         raise ValueError('{}: stop_at_silence_db cannot be None (pieces of max_iterations frames cannot be joined)'.format(caller))
     rate = getattr(hp, 'hparams', hp).sampling_rate
@@ -1136,7 +1117,7 @@ def main(argv=None):
     word, and ``--timbre ST`` moves the formants of every frame by ST semitones.  The default, ``resample``, is the above."""
     args = parse_args(argv)
     settings = settings_option(args)
-    SynthSettings.of(model_params, **settings)
+    SynthSettings(model_params, **settings)
     # Before we start doing anything we check if the required target folder actually exists (:131-133)
     out_dir = target_dir(args.synthesis_dir)
     path = args.synthesis_file or inference_params.synthesis_file

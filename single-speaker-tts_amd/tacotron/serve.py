@@ -36,7 +36,7 @@ def post_process_spectrograms(_spectrograms, engine, init_phase=None, seed=0, **
     with a ``watermark`` ``Engine.watermark_embed`` behind those;
     with a ``loudness`` ``Engine.loudness_normalize``, every waveform measured over its own samples; with a ``limiter`` ``Engine.limit``
     last, over the same samples."""
-    s = SynthSettings.of(model_params, **settings)
+    s = SynthSettings(model_params, **settings)
     stop, rate, octaves = s.stop, s.rate, s.octaves
     finish = finishing_tail('post_process_spectrograms', s, model_params.sampling_rate)
     rho = float(np.exp2(-np.float64(octaves)))
@@ -96,7 +96,7 @@ def serve(sentence_generator, weights, dataset=None, device_id=0, pipelined=Fals
     every answer gains, as its last element, the timing marks of every sentence (``tacotron.marks``; offsets into the raw
     sentence, samples of what is delivered): subtitles and barge-in positions in the same round trip as the waveforms."""
     # (a generator: a bad setting is refused at its first item, before a model is made)
-    s = SynthSettings.of(model_params, **settings)
+    s = SynthSettings(model_params, **settings)
     dataset, model = open_model(weights, dataset, device_id)
     if not pipelined:   # the reference's loop as it stands: one batch at a time, spectrograms through host memory
         for k, sentences in enumerate(sentence_generator):

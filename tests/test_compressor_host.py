@@ -210,19 +210,17 @@ def test_the_engine_refuses_before_the_library_is_touched():
 
 
 # ---------------------------------------------------------------------------------------------- the settings machinery
-def test_the_five_tables():
+def test_the_compressor_row_of_the_settings_table():
     H = pkg('_hip')
-    assert [r.keyword for r in H.SETTINGS] == ['momentum', 'stop_at_silence', 'speaking_rate', 'pitch', 'phase_init', 'loudness', 'alignment_stats',
-                                               'limiter']
-    assert [r.keyword for r in H.HOST_SETTINGS] == ['output'] and [r.keyword for r in H.MARK_SETTINGS] == ['token_times']
-    assert [r.keyword for r in H.TONE_SETTINGS] == ['equalizer'] and len(H.DYNAMICS_SETTINGS) == 1
-    row = H.DYNAMICS_SETTINGS[0]
-    assert (row.keyword, row.mirror, row.initial) == ('compressor', '_compressor', None) and row.check is H.compressor_setting
+    keys = [r.keyword for r in H.SETTINGS]
+    row = H.SETTINGS[keys.index('compressor')]
+    assert (row.mirror, row.initial, row.host_only) == ('_compressor', None, False) and row.check is H.compressor_setting
+    assert keys[keys.index('compressor') - 1:] == ['watermark', 'compressor', 'equalizer']
     assert no_device_engine()._compressor is None
 
 
 def test_the_keyword_is_set_ahead_of_the_equaliser_and_put_back_behind_it():
-    """the row of DYNAMICS_SETTINGS around a call, on a library that records its calls (tests/test_settings_host.py): behind the
+    """the ``compressor`` row of SETTINGS around a call, on a library that records its calls (tests/test_settings_host.py): behind the
     timing marks, ahead of the equaliser, which stays the last one set and the first one put back"""
     import test_settings_host as S
     H = pkg('_hip')
@@ -272,16 +270,16 @@ def test_the_keyword_is_threaded_through_the_helpers_and_the_command_line():
     for fn in (H.Engine.synthesize, H.Engine.synthesize_host, inf.synthesize_batch, inf.synthesize_stream, inf.synthesize_sentences, inf.synthesize_text,
                inf.synthesize_texts, inf.synthesize_marked, inf.synthesize_marked_sentences, serve.serve, serve.post_process_spectrograms):
         assert inspect.signature(fn).parameters['compressor'].default is None, fn
-    assert inf.DYNAMICS_KEYWORDS == ('compressor',) and inf.SETTING_KEYWORDS[-2:] == ('compressor', 'equalizer')
+    assert inf.SETTING_KEYWORDS[-2:] == ('compressor', 'equalizer')
     hp = pkg('tacotron.params').model_params
-    s = inf.SynthSettings.of(hp, compressor='speech', limiter=0.5)
+    s = inf.SynthSettings(hp, compressor='speech', limiter=0.5)
     assert s.compressor == ('profile', 'speech')
     assert s.engine_keywords()['compressor'] == s.keywords()['compressor'] == s.host_keywords()['compressor'] == s.compressor
-    assert inf.SynthSettings.of(hp).compressor is None and inf.SynthSettings(hp).compressor is None
-    assert inf.SynthSettings.of(hp).engine_keywords()['compressor'] is None
+    assert inf.SynthSettings(hp).compressor is None and inf.SynthSettings(hp).compressor is None
+    assert inf.SynthSettings(hp).engine_keywords()['compressor'] is None
     for bad in ('loud', (-20.0, 0.5), np.zeros((2, 4))):          # refused before a model is made
         with pytest.raises(ValueError):
-            inf.SynthSettings.of(hp, compressor=bad)
+            inf.SynthSettings(hp, compressor=bad)
         with pytest.raises(ValueError):
             inf.synthesize_sentences(['x'], '/nonexistent/weights', out_dir='/nonexistent', compressor=bad)
         with pytest.raises(ValueError):
@@ -325,7 +323,7 @@ def test_the_finishing_tail_runs_the_compressor_behind_the_equaliser_and_never_t
                                   ['equalize', 'compress', 'loudness_normalize', 'limit']),
                                  (dict(equalizer='warm', loudness=-20.0), True, ['equalize', 'loudness_normalize'])):
         eng = Eng()
-        inf.finishing_tail('test', inf.SynthSettings.of(hp, **settings), T.SR)(eng, rows, held, peak_normalize=peak)
+        inf.finishing_tail('test', inf.SynthSettings(hp, **settings), T.SR)(eng, rows, held, peak_normalize=peak)
         names = [name for name, _n in eng.calls if name in stages]
         assert names == want, (settings, names)
         if 'compress' in want:
@@ -334,6 +332,6 @@ def test_the_finishing_tail_runs_the_compressor_behind_the_equaliser_and_never_t
             assert how == 'params' and values == pkg('_hip').compressor_params(pkg('_hip').compressor_setting(settings['compressor']), T.SR)
     # with the setting off the tail runs on engines that have no such method
     for eng, settings in ((T.TailEngine(), dict(loudness=-20.0, limiter=0.5)), (Eq(), dict(equalizer='warm'))):
-        inf.finishing_tail('test', inf.SynthSettings.of(hp, **settings), T.SR)(eng, rows, held, peak_normalize=True)
+        inf.finishing_tail('test', inf.SynthSettings(hp, **settings), T.SR)(eng, rows, held, peak_normalize=True)
     with pytest.raises(ValueError):
-        inf.finishing_tail('test', inf.SynthSettings.of(None, compressor='speech'), 7000)
+        inf.finishing_tail('test', inf.SynthSettings(None, compressor='speech'), 7000)

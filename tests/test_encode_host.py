@@ -162,7 +162,11 @@ def test_the_output_setting_is_checked_before_a_handle_is_touched():
                 ('pcm16', None, 22050.0, 8000), ('pcm16', None, 22050, 5000), ('pcm16', None, 8000, 32001), ('wav', None, 8000, 8000)):
         with pytest.raises(ValueError):
             S(bad)
-    assert [row.keyword for row in H.HOST_SETTINGS] == ['output'] and 'output' not in [row.keyword for row in H.SETTINGS]
+    keys = [r.keyword for r in H.SETTINGS]
+    row = H.SETTINGS[keys.index('output')]
+    assert (row.mirror, row.initial, row.host_only) == ('_output', H.OUTPUT_OFF, True) and row.check is H.output_setting
+    assert keys[keys.index('output') - 1:keys.index('output') + 2] == ['limiter', 'output', 'token_times']
+    assert [r.keyword for r in H.SETTINGS if r.host_only] == ['output']
     assert [H.FORMATS[k] for k in ('float32', 'pcm16', 'pcm8', 'mulaw', 'alaw')] == [O.F32, O.S16, O.U8, O.MULAW, O.ALAW]
     assert H.ENCODE_RECORD == O.RECORD
 

@@ -1,7 +1,7 @@
 """CPU: the equaliser without a device.  (a) the segmented arithmetic of tests/equalizer_oracle.py (csrc/equalizer_plan.h restated)
 against scipy's ``sosfilt`` over the whole signal, (b) the designs against ``scipy.signal.butter`` and against the same formulas in
 ``mpmath``, and their responses by properties, through Python and through the library, (c) what the 'telephony' profile is for, on
-tones, and (d) the Python surface: ``equalizer_setting``, the TONE_SETTINGS row around a call on a library that records its calls,
+tones, and (d) the Python surface: ``equalizer_setting``, the SETTINGS row around a call on a library that records its calls,
 the three older tables as they were, the helpers and the command line."""
 import ctypes
 import inspect
@@ -301,19 +301,17 @@ def test_equalizer_setting_accepts_and_refuses_as_documented():
             eng.synthesize_host(ids, 2, 6.0, 100.0, 1.3, 3, 1102, 275, equalizer=bad)
 
 
-def test_the_older_tables_are_what_they_were_and_the_tone_has_its_own():
+def test_the_equalizer_row_is_the_last_of_the_settings_table():
     H = pkg('_hip')
-    assert [r.keyword for r in H.SETTINGS] == ['momentum', 'stop_at_silence', 'speaking_rate', 'pitch', 'phase_init', 'loudness', 'alignment_stats',
-                                               'limiter']
-    assert [r.keyword for r in H.HOST_SETTINGS] == ['output'] and [r.keyword for r in H.MARK_SETTINGS] == ['token_times']
-    assert len(H.TONE_SETTINGS) == 1
-    row = H.TONE_SETTINGS[0]
-    assert (row.keyword, row.mirror, row.initial) == ('equalizer', '_equalizer', None) and row.check is H.equalizer_setting
+    keys = [r.keyword for r in H.SETTINGS]
+    row = H.SETTINGS[-1]                                      # the last row: set last, put back first
+    assert (row.keyword, row.mirror, row.initial, row.host_only) == ('equalizer', '_equalizer', None, False) and row.check is H.equalizer_setting
+    assert keys[-2:] == ['compressor', 'equalizer']
     assert no_device_engine()._equalizer is None
 
 
 def test_the_keyword_is_set_last_and_put_back_first():
-    """the row of TONE_SETTINGS around a call, on a library that records its calls (as tests/test_settings_host.py holds the first
+    """the last row of SETTINGS around a call, on a library that records its calls (as tests/test_settings_host.py holds the first
     seven rows and tests/test_limiter_host.py the eighth)"""
     import test_settings_host as S
     H = pkg('_hip')
@@ -355,17 +353,17 @@ def test_the_keyword_is_threaded_through_the_helpers_and_the_command_line():
     inf, serve = pkg('tacotron.inference'), pkg('tacotron.serve')
     H = pkg('_hip')
     for fn in (H.Engine.synthesize, H.Engine.synthesize_host, inf.synthesize_batch, inf.synthesize_stream, inf.synthesize_sentences, inf.synthesize_text,
-               inf.synthesize_texts, inf.synthesize_marked, serve.serve, serve.post_process_spectrograms, inf.SynthSettings.of):
+               inf.synthesize_texts, inf.synthesize_marked, serve.serve, serve.post_process_spectrograms, inf.SynthSettings):
         assert inspect.signature(fn).parameters['equalizer'].default is None, fn
-    assert inf.TONE_KEYWORDS == ('equalizer',) and inf.SETTING_KEYWORDS[-1] == 'equalizer'
+    assert inf.SETTING_KEYWORDS[-1] == 'equalizer'
     hp = pkg('tacotron.params').model_params
-    s = inf.SynthSettings.of(hp, equalizer='telephony', limiter=0.5)
+    s = inf.SynthSettings(hp, equalizer='telephony', limiter=0.5)
     assert s.equalizer == ('profile', 'telephony') and s.engine_keywords()['equalizer'] == s.keywords()['equalizer'] == s.host_keywords()['equalizer'] == s.equalizer
-    assert inf.SynthSettings.of(hp).equalizer is None and inf.SynthSettings(hp).equalizer is None
-    assert inf.SynthSettings.of(hp).engine_keywords()['equalizer'] is None
+    assert inf.SynthSettings(hp).equalizer is None and inf.SynthSettings(hp).equalizer is None
+    assert inf.SynthSettings(hp).engine_keywords()['equalizer'] is None
     for bad in ('phone', [('lowpass', 0.6 * hp.sampling_rate)], np.zeros((2, 4))):      # refused before a model is made
         with pytest.raises(ValueError):
-            inf.SynthSettings.of(hp, equalizer=bad)
+            inf.SynthSettings(hp, equalizer=bad)
         with pytest.raises(ValueError):
             inf.synthesize_sentences(['x'], '/nonexistent/weights', out_dir='/nonexistent', equalizer=bad)
         with pytest.raises(ValueError):
@@ -400,11 +398,11 @@ def test_the_finishing_tail_runs_the_equaliser_behind_the_peak_normalisation_and
                                  (dict(equalizer='warm', loudness=-20.0, limiter=0.5), True, ['equalize', 'loudness_normalize', 'limit']),
                                  (dict(loudness=-20.0), True, ['loudness_normalize']), (dict(), True, ['peak_normalize'])):
         eng = Eng()
-        inf.finishing_tail('test', inf.SynthSettings.of(hp, **settings), T.SR)(eng, rows, held, peak_normalize=peak)
+        inf.finishing_tail('test', inf.SynthSettings(hp, **settings), T.SR)(eng, rows, held, peak_normalize=peak)
         names = [name for name, _n in eng.calls if name in ('peak_normalize', 'equalize', 'loudness_normalize', 'limit')]
         assert names == want, (settings, names)
         if 'equalize' in want:
             assert dict(eng.calls)['equalize'] == held.tolist()
             assert np.array_equal(eng.kept['equalize']['sections'], pkg('_hip').equalizer_profile(settings['equalizer'], T.SR))
     with pytest.raises(ValueError, match='bright'):
-        inf.finishing_tail('test', inf.SynthSettings.of(None, equalizer='bright'), 8000)
+        inf.finishing_tail('test', inf.SynthSettings(None, equalizer='bright'), 8000)

@@ -18,7 +18,8 @@ BAD = dict(momentum=dict(momentum=2.0), stop_at_silence_db=dict(stop_at_silence_
            pitch=dict(pitch=3.0), phase_init=dict(phase_init='guess'), loudness=dict(loudness=float('nan')),
            check_alignment=dict(check_alignment=True, momentum=2.0),   # (any value switches it on: refused for the momentum beside it)
            pitch_semitones=dict(pitch_semitones=30.0), limiter=dict(limiter=float('nan')), output=dict(output='mp3'),
-           marks=dict(marks='syllable'), marks_max_jump=dict(marks_max_jump=0))
+           marks=dict(marks='syllable'), marks_max_jump=dict(marks_max_jump=0), watermark=dict(watermark='key'),
+           compressor=dict(compressor='loud'), equalizer=dict(equalizer='phone'))
 IDS = np.ones((2, 5), np.int32)
 LIN = np.zeros((2, 40, 1025), np.float32)
 NOWHERE = '/nonexistent/weights'

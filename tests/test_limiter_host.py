@@ -128,7 +128,10 @@ def test_symbols_and_the_record():
     assert ctypes.sizeof(H.TtsLimitStats) == 16 == H.LIMIT_RECORD.itemsize
     assert [(n, H.LIMIT_RECORD.fields[n][1]) for n in H.LIMIT_RECORD.names] == [('over', 0), ('limited', 4), ('min_gain', 8)]
     assert (H.TtsLimitStats.over.offset, H.TtsLimitStats.limited.offset, H.TtsLimitStats.min_gain.offset) == (0, 4, 8)
-    assert H.SETTINGS[-1].keyword == 'limiter' and H.SETTINGS[-1].mirror == '_limiter' and H.SETTINGS[-1].initial is None and len(H.SETTINGS) == 8
+    keys = [r.keyword for r in H.SETTINGS]
+    row = H.SETTINGS[keys.index('limiter')]
+    assert (row.mirror, row.initial, row.host_only) == ('_limiter', None, False) and row.check is H.limiter_setting
+    assert keys[keys.index('limiter') - 1:keys.index('limiter') + 2] == ['alignment_stats', 'limiter', 'output']
     assert no_device_engine()._limiter is None
 
 

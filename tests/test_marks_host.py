@@ -194,7 +194,10 @@ TT = (('tts_set_token_times', (1, 3, 2)), ('tts_set_token_times', (0, 0, 4)))
 @pytest.mark.parametrize('method', sorted(CALLS))
 def test_off_makes_no_new_call_and_on_is_applied_last_and_put_back_first(eng, method):   # noqa: F811
     H = pkg('_hip')
-    assert len(H.SETTINGS) == 8 and [r.keyword for r in H.HOST_SETTINGS] == ['output'] and [r.keyword for r in H.MARK_SETTINGS] == ['token_times']
+    keys = [r.keyword for r in H.SETTINGS]
+    row = H.SETTINGS[keys.index('token_times')]
+    assert (row.mirror, row.initial, row.host_only) == ('_token_times', H.TOKEN_TIMES_OFF, False) and row.check is H.token_times_setting
+    assert keys[keys.index('token_times') - 1:keys.index('token_times') + 2] == ['output', 'token_times', 'watermark']
     run(eng, method, **ALL)                                   # the pinned order of tests/test_settings_host.py, unchanged
     assert eng.lib.trace() == [SET[k][0] for k in ORDER] + [CALLS[method]] + [SET[k][1] for k in reversed(ORDER)]
     del eng.lib.calls[:]

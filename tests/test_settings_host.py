@@ -71,6 +71,13 @@ def run(e, method, **keywords):
     return getattr(e, method)(np.ones((2, 5), np.int32), *SYN, **keywords)
 
 
+def test_the_one_table_has_every_keyword_in_the_order_it_is_applied_in():
+    H = pkg('_hip')
+    assert [row.keyword for row in H.SETTINGS] == list(ORDER) + ['limiter', 'output', 'token_times', 'watermark', 'compressor', 'equalizer']
+    assert len({row.mirror for row in H.SETTINGS}) == 13 and [row.keyword for row in H.SETTINGS if row.host_only] == ['output']
+    assert tuple(row.mirror for row in H.SETTINGS[:7]) == MIRRORS and tuple(row.initial for row in H.SETTINGS[:7]) == INITIAL
+
+
 @pytest.mark.parametrize('method', sorted(CALLS))
 def test_no_keyword_no_setter(eng, method):
     run(eng, method)

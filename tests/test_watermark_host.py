@@ -184,16 +184,17 @@ def test_the_engine_refuses_before_the_library_is_touched():
 
 
 # ---------------------------------------------------------------------------------------------- the settings machinery
-def test_the_table_of_its_own():
+def test_the_watermark_row_of_the_settings_table():
     H = pkg('_hip')
-    assert len(H.WATERMARK_SETTINGS) == 1 and len(H.DYNAMICS_SETTINGS) == 1 and len(H.TONE_SETTINGS) == 1
-    row = H.WATERMARK_SETTINGS[0]
-    assert (row.keyword, row.mirror, row.initial) == ('watermark', '_watermark', None) and row.check is H.watermark_setting
+    keys = [r.keyword for r in H.SETTINGS]
+    row = H.SETTINGS[keys.index('watermark')]
+    assert (row.mirror, row.initial, row.host_only) == ('_watermark', None, False) and row.check is H.watermark_setting
+    assert keys[keys.index('watermark') - 1:] == ['token_times', 'watermark', 'compressor', 'equalizer']
     assert no_device_engine()._watermark is None
 
 
 def test_the_keyword_is_set_behind_the_timing_marks_and_ahead_of_the_compressor():
-    """the row of WATERMARK_SETTINGS around a call, on a library that records its calls (tests/test_settings_host.py)"""
+    """the ``watermark`` row of SETTINGS around a call, on a library that records its calls (tests/test_settings_host.py)"""
     import test_settings_host as S
     H = pkg('_hip')
     eng = no_device_engine()
@@ -238,15 +239,15 @@ def test_the_keyword_is_threaded_through_the_helpers_and_the_command_lines():
     for fn in (H.Engine.synthesize, H.Engine.synthesize_host, inf.synthesize_batch, inf.synthesize_stream, inf.synthesize_sentences, inf.synthesize_text,
                inf.synthesize_texts, inf.synthesize_marked, inf.synthesize_marked_sentences, serve.serve, serve.post_process_spectrograms):
         assert inspect.signature(fn).parameters['watermark'].default is None, fn
-    assert inf.WATERMARK_KEYWORDS == ('watermark',) and inf.SETTING_KEYWORDS[-3:] == ('watermark', 'compressor', 'equalizer')
+    assert inf.SETTING_KEYWORDS[-3:] == ('watermark', 'compressor', 'equalizer')
     hp = pkg('tacotron.params').model_params
-    s = inf.SynthSettings.of(hp, watermark=(7, 3), limiter=0.5)
+    s = inf.SynthSettings(hp, watermark=(7, 3), limiter=0.5)
     assert s.watermark == (7, 3, 16, 8, 64, 0.02)
     assert s.engine_keywords()['watermark'] == s.keywords()['watermark'] == s.host_keywords()['watermark'] == s.watermark
-    assert inf.SynthSettings.of(hp).watermark is None and inf.SynthSettings(hp).watermark is None
+    assert inf.SynthSettings(hp).watermark is None and inf.SynthSettings(hp).watermark is None
     for bad in ('key', (7, 0, 16, 7), np.zeros((2, 4))):                 # refused before a model is made
         with pytest.raises(ValueError):
-            inf.SynthSettings.of(hp, watermark=bad)
+            inf.SynthSettings(hp, watermark=bad)
         with pytest.raises(ValueError):
             inf.synthesize_sentences(['x'], '/nonexistent/weights', out_dir='/nonexistent', watermark=bad)
         with pytest.raises(ValueError):
@@ -302,11 +303,11 @@ def test_the_finishing_tail_marks_behind_the_compressor_and_ahead_of_the_loudnes
                                   ['equalize', 'compress', 'watermark_embed', 'loudness_normalize', 'limit']),
                                  (dict(compressor='speech', loudness=-20.0), True, ['compress', 'loudness_normalize'])):
         eng = Eng()
-        inf.finishing_tail('test', inf.SynthSettings.of(hp, **settings), T.SR)(eng, rows, held, peak_normalize=peak)
+        inf.finishing_tail('test', inf.SynthSettings(hp, **settings), T.SR)(eng, rows, held, peak_normalize=peak)
         names = [name for name, _n in eng.calls if name in stages]
         assert names == want, (settings, names)
         if 'watermark_embed' in want:
             assert dict(eng.calls)['watermark_embed'] == held.tolist()
             assert eng.kept['watermark_embed']['watermark'] == pkg('_hip').watermark_setting(settings['watermark'])
     # with the setting off the tail runs on engines that have no such method
-    inf.finishing_tail('test', inf.SynthSettings.of(hp, loudness=-20.0, limiter=0.5), T.SR)(T.TailEngine(), rows, held, peak_normalize=True)
+    inf.finishing_tail('test', inf.SynthSettings(hp, loudness=-20.0, limiter=0.5), T.SR)(T.TailEngine(), rows, held, peak_normalize=True)
